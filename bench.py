@@ -7,7 +7,12 @@ traffic, with the Ajtai matrix, the CCS and both witnesses already resident in H
 `bench_e2e_prover`, benches/utils.rs:619-680, which also sets everything up outside the timed closure and clones the
 transcript per iteration).  Synthetic inputs: latticefold_amd/workload.py.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C4]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C4] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step, ...).  --full adds everything else the bench
+measures or checks after the timed steps: `roofline` (kernels, phases, traffic from the committed profiles), the comparison of the last proof with
+the oracle-only fixture, and the extra keys `ajtai`, `ivc`, `shard_model`, `lfplus`, `cpu_baseline` (the --no-* options / --chain 0 drop single ones).
+--dump-outputs DIR writes what the last timed step returned to its caller (step_outputs, dump_outputs) for comparing two builds output for output.
 
 N = 1: one prover on one GPU ("scaling": "none").  N > 1: one process per GPU (torch.distributed for rendezvous, barrier and the
 max-over-ranks clock); by default ONE fold stream is sharded over the N GPUs (BASELINE configs[3]: witness columns / table rows split by
@@ -416,14 +421,160 @@ def ivc_extra(name, steps, device=0, headline_ms=None, overlap=True):
     return rec
 
 
+def roofline_report(args, wl, world, shard, elapsed, steps_per_s, kstats, timelines, phases_acc):
+    """`roofline` of the line (--full): the dominant kernels of the timed steps (live HIP-event timing) against their roofline, the phases of the step
+    and the whole step's HBM traffic from the committed profiles"""
+    E = 192 if wl.ring == "goldilocks" else 288
+    alg = wl.alg_bytes()
+    # dominant kernels, live HIP-event timing on the library's stream (lf_last_kernel_stats)
+    fr_ms = sum(k["fold_round_ms"] for k in kstats)
+    fr_n = sum(k["fold_round_launches"] for k in kstats)
+    aj_ms = sum(k["ajtai_ms"] for k in kstats)
+    aj_n = sum(k["ajtai_launches"] for k in kstats)
+    P_F = 5 + 2 * wl.K * wl.tau
+    fr_bytes = sum(P_F * (wl.m >> i) * E for i in range(wl.s)) / wl.s     # SURVEY 8(d): round i reads P*(N/2^(i-1))*E
+    aj_bytes = (wl.kappa + wl.K - 1) * wl.N * E                              # batched commit: A once + K-1 witnesses
+    kernels = {
+        "k_fold_round(+round1)": {"avg_ms": fr_ms / max(fr_n, 1), "launches_per_step": fr_n / args.steps, "alg_bytes_per_launch": fr_bytes,
+                                  "achieved_GBps": fr_bytes / (fr_ms / max(fr_n, 1) * 1e-3) / 1e9 if fr_ms else 0.0},
+        "k_ajtai": {"avg_ms": aj_ms / max(aj_n, 1), "launches_per_step": aj_n / args.steps, "alg_bytes_per_launch": aj_bytes,
+                    "achieved_GBps": aj_bytes / (aj_ms / max(aj_n, 1) * 1e-3) / 1e9 if aj_ms else 0.0},
+    }
+    # the batched commit is the largest single kernel (two launches per step); the twenty fold-round launches together are of the same order and are
+    # listed next to it in `kernels`.  Fixed choice: the two totals are within a few per cent of each other, so a max() would flip from run to run.
+    i8 = wl.b == 2   # digit-plane commits on the int8 matrix cores (lf_ajtai_i8.hip), both rings
+    dom = "k_ajtai"
+    peak = 8000.0
+    # HBM traffic of the dominant kernel from the PMC passes (collected separately, as rocprofv3 requires; see profiles/)
+    traffic = None
+    try:
+        pmc_path, _ = _prof("pmc", wl.name.lower())
+        pmc = json.load(open(pmc_path))["kernels"]
+        want = "k_ajtai_i8" if i8 else ("bb::" if wl.ring == "babybear" else "") + "k_ajtai"
+        for name, k in pmc.items():
+            base = name.split("<")[0]
+            if (base == want or (i8 and base in (want + "s", want + "x"))) and k["fetch_bytes_max_corrected"] is not None:   # (k_ajtai_i8s / _i8x: the specialised-wave kernels of the 24- / 72-ring)
+                traffic = k["fetch_bytes_max_corrected"] + k["write_bytes_max"]   # per launch like `achieved`: the largest launch (the K-1 batch)
+    except Exception:
+        traffic = None
+    aj_t = aj_ms / max(aj_n, 1) * 1e-3
+    src = "%s (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, tools/gpu_pmc.sh; not re-measured in this run)" % (
+        os.path.relpath(_prof("pmc", wl.name.lower())[0], ROOT) if _prof("pmc", wl.name.lower())[0] else "profiles/: no PMC file")
+    if i8:
+        # The K-1 digit-plane commitments of a decomposition as int8 GEMMs: (NL kappa) x (RD N) bytes of A times (RD N) x (RD planes) digits per launch
+        # (Goldilocks: all 15 planes and 26 rows in one launch; BabyBear: plane groups of 8 + 7).  Useful MACs exclude the padding of the 16-wide MFMA
+        # tiles.  Peak: dense int8 = 2 x the MI355X's dense bf16 rate (2.5 PF -> 5 POP/s; a microbenchmark ceiling of the int8 MFMA is
+        # >= 3.94 POP/s).
+        RD, NL, maxp, maxr = (24, 8, 16, 26) if wl.ring == "goldilocks" else (72, 4, 8, 16)
+        row_chunks = -(-wl.kappa // maxr)
+        lps = aj_n / args.steps if aj_n else 2.0                                         # launches per step (measured): 1 per row chunk and plane group
+        sides_per_launch = 2.0 * -(-(wl.K - 1) // maxp) * row_chunks / lps               # 2 = both decompositions' planes in one launch (paired workgroups)
+        macs = 2 * NL * wl.kappa * RD * (wl.K - 1) * RD * wl.N / lps                     # average per launch
+        a_bytes = NL * wl.kappa * RD * wl.N / row_chunks + sides_per_launch * RD * 4 * wl.N   # A row chunk as bytes (from HBM once per launch) + the int32 planes
+        # SURVEY 8(d)'s own figure for the same launch -- element bytes E, not byte planes: the rows of A this launch streams + the digit-plane
+        # witnesses it commits, (kappa_launch + planes_launch) N E  (= (kappa + K - 1) N E when one launch covers a whole decomposition)
+        bytes_8d = (wl.kappa / row_chunks + 2 * (wl.K - 1) * row_chunks / lps) * wl.N * E
+        kernels["k_ajtai"]["alg_bytes_8d_per_launch"] = bytes_8d
+        kernels["k_ajtai"]["alg_bytes_per_launch"] = a_bytes
+        kernels["k_ajtai"]["achieved_GBps"] = a_bytes / aj_t / 1e9 if aj_ms else 0.0
+        # the instantiation that is launched (lf_ajtai_i8.hip launch_ajtai_i8): the specialised-wave kernels for the 13-row-tile shape of the 24-ring and the
+        # 4-row-tile shape of the 72-ring, the generic one otherwise
+        mt = -(-NL * -(-wl.kappa // row_chunks) // 16)
+        dom = "k_ajtai_i8s<false, true>" if (RD, mt) == (24, 13) else ("k_ajtai_i8x<72, 4, false>" if (RD, mt) == (72, 4) else "k_ajtai_i8")   # (as rocprofv3 prints them)
+        kernels[dom] = kernels.pop("k_ajtai")
+        tops = 2 * macs / aj_t / 1e12 if aj_ms else 0.0
+        gbps_8d = bytes_8d / aj_t / 1e9 if aj_ms else 0.0
+        roof = {"bound": "hbm", "kernel": dom, "achieved": gbps_8d, "peak": peak, "unit": "GB/s", "frac": gbps_8d / peak, "alg_bytes_per_launch": bytes_8d,
+                "frac_note": "THE CONTRACT'S NUMBER: SURVEY 8(d) algorithmic bytes of the batched commit, (kappa + planes) N E per launch, over the live HIP-event "
+                             "duration of the launch and the 8 TB/s HBM peak",
+                "traffic": traffic, "traffic_source": src,
+                "mfma": {"achieved": tops, "peak": 5000.0, "unit": "TOP/s (int8, 2 ops per MAC)", "frac": tops / 5000.0, "flops_per_launch": 2 * macs,
+                         "note": "the kernel is an exact int8 GEMM on v_mfma_i32_16x16x64_i8; peak = 2 x the dense bf16 rate of the guide (it lists no int8 figure; "
+                                 "its microbenchmark ceiling is 3.94 POP/s)"},
+                "hbm_8d": {"achieved_GBps": gbps_8d, "peak": peak, "frac": gbps_8d / peak, "alg_bytes_per_launch": bytes_8d, "note": "= achieved / peak / frac above (kept for readers of earlier rounds' lines)"},
+                "hbm": {"achieved_GBps": kernels[dom]["achieved_GBps"], "peak": peak, "frac": kernels[dom]["achieved_GBps"] / peak,
+                        "note": "the same launch with the bytes this implementation really has to move: A once per launch as byte planes (NL kappa RD N) + the int32 witness planes"},
+                "note": "dominant kernel = the batched digit-plane commit, an exact int8 GEMM on v_mfma_i32_16x16x64_i8 (was k_ajtai on the integer multiplier: "
+                        "7.1 ms / launch at C4, 4.0 ms at C3); the rest of the step stays integer-ALU-bound; whole-step algorithmic rate = %.1f GB/s = %.3f of the HBM peak"
+                        % (alg * steps_per_s / world / 1e9, alg * steps_per_s / world / 1e9 / peak),
+                "kernels": kernels}
+    else:
+        # the binding roofline of this path is the integer multiplier (v_mad_*64_*32: 15.7e12 lane-ops/s measured, profiles/r01_microbench.txt):
+        # multiply-accumulates of one batched commit = kappa*(K-1)*N*8 slots, 20 mads each (Toom-3 over F_{p^3}) / 81 (F_{p^9} schoolbook)
+        mads_per_mac = 20 if wl.ring == "goldilocks" else 81
+        aj_mads = wl.kappa * (wl.K - 1) * wl.N * 8 * mads_per_mac
+        alu = {"kernel": "k_ajtai", "unit": "v_mad lane-op/s", "peak": 15.7e12, "achieved": aj_mads / aj_t if aj_ms else 0.0}
+        alu["frac"] = alu["achieved"] / alu["peak"]
+        roof = {"bound": "valu_int64", "bound_note": "neither HBM nor MFMA binds: the kernel is issue-bound on 64-bit integer multiply-adds (integer_alu below); "
+                "achieved / peak / frac are the HBM figures the bench contract asks for", "kernel": dom, "integer_alu": alu, "achieved": kernels[dom]["achieved_GBps"], "peak": peak, "unit": "GB/s",
+                "frac": kernels[dom]["achieved_GBps"] / peak, "traffic": traffic, "traffic_source": src,
+                "note": "integer-ALU-bound path (modular multiply from quarter-rate v_mad_*64_*32); whole-step algorithmic "
+                        "rate = %.1f GB/s = %.3f of peak" % (alg * steps_per_s / world / 1e9, alg * steps_per_s / world / 1e9 / peak),
+                "kernels": kernels}
+    if wl.ring == "goldilocks" and not shard and args.streams == 1:
+        try:
+            ph, ph_src = phase_report(wl.name.lower(), timelines, phases_acc.get("host_transcript", 0.0) / args.steps)
+            roof["phases"] = ph
+            roof["phases_source"] = ph_src
+        except Exception as e:   # a reporting extra: never lose the headline over it
+            roof["phases"] = None
+            roof["phases_source"] = f"failed: {e!r}"
+    try:   # the whole step against the HBM peak with the bytes it REALLY moves: sum over the committed PMC passes (FETCH x 2 + WRITE per launch x launches per step)
+        pmc_path, _ = _prof("pmc", wl.name.lower())
+        st_path, _ = _prof("stats", wl.name.lower())
+        if pmc_path and st_path and not shard and args.streams == 1:
+            import csv
+            pmc = json.load(open(pmc_path))["kernels"]
+            calls = {}
+            for r in csv.DictReader(open(st_path)):
+                calls[r["Name"].replace("void ", "").replace("lf::", "").replace("bb::", "").split("(")[0]] = int(r["Calls"])
+            setup = ("k_ajtai_icrt_pack_i8", "k_ajtai_unpack_i8", "k_fill_ajtai", "k_ajtai<", "k_aos_to_soa", "k_decompose", "k_coef_to_i32")   # matrix install / witness ingest: not per step
+            nsteps = 7.0   # tools/gpu_round.sh profiles 5 timed + 2 warm-up steps
+            tot = sum((v["fetch_bytes_mean_corrected"] + v["write_bytes_mean"]) * calls[k] / nsteps for k, v in pmc.items()
+                      if k in calls and not k.startswith(setup) and v["fetch_bytes_mean_corrected"] is not None)
+            roof["whole_step_traffic"] = {"hbm_bytes_per_step": tot, "achieved_GBps": tot / (elapsed / args.steps) / 1e9, "frac": tot / (elapsed / args.steps) / 1e9 / peak,
+                                          "source": f"{os.path.relpath(pmc_path, ROOT)} x launches of {os.path.relpath(st_path, ROOT)} (committed rocprofv3 passes; bytes not re-measured in this run) over this run's ms_per_step"}
+    except Exception as e:
+        roof["whole_step_traffic"] = {"note": f"failed: {e!r}"}
+    return roof
+
+
+def step_outputs(w0, lc, proof, rows=4096):
+    """What NIFSProver::prove handed its caller in one step: the folded LCCCS and the proof in full, and of the folded witness (f in NTT form, f_coeff,
+    w_ccs) a fixed sample of `rows` rows (seed 0, the same rows in every run).  Frees w0."""
+    import numpy as np
+    try:
+        out = {"lcccs": lc, "proof": proof}
+        for name in ("f", "f_coeff", "w_ccs"):
+            a = getattr(w0, name)
+            pick = np.sort(np.random.default_rng(0).choice(len(a), size=min(rows, len(a)), replace=False))
+            out["folded_witness_" + name] = a[pick]
+        return out
+    finally:
+        w0.free()
+
+
+def dump_outputs(d, arrays):
+    """DIR/<name>.npy for every output.  The words are field elements (uint64); each is written as its 8 little-endian bytes in float32 (last axis),
+    which is exact and makes any difference of one bit a difference of at least 1 in some entry.  About 11 MB at C4, 32 MB at C3 (the 64 MB a dump may take)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype="<u8")
+        np.save(os.path.join(d, name + ".npy"), a.view(np.uint8).reshape(a.shape + (8,)).astype(np.float32))
+
+
 def _headline_fallback(args, world, wl, elapsed, shard, lfplus):
     """the metric line without the reporting extras (used only when the sharded LatticeFold+ extra hangs: the process group is unusable afterwards)"""
     sps = (1 if shard else world) * args.steps / elapsed
-    return {"metric": "folding-prover steps/sec (one NIFSProver::prove per step), " + ("GoldilocksRingNTT" if wl.ring == "goldilocks" else "BabyBearRingNTT"), "value": sps,
+    line = {"metric": "folding-prover steps/sec (one NIFSProver::prove per step), " + ("GoldilocksRingNTT" if wl.ring == "goldilocks" else "BabyBearRingNTT"), "value": sps,
             "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
             "scaling": "strong" if shard else "weak", "vs_baseline": None, "dtype": "u64" if wl.ring == "goldilocks" else "u32 (31-bit Montgomery)", "data": "synthetic",
-            "config": {"workload": wl.name, "parallelism": ("shard" if shard else "replicas") + f" x{world}"}, "roofline": None, "cpu_baseline": None, "lfplus": lfplus,
+            "config": {"workload": wl.name, "parallelism": ("shard" if shard else "replicas") + f" x{world}"},
             "note": "reporting extras dropped: the sharded LatticeFold+ extra did not complete"}
+    if args.full:      # (the keys of the extras exist in a --full line only)
+        line.update(roofline=None, cpu_baseline=None, lfplus=lfplus)
+    return line
 
 
 def _bcast_id(plus, dist, rank):
@@ -438,17 +589,17 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default=os.environ.get("LF_WORKLOAD", "C4"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the extra key `cpu_baseline`")
     ap.add_argument("--ccs", choices=["r1cs", "multi4", "multi16", "deg3"], default="r1cs",
                     help="constraint-system shape (workload.make_workload): the reference bench's 1-nnz R1CS (default, the metric's configuration); multi4 / multi16 = 4 / 16 entries "
                          "per row at pseudo-random columns, ring-valued entries in C (general CSR SpMV, arith/utils.rs:52-65); deg3 = the reference's degree-three CCS "
                          "(arith/ccs.rs:14-43: t = 4, S = {{0,1,2},{3}})")
-    ap.add_argument("--no-ajtai", action="store_true", help="skip the reference's Ajtai bench rows (commit_ntt at benches/config.toml:715 / :670; an extra key, not part of the metric)")
-    ap.add_argument("--chain", type=int, default=8, help="steps of the chained-folding extra key `ivc` (every step ingests and commits a new witness and folds it into the "
+    ap.add_argument("--no-ajtai", action="store_true", help="with --full: skip the reference's Ajtai bench rows (commit_ntt at benches/config.toml:715 / :670; an extra key, not part of the metric)")
+    ap.add_argument("--chain", type=int, default=8, help="with --full: steps of the chained-folding extra key `ivc` (every step ingests and commits a new witness and folds it into the "
                                                          "carried accumulator; run for the bench workload and for C2); 0 = skip")
-    ap.add_argument("--no-shard-model", action="store_true", help="skip the extra key `shard_model` (N=1: the predicted per-rank ms of --gpus 2/4/8 --parallelism shard, "
+    ap.add_argument("--no-shard-model", action="store_true", help="with --full: skip the extra key `shard_model` (N=1: the predicted per-rank ms of --gpus 2/4/8 --parallelism shard, "
                                                                   "latticefold_amd/shard_model.py: rank 0 measured with the model transport + assumed xGMI terms)")
-    ap.add_argument("--no-lfplus", action="store_true", help="skip the LatticeFold+ PlusProver::prove timing (an extra key, not part of the metric)")
+    ap.add_argument("--no-lfplus", action="store_true", help="with --full: skip the LatticeFold+ PlusProver::prove timing (an extra key, not part of the metric)")
     ap.add_argument("--streams", type=int, default=1,
                     help="opt-in throughput mode: S independent fold streams per GPU (S contexts driven by S host threads); every "
                          "stream does --steps steps, value counts all of them.  Default 1 = one prover, latency-honest ms_per_step")
@@ -457,6 +608,11 @@ def main():
                          "index-sharded sumcheck rounds and evaluations, RCCL exchanges; strong scaling, SURVEY 8e) -- the default ('auto') "
                          "for N>1, which also reports the replicas rate as an extra key; 'replicas' = one independent fold stream per GPU "
                          "(weak scaling) only")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the reporting extras after the timed steps: roofline, the oracle-fixture comparison, ajtai, ivc, shard_model, lfplus, "
+                         "cpu_baseline (off by default: a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (folded LCCCS, proof, a fixed sample of the folded witness) to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -511,9 +667,12 @@ def main():
         tr0 = api.PoseidonTranscript(ring=wl.ring)
         last = {}
 
-        def step():
+        def step(keep=False):
             lc, w0, proof = api.NIFSProver.prove(ctx, acc, wit, cccs, wit, tr0.clone())
-            w0.free()
+            if keep:      # (--dump-outputs: the last timed step's witness is read back after the clock stops)
+                last["w0"] = w0
+            else:
+                w0.free()
             last["lc"], last["proof"] = lc, proof
             return proof
 
@@ -561,8 +720,8 @@ def main():
         threads = [threading.Thread(target=run_stream, args=(st, args.steps)) for st in extra]
         for th in threads:
             th.start()
-        for _ in range(args.steps):
-            step()
+        for i in range(args.steps):
+            step(keep=dump and i == args.steps - 1)
             for k, v in ctx.phase_ms().items():
                 phases_acc[k] = phases_acc.get(k, 0.0) + v
             kstats.append(ctx.kernel_stats())
@@ -575,6 +734,8 @@ def main():
             tmax = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local_rank}" if backend == "nccl" else "cpu")
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = float(tmax.item())
+        if "w0" in last:
+            outputs[shard] = step_outputs(last.pop("w0"), last["lc"], last["proof"])
         ex = None
         if shard:
             n_ex, us_tot, us_max = ctx.dist_stats()
@@ -583,7 +744,7 @@ def main():
                           "round trip for the host transport)"}
         # the proof of the LAST TIMED step against the committed oracle-only fixture of this workload (seed 0: rank 0 of a replica run, every rank of a sharded one)
         fixture_info.clear()
-        if (shard or rank == 0) and last:
+        if args.full and (shard or rank == 0) and last:
             try:
                 import hashlib
                 fkey = wl.name if args.ccs == "r1cs" else f"{wl.name}/{args.ccs}"
@@ -597,7 +758,7 @@ def main():
                 fixture_info.update(matches_oracle_fixture=None, fixture=f"not checked: {e!r}")
         free_b, total_b = ctx.device_memory()
         mem_info["hbm_in_use_gib"] = (total_b - free_b) / 2.0 ** 30   # whole device, this process being its only user: context, witnesses, torch's own few MB
-        if world == 1 and not shard and not args.no_ajtai:
+        if args.full and world == 1 and not shard and not args.no_ajtai:
             # Witness::commit (arith.rs:357-362) of the bench's own resident witness: the cm_i every fresh instance of a real chain needs.  After the timed loop
             # (a reported extra); device side of the call (HIP events: digit pass of the int32 planes, int8 contraction, recombination, CRT)
             try:
@@ -619,6 +780,8 @@ def main():
 
     mode = args.parallelism
     mem_info, fixture_info = {}, {}
+    dump = args.dump_outputs is not None and rank == 0
+    outputs = {}      # shard flag of the measurement -> arrays of its last timed step (--dump-outputs)
     shard = world > 1 and mode in ("auto", "shard")
     replicas_extra, shard_note = None, None
     if shard:
@@ -667,15 +830,19 @@ def main():
             if rank == 0:
                 line = _headline_fallback(args, world, res_r[0], res_r[1], False, None)
                 line["note"] = shard_note
+                if dump:
+                    dump_outputs(args.dump_outputs, outputs[False])
                 print(json.dumps(line), flush=True)
             os._exit(0)      # the communicator may be unusable: no further collective, no destroy_process_group
     else:
         wl, elapsed, phases_acc, kstats, exch, timelines = measure(False)
+    if dump:
+        dump_outputs(args.dump_outputs, outputs[shard])
 
     # BASELINE configs[4]: the 2^20-row LatticeFold+ prove sharded over the same GPUs (an extra key; every rank takes part).  A watchdog bounds it: an exchange
     # that never completes must not cost the headline -- the ranks then drop the key and go on.
     lfplus_sharded = None
-    if world > 1 and not args.no_lfplus:
+    if args.full and world > 1 and not args.no_lfplus:
         box = {}
 
         def _run():
@@ -693,94 +860,8 @@ def main():
             os._exit(0)
 
     if rank == 0:
-        E = 192 if wl.ring == "goldilocks" else 288
         steps_per_s = (1 if shard else world) * max(1, args.streams) * args.steps / elapsed
         alg = wl.alg_bytes()
-        # dominant kernels, live HIP-event timing on the library's stream (lf_last_kernel_stats)
-        fr_ms = sum(k["fold_round_ms"] for k in kstats)
-        fr_n = sum(k["fold_round_launches"] for k in kstats)
-        aj_ms = sum(k["ajtai_ms"] for k in kstats)
-        aj_n = sum(k["ajtai_launches"] for k in kstats)
-        P_F = 5 + 2 * wl.K * wl.tau
-        fr_bytes = sum(P_F * (wl.m >> i) * E for i in range(wl.s)) / wl.s     # round i reads P*(N/2^(i-1))*E
-        aj_bytes = (wl.kappa + wl.K - 1) * wl.N * E                              # batched commit: A once + K-1 witnesses
-        kernels = {
-            "k_fold_round(+round1)": {"avg_ms": fr_ms / max(fr_n, 1), "launches_per_step": fr_n / args.steps, "alg_bytes_per_launch": fr_bytes,
-                                      "achieved_GBps": fr_bytes / (fr_ms / max(fr_n, 1) * 1e-3) / 1e9 if fr_ms else 0.0},
-            "k_ajtai": {"avg_ms": aj_ms / max(aj_n, 1), "launches_per_step": aj_n / args.steps, "alg_bytes_per_launch": aj_bytes,
-                        "achieved_GBps": aj_bytes / (aj_ms / max(aj_n, 1) * 1e-3) / 1e9 if aj_ms else 0.0},
-        }
-        # the batched commit is the largest single kernel (two launches per step); the twenty fold-round launches together are of the same order and are
-        # listed next to it in `kernels`.  Fixed choice: the two totals are within a few per cent of each other, so a max() would flip from run to run.
-        i8 = wl.b == 2   # digit-plane commits on the int8 matrix cores (lf_ajtai_i8.hip), both rings
-        dom = "k_ajtai"
-        peak = 8000.0
-        # HBM traffic of the dominant kernel from the PMC passes (collected separately, as rocprofv3 requires; see profiles/)
-        traffic = None
-        try:
-            pmc_path, _ = _prof("pmc", wl.name.lower())
-            pmc = json.load(open(pmc_path))["kernels"]
-            want = "k_ajtai_i8" if i8 else ("bb::" if wl.ring == "babybear" else "") + "k_ajtai"
-            for name, k in pmc.items():
-                base = name.split("<")[0]
-                if (base == want or (i8 and base in (want + "s", want + "x"))) and k["fetch_bytes_max_corrected"] is not None:   # (k_ajtai_i8s / _i8x: the specialised-wave kernels of the 24- / 72-ring)
-                    traffic = k["fetch_bytes_max_corrected"] + k["write_bytes_max"]   # per launch like `achieved`: the largest launch (the K-1 batch)
-        except Exception:
-            traffic = None
-        aj_t = aj_ms / max(aj_n, 1) * 1e-3
-        src = "%s (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, tools/gpu_pmc.sh; not re-measured in this run)" % (
-            os.path.relpath(_prof("pmc", wl.name.lower())[0], ROOT) if _prof("pmc", wl.name.lower())[0] else "profiles/: no PMC file")
-        if i8:
-            # The K-1 digit-plane commitments of a decomposition as int8 GEMMs: (NL kappa) x (RD N) bytes of A times (RD N) x (RD planes) digits per launch
-            # (Goldilocks: all 15 planes and 26 rows in one launch; BabyBear: plane groups of 8 + 7).  Useful MACs exclude the padding of the 16-wide MFMA
-            # tiles.  Peak: dense int8 = 2 x the dense bf16 rate of /opt/skills/guides/MI355X_MICROARCH.md (2.5 PF -> 5 POP/s; its microbenchmark
-            # ceiling is >= 3.94 POP/s).
-            RD, NL, maxp, maxr = (24, 8, 16, 26) if wl.ring == "goldilocks" else (72, 4, 8, 16)
-            row_chunks = -(-wl.kappa // maxr)
-            lps = aj_n / args.steps if aj_n else 2.0                                         # launches per step (measured): 1 per row chunk and plane group
-            sides_per_launch = 2.0 * -(-(wl.K - 1) // maxp) * row_chunks / lps               # 2 = both decompositions' planes in one launch (paired workgroups)
-            macs = 2 * NL * wl.kappa * RD * (wl.K - 1) * RD * wl.N / lps                     # average per launch
-            a_bytes = NL * wl.kappa * RD * wl.N / row_chunks + sides_per_launch * RD * 4 * wl.N   # A row chunk as bytes (from HBM once per launch) + the int32 planes
-            # SURVEY 8(d)'s own figure for the same launch -- element bytes E, not byte planes: the rows of A this launch streams + the digit-plane
-            # witnesses it commits, (kappa_launch + planes_launch) N E  (= (kappa + K - 1) N E when one launch covers a whole decomposition)
-            bytes_8d = (wl.kappa / row_chunks + 2 * (wl.K - 1) * row_chunks / lps) * wl.N * E
-            kernels["k_ajtai"]["alg_bytes_8d_per_launch"] = bytes_8d
-            kernels["k_ajtai"]["alg_bytes_per_launch"] = a_bytes
-            kernels["k_ajtai"]["achieved_GBps"] = a_bytes / aj_t / 1e9 if aj_ms else 0.0
-            # the instantiation that is launched (lf_ajtai_i8.hip launch_ajtai_i8): the specialised-wave kernels for the 13-row-tile shape of the 24-ring and the
-            # 4-row-tile shape of the 72-ring, the generic one otherwise
-            mt = -(-NL * -(-wl.kappa // row_chunks) // 16)
-            dom = "k_ajtai_i8s<false, true>" if (RD, mt) == (24, 13) else ("k_ajtai_i8x<72, 4, false>" if (RD, mt) == (72, 4) else "k_ajtai_i8")   # (as rocprofv3 prints them)
-            kernels[dom] = kernels.pop("k_ajtai")
-            tops = 2 * macs / aj_t / 1e12 if aj_ms else 0.0
-            gbps_8d = bytes_8d / aj_t / 1e9 if aj_ms else 0.0
-            roof = {"bound": "hbm", "kernel": dom, "achieved": gbps_8d, "peak": peak, "unit": "GB/s", "frac": gbps_8d / peak, "alg_bytes_per_launch": bytes_8d,
-                    "frac_note": "THE CONTRACT'S NUMBER: SURVEY 8(d) algorithmic bytes of the batched commit, (kappa + planes) N E per launch, over the live HIP-event "
-                                 "duration of the launch and the 8 TB/s HBM peak",
-                    "traffic": traffic, "traffic_source": src,
-                    "mfma": {"achieved": tops, "peak": 5000.0, "unit": "TOP/s (int8, 2 ops per MAC)", "frac": tops / 5000.0, "flops_per_launch": 2 * macs,
-                             "note": "the kernel is an exact int8 GEMM on v_mfma_i32_16x16x64_i8; peak = 2 x the dense bf16 rate of the guide (it lists no int8 figure; "
-                                     "its microbenchmark ceiling is 3.94 POP/s)"},
-                    "hbm_8d": {"achieved_GBps": gbps_8d, "peak": peak, "frac": gbps_8d / peak, "alg_bytes_per_launch": bytes_8d, "note": "= achieved / peak / frac above (kept for readers of earlier rounds' lines)"},
-                    "hbm": {"achieved_GBps": kernels[dom]["achieved_GBps"], "peak": peak, "frac": kernels[dom]["achieved_GBps"] / peak,
-                            "note": "the same launch with the bytes this implementation really has to move: A once per launch as byte planes (NL kappa RD N) + the int32 witness planes"},
-                    "note": "dominant kernel = the batched digit-plane commit, an exact int8 GEMM on v_mfma_i32_16x16x64_i8 (was k_ajtai on the integer multiplier: "
-                            "7.1 ms / launch at C4, 4.0 ms at C3); the rest of the step stays integer-ALU-bound; whole-step algorithmic rate = %.1f GB/s = %.3f of the HBM peak"
-                            % (alg * steps_per_s / world / 1e9, alg * steps_per_s / world / 1e9 / peak),
-                    "kernels": kernels}
-        else:
-            # the binding roofline of this path is the integer multiplier (v_mad_*64_*32: 15.7e12 lane-ops/s measured, profiles/r01_microbench.txt):
-            # multiply-accumulates of one batched commit = kappa*(K-1)*N*8 slots, 20 mads each (Toom-3 over F_{p^3}) / 81 (F_{p^9} schoolbook)
-            mads_per_mac = 20 if wl.ring == "goldilocks" else 81
-            aj_mads = wl.kappa * (wl.K - 1) * wl.N * 8 * mads_per_mac
-            alu = {"kernel": "k_ajtai", "unit": "v_mad lane-op/s", "peak": 15.7e12, "achieved": aj_mads / aj_t if aj_ms else 0.0}
-            alu["frac"] = alu["achieved"] / alu["peak"]
-            roof = {"bound": "valu_int64", "bound_note": "neither HBM nor MFMA binds: the kernel is issue-bound on 64-bit integer multiply-adds (integer_alu below); "
-                    "achieved / peak / frac are the HBM figures the bench contract asks for", "kernel": dom, "integer_alu": alu, "achieved": kernels[dom]["achieved_GBps"], "peak": peak, "unit": "GB/s",
-                    "frac": kernels[dom]["achieved_GBps"] / peak, "traffic": traffic, "traffic_source": src,
-                    "note": "integer-ALU-bound path (modular multiply from quarter-rate v_mad_*64_*32); whole-step algorithmic "
-                            "rate = %.1f GB/s = %.3f of peak" % (alg * steps_per_s / world / 1e9, alg * steps_per_s / world / 1e9 / peak),
-                    "kernels": kernels}
         out = {
             "metric": "folding-prover steps/sec (one NIFSProver::prove per step), " + ("GoldilocksRingNTT" if wl.ring == "goldilocks" else "BabyBearRingNTT"),
             "value": steps_per_s,
@@ -800,61 +881,37 @@ def main():
                        "folded_witness": ("Witness::from_f in full inside the timed step (arith.rs:299-313): the folded witness leaves the step as int32 coefficient planes (f_coeff, what the next step reads), "
                                           "f_0 in NTT form and w_ccs, all three on the device (lf_witness_get_f / _get_w_ccs only download)"),
                        "parity": "bit-exact vs in-repo CPU oracle; CRT/digit tables not yet confirmed against stark-rings@886a89f"},
-            "roofline": roof,
             "phases_ms_per_step": {k: v / args.steps for k, v in phases_acc.items()},
         }
         out["config"].update(fixture_info)
-        if wl.ring == "goldilocks" and not shard and args.streams == 1:
-            try:
-                ph, ph_src = phase_report(wl.name.lower(), timelines, phases_acc.get("host_transcript", 0.0) / args.steps)
-                roof["phases"] = ph
-                roof["phases_source"] = ph_src
-            except Exception as e:   # a reporting extra: never lose the headline over it
-                roof["phases"] = None
-                roof["phases_source"] = f"failed: {e!r}"
-        try:   # the whole step against the HBM peak with the bytes it REALLY moves: sum over the committed PMC passes (FETCH x 2 + WRITE per launch x launches per step)
-            pmc_path, _ = _prof("pmc", wl.name.lower())
-            st_path, _ = _prof("stats", wl.name.lower())
-            if pmc_path and st_path and not shard and args.streams == 1:
-                import csv
-                pmc = json.load(open(pmc_path))["kernels"]
-                calls = {}
-                for r in csv.DictReader(open(st_path)):
-                    calls[r["Name"].replace("void ", "").replace("lf::", "").replace("bb::", "").split("(")[0]] = int(r["Calls"])
-                setup = ("k_ajtai_icrt_pack_i8", "k_ajtai_unpack_i8", "k_fill_ajtai", "k_ajtai<", "k_aos_to_soa", "k_decompose", "k_coef_to_i32")   # matrix install / witness ingest: not per step
-                nsteps = 7.0   # tools/gpu_round.sh profiles 5 timed + 2 warm-up steps
-                tot = sum((v["fetch_bytes_mean_corrected"] + v["write_bytes_mean"]) * calls[k] / nsteps for k, v in pmc.items()
-                          if k in calls and not k.startswith(setup) and v["fetch_bytes_mean_corrected"] is not None)
-                roof["whole_step_traffic"] = {"hbm_bytes_per_step": tot, "achieved_GBps": tot / (elapsed / args.steps) / 1e9, "frac": tot / (elapsed / args.steps) / 1e9 / peak,
-                                              "source": f"{os.path.relpath(pmc_path, ROOT)} x launches of {os.path.relpath(st_path, ROOT)} (committed rocprofv3 passes; bytes not re-measured in this run) over this run's ms_per_step"}
-        except Exception as e:
-            roof["whole_step_traffic"] = {"note": f"failed: {e!r}"}
+        if args.full:
+            out["roofline"] = roofline_report(args, wl, world, shard, elapsed, steps_per_s, kstats, timelines, phases_acc)
         if exch is not None:
             out["exchanges"] = exch
         if replicas_extra is not None:
             out["replicas"] = replicas_extra
-        if world == 1 and not args.no_ajtai:
+        if args.full and world == 1 and not args.no_ajtai:
             out["ajtai"] = ajtai_extra()
             if "witness_commit" in mem_info:
                 out["ajtai"].append(mem_info["witness_commit"])
-        if world == 1 and args.chain > 0 and args.streams == 1 and args.ccs == "r1cs":
+        if args.full and world == 1 and args.chain > 0 and args.streams == 1 and args.ccs == "r1cs":
             out["ivc"] = [ivc_extra(wl.name, args.chain, local_rank, elapsed / args.steps * 1e3), ivc_extra(wl.name, args.chain, local_rank, elapsed / args.steps * 1e3, overlap=False)]
             if wl.name != "C2" and wl.ring == "goldilocks":
                 out["ivc"].append(ivc_extra("C2", args.chain, local_rank))
-        if world == 1 and not args.no_shard_model and args.streams == 1 and args.ccs == "r1cs" and wl.ring == "goldilocks" and wl.m >= (1 << 18):   # (a step worth sharding)
+        if args.full and world == 1 and not args.no_shard_model and args.streams == 1 and args.ccs == "r1cs" and wl.ring == "goldilocks" and wl.m >= (1 << 18):   # (a step worth sharding)
             try:   # the prediction the driver's SCALE run (strong scaling of ONE fold stream) can be checked against
                 from latticefold_amd.shard_model import model_summary
                 out["shard_model"] = model_summary(wl, (2, 4, 8), steps=4, warmup=2, device=local_rank, base_ms=elapsed / args.steps * 1e3)
             except Exception as e:
                 out["shard_model"] = {"note": f"failed: {e!r}"}
-        if world == 1 and not args.no_lfplus:
+        if args.full and world == 1 and not args.no_lfplus:
             try:
                 out["lfplus"] = lfplus_extra()
             except Exception as e:   # a reported extra, outside the timed region
                 out["lfplus"] = {"op": "PlusProver::prove", "ms": None, "note": f"failed: {e!r}"}
         if world > 1 and lfplus_sharded is not None:
             out["lfplus"] = lfplus_sharded
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(wl)
             except Exception as e:  # the baseline is a reported extra; never lose the GPU number over it

@@ -22,7 +22,7 @@ def test_bench_two_ranks_one_gpu(mode, workload):
     env = dict(os.environ, LF_FORCE_DEVICE="0", LF_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--workload", workload, "--parallelism", mode, "--no-lfplus"]
+           "--workload", workload, "--parallelism", mode, "--no-lfplus", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -46,7 +46,7 @@ def test_bench_default_for_n_gpus_is_the_sharded_config():
     env = dict(os.environ, LF_FORCE_DEVICE="0", LF_DIST_BACKEND="gloo", LF_LFPLUS_WORKLOADS="P16")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--workload", "T14"]
+           "--workload", "T14", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

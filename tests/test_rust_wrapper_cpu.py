@@ -1,16 +1,16 @@
 """bindings/latticefold-hip (the safe Rust layer over the generated -sys crate) cannot be compiled in the build image (no Rust toolchain).  What can be checked
 here: it is there as a crate (Cargo.toml, build.rs of the -sys crate linking lfhip), every `sys::` function it calls is a declared and exported symbol, it
-implements the reference's three prover traits and the two transcript traits, and -- against the reference sources where they are present (names only, nothing is
-copied) -- each `prove` has the reference's parameter NAMES and count (nifs/linearization.rs:26-52, nifs/decomposition/structs.rs:48-64,
-nifs/folding/structs.rs:43-70, nifs.rs:48-103), and the methods of AjtaiCommitmentScheme / Witness the path uses exist on HipAjtai / HipWitness."""
+implements the reference's three prover traits and the two transcript traits, and -- against the names recorded from the reference sources in
+tests/golden/reference_signatures.json (names only, nothing is copied; tests/tools/extract_reference_signatures.py) -- each `prove` has the reference's
+parameter NAMES and count (nifs/linearization.rs:26-52, nifs/decomposition/structs.rs:48-64, nifs/folding/structs.rs:43-70, nifs.rs:48-103), and the methods
+of AjtaiCommitmentScheme / Witness the path uses exist on HipAjtai / HipWitness."""
+import json
 import os
 import re
 
-import pytest
-
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 SRC = open(os.path.join(ROOT, "bindings", "latticefold-hip", "src", "lib.rs")).read()
-REF = "/root/reference/crates/latticefold/src"
+REF = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_signatures.json")))
 
 
 def _params(sig):
@@ -72,20 +72,18 @@ def test_wrapper_implements_the_reference_traits():
         assert re.search(r"pub fn " + name + r"\(", SRC), name
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference sources not present on this machine")
 def test_prove_signatures_carry_the_reference_parameter_names():
-    cases = [("nifs/linearization.rs", r"pub trait LinearizationProver<", r"LinearizationProver<NTT, T> for HipLinearizationProver<NTT, T>\s*\{"),
-             ("nifs/decomposition/structs.rs", r"pub trait DecompositionProver<", r"DecompositionProver<NTT, T> for HipDecompositionProver<NTT, T>\s*\{"),
-             ("nifs/folding/structs.rs", r"pub trait FoldingProver<", r"FoldingProver<NTT, T> for HipFoldingProver<NTT, T>\s*\{"),
-             ("nifs.rs", r"impl<NTT: SuitableRing, P: DecompositionParams, T: TranscriptWithShortChallenges<NTT>>\s*NIFSProver<NTT, P, T>\s*\{",
-              r"impl<NTT: SuitableRing, P: DecompositionParams, T: TranscriptWithShortChallenges<NTT>> HipNIFSProver<NTT, P, T>\s*\{")]
-    for rel, ref_pat, my_pat in cases:
-        want = _fn_sig(open(os.path.join(REF, rel)).read(), ref_pat)
+    cases = [("nifs/linearization.rs", r"LinearizationProver<NTT, T> for HipLinearizationProver<NTT, T>\s*\{"),
+             ("nifs/decomposition/structs.rs", r"DecompositionProver<NTT, T> for HipDecompositionProver<NTT, T>\s*\{"),
+             ("nifs/folding/structs.rs", r"FoldingProver<NTT, T> for HipFoldingProver<NTT, T>\s*\{"),
+             ("nifs.rs", r"impl<NTT: SuitableRing, P: DecompositionParams, T: TranscriptWithShortChallenges<NTT>> HipNIFSProver<NTT, P, T>\s*\{")]
+    assert sorted(REF["prove_params"]) == sorted(rel for rel, _ in cases)
+    for rel, my_pat in cases:
+        want = REF["prove_params"][rel]
         got = [p.lstrip("_") for p in _fn_sig(SRC, my_pat)]
         assert got == want, (rel, got, want)
     # the transcript traits: every REQUIRED method of the reference's traits is implemented
-    tr = open(os.path.join(REF, "transcript.rs")).read()
-    required = re.findall(r"\n    fn (\w+)\([^)]*\)[^{;]*;", tr)
+    required = REF["transcript_required_methods"]
     assert set(required) >= {"new", "absorb", "get_challenge", "squeeze_bytes", "get_short_challenge"}
     for name in required:
         assert re.search(r"fn " + name + r"\(", SRC), name

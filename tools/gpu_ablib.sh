@@ -7,7 +7,7 @@ cp $R/$1 /tmp/ab_a.so; cp $R/$2 /tmp/ab_b.so; cp $R/latticefold_amd/liblfhip.so 
 for i in 1 2 3; do
   for v in a b; do
     cp /tmp/ab_$v.so $R/latticefold_amd/liblfhip.so
-    python $R/bench.py --workload $wl --steps 20 --warmup 3 --no-cpu-baseline --no-lfplus --no-ajtai --no-shard-model --chain 0 2>/dev/null | python -c "
+    python $R/bench.py --full --workload $wl --steps 20 --warmup 3 --no-cpu-baseline --no-lfplus --no-ajtai --no-shard-model --chain 0 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); k = d['roofline']['kernels']
 aj = [v for n, v in k.items() if n.startswith('k_ajtai')]

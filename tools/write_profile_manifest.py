@@ -2,7 +2,7 @@
 """Writes <dir>/latest.json: the manifest of ONE profiling round (tag) that bench.py reads for `roofline.traffic`, `roofline.phases[].kernel_ms / hbm_bytes /
 valu_floor_ms` and `whole_step_traffic` -- so those columns can never point at a stale tag by hand.
 
-    python tools/write_profile_manifest.py <tag> [dir]        dir defaults to profiles/ (tools/gpu_round.sh calls it on gpurun_out/ on the GPU box;
+    python tools/write_profile_manifest.py <tag> [dir]        dir defaults to profiles/ (tools/gpu_round.sh calls it on its output folder, $LF_PROFILE_OUT;
                                                               copy the <tag>_* files AND latest.json into profiles/ together)
 
 A kind (pmc / stats / sq) that the round did not produce for a workload is simply absent: bench.py then reports null for it instead of an older file."""
