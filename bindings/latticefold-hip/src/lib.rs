@@ -5,7 +5,7 @@
 //!
 //! | reference (file:line)                                                         | here                                   |
 //! |-------------------------------------------------------------------------------|----------------------------------------|
-//! | `AjtaiCommitmentScheme::{new, rand, commit, commit_ntt, kappa, width}` `commitment/commitment_scheme.rs:17-77` | [`HipAjtai`]            |
+//! | `AjtaiCommitmentScheme::{new, rand, commit, commit_ntt, commit_coeff, decompose_and_commit_coeff, decompose_and_commit_ntt, kappa, width}` `commitment/commitment_scheme.rs:17-113` | [`HipAjtai`] |
 //! | `Witness::{from_w_ccs, from_f, from_f_coeff, commit}` `arith.rs:230-362`        | [`HipWitness`] (device resident)       |
 //! | `PoseidonTranscript` (`Transcript`, `TranscriptWithShortChallenges`) `transcript/poseidon.rs:17-75` | [`HipTranscript`] -- same traits, same challenges |
 //! | `LinearizationProver::prove` `nifs/linearization.rs:26-52`                      | `impl LinearizationProver for HipLinearizationProver` |
@@ -297,6 +297,52 @@ impl<NTT: SuitableRing> HipAjtai<NTT> {
 
     pub fn commit(&self, f: &[NTT]) -> Result<Commitment<NTT>, CommitmentError> {
         self.commit_ntt(f)
+    }
+
+    /// `commit_coeff::<P>(f)` (commitment_scheme.rs:81-87): the commitment of `CRT(f)` from the coefficient form, on the device (no host CRT)
+    pub fn commit_coeff<P: DecompositionParams>(&self, f: Vec<NTT::CoefficientRepresentation>) -> Result<Commitment<NTT>, CommitmentError> {
+        if f.len() != self.n {
+            return Err(CommitmentError::WrongWitnessLength(f.len(), self.n));
+        }
+        let w = flatten(&f);
+        let mut out = vec![0u64; self.kappa * NTT::WORDS];
+        // SAFETY: w holds n elements, out kappa elements
+        let rc = unsafe { sys::lf_ajtai_commit_coeff(self.ctx.raw, w.as_ptr(), self.n, 1, out.as_mut_ptr()) };
+        if rc != sys::LF_OK {
+            return Err(CommitmentError::WrongWitnessLength(f.len(), self.n));
+        }
+        Ok(Commitment::from(unflatten(&out)))
+    }
+
+    /// `decompose_and_commit_coeff::<P>(f)` (commitment_scheme.rs:90-101): the commitment of `f.decompose_to_vec(P::B, P::L)` flattened (element i ->
+    /// columns [i L, (i + 1) L)); the digits go straight into the commit kernel's operands, the `len * L` vector is never built
+    pub fn decompose_and_commit_coeff<P: DecompositionParams>(&self, f: &[NTT::CoefficientRepresentation]) -> Result<Commitment<NTT>, CommitmentError> {
+        self.gadget_commit::<P>(&flatten(f), f.len(), sys::lf_ajtai_decompose_and_commit_coeff)
+    }
+
+    /// `decompose_and_commit_ntt::<P>(w)` (commitment_scheme.rs:106-113): the same from the NTT form (inverse CRT on the device)
+    pub fn decompose_and_commit_ntt<P: DecompositionParams>(&self, w: Vec<NTT>) -> Result<Commitment<NTT>, CommitmentError> {
+        self.gadget_commit::<P>(&flatten(&w), w.len(), sys::lf_ajtai_decompose_and_commit_ntt)
+    }
+
+    fn gadget_commit<P: DecompositionParams>(
+        &self,
+        words: &[u64],
+        count: usize,
+        entry: unsafe extern "C" fn(*mut sys::lf_ctx, *const u64, usize, u64, core::ffi::c_uint, usize, *mut u64) -> i32,
+    ) -> Result<Commitment<NTT>, CommitmentError> {
+        if count * P::L != self.n {
+            return Err(CommitmentError::WrongWitnessLength(count * P::L, self.n));
+        }
+        // a base the kernels do not take (above 2^63, or not a power of two) is refused by the library (LF_ERR_UNSUPPORTED)
+        let base = u64::try_from(P::B).unwrap_or(0);
+        let mut out = vec![0u64; self.kappa * NTT::WORDS];
+        // SAFETY: words holds count elements, out kappa elements
+        let rc = unsafe { entry(self.ctx.raw, words.as_ptr(), count, base, P::L as core::ffi::c_uint, 1, out.as_mut_ptr()) };
+        if rc != sys::LF_OK {
+            return Err(CommitmentError::WrongWitnessLength(count * P::L, self.n));
+        }
+        Ok(Commitment::from(unflatten(&out)))
     }
 
     pub fn kappa(&self) -> usize {

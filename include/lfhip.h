@@ -120,7 +120,8 @@ int lf_recompose(lf_ctx *, const uint64_t *in, size_t count_out, uint64_t base, 
 int lf_linf_check(lf_ctx *, const uint64_t *f_ntt, size_t count, uint64_t bound, int unsigned_variant, int *ok,
                   uint64_t *max_out);
 
-/* ---- a5: AjtaiCommitmentScheme::{new, commit, commit_ntt} (commitment_scheme.rs:23-77) -------- */
+/* ---- a5: AjtaiCommitmentScheme::{new, commit, commit_ntt, commit_coeff, decompose_and_commit_coeff, decompose_and_commit_ntt}
+ * (commitment_scheme.rs:23-113) -------- */
 /* kappa <= 128 (Goldilocks: more than 48 rows of A are committed in equal row chunks, one LDS tile each) / 32 (BabyBear);
  * larger -> LF_ERR_INVALID */
 /* The context keeps A in ONE resident form: coefficient form, cut into bytes, in int8-MFMA operand order (lf_ajtai_i8.hip) -- 8*24*kappa*n bytes for
@@ -134,6 +135,20 @@ int lf_ajtai_load(lf_ctx *, const uint64_t *A /* kappa*n ring elements, row-majo
 int lf_ajtai_generate(lf_ctx *, uint64_t seed, size_t kappa, size_t n);
 /* out[b*kappa + i] = sum_j A[i][j] (.) f[b*n + j];  n != width -> LF_ERR_INVALID (WrongWitnessLength) */
 int lf_ajtai_commit(lf_ctx *, const uint64_t *f, size_t n, size_t batch, uint64_t *out);
+/* AjtaiCommitmentScheme::commit_coeff (commitment_scheme.rs:81-87): f_coeff = batch x n ring elements in COEFFICIENT form;
+ * out[b*kappa + i] = sum_j A[i][j] (.) CRT(f_coeff[b*n + j]).  n != width -> LF_ERR_INVALID (WrongWitnessLength) */
+int lf_ajtai_commit_coeff(lf_ctx *, const uint64_t *f_coeff, size_t n, size_t batch, uint64_t *out);
+/* decompose_and_commit_coeff (:90-101): each of the `count` elements is split coefficient-wise into `digits` balanced base-`base`
+ * digits (the context's digit mode, lf_set_digit_mode), element i -> columns [i*digits, (i+1)*digits) (= lf_decompose layout 0 =
+ * decompose_to_vec(B, L) flattened), and the count*digits vector is committed -- on the device, without the count*digits table: the digit
+ * pass writes the commit kernel's operands (as few base-128 planes as the base needs).  count*digits != width -> LF_ERR_INVALID;
+ * base not a power of two in [2, 2^63] (BabyBear: [2, 2^32]) -> LF_ERR_UNSUPPORTED; digits == 0 or > 64 -> LF_ERR_INVALID.
+ * Sharded contexts commit their column slice of the decomposed vector (a slice may start inside an element's digits). */
+int lf_ajtai_decompose_and_commit_coeff(lf_ctx *, const uint64_t *f_coeff, size_t count, uint64_t base, unsigned digits,
+                                        size_t batch, uint64_t *out);
+/* decompose_and_commit_ntt (:106-113): the same from NTT-form input (inverse CRT on the device first) */
+int lf_ajtai_decompose_and_commit_ntt(lf_ctx *, const uint64_t *w_ntt, size_t count, uint64_t base, unsigned digits,
+                                      size_t batch, uint64_t *out);
 
 /* Multi-GPU: a rank that holds only a COLUMN SLICE of A (lf_ajtai_load / lf_ajtai_generate on that slice)
  * gets the partial commitment of its slice from lf_ajtai_commit; partial commitments are exchanged with one all-gather

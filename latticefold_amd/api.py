@@ -95,6 +95,9 @@ def _lib():
         L.lf_ajtai_generate.argtypes = [vp, C.c_uint64, C.c_size_t, C.c_size_t]
         L.lf_device_memory.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         L.lf_ajtai_commit.argtypes = [vp, u64p, C.c_size_t, C.c_size_t, u64p]
+        L.lf_ajtai_commit_coeff.argtypes = [vp, u64p, C.c_size_t, C.c_size_t, u64p]
+        L.lf_ajtai_decompose_and_commit_coeff.argtypes = [vp, u64p, C.c_size_t, C.c_uint64, C.c_uint, C.c_size_t, u64p]
+        L.lf_ajtai_decompose_and_commit_ntt.argtypes = [vp, u64p, C.c_size_t, C.c_uint64, C.c_uint, C.c_size_t, u64p]
         L.lf_modsum.argtypes = [u64p, C.c_size_t, C.c_size_t, u64p]
         L.lf_modsum_ring.argtypes = [u64p, C.c_size_t, C.c_size_t, u64p, C.c_int]
         L.lf_set_sharding.argtypes = [vp, C.c_int, C.c_int, EXCHANGE_FN, vp]
@@ -470,6 +473,30 @@ class AjtaiCommitmentScheme:
         return o[0] if a.ndim == 2 else o
 
     commit = commit_ntt
+
+    def _commit_with(self, fn, name, f, *args, digits=1):
+        a, p = _a64(f)
+        batch = 1 if a.ndim == 2 else a.shape[0]
+        n = a.shape[-2]
+        o = np.zeros((batch, self._kappa, self.ctx.RE), dtype=np.uint64)
+        rc = fn(self.ctx.h, p, n, *args, batch, o.ctypes.data_as(u64p))
+        if rc == -1 and n * digits != self._n:
+            raise CommitmentError(rc, f"WrongWitnessLength({n * digits}, {self._n})")
+        _chk(rc, name)
+        return o[0] if a.ndim == 2 else o
+
+    def commit_coeff(self, f_coeff):
+        """commit_coeff (commitment_scheme.rs:81-87): commit_ntt of CRT(f_coeff); f_coeff (n,d) or (batch,n,d) in coefficient form"""
+        return self._commit_with(_lib().lf_ajtai_commit_coeff, "lf_ajtai_commit_coeff", f_coeff)
+
+    def decompose_and_commit_coeff(self, f_coeff, B, L):
+        """decompose_and_commit_coeff (commitment_scheme.rs:90-101): the commitment of the count*L vector decompose_to_vec(B, L) (element i -> columns
+        [i*L, (i+1)*L)), without building it; f_coeff (count,d) or (batch,count,d) in coefficient form"""
+        return self._commit_with(_lib().lf_ajtai_decompose_and_commit_coeff, "lf_ajtai_decompose_and_commit_coeff", f_coeff, int(B), int(L), digits=int(L))
+
+    def decompose_and_commit_ntt(self, w, B, L):
+        """decompose_and_commit_ntt (commitment_scheme.rs:106-113): the same from NTT-form w"""
+        return self._commit_with(_lib().lf_ajtai_decompose_and_commit_ntt, "lf_ajtai_decompose_and_commit_ntt", w, int(B), int(L), digits=int(L))
 
 
 class PendingWitness:

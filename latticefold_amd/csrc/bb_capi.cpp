@@ -449,15 +449,13 @@ int BbCtx::ajtai_generate(uint64_t seed, size_t kappa, size_t n) {
     c->nA = cnt; c->nA_total = n; c->A_col0 = col0;
     return prep_ajtai_i8(c);
 }
-// General commitments from the resident byte planes of A (lf_ajtai_i8g.hip, shared with the Goldilocks backend): commit_ntt for `batch` vectors
-// F [batch][72][ldF] in NTT form (pointing at this rank's first column), or Witness::commit for the centred int32 planes of a witness handle
-// (F null, batch 1).  Five balanced base-128 digit planes cover the centred 31-bit residues.  out_dev: canonical u64 [batch][kappa][72], NTT form.
-static int commit_dev_i8g(C *c, const fe *F, size_t ldF, u32 batch, const int32_t *planes, size_t ldp, u64 *out_dev, bool timed) {
+// The contraction of `batch` operands whose digit words [NP][72][ntiles] of this rank's columns the caller's pass cut(b, pre, ntiles) writes.
+template <class Cut>
+static int commit_dev_pre(C *c, u32 NP, u32 batch, u64 *out_dev, bool timed, Cut &&cut) {
     if (!c->i8_nch || !c->dAb) return LF_ERR_STATE;
     const lf::AjtaiI8Ring R = lf::ajtai_i8_babybear();
     const u32 nch = c->i8_nch, kc = c->i8_kc, MT = lf::ajtai_i8_row_tiles(R, kc);
     const size_t ntiles = (c->nA + 7) / 8, chunk_bytes = ntiles * (R.RD / 8) * MT * 1024;
-    const u32 NP = planes ? lf::ajtai_i8g_planes_i32() : lf::ajtai_i8g_planes_general(R);
     const char *e_wgs = getenv("LF_I8G_WGS");           // (test hook: workgroups of the general commit kernel; default one per CU)
     const u32 nwg = e_wgs && atoi(e_wgs) > 0 ? (u32)atoi(e_wgs) : 256;
     size_t pw, dw, sw;
@@ -476,8 +474,7 @@ static int commit_dev_i8g(C *c, const fe *F, size_t ldF, u32 batch, const int32_
     RET(c->tbuf("i8g_ntt", (size_t)RE * c->kappa, &ntt));
     for (u32 b = 0; b < batch; b++) {
         const size_t ev = timed ? c->ev_begin(1) : 0;   // the whole device side of one commitment: digit pass, contraction, recombination, CRT
-        if (planes) lf::launch_i8g_cut_i32(planes, ldp, c->nA, RE, NP, pre, ntiles, c->stream());
-        else launch_i8g_cut_ntt(c->d_icrt, c->d_icrt_sp_val, c->d_icrt_sp_col, F + (size_t)b * RE * ldF, ldF, c->nA, NP, pre, ntiles, c->stream());
+        cut(b, pre, ntiles);
         for (u32 ch = 0; ch < nch; ch++) {
             const u32 row0 = ch * kc, kn = c->kappa - row0 < kc ? c->kappa - row0 : kc;
             const int g = lf::launch_ajtai_i8g(R, c->dAb + (size_t)ch * chunk_bytes, MT, pre, ntiles, c->nA, kn, row0, c->kappa, NP, nwg, part, dsum, sum, co, c->stream());
@@ -489,6 +486,16 @@ static int commit_dev_i8g(C *c, const fe *F, size_t ldF, u32 batch, const int32_
         if (timed) c->ev_end(ev);
     }
     return LF_OK;
+}
+// General commitments from the resident byte planes of A (lf_ajtai_i8g.hip, shared with the Goldilocks backend): commit_ntt for `batch` vectors
+// F [batch][72][ldF] in NTT form (pointing at this rank's first column), or Witness::commit for the centred int32 planes of a witness handle
+// (F null, batch 1).  Five balanced base-128 digit planes cover the centred 31-bit residues.  out_dev: canonical u64 [batch][kappa][72], NTT form.
+static int commit_dev_i8g(C *c, const fe *F, size_t ldF, u32 batch, const int32_t *planes, size_t ldp, u64 *out_dev, bool timed) {
+    const u32 NP = planes ? lf::ajtai_i8g_planes_i32() : lf::ajtai_i8g_planes_general(lf::ajtai_i8_babybear());
+    return commit_dev_pre(c, NP, batch, out_dev, timed, [&](u32 b, unsigned long long *pre, size_t ntiles) {
+        if (planes) lf::launch_i8g_cut_i32(planes, ldp, c->nA, RE, NP, pre, ntiles, c->stream());
+        else launch_i8g_cut_ntt(c->d_icrt, c->d_icrt_sp_val, c->d_icrt_sp_col, F + (size_t)b * RE * ldF, ldF, c->nA, NP, pre, ntiles, c->stream());
+    });
 }
 // F: [batch][72][ldF]; out_dev: canonical u64 [batch][kappa][72]
 static int commit_dev(C *c, const fe *F, size_t ldF, u32 batch, u64 *out_dev, bool timed) { return commit_dev_i8g(c, F, ldF, batch, nullptr, 0, out_dev, timed); }
@@ -505,6 +512,32 @@ int BbCtx::ajtai_commit(const uint64_t *f, size_t n, size_t batch, uint64_t *out
     for (size_t b = 0; b < batch; b++) RET(up_ring(c, f + b * n * RE, n, F + b * RE * n));
     c->ev_reset();
     RET(commit_dev(c, F + c->A_col0, n, (u32)batch, o, true));   // timed: lf_last_kernel_stats reports the stand-alone kernel
+    c->ev_collect();
+    RET(down_small(c, o, batch * c->kappa * RE, out));
+    return exchange_modsum(c, out, batch * c->kappa * RE);
+}
+// commit_coeff / decompose_and_commit_{coeff,ntt} (commitment_scheme.rs:81-113), as lf_capi.cpp ajtai_commit_gadget: the gadget digit pass writes the
+// commit kernel's operand words from the coefficient table (NTT-form input: inverse CRT into one coefficient table first)
+int BbCtx::ajtai_commit_gadget(const uint64_t *f, bool ntt_in, size_t count, uint32_t lb, unsigned L, size_t batch, uint64_t *out) {
+    C *c = p;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!c->dAb) return LF_ERR_STATE;
+    if (count > c->nA_total || count * L != c->nA_total) return LF_ERR_INVALID;   // CommitmentError::WrongWitnessLength
+    HIPCHK(hipSetDevice(c->device));
+    fe *F, *X = nullptr;
+    u64 *o;
+    RET(c->tbuf("io_a", batch * count * RE, &F));
+    if (ntt_in) RET(c->tbuf("io_c", count * RE, &X));
+    RET(c->tbuf("io_o", batch * c->kappa * RE, &o));
+    for (size_t b = 0; b < batch; b++) RET(up_ring(c, f + b * count * RE, count, F + b * RE * count));
+    c->ev_reset();
+    const lf::AjtaiI8Ring R = lf::ajtai_i8_babybear();
+    const u32 NP = lb ? lf::ajtai_i8g_planes_base(R, 1ull << lb) : lf::ajtai_i8g_planes_general(R);
+    RET(commit_dev_pre(c, NP, (u32)batch, o, true, [&](u32 b, unsigned long long *pre, size_t ntiles) {   // timed: the ICRT, digit pass and contraction
+        const fe *src = F + (size_t)b * RE * count;
+        if (ntt_in) { launch_icrt_dense(c->d_icrt, src, X, count, c->stream()); src = X; }
+        launch_i8g_cut_dec(src, count, c->A_col0, c->nA, L, lb, c->digit_mode, NP, pre, ntiles, c->stream());
+    }));
     c->ev_collect();
     RET(down_small(c, o, batch * c->kappa * RE, out));
     return exchange_modsum(c, out, batch * c->kappa * RE);

@@ -43,6 +43,8 @@ struct BbCtx {
     int ajtai_load(const uint64_t *A, size_t kappa, size_t n);
     int ajtai_generate(uint64_t seed, size_t kappa, size_t n);
     int ajtai_commit(const uint64_t *f, size_t n, size_t batch, uint64_t *out);
+    // commit_coeff / decompose_and_commit_{coeff,ntt}: element i of f [batch][count] -> its balanced base-2^lb digits, columns [i L, (i + 1) L) (lb 0, L 1: itself)
+    int ajtai_commit_gadget(const uint64_t *f, bool ntt_in, size_t count, uint32_t lb, unsigned L, size_t batch, uint64_t *out);
     int build_eq(const uint64_t *point, unsigned nv, uint64_t *out);
     int mle_eval_batch(const uint64_t *tables, size_t ntables, size_t len, const uint64_t *point, unsigned nv, uint64_t *out);
     int ccs_load(const lf_params *p, const uint32_t *const *rowptr, const uint32_t *const *col, const uint64_t *const *val,

@@ -41,6 +41,9 @@ void launch_icrt_dense(const fe *icrt_mat /*72*72*/, const fe *ntt, fe *coef, si
 // no row has more than 8 entries) -> centred residues -> NP balanced base-128 digit words pre [NP][72][ldw]
 void launch_i8g_cut_ntt(const fe *icrt_mat, const fe *sp_val, const u32 *sp_col, const fe *ntt, size_t ld, size_t n, u32 NP, unsigned long long *pre, size_t ldw,
                         hipStream_t s);
+// gadget digit pass (lf_i8g_dec.cuh) from a coefficient table [72][ldc]: columns [col0, col0 + n) of the count x L decomposed vector, base 2^lb (lb 0: the centred
+// coefficients themselves) -> pre [NP][72][ldw]
+void launch_i8g_cut_dec(const fe *coef, size_t ldc, size_t col0, size_t n, u32 L, u32 lb, int mode, u32 NP, unsigned long long *pre, size_t ldw, hipStream_t s);
 
 // ---- decomposition ---------------------------------------------------------------------------------------------
 void launch_decompose(const fe *coef, size_t n, u64 base, u32 digits, int layout, fe *out, hipStream_t s, int mode = 0);

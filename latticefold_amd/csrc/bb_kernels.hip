@@ -8,6 +8,7 @@
 #include <stdlib.h>
 
 #include "bb_kernels_dev.cuh"
+#include "lf_i8g_dec.cuh"
 
 namespace lfbb {
 
@@ -270,6 +271,16 @@ void launch_i8g_cut_ntt(const fe *icrt_mat, const fe *sp_val, const u32 *sp_col,
     const size_t ntiles = (n + 7) / 8;
     const size_t lds = (sp_val ? (size_t)RE * 8 * 8 : (size_t)RE * RE * 4) + 73 * 32 * 4 + 72 * 33 * 4;
     if (n) hipLaunchKernelGGL(k_i8g_cut_ntt, dim3((unsigned)cdiv(ntiles, 4)), dim3(256), lds, s, icrt_mat, sp_val, sp_col, ntt, ld, n, NP, ntiles, pre, ldw);
+}
+// the gadget digit pass of decompose_and_commit_* / commit_coeff (lf_i8g_dec.cuh) from a Montgomery coefficient table [72][ldc]
+struct I8gLdBabyBear {
+    const fe *x;
+    __device__ __forceinline__ u64 operator()(size_t o) const { return to_canon(x[o]); }
+};
+void launch_i8g_cut_dec(const fe *coef, size_t ldc, size_t col0, size_t n, u32 L, u32 lb, int mode, u32 NP, unsigned long long *pre, size_t ldw, hipStream_t s) {
+    const size_t ntiles = (n + 7) / 8;
+    if (n) hipLaunchKernelGGL((lfdec::k_i8g_cut_dec<I8gLdBabyBear>), dim3((unsigned)cdiv(ntiles * RE, 256)), dim3(256), 0, s, I8gLdBabyBear{coef}, ldc, (u64)BB_P, col0, n,
+                               L, lb, mode, (u32)RE, NP, ntiles, pre, ldw);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -36,6 +36,12 @@ int launch_ajtai_i8(const AjtaiI8Ring &R, const unsigned char *Ab, uint32_t MT, 
 // NP = ajtai_i8g_planes_general (an arbitrary element) or ajtai_i8g_planes_i32 (centred coefficients that fit an int32).
 uint32_t ajtai_i8g_planes_general(const AjtaiI8Ring &R);
 uint32_t ajtai_i8g_planes_i32();
+// ... or ajtai_i8g_planes_base (balanced base-`base` digits of a gadget decomposition: 1 plane for base 2, 2 for 2^8, 3 for 2^16, ... at most the general count)
+uint32_t ajtai_i8g_planes_base(const AjtaiI8Ring &R, uint64_t base);
+// the gadget digit pass of decompose_and_commit_* / commit_coeff (lf_i8g_dec.cuh) from canonical Goldilocks coefficients coef [24][ldc]: columns [col0, col0 + n)
+// of the count x L decomposed vector (column g = digit g % L of element g / L, base 2^lb, digit mode `mode`; lb 0: the centred coefficient of element g)
+void launch_i8g_cut_dec(const uint64_t *coef, size_t ldc, size_t col0, size_t n, uint32_t L, uint32_t lb, int mode, uint32_t NP, unsigned long long *pre, size_t ldw,
+                        hipStream_t s);
 // ... straight from the NTT form of a Goldilocks vector f [24][ld] (dense inverse map icrt_mat [24][24] on the device)
 // sp_val / sp_col (optional, [24][8]): the rows of the same map in compressed form when none has more than 8 non-zero entries (column 0xFFFFFFFF = no entry)
 void launch_i8g_cut_ntt(const uint64_t *icrt_mat, const uint64_t *sp_val, const uint32_t *sp_col, const uint64_t *ntt, size_t ld, size_t n, uint32_t NP,

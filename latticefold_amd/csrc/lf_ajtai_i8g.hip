@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include "lf_field.cuh"
 #include "lf_ajtai_i8.h"
+#include "lf_i8g_dec.cuh"
 
 namespace lf {
 namespace {
@@ -581,9 +582,28 @@ void launch_i8g_cut_i32(const int32_t *planes, size_t ld, size_t n, u32 RD, u32 
     hipLaunchKernelGGL(k_i8g_cut<1>, dim3((unsigned)cdiv(ntiles * RD, 256)), dim3(256), 0, s, (const void *)planes, ld, n, (u64)0, RD, NP, ntiles, pre, ldw);
 }
 
+// the gadget digit pass (lf_i8g_dec.cuh) from canonical Goldilocks coefficients coef [24][ldc]
+struct I8gLdGoldilocks {
+    const u64 *x;
+    __device__ __forceinline__ u64 operator()(size_t o) const { return x[o]; }
+};
+void launch_i8g_cut_dec(const u64 *coef, size_t ldc, size_t col0, size_t n, u32 L, u32 lb, int mode, u32 NP, unsigned long long *pre, size_t ldw, hipStream_t s) {
+    const size_t ntiles = (n + 7) / 8;
+    if (n) hipLaunchKernelGGL((lfdec::k_i8g_cut_dec<I8gLdGoldilocks>), dim3((unsigned)cdiv(ntiles * 24, 256)), dim3(256), 0, s, I8gLdGoldilocks{coef}, ldc, LF_P, col0, n, L,
+                               lb, mode, 24u, NP, ntiles, pre, ldw);
+}
+
 // planes of a general element / of centred coefficients bounded by 2^31
 u32 ajtai_i8g_planes_general(const AjtaiI8Ring &R) { return R.RD == 24 ? 10 : 5; }
 u32 ajtai_i8g_planes_i32() { return 5; }
+// planes of balanced base-`base` digits: |d| <= min(base / 2, (p - 1) / 2) under both digit rules, and k planes hold |d| <= 63 (128^k - 1) / 127
+u32 ajtai_i8g_planes_base(const AjtaiI8Ring &R, u64 base) {
+    const u64 p = R.p_small ? R.p_small : LF_P, bound = base / 2 < (p - 1) / 2 ? base / 2 : (p - 1) / 2;
+    const u32 cap = ajtai_i8g_planes_general(R);
+    u32 k = 1;
+    for (unsigned __int128 m = 63; m < bound && k < cap; m = m * 128 + 63) k++;
+    return k;
+}
 
 namespace {
 struct GPlan {

@@ -626,15 +626,15 @@ int lf_device_memory(lf_ctx *c, size_t *free_bytes, size_t *total_bytes) {
     HIPCHK(hipMemGetInfo(free_bytes, total_bytes));
     return LF_OK;
 }
-// General commitments from the resident byte planes of A (lf_ajtai_i8g.hip): AjtaiCommitmentScheme::commit_ntt (commitment_scheme.rs:37-54,75-77) for
-// `batch` vectors F [batch][24][ldF] in NTT form (pointing at this rank's first column), or Witness::commit (arith.rs:357-362) for the centred int32
-// coefficient planes of a witness handle (F null, batch 1).  out_dev: [batch][kappa][24] NTT form, AoS (PARTIAL when sharded).
-static int commit_dev_i8g(lf_ctx *c, const u64 *F, size_t ldF, u32 batch, const int32_t *planes, size_t ldp, u64 *out_dev, bool timed) {
+// The contraction of `batch` operands whose digit words [NP][24][ntiles] of this rank's columns the caller's pass cut(b, pre, ntiles) writes: NP = 10 for an
+// arbitrary element, 5 for the int32 planes of a witness handle, fewer for the digits of a gadget decomposition (ajtai_i8g_planes_base).
+// out_dev: [batch][kappa][24] NTT form, AoS (PARTIAL when sharded).
+template <class Cut>
+static int commit_dev_pre(lf_ctx *c, u32 NP, u32 batch, u64 *out_dev, bool timed, Cut &&cut) {
     if (!c->A_loaded || !c->i8_nch || !c->dAb) return LF_ERR_STATE;
     const AjtaiI8Ring R = ajtai_i8_goldilocks();
     const u32 nch = c->i8_nch, kc = c->i8_kc, MT = ajtai_i8_row_tiles(R, kc);
     const size_t ntiles = (c->nA + 7) / 8, chunk_bytes = ntiles * (R.RD / 8) * MT * 1024;
-    const u32 NP = planes ? ajtai_i8g_planes_i32() : ajtai_i8g_planes_general(R);
     const char *e_wgs = getenv("LF_I8G_WGS");           // (test hook: workgroups of the general commit kernel; default one per CU)
     const u32 nwg = e_wgs && atoi(e_wgs) > 0 ? (u32)atoi(e_wgs) : 256;
     size_t pw, dw, sw;
@@ -651,8 +651,7 @@ static int commit_dev_i8g(lf_ctx *c, const u64 *F, size_t ldF, u32 batch, const 
     RET(c->tbuf("i8g_ntt", (size_t)24 * c->kappa, &ntt));
     for (u32 b = 0; b < batch; b++) {
         const size_t ev = timed ? c->ev_begin(1) : 0;   // the whole device side of one commitment: digit pass, contraction, recombination, CRT
-        if (planes) launch_i8g_cut_i32(planes, ldp, c->nA, 24, NP, pre, ntiles, c->stream());
-        else launch_i8g_cut_ntt(c->d_icrt, c->d_icrt_sp_val, c->d_icrt_sp_col, F + (size_t)b * 24 * ldF, ldF, c->nA, NP, pre, ntiles, c->stream());
+        cut(b, pre, ntiles);
         for (u32 ch = 0; ch < nch; ch++) {
             const u32 row0 = ch * kc, kn = c->kappa - row0 < kc ? c->kappa - row0 : kc;
             const int g = launch_ajtai_i8g(R, c->dAb + (size_t)ch * chunk_bytes, MT, pre, ntiles, c->nA, kn, row0, c->kappa, NP, nwg, part, dsum, sum, coef, c->stream());
@@ -663,6 +662,16 @@ static int commit_dev_i8g(lf_ctx *c, const u64 *F, size_t ldF, u32 batch, const 
         if (timed) c->ev_end(ev);
     }
     return LF_OK;
+}
+// General commitments from the resident byte planes of A (lf_ajtai_i8g.hip): AjtaiCommitmentScheme::commit_ntt (commitment_scheme.rs:37-54,75-77) for
+// `batch` vectors F [batch][24][ldF] in NTT form (pointing at this rank's first column), or Witness::commit (arith.rs:357-362) for the centred int32
+// coefficient planes of a witness handle (F null, batch 1).  out_dev: [batch][kappa][24] NTT form, AoS (PARTIAL when sharded).
+static int commit_dev_i8g(lf_ctx *c, const u64 *F, size_t ldF, u32 batch, const int32_t *planes, size_t ldp, u64 *out_dev, bool timed) {
+    const u32 NP = planes ? ajtai_i8g_planes_i32() : ajtai_i8g_planes_general(ajtai_i8_goldilocks());
+    return commit_dev_pre(c, NP, batch, out_dev, timed, [&](u32 b, unsigned long long *pre, size_t ntiles) {
+        if (planes) launch_i8g_cut_i32(planes, ldp, c->nA, 24, NP, pre, ntiles, c->stream());
+        else launch_i8g_cut_ntt(c->d_icrt, c->d_icrt_sp_val, c->d_icrt_sp_col, F + (size_t)b * 24 * ldF, ldF, c->nA, NP, pre, ntiles, c->stream());
+    });
 }
 // F: [batch][24][ldF] device, pointing at this rank's first column; out_dev: [batch][kappa][24] device AoS (PARTIAL when sharded)
 static int commit_dev(lf_ctx *c, const u64 *F, size_t ldF, u32 batch, u64 *out_dev, bool timed) { return commit_dev_i8g(c, F, ldF, batch, nullptr, 0, out_dev, timed); }
@@ -747,6 +756,61 @@ int lf_ajtai_commit(lf_ctx *c, const uint64_t *f, size_t n, size_t batch, uint64
     RET(commit_dev(c, F + c->A_col0, n, (u32)batch, o, true));   // timed: lf_last_kernel_stats reports the stand-alone kernel
     c->ev_collect();
     return commit_download(c, o, batch * c->kappa * 24, out);
+}
+// commit_coeff / decompose_and_commit_{coeff,ntt} (commitment_scheme.rs:81-113): element i of f [batch][count] (coefficient form, or NTT form: ntt_in)
+// becomes columns [i L, (i + 1) L) of the committed vector, its balanced base-2^lb digits (lb 0, L 1: the element itself).  The count x L vector is never
+// built: the gadget digit pass (lf_i8g_dec.cuh) writes the commit kernel's operand words from the coefficient table, as few planes as the base needs.
+// NTT-form input is inverse-CRT-ed into one coefficient table first (one pass over count elements; the fused form of k_i8g_cut_ntt would map 32 elements
+// = 32 L columns per block -- DESIGN.md, k_ajtai_i8g row).
+static int ajtai_commit_gadget(lf_ctx *c, const uint64_t *f, bool ntt_in, size_t count, u32 lb, u32 L, size_t batch, uint64_t *out) {
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!c->A_loaded) return LF_ERR_STATE;
+    if (count > c->nA_total || count * L != c->nA_total) return LF_ERR_INVALID;   // CommitmentError::WrongWitnessLength
+    HIPCHK(hipSetDevice(c->device));
+    u64 *F, *X = nullptr, *o;
+    RET(c->tbuf("io_a", batch * count * 24, &F));
+    if (ntt_in) RET(c->tbuf("io_c", count * 24, &X));
+    RET(c->tbuf("io_b", batch * c->kappa * 24, &o));
+    for (size_t b = 0; b < batch; b++) RET(up_ring(c, f + b * count * 24, count, F + b * 24 * count));
+    c->tn = Tunables::read((size_t)1 << 14);
+    c->ev_reset();
+    const AjtaiI8Ring R = ajtai_i8_goldilocks();
+    const u32 NP = lb ? ajtai_i8g_planes_base(R, 1ull << lb) : ajtai_i8g_planes_general(R);
+    RET(commit_dev_pre(c, NP, (u32)batch, o, true, [&](u32 b, unsigned long long *pre, size_t ntiles) {   // timed: the ICRT, digit pass and contraction
+        const u64 *src = F + (size_t)b * 24 * count;
+        if (ntt_in) { launch_icrt_dense(c->d_icrt, src, X, count, c->stream()); src = X; }
+        launch_i8g_cut_dec(src, count, c->A_col0, c->nA, L, lb, c->digit_mode, NP, pre, ntiles, c->stream());
+    }));
+    c->ev_collect();
+    return commit_download(c, o, batch * c->kappa * 24, out);
+}
+// The ABI side of the three (dec false: commit_coeff, no decomposition): arguments are checked before any device work; in an external basis the commitments
+// leave converted and NTT-form input is converted on the way in, coefficient-form input is not (as lf_witness_from_f_coeff).
+static int ajtai_commit_gadget_api(lf_ctx *c, const uint64_t *f, bool ntt_in, size_t count, bool dec, uint64_t base, unsigned digits, size_t batch, uint64_t *out) {
+    if (LF_XB(c) && f && out) {
+        XB x(c);
+        const u32 kap = c->bb ? c->bb->kappa() : c->kappa;
+        int rc = ajtai_commit_gadget_api(c, ntt_in ? x.ring_in(f, count * batch) : f, ntt_in, count, dec, base, digits, batch, out);
+        if (rc == LF_OK) x.ring_out(out, batch * kap);
+        return rc;
+    }
+    if (!c || !f || !out || !batch || digits == 0 || digits > 64) return LF_ERR_INVALID;
+    u32 lb = 0;
+    if (dec) {
+        if (!pow2(base) || (c->bb && base > (1ull << 32))) return LF_ERR_UNSUPPORTED;
+        while ((1ull << lb) < base) lb++;
+    }
+    if (c->bb) return c->bb->ajtai_commit_gadget(f, ntt_in, count, lb, digits, batch, out);
+    return ajtai_commit_gadget(c, f, ntt_in, count, lb, digits, batch, out);
+}
+int lf_ajtai_commit_coeff(lf_ctx *c, const uint64_t *f_coeff, size_t n, size_t batch, uint64_t *out) {
+    return ajtai_commit_gadget_api(c, f_coeff, false, n, false, 0, 1, batch, out);
+}
+int lf_ajtai_decompose_and_commit_coeff(lf_ctx *c, const uint64_t *f_coeff, size_t count, uint64_t base, unsigned digits, size_t batch, uint64_t *out) {
+    return ajtai_commit_gadget_api(c, f_coeff, false, count, true, base, digits, batch, out);
+}
+int lf_ajtai_decompose_and_commit_ntt(lf_ctx *c, const uint64_t *w_ntt, size_t count, uint64_t base, unsigned digits, size_t batch, uint64_t *out) {
+    return ajtai_commit_gadget_api(c, w_ntt, true, count, true, base, digits, batch, out);
 }
 
 // column-sharded commit: the context holds only columns [col0, col0+n_local) of A (loaded with lf_ajtai_load on
@@ -1258,6 +1322,8 @@ int lf_debug_i8_prof(uint64_t *out64) {   // (LF_I8G_PROF set: the table of the 
 }
 // (not part of the ABI: tools/i8g_prof.py) per-workgroup loop durations of the last profiled general commit
 extern "C" int lfdbg_i8g_wg(unsigned int *out512) { return out512 ? ajtai_i8g_read_wg(out512) : -1; }
+// (not part of the ABI: tests) digit planes the gadget commitments use for a power-of-two base (ring: LF_RING_*)
+extern "C" unsigned lfdbg_i8g_planes_base(int ring, uint64_t base) { return ajtai_i8g_planes_base(ring == LF_RING_BABYBEAR ? ajtai_i8_babybear() : ajtai_i8_goldilocks(), base); }
 int lf_last_fold_paths(lf_ctx *c, unsigned *sv_round_mask) {
     if (!c || !sv_round_mask) return LF_ERR_INVALID;
     *sv_round_mask = c->bb ? c->bb->fold_paths() : c->sv_round_mask;
