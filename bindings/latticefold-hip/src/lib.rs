@@ -7,6 +7,7 @@
 //! |-------------------------------------------------------------------------------|----------------------------------------|
 //! | `AjtaiCommitmentScheme::{new, rand, commit, commit_ntt, commit_coeff, decompose_and_commit_coeff, decompose_and_commit_ntt, kappa, width}` `commitment/commitment_scheme.rs:17-113` | [`HipAjtai`] |
 //! | `Witness::{from_w_ccs, from_f, from_f_coeff, commit}` `arith.rs:230-362`        | [`HipWitness`] (device resident)       |
+//! | `Arith::check_relation` of `CCS` / `CCCS` / `LCCCS` `arith.rs:76-110,193-206`      | [`HipContext::check_relation`], `check_cccs`, `check_lcccs` (on the device) |
 //! | `PoseidonTranscript` (`Transcript`, `TranscriptWithShortChallenges`) `transcript/poseidon.rs:17-75` | [`HipTranscript`] -- same traits, same challenges |
 //! | `LinearizationProver::prove` `nifs/linearization.rs:26-52`                      | `impl LinearizationProver for HipLinearizationProver` |
 //! | `DecompositionProver::prove` `nifs/decomposition/structs.rs:48-64`              | `impl DecompositionProver for HipDecompositionProver` |
@@ -34,7 +35,7 @@ use ark_ff::{Field, PrimeField};
 use ark_serialize::{CanonicalDeserialize, CanonicalSerialize};
 use cyclotomic_rings::{challenge_set::LatticefoldChallengeSet, rings::SuitableRing};
 use latticefold::{
-    arith::{Witness, CCCS, CCS, LCCCS},
+    arith::{error::CSError, Witness, CCCS, CCS, LCCCS},
     commitment::{AjtaiCommitmentScheme, Commitment, CommitmentError},
     decomposition_parameters::DecompositionParams,
     nifs::{
@@ -210,6 +211,51 @@ impl HipContext {
 
     fn params(&self) -> Result<sys::lf_params, HipError> {
         self.params.lock().unwrap().ok_or(HipError::NoSession)
+    }
+
+    /// `CCS::check_relation(z)` (arith.rs:76-110) on the loaded CCS, on the device: `Ok(Err(CSError::NotSatisfied(i)))` names the first bad row
+    pub fn check_relation<NTT: SuitableRing>(&self, z: &[NTT]) -> Result<Result<(), CSError>, HipError> {
+        let p = self.params()?;
+        assert_eq!(z.len(), (p.l + 1 + p.wit_len) as usize);
+        let w = flatten(z);
+        let mut first_bad = 0u64;
+        // SAFETY: w holds n elements; first_bad is a plain out-parameter
+        let rc = unsafe { sys::lf_ccs_check(self.raw, w.as_ptr(), &mut first_bad) };
+        if rc == sys::LF_ERR_REJECT {
+            return Ok(Err(CSError::NotSatisfied(first_bad as usize)));
+        }
+        chk(rc, "lf_ccs_check").map(Ok)
+    }
+
+    /// R_CCCS of (`cccs`, `wit`): the `LF_REL_*` bits of the failing components (cm, CCS on z = (x_ccs, 1, w_ccs), norm when `bound` != 0); 0 = holds
+    pub fn check_cccs<NTT: SuitableRing>(&self, cccs: &CCCS<NTT>, wit: &HipWitness<NTT>, bound: u64) -> Result<u32, HipError> {
+        let mut w = flatten(cccs.cm.as_ref());
+        w.extend(flatten(&cccs.x_ccs));
+        let (mut failed, mut first_bad) = (0u32, 0u64);
+        // SAFETY: w holds kappa + l elements (lf_cccs_len); failed / first_bad are plain out-parameters
+        let rc = unsafe { sys::lf_cccs_check(self.raw, w.as_ptr(), wit.raw, bound, &mut failed, &mut first_bad) };
+        if rc != sys::LF_ERR_REJECT {
+            chk(rc, "lf_cccs_check")?;
+        }
+        Ok(failed)
+    }
+
+    /// R_LCCCS of (`lcccs`, `wit`), the decider of an accumulator (arith.rs:193-206): the `LF_REL_*` bits of the failing components (cm, u, v, norm when
+    /// `bound` != 0); 0 = holds
+    pub fn check_lcccs<NTT: SuitableRing>(&self, lcccs: &LCCCS<NTT>, wit: &HipWitness<NTT>, bound: u64) -> Result<u32, HipError> {
+        let mut w = flatten(&lcccs.r);
+        w.extend(flatten(&lcccs.v));
+        w.extend(flatten(lcccs.cm.as_ref()));
+        w.extend(flatten(&lcccs.u));
+        w.extend(flatten(&lcccs.x_w));
+        w.extend(flatten(core::slice::from_ref(&lcccs.h)));
+        let mut failed = 0u32;
+        // SAFETY: w holds the flat LCCCS (lf_lcccs_len_ring); failed is a plain out-parameter
+        let rc = unsafe { sys::lf_lcccs_check(self.raw, w.as_ptr(), wit.raw, bound, &mut failed) };
+        if rc != sys::LF_ERR_REJECT {
+            chk(rc, "lf_lcccs_check")?;
+        }
+        Ok(failed)
     }
 }
 

@@ -312,6 +312,21 @@ int lf_decomposition_prove(lf_ctx *, lf_transcript *, const uint64_t *lcccs, con
 int lf_folding_prove(lf_ctx *, lf_transcript *, const uint64_t *lcccs_s, const lf_witness *w_left, const lf_witness *w_right,
                      uint64_t *lcccs_out, lf_witness **w_out, uint64_t *fold_proof_out);
 
+/* ---- relation checks: Arith::check_relation of CCS, CCCS and LCCCS (arith.rs:76-110, 193-206) on the device ----------------------------
+ * Every component is evaluated; *failed names all the failing ones.  The norm rule is lf_linf_check's balanced one: max |centred coefficient| of
+ * the witness < bound (bound 0: not checked).  No CCS loaded or (cm) no Ajtai matrix -> LF_ERR_STATE; a witness of another context, a wrong N or a
+ * NULL argument -> LF_ERR_INVALID; an LCCCS point that is not made of diagonal challenges or a sharded context (world > 1) -> LF_ERR_UNSUPPORTED. */
+enum { LF_REL_CM = 1, LF_REL_CCS = 2, LF_REL_U = 4, LF_REL_V = 8, LF_REL_NORM = 16 };
+/* CCS::check_relation (arith.rs:76-110) on the loaded CCS.  z = n NTT elements.  LF_OK if every row is zero, else
+ * LF_ERR_REJECT and *first_bad = the smallest row i with a non-zero residual (Error::NotSatisfied(i)); m when every row is zero. */
+int lf_ccs_check(lf_ctx *, const uint64_t *z, uint64_t *first_bad);
+/* R_CCCS for (cccs [lf_cccs_len_ring], wit): the commitment, the CCS on z = (x_ccs, 1, w_ccs), and the norm if bound != 0.
+ * LF_OK, or LF_ERR_REJECT with *failed = OR of LF_REL_{CM,CCS,NORM} and *first_bad as above (m when the CCS holds). */
+int lf_cccs_check(lf_ctx *, const uint64_t *cccs, const lf_witness *wit, uint64_t bound, unsigned *failed, uint64_t *first_bad);
+/* R_LCCCS, the decider of an accumulator (lcccs [lf_lcccs_len_ring], wit): cm == Com(f), u_j == MLE(M_j z)(r) with z = (x_w, h, w_ccs) for
+ * every j, v == f-hat(r) (Witness::get_fhat), and the norm if bound != 0.  LF_OK, or LF_ERR_REJECT with *failed = OR of LF_REL_{CM,U,V,NORM}. */
+int lf_lcccs_check(lf_ctx *, const uint64_t *lcccs, const lf_witness *wit, uint64_t bound, unsigned *failed);
+
 /* ---- measurement hooks (bench.py): HIP-event time of the last fold step, per phase, in ms ------------ */
 #define LF_N_PHASES 8
 int lf_last_phase_ms(lf_ctx *, float *out /* LF_N_PHASES */);

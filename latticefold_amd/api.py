@@ -39,6 +39,19 @@ class CommitmentError(LfError):
     """CommitmentError::WrongWitnessLength (commitment.rs:14-27)"""
 
 
+LF_ERR_REJECT = -8
+# the components of a relation: the LF_REL_* bits of lf_cccs_check / lf_lcccs_check
+REL_BITS = {"cm": 1, "ccs": 2, "u": 4, "v": 8, "norm": 16}
+
+
+class NotSatisfied(LfError):
+    """Error::NotSatisfied(row) of CCS::check_relation (arith.rs:76-110): `row` is the first row with a non-zero residual"""
+
+    def __init__(self, row, where="lf_ccs_check"):
+        super().__init__(LF_ERR_REJECT, where)
+        self.row = row
+
+
 class Params(C.Structure):
     """lf_params == DecompositionParams {B, L, B_SMALL=b, K} + CCS shape + kappa."""
     _fields_ = [("s", C.c_uint32), ("wit_len", C.c_uint32), ("l", C.c_uint32), ("L", C.c_uint32),
@@ -397,6 +410,42 @@ class Context:
         o = np.zeros((self.m, self.RE), dtype=np.uint64)
         _chk(_lib().lf_spmv(self.h, j, p, o.ctypes.data_as(u64p)), "lf_spmv")
         return o
+
+    # ---- relation checks (arith.rs:76-110, 193-206) ------------------------------------------------------------
+    def check_relation(self, z):
+        """CCS::check_relation (arith.rs:76-110) of the loaded CCS on z (n NTT-form elements): None, or raises NotSatisfied with .row = the first bad row"""
+        L = _lib()
+        L.lf_ccs_check.argtypes = [C.c_void_p, u64p, u64p]
+        a, p = _a64(z)
+        fb = C.c_uint64()
+        rc = L.lf_ccs_check(self.h, p, C.cast(C.byref(fb), u64p))
+        if rc == LF_ERR_REJECT:
+            raise NotSatisfied(fb.value)
+        _chk(rc, "lf_ccs_check")
+
+    def check_cccs(self, cccs, wit, bound=0):
+        """R_CCCS of (cccs, wit): the set of failing components among "cm", "ccs", "norm" (norm: max |centred coefficient| < bound, checked when
+        bound != 0); empty when the relation holds.  The first bad row of the CCS (m when it holds) is left in .last_first_bad"""
+        L = _lib()
+        L.lf_cccs_check.argtypes = [C.c_void_p, u64p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint), u64p]
+        a, p = _a64(cccs)
+        f, fb = C.c_uint(), C.c_uint64()
+        rc = L.lf_cccs_check(self.h, p, wit.h, int(bound), C.byref(f), C.cast(C.byref(fb), u64p))
+        if rc != LF_ERR_REJECT:
+            _chk(rc, "lf_cccs_check")
+        self.last_first_bad = fb.value
+        return {name for name, bit in REL_BITS.items() if f.value & bit}
+
+    def check_lcccs(self, lcccs, wit, bound=0):
+        """R_LCCCS of (lcccs, wit), the decider of an accumulator: the set of failing components among "cm", "u", "v", "norm"; empty when it holds"""
+        L = _lib()
+        L.lf_lcccs_check.argtypes = [C.c_void_p, u64p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint)]
+        a, p = _a64(lcccs)
+        f = C.c_uint()
+        rc = L.lf_lcccs_check(self.h, p, wit.h, int(bound), C.byref(f))
+        if rc != LF_ERR_REJECT:
+            _chk(rc, "lf_lcccs_check")
+        return {name for name, bit in REL_BITS.items() if f.value & bit}
 
     def phase_ms(self):
         out = (C.c_float * 8)()

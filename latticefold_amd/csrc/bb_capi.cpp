@@ -497,6 +497,7 @@ static int commit_dev_i8g(C *c, const fe *F, size_t ldF, u32 batch, const int32_
         else launch_i8g_cut_ntt(c->d_icrt, c->d_icrt_sp_val, c->d_icrt_sp_col, F + (size_t)b * RE * ldF, ldF, c->nA, NP, pre, ntiles, c->stream());
     });
 }
+int witness_commit_dev(C *c, const lf_witness *w, u64 *out_dev) { return commit_dev_i8g(c, nullptr, 0, 1, w->planes + c->A_col0, w->N, out_dev, false); }
 // F: [batch][72][ldF]; out_dev: canonical u64 [batch][kappa][72]
 static int commit_dev(C *c, const fe *F, size_t ldF, u32 batch, u64 *out_dev, bool timed) { return commit_dev_i8g(c, F, ldF, batch, nullptr, 0, out_dev, timed); }
 int BbCtx::ajtai_commit(const uint64_t *f, size_t n, size_t batch, uint64_t *out) {

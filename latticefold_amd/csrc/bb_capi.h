@@ -57,6 +57,10 @@ struct BbCtx {
     int witness_get_f(const lf_witness *w, uint64_t *out);
     int witness_get_w_ccs(const lf_witness *w, uint64_t *out);
     int witness_commit(const lf_witness *w, uint64_t *cm_out);
+    // relation checks (lf_ccs_check / lf_cccs_check / lf_lcccs_check, bb_check.cpp)
+    int ccs_check(const uint64_t *z, uint64_t *first_bad);
+    int cccs_check(const uint64_t *cccs, const lf_witness *wit, uint64_t bound, unsigned *failed, uint64_t *first_bad);
+    int lcccs_check(const uint64_t *lcccs, const lf_witness *wit, uint64_t bound, unsigned *failed);
     int sumcheck_lin_begin(const uint64_t *tables, const uint64_t *eq_point);
     int sumcheck_lin_round(const uint64_t *r_prev, uint64_t *evals_out);
     int sumcheck_lin_end();

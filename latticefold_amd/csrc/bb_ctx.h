@@ -191,6 +191,9 @@ int up_ring(C *c, const u64 *host, size_t n, fe *dst);
 int down_ring(C *c, const fe *src, size_t n, u64 *host);
 size_t dec_proof_len(const lf_params *p);
 size_t lin_proof_len(const lf_params *p);
+int build_z(C *c, const int32_t *planes, u32 K, int mode_bits, const u64 *heads, fe *z);   // bb_prove.cpp (synchronises the stream)
+bool lcccs_point(const lf_params &P, const u64 *lcccs, std::vector<H9> &pt);
+int witness_commit_dev(C *c, const lf_witness *w, u64 *out_dev);   // Witness::commit into device memory (kappa ring elements, canonical AoS; unsharded contexts)
 #pragma GCC visibility pop
 
 }  // namespace lfbb

@@ -84,7 +84,7 @@ static int run_lin_sumcheck(C *c, BbTranscript &tr, const fe *mz, const fe *eqb,
 }
 
 // z tables: head (x.., h) || w, w from the planes
-static int build_z(C *c, const int32_t *planes, u32 K, int mode_bits, const u64 *heads /* K*(l+1) ring AoS host */, fe *z /* [K][72][n] */) {
+int build_z(C *c, const int32_t *planes, u32 K, int mode_bits, const u64 *heads /* K*(l+1) ring AoS host */, fe *z /* [K][72][n] */) {
     const lf_params &P = c->P;
     u32 hl = P.l + 1;
     launch_recompose_crt(c->dev, planes, c->N, P.wit_len, P.L, P.B, K, mode_bits, z, c->n, hl, c->stream());
@@ -115,7 +115,7 @@ static int build_z_async(C *c, const int32_t *planes, u32 K, int mode_bits, cons
     HIPCHK(hipMemcpy2DAsync(z, c->n * sizeof(fe), stage, hl * sizeof(fe), hl * sizeof(fe), (size_t)K * RE, hipMemcpyDeviceToDevice, c->stream()));
     return LF_OK;
 }
-static bool lcccs_point(const lf_params &P, const u64 *lcccs, std::vector<H9> &pt) {
+bool lcccs_point(const lf_params &P, const u64 *lcccs, std::vector<H9> &pt) {
     pt.resize(P.s);
     for (u32 i = 0; i < P.s; i++)
         if (!is_diag(lcccs + (size_t)i * RE, &pt[i])) return false;

@@ -451,4 +451,8 @@ int coef_eval_dev(lf_ctx *c, const int32_t *planes, size_t n, const u64 *eq, siz
 int lin_tail_rounds(lf_ctx *c, Transcript &tr, const u64 *cur, const u64 *cure, size_t n, u64 *tout, u64 *partial, u32 round, Fq3 *point,
                            u64 *msgs, u32 deg, const std::function<void(u32)> *after_round);
 int down_ring(lf_ctx *c, const u64 *src, size_t n, u64 *host);
+// z tables [K][24][n] = heads (l + 1 elements per table) || the recomposed witness columns [w0, w0 + wcnt) (lf_prove.cpp)
+int build_z(lf_ctx *c, const int32_t *planes, u32 K, int mode_bits, const u64 *heads, u64 *z, size_t w0 = 0, size_t wcnt = (size_t)-1);
+bool lcccs_point(const lf_params &P, const u64 *lcccs, std::vector<Fq3> &pt);   // the LCCCS point r as F_{p^3} challenges; false if not diagonal
+int witness_commit_dev(lf_ctx *c, const lf_witness *w, u64 *out_dev);   // Witness::commit into device memory (kappa ring elements, AoS; unsharded contexts)
 #pragma GCC visibility pop

@@ -217,8 +217,8 @@ int shard_col_range(lf_ctx *c, size_t r0, size_t rcnt, size_t *lo, size_t *hi) {
     return LF_OK;
 }
 // w0 / wcnt (optional): only the witness columns [w0, w0 + wcnt) -- z columns l + 1 + w0 .. -- are built (a sharded rank's slice; the heads always)
-static int build_z(lf_ctx *c, const int32_t *planes, u32 K, int mode_bits, const u64 *heads /* K*(l+1) ring AoS host */, u64 *z /* [K][24][n] */,
-                   size_t w0 = 0, size_t wcnt = (size_t)-1) {
+int build_z(lf_ctx *c, const int32_t *planes, u32 K, int mode_bits, const u64 *heads /* K*(l+1) ring AoS host */, u64 *z /* [K][24][n] */,
+            size_t w0, size_t wcnt) {
     const lf_params &P = c->P;
     u32 hl = P.l + 1;
     if (wcnt == (size_t)-1) { w0 = 0; wcnt = P.wit_len; }
@@ -239,7 +239,7 @@ struct LinOut {
     std::vector<Fq3> r;  // point
 };
 
-static bool lcccs_point(const lf_params &P, const u64 *lcccs, std::vector<Fq3> &pt) {
+bool lcccs_point(const lf_params &P, const u64 *lcccs, std::vector<Fq3> &pt) {
     pt.resize(P.s);
     for (u32 i = 0; i < P.s; i++)
         if (!HostRing::is_diag(lcccs + (size_t)i * 24, &pt[i])) return false;
