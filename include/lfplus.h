@@ -89,6 +89,19 @@ int lfplus_set_matrix(lfplus_ctx *ctx, const uint64_t *A, uint32_t kappa, uint64
 int lfplus_share_matrix(lfplus_ctx *ctx, lfplus_ctx *from);
 /* witness vector f (n ring elements); stays resident */
 int lfplus_set_witness(lfplus_ctx *ctx, const uint64_t *f, uint64_t n);
+/* ComR1CS::new (src/r1cs.rs:48-60) on the resident matrix A (kappa x n): z = m ring elements (host pointer, canonical words), n = m * k.
+ * f = z.gadget_decompose(b, k) (element j -> its k balanced base-b digits, least significant first, at rows [j k, (j + 1) k)) becomes the
+ * context's resident witness, exactly as after lfplus_set_witness(f); cm_f (kappa * 16 words, may be NULL) = A f.  Only z crosses PCIe (a k-th of f);
+ * its words are checked on the device behind the upload (LFPLUS_E_ARG for a non-canonical one), the digits are cut and committed in one pass over A.
+ * Envelope: matrix set, context not sharded (LFPLUS_E_ARG; a sharded prover uploads f with lfplus_set_witness), m * k == n <= 2^28, 1 <= k <= 16,
+ * 2 <= b <= 2^31 (a digit fits an int32; larger bases stay on lfplus_set_witness + lfplus_commit).  A value that does not fit k digits loses its remainder,
+ * as in the reference.  Waits for a pending lfplus_rg_from_f_async pass first.  After ANY error return the context has no resident witness. */
+int lfplus_witness_from_z(lfplus_ctx *ctx, const uint64_t *z, uint64_t m, uint64_t b, uint32_t k, uint64_t *cm_f);
+/* the same, then the pass alone `iters` times back to back, timed with HIP events on the library's stream (z resident): average ms */
+int lfplus_witness_from_z_timed(lfplus_ctx *ctx, const uint64_t *z, uint64_t m, uint64_t b, uint32_t k, uint32_t iters, double *ms_avg);
+/* Matrix::try_mul_vec on the RESIDENT witness (no upload): out = A f, kappa * 16 words.  Waits for a pending lfplus_rg_from_f_async pass first.  A sharded
+ * context is refused with LFPLUS_E_ARG (lfplus_commit is the call that exchanges the ranks' partial sums). */
+int lfplus_commit_resident(lfplus_ctx *ctx, uint64_t *out);
 
 /* RgInstance::from_f on the resident (A, f).  b >= 2 (digits must land in (-8, 8): b <= 14), 1 <= k <= 16, 1 <= l <= 64.
  * Results stay on the device until lfplus_rg_read. */

@@ -612,6 +612,118 @@ extern "C" int lfplus_get_witness(lfplus_ctx *c, uint64_t *f_out, uint64_t n) {
     HIPCHK(c, hipStreamSynchronize(c->st));
     return LFPLUS_OK;
 }
+// ---- ComR1CS::new on the device (r1cs.rs:48-60; kernel: lfp_ingest.hip) ----------------------------------------------------------------------------
+static void drop_witness(lfplus_ctx *c) {
+    (void)hipStreamSynchronize(c->st);
+    c->own_free(c->f);
+    c->f = nullptr;
+    c->nf = 0;
+    c->have = false;
+}
+static int witness_from_z_impl(lfplus_ctx *c, const uint64_t *z, uint64_t m, uint64_t b, uint32_t k, uint64_t *cm_f, u64 **dz, u32 iters, double *ms_avg) {
+    if (!z || !m) return fail(c, LFPLUS_E_ARG, "lfplus_witness_from_z: null / empty z");
+    if (!c->A) return fail(c, LFPLUS_E_ARG, "lfplus_witness_from_z: matrix not set");
+    if (c->sharded()) return fail(c, LFPLUS_E_ARG, "lfplus_witness_from_z: sharded contexts are not supported (upload f with lfplus_set_witness)");
+    if (b < 2 || b > (1ull << 31) || !k || k > 16) return fail(c, LFPLUS_E_ARG, "lfplus_witness_from_z: parameters outside the envelope (2 <= b <= 2^31, 1 <= k <= 16)");
+    if (m > c->n || m * k != c->n) return fail(c, LFPLUS_E_ARG, "lfplus_witness_from_z: m * k differs from the matrix width");
+    if (c->n > (1ull << 28)) return fail(c, LFPLUS_E_ARG, "lfplus_witness_from_z: more than 2^28 rows (the lazy 128-bit sums would no longer be exact)");
+    const u64 n = c->n;
+    if (!(c->f && c->nf == n)) {
+        c->own_free(c->f);
+        c->f = nullptr; c->nf = 0;
+        HIPCHK(c, c->own_alloc(&c->f, (size_t)n * 16 * 8));
+    }
+    c->nf = 0;                                  // no resident witness until the pass has completed
+    u64 JZ = (m + 2047) / 2048;                 // a streaming pass: up to 2048 blocks, whole tiles of 16 elements
+    JZ = (JZ + 15) / 16 * 16;
+    const u32 nblk = (u32)((m + JZ - 1) / JZ);
+    const size_t nout = (size_t)c->kappa * 16;
+    int rc = ensure_part(c, (size_t)nblk * nout + nout);
+    if (rc) return rc;
+    *dz = (u64 *)c->pool.get((size_t)m * 16 * 8);
+    if (!*dz) return fail(c, LFPLUS_E_HIP, "lfplus_witness_from_z: out of device memory");
+    u32 flag = 0;
+    HIPCHK(c, hipMemsetAsync(c->err_d, 0, 4, c->st));
+    HIPCHK(c, hipMemcpyAsync(*dz, z, (size_t)m * 16 * 8, hipMemcpyHostToDevice, c->st));
+    u64 *res = c->part + (size_t)nblk * nout;
+    auto enqueue = [&]() -> hipError_t {
+        for (u32 i0 = 0; i0 < c->kappa;) {
+            lfp::IngestArgs a;
+            a.z = *dz; a.A = c->A; a.f = c->f; a.m = m; a.n = n;
+            a.kappa = c->kappa; a.i0 = i0; a.icnt = lfp::group_size(c->kappa - i0);
+            a.k = k; a.b = b; a.sh = log2_exact(b); a.JZ = (u32)JZ;
+            a.part = c->part; a.err = c->err_d; a.first = i0 == 0;
+            hipError_t e = lfp::launch_ingest(a, nblk, c->st);
+            if (e != hipSuccess) return e;
+            i0 += a.icnt;
+        }
+        lfp::launch_reduce(c->part, nblk, (u32)nout, res, 0, c->kappa, 0, 2, 0, nullptr, c->st);
+        return hipGetLastError();
+    };
+    HIPCHK(c, enqueue());
+    if (cm_f) HIPCHK(c, hipMemcpyAsync(cm_f, res, nout * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(&flag, c->err_d, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (ms_avg && !(flag & 4u)) {      // the same pass `iters` times back to back between two events (z resident; it rewrites the same f)
+        hipEvent_t e0, e1;
+        HIPCHK(c, hipEventCreate(&e0));
+        HIPCHK(c, hipEventCreate(&e1));
+        HIPCHK(c, hipEventRecord(e0, c->st));
+        hipError_t e = hipSuccess;
+        for (u32 it = 0; it < iters && e == hipSuccess; it++) e = enqueue();
+        if (e == hipSuccess) e = hipEventRecord(e1, c->st);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        float ms = 0;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        HIPCHK(c, e);
+        *ms_avg = (double)ms / iters;
+    }
+    if (flag & 4u) return fail(c, LFPLUS_E_ARG, "lfplus_witness_from_z: non-canonical word");
+    c->nf = n;
+    return LFPLUS_OK;
+}
+static int witness_from_z(lfplus_ctx *c, const uint64_t *z, uint64_t m, uint64_t b, uint32_t k, uint64_t *cm_f, u32 iters, double *ms_avg) {
+    if (!c) return LFPLUS_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    ff_join(c);      // (an asynchronous from_f may still read the witness that is being replaced)
+    c->have = false;
+    u64 *dz = nullptr;
+    const int rc = witness_from_z_impl(c, z, m, b, k, cm_f, &dz, iters, ms_avg);
+    if (rc) {        // whatever failed: the context is left without a resident witness, never with a half-written one
+        const std::string keep = c->err;
+        drop_witness(c);
+        c->err = keep;
+    }
+    if (dz) c->pool.put(dz);
+    return rc;
+}
+extern "C" int lfplus_witness_from_z(lfplus_ctx *c, const uint64_t *z, uint64_t m, uint64_t b, uint32_t k, uint64_t *cm_f) {
+    return witness_from_z(c, z, m, b, k, cm_f, 0, nullptr);
+}
+// the same, then the pass alone `iters` times back to back, timed with HIP events on the library's stream (z resident): average ms
+extern "C" int lfplus_witness_from_z_timed(lfplus_ctx *c, const uint64_t *z, uint64_t m, uint64_t b, uint32_t k, uint32_t iters, double *ms_avg) {
+    if (!ms_avg || !iters) return fail(c, LFPLUS_E_ARG, "lfplus_witness_from_z_timed: bad arguments");
+    return witness_from_z(c, z, m, b, k, nullptr, iters, ms_avg);
+}
+extern "C" int lfplus_commit_resident(lfplus_ctx *c, uint64_t *out) {
+    if (!c || !out) return fail(c, LFPLUS_E_ARG, "lfplus_commit_resident: null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    ff_join(c);
+    if (c->sharded()) return fail(c, LFPLUS_E_ARG, "lfplus_commit_resident: sharded contexts are not supported (lfplus_commit exchanges the ranks' partial sums)");
+    if (!c->A || !c->f || c->nf != c->n) return fail(c, LFPLUS_E_ARG, "lfplus_commit_resident: matrix / witness not set or of different length");
+    Plan p = plan_for(c->nloc, c->kappa, 0);
+    int rc = ensure_part(c, (size_t)p.nblk * p.nout_f + p.nout_f);
+    if (rc) return rc;
+    u64 *res = c->part + (size_t)p.nblk * p.nout_f;
+    enqueue_phase1(c, c->f, 2, 0, p, c->part);
+    lfp::launch_reduce(c->part, p.nblk, (u32)p.nout_f, res, 0, c->kappa, 0, 2, 0, nullptr, c->st);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, res, p.nout_f * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return LFPLUS_OK;
+}
 extern "C" int lfplus_tensor(lfplus_ctx *c, const uint64_t *r, uint32_t n, uint64_t *out) {
     if (!c || !out || (n && !r) || n > 28) return fail(c, LFPLUS_E_ARG, "lfplus_tensor: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));

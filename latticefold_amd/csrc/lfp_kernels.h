@@ -43,6 +43,22 @@ void launch_mtau_all(const u64 *tau, u64 n, int8_t *mtau, u32 *err, hipStream_t 
 // out[o] = sum over blocks of part[blk][o] mod p; with l != 0 the first nsplit outputs (comM_f, [k][kappa][16][16]) are also cut into
 // their l gadget digits: tau = split(hconcat(comM_f), n, base, l) (utils.rs:12-43), positions [0, kappa*k*16*l*16)
 void launch_reduce(const u64 *part, u32 nblk, u32 nout, u64 *out, u32 nsplit, u32 kappa, u32 k, u64 base, u32 l, u64 *tau, hipStream_t s);
+// ComR1CS::new (lfp_ingest.hip): f = z.gadget_decompose(b, k) and the block partial sums of A f for rows [i0, i0 + icnt) of A
+struct IngestArgs {
+    const u64 *z;       // m x 16 words (checked for canonicity when first: bit 4 of err)
+    const u64 *A;       // kappa x n x 16
+    u64 *f;             // n x 16 canonical words, written when first
+    u64 m, n;           // n = m k
+    u32 kappa, i0, icnt;
+    u32 k;
+    u64 b;
+    int sh;             // log2(b) when b is a power of two, else -1
+    u32 JZ;             // z elements per block (multiple of 16)
+    u64 *part;          // [nblk][kappa*16] partial sums mod p
+    u32 *err;
+    int first;
+};
+hipError_t launch_ingest(const IngestArgs &a, u32 nblk, hipStream_t s);      // icnt in {1, 2, 4}; returns the launch's error
 // largest launch group (1, 2 or 4) not above `left`
 inline u32 group_size(u32 left) { return left >= 4 ? 4 : left >= 2 ? 2 : 1; }
 // Decomp::decompose (decomp.rs:32-99): base-B split, fix_variables over ring tables, sparse mat-vec with ring coefficients

@@ -14,6 +14,7 @@
 #include "lfp_kernels.h"
 #include "lf_field.cuh"
 #include "lfp_field.cuh"
+#include "lfp_dev.cuh"
 
 namespace lfp {
 using lf::AccP;
@@ -55,42 +56,8 @@ __device__ __forceinline__ void accp_zero(AccP &s) {
     s.c00 = s.c01 = s.c11 = 0;
 }
 
-// (r 2^64 + w) mod p for r < p: mont_mul(r, 2^128) = r 2^64
-__device__ __forceinline__ u64 red_word(u64 r, u64 w) { return add_p(mont_mul(r, R2), w >= P ? w - P : w); }
 __device__ __forceinline__ u64 mod_p_192(U192 x) { return red_word(red_word(x.w2 % P, x.w1), x.w0); }
 
-// balanced digit step (stark_rings::balanced_decomposition as restated in oracle/lfp.c: truncating remainder, |rem| <= b/2 kept)
-__device__ __forceinline__ int64_t digit_step(int64_t &cur, u64 b, int sh) {
-    int64_t q, rem;
-    if (sh >= 0) {
-        q = (cur + ((cur >> 63) & (int64_t)(b - 1))) >> sh;
-        rem = cur - (q << sh);
-    } else {
-        q = cur / (int64_t)b;
-        rem = cur - q * (int64_t)b;
-    }
-    int64_t half = (int64_t)(b >> 1), ar = rem < 0 ? -rem : rem;
-    if (ar > half) {
-        if (rem < 0) { rem += (int64_t)b; q -= 1; }
-        else { rem -= (int64_t)b; q += 1; }
-    }
-    cur = q;
-    return rem;
-}
-__device__ __forceinline__ int64_t centre(u64 v) { return v <= (P - 1) / 2 ? (int64_t)v : -(int64_t)(P - v); }
-
-// sum over the 16 row lanes (tid >> 4) of a value mod p held by thread (jl, t): two 16-lane shuffles inside each wave, LDS across waves;
-// valid in threads tid < 16
-__device__ __forceinline__ u64 sum_over_row_lanes(u64 v, u64 (*sh)[16], int tid) {
-    v = add_p(v, __shfl_xor(v, 16));
-    v = add_p(v, __shfl_xor(v, 32));
-    __syncthreads();
-    if ((tid & 63) < 16) sh[tid >> 6][tid & 15] = v;
-    __syncthreads();
-    u64 r = 0;
-    if (tid < 16) r = add_p(add_p(sh[0][tid], sh[1][tid]), add_p(sh[2][tid], sh[3][tid]));
-    return r;
-}
 // ICNT rows of A and KCNT digit planes per launch, both compile-time: the inner loops carry no predicates, so the LDS reads of a
 // whole 8-row group are in flight together.  The next tile's global loads are issued before the current tile is consumed.
 template <int ICNT, int KCNT>

@@ -53,6 +53,9 @@ def _lib():
         L.lfplus_last_error.restype = C.c_char_p
         L.lfplus_set_matrix.argtypes = [vp, u64p, C.c_uint32, C.c_uint64]
         L.lfplus_set_witness.argtypes = [vp, u64p, C.c_uint64]
+        L.lfplus_witness_from_z.argtypes = [vp, u64p, C.c_uint64, C.c_uint64, C.c_uint32, u64p]
+        L.lfplus_witness_from_z_timed.argtypes = [vp, u64p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
+        L.lfplus_commit_resident.argtypes = [vp, u64p]
         L.lfplus_rg_from_f.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32]
         L.lfplus_rg_from_f_async.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32]
         L.lfplus_join_async.argtypes = [vp]
@@ -213,6 +216,27 @@ class PlusContext:
         f, p = _w(f)
         assert f.ndim == 2 and f.shape[1] == D
         self._chk(_lib().lfplus_set_witness(self.h, p, f.shape[0]))
+
+    def witness_from_z(self, z, b, k):
+        """ComR1CS::new on the device (lfplus_witness_from_z): f = z.gadget_decompose(b, k) becomes the resident witness, only z is uploaded -> cm_f = A f"""
+        z, p = _w(z)
+        assert z.ndim == 2 and z.shape[1] == D
+        out = np.zeros((self.kappa, D), dtype=np.uint64)
+        self._chk(_lib().lfplus_witness_from_z(self.h, p, z.shape[0], int(b), int(k), out.ctypes.data_as(u64p)))
+        return out
+
+    def time_witness_from_z(self, z, b, k, iters):
+        """lfplus_witness_from_z_timed: HIP-event milliseconds of the ingestion pass alone (z resident), averaged over `iters`"""
+        z, p = _w(z)
+        ms = C.c_double()
+        self._chk(_lib().lfplus_witness_from_z_timed(self.h, p, z.shape[0], int(b), int(k), int(iters), C.byref(ms)))
+        return ms.value
+
+    def commit_resident(self):
+        """Matrix::try_mul_vec on the resident witness (lfplus_commit_resident: no upload)"""
+        out = np.zeros((self.kappa, D), dtype=np.uint64)
+        self._chk(_lib().lfplus_commit_resident(self.h, out.ctypes.data_as(u64p)))
+        return out
 
     def commit(self, v):
         """Matrix::try_mul_vec"""
@@ -645,12 +669,14 @@ def r1cs_decomposed_square(r1cs, n, b, k):
 
 @dataclass
 class ComR1CS:
-    """r1cs.rs:21-58: r1cs = (A, B, C) CSR matrices (n x n), z the short witness, f = z.gadget_decompose(b, k), cm_f = A f"""
+    """r1cs.rs:21-58: r1cs = (A, B, C) CSR matrices (n x n), z the short witness, f = z.gadget_decompose(b, k), cm_f = A f.
+    A RESIDENT instance (new_resident) has f = None: the witness was cut on the device and lives in `ctx`, until that context gets another witness"""
     r1cs: tuple
     z: np.ndarray
     f: np.ndarray
     cm_f: np.ndarray
     l_in: int = 1
+    ctx: object = None
 
     @staticmethod
     def new(ctx, r1cs, z, l_in, b, k, A=None):
@@ -658,6 +684,17 @@ class ComR1CS:
             ctx.set_matrix(A)
         f = gadget_decompose(z, b, k)
         return ComR1CS(tuple(r1cs), np.asarray(z, dtype=np.uint64), f, ctx.commit(f), l_in)
+
+    @staticmethod
+    def new_resident(ctx, r1cs, z, l_in, b, k):
+        """ComR1CS::new with f cut and committed on the device (PlusContext.witness_from_z): only z crosses PCIe, f stays in `ctx` and is not downloaded
+        (fetch_f reads it back)"""
+        z = np.ascontiguousarray(z, dtype=np.uint64)
+        return ComR1CS(tuple(r1cs), z, None, ctx.witness_from_z(z, b, k), l_in, ctx)
+
+    def fetch_f(self):
+        """f as a host array: of a resident instance, read back from its context (which must still hold it)"""
+        return self.f if self.f is not None else self.ctx.get_witness()
 
     def matrices(self):
         return list(self.r1cs)
@@ -667,11 +704,14 @@ class ComR1CS:
         matrices are the ones ctx.set_matrices / share_matrices left on the device; preloaded: ctx.set_witness(self.f) was already called (PlusProver.preload);
         from_f_hint: DecompParameters of the Mlin::mlin that follows -- the double commitment of this witness is enqueued on the context's second stream now
         (lfplus_rg_from_f_async) and runs next to the sumcheck rounds"""
-        if not preloaded:
+        if self.f is None:
+            if ctx is not self.ctx:
+                raise LfPlusError(E_ARG, "ComR1CS.linearize: a resident instance is linearized in the context that holds its witness")
+        elif not preloaded:
             ctx.set_witness(self.f)
         if from_f_hint is not None:
             ctx.rg_from_f_async(from_f_hint)
-        n = self.f.shape[0]
+        n = ctx.n if self.f is None else self.f.shape[0]
         nvars = n.bit_length() - 1
         keep, rp, cp, vp = _csr_args(RESIDENT(3) if resident else self.r1cs)
         msgs, ro, ev = np.zeros((nvars, 4, D), dtype=np.uint64), np.zeros(nvars, dtype=np.uint64), np.zeros((4, D), dtype=np.uint64)
@@ -787,6 +827,23 @@ class PlusProver:
             self.ctxs[nacc + i].set_witness(ci.f)
         self._preloaded = [ci.f for ci in comp]
 
+    def ingest(self, zs, r1cs, l_in=1):
+        """The fresh instances of the next prove, built in the contexts that prove will use (ComR1CS.new_resident in ctxs[nacc + i]: z is uploaded, cut into
+        f = z.gadget_decompose(B, k) and committed on the device) -> the ComR1CS list; prove(comps) then neither uploads nor reads a host f.  Not for a sharded
+        prover.  A prover whose ingest raised is failed, as one whose prove raised (a context may be left without its witness)."""
+        if self.failed is not None:
+            raise LfPlusError(E_ARG, f"PlusProver.ingest: this prover failed earlier ({self.failed}) -- build a new prover")
+        nacc = len(self.acc)
+        if nacc + len(zs) > len(self.ctxs):
+            raise LfPlusError(E_ARG, "PlusProver.ingest: more instances than contexts (ncomp)")
+        try:
+            comps = [ComR1CS.new_resident(self.ctxs[nacc + i], r1cs, z, l_in, self.params.B, self.params.lin.decomp.k) for i, z in enumerate(zs)]
+        except Exception as ex:
+            self.failed = repr(ex)
+            raise
+        self._preloaded = list(comps)
+        return comps
+
     def accumulator(self):
         """(F0, F1) of the last prove as host arrays"""
         if self.device_acc and self.acc:
@@ -810,8 +867,12 @@ class PlusProver:
     def _prove(self, comp, nacc):
         ctxs = self.ctxs[:nacc + len(comp)]
         lproof = []
-        pre = self._preloaded is not None and len(self._preloaded) == len(comp) and all(a is ci.f for a, ci in zip(self._preloaded, comp))
+        # preloaded: by preload (the same host arrays) or by ingest (the same resident instances, each in the context it is folded from)
+        pre = self._preloaded is not None and len(self._preloaded) == len(comp) and all(
+            (a is ci and ci.ctx is self.ctxs[nacc + i]) if ci.f is None else a is ci.f for i, (a, ci) in enumerate(zip(self._preloaded, comp)))
         self._preloaded = None
+        if not pre and any(ci.f is None for ci in comp):
+            raise LfPlusError(E_ARG, "PlusProver.prove: resident instances must come from this prover's last ingest, in its order")
         # RgInstance::from_f of every instance (Mlin::mlin, mlin.rs:52-60) needs no challenge: each is enqueued on its context's second stream as soon as the
         # witness is resident and runs next to the linearizations' latency-bound rounds; lfplus_mlin collects the results
         dp = self.params.lin.decomp
