@@ -1,4 +1,4 @@
-// bb_host.cpp -- BabyBearRingNTT: ring tables, small host ring ops, Poseidon, transcript (see bb_host.h).
+// bb_host.cpp -- BabyBearRingNTT: ring tables, small host ring ops, Poseidon (shared pieces in poseidon_host.h), transcript (see bb_host.h).
 #include "bb_host.h"
 
 #include <stdlib.h>
@@ -7,7 +7,6 @@
 #include <mutex>
 #include <utility>
 
-#include "lf_host.h"   // lf::Transcript::params: the Grain-generated 64-bit Poseidon table shared by both rings
 #if defined(__AVX2__) && !defined(__HIP_DEVICE_COMPILE__)
 #include "bb_poseidon_simd.h"
 #define BB_POSEIDON_SIMD 1
@@ -15,9 +14,8 @@
 
 namespace lfbb {
 
-namespace simd512 {   // bb_poseidon_avx512.cc (host-only translation unit, entered after a cpuid check)
-bool supported();
-void build(const u64 *ark, const u64 *mds, const u64 *cst, const u64 *e00, const u64 *row, const u64 *col, const u64 *post);
+namespace simd512 {   // bb_poseidon_avx512.cc (host-only translation unit, entered only where poseidon::avx512_ifma_supported())
+void build(const poseidon::Table &t, const poseidon::Collapsed &c);
 void permute(u64 st[24]);
 }  // namespace simd512
 
@@ -227,18 +225,11 @@ void bb_balanced_digits(u64 v, u64 base, unsigned digits, int64_t *out, int mode
 // Poseidon over BabyBear: the reference table (rings/poseidon/babybear.rs:7-1425) holds the SAME 64-bit literals as the
 // Goldilocks table, embedded with Fq::from(i128) -- i.e. the Grain-generated Goldilocks constants reduced mod p_BB.
 namespace {
-constexpr int W = 24, RATE = 20, CAP = 4, RF = 8, RP = 22;
-u64 g_ark[(RF + RP) * W];
-u64 g_mds[W * W];
+using namespace poseidon;   // W, RATE, CAP, RF, RP, Table, Sparse
+Table g_tab;
+u64 (&g_ark)[(RF + RP) * W] = g_tab.ark, (&g_mds)[W * W] = g_tab.mds;
 std::once_flag g_once;
-struct PartialOpt {
-    u64 cst[RP][W];
-    u64 e00[RP];
-    u64 row[RP][W - 1];
-    u64 col[RP][W - 1];
-    u64 post[W - 1][W - 1];
-};
-PartialOpt g_opt;
+Sparse g_opt;   // sparse factorisation of the partial rounds
 
 inline u64 sbox(u64 x) {
     u64 x2 = hmul(x, x), x3 = hmul(x2, x), x4 = hmul(x2, x2);
@@ -278,67 +269,10 @@ int g_path = 0;           // 0 scalar, 1 AVX2 (bb_poseidon_simd.h), 2 AVX-512 IF
 u32 g_mdsT[24][24];       // MDS transposed
 u32 g_postT[24][24];      // deferred factor of the sparse partial rounds, transposed (23 x 23 used)
 
-bool mat_inv(const u64 *in, u64 *out, int n) {
-    std::vector<u64> M((size_t)n * 2 * n, 0);
-    for (int r = 0; r < n; r++) {
-        for (int c = 0; c < n; c++) M[(size_t)r * 2 * n + c] = in[r * n + c];
-        M[(size_t)r * 2 * n + n + r] = 1;
-    }
-    for (int col = 0; col < n; col++) {
-        int piv = -1;
-        for (int r = col; r < n; r++)
-            if (M[(size_t)r * 2 * n + col]) { piv = r; break; }
-        if (piv < 0) return false;
-        if (piv != col)
-            for (int c = 0; c < 2 * n; c++) std::swap(M[(size_t)piv * 2 * n + c], M[(size_t)col * 2 * n + c]);
-        u64 inv = hinv(M[(size_t)col * 2 * n + col]);
-        for (int c = 0; c < 2 * n; c++) M[(size_t)col * 2 * n + c] = hmul(M[(size_t)col * 2 * n + c], inv);
-        for (int r = 0; r < n; r++) {
-            u64 f = M[(size_t)r * 2 * n + col];
-            if (r == col || !f) continue;
-            for (int c = 0; c < 2 * n; c++) M[(size_t)r * 2 * n + c] = hsub(M[(size_t)r * 2 * n + c], hmul(f, M[(size_t)col * 2 * n + c]));
-        }
-    }
-    for (int r = 0; r < n; r++)
-        for (int c = 0; c < n; c++) out[r * n + c] = M[(size_t)r * 2 * n + n + c];
-    return true;
-}
-// sparse factorisation of the partial rounds (Poseidon paper, optimised partial rounds): M*diag(1,E) = diag(1,E')*[[e00,row],[col,I]]
 void init_all() {
-    const u64 *ga, *gm;
-    lf::Transcript::params(&ga, &gm);
-    for (int i = 0; i < (RF + RP) * W; i++) g_ark[i] = ga[i] % BB_P;
-    for (int i = 0; i < W * W; i++) g_mds[i] = gm[i] % BB_P;
     const int n = W - 1;
-    std::vector<u64> Eprev((size_t)n * n, 0), EprevInv((size_t)n * n, 0), eff((size_t)W * W), Eh((size_t)n * n), Ei((size_t)n * n);
-    for (int i = 0; i < n; i++) Eprev[(size_t)i * n + i] = EprevInv[(size_t)i * n + i] = 1;
-    for (int r = 0; r < RP; r++) {
-        const u64 *c = g_ark + (size_t)(RF / 2 + r) * W;
-        g_opt.cst[r][0] = c[0];
-        for (int i = 0; i < n; i++) g_opt.cst[r][1 + i] = dot(&EprevInv[(size_t)i * n], c + 1, n);
-        for (int i = 0; i < W; i++) {
-            eff[(size_t)i * W] = g_mds[i * W];
-            for (int j = 0; j < n; j++) {
-                u64 acc = 0;
-                for (int k = 0; k < n; k++) acc = hadd(acc, hmul(g_mds[i * W + 1 + k], Eprev[(size_t)k * n + j]));
-                eff[(size_t)i * W + 1 + j] = acc;
-            }
-        }
-        for (int i = 0; i < n; i++)
-            for (int j = 0; j < n; j++) Eh[(size_t)i * n + j] = eff[(size_t)(1 + i) * W + 1 + j];
-        if (!mat_inv(Eh.data(), Ei.data(), n)) abort();
-        g_opt.e00[r] = eff[0];
-        for (int j = 0; j < n; j++) g_opt.row[r][j] = eff[1 + j];
-        for (int i = 0; i < n; i++) {
-            u64 acc = 0;
-            for (int k = 0; k < n; k++) acc = hadd(acc, hmul(Ei[(size_t)i * n + k], eff[(size_t)(1 + k) * W]));
-            g_opt.col[r][i] = acc;
-        }
-        Eprev = Eh;
-        EprevInv = Ei;
-    }
-    for (int i = 0; i < n; i++)
-        for (int j = 0; j < n; j++) g_opt.post[i][j] = Eprev[(size_t)i * n + j];
+    reduced_table<BbField>(g_tab);
+    if (!sparse_partial<BbField>(g_tab, g_opt)) abort();
     memset(g_mdsT, 0, sizeof(g_mdsT));
     memset(g_postT, 0, sizeof(g_postT));
     for (int i = 0; i < W; i++)
@@ -350,8 +284,10 @@ void init_all() {
     simd::build_tables(g_simd, g_ark, g_mds, g_opt.cst, g_opt.e00, g_opt.row, g_opt.col, g_opt.post);
     g_path = 1;
 #endif
-    if (simd512::supported() && !getenv("LF_POSEIDON_AVX2")) {
-        simd512::build(g_ark, g_mds, &g_opt.cst[0][0], g_opt.e00, &g_opt.row[0][0], &g_opt.col[0][0], &g_opt.post[0][0]);
+    if (avx512_ifma_supported() && !getenv("LF_POSEIDON_AVX2")) {
+        Collapsed c;
+        collapse_partial<BbField>(g_tab, g_opt, c);
+        simd512::build(g_tab, c);
         g_path = 2;
     }
 }
@@ -370,16 +306,7 @@ void BbTranscript::params(const u64 **ark, const u64 **mds) {
 }
 void BbTranscript::permute_plain(u64 st[24]) {
     std::call_once(g_once, init_all);
-    u64 nw[W];
-    for (int r = 0; r < RF + RP; r++) {
-        const u64 *ark = g_ark + r * W;
-        bool full = r < RF / 2 || r >= RF / 2 + RP;
-        for (int i = 0; i < W; i++) st[i] = hadd(st[i], ark[i]);
-        if (full) for (int i = 0; i < W; i++) st[i] = sbox(st[i]);
-        else st[0] = sbox(st[0]);
-        for (int i = 0; i < W; i++) nw[i] = dot(st, g_mds + i * W, W);
-        memcpy(st, nw, sizeof(nw));
-    }
+    poseidon::permute_plain<BbField>(g_tab, st);
 }
 void BbTranscript::permute(u64 st[24]) {
     std::call_once(g_once, init_all);
@@ -408,53 +335,9 @@ void BbTranscript::permute_scalar(u64 st[24]) {
     for (int r = RF / 2 + RP; r < RF + RP; r++) full_round(st, g_ark + r * W);
 }
 
-BbTranscript::BbTranscript() : squeezing_(false), idx_(0) {
-    std::call_once(g_once, init_all);
-    memset(st_, 0, sizeof(st_));
-}
-void BbTranscript::absorb_fq(const u64 *x, size_t n) {
-    if (!n) return;
-    int idx;
-    if (!squeezing_) {
-        idx = idx_;
-        if (idx == RATE) { permute(st_); idx = 0; }
-    } else {
-        permute(st_);
-        idx = 0;
-    }
-    for (;;) {
-        if ((size_t)idx + n <= (size_t)RATE) {
-            for (size_t i = 0; i < n; i++) st_[CAP + idx + i] = hadd(st_[CAP + idx + i], x[i] % BB_P);
-            squeezing_ = false;
-            idx_ = idx + (int)n;
-            return;
-        }
-        size_t take = RATE - idx;
-        for (size_t i = 0; i < take; i++) st_[CAP + idx + i] = hadd(st_[CAP + idx + i], x[i] % BB_P);
-        permute(st_);
-        x += take; n -= take; idx = 0;
-    }
-}
-void BbTranscript::squeeze(u64 *out, size_t n) {
-    int idx;
-    if (!squeezing_) { permute(st_); idx = 0; }
-    else {
-        idx = idx_;
-        if (idx == RATE) { permute(st_); idx = 0; }
-    }
-    for (;;) {
-        if ((size_t)idx + n <= (size_t)RATE) {
-            memcpy(out, st_ + CAP + idx, n * sizeof(u64));
-            squeezing_ = true;
-            idx_ = idx + (int)n;
-            return;
-        }
-        size_t take = RATE - idx;
-        memcpy(out, st_ + CAP + idx, take * sizeof(u64));
-        if (n != (size_t)RATE) permute(st_);
-        out += take; n -= take; idx = 0;
-    }
-}
+BbTranscript::BbTranscript() { std::call_once(g_once, init_all); }
+void BbTranscript::absorb_fq(const u64 *x, size_t n) { sp_.absorb(x, n); }
+void BbTranscript::squeeze(u64 *out, size_t n) { sp_.squeeze(out, n); }
 static void basis9(const u64 *M, const u64 *v, u64 *o) {   // o = M v over F_p, 9x9 (words < 2^31)
     for (int i = 0; i < TAU; i++) {
         u64 acc = 0;

@@ -1,5 +1,6 @@
 // bb_host.h -- host-side pieces of the BabyBearRingNTT backend: ring tables (data-driven CRT), ring operations on a
-// handful of elements (canonical u64 words, plain % arithmetic: O(proof size) only), Poseidon + Fiat-Shamir transcript.
+// handful of elements (canonical u64 words, plain % arithmetic: O(proof size) only), Poseidon + Fiat-Shamir transcript (sponge and table
+// builders: poseidon_host.h).
 // Reference anchors: cyclotomic-rings/src/rings/babybear.rs:1-68 (ring aliases, challenge set),
 // rings/poseidon/babybear.rs:7-1425 (Poseidon parameters), latticefold/src/transcript/poseidon.rs:29-75.
 #pragma once
@@ -7,6 +8,7 @@
 #include <vector>
 
 #include "bb_field.cuh"
+#include "poseidon_host.h"
 
 namespace lfbb {
 
@@ -48,6 +50,14 @@ struct BbHostRing {
 };
 void bb_balanced_digits(u64 v, u64 base, unsigned digits, int64_t *out, int mode = 0);
 
+struct BbField {   // field policy of poseidon_host.h
+    static constexpr u64 P = BB_P;
+    static u64 add(u64 a, u64 b) { return hadd(a, b); }
+    static u64 sub(u64 a, u64 b) { return hsub(a, b); }
+    static u64 mul(u64 a, u64 b) { return hmul(a, b); }
+    static u64 inv(u64 a) { return hinv(a); }
+    static u64 from_word(u64 x) { return x % BB_P; }
+};
 class BbTranscript {
   public:
     BbTranscript();
@@ -68,9 +78,7 @@ class BbTranscript {
     void squeeze(u64 *out, size_t n);   // raw field elements of the sponge (lf_transcript_squeeze_bytes)
 
   private:
-    u64 st_[24];
-    bool squeezing_;
-    int idx_;
+    poseidon::Sponge<BbField, &BbTranscript::permute> sp_;
     const u64 *bT_ = nullptr, *bTi_ = nullptr;
 };
 

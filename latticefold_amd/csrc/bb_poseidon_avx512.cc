@@ -7,7 +7,7 @@
 //  * dense mat-vec: the 62-bit products x_j * M_ij are accumulated as 52-bit halves with vpmadd52luq / vpmadd52huq
 //    (46 terms + a seed stay below 2^58), one Montgomery reduction per output word; the constants of the next full round enter
 //    as the seed of the mat-vec (times R);
-//  * the 22 partial rounds are collapsed by linearity (as in lf_poseidon_simd.cc): D = SX x (one mat-vec up front), a scalar
+//  * the 22 partial rounds are collapsed by linearity (poseidon::collapse_partial): D = SX x (one mat-vec up front), a scalar
 //    chain over word 0,  s_{r+1} = D_r + K_r + sum_{i<=r} G[r][i] X_i,  X_r = sbox(s_r + c_r),  and a closing map over
 //    [x ; X].  The chain is the only sequential part and is kept at three dependent products per round: G[r][r] x^7 is formed as
 //    ((G x) x^2) x^4 next to x^7 itself; everything else of s_{r+1} -- D, constants, the cross terms sum_{i<r} -- is prepared while
@@ -17,6 +17,8 @@
 #include <immintrin.h>
 #include <stdint.h>
 #include <string.h>
+
+#include "poseidon_host.h"
 
 namespace lfbb {
 namespace simd512 {
@@ -32,13 +34,12 @@ constexpr u32 PINV = 0x88000001u;            // p^-1 mod 2^32
 constexpr u32 NEGPINV = 0x77FFFFFFu;          // -p^-1 mod 2^32
 constexpr u64 R1 = (1ull << 32) % P;
 constexpr u64 R2 = (R1 * R1) % P;
-constexpr int W = 24, RF = 8, RP = 22, NX = W + RP;
+using poseidon::W; using poseidon::RF; using poseidon::RP; using poseidon::NX;
 
 struct Tables {
     alignas(64) u64 mds[W][W];        // [j][i] = Montgomery form of M[i][j]
     alignas(64) u64 arkf[RF][W];      // constants of the full rounds (Montgomery form)
     alignas(64) u64 arks[RF][W];      // ... times R: the seed of the mat-vec in front of that round
-    alignas(64) u64 sx[W][W];         // [j][r] = coefficient of state word j in D_r (column 0 and lanes >= 22 zero)
     alignas(64) u64 fin[NX][W];       // closing map, [j][i]: columns 0..23 state words, 24..45 the S-box outputs X_r; lane 0 zero
     alignas(64) u64 sxm[W][W];        // SX M (rows 0..21) and row 0 of M in lane 22: D and word 0 straight from the S-box outputs of the last full round
     alignas(64) u64 finm[W][W];       // (state columns of the closing map) M
@@ -159,89 +160,33 @@ inline void full_round(V x[3], const u64 *seed) {
     sbox_layer(x);
     matvec(T.mds, x, seed);
 }
-// canonical host arithmetic for build()
-inline u64 hadd(u64 a, u64 b) { u64 s = a + b; return s >= P ? s - P : s; }
-inline u64 hmul(u64 a, u64 b) { return a * b % P; }
 }  // namespace
 
-bool supported() {
-    static const bool ok = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512ifma") && __builtin_cpu_supports("avx512dq");
-    return ok;
-}
-
-// canonical parameter tables (the numbers bb_host.cpp uses): ark[30*24], mds[24*24] row-major, cst[22*24], e00[22], row[22*23],
-// col[22*23], post[23*23] row-major
-void build(const u64 *ark, const u64 *mds, const u64 *cst, const u64 *e00, const u64 *row, const u64 *col, const u64 *post) {
+// the BabyBear table and its collapsed partial rounds (canonical words) -> Montgomery lanes
+void build(const poseidon::Table &t, const poseidon::Collapsed &c) {
     memset(&T, 0, sizeof(T));
     for (int i = 0; i < W; i++)
-        for (int j = 0; j < W; j++) T.mds[j][i] = to_mont(mds[i * W + j]);
+        for (int j = 0; j < W; j++) T.mds[j][i] = to_mont(t.mds[i * W + j]);
     for (int r = 0; r < RF; r++) {
         int src = r < RF / 2 ? r : RP + r;
         for (int i = 0; i < W; i++) {
-            T.arkf[r][i] = to_mont(ark[(size_t)src * W + i]);
+            T.arkf[r][i] = to_mont(t.ark[(size_t)src * W + i]);
             T.arks[r][i] = to_mont(T.arkf[r][i]);
         }
     }
     T.ark40 = (u32)T.arkf[RF / 2][0];
-    // Symbolic run of the 22 sparse partial rounds (canonical numbers).  Every state word 1..23 is an affine form over
-    //   [ x_1..x_23 (words on entry) | X_0..X_21 (S-box outputs of word 0) | 1 ]
-    // because a partial round is  xs = state[1..] + cst_r,  X_r = sbox(s0 + c0_r),  s0' = e00_r X_r + row_r . xs,
-    // state'[1..] = xs + col_r X_r -- linear except for the S-box.  Collecting coefficients turns the rounds into
-    //   D = SX x (one mat-vec up front),  s0_{r+1} = D_r + K_r + sum_{i<=r} G[r][i] X_i (scalar chain),
-    //   state' = diag(1, post) [s0_22 ; x + CX X + ck] (one closing mat-vec over [x ; X]).
-    const int n = W - 1, NB = n + RP + 1;   // basis size
-    static u64 form[W - 1][W - 1 + RP + 1];
-    static u64 G[RP][RP], K[RP], sxc[W][W], finc[W][W];
-    memset(form, 0, sizeof(form));
-    memset(G, 0, sizeof(G));
-    memset(sxc, 0, sizeof(sxc));
-    memset(finc, 0, sizeof(finc));
-    for (int i = 0; i < n; i++) { form[i][i] = 1; form[i][NB - 1] = cst[0 * W + 1 + i] % P; }
-    for (int r = 0; r < RP; r++) {
-        T.cst0[r] = to_mont(cst[r * W]);
-        u64 dotf[W - 1 + RP + 1];
-        for (int b = 0; b < NB; b++) {
-            u64 a = 0;
-            for (int i = 0; i < n; i++) a = hadd(a, hmul(row[r * n + i] % P, form[i][b]));
-            dotf[b] = a;
-        }
-        for (int j = 0; j < n; j++) { T.sx[1 + j][r] = to_mont(dotf[j]); sxc[1 + j][r] = dotf[j]; }
-        for (int i = 0; i < r; i++) G[r][i] = dotf[n + i];
-        G[r][r] = e00[r] % P;
-        K[r] = dotf[NB - 1];
-        for (int i = 0; i < n; i++) {
-            form[i][n + r] = hadd(form[i][n + r], col[r * n + i] % P);
-            if (r + 1 < RP) form[i][NB - 1] = hadd(form[i][NB - 1], cst[(r + 1) * W + 1 + i] % P);
-        }
-    }
-    // closing map: words 1..23 = post * form
-    for (int i = 0; i < n; i++)
-        for (int b = 0; b < NB; b++) {
-            u64 a = 0;
-            for (int k = 0; k < n; k++) a = hadd(a, hmul(post[i * n + k] % P, form[k][b]));
-            if (b < n) { T.fin[1 + b][1 + i] = to_mont(a); finc[1 + b][1 + i] = a; }
-            else if (b < n + RP) T.fin[W + (b - n)][1 + i] = to_mont(a);
-            else T.fks[1 + i] = to_mont(sadd(to_mont(a), (u32)T.arkf[RF / 2][1 + i]));   // (constant + next round's constant) R
-        }
-    for (int r = 0; r < RP; r++) {
-        T.Gd[r] = to_mont(G[r][r]);
-        T.Gs[r] = r ? to_mont(G[r][r - 1]) : 0;
-        T.Kc[r] = sadd(to_mont(K[r]), r + 1 < RP ? T.cst0[r + 1] : 0);
-        for (int q = r + 2; q < RP; q++) T.e[r][q] = to_mont(G[q][r]);
-    }
-    // The mat-vec of the full round in front of the partial rounds is folded into what consumes its output: x = M s, D = (SX M) s, closing-map part
-    // (FIN_x M) s, word 0 = (row 0 of M) s in lane 22 of the D table: two mat-vecs over s instead of three
+    for (int j = 0; j < NX; j++)
+        for (int i = 0; i < W; i++) T.fin[j][i] = to_mont(c.fin[j][i]);
     for (int j = 0; j < W; j++)
-        for (int r = 0; r < W; r++) {
-            u64 a = 0, b = 0;
-            for (int i = 0; i < W; i++) {
-                a = hadd(a, hmul(sxc[i][r], mds[i * W + j] % P));
-                b = hadd(b, hmul(finc[i][r], mds[i * W + j] % P));
-            }
-            if (r == RP) a = mds[0 * W + j] % P;
-            T.sxm[j][r] = to_mont(a);
-            T.finm[j][r] = to_mont(b);
-        }
+        for (int i = 0; i < W; i++) { T.sxm[j][i] = to_mont(c.sxm[j][i]); T.finm[j][i] = to_mont(c.finm[j][i]); }
+    for (int i = 1; i < W; i++) T.fks[i] = to_mont(sadd(to_mont(c.fk[i]), (u32)T.arkf[RF / 2][i]));   // (constant + next round's constant) R
+    for (int r = 0; r < RP; r++) {
+        T.cst0[r] = to_mont(c.cst0[r]);
+        T.Gd[r] = to_mont(c.G[r][r]);
+        T.Gs[r] = r ? to_mont(c.G[r][r - 1]) : 0;
+        T.Kc[r] = to_mont(c.Kc[r]);
+        for (int q = r + 2; q < RP; q++) T.e[r][q] = to_mont(c.G[q][r]);
+    }
 }
 
 void permute(u64 st[24]) {

@@ -1,5 +1,5 @@
 // bb_poseidon_simd.h -- AVX2 implementation of the BabyBear Poseidon permutation (width 24, 8 full + 22 partial rounds,
-// alpha 7; same sparse partial-round factorisation as bb_host.cpp).  The transcript of a BabyBear fold step needs ~5300
+// alpha 7; partial rounds in the sparse form of poseidon::sparse_partial).  The transcript of a BabyBear fold step needs ~5300
 // permutations (a ring element is 72 words = 3.6 permutations), all on the host and partly on the critical path.
 //
 // State: three __m256i of eight 32-bit Montgomery words (R = 2^32) in [0, p).  The dense mat-vecs broadcast one state word
@@ -59,7 +59,7 @@ struct Tables {
     alignas(32) u32 col[22][24];         // lane 0 = 0
 };
 
-// load canonical parameter tables (same numbers bb_host.cpp uses) into Montgomery vector form
+// load the canonical parameter tables (the BabyBear table and its poseidon::Sparse members) into Montgomery vector form
 static inline void build_tables(Tables &T, const u64 *ark /*30x24*/, const u64 *mds /*24x24*/, const u64 (*cst)[24], const u64 *e00,
                                 const u64 (*row)[23], const u64 (*col)[23], const u64 (*post)[23]) {
     memset(&T, 0, sizeof(T));

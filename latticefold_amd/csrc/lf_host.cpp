@@ -1,4 +1,4 @@
-// lf_host.cpp -- ring tables, small host ring ops, Poseidon (Grain-generated constants), transcript.
+// lf_host.cpp -- ring tables, small host ring ops, Poseidon (Grain-generated constants; shared pieces in poseidon_host.h), transcript.
 // Reference anchors: cyclotomic-rings/src/rings.rs:28-40 (CRT splitting), rings/goldilocks.rs:36-68
 // (challenge set), rings/poseidon/goldilocks.rs:7-1425 (Poseidon parameters: regenerated, not copied),
 // latticefold/src/transcript/poseidon.rs:29-75 (transcript), ark-crypto-primitives 0.4.0 PoseidonSponge.
@@ -185,11 +185,12 @@ void balanced_digits(u64 v, u64 base, unsigned digits, int64_t *out, int mode) {
 
 // ---------------------------------------------------------------------------------------------------------
 // Poseidon: width 24 (rate 20 + capacity 4), 8 full + 22 partial rounds, alpha = 7; round constants and the
-// Cauchy MDS matrix come from the Poseidon Grain LFSR (n = 64, t = 24, R_F = 8, R_P = 22).
+// Cauchy MDS matrix come from the Poseidon Grain LFSR (n = 64, t = 24, R_F = 8, R_P = 22).  The table builders, the textbook permutation and the
+// sponge are poseidon_host.h; here: the Grain generator and the scalar sparse permutation with the Goldilocks reductions.
 namespace {
-constexpr int W = 24, RATE = 20, CAP = 4, RF = 8, RP = 22;
-u64 g_ark[(RF + RP) * W];
-u64 g_mds[W * W];
+using namespace poseidon;   // W, RATE, CAP, RF, RP, Table, Sparse
+Table g_tab;
+u64 (&g_ark)[(RF + RP) * W] = g_tab.ark, (&g_mds)[W * W] = g_tab.mds;
 std::once_flag g_once;
 
 struct Grain {
@@ -292,85 +293,17 @@ inline void matvec_fq(const u64 *M, int ld, int n, const u64 *x, u64 *out) {
 #endif
 }
 
-// Partial rounds through the sparse factorisation M*diag(1,E) = diag(1,E') * [[e00, row],[col, I]] (Poseidon paper,
-// appendix on optimised partial rounds): identical output, 47 instead of 576 multiplications per partial round.
-struct PartialOpt {
-    u64 cst[RP][W];       // round constants pulled through the deferred block-diagonal factor
-    u64 e00[RP];
-    u64 row[RP][W - 1];
-    u64 col[RP][W - 1];
-    u64 post[W - 1][W - 1];  // deferred factor applied once after the last partial round
-};
-PartialOpt g_opt;
-
-bool mat_inv(const u64 *in, u64 *out, int n) {  // Gauss-Jordan over F_p
-    std::vector<u64> M((size_t)n * 2 * n, 0);
-    for (int r = 0; r < n; r++) {
-        for (int c = 0; c < n; c++) M[(size_t)r * 2 * n + c] = in[r * n + c];
-        M[(size_t)r * 2 * n + n + r] = 1;
-    }
-    for (int col = 0; col < n; col++) {
-        int piv = -1;
-        for (int r = col; r < n; r++)
-            if (M[(size_t)r * 2 * n + col]) { piv = r; break; }
-        if (piv < 0) return false;
-        if (piv != col)
-            for (int c = 0; c < 2 * n; c++) std::swap(M[(size_t)piv * 2 * n + c], M[(size_t)col * 2 * n + c]);
-        u64 inv = fq_inv(M[(size_t)col * 2 * n + col]);
-        for (int c = 0; c < 2 * n; c++) M[(size_t)col * 2 * n + c] = fq_mul(M[(size_t)col * 2 * n + c], inv);
-        for (int r = 0; r < n; r++) {
-            u64 f = M[(size_t)r * 2 * n + col];
-            if (r == col || !f) continue;
-            for (int c = 0; c < 2 * n; c++) M[(size_t)r * 2 * n + c] = fq_sub(M[(size_t)r * 2 * n + c], fq_mul(f, M[(size_t)col * 2 * n + c]));
-        }
-    }
-    for (int r = 0; r < n; r++)
-        for (int c = 0; c < n; c++) out[r * n + c] = M[(size_t)r * 2 * n + n + c];
-    return true;
-}
-
-void partial_opt_init() {
-    const int n = W - 1;
-    std::vector<u64> Eprev((size_t)n * n, 0), EprevInv((size_t)n * n, 0), eff((size_t)W * W), Eh((size_t)n * n), Ei((size_t)n * n);
-    for (int i = 0; i < n; i++) Eprev[(size_t)i * n + i] = EprevInv[(size_t)i * n + i] = 1;
-    for (int r = 0; r < RP; r++) {
-        const u64 *c = g_ark + (size_t)(RF / 2 + r) * W;
-        // constants: c' = diag(1, Eprev^-1) c
-        g_opt.cst[r][0] = c[0];
-        for (int i = 0; i < n; i++) g_opt.cst[r][1 + i] = dot_fq(&EprevInv[(size_t)i * n], c + 1, n);
-        // eff = M * diag(1, Eprev)
-        for (int i = 0; i < W; i++) {
-            eff[(size_t)i * W] = g_mds[i * W];
-            for (int j = 0; j < n; j++) {
-                u64 acc = 0;
-                for (int k = 0; k < n; k++) acc = fq_add(acc, fq_mul(g_mds[i * W + 1 + k], Eprev[(size_t)k * n + j]));
-                eff[(size_t)i * W + 1 + j] = acc;
-            }
-        }
-        for (int i = 0; i < n; i++)
-            for (int j = 0; j < n; j++) Eh[(size_t)i * n + j] = eff[(size_t)(1 + i) * W + 1 + j];
-        if (!mat_inv(Eh.data(), Ei.data(), n)) abort();
-        g_opt.e00[r] = eff[0];
-        for (int j = 0; j < n; j++) g_opt.row[r][j] = eff[1 + j];
-        for (int i = 0; i < n; i++) {
-            u64 acc = 0;
-            for (int k = 0; k < n; k++) acc = fq_add(acc, fq_mul(Ei[(size_t)i * n + k], eff[(size_t)(1 + k) * W]));
-            g_opt.col[r][i] = acc;
-        }
-        Eprev = Eh;
-        EprevInv = Ei;
-    }
-    for (int i = 0; i < n; i++)
-        for (int j = 0; j < n; j++) g_opt.post[i][j] = Eprev[(size_t)i * n + j];
-}
+Sparse g_opt;   // sparse factorisation of the partial rounds
 
 // AVX-512 IFMA lanes (lf_poseidon_simd.cc) when the CPU has them; LF_POSEIDON_SCALAR=1 keeps the scalar path
 bool g_simd = false;
 void init_all() {
     poseidon_init();
-    partial_opt_init();
-    if (psimd::supported() && !getenv("LF_POSEIDON_SCALAR")) {
-        psimd::build(g_ark, g_mds, &g_opt.cst[0][0], g_opt.e00, &g_opt.row[0][0], &g_opt.col[0][0], &g_opt.post[0][0]);
+    if (!sparse_partial<FqField>(g_tab, g_opt)) abort();
+    if (avx512_ifma_supported() && !getenv("LF_POSEIDON_SCALAR")) {
+        Collapsed c;
+        collapse_partial<FqField>(g_tab, g_opt, c);
+        psimd::build(g_tab, c);
         g_simd = true;
     }
 }
@@ -389,19 +322,9 @@ void Transcript::params(const u64 **ark, const u64 **mds) {
     *mds = g_mds;
 }
 
-// plain definition (arkworks PoseidonSponge::permute): used by the self-test
 void Transcript::permute_plain(u64 st[24]) {
     std::call_once(g_once, init_all);
-    u64 nw[W];
-    for (int r = 0; r < RF + RP; r++) {
-        const u64 *ark = g_ark + r * W;
-        bool full = r < RF / 2 || r >= RF / 2 + RP;
-        for (int i = 0; i < W; i++) st[i] = fq_add(st[i], ark[i]);
-        if (full) for (int i = 0; i < W; i++) st[i] = sbox(st[i]);
-        else st[0] = sbox(st[0]);
-        for (int i = 0; i < W; i++) nw[i] = dot_fq(st, g_mds + i * W, W);
-        memcpy(st, nw, sizeof(nw));
-    }
+    poseidon::permute_plain<FqField>(g_tab, st);
 }
 
 void Transcript::permute(u64 st[24]) {
@@ -438,55 +361,9 @@ void Transcript::permute_scalar(u64 st[24]) {
     for (int r = RF / 2 + RP; r < RF + RP; r++) full_round(st, g_ark + r * W);
 }
 
-Transcript::Transcript() : squeezing_(false), idx_(0) {
-    std::call_once(g_once, init_all);
-    memset(st_, 0, sizeof(st_));
-}
-
-void Transcript::absorb_fq(const u64 *x, size_t n) {
-    if (!n) return;
-    int idx;
-    if (!squeezing_) {
-        idx = idx_;
-        if (idx == RATE) { permute(st_); idx = 0; }
-    } else {
-        permute(st_);
-        idx = 0;
-    }
-    for (;;) {
-        if ((size_t)idx + n <= (size_t)RATE) {
-            for (size_t i = 0; i < n; i++) st_[CAP + idx + i] = fq_add(st_[CAP + idx + i], x[i]);
-            squeezing_ = false;
-            idx_ = idx + (int)n;
-            return;
-        }
-        size_t take = RATE - idx;
-        for (size_t i = 0; i < take; i++) st_[CAP + idx + i] = fq_add(st_[CAP + idx + i], x[i]);
-        permute(st_);
-        x += take; n -= take; idx = 0;
-    }
-}
-
-void Transcript::squeeze(u64 *out, size_t n) {
-    int idx;
-    if (!squeezing_) { permute(st_); idx = 0; }
-    else {
-        idx = idx_;
-        if (idx == RATE) { permute(st_); idx = 0; }
-    }
-    for (;;) {
-        if ((size_t)idx + n <= (size_t)RATE) {
-            memcpy(out, st_ + CAP + idx, n * sizeof(u64));
-            squeezing_ = true;
-            idx_ = idx + (int)n;
-            return;
-        }
-        size_t take = RATE - idx;
-        memcpy(out, st_ + CAP + idx, take * sizeof(u64));
-        if (n != (size_t)RATE) permute(st_);
-        out += take; n -= take; idx = 0;
-    }
-}
+Transcript::Transcript() { std::call_once(g_once, init_all); }
+void Transcript::absorb_fq(const u64 *x, size_t n) { sp_.absorb(x, n); }
+void Transcript::squeeze(u64 *out, size_t n) { sp_.squeeze(out, n); }
 
 static void basis3(const u64 *M, const u64 *v, u64 *o) {   // o = M v over F_p, 3x3
     for (int i = 0; i < 3; i++) o[i] = fq_add(fq_add(fq_mul(M[3 * i], v[0]), fq_mul(M[3 * i + 1], v[1])), fq_mul(M[3 * i + 2], v[2]));
@@ -538,3 +415,8 @@ void Transcript::get_short_challenge(u64 out[24]) {
 }
 
 }  // namespace lf
+
+const poseidon::Table &poseidon::grain_table() {
+    std::call_once(lf::g_once, lf::init_all);
+    return lf::g_tab;
+}

@@ -1,5 +1,5 @@
 // lf_host.h -- host-side pieces of the MI355X LatticeFold prover: ring tables (data-driven CRT), small
-// ring operations on a handful of elements, Poseidon/Grain, Fiat-Shamir transcript.
+// ring operations on a handful of elements, Poseidon/Grain, Fiat-Shamir transcript (sponge and table builders: poseidon_host.h).
 // Everything bulk runs on the GPU (lf_kernels.hip); this file only handles O(proof size) data.
 #pragma once
 #include <stddef.h>
@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "lf_field.cuh"
+#include "poseidon_host.h"
 
 namespace lf {
 
@@ -61,6 +62,14 @@ struct HostRing {
 void balanced_digits(u64 v, u64 base, unsigned digits, int64_t *out, int mode = 0);   // mode: see lf_set_digit_mode
 
 // ---- Poseidon + transcript (crates/latticefold/src/transcript/poseidon.rs:29-75) ------------------------------
+struct FqField {   // field policy of poseidon_host.h
+    static constexpr u64 P = LF_P;
+    static u64 add(u64 a, u64 b) { return fq_add(a, b); }
+    static u64 sub(u64 a, u64 b) { return fq_sub(a, b); }
+    static u64 mul(u64 a, u64 b) { return fq_mul(a, b); }
+    static u64 inv(u64 a) { return fq_inv(a); }
+    static u64 from_word(u64 x) { return x; }   // absorbed words enter the state as they are: every caller hands canonical words
+};
 class Transcript {
   public:
     Transcript();
@@ -76,19 +85,17 @@ class Transcript {
     static void permute_plain(u64 st[24]);  // textbook definition, for the self-test
     static void params(const u64 **ark, const u64 **mds);
     // sponge state hand-over to / from the device sponge (lf_kernels.hip): 24 state words, rate index, mode (1 = squeezing)
-    void get_state(u64 out[26]) const { for (int i = 0; i < 24; i++) out[i] = st_[i]; out[24] = (u64)idx_; out[25] = squeezing_ ? 1 : 0; }
+    void get_state(u64 out[26]) const { sp_.get_state(out); }
     // External-basis hook (lf_set_ext_basis): while set, ring elements / challenges handed to absorb_ring / absorb_fq3_as_ring /
     // absorb_u64_as_ring are INTERNAL-basis words and are converted to the external basis before the sponge sees them, and get_challenge
     // returns the internal coordinates of the squeezed (external) challenge.  T, Ti: 3x3 row-major, ext = T int; nullptr = off.
     void set_basis(const u64 *T, const u64 *Ti) { bT_ = T; bTi_ = Ti; }
-    void set_state(const u64 in[26]) { for (int i = 0; i < 24; i++) st_[i] = in[i]; idx_ = (int)in[24]; squeezing_ = in[25] != 0; }
+    void set_state(const u64 in[26]) { sp_.set_state(in); }
 
     void squeeze(u64 *out, size_t n);   // raw field elements of the sponge (lf_transcript_squeeze_bytes)
 
   private:
-    u64 st_[24];
-    bool squeezing_;
-    int idx_;
+    poseidon::Sponge<FqField, &Transcript::permute> sp_;
     const u64 *bT_ = nullptr, *bTi_ = nullptr;
 };
 

@@ -1,5 +1,5 @@
 // lf_poseidon_simd.cc -- see lf_poseidon_simd.h.  Plain host C++ (compiled with the AVX-512 IFMA target for this file only;
-// every entry point is reached through the run-time check psimd::supported()).
+// every entry point is reached through the run-time check poseidon::avx512_ifma_supported()).
 //
 // Arithmetic.  vpmadd52{l,h}uq multiply the low 52 bits of their operands.  A product a * b with a = a0 + 2^52 a1 (a1 < 2^13,
 // the un-split word serves as a0) and b = bl + 2^32 bh (32-bit halves) is
@@ -32,23 +32,20 @@ typedef unsigned __int128 u128;
 typedef __m512i V;
 
 namespace {
-constexpr int W = 24, RF = 8, RP = 22;
-constexpr u64 P = 0xFFFFFFFF00000001ULL, EPS = 0xFFFFFFFFULL;
+using poseidon::W; using poseidon::RF; using poseidon::RP; using poseidon::NX;
+constexpr u64 P = 0xFFFFFFFF00000001ULL, EPS = 0xFFFFFFFFULL, M52 = (1ULL << 52) - 1;
 
-constexpr int NX = W + RP;   // columns of the closing map: 24 state words + 22 S-box outputs
 struct Tables {
     alignas(64) u64 mds0[W][W], mds1[W][W];     // [j][i] = M[i][j] and its top 12 bits
     alignas(64) u64 arkf[RF][W];                // constants of the full rounds
     alignas(64) u64 ark0[RF][W], ark1[RF][W];   // ... as the seed of the mat-vec before them: low 52 bits / top 12 bits
-    // partial rounds in scalar form (see permute): D = SX x, s0_{r+1} = D_r + K_r + sum_{i<=r} G[r][i] X_i,
-    // closing map  state' = FIN [x ; X] + FK
-    alignas(64) u64 sx0[W][W], sx1[W][W];       // [j][r] = coefficient of state word j in D_r (column 0 and lanes >= 22 zero)
+    // the collapsed partial rounds (poseidon::Collapsed), every table as its words / their top 12 bits
     alignas(64) u64 fin0[NX][W], fin1[NX][W];   // [j][i]: columns 0..23 state words, 24..45 the S-box outputs X_r; lane 0 zero
     alignas(64) u64 sxm0[W][W], sxm1[W][W];     // SX M (rows 0..21) and row 0 of M in lane 22: D and word 0 straight from the S-box outputs of the last full round
     alignas(64) u64 finm0[W][W], finm1[W][W];   // (state columns of the closing map) M
     alignas(64) u64 fk0[W], fk1[W];             // constant of the closing map (52-bit / top-12-bit halves), + the constants of the full round behind it
     alignas(64) u64 e0[RP][W], e1[RP][W];       // [r][q] = G[q][r] for q >= r + 2 (the cross terms the vector unit accumulates), else 0
-    u64 cst0[RP], K[RP], G[RP][RP];
+    u64 cst0[RP], G[RP][RP];
     u64 Kc[RP];                                 // K_q + cst0[q + 1] (the next round's constant of word 0 rides along)
 };
 Tables T;
@@ -64,11 +61,6 @@ inline u64 reduce128_loose(u64 lo, u64 hi) {
     u64 t1 = (hl << 32) - hl;
     u64 c = __builtin_add_overflow(t0, t1, &r);
     return r + (EPS & (0 - c));
-}
-inline u64 reduce128(u64 lo, u64 hi) { return canon(reduce128_loose(lo, hi)); }
-inline u64 mulmod(u64 a, u64 b) {   // canonical
-    u128 pr = (u128)a * b;
-    return reduce128((u64)pr, (u64)(pr >> 64));
 }
 inline u64 mul_loose(u64 a, u64 b) {   // any a, b; result below 2^64
     u128 pr = (u128)a * b;
@@ -237,80 +229,35 @@ inline void full_round(UV x[3], const u64 *seed0, const u64 *seed52) {
 }
 }  // namespace
 
-bool supported() {
-    static const bool ok = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512ifma") && __builtin_cpu_supports("avx512dq");
-    return ok;
+// two 24 x 24 tables of a lane form: the words (their low 52 bits are what the IFMAs use) and their top 12 bits
+static void split52(const u64 (*src)[W], int rows, u64 (*t0)[W], u64 (*t1)[W]) {
+    for (int j = 0; j < rows; j++)
+        for (int i = 0; i < W; i++) { t0[j][i] = src[j][i]; t1[j][i] = src[j][i] >> 52; }
 }
-
-void build(const u64 *ark, const u64 *mds, const u64 *cst, const u64 *e00, const u64 *row, const u64 *col, const u64 *post) {
+void build(const poseidon::Table &t, const poseidon::Collapsed &c) {
     memset(&T, 0, sizeof(T));
     for (int i = 0; i < W; i++)
         for (int j = 0; j < W; j++) {
-            T.mds0[j][i] = mds[i * W + j];
-            T.mds1[j][i] = mds[i * W + j] >> 52;
+            T.mds0[j][i] = t.mds[i * W + j];
+            T.mds1[j][i] = t.mds[i * W + j] >> 52;
         }
     for (int r = 0; r < RF; r++) {
         int src = r < RF / 2 ? r : RP + r;
-        memcpy(T.arkf[r], ark + (size_t)src * W, W * 8);
-        for (int i = 0; i < W; i++) { T.ark0[r][i] = T.arkf[r][i] & ((1ULL << 52) - 1); T.ark1[r][i] = T.arkf[r][i] >> 52; }
+        memcpy(T.arkf[r], t.ark + (size_t)src * W, W * 8);
+        for (int i = 0; i < W; i++) { T.ark0[r][i] = T.arkf[r][i] & M52; T.ark1[r][i] = T.arkf[r][i] >> 52; }
     }
-    // Symbolic run of the 22 sparse partial rounds.  Every state word 1..23 is an affine form over
-    //   [ x_1..x_23 (words on entry) | X_0..X_21 (S-box outputs of word 0) | 1 ]
-    // because a partial round is  xs = state[1..] + cst_r,  X_r = sbox(s0 + c0_r),  s0' = e00_r X_r + row_r . xs,
-    // state'[1..] = xs + col_r X_r -- linear except for the S-box.  Collecting coefficients turns the rounds into
-    //   D = SX x (one mat-vec up front),  s0_{r+1} = D_r + K_r + sum_{i<=r} G[r][i] X_i (scalar chain),
-    //   state' = diag(1, post) [s0_22 ; x + CX X + ck] (one closing mat-vec over [x ; X]).
-    const int n = W - 1, NB = n + RP + 1;   // basis size
-    static u64 form[W - 1][W - 1 + RP + 1];
-    memset(form, 0, sizeof(form));
-    for (int i = 0; i < n; i++) { form[i][i] = 1; form[i][NB - 1] = cst[0 * W + 1 + i]; }
-    for (int r = 0; r < RP; r++) {
-        T.cst0[r] = cst[r * W];
-        u64 dotf[W - 1 + RP + 1];
-        for (int b = 0; b < NB; b++) {
-            u64 a = 0;
-            for (int i = 0; i < n; i++) a = addmod(a, mulmod(row[r * n + i], form[i][b]));
-            dotf[b] = a;
-        }
-        for (int j = 0; j < n; j++) { T.sx0[1 + j][r] = dotf[j]; T.sx1[1 + j][r] = dotf[j] >> 52; }
-        for (int i = 0; i < r; i++) T.G[r][i] = dotf[n + i];
-        T.G[r][r] = e00[r];
-        T.K[r] = dotf[NB - 1];
-        for (int i = 0; i < n; i++) {
-            form[i][n + r] = addmod(form[i][n + r], col[r * n + i]);
-            if (r + 1 < RP) form[i][NB - 1] = addmod(form[i][NB - 1], cst[(r + 1) * W + 1 + i]);
-        }
+    split52(c.fin, NX, T.fin0, T.fin1);
+    split52(c.sxm, W, T.sxm0, T.sxm1);
+    split52(c.finm, W, T.finm0, T.finm1);
+    for (int i = 1; i < W; i++) {   // the closing map's constant plus the constants of the full round that follows it
+        const u64 a = addmod(c.fk[i], T.arkf[RF / 2][i]);
+        T.fk0[i] = a & M52; T.fk1[i] = a >> 52;
     }
-    // closing map: words 1..23 = post * form
-    for (int i = 0; i < n; i++)
-        for (int b = 0; b < NB; b++) {
-            u64 a = 0;
-            for (int k = 0; k < n; k++) a = addmod(a, mulmod(post[i * n + k], form[k][b]));
-            if (b < n) { T.fin0[1 + b][1 + i] = a; T.fin1[1 + b][1 + i] = a >> 52; }
-            else if (b < n + RP) { T.fin0[W + (b - n)][1 + i] = a; T.fin1[W + (b - n)][1 + i] = a >> 52; }
-            else {   // the closing map's constant plus the constants of the full round that follows it
-                a = addmod(a, T.arkf[RF / 2][1 + i]);
-                T.fk0[1 + i] = a & ((1ULL << 52) - 1); T.fk1[1 + i] = a >> 52;
-            }
-        }
-    for (int r = 0; r < RP; r++) {
-        T.Kc[r] = r + 1 < RP ? addmod(T.K[r], T.cst0[r + 1]) : T.K[r];
+    memcpy(T.cst0, c.cst0, sizeof(T.cst0));
+    memcpy(T.G, c.G, sizeof(T.G));
+    memcpy(T.Kc, c.Kc, sizeof(T.Kc));
+    for (int r = 0; r < RP; r++)
         for (int q = r + 2; q < RP; q++) { T.e0[r][q] = T.G[q][r]; T.e1[r][q] = T.G[q][r] >> 52; }
-    }
-    // The mat-vec of the full round in front of the partial rounds is folded into what consumes its output: x = M s, D = SX x = (SX M) s,
-    // closing-map part = FIN_x x = (FIN_x M) s, word 0 = (row 0 of M) s (lane 22 of the D table): two mat-vecs over s instead of three
-    for (int j = 0; j < W; j++) {
-        for (int r = 0; r < W; r++) {
-            u64 a = 0, b = 0;
-            for (int i = 0; i < W; i++) {
-                a = addmod(a, mulmod(T.sx0[i][r], mds[i * W + j]));
-                b = addmod(b, mulmod(T.fin0[i][r], mds[i * W + j]));
-            }
-            if (r == RP) a = mds[0 * W + j];
-            T.sxm0[j][r] = a; T.sxm1[j][r] = a >> 52;
-            T.finm0[j][r] = b; T.finm1[j][r] = b >> 52;
-        }
-    }
 }
 
 void permute(u64 st[24]) {

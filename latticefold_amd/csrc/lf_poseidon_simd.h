@@ -7,16 +7,13 @@
 // closing 24 x 46 mat-vec.  Same output as Transcript::permute_scalar / permute_plain (tested).
 // Selected at run time (cpuid); LF_POSEIDON_SCALAR=1 forces the scalar path.
 #pragma once
-#include <stdint.h>
+#include "poseidon_host.h"
 
 namespace lf {
 namespace psimd {
 
-bool supported();   // avx512f + avx512ifma + avx512dq on this CPU
-// tables of the sparse-factorised permutation (lf_host.cpp): ark[(RF+RP)*24], mds[24*24] row-major, cst[RP*24], e00[RP],
-// row[RP*23], col[RP*23], post[23*23] row-major
-void build(const uint64_t *ark, const uint64_t *mds, const uint64_t *cst, const uint64_t *e00, const uint64_t *row, const uint64_t *col,
-           const uint64_t *post);
+// both only where poseidon::avx512_ifma_supported()
+void build(const poseidon::Table &t, const poseidon::Collapsed &c);   // the Goldilocks table and its collapsed partial rounds
 void permute(uint64_t st[24]);
 
 }  // namespace psimd

@@ -1,5 +1,5 @@
 // lfp_poseidon_simd.cc -- see lfp_poseidon_simd.h.  Plain host C++ (compiled with the AVX-512 IFMA target for this file only; every entry
-// point is reached through the run-time check lfp_psimd::supported()).
+// point is reached through the run-time check poseidon::avx512_ifma_supported()).
 //
 // The Frog prime p = 15912092521325583641 (~2^63.8) has no special form, so the lanes work on MONTGOMERY words with R = 2^104:
 //   * a 64-bit word a = a0 + 2^52 a1 (a1 < 2^12); vpmadd52{l,h}uq multiply the low 52 bits of their operands, so the un-split word serves as a0.
@@ -10,7 +10,7 @@
 //     Goldilocks lanes (lf_poseidon_simd.cc).
 //   * the mat-vecs split the MULTIPLIER into 32-bit halves instead (x = xl + 2^32 xh: a0 xl, a1 xl < 2^44 whole, the same at weight 2^32): six IFMAs
 //     per product, four weight classes that are put back on the 52-bit grid once per output word (eight cheap operations).
-// The 22 partial rounds are collapsed by linearity exactly as there: D = SX x (one mat-vec), the scalar chain over word 0
+// The 22 partial rounds are collapsed by linearity (poseidon::collapse_partial): D = SX x (one mat-vec), the scalar chain over word 0
 // (s0_{r+1} = D_r + K_r + sum_{i<=r} G[r][i] X_i; scalar Montgomery words with R = 2^64, the factors 2^+-40 between the two domains are folded
 // into the SX / closing tables), a closing map over [x ; X].  The chain carries three dependent products per round (G x^7 = ((G x) x^2) x^4
 // next to x^7) and one addition; the rest of s0_{r+1} is prepared while the S-box of round r runs: the cross terms sum_{i<=r-2} G[r][i] X_i
@@ -28,7 +28,7 @@ typedef unsigned __int128 u128;
 typedef __m512i V;
 
 namespace {
-constexpr int W = 24, RF = 8, RP = 22, NX = W + RP;
+using poseidon::W; using poseidon::RF; using poseidon::RP; using poseidon::NX;
 constexpr u64 M52 = (1ULL << 52) - 1;
 
 struct Tables {
@@ -37,13 +37,12 @@ struct Tables {
     u64 two24, two104;                          // 2^24, 2^104 mod p (domain changes of word 0 through the scalar Montgomery product)
     alignas(64) u64 mds0[W][W], mds1[W][W];     // [j][i] = M[i][j] 2^104 and its top 12 bits
     alignas(64) u64 arkf[RF][W];                // constants of the full rounds, 2^104 form
-    alignas(64) u64 sx0[W][W], sx1[W][W];       // [j][r]: coefficient of state word j in D_r, times 2^-40 (2^104 form): D comes out in 2^64 form
     alignas(64) u64 fin0[NX][W], fin1[NX][W];   // closing map: columns 0..23 state words (2^104 form), 24..45 the S-box outputs X_r (given in 2^64 form: times 2^40)
     alignas(64) u64 sxm0[W][W], sxm1[W][W];     // SX M (rows 0..21) and row 0 of M in lane 22, times 2^-40: D and word 0 (2^64 form) straight from the S-box outputs of the last full round
     alignas(64) u64 finm0[W][W], finm1[W][W];   // (state columns of the closing map) M
     alignas(64) u64 fk[W];                      // constant of the closing map (2^104 form), added after the reduction
     alignas(64) u64 e0[RP][W], e1[RP][W];       // [r][q] = G[q][r] for q >= r + 2 (the cross terms the vector unit accumulates, raw 2^64-form words), else 0
-    u64 cst0[RP], K[RP], G[RP][RP];             // scalar chain, 2^64 form
+    u64 cst0[RP], G[RP][RP];                    // scalar chain, 2^64 form
     u64 Kc[RP];                                 // K_q + cst0[q + 1]
 };
 Tables T;
@@ -203,12 +202,7 @@ inline void full_round(V x[3], const u64 *ark) {
 }
 }  // namespace
 
-bool supported() {
-    static const bool ok = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512ifma") && __builtin_cpu_supports("avx512dq");
-    return ok;
-}
-
-void build(u64 p, const u64 *ark, const u64 *mds, const u64 *cst, const u64 *e00, const u64 *row, const u64 *col, const u64 *post) {
+void build(u64 p, const poseidon::Table &t, const poseidon::Collapsed &c) {
     memset(&T, 0, sizeof(T));
     T.p = p;
     u64 x = 1;
@@ -220,74 +214,33 @@ void build(u64 p, const u64 *ark, const u64 *mds, const u64 *cst, const u64 *e00
     T.two24 = shl_mod(1, 24);
     T.two104 = shl_mod(1, 104);
     const u64 inv2 = (p + 1) / 2, i40 = powmod(inv2, 40);                      // 2^-40
-    auto to104 = [&](u64 a) { return shl_mod(a % p, 104); };
-    auto to64 = [&](u64 a) { return shl_mod(a % p, 64); };
+    auto to104 = [&](u64 a) { return shl_mod(a, 104); };
+    auto to64 = [&](u64 a) { return shl_mod(a, 64); };
+    auto put = [](u64 (*t0)[W], u64 (*t1)[W], int j, int i, u64 v) { t0[j][i] = v; t1[j][i] = v >> 52; };
     for (int i = 0; i < W; i++)
-        for (int j = 0; j < W; j++) {
-            const u64 m = to104(mds[i * W + j]);
-            T.mds0[j][i] = m;
-            T.mds1[j][i] = m >> 52;
-        }
+        for (int j = 0; j < W; j++) put(T.mds0, T.mds1, j, i, to104(t.mds[i * W + j]));
     for (int r = 0; r < RF; r++) {
         const int src = r < RF / 2 ? r : RP + r;
-        for (int i = 0; i < W; i++) T.arkf[r][i] = to104(ark[(size_t)src * W + i]);
+        for (int i = 0; i < W; i++) T.arkf[r][i] = to104(t.ark[(size_t)src * W + i]);
     }
-    // Symbolic run of the 22 sparse partial rounds (as lf_poseidon_simd.cc): every state word 1..23 is an affine form over
-    //   [ x_1..x_23 (words on entry) | X_0..X_21 (S-box outputs of word 0) | 1 ]
-    const int n = W - 1, NB = n + RP + 1;
-    static u64 form[W - 1][W - 1 + RP + 1], sxc[W][W], finc[W][W];
-    memset(form, 0, sizeof(form));
-    memset(sxc, 0, sizeof(sxc));
-    memset(finc, 0, sizeof(finc));
-    for (int i = 0; i < n; i++) { form[i][i] = 1; form[i][NB - 1] = cst[0 * W + 1 + i] % p; }
-    for (int r = 0; r < RP; r++) {
-        T.cst0[r] = to64(cst[r * W]);
-        u64 dotf[W - 1 + RP + 1];
-        for (int b = 0; b < NB; b++) {
-            u64 a = 0;
-            for (int i = 0; i < n; i++) a = addmod(a, mulmod(row[r * n + i] % p, form[i][b]));
-            dotf[b] = a;
-        }
-        for (int j = 0; j < n; j++) {
-            const u64 v = to104(mulmod(dotf[j], i40));
-            sxc[1 + j][r] = dotf[j];
-            T.sx0[1 + j][r] = v;
-            T.sx1[1 + j][r] = v >> 52;
-        }
-        for (int i = 0; i < r; i++) T.G[r][i] = to64(dotf[n + i]);
-        T.G[r][r] = to64(e00[r]);
-        T.K[r] = to64(dotf[NB - 1]);
-        for (int i = 0; i < n; i++) {
-            form[i][n + r] = addmod(form[i][n + r], col[r * n + i] % p);
-            if (r + 1 < RP) form[i][NB - 1] = addmod(form[i][NB - 1], cst[(r + 1) * W + 1 + i] % p);
-        }
-    }
-    for (int i = 0; i < n; i++)
-        for (int b = 0; b < NB; b++) {
-            u64 a = 0;
-            for (int k = 0; k < n; k++) a = addmod(a, mulmod(post[i * n + k] % p, form[k][b]));
-            if (b < n) { const u64 v = to104(a); T.fin0[1 + b][1 + i] = v; T.fin1[1 + b][1 + i] = v >> 52; finc[1 + b][1 + i] = a; }
-            else if (b < n + RP) { const u64 v = shl_mod(a, 144); T.fin0[W + (b - n)][1 + i] = v; T.fin1[W + (b - n)][1 + i] = v >> 52; }   // x 2^104 x 2^40
-            else T.fk[1 + i] = to104(a);
-        }
-    for (int r = 0; r < RP; r++) {
-        T.Kc[r] = r + 1 < RP ? addmod(T.K[r], T.cst0[r + 1]) : T.K[r];
-        for (int q = r + 2; q < RP; q++) { T.e0[r][q] = T.G[q][r]; T.e1[r][q] = T.G[q][r] >> 52; }
-    }
-    // The mat-vec of the full round in front of the partial rounds is folded into what consumes its output: x = M s, D = (SX M) s, closing-map part
-    // (FIN_x M) s, word 0 = (row 0 of M) s in lane 22 of the D table (so it arrives in 2^64 form like D): two mat-vecs over s instead of three
+    // The vector lanes work in 2^104 form, the scalar chain in 2^64 form: D (and word 0, lane 22 of the D table) leaves the lanes for the chain, so its
+    // table carries 2^-40; the S-box outputs X_r enter the closing map from the chain, so their columns carry 2^40 on top of 2^104
     for (int j = 0; j < W; j++)
-        for (int r = 0; r < W; r++) {
-            u64 a = 0, b = 0;
-            for (int i = 0; i < W; i++) {
-                a = addmod(a, mulmod(sxc[i][r], mds[i * W + j] % p));
-                b = addmod(b, mulmod(finc[i][r], mds[i * W + j] % p));
-            }
-            if (r == RP) a = mds[0 * W + j] % p;
-            const u64 va = to104(mulmod(a, i40)), vb = to104(b);
-            T.sxm0[j][r] = va; T.sxm1[j][r] = va >> 52;
-            T.finm0[j][r] = vb; T.finm1[j][r] = vb >> 52;
+        for (int i = 0; i < W; i++) {
+            put(T.sxm0, T.sxm1, j, i, to104(mulmod(c.sxm[j][i], i40)));
+            put(T.finm0, T.finm1, j, i, to104(c.finm[j][i]));
+            put(T.fin0, T.fin1, j, i, to104(c.fin[j][i]));
         }
+    for (int r = 0; r < RP; r++)
+        for (int i = 0; i < W; i++) put(T.fin0, T.fin1, W + r, i, shl_mod(c.fin[W + r][i], 144));
+    for (int i = 0; i < W; i++) T.fk[i] = to104(c.fk[i]);
+    for (int r = 0; r < RP; r++) {
+        T.cst0[r] = to64(c.cst0[r]);
+        T.Kc[r] = to64(c.Kc[r]);
+        for (int i = 0; i <= r; i++) T.G[r][i] = to64(c.G[r][i]);
+    }
+    for (int r = 0; r < RP; r++)
+        for (int q = r + 2; q < RP; q++) { T.e0[r][q] = T.G[q][r]; T.e1[r][q] = T.G[q][r] >> 52; }
 }
 
 void permute(u64 st[24]) {

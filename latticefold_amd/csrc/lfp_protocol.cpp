@@ -10,9 +10,9 @@
 #include <cstring>
 #include <functional>
 #include <memory>
-#include "lf_host.h"
 #include "lfp_ctx.h"
 #include "lfp_poseidon_simd.h"
+#include "poseidon_host.h"
 static constexpr uint32_t LFP_HOST_SUM_BLOCKS = 256;   // block partials the host adds per round; rounds with more workgroups add theirs on the device (launch_reduce)
 
 // LFPLUS_TIMELINE=1: wall-clock marks of the protocol stages on stderr (the stream is drained at every mark, so the stages do not overlap)
@@ -32,7 +32,8 @@ static LfpTl g_tl;
 namespace {
 typedef unsigned __int128 u128;
 constexpr u64 P = lfp::P;
-constexpr int D = 16, W = 24, RATE = 20, CAP = 4, RF = 8, RP = 22;
+constexpr int D = 16;
+using poseidon::W; using poseidon::RF; using poseidon::RP;
 inline u64 fadd(u64 a, u64 b) { u128 s = (u128)a + b; return (u64)(s >= P ? s - P : s); }
 inline u64 fsub(u64 a, u64 b) { return a >= b ? a - b : a + (P - b); }
 inline u64 fmul(u64 a, u64 b) { return (u64)(((u128)a * b) % P); }
@@ -40,41 +41,26 @@ u64 fpow(u64 a, u64 e) { u64 r = 1; while (e) { if (e & 1) r = fmul(r, a); a = f
 inline u64 to_mont(u64 a) { return (u64)((((u128)a) << 64) % P); }
 const u64 RINV = fpow(to_mont(1), P - 2);   // 2^-64 mod p
 inline u64 from_mont(u64 a) { return fmul(a, RINV); }
+struct FrogField {   // field policy of poseidon_host.h
+    static constexpr u64 P = lfp::P;
+    static u64 add(u64 a, u64 b) { return fadd(a, b); }
+    static u64 sub(u64 a, u64 b) { return fsub(a, b); }
+    static u64 mul(u64 a, u64 b) { return fmul(a, b); }
+    static u64 inv(u64 a) { return fpow(a, P - 2); }
+    static u64 from_word(u64 x) { return x % P; }
+};
 
 // The reference's Frog table (rings/poseidon/frog.rs:7-1425) is the Grain-LFSR table of the 64-bit Goldilocks prime embedded with
-// Fq::from(i128): the generator of lf_host.cpp, reduced mod p_frog (pinned by the reference's checksums in tests/golden/kats.json)
-struct Params {
-    u64 ark[(RF + RP) * W], mds[W * W];
-    Params() {
-        const u64 *a, *m;
-        lf::Transcript::params(&a, &m);
-        for (int i = 0; i < (RF + RP) * W; i++) ark[i] = a[i] % P;
-        for (int i = 0; i < W * W; i++) mds[i] = m[i] % P;
-    }
+// Fq::from(i128), i.e. reduced mod p_frog (pinned by the reference's checksums in tests/golden/kats.json)
+struct Params : poseidon::Table {
+    Params() { poseidon::reduced_table<FrogField>(*this); }
 };
 const Params &params() { static const Params p; return p; }
-inline u64 pow7(u64 x) { u64 x2 = fmul(x, x), x4 = fmul(x2, x2); return fmul(fmul(x4, x2), x); }
-// the definition (ark-crypto-primitives PoseidonSponge::permute): the self-test reference of permute()
-void permute_plain(u64 *st) {
-    const Params &pp = params();
-    u64 nw[W];
-    for (int r = 0; r < RF + RP; r++) {
-        for (int i = 0; i < W; i++) st[i] = fadd(st[i], pp.ark[r * W + i]);
-        if (r < RF / 2 || r >= RF / 2 + RP) for (int i = 0; i < W; i++) st[i] = pow7(st[i]);
-        else st[0] = pow7(st[0]);
-        for (int i = 0; i < W; i++) {
-            u64 acc = 0;
-            for (int j = 0; j < W; j++) acc = fadd(acc, fmul(st[j], pp.mds[i * W + j]));
-            nw[i] = acc;
-        }
-        memcpy(st, nw, sizeof(nw));
-    }
-}
+void permute_plain(u64 *st) { poseidon::permute_plain<FrogField>(params(), st); }   // the self-test reference of permute()
 
 // ---- the permutation as it runs: Montgomery words, lazy row sums, sparse partial rounds ---------------------------------------------------
 // (a prove at n = 2^15 makes ~500 permutations; the plain form costs 80 us each on the host and was most of the wall time.)
-// Partial rounds through the factorisation M diag(1, E) = diag(1, E') [[e00, row], [col, I]] (Poseidon paper, appendix on optimised partial rounds; the
-// same construction as lf_host.cpp uses for the Goldilocks table): identical output, 47 instead of 576 multiplications per partial round.
+// Partial rounds in the sparse form of poseidon::sparse_partial: 47 instead of 576 multiplications per partial round.
 struct FastPerm {
     u64 pinv, r2;                                  // p^-1 mod 2^64, 2^128 mod p
     u64 ark[(RF + RP) * W], mds[W * W];            // Montgomery
@@ -101,28 +87,6 @@ struct FastPerm {
         u64 r = th >= mh ? th - mh : th + (P - mh);   // th < 2^64 may exceed p
         return r >= P ? r - P : r;
     }
-    static bool mat_inv(const u64 *in, u64 *out, int n) {   // Gauss-Jordan over F_p, canonical words
-        std::vector<u64> M((size_t)n * 2 * n, 0);
-        for (int r = 0; r < n; r++) {
-            for (int c = 0; c < n; c++) M[(size_t)r * 2 * n + c] = in[r * n + c];
-            M[(size_t)r * 2 * n + n + r] = 1;
-        }
-        for (int cc = 0; cc < n; cc++) {
-            int piv = -1;
-            for (int r = cc; r < n; r++) if (M[(size_t)r * 2 * n + cc]) { piv = r; break; }
-            if (piv < 0) return false;
-            if (piv != cc) for (int c = 0; c < 2 * n; c++) std::swap(M[(size_t)piv * 2 * n + c], M[(size_t)cc * 2 * n + c]);
-            const u64 inv = fpow(M[(size_t)cc * 2 * n + cc], P - 2);
-            for (int c = 0; c < 2 * n; c++) M[(size_t)cc * 2 * n + c] = fmul(M[(size_t)cc * 2 * n + c], inv);
-            for (int r = 0; r < n; r++) {
-                const u64 f = M[(size_t)r * 2 * n + cc];
-                if (r == cc || !f) continue;
-                for (int c = 0; c < 2 * n; c++) M[(size_t)r * 2 * n + c] = fsub(M[(size_t)r * 2 * n + c], fmul(f, M[(size_t)cc * 2 * n + c]));
-            }
-        }
-        for (int r = 0; r < n; r++) for (int c = 0; c < n; c++) out[r * n + c] = M[(size_t)r * 2 * n + n + c];
-        return true;
-    }
     bool ok = false;
     FastPerm() {
         const Params &pp = params();
@@ -131,50 +95,22 @@ struct FastPerm {
         pinv = x;
         r2 = to_mont(to_mont(1));
         const int n = W - 1;
-        std::vector<u64> Eprev((size_t)n * n, 0), EprevInv((size_t)n * n, 0), eff((size_t)W * W), Eh((size_t)n * n), Ei((size_t)n * n);
-        for (int i = 0; i < n; i++) Eprev[(size_t)i * n + i] = EprevInv[(size_t)i * n + i] = 1;
+        poseidon::Sparse sp;
+        if (!poseidon::sparse_partial<FrogField>(pp, sp)) return;   // (never for this table; permute() then keeps the plain form)
         for (int r = 0; r < RP; r++) {
-            const u64 *c = pp.ark + (size_t)(RF / 2 + r) * W;
-            cst[r][0] = to_mont(c[0]);
-            for (int i = 0; i < n; i++) {               // constants pulled through the deferred factor: c' = diag(1, Eprev^-1) c
-                u64 acc = 0;
-                for (int k = 0; k < n; k++) acc = fadd(acc, fmul(EprevInv[(size_t)i * n + k], c[1 + k]));
-                cst[r][1 + i] = to_mont(acc);
-            }
-            for (int i = 0; i < W; i++) {               // eff = M diag(1, Eprev)
-                eff[(size_t)i * W] = pp.mds[i * W];
-                for (int j = 0; j < n; j++) {
-                    u64 acc = 0;
-                    for (int k = 0; k < n; k++) acc = fadd(acc, fmul(pp.mds[i * W + 1 + k], Eprev[(size_t)k * n + j]));
-                    eff[(size_t)i * W + 1 + j] = acc;
-                }
-            }
-            for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) Eh[(size_t)i * n + j] = eff[(size_t)(1 + i) * W + 1 + j];
-            if (!mat_inv(Eh.data(), Ei.data(), n)) return;   // (never for this table; permute() then keeps the plain form)
-            e00[r] = to_mont(eff[0]);
-            for (int j = 0; j < n; j++) row[r][j] = to_mont(eff[1 + j]);
-            for (int i = 0; i < n; i++) {
-                u64 acc = 0;
-                for (int k = 0; k < n; k++) acc = fadd(acc, fmul(Ei[(size_t)i * n + k], eff[(size_t)(1 + k) * W]));
-                col[r][i] = to_mont(acc);
-            }
-            Eprev = Eh;
-            EprevInv = Ei;
+            e00[r] = to_mont(sp.e00[r]);
+            for (int i = 0; i < W; i++) cst[r][i] = to_mont(sp.cst[r][i]);
+            for (int i = 0; i < n; i++) { row[r][i] = to_mont(sp.row[r][i]); col[r][i] = to_mont(sp.col[r][i]); }
         }
-        for (int i = 0; i < n * n; i++) post[i] = to_mont(Eprev[i]);
+        for (int i = 0; i < n * n; i++) post[i] = to_mont(sp.post[i / n][i % n]);
         for (int i = 0; i < (RF + RP) * W; i++) ark[i] = to_mont(pp.ark[i]);
         for (int i = 0; i < W * W; i++) mds[i] = to_mont(pp.mds[i]);
         ok = true;
         // AVX-512 IFMA lanes (lfp_poseidon_simd.cc) when the CPU has them; LFPLUS_POSEIDON_SCALAR=1 keeps this scalar form
-        if (lfp_psimd::supported() && !getenv("LFPLUS_POSEIDON_SCALAR")) {
-            std::vector<u64> cstP((size_t)RP * W), e00P(RP), rowP((size_t)RP * n), colP((size_t)RP * n), postP((size_t)n * n);
-            for (int r = 0; r < RP; r++) {
-                e00P[r] = from_mont(e00[r]);
-                for (int i = 0; i < W; i++) cstP[(size_t)r * W + i] = from_mont(cst[r][i]);
-                for (int i = 0; i < n; i++) { rowP[(size_t)r * n + i] = from_mont(row[r][i]); colP[(size_t)r * n + i] = from_mont(col[r][i]); }
-            }
-            for (int i = 0; i < n * n; i++) postP[i] = from_mont(post[i]);
-            lfp_psimd::build(P, pp.ark, pp.mds, cstP.data(), e00P.data(), rowP.data(), colP.data(), postP.data());
+        if (poseidon::avx512_ifma_supported() && !getenv("LFPLUS_POSEIDON_SCALAR")) {
+            poseidon::Collapsed c;
+            poseidon::collapse_partial<FrogField>(pp, sp, c);
+            lfp_psimd::build(P, pp, c);
             simd = true;
         }
     }
@@ -217,46 +153,10 @@ void permute(u64 *st) {
 }
 }  // namespace
 
-// ark-crypto-primitives 0.4.0 PoseidonSponge (duplex): state[0..4) capacity, [4..24) rate
-struct lfplus_transcript {
-    u64 st[W] = {0};
-    bool squeezing = false;
-    int idx = 0;
-    void absorb_fq(const u64 *x, size_t n) {
-        if (!n) return;
-        int i0;
-        if (!squeezing) { i0 = idx; if (i0 == RATE) { permute(st); i0 = 0; } }
-        else { permute(st); i0 = 0; }
-        for (;;) {
-            if ((size_t)i0 + n <= RATE) {
-                for (size_t i = 0; i < n; i++) st[CAP + i0 + i] = fadd(st[CAP + i0 + i], x[i] % P);
-                squeezing = false;
-                idx = i0 + (int)n;
-                return;
-            }
-            const size_t take = RATE - i0;
-            for (size_t i = 0; i < take; i++) st[CAP + i0 + i] = fadd(st[CAP + i0 + i], x[i] % P);
-            permute(st);
-            x += take; n -= take; i0 = 0;
-        }
-    }
-    void squeeze_fq(u64 *out, size_t n) {
-        int i0;
-        if (!squeezing) { permute(st); i0 = 0; }
-        else { i0 = idx; if (i0 == RATE) { permute(st); i0 = 0; } }
-        for (;;) {
-            if ((size_t)i0 + n <= RATE) {
-                memcpy(out, st + CAP + i0, n * sizeof(u64));
-                squeezing = true;
-                idx = i0 + (int)n;
-                return;
-            }
-            const size_t take = RATE - i0;
-            memcpy(out, st + CAP + i0, take * sizeof(u64));
-            if (n != RATE) permute(st);
-            out += take; n -= take; i0 = 0;
-        }
-    }
+// PoseidonTranscript<RqPoly> on the duplex sponge of poseidon_host.h
+struct lfplus_transcript : poseidon::Sponge<FrogField, permute> {
+    void absorb_fq(const u64 *x, size_t n) { absorb(x, n); }
+    void squeeze_fq(u64 *out, size_t n) { squeeze(out, n); }
     void absorb_ring(const u64 *e, size_t count) { for (size_t i = 0; i < count; i++) absorb_fq(e + i * D, D); }   // Transcript::absorb: the 16 coefficients
     void absorb_const(u64 c) { u64 e[D] = {0}; e[0] = c % P; absorb_ring(e, 1); }                                   // absorb(&R::from(c))
     u64 challenge() { u64 c; squeeze_fq(&c, 1); absorb_fq(&c, 1); return c; }                                       // transcript.rs:44-53

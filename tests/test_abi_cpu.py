@@ -229,3 +229,20 @@ def test_transcript_squeeze_bytes_matches_the_short_challenge():
             w = bs[3 * g] | (bs[3 * g + 1] << 8) | (bs[3 * g + 2] << 16)
             got += [((w >> (6 * j)) & 63) - 32 for j in range(4)]
         assert [int(v) if int(v) < p // 2 else int(v) - p for v in want[:24]] == got
+
+
+def test_transcript_squeeze_bytes_digests_on_a_long_script():
+    """The Goldilocks and BabyBear host transcripts on the fixed script of tools/gen_transcript_digests.py -- absorbs of 1..70 unreduced 64-bit words, squeezes of
+    1, 19, 20, 21, 40, 41 and 45 words' worth of bytes (around and beyond one block of the rate, which the oracle never squeezes on these rings) -- against the
+    SHA-256 digests recorded in tests/golden/host_transcript_digests.json from the library before the sponges were merged into poseidon_host.h"""
+    import importlib.util
+    import json
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("gen_transcript_digests", os.path.join(root, "tools", "gen_transcript_digests.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    want = json.load(open(mod.GOLDEN))["sha256"]
+    assert sorted(want) == sorted(mod.RINGS)
+    lib = mod.load(api._SO)
+    for ring in mod.RINGS:
+        assert mod.digest(lib, ring) == want[ring], ring

@@ -99,6 +99,15 @@ def test_transcript_equals_oracle_on_random_scripts():
             assert (tp.squeeze_bytes(n) == to.squeeze_bytes(n)).all()
         else:
             assert (tp.short_challenge() == to.short_challenge()).all()
+    # squeezes around and beyond one block of the rate (20 words = 140 bytes: the multi-block branch of the duplex sponge), first each followed by an absorb and
+    # a challenge, then back to back
+    for i, n in enumerate((140, 141, 280, 281, 300)):
+        assert (tp.squeeze_bytes(n) == to.squeeze_bytes(n)).all()
+        x = lfp.splitmix(200 + i, 0, D).reshape(-1, D)
+        tp.absorb(x); to.absorb(x)
+        assert tp.get_challenge() == to.challenge()
+    for n in (141, 140, 300, 280, 281, 7, 140):
+        assert (tp.squeeze_bytes(n) == to.squeeze_bytes(n)).all()
     assert tp.clone().get_challenge() == to.clone().challenge()
 
 
