@@ -135,6 +135,26 @@ int lfplus_decompose_resident(lfplus_ctx *ctx, uint64_t B, const uint64_t *r_a, 
                               uint64_t *v0, uint64_t *v1);
 int lfplus_get_witness(lfplus_ctx *ctx, uint64_t *f_out /* n * 16 words */, uint64_t n);
 
+/* ---- relation checks on the resident (A, f): "is this instance satisfied?" without moving the witness (134 MB at 2^20 rows) to the host.  The reference has no
+ * check_relation for LatticeFold+; the relations are the ones its structs define and its tests assert piecewise (decomp.rs:157-215, r1cs.rs:211-233).
+ * Every component is evaluated; *failed is the OR of the LFPLUS_REL_* bits of the failing ones; the return value is LFPLUS_OK, or LFPLUS_E_REJECT when *failed != 0.
+ * *absmax (may be NULL) = the largest |centred coefficient| of f (centred: w if w <= (p - 1) / 2, else p - w); the norm rule is the balanced one, absmax < bound
+ * (bound 0: not checked).  Read-only: neither the witness, the from_f buffers nor a transcript is touched; a pending lfplus_rg_from_f_async pass is waited for.
+ * Arguments are validated as by lfplus_decompose (CSR shape, canonical words, n a power of two): LFPLUS_E_ARG, as for a context without matrix or witness, a
+ * NULL `failed`, and a sharded context (a rank holds only its columns of A; as lfplus_witness_from_z).  The context stays usable after every return. */
+enum { LFPLUS_REL_CM = 1, LFPLUS_REL_R1CS = 2, LFPLUS_REL_V = 4, LFPLUS_REL_NORM = 8 };
+/* R_ComR1CS (src/r1cs.rs:21-60): cm_f = A f (cm_f NULL: not checked) and (M_A f) o (M_B f) = M_C f row by row in Z_p[X]/(X^16 + 1), for the three n x n
+ * matrices that act on f (r1cs_decomposed_square; rowptr NULL: the resident ones, which must number 3).  *first_bad (may be NULL) = the smallest row with a
+ * non-zero residual in any of its 16 coefficients, n when every row holds.  The residual is fused: the three product tables are never written. */
+int lfplus_r1cs_check(lfplus_ctx *ctx, const uint64_t *cm_f, const uint32_t *const *rowptr, const uint32_t *const *col, const uint64_t *const *val, uint64_t bound,
+                      unsigned *failed, uint64_t *first_bad, uint64_t *absmax);
+/* R_LinB (src/lin.rs:29-40; built at decomp.rs:76-91, r1cs.rs:119-130): cm_f = A f (kappa*16 words; NULL: not checked) and, for both points pt in {a, b},
+ * v[0][pt] = mle(f)(r_pt), v[1 + j][pt] = mle(M_j f)(r_pt).  r_a / r_b: log2(n) ring elements each and v: (1 + nM)*2*16 words, both as lfplus_decompose lays
+ * them out (v0); nM matrices (rowptr NULL: the resident ones).  Points whose coordinates are all ring constants (PlusProver's always are) with
+ * constant-coefficient matrices take one pass over f; anything else runs through lfplus_decompose's fix_variables tables (correct, not fast). */
+int lfplus_linb_check(lfplus_ctx *ctx, const uint64_t *cm_f, const uint64_t *r_a, const uint64_t *r_b, uint32_t nM, const uint32_t *const *rowptr,
+                      const uint32_t *const *col, const uint64_t *const *val, const uint64_t *v, uint64_t bound, unsigned *failed, uint64_t *absmax);
+
 /* Matrix::try_mul_vec: out (kappa*16 words) = A * v for a general vector of n ring elements (host pointer) */
 int lfplus_commit(lfplus_ctx *ctx, const uint64_t *v, uint64_t n, uint64_t *out);
 

@@ -707,12 +707,9 @@ extern "C" int lfplus_witness_from_z_timed(lfplus_ctx *c, const uint64_t *z, uin
     if (!ms_avg || !iters) return fail(c, LFPLUS_E_ARG, "lfplus_witness_from_z_timed: bad arguments");
     return witness_from_z(c, z, m, b, k, nullptr, iters, ms_avg);
 }
-extern "C" int lfplus_commit_resident(lfplus_ctx *c, uint64_t *out) {
-    if (!c || !out) return fail(c, LFPLUS_E_ARG, "lfplus_commit_resident: null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    ff_join(c);
-    if (c->sharded()) return fail(c, LFPLUS_E_ARG, "lfplus_commit_resident: sharded contexts are not supported (lfplus_commit exchanges the ranks' partial sums)");
-    if (!c->A || !c->f || c->nf != c->n) return fail(c, LFPLUS_E_ARG, "lfplus_commit_resident: matrix / witness not set or of different length");
+// A f of the resident witness, enqueued on the context's stream: *res_dev = the kappa * 16 result words on the device (inside c->part: valid until the next call
+// that uses the partial-sum buffer).  The caller has validated the context (matrix, witness, not sharded) and joined a pending from_f pass.
+int lfp_commit_resident_enqueue(lfplus_ctx *c, u64 **res_dev) {
     Plan p = plan_for(c->nloc, c->kappa, 0);
     int rc = ensure_part(c, (size_t)p.nblk * p.nout_f + p.nout_f);
     if (rc) return rc;
@@ -720,7 +717,19 @@ extern "C" int lfplus_commit_resident(lfplus_ctx *c, uint64_t *out) {
     enqueue_phase1(c, c->f, 2, 0, p, c->part);
     lfp::launch_reduce(c->part, p.nblk, (u32)p.nout_f, res, 0, c->kappa, 0, 2, 0, nullptr, c->st);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, res, p.nout_f * 8, hipMemcpyDeviceToHost, c->st));
+    *res_dev = res;
+    return LFPLUS_OK;
+}
+extern "C" int lfplus_commit_resident(lfplus_ctx *c, uint64_t *out) {
+    if (!c || !out) return fail(c, LFPLUS_E_ARG, "lfplus_commit_resident: null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    ff_join(c);
+    if (c->sharded()) return fail(c, LFPLUS_E_ARG, "lfplus_commit_resident: sharded contexts are not supported (lfplus_commit exchanges the ranks' partial sums)");
+    if (!c->A || !c->f || c->nf != c->n) return fail(c, LFPLUS_E_ARG, "lfplus_commit_resident: matrix / witness not set or of different length");
+    u64 *res = nullptr;
+    int rc = lfp_commit_resident_enqueue(c, &res);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(out, res, (size_t)c->kappa * 16 * 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     return LFPLUS_OK;
 }

@@ -246,6 +246,9 @@ static inline bool canonical(const u64 *w, size_t n) {
         if (w[i] >= lfp::P) return false;
     return true;
 }
+// helpers one translation unit of the slice lends the others (lfp_check.cpp)
+int lfp_commit_resident_enqueue(lfplus_ctx *c, u64 **res_dev);                                                                       // lfp_capi.cpp
+int lfp_upload_matrix(lfplus_ctx *c, size_t n, const u32 *rowptr, const u32 *col, const u64 *val, LfpMatrix &m);   // lfp_protocol.cpp
 // ---- exchanges of a sharded prover (no-ops when world == 1).  Every small exchange is "all-gather `words` u64 per rank, add the world vectors mod p" on host
 // buffers (the round messages and evaluations are summed on the host anyway); the two large ones (h and the folded g, n ring elements) are device all-gathers.
 static inline u64 lfp_addp(u64 a, u64 b) { unsigned __int128 s = (unsigned __int128)a + b; return (u64)(s >= lfp::P ? s - lfp::P : s); }

@@ -122,6 +122,14 @@ void launch_cm_evals_c(const u64 *R, size_t ldr, size_t n, const u64 *eq, u32 nt
 // ---- ComR1CS::linearize (r1cs.rs:76-139): degree-3 round of eq (ga gb - gc); part: cm_round_blocks(half) * 64
 void launch_r1cs_round_fused(const u64 *E, const u64 *G, size_t ld, size_t half, u64 rM, u64 *Eo, u64 *Go, size_t ld_o, u64 *part, hipStream_t s);   // + fix_variables of the previous round (E / G: previous tables)
 void launch_r1cs_round(const u64 *E, const u64 *G, size_t ld, size_t half, u64 *part, hipStream_t s);
+// ---- relation checks (lfp_check.hip): R_ComR1CS (r1cs.rs:21-60), R_LinB (lin.rs:29-40)
+// *first_bad = min(*first_bad, smallest row r < nrows with ((M_0 f) (M_1 f) - M_2 f)[r] != 0); vals[q]: LfpMatrix::spmv_vals() of matrix q (const_coef[q] as there)
+void launch_r1cs_residual(const u32 *const *rowptr, const u32 *const *col, const u64 *const *vals, const int *const_coef, const u64 *f, size_t nrows, u64 *first_bad,
+                          hipStream_t s);
+// out[q][16] = sum_row w[q ldw + row] f[row] for q < nw, nw in {2, 4, 8} (w: SCALAR weights, Montgomery; out canonical) in one pass over f; absmax (may be null):
+// *absmax = max(*absmax, largest |centred word| of f).  part: eval_chunks(n) * nw * 16 words
+void launch_linb_dots(const u64 *f, size_t n, const u64 *w, size_t ldw, u32 nw, u64 *part, u64 *out, u64 *absmax, hipStream_t s);
+void launch_absmax(const u64 *x, size_t words, u64 *absmax, hipStream_t s);
 void launch_vec_add(u64 *acc, const u64 *x, size_t n, hipStream_t s);
 void launch_check_canonical(const u64 *x /* 16-byte aligned */, size_t n, u32 *flag, u32 bit, hipStream_t s);
 void launch_tensor_level(const u64 *cur, u64 len, u64 r, u64 *nxt, hipStream_t s);

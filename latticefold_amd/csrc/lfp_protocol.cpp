@@ -283,6 +283,10 @@ int upload_matrix(lfplus_ctx *c, size_t n, const u32 *rowptr, const u32 *col, co
     HIPCHK(c, hipStreamSynchronize(c->st));   // the host staging vectors die here
     return LFPLUS_OK;
 }
+}  // namespace
+// (the same for lfp_check.cpp)
+int lfp_upload_matrix(lfplus_ctx *c, size_t n, const u32 *rowptr, const u32 *col, const u64 *val, LfpMatrix &m) { return upload_matrix(c, n, rowptr, col, val, m); }
+namespace {
 // the matrices of one call: the caller's CSR arrays uploaded for the duration of the call, or (rowptr == NULL) the set lfplus_set_matrices left in the context
 struct MatHold {
     std::vector<LfpMatrix> own;

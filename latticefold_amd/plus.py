@@ -27,6 +27,7 @@ class LfPlusError(RuntimeError):
 
 
 E_ARG, E_NO_DEVICE, E_HIP, E_EXP_DOMAIN, E_SMALL_N, E_REJECT = -1, -2, -3, -4, -5, -6
+REL_CM, REL_R1CS, REL_V, REL_NORM = 1, 2, 4, 8      # lfplus.h LFPLUS_REL_*: the components of a relation check (lfplus_r1cs_check / lfplus_linb_check)
 ABSENT = -128     # exponent digit of a zero entry of a monomial set (lfplus.h LFPLUS_ABSENT)
 
 
@@ -66,6 +67,9 @@ def _lib():
         L.lfplus_decompose.argtypes = [vp, C.c_uint64, u64p, u64p, C.c_uint32, u32pp, u32pp, u64pp, u64p, u64p, u64p, u64p, u64p, u64p]
         L.lfplus_decompose_resident.argtypes = [vp, C.c_uint64, u64p, u64p, C.c_uint32, u32pp, u32pp, u64pp, vp, vp, u64p, u64p, u64p, u64p]
         L.lfplus_get_witness.argtypes = [vp, u64p, C.c_uint64]
+        uip = C.POINTER(C.c_uint)
+        L.lfplus_r1cs_check.argtypes = [vp, u64p, u32pp, u32pp, u64pp, C.c_uint64, uip, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.lfplus_linb_check.argtypes = [vp, u64p, u64p, u64p, C.c_uint32, u32pp, u32pp, u64pp, u64p, C.c_uint64, uip, C.POINTER(C.c_uint64)]
         L.lfplus_tensor.argtypes = [vp, u64p, C.c_uint32, u64p]
         L.lfplus_tensor_product.argtypes = [vp, u64p, C.c_uint64, u64p, C.c_uint64, u64p]
         u8p, vpp, ip = C.POINTER(C.c_uint8), C.POINTER(vp), C.POINTER(C.c_int)
@@ -128,6 +132,14 @@ def scratch_bytes(device=0):
 def scratch_trim(device=-1):
     """Frees the scratch blocks destroyed contexts left in the process-wide cache (lfplus_scratch_trim; device < 0: every device)"""
     _lib().lfplus_scratch_trim(int(device))
+
+
+class _Resident(tuple):
+    """M = RESIDENT(count): use the matrices lfplus_set_matrices left in the (first) context"""
+
+
+def RESIDENT(count):
+    return _Resident((None,) * count)
 
 
 class PlusContext:
@@ -264,6 +276,46 @@ class PlusContext:
         self._chk(_lib().lfplus_get_witness(self.h, out.ctypes.data_as(u64p), self.n))
         return out
 
+    def _cm_arg(self, cm_f):
+        if cm_f is None:
+            return None, None
+        cm = np.ascontiguousarray(cm_f, dtype=np.uint64)
+        if cm.shape != (self.kappa, D):
+            raise LfPlusError(E_ARG, f"relation check: cm_f must be (kappa, 16) = ({self.kappa}, {D})")
+        return cm, cm.ctypes.data_as(u64p)
+
+    def r1cs_check(self, cm_f, M=RESIDENT(3), bound=0):
+        """R_ComR1CS on the resident (A, f) (lfplus_r1cs_check; r1cs.rs:21-60): cm_f = A f (None: not checked), (M_A f) o (M_B f) = M_C f row by row, and
+        ||f||_inf < bound (0: not checked) -> (ok, failed, first_bad, absmax): failed = OR of the REL_* bits of the failing components, first_bad = the smallest
+        row with a non-zero residual (n when all hold), absmax = the largest |centred coefficient| of f.  Nothing but these words leaves the device."""
+        if len(M) != 3:
+            raise LfPlusError(E_ARG, "r1cs_check: an R1CS has three matrices")
+        keep, rp, cp, vp = _csr_args(M)
+        cm, cmp_ = self._cm_arg(cm_f)
+        failed, fb, am = C.c_uint(), C.c_uint64(), C.c_uint64()
+        rc = _lib().lfplus_r1cs_check(self.h, cmp_, rp, cp, vp, int(bound), C.byref(failed), C.byref(fb), C.byref(am))
+        if rc not in (0, E_REJECT):
+            self._chk(rc)
+        return rc == 0, failed.value, fb.value, am.value
+
+    def linb_check(self, cm_f, r, v, M=(), bound=0):
+        """R_LinB on the resident (A, f) (lfplus_linb_check; lin.rs:29-40): cm_f = A f (None: not checked), v[0][pt] = mle(f)(r_pt) and v[1 + j][pt] =
+        mle(M_j f)(r_pt) for both points, ||f||_inf < bound (0: not checked).  r: (nvars, 2, 16) pairs of ring elements and v: (1 + len(M), 2, 16), both as
+        decompose takes / returns them -> (ok, failed, absmax)"""
+        nvars, nm = self.n.bit_length() - 1, len(M)
+        r, v = np.ascontiguousarray(r, dtype=np.uint64), np.ascontiguousarray(v, dtype=np.uint64)
+        if r.shape != (nvars, 2, D) or v.shape != (1 + nm, 2, D):
+            raise LfPlusError(E_ARG, f"linb_check: r must be ({nvars}, 2, 16) and v ({1 + nm}, 2, 16)")
+        r_a, r_b = np.ascontiguousarray(r[:, 0]), np.ascontiguousarray(r[:, 1])
+        keep, rp, cp, vp = _csr_args(M)
+        cm, cmp_ = self._cm_arg(cm_f)
+        failed, am = C.c_uint(), C.c_uint64()
+        rc = _lib().lfplus_linb_check(self.h, cmp_, r_a.ctypes.data_as(u64p), r_b.ctypes.data_as(u64p), nm, rp, cp, vp, v.ctypes.data_as(u64p), int(bound),
+                                      C.byref(failed), C.byref(am))
+        if rc not in (0, E_REJECT):
+            self._chk(rc)
+        return rc == 0, failed.value, am.value
+
     def decompose(self, f, A, B, r, M=(), into=None, out_bufs=None):
         """Decomp{f, r, M}.decompose(&A, B) (decomp.rs:32-99).  r: (nvars, 2, 16) pairs of ring elements; M: CSR matrices (rowptr, col, val[nnz][16]).
         -> dict(F0, F1 (n,16); C0, C1 (kappa,16); v0, v1 (1+len(M), 2, 16)): ((LinB0, LinB1), DecompProof) of the reference, flat.
@@ -366,14 +418,6 @@ def exp(digits):
 
 
 # ---- the transcript-driven part (src/transcript.rs, setchk.rs, rgchk.rs:81-258) ------------------------------------------------------------
-class _Resident(tuple):
-    """M = RESIDENT(count): use the matrices lfplus_set_matrices left in the (first) context"""
-
-
-def RESIDENT(count):
-    return _Resident((None,) * count)
-
-
 def _csr_args(mats):
     """mats: list of (rowptr uint32 [n+1], col uint32 [nnz], val uint64 [nnz][16]), or RESIDENT(count)"""
     if isinstance(mats, _Resident):
@@ -699,6 +743,18 @@ class ComR1CS:
     def matrices(self):
         return list(self.r1cs)
 
+    def check_relation(self, ctx, bound=0, resident=False):
+        """Is this instance in R_ComR1CS (r1cs.rs:21-60)?  cm_f = A f for the matrix resident in `ctx`, (M_A f) o (M_B f) = M_C f, ||f||_inf < bound (0: not
+        checked), all on the device (PlusContext.r1cs_check) -> (ok, failed, first_bad, absmax).  A host instance uploads its f into `ctx` (it becomes the
+        resident witness there); a resident instance is checked in the context that holds its witness, which is not touched.  resident: the three matrices are
+        the ones ctx.set_matrices / share_matrices left on the device"""
+        if self.f is None:
+            if ctx is not self.ctx:
+                raise LfPlusError(E_ARG, "ComR1CS.check_relation: a resident instance is checked in the context that holds its witness")
+        else:
+            ctx.set_witness(self.f)
+        return ctx.r1cs_check(self.cm_f, RESIDENT(3) if resident else self.r1cs, bound)
+
     def linearize(self, ctx, transcript, resident=False, preloaded=False, from_f_hint=None):
         """Linearize::linearize (r1cs.rs:76-139) on `ctx` (the witness becomes resident there) -> (LinB fields, ComR1CSProof fields); resident: the three
         matrices are the ones ctx.set_matrices / share_matrices left on the device; preloaded: ctx.set_witness(self.f) was already called (PlusProver.preload);
@@ -788,6 +844,7 @@ class PlusProver:
         16); transport is an allgather callable (host transport: PlusContext.set_sharding) or the bytes of an ncclUniqueId (RCCL: PlusContext.dist_init).
         Every rank makes the same calls with the same (whole) witnesses and gets the same proof."""
         self.M, self.params, self.transcript = list(M), params, transcript
+        self.device = device
         self.ctxs = [PlusContext(device) for _ in range(2 + ncomp)]
         if shard is not None:
             rank, world, transport = shard
@@ -849,6 +906,28 @@ class PlusProver:
         if self.device_acc and self.acc:
             return self.ctxs[0].get_witness(), self.ctxs[1].get_witness()
         return tuple(self.acc)
+
+    def decide(self, proof, bound=0):
+        """Are the two halves of the accumulator this prover holds after prove() -> proof valid LinB instances (lin.rs:29-40)?  Half i = (F_i, C_i, v_i) at the
+        points linb2x.ro: C_i = A F_i, v_i = the evaluations of F_i and M_j F_i at both points, ||F_i||_inf < bound (0: not checked) -- PlusContext.linb_check
+        on the device.  With device_acc the halves are checked where they live (ctxs[0] / ctxs[1]) and nothing moves; a host accumulator is uploaded into
+        scratch contexts.  -> [(ok, failed, absmax)] per half.  Read-only: the prover, its transcript and its accumulator are as before the call."""
+        if self.failed is not None or len(self.acc) != 2:
+            raise LfPlusError(E_ARG, "PlusProver.decide: no accumulator (call it after a successful prove)")
+        r, dproof, out = _ro_pairs(np.asarray(proof["linb2x"]["ro"], dtype=np.uint64)), proof["dproof"], []
+        for i in range(2):
+            if self.device_acc:
+                out.append(self.ctxs[i].linb_check(dproof[f"C{i}"], r, dproof[f"v{i}"], self.res, bound))
+                continue
+            cx = PlusContext(self.device)
+            try:
+                cx.share_matrix(self.ctxs[0])
+                cx.share_matrices(self.ctxs[0])
+                cx.set_witness(self.acc[i])
+                out.append(cx.linb_check(dproof[f"C{i}"], r, dproof[f"v{i}"], self.res, bound))
+            finally:
+                cx.close()
+        return out
 
     def prove(self, comp):
         """PlusProver::prove (plus.rs:77-108) -> PlusProof fields: linb2x, lproof, cmproof, dproof"""
