@@ -206,7 +206,10 @@ typedef struct {
     uint32_t s;       /* log2 m */
     uint32_t wit_len; /* ring elements in w_ccs */
     uint32_t l;       /* x_len */
-    uint32_t L, K, b; /* DecompositionParams (decomposition_parameters.rs:11-20) */
+    uint32_t L, K, b; /* DecompositionParams (decomposition_parameters.rs:11-20).  b = 2 everywhere; b = 4, 8, 16 on an unsharded Goldilocks context
+                       * (K <= 11).  K base-b digits must cover B/2 under the active digit rule (lf_set_digit_mode): rule 0 reaches
+                       * +-(b/2)(b^K - 1)/(b - 1), rule 1 only (b/2 - 1)(b^K - 1)/(b - 1) on the positive side -- checked by lf_ccs_load and again where a
+                       * step starts; anything else is LF_ERR_UNSUPPORTED */
     uint64_t B;
     uint32_t kappa;
     uint32_t t, q, d; /* #matrices, #multisets, degree */

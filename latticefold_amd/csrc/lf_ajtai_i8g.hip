@@ -444,6 +444,9 @@ __device__ __forceinline__ u64 g_s128_mod_small(__int128 v, u64 p) {
 }  // namespace
 // y[row][c_out] = sum_k 128^k * (+-)(C_k + 128 * colsum_k) mod p, canonical, coefficient form.  Element e = row0 + i of kappa_total:
 // soa != 0: out[c_out * kappa_total + e], else out[e * RD + c_out].  p_small = 0: the Goldilocks modulus.
+// PER_PLANE: no recombination -- plane p is a commitment of its own (the part commitments of a base-b decomposition, lf_sb.h): element p * kappa_total + e of
+// NP * kappa_total, out[c_out * NP * kappa_total + ..] (soa) or out[.. * RD + c_out].
+template <bool PER_PLANE>
 __global__ void __launch_bounds__(256) k_ajtai_i8g_finish(const long long *sum, u32 mth0, u32 mth1, u32 NT, u32 ndi, u32 NP, u32 kappa, u32 row0, u32 kappa_total, u32 RD,
                                                           u32 NL, u64 p_small, int soa, u64 *out) {
     const u32 o = blockIdx.x * 256 + threadIdx.x;
@@ -475,7 +478,12 @@ __global__ void __launch_bounds__(256) k_ajtai_i8g_finish(const long long *sum, 
             tot += (__int128)(c + 128 * Tsum) << (8 * u);
         }
         if (co < HALF) tot = -tot;
-        if (p_small) {
+        if (PER_PLANE) {
+            const u64 v = p_small ? g_s128_mod_small(tot, p_small) : fq_from_s128((u64)tot, (int64_t)(tot >> 64));
+            const size_t ep = (size_t)p * kappa_total + row0 + i, ne = (size_t)NP * kappa_total;
+            if (soa) out[(size_t)co * ne + ep] = v;
+            else out[ep * RD + co] = v;
+        } else if (p_small) {
             val = (val + (u64)(((unsigned __int128)g_s128_mod_small(tot, p_small) * pw) % p_small)) % p_small;
             pw = (pw * 128) % p_small;
         } else {
@@ -483,6 +491,7 @@ __global__ void __launch_bounds__(256) k_ajtai_i8g_finish(const long long *sum, 
             pw = fq_mul(pw, 128);
         }
     }
+    if (PER_PLANE) return;
     const size_t e = (size_t)row0 + i;
     if (soa) out[(size_t)co * kappa_total + e] = val;
     else out[e * RD + co] = val;
@@ -656,7 +665,7 @@ int ajtai_i8g_scratch(const AjtaiI8Ring &R, u32 MT, size_t n, u32 NP, u32 nwg, s
     return 0;
 }
 int launch_ajtai_i8g(const AjtaiI8Ring &R, const unsigned char *Ab, u32 MT, const unsigned long long *pre, size_t ldw, size_t n, u32 kappa, u32 row0, u32 kappa_total,
-                     u32 NP, u32 nwg, int32_t *part, int32_t *dsum, long long *sum, u64 *coef_out, hipStream_t s) {
+                     u32 NP, u32 nwg, int32_t *part, int32_t *dsum, long long *sum, u64 *coef_out, hipStream_t s, int per_plane) {
     GPlan g;
     if (!g_plan(R, MT, n, NP, nwg, &g) || R.NL * kappa > 16 * MT) return -1;
     AjtaiI8GArgs a;
@@ -693,8 +702,13 @@ int launch_ajtai_i8g(const AjtaiI8Ring &R, const unsigned char *Ab, u32 MT, cons
 #undef LF_G_LAUNCH
     hipLaunchKernelGGL(k_ajtai_i8g_sum, dim3((unsigned)cdiv(g.sum_words, 256)), dim3(256), 0, s, a.part[0], g.per[0], g.nch[0] * g.nsub[0], a.part[1], g.per[1],
                        g.nch[1] * g.nsub[1], dsum, g.ndi, g.nch[0], sum);
-    hipLaunchKernelGGL(k_ajtai_i8g_finish, dim3((unsigned)cdiv((size_t)kappa * R.RD, 256)), dim3(256), 0, s, sum, g.mth[0], g.mth[1], g.NT, g.ndi, NP, kappa, row0,
+    if (per_plane)
+        hipLaunchKernelGGL(k_ajtai_i8g_finish<true>, dim3((unsigned)cdiv((size_t)kappa * R.RD, 256)), dim3(256), 0, s, sum, g.mth[0], g.mth[1], g.NT, g.ndi, NP, kappa, row0,
+                           kappa_total, R.RD, R.NL, R.p_small, R.soa_out, coef_out);
+    else
+    hipLaunchKernelGGL(k_ajtai_i8g_finish<false>, dim3((unsigned)cdiv((size_t)kappa * R.RD, 256)), dim3(256), 0, s, sum, g.mth[0], g.mth[1], g.NT, g.ndi, NP, kappa, row0,
                        kappa_total, R.RD, R.NL, R.p_small, R.soa_out, coef_out);
+    if (per_plane && hipGetLastError() != hipSuccess) return -1;
     return (int)grid.x;
 }
 }  // namespace lf

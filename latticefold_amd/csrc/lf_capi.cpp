@@ -673,6 +673,49 @@ static int commit_dev_i8g(lf_ctx *c, const u64 *F, size_t ldF, u32 batch, const 
         else launch_i8g_cut_ntt(c->d_icrt, c->d_icrt_sp_val, c->d_icrt_sp_col, F + (size_t)b * 24 * ldF, ldF, c->nA, NP, pre, ntiles, c->stream());
     });
 }
+// The K - 1 part commitments of a base-b decomposition (decomposition.rs:178-201) as the planes of ONE general-commit launch per row chunk: A leaves HBM once
+// per decomposition.  D [NP][24][ldn] are the operand words already (lf_sb.h); the finish writes every plane's commitment instead of recombining them.
+int commit_parts_i8g(lf_ctx *c, const unsigned char *D, size_t ldn, u32 NP, u64 *out_dev) {
+    if (!c->A_loaded || !c->i8_nch || !c->dAb) return LF_ERR_STATE;
+    if (c->A_col0 != 0 || c->nA != c->N || ldn != sb_ld(c->N)) return LF_ERR_UNSUPPORTED;
+    const AjtaiI8Ring R = ajtai_i8_goldilocks();
+    const u32 nch = c->i8_nch, kc = c->i8_kc, MT = ajtai_i8_row_tiles(R, kc), nwg = 256;
+    const size_t ntiles = (c->nA + 7) / 8, chunk_bytes = ntiles * (R.RD / 8) * MT * 1024;
+    size_t pw, dw, sw;
+    if (ajtai_i8g_scratch(R, MT, c->nA, NP, nwg, &pw, &dw, &sw) != 0) return LF_ERR_UNSUPPORTED;
+    int32_t *part, *dsum;
+    long long *sum;
+    u64 *coef, *ntt;
+    const size_t ne = (size_t)NP * c->kappa;
+    RET(c->tbuf("i8g_part", pw, &part));
+    RET(c->tbuf("i8g_dsum", dw, &dsum));
+    RET(c->tbuf("i8g_sum", sw, &sum));
+    RET(c->tbuf("sb_y_coef", 24 * ne, &coef));
+    RET(c->tbuf("sb_y_ntt", 24 * ne, &ntt));
+    const size_t ev = c->ev_begin(1);
+    for (u32 ch = 0; ch < nch; ch++) {
+        const u32 row0 = ch * kc, kn = c->kappa - row0 < kc ? c->kappa - row0 : kc;
+        if (launch_ajtai_i8g(R, c->dAb + (size_t)ch * chunk_bytes, MT, (const unsigned long long *)D, ldn / 8, c->nA, kn, row0, c->kappa, NP, nwg, part, dsum, sum, coef,
+                             c->stream(), 1) < 0)
+            return hipGetLastError() == hipSuccess ? LF_ERR_UNSUPPORTED : LF_ERR_HIP;
+    }
+    c->ev_end(ev);
+    launch_crt_fwd(c->dcrt, coef, ntt, ne, c->stream());
+    launch_soa_to_aos(ntt, out_dev, ne, c->stream());
+    if (hipGetLastError() != hipSuccess) return LF_ERR_HIP;
+    return LF_OK;
+}
+int sb_cut_parts(lf_ctx *c, const lf_witness *wit, const char *name, const unsigned char **D) {
+    const lf_params &P = c->P;
+    if (!sb_base_ok(P.b) || c->sh_world > 1 || c->comm[0].model) return LF_ERR_UNSUPPORTED;
+    if (!sb_digits_cover(P.b, P.K, P.B, c->digit_mode)) return LF_ERR_UNSUPPORTED;   // never a truncated decomposition
+    unsigned char *d;
+    const size_t ldn = sb_ld(c->N);
+    RET(c->tbuf(name, (size_t)P.K * 24 * ldn, &d));
+    if (launch_sb_cut(wit->planes, c->N, P.K, sb_log2(P.b), c->digit_mode, d, ldn, c->stream()) != 0) return LF_ERR_HIP;
+    *D = d;
+    return LF_OK;
+}
 int witness_commit_dev(lf_ctx *c, const lf_witness *w, u64 *out_dev) { return commit_dev_i8g(c, nullptr, 0, 1, w->planes + c->A_col0, w->N, out_dev, false); }
 // F: [batch][24][ldF] device, pointing at this rank's first column; out_dev: [batch][kappa][24] device AoS (PARTIAL when sharded)
 static int commit_dev(lf_ctx *c, const u64 *F, size_t ldF, u32 batch, u64 *out_dev, bool timed) { return commit_dev_i8g(c, F, ldF, batch, nullptr, 0, out_dev, timed); }
@@ -932,16 +975,14 @@ int lf_ccs_load(lf_ctx *c, const lf_params *p, const uint32_t *const *rowptr, co
     if (p->s < 3 || p->s > 30 || p->t == 0 || p->t > 4 || p->q == 0 || p->q > 8 || p->K == 0 || p->K > 32 || p->L == 0 || p->L > 8 ||
         p->d + 1 > 4 || p->wit_len == 0)
         return LF_ERR_UNSUPPORTED;
-    if (p->b != 2) return LF_ERR_UNSUPPORTED;  // folding comb is specialised to b = 2 (all reference Goldilocks rows)
+    // b = 2: the bit-plane kernels of the reference Goldilocks rows; b = 4, 8, 16: the small-base path (lf_sb.h), one unsharded GPU
+    if (p->b != 2 && !sb_base_ok(p->b)) return LF_ERR_UNSUPPORTED;
+    if (p->b != 2 && (c->sh_world > 1 || c->comm[0].model || p->K > 11)) return LF_ERR_UNSUPPORTED;   // (K - 1 <= 10 planes of one commit launch)
     // B = 2^32 (config.toml:158): balanced digits lie in [-2^31, 2^31]; the int32 planes hold all of them but +2^31 exactly, which the ingest
     // rejects (LF_ERR_UNSUPPORTED) -- one value in 2^32 per digit
     if (!pow2(p->B) || p->B > (1ULL << 32)) return LF_ERR_UNSUPPORTED;
-    {   // K base-2 digits must cover |coeff| <= B/2
-        u64 half = p->B / 2;
-        u32 need = 0;
-        while ((half >> need) != 0) need++;
-        if (need > p->K) return LF_ERR_UNSUPPORTED;
-    }
+    // K base-b digits must cover |coeff| <= B/2 under the active digit rule (checked again where a step starts: the rule may change after the load)
+    if (!sb_digits_cover(p->b, p->K, p->B, c->digit_mode)) return LF_ERR_UNSUPPORTED;
     size_t m = (size_t)1 << p->s, N = (size_t)p->wit_len * p->L, n = (size_t)p->l + 1 + p->wit_len;
     if (N > m) return LF_ERR_SIZE_BOUNDS;  // sanity_check, nifs.rs:165-173
     // the reference indexes comb values by matrix index: multisets must concatenate to 0..t-1

@@ -21,6 +21,7 @@
 #include "lf_common.h"
 #include "lf_dist.h"
 #include "lf_kernels.h"
+#include "lf_sb.h"
 #include "lf_verify.h"
 
 using namespace lf;
@@ -402,6 +403,7 @@ struct SideState {
     // (z, x_s valid once z_ev has completed), -1 = that lane failed, 0 = nobody built it yet
     std::atomic<int> z_state{0};
     hipEvent_t z_ev = nullptr;
+    const unsigned char *D = nullptr;   // small-base path (b > 2, lf_sb.h): the K digit planes of the side's witness, [K][24][sb_ld(N)]
     u32 *sv_bits = nullptr;  // bit-plane form of the witness planes for the GEMM rounds of the folding sumcheck (lf_sv_rounds.h), if built ahead
     ~SideState() { if (z_ev) (void)hipEventDestroy(z_ev); }
 };
@@ -443,6 +445,15 @@ size_t dec_proof_len(const lf_params *p);
 size_t lin_proof_len(const lf_params *p);
 int commit_planes_i8(lf_ctx *c, const int32_t *planes, size_t ld, u32 k0, u32 NP, u64 *out_dev, const lf_witness *wit = nullptr);
 int commit_download(lf_ctx *c, const u64 *dev, size_t words, u64 *host);
+// small-base path: the NP part commitments y_k = A f_k of the digit planes D [NP][24][ldn] (lf_sb.h) in ONE pass over A -> out_dev [NP][kappa][24] NTT form
+int commit_parts_i8g(lf_ctx *c, const unsigned char *D, size_t ldn, u32 NP, u64 *out_dev);
+// the digit planes of a witness, cut on the calling lane's stream into the buffer `name`
+int sb_cut_parts(lf_ctx *c, const lf_witness *wit, const char *name, const unsigned char **D);
+void fold_draw_rho(lf_ctx *c, Transcript &tr, const u64 *eta, std::vector<u64> &rho_c, std::vector<u64> &rho, std::vector<int8_t> &rho8);
+void fold_instance_host(lf_ctx *c, const std::vector<Fq3> &pt, const u64 *theta, const u64 *eta, const std::vector<u64> &rho_c, const std::vector<u64> &rho, SideState *S,
+                        u64 *lcccs_out);
+int fold_impl_sb(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out, lf_witness **w_out, u64 *proof);
+int sb_fold_round_abi(lf_ctx *c, const u64 *t5, const u64 *F, size_t n, const Fq3Const *d_mu, u64 *evals_out);
 int up_ring(lf_ctx *c, const u64 *host, size_t n, u64 *dst);
 int dot_batch_dev(lf_ctx *c, const u64 *X, size_t ldx, u32 na, const u64 *Y, size_t ldy, u32 nb, size_t n, u64 *dpart, u64 *od, hipStream_t st = nullptr,
                          const char *tag = "", unsigned char *yb_pre = nullptr);
@@ -452,7 +463,8 @@ int lin_tail_rounds(lf_ctx *c, Transcript &tr, const u64 *cur, const u64 *cure, 
                            u64 *msgs, u32 deg, const std::function<void(u32)> *after_round);
 int down_ring(lf_ctx *c, const u64 *src, size_t n, u64 *host);
 // z tables [K][24][n] = heads (l + 1 elements per table) || the recomposed witness columns [w0, w0 + wcnt) (lf_prove.cpp)
-int build_z(lf_ctx *c, const int32_t *planes, u32 K, int mode_bits, const u64 *heads, u64 *z, size_t w0 = 0, size_t wcnt = (size_t)-1);
+int build_z(lf_ctx *c, const int32_t *planes, u32 K, int mode_bits, const u64 *heads, u64 *z, size_t w0 = 0, size_t wcnt = (size_t)-1,
+            const unsigned char *D = nullptr /* small-base path: the digit planes the K parts come from (lf_sb.h) */);
 bool lcccs_point(const lf_params &P, const u64 *lcccs, std::vector<Fq3> &pt);   // the LCCCS point r as F_{p^3} challenges; false if not diagonal
 int witness_commit_dev(lf_ctx *c, const lf_witness *w, u64 *out_dev);   // Witness::commit into device memory (kappa ring elements, AoS; unsharded contexts)
 #pragma GCC visibility pop

@@ -160,12 +160,78 @@ static void sv_build_coef(lf_ctx *c, int V, const Fq3 *W, std::vector<u64> &out)
         for (int q = 0; q < 3; q++) out[i * 3 + q] = C[i].c[q];
 }
 
+// absorb eta and draw the short folding challenges: get_rhos (folding/utils.rs:116-131) -- coefficient form, NTT form and int8 coefficients of the 2K rho_i
+void fold_draw_rho(lf_ctx *c, Transcript &tr, const u64 *eta, std::vector<u64> &rho_c, std::vector<u64> &rho, std::vector<int8_t> &rho8) {
+    const lf_params &P = c->P;
+    const u32 K2 = 2 * P.K;
+    rho_c.assign((size_t)K2 * 24, 0); rho.assign((size_t)K2 * 24, 0); rho8.assign((size_t)K2 * 24, 0);
+    {
+        HostTimer ht(c);
+        tr.absorb_ring(eta, (size_t)K2 * P.t);
+        // get_rhos (folding/utils.rs:116-131)
+        tr.absorb_label("rho_s");
+        for (u32 i = 0; i + 1 < K2; i++) tr.get_short_challenge(&rho_c[(size_t)i * 24]);
+        rho_c[(size_t)(K2 - 1) * 24] = 1;
+        for (u32 i = 0; i < K2; i++) {
+            c->ring.crt(&rho_c[(size_t)i * 24], &rho[(size_t)i * 24]);
+            for (int q2 = 0; q2 < 24; q2++) {
+                u64 v = rho_c[(size_t)i * 24 + q2];
+                rho8[(size_t)i * 24 + q2] = (int8_t)(v > LF_P / 2 ? -(int64_t)(LF_P - v) : (int64_t)v);
+            }
+        }
+    }
+}
+// compute_v0_u0_x0_cm_0 (folding/utils.rs:460-521): the folded LCCCS from the point, theta, eta, the challenges rho_i and the 2K decomposed instances
+void fold_instance_host(lf_ctx *c, const std::vector<Fq3> &pt, const u64 *theta, const u64 *eta, const std::vector<u64> &rho_c, const std::vector<u64> &rho, SideState *S,
+                        u64 *lcccs_out) {
+    const lf_params &P = c->P;
+    const u32 K = P.K, K2 = 2 * K;
+    const size_t ll = lf_lcccs_len(&P);
+    HostTimer ht(c);
+    u64 *o = lcccs_out;
+    for (u32 i = 0; i < P.s; i++, o += 24) HostRing::from_fq3(pt[i], o);
+    {   // v_0 = rot_lin_combination(rho_coeff, theta) (cyclotomic-rings/src/rotation.rs:85-104)
+        Fq3 res[24];
+        for (int j = 0; j < 24; j++) res[j] = fq3_zero();
+        for (u32 i = 0; i < K2; i++) {
+            u64 rot[24];
+            memcpy(rot, &rho_c[(size_t)i * 24], sizeof(rot));
+            const u64 *th = theta + (size_t)i * 72;
+            for (int bi = 0; bi < 24; bi++) {
+                Fq3 b = fq3_make(th[3 * bi], th[3 * bi + 1], th[3 * bi + 2]);
+                for (int j = 0; j < 24; j++)
+                    if (rot[j]) res[j] = fq3_add(res[j], fq3_mul_fq(b, rot[j]));
+                // multiply by X modulo X^24 - X^12 + 1
+                u64 top = rot[23];
+                for (int j = 23; j > 0; j--) rot[j] = rot[j - 1];
+                rot[0] = fq_neg(top);
+                rot[12] = fq_add(rot[12], top);
+            }
+        }
+        for (int j = 0; j < 24; j++) { o[3 * j] = res[j].c[0]; o[3 * j + 1] = res[j].c[1]; o[3 * j + 2] = res[j].c[2]; }
+        o += 72;
+    }
+    u64 tmp[24];
+    auto part = [&](u32 i) { return &S[i < K ? 0 : 1].lcccs[(size_t)(i % K) * ll * 24]; };
+    for (u32 q2 = 0; q2 < P.kappa; q2++, o += 24) {
+        memset(o, 0, 24 * 8);
+        for (u32 i = 0; i < K2; i++) { c->ring.mul_ntt(part(i) + ((size_t)P.s + 3 + q2) * 24, &rho[(size_t)i * 24], tmp); HostRing::add(o, tmp, o); }
+    }
+    for (u32 j = 0; j < P.t; j++, o += 24) {
+        memset(o, 0, 24 * 8);
+        for (u32 i = 0; i < K2; i++) { c->ring.mul_ntt(&rho[(size_t)i * 24], eta + ((size_t)i * P.t + j) * 24, tmp); HostRing::add(o, tmp, o); }
+    }
+    for (u32 q2 = 0; q2 < P.l + 1; q2++, o += 24) {
+        memset(o, 0, 24 * 8);
+        for (u32 i = 0; i < K2; i++) { c->ring.mul_ntt(&rho[(size_t)i * 24], part(i) + ((size_t)P.s + 3 + P.kappa + P.t + q2) * 24, tmp); HostRing::add(o, tmp, o); }
+    }
+}
 // LFFoldingProver::prove (nifs/folding.rs:42-130)
 int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out, lf_witness **w_out, u64 *proof) {
+    if (c->P.b != 2) return fold_impl_sb(c, tr, S, lcccs_out, w_out, proof);   // small-base path (lf_fold_sb.cpp)
     const lf_params &P = c->P;
     size_t m = c->m, n = c->n, N = c->N;
     u32 K = P.K, K2 = 2 * K, deg = 2 * P.b;
-    size_t ll = lf_lcccs_len(&P);
     std::vector<Fq3> alpha(K2), zeta(K2), mu(K2), beta(P.s);
     {
         HostTimer ht(c);
@@ -718,23 +784,9 @@ int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out,
     HIPCHK(hipStreamSynchronize(c->stream()));
     memcpy(eta, hp + (size_t)K2 * 72, (size_t)K2 * P.t * 24 * 8);
     TL_MARK(" theta/eta");
-    std::vector<u64> rho_c((size_t)K2 * 24, 0), rho((size_t)K2 * 24);
-    std::vector<int8_t> rho8((size_t)K2 * 24, 0);
-    {
-        HostTimer ht(c);
-        tr.absorb_ring(eta, (size_t)K2 * P.t);
-        // get_rhos (folding/utils.rs:116-131)
-        tr.absorb_label("rho_s");
-        for (u32 i = 0; i + 1 < K2; i++) tr.get_short_challenge(&rho_c[(size_t)i * 24]);
-        rho_c[(size_t)(K2 - 1) * 24] = 1;
-        for (u32 i = 0; i < K2; i++) {
-            c->ring.crt(&rho_c[(size_t)i * 24], &rho[(size_t)i * 24]);
-            for (int q2 = 0; q2 < 24; q2++) {
-                u64 v = rho_c[(size_t)i * 24 + q2];
-                rho8[(size_t)i * 24 + q2] = (int8_t)(v > LF_P / 2 ? -(int64_t)(LF_P - v) : (int64_t)v);
-            }
-        }
-    }
+    std::vector<u64> rho_c, rho;
+    std::vector<int8_t> rho8;
+    fold_draw_rho(c, tr, eta, rho_c, rho, rho8);
     // f_0 in the coefficient domain -> new witness
     int8_t *d_rho;
     RET(c->tbuf("c_rho", (size_t)K2 * 24 + 64, &d_rho));
@@ -754,46 +806,7 @@ int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out,
     TL_MARK("  eta absorbed, rho drawn, fold_witness enqueued");
 
     // compute_v0_u0_x0_cm_0 (folding/utils.rs:460-521) on the host while the GPU folds the witness
-    {
-    HostTimer ht(c);
-    u64 *o = lcccs_out;
-    for (u32 i = 0; i < P.s; i++, o += 24) HostRing::from_fq3(pt[i], o);
-    {   // v_0 = rot_lin_combination(rho_coeff, theta) (cyclotomic-rings/src/rotation.rs:85-104)
-        Fq3 res[24];
-        for (int j = 0; j < 24; j++) res[j] = fq3_zero();
-        for (u32 i = 0; i < K2; i++) {
-            u64 rot[24];
-            memcpy(rot, &rho_c[(size_t)i * 24], sizeof(rot));
-            const u64 *th = theta + (size_t)i * 72;
-            for (int bi = 0; bi < 24; bi++) {
-                Fq3 b = fq3_make(th[3 * bi], th[3 * bi + 1], th[3 * bi + 2]);
-                for (int j = 0; j < 24; j++)
-                    if (rot[j]) res[j] = fq3_add(res[j], fq3_mul_fq(b, rot[j]));
-                // multiply by X modulo X^24 - X^12 + 1
-                u64 top = rot[23];
-                for (int j = 23; j > 0; j--) rot[j] = rot[j - 1];
-                rot[0] = fq_neg(top);
-                rot[12] = fq_add(rot[12], top);
-            }
-        }
-        for (int j = 0; j < 24; j++) { o[3 * j] = res[j].c[0]; o[3 * j + 1] = res[j].c[1]; o[3 * j + 2] = res[j].c[2]; }
-        o += 72;
-    }
-    u64 tmp[24];
-    auto part = [&](u32 i) { return &S[i < K ? 0 : 1].lcccs[(size_t)(i % K) * ll * 24]; };
-    for (u32 q2 = 0; q2 < P.kappa; q2++, o += 24) {
-        memset(o, 0, 24 * 8);
-        for (u32 i = 0; i < K2; i++) { c->ring.mul_ntt(part(i) + ((size_t)P.s + 3 + q2) * 24, &rho[(size_t)i * 24], tmp); HostRing::add(o, tmp, o); }
-    }
-    for (u32 j = 0; j < P.t; j++, o += 24) {
-        memset(o, 0, 24 * 8);
-        for (u32 i = 0; i < K2; i++) { c->ring.mul_ntt(&rho[(size_t)i * 24], eta + ((size_t)i * P.t + j) * 24, tmp); HostRing::add(o, tmp, o); }
-    }
-    for (u32 q2 = 0; q2 < P.l + 1; q2++, o += 24) {
-        memset(o, 0, 24 * 8);
-        for (u32 i = 0; i < K2; i++) { c->ring.mul_ntt(&rho[(size_t)i * 24], part(i) + ((size_t)P.s + 3 + P.kappa + P.t + q2) * 24, tmp); HostRing::add(o, tmp, o); }
-    }
-    }
+    fold_instance_host(c, pt, theta, eta, rho_c, rho, S, lcccs_out);
     TL_MARK("  folded instance on the host");
     HIPCHK(hipStreamSynchronize(c->stream()));
     *w_out = new lf_witness{c, npl, N, c->device, N * 24 * 4};
@@ -967,8 +980,9 @@ int lf_sumcheck_fold_round(lf_ctx *c, const uint64_t *r_prev, uint64_t *evals_ou
     FoldRoundArgs a;
     a.eqL = t5; a.eqR = t5 + 3 * n; a.eqB = t5 + 6 * n; a.G1 = t5 + 9 * n; a.G2 = t5 + 33 * n;
     a.ld = n; a.n = n; a.p0 = 0; a.pcnt = n / 2; a.pF0 = 0;
-    launch_fold_round(c->dcrt, a, F[c->sf_cur], n, P.K, d_mu, partial, od, c->stream());
     c->sf_round++;
+    if (P.b != 2) return sb_fold_round_abi(c, t5, F[c->sf_cur], n, d_mu, evals_out);
+    launch_fold_round(c->dcrt, a, F[c->sf_cur], n, P.K, d_mu, partial, od, c->stream());
     return down_small(c, od, (size_t)(2 * P.b + 1) * 24, evals_out);
 }
 int lf_sumcheck_fold_end(lf_ctx *c) {

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include "lf_kernels_dev.cuh"
+#include "lf_sb.h"
 
 namespace lf {
 
@@ -426,6 +427,32 @@ void launch_recompose_crt(const DevCrt &t, const int32_t *planes, size_t n_plane
     for (int l = 0; l < 8; l++) { bp.v[l] = pw; pw = fq_mul(pw, B % LF_P); }
     hipLaunchKernelGGL(k_recompose_crt, dim3(cdiv(wit_len, 256), K), dim3(256), 0, s, t, planes, n_planes, wit_len, L, bp, K, mode_bits,
                        out, ldz, off);
+}
+// the same tails from the digit planes of the small-base path (lf_sb.h: D [K][24][ldn], byte = 64 + digit): part k of element i is sum_l B^l digit_k(f[i L + l])
+__global__ void __launch_bounds__(256) k_sb_recompose_crt(DevCrt t, const unsigned char *D, size_t ldn, u32 wit_len, u32 L, BPow bp, u64 *out, size_t ldz, size_t off) {
+    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    u32 k = blockIdx.y;
+    if (i >= wit_len) return;
+    u64 a[24];
+#pragma unroll
+    for (int c = 0; c < 24; c++) {
+        u64 acc = 0;
+        for (u32 l = 0; l < L; l++) {
+            const int d = (int)D[((size_t)k * 24 + c) * ldn + i * L + l] - 64;
+            const u64 term = fq_mul(bp.v[l], (u64)(d < 0 ? -d : d));
+            acc = d < 0 ? fq_sub(acc, term) : fq_add(acc, term);
+        }
+        a[c] = acc;
+    }
+    crt_store(a, out + (size_t)k * 24 * ldz, ldz, off + i, t);
+}
+int launch_sb_recompose_crt(const DevCrt &t, const unsigned char *D, size_t ldn, u32 wit_len, u32 L, u64 B, u32 K, u64 *out, size_t ldz, size_t off, hipStream_t s) {
+    if (!wit_len || L > 8) return -1;
+    BPow bp;
+    u64 pw = 1;
+    for (int l = 0; l < 8; l++) { bp.v[l] = pw; pw = fq_mul(pw, B % LF_P); }
+    hipLaunchKernelGGL(k_sb_recompose_crt, dim3(cdiv(wit_len, 256), K), dim3(256), 0, s, t, D, ldn, wit_len, L, bp, out, ldz, off);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 

@@ -218,10 +218,14 @@ int shard_col_range(lf_ctx *c, size_t r0, size_t rcnt, size_t *lo, size_t *hi) {
 }
 // w0 / wcnt (optional): only the witness columns [w0, w0 + wcnt) -- z columns l + 1 + w0 .. -- are built (a sharded rank's slice; the heads always)
 int build_z(lf_ctx *c, const int32_t *planes, u32 K, int mode_bits, const u64 *heads /* K*(l+1) ring AoS host */, u64 *z /* [K][24][n] */,
-            size_t w0, size_t wcnt) {
+            size_t w0, size_t wcnt, const unsigned char *D) {
     const lf_params &P = c->P;
     u32 hl = P.l + 1;
     if (wcnt == (size_t)-1) { w0 = 0; wcnt = P.wit_len; }
+    if (D) {   // small-base path: the K parts come from their digit planes (whole witness: b > 2 is never sharded)
+        if (w0 != 0 || wcnt != P.wit_len || !mode_bits) return LF_ERR_UNSUPPORTED;
+        if (launch_sb_recompose_crt(c->dcrt, D, sb_ld(c->N), P.wit_len, P.L, P.B, K, z, c->n, hl, c->stream()) != 0) return LF_ERR_HIP;
+    } else
     if (wcnt) launch_recompose_crt(c->dcrt, planes + w0 * P.L, c->N, (u32)wcnt, P.L, P.B, K, mode_bits, z, c->n, hl + w0, c->stream());
     // heads: write plane entries 0..l of each table
     std::vector<u64> h((size_t)K * 24 * hl);
@@ -423,7 +427,7 @@ static void compute_x_s(const lf_ctx *c, const u64 *xh /* (l+1) NTT */, u64 *x_s
 // commit_witnesses (decomposition.rs:178-201): NTT of the K-1 upper bit-planes, one batched pass over A, then
 // y_0 = cm - sum_{k>=1} b^k y_k on the host.  Depends only on the witness and on cm -- not on the evaluation point.
 // `enqueue_only`: leave the result in flight on the lane's stream (finished later by decompose_commit_finish).
-static int decompose_commit_enqueue(lf_ctx *c, const lf_witness *wit, u64 **yd_out, size_t *ev_out, const char *ybuf = "dec_y") {
+static int decompose_commit_enqueue(lf_ctx *c, const lf_witness *wit, u64 **yd_out, size_t *ev_out, const char *ybuf = "dec_y", const unsigned char *D = nullptr) {
     const lf_params &P = c->P;
     size_t N = c->N;
     u32 K = P.K;
@@ -431,6 +435,13 @@ static int decompose_commit_enqueue(lf_ctx *c, const lf_witness *wit, u64 **yd_o
     RET(c->tbuf(ybuf, (size_t)K * P.kappa * 24, &yd));
     size_t ph = c->ev_begin(11);
     if (!c->i8_nch) return LF_ERR_STATE;
+    if (P.b != 2) {   // small-base path: parts 1 .. K-1 of the digit planes are the planes of one general-commit launch
+        if (!D) return LF_ERR_STATE;
+        if (K > 1) RET(commit_parts_i8g(c, D + (size_t)24 * sb_ld(N), sb_ld(N), K - 1, yd));
+        *yd_out = yd;
+        *ev_out = ph;
+        return LF_OK;
+    }
     // int8 matrix cores: digits straight from the coefficient planes, no bit-plane NTTs (this rank's column slice when sharded)
     RET(commit_planes_i8(c, wit->planes + c->A_col0, N, 1, K - 1, yd, wit));
     *yd_out = yd;
@@ -548,7 +559,8 @@ static int decompose_prepare_z(lf_ctx *c, const u64 *xh /* (l+1) elements: x_w |
             wcnt = w1 > w0 ? w1 - w0 : 0;
             if (w0 + wcnt > P.wit_len) wcnt = P.wit_len > w0 ? P.wit_len - w0 : 0;
         }
-        if (rc == LF_OK) rc = build_z(c, wit->planes, K, 1, x_s, z, w0, wcnt);
+        if (rc == LF_OK && P.b != 2 && !S.D) rc = LF_ERR_STATE;
+        if (rc == LF_OK) rc = build_z(c, wit->planes, K, 1, x_s, z, w0, wcnt, S.D);
     }
     if (rc == LF_OK && !S.z_ev && hipEventCreateWithFlags(&S.z_ev, hipEventDisableTiming) != hipSuccess) rc = LF_ERR_HIP;
     if (rc == LF_OK && hipEventRecord(S.z_ev, c->stream()) != hipSuccess) rc = LF_ERR_HIP;
@@ -588,6 +600,11 @@ static int decompose_evals(lf_ctx *c, const u64 *lcccs, const std::vector<Fq3> &
         if (c->vs_wit == wit && c->vs_eq == eq_r && c->sh_world == 1) {   // computed by the linearization of this step at this very point
             HIPCHK(hipMemcpyAsync(od_v, c->vs_dev, (size_t)K * 72 * 8, hipMemcpyDeviceToDevice, c->stream()));
             c->vs_wit = nullptr;
+        } else if (P.b != 2) {   // small-base path: the digit planes against eq(r)
+            u64 *sbp;
+            if (!S.D) return LF_ERR_STATE;
+            RET(c->tbuf("sb_eval_partial", sb_eval_partial_words(K), &sbp));
+            if (launch_sb_eval(S.D, sb_ld(N), N, eq_r, m, K, sbp, od_v, c->stream()) != 0) return LF_ERR_HIP;
         } else {
             if (c->sh_world > 1) HIPCHK(hipMemsetAsync(od, 0, (32 * 72 + 32 * 4 * 24) * 8, c->stream()));   // (one exchange carries v_s and u_s: the gaps of the buffer must be canonical)
             RET(coef_eval_dev(c, wit->planes + i0, cnt, eq_r + i0, m, K, 1, partial, od_v, N, c->sh_world == 1 ? wit : nullptr));
@@ -718,6 +735,33 @@ int lf_fold_step(lf_ctx *c, lf_transcript *t, const uint64_t *acc, const lf_witn
     std::vector<Fq3> rR;
     // (after an RCCL handshake the agreed value decides: a rank-local environment switch must not make this rank issue a different collective sequence)
     const bool shard_threads = c->agreed_two_lanes >= 0 ? c->agreed_two_lanes == 1 : (c->tn.shard_two_lanes == 1 || (c->tn.shard_two_lanes < 0 && c->two_lanes_ok));
+    if (P.b != 2) {
+        // Small-base path (b = 4, 8, 16): one lane, in program order -- the part cut of both witnesses, the left decomposition, the linearization, the right
+        // decomposition, the absorbs in transcript order.  (The two-lane schedule of b = 2 is built around its bit-plane kernels)
+        u64 *ydL = nullptr, *ydR = nullptr;
+        size_t evL = 0, evR = 0;
+        rc = sb_cut_parts(c, w_acc, "sb_D_L", &S[0].D);
+        if (rc == LF_OK) rc = sb_cut_parts(c, w_i, "sb_D_R", &S[1].D);
+        if (rc == LF_OK) rc = decompose_commit_enqueue(c, w_acc, &ydL, &evL, "dec_y", S[0].D);
+        if (rc == LF_OK) rc = decompose_commit_finish(c, acc + ((size_t)P.s + 3) * 24, ydL, evL, decl);
+        if (rc == LF_OK) rc = decompose_evals(c, acc, rL, w_acc, "L", nullptr, S[0], decl);
+        if (rc == LF_OK) rc = decompose_commit_enqueue(c, w_i, &ydR, &evR, "dec_y2", S[1].D);
+        if (rc == LF_OK) {
+            HostTimer ht(c);
+            tr.absorb_label("acc");
+            tr.absorb_ring(acc, ll);
+            tr.absorb_label("cm_i");
+            tr.absorb_ring(cm_i, lf_cccs_len(&P));
+        }
+        if (rc == LF_OK) rc = linearize_impl(c, tr, cm_i, w_i, lin.data(), lin_proof, &eq_r_R);
+        if (rc == LF_OK) {
+            lcccs_point(P, lin.data(), rR);
+            rc = decompose_evals(c, lin.data(), rR, w_i, "R", eq_r_R, S[1], decr);
+        }
+        if (rc == LF_OK) c->host_tr_ms += absorb_decomposition(P, tr, acc, decl, S[0]);
+        if (rc == LF_OK) rc = decompose_commit_finish(c, cm_i, ydR, evR, decr);
+        if (rc == LF_OK) c->host_tr_ms += absorb_decomposition(P, tr, lin.data(), decr, S[1]);
+    } else
     if (c->sh_world > 1 && !shard_threads) {
         // Sharded step: ONE host thread issues every exchange in program order (collectives of the ranks can then never cross), the two
         // streams still overlap the right commit with the linearization rounds on the GPU.  (LF_SHARD_TWO_LANES=1: the threaded schedule
@@ -884,7 +928,8 @@ int lf_decomposition_prove(lf_ctx *c, lf_transcript *t, const uint64_t *lcccs, c
     u64 *yd = nullptr;
     size_t ev = 0;
     SideState S;
-    RET(decompose_commit_enqueue(c, wit, &yd, &ev));
+    if (P.b != 2) RET(sb_cut_parts(c, wit, "sb_D_L", &S.D));
+    RET(decompose_commit_enqueue(c, wit, &yd, &ev, "dec_y", S.D));
     RET(decompose_commit_finish(c, lcccs + ((size_t)P.s + 3) * 24, yd, ev, dec_proof_out));
     RET(decompose_evals(c, lcccs, r, wit, "L", nullptr, S, dec_proof_out));
     c->host_tr_ms += absorb_decomposition(P, t->t, lcccs, dec_proof_out, S);
@@ -935,7 +980,8 @@ int lf_folding_prove(lf_ctx *c, lf_transcript *t, const uint64_t *lcccs_s, const
         std::vector<u64> heads((size_t)K * hl * 24);
         for (u32 k = 0; k < K; k++)
             memcpy(&heads[(size_t)k * hl * 24], base + ((size_t)k * ll + P.s + 3 + P.kappa + P.t) * 24, (size_t)hl * 24 * 8);
-        RET(build_z(c, w->planes, K, 1, heads.data(), z));
+        if (P.b != 2) RET(sb_cut_parts(c, w, sd ? "sb_D_R" : "sb_D_L", &S[sd].D));
+        RET(build_z(c, w->planes, K, 1, heads.data(), z, 0, (size_t)-1, S[sd].D));
         RET(build_eq_dev(c, r.data(), P.s, eq_r));
         S[sd].planes = w->planes; S[sd].z = z; S[sd].eq_r = eq_r;
         S[sd].lcccs.assign(base, base + (size_t)K * ll * 24);

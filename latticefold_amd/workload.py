@@ -29,6 +29,17 @@ CONFIGS = {
     "C2": (16, 1 << 14, 4, 1 << 16, 2, 16, 25),  # BASELINE configs[1]
     "T18": (18, 1 << 16, 4, 1 << 16, 2, 16, 26),
     "C4": (20, 1 << 18, 4, 1 << 16, 2, 16, 26),  # BASELINE configs[3] / metric config
+    # decomposition bases b = 4, 8, 16 (DecompositionParams::B_SMALL): K = log_b B parts at sumcheck degree 2b; C4b4 / C4b16 are for timing only
+    "T8b4": (8, 64, 4, 1 << 16, 4, 8, 4),
+    "T8b8": (8, 48, 5, 1 << 15, 8, 5, 4),       # (L 5: B^L must reach p for w_ccs to recompose, as in G5; 48 x 5 = 240 <= 2^8 rows)
+    "T8b16": (8, 64, 4, 1 << 16, 16, 4, 4),
+    "R61b4": (8, 61, 4, 1 << 16, 4, 8, 4),      # ragged N = 244: the last 8-column tile of the part planes is half empty
+    "R61b16": (8, 61, 4, 1 << 16, 16, 4, 4),
+    "C1b4": (10, 256, 4, 1 << 16, 4, 8, 21),
+    "C2b4": (16, 1 << 14, 4, 1 << 16, 4, 8, 25),
+    "C2b16": (16, 1 << 14, 4, 1 << 16, 16, 4, 25),
+    "C4b4": (20, 1 << 18, 4, 1 << 16, 4, 8, 26),
+    "C4b16": (20, 1 << 18, 4, 1 << 16, 16, 4, 26),
     # the reference's own wider Goldilocks rows at small wit_len (benches/config.toml:150-165): kappa 42-44 / B 2^22 / L 3 / K 22,
     # kappa 99 (row-chunked commits), and the widest digits the int32 witness planes hold (B 2^31, K 31)
     "E22": (10, 256, 3, 1 << 22, 2, 22, 43),
