@@ -960,10 +960,10 @@ size_t lf_proof_len(const lf_params *p) { return lin_proof_len(p) + 2 * dec_proo
 
 int lf_ccs_load(lf_ctx *c, const lf_params *p, const uint32_t *const *rowptr, const uint32_t *const *col, const uint64_t *const *val,
                 const uint32_t *S_off, const uint32_t *S_idx, const uint64_t *cc) {
-    if (LF_XB(c) && p && rowptr && col && val && S_off && S_idx && cc && p->t >= 1 && p->t <= 4 && p->s <= 30 && p->q <= 8) {
+    if (LF_XB(c) && p && rowptr && col && val && S_off && S_idx && cc && p->t >= 1 && p->t <= 8 && p->s <= 30 && p->q <= 8) {
         XB x(c);
         const size_t m = (size_t)1 << p->s;
-        const uint64_t *v2[4];
+        const uint64_t *v2[8];
         for (u32 j = 0; j < p->t; j++) {
             if (!rowptr[j] || !val[j]) return LF_ERR_INVALID;
             v2[j] = x.ring_in(val[j], rowptr[j][m]);
@@ -972,9 +972,11 @@ int lf_ccs_load(lf_ctx *c, const lf_params *p, const uint32_t *const *rowptr, co
     }
     if (!c || !p || !rowptr || !col || !val || !S_off || !S_idx || !cc) return LF_ERR_INVALID;
     if (c->bb) return c->bb->ccs_load(p, rowptr, col, val, S_off, S_idx, cc);
-    if (p->s < 3 || p->s > 30 || p->t == 0 || p->t > 4 || p->q == 0 || p->q > 8 || p->K == 0 || p->K > 32 || p->L == 0 || p->L > 8 ||
-        p->d + 1 > 4 || p->wit_len == 0)
+    if (p->s < 3 || p->s > 30 || p->t == 0 || p->t > 8 || p->q == 0 || p->q > 8 || p->K == 0 || p->K > 32 || p->L == 0 || p->L > 8 ||
+        p->d > 7 || p->wit_len == 0)
         return LF_ERR_UNSUPPORTED;
+    // the wide envelope (t > 4 or d > 3: k_lin_round_wide and the chunked launches below it) runs on one unsharded GPU
+    if ((p->t > 4 || p->d > 3) && (c->sh_world > 1 || c->comm[0].model)) return LF_ERR_UNSUPPORTED;
     // b = 2: the bit-plane kernels of the reference Goldilocks rows; b = 4, 8, 16: the small-base path (lf_sb.h), one unsharded GPU
     if (p->b != 2 && !sb_base_ok(p->b)) return LF_ERR_UNSUPPORTED;
     if (p->b != 2 && (c->sh_world > 1 || c->comm[0].model || p->K > 11)) return LF_ERR_UNSUPPORTED;   // (K - 1 <= 10 planes of one commit launch)

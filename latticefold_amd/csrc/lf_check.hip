@@ -11,15 +11,15 @@
 
 namespace lf {
 
-template <bool NU>
+template <bool NU, int TT>   // TT = 4: the bench envelope (t <= 4); 8: the wide envelope
 __global__ void __launch_bounds__(256) k_ccs_residual(DevCrt t, LinCombDesc desc, const u64 *mz, size_t ld, size_t m, u32 *first_bad) {
     const u32 slot = blockIdx.y;
     const size_t row = (size_t)blockIdx.x * 256 + threadIdx.x;
     // the unit coefficients of the tables' multisets, selected once (see k_lin_round: a dynamically indexed field of the by-value descriptor would be
     // copied to scratch memory)
-    int cu_j[4];
+    int cu_j[TT];
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
+    for (int j = 0; j < TT; j++) {
         const u32 i = desc.ms[j];
         int r = desc.c_unit[0];
 #pragma unroll
@@ -31,7 +31,7 @@ __global__ void __launch_bounds__(256) k_ccs_residual(DevCrt t, LinCombDesc desc
         Fq3 res = fq3_zero(), term = fq3_zero();
         int sgn = 0;
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
+        for (int j = 0; j < TT; j++) {
             if ((u32)j < desc.t) {
                 const Fq3 v = ld3(mz + (size_t)j * 24 * ld, ld, slot, row);
                 if (desc.first[j]) {   // (wave-uniform)
@@ -39,6 +39,10 @@ __global__ void __launch_bounds__(256) k_ccs_residual(DevCrt t, LinCombDesc desc
                     if (cu_j[j]) { term = v; sgn = cu_j[j]; }
                     else {
                         const u32 i = desc.ms[j];
+                        if (TT > 4) {   // (from the kernel-argument segment: eight tables leave no room for a scratch copy of the descriptor)
+                            const u64 *cp = lin_desc_coef(desc, i, slot);
+                            term = M3<NU>(fq3_make(cp[0], cp[1], cp[2]), v, t.nu);
+                        } else
                         term = M3<NU>(fq3_make(desc.c[i][3 * slot], desc.c[i][3 * slot + 1], desc.c[i][3 * slot + 2]), v, t.nu);
                         sgn = 1;
                     }
@@ -54,8 +58,13 @@ __global__ void __launch_bounds__(256) k_ccs_residual(DevCrt t, LinCombDesc desc
 void launch_ccs_residual(const DevCrt &t, const LinCombDesc &desc, const u64 *mz, size_t ld, size_t m, u32 *first_bad, hipStream_t s) {
     if (!m) return;
     const dim3 grid(cdiv(m, 256), 8);
-    if (t.nu2p40) hipLaunchKernelGGL((k_ccs_residual<true>), grid, dim3(256), 0, s, t, desc, mz, ld, m, first_bad);
-    else hipLaunchKernelGGL((k_ccs_residual<false>), grid, dim3(256), 0, s, t, desc, mz, ld, m, first_bad);
+    if (desc.t > 4) {
+        if (t.nu2p40) hipLaunchKernelGGL((k_ccs_residual<true, 8>), grid, dim3(256), 0, s, t, desc, mz, ld, m, first_bad);
+        else hipLaunchKernelGGL((k_ccs_residual<false, 8>), grid, dim3(256), 0, s, t, desc, mz, ld, m, first_bad);
+        return;
+    }
+    if (t.nu2p40) hipLaunchKernelGGL((k_ccs_residual<true, 4>), grid, dim3(256), 0, s, t, desc, mz, ld, m, first_bad);
+    else hipLaunchKernelGGL((k_ccs_residual<false, 4>), grid, dim3(256), 0, s, t, desc, mz, ld, m, first_bad);
 }
 
 // max |v| over the int32 planes: a grid-stride pass, a wave maximum by shuffles, one atomic max per wave with a non-zero maximum

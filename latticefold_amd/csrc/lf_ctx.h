@@ -278,7 +278,9 @@ struct lf_ctx {
     u64 *h_round[LF_NLANES] = {nullptr, nullptr};   // pinned + device-mapped: sumcheck round kernels write their message straight to the host
     u64 *round_out() {
         u64 *&p = h_round[t_lane];
-        if (!p && hipHostMalloc((void **)&p, 5 * 24 * 8 * 2, hipHostMallocMapped) != hipSuccess) p = nullptr;
+        // two messages of up to 9 evaluations x 24 words: the wide linearization round writes d + 2 <= 9 (k_reduce_rows of launch_lin_round_wide), the fold
+        // rounds write their G part at word 120 behind the norm part
+        if (!p && hipHostMalloc((void **)&p, 2 * 9 * 24 * sizeof(u64), hipHostMallocMapped) != hipSuccess) p = nullptr;
         return p;
     }
     // persistent sumcheck tail (k_fold_tail): host-mapped mailbox + device scratch, created on first use

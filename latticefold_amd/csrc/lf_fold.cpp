@@ -709,7 +709,7 @@ int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out,
     RET(c->tbuf("fold_eq0", 3 * m, &eq0));
     RET(c->tbuf("dec_q", (size_t)P.t * 24 * n, &q));
     RET(c->tbuf("red_partial", 256 * 4096, &red));
-    RET(c->tbuf("dec_small", 32 * 72 + 32 * 4 * 24 + 64, &sm));
+    RET(c->tbuf("dec_small", 32 * 72 + 32 * 8 * 24 + 64, &sm));
     RET(c->tbuf("dot_partial", dot_partial_words(K, P.t), &dpart));
     RET(build_eq_dev(c, pt.data(), P.s, eq0));
     // the helper lane's stream is idle here: every second q_j = M_j^T eq(r_o) is gathered there (the gathers are latency-bound: 3 x 63 us in a row at C4)
@@ -852,7 +852,7 @@ int lf_sumcheck_lin_round(lf_ctx *c, const uint64_t *r_prev, uint64_t *evals_out
     RET(c->tbuf("sc_eq0", 3 * m, &eq[0]));
     RET(c->tbuf("sc_eq1", 3 * (m / 2 ? m / 2 : 1), &eq[1]));
     RET(c->tbuf("round_partial", round_partial_words(), &partial));
-    RET(c->tbuf("round_out", 5 * 24, &od));
+    RET(c->tbuf("round_out", 9 * 24, &od));      // d + 2 <= 9 evaluations
     if (r_prev) {
         Fq3Const r; r.c[0] = r_prev[0]; r.c[1] = r_prev[1]; r.c[2] = r_prev[2];
         int src = c->sc_cur, dst = src ^ 1;

@@ -75,7 +75,7 @@ void launch_build_eq2(const DevCrt &t, const Fq3Const *r_dev, u32 nv, u64 *scrat
 // sparse mat-vec (a7): CSR rows m; z ring table [24][n]; out ring table [24][m]; accumulate != 0 adds into out
 void launch_spmv(const DevCrt &t, const u32 *rowptr, const u32 *col, const u64 *val /*[nnz][24] AoS*/, const u64 *z,
                  size_t ldz, u64 *out, size_t m, int accumulate, hipStream_t s, size_t r0 = 0, size_t rcnt = (size_t)-1 /* all rows */);
-// out = sum_{j<nm} M_j z_j (nm <= 4), z_j = z + j*z_stride: one launch, one write of out
+// out = sum_{j<nm} M_j z_j, z_j = z + j*z_stride: one launch, one write of out for nm <= 4 (matrices 4 .. 7 of the wide envelope are added one by one)
 void launch_spmv_sum(const DevCrt &t, u32 nm, const u32 *const *rowptr, const u32 *const *col, const u64 *const *val, const u64 *z,
                      size_t z_stride, size_t ldz, u64 *out, size_t m, hipStream_t s, size_t r0 = 0, size_t rcnt = (size_t)-1 /* all rows */);
 // q[col] = sum_{rows} eq[row] * val  (CSC: colptr over n columns, rowidx, val AoS)
@@ -129,11 +129,11 @@ struct LinCombDesc {  // CCS multiset structure for the linearization comb (nifs
     u32 S_idx[16];
     u64 c[8][24];  // coefficients c_i (ring elements, AoS)
     int c_unit[8]; // +1 / -1 when c_i is the ring element +-1 (multiplication skipped), else 0
-    u32 first[4];  // table j starts a new multiset
-    u32 ms[4];     // multiset of table j
+    u32 first[8];  // table j starts a new multiset
+    u32 ms[8];     // multiset of table j
 };
 // round message of the linearization sumcheck: tables Mz [t][24][ld], eq [3][ld]; n = current length
-// out: (deg+1) ring elements AoS, deg = d+1 <= 4
+// out: (deg+1) ring elements AoS, deg = d+1 <= 4 (k_lin_round); a CCS with t > 4 or d > 3 goes to k_lin_round_wide (lf_lin_wide.hip: t <= 8, deg <= 8)
 // max_blocks (0 = default 256 per slot) bounds the grid: inside a fold step the linearization shares the GPU with the commit chain
 // of the other lane, which is the critical path, and yields to it by running on fewer workgroups
 void launch_lin_round(const DevCrt &t, const LinCombDesc &desc, const u64 *mz, size_t ld, const u64 *eq, size_t ldeq, size_t n,
@@ -141,6 +141,10 @@ void launch_lin_round(const DevCrt &t, const LinCombDesc &desc, const u64 *mz, s
 void launch_lin_round_fused(const DevCrt &t, const LinCombDesc &desc, const u64 *mz_prev, size_t ld_prev, const u64 *eq_prev, size_t ldeq_prev, Fq3Const r, u64 *mz_out,
                             size_t ld_out, u64 *eq_out, size_t ldeq_out, size_t n, u32 deg, u64 *partial, u64 *out, hipStream_t s, u32 max_blocks = 0,
                             u32 split_xmask = 0 /* eq_prev = E_{i-1}, eq_out = E_i (per pair) */);
+// the wide envelope (desc.t > 4 or deg > 4; desc.t <= 8, deg <= 8): called by the two launchers above, same arguments (fx = nullptr: no fused fix_variables)
+struct LinFix;
+void launch_lin_round_wide(const DevCrt &t, const LinCombDesc &desc, const u64 *mz, size_t ld, const u64 *eq, size_t ldeq, size_t n, u32 deg, u64 *partial, u64 *out,
+                           hipStream_t s, u32 max_blocks, u32 split_xmask, const LinFix *fx);
 void launch_eq_pairsum(const u64 *in, size_t ld_in, size_t n_out, u64 *out, size_t ld_out, hipStream_t s);
 void launch_eq_expand(const DevCrt &t, const u64 *E, size_t lde, size_t pairs, Fq3Const w0, Fq3Const w1, u64 *out, size_t ldo, hipStream_t s);
 

@@ -612,7 +612,10 @@ void launch_spmv_sum(const DevCrt &t, u32 nm, const u32 *const *rowptr, const u3
     SpmvSet ms = {};
     ms.nm = nm;
     for (u32 j = 0; j < nm && j < 4; j++) { ms.rowptr[j] = rowptr[j]; ms.col[j] = col[j]; ms.val[j] = val[j]; ms.z[j] = z + (size_t)j * z_stride; }
+    if (nm > 4) ms.nm = 4;
     LF_LAUNCH(k_spmv_sum, t.nu2p40, dim3(cdiv(rcnt, 256), 8), dim3(256), s, t, ms, ldz, out, m, r0, rcnt);
+    // wide CCS envelope (five to eight matrices): the rest is added matrix by matrix (exact field sums: the same words in any order)
+    for (u32 j = 4; j < nm; j++) launch_spmv(t, rowptr[j], col[j], val[j], z + (size_t)j * z_stride, ldz, out, m, 1, s, r0, rcnt);
 }
 // General matrices (several entries per row at arbitrary columns, ring-valued entries: arith/utils.rs:52-65 as a real CSR SpMV).  k_spmv / k_spmv_sum above are the
 // shape of the reference's bench matrices (one entry per row, neighbouring rows at neighbouring columns): thread = (row, one slot per block), z plane-major.  With k
@@ -655,14 +658,16 @@ void launch_spmv_rows(const DevCrt &t, u32 nm, const u32 *const *rowptr, const u
                       u64 *zaos, u64 *out, size_t m, int accumulate, hipStream_t s, size_t r0, size_t rcnt) {
     if (rcnt == (size_t)-1) { r0 = 0; rcnt = m; }
     if (!rcnt || !nm) return;
-    SpmvRowsSet ms = {};
-    ms.nm = nm;
-    for (u32 j = 0; j < nm && j < 4; j++) {
-        u64 *za = zaos + (size_t)j * n * 24;
-        if (z) launch_soa_to_aos(z + (size_t)j * z_stride, za, n, s);        // (z null: zaos holds the element-major copies already)
-        ms.rowptr[j] = rowptr[j]; ms.col[j] = col[j]; ms.val[j] = val[j]; ms.zaos[j] = za;
+    for (u32 j0 = 0; j0 < nm; j0 += 4) {   // (more than four matrices -- the wide CCS envelope -- in chunks that add into out)
+        SpmvRowsSet ms = {};
+        ms.nm = nm - j0 < 4 ? nm - j0 : 4;
+        for (u32 j = 0; j < ms.nm; j++) {
+            u64 *za = zaos + (size_t)(j0 + j) * n * 24;
+            if (z) launch_soa_to_aos(z + (size_t)(j0 + j) * z_stride, za, n, s);        // (z null: zaos holds the element-major copies already)
+            ms.rowptr[j] = rowptr[j0 + j]; ms.col[j] = col[j0 + j]; ms.val[j] = val[j0 + j]; ms.zaos[j] = za;
+        }
+        LF_LAUNCH(k_spmv_rows, t.nu2p40, dim3(cdiv(rcnt, 32)), dim3(256), s, t, ms, out, m, j0 ? 1 : accumulate, r0, rcnt);
     }
-    LF_LAUNCH(k_spmv_rows, t.nu2p40, dim3(cdiv(rcnt, 32)), dim3(256), s, t, ms, out, m, accumulate, r0, rcnt);
 }
 // block = 32 columns x 8 slots, the slots of a column side by side: a wave reads the 24 coefficient words of eight non-zeros as one contiguous 1.5 KB run (with
 // thread = column and one slot per block a load instruction touched 64 cache lines for 24 bytes each, eight blocks re-reading them: 63 us for 100 MB at 2^18
@@ -847,9 +852,10 @@ void launch_coef_eval(const DevCrt &t, const int32_t *planes, size_t n, const u6
     hipLaunchKernelGGL(k_reduce_rows, dim3(K * 72), dim3(256), 0, s, partial, gb, K * 72, out);
 }
 
-template <bool NU, int TT>
+template <bool NU, int TT, int TS = TT, int J0 = 0>
 __global__ void __launch_bounds__(256) k_lincomb_z(DevCrt t, const u64 *z, size_t ldz, u32 K, const Fq3Const *coef, size_t n, u64 *out, u32 per_slot) {
-    // TT output tables (compile time: only the accumulators that are used occupy registers)
+    // TT output tables (compile time: only the accumulators that are used occupy registers); a set of TS > 4 tables goes in two launches, this one writing
+    // tables J0 .. J0 + TT - 1 (the defaults are the single launch of TS = TT <= 4 tables)
     size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     u32 slot = blockIdx.y;
     if (i >= n) return;
@@ -858,7 +864,7 @@ __global__ void __launch_bounds__(256) k_lincomb_z(DevCrt t, const u64 *z, size_
 #pragma unroll
     for (int j = 0; j < TT; j++) { lh5_zero(acc[j]); accg[j] = fq3_zero(); }
     auto cf = [&](u32 k, int j) {
-        Fq3Const cc = coef[per_slot ? (size_t)(k * TT + j) * 8 + slot : (size_t)(k * TT + j)];   // per_slot: ring-element coefficients
+        Fq3Const cc = coef[per_slot ? (size_t)(k * TS + J0 + j) * 8 + slot : (size_t)(k * TS + J0 + j)];   // per_slot: ring-element coefficients
         return fq3_make(cc.c[0], cc.c[1], cc.c[2]);
     };
     u32 k = 0;
@@ -890,7 +896,7 @@ __global__ void __launch_bounds__(256) k_lincomb_z(DevCrt t, const u64 *z, size_
         }
     }
 #pragma unroll
-    for (int j = 0; j < TT; j++) st3(out + (size_t)j * 24 * ldz, ldz, slot, i, NU ? lh5_finish(acc[j]) : accg[j]);
+    for (int j = 0; j < TT; j++) st3(out + (size_t)(J0 + j) * 24 * ldz, ldz, slot, i, NU ? lh5_finish(acc[j]) : accg[j]);
 }
 void launch_lincomb_z(const DevCrt &t, const u64 *z, size_t ldz, u32 K, const Fq3Const *coef_dev, u32 tt, size_t n, u64 *out, hipStream_t s, u32 per_slot) {
     if (!n) return;
@@ -903,7 +909,19 @@ void launch_lincomb_z(const DevCrt &t, const u64 *z, size_t ldz, u32 K, const Fq
         case 1: LF_LZ(1); break;
         case 2: LF_LZ(2); break;
         case 3: LF_LZ(3); break;
-        default: LF_LZ(4); break;   // callers keep tt <= 4
+        case 4: LF_LZ(4); break;
+        // five to eight tables (wide CCS envelope): tables 0..3, then the rest, against the same coefficient array
+#define LF_LZ2(N, TS, J0)                                                                                                                     \
+    do {                                                                                                                                      \
+        if (t.nu2p40) hipLaunchKernelGGL((k_lincomb_z<true, N, TS, J0>), dim3(cdiv(n, 256), 8), dim3(256), 0, s, t, z, ldz, K, coef_dev, n, out, per_slot);    \
+        else hipLaunchKernelGGL((k_lincomb_z<false, N, TS, J0>), dim3(cdiv(n, 256), 8), dim3(256), 0, s, t, z, ldz, K, coef_dev, n, out, per_slot);            \
+    } while (0)
+        case 5: LF_LZ2(4, 5, 0); LF_LZ2(1, 5, 4); break;
+        case 6: LF_LZ2(4, 6, 0); LF_LZ2(2, 6, 4); break;
+        case 7: LF_LZ2(4, 7, 0); LF_LZ2(3, 7, 4); break;
+        case 8: LF_LZ2(4, 8, 0); LF_LZ2(4, 8, 4); break;
+#undef LF_LZ2
+        default: break;             // callers keep tt <= 8 (lf_ccs_load)
     }
 #undef LF_LZ
 }

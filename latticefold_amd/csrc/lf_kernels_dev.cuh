@@ -1,6 +1,8 @@
 // lf_kernels_dev.cuh -- device-side helpers shared by the kernel translation units of the Goldilocks backend (lf_kernels.hip, lf_rounds.hip): the F_{p^3}
 // product wrappers, the nu-specialised launch macro, grid helpers, wave / block reductions, plane-major element access, base-2 digits.
 #pragma once
+#include <stddef.h>
+
 #include "lf_kernels.h"
 
 namespace lf {
@@ -63,6 +65,16 @@ __device__ __forceinline__ void st3(u64 *tab, size_t ld, u32 slot, size_t i, Fq3
 }
 
 constexpr u32 RED_BLOCKS = 256;   // partial rows of every two-stage reduction
+
+// fused fix_variables of the linearization round kernels (k_lin_round, k_lin_round_wide): the challenge and where the fixed tables go
+struct LinFix { Fq3Const r; u64 *mzo; size_t ldo; u64 *eqo; size_t ldeo; };
+// c_i[3 slot ..] of the by-value descriptor, read from the kernel-argument segment itself (constant memory; the descriptor is the second argument of every
+// kernel that takes it, behind DevCrt)
+__device__ __forceinline__ const u64 *lin_desc_coef(const LinCombDesc &, u32 i, u32 slot) {
+    constexpr size_t off = (sizeof(DevCrt) + alignof(LinCombDesc) - 1) / alignof(LinCombDesc) * alignof(LinCombDesc);
+    const char *ka = (const char *)__builtin_amdgcn_kernarg_segment_ptr();
+    return (const u64 *)(ka + off + offsetof(LinCombDesc, c)) + (size_t)i * 24 + 3 * slot;
+}
 
 // out[i] = sum_b partial[b*nv + i]; one block per i
 static __global__ void __launch_bounds__(256) k_reduce_rows(const u64 *partial, u32 nblocks, u32 nv, u64 *out) {

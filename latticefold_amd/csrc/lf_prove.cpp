@@ -54,7 +54,8 @@ static int run_lin_sumcheck(lf_ctx *c, Transcript &tr, const u64 *mz, const u64 
     if (Gw > 1) RET(c->tbuf("lin_round_out", 5 * 24 + 8, &od_dev));
     // split form: while `split` is set, cure is the per-pair table E_i of the round i that ran last (in fe[(i - 1) & 1]) and c_lvl = c_i = prod_{k<i} eq(beta_k, r_k)
     const u32 dT = P.d;                                          // degree of T_i; the message has degree dT + 1 = deg
-    bool split = beta && Gw == 1 && !c->tn.lin_no_split && P.s >= 2 && m >= c->tn.lin_split_min && m >= 16 && dT >= 1 && deg <= 4;
+    const bool wide = P.t > 4 || P.d > 3;                        // k_lin_round_wide (lf_lin_wide.hip): per-round launches only, no persistent tail
+    bool split = beta && Gw == 1 && !c->tn.lin_no_split && P.s >= 2 && m >= c->tn.lin_split_min && m >= 16 && dT >= 1 && deg <= 8;
     Fq3 c_lvl = fq3_one();
     auto f3zero = [](const Fq3 &x) { return !(x.c[0] | x.c[1] | x.c[2]); };
     auto eq1 = [&](const Fq3 &b, const Fq3 &r) {   // eq(beta, r) = (1 - beta)(1 - r) + beta r
@@ -65,7 +66,7 @@ static int run_lin_sumcheck(lf_ctx *c, Transcript &tr, const u64 *mz, const u64 
     for (u32 round = 1; round <= P.s; round++) {
         if (split && round >= 2) {
             // stay in the split form?  Not into the persistent tail, not below the size where it pays, not when c_i or beta_i cannot be divided by
-            const bool tail_next = !c->tn.no_tail && n <= c->tn.tail_n && n >= 4 && P.s - round + 1 <= TAIL_MAX_ROUNDS;
+            const bool tail_next = !wide && !c->tn.no_tail && n <= c->tn.tail_n && n >= 4 && P.s - round + 1 <= TAIL_MAX_ROUNDS;
             const Fq3 c_next = c->ring.mul3(c_lvl, eq1(beta[round - 2], point[round - 2]));
             if (tail_next || n < 8 || n / 2 < c->tn.lin_split_min || f3zero(c_next) || f3zero(beta[round - 1])) {
                 // back to the ordinary table of the previous round's n entries: eq(beta, (r_1..r_{i-1}, b, p)) = c_i eq(beta_i, b) E_i[p] at entry 2p + b
@@ -78,7 +79,7 @@ static int run_lin_sumcheck(lf_ctx *c, Transcript &tr, const u64 *mz, const u64 
             } else c_lvl = c_next;
         }
         // persistent tail (k_lin_tail): all remaining rounds in one launch once the tables are small, as in the folding sumcheck
-        if (!sharded && !c->tn.no_tail && round >= 2 && n <= c->tn.tail_n && n >= 4 && P.s - round + 1 <= TAIL_MAX_ROUNDS) {
+        if (!wide && !sharded && !c->tn.no_tail && round >= 2 && n <= c->tn.tail_n && n >= 4 && P.s - round + 1 <= TAIL_MAX_ROUNDS) {
             int trc = lin_tail_rounds(c, tr, cur, cure, n, fx[flip], partial, round, point, msgs, deg, after_round);
             if (trc == LF_OK) { cur = fx[flip]; n = 2; break; }
             if (trc != LF_ERR_UNSUPPORTED) return trc;
@@ -130,7 +131,7 @@ static int run_lin_sumcheck(lf_ctx *c, Transcript &tr, const u64 *mz, const u64 
             HostTimer ht2(c);
             c->lin_split_rounds++;
             const Fq3 bi = beta[round - 1], obi = fq3_sub(fq3_one(), bi);
-            Fq3 wS[5];   // Lagrange weights of the previous message at r_{i-1} (nodes 0..deg)
+            Fq3 wS[9];   // Lagrange weights of the previous message at r_{i-1} (nodes 0..deg <= 8)
             Fq3 cinv = fq3_one(), binv = fq3_one();
             if (round >= 2) {
                 const Fq3 x = point[round - 2];
@@ -149,9 +150,10 @@ static int run_lin_sumcheck(lf_ctx *c, Transcript &tr, const u64 *mz, const u64 
                 binv = c->ring.inv3(bi);
             }
             const u64 *prev_ev = round >= 2 ? msgs + (size_t)(round - 2) * (deg + 1) * 24 : nullptr;
-            static const int binom[5][6] = {{1}, {1, 1}, {1, 2, 1}, {1, 3, 3, 1}, {1, 4, 6, 4, 1}};
+            static const int binom[9][9] = {{1}, {1, 1}, {1, 2, 1}, {1, 3, 3, 1}, {1, 4, 6, 4, 1}, {1, 5, 10, 10, 5, 1}, {1, 6, 15, 20, 15, 6, 1}, {1, 7, 21, 35, 35, 21, 7, 1},
+                                            {1, 8, 28, 56, 70, 56, 28, 8, 1}};
             for (u32 slot = 0; slot < 8; slot++) {
-                Fq3 T[5];
+                Fq3 T[9];
                 for (u32 X = 0; X <= dT; X++) T[X] = fq3_make(od[X * 24 + 3 * slot], od[X * 24 + 3 * slot + 1], od[X * 24 + 3 * slot + 2]);
                 if (round >= 2) {
                     Fq3 S = fq3_zero();
@@ -511,7 +513,7 @@ int coef_eval_dev(lf_ctx *c, const int32_t *planes, size_t n, const u64 *eq, siz
 int dot_batch_dev(lf_ctx *c, const u64 *X, size_t ldx, u32 na, const u64 *Y, size_t ldy, u32 nb, size_t n, u64 *dpart, u64 *od, hipStream_t st,
                          const char *tag, unsigned char *yb_pre) {
     if (!st) st = c->stream();
-    if (!c->tn.dot_valu && n >= c->tn.dot_min && nb <= 4) {
+    if (!c->tn.dot_valu && n >= c->tn.dot_min && nb <= 8) {
         unsigned char *yb;
         int32_t *part;
         long long *tot;
@@ -529,6 +531,16 @@ int dot_batch_dev(lf_ctx *c, const u64 *X, size_t ldx, u32 na, const u64 *Y, siz
                 ok = launch_dot_batch_i8(c->dcrt, X + (size_t)a0 * 24 * ldx, ldx, na - a0 < 16 ? na - a0 : 16, Y + (size_t)b0 * 24 * ldy, ldy, nb - b0 < gsz ? nb - b0 : gsz, n, yb, part, tot,
                                          od + (size_t)a0 * nb * 24, st, yb_pre != nullptr && nb <= 3, nb, b0) == 0;
         if (ok) return LF_OK;
+    }
+    if (nb > 4) {   // wide CCS envelope on the 64-bit VALU kernel (four tables Y per launch): groups of four into a scratch, copied to their place in [na][nb][24]
+        u64 *tmp;
+        RET(c->tbuf(std::string("dot_wide_tmp") + tag, (size_t)na * 4 * 24, &tmp));
+        for (u32 b0 = 0; b0 < nb; b0 += 4) {
+            const u32 cb = nb - b0 < 4 ? nb - b0 : 4;
+            launch_dot_batch(c->dcrt, X, ldx, na, Y + (size_t)b0 * 24 * ldy, ldy, cb, n, dpart, tmp, st);
+            HIPCHK(hipMemcpy2DAsync(od + (size_t)b0 * 24, (size_t)nb * 24 * 8, tmp, (size_t)cb * 24 * 8, (size_t)cb * 24 * 8, na, hipMemcpyDeviceToDevice, st));
+        }
+        return LF_OK;
     }
     launch_dot_batch(c->dcrt, X, ldx, na, Y, ldy, nb, n, dpart, od, st);
     return LF_OK;
@@ -578,8 +590,8 @@ static int decompose_evals(lf_ctx *c, const u64 *lcccs, const std::vector<Fq3> &
     u64 *u_s = proof, *v_s = u_s + (size_t)K * P.t * 24;
     u64 *partial, *od, *q;
     RET(c->tbuf("red_partial", 256 * 4096, &partial));
-    if (K > 32 || P.t > 4) return LF_ERR_UNSUPPORTED;       // the fixed layout of dec_small below (v_s: 32 x 72 words, u_s: 32 x 4 elements); lf_ccs_load enforces the same envelope
-    RET(c->tbuf("dec_small", 32 * 72 + 32 * 4 * 24 + 64, &od));
+    if (K > 32 || P.t > 8) return LF_ERR_UNSUPPORTED;       // the fixed layout of dec_small below (v_s: 32 x 72 words, u_s: 32 x 8 elements); lf_ccs_load enforces the same envelope
+    RET(c->tbuf("dec_small", 32 * 72 + 32 * 8 * 24 + 64, &od));
     RET(c->tbuf("dec_q", (size_t)P.t * 24 * n, &q));
     u64 *od_v = od, *od_u = od + 32 * 72;
     if (!eq_r) {
@@ -606,7 +618,7 @@ static int decompose_evals(lf_ctx *c, const u64 *lcccs, const std::vector<Fq3> &
             RET(c->tbuf("sb_eval_partial", sb_eval_partial_words(K), &sbp));
             if (launch_sb_eval(S.D, sb_ld(N), N, eq_r, m, K, sbp, od_v, c->stream()) != 0) return LF_ERR_HIP;
         } else {
-            if (c->sh_world > 1) HIPCHK(hipMemsetAsync(od, 0, (32 * 72 + 32 * 4 * 24) * 8, c->stream()));   // (one exchange carries v_s and u_s: the gaps of the buffer must be canonical)
+            if (c->sh_world > 1) HIPCHK(hipMemsetAsync(od, 0, (32 * 72 + 32 * 8 * 24) * 8, c->stream()));   // (one exchange carries v_s and u_s: the gaps of the buffer must be canonical)
             RET(coef_eval_dev(c, wit->planes + i0, cnt, eq_r + i0, m, K, 1, partial, od_v, N, c->sh_world == 1 ? wit : nullptr));
         }
     }

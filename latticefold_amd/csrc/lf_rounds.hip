@@ -25,18 +25,13 @@ __device__ __forceinline__ void add_poly_evals(Fq3 (&acc)[NP], const Fq3 *co, in
 // linearization sumcheck round (sumcheck/prover.rs:56-162 with comb = linearization/utils.rs:90-107)
 // FUSED: fix_variables of the previous round's tables (mz / eq hold 2n entries per row, ld / ldeq their strides) with rfix happens here: pair p is built from
 // the entries 4p..4p+3 and stored to mzo / eqo (n entries per row) for the next round -- no separate k_fix pass over the tables
-struct LinFix { Fq3Const r; u64 *mzo; size_t ldo; u64 *eqo; size_t ldeo; };
+// (struct LinFix: lf_kernels_dev.cuh, shared with the wide-envelope kernel of lf_lin_wide.hip)
 // SPLIT (xmask != 0 at the launch): eq(beta, (r_1..r_{i-1}, X, x)) = c_i * eq(beta_i, X) * E_i[x] with E_i = eq((beta_{i+1}..beta_s), .), one entry per
 // PAIR and no X in it -- the kernel sums E_i[p] * h(X, p) for the X of `xmask` only (the host multiplies by c_i eq(beta_i, X), derives the value at X = 1
 // from the previous round's message and extrapolates the top one: exact field arithmetic, the same message words).  `eq` is then E_i (one entry per pair;
 // FUSED: E_{i-1}, whose pair sums are E_i, stored through fx.eqo).  Half the products per pair of the plain form.
 // c_i[3 slot ..] of the by-value descriptor, read from the kernel-argument segment itself (constant memory; the descriptor is the second argument of every kernel
-// that takes it, behind DevCrt): indexing the by-value copy with i and slot would put it in scratch
-__device__ __forceinline__ const u64 *lin_desc_coef(const LinCombDesc &, u32 i, u32 slot) {
-    constexpr size_t off = (sizeof(DevCrt) + alignof(LinCombDesc) - 1) / alignof(LinCombDesc) * alignof(LinCombDesc);
-    const char *ka = (const char *)__builtin_amdgcn_kernarg_segment_ptr();
-    return (const u64 *)(ka + off + offsetof(LinCombDesc, c)) + (size_t)i * 24 + 3 * slot;
-}
+// that takes it, behind DevCrt): indexing the by-value copy with i and slot would put it in scratch -- lin_desc_coef (lf_kernels_dev.cuh)
 template <bool NU, bool FUSED, bool SPLIT>
 __global__ void __launch_bounds__(256) k_lin_round(DevCrt t, LinCombDesc desc, const u64 *mz, size_t ld, const u64 *eq, size_t ldeq, size_t n,
                                                    u32 deg, u64 *partial, LinFix fx, u32 xmask) {
@@ -180,6 +175,7 @@ void launch_eq_expand(const DevCrt &t, const u64 *E, size_t lde, size_t pairs, F
 }
 void launch_lin_round(const DevCrt &t, const LinCombDesc &desc, const u64 *mz, size_t ld, const u64 *eq, size_t ldeq, size_t n, u32 deg,
                       u64 *partial, u64 *out, hipStream_t s, u32 max_blocks, u32 xmask) {
+    if (desc.t > 4 || deg > 4) return launch_lin_round_wide(t, desc, mz, ld, eq, ldeq, n, deg, partial, out, s, max_blocks, xmask, nullptr);
     u32 gb = (u32)((n / 2 + 255) / 256);
     const u32 cap = max_blocks && max_blocks < RED_BLOCKS ? max_blocks : RED_BLOCKS;
     if (gb > cap) gb = cap;
@@ -197,6 +193,10 @@ void launch_lin_round(const DevCrt &t, const LinCombDesc &desc, const u64 *mz, s
 // mz_out / eq_out (n entries per row, strides ld_out / ldeq_out) and the message is that of the fixed tables
 void launch_lin_round_fused(const DevCrt &t, const LinCombDesc &desc, const u64 *mz_prev, size_t ld_prev, const u64 *eq_prev, size_t ldeq_prev, Fq3Const r, u64 *mz_out,
                             size_t ld_out, u64 *eq_out, size_t ldeq_out, size_t n, u32 deg, u64 *partial, u64 *out, hipStream_t s, u32 max_blocks, u32 xmask) {
+    if (desc.t > 4 || deg > 4) {
+        const LinFix fw = {r, mz_out, ld_out, eq_out, ldeq_out};
+        return launch_lin_round_wide(t, desc, mz_prev, ld_prev, eq_prev, ldeq_prev, n, deg, partial, out, s, max_blocks, xmask, &fw);
+    }
     u32 gb = (u32)((n / 2 + 255) / 256);
     const u32 cap = max_blocks && max_blocks < RED_BLOCKS ? max_blocks : RED_BLOCKS;
     if (gb > cap) gb = cap;
@@ -1658,7 +1658,7 @@ __global__ void __launch_bounds__(256) k_lin_tail(DevCrt t, LinCombDesc desc, Li
 size_t lin_tail_priv_words(size_t n0, u32 t) { return (size_t)8 * 2 * ((((1 + (size_t)t) * 3 * (n0 / 2)) + 15) & ~(size_t)15) + 16; }
 // eight workgroups (one per slot); returns 0 when the tail cannot run (the caller keeps per-round launches)
 u32 launch_lin_tail(const DevCrt &t, const LinCombDesc &desc, const LinTailArgs &A, hipStream_t s) {
-    if (A.n0 < 4 || A.rounds < 1 || A.rounds > TAIL_MAX_ROUNDS || A.deg + 1 > 5) return 0;
+    if (A.n0 < 4 || A.rounds < 1 || A.rounds > TAIL_MAX_ROUNDS || A.deg + 1 > 5 || desc.t > 4) return 0;   // (the wide envelope keeps per-round launches)
     if (t.nu2p40) hipLaunchKernelGGL((k_lin_tail<true>), dim3(1, 8), dim3(256), 0, s, t, desc, A);
     else hipLaunchKernelGGL((k_lin_tail<false>), dim3(1, 8), dim3(256), 0, s, t, desc, A);
     return 8;

@@ -186,6 +186,15 @@ def ring_mul_ntt(a: np.ndarray, b: np.ndarray, ring: str = "goldilocks") -> np.n
     return out.reshape(shape)
 
 
+def mix8_gamma(ring: str = "goldilocks") -> np.ndarray:
+    """the fixed coefficient of the "mix8" CCS: a ring element (NTT form) whose eight slots are distinct and none of them +-1"""
+    p, d, tau = RINGS[ring]
+    g = splitmix_fq(0x6A33A, 0, d, ring)
+    slots = {tuple(int(x) for x in g[i * tau:(i + 1) * tau]) for i in range(d // tau)}
+    assert len(slots) == d // tau and (1,) + (0,) * (tau - 1) not in slots and (p - 1,) + (0,) * (tau - 1) not in slots
+    return g
+
+
 @dataclass
 class Workload:
     name: str
@@ -290,7 +299,11 @@ def make_workload(name: str, seed: int = 0, kappa: int = None, ccs: str = "r1cs"
        ccs = "multi": an R1CS with 2 nnz/row and non-identity values: (A z)_i = z_i + z_{i+1}, B = I,
                       (C z)_i = z_i * (z_i + z_{i+1})  (satisfied by construction);
        ccs = "multi4" / "multi16": 4 / 16 entries per row at pseudo-random columns with scalar coefficients 1..7 in A, ring-valued entries in C (any size:
-                      vectorised generators)."""
+                      vectorised generators);
+       ccs = "deg4" .. "deg7": the deg3 construction at degree D: t = D + 1, M = (I x D, diag(z^(D-1))), S = {{0..D-1},{D}}, c = (1,-1), d = D;
+       ccs = "mix8": t = 8, q = 3, d = 5: M_0..M_6 = I, M_7 = diag(z^4 + gamma z), S = {{0,1,2,3,4},{5,6},{7}}, c = (1, gamma, -1) with a fixed ring element
+                     gamma of eight distinct non-unit slots (MIX8_GAMMA): multisets of three sizes and a coefficient that is not +-1; satisfied by construction,
+                     z^5 + gamma z^2 - z (z^4 + gamma z) = 0."""
     cfg = CONFIGS[name]
     s, wit_len, L, B, b, K, kap = cfg[:7]
     ring = cfg[7] if len(cfg) > 7 else "goldilocks"
@@ -322,6 +335,29 @@ def make_workload(name: str, seed: int = 0, kappa: int = None, ccs: str = "r1cs"
         wl.val = [ident, ident.copy(), ident.copy(), np.ascontiguousarray(zsq)]
         wl.S_off = np.array([0, 3, 4], dtype=np.uint32)
         wl.S_idx = np.array([0, 1, 2, 3], dtype=np.uint32)
+    elif ccs in ("deg4", "deg5", "deg6", "deg7"):
+        D = int(ccs[3:])
+        zp = z[:rows]
+        for _ in range(D - 2):
+            zp = ring_mul_ntt(zp, z[:rows], ring)                   # z^(D-1)
+        wl.t, wl.q, wl.d = D + 1, 2, D
+        wl.rowptr = [rp.copy() for _ in range(D + 1)]
+        wl.col = [ci.copy() for _ in range(D + 1)]
+        wl.val = [ident.copy() for _ in range(D)] + [np.ascontiguousarray(zp)]
+        wl.S_off = np.array([0, D, D + 1], dtype=np.uint32)
+        wl.S_idx = np.arange(D + 1, dtype=np.uint32)
+    elif ccs == "mix8":
+        gamma = mix8_gamma(ring)
+        z2 = ring_mul_ntt(z[:rows], z[:rows], ring)
+        z4 = ring_mul_ntt(z2, z2, ring)
+        last = _fp_add(z4, ring_mul_ntt(gamma[None, :], z[:rows], ring), ring)   # z^4 + gamma z
+        wl.t, wl.q, wl.d = 8, 3, 5
+        wl.rowptr = [rp.copy() for _ in range(8)]
+        wl.col = [ci.copy() for _ in range(8)]
+        wl.val = [ident.copy() for _ in range(7)] + [np.ascontiguousarray(last)]
+        wl.S_off = np.array([0, 5, 7, 8], dtype=np.uint32)
+        wl.S_idx = np.arange(8, dtype=np.uint32)
+        wl.c = np.stack([diag(1, ring), gamma, diag(p - 1, ring)])
     elif ccs == "multi":
         assert rows >= 2
         nxt = (np.arange(rows, dtype=np.uint32) + 1) % np.uint32(rows)
