@@ -1,16 +1,9 @@
 // bb_capi.cpp -- BabyBearRingNTT backend of the C ABI, part 1: context, ring tables, staging, the component entry points (CRT, decomposition, Ajtai
 // commitments, eq tables, MLE evaluations, SpMV), constraint-system load, device-resident witnesses, timing read-outs and the host verifier.  The provers are
 // in bb_prove.cpp.
-#include "bb_ctx.h"
+#include "lf_ring_host.h"
 
 namespace lfbb {
-
-size_t bb_lcccs_len(const lf_params *p) { return (size_t)p->s + TAU + p->kappa + p->t + p->l + 1; }
-size_t bb_cccs_len(const lf_params *p) { return (size_t)p->kappa + p->l; }
-size_t lin_proof_len(const lf_params *p) { return (size_t)p->s * (p->d + 2) + TAU + p->t; }
-size_t dec_proof_len(const lf_params *p) { return (size_t)p->K * (p->t + TAU + p->l + 1 + p->kappa); }
-static size_t fold_proof_len(const lf_params *p) { return (size_t)p->s * (2 * p->b + 1) + 2 * (size_t)p->K * (TAU + p->t); }
-size_t bb_proof_len(const lf_params *p) { return lin_proof_len(p) + 2 * dec_proof_len(p) + fold_proof_len(p); }
 
 // ---------------------------------------------------------------------------------------------------------------
 static int install_tables(C *c, u64 nonres, const u64 *y) {
@@ -163,24 +156,7 @@ int BbCtx::mem_info(size_t *f, size_t *t) {
     return LF_OK;
 }
 
-// ---- host<->device staging of AoS ring-element arrays (canonical u64 at the ABI, Montgomery planes on the device) -----
-int up_ring(C *c, const u64 *host, size_t n, fe *dst) {
-    if (!n) return LF_OK;
-    u64 *tmp;
-    RET(c->tbuf("stage_aos", n * RE, &tmp));
-    HIPCHK(hipMemcpyAsync(tmp, host, n * RE * 8, hipMemcpyHostToDevice, c->stream()));
-    launch_aos_to_soa(tmp, dst, n, c->stream());
-    return LF_OK;
-}
-int down_ring(C *c, const fe *src, size_t n, u64 *host) {
-    if (!n) return LF_OK;
-    u64 *tmp;
-    RET(c->tbuf("stage_aos", n * RE, &tmp));
-    launch_soa_to_aos(src, tmp, n, c->stream());
-    HIPCHK(hipMemcpyAsync(host, tmp, n * RE * 8, hipMemcpyDeviceToHost, c->stream()));
-    HIPCHK(hipStreamSynchronize(c->stream()));
-    return LF_OK;
-}
+// small device array -> host through pinned memory (up_ring / down_ring: lf_ring_host.h)
 int down_small(C *c, const u64 *dsrc, size_t words, u64 *host) {
     RET(c->pin(words));
     HIPCHK(hipMemcpyAsync(c->h_pin, dsrc, words * 8, hipMemcpyDeviceToHost, c->stream()));
@@ -271,83 +247,6 @@ int BbCtx::selftest_field(uint64_t seed, uint32_t n, uint64_t *mismatches) {
         bad += out[(size_t)i * 12 + 11] != hmul(a.c[0], b.c[0]);
     }
     *mismatches = bad;
-    return LF_OK;
-}
-
-// ---- a1/a2/a3 --------------------------------------------------------------------------------------------------------
-int BbCtx::ntt_fwd(const uint64_t *in, uint64_t *out, size_t count) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    fe *a, *b;
-    RET(c->tbuf("io_a", count * RE, &a));
-    RET(c->tbuf("io_b", count * RE, &b));
-    RET(up_ring(c, in, count, a));
-    launch_crt_fwd(c->dev, a, b, count, c->stream());
-    return down_ring(c, b, count, out);
-}
-int BbCtx::ntt_inv(const uint64_t *in, uint64_t *out, size_t count) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    fe *a, *b;
-    RET(c->tbuf("io_a", count * RE, &a));
-    RET(c->tbuf("io_b", count * RE, &b));
-    RET(up_ring(c, in, count, a));
-    launch_icrt_dense(c->d_icrt, a, b, count, c->stream());
-    return down_ring(c, b, count, out);
-}
-static bool pow2(u64 b) { return b >= 2 && (b & (b - 1)) == 0; }
-int BbCtx::decompose(const uint64_t *in, size_t count, uint64_t base, unsigned digits, int layout, uint64_t *out) {
-    C *c = p;
-    if (!pow2(base)) return LF_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    fe *a, *b;
-    RET(c->tbuf("io_a", count * RE, &a));
-    RET(c->tbuf("io_b", count * digits * RE, &b));
-    RET(up_ring(c, in, count, a));
-    launch_decompose(a, count, base, digits, layout, b, c->stream(), c->digit_mode);
-    if (layout == 0) return down_ring(c, b, count * digits, out);
-    for (unsigned k = 0; k < digits; k++) RET(down_ring(c, b + (size_t)k * RE * count, count, out + (size_t)k * count * RE));
-    return LF_OK;
-}
-int BbCtx::recompose(const uint64_t *in, size_t count_out, uint64_t base, unsigned digits, uint64_t *out) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    fe *a, *b;
-    RET(c->tbuf("io_a", count_out * digits * RE, &a));
-    RET(c->tbuf("io_b", count_out * RE, &b));
-    RET(up_ring(c, in, count_out * digits, a));
-    launch_recompose(a, count_out, base, digits, b, c->stream());
-    return down_ring(c, b, count_out, out);
-}
-int BbCtx::linf_check(const uint64_t *f_ntt, size_t count, uint64_t bound, int unsigned_variant, int *ok, uint64_t *max_out) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    fe *a, *b;
-    u64 *mx;
-    RET(c->tbuf("io_a", count * RE, &a));
-    RET(c->tbuf("io_b", count * RE, &b));
-    RET(c->tbuf("small_dev", 4096, &mx));
-    RET(up_ring(c, f_ntt, count, a));
-    launch_icrt_dense(c->d_icrt, a, b, count, c->stream());
-    if (unsigned_variant) {   // literal Witness::within_bound (arith.rs:372-386): canonical coefficient < bound
-        std::vector<u64> h(count * RE);
-        RET(down_ring(c, b, count, h.data()));
-        u64 m = 0;
-        for (u64 v : h) m = v > m ? v : m;
-        if (max_out) *max_out = m;
-        *ok = m < bound;
-        return LF_OK;
-    }
-    launch_linf(b, count, mx, c->stream());
-    u64 m = 0;
-    RET(down_small(c, mx, 1, &m));
-    if (max_out) *max_out = m;
-    *ok = m < bound;
     return LF_OK;
 }
 
@@ -449,55 +348,6 @@ int BbCtx::ajtai_generate(uint64_t seed, size_t kappa, size_t n) {
     c->nA = cnt; c->nA_total = n; c->A_col0 = col0;
     return prep_ajtai_i8(c);
 }
-// The contraction of `batch` operands whose digit words [NP][72][ntiles] of this rank's columns the caller's pass cut(b, pre, ntiles) writes.
-template <class Cut>
-static int commit_dev_pre(C *c, u32 NP, u32 batch, u64 *out_dev, bool timed, Cut &&cut) {
-    if (!c->i8_nch || !c->dAb) return LF_ERR_STATE;
-    const lf::AjtaiI8Ring R = lf::ajtai_i8_babybear();
-    const u32 nch = c->i8_nch, kc = c->i8_kc, MT = lf::ajtai_i8_row_tiles(R, kc);
-    const size_t ntiles = (c->nA + 7) / 8, chunk_bytes = ntiles * (R.RD / 8) * MT * 1024;
-    const char *e_wgs = getenv("LF_I8G_WGS");           // (test hook: workgroups of the general commit kernel; default one per CU)
-    const u32 nwg = e_wgs && atoi(e_wgs) > 0 ? (u32)atoi(e_wgs) : 256;
-    size_t pw, dw, sw;
-    if (lf::ajtai_i8g_scratch(R, MT, c->nA, NP, nwg, &pw, &dw, &sw) != 0) return LF_ERR_UNSUPPORTED;
-    unsigned long long *pre;
-    int32_t *part, *dsum;
-    long long *sum;
-    u64 *co;
-    fe *cf, *ntt;
-    RET(c->tbuf("i8g_pre", (size_t)NP * RE * ntiles, &pre));
-    RET(c->tbuf("i8g_part", pw, &part));
-    RET(c->tbuf("i8g_dsum", dw, &dsum));
-    RET(c->tbuf("i8g_sum", sw, &sum));
-    RET(c->tbuf("i8g_co", (size_t)RE * c->kappa, &co));
-    RET(c->tbuf("i8g_cf", (size_t)RE * c->kappa, &cf));
-    RET(c->tbuf("i8g_ntt", (size_t)RE * c->kappa, &ntt));
-    for (u32 b = 0; b < batch; b++) {
-        const size_t ev = timed ? c->ev_begin(1) : 0;   // the whole device side of one commitment: digit pass, contraction, recombination, CRT
-        cut(b, pre, ntiles);
-        for (u32 ch = 0; ch < nch; ch++) {
-            const u32 row0 = ch * kc, kn = c->kappa - row0 < kc ? c->kappa - row0 : kc;
-            const int g = lf::launch_ajtai_i8g(R, c->dAb + (size_t)ch * chunk_bytes, MT, pre, ntiles, c->nA, kn, row0, c->kappa, NP, nwg, part, dsum, sum, co, c->stream());
-            if (g < 0) return LF_ERR_UNSUPPORTED;
-        }
-        launch_aos_to_soa(co, cf, c->kappa, c->stream());       // canonical -> Montgomery planes
-        launch_crt_fwd(c->dev, cf, ntt, c->kappa, c->stream());
-        launch_soa_to_aos(ntt, out_dev + (size_t)b * c->kappa * RE, c->kappa, c->stream());
-        if (timed) c->ev_end(ev);
-    }
-    return LF_OK;
-}
-// General commitments from the resident byte planes of A (lf_ajtai_i8g.hip, shared with the Goldilocks backend): commit_ntt for `batch` vectors
-// F [batch][72][ldF] in NTT form (pointing at this rank's first column), or Witness::commit for the centred int32 planes of a witness handle
-// (F null, batch 1).  Five balanced base-128 digit planes cover the centred 31-bit residues.  out_dev: canonical u64 [batch][kappa][72], NTT form.
-static int commit_dev_i8g(C *c, const fe *F, size_t ldF, u32 batch, const int32_t *planes, size_t ldp, u64 *out_dev, bool timed) {
-    const u32 NP = planes ? lf::ajtai_i8g_planes_i32() : lf::ajtai_i8g_planes_general(lf::ajtai_i8_babybear());
-    return commit_dev_pre(c, NP, batch, out_dev, timed, [&](u32 b, unsigned long long *pre, size_t ntiles) {
-        if (planes) lf::launch_i8g_cut_i32(planes, ldp, c->nA, RE, NP, pre, ntiles, c->stream());
-        else launch_i8g_cut_ntt(c->d_icrt, c->d_icrt_sp_val, c->d_icrt_sp_col, F + (size_t)b * RE * ldF, ldF, c->nA, NP, pre, ntiles, c->stream());
-    });
-}
-int witness_commit_dev(C *c, const lf_witness *w, u64 *out_dev) { return commit_dev_i8g(c, nullptr, 0, 1, w->planes + c->A_col0, w->N, out_dev, false); }
 // F: [batch][72][ldF]; out_dev: canonical u64 [batch][kappa][72]
 static int commit_dev(C *c, const fe *F, size_t ldF, u32 batch, u64 *out_dev, bool timed) { return commit_dev_i8g(c, F, ldF, batch, nullptr, 0, out_dev, timed); }
 int BbCtx::ajtai_commit(const uint64_t *f, size_t n, size_t batch, uint64_t *out) {
@@ -575,44 +425,6 @@ int build_eq_dev(C *c, const H9 *pt, u32 nv, fe *eq_dev) {
     launch_build_eq(c->dev, rd, rd + nv, nv, eq_dev, c->stream());
     return LF_OK;
 }
-int BbCtx::build_eq(const uint64_t *point, unsigned nv, uint64_t *out) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    size_t n = (size_t)1 << nv;
-    fe *eq;
-    RET(c->tbuf("io_a", TAU * n, &eq));
-    std::vector<H9> pt(nv);
-    for (unsigned i = 0; i < nv; i++) pt[i] = h9_load(point + (size_t)TAU * i);
-    RET(build_eq_dev(c, pt.data(), nv, eq));
-    std::vector<fe> h(TAU * n);
-    HIPCHK(hipMemcpyAsync(h.data(), eq, h.size() * sizeof(fe), hipMemcpyDeviceToHost, c->stream()));
-    HIPCHK(hipStreamSynchronize(c->stream()));
-    for (size_t i = 0; i < n; i++)
-        for (int q = 0; q < TAU; q++) out[TAU * i + q] = to_canon(h[(size_t)q * n + i]);
-    return LF_OK;
-}
-int BbCtx::mle_eval_batch(const uint64_t *tables, size_t ntables, size_t len, const uint64_t *point, unsigned nv, uint64_t *out) {
-    C *c = p;
-    size_t n = (size_t)1 << nv;
-    if (len > n || len == 0) return LF_ERR_INVALID;   // MleEvaluationError::IncorrectLength
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    fe *eq, *X;
-    i64 *partial;
-    u64 *o;
-    RET(c->tbuf("io_eq", TAU * n, &eq));
-    RET(c->tbuf("io_a", ntables * len * RE, &X));
-    RET(c->tbuf("red_partial", red_partial_words((u32)(ntables * RE > 16 * RE * TAU ? ntables * RE : 16 * RE * TAU)), &partial));
-    RET(c->tbuf("io_o", ntables * RE, &o));
-    std::vector<H9> pt(nv);
-    for (unsigned i = 0; i < nv; i++) pt[i] = h9_load(point + (size_t)TAU * i);
-    RET(build_eq_dev(c, pt.data(), nv, eq));
-    for (size_t a = 0; a < ntables; a++) RET(up_ring(c, tables + a * len * RE, len, X + a * RE * len));
-    launch_dot_eq(c->dev, X, len, (u32)ntables, eq, n, len, partial, o, c->stream());
-    return down_small(c, o, ntables * RE, out);
-}
-
 // ---- CCS ------------------------------------------------------------------------------------------------------------------
 int BbCtx::ccs_load(const lf_params *P, const uint32_t *const *rowptr, const uint32_t *const *col, const uint64_t *const *val,
                     const uint32_t *S_off, const uint32_t *S_idx, const uint64_t *cc) {
@@ -689,121 +501,6 @@ int BbCtx::ccs_load(const lf_params *P, const uint32_t *const *rowptr, const uin
     c->have_ccs = true;
     return LF_OK;
 }
-int BbCtx::spmv(unsigned j, const uint64_t *z, uint64_t *out) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->have_ccs) return LF_ERR_STATE;
-    if (j >= c->P.t) return LF_ERR_INVALID;
-    HIPCHK(hipSetDevice(c->device));
-    fe *zd, *od;
-    RET(c->tbuf("io_a", c->n * RE, &zd));
-    RET(c->tbuf("io_b", c->m * RE, &od));
-    RET(up_ring(c, z, c->n, zd));
-    launch_spmv(c->dev, c->d_rowptr[j], c->d_col[j], c->d_val[j], zd, c->n, od, c->m, 0, c->stream());
-    return down_ring(c, od, c->m, out);
-}
-
-// ---- witnesses -----------------------------------------------------------------------------------------------------------
-static int witness_from_coef_table(C *c, const fe *coef_dev, lf_witness **out) {
-    int32_t *pl;
-    HIPCHK(lf_dev_malloc(&pl, c->N * RE * 4));
-    int *viol;
-    if (c->tbuf("small_dev", 4096, (u64 **)&viol) != LF_OK) { (void)hipFree(pl); return LF_ERR_HIP; }
-    (void)hipMemsetAsync(viol, 0, 4, c->stream());
-    launch_coef_to_i32(coef_dev, pl, c->N, (u32)(c->P.B / 2), viol, c->stream());
-    int hv = 0;
-    if (hipMemcpyAsync(&hv, viol, 4, hipMemcpyDeviceToHost, c->stream()) != hipSuccess || hipStreamSynchronize(c->stream()) != hipSuccess) {
-        (void)hipFree(pl);
-        return LF_ERR_HIP;
-    }
-    if (hv) { (void)hipFree(pl); return LF_ERR_NORM; }
-    *out = new lf_witness{c->owner, pl, c->N, lf_ctx_device(c->owner), c->N * RE * 4};
-    return LF_OK;
-}
-int BbCtx::witness_from_w_ccs(const uint64_t *w_ccs, lf_witness **out) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->have_ccs) return LF_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    fe *a, *b, *d;   // Witness::from_w_ccs, arith.rs:230-248: ICRT -> gadget_decompose(B, L)
-    RET(c->tbuf("io_a", (size_t)c->P.wit_len * RE, &a));
-    RET(c->tbuf("io_b", (size_t)c->P.wit_len * RE, &b));
-    RET(c->tbuf("io_c", c->N * RE, &d));
-    RET(up_ring(c, w_ccs, c->P.wit_len, a));
-    launch_icrt_dense(c->d_icrt, a, b, c->P.wit_len, c->stream());
-    launch_decompose(b, c->P.wit_len, c->P.B, c->P.L, 0, d, c->stream(), c->digit_mode);
-    return witness_from_coef_table(c, d, out);
-}
-int BbCtx::witness_from_f_coeff(const uint64_t *f_coeff, lf_witness **out) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->have_ccs) return LF_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    fe *d;
-    RET(c->tbuf("io_c", c->N * RE, &d));
-    RET(up_ring(c, f_coeff, c->N, d));
-    return witness_from_coef_table(c, d, out);
-}
-int BbCtx::witness_from_f(const uint64_t *f_ntt, lf_witness **out) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->have_ccs) return LF_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    fe *a, *d;
-    RET(c->tbuf("io_a", c->N * RE, &a));
-    RET(c->tbuf("io_c", c->N * RE, &d));
-    RET(up_ring(c, f_ntt, c->N, a));
-    launch_icrt_dense(c->d_icrt, a, d, c->N, c->stream());
-    return witness_from_coef_table(c, d, out);
-}
-int BbCtx::witness_get_f_coeff(const lf_witness *w, uint64_t *out) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    fe *d;
-    RET(c->tbuf("io_c", w->N * RE, &d));
-    launch_i32_to_coef(w->planes, d, w->N, c->stream());
-    return down_ring(c, d, w->N, out);
-}
-int BbCtx::witness_get_f(const lf_witness *w, uint64_t *out) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    if (w->f_ntt) return down_ring(c, (const fe *)w->f_ntt, w->N, out);      // built inside the fold step that produced this witness
-    fe *d, *e;
-    RET(c->tbuf("io_c", w->N * RE, &d));
-    RET(c->tbuf("io_b", w->N * RE, &e));
-    launch_i32_to_coef(w->planes, d, w->N, c->stream());
-    launch_crt_fwd(c->dev, d, e, w->N, c->stream());
-    return down_ring(c, e, w->N, out);
-}
-int BbCtx::witness_get_w_ccs(const lf_witness *w, uint64_t *out) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->have_ccs) return LF_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    if (w->w_ccs && w->w_bytes == (size_t)c->P.wit_len * RE * sizeof(fe)) return down_ring(c, (const fe *)w->w_ccs, c->P.wit_len, out);
-    fe *e;
-    RET(c->tbuf("io_b", (size_t)c->P.wit_len * RE, &e));
-    launch_recompose_crt(c->dev, w->planes, w->N, c->P.wit_len, c->P.L, c->P.B, 1, 0, e, c->P.wit_len, 0, c->stream());
-    return down_ring(c, e, c->P.wit_len, out);
-}
-int BbCtx::witness_commit(const lf_witness *w, uint64_t *cm_out) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->dAb) return LF_ERR_STATE;
-    if (w->N != c->nA_total) return LF_ERR_INVALID;
-    HIPCHK(hipSetDevice(c->device));
-    u64 *o;
-    RET(c->tbuf("io_o", (size_t)c->kappa * RE, &o));
-    // the int32 planes of the handle are the operand
-    c->ev_reset();
-    RET(commit_dev_i8g(c, nullptr, 0, 1, w->planes + c->A_col0, w->N, o, true));   // timed: lf_last_kernel_stats reports the stand-alone kernel
-    c->ev_collect();
-    RET(down_small(c, o, (size_t)c->kappa * RE, cm_out));
-    return exchange_modsum(c, cm_out, (size_t)c->kappa * RE);
-}
-
 int BbCtx::last_phase_ms(float *out) {
     for (int i = 0; i < NPH; i++) out[i] = p->phase_ms[i];
     return LF_OK;

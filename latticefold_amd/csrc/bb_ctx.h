@@ -187,13 +187,8 @@ int exchange_modsum(C *c, u64 *inout, size_t words);
 bool is_diag(const u64 *e, H9 *out);
 int commit_planes_i8(C *c, const int32_t *planes, size_t ld, u32 k0, u32 NP, u64 *out_dev);
 int build_eq_async(C *c, const H9 *pt, u32 nv, fe *eq_dev);
-int up_ring(C *c, const u64 *host, size_t n, fe *dst);
-int down_ring(C *c, const fe *src, size_t n, u64 *host);
-size_t dec_proof_len(const lf_params *p);
-size_t lin_proof_len(const lf_params *p);
 int build_z(C *c, const int32_t *planes, u32 K, int mode_bits, const u64 *heads, fe *z);   // bb_prove.cpp (synchronises the stream)
 bool lcccs_point(const lf_params &P, const u64 *lcccs, std::vector<H9> &pt);
-int witness_commit_dev(C *c, const lf_witness *w, u64 *out_dev);   // Witness::commit into device memory (kappa ring elements, canonical AoS; unsharded contexts)
 #pragma GCC visibility pop
 
 }  // namespace lfbb

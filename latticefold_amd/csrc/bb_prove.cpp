@@ -2,7 +2,7 @@
 // bb_kernels.hip -- linearization, decomposition and folding provers and the two sumchecks as stand-alone entry points.  Same structure as the Goldilocks
 // driver (lf_prove.cpp / lf_fold.cpp: f-hat virtual, Mz restructured, f_0 in the coefficient domain), one stream.  Host <-> device traffic inside a fold
 // step is O(proof size).
-#include "bb_ctx.h"
+#include "lf_ring_host.h"
 
 namespace lfbb {
 
@@ -358,7 +358,7 @@ static int dec_finish(C *c, BbTranscript &tr, const u64 *lcccs, SideState &S, u6
         for (u32 i = 0; i < P.kappa; i++) BbHostRing::sub(cm + (size_t)i * RE, &acc[(size_t)i * RE], y_s + (size_t)i * RE);
     }
     // transcript (decomposition.rs:65-83): absorb x_k, y_k, u_k, v_k and build the K LCCCS
-    size_t ll = bb_lcccs_len(&P);
+    size_t ll = lcccs_len(&P, TAU);
     S.lcccs.assign((size_t)K * ll * RE, 0);
     for (u32 k = 0; k < K; k++) {
         const u64 *xk = x_s + (size_t)k * (P.l + 1) * RE, *yk = y_s + (size_t)k * P.kappa * RE;
@@ -374,14 +374,6 @@ static int dec_finish(C *c, BbTranscript &tr, const u64 *lcccs, SideState &S, u6
         memcpy(o, uk, (size_t)P.t * RE * 8); o += (size_t)P.t * RE;
         memcpy(o, xk, (size_t)(P.l + 1) * RE * 8);
     }
-    return LF_OK;
-}
-
-template <class T>
-static int upload_consts(C *c, const std::string &name, const std::vector<T> &v, T **out) {
-    RET(c->tbuf(name, v.size() + 8, out));
-    HIPCHK(hipMemcpyAsync(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream()));
-    HIPCHK(hipStreamSynchronize(c->stream()));
     return LF_OK;
 }
 
@@ -440,7 +432,7 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
     const lf_params &P = c->P;
     size_t m = c->m, n = c->n, N = c->N;
     u32 K = P.K, K2 = 2 * K, deg = 2 * P.b;
-    size_t ll = bb_lcccs_len(&P);
+    size_t ll = lcccs_len(&P, TAU);
     const u64 nu = c->ring.T.nu;
     std::vector<H9> alpha(K2), zeta(K2), mu(K2), beta(P.s);
     // the bit-plane form of the two witnesses (GEMM rounds below) needs no challenge: built while the host squeezes alpha and zeta
@@ -1004,8 +996,8 @@ int BbCtx::fold_step(BbTranscript &tr, const uint64_t *acc, const lf_witness *w_
     c->ev_reset();
     c->host_tr_ms = 0;
     size_t tot = c->ev_begin(17);
-    size_t ll = bb_lcccs_len(&P);
-    u64 *lin_proof = proof, *decl = lin_proof + lin_proof_len(&P) * RE, *decr = decl + dec_proof_len(&P) * RE, *foldp = decr + dec_proof_len(&P) * RE;
+    size_t ll = lcccs_len(&P, TAU);
+    u64 *lin_proof = proof, *decl = lin_proof + lin_proof_len(&P, TAU) * RE, *decr = decl + dec_proof_len(&P, TAU) * RE, *foldp = decr + dec_proof_len(&P, TAU) * RE;
     std::vector<u64> lin(ll * RE);
     fe *eq_r_R = nullptr;
     SideState S[2];
@@ -1033,7 +1025,7 @@ int BbCtx::fold_step(BbTranscript &tr, const uint64_t *acc, const lf_witness *w_
         tr.absorb_label("acc");
         tr.absorb_ring(acc, ll);
         tr.absorb_label("cm_i");
-        tr.absorb_ring(cm_i, bb_cccs_len(&P));
+        tr.absorb_ring(cm_i, cccs_len(&P));
     }
     c->vs_keep = true;
     BB_MARK("public input absorbed");
@@ -1100,7 +1092,7 @@ int BbCtx::folding_prove(BbTranscript &tr, const uint64_t *lcccs_s, const lf_wit
     c->host_tr_ms = 0;
     c->arena_used[0] = c->arena_used[1] = 0;
     c->lane = 0;
-    const size_t ll = bb_lcccs_len(&P);
+    const size_t ll = lcccs_len(&P, TAU);
     const u32 K = P.K, hl = P.l + 1;
     SideState S[2];
     for (int sd = 0; sd < 2; sd++) {
@@ -1256,43 +1248,6 @@ int BbCtx::sumcheck_fold_end() {
     std::lock_guard<std::mutex> g(p->mu);
     p->sf_round = -1;
     return LF_OK;
-}
-// compute_f_0 (nifs/folding.rs:258-268) with ring-element coefficients
-int BbCtx::lincomb(const uint64_t *coef, const uint64_t *tables, size_t n_terms, size_t len, uint64_t *out) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    fe *X, *o;
-    RET(c->tbuf("io_a", n_terms * len * RE, &X));
-    RET(c->tbuf("io_b", len * RE, &o));
-    for (size_t i = 0; i < n_terms; i++) RET(up_ring(c, tables + i * len * RE, len, X + i * RE * len));
-    std::vector<E9PreC> cf(n_terms * 8);
-    for (size_t i = 0; i < n_terms; i++)
-        for (int sl = 0; sl < 8; sl++) cf[i * 8 + sl] = e9pre_from_h9(h9_load(coef + i * RE + (size_t)TAU * sl), c->ring.T.nu);
-    E9PreC *d_cf;
-    RET(upload_consts(c, "lc_coef", cf, &d_cf));
-    launch_lincomb_z(c->dev, X, len, (u32)n_terms, d_cf, 1, len, o, c->stream(), 1);
-    return down_ring(c, o, len, out);
-}
-// calculate_challenged_mz_mle (nifs/folding.rs:208-226) / prepare_g1_and_3_k_mles_list (folding/utils.rs:524-546)
-int BbCtx::horner_combine(const uint64_t *tables, size_t groups, size_t per_group, size_t len, const uint64_t *challenges, uint64_t *out) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    const size_t nt = groups * per_group;
-    fe *X, *o;
-    RET(c->tbuf("io_a", nt * len * RE, &X));
-    RET(c->tbuf("io_b", len * RE, &o));
-    for (size_t i = 0; i < nt; i++) RET(up_ring(c, tables + i * len * RE, len, X + i * RE * len));
-    std::vector<E9PreC> cf(nt);
-    for (size_t i = 0; i < groups; i++) {
-        H9 ci = h9_load(challenges + (size_t)TAU * i), pw = ci;
-        for (size_t j = 0; j < per_group; j++) { cf[i * per_group + j] = e9pre_from_h9(pw, c->ring.T.nu); pw = c->ring.mul9(pw, ci); }
-    }
-    E9PreC *d_cf;
-    RET(upload_consts(c, "lc_coef", cf, &d_cf));
-    launch_lincomb_z(c->dev, X, len, (u32)nt, d_cf, 1, len, o, c->stream(), 0);
-    return down_ring(c, o, len, out);
 }
 int BbCtx::sumcheck_lin_end() {
     std::lock_guard<std::mutex> g(p->mu);

@@ -1,7 +1,7 @@
 // lf_capi.cpp -- the C ABI (include/lfhip.h) of the Goldilocks backend, part 1: context, ring tables, sharding / RCCL set-up, staging, the component entry
 // points (CRT, decomposition, Ajtai commitments, eq tables, MLE evaluations, SpMV), constraint-system load, device-resident witnesses, transcripts, timing
 // read-outs and the host verifier.  The provers are in lf_prove.cpp (linearization, decomposition, entry points) and lf_fold.cpp (the folding prover).
-#include "lf_ctx.h"
+#include "lf_ring_host.h"
 
 const char *lf_strerror(int code) {
     switch (code) {
@@ -376,25 +376,7 @@ int lf_device_synchronize(lf_ctx *c) {
     return LF_OK;
 }
 
-// ---- host<->device staging of AoS ring-element arrays ----------------------------------------------------------
-// upload n ring elements (AoS) into a plane table dst [24][n]
-int up_ring(lf_ctx *c, const u64 *host, size_t n, u64 *dst) {
-    if (!n) return LF_OK;
-    u64 *tmp;
-    RET(c->tbuf("stage_aos", n * 24, &tmp));
-    HIPCHK(hipMemcpyAsync(tmp, host, n * 24 * 8, hipMemcpyHostToDevice, c->stream()));
-    launch_aos_to_soa(tmp, dst, n, c->stream());
-    return LF_OK;
-}
-int down_ring(lf_ctx *c, const u64 *src, size_t n, u64 *host) {
-    if (!n) return LF_OK;
-    u64 *tmp;
-    RET(c->tbuf("stage_aos", n * 24, &tmp));
-    launch_soa_to_aos(src, tmp, n, c->stream());
-    HIPCHK(hipMemcpyAsync(host, tmp, n * 24 * 8, hipMemcpyDeviceToHost, c->stream()));
-    HIPCHK(hipStreamSynchronize(c->stream()));
-    return LF_OK;
-}
+// ---- host<->device staging (up_ring / down_ring: lf_ring_host.h) -----------------------------------------------
 // small device array -> host (through pinned memory)
 int down_small(lf_ctx *c, const u64 *dsrc, size_t words, u64 *host) {
     RET(c->pin(words));
@@ -420,88 +402,25 @@ int lf_selftest_field(lf_ctx *c, uint64_t seed, uint32_t n, uint64_t *mismatches
 int lf_ntt_fwd(lf_ctx *c, const uint64_t *in, uint64_t *out, size_t count) {
     if (LF_XB(c)) { XB x(c); int rc = lf_ntt_fwd(c, in, out, count); if (rc == LF_OK) x.ring_out(out, count); return rc; }
     if (!c || (!in && count) || (!out && count)) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->ntt_fwd(in, out, count);
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    u64 *a, *b;
-    RET(c->tbuf("io_a", count * 24, &a));
-    RET(c->tbuf("io_b", count * 24, &b));
-    RET(up_ring(c, in, count, a));
-    launch_crt_fwd(c->dcrt, a, b, count, c->stream());
-    return down_ring(c, b, count, out);
+    return c->bb ? ring_ops<BbRing>::ntt_fwd(c->bb->p, in, out, count) : ring_ops<GoldRing>::ntt_fwd(c, in, out, count);
 }
 int lf_ntt_inv(lf_ctx *c, const uint64_t *in, uint64_t *out, size_t count) {
     if (LF_XB(c) && in) { XB x(c); return lf_ntt_inv(c, x.ring_in(in, count), out, count); }
     if (!c || (!in && count) || (!out && count)) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->ntt_inv(in, out, count);
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    u64 *a, *b;
-    RET(c->tbuf("io_a", count * 24, &a));
-    RET(c->tbuf("io_b", count * 24, &b));
-    RET(up_ring(c, in, count, a));
-    launch_icrt_dense(c->d_icrt, a, b, count, c->stream());
-    return down_ring(c, b, count, out);
+    return c->bb ? ring_ops<BbRing>::ntt_inv(c->bb->p, in, out, count) : ring_ops<GoldRing>::ntt_inv(c, in, out, count);
 }
-static bool pow2(u64 b) { return b >= 2 && (b & (b - 1)) == 0; }
 int lf_decompose(lf_ctx *c, const uint64_t *in, size_t count, uint64_t base, unsigned digits, int layout, uint64_t *out) {
     if (!c || !in || !out || digits == 0 || digits > 64 || (layout != 0 && layout != 1)) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->decompose(in, count, base, digits, layout, out);
-    if (!pow2(base)) return LF_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    u64 *a, *b;
-    RET(c->tbuf("io_a", count * 24, &a));
-    RET(c->tbuf("io_b", count * digits * 24, &b));
-    RET(up_ring(c, in, count, a));
-    launch_decompose(a, count, base, digits, layout, b, c->stream(), c->digit_mode);
-    if (layout == 0) return down_ring(c, b, count * digits, out);
-    for (unsigned k = 0; k < digits; k++) RET(down_ring(c, b + (size_t)k * 24 * count, count, out + (size_t)k * count * 24));
-    return LF_OK;
+    return c->bb ? ring_ops<BbRing>::decompose(c->bb->p, in, count, base, digits, layout, out) : ring_ops<GoldRing>::decompose(c, in, count, base, digits, layout, out);
 }
 int lf_recompose(lf_ctx *c, const uint64_t *in, size_t count_out, uint64_t base, unsigned digits, uint64_t *out) {
     if (!c || !in || !out || digits == 0) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->recompose(in, count_out, base, digits, out);
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    u64 *a, *b;
-    RET(c->tbuf("io_a", count_out * digits * 24, &a));
-    RET(c->tbuf("io_b", count_out * 24, &b));
-    RET(up_ring(c, in, count_out * digits, a));
-    launch_recompose(a, count_out, base, digits, b, c->stream());
-    return down_ring(c, b, count_out, out);
+    return c->bb ? ring_ops<BbRing>::recompose(c->bb->p, in, count_out, base, digits, out) : ring_ops<GoldRing>::recompose(c, in, count_out, base, digits, out);
 }
 int lf_linf_check(lf_ctx *c, const uint64_t *f_ntt, size_t count, uint64_t bound, int unsigned_variant, int *ok, uint64_t *max_out) {
     if (LF_XB(c) && f_ntt) { XB x(c); return lf_linf_check(c, x.ring_in(f_ntt, count), count, bound, unsigned_variant, ok, max_out); }
     if (!c || !f_ntt || !ok) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->linf_check(f_ntt, count, bound, unsigned_variant, ok, max_out);
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    u64 *a, *b, *mx;
-    RET(c->tbuf("io_a", count * 24, &a));
-    RET(c->tbuf("io_b", count * 24, &b));
-    RET(c->tbuf("small_dev", 4096, &mx));
-    RET(up_ring(c, f_ntt, count, a));
-    launch_icrt_dense(c->d_icrt, a, b, count, c->stream());
-    if (unsigned_variant) {
-        // literal Witness::within_bound: canonical coefficient < bound  <=>  max canonical < bound; reuse the
-        // centred kernel on a table where "negative" values are impossible: compare canonical values on host
-        // through a max reduction of min(v, p-1-v)?  Not equivalent -- do it exactly: download max canonical.
-        std::vector<u64> h(count * 24);
-        HIPCHK(hipMemcpyAsync(h.data(), b, count * 24 * 8, hipMemcpyDeviceToHost, c->stream()));
-        HIPCHK(hipStreamSynchronize(c->stream()));
-        u64 m = 0;
-        for (u64 v : h) m = v > m ? v : m;
-        if (max_out) *max_out = m;
-        *ok = m < bound;
-        return LF_OK;
-    }
-    launch_linf(b, count, mx, c->stream());
-    u64 m = 0;
-    RET(down_small(c, mx, 1, &m));
-    if (max_out) *max_out = m;
-    *ok = m < bound;
-    return LF_OK;
+    return c->bb ? ring_ops<BbRing>::linf_check(c->bb->p, f_ntt, count, bound, unsigned_variant, ok, max_out) : ring_ops<GoldRing>::linf_check(c, f_ntt, count, bound, unsigned_variant, ok, max_out);
 }
 
 // ---- a5 -----------------------------------------------------------------------------------------------------------
@@ -626,53 +545,6 @@ int lf_device_memory(lf_ctx *c, size_t *free_bytes, size_t *total_bytes) {
     HIPCHK(hipMemGetInfo(free_bytes, total_bytes));
     return LF_OK;
 }
-// The contraction of `batch` operands whose digit words [NP][24][ntiles] of this rank's columns the caller's pass cut(b, pre, ntiles) writes: NP = 10 for an
-// arbitrary element, 5 for the int32 planes of a witness handle, fewer for the digits of a gadget decomposition (ajtai_i8g_planes_base).
-// out_dev: [batch][kappa][24] NTT form, AoS (PARTIAL when sharded).
-template <class Cut>
-static int commit_dev_pre(lf_ctx *c, u32 NP, u32 batch, u64 *out_dev, bool timed, Cut &&cut) {
-    if (!c->A_loaded || !c->i8_nch || !c->dAb) return LF_ERR_STATE;
-    const AjtaiI8Ring R = ajtai_i8_goldilocks();
-    const u32 nch = c->i8_nch, kc = c->i8_kc, MT = ajtai_i8_row_tiles(R, kc);
-    const size_t ntiles = (c->nA + 7) / 8, chunk_bytes = ntiles * (R.RD / 8) * MT * 1024;
-    const char *e_wgs = getenv("LF_I8G_WGS");           // (test hook: workgroups of the general commit kernel; default one per CU)
-    const u32 nwg = e_wgs && atoi(e_wgs) > 0 ? (u32)atoi(e_wgs) : 256;
-    size_t pw, dw, sw;
-    if (ajtai_i8g_scratch(R, MT, c->nA, NP, nwg, &pw, &dw, &sw) != 0) return LF_ERR_UNSUPPORTED;
-    unsigned long long *pre;
-    int32_t *part, *dsum;
-    long long *sum;
-    u64 *coef, *ntt;
-    RET(c->tbuf("i8g_pre", (size_t)NP * 24 * ntiles, &pre));
-    RET(c->tbuf("i8g_part", pw, &part));
-    RET(c->tbuf("i8g_dsum", dw, &dsum));
-    RET(c->tbuf("i8g_sum", sw, &sum));
-    RET(c->tbuf("i8g_coef", (size_t)24 * c->kappa, &coef));
-    RET(c->tbuf("i8g_ntt", (size_t)24 * c->kappa, &ntt));
-    for (u32 b = 0; b < batch; b++) {
-        const size_t ev = timed ? c->ev_begin(1) : 0;   // the whole device side of one commitment: digit pass, contraction, recombination, CRT
-        cut(b, pre, ntiles);
-        for (u32 ch = 0; ch < nch; ch++) {
-            const u32 row0 = ch * kc, kn = c->kappa - row0 < kc ? c->kappa - row0 : kc;
-            const int g = launch_ajtai_i8g(R, c->dAb + (size_t)ch * chunk_bytes, MT, pre, ntiles, c->nA, kn, row0, c->kappa, NP, nwg, part, dsum, sum, coef, c->stream());
-            if (g < 0) return LF_ERR_UNSUPPORTED;
-        }
-        launch_crt_fwd(c->dcrt, coef, ntt, c->kappa, c->stream());
-        launch_soa_to_aos(ntt, out_dev + (size_t)b * c->kappa * 24, c->kappa, c->stream());
-        if (timed) c->ev_end(ev);
-    }
-    return LF_OK;
-}
-// General commitments from the resident byte planes of A (lf_ajtai_i8g.hip): AjtaiCommitmentScheme::commit_ntt (commitment_scheme.rs:37-54,75-77) for
-// `batch` vectors F [batch][24][ldF] in NTT form (pointing at this rank's first column), or Witness::commit (arith.rs:357-362) for the centred int32
-// coefficient planes of a witness handle (F null, batch 1).  out_dev: [batch][kappa][24] NTT form, AoS (PARTIAL when sharded).
-static int commit_dev_i8g(lf_ctx *c, const u64 *F, size_t ldF, u32 batch, const int32_t *planes, size_t ldp, u64 *out_dev, bool timed) {
-    const u32 NP = planes ? ajtai_i8g_planes_i32() : ajtai_i8g_planes_general(ajtai_i8_goldilocks());
-    return commit_dev_pre(c, NP, batch, out_dev, timed, [&](u32 b, unsigned long long *pre, size_t ntiles) {
-        if (planes) launch_i8g_cut_i32(planes, ldp, c->nA, 24, NP, pre, ntiles, c->stream());
-        else launch_i8g_cut_ntt(c->d_icrt, c->d_icrt_sp_val, c->d_icrt_sp_col, F + (size_t)b * 24 * ldF, ldF, c->nA, NP, pre, ntiles, c->stream());
-    });
-}
 // The K - 1 part commitments of a base-b decomposition (decomposition.rs:178-201) as the planes of ONE general-commit launch per row chunk: A leaves HBM once
 // per decomposition.  D [NP][24][ldn] are the operand words already (lf_sb.h); the finish writes every plane's commitment instead of recombining them.
 int commit_parts_i8g(lf_ctx *c, const unsigned char *D, size_t ldn, u32 NP, u64 *out_dev) {
@@ -716,7 +588,6 @@ int sb_cut_parts(lf_ctx *c, const lf_witness *wit, const char *name, const unsig
     *D = d;
     return LF_OK;
 }
-int witness_commit_dev(lf_ctx *c, const lf_witness *w, u64 *out_dev) { return commit_dev_i8g(c, nullptr, 0, 1, w->planes + c->A_col0, w->N, out_dev, false); }
 // F: [batch][24][ldF] device, pointing at this rank's first column; out_dev: [batch][kappa][24] device AoS (PARTIAL when sharded)
 static int commit_dev(lf_ctx *c, const u64 *F, size_t ldF, u32 batch, u64 *out_dev, bool timed) { return commit_dev_i8g(c, F, ldF, batch, nullptr, 0, out_dev, timed); }
 // download a (partial) commitment and, when sharded, all-gather + add the partials mod p
@@ -905,21 +776,7 @@ int build_eq_dev(lf_ctx *c, const Fq3 *pt, u32 nv, u64 *eq_dev) {
 int lf_build_eq(lf_ctx *c, const uint64_t *point, unsigned nv, uint64_t *out) {
     if (LF_XB(c) && point && out && nv && nv <= 40) { XB x(c); int rc = lf_build_eq(c, x.ext_in(point, nv), nv, out); if (rc == LF_OK) x.ext_out(out, (size_t)1 << nv); return rc; }
     if (!c || !point || !out || nv == 0 || nv > 40) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->build_eq(point, nv, out);
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    size_t n = (size_t)1 << nv;
-    u64 *eq;
-    RET(c->tbuf("io_a", 3 * n, &eq));
-    std::vector<Fq3> pt(nv);
-    for (unsigned i = 0; i < nv; i++) pt[i] = fq3_make(point[3 * i], point[3 * i + 1], point[3 * i + 2]);
-    RET(build_eq_dev(c, pt.data(), nv, eq));
-    std::vector<u64> h(3 * n);
-    HIPCHK(hipMemcpyAsync(h.data(), eq, 3 * n * 8, hipMemcpyDeviceToHost, c->stream()));
-    HIPCHK(hipStreamSynchronize(c->stream()));
-    for (size_t i = 0; i < n; i++)
-        for (int q = 0; q < 3; q++) out[3 * i + q] = h[(size_t)q * n + i];
-    return LF_OK;
+    return c->bb ? ring_ops<BbRing>::build_eq(c->bb->p, point, nv, out) : ring_ops<GoldRing>::build_eq(c, point, nv, out);
 }
 int lf_mle_eval_batch(lf_ctx *c, const uint64_t *tables, size_t ntables, size_t len, const uint64_t *point, unsigned nv, uint64_t *out) {
     if (LF_XB(c) && tables && point && out) {
@@ -929,34 +786,16 @@ int lf_mle_eval_batch(lf_ctx *c, const uint64_t *tables, size_t ntables, size_t 
         return rc;
     }
     if (!c || !tables || !point || !out || !ntables || nv == 0 || nv > 40) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->mle_eval_batch(tables, ntables, len, point, nv, out);
-    size_t n = (size_t)1 << nv;
-    if (len > n || len == 0) return LF_ERR_INVALID;  // MleEvaluationError::IncorrectLength
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    u64 *eq, *X, *partial, *o;
-    RET(c->tbuf("io_eq", 3 * n, &eq));
-    RET(c->tbuf("io_a", ntables * len * 24, &X));
-    RET(c->tbuf("red_partial", 256 * (ntables * 24 > 4096 ? ntables * 24 : 4096), &partial));
-    RET(c->tbuf("io_b", ntables * 24, &o));
-    std::vector<Fq3> pt(nv);
-    for (unsigned i = 0; i < nv; i++) pt[i] = fq3_make(point[3 * i], point[3 * i + 1], point[3 * i + 2]);
-    RET(build_eq_dev(c, pt.data(), nv, eq));
-    for (size_t a = 0; a < ntables; a++) RET(up_ring(c, tables + a * len * 24, len, X + a * 24 * len));
-    launch_dot_eq(c->dcrt, X, len, (u32)ntables, eq, n, len, partial, o, c->stream());
-    return down_small(c, o, ntables * 24, out);
+    return c->bb ? ring_ops<BbRing>::mle_eval_batch(c->bb->p, tables, ntables, len, point, nv, out) : ring_ops<GoldRing>::mle_eval_batch(c, tables, ntables, len, point, nv, out);
 }
 
 // ---- CCS -------------------------------------------------------------------------------------------------------------
-size_t lf_lcccs_len_ring(const lf_params *p, int ring) { return ring == LF_RING_BABYBEAR ? lfbb::bb_lcccs_len(p) : lf_lcccs_len(p); }
-size_t lf_cccs_len_ring(const lf_params *p, int ring) { return ring == LF_RING_BABYBEAR ? lfbb::bb_cccs_len(p) : lf_cccs_len(p); }
-size_t lf_proof_len_ring(const lf_params *p, int ring) { return ring == LF_RING_BABYBEAR ? lfbb::bb_proof_len(p) : lf_proof_len(p); }
-size_t lf_lcccs_len(const lf_params *p) { return (size_t)p->s + 3 + p->kappa + p->t + p->l + 1; }
-size_t lf_cccs_len(const lf_params *p) { return (size_t)p->kappa + p->l; }
-size_t lin_proof_len(const lf_params *p) { return (size_t)p->s * (p->d + 2) + 3 + p->t; }
-size_t dec_proof_len(const lf_params *p) { return (size_t)p->K * (p->t + 3 + p->l + 1 + p->kappa); }
-static size_t fold_proof_len(const lf_params *p) { return (size_t)p->s * (2 * p->b + 1) + 2 * (size_t)p->K * (3 + p->t); }
-size_t lf_proof_len(const lf_params *p) { return lin_proof_len(p) + 2 * dec_proof_len(p) + fold_proof_len(p); }
+size_t lf_lcccs_len_ring(const lf_params *p, int ring) { return lcccs_len(p, ring == LF_RING_BABYBEAR ? 9 : 3); }
+size_t lf_cccs_len_ring(const lf_params *p, int) { return cccs_len(p); }
+size_t lf_proof_len_ring(const lf_params *p, int ring) { return proof_len(p, ring == LF_RING_BABYBEAR ? 9 : 3); }
+size_t lf_lcccs_len(const lf_params *p) { return lcccs_len(p, 3); }
+size_t lf_cccs_len(const lf_params *p) { return cccs_len(p); }
+size_t lf_proof_len(const lf_params *p) { return proof_len(p, 3); }
 
 int lf_ccs_load(lf_ctx *c, const lf_params *p, const uint32_t *const *rowptr, const uint32_t *const *col, const uint64_t *const *val,
                 const uint32_t *S_off, const uint32_t *S_idx, const uint64_t *cc) {
@@ -1059,53 +898,10 @@ int lf_ccs_load(lf_ctx *c, const lf_params *p, const uint32_t *const *rowptr, co
 int lf_spmv(lf_ctx *c, unsigned j, const uint64_t *z, uint64_t *out) {
     if (LF_XB(c) && z && out && c->have_ccs_any()) { XB x(c); int rc = lf_spmv(c, j, x.ring_in(z, c->n_any()), out); if (rc == LF_OK) x.ring_out(out, c->m_any()); return rc; }
     if (!c || !z || !out) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->spmv(j, z, out);
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->have_ccs) return LF_ERR_STATE;
-    if (j >= c->P.t) return LF_ERR_INVALID;
-    HIPCHK(hipSetDevice(c->device));
-    u64 *zd, *od;
-    RET(c->tbuf("io_a", c->n * 24, &zd));
-    RET(c->tbuf("io_b", c->m * 24, &od));
-    RET(up_ring(c, z, c->n, zd));
-    if (c->ccs_general) {
-        u64 *zaos;
-        RET(c->tbuf("spmv_zaos", c->n * 24, &zaos));
-        launch_spmv_rows(c->dcrt, 1, &c->d_rowptr[j], &c->d_col[j], &c->d_val[j], zd, 0, c->n, zaos, od, c->m, 0, c->stream());
-    } else
-    launch_spmv(c->dcrt, c->d_rowptr[j], c->d_col[j], c->d_val[j], zd, c->n, od, c->m, 0, c->stream());
-    return down_ring(c, od, c->m, out);
+    return c->bb ? ring_ops<BbRing>::spmv(c->bb->p, j, z, out) : ring_ops<GoldRing>::spmv(c, j, z, out);
 }
 
 // ---- witnesses ---------------------------------------------------------------------------------------------------------
-static int witness_from_coef_table(lf_ctx *c, const u64 *coef_dev /* [24][N] canonical */, lf_witness **out) {
-    int32_t *pl;
-    HIPCHK(lf_dev_malloc(&pl, c->N * 24 * 4));
-    int *viol;
-    if (c->tbuf("small_dev", 4096, (u64 **)&viol) != LF_OK) { (void)hipFree(pl); return LF_ERR_HIP; }
-    (void)hipMemsetAsync(viol, 0, 4, c->stream());
-    launch_coef_to_i32(coef_dev, pl, c->N, (u32)(c->P.B / 2), viol, c->stream());
-    int hv = 0;
-    if (hipMemcpyAsync(&hv, viol, 4, hipMemcpyDeviceToHost, c->stream()) != hipSuccess || hipStreamSynchronize(c->stream()) != hipSuccess) {
-        (void)hipFree(pl);
-        return LF_ERR_HIP;
-    }
-    if (hv) { (void)hipFree(pl); return (hv & 1) ? LF_ERR_NORM : LF_ERR_UNSUPPORTED; }
-    lf_witness *w = new lf_witness{c, pl, c->N, c->device, c->N * 24 * 4};
-    *out = w;
-    return LF_OK;
-}
-// Witness::from_w_ccs, arith.rs:230-248: ICRT -> gadget_decompose(B, L); on the calling thread's lane (its stream, its buffers)
-static int witness_from_w_ccs_lane(lf_ctx *c, const uint64_t *w_ccs, lf_witness **out) {
-    u64 *a, *b, *d;
-    RET(c->tbuf("io_a", (size_t)c->P.wit_len * 24, &a));
-    RET(c->tbuf("io_b", (size_t)c->P.wit_len * 24, &b));
-    RET(c->tbuf("io_c", c->N * 24, &d));
-    RET(up_ring(c, w_ccs, c->P.wit_len, a));
-    launch_icrt_dense(c->d_icrt, a, b, c->P.wit_len, c->stream());
-    launch_decompose(b, c->P.wit_len, c->P.B, c->P.L, 0, d, c->stream(), c->digit_mode);
-    return witness_from_coef_table(c, d, out);
-}
 // ---- ingestion next to a running fold step (a chain's next witness: upload over PCIe, ICRT and gadget decomposition on the lowest-priority stream while the
 // step before it folds).  Goldilocks contexts in the default basis run it on lane 2 (own stream, own buffers, c->io_mu instead of c->mu: the constraint system
 // must not be reloaded meanwhile); every other configuration runs the blocking call on the worker thread -- the same witness, no overlap promised.
@@ -1124,7 +920,7 @@ int lf_witness_from_w_ccs_begin(lf_ctx *c, const uint64_t *w_ccs, lf_witness_job
         std::lock_guard<std::mutex> g(c->io_mu);
         if (hipSetDevice(c->device) != hipSuccess) return LF_ERR_HIP;
         t_lane = 2;
-        return witness_from_w_ccs_lane(c, w_ccs, &j->w);
+        return ring_ops<GoldRing>::witness_from_w_ccs_lane(c, w_ccs, &j->w);
     });
     *job = j;
     return LF_OK;
@@ -1140,89 +936,35 @@ int lf_witness_job_finish(lf_witness_job *job, lf_witness **out) {
 int lf_witness_from_w_ccs(lf_ctx *c, const uint64_t *w_ccs, lf_witness **out) {
     if (LF_XB(c) && w_ccs && c->have_ccs_any()) { XB x(c); return lf_witness_from_w_ccs(c, x.ring_in(w_ccs, c->params_any().wit_len), out); }
     if (!c || !w_ccs || !out) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->witness_from_w_ccs(w_ccs, out);
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->have_ccs) return LF_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    return witness_from_w_ccs_lane(c, w_ccs, out);
+    return c->bb ? ring_ops<BbRing>::witness_from_w_ccs(c->bb->p, w_ccs, out) : ring_ops<GoldRing>::witness_from_w_ccs(c, w_ccs, out);
 }
 int lf_witness_from_f_coeff(lf_ctx *c, const uint64_t *f_coeff, lf_witness **out) {
     if (!c || !f_coeff || !out) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->witness_from_f_coeff(f_coeff, out);
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->have_ccs) return LF_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    u64 *d;
-    RET(c->tbuf("io_c", c->N * 24, &d));
-    RET(up_ring(c, f_coeff, c->N, d));
-    return witness_from_coef_table(c, d, out);
+    return c->bb ? ring_ops<BbRing>::witness_from_f_coeff(c->bb->p, f_coeff, out) : ring_ops<GoldRing>::witness_from_f_coeff(c, f_coeff, out);
 }
 int lf_witness_from_f(lf_ctx *c, const uint64_t *f_ntt, lf_witness **out) {
     if (LF_XB(c) && f_ntt && c->have_ccs_any()) { XB x(c); return lf_witness_from_f(c, x.ring_in(f_ntt, c->N_any()), out); }
     if (!c || !f_ntt || !out) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->witness_from_f(f_ntt, out);
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->have_ccs) return LF_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    u64 *a, *d;
-    RET(c->tbuf("io_a", c->N * 24, &a));
-    RET(c->tbuf("io_c", c->N * 24, &d));
-    RET(up_ring(c, f_ntt, c->N, a));
-    launch_icrt_dense(c->d_icrt, a, d, c->N, c->stream());
-    return witness_from_coef_table(c, d, out);
+    return c->bb ? ring_ops<BbRing>::witness_from_f(c->bb->p, f_ntt, out) : ring_ops<GoldRing>::witness_from_f(c, f_ntt, out);
 }
 int lf_witness_get_f_coeff(lf_ctx *c, const lf_witness *w, uint64_t *out) {
     if (!c || !w || !out || w->ctx != c) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->witness_get_f_coeff(w, out);
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    u64 *d;
-    RET(c->tbuf("io_c", w->N * 24, &d));
-    launch_i32_to_coef(w->planes, d, w->N, c->stream());
-    return down_ring(c, d, w->N, out);
+    return c->bb ? ring_ops<BbRing>::witness_get_f_coeff(c->bb->p, w, out) : ring_ops<GoldRing>::witness_get_f_coeff(c, w, out);
 }
 int lf_witness_get_f(lf_ctx *c, const lf_witness *w, uint64_t *out) {
     if (LF_XB(c) && w && out) { XB x(c); int rc = lf_witness_get_f(c, w, out); if (rc == LF_OK) x.ring_out(out, w->N); return rc; }
     if (!c || !w || !out || w->ctx != c) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->witness_get_f(w, out);
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    if (w->f_ntt) return down_ring(c, w->f_ntt, w->N, out);      // built inside the fold step that produced this witness
-    u64 *d, *e;
-    RET(c->tbuf("io_c", w->N * 24, &d));
-    RET(c->tbuf("io_b", w->N * 24, &e));
-    launch_i32_to_coef(w->planes, d, w->N, c->stream());
-    launch_crt_fwd(c->dcrt, d, e, w->N, c->stream());
-    return down_ring(c, e, w->N, out);
+    return c->bb ? ring_ops<BbRing>::witness_get_f(c->bb->p, w, out) : ring_ops<GoldRing>::witness_get_f(c, w, out);
 }
 int lf_witness_get_w_ccs(lf_ctx *c, const lf_witness *w, uint64_t *out) {
     if (LF_XB(c) && w && out && c->have_ccs_any()) { XB x(c); int rc = lf_witness_get_w_ccs(c, w, out); if (rc == LF_OK) x.ring_out(out, c->params_any().wit_len); return rc; }
     if (!c || !w || !out || w->ctx != c) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->witness_get_w_ccs(w, out);
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->have_ccs) return LF_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    if (w->w_ccs && w->w_bytes == (size_t)c->P.wit_len * 24 * 8) return down_ring(c, w->w_ccs, c->P.wit_len, out);
-    u64 *e;
-    RET(c->tbuf("io_b", (size_t)c->P.wit_len * 24, &e));
-    launch_recompose_crt(c->dcrt, w->planes, w->N, c->P.wit_len, c->P.L, c->P.B, 1, 0, e, c->P.wit_len, 0, c->stream());
-    return down_ring(c, e, c->P.wit_len, out);
+    return c->bb ? ring_ops<BbRing>::witness_get_w_ccs(c->bb->p, w, out) : ring_ops<GoldRing>::witness_get_w_ccs(c, w, out);
 }
 int lf_witness_commit(lf_ctx *c, const lf_witness *w, uint64_t *cm_out) {
     if (LF_XB(c) && w && cm_out) { XB x(c); int rc = lf_witness_commit(c, w, cm_out); if (rc == LF_OK) x.ring_out(cm_out, c->bb ? c->bb->kappa() : c->kappa); return rc; }
     if (!c || !w || !cm_out || w->ctx != c) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->witness_commit(w, cm_out);
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->A_loaded) return LF_ERR_STATE;
-    if (w->N != c->nA_total) return LF_ERR_INVALID;
-    HIPCHK(hipSetDevice(c->device));
-    u64 *o;
-    RET(c->tbuf("io_o", (size_t)c->kappa * 24, &o));
-    // the int32 planes of the handle are the operand: five base-128 digit planes, no NTT of the witness
-    c->ev_reset();
-    RET(commit_dev_i8g(c, nullptr, 0, 1, w->planes + c->A_col0, w->N, o, true));   // timed: lf_last_kernel_stats reports the stand-alone kernel
-    c->ev_collect();
-    return commit_download(c, o, (size_t)c->kappa * 24, cm_out);
+    return c->bb ? ring_ops<BbRing>::witness_commit(c->bb->p, w, cm_out) : ring_ops<GoldRing>::witness_commit(c, w, cm_out);
 }
 // pool of recycled witness-plane buffers: process-wide (a witness may be freed after its context), keyed by device and size
 namespace {

@@ -443,8 +443,6 @@ struct XB {
 };
 #define LF_XB(c) ((c) && (c)->xb.on && !t_xb_active)
 int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out, lf_witness **w_out, u64 *proof);
-size_t dec_proof_len(const lf_params *p);
-size_t lin_proof_len(const lf_params *p);
 int commit_planes_i8(lf_ctx *c, const int32_t *planes, size_t ld, u32 k0, u32 NP, u64 *out_dev, const lf_witness *wit = nullptr);
 int commit_download(lf_ctx *c, const u64 *dev, size_t words, u64 *host);
 // small-base path: the NP part commitments y_k = A f_k of the digit planes D [NP][24][ldn] (lf_sb.h) in ONE pass over A -> out_dev [NP][kappa][24] NTT form
@@ -456,17 +454,14 @@ void fold_instance_host(lf_ctx *c, const std::vector<Fq3> &pt, const u64 *theta,
                         u64 *lcccs_out);
 int fold_impl_sb(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out, lf_witness **w_out, u64 *proof);
 int sb_fold_round_abi(lf_ctx *c, const u64 *t5, const u64 *F, size_t n, const Fq3Const *d_mu, u64 *evals_out);
-int up_ring(lf_ctx *c, const u64 *host, size_t n, u64 *dst);
 int dot_batch_dev(lf_ctx *c, const u64 *X, size_t ldx, u32 na, const u64 *Y, size_t ldy, u32 nb, size_t n, u64 *dpart, u64 *od, hipStream_t st = nullptr,
                          const char *tag = "", unsigned char *yb_pre = nullptr);
 int coef_eval_dev(lf_ctx *c, const int32_t *planes, size_t n, const u64 *eq, size_t ldeq, u32 K, int mode_bits, u64 *partial, u64 *od, size_t ldp,
                          const lf_witness *wit = nullptr);
 int lin_tail_rounds(lf_ctx *c, Transcript &tr, const u64 *cur, const u64 *cure, size_t n, u64 *tout, u64 *partial, u32 round, Fq3 *point,
                            u64 *msgs, u32 deg, const std::function<void(u32)> *after_round);
-int down_ring(lf_ctx *c, const u64 *src, size_t n, u64 *host);
 // z tables [K][24][n] = heads (l + 1 elements per table) || the recomposed witness columns [w0, w0 + wcnt) (lf_prove.cpp)
 int build_z(lf_ctx *c, const int32_t *planes, u32 K, int mode_bits, const u64 *heads, u64 *z, size_t w0 = 0, size_t wcnt = (size_t)-1,
             const unsigned char *D = nullptr /* small-base path: the digit planes the K parts come from (lf_sb.h) */);
 bool lcccs_point(const lf_params &P, const u64 *lcccs, std::vector<Fq3> &pt);   // the LCCCS point r as F_{p^3} challenges; false if not diagonal
-int witness_commit_dev(lf_ctx *c, const lf_witness *w, u64 *out_dev);   // Witness::commit into device memory (kappa ring elements, AoS; unsharded contexts)
 #pragma GCC visibility pop

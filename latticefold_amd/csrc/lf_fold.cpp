@@ -1,11 +1,6 @@
 // lf_fold.cpp -- the folding prover (nifs/folding.rs:74-179 with the sumcheck of nifs/folding/utils.rs:273-325) on the GPU kernels: the int8 GEMM rounds,
 // the look-up-table and table rounds, the persistent tail and the fold of the witnesses; plus the two sumchecks as stand-alone ABI entry points.
-#include "lf_ctx.h"
-
-static int upload_consts(lf_ctx *c, const std::string &name, const std::vector<Fq3Const> &v, Fq3Const **out) {
-    RET(c->tbuf(name, v.size() + 8, out));
-    return c->h2d_small(*out, v.data(), v.size() * sizeof(Fq3Const));
-}
+#include "lf_ring_host.h"
 
 // Host side of the mailbox protocol of a persistent tail kernel (k_fold_tail / k_lin_tail): per round poll the message, run the transcript
 // (unless the device sponge does), write the challenge back.  msgs = slot of the first tail round's message, pt = its challenge.
@@ -997,43 +992,14 @@ int lf_sumcheck_fold_end(lf_ctx *c) {
 int lf_lincomb(lf_ctx *c, const uint64_t *coef, const uint64_t *tables, size_t n_terms, size_t len, uint64_t *out) {
     if (LF_XB(c) && coef && tables && out) { XB x(c); int rc = lf_lincomb(c, x.ring_in(coef, n_terms), x.ring_in(tables, n_terms * len), n_terms, len, out); if (rc == LF_OK) x.ring_out(out, len); return rc; }
     if (!c || !coef || !tables || !out || !n_terms || !len) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->lincomb(coef, tables, n_terms, len, out);
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    u64 *X, *o;
-    RET(c->tbuf("io_a", n_terms * len * 24, &X));
-    RET(c->tbuf("io_b", len * 24, &o));
-    for (size_t i = 0; i < n_terms; i++) RET(up_ring(c, tables + i * len * 24, len, X + i * 24 * len));
-    std::vector<Fq3Const> cf(n_terms * 8);
-    for (size_t i = 0; i < n_terms; i++)
-        for (int sl = 0; sl < 8; sl++)
-            for (int q = 0; q < 3; q++) cf[i * 8 + sl].c[q] = coef[i * 24 + 3 * sl + q];
-    Fq3Const *d_cf;
-    RET(upload_consts(c, "lc_coef", cf, &d_cf));
-    launch_lincomb_z(c->dcrt, X, len, (u32)n_terms, d_cf, 1, len, o, c->stream(), 1);
-    return down_ring(c, o, len, out);
+    return c->bb ? ring_ops<BbRing>::lincomb(c->bb->p, coef, tables, n_terms, len, out) : ring_ops<GoldRing>::lincomb(c, coef, tables, n_terms, len, out);
 }
 // calculate_challenged_mz_mle (nifs/folding.rs:208-226) and the f-hat half of prepare_g1_and_3_k_mles_list (folding/utils.rs:524-546):
 // out[x] = sum_{i<groups} sum_{j<per_group} c_i^{j+1} T_{i,j}[x] (the reference's Horner loop `mle += M; mle *= c_i` over j reversed)
 int lf_horner_combine(lf_ctx *c, const uint64_t *tables, size_t groups, size_t per_group, size_t len, const uint64_t *challenges, uint64_t *out) {
     if (LF_XB(c) && tables && challenges && out) { XB x(c); int rc = lf_horner_combine(c, x.ring_in(tables, groups * per_group * len), groups, per_group, len, x.ext_in(challenges, groups), out); if (rc == LF_OK) x.ring_out(out, len); return rc; }
     if (!c || !tables || !challenges || !out || !groups || !per_group || !len) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->horner_combine(tables, groups, per_group, len, challenges, out);
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    const size_t nt = groups * per_group;
-    u64 *X, *o;
-    RET(c->tbuf("io_a", nt * len * 24, &X));
-    RET(c->tbuf("io_b", len * 24, &o));
-    for (size_t i = 0; i < nt; i++) RET(up_ring(c, tables + i * len * 24, len, X + i * 24 * len));
-    std::vector<Fq3Const> cf(nt);
-    for (size_t i = 0; i < groups; i++) {
-        Fq3 ci = fq3_make(challenges[3 * i], challenges[3 * i + 1], challenges[3 * i + 2]), pw = ci;
-        for (size_t j = 0; j < per_group; j++) { cf[i * per_group + j] = f3c(pw); pw = c->ring.mul3(pw, ci); }
-    }
-    Fq3Const *d_cf;
-    RET(upload_consts(c, "lc_coef", cf, &d_cf));
-    launch_lincomb_z(c->dcrt, X, len, (u32)nt, d_cf, 1, len, o, c->stream(), 0);
-    return down_ring(c, o, len, out);
+    return c->bb ? ring_ops<BbRing>::horner_combine(c->bb->p, tables, groups, per_group, len, challenges, out)
+                 : ring_ops<GoldRing>::horner_combine(c, tables, groups, per_group, len, challenges, out);
 }
 

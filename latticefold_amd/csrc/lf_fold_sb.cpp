@@ -1,12 +1,8 @@
 // lf_fold_sb.cpp -- the folding prover (nifs/folding.rs:74-179) on the small-base path, b = 4, 8, 16 (lf_sb.h): the sumcheck of nifs/folding/utils.rs:273-325 at
 // degree 2b over the norm polynomial f prod_{j=1}^{b-1} (f^2 - j^2), theta / eta, and the fold of the witnesses from their digit planes.  One lane, ordinary
 // launches, one host hop per round: round 1 reads the digit planes (f-hat virtual), r_1 materialises the m/2-entry tables, later rounds fix them ping-pong.
-#include "lf_ctx.h"
+#include "lf_ring_host.h"
 
-static int sb_upload_consts(lf_ctx *c, const std::string &name, const std::vector<Fq3Const> &v, Fq3Const **out) {
-    RET(c->tbuf(name, v.size() + 8, out));
-    return c->h2d_small(*out, v.data(), v.size() * sizeof(Fq3Const));
-}
 
 // One round message from its two device halves: `norm` [X][24] at X = 0 .. 2b (launch_sb_round) and `g` [X][24] at X = 0 .. 4 (launch_fold_round_g).  The G
 // part eqL G1 + eqR G2 has degree 2: its values at X >= 3 follow from those at 0, 1, 2 by the vanishing third difference -- exact field arithmetic, the words
@@ -74,9 +70,9 @@ int fold_impl_sb(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_o
         for (u32 j = 0; j < P.t; j++) { z_pow[(size_t)i * P.t + j] = f3c(pz); pz = c->ring.mul3(pz, zeta[i]); }
     }
     Fq3Const *d_mu, *d_ap, *d_zp;
-    RET(sb_upload_consts(c, "c_ap", a_pow, &d_ap));
-    RET(sb_upload_consts(c, "c_zp", z_pow, &d_zp));
-    RET(sb_upload_consts(c, "c_mu", mu_pow, &d_mu));
+    RET(upload_consts(c, "c_ap", a_pow, &d_ap));
+    RET(upload_consts(c, "c_zp", z_pow, &d_zp));
+    RET(upload_consts(c, "c_mu", mu_pow, &d_mu));
     u64 *G[2], *eqb, *zz, *partial, *partial_g, *od;
     RET(c->tbuf("fold_G1", 24 * m, &G[0]));
     RET(c->tbuf("fold_G2", 24 * m, &G[1]));

@@ -4,7 +4,7 @@
 //
 // Host <-> device traffic inside a fold step is O(proof size): per sumcheck round (D+1) ring elements come back
 // and one F_{p^3} challenge goes down; everything of size N stays in HBM.
-#include "lf_ctx.h"
+#include "lf_ring_host.h"
 
 // =================================================================================================================================
 // the driver
@@ -729,7 +729,7 @@ int lf_fold_step(lf_ctx *c, lf_transcript *t, const uint64_t *acc, const lf_witn
     size_t tot = c->ev_begin(17);
     Transcript &tr = t->t;
     size_t ll = lf_lcccs_len(&P);
-    u64 *lin_proof = proof, *decl = lin_proof + lin_proof_len(&P) * 24, *decr = decl + dec_proof_len(&P) * 24, *foldp = decr + dec_proof_len(&P) * 24;
+    u64 *lin_proof = proof, *decl = lin_proof + lin_proof_len(&P, 3) * 24, *decr = decl + dec_proof_len(&P, 3) * 24, *foldp = decr + dec_proof_len(&P, 3) * 24;
     std::vector<u64> lin(ll * 24);
     u64 *eq_r_R = nullptr;
     SideState S[2];

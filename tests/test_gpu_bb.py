@@ -524,3 +524,47 @@ def test_fold_step_with_several_public_inputs(ctx):
     assert (acc_g == acc_o).all() and (proof_g == proof_o).all() and (lc_g == lc_o).all() and (w0.f == f0_o).all()
     ok, lc_p, _ = api.NIFSVerifier.verify(wl, acc_g, cccs, proof_g, tr_new())
     assert ok and (lc_p == lc_g).all()
+
+
+# ---- behaviour that sits around the ring dispatch of the shared host bodies ---------------------------------------
+def test_witness_bound_edges(ctx):
+    """|coefficient| <= B/2 is the ingest's bound on this ring as on Goldilocks: B/2 - 1 and -B/2 pass and come back unchanged, -B/2 - 1 is LF_ERR_NORM"""
+    wl, inst, A, scheme = setup_case(ctx, "B6")
+    f_coeff = inst.witness_from_w_ccs(wl.w_ccs)
+    half = wl.B // 2
+    bad = f_coeff.copy(); bad[0, 0] = half; bad[1, 0] = P - (half + 1)
+    with pytest.raises(api.LfError) as e:
+        api.Witness.from_f_coeff(ctx, bad)
+    print("from_f_coeff(B/2, -B/2-1) ->", e.value.code)
+    assert e.value.code == -5                       # LF_ERR_NORM
+    ok = f_coeff.copy(); ok[0, 0] = half - 1; ok[1, 0] = P - half
+    assert (api.Witness.from_f_coeff(ctx, ok).f_coeff == ok).all()
+
+
+@pytest.mark.parametrize("ring,name", [("goldilocks", "T8"), ("babybear", "B6")])
+def test_error_codes_around_dispatch(ring, name):
+    """the code a caller gets for an invalid input does not depend on the ring (checks before the dispatch, checks inside the shared bodies)"""
+    import ctypes as C
+    c = api.Context(0, ring=ring)
+    try:
+        codes = {}
+        def code(key, fn):
+            try:
+                fn()
+                codes[key] = 0
+            except api.LfError as e:
+                codes[key] = e.code
+        x = splitmix_fq(1, 0, 4 * c.RE, ring).reshape(4, c.RE)
+        code("decompose base 6", lambda: c.decompose(x, 6, 2, 0))
+        code("decompose digits 0", lambda: c.decompose(x, 2, 0, 0))
+        code("evaluate_mles len 2^nv + 1", lambda: c.evaluate_mles(splitmix_fq(2, 0, 9 * c.RE, ring).reshape(1, 9, c.RE), splitmix_fq(3, 0, 3 * c.TAU, ring).reshape(3, c.TAU)))
+        z1 = np.zeros((1, c.RE), dtype=np.uint64)
+        codes["mat_vec_mul before load_ccs"] = api._lib().lf_spmv(c.h, 0, z1.ctypes.data_as(api.u64p), z1.ctypes.data_as(api.u64p))
+        wl = make_workload(name)
+        c.load_ccs(wl)
+        code("mat_vec_mul j = t", lambda: c.mat_vec_mul(wl.t, wl.z()))
+        print(ring, codes)
+        assert codes == {"decompose base 6": -3, "decompose digits 0": -1, "evaluate_mles len 2^nv + 1": -1,
+                         "mat_vec_mul before load_ccs": -7, "mat_vec_mul j = t": -1}
+    finally:
+        c.close()
