@@ -99,16 +99,17 @@ __device__ __forceinline__ u64 splitmix_bb(u64 seed, u64 index) {
     z = z ^ (z >> 31);
     return (z >> 32) % BB_P;
 }
-__global__ void __launch_bounds__(256) k_fill_ajtai(fe *A, u32 kappa, size_t n, size_t n_total, size_t col0, u64 seed) {
+__global__ void __launch_bounds__(256) k_fill_ajtai(fe *A, u32 kappa, size_t n, size_t n_total, size_t col0, u64 seed, u32 row0) {
     size_t total = (size_t)kappa * RE * n;
     size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, st = (size_t)gridDim.x * 256;
     for (; i < total; i += st) {
-        size_t j = i % n, w = (i / n) % RE, row = i / (RE * n);
+        size_t j = i % n, w = (i / n) % RE, row = row0 + i / (RE * n);
         A[i] = from_canon(splitmix_bb(seed, (row * n_total + col0 + j) * RE + w));
     }
 }
-void launch_fill_ajtai(fe *A, u32 kappa, size_t n, size_t n_total, size_t col0, u64 seed, hipStream_t s) {
-    hipLaunchKernelGGL(k_fill_ajtai, dim3(4096), dim3(256), 0, s, A, kappa, n, n_total, col0, seed);
+// rows [row0, row0 + kappa) of the synthetic matrix into A [kappa][72][n]
+void launch_fill_ajtai(fe *A, u32 kappa, size_t n, size_t n_total, size_t col0, u64 seed, hipStream_t s, u32 row0) {
+    hipLaunchKernelGGL(k_fill_ajtai, dim3(4096), dim3(256), 0, s, A, kappa, n, n_total, col0, seed, row0);
 }
 // arithmetic self-test: in[i] = (a[9], b[9]) canonical; out[i] = (a*b [9], a0+b0, a0-b0, a0*b0) canonical.
 // The host recomputes with plain % arithmetic (bb_host.cpp) and compares.

@@ -480,7 +480,7 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
     {
         // G = sum_j M_j (sum_k zeta_k^{j+1} z_k)  +  sum_k sum_d alpha_k^{d+1} fhat_{k,d}   (folding.rs:208-226, utils.rs:524-546): the two sides are
         // independent chains -- the right one runs on the other (idle) stream, as in the Goldilocks driver
-        hipStream_t s0 = c->stream(), s1 = (c->lane == 0 && c->sh_world == 1) ? c->st_lane[1] : s0;
+        hipStream_t s0 = c->stream(), s1 = (c->cur_lane == 0 && c->sh_world == 1) ? c->st_lane[1] : s0;
         fe *zz1 = zz;
         if (s1 != s0) {
             RET(c->tbuf("fold_zz1", (size_t)P.t * RE * n, &zz1));
@@ -695,7 +695,7 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
             i64 *gpartial;
             RET(c->tbuf("sv_gpartial", red_partial_words(5 * RE), &gpartial));
             // the G part (eqL G1 + eqR G2: the round kernel without tables) on the other, idle stream next to the GEMM chain
-            hipStream_t sg = (c->lane == 0 && c->st_lane[1]) ? c->st_lane[1] : c->stream();
+            hipStream_t sg = (c->cur_lane == 0 && c->st_lane[1]) ? c->st_lane[1] : c->stream();
             hipEvent_t g_ready = nullptr;
             if (sg != c->stream()) {
                 for (int e = 0; e < 2; e++)
@@ -823,7 +823,7 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
     RET(c->tbuf("dec_small", 16 * RE * TAU + 16 * 4 * RE, &sm));
     RET(build_eq_dev(c, pt.data(), P.s, eq0));
     // the other stream is idle here: every second q_j = M_j^T eq(r_o) is gathered there, and the eta products of the right side run there (as in the Goldilocks driver)
-    hipStream_t s1f = (c->lane == 0 && c->sh_world == 1 && c->st_lane[1]) ? c->st_lane[1] : c->stream();
+    hipStream_t s1f = (c->cur_lane == 0 && c->sh_world == 1 && c->st_lane[1]) ? c->st_lane[1] : c->stream();
     if (s1f != c->stream()) {
         for (int e = 0; e < 2; e++)
             if (!c->ev_prep[e]) HIPCHK(hipEventCreateWithFlags(&c->ev_prep[e], hipEventDisableTiming));
@@ -986,7 +986,7 @@ int BbCtx::fold_step(BbTranscript &tr, const uint64_t *acc, const lf_witness *w_
                      uint64_t *lcccs_out, lf_witness **w_out, uint64_t *proof) {
     C *c = p;
     std::lock_guard<std::mutex> g(c->mu);
-    if (!c->have_ccs || !c->dAb) return LF_ERR_STATE;
+    if (!c->have_ccs || !c->A_loaded) return LF_ERR_STATE;
     const lf_params &P = c->P;
     if (c->kappa != P.kappa || c->nA_total != c->N || w_acc->N != c->N || w_i->N != c->N) return LF_ERR_INVALID;
     HIPCHK(hipSetDevice(c->device));
@@ -1008,7 +1008,7 @@ int BbCtx::fold_step(BbTranscript &tr, const uint64_t *acc, const lf_witness *w_
     c->arena_used[0] = c->arena_used[1] = 0;
     DecPending pdL, pdR;
     pdL.side = 0; pdR.side = 1;
-    c->lane = 1;
+    c->cur_lane = 1;
     g_marks.start();
     // (LF_BB_EVALS_FIRST=1: the left evaluations before the left commit -- the two large linearization rounds then run next to them instead of next to a commit)
     int rc = LF_OK;
@@ -1018,7 +1018,7 @@ int BbCtx::fold_step(BbTranscript &tr, const uint64_t *acc, const lf_witness *w_
     BB_MARK("L1: left evals enqueued");
     if (rc == LF_OK) rc = dec_enqueue_commit(c, w_i, pdR);
     BB_MARK("L1: right commit enqueued");
-    c->lane = 0;
+    c->cur_lane = 0;
     c->lin_blocks = 0;
     {   // absorb_public_input (nifs.rs:175-197) -- while the GPU already works on the left decomposition
         HostTimer ht(c);
@@ -1056,7 +1056,7 @@ int BbCtx::fold_step(BbTranscript &tr, const uint64_t *acc, const lf_witness *w_
 int BbCtx::decomposition_prove(BbTranscript &tr, const uint64_t *lcccs, const lf_witness *wit, uint64_t *lcccs_s_out, uint64_t *dec_proof_out) {
     C *c = p;
     std::lock_guard<std::mutex> g(c->mu);
-    if (!c->have_ccs || !c->dAb) return LF_ERR_STATE;
+    if (!c->have_ccs || !c->A_loaded) return LF_ERR_STATE;
     const lf_params &P = c->P;
     if (c->kappa != P.kappa || c->nA_total != c->N || wit->N != c->N) return LF_ERR_INVALID;
     HIPCHK(hipSetDevice(c->device));
@@ -1066,7 +1066,7 @@ int BbCtx::decomposition_prove(BbTranscript &tr, const uint64_t *lcccs, const lf
     c->ev_reset();
     c->host_tr_ms = 0;
     c->arena_used[0] = c->arena_used[1] = 0;
-    c->lane = 0;
+    c->cur_lane = 0;
     DecPending pd;
     pd.side = 0;
     SideState S;
@@ -1091,7 +1091,7 @@ int BbCtx::folding_prove(BbTranscript &tr, const uint64_t *lcccs_s, const lf_wit
     c->ev_reset();
     c->host_tr_ms = 0;
     c->arena_used[0] = c->arena_used[1] = 0;
-    c->lane = 0;
+    c->cur_lane = 0;
     const size_t ll = lcccs_len(&P, TAU);
     const u32 K = P.K, hl = P.l + 1;
     SideState S[2];
@@ -1116,143 +1116,6 @@ int BbCtx::folding_prove(BbTranscript &tr, const uint64_t *lcccs_s, const lf_wit
     int rc = fold_impl(c, tr, S, lcccs_out, w_out, fold_proof_out);
     c->ev_collect();
     return rc;
-}
-
-// ---- generic linearization-shaped sumcheck through the ABI -----------------------------------------------------------------------
-int BbCtx::sumcheck_lin_begin(const uint64_t *tables, const uint64_t *eq_point) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->have_ccs) return LF_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    const lf_params &P = c->P;
-    size_t m = c->m;
-    fe *mz, *eqb;
-    RET(c->tbuf("sc_tab0", (size_t)P.t * RE * m, &mz));
-    RET(c->tbuf("sc_eq0", TAU * m, &eqb));
-    for (u32 j = 0; j < P.t; j++) RET(up_ring(c, tables + (size_t)j * m * RE, m, mz + (size_t)j * RE * m));
-    std::vector<H9> pt(P.s);
-    for (u32 i = 0; i < P.s; i++) pt[i] = h9_load(eq_point + (size_t)TAU * i);
-    RET(build_eq_dev(c, pt.data(), P.s, eqb));
-    c->sc_round = 0; c->sc_n = m; c->sc_cur = 0;
-    return LF_OK;
-}
-int BbCtx::sumcheck_lin_round(const uint64_t *r_prev, uint64_t *evals_out) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    if (c->sc_round < 0 || c->sc_round >= (int)c->P.s) return LF_ERR_STATE;
-    if ((c->sc_round == 0) != (r_prev == nullptr)) return LF_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    const lf_params &P = c->P;
-    size_t m = c->m;
-    fe *tab[2], *eq[2];
-    i64 *partial;
-    u64 *od;
-    RET(c->tbuf("sc_tab0", (size_t)P.t * RE * m, &tab[0]));
-    RET(c->tbuf("sc_tab1", (size_t)P.t * RE * atl(m / 2), &tab[1]));
-    RET(c->tbuf("sc_eq0", TAU * m, &eq[0]));
-    RET(c->tbuf("sc_eq1", TAU * atl(m / 2), &eq[1]));
-    RET(c->tbuf("round_partial", red_partial_words(5 * RE), &partial));
-    RET(c->tbuf("round_out", 5 * RE, &od));
-    if (r_prev) {
-        E9PreC r = e9pre_from_h9(h9_load(r_prev), c->ring.T.nu);
-        int src = c->sc_cur, dst = src ^ 1;
-        size_t ldi = c->sc_n == m ? m : atl(c->sc_n);
-        launch_fix(c->dev, tab[src], ldi, tab[dst], atl(c->sc_n / 2), c->sc_n, P.t * 8, r, c->stream());
-        launch_fix(c->dev, eq[src], ldi, eq[dst], atl(c->sc_n / 2), c->sc_n, 1, r, c->stream());
-        c->sc_cur = dst; c->sc_n /= 2;
-    }
-    size_t ld = c->sc_n == m ? m : atl(c->sc_n);
-    launch_lin_round(c->dev, c->desc, tab[c->sc_cur], ld, eq[c->sc_cur], ld, c->sc_n, P.d + 1, partial, od, c->stream());
-    c->sc_round++;
-    return down_small(c, od, (size_t)(P.d + 2) * RE, evals_out);
-}
-// ---- the folding sumcheck through the ABI (see lf_sumcheck_fold_* in lf_capi.cpp / include/lfhip.h) -----------------------------
-int BbCtx::sumcheck_fold_begin(const uint64_t *tables, const uint64_t *mu) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->have_ccs) return LF_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    const lf_params &P = c->P;
-    const size_t m = c->m;
-    if (m < 2) return LF_ERR_UNSUPPORTED;
-    const u32 K2 = 2 * P.K;
-    static const int eq_idx[3] = {0, 2, 4};
-    for (int e = 0; e < 3; e++) {
-        const u64 *tb = tables + (size_t)eq_idx[e] * m * RE;
-        for (size_t i = 0; i < m; i++)
-            for (int sl = 1; sl < 8; sl++)
-                if (memcmp(tb + i * RE, tb + i * RE + TAU * sl, TAU * 8) != 0) return LF_ERR_UNSUPPORTED;
-    }
-    const size_t T5P = 3 * TAU + 2 * RE;
-    fe *T, *F, *tmp;
-    RET(c->tbuf("sf_T0", T5P * m, &T));
-    RET(c->tbuf("sf_F0", (size_t)K2 * TAU * RE * m, &F));
-    RET(c->tbuf("sf_tmp", RE * m, &tmp));
-    for (int e = 0; e < 3; e++) {
-        RET(up_ring(c, tables + (size_t)eq_idx[e] * m * RE, m, tmp));
-        HIPCHK(hipMemcpyAsync(T + (size_t)TAU * e * m, tmp, TAU * m * sizeof(fe), hipMemcpyDeviceToDevice, c->stream()));
-        HIPCHK(hipStreamSynchronize(c->stream()));
-    }
-    RET(up_ring(c, tables + (size_t)1 * m * RE, m, T + (size_t)3 * TAU * m));
-    RET(up_ring(c, tables + (size_t)3 * m * RE, m, T + (size_t)(3 * TAU + RE) * m));
-    for (u32 i = 0; i < K2 * TAU; i++) RET(up_ring(c, tables + (size_t)(5 + i) * m * RE, m, F + (size_t)i * RE * m));
-    std::vector<E9PreC> mu_pre((size_t)K2 * TAU);
-    for (u32 i = 0; i < K2; i++) {
-        H9 mi = h9_load(mu + (size_t)TAU * i), pm = mi;
-        for (u32 d = 0; d < (u32)TAU; d++) { mu_pre[(size_t)i * TAU + d] = e9pre_from_h9(pm, c->ring.T.nu); pm = c->ring.mul9(pm, mi); }
-    }
-    E9PreC *d_mup;
-    RET(upload_consts(c, "sf_mup", mu_pre, &d_mup));
-    c->sf_round = 0; c->sf_n = m; c->sf_cur = 0;
-    return LF_OK;
-}
-int BbCtx::sumcheck_fold_round(const uint64_t *r_prev, uint64_t *evals_out) {
-    C *c = p;
-    std::lock_guard<std::mutex> g(c->mu);
-    if (c->sf_round < 0 || c->sf_round >= (int)c->P.s) return LF_ERR_STATE;
-    if ((c->sf_round == 0) != (r_prev == nullptr)) return LF_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    const lf_params &P = c->P;
-    const size_t m = c->m;
-    const u32 K2 = 2 * P.K;
-    const size_t T5P = 3 * TAU + 2 * RE;
-    fe *T[2], *F[2];
-    i64 *partial;
-    u64 *od;
-    E9PreC *d_mup;
-    RET(c->tbuf("sf_T0", T5P * m, &T[0]));
-    RET(c->tbuf("sf_T1", T5P * atl(m / 2), &T[1]));
-    RET(c->tbuf("sf_F0", (size_t)K2 * TAU * RE * m, &F[0]));
-    RET(c->tbuf("sf_F1", (size_t)K2 * TAU * RE * atl(m / 2), &F[1]));
-    RET(c->tbuf("sf_mup", (size_t)K2 * TAU + 8, &d_mup));
-    RET(c->tbuf("round_partial", fold_partial_words(m), &partial));
-    RET(c->tbuf("round_out", 5 * RE, &od));
-    if (r_prev) {
-        E9PreC r = e9pre_from_h9(h9_load(r_prev), c->ring.T.nu);
-        int src = c->sf_cur, dst = src ^ 1;
-        size_t ldi = c->sf_n == m ? m : atl(c->sf_n), ldo = atl(c->sf_n / 2);
-        launch_fix(c->dev, T[src], ldi, T[dst], ldo, c->sf_n, 19, r, c->stream());
-        launch_fix(c->dev, F[src], ldi, F[dst], ldo, c->sf_n, K2 * TAU * 8, r, c->stream());
-        c->sf_cur = dst; c->sf_n /= 2;
-    }
-    const size_t n = c->sf_n, ld = n == m ? m : atl(n);
-    const fe *t5 = T[c->sf_cur];
-    FoldArgs a;
-    a.eqL = t5; a.eqR = t5 + (size_t)TAU * ld; a.eqB = t5 + (size_t)2 * TAU * ld; a.G1 = t5 + (size_t)3 * TAU * ld; a.G2 = t5 + (size_t)(3 * TAU + RE) * ld;
-    a.ld = ld; a.n = n; a.p0 = 0; a.pcnt = n / 2; a.pF0 = 0;
-    launch_fold_round(c->dev, a, F[c->sf_cur], ld, P.K, d_mup, partial, od, c->stream());
-    c->sf_round++;
-    return down_small(c, od, (size_t)(2 * P.b + 1) * RE, evals_out);
-}
-int BbCtx::sumcheck_fold_end() {
-    std::lock_guard<std::mutex> g(p->mu);
-    p->sf_round = -1;
-    return LF_OK;
-}
-int BbCtx::sumcheck_lin_end() {
-    std::lock_guard<std::mutex> g(p->mu);
-    p->sc_round = -1;
-    return LF_OK;
 }
 
 }  // namespace lfbb

@@ -25,30 +25,7 @@ static int install_tables(lf_ctx *c, u64 nonres, const u64 *y) {
     if (build_crt_tables(nonres, y, T) != 0) return LF_ERR_BAD_TABLES;
     c->ring.T = T;
     c->dcrt = make_dev_crt(T);
-    if (!c->d_icrt) HIPCHK(lf_dev_malloc(&c->d_icrt, 576 * 8));
-    HIPCHK(hipMemcpy(c->d_icrt, &T.icrt[0][0], 576 * 8, hipMemcpyHostToDevice));
-    // compressed rows for the digit pass of the general commitment (lf_ajtai_i8g.hip k_i8g_cut_ntt): the shipped tables have one entry per slot
-    u64 sv[24 * 8];
-    u32 sc[24 * 8];
-    bool sparse = true;
-    for (int r = 0; r < 24 && sparse; r++) {
-        int q = 0;
-        for (int col = 0; col < 24; col++)
-            if (T.icrt[r][col]) {
-                if (q == 8) { sparse = false; break; }
-                sv[r * 8 + q] = T.icrt[r][col]; sc[r * 8 + q] = (u32)col; q++;
-            }
-        for (; q < 8; q++) { sv[r * 8 + q] = 0; sc[r * 8 + q] = 0xFFFFFFFFu; }
-    }
-    if (sparse) {
-        if (!c->d_icrt_sp_val) { HIPCHK(lf_dev_malloc(&c->d_icrt_sp_val, sizeof(sv))); HIPCHK(lf_dev_malloc(&c->d_icrt_sp_col, sizeof(sc))); }
-        HIPCHK(hipMemcpy(c->d_icrt_sp_val, sv, sizeof(sv), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(c->d_icrt_sp_col, sc, sizeof(sc), hipMemcpyHostToDevice));
-    } else if (c->d_icrt_sp_val) {
-        (void)hipFree(c->d_icrt_sp_val); (void)hipFree(c->d_icrt_sp_col);
-        c->d_icrt_sp_val = nullptr; c->d_icrt_sp_col = nullptr;
-    }
-    return LF_OK;
+    return ring_ops<GoldRing>::install_icrt(c, &T.icrt[0][0]);
 }
 
 int lf_ctx_create_ring(lf_ctx **out, int device, int ring) {
@@ -74,16 +51,9 @@ int lf_ctx_create(lf_ctx **out, int device) {
     HIPCHK(hipSetDevice(device));
     lf_ctx *c = new lf_ctx();
     c->device = device;
-    {   // lane 1 carries the critical chain of a fold step (two commits back to back); its kernels get dispatch priority over
-        // lane 0's latency-bound linearization, which has slack (LF_NO_PRIO=1: equal priorities)
-        int least = 0, greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        const bool prio = true;
-        const int p0 = least;
-        if (hipStreamCreateWithPriority(&c->st_lane[0], hipStreamDefault, prio ? p0 : 0) != hipSuccess ||
-            hipStreamCreateWithPriority(&c->st_lane[1], hipStreamDefault, prio ? greatest : 0) != hipSuccess ||
-            hipStreamCreateWithPriority(&c->st_io, hipStreamDefault, least) != hipSuccess) { delete c; return LF_ERR_HIP; }
-    }
+    int least = 0, greatest = 0;
+    (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+    if (c->create_lane_streams() != LF_OK || hipStreamCreateWithPriority(&c->st_io, hipStreamDefault, least) != hipSuccess) { delete c; return LF_ERR_HIP; }
     (void)hipEventCreateWithFlags(&c->ev_block, hipEventBlockingSync | hipEventDisableTiming);
     u64 nr, y[24];
     default_ring(&nr, y);
@@ -92,16 +62,6 @@ int lf_ctx_create(lf_ctx **out, int device) {
     *out = c;
     return LF_OK;
 }
-static void free_ccs(lf_ctx *c) {
-    for (auto p : c->d_rowptr) (void)hipFree(p);
-    for (auto p : c->d_col) (void)hipFree(p);
-    for (auto p : c->d_val) (void)hipFree(p);
-    for (auto p : c->d_colptr) (void)hipFree(p);
-    for (auto p : c->d_rowidx) (void)hipFree(p);
-    for (auto p : c->d_valT) (void)hipFree(p);
-    c->d_rowptr.clear(); c->d_col.clear(); c->d_val.clear(); c->d_colptr.clear(); c->d_rowidx.clear(); c->d_valT.clear();
-    c->have_ccs = false;
-}
 static void planes_pool_drop(int device);
 void lf_ctx_destroy(lf_ctx *c) {
     if (!c) return;
@@ -109,21 +69,11 @@ void lf_ctx_destroy(lf_ctx *c) {
     (void)hipSetDevice(c->device);
     planes_pool_drop(c->device);
     if (c->bb) { c->bb->destroy(); delete c; return; }
-    (void)hipStreamSynchronize(c->st_lane[0]);
-    (void)hipStreamSynchronize(c->st_lane[1]);
+    (void)c->sync_lanes();
     if (c->st_io) (void)hipStreamSynchronize(c->st_io);
-    free_ccs(c);
-    for (auto &kv : c->bufs) kv.second.release();
-    if (c->dAb) (void)hipFree(c->dAb);
-    for (int l = 0; l < LF_NLANES; l++) if (c->stage[l]) (void)hipHostFree(c->stage[l]);
-    if (c->d_icrt) (void)hipFree(c->d_icrt);
-    if (c->d_icrt_sp_val) { (void)hipFree(c->d_icrt_sp_val); (void)hipFree(c->d_icrt_sp_col); }
     for (int l = 0; l < LF_NLANES; l++)
-        if (c->h_pin_lane[l]) (void)hipHostFree(c->h_pin_lane[l]);
+        if (c->stage[l]) (void)hipHostFree(c->stage[l]);
     if (c->h_pin2) { (void)hipHostFree(c->h_pin2); c->h_pin2 = nullptr; }
-    for (auto &e : c->ev_pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    for (int l = 0; l < LF_NLANES; l++)
-        if (c->h_round[l]) (void)hipHostFree(c->h_round[l]);
     if (c->ev_block) (void)hipEventDestroy(c->ev_block);
     c->comm[0].destroy();
     c->comm[1].destroy();
@@ -134,13 +84,9 @@ void lf_ctx_destroy(lf_ctx *c) {
     if (c->ev_aux) (void)hipEventDestroy(c->ev_aux);
     if (c->st_aux) (void)hipStreamDestroy(c->st_aux);
     if (c->h_aux) (void)hipHostFree(c->h_aux);
-    for (int i = 0; i < 2; i++) {
-        if (c->ev_prep[i]) (void)hipEventDestroy(c->ev_prep[i]);
+    for (int i = 0; i < 2; i++)
         if (c->bits_ev[i]) (void)hipEventDestroy(c->bits_ev[i]);
-    }
-    (void)hipStreamDestroy(c->st_lane[0]);
-    (void)hipStreamDestroy(c->st_lane[1]);
-    if (c->st_io) (void)hipStreamDestroy(c->st_io);
+    c->release_core();   // buffers, matrix, constraint system, per-lane pinned memory, the event pool and the three lanes' streams
     delete c;
 }
 int lf_set_ring_tables(lf_ctx *c, uint64_t nonres, const uint64_t *y) {
@@ -166,8 +112,7 @@ int lf_get_ring_tables(lf_ctx *c, uint64_t *nonres, uint64_t *y) {
 int lf_set_digit_mode(lf_ctx *c, int mode) {
     if (!c || (mode != 0 && mode != 1)) return LF_ERR_INVALID;
     std::lock_guard<std::mutex> g(c->mu);
-    c->digit_mode = mode;
-    if (c->bb) c->bb->set_digit_mode(mode);
+    c->core_any().digit_mode = mode;
     return LF_OK;
 }
 int lf_set_ext_basis(lf_ctx *c, const uint64_t *T) {
@@ -348,7 +293,7 @@ int lf_set_sharding_lanes(lf_ctx *c, int rank, int world, lf_exchange_fn cb0, vo
 }
 int lf_dist_stats(lf_ctx *c, uint64_t *n_exchanges, double *total_us, double *max_us, int reset) {
     if (!c) return LF_ERR_INVALID;
-    lfdist::Comm *ms[2] = {c->bb ? c->bb->comm() : &c->comm[0], c->bb ? nullptr : &c->comm[1]};
+    lfdist::Comm *ms[2] = {c->bb ? &c->bb->p->comm : &c->comm[0], c->bb ? nullptr : &c->comm[1]};
     uint64_t n = 0;
     double tot = 0, mx = 0;
     for (auto *m : ms)
@@ -363,15 +308,14 @@ int lf_dist_stats(lf_ctx *c, uint64_t *n_exchanges, double *total_us, double *ma
 }
 int lf_mem_info(lf_ctx *c, size_t *free_bytes, size_t *total_bytes) {
     if (!c || !free_bytes || !total_bytes) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->mem_info(free_bytes, total_bytes);
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemGetInfo(free_bytes, total_bytes));
     return LF_OK;
 }
 int lf_device_synchronize(lf_ctx *c) {
     if (!c) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->synchronize();
     HIPCHK(hipSetDevice(c->device));
+    if (c->bb) return c->bb->p->sync_lanes();
     HIPCHK(hipStreamSynchronize(c->stream()));
     return LF_OK;
 }
@@ -424,120 +368,14 @@ int lf_linf_check(lf_ctx *c, const uint64_t *f_ntt, size_t count, uint64_t bound
 }
 
 // ---- a5 -----------------------------------------------------------------------------------------------------------
-static int shard_columns(lf_ctx *c, size_t n, size_t *col0, size_t *cnt) {
-    if (n % (size_t)c->sh_world) return LF_ERR_UNSUPPORTED;
-    *cnt = n / c->sh_world;
-    *col0 = *cnt * c->sh_rank;
-    return LF_OK;
-}
-// A lives on the device in ONE form: coefficient form, cut into bytes, in MFMA operand order (lf_ajtai_i8.hip) -- what the digit-plane commitments of a fold
-// step (k_ajtai_i8s) and the general commitments (lf_ajtai_i8g.hip: commit_ntt, Witness::commit) both stream.  Built once per matrix: rows arrive one at a time
-// in NTT form (row_ntt [24][nA] on the device), one fused pass -- inverse CRT map + byte packing -- per row, so the context never holds more than one u64 row.
-// (Rounds 2-5 also kept the NTT form, 4.9 GiB at C4, for a 64-bit VALU commit kernel; the int8 general commit retired both.)
-static int prep_ajtai_i8_begin(lf_ctx *c) {
-    if (c->dAb) { (void)hipFree(c->dAb); c->dAb = nullptr; }
-    c->i8_nch = 0;
-    const AjtaiI8Ring R = ajtai_i8_goldilocks();
-    const u32 maxr = ajtai_i8_max_rows(R), nch = (c->kappa + maxr - 1) / maxr, kc = (c->kappa + nch - 1) / nch;
-    const size_t ntiles = (c->nA + 7) / 8;
-    const u32 MT = ajtai_i8_row_tiles(R, kc);
-    const size_t chunk_bytes = ntiles * (R.RD / 8) * MT * 1024;
-    HIPCHK(lf_dev_malloc(&c->dAb, chunk_bytes * nch + ajtai_i8_slack_bytes()));
-    HIPCHK(hipMemsetAsync(c->dAb, 0, chunk_bytes * nch + ajtai_i8_slack_bytes(), c->stream()));
-    c->i8_nch = nch;
-    c->i8_kc = kc;
-    return LF_OK;
-}
-static void prep_ajtai_i8_row(lf_ctx *c, u32 i, const u64 *row_ntt) {
-    const AjtaiI8Ring R = ajtai_i8_goldilocks();
-    const u32 kc = c->i8_kc, MT = ajtai_i8_row_tiles(R, kc);
-    const size_t chunk_bytes = (c->nA + 7) / 8 * (R.RD / 8) * MT * 1024;
-    launch_ajtai_icrt_pack_i8(c->d_icrt, row_ntt, c->nA, i % kc, MT, c->dAb + (size_t)(i / kc) * chunk_bytes, c->stream());
-}
-static int ajtai_install(lf_ctx *c, size_t kappa, size_t n, const uint64_t *A_host, uint64_t seed) {
-    size_t col0, cnt;
-    RET(shard_columns(c, n, &col0, &cnt));   // a sharded rank keeps only its column slice of the caller's matrix
-    c->A_loaded = false;
-    c->kappa = (u32)kappa;
-    c->nA = cnt; c->nA_total = n; c->A_col0 = col0;
-    RET(prep_ajtai_i8_begin(c));
-    u64 *row = nullptr;
-    RET(c->tbuf("i8_prep_row", 24 * cnt, &row));
-    for (size_t i = 0; i < kappa; i++) {
-        if (A_host) RET(up_ring(c, A_host + (i * n + col0) * 24, cnt, row));
-        else launch_fill_ajtai(row, 1, cnt, n, col0, seed, c->stream(), (u32)i);
-        prep_ajtai_i8_row(c, (u32)i, row);
-    }
-    HIPCHK(hipStreamSynchronize(c->stream()));
-    c->drop_buf("i8_prep_row");
-    c->drop_buf("stage_aos");
-    c->A_loaded = true;
-    return LF_OK;
-}
-// digit planes k0 .. k0+NP-1 of `planes` (this rank's column slice) -> out_dev [NP][kappa][24] NTT form (PARTIAL when sharded)
-// wit (optional): the witness `planes` belong to -- if its bit-plane form is at hand (built at the start of the fold step for the GEMM rounds) the
-// kernel cuts the digits from it
-int commit_planes_i8(lf_ctx *c, const int32_t *planes, size_t ld, u32 k0, u32 NP, u64 *out_dev, const lf_witness *wit) {
-    const AjtaiI8Ring R = ajtai_i8_goldilocks();
-    const u32 nch = c->i8_nch, kc = c->i8_kc, MT = ajtai_i8_row_tiles(R, kc), maxp = ajtai_i8_max_planes(R);
-    const size_t ntiles = (c->nA + 7) / 8, chunk_bytes = ntiles * (R.RD / 8) * MT * 1024;
-    // One persistent workgroup per CU fills its LDS (157 KB): on a fully occupied chip the latency-bound round kernels of the other lane
-    // cannot be placed until a commit workgroup retires.  7/8 of the CUs (28 of 32 per XCD) leaves them room: C4 26.1 -> 25.0 ms/step
-    // (measured 256 / 240 / 224 / 192 / 160 / 128 workgroups: 26.1 / 26.3 / 25.0 / 25.1 / 26.1 / 28.2 ms).
-    u32 nwg = c->tn.i8_wgs > 0 ? (u32)c->tn.i8_wgs : 224;
-    if (nwg > ntiles) nwg = (u32)ntiles;
-    const u32 nslots = nwg < 16 ? 16 : nwg;    // (two plane groups run as 2 x 8 chunks at least: launch_ajtai_i8)
-    int32_t *part, *dsum;
-    long long *sum;
-    u64 *coef, *ntt;
-    const u32 NTmax = ajtai_i8_col_tiles(R, maxp);
-    RET(c->tbuf("i8_part", ajtai_i8_part_words(nslots, MT, NTmax), &part));
-    RET(c->tbuf("i8_dsum", (size_t)nslots * maxp * R.RD, &dsum));
-    RET(c->tbuf("i8_sum", ajtai_i8_sum_words(R, MT, NTmax, maxp), &sum));
-    const size_t side_words = (size_t)24 * NP * c->kappa;
-    RET(c->tbuf("i8_coef", side_words, &coef));
-    RET(c->tbuf("i8_ntt", side_words, &ntt));
-    const u32 *bits = nullptr;
-    if (wit && c->A_col0 == 0 && planes == wit->planes && c->nA == c->N)
-        for (int sd = 0; sd < 2; sd++)
-            if (c->bits_wit[sd] == wit && c->bits_ptr[sd]) {
-                bits = c->bits_ptr[sd];
-                if (c->stream() != c->st_lane[1]) HIPCHK(hipStreamWaitEvent(c->stream(), c->bits_ev[sd], 0));
-                break;
-            }
-    const size_t bits_nw = (c->N + 511) / 512 * 16;          // words per row of the bit-plane form (positions padded to 512)
-    const u32 bits_rows = 16 * ((c->P.K + 15) / 16) + 1;
-    for (u32 p0 = 0; p0 < NP; p0 += maxp) {
-        const u32 np = NP - p0 < maxp ? NP - p0 : maxp;
-        u64 *cf = coef + (size_t)24 * p0 * c->kappa;   // SoA block of this plane group: [24][np*kappa]
-        for (u32 ch = 0; ch < nch; ch++) {
-            const u32 row0 = ch * kc, kn = c->kappa - row0 < kc ? c->kappa - row0 : kc;
-            size_t ev = c->ev_begin(1);
-            int g = launch_ajtai_i8(R, c->dAb + (size_t)ch * chunk_bytes, MT, planes, ld, c->nA, kn, row0, c->kappa, k0 + p0, np, nwg, part, dsum, sum, cf, c->stream(),
-                                    bits, bits_nw, bits_rows);
-            c->ev_end(ev);
-            if (g < 0) return LF_ERR_UNSUPPORTED;
-        }
-        const size_t ne = (size_t)np * c->kappa;
-        launch_crt_fwd(c->dcrt, cf, ntt, ne, c->stream());
-        launch_soa_to_aos(ntt, out_dev + (size_t)p0 * c->kappa * 24, ne, c->stream());
-    }
-    return LF_OK;
-}
 int lf_ajtai_load(lf_ctx *c, const uint64_t *A, size_t kappa, size_t n) {
     if (LF_XB(c) && A && kappa <= 128) { XB x(c); return lf_ajtai_load(c, x.ring_in(A, kappa * n), kappa, n); }
     if (!c || !A || !kappa || !n || kappa > 128) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->ajtai_load(A, kappa, n);
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    return ajtai_install(c, kappa, n, A, 0);
+    return c->bb ? ring_ops<BbRing>::ajtai_install(c->bb->p, kappa, n, A, 0) : ring_ops<GoldRing>::ajtai_install(c, kappa, n, A, 0);
 }
 int lf_ajtai_generate(lf_ctx *c, uint64_t seed, size_t kappa, size_t n) {
     if (!c || !kappa || !n || kappa > 128) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->ajtai_generate(seed, kappa, n);
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    return ajtai_install(c, kappa, n, nullptr, seed);
+    return c->bb ? ring_ops<BbRing>::ajtai_install(c->bb->p, kappa, n, nullptr, seed) : ring_ops<GoldRing>::ajtai_install(c, kappa, n, nullptr, seed);
 }
 int lf_device_memory(lf_ctx *c, size_t *free_bytes, size_t *total_bytes) {
     if (!c || !free_bytes || !total_bytes) return LF_ERR_INVALID;
@@ -588,8 +426,6 @@ int sb_cut_parts(lf_ctx *c, const lf_witness *wit, const char *name, const unsig
     *D = d;
     return LF_OK;
 }
-// F: [batch][24][ldF] device, pointing at this rank's first column; out_dev: [batch][kappa][24] device AoS (PARTIAL when sharded)
-static int commit_dev(lf_ctx *c, const u64 *F, size_t ldF, u32 batch, u64 *out_dev, bool timed) { return commit_dev_i8g(c, F, ldF, batch, nullptr, 0, out_dev, timed); }
 // download a (partial) commitment and, when sharded, all-gather + add the partials mod p
 int commit_download(lf_ctx *c, const u64 *dev, size_t words, u64 *host) {
     RET(exchange_modsum_dev(c, (u64 *)dev, words));   // sharded: ncclAllGather of the partial commitments + k_modsum, in stream
@@ -651,60 +487,19 @@ int gather_parts(lf_ctx *c, const GatherPart *parts, int np, size_t lcl) {
 int lf_ajtai_commit(lf_ctx *c, const uint64_t *f, size_t n, size_t batch, uint64_t *out) {
     if (LF_XB(c) && f && out) {
         XB x(c);
-        u32 kap = c->bb ? 0 : c->kappa;
         int rc = lf_ajtai_commit(c, x.ring_in(f, n * batch), n, batch, out);
-        if (rc == LF_OK) x.ring_out(out, batch * (c->bb ? c->bb->kappa() : kap));
+        if (rc == LF_OK) x.ring_out(out, batch * c->core_any().kappa);
         return rc;
     }
     if (!c || !f || !out || !batch) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->ajtai_commit(f, n, batch, out);
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->A_loaded) return LF_ERR_STATE;
-    if (n != c->nA_total) return LF_ERR_INVALID;  // CommitmentError::WrongWitnessLength(n, width)
-    HIPCHK(hipSetDevice(c->device));
-    u64 *F, *o;
-    RET(c->tbuf("io_a", batch * n * 24, &F));
-    RET(c->tbuf("io_b", batch * c->kappa * 24, &o));
-    for (size_t b = 0; b < batch; b++) RET(up_ring(c, f + b * n * 24, n, F + b * 24 * n));
-    c->tn = Tunables::read((size_t)1 << 14);
-    c->ev_reset();
-    RET(commit_dev(c, F + c->A_col0, n, (u32)batch, o, true));   // timed: lf_last_kernel_stats reports the stand-alone kernel
-    c->ev_collect();
-    return commit_download(c, o, batch * c->kappa * 24, out);
-}
-// commit_coeff / decompose_and_commit_{coeff,ntt} (commitment_scheme.rs:81-113): element i of f [batch][count] (coefficient form, or NTT form: ntt_in)
-// becomes columns [i L, (i + 1) L) of the committed vector, its balanced base-2^lb digits (lb 0, L 1: the element itself).  The count x L vector is never
-// built: the gadget digit pass (lf_i8g_dec.cuh) writes the commit kernel's operand words from the coefficient table, as few planes as the base needs.
-// NTT-form input is inverse-CRT-ed into one coefficient table first (one pass over count elements; the fused form of k_i8g_cut_ntt would map 32 elements
-// = 32 L columns per block -- DESIGN.md, k_ajtai_i8g row).
-static int ajtai_commit_gadget(lf_ctx *c, const uint64_t *f, bool ntt_in, size_t count, u32 lb, u32 L, size_t batch, uint64_t *out) {
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->A_loaded) return LF_ERR_STATE;
-    if (count > c->nA_total || count * L != c->nA_total) return LF_ERR_INVALID;   // CommitmentError::WrongWitnessLength
-    HIPCHK(hipSetDevice(c->device));
-    u64 *F, *X = nullptr, *o;
-    RET(c->tbuf("io_a", batch * count * 24, &F));
-    if (ntt_in) RET(c->tbuf("io_c", count * 24, &X));
-    RET(c->tbuf("io_b", batch * c->kappa * 24, &o));
-    for (size_t b = 0; b < batch; b++) RET(up_ring(c, f + b * count * 24, count, F + b * 24 * count));
-    c->tn = Tunables::read((size_t)1 << 14);
-    c->ev_reset();
-    const AjtaiI8Ring R = ajtai_i8_goldilocks();
-    const u32 NP = lb ? ajtai_i8g_planes_base(R, 1ull << lb) : ajtai_i8g_planes_general(R);
-    RET(commit_dev_pre(c, NP, (u32)batch, o, true, [&](u32 b, unsigned long long *pre, size_t ntiles) {   // timed: the ICRT, digit pass and contraction
-        const u64 *src = F + (size_t)b * 24 * count;
-        if (ntt_in) { launch_icrt_dense(c->d_icrt, src, X, count, c->stream()); src = X; }
-        launch_i8g_cut_dec(src, count, c->A_col0, c->nA, L, lb, c->digit_mode, NP, pre, ntiles, c->stream());
-    }));
-    c->ev_collect();
-    return commit_download(c, o, batch * c->kappa * 24, out);
+    return c->bb ? ring_ops<BbRing>::ajtai_commit(c->bb->p, f, n, batch, out) : ring_ops<GoldRing>::ajtai_commit(c, f, n, batch, out);
 }
 // The ABI side of the three (dec false: commit_coeff, no decomposition): arguments are checked before any device work; in an external basis the commitments
 // leave converted and NTT-form input is converted on the way in, coefficient-form input is not (as lf_witness_from_f_coeff).
 static int ajtai_commit_gadget_api(lf_ctx *c, const uint64_t *f, bool ntt_in, size_t count, bool dec, uint64_t base, unsigned digits, size_t batch, uint64_t *out) {
     if (LF_XB(c) && f && out) {
         XB x(c);
-        const u32 kap = c->bb ? c->bb->kappa() : c->kappa;
+        const u32 kap = c->core_any().kappa;
         int rc = ajtai_commit_gadget_api(c, ntt_in ? x.ring_in(f, count * batch) : f, ntt_in, count, dec, base, digits, batch, out);
         if (rc == LF_OK) x.ring_out(out, batch * kap);
         return rc;
@@ -715,8 +510,8 @@ static int ajtai_commit_gadget_api(lf_ctx *c, const uint64_t *f, bool ntt_in, si
         if (!pow2(base) || (c->bb && base > (1ull << 32))) return LF_ERR_UNSUPPORTED;
         while ((1ull << lb) < base) lb++;
     }
-    if (c->bb) return c->bb->ajtai_commit_gadget(f, ntt_in, count, lb, digits, batch, out);
-    return ajtai_commit_gadget(c, f, ntt_in, count, lb, digits, batch, out);
+    return c->bb ? ring_ops<BbRing>::ajtai_commit_gadget(c->bb->p, f, ntt_in, count, lb, digits, batch, out)
+                 : ring_ops<GoldRing>::ajtai_commit_gadget(c, f, ntt_in, count, lb, digits, batch, out);
 }
 int lf_ajtai_commit_coeff(lf_ctx *c, const uint64_t *f_coeff, size_t n, size_t batch, uint64_t *out) {
     return ajtai_commit_gadget_api(c, f_coeff, false, n, false, 0, 1, batch, out);
@@ -810,7 +605,7 @@ int lf_ccs_load(lf_ctx *c, const lf_params *p, const uint32_t *const *rowptr, co
         return lf_ccs_load(c, p, rowptr, col, v2, S_off, S_idx, x.ring_in(cc, p->q));
     }
     if (!c || !p || !rowptr || !col || !val || !S_off || !S_idx || !cc) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->ccs_load(p, rowptr, col, val, S_off, S_idx, cc);
+    if (c->bb) { RET(lfbb::ccs_envelope(p)); return ring_ops<BbRing>::ccs_load(c->bb->p, p, rowptr, col, val, S_off, S_idx, cc); }
     if (p->s < 3 || p->s > 30 || p->t == 0 || p->t > 8 || p->q == 0 || p->q > 8 || p->K == 0 || p->K > 32 || p->L == 0 || p->L > 8 ||
         p->d > 7 || p->wit_len == 0)
         return LF_ERR_UNSUPPORTED;
@@ -824,76 +619,7 @@ int lf_ccs_load(lf_ctx *c, const lf_params *p, const uint32_t *const *rowptr, co
     if (!pow2(p->B) || p->B > (1ULL << 32)) return LF_ERR_UNSUPPORTED;
     // K base-b digits must cover |coeff| <= B/2 under the active digit rule (checked again where a step starts: the rule may change after the load)
     if (!sb_digits_cover(p->b, p->K, p->B, c->digit_mode)) return LF_ERR_UNSUPPORTED;
-    size_t m = (size_t)1 << p->s, N = (size_t)p->wit_len * p->L, n = (size_t)p->l + 1 + p->wit_len;
-    if (N > m) return LF_ERR_SIZE_BOUNDS;  // sanity_check, nifs.rs:165-173
-    // the reference indexes comb values by matrix index: multisets must concatenate to 0..t-1
-    {
-        u32 next = 0;
-        for (u32 i = 0; i < p->q; i++)
-            for (u32 k = S_off[i]; k < S_off[i + 1]; k++)
-                if (S_idx[k] != next++) return LF_ERR_UNSUPPORTED;
-        if (next != p->t || S_off[p->q] > 16) return LF_ERR_UNSUPPORTED;
-    }
-    RET(lf_validate_csr(p->t, m, n, rowptr, col, val, 24, LF_P));   // before any context state is touched
-    for (size_t k = 0; k < (size_t)p->q * 24; k++)
-        if (cc[k] >= LF_P) return LF_ERR_INVALID;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    free_ccs(c);
-    c->P = *p; c->N = N; c->m = m; c->n = n;
-    memset(&c->desc, 0, sizeof(c->desc));
-    c->desc.t = p->t; c->desc.q = p->q;
-    for (u32 i = 0; i <= p->q; i++) c->desc.S_off[i] = S_off[i];
-    for (u32 k = 0; k < S_off[p->q]; k++) c->desc.S_idx[k] = S_idx[k];
-    for (u32 i = 0; i < p->q; i++)
-        for (u32 k = S_off[i]; k < S_off[i + 1]; k++) { c->desc.ms[k] = i; c->desc.first[k] = (k == S_off[i]); }
-    for (u32 i = 0; i < p->q; i++) {
-        memcpy(c->desc.c[i], cc + (size_t)i * 24, 24 * 8);
-        u64 one[24], mone[24];
-        HostRing::from_u64(1, one);
-        HostRing::from_u64(LF_P - 1, mone);
-        c->desc.c_unit[i] = !memcmp(c->desc.c[i], one, sizeof(one)) ? 1 : (!memcmp(c->desc.c[i], mone, sizeof(mone)) ? -1 : 0);
-    }
-    // every device array is registered in the context as soon as it exists, so a failure half-way leaks nothing (free_ccs frees them)
-    auto dalloc = [](auto &vec, size_t bytes) -> void * {
-        void *ptr = nullptr;
-        if (lf_dev_malloc(&ptr, bytes) != hipSuccess) return nullptr;
-        vec.push_back((typename std::remove_reference<decltype(vec)>::type::value_type)ptr);
-        return ptr;
-    };
-    for (u32 j = 0; j < p->t; j++) {
-        size_t nnz = rowptr[j][m];
-        void *drp = dalloc(c->d_rowptr, (m + 1) * 4), *dci = dalloc(c->d_col, (nnz + 1) * 4), *dv = dalloc(c->d_val, (nnz + 1) * 24 * 8);
-        void *dcp = dalloc(c->d_colptr, (n + 1) * 4), *dri = dalloc(c->d_rowidx, (nnz + 1) * 4), *dvT = dalloc(c->d_valT, (nnz + 1) * 24 * 8);
-        if (!drp || !dci || !dv || !dcp || !dri || !dvT) return LF_ERR_HIP;
-        HIPCHK(hipMemcpy(drp, rowptr[j], (m + 1) * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dci, col[j], nnz * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dv, val[j], nnz * 24 * 8, hipMemcpyHostToDevice));
-        // CSC
-        std::vector<u32> cp(n + 1, 0), ri(nnz);
-        std::vector<u64> vT(nnz * 24);
-        for (size_t k = 0; k < nnz; k++) cp[col[j][k] + 1]++;
-        for (size_t i = 0; i < n; i++) cp[i + 1] += cp[i];
-        std::vector<u32> fill(cp.begin(), cp.end() - 1);
-        for (size_t r = 0; r < m; r++)
-            for (u32 k = rowptr[j][r]; k < rowptr[j][r + 1]; k++) {
-                u32 pos = fill[col[j][k]]++;
-                ri[pos] = (u32)r;
-                memcpy(&vT[(size_t)pos * 24], val[j] + (size_t)k * 24, 24 * 8);
-            }
-        HIPCHK(hipMemcpy(dcp, cp.data(), (n + 1) * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dri, ri.data(), nnz * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dvT, vT.data(), nnz * 24 * 8, hipMemcpyHostToDevice));
-    }
-    {
-        const size_t rows_used = n < m ? n : m;
-        c->ccs_general = false;
-        for (u32 jj = 0; jj < p->t; jj++)
-            if ((size_t)rowptr[jj][m] * 2 > rows_used * 3) c->ccs_general = true;
-    }
-    c->have_ccs = true;
-    c->shc_r0 = (size_t)-1;
-    return LF_OK;
+    return ring_ops<GoldRing>::ccs_load(c, p, rowptr, col, val, S_off, S_idx, cc);
 }
 int lf_spmv(lf_ctx *c, unsigned j, const uint64_t *z, uint64_t *out) {
     if (LF_XB(c) && z && out && c->have_ccs_any()) { XB x(c); int rc = lf_spmv(c, j, x.ring_in(z, c->n_any()), out); if (rc == LF_OK) x.ring_out(out, c->m_any()); return rc; }
@@ -962,7 +688,7 @@ int lf_witness_get_w_ccs(lf_ctx *c, const lf_witness *w, uint64_t *out) {
     return c->bb ? ring_ops<BbRing>::witness_get_w_ccs(c->bb->p, w, out) : ring_ops<GoldRing>::witness_get_w_ccs(c, w, out);
 }
 int lf_witness_commit(lf_ctx *c, const lf_witness *w, uint64_t *cm_out) {
-    if (LF_XB(c) && w && cm_out) { XB x(c); int rc = lf_witness_commit(c, w, cm_out); if (rc == LF_OK) x.ring_out(cm_out, c->bb ? c->bb->kappa() : c->kappa); return rc; }
+    if (LF_XB(c) && w && cm_out) { XB x(c); int rc = lf_witness_commit(c, w, cm_out); if (rc == LF_OK) x.ring_out(cm_out, c->core_any().kappa); return rc; }
     if (!c || !w || !cm_out || w->ctx != c) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::witness_commit(c->bb->p, w, cm_out) : ring_ops<GoldRing>::witness_commit(c, w, cm_out);
 }
@@ -1080,8 +806,7 @@ void lf_poseidon_params_ring(uint64_t *ark, uint64_t *mds, int ring) {
 
 int lf_last_phase_ms(lf_ctx *c, float *out) {
     if (!c || !out) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->last_phase_ms(out);
-    for (int i = 0; i < LF_N_PHASES; i++) out[i] = c->phase_ms[i];
+    for (int i = 0; i < LF_N_PHASES; i++) out[i] = c->core_any().phase_ms[i];
     return LF_OK;
 }
 // wall-clock marks of the caller thread during the last lf_fold_step (Goldilocks driver): name i (NUL-terminated, at most 31 characters) at
@@ -1112,12 +837,12 @@ extern "C" int lfdbg_i8g_wg(unsigned int *out512) { return out512 ? ajtai_i8g_re
 extern "C" unsigned lfdbg_i8g_planes_base(int ring, uint64_t base) { return ajtai_i8g_planes_base(ring == LF_RING_BABYBEAR ? ajtai_i8_babybear() : ajtai_i8_goldilocks(), base); }
 int lf_last_fold_paths(lf_ctx *c, unsigned *sv_round_mask) {
     if (!c || !sv_round_mask) return LF_ERR_INVALID;
-    *sv_round_mask = c->bb ? c->bb->fold_paths() : c->sv_round_mask;
+    *sv_round_mask = c->core_any().sv_round_mask;
     return LF_OK;
 }
 int lf_last_fold_split_rounds(lf_ctx *c, unsigned *round_mask) {
     if (!c || !round_mask) return LF_ERR_INVALID;
-    *round_mask = c->bb ? c->bb->fold_split_rounds() : c->fold_split_mask;
+    *round_mask = c->core_any().fold_split_mask;
     return LF_OK;
 }
 int lf_last_lin_split_rounds(lf_ctx *c, unsigned *rounds) {
@@ -1127,11 +852,11 @@ int lf_last_lin_split_rounds(lf_ctx *c, unsigned *rounds) {
 }
 int lf_last_kernel_stats(lf_ctx *c, float *fold_ms, int *fold_n, float *aj_ms, int *aj_n) {
     if (!c) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->last_kernel_stats(fold_ms, fold_n, aj_ms, aj_n);
-    if (fold_ms) *fold_ms = c->k_fold_ms;
-    if (fold_n) *fold_n = c->k_fold_n;
-    if (aj_ms) *aj_ms = c->k_ajtai_ms;
-    if (aj_n) *aj_n = c->k_ajtai_n;
+    const CtxCoreBase &k = c->core_any();
+    if (fold_ms) *fold_ms = k.k_fold_ms;
+    if (fold_n) *fold_n = k.k_fold_n;
+    if (aj_ms) *aj_ms = k.k_ajtai_ms;
+    if (aj_n) *aj_n = k.k_ajtai_n;
     return LF_OK;
 }
 

@@ -53,7 +53,7 @@ static int check_state(C *c, const lf_witness *wit, bool need_A) {
     if (!c->have_ccs) return LF_ERR_STATE;
     if (c->sh_world > 1) return LF_ERR_UNSUPPORTED;   // sharded deciding is not implemented
     if (wit && wit->N != c->N) return LF_ERR_INVALID;
-    if (need_A && !Ring<C>::have_A(c)) return LF_ERR_STATE;
+    if (need_A && !c->A_loaded) return LF_ERR_STATE;
     if (need_A && c->nA_total != c->N) return LF_ERR_INVALID;   // CommitmentError::WrongWitnessLength
     return LF_OK;
 }

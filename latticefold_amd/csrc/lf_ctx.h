@@ -2,6 +2,7 @@
 // timeline, resident matrices and tables), the transcript handle and the helpers the three translation units share.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <assert.h>
 #include <string.h>
 
 #include <atomic>
@@ -18,6 +19,7 @@
 
 #include "../../include/lfhip.h"
 #include "bb_capi.h"
+#include "lf_ctx_core.h"
 #include "lf_common.h"
 #include "lf_dist.h"
 #include "lf_kernels.h"
@@ -42,8 +44,7 @@ static bool lf_trace_on() { static int v = -1; if (v < 0) v = getenv("LF_TRACE")
         }                                                                             \
     } while (0)
 
-inline thread_local int t_lane = 0;  // 0 = caller thread, 1 = helper thread running the left decomposition
-constexpr int LF_NLANES = 2;
+inline thread_local int t_lane = 0;  // 0 = caller thread, 1 = helper thread running the left decomposition, 2 = ingestion worker (LF_NLANES: lf_ctx_core.h)
 
 struct lf_transcript {
     Transcript t;
@@ -79,8 +80,6 @@ inline thread_local Timeline *t_tl = nullptr;
 
 static const char *PHASE_NAMES[LF_N_PHASES] = {"linearization", "decomp_crt_commit", "decomp_evals", "fold_prepare",
                                                 "fold_sumcheck", "fold_finish", "host_transcript", "total"};
-
-struct EvPair { hipEvent_t a, b; };
 
 // The helper lane of a fold step: ONE thread per context, created at the first step and parked on a condition variable between steps
 // (a std::async thread per step cost a thread creation + join every 7-30 ms).
@@ -129,85 +128,41 @@ struct LaneWorker {
     }
 };
 
-struct lf_ctx {
+struct lf_ctx : CtxCore<u64> {
+    lf_ctx() : CtxCore<u64>(8192, 2 * 9 * 24 * sizeof(u64)) {}   // round_out: two messages of up to 9 evaluations x 24 words: the wide linearization round writes
+                                                                  // d + 2 <= 9 (k_reduce_rows of launch_lin_round_wide), the fold rounds write their G part at word 120
+    int lane() const override { return t_lane; }
     lfbb::BbCtx *bb = nullptr;   // BabyBearRingNTT backend (ring 1): every entry point forwards to it
-    int device = 0;
-    hipStream_t st_lane[LF_NLANES] = {nullptr, nullptr};
-    int digit_mode = 0;   // balanced-digit rule of base-B decompositions (lf_set_digit_mode)
     ExtBasis xb;          // external coordinate basis of F_{p^tau} (lf_set_ext_basis); identity by default
-    Tunables tn;          // environment switches, re-read at the start of every lf_linearize / lf_fold_step
-    u32 lin_blocks = 0;   // grid bound of the linearization rounds while a fold step's commit chain runs on the other lane (0 = none)
-    std::mutex mu, buf_mu, ev_mu;
-    hipStream_t st_io = nullptr;   // lane 2: witness ingestion next to a running fold step (lf_witness_from_w_ccs_begin), lowest priority; own buffers ("lane2:" names)
+    hipStream_t &st_io = st_lane[2];   // lane 2: witness ingestion next to a running fold step (lf_witness_from_w_ccs_begin), lowest priority; own buffers ("lane2:" names)
     std::mutex io_mu;              // one ingestion at a time per context
     std::atomic<int> io_jobs{0};   // ingestion jobs whose worker has not finished (lf_ctx_destroy waits for them)
-    hipStream_t stream() const { return t_lane == 2 ? st_io : st_lane[t_lane]; }
-    // the same facts for either backend (the external-basis marshalling is ring-agnostic)
-    bool have_ccs_any() const { return bb ? bb->have_ccs() : have_ccs; }
-    const lf_params &params_any() const { return bb ? bb->params() : P; }
-    size_t n_any() const { return bb ? bb->dim_n() : n; }
-    size_t m_any() const { return bb ? bb->dim_m() : m; }
-    size_t N_any() const { return bb ? bb->dim_N() : N; }
+    // the core of whichever backend this handle drives (the external-basis marshalling and the read-outs are ring-agnostic)
+    inline CtxCoreBase &core_any();
+    bool have_ccs_any() { return core_any().have_ccs; }
+    const lf_params &params_any() { return core_any().P; }
+    size_t n_any() { return core_any().n; }
+    size_t m_any() { return core_any().m; }
+    size_t N_any() { return core_any().N; }
     HostRing ring;
     DevCrt dcrt;
-    u64 *d_icrt = nullptr;
-    u64 *d_icrt_sp_val = nullptr;   // the rows of the inverse CRT map in compressed form ([24][8] values / columns), null when a row has more than 8 entries
-    u32 *d_icrt_sp_col = nullptr;
-    // Ajtai (nA = columns held by this rank, starting at global column A_col0 of nA_total)
     LaneWorker lane1;
-    bool A_loaded = false;
-    unsigned char *dAb = nullptr;   // the matrix in coefficient form, bytes in int8-MFMA operand order (lf_ajtai_i8.hip); row chunks of <= 26
-    u32 i8_nch = 0, i8_kc = 0;
-    u32 kappa = 0;
-    size_t nA = 0, nA_total = 0, A_col0 = 0;
-    // intra-step sharding: rank/world and the all-gather callback supplied by the host language
-    int sh_rank = 0, sh_world = 1;   // mirror comm.rank / comm.world
     int agreed_two_lanes = -1;       // lf_dist_init's handshake: the schedule ALL ranks agreed on (1 threaded / 0 one thread); -1 = no handshake ran (host transports, model)
     bool two_lanes_ok = false;       // the transport's two channels have been seen working concurrently (lf_dist_init's handshake; two host callbacks): a sharded
                                      // step then runs the threaded two-lane schedule unless LF_SHARD_TWO_LANES=0
-    // exchange layer, one per lane: the two lanes of a fold step exchange concurrently (lane 0: linearization rounds and right evaluations,
-    // lane 1: commits and left evaluations) and collectives of ONE communicator must be issued in the same order on every rank
+    // exchange layer, one per prover lane: the two lanes of a fold step exchange concurrently (lane 0: linearization rounds and right evaluations,
+    // lane 1: commits and left evaluations) and collectives of ONE communicator must be issued in the same order on every rank.  Lane 2 never exchanges
     lfdist::Comm comm[2];
-    lfdist::Comm &cm() { return comm[t_lane]; }
-    // CCS
-    bool have_ccs = false;
+    lfdist::Comm &cm() { assert(t_lane < 2); return comm[t_lane]; }
     bool ccs_general = false;   // some constraint matrix has more than ~1.5 entries per (non-empty) row: M z runs on k_spmv_rows (whole-element gathers from an element-major z)
     // sharded step: the columns of z this rank's row slice of the constraint matrices refers to (shard_col_range; (size_t)-1 = not computed)
     size_t shc_r0 = (size_t)-1, shc_rcnt = 0, shc_lo = 0, shc_hi = 0;
-    lf_params P{};
-    size_t N = 0, m = 0, n = 0;
-    std::vector<u32 *> d_rowptr, d_col, d_colptr, d_rowidx;
-    std::vector<u64 *> d_val, d_valT;
     LinCombDesc desc{};
-    std::map<std::string, DevBuf> bufs;
-    u64 *h_pin_lane[LF_NLANES] = {nullptr, nullptr};
-    size_t h_pin_words_lane[LF_NLANES] = {0, 0};
-    // lin sumcheck ABI state
-    int sc_round = -1;
-    size_t sc_n = 0;
-    int sc_cur = 0;
-    int sf_round = -1;   // folding-sumcheck ABI state (lf_sumcheck_fold_*)
-    size_t sf_n = 0;
-    int sf_cur = 0;
-    // measurement
-    float phase_ms[LF_N_PHASES] = {0};
     std::vector<std::pair<const char *, double>> tl_marks;   // wall-clock marks of the last fold step (lf_last_timeline)
-    std::vector<EvPair> ev_pool;
-    size_t ev_used = 0;
-    std::vector<std::pair<int, size_t>> ev_tags;  // (tag, event index)
-    float k_fold_ms = 0, k_ajtai_ms = 0;
-    int k_fold_n = 0, k_ajtai_n = 0;
-    double host_tr_ms = 0;
-    // v_s of the linearized instance computed inside the linearization (v = sum_k 2^k v_s[k]); reused by the right decomposition of the same step
-    const lf_witness *vs_wit = nullptr;
-    bool vs_keep = false;            // set by the fold step around its linearization: only there the decomposition that follows uses the same point
-    const u64 *vs_eq = nullptr;
-    u64 *vs_dev = nullptr;
     // bit-plane forms of the two witnesses of the running fold step (lf_sv_rounds.h), enqueued on the helper lane's stream before anything else
     const lf_witness *bits_wit[2] = {nullptr, nullptr};
     u32 *bits_ptr[2] = {nullptr, nullptr};
     hipEvent_t bits_ev[2] = {nullptr, nullptr};
-    hipEvent_t ev_prep[2] = {nullptr, nullptr};   // fold prepare: fork / join of the right side's chain on the helper lane's stream
     hipEvent_t ev_yR = nullptr, ev_yL = nullptr;  // the right / left commit's results are in h_pin2 (second / first half)
     u64 *h_pin2 = nullptr;
     size_t h_pin2_words = 0;
@@ -223,38 +178,12 @@ struct lf_ctx {
     hipStream_t st_aux = nullptr;
     hipEvent_t ev_aux = nullptr;
     u64 *h_aux = nullptr;   // pinned, 1 KB: the known part of the point
-    unsigned sv_round_mask = 0;      // rounds of the last folding sumcheck that ran as int8 GEMMs (bit i-1 = round i)
-    unsigned fold_split_mask = 0;    // table rounds of the last folding sumcheck that ran in the split eq form (bit i-1 = round i)
     unsigned lin_split_rounds = 0;   // rounds of the last linearization sumcheck that ran in the split eq form (run_lin_sumcheck)
 
-
-    int buf(const std::string &name, size_t bytes, void **out) {
-        DevBuf *b;
-        {
-            std::lock_guard<std::mutex> g(buf_mu);
-            b = &bufs[t_lane ? (t_lane == 1 ? "lane1:" : "lane2:") + name : name];  // std::map nodes are stable
-        }
-        int rc = b->ensure(bytes);
-        *out = b->p;
-        return rc;
-    }
-    // give a set-up scratch buffer back (caller has synchronised the stream that used it)
-    void drop_buf(const std::string &name) {
-        std::lock_guard<std::mutex> g(buf_mu);
-        auto it = bufs.find(t_lane ? (t_lane == 1 ? "lane1:" : "lane2:") + name : name);
-        if (it != bufs.end()) { it->second.release(); bufs.erase(it); }
-    }
-    template <class T>
-    int tbuf(const std::string &name, size_t count, T **out) {
-        void *p;
-        int rc = buf(name, count * sizeof(T), &p);
-        *out = (T *)p;
-        return rc;
-    }
     // Small host-to-device uploads inside a step (challenge powers, look-up tables, evaluation points) go through a pinned ring per lane:
     // the copy is truly asynchronous and the caller's stack / vector buffer is free at once -- no stream synchronisation per upload.
-    unsigned char *stage[LF_NLANES] = {nullptr, nullptr};
-    size_t stage_off[LF_NLANES] = {0, 0};
+    unsigned char *stage[LF_NLANES] = {nullptr, nullptr, nullptr};
+    size_t stage_off[LF_NLANES] = {0, 0, 0};
     static constexpr size_t STAGE_BYTES = (size_t)1 << 20;
     int h2d_small(void *dst, const void *src, size_t bytes) {
         unsigned char *&ring = stage[t_lane];
@@ -274,14 +203,6 @@ struct lf_ctx {
         memcpy(slot, src, bytes);
         HIPCHK(hipMemcpyAsync(dst, slot, bytes, hipMemcpyHostToDevice, stream()));
         return LF_OK;
-    }
-    u64 *h_round[LF_NLANES] = {nullptr, nullptr};   // pinned + device-mapped: sumcheck round kernels write their message straight to the host
-    u64 *round_out() {
-        u64 *&p = h_round[t_lane];
-        // two messages of up to 9 evaluations x 24 words: the wide linearization round writes d + 2 <= 9 (k_reduce_rows of launch_lin_round_wide), the fold
-        // rounds write their G part at word 120 behind the norm part
-        if (!p && hipHostMalloc((void **)&p, 2 * 9 * 24 * sizeof(u64), hipHostMallocMapped) != hipSuccess) p = nullptr;
-        return p;
     }
     // persistent sumcheck tail (k_fold_tail): host-mapped mailbox + device scratch, created on first use
     TailMail *tail_mail = nullptr;
@@ -324,57 +245,8 @@ struct lf_ctx {
         HIPCHK(hipStreamSynchronize(stream()));
         return LF_OK;
     }
-    u64 *&h_pin_ref() { return h_pin_lane[t_lane]; }
-    int pin(size_t words) {
-        u64 *&hp = h_pin_lane[t_lane];
-        size_t &hw = h_pin_words_lane[t_lane];
-        if (words <= hw) return LF_OK;
-        if (hp) (void)hipHostFree(hp);
-        hp = nullptr;
-        if (words < 8192) words = 8192;
-        if (hipHostMalloc((void **)&hp, words * 8) != hipSuccess) return LF_ERR_HIP;
-        hw = words;
-        return LF_OK;
-    }
-    // timed-launch helpers: tag 0 = fold round kernels, 1 = ajtai, 10+i = phase i
-    size_t ev_begin(int tag) {
-        std::lock_guard<std::mutex> g(ev_mu);
-        if (ev_used == ev_pool.size()) {
-            EvPair e;
-            (void)hipEventCreate(&e.a);
-            (void)hipEventCreate(&e.b);
-            ev_pool.push_back(e);
-        }
-        size_t i = ev_used++;
-        (void)hipEventRecord(ev_pool[i].a, stream());
-        ev_tags.push_back({tag, i});
-        return i;
-    }
-    void ev_end(size_t i) {
-        if (i == (size_t)-1) return;
-        std::lock_guard<std::mutex> g(ev_mu);
-        (void)hipEventRecord(ev_pool[i].b, stream());
-    }
-    void ev_reset() {
-        ev_used = 0;
-        ev_tags.clear();
-    }
-    void ev_collect() {
-        (void)hipStreamSynchronize(st_lane[0]);
-        (void)hipStreamSynchronize(st_lane[1]);
-        k_fold_ms = k_ajtai_ms = 0;
-        k_fold_n = k_ajtai_n = 0;
-        for (int i = 0; i < LF_N_PHASES; i++) phase_ms[i] = 0;
-        for (auto &tg : ev_tags) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, ev_pool[tg.second].a, ev_pool[tg.second].b);
-            if (tg.first == 0) { k_fold_ms += ms; k_fold_n++; }
-            else if (tg.first == 1) { k_ajtai_ms += ms; k_ajtai_n++; }
-            else if (tg.first >= 10 && tg.first < 10 + LF_N_PHASES) phase_ms[tg.first - 10] += ms;
-        }
-        phase_ms[6] = (float)host_tr_ms;
-    }
 };
+inline CtxCoreBase &lf_ctx::core_any() { return bb ? bb->core() : *this; }
 
 
 // ---- shared between lf_capi.cpp / lf_prove.cpp / lf_fold.cpp (hidden: not part of the ABI) -------------------------------------------------------
@@ -386,12 +258,6 @@ int exchange_modsum_dev(lf_ctx *c, u64 *inout_dev, size_t words);
 int down_small(lf_ctx *c, const u64 *dsrc, size_t words, u64 *host);
 void shard_slice(const lf_ctx *c, size_t n, size_t *i0, size_t *cnt);
 struct GatherPart { const u64 *src; size_t src_ld; u64 *dst; size_t planes; };
-struct HostTimer {
-    lf_ctx *c;
-    std::chrono::steady_clock::time_point t0;
-    explicit HostTimer(lf_ctx *cc) : c(cc), t0(std::chrono::steady_clock::now()) {}
-    ~HostTimer() { c->host_tr_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-};
 int shard_col_range(lf_ctx *c, size_t r0, size_t rcnt, size_t *lo, size_t *hi);
 Fq3 sc_round_transcript(Transcript &tr, const u64 *evals, u32 npts);
 void sc_prologue(Transcript &tr, u32 nv, u32 deg);
@@ -443,7 +309,6 @@ struct XB {
 };
 #define LF_XB(c) ((c) && (c)->xb.on && !t_xb_active)
 int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out, lf_witness **w_out, u64 *proof);
-int commit_planes_i8(lf_ctx *c, const int32_t *planes, size_t ld, u32 k0, u32 NP, u64 *out_dev, const lf_witness *wit = nullptr);
 int commit_download(lf_ctx *c, const u64 *dev, size_t words, u64 *host);
 // small-base path: the NP part commitments y_k = A f_k of the digit planes D [NP][24][ldn] (lf_sb.h) in ONE pass over A -> out_dev [NP][kappa][24] NTT form
 int commit_parts_i8g(lf_ctx *c, const unsigned char *D, size_t ldn, u32 NP, u64 *out_dev);

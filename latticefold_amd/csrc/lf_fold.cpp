@@ -815,56 +815,16 @@ int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out,
 int lf_sumcheck_lin_begin(lf_ctx *c, const uint64_t *tables, const uint64_t *eq_point) {
     if (LF_XB(c) && tables && eq_point && c->have_ccs_any()) { XB x(c); const lf_params &P = c->params_any(); return lf_sumcheck_lin_begin(c, x.ring_in(tables, (size_t)P.t * c->m_any()), x.ext_in(eq_point, P.s)); }
     if (!c || !tables || !eq_point) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->sumcheck_lin_begin(tables, eq_point);
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->have_ccs) return LF_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    const lf_params &P = c->P;
-    size_t m = c->m;
-    u64 *mz, *eqb;
-    RET(c->tbuf("sc_tab0", (size_t)P.t * 24 * m, &mz));
-    RET(c->tbuf("sc_eq0", 3 * m, &eqb));
-    for (u32 j = 0; j < P.t; j++) RET(up_ring(c, tables + (size_t)j * m * 24, m, mz + (size_t)j * 24 * m));
-    std::vector<Fq3> pt(P.s);
-    for (u32 i = 0; i < P.s; i++) pt[i] = fq3_make(eq_point[3 * i], eq_point[3 * i + 1], eq_point[3 * i + 2]);
-    RET(build_eq_dev(c, pt.data(), P.s, eqb));
-    c->sc_round = 0; c->sc_n = m; c->sc_cur = 0;
-    return LF_OK;
+    return c->bb ? ring_ops<BbRing>::sumcheck_lin_begin(c->bb->p, tables, eq_point) : ring_ops<GoldRing>::sumcheck_lin_begin(c, tables, eq_point);
 }
 int lf_sumcheck_lin_round(lf_ctx *c, const uint64_t *r_prev, uint64_t *evals_out) {
     if (LF_XB(c) && evals_out) { XB x(c); int rc = lf_sumcheck_lin_round(c, x.ext_in(r_prev, 1), evals_out); if (rc == LF_OK) x.ring_out(evals_out, c->params_any().d + 2); return rc; }
     if (!c || !evals_out) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->sumcheck_lin_round(r_prev, evals_out);
-    std::lock_guard<std::mutex> g(c->mu);
-    if (c->sc_round < 0 || c->sc_round >= (int)c->P.s) return LF_ERR_STATE;  // "Prover is not active"
-    if ((c->sc_round == 0) != (r_prev == nullptr)) return LF_ERR_STATE;      // "first round should be prover first" / "verifier message is empty"
-    HIPCHK(hipSetDevice(c->device));
-    const lf_params &P = c->P;
-    size_t m = c->m;
-    u64 *tab[2], *eq[2], *partial, *od;
-    RET(c->tbuf("sc_tab0", (size_t)P.t * 24 * m, &tab[0]));
-    RET(c->tbuf("sc_tab1", (size_t)P.t * 24 * (m / 2 ? m / 2 : 1), &tab[1]));
-    RET(c->tbuf("sc_eq0", 3 * m, &eq[0]));
-    RET(c->tbuf("sc_eq1", 3 * (m / 2 ? m / 2 : 1), &eq[1]));
-    RET(c->tbuf("round_partial", round_partial_words(), &partial));
-    RET(c->tbuf("round_out", 9 * 24, &od));      // d + 2 <= 9 evaluations
-    if (r_prev) {
-        Fq3Const r; r.c[0] = r_prev[0]; r.c[1] = r_prev[1]; r.c[2] = r_prev[2];
-        int src = c->sc_cur, dst = src ^ 1;
-        launch_fix_many(c->dcrt, tab[src], c->sc_n, tab[dst], c->sc_n / 2, c->sc_n, P.t * 8, r, c->stream());
-        launch_fix_many(c->dcrt, eq[src], c->sc_n, eq[dst], c->sc_n / 2, c->sc_n, 1, r, c->stream());
-        c->sc_cur = dst; c->sc_n /= 2;
-    }
-    launch_lin_round(c->dcrt, c->desc, tab[c->sc_cur], c->sc_n, eq[c->sc_cur], c->sc_n, c->sc_n, P.d + 1, partial, od, c->stream());
-    c->sc_round++;
-    return down_small(c, od, (size_t)(P.d + 2) * 24, evals_out);
+    return c->bb ? ring_ops<BbRing>::sumcheck_lin_round(c->bb->p, r_prev, evals_out) : ring_ops<GoldRing>::sumcheck_lin_round(c, r_prev, evals_out);
 }
 int lf_sumcheck_lin_end(lf_ctx *c) {
     if (!c) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->sumcheck_lin_end();
-    std::lock_guard<std::mutex> g(c->mu);
-    c->sc_round = -1;
-    return LF_OK;
+    return c->bb ? ring_ops<BbRing>::sumcheck_lin_end(c->bb->p) : ring_ops<GoldRing>::sumcheck_lin_end(c);
 }
 
 // PoseidonSponge on the device: a script of absorb / squeeze operations on a fresh sponge, one wave.  ops[i] =
@@ -901,91 +861,20 @@ int lf_device_sponge(lf_ctx *c, const uint32_t *ops, size_t nops, const uint64_t
     return LF_OK;
 }
 
-// ---- the folding sumcheck through the ABI: MLSumcheck::prove_as_subprotocol (utils/sumcheck.rs:53-80) with the comb
-// function of nifs/folding/utils.rs:273-325, split at the transcript.  `tables` is the reference's mle list of
-// create_sumcheck_polynomial (folding/utils.rs:200-259): [eq(r_L), G_L, eq(r_R), G_R, eq(beta), f-hat_{0,0} .. f-hat_{2K-1,tau-1}],
-// P = 5 + 2K*tau tables of m ring elements; the three eq tables must be slot-constant (they are diagonal embeddings in the reference).
+// ---- the folding sumcheck through the ABI: the bodies and the layout of `tables` are in lf_ring_host.h (ring_ops::sumcheck_fold_*)
 int lf_sumcheck_fold_begin(lf_ctx *c, const uint64_t *tables, const uint64_t *mu) {
     if (LF_XB(c) && tables && mu && c->have_ccs_any()) { XB x(c); const lf_params &P = c->params_any(); return lf_sumcheck_fold_begin(c, x.ring_in(tables, (size_t)(5 + 2 * P.K * x.TAU) * c->m_any()), x.ext_in(mu, 2 * P.K)); }
     if (!c || !tables || !mu) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->sumcheck_fold_begin(tables, mu);
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->have_ccs) return LF_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    const lf_params &P = c->P;
-    const size_t m = c->m;
-    const u32 K2 = 2 * P.K;
-    static const int eq_idx[3] = {0, 2, 4};
-    for (int e = 0; e < 3; e++) {   // slot-constant check of the eq tables
-        const u64 *tb = tables + (size_t)eq_idx[e] * m * 24;
-        for (size_t i = 0; i < m; i++)
-            for (int sl = 1; sl < 8; sl++)
-                if (memcmp(tb + i * 24, tb + i * 24 + 3 * sl, 24) != 0) return LF_ERR_UNSUPPORTED;
-    }
-    u64 *T, *F, *tmp;
-    RET(c->tbuf("sf_T0", 57 * m, &T));
-    RET(c->tbuf("sf_F0", (size_t)K2 * 3 * 24 * m, &F));
-    RET(c->tbuf("sf_tmp", 24 * m, &tmp));
-    for (int e = 0; e < 3; e++) {   // eqL, eqR, eqB -> fq3 tables (slot 0 of the ring table)
-        RET(up_ring(c, tables + (size_t)eq_idx[e] * m * 24, m, tmp));
-        HIPCHK(hipMemcpyAsync(T + (size_t)3 * e * m, tmp, 3 * m * 8, hipMemcpyDeviceToDevice, c->stream()));
-    }
-    RET(up_ring(c, tables + (size_t)1 * m * 24, m, T + 9 * m));
-    RET(up_ring(c, tables + (size_t)3 * m * 24, m, T + 33 * m));
-    for (u32 i = 0; i < K2 * 3; i++) RET(up_ring(c, tables + (size_t)(5 + i) * m * 24, m, F + (size_t)i * 24 * m));
-    std::vector<Fq3Const> mu_pow((size_t)K2 * 3);
-    for (u32 i = 0; i < K2; i++) {
-        Fq3 mi = fq3_make(mu[3 * i], mu[3 * i + 1], mu[3 * i + 2]), pm = mi;
-        for (u32 d = 0; d < 3; d++) { mu_pow[(size_t)i * 3 + d] = f3c(pm); pm = c->ring.mul3(pm, mi); }
-    }
-    Fq3Const *d_mu;
-    RET(upload_consts(c, "sf_mu", mu_pow, &d_mu));
-    c->sf_round = 0; c->sf_n = m; c->sf_cur = 0;
-    return LF_OK;
+    return c->bb ? ring_ops<BbRing>::sumcheck_fold_begin(c->bb->p, tables, mu) : ring_ops<GoldRing>::sumcheck_fold_begin(c, tables, mu);
 }
 int lf_sumcheck_fold_round(lf_ctx *c, const uint64_t *r_prev, uint64_t *evals_out) {
     if (LF_XB(c) && evals_out) { XB x(c); int rc = lf_sumcheck_fold_round(c, x.ext_in(r_prev, 1), evals_out); if (rc == LF_OK) x.ring_out(evals_out, 2 * c->params_any().b + 1); return rc; }
     if (!c || !evals_out) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->sumcheck_fold_round(r_prev, evals_out);
-    std::lock_guard<std::mutex> g(c->mu);
-    if (c->sf_round < 0 || c->sf_round >= (int)c->P.s) return LF_ERR_STATE;   // "Prover is not active" (sumcheck/prover.rs:63)
-    if ((c->sf_round == 0) != (r_prev == nullptr)) return LF_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    const lf_params &P = c->P;
-    const size_t m = c->m;
-    const u32 K2 = 2 * P.K;
-    u64 *T[2], *F[2], *partial, *od;
-    Fq3Const *d_mu;
-    RET(c->tbuf("sf_T0", 57 * m, &T[0]));
-    RET(c->tbuf("sf_T1", 57 * (m / 2 ? m / 2 : 1), &T[1]));
-    RET(c->tbuf("sf_F0", (size_t)K2 * 3 * 24 * m, &F[0]));
-    RET(c->tbuf("sf_F1", (size_t)K2 * 3 * 24 * (m / 2 ? m / 2 : 1), &F[1]));
-    RET(c->tbuf("sf_mu", (size_t)K2 * 3 + 8, &d_mu));
-    RET(c->tbuf("round_partial", round_partial_words(), &partial));
-    RET(c->tbuf("round_out", 5 * 24, &od));
-    if (r_prev) {
-        Fq3Const r; r.c[0] = r_prev[0]; r.c[1] = r_prev[1]; r.c[2] = r_prev[2];
-        int src = c->sf_cur, dst = src ^ 1;
-        launch_fix_many(c->dcrt, T[src], c->sf_n, T[dst], c->sf_n / 2, c->sf_n, 19, r, c->stream());
-        launch_fix_many(c->dcrt, F[src], c->sf_n, F[dst], c->sf_n / 2, c->sf_n, K2 * 3 * 8, r, c->stream());
-        c->sf_cur = dst; c->sf_n /= 2;
-    }
-    const size_t n = c->sf_n;
-    const u64 *t5 = T[c->sf_cur];
-    FoldRoundArgs a;
-    a.eqL = t5; a.eqR = t5 + 3 * n; a.eqB = t5 + 6 * n; a.G1 = t5 + 9 * n; a.G2 = t5 + 33 * n;
-    a.ld = n; a.n = n; a.p0 = 0; a.pcnt = n / 2; a.pF0 = 0;
-    c->sf_round++;
-    if (P.b != 2) return sb_fold_round_abi(c, t5, F[c->sf_cur], n, d_mu, evals_out);
-    launch_fold_round(c->dcrt, a, F[c->sf_cur], n, P.K, d_mu, partial, od, c->stream());
-    return down_small(c, od, (size_t)(2 * P.b + 1) * 24, evals_out);
+    return c->bb ? ring_ops<BbRing>::sumcheck_fold_round(c->bb->p, r_prev, evals_out) : ring_ops<GoldRing>::sumcheck_fold_round(c, r_prev, evals_out);
 }
 int lf_sumcheck_fold_end(lf_ctx *c) {
     if (!c) return LF_ERR_INVALID;
-    if (c->bb) return c->bb->sumcheck_fold_end();
-    std::lock_guard<std::mutex> g(c->mu);
-    c->sf_round = -1;
-    return LF_OK;
+    return c->bb ? ring_ops<BbRing>::sumcheck_fold_end(c->bb->p) : ring_ops<GoldRing>::sumcheck_fold_end(c);
 }
 
 // compute_f_0 (nifs/folding.rs:258-268): out[j] = sum_i coef_i (.) tables_i[j] with ring-element coefficients (8 distinct slots)

@@ -5,10 +5,16 @@
 // tbuf, ring, d_icrt, P, N, m, n, kappa, nA, ...) are used directly.  lf_capi.cpp keeps the argument checks, the external-basis wrapper and the
 // dispatch `c->bb ? ring_ops<BbRing>::f(c->bb->p, ..) : ring_ops<GoldRing>::f(c, ..)`.
 //
-// Stays per backend (really different, not copies): build_eq_dev / build_eq_async (two-level kernel against pre-multiplied constants), build_z,
-// lcccs_point, install_tables, ccs_load, ajtai_load / ajtai_generate / prep_ajtai_i8*, the lf_ajtai_commit* and ajtai_commit_gadget bodies (their sharded
-// finishes differ), selftest_field, down_small (per-lane pinned buffer + lane_sync() against one buffer + stream sync), the sumcheck state machines, the
-// provers (lf_prove.cpp, lf_fold.cpp, lf_fold_sb.cpp, bb_prove.cpp), lf_dist.cpp, the verifier, the wire format and lfp_*.
+// The context members both rings share are defined once, in lf_ctx_core.h; the set-up bodies (ICRT upload, matrix install, constraint-system load), the general
+// commits and the read-outs below use nothing else.
+//
+// Stays per backend, one line each:
+//   build_eq_dev / build_eq_async   two-level kernel on Goldilocks, pre-multiplied constants staged in the pinned arena on BabyBear
+//   build_z, lcccs_point            different table layouts (atl() leading dimension) and extension types
+//   the table build of install_tables, the envelope check of ccs_load   per-ring tables and per-ring limits (wide CCS, small bases on Goldilocks only)
+//   down_small                      lane_sync() on a blocking event (Goldilocks) against a plain stream synchronise
+//   selftest_field, set_sharding / dist_init   different kernels; two communicators and a handshake against one
+//   the provers (lf_prove.cpp, lf_fold.cpp, lf_fold_sb.cpp, bb_prove.cpp), lf_dist.cpp, the verifier, the wire format and lfp_*
 //
 // Order of the argument checks, the same on both rings: (1) null / range checks of the ABI function -> LF_ERR_INVALID, (2) here, before the context
 // lock: pow2(base) -> LF_ERR_UNSUPPORTED (decompose), len against 2^nv -> LF_ERR_INVALID (mle_eval_batch), (3) under the lock: have_ccs / resident
@@ -40,9 +46,42 @@ template <> struct Ring<lf_ctx> {
     static constexpr int RE = 24, TAU = 3;
     static constexpr bool general_csr = true;    // ccs_general / launch_spmv_rows exist on this ring only
     static constexpr bool montgomery = false;
-    static constexpr const char *mle_out = "io_b", *i8g_co = "i8g_coef";
+    static constexpr u32 max_kappa = 128;        // rows of a resident matrix
+    static constexpr size_t lut_min_default = (size_t)1 << 14;   // Tunables::read: this ring's default of LF_FOLD_LUT_MIN
+    static constexpr u64 modulus = LF_P;
+    static constexpr const char *io_out = "io_b", *i8g_co = "i8g_coef";
     static const DevCrt &tab(const lf_ctx *c) { return c->dcrt; }
-    static bool have_A(const lf_ctx *c) { return c->A_loaded; }
+    static W from_canon(u64 w) { return w; }
+    static void ring_from_u64(u64 v, u64 *o) { HostRing::from_u64(v, o); }
+    // the bit-plane form of the witness `planes` belong to, if the running fold step built it for its GEMM rounds (lf_sv_rounds.h): the digit-plane commit
+    // kernel then cuts the digits from it.  Null otherwise
+    static int bit_planes(lf_ctx *c, const int32_t *planes, const lf_witness *wit, const u32 **bits) {
+        *bits = nullptr;
+        if (wit && c->A_col0 == 0 && planes == wit->planes && c->nA == c->N)
+            for (int sd = 0; sd < 2; sd++)
+                if (c->bits_wit[sd] == wit && c->bits_ptr[sd]) {
+                    *bits = c->bits_ptr[sd];
+                    if (c->stream() != c->st_lane[1]) HIPCHK(hipStreamWaitEvent(c->stream(), c->bits_ev[sd], 0));
+                    break;
+                }
+        return LF_OK;
+    }
+    // the sumcheck ABI (lf_sumcheck_{lin,fold}_*): leading dimension of a halved table, block partials and message words of a round, the fix launcher
+    typedef FoldRoundArgs FoldA;
+    static constexpr bool small_base = true;     // b = 4, 8, 16 (lf_sb.h) exist on this ring only
+    static constexpr const char *sf_mu = "sf_mu";
+    static constexpr size_t lin_out_words = 9 * 24;   // d + 2 <= 9 evaluations
+    static size_t halved_ld(size_t n) { return n ? n : 1; }
+    static size_t lin_partial_words(size_t) { return round_partial_words(); }
+    static size_t fold_partial_words(size_t) { return round_partial_words(); }
+    static void fix(lf_ctx *c, const u64 *in, size_t ld_in, u64 *out, size_t ld_out, size_t n_in, u32 rows, const ExtC &r) {
+        launch_fix_many(c->dcrt, in, ld_in, out, ld_out, n_in, rows, r, c->stream());
+    }
+    // one row of A (NTT form [RE][cnt]) -> row i of a row chunk of the byte planes: inverse CRT and packing fused
+    static int pack_row(lf_ctx *c, const u64 *row, size_t cnt, u32 i, u32 MT, unsigned char *Ab) {
+        launch_ajtai_icrt_pack_i8(c->d_icrt, row, cnt, i, MT, Ab, c->stream());
+        return LF_OK;
+    }
     static lf_ctx *owner(lf_ctx *c) { return c; }
     static AjtaiI8Ring i8() { return ajtai_i8_goldilocks(); }
     static Ext ext_load(const u64 *w) { return fq3_make(w[0], w[1], w[2]); }
@@ -61,9 +100,35 @@ template <> struct Ring<BbCtxImpl> {
     static constexpr int RE = lfbb::RE, TAU = lfbb::TAU;
     static constexpr bool general_csr = false;
     static constexpr bool montgomery = true;
-    static constexpr const char *mle_out = "io_o", *i8g_co = "i8g_co";
+    static constexpr u32 max_kappa = 32;
+    static constexpr size_t lut_min_default = (size_t)1 << 15;
+    static constexpr u64 modulus = BB_P;
+    static constexpr const char *io_out = "io_o", *i8g_co = "i8g_co";
     static const DevBb &tab(const BbCtxImpl *c) { return c->dev; }
-    static bool have_A(const BbCtxImpl *c) { return c->dAb != nullptr; }
+    static W from_canon(u64 w) { return lfbb::from_canon(w); }
+    static void ring_from_u64(u64 v, u64 *o) { BbHostRing::from_u64(v, o); }
+    static int bit_planes(BbCtxImpl *, const int32_t *, const lf_witness *, const u32 **bits) { *bits = nullptr; return LF_OK; }   // no bit-plane form on this ring
+    typedef FoldArgs FoldA;
+    static constexpr bool small_base = false;
+    static constexpr const char *sf_mu = "sf_mup";
+    static constexpr size_t lin_out_words = 5 * RE;
+    static size_t halved_ld(size_t n) { return n < 2 ? 2 : n; }   // leading dimensions stay even (8-byte pair loads)
+    static size_t lin_partial_words(size_t) { return red_partial_words(5 * RE); }
+    static size_t fold_partial_words(size_t m) { return lfbb::fold_partial_words(m); }
+    static void fix(BbCtxImpl *c, const fe *in, size_t ld_in, fe *out, size_t ld_out, size_t n_in, u32 rows, const ExtC &r) {
+        launch_fix(c->dev, in, ld_in, out, ld_out, n_in, rows, r, c->stream());
+    }
+    static int pack_row(BbCtxImpl *c, const fe *row, size_t cnt, u32 i, u32 MT, unsigned char *Ab) {   // inverse CRT -> canonical element-major words -> bytes
+        const AjtaiI8Ring I = i8();
+        fe *coef;
+        u64 *canon;
+        RET(c->tbuf("i8_prep_coef", (size_t)RE * cnt, &coef));
+        RET(c->tbuf("i8_prep_canon", (size_t)RE * cnt, &canon));
+        launch_icrt_dense(c->d_icrt, row, coef, cnt, c->stream());
+        launch_soa_to_aos(coef, canon, cnt, c->stream());
+        launch_ajtai_pack_i8(canon, 1, RE, cnt, i, MT, I.RD, I.NL, Ab, c->stream());
+        return LF_OK;
+    }
     static lf_ctx *owner(BbCtxImpl *c) { return c->owner; }
     static AjtaiI8Ring i8() { return ajtai_i8_babybear(); }
     static Ext ext_load(const u64 *w) { return h9_load(w); }
@@ -119,7 +184,7 @@ template <class C, class Cut>
 int commit_dev_pre(C *c, u32 NP, u32 batch, u64 *out_dev, bool timed, Cut &&cut) {
     typedef Ring<C> R;
     typedef typename R::W W;
-    if (!R::have_A(c) || !c->i8_nch || !c->dAb) return LF_ERR_STATE;
+    if (!c->A_loaded || !c->i8_nch || !c->dAb) return LF_ERR_STATE;
     const AjtaiI8Ring I = R::i8();
     const u32 nch = c->i8_nch, kc = c->i8_kc, MT = ajtai_i8_row_tiles(I, kc);
     const size_t ntiles = (c->nA + 7) / 8, chunk_bytes = ntiles * (I.RD / 8) * MT * 1024;
@@ -171,6 +236,59 @@ int commit_dev_i8g(C *c, const typename Ring<C>::W *F, size_t ldF, u32 batch, co
 template <class C>
 int witness_commit_dev(C *c, const lf_witness *w, u64 *out_dev) { return commit_dev_i8g(c, nullptr, 0, 1, w->planes + c->A_col0, w->N, out_dev, false); }
 
+// The commitments of a fold step: digit planes k0 .. k0+NP-1 of `planes` (this rank's column slice) -> out_dev canonical u64 [NP][kappa][RE], NTT form, AoS
+// (PARTIAL when sharded).  wit (optional): the witness `planes` belong to (R::bit_planes).  Buffer names and sizes are what they were per ring: a step's
+// memory footprint depends on them.
+template <class C>
+int commit_planes_i8(C *c, const int32_t *planes, size_t ld, u32 k0, u32 NP, u64 *out_dev, const lf_witness *wit = nullptr) {
+    typedef Ring<C> R;
+    typedef typename R::W W;
+    constexpr size_t RE = R::RE;
+    const AjtaiI8Ring I = R::i8();
+    const u32 nch = c->i8_nch, kc = c->i8_kc, MT = ajtai_i8_row_tiles(I, kc), maxp = ajtai_i8_max_planes_mt(I, MT);
+    const size_t ntiles = (c->nA + 7) / 8, chunk_bytes = ntiles * (I.RD / 8) * MT * 1024;
+    // One persistent workgroup per CU fills its LDS (157 KB): on a fully occupied chip the latency-bound round kernels of the other lane
+    // cannot be placed until a commit workgroup retires.  7/8 of the CUs (28 of 32 per XCD) leaves them room: C4 26.1 -> 25.0 ms/step
+    // (measured 256 / 240 / 224 / 192 / 160 / 128 workgroups: 26.1 / 26.3 / 25.0 / 25.1 / 26.1 / 28.2 ms).
+    u32 nwg = c->tn.i8_wgs > 0 ? (u32)c->tn.i8_wgs : 224;
+    if (nwg > ntiles) nwg = (u32)ntiles;
+    const u32 nslots = nwg < 16 ? 16 : nwg;    // (two plane groups run as 2 x 8 chunks at least: launch_ajtai_i8)
+    int32_t *part, *dsum;
+    long long *sum;
+    u64 *coef;
+    W *cf = nullptr, *ntt;
+    const u32 NTmax = ajtai_i8_col_tiles(I, maxp);
+    RET(c->tbuf("i8_part", ajtai_i8_part_words(nslots, MT, NTmax), &part));
+    RET(c->tbuf("i8_dsum", (size_t)nslots * maxp * I.RD, &dsum));
+    RET(c->tbuf("i8_sum", ajtai_i8_sum_words(I, MT, NTmax, maxp), &sum));
+    RET(c->tbuf("i8_coef", RE * NP * c->kappa, &coef));
+    if constexpr (R::montgomery) RET(c->tbuf("i8_cf", RE * NP * c->kappa, &cf));
+    RET(c->tbuf("i8_ntt", RE * NP * c->kappa, &ntt));
+    const u32 *bits;
+    RET(R::bit_planes(c, planes, wit, &bits));
+    const size_t bits_nw = (c->N + 511) / 512 * 16;          // words per row of the bit-plane form (positions padded to 512)
+    const u32 bits_rows = 16 * ((c->P.K + 15) / 16) + 1;
+    for (u32 p0 = 0; p0 < NP; p0 += maxp) {
+        const u32 np = NP - p0 < maxp ? NP - p0 : maxp;
+        u64 *co = coef + RE * p0 * c->kappa;   // block of this plane group: coefficient planes [RE][np*kappa] (Goldilocks), element-major [np*kappa][RE] (BabyBear)
+        for (u32 ch = 0; ch < nch; ch++) {
+            const u32 row0 = ch * kc, kn = c->kappa - row0 < kc ? c->kappa - row0 : kc;
+            size_t ev = c->ev_begin(1);
+            int g = launch_ajtai_i8(I, c->dAb + (size_t)ch * chunk_bytes, MT, planes, ld, c->nA, kn, row0, c->kappa, k0 + p0, np, nwg, part, dsum, sum, co, c->stream(),
+                                    bits, bits_nw, bits_rows);
+            c->ev_end(ev);
+            if (g < 0) return LF_ERR_UNSUPPORTED;
+        }
+        const size_t ne = (size_t)np * c->kappa;
+        const W *src;
+        if constexpr (R::montgomery) { launch_aos_to_soa(co, cf, ne, c->stream()); src = cf; }   // canonical -> Montgomery planes
+        else src = co;                                                                         // the kernel's canonical planes ARE the device form
+        launch_crt_fwd(R::tab(c), src, ntt, ne, c->stream());
+        launch_soa_to_aos(ntt, out_dev + (size_t)p0 * c->kappa * RE, ne, c->stream());
+    }
+    return LF_OK;
+}
+
 inline bool pow2(u64 b) { return b >= 2 && (b & (b - 1)) == 0; }
 
 // ---- the entry points: everything after the argument checks, the external-basis wrapper and the ring dispatch ----------------------------------------
@@ -184,6 +302,202 @@ struct ring_ops<Ring<C>> {
     typedef typename R::ExtC ExtC;
     typedef typename R::Part Part;
     static constexpr size_t RE = R::RE, TAU = R::TAU;
+
+    // ---- set-up ----
+    // install_tables after the ring's own table build: the dense inverse CRT map icrt [RE][RE] (canonical) and its rows in compressed form for the digit pass
+    // of the general commitment (k_i8g_cut_ntt): the shipped tables have one entry per slot
+    static int install_icrt(C *c, const u64 *icrt) {
+        std::vector<W> mat(RE * RE), sv(RE * 8, 0);
+        std::vector<u32> sc(RE * 8, 0xFFFFFFFFu);
+        for (size_t i = 0; i < RE * RE; i++) mat[i] = R::from_canon(icrt[i]);
+        if (!c->d_icrt) HIPCHK(lf_dev_malloc(&c->d_icrt, mat.size() * sizeof(W)));
+        HIPCHK(hipMemcpy(c->d_icrt, mat.data(), mat.size() * sizeof(W), hipMemcpyHostToDevice));
+        bool sparse = true;
+        for (size_t r = 0; r < RE && sparse; r++) {
+            int q = 0;
+            for (size_t col = 0; col < RE; col++)
+                if (icrt[r * RE + col]) {
+                    if (q == 8) { sparse = false; break; }
+                    sv[r * 8 + q] = mat[r * RE + col]; sc[r * 8 + q] = (u32)col; q++;
+                }
+        }
+        if (sparse) {
+            if (!c->d_icrt_sp_val) { HIPCHK(lf_dev_malloc(&c->d_icrt_sp_val, sv.size() * sizeof(W))); HIPCHK(lf_dev_malloc(&c->d_icrt_sp_col, sc.size() * sizeof(u32))); }
+            HIPCHK(hipMemcpy(c->d_icrt_sp_val, sv.data(), sv.size() * sizeof(W), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(c->d_icrt_sp_col, sc.data(), sc.size() * sizeof(u32), hipMemcpyHostToDevice));
+        } else if (c->d_icrt_sp_val) {
+            (void)hipFree(c->d_icrt_sp_val); (void)hipFree(c->d_icrt_sp_col);
+            c->d_icrt_sp_val = nullptr; c->d_icrt_sp_col = nullptr;
+        }
+        return LF_OK;
+    }
+    // A lives on the device in ONE form: coefficient form, cut into bytes, in MFMA operand order (lf_ajtai_i8.hip) -- what the digit-plane commitments of a fold
+    // step and the general commitments (lf_ajtai_i8g.hip) both stream.  Built once per matrix, one row at a time through one row buffer (uploaded, or filled from
+    // the seed), so the peak is the byte planes plus one row.  The context holds NO matrix from the first line that can fail to the last: kappa, the column
+    // slice, the chunking and "A is resident" are published together, on success only.
+    static int ajtai_install(C *c, size_t kappa, size_t n, const u64 *A_host, u64 seed) {
+        if (kappa > R::max_kappa) return LF_ERR_INVALID;
+        std::lock_guard<std::mutex> g(c->mu);
+        HIPCHK(hipSetDevice(c->device));
+        size_t col0, cnt;
+        RET(c->shard_columns(n, &col0, &cnt));   // a sharded rank keeps only its column slice of the caller's matrix
+        c->drop_matrix();
+        const AjtaiI8Ring I = R::i8();
+        const u32 maxr = ajtai_i8_max_rows(I), nch = ((u32)kappa + maxr - 1) / maxr, kc = ((u32)kappa + nch - 1) / nch, MT = ajtai_i8_row_tiles(I, kc);
+        const size_t chunk_bytes = (cnt + 7) / 8 * (I.RD / 8) * MT * 1024, bytes = chunk_bytes * nch + ajtai_i8_slack_bytes();
+        unsigned char *Ab = nullptr;
+        HIPCHK(lf_dev_malloc(&Ab, bytes));
+        const int rc = [&]() -> int {
+            HIPCHK(hipMemsetAsync(Ab, 0, bytes, c->stream()));
+            W *row;
+            RET(c->tbuf("i8_prep_row", RE * cnt, &row));
+            for (size_t i = 0; i < kappa; i++) {
+                if (A_host) RET(up_ring(c, A_host + (i * n + col0) * RE, cnt, row));
+                else launch_fill_ajtai(row, 1, cnt, n, col0, seed, c->stream(), (u32)i);
+                RET(R::pack_row(c, row, cnt, (u32)i % kc, MT, Ab + (i / kc) * chunk_bytes));
+            }
+            HIPCHK(hipStreamSynchronize(c->stream()));
+            return LF_OK;
+        }();
+        if (rc != LF_OK) (void)hipStreamSynchronize(c->stream());   // nothing enqueued above still uses the scratch or Ab when they go
+        for (const char *name : {"i8_prep_row", "i8_prep_coef", "i8_prep_canon", "stage_aos"}) c->drop_buf(name);
+        if (rc != LF_OK) { (void)hipFree(Ab); return rc; }
+        c->dAb = Ab;
+        c->kappa = (u32)kappa;
+        c->nA = cnt; c->nA_total = n; c->A_col0 = col0;
+        c->i8_nch = nch; c->i8_kc = kc;
+        c->A_loaded = true;
+        return LF_OK;
+    }
+    // lf_ccs_load after the ring's envelope check (limits on s, t, q, K, L, d, b, B: per ring): the checks that need no context, then the descriptor, the CSR
+    // arrays and their CSC form on the device
+    static int ccs_load(C *c, const lf_params *P, const u32 *const *rowptr, const u32 *const *col, const u64 *const *val, const u32 *S_off, const u32 *S_idx,
+                        const u64 *cc) {
+        const size_t m = (size_t)1 << P->s, N = (size_t)P->wit_len * P->L, n = (size_t)P->l + 1 + P->wit_len;
+        if (N > m) return LF_ERR_SIZE_BOUNDS;  // sanity_check, nifs.rs:165-173
+        {   // the reference indexes comb values by matrix index: multisets must concatenate to 0..t-1
+            u32 next = 0;
+            for (u32 i = 0; i < P->q; i++)
+                for (u32 k = S_off[i]; k < S_off[i + 1]; k++)
+                    if (S_idx[k] != next++) return LF_ERR_UNSUPPORTED;
+            if (next != P->t || S_off[P->q] > 16) return LF_ERR_UNSUPPORTED;
+        }
+        RET(lf_validate_csr(P->t, m, n, rowptr, col, val, RE, R::modulus));   // before any context state is touched
+        for (size_t k = 0; k < (size_t)P->q * RE; k++)
+            if (cc[k] >= R::modulus) return LF_ERR_INVALID;
+        std::lock_guard<std::mutex> g(c->mu);
+        HIPCHK(hipSetDevice(c->device));
+        c->free_ccs();
+        c->P = *P; c->N = N; c->m = m; c->n = n;
+        memset(&c->desc, 0, sizeof(c->desc));
+        c->desc.t = P->t; c->desc.q = P->q;
+        for (u32 i = 0; i <= P->q; i++) c->desc.S_off[i] = S_off[i];
+        for (u32 k = 0; k < S_off[P->q]; k++) c->desc.S_idx[k] = S_idx[k];
+        if constexpr (R::general_csr)
+            for (u32 i = 0; i < P->q; i++)
+                for (u32 k = S_off[i]; k < S_off[i + 1]; k++) { c->desc.ms[k] = i; c->desc.first[k] = (k == S_off[i]); }
+        u64 one[RE], mone[RE];
+        R::ring_from_u64(1, one);
+        R::ring_from_u64(R::modulus - 1, mone);
+        for (u32 i = 0; i < P->q; i++) {
+            const u64 *ci = cc + (size_t)i * RE;
+            for (size_t w = 0; w < RE; w++) c->desc.c[i][w] = R::from_canon(ci[w]);
+            c->desc.c_unit[i] = !memcmp(ci, one, sizeof(one)) ? 1 : (!memcmp(ci, mone, sizeof(mone)) ? -1 : 0);
+        }
+        // every device array is registered in the context as soon as it exists, so a failure half-way leaks nothing (free_ccs frees them)
+        auto dalloc = [](auto &vec, size_t bytes) -> void * {
+            void *ptr = nullptr;
+            if (lf_dev_malloc(&ptr, bytes) != hipSuccess) return nullptr;
+            vec.push_back((typename std::remove_reference<decltype(vec)>::type::value_type)ptr);
+            return ptr;
+        };
+        for (u32 j = 0; j < P->t; j++) {
+            const size_t nnz = rowptr[j][m];
+            std::vector<W> conv;
+            const W *v;
+            if constexpr (R::montgomery) {
+                conv.resize(nnz * RE + 1);
+                for (size_t k = 0; k < nnz * RE; k++) conv[k] = R::from_canon(val[j][k]);
+                v = conv.data();
+            } else v = val[j];   // canonical words are the device form
+            std::vector<u32> cp(n + 1, 0), ri(nnz + 1);
+            std::vector<W> vT(nnz * RE + 1);
+            for (size_t k = 0; k < nnz; k++) cp[col[j][k] + 1]++;
+            for (size_t i = 0; i < n; i++) cp[i + 1] += cp[i];
+            std::vector<u32> fill(cp.begin(), cp.end() - 1);
+            for (size_t r = 0; r < m; r++)
+                for (u32 k = rowptr[j][r]; k < rowptr[j][r + 1]; k++) {
+                    const u32 pos = fill[col[j][k]]++;
+                    ri[pos] = (u32)r;
+                    memcpy(&vT[(size_t)pos * RE], v + (size_t)k * RE, RE * sizeof(W));
+                }
+            void *drp = dalloc(c->d_rowptr, (m + 1) * 4), *dci = dalloc(c->d_col, (nnz + 1) * 4), *dv = dalloc(c->d_val, (nnz + 1) * RE * sizeof(W));
+            void *dcp = dalloc(c->d_colptr, (n + 1) * 4), *dri = dalloc(c->d_rowidx, (nnz + 1) * 4), *dvT = dalloc(c->d_valT, (nnz + 1) * RE * sizeof(W));
+            if (!drp || !dci || !dv || !dcp || !dri || !dvT) return LF_ERR_HIP;
+            HIPCHK(hipMemcpy(drp, rowptr[j], (m + 1) * 4, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(dci, col[j], nnz * 4, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(dv, v, nnz * RE * sizeof(W), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(dcp, cp.data(), (n + 1) * 4, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(dri, ri.data(), nnz * 4, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(dvT, vT.data(), nnz * RE * sizeof(W), hipMemcpyHostToDevice));
+        }
+        if constexpr (R::general_csr) {
+            const size_t rows_used = n < m ? n : m;
+            c->ccs_general = false;
+            for (u32 jj = 0; jj < P->t; jj++)
+                if ((size_t)rowptr[jj][m] * 2 > rows_used * 3) c->ccs_general = true;
+            c->shc_r0 = (size_t)-1;
+        }
+        c->have_ccs = true;
+        return LF_OK;
+    }
+
+    // ---- a5: general commitments through the ABI ----
+    // Both re-read the environment switches, as every prover entry point does (the BabyBear bodies did not before they were merged: nothing in the general
+    // commit path of that ring consumes a tunable, so the read changes nothing there until the next linearize / fold step reads them again anyway).
+    static int ajtai_commit(C *c, const u64 *f, size_t n, size_t batch, u64 *out) {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (!c->A_loaded) return LF_ERR_STATE;
+        if (n != c->nA_total) return LF_ERR_INVALID;  // CommitmentError::WrongWitnessLength(n, width)
+        HIPCHK(hipSetDevice(c->device));
+        W *F;
+        u64 *o;
+        RET(c->tbuf("io_a", batch * n * RE, &F));
+        RET(c->tbuf(R::io_out, batch * c->kappa * RE, &o));
+        for (size_t b = 0; b < batch; b++) RET(up_ring(c, f + b * n * RE, n, F + b * RE * n));
+        c->tn = Tunables::read(R::lut_min_default);
+        c->ev_reset();
+        RET(commit_dev_i8g(c, F + c->A_col0, n, (u32)batch, nullptr, 0, o, true));   // timed: lf_last_kernel_stats reports the stand-alone kernel
+        c->ev_collect();
+        return R::commit_finish(c, o, batch * c->kappa * RE, out);
+    }
+    // commit_coeff / decompose_and_commit_{coeff,ntt} (commitment_scheme.rs:81-113): element i of f [batch][count] (coefficient form, or NTT form: ntt_in)
+    // becomes columns [i L, (i + 1) L) of the committed vector, its balanced base-2^lb digits (lb 0, L 1: the element itself).  The count x L vector is never
+    // built: the gadget digit pass (lf_i8g_dec.cuh) writes the commit kernel's operand words from the coefficient table, as few planes as the base needs.
+    // NTT-form input is inverse-CRT-ed into one coefficient table first (one pass over count elements; the fused form of k_i8g_cut_ntt would map 32 elements
+    // = 32 L columns per block -- DESIGN.md, k_ajtai_i8g row).
+    static int ajtai_commit_gadget(C *c, const u64 *f, bool ntt_in, size_t count, u32 lb, u32 L, size_t batch, u64 *out) {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (!c->A_loaded) return LF_ERR_STATE;
+        if (count > c->nA_total || count * L != c->nA_total) return LF_ERR_INVALID;   // CommitmentError::WrongWitnessLength
+        HIPCHK(hipSetDevice(c->device));
+        W *F, *X = nullptr;
+        u64 *o;
+        RET(c->tbuf("io_a", batch * count * RE, &F));
+        if (ntt_in) RET(c->tbuf("io_c", count * RE, &X));
+        RET(c->tbuf(R::io_out, batch * c->kappa * RE, &o));
+        for (size_t b = 0; b < batch; b++) RET(up_ring(c, f + b * count * RE, count, F + b * RE * count));
+        c->tn = Tunables::read(R::lut_min_default);
+        c->ev_reset();
+        const u32 NP = lb ? ajtai_i8g_planes_base(R::i8(), 1ull << lb) : ajtai_i8g_planes_general(R::i8());
+        RET(commit_dev_pre(c, NP, (u32)batch, o, true, [&](u32 b, unsigned long long *pre, size_t ntiles) {   // timed: the ICRT, digit pass and contraction
+            const W *src = F + (size_t)b * RE * count;
+            if (ntt_in) { launch_icrt_dense(c->d_icrt, src, X, count, c->stream()); src = X; }
+            launch_i8g_cut_dec(src, count, c->A_col0, c->nA, L, lb, c->digit_mode, NP, pre, ntiles, c->stream());
+        }));
+        c->ev_collect();
+        return R::commit_finish(c, o, batch * c->kappa * RE, out);
+    }
 
     // ---- a1/a2/a3 ----
     static int ntt_fwd(C *c, const u64 *in, u64 *out, size_t count) {
@@ -286,7 +600,7 @@ struct ring_ops<Ring<C>> {
         RET(c->tbuf("io_eq", TAU * n, &eq));
         RET(c->tbuf("io_a", ntables * len * RE, &X));
         RET(c->tbuf("red_partial", R::red_partial(ntables * RE), &partial));
-        RET(c->tbuf(R::mle_out, ntables * RE, &o));   // (the rings name this buffer differently; kept: buffer names are part of a context's memory footprint)
+        RET(c->tbuf(R::io_out, ntables * RE, &o));   // (the rings name this buffer differently; kept: buffer names are part of a context's memory footprint)
         RET(build_eq_dev(c, load_point(point, nv).data(), nv, eq));
         for (size_t a = 0; a < ntables; a++) RET(up_ring(c, tables + a * len * RE, len, X + a * RE * len));
         launch_dot_eq(R::tab(c), X, len, (u32)ntables, eq, n, len, partial, o, c->stream());
@@ -311,6 +625,141 @@ struct ring_ops<Ring<C>> {
         }
         launch_spmv(R::tab(c), c->d_rowptr[j], c->d_col[j], c->d_val[j], zd, c->n, od, c->m, 0, c->stream());
         return down_ring(c, od, c->m, out);
+    }
+
+    // ---- the sumchecks through the ABI (tests / SURVEY 8b): MLSumcheck::prove_as_subprotocol (utils/sumcheck.rs:53-80) split at the transcript ----
+    // tables of the current round: the caller's [..][m] in round 1, halved into the other buffer (leading dimension R::halved_ld) by every later round
+    static size_t sc_ld(const C *c, size_t n) { return n == c->m ? c->m : R::halved_ld(n); }
+    static int sumcheck_lin_begin(C *c, const u64 *tables, const u64 *eq_point) {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (!c->have_ccs) return LF_ERR_STATE;
+        HIPCHK(hipSetDevice(c->device));
+        const lf_params &P = c->P;
+        const size_t m = c->m;
+        W *mz, *eqb;
+        RET(c->tbuf("sc_tab0", (size_t)P.t * RE * m, &mz));
+        RET(c->tbuf("sc_eq0", TAU * m, &eqb));
+        for (u32 j = 0; j < P.t; j++) RET(up_ring(c, tables + (size_t)j * m * RE, m, mz + (size_t)j * RE * m));
+        RET(build_eq_dev(c, load_point(eq_point, P.s).data(), P.s, eqb));
+        c->sc_round = 0; c->sc_n = m; c->sc_cur = 0;
+        return LF_OK;
+    }
+    static int sumcheck_lin_round(C *c, const u64 *r_prev, u64 *evals_out) {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (c->sc_round < 0 || c->sc_round >= (int)c->P.s) return LF_ERR_STATE;  // "Prover is not active"
+        if ((c->sc_round == 0) != (r_prev == nullptr)) return LF_ERR_STATE;      // "first round should be prover first" / "verifier message is empty"
+        HIPCHK(hipSetDevice(c->device));
+        const lf_params &P = c->P;
+        const size_t m = c->m;
+        W *tab[2], *eq[2];
+        Part *partial;
+        u64 *od;
+        RET(c->tbuf("sc_tab0", (size_t)P.t * RE * m, &tab[0]));
+        RET(c->tbuf("sc_tab1", (size_t)P.t * RE * R::halved_ld(m / 2), &tab[1]));
+        RET(c->tbuf("sc_eq0", TAU * m, &eq[0]));
+        RET(c->tbuf("sc_eq1", TAU * R::halved_ld(m / 2), &eq[1]));
+        RET(c->tbuf("round_partial", R::lin_partial_words(m), &partial));
+        RET(c->tbuf("round_out", R::lin_out_words, &od));
+        if (r_prev) {
+            const ExtC r = R::ext_const(c, R::ext_load(r_prev));
+            const int src = c->sc_cur, dst = src ^ 1;
+            const size_t ldi = sc_ld(c, c->sc_n), ldo = R::halved_ld(c->sc_n / 2);
+            R::fix(c, tab[src], ldi, tab[dst], ldo, c->sc_n, P.t * 8, r);
+            R::fix(c, eq[src], ldi, eq[dst], ldo, c->sc_n, 1, r);
+            c->sc_cur = dst; c->sc_n /= 2;
+        }
+        const size_t ld = sc_ld(c, c->sc_n);
+        launch_lin_round(R::tab(c), c->desc, tab[c->sc_cur], ld, eq[c->sc_cur], ld, c->sc_n, P.d + 1, partial, od, c->stream());
+        c->sc_round++;
+        return down_small(c, od, (size_t)(P.d + 2) * RE, evals_out);
+    }
+    static int sumcheck_lin_end(C *c) {
+        std::lock_guard<std::mutex> g(c->mu);
+        c->sc_round = -1;
+        return LF_OK;
+    }
+    // The folding sumcheck with the comb function of nifs/folding/utils.rs:273-325.  `tables` is the reference's mle list of create_sumcheck_polynomial
+    // (folding/utils.rs:200-259): [eq(r_L), G_L, eq(r_R), G_R, eq(beta), f-hat_{0,0} .. f-hat_{2K-1,tau-1}], 5 + 2K*tau tables of m ring elements; the three eq
+    // tables must be slot-constant (they are diagonal embeddings in the reference).  On the device: T = [eqL, eqR, eqB (tau planes each), G_L, G_R (RE planes each)]
+    static constexpr size_t T5P = 3 * TAU + 2 * RE;
+    static int sumcheck_fold_begin(C *c, const u64 *tables, const u64 *mu) {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (!c->have_ccs) return LF_ERR_STATE;
+        HIPCHK(hipSetDevice(c->device));
+        const lf_params &P = c->P;
+        const size_t m = c->m;
+        const u32 K2 = 2 * P.K;
+        static const int eq_idx[3] = {0, 2, 4};
+        for (int e = 0; e < 3; e++) {   // slot-constant check of the eq tables
+            const u64 *tb = tables + (size_t)eq_idx[e] * m * RE;
+            for (size_t i = 0; i < m; i++)
+                for (size_t sl = 1; sl < 8; sl++)
+                    if (memcmp(tb + i * RE, tb + i * RE + TAU * sl, TAU * 8) != 0) return LF_ERR_UNSUPPORTED;
+        }
+        W *T, *F, *tmp;
+        RET(c->tbuf("sf_T0", T5P * m, &T));
+        RET(c->tbuf("sf_F0", (size_t)K2 * TAU * RE * m, &F));
+        RET(c->tbuf("sf_tmp", RE * m, &tmp));
+        for (int e = 0; e < 3; e++) {   // eqL, eqR, eqB -> extension-field tables (slot 0 of the ring table); one stream orders tmp's reuse
+            RET(up_ring(c, tables + (size_t)eq_idx[e] * m * RE, m, tmp));
+            HIPCHK(hipMemcpyAsync(T + TAU * e * m, tmp, TAU * m * sizeof(W), hipMemcpyDeviceToDevice, c->stream()));
+        }
+        RET(up_ring(c, tables + (size_t)1 * m * RE, m, T + 3 * TAU * m));
+        RET(up_ring(c, tables + (size_t)3 * m * RE, m, T + (3 * TAU + RE) * m));
+        for (u32 i = 0; i < K2 * TAU; i++) RET(up_ring(c, tables + (size_t)(5 + i) * m * RE, m, F + (size_t)i * RE * m));
+        std::vector<ExtC> mu_pow((size_t)K2 * TAU);   // mu_i^1 .. mu_i^tau in the kernels' constant form
+        for (u32 i = 0; i < K2; i++) {
+            const Ext mi = R::ext_load(mu + TAU * i);
+            Ext pm = mi;
+            for (size_t d = 0; d < TAU; d++) { mu_pow[(size_t)i * TAU + d] = R::ext_const(c, pm); pm = R::ext_mul(c, pm, mi); }
+        }
+        ExtC *d_mu;
+        RET(upload_consts(c, R::sf_mu, mu_pow, &d_mu));
+        c->sf_round = 0; c->sf_n = m; c->sf_cur = 0;
+        return LF_OK;
+    }
+    static int sumcheck_fold_round(C *c, const u64 *r_prev, u64 *evals_out) {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (c->sf_round < 0 || c->sf_round >= (int)c->P.s) return LF_ERR_STATE;   // "Prover is not active" (sumcheck/prover.rs:63)
+        if ((c->sf_round == 0) != (r_prev == nullptr)) return LF_ERR_STATE;
+        HIPCHK(hipSetDevice(c->device));
+        const lf_params &P = c->P;
+        const size_t m = c->m;
+        const u32 K2 = 2 * P.K;
+        W *T[2], *F[2];
+        Part *partial;
+        u64 *od;
+        ExtC *d_mu;
+        RET(c->tbuf("sf_T0", T5P * m, &T[0]));
+        RET(c->tbuf("sf_T1", T5P * R::halved_ld(m / 2), &T[1]));
+        RET(c->tbuf("sf_F0", (size_t)K2 * TAU * RE * m, &F[0]));
+        RET(c->tbuf("sf_F1", (size_t)K2 * TAU * RE * R::halved_ld(m / 2), &F[1]));
+        RET(c->tbuf(R::sf_mu, (size_t)K2 * TAU + 8, &d_mu));
+        RET(c->tbuf("round_partial", R::fold_partial_words(m), &partial));
+        RET(c->tbuf("round_out", 5 * RE, &od));
+        if (r_prev) {
+            const ExtC r = R::ext_const(c, R::ext_load(r_prev));
+            const int src = c->sf_cur, dst = src ^ 1;
+            const size_t ldi = sc_ld(c, c->sf_n), ldo = R::halved_ld(c->sf_n / 2);
+            R::fix(c, T[src], ldi, T[dst], ldo, c->sf_n, 19, r);
+            R::fix(c, F[src], ldi, F[dst], ldo, c->sf_n, K2 * TAU * 8, r);
+            c->sf_cur = dst; c->sf_n /= 2;
+        }
+        const size_t n = c->sf_n, ld = sc_ld(c, n);
+        const W *t5 = T[c->sf_cur];
+        typename R::FoldA a;
+        a.eqL = t5; a.eqR = t5 + TAU * ld; a.eqB = t5 + 2 * TAU * ld; a.G1 = t5 + 3 * TAU * ld; a.G2 = t5 + (3 * TAU + RE) * ld;
+        a.ld = ld; a.n = n; a.p0 = 0; a.pcnt = n / 2; a.pF0 = 0;
+        c->sf_round++;
+        if constexpr (R::small_base)
+            if (P.b != 2) return sb_fold_round_abi(c, t5, F[c->sf_cur], n, d_mu, evals_out);
+        launch_fold_round(R::tab(c), a, F[c->sf_cur], ld, P.K, d_mu, partial, od, c->stream());
+        return down_small(c, od, (size_t)(2 * P.b + 1) * RE, evals_out);
+    }
+    static int sumcheck_fold_end(C *c) {
+        std::lock_guard<std::mutex> g(c->mu);
+        c->sf_round = -1;
+        return LF_OK;
     }
 
     // ---- witnesses ----
@@ -400,7 +849,7 @@ struct ring_ops<Ring<C>> {
     }
     static int witness_commit(C *c, const lf_witness *w, u64 *cm_out) {
         std::lock_guard<std::mutex> g(c->mu);
-        if (!R::have_A(c)) return LF_ERR_STATE;
+        if (!c->A_loaded) return LF_ERR_STATE;
         if (w->N != c->nA_total) return LF_ERR_INVALID;
         HIPCHK(hipSetDevice(c->device));
         u64 *o;
@@ -456,6 +905,7 @@ using lfring::ring_ops;
 // the staging and commit helpers the provers of both backends call (unqualified, from the global namespace and from lfbb)
 using lfring::commit_dev_i8g;
 using lfring::commit_dev_pre;
+using lfring::commit_planes_i8;
 using lfring::down_ring;
 using lfring::pow2;
 using lfring::up_ring;

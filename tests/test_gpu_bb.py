@@ -6,7 +6,7 @@ import pytest
 
 import lfo_bb as lfo
 from latticefold_amd import api
-from latticefold_amd.workload import diag, make_workload, splitmix_fq
+from latticefold_amd.workload import chain_w_ccs, diag, make_workload, splitmix_fq
 
 pytestmark = pytest.mark.gpu
 RING = "babybear"
@@ -568,3 +568,166 @@ def test_error_codes_around_dispatch(ring, name):
                          "mat_vec_mul before load_ccs": -7, "mat_vec_mul j = t": -1}
     finally:
         c.close()
+
+
+# ---- the set-up, commit and sumcheck bodies the two rings share ----------------------------------------------------
+def _oracle(ring):
+    if ring == "goldilocks":
+        import lfo as O
+        return O
+    return lfo
+
+
+@pytest.mark.parametrize("ring,kappa", [("goldilocks", 27), ("babybear", 17)])
+def test_streamed_matrix_install(ring, kappa):
+    """the matrix is installed one row at a time: kappa crosses a row-chunk boundary of the int8 kernel (14 + 13 rows on Goldilocks, 9 + 8 on BabyBear) and
+    n = 9 columns are two column tiles, the second ragged.  A loaded matrix, a generated one and a second, smaller one in the same context all commit exactly"""
+    O = _oracle(ring)
+    c = api.Context(0, ring=ring)
+    try:
+        n, RE_ = 9, c.RE
+        A = splitmix_fq(31, 0, kappa * n * RE_, ring).reshape(kappa, n, RE_)
+        f = splitmix_fq(32, 0, n * RE_, ring).reshape(n, RE_)
+        assert (api.AjtaiCommitmentScheme(c, matrix=A).commit_ntt(f) == O.ajtai_commit(A, kappa, n, f)).all()
+        seed = 0xA17A1 + 5
+        G = splitmix_fq(seed, 0, kappa * n * RE_, ring).reshape(kappa, n, RE_)     # Workload.ajtai_matrix of that seed
+        assert (api.AjtaiCommitmentScheme(c, kappa=kappa, n=n, seed=seed).commit_ntt(f) == O.ajtai_commit(G, kappa, n, f)).all()
+        k2, n2 = 6, 17
+        A2 = splitmix_fq(33, 0, k2 * n2 * RE_, ring).reshape(k2, n2, RE_)
+        f2 = splitmix_fq(34, 0, n2 * RE_, ring).reshape(n2, RE_)
+        assert (api.AjtaiCommitmentScheme(c, matrix=A2).commit_ntt(f2) == O.ajtai_commit(A2, k2, n2, f2)).all()
+    finally:
+        c.close()
+
+
+def _shared_body_codes(ring, name):
+    """return codes of invalid calls into the set-up, commit and sumcheck-ABI bodies (0 = accepted)"""
+    import copy
+    import ctypes as C
+    L = api._lib()
+    c = api.Context(0, ring=ring)
+    codes = {}
+
+    def code(key, fn):
+        try:
+            fn()
+            codes[key] = 0
+        except api.LfError as e:
+            codes[key] = e.code
+    try:
+        RE_, TAU_ = c.RE, c.TAU
+        lim = 128 if ring == "goldilocks" else 32
+        x = splitmix_fq(1, 0, 8 * RE_, ring).reshape(8, RE_)
+        o = np.zeros((lim + 1, RE_), dtype=np.uint64)
+        xp, op = x.ctypes.data_as(api.u64p), o.ctypes.data_as(api.u64p)
+        codes["commit before load"] = L.lf_ajtai_commit(c.h, xp, 8, 1, op)
+        big = np.zeros((lim + 1, 1, RE_), dtype=np.uint64)
+        codes["load kappa limit + 1"] = L.lf_ajtai_load(c.h, big.ctypes.data_as(api.u64p), lim + 1, 1)
+        codes["commit after refused load"] = L.lf_ajtai_commit(c.h, xp, 1, 1, op)
+        s = api.AjtaiCommitmentScheme(c, matrix=splitmix_fq(2, 0, 3 * 8 * RE_, ring).reshape(3, 8, RE_))
+        codes["commit n != width"] = L.lf_ajtai_commit(c.h, xp, 7, 1, op)
+        codes["decompose_and_commit count L != width"] = L.lf_ajtai_decompose_and_commit_coeff(c.h, xp, 3, 4, 2, 1, op)
+        codes["decompose_and_commit base 6"] = L.lf_ajtai_decompose_and_commit_coeff(c.h, xp, 4, 6, 2, 1, op)
+        codes["set_sharding after load"] = L.lf_set_sharding(c.h, 0, 1, api.EXCHANGE_FN(0), None)
+        z = np.zeros(TAU_, dtype=np.uint64)
+        codes["lin round before begin"] = L.lf_sumcheck_lin_round(c.h, None, op)
+        codes["fold round before begin"] = L.lf_sumcheck_fold_round(c.h, None, op)
+        code("ccs_load t 5 d 4", lambda: c.load_ccs(make_workload(name, ccs="deg4")))
+        wl = make_workload(name)
+        bad = copy.copy(wl)
+        bad.S_idx = np.asarray(wl.S_idx)[::-1].copy()
+        code("ccs_load multisets not 0..t-1", lambda: c.load_ccs(bad))
+        c.load_ccs(wl)
+        tabs = splitmix_fq(3, 0, wl.t * wl.m * RE_, ring).reshape(wl.t, wl.m, RE_)
+        sc = api.MLSumcheckLin(c, tabs, splitmix_fq(4, 0, wl.s * TAU_, ring).reshape(wl.s, TAU_))
+        code("lin first round with r_prev", lambda: sc.prove_round(z))
+        sc.prove_round(None)
+        for _ in range(wl.s - 1):
+            sc.prove_round(z)
+        code("lin round after the last", lambda: sc.prove_round(z))
+        sc.end()
+        K2 = 2 * wl.K
+        ft = np.zeros((5 + K2 * TAU_, wl.m, RE_), dtype=np.uint64)
+        sf = api.MLSumcheckFold(c, ft, np.zeros((K2, TAU_), dtype=np.uint64))
+        code("fold first round with r_prev", lambda: sf.prove_round(z))
+        sf.prove_round(None)
+        for _ in range(wl.s - 1):
+            sf.prove_round(z)
+        code("fold round after the last", lambda: sf.prove_round(z))
+        sf.end()
+    finally:
+        c.close()
+    return codes
+
+
+# LF_ERR_INVALID -1, LF_ERR_UNSUPPORTED -3, LF_ERR_STATE -7
+_SHARED_CODES = {"commit before load": -7, "load kappa limit + 1": -1, "commit after refused load": -7, "commit n != width": -1,
+                 "decompose_and_commit count L != width": -1, "decompose_and_commit base 6": -3, "set_sharding after load": -7,
+                 "lin round before begin": -7, "fold round before begin": -7, "ccs_load t 5 d 4": -3, "ccs_load multisets not 0..t-1": -3,
+                 "lin first round with r_prev": -7, "lin round after the last": -7, "fold first round with r_prev": -7, "fold round after the last": -7}
+SHARED_BODY_CODES = {"babybear": _SHARED_CODES, "goldilocks": dict(_SHARED_CODES, **{"ccs_load t 5 d 4": 0})}
+
+
+@pytest.mark.parametrize("ring,name", [("goldilocks", "T8"), ("babybear", "B6")])
+def test_error_codes_around_shared_bodies(ring, name):
+    """what an invalid call into the shared set-up, commit and sumcheck-ABI bodies returns, as recorded on the commit before they were merged.  The rings
+    differ in one place only: a constraint system with t = 5, d = 4 loads on Goldilocks (the wide envelope) and is LF_ERR_UNSUPPORTED on BabyBear"""
+    codes = _shared_body_codes(ring, name)
+    print(ring, codes)
+    assert codes == SHARED_BODY_CODES[ring]
+
+
+def _fold_step(ring, name, ingest):
+    """one fold step against the oracle; ingest: a second witness is ingested on the same context while the step runs (lf_witness_from_w_ccs_begin /
+    lf_witness_job_finish) and compared with from_w_ccs.  Returns the context's read-outs of the step"""
+    O = _oracle(ring)
+    wl = make_workload(name)
+    inst = O.Instance(wl)
+    c = api.Context(0, ring=ring)
+    try:
+        c.load_ccs(wl)
+        A = wl.ajtai_matrix()
+        scheme = api.AjtaiCommitmentScheme(c, matrix=A)
+        wit = api.Witness.from_w_ccs(c, wl.w_ccs)
+        cccs = np.concatenate([wit.commit(scheme), wl.x_ccs])
+        tr = lambda: api.PoseidonTranscript(ring=ring)
+        acc, _ = api.LFLinearizationProver.prove(c, cccs, wit, tr())
+        w2 = chain_w_ccs(wl, 1)
+        pending = api.Witness.from_w_ccs_begin(c, w2) if ingest else None
+        lc, w0, proof = api.NIFSProver.prove(c, acc, wit, cccs, wit, tr())
+        ph, ks, paths, split = c.phase_ms(), c.kernel_stats(), c.fold_paths(), c.fold_split_rounds()
+        f_coeff = inst.witness_from_w_ccs(wl.w_ccs)
+        acc_o, _ = inst.linearize(O.Transcript(), cccs, f_coeff)
+        lc_o, f0_o, proof_o = inst.fold_step(O.Transcript(), A, acc_o, f_coeff, cccs, f_coeff)
+        assert (proof == proof_o).all() and (lc == lc_o).all() and (w0.f == f0_o).all()
+        if ingest:
+            w_in = pending.result()
+            assert (w_in.f_coeff == inst.witness_from_w_ccs(w2)).all() and (w_in.w_ccs == w2).all()
+        return ph, {"fold_round_launches": ks["fold_round_launches"], "ajtai_launches": ks["ajtai_launches"], "fold_paths": paths, "fold_split_rounds": split}
+    finally:
+        c.close()
+
+
+def _step_readouts(ring, name):
+    return _fold_step(ring, name, False)
+
+
+# launch counts (not times) and path masks of one T8 / B6 fold step, recorded on the commit before the contexts shared one core
+STEP_READOUTS = {"goldilocks": {"fold_round_launches": 4, "ajtai_launches": 2, "fold_paths": 0, "fold_split_rounds": 0},
+                 "babybear": {"fold_round_launches": 6, "ajtai_launches": 4, "fold_paths": 0, "fold_split_rounds": 0}}
+
+
+@pytest.mark.parametrize("ring,name", [("goldilocks", "T8"), ("babybear", "B6")])
+def test_readouts_after_a_step(ring, name):
+    """the read-outs of one fold step report what they reported before the contexts shared one core: positive total and host-transcript times, the same launch
+    counts and the same path masks (the step itself is checked against the oracle)"""
+    ph, counts = _step_readouts(ring, name)
+    print(ring, ph, counts)
+    assert ph["total"] > 0 and ph["host_transcript"] > 0
+    assert counts == STEP_READOUTS[ring]
+
+
+def test_ingestion_on_lane_2_next_to_a_step():
+    """T8, Goldilocks: one lf_witness_from_w_ccs_begin / lf_witness_job_finish runs on lane 2 (its stream, its "lane2:" buffers, its per-lane slots) while a
+    fold step runs on the same context: the step's proof equals the oracle's and the ingested witness equals from_w_ccs (both asserted in _fold_step)"""
+    _fold_step("goldilocks", "T8", True)
