@@ -215,9 +215,9 @@ typedef struct {
     uint32_t t, q, d; /* #matrices, #multisets, degree */
 } lf_params;
 /* matrices in CSR (rows m = 1<<s, cols n = l + 1 + wit_len), values = NTT-form ring elements.
- * Envelope: t <= 4, d <= 3 on every context; t <= 8, d <= 7 on a Goldilocks context with one unsharded GPU (q <= 8 and S_off[q] <= 16 either way; the
- * multisets concatenate to 0..t-1).  Anything wider -- d >= 8, t >= 9, or t > 4 / d > 3 on a BabyBear or sharded context -- is LF_ERR_UNSUPPORTED and leaves
- * the context as it was. */
+ * Envelope: t <= 4, d <= 3 on every context; t <= 8, d <= 7 on a Goldilocks context at b = 2, sharded (lf_set_sharding, lf_dist_init, lf_set_sharding_model)
+ * or not, and at b = 4, 8, 16 on one unsharded GPU (q <= 8 and S_off[q] <= 16 either way; the multisets concatenate to 0..t-1).  Anything wider -- d >= 8,
+ * t >= 9, or t > 4 / d > 3 on a BabyBear context -- is LF_ERR_UNSUPPORTED and leaves the context as it was. */
 int lf_ccs_load(lf_ctx *, const lf_params *, const uint32_t *const *rowptr, const uint32_t *const *col,
                 const uint64_t *const *val, const uint32_t *S_off, const uint32_t *S_idx, const uint64_t *c);
 /* mat_vec_mul (arith/utils.rs:52-65): out (m ring elements) = M_j * z (n ring elements) */

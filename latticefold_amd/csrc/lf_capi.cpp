@@ -609,8 +609,6 @@ int lf_ccs_load(lf_ctx *c, const lf_params *p, const uint32_t *const *rowptr, co
     if (p->s < 3 || p->s > 30 || p->t == 0 || p->t > 8 || p->q == 0 || p->q > 8 || p->K == 0 || p->K > 32 || p->L == 0 || p->L > 8 ||
         p->d > 7 || p->wit_len == 0)
         return LF_ERR_UNSUPPORTED;
-    // the wide envelope (t > 4 or d > 3: k_lin_round_wide and the chunked launches below it) runs on one unsharded GPU
-    if ((p->t > 4 || p->d > 3) && (c->sh_world > 1 || c->comm[0].model)) return LF_ERR_UNSUPPORTED;
     // b = 2: the bit-plane kernels of the reference Goldilocks rows; b = 4, 8, 16: the small-base path (lf_sb.h), one unsharded GPU
     if (p->b != 2 && !sb_base_ok(p->b)) return LF_ERR_UNSUPPORTED;
     if (p->b != 2 && (c->sh_world > 1 || c->comm[0].model || p->K > 11)) return LF_ERR_UNSUPPORTED;   // (K - 1 <= 10 planes of one commit launch)

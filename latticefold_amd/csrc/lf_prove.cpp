@@ -51,7 +51,7 @@ static int run_lin_sumcheck(lf_ctx *c, Transcript &tr, const u64 *mz, const u64 
     const size_t Gw = (size_t)c->sh_world, gr = (size_t)c->sh_rank;
     bool sharded = shard_keep(c, 0, m);
     u64 *od_dev = nullptr;
-    if (Gw > 1) RET(c->tbuf("lin_round_out", 5 * 24 + 8, &od_dev));
+    if (Gw > 1) RET(c->tbuf("lin_round_out", (size_t)(deg + 1) * 24 + 8, &od_dev));   // (up to d + 2 = 9 points in the wide envelope)
     // split form: while `split` is set, cure is the per-pair table E_i of the round i that ran last (in fe[(i - 1) & 1]) and c_lvl = c_i = prod_{k<i} eq(beta_k, r_k)
     const u32 dT = P.d;                                          // degree of T_i; the message has degree dT + 1 = deg
     const bool wide = P.t > 4 || P.d > 3;                        // k_lin_round_wide (lf_lin_wide.hip): per-round launches only, no persistent tail
