@@ -28,6 +28,9 @@
 //! /root/reference and of stark-rings@886a89f as the reference uses it; `tests/test_rust_wrapper_cpu.py` checks names and arities against the reference sources.
 #![forbid(unsafe_op_in_unsafe_fn)]
 
+/// LatticeFold+ (`crates/latticefold-plus`): `HipPlusProver` / `HipPlusVerifier` over the prover and verifier objects of include/lfplus.h
+pub mod plus;
+
 use core::marker::PhantomData;
 use std::sync::{Arc, Mutex, OnceLock};
 

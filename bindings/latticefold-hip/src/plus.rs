@@ -1,0 +1,243 @@
+//! LatticeFold+ behind the reference's `PlusProver` / `PlusVerifier` surface (`crates/latticefold-plus/src/plus.rs:15-146`) over the prover and verifier
+//! objects of `include/lfplus.h` (`lfplus_prover_*`, `lfplus_verify`).
+//!
+//! | reference (file:line)                                   | here                                           |
+//! |---------------------------------------------------------|------------------------------------------------|
+//! | `PlusProver::{init, prove}` `plus.rs:55-108`            | [`HipPlusProver::init`], [`HipPlusProver::prove`] |
+//! | `PlusVerifier::{init, verify}` `plus.rs:118-143`        | [`HipPlusVerifier::init`], [`HipPlusVerifier::verify`] (host only) |
+//! | `PlusProof` `plus.rs:34-40`                             | [`PlusProof`]: the flat words of `lfplus.h`    |
+//! | `PlusParameters` `plus.rs:42-47`                        | [`PlusParameters`] (`sys::lfplus_params`)      |
+//! | `PoseidonTranscript<RqPoly>` `transcript.rs:20-78`      | [`HipPlusTranscript`]                          |
+//!
+//! The ring is the one the reference runs latticefold-plus on (FrogRing `RqPoly`, coefficient form, 16 canonical words per element); `R: RingWords` with
+//! `WORDS == 16` marshals it.  The schedule of a prove -- which context holds which accumulator half, the upload thread, the refusal to continue after a
+//! half-advanced transcript -- is the library's; this module only marshals.  NOT COMPILED in the build image, as the rest of the crate;
+//! `tests/test_lfplus_native_cpu.py` checks names and arities against the reference.
+#![allow(non_snake_case)]
+
+use core::marker::PhantomData;
+
+use latticefold_hip_sys as sys;
+use stark_rings_linalg::{Matrix, SparseMatrix};
+
+use crate::{flatten, RingWords};
+
+/// A failure of the LatticeFold+ ABI: `code` is the library's `LFPLUS_E_*` value (`sys::LFPLUS_E_ARG`, `sys::LFPLUS_E_REJECT`, ...)
+#[derive(Debug, Clone, thiserror::Error)]
+#[error("liblfhip (lfplus): {what}: {msg} ({code})")]
+pub struct HipPlusError {
+    pub code: i32,
+    pub what: &'static str,
+    pub msg: String,
+}
+
+impl HipPlusError {
+    fn new(code: i32, what: &'static str, msg: impl Into<String>) -> Self {
+        HipPlusError { code, what, msg: msg.into() }
+    }
+    /// `LFPLUS_E_ARG`: a shape, a length or the object's state refuses the call
+    pub fn is_arg(&self) -> bool {
+        self.code == sys::LFPLUS_E_ARG
+    }
+    /// `LFPLUS_E_REJECT`: a verifier rejected the proof
+    pub fn is_reject(&self) -> bool {
+        self.code == sys::LFPLUS_E_REJECT
+    }
+}
+
+/// `PlusParameters { lin: LinParameters { kappa, decomp: DecompParameters { b, k, l } }, B }`, flat
+pub type PlusParameters = sys::lfplus_params;
+
+/// `PlusProof` as the flat canonical words `lfplus.h` documents (header, per fresh instance `msgs | r | evals`, the `CmProof` fields, `linb2x`, `dproof`)
+#[derive(Debug, Clone, PartialEq, Eq)]
+pub struct PlusProof(pub Vec<u64>);
+
+impl PlusProof {
+    /// `lfplus_proof_len`: the words of a proof that folds `L` instances, `nfresh` of them fresh
+    pub fn len_for(params: &PlusParameters, n: usize, nM: usize, L: usize, nfresh: usize) -> usize {
+        // SAFETY: params is a valid reference; the call reads nothing else
+        unsafe { sys::lfplus_proof_len(params, n as u64, nM as u32, L as u32, nfresh as u32) as usize }
+    }
+}
+
+/// `PoseidonTranscript::<RqPoly>::empty::<FrogPoseidonConfig>()`: the host sponge the library advances
+pub struct HipPlusTranscript {
+    raw: *mut sys::lfplus_transcript,
+}
+// SAFETY: a transcript is a plain host object with no thread affinity; `&mut self` serialises its users
+unsafe impl Send for HipPlusTranscript {}
+
+impl Default for HipPlusTranscript {
+    fn default() -> Self {
+        // SAFETY: returns an owned handle (never null: the allocation aborts on failure)
+        HipPlusTranscript { raw: unsafe { sys::lfplus_transcript_new() } }
+    }
+}
+impl Clone for HipPlusTranscript {
+    fn clone(&self) -> Self {
+        // SAFETY: self.raw is a live handle
+        HipPlusTranscript { raw: unsafe { sys::lfplus_transcript_clone(self.raw) } }
+    }
+}
+impl Drop for HipPlusTranscript {
+    fn drop(&mut self) {
+        // SAFETY: the handle is owned and freed exactly once
+        unsafe { sys::lfplus_transcript_free(self.raw) }
+    }
+}
+impl HipPlusTranscript {
+    pub fn absorb<R: RingWords>(&mut self, v: &[R]) {
+        let w = flatten(v);
+        // SAFETY: w holds v.len() ring elements of 16 words
+        unsafe { sys::lfplus_transcript_absorb(self.raw, w.as_ptr(), v.len()) };
+    }
+    pub fn get_challenge(&mut self) -> u64 {
+        let mut out = 0u64;
+        // SAFETY: out is one word
+        unsafe { sys::lfplus_transcript_challenge(self.raw, &mut out) };
+        out
+    }
+}
+
+/// CSR triples (`rowptr`, `col`, `val[nnz][16]`) of a `SparseMatrix<R>` padded to `n` rows
+fn csr<R: RingWords + Clone>(m: &SparseMatrix<R>, n: usize) -> (Vec<u32>, Vec<u32>, Vec<u64>) {
+    let (mut rowptr, mut col, mut val) = (vec![0u32], Vec::new(), Vec::new());
+    for row in &m.coeffs {
+        for (c, j) in row {
+            col.push(*j as u32);
+            c.to_words(&mut val);
+        }
+        rowptr.push(col.len() as u32);
+    }
+    rowptr.resize(n + 1, col.len() as u32);
+    (rowptr, col, val)
+}
+
+/// A fresh `ComR1CS` instance in host form: the witness `f` (n ring elements) and its commitment `cm_f` (kappa ring elements), flat
+pub struct HipComR1CS {
+    pub f: Vec<u64>,
+    pub cm_f: Vec<u64>,
+}
+
+impl HipComR1CS {
+    pub fn new<R: RingWords>(f: &[R], cm_f: &[R]) -> Self {
+        HipComR1CS { f: flatten(f), cm_f: flatten(cm_f) }
+    }
+}
+
+/// `PlusProver<R, TS>`: 2 + ncomp device contexts sharing A and M, the accumulator resident between proves
+pub struct HipPlusProver<R> {
+    raw: *mut sys::lfplus_prover,
+    // private: the C object holds this handle's raw pointer for its whole life, so the field must never be replaced (see `transcript`)
+    transcript: HipPlusTranscript,
+    pub params: PlusParameters,
+    n: usize,
+    nM: usize,
+    nacc: usize,
+    _r: PhantomData<R>,
+}
+// SAFETY: the object has no thread affinity (every entry point selects its device); `&mut self` gives the one-thread-at-a-time the header asks for
+unsafe impl<R> Send for HipPlusProver<R> {}
+
+impl<R: RingWords + Clone> HipPlusProver<R> {
+    /// Initialize (plus.rs:55-74) on device 0
+    pub fn init(A: Matrix<R>, M: Vec<SparseMatrix<R>>, ncomp: usize, params: PlusParameters, transcript: HipPlusTranscript) -> Result<Self, HipPlusError> {
+        assert_eq!(R::WORDS, 16, "the LatticeFold+ ABI is the Frog ring: 16 words per element");
+        let n = A.ncols;
+        let a_words: Vec<u64> = A.vals.iter().flat_map(|row| flatten(row)).collect();
+        let mats: Vec<_> = M.iter().map(|m| csr(m, n)).collect();
+        let rp: Vec<*const u32> = mats.iter().map(|m| m.0.as_ptr()).collect();
+        let cp: Vec<*const u32> = mats.iter().map(|m| m.1.as_ptr()).collect();
+        let vp: Vec<*const u64> = mats.iter().map(|m| m.2.as_ptr()).collect();
+        let mut raw = core::ptr::null_mut();
+        // SAFETY: every pointer outlives the call (the library copies A and M to the device); the transcript handle outlives the prover, which owns it
+        let rc = unsafe {
+            sys::lfplus_prover_create(0, &params, a_words.as_ptr(), 0, n as u64, M.len() as u32, rp.as_ptr(), cp.as_ptr(), vp.as_ptr(), ncomp as u32, transcript.raw, &mut raw)
+        };
+        if rc != sys::LFPLUS_OK {
+            return Err(HipPlusError::new(rc, "lfplus_prover_create", "no usable device, or parameters outside the envelope"));
+        }
+        Ok(HipPlusProver { raw, transcript, params, n, nM: M.len(), nacc: 0, _r: PhantomData })
+    }
+
+    /// The transcript the prover advances (`PlusProver::transcript` of the reference, read-only here: the library borrows the handle until the prover is
+    /// dropped).  Clone it to continue the Fiat-Shamir schedule elsewhere.
+    pub fn transcript(&self) -> &HipPlusTranscript {
+        &self.transcript
+    }
+
+    fn err(&self, rc: i32, what: &'static str) -> HipPlusError {
+        // SAFETY: returns a NUL-terminated string owned by the prover, valid until its next call
+        let msg = unsafe { std::ffi::CStr::from_ptr(sys::lfplus_prover_last_error(self.raw)) }.to_string_lossy().into_owned();
+        HipPlusError::new(rc, what, msg)
+    }
+
+    /// Prove (plus.rs:77-108): the fresh instances go up on the library's worker thread while the ones that have arrived are linearized
+    pub fn prove(&mut self, comp: &[HipComR1CS]) -> Result<PlusProof, HipPlusError> {
+        let fp: Vec<*const u64> = comp.iter().map(|c| c.f.as_ptr()).collect();
+        let cp: Vec<*const u64> = comp.iter().map(|c| c.cm_f.as_ptr()).collect();
+        // SAFETY: `comp` is borrowed for the whole call, which covers the span the library borrows f for (until lfplus_prover_prove returns)
+        let rc = unsafe { sys::lfplus_prover_set_instances(self.raw, fp.as_ptr(), cp.as_ptr(), comp.len() as u32) };
+        if rc != sys::LFPLUS_OK {
+            return Err(self.err(rc, "lfplus_prover_set_instances"));
+        }
+        let words = PlusProof::len_for(&self.params, self.n, self.nM, self.nacc + comp.len(), comp.len());
+        let mut proof = vec![0u64; words];
+        // SAFETY: proof holds exactly the words the library checks the length against
+        let rc = unsafe { sys::lfplus_prover_prove(self.raw, proof.as_mut_ptr(), words as u64) };
+        if rc != sys::LFPLUS_OK {
+            return Err(self.err(rc, "lfplus_prover_prove"));
+        }
+        self.nacc = 2;
+        Ok(PlusProof(proof))
+    }
+}
+
+impl<R> Drop for HipPlusProver<R> {
+    fn drop(&mut self) {
+        // SAFETY: owned handle, destroyed once, before the transcript field it borrows is dropped
+        unsafe { sys::lfplus_prover_destroy(self.raw) }
+    }
+}
+
+/// `PlusVerifier<R, TS>` (host only: no GPU, no context)
+pub struct HipPlusVerifier<R> {
+    pub transcript: HipPlusTranscript,
+    pub params: PlusParameters,
+    n: usize,
+    nM: usize,
+    nacc: usize,
+    _r: PhantomData<R>,
+}
+
+impl<R: RingWords> HipPlusVerifier<R> {
+    /// Initialize (plus.rs:118-130): only the shapes of A and M enter the verification
+    pub fn init(A: Matrix<R>, M: Vec<SparseMatrix<R>>, params: PlusParameters, transcript: HipPlusTranscript) -> Self {
+        HipPlusVerifier { transcript, params, n: A.ncols, nM: M.len(), nacc: 0, _r: PhantomData }
+    }
+
+    /// Verify (plus.rs:133-143) a proof that folds `nfresh` fresh instances into this verifier's accumulator.  `Err` with `LFPLUS_E_REJECT` and the
+    /// `(which, stage)` of the sub-verifier in the message where the reference panics; `LFPLUS_E_ARG` for a buffer that does not fit the statement
+    pub fn verify_fresh(&mut self, proof: &PlusProof, nfresh: usize) -> Result<bool, HipPlusError> {
+        let (mut which, mut stage) = (0i32, 0i32);
+        let L = self.nacc + nfresh;
+        // SAFETY: the library checks proof.0.len() against its own layout before it reads a field
+        let rc = unsafe {
+            sys::lfplus_verify(&self.params, self.n as u64, self.nM as u32, L as u32, nfresh as u32, self.transcript.raw, proof.0.as_ptr(), proof.0.len() as u64, &mut which, &mut stage)
+        };
+        if rc != sys::LFPLUS_OK {
+            return Err(HipPlusError::new(rc, "lfplus_verify", format!("which = {which}, stage = {stage}")));
+        }
+        self.nacc = 2;
+        Ok(true)
+    }
+
+    /// Verify with the reference's signature.  The reference takes the number of fresh instances from the proof it is handed (`proof.lproof.len()`,
+    /// plus.rs:134-136); this mirrors it deliberately by reading the header's nfresh word and passing it on as the statement.  Nothing is SIZED from that
+    /// word: the library derives the one admissible length from (params, n, nM, L, nfresh) and refuses any other buffer before it reads a field.  A caller
+    /// that knows how many instances it expects calls [`HipPlusVerifier::verify_fresh`] with its own count.
+    pub fn verify(&mut self, proof: &PlusProof) -> bool {
+        let nfresh = proof.0.get(2).copied().unwrap_or(0) as usize;
+        self.verify_fresh(proof, nfresh).unwrap_or(false)
+    }
+}

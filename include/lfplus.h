@@ -15,6 +15,7 @@
  *   PoseidonTranscript<RqPoly>, utils::short_challenge       src/transcript.rs:20-78, src/utils.rs:87-101
  *   In::set_check / Out::verify                      src/setchk.rs:65-262 / 266-340
  *   Rg::range_check / Dcom::verify                   src/rgchk.rs:81-186 / 193-258
+ *   PlusProver::{init, prove} / PlusVerifier::{init, verify}   src/plus.rs:15-146   (lfplus_prover_*, lfplus_verify: the objects, at the end of this file)
  *
  * M_f and m_tau are matrices / vectors of unit monomials; they cross this boundary as their EXPONENT digits (int8 in (-d/2, d/2)):
  * exp(a) = X^a for a >= 0 and X^(d + a) for a < 0.  The Rust binding rebuilds Matrix<R> from them if a caller needs the dense form
@@ -84,6 +85,13 @@ int lfplus_set_sharding_model(lfplus_ctx *ctx, int rank, int world);
 /* Ajtai matrix A (kappa x n ring elements, row-major, coefficient form); stays resident in HBM.  kappa <= 64.  In a sharded context: the rank's columns,
  * kappa x (n / world), and `n` is that local width. */
 int lfplus_set_matrix(lfplus_ctx *ctx, const uint64_t *A, uint32_t kappa, uint64_t n);
+/* The commitment matrix generated on the device from a seed instead of uploaded: word w of the row-major kappa x n x 16 matrix is
+ * splitmix64(seed + (w + 1) G) mod p, G = 0x9E3779B97F4A7C15 (the indexable stream of PlusWorkload.ajtai_matrix; lf_ajtai_generate is the counterpart on the
+ * LatticeFold side).  A pure write stream: no host generation, no upload.  Preconditions as lfplus_set_matrix: kappa <= 64, n <= 2^32, before the witness
+ * (LFPLUS_E_ARG once the context holds one); a sharded context is refused (a rank uploads its columns).  The _timed form repeats the fill `iters` times between
+ * two HIP events: average ms. */
+int lfplus_matrix_generate(lfplus_ctx *ctx, uint64_t seed, uint32_t kappa, uint64_t n);
+int lfplus_matrix_generate_timed(lfplus_ctx *ctx, uint64_t seed, uint32_t kappa, uint64_t n, uint32_t iters, double *ms_avg);
 /* use the commitment matrix resident in `from` (same device) without copying it; the allocation is reference-counted and lives until its last holder
  * re-uploads or is destroyed */
 int lfplus_share_matrix(lfplus_ctx *ctx, lfplus_ctx *from);
@@ -239,6 +247,83 @@ int lfplus_mlin(lfplus_ctx *const *ctxs, uint32_t L, lfplus_transcript *t, uint6
                 const uint32_t *const *col, const uint64_t *const *val, uint64_t *r_out, uint64_t *msgs, uint64_t *e_out, uint64_t *b_out, uint64_t *v_out,
                 uint64_t *a_out, uint64_t *bb_out, uint64_t *c_out, uint64_t *comh, uint64_t *pa, uint64_t *pb, uint64_t *ea, uint64_t *eb, uint64_t *cm_g,
                 uint64_t *ro, uint64_t *vo, uint64_t *fcoms_out, uint64_t *cm_g_sum, uint64_t *vo_sum);
+
+/* ---- PlusProver / PlusVerifier as objects (src/plus.rs:15-146) and the flat PlusProof --------------------------------------------------------------
+ * PlusParameters (plus.rs:43-47) with LinParameters and DecompParameters flattened: kappa (rows of A), the digit base b, k digits and l gadget digits of the
+ * range check, and the decomposition base B of Decomp::decompose (also the base of ComR1CS::new's gadget decomposition of z). */
+typedef struct { uint32_t kappa, k, l; uint64_t b, B; } lfplus_params;
+
+/* The flat PlusProof: canonical u64 words, LFPLUS_PROOF_HEADER words of header and then the fields back to back in ONE fixed order
+ * (nvars = log2 n, per = 4 + 4 nM, d = 16; sizes in words):
+ *   header        LFPLUS_PROOF_MAGIC, L, nfresh, nvars, k, l, kappa, nM
+ *   per fresh instance i < nfresh (ComR1CSProof, r1cs.rs:62-74)
+ *     msgs        nvars * 4 * d          r        nvars          evals    4 * d
+ *   CmProof (cm.rs:24-54), in the order lfplus_mlin takes the pointers
+ *     r           nvars                  msgs     nvars * 4 * d  e        (1 + nM) * L * k * d * d
+ *     b           L * d                  v        L * d          a        L * (1 + nM)
+ *     bb          L * (1 + nM) * d       c        L * (1 + nM) * d
+ *     comh        L * kappa * d          pa       nvars * 3 * d  pb       nvars * 3 * d
+ *     ea          L * per * d            eb       L * per * d
+ *     cm_g        L * kappa * d          ro       2 * nvars      vo       L * (1 + nM) * 2 * d
+ *     fcoms       L * 3 * kappa * d      (cm_f | C_Mf | cm_mtau per instance)
+ *   LinB2X (mlin.rs:21-40)
+ *     cm_g        kappa * d              ro       2 * nvars      vo       (1 + nM) * 2 * d
+ *   DecompProof (decomp.rs:24-30)
+ *     C0, C1      kappa * d each         v0, v1   (1 + nM) * 2 * d each
+ * L = accumulated + fresh instances folded by the prove (2 + nfresh, or nfresh for the first).  lfplus_proof_fields = 3 nfresh + 24 is the number of fields,
+ * lfplus_proof_len the total length in words (0: parameters outside the envelope), lfplus_proof_layout writes the offset (in words from the start of the
+ * buffer) and the length of every field in the order above (nfields must equal lfplus_proof_fields(nfresh)).  Envelope: n = 2^nvars, 1 <= nvars <= 32,
+ * 1 <= L, nfresh <= L <= 4096, 1 <= k <= 16, 1 <= l <= 64, 1 <= kappa <= 64, nM <= 64.  The header is there to be CHECKED: a verifier compares it with its own
+ * parameters and never sizes anything from it. */
+#define LFPLUS_PROOF_HEADER 8
+#define LFPLUS_PROOF_MAGIC 0x4C46504C55533031ULL   /* the bytes "LFPLUS01", most significant first (a canonical word: below p) */
+uint32_t lfplus_proof_fields(uint32_t nfresh);
+uint64_t lfplus_proof_len(const lfplus_params *params, uint64_t n, uint32_t nM, uint32_t L, uint32_t nfresh);
+int lfplus_proof_layout(const lfplus_params *params, uint64_t n, uint32_t nM, uint32_t L, uint32_t nfresh, uint64_t *offsets, uint64_t *lengths, uint32_t nfields);
+
+/* PlusProver::init (plus.rs:55-74) on one device: 2 + ncomp contexts, the commitment matrix A (kappa x n x 16 words; NULL: generated on the device from `seed`,
+ * lfplus_matrix_generate) and the nM constraint-system matrices (n x n, CSR, as lfplus_set_matrices) installed in the first and shared with the rest.  The
+ * instances a prover folds are ComR1CS over these matrices (every reference use has M = cr1cs.x.matrices()), so nM must be 3.  The transcript is BORROWED: the
+ * caller keeps ownership, it must outlive the prover and is advanced by lfplus_prover_prove only.  Unsharded only (a column-sharded prover is built from the
+ * context-level calls).  The accumulator (F0, F1) of a prove stays on the device, in the first two contexts, as input of the next prove.
+ *
+ * State machine.  ingest / set_instances name the fresh instances of the NEXT prove (one of the two, once per prove: a second call before the prove is
+ * LFPLUS_E_ARG); more instances than free contexts (ncomp after the first prove, 2 + ncomp before it) is LFPLUS_E_ARG and touches nothing.  An error INSIDE
+ * ingest, set_instances or prove leaves witnesses half-installed or the Fiat-Shamir transcript half-advanced: the prover is then FAILED and every later call
+ * except lfplus_prover_destroy and lfplus_prover_last_error returns LFPLUS_E_ARG with a message.  Shape errors of a call (a NULL pointer, m k != n, a wrong
+ * proof_words) are refused before anything is touched and do not fail the prover.  Host memory that cannot be had ends a call with LFPLUS_E_HIP (no C++ exception
+ * leaves the library).  One thread per prover at a time. */
+typedef struct lfplus_prover lfplus_prover;
+int lfplus_prover_create(int device, const lfplus_params *params, const uint64_t *A, uint64_t seed, uint64_t n, uint32_t nM, const uint32_t *const *rowptr,
+                         const uint32_t *const *col, const uint64_t *const *val, uint32_t ncomp, lfplus_transcript *transcript, lfplus_prover **out);
+/* releases the contexts (their scratch goes to the process-wide cache: lfplus_scratch_trim) and joins the upload thread; the transcript is not freed */
+void lfplus_prover_destroy(lfplus_prover *prover);
+const char *lfplus_prover_last_error(const lfplus_prover *prover);
+/* ComR1CS::new for `count` fresh instances from their short witnesses z[i] (m ring elements each, n = m k; l_in is the instance's public-input length, kept for
+ * the reference's signature and not used by the fold): lfplus_witness_from_z(B, k) in the contexts the next prove folds from; cm_f_out (may be NULL) receives
+ * count x kappa x 16 words. */
+int lfplus_prover_ingest(lfplus_prover *prover, const uint64_t *const *z, uint32_t count, uint64_t m, uint32_t l_in, uint64_t *cm_f_out);
+/* The same from host witnesses f[i] (n ring elements each).  Returns at once: a worker thread uploads them one after the other, and the next prove linearizes
+ * the instances as they arrive (only the first upload is exposed).  f[i] is BORROWED until that prove -- or lfplus_prover_destroy -- returns; an upload that
+ * fails (a non-canonical word) is reported by the prove.  cm_f (may be NULL, as may any cm_f[i]): the instances' commitments, kappa x 16 words each, copied;
+ * the prove compares them with the commitments it computes (fcoms) and fails on a difference. */
+int lfplus_prover_set_instances(lfplus_prover *prover, const uint64_t *const *f, const uint64_t *const *cm_f, uint32_t count);
+/* PlusProver::prove (plus.rs:77-108): RgInstance::from_f of the accumulator halves and of every fresh instance on the contexts' second streams, the
+ * linearization of each fresh instance as it arrives, Mlin::mlin, Decomp::decompose with the parts left in the first two contexts.  Writes one flat proof:
+ * proof_words must equal lfplus_proof_len(params, n, nM, L, nfresh) for this prove's L and nfresh (otherwise LFPLUS_E_ARG, nothing touched). */
+int lfplus_prover_prove(lfplus_prover *prover, uint64_t *proof, uint64_t proof_words);
+/* the accumulator of the last prove read back: n x 16 words each (either may be NULL) */
+int lfplus_prover_accumulator(lfplus_prover *prover, uint64_t *F0, uint64_t *F1);
+/* Are the two halves of the accumulator valid LinB instances (lfplus_linb_check where they live) for `proof`, the flat proof of the LAST prove?  Half i = (F_i,
+ * C_i, v_i) at the points linb2x.ro, ||F_i||_inf < bound (0: not checked).  ok[i] = 1 / 0, failed[i] = the LFPLUS_REL_* bits, absmax[i] as lfplus_linb_check.
+ * LFPLUS_OK when both hold, LFPLUS_E_REJECT when one does not (all six outputs are written in both cases).  Read-only. */
+int lfplus_prover_decide(lfplus_prover *prover, const uint64_t *proof, uint64_t proof_words, uint64_t bound, int *ok, unsigned *failed, uint64_t *absmax);
+/* PlusVerifier::verify (plus.rs:132-143), host only: no GPU, no context.  The verifier's OWN statement is (params, n, nM, L, nfresh); a buffer whose length or
+ * header disagrees with it, or a NULL proof, is LFPLUS_E_ARG before any word of a field is read.  Then lfplus_r1cs_verify per fresh instance, lfplus_cm_verify,
+ * lfplus_decomp_verify on the borrowed transcript.  LFPLUS_E_REJECT: *which = i < nfresh for the i-th ComR1CSProof, nfresh for the CmProof, nfresh + 1 for the
+ * DecompProof, and *stage = that verifier's stage (either may be NULL). */
+int lfplus_verify(const lfplus_params *params, uint64_t n, uint32_t nM, uint32_t L, uint32_t nfresh, lfplus_transcript *transcript, const uint64_t *proof,
+                  uint64_t proof_words, int *which, int *stage);
 
 #ifdef __cplusplus
 }

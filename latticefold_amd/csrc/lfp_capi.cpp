@@ -145,6 +145,51 @@ extern "C" int lfplus_set_matrix(lfplus_ctx *c, const uint64_t *A, uint32_t kapp
     c->row0 = (u64)c->rank * n;
     return shape_buffers(c, kappa, n * (u64)c->world);
 }
+// The commitment matrix generated on the device from a seed (k_fill_ajtai, lfp_ingest.hip): the words PlusWorkload.ajtai_matrix computes on the host, without the
+// host generation and the pageable upload (268 MB at kappa 2, n = 2^20).  ms_avg != NULL: the fill alone `iters` times more between two HIP events.
+static int matrix_generate(lfplus_ctx *c, uint64_t seed, uint32_t kappa, uint64_t n, u32 iters, double *ms_avg) {
+    if (!c) return LFPLUS_E_ARG;
+    if (!kappa || kappa > 64 || !n || n > (1ull << 32)) return fail(c, LFPLUS_E_ARG, "lfplus_matrix_generate: bad shape");
+    if (c->sharded()) return fail(c, LFPLUS_E_ARG, "lfplus_matrix_generate: sharded contexts are not supported (a rank uploads its columns with lfplus_set_matrix)");
+    if (c->f) return fail(c, LFPLUS_E_ARG, "lfplus_matrix_generate: the matrix comes before the witness");
+    HIPCHK(c, hipSetDevice(c->device));
+    ff_join(c);
+    c->have = false;
+    const u64 words = (u64)kappa * n * 16;
+    u64 *fresh = nullptr;   // a new allocation, as in lfplus_set_matrix: contexts sharing the previous matrix keep it alive through their own reference
+    HIPCHK(c, lfp_dev_malloc(&fresh, words * 8));
+    hipError_t e = lfp::launch_fill_ajtai(fresh, words, seed, c->st);
+    if (e == hipSuccess && ms_avg) {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        e = hipEventCreate(&e0);
+        if (e == hipSuccess) e = hipEventCreate(&e1);
+        if (e == hipSuccess) e = hipEventRecord(e0, c->st);
+        for (u32 it = 0; it < iters && e == hipSuccess; it++) e = lfp::launch_fill_ajtai(fresh, words, seed, c->st);
+        if (e == hipSuccess) e = hipEventRecord(e1, c->st);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        float ms = 0;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        *ms_avg = (double)ms / iters;
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
+    if (e != hipSuccess) {
+        (void)hipFree(fresh);
+        return fail(c, LFPLUS_E_HIP, std::string("lfplus_matrix_generate: ") + hipGetErrorString(e));
+    }
+    c->A = fresh;
+    c->A_ref = std::shared_ptr<void>(fresh, [](void *p) { (void)hipFree(p); });
+    c->nloc = n;
+    c->row0 = 0;
+    return shape_buffers(c, kappa, n);
+}
+extern "C" int lfplus_matrix_generate(lfplus_ctx *c, uint64_t seed, uint32_t kappa, uint64_t n) { return matrix_generate(c, seed, kappa, n, 0, nullptr); }
+extern "C" int lfplus_matrix_generate_timed(lfplus_ctx *c, uint64_t seed, uint32_t kappa, uint64_t n, uint32_t iters, double *ms_avg) {
+    if (!c) return LFPLUS_E_ARG;
+    if (!ms_avg || !iters) return fail(c, LFPLUS_E_ARG, "lfplus_matrix_generate_timed: bad arguments");
+    return matrix_generate(c, seed, kappa, n, iters, ms_avg);
+}
 // The commitment matrix of `from` (same device), not copied: PlusProver keeps one context per accumulated / fresh instance and one Ajtai matrix.
 // The allocation is reference-counted: it lives until the last context holding it re-uploads or is destroyed.
 extern "C" int lfplus_share_matrix(lfplus_ctx *c, lfplus_ctx *from) {

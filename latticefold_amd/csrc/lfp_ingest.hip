@@ -91,4 +91,33 @@ hipError_t launch_ingest(const IngestArgs &a, u32 nblk, hipStream_t s) {
     else hipLaunchKernelGGL(k_ingest<4>, dim3(nblk), dim3(256), 0, s, a);
     return hipGetLastError();
 }
+
+// ---- the seeded commitment matrix (lfplus_matrix_generate; the host form is PlusWorkload.ajtai_matrix) -----------------------------------------------
+// Word w of the row-major (kappa, n, 16) matrix is splitmix64(seed + (w + 1) G) mod p: an indexable stream, so every word is independent of the others and the
+// kernel is a pure write stream.  2^64 < 2 p: the reduction is one conditional subtraction.  A thread writes two consecutive words with one 16-byte store (the
+// total is a multiple of 16 words and the buffer a device allocation: every pair is 16-byte aligned); the grid strides over the pairs with a 64-bit index.
+__device__ __forceinline__ u64 ajtai_word(u64 seed, u64 w) {
+    u64 z = seed + (w + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return z >= P ? z - P : z;
+}
+__global__ __launch_bounds__(256) void k_fill_ajtai(u64 *out, u64 pairs, u64 seed) {
+    const u64 stride = (u64)gridDim.x * blockDim.x;
+    for (u64 q = (u64)blockIdx.x * blockDim.x + threadIdx.x; q < pairs; q += stride) {
+        ulonglong2 v;
+        v.x = ajtai_word(seed, 2 * q);
+        v.y = ajtai_word(seed, 2 * q + 1);
+        reinterpret_cast<ulonglong2 *>(out)[q] = v;
+    }
+}
+hipError_t launch_fill_ajtai(u64 *out, u64 words, u64 seed, hipStream_t s) {
+    const u64 pairs = words / 2;      // (words is a multiple of 16)
+    if (!pairs) return hipSuccess;
+    const u64 want = (pairs + 255) / 256;
+    const u32 nblk = (u32)(want < 16384 ? want : 16384);      // 64 blocks per CU: enough stores in flight to fill HBM, few enough that the tail is short
+    hipLaunchKernelGGL(k_fill_ajtai, dim3(nblk), dim3(256), 0, s, out, pairs, seed);
+    return hipGetLastError();
+}
 }  // namespace lfp

@@ -59,6 +59,8 @@ struct IngestArgs {
     int first;
 };
 hipError_t launch_ingest(const IngestArgs &a, u32 nblk, hipStream_t s);      // icnt in {1, 2, 4}; returns the launch's error
+// the seeded commitment matrix (k_fill_ajtai): out[w] = splitmix64(seed + (w + 1) G) mod p for w < words (a multiple of 16; out 16-byte aligned)
+hipError_t launch_fill_ajtai(u64 *out, u64 words, u64 seed, hipStream_t s);
 // largest launch group (1, 2 or 4) not above `left`
 inline u32 group_size(u32 left) { return left >= 4 ? 4 : left >= 2 ? 2 : 1; }
 // Decomp::decompose (decomp.rs:32-99): base-B split, fix_variables over ring tables, sparse mat-vec with ring coefficients

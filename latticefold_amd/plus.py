@@ -210,6 +210,18 @@ class PlusContext:
         self._chk(_lib().lfplus_set_matrix(self.h, p, A.shape[0], A.shape[1]))
         self.kappa, self.n = A.shape[0], A.shape[1] * self.shard[1]
 
+    def generate_matrix(self, seed, kappa, n, iters=0):
+        """lfplus_matrix_generate: the (kappa, n, 16) commitment matrix filled on the device, word w = splitmix64(seed + (w + 1) G) mod p -- the words of
+        PlusWorkload.ajtai_matrix for seed = PlusWorkload.ajtai_seed, with no host generation and no upload.  iters > 0: the fill alone that many times more
+        between two HIP events -> average milliseconds (lfplus_matrix_generate_timed)"""
+        ms = C.c_double()
+        if iters:
+            self._chk(_nlib().lfplus_matrix_generate_timed(self.h, int(seed) & (2**64 - 1), int(kappa), int(n), int(iters), C.byref(ms)))
+        else:
+            self._chk(_nlib().lfplus_matrix_generate(self.h, int(seed) & (2**64 - 1), int(kappa), int(n)))
+        self.kappa, self.n = int(kappa), int(n)
+        return ms.value if iters else None
+
     def share_matrix(self, other):
         """use `other`'s resident commitment matrix (no copy, reference-counted) -- and, for a sharded prover, its transport"""
         self._chk(_lib().lfplus_share_matrix(self.h, other.h))
@@ -1124,6 +1136,11 @@ class PlusWorkload:
     def params(self):
         return PlusParameters(LinParameters(self.kappa, DecompParameters(D // 2, self.k, self.l)), self.B)
 
+    @property
+    def ajtai_seed(self):
+        """the seed of ajtai_matrix's stream: PlusContext.generate_matrix(ajtai_seed, kappa, n) fills the same words on the device"""
+        return 0xA17A2 + self.nvars
+
     def ajtai_matrix(self, cols=None):
         """(kappa, n, 16) canonical words, or the column range cols = (c0, c1) of it (what a rank of a sharded prover uploads)"""
         c0, c1 = cols if cols is not None else (0, self.n)
@@ -1144,3 +1161,252 @@ def make_plus_workload(name):
     nvars, L, k, kappa = PLUS_CONFIGS[name]
     B = estimate_bound(D * 128, L, D, k) // 2                                    # benches/e2e.rs:71
     return PlusWorkload(name, nvars, L, k, kappa, B, math.ceil(math.log(float(P)) / math.log(D / 2)))
+
+
+# ---- PlusProver / PlusVerifier behind the C ABI (lfplus_prover_*, lfplus_verify: csrc/lfp_prover.cpp) and the flat PlusProof ------------------------------
+PROOF_HEADER = 8                                  # lfplus.h LFPLUS_PROOF_HEADER
+PROOF_MAGIC = 0x4C46504C55533031                  # lfplus.h LFPLUS_PROOF_MAGIC
+PROOF_CM_KEYS = ("r", "msgs", "e", "b", "v", "a", "bb", "c", "comh", "pa", "pb", "ea", "eb", "cm_g", "ro", "vo", "fcoms")    # the order lfplus_mlin takes them
+_NATIVE_READY = False
+
+
+class _CParams(C.Structure):
+    """lfplus.h lfplus_params"""
+    _fields_ = [("kappa", C.c_uint32), ("k", C.c_uint32), ("l", C.c_uint32), ("b", C.c_uint64), ("B", C.c_uint64)]
+
+
+def _cparams(params):
+    dp = params.lin.decomp
+    return _CParams(int(params.lin.kappa), int(dp.k), int(dp.l), int(dp.b), int(params.B))
+
+
+def _nlib():
+    global _NATIVE_READY
+    L = _lib()
+    if not _NATIVE_READY:
+        vp, pp, u32pp, u64pp, ip = C.c_void_p, C.POINTER(_CParams), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(u64p), C.POINTER(C.c_int)
+        L.lfplus_matrix_generate.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64]
+        L.lfplus_matrix_generate_timed.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
+        L.lfplus_proof_fields.argtypes = [C.c_uint32]
+        L.lfplus_proof_fields.restype = C.c_uint32
+        L.lfplus_proof_len.argtypes = [pp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.lfplus_proof_len.restype = C.c_uint64
+        L.lfplus_proof_layout.argtypes = [pp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32]
+        L.lfplus_prover_create.argtypes = [C.c_int, pp, u64p, C.c_uint64, C.c_uint64, C.c_uint32, u32pp, u32pp, u64pp, C.c_uint32, vp, C.POINTER(vp)]
+        L.lfplus_prover_destroy.argtypes = [vp]
+        L.lfplus_prover_destroy.restype = None
+        L.lfplus_prover_last_error.argtypes = [vp]
+        L.lfplus_prover_last_error.restype = C.c_char_p
+        L.lfplus_prover_ingest.argtypes = [vp, u64pp, C.c_uint32, C.c_uint64, C.c_uint32, u64p]
+        L.lfplus_prover_set_instances.argtypes = [vp, u64pp, u64pp, C.c_uint32]
+        L.lfplus_prover_prove.argtypes = [vp, u64p, C.c_uint64]
+        L.lfplus_prover_accumulator.argtypes = [vp, u64p, u64p]
+        L.lfplus_prover_decide.argtypes = [vp, u64p, C.c_uint64, C.c_uint64, ip, C.POINTER(C.c_uint), u64p]
+        L.lfplus_verify.argtypes = [pp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, u64p, C.c_uint64, ip, ip]
+        _NATIVE_READY = True
+    return L
+
+
+def proof_len(params, n, nM, L, nfresh):
+    """lfplus_proof_len: words of the flat PlusProof of a prove that folds L instances, nfresh of them fresh (0: outside the envelope)"""
+    return int(_nlib().lfplus_proof_len(C.byref(_cparams(params)), int(n), int(nM), int(L), int(nfresh)))
+
+
+def proof_fields(params, n, nM, L, nfresh):
+    """The fields of the flat PlusProof in their fixed order (lfplus.h): [(path, shape)], path = ("lproof", i, key) or (part, key)"""
+    nvars, kappa, k, q, per = int(n).bit_length() - 1, params.lin.kappa, params.lin.decomp.k, 1 + nM, 4 + 4 * nM
+    out = []
+    for i in range(nfresh):
+        out += [(("lproof", i, "msgs"), (nvars, 4, D)), (("lproof", i, "r"), (nvars,)), (("lproof", i, "evals"), (4, D))]
+    cm = {"r": (nvars,), "msgs": (nvars, 4, D), "e": (q, L * k, D, D), "b": (L, D), "v": (L, D), "a": (L, q), "bb": (L, q, D), "c": (L, q, D), "comh": (L, kappa, D),
+          "pa": (nvars, 3, D), "pb": (nvars, 3, D), "ea": (L, per, D), "eb": (L, per, D), "cm_g": (L, kappa, D), "ro": (2, nvars), "vo": (L, q, 2, D),
+          "fcoms": (L, 3, kappa, D)}
+    out += [(("cmproof", key), cm[key]) for key in PROOF_CM_KEYS]
+    out += [(("linb2x", "cm_g"), (kappa, D)), (("linb2x", "ro"), (2, nvars)), (("linb2x", "vo"), (q, 2, D))]
+    out += [(("dproof", "C0"), (kappa, D)), (("dproof", "C1"), (kappa, D)), (("dproof", "v0"), (q, 2, D)), (("dproof", "v1"), (q, 2, D))]
+    return out
+
+
+def proof_layout(params, n, nM, L, nfresh):
+    """lfplus_proof_layout -> (offsets, lengths) in words, one entry per field of proof_fields; LfPlusError(E_ARG) outside the envelope"""
+    lib = _nlib()
+    nf = int(lib.lfplus_proof_fields(int(nfresh)))
+    off, ln = np.zeros(nf, dtype=np.uint64), np.zeros(nf, dtype=np.uint64)
+    rc = lib.lfplus_proof_layout(C.byref(_cparams(params)), int(n), int(nM), int(L), int(nfresh), off.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), nf)
+    if rc:
+        raise LfPlusError(rc, "lfplus_proof_layout: parameters outside the envelope")
+    return [int(x) for x in off], [int(x) for x in ln]
+
+
+def _proof_header(params, n, nM, L, nfresh):
+    dp = params.lin.decomp
+    return np.array([PROOF_MAGIC, L, nfresh, int(n).bit_length() - 1, dp.k, dp.l, params.lin.kappa, nM], dtype=np.uint64)
+
+
+def proof_to_flat(proof, params, n, nM):
+    """A PlusProof dict (PlusProver.prove, the oracle's) as the flat words of lfplus.h; L = the instances the Cm proof folds, nfresh = len(lproof).  A field
+    whose shape is not the one (params, n, nM, L) imply raises LfPlusError(E_ARG)"""
+    try:
+        L, nfresh = int(np.asarray(proof["cmproof"]["b"]).shape[0]), len(proof["lproof"])
+    except (KeyError, TypeError, IndexError) as ex:
+        raise LfPlusError(E_ARG, f"malformed proof: {ex!r}")
+    off, ln = proof_layout(params, n, nM, L, nfresh)
+    out = np.zeros(off[-1] + ln[-1], dtype=np.uint64)
+    out[:PROOF_HEADER] = _proof_header(params, n, nM, L, nfresh)
+    for (path, shape), o, w in zip(proof_fields(params, n, nM, L, nfresh), off, ln):
+        try:
+            src = proof["lproof"][path[1]] if path[0] == "lproof" else proof[path[0]]
+        except (KeyError, TypeError, IndexError) as ex:
+            raise LfPlusError(E_ARG, f"malformed proof: {ex!r}")
+        out[o:o + w] = _shaped(src, path[-1], shape).reshape(-1)
+    return out
+
+
+def proof_from_flat(words, params, n, nM, L, nfresh):
+    """The flat words as a PlusProof dict of the shapes PlusProver.prove returns (copies; the metadata k / ell / kappa / nvars is the CALLER's).  A buffer whose
+    length or header disagrees with (params, n, nM, L, nfresh) raises LfPlusError(E_ARG)"""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    off, ln = proof_layout(params, n, nM, L, nfresh)
+    if words.size != off[-1] + ln[-1] or (words[:PROOF_HEADER] != _proof_header(params, n, nM, L, nfresh)).any():
+        raise LfPlusError(E_ARG, "malformed proof: length or header differs from the parameters")
+    nvars, dp = int(n).bit_length() - 1, params.lin.decomp
+    proof = {"lproof": [{"nvars": nvars} for _ in range(nfresh)], "cmproof": {"k": dp.k, "ell": dp.l, "kappa": params.lin.kappa, "nvars": nvars}, "linb2x": {}, "dproof": {}}
+    for (path, shape), o, w in zip(proof_fields(params, n, nM, L, nfresh), off, ln):
+        dst = proof["lproof"][path[1]] if path[0] == "lproof" else proof[path[0]]
+        dst[path[-1]] = words[o:o + w].reshape(shape).copy()
+    return proof
+
+
+class NativePlusProver:
+    """PlusProver (plus.rs:15-108) as the C object lfplus_prover: the schedule PlusProver runs in Python (contexts, upload thread, from_f hints, device-resident
+    accumulator, failed state) lives below the ABI; this class only marshals.  Unsharded, the accumulator always stays on the device (PlusProver.device_acc).
+    A = None: the commitment matrix is generated on the device from `seed` (PlusContext.generate_matrix).  prove() returns the FLAT proof (proof_from_flat)."""
+
+    def __init__(self, A, M, ncomp, params, transcript, device=0, seed=0):
+        self.params, self.transcript, self.nM, self.ncomp = params, transcript, len(M), int(ncomp)
+        self.h = C.c_void_p()
+        self.nacc = self.nfresh = 0
+        self.last = None         # (L, nfresh) of the last proof
+        self._keep = None        # host witnesses the upload thread still reads
+        keep, rp, cp, vp = _csr_args(M)
+        if A is not None:
+            A, ap = _w(A)
+            if A.ndim != 3 or A.shape[2] != D or A.shape[0] != params.lin.kappa:
+                raise LfPlusError(E_ARG, "NativePlusProver: A must be (kappa, n, 16) with kappa = params.lin.kappa")
+            self.n = int(A.shape[1])
+        else:
+            ap, self.n = None, int(keep[0][0].size - 1) if keep else 0
+        self.kappa = int(params.lin.kappa)
+        rc = _nlib().lfplus_prover_create(int(device), C.byref(_cparams(params)), ap, int(seed) & (2**64 - 1), self.n, self.nM, rp, cp, vp, self.ncomp, transcript.h,
+                                          C.byref(self.h))
+        if rc:
+            self.h = C.c_void_p()
+            raise LfPlusError(rc, "lfplus_prover_create: no usable HIP device, parameters outside the envelope (three R1CS matrices, n = 2^nvars), or the upload failed")
+
+    @staticmethod
+    def init(A, M, ncomp, params, transcript, device=0, seed=0):
+        return NativePlusProver(A, M, ncomp, params, transcript, device, seed)
+
+    def last_error(self):
+        return _nlib().lfplus_prover_last_error(self.h).decode() if self.h else ""
+
+    def _chk(self, rc):
+        if rc:
+            raise LfPlusError(rc, self.last_error())
+
+    def close(self):
+        if self.h:
+            _nlib().lfplus_prover_destroy(self.h)
+            self.h = C.c_void_p()
+        self._keep = None
+
+    def ingest(self, zs, r1cs=None, l_in=1):
+        """lfplus_prover_ingest: the fresh instances of the next prove from their short witnesses -> cm_f (count, kappa, 16)"""
+        zs = [np.ascontiguousarray(z, dtype=np.uint64) for z in zs]
+        if not zs or any(z.ndim != 2 or z.shape != zs[0].shape or z.shape[1] != D for z in zs):
+            raise LfPlusError(E_ARG, "NativePlusProver.ingest: z must be equal (m, 16) arrays")
+        ptrs = (u64p * len(zs))(*[z.ctypes.data_as(u64p) for z in zs])
+        out = np.zeros((len(zs), self.kappa, D), dtype=np.uint64)
+        self._chk(_nlib().lfplus_prover_ingest(self.h, ptrs, len(zs), zs[0].shape[0], int(l_in), out.ctypes.data_as(u64p)))
+        self.nfresh = len(zs)
+        return out
+
+    def set_instances(self, fs, cm_fs=None):
+        """lfplus_prover_set_instances: the fresh instances of the next prove from host witnesses (n, 16); they go up on the library's worker thread"""
+        fs = [np.ascontiguousarray(f, dtype=np.uint64) for f in fs]
+        if not fs or any(f.shape != (self.n, D) for f in fs):
+            raise LfPlusError(E_ARG, "NativePlusProver.set_instances: f must be (n, 16) arrays")
+        cms = None if cm_fs is None else [np.ascontiguousarray(c, dtype=np.uint64) for c in cm_fs]
+        if cms is not None and (len(cms) != len(fs) or any(c.shape != (self.kappa, D) for c in cms)):
+            raise LfPlusError(E_ARG, "NativePlusProver.set_instances: cm_f must be (kappa, 16) arrays, one per instance")
+        fp = (u64p * len(fs))(*[f.ctypes.data_as(u64p) for f in fs])
+        cp = None if cms is None else (u64p * len(fs))(*[c.ctypes.data_as(u64p) for c in cms])
+        self._keep = fs          # borrowed by the worker until the prove returns
+        self._chk(_nlib().lfplus_prover_set_instances(self.h, fp, cp, len(fs)))
+        self.nfresh = len(fs)
+
+    def prove(self, comp=None):
+        """lfplus_prover_prove -> the flat proof.  comp: host ComR1CS instances (set_instances is called with their f and cm_f); None: the instances named by
+        the last ingest / set_instances"""
+        if comp is not None:
+            self.set_instances([ci.f for ci in comp], [ci.cm_f for ci in comp])
+        L, nfresh = self.nacc + self.nfresh, self.nfresh
+        words = proof_len(self.params, self.n, self.nM, L, nfresh) if L else 0
+        out = np.zeros(max(words, 1), dtype=np.uint64)
+        try:
+            self._chk(_nlib().lfplus_prover_prove(self.h, out.ctypes.data_as(u64p), words))
+        finally:
+            self._keep = None
+        self.nacc, self.nfresh, self.last = 2, 0, (L, nfresh)
+        return out
+
+    def accumulator(self):
+        """(F0, F1) of the last prove, read back from the device"""
+        F = [np.zeros((self.n, D), dtype=np.uint64) for _ in range(2)]
+        self._chk(_nlib().lfplus_prover_accumulator(self.h, F[0].ctypes.data_as(u64p), F[1].ctypes.data_as(u64p)))
+        return tuple(F)
+
+    def decide(self, proof, bound=0):
+        """lfplus_prover_decide on the flat proof of the last prove -> [(ok, failed, absmax)] per accumulator half (as PlusProver.decide)"""
+        w = np.ascontiguousarray(proof, dtype=np.uint64).reshape(-1)
+        ok, failed, am = (C.c_int * 2)(), (C.c_uint * 2)(), (C.c_uint64 * 2)()
+        rc = _nlib().lfplus_prover_decide(self.h, w.ctypes.data_as(u64p), w.size, int(bound), ok, failed, am)
+        if rc not in (0, E_REJECT):
+            self._chk(rc)
+        return [(bool(ok[i]), int(failed[i]), int(am[i])) for i in range(2)]
+
+
+class NativePlusVerifier:
+    """PlusVerifier (plus.rs:25-33, 110-146) through lfplus_verify: host only, on the flat proof.  The statement -- params, n, nM and per proof (L, nfresh) --
+    is the verifier's own.  verify returns True, or False with .stage = (which proof, stage) named as PlusVerifier names them, ("malformed", message) for a
+    buffer that does not fit the statement; .which is the C index (i < nfresh, nfresh: cmproof, nfresh + 1: dproof, -1: malformed)"""
+
+    def __init__(self, A, M, params, transcript):
+        self.params, self.transcript, self.nM = params, transcript, len(M)
+        shape = tuple(A) if isinstance(A, tuple) else np.asarray(A).shape          # (kappa, n, 16): the matrix or just its shape
+        if len(shape) != 3 or shape[2] != D or shape[0] != params.lin.kappa or shape[1] < 2 or shape[1] & (shape[1] - 1):
+            raise LfPlusError(E_ARG, "NativePlusVerifier: A must be (kappa, n = 2^nvars, 16) with kappa = params.lin.kappa")
+        self.n = int(shape[1])
+        self.stage, self.which, self.code = None, None, 0
+
+    @staticmethod
+    def init(A, M, params, transcript):
+        return NativePlusVerifier(A, M, params, transcript)
+
+    def verify(self, proof, L, nfresh):
+        w, p = (None, None) if proof is None else _w(np.asarray(proof).reshape(-1))
+        which, st = C.c_int(), C.c_int()
+        rc = _nlib().lfplus_verify(C.byref(_cparams(self.params)), self.n, self.nM, int(L), int(nfresh), self.transcript.h, p, 0 if w is None else w.size,
+                                   C.byref(which), C.byref(st))
+        self.code, self.which = rc, which.value
+        if rc == 0:
+            self.stage = None
+            return True
+        if rc == E_REJECT:
+            name = f"lproof[{which.value}]" if which.value < nfresh else ("cmproof", "dproof")[which.value - nfresh]
+            self.stage = (name, st.value)
+            return False
+        if rc == E_ARG:
+            self.stage = ("malformed", "length or header differs from the verifier's parameters")
+            return False
+        raise LfPlusError(rc, "lfplus_verify")

@@ -23,7 +23,7 @@ SCALARS = {
     "int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "char": "c_char", "float": "f32", "double": "f64", "void": "c_void",
     "size_t": "usize", "uint64_t": "u64", "uint32_t": "u32", "uint8_t": "u8", "int8_t": "i8", "int32_t": "i32", "int64_t": "i64",
 }
-OPAQUE = ["lf_ctx", "lf_witness", "lf_witness_job", "lf_transcript", "lfplus_ctx", "lfplus_transcript"]
+OPAQUE = ["lf_ctx", "lf_witness", "lf_witness_job", "lf_transcript", "lfplus_ctx", "lfplus_transcript", "lfplus_prover"]
 KEYWORDS = {"in": "inp", "type": "ty", "ref": "r", "fn": "f", "mod": "m", "box": "b", "use": "u", "loop": "lp", "match": "mt", "move": "mv", "self": "this"}
 
 
@@ -49,7 +49,7 @@ def rust_type(ctype):
     name = " ".join(base)
     if name in SCALARS:
         r = SCALARS[name]
-    elif name in OPAQUE or name in ("lf_params",):
+    elif name in OPAQUE or name in ("lf_params", "lfplus_params"):
         r = name
     elif name in ("lf_exchange_fn", "lfplus_exchange_fn"):
         r = "lf_exchange_fn"
@@ -70,7 +70,7 @@ def split_params(s):
     for i, p in enumerate(x.strip() for x in s.split(",")):
         m = re.match(r"^(.*?)([A-Za-z_][A-Za-z_0-9]*)?$", p)
         ctype, name = m.group(1).strip(), m.group(2)
-        if name in SCALARS or name in OPAQUE or name in ("lf_params", "lf_exchange_fn", "lfplus_exchange_fn", "unsigned", "const") or not ctype:   # unnamed parameter
+        if name in SCALARS or name in OPAQUE or name in ("lf_params", "lfplus_params", "lf_exchange_fn", "lfplus_exchange_fn", "unsigned", "const") or not ctype:   # unnamed parameter
             ctype, name = p, None
         if name is None:
             base = re.findall(r"[A-Za-z_][A-Za-z_0-9]*", ctype)[-1]
@@ -100,8 +100,8 @@ def parse(path):
 def defines(path):
     text = strip_comments(open(os.path.join(ROOT, path)).read())
     out = []
-    for name, val in re.findall(r"^\s*#define\s+(LF[A-Z_0-9]*)\s+\(?(-?\d+)(?:ULL)?\)?\s*$", text, flags=re.M):
-        out.append((name, int(val)))
+    for name, val in re.findall(r"^\s*#define\s+(LF[A-Z_0-9]*)\s+\(?(-?\d+|0x[0-9A-Fa-f]+)(?:ULL)?\)?\s*$", text, flags=re.M):
+        out.append((name, int(val, 0)))
     return out
 
 
@@ -117,6 +117,9 @@ def generate():
           "/// DecompositionParams + CCS shape (decomposition_parameters.rs:11-20, arith.rs:50-74)",
           "#[repr(C)] #[derive(Clone, Copy, Debug)]",
           "pub struct lf_params { pub s: u32, pub wit_len: u32, pub l: u32, pub L: u32, pub K: u32, pub b: u32, pub B: u64, pub kappa: u32, pub t: u32, pub q: u32, pub d: u32 }",
+          "/// PlusParameters with LinParameters / DecompParameters flattened (latticefold-plus plus.rs:43-47, lin.rs:24-28, rgchk.rs:20-24)",
+          "#[repr(C)] #[derive(Clone, Copy, Debug)]",
+          "pub struct lfplus_params { pub kappa: u32, pub k: u32, pub l: u32, pub b: u64, pub B: u64 }",
           "/// all-gather `words` u64 from every rank into recv_all[world * words] in rank order; 0 on success (lf_set_sharding)",
           "pub type lf_exchange_fn = Option<unsafe extern \"C\" fn(user: *mut c_void, send: *const u64, recv_all: *mut u64, words: usize) -> c_int>;", ""]
     allfns = []
