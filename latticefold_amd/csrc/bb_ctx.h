@@ -64,20 +64,11 @@ struct BbMarks {
 };
 inline BbMarks g_marks;
 #define BB_MARK(x) g_marks.mark(x)
-static inline H9 h9_load(const u64 *w) { H9 r; for (int i = 0; i < TAU; i++) r.c[i] = w[i] % BB_P; return r; }
-static inline H9 h9_one() { H9 r; memset(&r, 0, sizeof(r)); r.c[0] = 1; return r; }
-static inline H9 h9_sub(const H9 &a, const H9 &b) { H9 r; for (int i = 0; i < TAU; i++) r.c[i] = hsub(a.c[i], b.c[i]); return r; }
-static inline H9 h9_add(const H9 &a, const H9 &b) { H9 r; for (int i = 0; i < TAU; i++) r.c[i] = hadd(a.c[i], b.c[i]); return r; }
-static inline H9 h9_scale(const H9 &a, u64 k) { H9 r; for (int i = 0; i < TAU; i++) r.c[i] = hmul(a.c[i], k % BB_P); return r; }
-// inverse in F_p[Y]/(Y^9 - nu): solve (multiplication by a) x = 1 by Gaussian elimination on the 9 x 9 matrix M[i][j] = [Y^i](a Y^j); false if a = 0
 int build_eq_dev(C *c, const H9 *pt, u32 nv, fe *eq_dev);
 int down_small(C *c, const u64 *dsrc, size_t words, u64 *host);
-bool h9_inv(const H9 &a, u64 nu, H9 *out);
 int exchange_modsum(C *c, u64 *inout, size_t words);
-bool is_diag(const u64 *e, H9 *out);
 int build_eq_async(C *c, const H9 *pt, u32 nv, fe *eq_dev);
 int build_z(C *c, const int32_t *planes, u32 K, int mode_bits, const u64 *heads, fe *z);   // bb_prove.cpp (synchronises the stream)
-bool lcccs_point(const lf_params &P, const u64 *lcccs, std::vector<H9> &pt);
 #pragma GCC visibility pop
 
 }  // namespace lfbb

@@ -30,8 +30,6 @@ u64 hpow(u64 a, u64 e) {
     return r;
 }
 
-static H9 h9_zero() { H9 r; memset(&r, 0, sizeof(r)); return r; }
-static H9 h9_one() { H9 r = h9_zero(); r.c[0] = 1; return r; }
 // (inputs canonical: a product is < p^2 < 2^62, so four of them fit a 64-bit word -- the 81 products of an F_{p^9} product take 27 reductions instead of 81;
 // this is the host's ring arithmetic on proof-sized data: the folded instance, the challenge powers, the message completion of the split rounds)
 static H9 h9_mul_nu(const H9 &a, const H9 &b, u64 nu) {
@@ -156,6 +154,30 @@ int bb_build_tables(u64 nonres, const u64 *y, BbTables &T) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+bool h9_inv(const H9 &a, u64 nu, H9 *out) {
+    u64 M[TAU][TAU + 1];
+    for (int i = 0; i < TAU; i++) {
+        for (int j = 0; j < TAU; j++) M[i][j] = i >= j ? a.c[i - j] % BB_P : hmul(nu % BB_P, a.c[TAU + i - j] % BB_P);
+        M[i][TAU] = i == 0;
+    }
+    for (int col = 0; col < TAU; col++) {
+        int piv = -1;
+        for (int r = col; r < TAU; r++)
+            if (M[r][col]) { piv = r; break; }
+        if (piv < 0) return false;
+        if (piv != col)
+            for (int j = 0; j <= TAU; j++) std::swap(M[piv][j], M[col][j]);
+        const u64 iv = hinv(M[col][col]);
+        for (int j = col; j <= TAU; j++) M[col][j] = hmul(M[col][j], iv);
+        for (int r = 0; r < TAU; r++) {
+            if (r == col || !M[r][col]) continue;
+            const u64 f = M[r][col];
+            for (int j = col; j <= TAU; j++) M[r][j] = hsub(M[r][j], hmul(f, M[col][j]));
+        }
+    }
+    for (int i = 0; i < TAU; i++) out->c[i] = M[i][TAU];
+    return true;
+}
 H9 BbHostRing::mul9(const H9 &a, const H9 &b) const { return h9_mul_nu(a, b, T.nu); }
 void BbHostRing::crt(const u64 *a, u64 *out) const {
     u64 r[D];

@@ -1,23 +1,14 @@
 // bb_prove.cpp -- BabyBearRingNTT backend: the host driver that replays `NIFSProver::prove` (crates/latticefold/src/nifs.rs:48-103) on the kernels of
 // bb_kernels.hip -- linearization, decomposition and folding provers and the two sumchecks as stand-alone entry points.  Same structure as the Goldilocks
 // driver (lf_prove.cpp / lf_fold.cpp: f-hat virtual, Mz restructured, f_0 in the coefficient domain), one stream.  Host <-> device traffic inside a fold
-// step is O(proof size).
+// step is O(proof size).  This file is the SCHEDULE: what is enqueued where, the waits, the downloads, the timers.  The transcript steps and the instance
+// arithmetic in between are the bodies of lf_step_host.h over BbV (bb_host.h), the same ones the Goldilocks prover and the verifier run.
 #include "lf_ring_host.h"
 
 namespace lfbb {
 
 // =================================================================================================================================
 // the driver
-static void sc_prologue(BbTranscript &tr, u32 nv, u32 deg) {   // utils/sumcheck.rs:60-62
-    tr.absorb_u64_as_ring(nv);
-    tr.absorb_u64_as_ring(deg);
-}
-static H9 sc_round_transcript(BbTranscript &tr, const u64 *evals, u32 npts) {
-    tr.absorb_ring(evals, npts);
-    H9 r = tr.get_challenge();
-    tr.absorb_h9_as_ring(r);
-    return r;
-}
 static size_t atl(size_t x) { return x < 2 ? 2 : x; }   // leading dimensions stay even (8-byte pair loads)
 
 // linearization sumcheck on device tables mz [t][72][m] (left intact) and eq_beta [9][m]
@@ -36,7 +27,7 @@ static int run_lin_sumcheck(C *c, BbTranscript &tr, const fe *mz, const fe *eqb,
     RET(c->tbuf("round_partial", red_partial_words(5 * RE), &partial));
     od = c->round_out();
     if (!od) return LF_ERR_HIP;
-    { HostTimer ht(c); sc_prologue(tr, P.s, deg); }
+    { HostTimer ht(c); lfs::sumcheck_prologue<BbV>(tr, P.s, deg); }
     const fe *cur = mz, *cure = eqb;
     size_t n = m;
     int flip = 0;
@@ -76,7 +67,7 @@ static int run_lin_sumcheck(C *c, BbTranscript &tr, const fe *mz, const fe *eqb,
         HIPCHK(hipStreamSynchronize(c->stream()));            // the reduce kernel wrote the message into mapped host memory
         memcpy(ev, od, (size_t)(deg + 1) * RE * 8);
         HostTimer ht(c);
-        point[round - 1] = sc_round_transcript(tr, ev, deg + 1);
+        point[round - 1] = lfs::sumcheck_round<BbV>(tr, ev, deg + 1);
         if (round <= 4 || round == 8) { char nm[32]; snprintf(nm, sizeof nm, "  lin round %u", round); BB_MARK(nm); }
     }
     if (u_dev) launch_fix_final(c->dev, cur, 2, P.t * 8, e9pre_from_h9(point[P.s - 1], c->ring.T.nu), u_dev, c->stream());   // two entries per row left
@@ -114,12 +105,6 @@ static int build_z_async(C *c, const int32_t *planes, u32 K, int mode_bits, cons
     HIPCHK(hipMemcpyAsync(stage, h, cnt * sizeof(fe), hipMemcpyHostToDevice, c->stream()));
     HIPCHK(hipMemcpy2DAsync(z, c->n * sizeof(fe), stage, hl * sizeof(fe), hl * sizeof(fe), (size_t)K * RE, hipMemcpyDeviceToDevice, c->stream()));
     return LF_OK;
-}
-bool lcccs_point(const lf_params &P, const u64 *lcccs, std::vector<H9> &pt) {
-    pt.resize(P.s);
-    for (u32 i = 0; i < P.s; i++)
-        if (!is_diag(lcccs + (size_t)i * RE, &pt[i])) return false;
-    return true;
 }
 
 // LFLinearizationProver::prove (nifs/linearization.rs:145-189)
@@ -208,28 +193,6 @@ static int linearize_impl(C *c, BbTranscript &tr, const u64 *cccs, const lf_witn
     return LF_OK;
 }
 
-// decompose_big_vec_into_k_vec_and_compose_back (nifs/decomposition/utils.rs:12-42) on l+1 elements, host
-static void compute_x_s(const C *c, const u64 *xh, u64 *x_s) {
-    const lf_params &P = c->P;
-    u32 cnt = P.l + 1;
-    std::vector<u64> co(RE);
-    for (u32 i = 0; i < cnt; i++) {
-        c->ring.icrt(xh + (size_t)i * RE, co.data());
-        std::vector<int64_t> dB(P.L), dk(P.K);
-        std::vector<std::vector<u64>> part(P.K, std::vector<u64>(RE, 0));
-        for (int cc = 0; cc < RE; cc++) {
-            bb_balanced_digits(co[cc], P.B, P.L, dB.data(), c->digit_mode);
-            u64 pw = 1;
-            for (u32 l = 0; l < P.L; l++) {
-                bb_balanced_digits(hfrom_i64(dB[l]), P.b, P.K, dk.data(), c->digit_mode);
-                for (u32 k = 0; k < P.K; k++) part[k][cc] = hadd(part[k][cc], hmul(pw, hfrom_i64(dk[k])));
-                pw = hmul(pw, P.B % BB_P);
-            }
-        }
-        for (u32 k = 0; k < P.K; k++) c->ring.crt(part[k].data(), x_s + ((size_t)k * cnt + i) * RE);
-    }
-}
-
 struct SideState {
     const int32_t *planes;
     fe *z;      // [K][72][n]
@@ -314,7 +277,7 @@ static int dec_enqueue_evals(C *c, const u64 *lcccs, const std::vector<H9> &rpt,
     pd.h_u = c->arena_alloc((size_t)K * P.t * RE);
     if (!pd.h_v || !pd.h_u) return LF_ERR_HIP;
     pd.ph_evals = c->ev_begin(12);
-    compute_x_s(c, xh, x_s);   // host, O(l) elements
+    lfs::decompose_x(BbV{c->ring}, P, c->digit_mode, xh, x_s);   // host, O(l) elements
     // v_s (decomposition.rs:204-211) from the coefficient planes
     if (c->vs_wit == wit && c->vs_eq == eq_r) {   // computed by the linearization of this step at this very point
         HIPCHK(hipMemcpyAsync(od, c->vs_dev, (size_t)K * TAU * RE * 8, hipMemcpyDeviceToDevice, c->stream()));
@@ -345,96 +308,21 @@ static int dec_finish(C *c, BbTranscript &tr, const u64 *lcccs, SideState &S, u6
     memcpy(v_s, pd.h_v, (size_t)K * TAU * RE * 8);
     memcpy(u_s, pd.h_u, (size_t)K * P.t * RE * 8);
     HostTimer ht(c);
-    {   // y_0 = cm - sum_{k>=1} b^k y_k, as the reference's fold (acc + y_i) * b
-        // (b is a base-field constant: in the NTT form the product with it is the word-wise one -- 72 multiplications per element instead of eight F_{p^9} products)
-        std::vector<u64> acc((size_t)P.kappa * RE, 0);
-        const u64 bq = (u64)P.b % BB_P;
-        for (int k = (int)K - 1; k >= 1; k--)
-            for (u32 i = 0; i < P.kappa; i++) {
-                u64 *a = &acc[(size_t)i * RE];
-                const u64 *y = y_s + ((size_t)k * P.kappa + i) * RE;
-                for (int w = 0; w < RE; w++) a[w] = hmul(hadd(a[w], y[w] % BB_P), bq);
-            }
-        for (u32 i = 0; i < P.kappa; i++) BbHostRing::sub(cm + (size_t)i * RE, &acc[(size_t)i * RE], y_s + (size_t)i * RE);
-    }
-    // transcript (decomposition.rs:65-83): absorb x_k, y_k, u_k, v_k and build the K LCCCS
-    size_t ll = lcccs_len(&P, TAU);
-    S.lcccs.assign((size_t)K * ll * RE, 0);
-    for (u32 k = 0; k < K; k++) {
-        const u64 *xk = x_s + (size_t)k * (P.l + 1) * RE, *yk = y_s + (size_t)k * P.kappa * RE;
-        const u64 *uk = u_s + (size_t)k * P.t * RE, *vk = v_s + (size_t)k * TAU * RE;
-        tr.absorb_ring(xk, P.l + 1);
-        tr.absorb_ring(yk, P.kappa);
-        tr.absorb_ring(uk, P.t);
-        tr.absorb_ring(vk, TAU);
-        u64 *o = &S.lcccs[(size_t)k * ll * RE];
-        memcpy(o, lcccs, (size_t)P.s * RE * 8); o += (size_t)P.s * RE;
-        memcpy(o, vk, (size_t)TAU * RE * 8); o += (size_t)TAU * RE;
-        memcpy(o, yk, (size_t)P.kappa * RE * 8); o += (size_t)P.kappa * RE;
-        memcpy(o, uk, (size_t)P.t * RE * 8); o += (size_t)P.t * RE;
-        memcpy(o, xk, (size_t)(P.l + 1) * RE * 8);
-    }
+    lfs::commit_y0<BbV>(P, cm, y_s);
+    lfs::absorb_decomposition<BbV>(tr, P, lcccs, proof, S.lcccs);
     return LF_OK;
 }
 
 // LFFoldingProver::prove (nifs/folding.rs:42-130)
-// C_pi(X) of lf_sv_rounds.h for the V weights W_b = eq((r_1..), b) over F_{p^9}: coefficient table [pairs][4][9] (Montgomery words).  The BabyBear twin of
-// sv_build_coef in lf_capi.cpp: h = sum_x w_x(X) y_x, w_x = W_x (1 - X) (x < V), W_{x-V} X (x >= V); h^3 - h expanded over y^2 = b, y^3 = y.
 static E9 e9_from_h9(const H9 &h) { E9 r; for (int i = 0; i < TAU; i++) r.c[i] = from_canon(h.c[i]); return r; }
-static void bbsv_build_coef(int V, const E9 *W, fe nuM, std::vector<fe> &out) {
-    const int NX = 2 * V, NPR = lf::sv_num_pairs(V);
-    std::vector<E9> Cf((size_t)NPR * 4, e9_zero());
-    std::vector<lf::SvPair> prs(NPR);
-    for (int i = 0; i < NPR; i++) prs[i] = lf::sv_pair(V, i);
-    auto find = [&](unsigned s_, unsigned b_) {
-        for (int i = 0; i < NPR; i++)
-            if (prs[i].s == s_ && prs[i].b == b_) return i;
-        return -1;
-    };
-    std::vector<E9> wa(NX), wb(NX);
-    for (int x = 0; x < NX; x++) {
-        if (x < V) { wa[x] = W[x]; wb[x] = e9_neg(W[x]); }
-        else { wa[x] = e9_zero(); wb[x] = W[x - V]; }
-    }
-    auto mul = [&](const E9 &a, const E9 &b) { return e9_mul(a, b, nuM); };
-    for (int x = 0; x < NX; x++)
-        for (int y = x; y < NX; y++) {
-            const E9 p2[3] = {mul(wa[x], wa[y]), e9_add(mul(wa[x], wb[y]), mul(wb[x], wa[y])), mul(wb[x], wb[y])};
-            for (int z = y; z < NX; z++) {
-                E9 p3[4];
-                p3[0] = mul(p2[0], wa[z]);
-                p3[1] = e9_add(mul(p2[0], wb[z]), mul(p2[1], wa[z]));
-                p3[2] = e9_add(mul(p2[1], wb[z]), mul(p2[2], wa[z]));
-                p3[3] = mul(p2[2], wb[z]);
-                int mult, idx;
-                if (x == y && y == z) { mult = 1; idx = find(1u << x, 1u << x); }
-                else if (x == y) { mult = 3; idx = find(1u << z, (1u << x) | (1u << z)); }      // y_x^2 y_z = b_x y_z
-                else if (y == z) { mult = 3; idx = find(1u << x, (1u << x) | (1u << y)); }      // y_x y_y^2 = y_x b_y
-                else { mult = 6; const unsigned mk = (1u << x) | (1u << y) | (1u << z); idx = find(mk, mk); }
-                for (int e = 0; e < 4; e++) {
-                    E9 acc = e9_zero();
-                    for (int i = 0; i < mult; i++) acc = e9_add(acc, p3[e]);
-                    Cf[(size_t)idx * 4 + e] = e9_add(Cf[(size_t)idx * 4 + e], acc);
-                }
-            }
-        }
-    for (int x = 0; x < NX; x++) {   // - h
-        const int idx = find(1u << x, 1u << x);
-        Cf[(size_t)idx * 4] = e9_sub(Cf[(size_t)idx * 4], wa[x]);
-        Cf[(size_t)idx * 4 + 1] = e9_sub(Cf[(size_t)idx * 4 + 1], wb[x]);
-    }
-    out.resize((size_t)NPR * 4 * TAU);
-    for (size_t i = 0; i < (size_t)NPR * 4; i++)
-        for (int q = 0; q < TAU; q++) out[i * TAU + q] = Cf[i].c[q];
-}
-
 static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_witness **w_out, u64 *proof) {
     const lf_params &P = c->P;
     size_t m = c->m, n = c->n, N = c->N;
     u32 K = P.K, K2 = 2 * K, deg = 2 * P.b;
     size_t ll = lcccs_len(&P, TAU);
     const u64 nu = c->ring.T.nu;
-    std::vector<H9> alpha(K2), zeta(K2), mu(K2), beta(P.s);
+    const BbV hv{c->ring};
+    std::vector<H9> alpha, zeta, mu, beta;
     // the bit-plane form of the two witnesses (GEMM rounds below) needs no challenge: built while the host squeezes alpha and zeta
     u32 *svbits[2] = {nullptr, nullptr};
     {
@@ -445,13 +333,7 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
                 launch_bbsv_bits(S[sd].planes, N, N, K, svbits[sd], c->stream());
             }
     }
-    {
-        HostTimer ht(c);
-        tr.absorb_label("alpha_s");
-        for (u32 i = 0; i < K2; i++) alpha[i] = tr.get_challenge();
-        tr.absorb_label("zeta_s");
-        for (u32 i = 0; i < K2; i++) zeta[i] = tr.get_challenge();
-    }
+    { HostTimer ht(c); lfs::draw_alpha_zeta<BbV>(tr, K2, alpha, zeta); }
     // The G tables need alpha and zeta only: their chains are enqueued here, and the host squeezes mu and beta while the GPU combines the z_k (the
     // challenge order of the transcript -- alpha, zeta, mu, beta: folding/utils.rs:52-95 -- is untouched)
     size_t ph = c->ev_begin(13);
@@ -459,9 +341,8 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
     std::vector<E9C> mu_c((size_t)K2 * TAU), a_pow((size_t)K2 * TAU);
     std::vector<E9PreC> mu_pre((size_t)K2 * TAU), z_pow((size_t)K2 * P.t);
     for (u32 i = 0; i < K2; i++) {
-        H9 pa = alpha[i], pz = zeta[i];
-        for (u32 d = 0; d < (u32)TAU; d++) { a_pow[(size_t)i * TAU + d] = e9c_from_h9(pa); pa = c->ring.mul9(pa, alpha[i]); }
-        for (u32 j = 0; j < P.t; j++) { z_pow[(size_t)i * P.t + j] = e9pre_from_h9(pz, nu); pz = c->ring.mul9(pz, zeta[i]); }
+        lfs::powers(hv, alpha[i], TAU, [&](u32 d, const H9 &pw) { a_pow[(size_t)i * TAU + d] = e9c_from_h9(pw); });
+        lfs::powers(hv, zeta[i], P.t, [&](u32 j, const H9 &pw) { z_pow[(size_t)i * P.t + j] = e9pre_from_h9(pw, nu); });
     }
     E9C *d_mu, *d_ap;
     E9PreC *d_mup, *d_zp;
@@ -501,22 +382,12 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
             HIPCHK(hipStreamWaitEvent(s0, c->ev_prep[1], 0));
         }
     }
-    {
-        HostTimer ht(c);
-        tr.absorb_label("mu_s");
-        for (u32 i = 0; i + 1 < K2; i++) mu[i] = tr.get_challenge();
-        mu[K2 - 1] = h9_one();
-        tr.absorb_label("beta_s");
-        for (u32 i = 0; i < P.s; i++) beta[i] = tr.get_challenge();
-    }
-    for (u32 i = 0; i < K2; i++) {
-        H9 pm = mu[i];
-        for (u32 d = 0; d < (u32)TAU; d++) {
-            mu_c[(size_t)i * TAU + d] = e9c_from_h9(pm);
-            mu_pre[(size_t)i * TAU + d] = e9pre_from_h9(pm, nu);
-            pm = c->ring.mul9(pm, mu[i]);
-        }
-    }
+    { HostTimer ht(c); lfs::draw_mu_beta<BbV>(tr, K2, P.s, mu, beta); }
+    for (u32 i = 0; i < K2; i++)
+        lfs::powers(hv, mu[i], TAU, [&](u32 d, const H9 &pw) {
+            mu_c[(size_t)i * TAU + d] = e9c_from_h9(pw);
+            mu_pre[(size_t)i * TAU + d] = e9pre_from_h9(pw, nu);
+        });
     BB_MARK(" fold challenges");
     RET(upload_consts(c, "c_mu", mu_c, &d_mu));
     RET(upload_consts(c, "c_mup", mu_pre, &d_mup));
@@ -527,7 +398,7 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
     ph = c->ev_begin(14);
     u64 *msgs = proof;
     std::vector<H9> pt(P.s);
-    { HostTimer ht(c); sc_prologue(tr, P.s, deg); }
+    { HostTimer ht(c); lfs::sumcheck_prologue<BbV>(tr, P.s, deg); }
     // working tables (ping-pong): 5 special tables (eqL eqR eqB G1 G2 = 171 planes) + the 2K*9 materialised f-hat tables
     const size_t T5P = 3 * TAU + 2 * RE;
     fe *F[2], *T5[2];
@@ -660,11 +531,13 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
         if (use_sv && (int)round <= c->tn.sv_rounds && round <= 3 && a.pcnt >= sv_min && bbsv_shape_ok(svV, a.pcnt, K)) {
             // weights W_b = eq((r_1..r_{i-1}), b), their digit-monomial coefficients, c_i = prod_{k<i} eq(beta_k, r_k), w_h = c_i eq(beta_i, h)
             const fe nuM = from_canon(nu);
-            std::vector<E9> W((size_t)svV, e9_from_h9(h9_one()));
+            std::vector<H9> W((size_t)svV, h9_one()), Cf;
             for (int b = 0; b < svV; b++)
-                for (u32 j = 0; j + 1 < round; j++) W[b] = e9_mul(W[b], e9_from_h9(((b >> j) & 1) ? pt[j] : h9_sub(h9_one(), pt[j])), nuM);
-            std::vector<fe> coef;
-            bbsv_build_coef(svV, W.data(), nuM, coef);
+                for (u32 j = 0; j + 1 < round; j++) W[b] = c->ring.mul9(W[b], ((b >> j) & 1) ? pt[j] : h9_sub(h9_one(), pt[j]));
+            lfs::sv_coef(hv, svV, W.data(), lf::sv_num_pairs(svV), [&](int i) { return lf::sv_pair(svV, i); }, Cf);
+            std::vector<fe> coef(Cf.size() * TAU);   // C_pi(X) -> [pairs][4][9] Montgomery words
+            for (size_t i = 0; i < Cf.size(); i++)
+                for (int q = 0; q < TAU; q++) coef[i * TAU + q] = from_canon(Cf[i].c[q]);
             E9 cc = e9_from_h9(h9_one());
             for (u32 k2 = 1; k2 < round; k2++) {
                 const E9 b = e9_from_h9(beta[k2 - 1]), r = e9_from_h9(pt[k2 - 1]), one = e9_from_h9(h9_one());
@@ -805,7 +678,7 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
         memcpy(evs, od, (size_t)(deg + 1) * RE * 8);
         if (sharded) RET(exchange_modsum(c, evs, (size_t)(deg + 1) * RE));
         HostTimer ht(c);
-        pt[round - 1] = sc_round_transcript(tr, evs, deg + 1);
+        pt[round - 1] = lfs::sumcheck_round<BbV>(tr, evs, deg + 1);
         if (round <= 6 || round == 10) { char nm[32]; snprintf(nm, sizeof nm, "  round %u", round); BB_MARK(nm); }
     }
     c->ev_end(ph);
@@ -880,21 +753,12 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
     HIPCHK(hipStreamSynchronize(c->stream()));
     BB_MARK("  eta down");
     memcpy(eta, hp + nth, net * 8);
-    std::vector<u64> rho_c((size_t)K2 * RE, 0), rho((size_t)K2 * RE);
-    std::vector<int8_t> rho8((size_t)K2 * 24, 0);
-    {
+    std::vector<u64> rho_c, rho;
+    std::vector<int8_t> rho8;
+    {   // get_rhos (folding/utils.rs:116-131)
         HostTimer ht(c);
         tr.absorb_ring(eta, (size_t)K2 * P.t);
-        tr.absorb_label("rho_s");   // get_rhos (folding/utils.rs:116-131)
-        for (u32 i = 0; i + 1 < K2; i++) tr.get_short_challenge(&rho_c[(size_t)i * RE]);
-        rho_c[(size_t)(K2 - 1) * RE] = 1;
-        for (u32 i = 0; i < K2; i++) {
-            c->ring.crt(&rho_c[(size_t)i * RE], &rho[(size_t)i * RE]);
-            for (int q2 = 0; q2 < 24; q2++) {
-                u64 v = rho_c[(size_t)i * RE + q2];
-                rho8[(size_t)i * 24 + q2] = (int8_t)(v > BB_P / 2 ? -(int64_t)(BB_P - v) : (int64_t)v);
-            }
-        }
+        lfs::draw_rho(hv, tr, K2, rho_c, rho, &rho8);
     }
     // f_0 in the coefficient domain -> new witness
     int8_t *d_rho;
@@ -912,53 +776,10 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
     launch_recompose_crt(c->dev, npl, N, P.wit_len, P.L, P.B, 1, 0, nw, P.wit_len, 0, c->stream());
     BB_MARK("  eta absorbed, rho drawn, fold_witness enqueued");
 
-    // compute_v0_u0_x0_cm_0 (folding/utils.rs:460-521) on the host while the GPU folds the witness
+    // the folded instance (folding/utils.rs:460-521) on the host while the GPU folds the witness
     {
-    HostTimer ht(c);
-    u64 *o = lcccs_out;
-    for (u32 i = 0; i < P.s; i++, o += RE) BbHostRing::from_h9(pt[i], o);
-    {   // v_0 = rot_lin_combination(rho_coeff, theta) (cyclotomic-rings/src/rotation.rs:85-104)
-        // the rotations of a short challenge stay small signed integers (X^72 = X^36 - 1 adds at most one more term per step) and theta words are < 2^31:
-        // plain 64-bit integer multiply-accumulates, one reduction per output word (32 * 72 terms of < 2^31 * 2^12 fit easily)
-        // As one polynomial product per i: full[a + b] += rho_a theta_b over the (at most 24 non-zero) coefficients of rho and all of theta -- the inner loop is one
-        // contiguous multiply-add over theta's 72 x 9 words -- and ONE reduction of the degree-142 product by X^72 = X^36 - 1 at the end (the rotation-by-rotation
-        // form walked 72 x 72 pairs per i with rotations that fill up: twice the multiply-adds, none of them contiguous).  |full| < 72 * 32 * 2^5 * 2^31 < 2^48.
-        std::vector<int64_t> acc((size_t)(2 * RE) * TAU, 0);
-        std::vector<u64> res((size_t)RE * TAU, 0);   // res[j] in F_{p^9}
-        for (u32 i = 0; i < K2; i++) {
-            const u64 *th = theta + (size_t)i * TAU * RE;
-            for (int a = 0; a < RE; a++) {
-                const u64 rc = rho_c[(size_t)i * RE + a] % BB_P;
-                const int64_t ra = rc > BB_P / 2 ? (int64_t)rc - (int64_t)BB_P : (int64_t)rc;
-                if (!ra) continue;
-                int64_t *dst = acc.data() + (size_t)a * TAU;
-                for (int x = 0; x < RE * TAU; x++) dst[x] += (int64_t)th[x] * ra;
-            }
-        }
-        for (int d = 2 * RE - 2; d >= RE; d--)
-            for (int q2 = 0; q2 < TAU; q2++) {
-                const int64_t v = acc[(size_t)d * TAU + q2];
-                acc[(size_t)(d - RE / 2) * TAU + q2] += v;
-                acc[(size_t)(d - RE) * TAU + q2] -= v;
-            }
-        for (size_t x = 0; x < res.size(); x++) { const int64_t r = acc[x] % (int64_t)BB_P; res[x] = (u64)(r < 0 ? r + (int64_t)BB_P : r); }
-        memcpy(o, res.data(), res.size() * 8);
-        o += (size_t)TAU * RE;
-    }
-    u64 tmp[RE];
-    auto part = [&](u32 i) { return &S[i < K ? 0 : 1].lcccs[(size_t)(i % K) * ll * RE]; };
-    for (u32 q2 = 0; q2 < P.kappa; q2++, o += RE) {
-        memset(o, 0, RE * 8);
-        for (u32 i = 0; i < K2; i++) { c->ring.mul_ntt(part(i) + ((size_t)P.s + TAU + q2) * RE, &rho[(size_t)i * RE], tmp); BbHostRing::add(o, tmp, o); }
-    }
-    for (u32 j = 0; j < P.t; j++, o += RE) {
-        memset(o, 0, RE * 8);
-        for (u32 i = 0; i < K2; i++) { c->ring.mul_ntt(&rho[(size_t)i * RE], eta + ((size_t)i * P.t + j) * RE, tmp); BbHostRing::add(o, tmp, o); }
-    }
-    for (u32 q2 = 0; q2 < P.l + 1; q2++, o += RE) {
-        memset(o, 0, RE * 8);
-        for (u32 i = 0; i < K2; i++) { c->ring.mul_ntt(&rho[(size_t)i * RE], part(i) + ((size_t)P.s + TAU + P.kappa + P.t + q2) * RE, tmp); BbHostRing::add(o, tmp, o); }
-    }
+        HostTimer ht(c);
+        lfs::fold_instance(hv, P, pt, theta, eta, rho_c.data(), rho.data(), [&](u32 i) { return &S[i / K].lcccs[(size_t)(i % K) * ll * RE]; }, lcccs_out);
     }
     BB_MARK("  folded instance on the host");
     HIPCHK(hipStreamSynchronize(c->stream()));
@@ -991,7 +812,7 @@ int BbCtx::fold_step(BbTranscript &tr, const uint64_t *acc, const lf_witness *w_
     if (c->kappa != P.kappa || c->nA_total != c->N || w_acc->N != c->N || w_i->N != c->N) return LF_ERR_INVALID;
     HIPCHK(hipSetDevice(c->device));
     std::vector<H9> rL;
-    if (!lcccs_point(P, acc, rL)) return LF_ERR_UNSUPPORTED;   // evaluation points are always diagonal challenges
+    if (!lfs::lcccs_point<BbV>(P, acc, rL)) return LF_ERR_UNSUPPORTED;   // evaluation points are always diagonal challenges
     c->tn = Tunables::read((size_t)1 << 15);
     c->ev_reset();
     c->host_tr_ms = 0;
@@ -1020,13 +841,7 @@ int BbCtx::fold_step(BbTranscript &tr, const uint64_t *acc, const lf_witness *w_
     BB_MARK("L1: right commit enqueued");
     c->cur_lane = 0;
     c->lin_blocks = 0;
-    {   // absorb_public_input (nifs.rs:175-197) -- while the GPU already works on the left decomposition
-        HostTimer ht(c);
-        tr.absorb_label("acc");
-        tr.absorb_ring(acc, ll);
-        tr.absorb_label("cm_i");
-        tr.absorb_ring(cm_i, cccs_len(&P));
-    }
+    { HostTimer ht(c); lfs::absorb_public_input<BbV>(tr, P, acc, cm_i); }   // while the GPU already works on the left decomposition
     c->vs_keep = true;
     BB_MARK("public input absorbed");
     if (rc == LF_OK) rc = linearize_impl(c, tr, cm_i, w_i, lin.data(), lin_proof, &eq_r_R);
@@ -1034,7 +849,7 @@ int BbCtx::fold_step(BbTranscript &tr, const uint64_t *acc, const lf_witness *w_
     c->vs_keep = false;
     std::vector<H9> rR;
     if (rc == LF_OK) {
-        lcccs_point(P, lin.data(), rR);
+        lfs::lcccs_point<BbV>(P, lin.data(), rR);
         rc = dec_enqueue_evals(c, lin.data(), rR, w_i, "R", eq_r_R, S[1], decr, pdR);
     }
     c->vs_wit = nullptr;
@@ -1061,7 +876,7 @@ int BbCtx::decomposition_prove(BbTranscript &tr, const uint64_t *lcccs, const lf
     if (c->kappa != P.kappa || c->nA_total != c->N || wit->N != c->N) return LF_ERR_INVALID;
     HIPCHK(hipSetDevice(c->device));
     std::vector<H9> r;
-    if (!lcccs_point(P, lcccs, r)) return LF_ERR_UNSUPPORTED;
+    if (!lfs::lcccs_point<BbV>(P, lcccs, r)) return LF_ERR_UNSUPPORTED;
     c->tn = Tunables::read((size_t)1 << 15);
     c->ev_reset();
     c->host_tr_ms = 0;
@@ -1098,7 +913,7 @@ int BbCtx::folding_prove(BbTranscript &tr, const uint64_t *lcccs_s, const lf_wit
     for (int sd = 0; sd < 2; sd++) {
         const u64 *base = lcccs_s + (size_t)sd * K * ll * RE;
         std::vector<H9> r;
-        if (!lcccs_point(P, base, r)) return LF_ERR_UNSUPPORTED;
+        if (!lfs::lcccs_point<BbV>(P, base, r)) return LF_ERR_UNSUPPORTED;
         for (u32 k = 1; k < K; k++)
             if (memcmp(base, base + (size_t)k * ll * RE, (size_t)P.s * RE * 8) != 0) return LF_ERR_INVALID;
         const lf_witness *w = sd ? w_right : w_left;

@@ -123,7 +123,7 @@ static int lcccs_check(C *c, const u64 *lcccs, const lf_witness *wit, u64 bound,
     RET(check_state(c, wit, true));
     const lf_params &P = c->P;
     std::vector<typename R::Ext> pt;
-    if (!lcccs_point(P, lcccs, pt)) return LF_ERR_UNSUPPORTED;   // the reference's points are diagonal challenges (as lf_fold_step)
+    if (!lfs::lcccs_point<typename R::Host>(P, lcccs, pt)) return LF_ERR_UNSUPPORTED;   // the reference's points are diagonal challenges (as lf_fold_step)
     HIPCHK(hipSetDevice(c->device));
     // lcccs = r[s] v[tau] cm[kappa] u[t] x_w[l] h
     const size_t vw = TAU * RE, uw = (size_t)P.t * RE, cmw = (size_t)P.kappa * RE, ou = 0, ov = uw, ocm = ov + vw, ow = ocm + cmw;

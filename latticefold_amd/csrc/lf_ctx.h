@@ -259,8 +259,6 @@ int down_small(lf_ctx *c, const u64 *dsrc, size_t words, u64 *host);
 void shard_slice(const lf_ctx *c, size_t n, size_t *i0, size_t *cnt);
 struct GatherPart { const u64 *src; size_t src_ld; u64 *dst; size_t planes; };
 int shard_col_range(lf_ctx *c, size_t r0, size_t rcnt, size_t *lo, size_t *hi);
-Fq3 sc_round_transcript(Transcript &tr, const u64 *evals, u32 npts);
-void sc_prologue(Transcript &tr, u32 nv, u32 deg);
 int gather_slices(lf_ctx *c, u64 *buf, size_t planes, size_t n);
 struct SideState {
     const int32_t *planes = nullptr;
@@ -314,9 +312,6 @@ int commit_download(lf_ctx *c, const u64 *dev, size_t words, u64 *host);
 int commit_parts_i8g(lf_ctx *c, const unsigned char *D, size_t ldn, u32 NP, u64 *out_dev);
 // the digit planes of a witness, cut on the calling lane's stream into the buffer `name`
 int sb_cut_parts(lf_ctx *c, const lf_witness *wit, const char *name, const unsigned char **D);
-void fold_draw_rho(lf_ctx *c, Transcript &tr, const u64 *eta, std::vector<u64> &rho_c, std::vector<u64> &rho, std::vector<int8_t> &rho8);
-void fold_instance_host(lf_ctx *c, const std::vector<Fq3> &pt, const u64 *theta, const u64 *eta, const std::vector<u64> &rho_c, const std::vector<u64> &rho, SideState *S,
-                        u64 *lcccs_out);
 int fold_impl_sb(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out, lf_witness **w_out, u64 *proof);
 int sb_fold_round_abi(lf_ctx *c, const u64 *t5, const u64 *F, size_t n, const Fq3Const *d_mu, u64 *evals_out);
 int dot_batch_dev(lf_ctx *c, const u64 *X, size_t ldx, u32 na, const u64 *Y, size_t ldy, u32 nb, size_t n, u64 *dpart, u64 *od, hipStream_t st = nullptr,
@@ -328,5 +323,4 @@ int lin_tail_rounds(lf_ctx *c, Transcript &tr, const u64 *cur, const u64 *cure, 
 // z tables [K][24][n] = heads (l + 1 elements per table) || the recomposed witness columns [w0, w0 + wcnt) (lf_prove.cpp)
 int build_z(lf_ctx *c, const int32_t *planes, u32 K, int mode_bits, const u64 *heads, u64 *z, size_t w0 = 0, size_t wcnt = (size_t)-1,
             const unsigned char *D = nullptr /* small-base path: the digit planes the K parts come from (lf_sb.h) */);
-bool lcccs_point(const lf_params &P, const u64 *lcccs, std::vector<Fq3> &pt);   // the LCCCS point r as F_{p^3} challenges; false if not diagonal
 #pragma GCC visibility pop

@@ -31,7 +31,7 @@ static int tail_host_rounds(lf_ctx *c, Transcript &tr, u32 epoch, u32 nr, u32 np
         HostTimer ht(c);
         Fq3 r;
         if (dev_transcript) r = fq3_make(mail->chal_out[i][0], mail->chal_out[i][1], mail->chal_out[i][2]);   // drawn by the device sponge
-        else r = sc_round_transcript(tr, evs, npts);
+        else r = lfs::sumcheck_round<GoldV>(tr, evs, npts);
         pt[i] = r;
         if (i + 1 < nr && !dev_transcript) {
             mail->chal[i][0] = r.c[0]; mail->chal[i][1] = r.c[1]; mail->chal[i][2] = r.c[2];
@@ -106,144 +106,23 @@ static int fold_tail_rounds(lf_ctx *c, Transcript &tr, const FoldRoundArgs &a, u
     return tail_host_rounds(c, tr, A.epoch, nr, deg + 1, A.dev_transcript != 0, msgs + (size_t)(round - 1) * (deg + 1) * 24, &pt[round - 1]);
 }
 
-// C_pi(X) of lf_sv_rounds.h for the V weights W_b = eq((r_1..), b): coefficient table [pairs][4][3] (internal basis words)
-static void sv_build_coef(lf_ctx *c, int V, const Fq3 *W, std::vector<u64> &out) {
-    const int NX = 2 * V, NPR = sv_num_pairs(V);
-    std::vector<Fq3> C((size_t)NPR * 4, fq3_zero());
-    std::vector<SvPair> prs(NPR);
-    for (int i = 0; i < NPR; i++) prs[i] = sv_pair(V, i);
-    auto find = [&](unsigned s, unsigned b) {
-        for (int i = 0; i < NPR; i++)
-            if (prs[i].s == s && prs[i].b == b) return i;
-        return -1;
-    };
-    // w_x(X) = wa_x + wb_x X
-    std::vector<Fq3> wa(NX), wb(NX);
-    for (int x = 0; x < NX; x++) {
-        if (x < V) { wa[x] = W[x]; wb[x] = fq3_neg(W[x]); }
-        else { wa[x] = fq3_zero(); wb[x] = W[x - V]; }
-    }
-    // h^3: multisets {x <= y <= z} with their multinomial multiplicity
-    for (int x = 0; x < NX; x++)
-        for (int y = x; y < NX; y++) {
-            const Fq3 p2[3] = {c->ring.mul3(wa[x], wa[y]), fq3_add(c->ring.mul3(wa[x], wb[y]), c->ring.mul3(wb[x], wa[y])), c->ring.mul3(wb[x], wb[y])};
-            for (int z = y; z < NX; z++) {
-                Fq3 p3[4];
-                p3[0] = c->ring.mul3(p2[0], wa[z]);
-                p3[1] = fq3_add(c->ring.mul3(p2[0], wb[z]), c->ring.mul3(p2[1], wa[z]));
-                p3[2] = fq3_add(c->ring.mul3(p2[1], wb[z]), c->ring.mul3(p2[2], wa[z]));
-                p3[3] = c->ring.mul3(p2[2], wb[z]);
-                int mult, idx;
-                if (x == y && y == z) { mult = 1; idx = find(1u << x, 1u << x); }
-                else if (x == y) { mult = 3; idx = find(1u << z, (1u << x) | (1u << z)); }      // y_x^2 y_z = b_x y_z
-                else if (y == z) { mult = 3; idx = find(1u << x, (1u << x) | (1u << y)); }      // y_x y_y^2 = y_x b_y
-                else { mult = 6; const unsigned mk = (1u << x) | (1u << y) | (1u << z); idx = find(mk, mk); }
-                for (int e = 0; e < 4; e++) {
-                    Fq3 t = p3[e], acc = fq3_zero();
-                    for (int i = 0; i < mult; i++) acc = fq3_add(acc, t);
-                    C[(size_t)idx * 4 + e] = fq3_add(C[(size_t)idx * 4 + e], acc);
-                }
-            }
-        }
-    for (int x = 0; x < NX; x++) {   // - h
-        const int idx = find(1u << x, 1u << x);
-        C[(size_t)idx * 4] = fq3_sub(C[(size_t)idx * 4], wa[x]);
-        C[(size_t)idx * 4 + 1] = fq3_sub(C[(size_t)idx * 4 + 1], wb[x]);
-    }
-    out.resize((size_t)NPR * 12);
-    for (size_t i = 0; i < (size_t)NPR * 4; i++)
-        for (int q = 0; q < 3; q++) out[i * 3 + q] = C[i].c[q];
-}
-
-// absorb eta and draw the short folding challenges: get_rhos (folding/utils.rs:116-131) -- coefficient form, NTT form and int8 coefficients of the 2K rho_i
-void fold_draw_rho(lf_ctx *c, Transcript &tr, const u64 *eta, std::vector<u64> &rho_c, std::vector<u64> &rho, std::vector<int8_t> &rho8) {
-    const lf_params &P = c->P;
-    const u32 K2 = 2 * P.K;
-    rho_c.assign((size_t)K2 * 24, 0); rho.assign((size_t)K2 * 24, 0); rho8.assign((size_t)K2 * 24, 0);
-    {
-        HostTimer ht(c);
-        tr.absorb_ring(eta, (size_t)K2 * P.t);
-        // get_rhos (folding/utils.rs:116-131)
-        tr.absorb_label("rho_s");
-        for (u32 i = 0; i + 1 < K2; i++) tr.get_short_challenge(&rho_c[(size_t)i * 24]);
-        rho_c[(size_t)(K2 - 1) * 24] = 1;
-        for (u32 i = 0; i < K2; i++) {
-            c->ring.crt(&rho_c[(size_t)i * 24], &rho[(size_t)i * 24]);
-            for (int q2 = 0; q2 < 24; q2++) {
-                u64 v = rho_c[(size_t)i * 24 + q2];
-                rho8[(size_t)i * 24 + q2] = (int8_t)(v > LF_P / 2 ? -(int64_t)(LF_P - v) : (int64_t)v);
-            }
-        }
-    }
-}
-// compute_v0_u0_x0_cm_0 (folding/utils.rs:460-521): the folded LCCCS from the point, theta, eta, the challenges rho_i and the 2K decomposed instances
-void fold_instance_host(lf_ctx *c, const std::vector<Fq3> &pt, const u64 *theta, const u64 *eta, const std::vector<u64> &rho_c, const std::vector<u64> &rho, SideState *S,
-                        u64 *lcccs_out) {
-    const lf_params &P = c->P;
-    const u32 K = P.K, K2 = 2 * K;
-    const size_t ll = lf_lcccs_len(&P);
-    HostTimer ht(c);
-    u64 *o = lcccs_out;
-    for (u32 i = 0; i < P.s; i++, o += 24) HostRing::from_fq3(pt[i], o);
-    {   // v_0 = rot_lin_combination(rho_coeff, theta) (cyclotomic-rings/src/rotation.rs:85-104)
-        Fq3 res[24];
-        for (int j = 0; j < 24; j++) res[j] = fq3_zero();
-        for (u32 i = 0; i < K2; i++) {
-            u64 rot[24];
-            memcpy(rot, &rho_c[(size_t)i * 24], sizeof(rot));
-            const u64 *th = theta + (size_t)i * 72;
-            for (int bi = 0; bi < 24; bi++) {
-                Fq3 b = fq3_make(th[3 * bi], th[3 * bi + 1], th[3 * bi + 2]);
-                for (int j = 0; j < 24; j++)
-                    if (rot[j]) res[j] = fq3_add(res[j], fq3_mul_fq(b, rot[j]));
-                // multiply by X modulo X^24 - X^12 + 1
-                u64 top = rot[23];
-                for (int j = 23; j > 0; j--) rot[j] = rot[j - 1];
-                rot[0] = fq_neg(top);
-                rot[12] = fq_add(rot[12], top);
-            }
-        }
-        for (int j = 0; j < 24; j++) { o[3 * j] = res[j].c[0]; o[3 * j + 1] = res[j].c[1]; o[3 * j + 2] = res[j].c[2]; }
-        o += 72;
-    }
-    u64 tmp[24];
-    auto part = [&](u32 i) { return &S[i < K ? 0 : 1].lcccs[(size_t)(i % K) * ll * 24]; };
-    for (u32 q2 = 0; q2 < P.kappa; q2++, o += 24) {
-        memset(o, 0, 24 * 8);
-        for (u32 i = 0; i < K2; i++) { c->ring.mul_ntt(part(i) + ((size_t)P.s + 3 + q2) * 24, &rho[(size_t)i * 24], tmp); HostRing::add(o, tmp, o); }
-    }
-    for (u32 j = 0; j < P.t; j++, o += 24) {
-        memset(o, 0, 24 * 8);
-        for (u32 i = 0; i < K2; i++) { c->ring.mul_ntt(&rho[(size_t)i * 24], eta + ((size_t)i * P.t + j) * 24, tmp); HostRing::add(o, tmp, o); }
-    }
-    for (u32 q2 = 0; q2 < P.l + 1; q2++, o += 24) {
-        memset(o, 0, 24 * 8);
-        for (u32 i = 0; i < K2; i++) { c->ring.mul_ntt(&rho[(size_t)i * 24], part(i) + ((size_t)P.s + 3 + P.kappa + P.t + q2) * 24, tmp); HostRing::add(o, tmp, o); }
-    }
-}
 // LFFoldingProver::prove (nifs/folding.rs:42-130)
 int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out, lf_witness **w_out, u64 *proof) {
     if (c->P.b != 2) return fold_impl_sb(c, tr, S, lcccs_out, w_out, proof);   // small-base path (lf_fold_sb.cpp)
     const lf_params &P = c->P;
     size_t m = c->m, n = c->n, N = c->N;
     u32 K = P.K, K2 = 2 * K, deg = 2 * P.b;
-    std::vector<Fq3> alpha(K2), zeta(K2), mu(K2), beta(P.s);
-    {
-        HostTimer ht(c);
-        tr.absorb_label("alpha_s");
-        for (u32 i = 0; i < K2; i++) alpha[i] = tr.get_challenge();
-        tr.absorb_label("zeta_s");
-        for (u32 i = 0; i < K2; i++) zeta[i] = tr.get_challenge();
-    }
+    const GoldV hv{c->ring};
+    std::vector<Fq3> alpha, zeta, mu, beta;
+    { HostTimer ht(c); lfs::draw_alpha_zeta<GoldV>(tr, K2, alpha, zeta); }
     // The G tables need alpha and zeta only: their chains are enqueued HERE, and the host squeezes mu and beta (~100 permutations) while the GPU combines
     // the z_k -- the challenge order of the transcript (alpha, zeta, mu, beta: folding/utils.rs:52-95) is untouched.
     size_t ph = c->ev_begin(13);
     // powers x^{j+1}
     std::vector<Fq3Const> mu_pow((size_t)K2 * 3), a_pow((size_t)K2 * 3), z_pow((size_t)K2 * P.t);
     for (u32 i = 0; i < K2; i++) {
-        Fq3 pa = alpha[i], pz = zeta[i];
-        for (u32 d = 0; d < 3; d++) { a_pow[(size_t)i * 3 + d] = f3c(pa); pa = c->ring.mul3(pa, alpha[i]); }
-        for (u32 j = 0; j < P.t; j++) { z_pow[(size_t)i * P.t + j] = f3c(pz); pz = c->ring.mul3(pz, zeta[i]); }
+        lfs::powers(hv, alpha[i], 3, [&](u32 d, const Fq3 &pw) { a_pow[(size_t)i * 3 + d] = f3c(pw); });
+        lfs::powers(hv, zeta[i], P.t, [&](u32 j, const Fq3 &pw) { z_pow[(size_t)i * P.t + j] = f3c(pw); });
     }
     Fq3Const *d_mu, *d_ap, *d_zp;
     RET(upload_consts(c, "c_ap", a_pow, &d_ap));
@@ -295,19 +174,9 @@ int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out,
             HIPCHK(hipStreamWaitEvent(s0, c->ev_prep[1], 0));
         }
     }
-    {
-        HostTimer ht(c);
-        tr.absorb_label("mu_s");
-        for (u32 i = 0; i + 1 < K2; i++) mu[i] = tr.get_challenge();
-        mu[K2 - 1] = fq3_one();
-        tr.absorb_label("beta_s");
-        for (u32 i = 0; i < P.s; i++) beta[i] = tr.get_challenge();
-    }
+    { HostTimer ht(c); lfs::draw_mu_beta<GoldV>(tr, K2, P.s, mu, beta); }
     TL_MARK(" fold challenges");
-    for (u32 i = 0; i < K2; i++) {
-        Fq3 pm = mu[i];
-        for (u32 d = 0; d < 3; d++) { mu_pow[(size_t)i * 3 + d] = f3c(pm); pm = c->ring.mul3(pm, mu[i]); }
-    }
+    for (u32 i = 0; i < K2; i++) lfs::powers(hv, mu[i], 3, [&](u32 d, const Fq3 &pw) { mu_pow[(size_t)i * 3 + d] = f3c(pw); });
     RET(upload_consts(c, "c_mu", mu_pow, &d_mu));
     RET(build_eq_dev(c, beta.data(), P.s, eqb));
     // split form of the GEMM rounds (lf_sv_rounds.h): eqB fixed at r_1..r_{i-1} is c_i eq(beta_i, b) E_i[p] at entry 2p + b, E_i = eq((beta_{i+1}..beta_s), .) -- one
@@ -352,7 +221,7 @@ int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out,
     ph = c->ev_begin(14);
     u64 *msgs = proof;
     std::vector<Fq3> pt(P.s);
-    { HostTimer ht(c); sc_prologue(tr, P.s, deg); }
+    { HostTimer ht(c); lfs::sumcheck_prologue<GoldV>(tr, P.s, deg); }
     const size_t Gw = (size_t)c->sh_world, gr = (size_t)c->sh_rank;
     bool sharded = Gw > 1;
     // Rounds >= 4 with many pairs: fix_variables of the f-hat tables is fused into the (ALU-bound) round kernel,
@@ -534,8 +403,10 @@ int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out,
             std::vector<Fq3> W((size_t)svV, fq3_one());
             for (int b = 0; b < svV; b++)
                 for (u32 j = 0; j + 1 < round; j++) W[b] = c->ring.mul3(W[b], ((b >> j) & 1) ? pt[j] : fq3_sub(fq3_one(), pt[j]));
-            std::vector<u64> coef;
-            sv_build_coef(c, svV, W.data(), coef);
+            std::vector<Fq3> Cf;   // C_pi(X) -> [pairs][4][3] internal-basis words
+            lfs::sv_coef(hv, svV, W.data(), sv_num_pairs(svV), [&](int i) { return sv_pair(svV, i); }, Cf);
+            std::vector<u64> coef(Cf.size() * 3);
+            for (size_t i = 0; i < Cf.size(); i++) memcpy(&coef[i * 3], Cf[i].c, 3 * 8);
             u64 *d_coef, *gtmp, *svtp;
             unsigned char *sveb;
             int32_t *svpart, *svtot;
@@ -687,7 +558,7 @@ int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out,
         } else
         memcpy(evs, od_host, (size_t)(deg + 1) * 24 * 8);
         HostTimer ht(c);
-        pt[round - 1] = sc_round_transcript(tr, evs, deg + 1);
+        pt[round - 1] = lfs::sumcheck_round<GoldV>(tr, evs, deg + 1);
         if (round == 1) TL_MARK("  round 1");
         if (round == 2) TL_MARK("  round 2");
         if (round == 3) TL_MARK("  round 3");
@@ -781,7 +652,11 @@ int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out,
     TL_MARK(" theta/eta");
     std::vector<u64> rho_c, rho;
     std::vector<int8_t> rho8;
-    fold_draw_rho(c, tr, eta, rho_c, rho, rho8);
+    {   // get_rhos (folding/utils.rs:116-131)
+        HostTimer ht(c);
+        tr.absorb_ring(eta, (size_t)K2 * P.t);
+        lfs::draw_rho(hv, tr, K2, rho_c, rho, &rho8);
+    }
     // f_0 in the coefficient domain -> new witness
     int8_t *d_rho;
     RET(c->tbuf("c_rho", (size_t)K2 * 24 + 64, &d_rho));
@@ -800,8 +675,12 @@ int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out,
     LF_TRACE(c, "fold_witness");
     TL_MARK("  eta absorbed, rho drawn, fold_witness enqueued");
 
-    // compute_v0_u0_x0_cm_0 (folding/utils.rs:460-521) on the host while the GPU folds the witness
-    fold_instance_host(c, pt, theta, eta, rho_c, rho, S, lcccs_out);
+    // the folded instance (folding/utils.rs:460-521) on the host while the GPU folds the witness
+    {
+        HostTimer ht(c);
+        const size_t ll = lf_lcccs_len(&P);
+        lfs::fold_instance(hv, P, pt, theta, eta, rho_c.data(), rho.data(), [&](u32 i) { return &S[i / K].lcccs[(size_t)(i % K) * ll * 24]; }, lcccs_out);
+    }
     TL_MARK("  folded instance on the host");
     HIPCHK(hipStreamSynchronize(c->stream()));
     *w_out = new lf_witness{c, npl, N, c->device, N * 24 * 4};

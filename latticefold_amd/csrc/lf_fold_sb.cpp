@@ -46,28 +46,19 @@ int fold_impl_sb(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_o
     const size_t m = c->m, n = c->n, N = c->N, ldn = sb_ld(N);
     const u32 K = P.K, K2 = 2 * K, deg = 2 * P.b;
     if (!sb_base_ok(P.b) || c->sh_world > 1 || !S[0].D || !S[1].D) return LF_ERR_UNSUPPORTED;
-    std::vector<Fq3> alpha(K2), zeta(K2), mu(K2), beta(P.s);
+    const GoldV hv{c->ring};
+    std::vector<Fq3> alpha, zeta, mu, beta;
     {
         HostTimer ht(c);
-        tr.absorb_label("alpha_s");
-        for (u32 i = 0; i < K2; i++) alpha[i] = tr.get_challenge();
-        tr.absorb_label("zeta_s");
-        for (u32 i = 0; i < K2; i++) zeta[i] = tr.get_challenge();
-        tr.absorb_label("mu_s");
-        for (u32 i = 0; i + 1 < K2; i++) mu[i] = tr.get_challenge();
-        mu[K2 - 1] = fq3_one();
-        tr.absorb_label("beta_s");
-        for (u32 i = 0; i < P.s; i++) beta[i] = tr.get_challenge();
+        lfs::draw_alpha_zeta<GoldV>(tr, K2, alpha, zeta);
+        lfs::draw_mu_beta<GoldV>(tr, K2, P.s, mu, beta);
     }
     size_t ph = c->ev_begin(13);
     std::vector<Fq3Const> mu_pow((size_t)K2 * 3), a_pow((size_t)K2 * 3), z_pow((size_t)K2 * P.t);
     for (u32 i = 0; i < K2; i++) {
-        Fq3 pa = alpha[i], pz = zeta[i], pm = mu[i];
-        for (u32 d = 0; d < 3; d++) {
-            a_pow[(size_t)i * 3 + d] = f3c(pa); pa = c->ring.mul3(pa, alpha[i]);
-            mu_pow[(size_t)i * 3 + d] = f3c(pm); pm = c->ring.mul3(pm, mu[i]);
-        }
-        for (u32 j = 0; j < P.t; j++) { z_pow[(size_t)i * P.t + j] = f3c(pz); pz = c->ring.mul3(pz, zeta[i]); }
+        lfs::powers(hv, alpha[i], 3, [&](u32 d, const Fq3 &pw) { a_pow[(size_t)i * 3 + d] = f3c(pw); });
+        lfs::powers(hv, mu[i], 3, [&](u32 d, const Fq3 &pw) { mu_pow[(size_t)i * 3 + d] = f3c(pw); });
+        lfs::powers(hv, zeta[i], P.t, [&](u32 j, const Fq3 &pw) { z_pow[(size_t)i * P.t + j] = f3c(pw); });
     }
     Fq3Const *d_mu, *d_ap, *d_zp;
     RET(upload_consts(c, "c_ap", a_pow, &d_ap));
@@ -101,7 +92,7 @@ int fold_impl_sb(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_o
     c->fold_split_mask = 0;
     u64 *msgs = proof;
     std::vector<Fq3> pt(P.s);
-    { HostTimer ht(c); sc_prologue(tr, P.s, deg); }
+    { HostTimer ht(c); lfs::sumcheck_prologue<GoldV>(tr, P.s, deg); }
     u64 *F[2], *T5[2];
     RET(c->tbuf("sb_F0", (size_t)K2 * 3 * 24 * (m / 2), &F[0]));
     RET(c->tbuf("sb_F1", (size_t)K2 * 3 * 24 * (m / 4 ? m / 4 : 1), &F[1]));
@@ -146,7 +137,7 @@ int fold_impl_sb(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_o
         u64 *evs = msgs + (size_t)(round - 1) * (deg + 1) * 24;
         HostTimer ht(c);
         sb_compose_message(h.data(), h.data() + sb_round_out_words(), deg, evs);
-        pt[round - 1] = sc_round_transcript(tr, evs, deg + 1);
+        pt[round - 1] = lfs::sumcheck_round<GoldV>(tr, evs, deg + 1);
     }
     c->ev_end(ph);
 
@@ -178,7 +169,11 @@ int fold_impl_sb(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_o
     }
     std::vector<u64> rho_c, rho;
     std::vector<int8_t> rho8;
-    fold_draw_rho(c, tr, eta, rho_c, rho, rho8);
+    {   // get_rhos (folding/utils.rs:116-131)
+        HostTimer ht(c);
+        tr.absorb_ring(eta, (size_t)K2 * P.t);
+        lfs::draw_rho(hv, tr, K2, rho_c, rho, &rho8);
+    }
     // f_0 in the coefficient domain -> new witness; Witness::from_f (arith.rs:299-313) behind it on the same stream
     int8_t *d_rho;
     RET(c->tbuf("c_rho", (size_t)K2 * 24 + 64, &d_rho));
@@ -193,7 +188,11 @@ int fold_impl_sb(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_o
     launch_recompose_crt(c->dcrt, npl, N, (u32)N, 1, P.B, 1, 0, nf, N, 0, c->stream());
     launch_recompose_crt(c->dcrt, npl, N, P.wit_len, P.L, P.B, 1, 0, nw, P.wit_len, 0, c->stream());
     if (hipGetLastError() != hipSuccess) return LF_ERR_HIP;
-    fold_instance_host(c, pt, theta, eta, rho_c, rho, S, lcccs_out);
+    {
+        HostTimer ht(c);
+        const size_t ll = lf_lcccs_len(&P);
+        lfs::fold_instance(hv, P, pt, theta, eta, rho_c.data(), rho.data(), [&](u32 i) { return &S[i / K].lcccs[(size_t)(i % K) * ll * 24]; }, lcccs_out);
+    }
     HIPCHK(hipStreamSynchronize(c->stream()));
     *w_out = new lf_witness{c, npl, N, c->device, N * 24 * 4};
     (*w_out)->f_ntt = nf; (*w_out)->f_bytes = nf_bytes; (*w_out)->w_ccs = nw; (*w_out)->w_bytes = nw_bytes;

@@ -99,4 +99,41 @@ class Transcript {
     const u64 *bT_ = nullptr, *bTi_ = nullptr;
 };
 
+// ---- host policy of lf_step_host.h / lf_verify.h on this ring: small inline functions over a host ring it REFERS to (a context's, or the default one) ------
+#pragma GCC visibility push(hidden)   // (not part of the ABI)
+struct GoldV {
+    static constexpr int RE = lf::RE, TAU = lf::TAU;
+    static u64 modulus() { return LF_P; }
+    typedef Fq3 Ext;
+    typedef Transcript Tr;
+    const HostRing &ring;
+    void mul(const u64 *a, const u64 *b, u64 *o) const { ring.mul_ntt(a, b, o); }
+    void mul_ext(const u64 *a, Ext s, u64 *o) const { ring.mul_fq3(a, s, o); }
+    static void add(const u64 *a, const u64 *b, u64 *o) { HostRing::add(a, b, o); }
+    static void sub(const u64 *a, const u64 *b, u64 *o) { HostRing::sub(a, b, o); }
+    static void from_u64(u64 v, u64 *o) { HostRing::from_u64(v, o); }
+    static void from_ext(Ext e, u64 *o) { HostRing::from_fq3(e, o); }
+    static bool is_diag(const u64 *e, Ext *out) { return HostRing::is_diag(e, out); }
+    static Ext ext_from_u64(u64 v) { return fq3_make(v % LF_P, 0, 0); }
+    Ext ext_mul(Ext a, Ext b) const { return ring.mul3(a, b); }
+    static Ext ext_add(Ext a, Ext b) { return fq3_add(a, b); }
+    static Ext ext_sub(Ext a, Ext b) { return fq3_sub(a, b); }
+    Ext ext_inv(Ext a) const { return ring.inv3(a); }
+    static void absorb_ext(Tr &tr, Ext e) { tr.absorb_fq3_as_ring(e); }
+    void crt(const u64 *c, u64 *o) const { ring.crt(c, o); }
+    void icrt(const u64 *x, u64 *o) const { ring.icrt(x, o); }
+    static u64 fmul(u64 a, u64 b) { return fq_mul(a % LF_P, b % LF_P); }
+    static u64 fadd(u64 a, u64 b) { return fq_add(a, b); }
+    static u64 from_i64(int64_t v) { return fq_from_i64(v); }
+    static void balanced_digits(u64 v, u64 base, unsigned digits, int64_t *out, int mode) { lf::balanced_digits(v, base, digits, out, mode); }
+    // accumulation of the v_0 product (lfs::fold_v0): modular per term.  acc_mac takes any 64-bit words t (fq_mul reduces its operands and returns a canonical
+    // word); the accumulators stay canonical
+    typedef u64 Acc;
+    static Acc acc_coef(u64 c) { return c % LF_P; }
+    static void acc_mac(Acc *d, const u64 *t, int n, Acc r) { for (int x = 0; x < n; x++) d[x] = fq_add(d[x], fq_mul(t[x], r)); }
+    static void acc_fold(Acc &mid, Acc &lo, Acc top) { mid = fq_add(mid, top); lo = fq_sub(lo, top); }   // X^d = X^(d - RE/2) - X^(d - RE)
+    static u64 acc_word(Acc a) { return a; }
+};
+#pragma GCC visibility pop
+
 }  // namespace lf

@@ -9,18 +9,6 @@
 // =================================================================================================================================
 // the driver
 
-// sumcheck transcript prologue: absorb R::from(nvars), R::from(degree)  (utils/sumcheck.rs:60-62)
-void sc_prologue(Transcript &tr, u32 nv, u32 deg) {
-    tr.absorb_u64_as_ring(nv);
-    tr.absorb_u64_as_ring(deg);
-}
-Fq3 sc_round_transcript(Transcript &tr, const u64 *evals, u32 npts) {
-    tr.absorb_ring(evals, npts);
-    Fq3 r = tr.get_challenge();
-    tr.absorb_fq3_as_ring(r);
-    return r;
-}
-
 // linearization sumcheck on device tables mz [t][24][m] (left intact) and eq_beta [3][m]
 // `u_dev` (optional): the Mz tables fixed at the whole point, i.e. u_j = Mz_j(r) (t ring elements, canonical) -- the last fix of the
 // tables the rounds work on, so linearization.rs:136's evaluate_mles pass over the full tables is not needed.
@@ -41,7 +29,7 @@ static int run_lin_sumcheck(lf_ctx *c, Transcript &tr, const u64 *mz, const u64 
     RET(c->tbuf("round_partial", round_partial_words(), &partial));
     od = c->round_out();
     if (!od) return LF_ERR_HIP;
-    { HostTimer ht(c); sc_prologue(tr, P.s, deg); }
+    { HostTimer ht(c); lfs::sumcheck_prologue<GoldV>(tr, P.s, deg); }
     const u64 *cur = mz, *cure = eqb;
     size_t n = m;
     int flip = 0;
@@ -182,7 +170,7 @@ static int run_lin_sumcheck(lf_ctx *c, Transcript &tr, const u64 *mz, const u64 
         } else
         memcpy(ev, od, (size_t)(deg + 1) * 24 * 8);
         HostTimer ht(c);
-        point[round - 1] = sc_round_transcript(tr, ev, deg + 1);
+        point[round - 1] = lfs::sumcheck_round<GoldV>(tr, ev, deg + 1);
         if (after_round) (*after_round)(round);
         if (round == 1) TL_MARK("  lin round 1");
         if (round == 2) TL_MARK("  lin round 2");
@@ -244,13 +232,6 @@ int build_z(lf_ctx *c, const int32_t *planes, u32 K, int mode_bits, const u64 *h
 struct LinOut {
     std::vector<Fq3> r;  // point
 };
-
-bool lcccs_point(const lf_params &P, const u64 *lcccs, std::vector<Fq3> &pt) {
-    pt.resize(P.s);
-    for (u32 i = 0; i < P.s; i++)
-        if (!HostRing::is_diag(lcccs + (size_t)i * 24, &pt[i])) return false;
-    return true;
-}
 
 static int linearize_impl(lf_ctx *c, Transcript &tr, const u64 *cccs, const lf_witness *wit, u64 *lcccs_out, u64 *proof, u64 **eq_r_keep) {
     const lf_params &P = c->P;
@@ -398,33 +379,6 @@ static int linearize_impl(lf_ctx *c, Transcript &tr, const u64 *cccs, const lf_w
     return LF_OK;
 }
 
-// decompose_big_vec_into_k_vec_and_compose_back (nifs/decomposition/utils.rs:12-42) on l+1 elements, host
-static void compute_x_s(const lf_ctx *c, const u64 *xh /* (l+1) NTT */, u64 *x_s /* K*(l+1) NTT */) {
-    const lf_params &P = c->P;
-    u32 cnt = P.l + 1;
-    std::vector<u64> co(24);
-    for (u32 i = 0; i < cnt; i++) {
-        c->ring.icrt(xh + (size_t)i * 24, co.data());
-        // per coefficient: L digits base B, each K digits base b
-        std::vector<int64_t> dB(P.L), dk(P.K);
-        std::vector<std::vector<u64>> part(P.K, std::vector<u64>(24, 0));
-        for (int cc = 0; cc < 24; cc++) {
-            balanced_digits(co[cc], P.B, P.L, dB.data(), c->digit_mode);
-            u64 pw = 1;
-            for (u32 l = 0; l < P.L; l++) {
-                balanced_digits(fq_from_i64(dB[l]), P.b, P.K, dk.data(), c->digit_mode);
-                for (u32 k = 0; k < P.K; k++) {
-                    u64 term = fq_mul(pw, fq_from_i64(dk[k]));
-                    part[k][cc] = fq_add(part[k][cc], term);
-                }
-                pw = fq_mul(pw, P.B % LF_P);
-            }
-        }
-        for (u32 k = 0; k < P.K; k++) c->ring.crt(part[k].data(), x_s + ((size_t)k * cnt + i) * 24);
-    }
-}
-
-
 // LFDecompositionProver::prove (nifs/decomposition.rs:33-88)
 // commit_witnesses (decomposition.rs:178-201): NTT of the K-1 upper bit-planes, one batched pass over A, then
 // y_0 = cm - sum_{k>=1} b^k y_k on the host.  Depends only on the witness and on cm -- not on the evaluation point.
@@ -460,17 +414,7 @@ static int decompose_commit_finish(lf_ctx *c, const u64 *cm, u64 *yd, size_t ev,
         memcpy(y_s + (size_t)P.kappa * 24, early, (size_t)(K - 1) * P.kappa * 24 * 8);
     } else RET(commit_download(c, yd, (size_t)(K - 1) * P.kappa * 24, y_s + (size_t)P.kappa * 24));
     c->ev_end(ev);
-    // y_0 = cm - sum_{k>=1} b^k y_k, as the reference's fold (acc + y_i) * b
-    // (b is a base-field constant: in the NTT form the product with it is the word-wise one -- 24 multiplications per element instead of eight F_{p^3} products)
-    std::vector<u64> acc((size_t)P.kappa * 24, 0);
-    const u64 bq = (u64)P.b % LF_P;
-    for (int k = (int)K - 1; k >= 1; k--)
-        for (u32 i = 0; i < P.kappa; i++) {
-            u64 *a = &acc[(size_t)i * 24];
-            const u64 *y = y_s + ((size_t)k * P.kappa + i) * 24;
-            for (int w = 0; w < 24; w++) a[w] = fq_mul(fq_add(a[w], y[w]), bq);
-        }
-    for (u32 i = 0; i < P.kappa; i++) HostRing::sub(cm + (size_t)i * 24, &acc[(size_t)i * 24], y_s + (size_t)i * 24);
+    lfs::commit_y0<GoldV>(P, cm, y_s);
     return LF_OK;
 }
 
@@ -554,7 +498,7 @@ static int decompose_prepare_z(lf_ctx *c, const u64 *xh /* (l+1) elements: x_w |
     u64 *x_s = proof + (size_t)K * P.t * 24 + (size_t)K * 72, *z;
     int rc = c->tbuf("z_" + std::string(side), (size_t)K * 24 * c->n, &z);
     if (rc == LF_OK) {
-        compute_x_s(c, xh, x_s);
+        lfs::decompose_x(GoldV{c->ring}, P, c->digit_mode, xh, x_s);
         // a sharded rank reads z_k in its column slice (the u_s / eta inner products) and in the columns its rows of G refer to (the z-space
         // combination of fold prepare): it builds the range that covers both -- its own n / G columns for a column-local constraint system
         size_t w0 = 0, wcnt = (size_t)-1;
@@ -650,27 +594,9 @@ static int decompose_evals(lf_ctx *c, const u64 *lcccs, const std::vector<Fq3> &
 
 // transcript part of the decomposition (decomposition.rs:65-83): absorb x_k, y_k, u_k, v_k and build the K LCCCS.
 // No challenge is drawn here, so for the left instance it runs on a host thread while the GPU decomposes the right one.
-static double absorb_decomposition(const lf_params &P, Transcript &tr, const u64 *lcccs, const u64 *proof, SideState &S, u32 k0 = 0, u32 k1 = ~0u) {
+static double absorb_decomposition(const lf_params &P, Transcript &tr, const u64 *lcccs, const u64 *proof, SideState &S) {
     auto t0 = std::chrono::steady_clock::now();
-    u32 K = P.K;
-    const u64 *u_s = proof, *v_s = u_s + (size_t)K * P.t * 24, *x_s = v_s + (size_t)K * 72, *y_s = x_s + (size_t)K * (P.l + 1) * 24;
-    size_t ll = lf_lcccs_len(&P);
-    if (k1 > K) k1 = K;
-    if (k0 == 0) S.lcccs.assign((size_t)K * ll * 24, 0);
-    for (u32 k = k0; k < k1; k++) {
-        const u64 *xk = x_s + (size_t)k * (P.l + 1) * 24, *yk = y_s + (size_t)k * P.kappa * 24;
-        const u64 *uk = u_s + (size_t)k * P.t * 24, *vk = v_s + (size_t)k * 72;
-        tr.absorb_ring(xk, P.l + 1);
-        tr.absorb_ring(yk, P.kappa);
-        tr.absorb_ring(uk, P.t);
-        tr.absorb_ring(vk, 3);
-        u64 *o = &S.lcccs[(size_t)k * ll * 24];
-        memcpy(o, lcccs, (size_t)P.s * 24 * 8); o += (size_t)P.s * 24;
-        memcpy(o, vk, 72 * 8); o += 72;
-        memcpy(o, yk, (size_t)P.kappa * 24 * 8); o += (size_t)P.kappa * 24;
-        memcpy(o, uk, (size_t)P.t * 24 * 8); o += (size_t)P.t * 24;
-        memcpy(o, xk, (size_t)(P.l + 1) * 24 * 8);
-    }
+    lfs::absorb_decomposition<GoldV>(tr, P, lcccs, proof, S.lcccs);
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
@@ -720,7 +646,7 @@ int lf_fold_step(lf_ctx *c, lf_transcript *t, const uint64_t *acc, const lf_witn
     if (c->kappa != P.kappa || c->nA_total != c->N || w_acc->N != c->N || w_i->N != c->N) return LF_ERR_INVALID;
     HIPCHK(hipSetDevice(c->device));
     std::vector<Fq3> rL;
-    if (!lcccs_point(P, acc, rL)) return LF_ERR_UNSUPPORTED;  // evaluation points are always diagonal challenges
+    if (!lfs::lcccs_point<GoldV>(P, acc, rL)) return LF_ERR_UNSUPPORTED;  // evaluation points are always diagonal challenges
     c->tn = Tunables::read((size_t)1 << 14);
     Timeline tl;
     t_tl = &tl;
@@ -760,14 +686,11 @@ int lf_fold_step(lf_ctx *c, lf_transcript *t, const uint64_t *acc, const lf_witn
         if (rc == LF_OK) rc = decompose_commit_enqueue(c, w_i, &ydR, &evR, "dec_y2", S[1].D);
         if (rc == LF_OK) {
             HostTimer ht(c);
-            tr.absorb_label("acc");
-            tr.absorb_ring(acc, ll);
-            tr.absorb_label("cm_i");
-            tr.absorb_ring(cm_i, lf_cccs_len(&P));
+            lfs::absorb_public_input<GoldV>(tr, P, acc, cm_i);
         }
         if (rc == LF_OK) rc = linearize_impl(c, tr, cm_i, w_i, lin.data(), lin_proof, &eq_r_R);
         if (rc == LF_OK) {
-            lcccs_point(P, lin.data(), rR);
+            lfs::lcccs_point<GoldV>(P, lin.data(), rR);
             rc = decompose_evals(c, lin.data(), rR, w_i, "R", eq_r_R, S[1], decr);
         }
         if (rc == LF_OK) c->host_tr_ms += absorb_decomposition(P, tr, acc, decl, S[0]);
@@ -789,14 +712,11 @@ int lf_fold_step(lf_ctx *c, lf_transcript *t, const uint64_t *acc, const lf_witn
         });
         {
             HostTimer ht(c);
-            tr.absorb_label("acc");
-            tr.absorb_ring(acc, ll);
-            tr.absorb_label("cm_i");
-            tr.absorb_ring(cm_i, lf_cccs_len(&P));
+            lfs::absorb_public_input<GoldV>(tr, P, acc, cm_i);
         }
         if (rc == LF_OK) rc = linearize_impl(c, tr, cm_i, w_i, lin.data(), lin_proof, &eq_r_R);   // ... while the linearization runs on stream 0
         if (rc == LF_OK) {
-            lcccs_point(P, lin.data(), rR);
+            lfs::lcccs_point<GoldV>(P, lin.data(), rR);
             rc = decompose_evals(c, lin.data(), rR, w_i, "R", eq_r_R, S[1], decr);
         }
         if (rc == LF_OK) c->host_tr_ms += absorb_decomposition(P, tr, acc, decl, S[0]);
@@ -871,10 +791,7 @@ int lf_fold_step(lf_ctx *c, lf_transcript *t, const uint64_t *acc, const lf_witn
     });
     {   // absorb_public_input (nifs.rs:175-197) -- after lane 1 has been started: the left decomposition does not depend on it
         HostTimer ht(c);
-        tr.absorb_label("acc");
-        tr.absorb_ring(acc, ll);
-        tr.absorb_label("cm_i");
-        tr.absorb_ring(cm_i, lf_cccs_len(&P));
+        lfs::absorb_public_input<GoldV>(tr, P, acc, cm_i);
     }
     TL_MARK("public input absorbed");
     c->vs_keep = true;
@@ -885,7 +802,7 @@ int lf_fold_step(lf_ctx *c, lf_transcript *t, const uint64_t *acc, const lf_witn
     // From here the host runs a serial Poseidon chain (left absorb, right absorb, folding challenges: ~2.4 ms at 2^20 rows) next to which the GPU only has the
     // right evaluations (0.5 ms)
     if (rc == LF_OK) {
-        lcccs_point(P, lin.data(), rR);
+        lfs::lcccs_point<GoldV>(P, lin.data(), rR);
         while (S[1].z_state.load(std::memory_order_acquire) == 0) std::this_thread::yield();   // published by lane 1 within its first millisecond (or -1)
         rc = decompose_evals(c, lin.data(), rR, w_i, "R", eq_r_R, S[1], decr);
     }
@@ -933,7 +850,7 @@ int lf_decomposition_prove(lf_ctx *c, lf_transcript *t, const uint64_t *lcccs, c
     if (c->kappa != P.kappa || c->nA_total != c->N || wit->N != c->N) return LF_ERR_INVALID;
     HIPCHK(hipSetDevice(c->device));
     std::vector<Fq3> r;
-    if (!lcccs_point(P, lcccs, r)) return LF_ERR_UNSUPPORTED;
+    if (!lfs::lcccs_point<GoldV>(P, lcccs, r)) return LF_ERR_UNSUPPORTED;
     c->tn = Tunables::read((size_t)1 << 14);
     c->ev_reset();
     c->host_tr_ms = 0;
@@ -982,7 +899,7 @@ int lf_folding_prove(lf_ctx *c, lf_transcript *t, const uint64_t *lcccs_s, const
     for (int sd = 0; sd < 2; sd++) {
         const u64 *base = lcccs_s + (size_t)sd * K * ll * 24;
         std::vector<Fq3> r;
-        if (!lcccs_point(P, base, r)) return LF_ERR_UNSUPPORTED;
+        if (!lfs::lcccs_point<GoldV>(P, base, r)) return LF_ERR_UNSUPPORTED;
         for (u32 k = 1; k < K; k++)   // the K parts of one side share r (folding/utils.rs:232-250)
             if (memcmp(base, base + (size_t)k * ll * 24, (size_t)P.s * 24 * 8) != 0) return LF_ERR_INVALID;
         const lf_witness *w = sd ? w_right : w_left;

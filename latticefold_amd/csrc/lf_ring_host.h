@@ -10,11 +10,15 @@
 //
 // Stays per backend, one line each:
 //   build_eq_dev / build_eq_async   two-level kernel on Goldilocks, pre-multiplied constants staged in the pinned arena on BabyBear
-//   build_z, lcccs_point            different table layouts (atl() leading dimension) and extension types
+//   build_z                         different table layouts (atl() leading dimension)
 //   the table build of install_tables, the envelope check of ccs_load   per-ring tables and per-ring limits (wide CCS, small bases on Goldilocks only)
 //   down_small                      lane_sync() on a blocking event (Goldilocks) against a plain stream synchronise
 //   selftest_field, set_sharding / dist_init   different kernels; two communicators and a handshake against one
-//   the provers (lf_prove.cpp, lf_fold.cpp, lf_fold_sb.cpp, bb_prove.cpp), lf_dist.cpp, the verifier, the wire format and lfp_*
+//   the SCHEDULES of the provers (lf_prove.cpp, lf_fold.cpp, lf_fold_sb.cpp: lane worker, mailbox tails, sharded rounds, small bases, wide CCS; bb_prove.cpp:
+//   one thread, pinned arenas) -- what they enqueue, wait for and time.  The protocol's host arithmetic underneath them (sumcheck transcript, public input,
+//   x_s, y_0, the absorbs, the challenge draws, get_rhos, the folded instance, the C_pi table) is lf_step_host.h, shared with the verifier (lf_verify.h), over
+//   the host policies GoldV (lf_host.h) / BbV (bb_host.h) -- Ring<Ctx>::Host below
+//   lf_dist.cpp, the checks of the verifier, the wire format and lfp_*
 //
 // Order of the argument checks, the same on both rings: (1) null / range checks of the ABI function -> LF_ERR_INVALID, (2) here, before the context
 // lock: pow2(base) -> LF_ERR_UNSUPPORTED (decompose), len against 2^nv -> LF_ERR_INVALID (mle_eval_batch), (3) under the lock: have_ccs / resident
@@ -43,6 +47,7 @@ template <> struct Ring<lf_ctx> {
     typedef u64 Part;         // block partials of the reductions
     typedef Fq3 Ext;
     typedef Fq3Const ExtC;
+    typedef GoldV Host;       // host arithmetic of lf_step_host.h
     static constexpr int RE = 24, TAU = 3;
     static constexpr bool general_csr = true;    // ccs_general / launch_spmv_rows exist on this ring only
     static constexpr bool montgomery = false;
@@ -97,6 +102,7 @@ template <> struct Ring<BbCtxImpl> {
     typedef i64 Part;
     typedef H9 Ext;
     typedef E9PreC ExtC;
+    typedef BbV Host;
     static constexpr int RE = lfbb::RE, TAU = lfbb::TAU;
     static constexpr bool general_csr = false;
     static constexpr bool montgomery = true;

@@ -251,6 +251,31 @@ def test_fold_step_parity(ctx, name, seed):
         assert (proof2_g == proof2_o).all() and (lc2_g == lc2_o).all() and (w2.f == f2_o).all()
 
 
+@pytest.mark.parametrize("name", ["B6", "BDP"])
+def test_sub_provers_match_oracle_fold_step_sections(ctx, name):
+    """BbCtx::decomposition_prove / BbCtx::folding_prove (lf_decomposition_prove, lf_folding_prove on this ring): nifs.rs:59-103 replayed with the three
+    sub-provers under one transcript -- public input, linearization, the two decompositions, the folding -- gives, word for word, the decomposition-left,
+    decomposition-right and folding sections of the ORACLE's fold_step proof and its folded LCCCS"""
+    wl, inst, A, f_coeff, wit, cccs, acc_g, _, acc_o, _ = run_both(ctx, name)
+    lc_o, f0_o, proof_o = inst.fold_step(lfo.Transcript(), A, acc_o, f_coeff, cccs, f_coeff)
+    lin = wl.s * (wl.d + 2) + TAU + wl.t
+    dec = wl.K * (wl.t + TAU + wl.l + 1 + wl.kappa)
+    t1 = tr_new()
+    for label, x in (("acc", acc_o), ("cm_i", cccs)):       # absorb_public_input (nifs.rs:175-197)
+        t1.absorb_slice(diag(int.from_bytes(label.encode(), "big") % P, RING)[None, :])
+        t1.absorb_slice(x)
+    lin_lc, lin_pr = api.LFLinearizationProver.prove(ctx, cccs, wit, t1)
+    lcs_l, dec_l = api.LFDecompositionProver.prove(ctx, acc_o, wit, t1)
+    lcs_r, dec_r = api.LFDecompositionProver.prove(ctx, lin_lc, wit, t1)
+    lc, w0, fold_pr = api.LFFoldingProver.prove(ctx, np.concatenate([lcs_l, lcs_r]), wit, wit, t1)
+    assert (lin_pr == proof_o[:lin]).all()
+    assert (dec_l == proof_o[lin:lin + dec]).all()
+    assert (dec_r == proof_o[lin + dec:lin + 2 * dec]).all()
+    assert (fold_pr == proof_o[lin + 2 * dec:]).all()
+    assert (lc == lc_o).all()
+    assert (w0.f == f0_o).all()
+
+
 @pytest.mark.parametrize("name", ["B6"])
 def test_fold_step_builds_f_and_w_ccs_of_the_folded_witness(ctx, name, monkeypatch):
     """Witness::from_f (arith.rs:299-313) builds f_coeff, f (NTT form) and w_ccs inside prove: a fold step materialises all three behind compute_f_0
