@@ -2,6 +2,8 @@
 // points (CRT, decomposition, Ajtai commitments, eq tables, MLE evaluations, SpMV), constraint-system load, device-resident witnesses, transcripts, timing
 // read-outs and the host verifier.  The provers are in lf_prove.cpp (linearization, decomposition, entry points) and lf_fold.cpp (the folding prover).
 #include "lf_ring_host.h"
+#include <thread>
+#include <vector>
 
 const char *lf_strerror(int code) {
     switch (code) {
@@ -331,15 +333,126 @@ int down_small(lf_ctx *c, const u64 *dsrc, size_t words, u64 *host) {
 }
 Fq3Const f3c(Fq3 a) { Fq3Const r; r.c[0] = a.c[0]; r.c[1] = a.c[1]; r.c[2] = a.c[2]; return r; }
 
+// ---- arithmetic self-test -----------------------------------------------------------------------------------------
+// The device computes (k_selftest_field), the host judges: every stored word is compared with `unsigned __int128 %` arithmetic written out here -- nothing of
+// lf_field.cuh, whose host and device paths share their formulas.  The first operand pairs put every pair of the reduction-corner grid into every coordinate
+// position (the borrow / carry / hl == 0 branches of fq_reduce128_loose, both wraps of fq_from_s128 and results in [p, 2^64) occur only there: uniform words
+// never reach them); the rest are pseudo-random from `seed` with a quarter of the words drawn from the grid.
+namespace selftest {
+typedef unsigned __int128 u128;
+constexpr u64 PM = 0xFFFFFFFF00000001ULL;
+constexpr int NG = 22;
+const u64 GRID[NG] = {0, 1, 2, PM - 1, PM - 2, 0xFFFFFFFFULL, 1ULL << 32, (1ULL << 32) + 1, (1ULL << 32) + 2, PM - 0xFFFFFFFFULL, 0xFFFFFFFEULL,
+                      (PM - 1) / 2, (PM + 1) / 2, 1ULL << 63, (1ULL << 63) + 1, 1ULL << 40, 1ULL << 24, PM - (1ULL << 40), 0xFFFFFFFE00000001ULL,
+                      3ULL << 62, 0x1FFFFFFFFULL, PM - (1ULL << 24)};
+inline u64 md(u128 v) { return (u64)(v % PM); }
+inline u64 mm(u64 a, u64 b) { return md((u128)a * b); }
+struct E3 { u64 c[3]; };
+inline void columns(const E3 &a, const E3 &b, u64 col[5]) {   // the five schoolbook column sums, each reduced
+    col[0] = mm(a.c[0], b.c[0]);
+    col[1] = md((u128)mm(a.c[0], b.c[1]) + mm(a.c[1], b.c[0]));
+    col[2] = md((u128)mm(a.c[0], b.c[2]) + mm(a.c[1], b.c[1]) + mm(a.c[2], b.c[0]));
+    col[3] = md((u128)mm(a.c[1], b.c[2]) + mm(a.c[2], b.c[1]));
+    col[4] = mm(a.c[2], b.c[2]);
+}
+inline E3 finish(const u64 col[5], u64 nu) {                  // Y^3 = nu
+    E3 r;
+    r.c[0] = md((u128)col[0] + mm(nu, col[3]));
+    r.c[1] = md((u128)col[1] + mm(nu, col[4]));
+    r.c[2] = col[2];
+    return r;
+}
+inline unsigned differ(const u64 *got, const E3 &want) { return (got[0] != want.c[0]) + (got[1] != want.c[1]) + (got[2] != want.c[2]); }
+void operands(u64 seed, u32 n, std::vector<u64> &in) {
+    in.resize((size_t)n * 6);
+    u32 i = 0;
+    for (int sh = 0; sh < 3 && i < n; sh++)
+        for (int x = 0; x < NG && i < n; x++)
+            for (int y = 0; y < NG && i < n; y++, i++) {
+                u64 *w = &in[(size_t)i * 6];
+                w[0] = GRID[x]; w[1] = GRID[(x + sh) % NG]; w[2] = GRID[(x + 2 * sh) % NG];
+                w[3] = GRID[y]; w[4] = GRID[(y + 5 * sh) % NG]; w[5] = GRID[(y + 7 * sh) % NG];
+            }
+    u64 s = seed * 0x9E3779B97F4A7C15ULL + 1;
+    for (size_t k = (size_t)i * 6; k < in.size(); k++) {
+        s ^= s << 13; s ^= s >> 7; s ^= s << 17;
+        in[k] = ((s >> 7) & 3) == 0 ? GRID[(s >> 11) % NG] : s % PM;
+    }
+}
+// mismatching words among the outputs of operand pairs [i0, i1)
+u64 check(const u64 *in, const u64 *out, const u64 *outc, u32 nc, u64 nu_gen, u32 i0, u32 i1) {
+    const u64 nu = 1ULL << 40;
+    u64 bad = 0;
+    for (u32 i = i0; i < i1; i++) {
+        const u64 *w = in + (size_t)i * 6, *o = out + (size_t)i * SELFTEST_OUT;
+        E3 a = {{w[0], w[1], w[2]}}, b = {{w[3], w[4], w[5]}};
+        bad += o[0] != md((u128)a.c[0] + b.c[0]);
+        bad += o[1] != md((u128)a.c[0] + PM - b.c[0]);
+        bad += o[2] != mm(a.c[0], b.c[0]);
+        bad += o[3] != mm(a.c[0], nu);
+        u64 col[5];
+        columns(a, b, col);
+        const E3 p40 = finish(col, nu);
+        bad += differ(o + 4, p40) + differ(o + 7, p40) + differ(o + 10, finish(col, nu_gen));
+        if (i < nc) {
+            E3 x = a, y = b, sum = {{0, 0, 0}};
+            for (int r = 0; r < 37; r++) {
+                columns(x, y, col);
+                const E3 pr = finish(col, nu);
+                E3 t;
+                for (int q = 0; q < 3; q++) { sum.c[q] = md((u128)sum.c[q] + pr.c[q]); t.c[q] = md((u128)x.c[q] + y.c[q]); }
+                x = y; y = t;
+            }
+            const u64 *oc = outc + (size_t)i * SELFTEST_OUTC;
+            bad += differ(oc, sum) + differ(oc + 3, sum) + differ(oc + 6, sum) + differ(oc + 9, sum);
+        }
+    }
+    return bad;
+}
+}  // namespace selftest
+
 int lf_selftest_field(lf_ctx *c, uint64_t seed, uint32_t n, uint64_t *mismatches) {
     if (!c || !mismatches) return LF_ERR_INVALID;
     if (c->bb) return c->bb->selftest_field(seed, n, mismatches);
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(hipSetDevice(c->device));
-    u64 *d;
+    const u32 nc = n < (1u << 14) ? n : (1u << 14);     // the 37-term sums are checked on the grid pairs and the first pseudo-random ones (37 products each on the host)
+    const u64 nu_gen = c->dcrt.nu2p40 ? 0xFFFFFFFE00000002ULL : c->dcrt.nu;   // the context's own non-residue where it is not 2^40
+    std::vector<u64> in, out((size_t)n * SELFTEST_OUT), outc((size_t)nc * SELFTEST_OUTC);
+    selftest::operands(seed, n, in);
+    u64 *d, *di, *dout, *doutc;
     RET(c->tbuf("small_dev", 4096, &d));
-    launch_selftest_field(seed, n, d, c->stream());
-    return down_small(c, d, 1, mismatches);
+    RET(c->tbuf("io_a", in.size() + 8, &di));
+    RET(c->tbuf("io_b", out.size() + 8, &dout));
+    RET(c->tbuf("io_c", outc.size() + 8, &doutc));
+    u64 dev_bad = 0;
+    if (n) {
+        HIPCHK(hipMemcpyAsync(di, in.data(), in.size() * 8, hipMemcpyHostToDevice, c->stream()));
+        launch_selftest_field(di, n, nc, nu_gen, dout, doutc, d, c->stream());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out.data(), dout, out.size() * 8, hipMemcpyDeviceToHost, c->stream()));
+        HIPCHK(hipMemcpyAsync(outc.data(), doutc, outc.size() * 8, hipMemcpyDeviceToHost, c->stream()));
+        HIPCHK(hipMemcpyAsync(&dev_bad, d, 8, hipMemcpyDeviceToHost, c->stream()));
+        HIPCHK(hipStreamSynchronize(c->stream()));
+    }
+    // the pairs with 37-term sums cost most: they go round-robin in blocks of 256 pairs over the checking threads
+    const u32 nthr = n >= (1u << 14) ? 8 : 1;
+    const u64 blocks = ((u64)n + 255) / 256;      // (64-bit: n within 255 of 2^32 must not wrap)
+    std::vector<u64> bad(nthr, 0);
+    std::vector<std::thread> th;
+    auto work = [&](u32 t) {
+        for (u64 bl = t; bl < blocks; bl += nthr) {
+            const u64 i0 = bl * 256, i1 = i0 + 256 < n ? i0 + 256 : n;
+            bad[t] += selftest::check(in.data(), out.data(), outc.data(), nc, nu_gen, (u32)i0, (u32)i1);
+        }
+    };
+    for (u32 t = 1; t < nthr; t++) th.emplace_back(work, t);
+    work(0);
+    for (auto &t : th) t.join();
+    u64 total = dev_bad;
+    for (u64 v : bad) total += v;
+    *mismatches = total;
+    return LF_OK;
 }
 
 // ---- a1/a2 --------------------------------------------------------------------------------------------------------
@@ -606,7 +719,7 @@ int lf_ccs_load(lf_ctx *c, const lf_params *p, const uint32_t *const *rowptr, co
     }
     if (!c || !p || !rowptr || !col || !val || !S_off || !S_idx || !cc) return LF_ERR_INVALID;
     if (c->bb) { RET(lfbb::ccs_envelope(p)); return ring_ops<BbRing>::ccs_load(c->bb->p, p, rowptr, col, val, S_off, S_idx, cc); }
-    if (p->s < 3 || p->s > 30 || p->t == 0 || p->t > 8 || p->q == 0 || p->q > 8 || p->K == 0 || p->K > 32 || p->L == 0 || p->L > 8 ||
+    if (p->s < 3 || p->s > LF_S_MAX || p->t == 0 || p->t > 8 || p->q == 0 || p->q > 8 || p->K == 0 || p->K > 32 || p->L == 0 || p->L > 8 ||
         p->d > 7 || p->wit_len == 0)
         return LF_ERR_UNSUPPORTED;
     // b = 2: the bit-plane kernels of the reference Goldilocks rows; b = 4, 8, 16: the small-base path (lf_sb.h), one unsharded GPU

@@ -199,7 +199,7 @@ LF_HD LH accp_lh(const AccP &s) {
 // signed value  lo64 + 2^64 * hi  (|hi| small) -> canonical residue
 LF_HD u64 fq_from_s128(u64 lo, int64_t hi) {
     // 2^64 = eps: add hi*eps to lo, fix the single possible wrap in either direction
-    int64_t t = (int64_t)((u64)hi << 32) - hi;  // hi * (2^32 - 1), |hi| < 2^30 -> no overflow
+    int64_t t = (int64_t)((u64)hi << 32) - hi;  // hi * (2^32 - 1): no overflow for |hi| < 2^31; fq_from_lin passes |hi| < 2^12 (one column: |L + H| < 2^35, times 2^40), fq_from_lin_wide |hi| <= 1 after its own fold
     u64 s = lo + (u64)t;
     if (t >= 0) {
         if (s < lo) s += LF_EPS;       // wrapped past 2^64: -p
@@ -211,14 +211,15 @@ LF_HD u64 fq_from_s128(u64 lo, int64_t hi) {
 // value = base + 2^32 * h32 + 2^40 * h40 as a signed 128-bit integer, reduced (all inputs small signed, < 2^40)
 LF_HD u64 fq_from_lin(int64_t base, int64_t h32, int64_t h40) {
     typedef __int128 i128;
-    i128 v = (i128)base + ((i128)h32 << 32) + ((i128)h40 << 40);
+    // (signed terms are scaled by multiplication: shifting a negative value left is undefined before C++20; the compiler emits the same shifts)
+    i128 v = (i128)base + (i128)h32 * ((i128)1 << 32) + (i128)h40 * ((i128)1 << 40);
     return fq_from_s128((u64)v, (int64_t)(v >> 64));
 }
 LF_HD Fq3 fq3_from_columns_2p40(const AccP *s) {
     LH c0 = accp_lh(s[0]), c1 = accp_lh(s[1]), c2 = accp_lh(s[2]), c3 = accp_lh(s[3]), c4 = accp_lh(s[4]);
     Fq3 r;
-    r.c[0] = fq_from_lin(c0.l - (c3.h << 8), c0.h, c3.l + c3.h);
-    r.c[1] = fq_from_lin(c1.l - (c4.h << 8), c1.h, c4.l + c4.h);
+    r.c[0] = fq_from_lin(c0.l - c3.h * 256, c0.h, c3.l + c3.h);
+    r.c[1] = fq_from_lin(c1.l - c4.h * 256, c1.h, c4.l + c4.h);
     r.c[2] = fq_from_lin(c2.l, c2.h, 0);
     return r;
 }
@@ -233,7 +234,15 @@ LF_HD Fq3 fq3_mul_2p40(Fq3 a, Fq3 b) {
 }
 
 // Lazy sum of F_{p^3} products for NU = 2^40: each product's five columns are folded to their (L,H) linear forms and
-// added as plain 64-bit integers (|L|,|H| < 2^36 per product -> 2^27 products fit); one reduction at the very end.
+// added as plain 64-bit integers; one reduction at the very end.  Bound per product, from accp_lh: H is the sum of four 32-bit pieces of s00 / s01 / s11 plus c00
+// minus c11, L one such piece minus three, so for a column of up to three products |H| < 2^34 and |L| < 2^33.6.  lf_field_selftest.cpp prints the largest on the
+// reduction-corner grid: |L| = 8573157372 (2^33.0), |H| = 17146314750 (2^34.0) at (x, x, x) (y, y, y), x = 0x1ffffffff, y = p - 2^24.  The binding limit is not
+// the 64-bit sums but lh5_finish, which scales H by 2^8 in 64 bits and so needs |sum H| < 2^55: 2^55 / 2^34 = 2^21 worst-case products fit (printed: 2101256,
+// 32.1 x LF_LAZY_N_MAX).
+constexpr unsigned LF_S_MAX = 30;          // log2 of the longest table: lf_ccs_load refuses s > LF_S_MAX
+constexpr unsigned LF_DOT_BLOCKS = 64;     // launch_dot_batch strides at most this many blocks of 256 threads over a table
+// the most products one thread of any launch adds into one LH5 / Acc5 accumulator (k_dot_batch; the derivation is in lf_field_selftest.cpp): 65 536
+constexpr unsigned long long LF_LAZY_N_MAX = (1ULL << LF_S_MAX) / (LF_DOT_BLOCKS * 256);
 struct LH5 {
     LH c[5];
 };
@@ -300,20 +309,20 @@ LF_HD void lh5_macn(LH5 &acc, const Fq3 (&a)[N], const Fq3 (&b)[N]) {
         acc.c[i].h += t.h;
     }
 }
-// signed wide value base + 2^32 h32 + 2^40 h40 with |terms| up to ~2^62: split before shifting
+// signed wide value base + 2^32 h32 + 2^40 h40 with |terms| up to ~2^62 (reached in practice: 2^50 at 65 536 products): widen to 128 bits before scaling
 LF_HD u64 fq_from_lin_wide(int64_t base, int64_t h32, int64_t h40) {
     typedef __int128 i128;
-    i128 v = (i128)base + ((i128)h32 << 32) + ((i128)h40 << 40);   // |v| < 2^103
+    i128 v = (i128)base + (i128)h32 * ((i128)1 << 32) + (i128)h40 * ((i128)1 << 40);   // |v| < 2^103
     // fold the high part: v = lo + 2^64 hi, hi up to 2^39 -> hi*eps needs 71 bits: fold twice
     u64 lo = (u64)v;
     i128 hi = v >> 64;
-    i128 w = (i128)lo + (hi << 32) - hi;                            // |w| < 2^72
+    i128 w = (i128)lo + hi * ((i128)1 << 32) - hi;                  // |w| < 2^72
     return fq_from_s128((u64)w, (int64_t)(w >> 64));
 }
 LF_HD Fq3 lh5_finish(const LH5 &a) {
     Fq3 r;
-    r.c[0] = fq_from_lin_wide(a.c[0].l - (a.c[3].h << 8), a.c[0].h, a.c[3].l + a.c[3].h);
-    r.c[1] = fq_from_lin_wide(a.c[1].l - (a.c[4].h << 8), a.c[1].h, a.c[4].l + a.c[4].h);
+    r.c[0] = fq_from_lin_wide(a.c[0].l - a.c[3].h * 256, a.c[0].h, a.c[3].l + a.c[3].h);
+    r.c[1] = fq_from_lin_wide(a.c[1].l - a.c[4].h * 256, a.c[1].h, a.c[4].l + a.c[4].h);
     r.c[2] = fq_from_lin_wide(a.c[2].l, a.c[2].h, 0);
     return r;
 }

@@ -38,7 +38,8 @@ void launch_modsum(const u64 *parts, u32 nparts, size_t words, u64 *out, hipStre
 void launch_gather_relayout(const u64 *all, u32 nranks, size_t planes, size_t lcl, u64 *full, hipStream_t s);
 void launch_gather_relayout_part(const u64 *all, u32 nranks, size_t planes_tot, size_t p0, size_t planes, size_t lcl, u64 *full, hipStream_t s);
 
-void launch_selftest_field(u64 seed, u32 n, u64 *mism_dev, hipStream_t s);  // arithmetic self-test, see lf_kernels.hip
+constexpr u32 SELFTEST_OUT = 13, SELFTEST_OUTC = 12;   // words per operand pair of the self-test's two output arrays
+void launch_selftest_field(const u64 *in, u32 n, u32 nc, u64 nu_gen, u64 *out, u64 *outc, u64 *mism_dev, hipStream_t s);  // arithmetic self-test: computes and stores, the host compares (lf_kernels.hip)
 
 // ---- CRT / ICRT (a1, a2) ---------------------------------------------------------------------------------------
 void launch_crt_fwd(const DevCrt &t, const u64 *coef, u64 *ntt, size_t n, hipStream_t s);

@@ -481,41 +481,55 @@ __device__ __forceinline__ Fq3 acc5_finish(const Acc5 &a, u64 nu) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// arithmetic self-test: the fast NU = 2^40 product, the lazy (L,H) accumulator and the partial-product accumulator
-// against the generic schoolbook path on pseudo-random and edge operands; counts mismatching words.
-__global__ void __launch_bounds__(256) k_selftest_field(u64 seed, u32 n, unsigned long long *mism) {
+// arithmetic self-test: the kernel only COMPUTES, on operands the host uploads (in[i] = six words: a, b in F_{p^3}), and stores every result; the host compares the
+// stored words with 128-bit integer arithmetic of its own (lf_selftest_field), so a fault in a primitive that both sides of a device-only comparison would
+// share -- mul64wide's device branch, fq_reduce128_loose, fq_canon, fq_add -- cannot cancel out.
+//   out[i][0..3]    fq_add, fq_sub, fq_mul of the first words, fq_mul_2p40 of a's
+//   out[i][4..12]   fq3_mul_2p40, fq3_mul<false> with nu = 2^40, fq3_mul<false> with the generic nu_gen
+//   outc[i][0..11]  (i < nc) the sum of 37 products x_r y_r (x_0 = a, y_0 = b, x_{r+1} = y_r, y_{r+1} = x_r + y_r) through lh5_mac, lh5_mac2 and acc5_mac, the
+//                   partial-product sums finished both ways
+// *mism additionally counts, for every i, the lazy sums that differ from the sum of reduced generic products (a device-side comparison, kept as an extra).
+__global__ void __launch_bounds__(256) k_selftest_field(const u64 *in, u32 n, u32 nc, u64 nu_gen, u64 *out, u64 *outc, unsigned long long *mism) {
     u32 i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const u64 edge[8] = {0, 1, LF_P - 1, LF_P - 2, 0xFFFFFFFFULL, 0xFFFFFFFF00000000ULL, 1ULL << 32, (LF_P - 1) / 2};
-    u64 w[6];
-    for (int k = 0; k < 6; k++) {
-        u64 v = splitmix_fq(seed, (u64)i * 6 + k);
-        if (((v >> 7) & 3) == 0) v = edge[(v >> 3) & 7];  // a quarter of the operands are edge values
-        w[k] = v;
-    }
+    const u64 *w = in + (size_t)i * 6;
     Fq3 a = fq3_make(w[0], w[1], w[2]), b = fq3_make(w[3], w[4], w[5]);
     const u64 nu = 1ULL << 40;
-    Fq3 ref = fq3_mul<false>(a, b, nu), fast = fq3_mul_2p40(a, b);
-    unsigned bad = !fq3_eq(ref, fast);
-    // lazy sums of 37 products (with repeated operands) vs reduced sums
-    LH5 lz; lh5_zero(lz);
+    u64 *o = out + (size_t)i * SELFTEST_OUT;
+    o[0] = fq_add(a.c[0], b.c[0]); o[1] = fq_sub(a.c[0], b.c[0]); o[2] = fq_mul(a.c[0], b.c[0]); o[3] = fq_mul_2p40(a.c[0]);
+    Fq3 fast = fq3_mul_2p40(a, b), ref = fq3_mul<false>(a, b, nu), gen = fq3_mul<false>(a, b, nu_gen);
+#pragma unroll
+    for (int q = 0; q < 3; q++) { o[4 + q] = fast.c[q]; o[7 + q] = ref.c[q]; o[10 + q] = gen.c[q]; }
+    // lazy sums of 37 products (with repeated operands)
+    LH5 lz, lz2; lh5_zero(lz); lh5_zero(lz2);
     Acc5 ap; acc5_zero(ap);
     Fq3 sum = fq3_zero();
-    Fq3 x = a, y = b;
+    Fq3 x = a, y = b, xp = a, yp = b;
     for (int r = 0; r < 37; r++) {
         lh5_mac(lz, x, y);
         acc5_mac(ap, x.c, y.c);
         sum = fq3_add(sum, fq3_mul<false>(x, y, nu));
+        if (r & 1) lh5_mac2(lz2, xp, yp, x, y);     // products (0, 1), (2, 3), .. pairwise
+        else { xp = x; yp = y; }
         Fq3 t = fq3_add(x, y); x = y; y = t;
     }
-    bad += !fq3_eq(sum, lh5_finish(lz));
-    bad += !fq3_eq(sum, acc5_finish<true>(ap, nu));
-    bad += !fq3_eq(sum, acc5_finish<false>(ap, nu));
+    lh5_mac(lz2, xp, yp);                           // ... and the 37th alone
+    Fq3 l1 = lh5_finish(lz), a1 = acc5_finish<true>(ap, nu), a2 = acc5_finish<false>(ap, nu);
+    unsigned bad = !fq3_eq(sum, l1);
+    bad += !fq3_eq(sum, a1);
+    bad += !fq3_eq(sum, a2);
+    if (i < nc) {
+        u64 *oc = outc + (size_t)i * SELFTEST_OUTC;
+        Fq3 l2 = lh5_finish(lz2);
+#pragma unroll
+        for (int q = 0; q < 3; q++) { oc[q] = l1.c[q]; oc[3 + q] = l2.c[q]; oc[6 + q] = a1.c[q]; oc[9 + q] = a2.c[q]; }
+    }
     if (bad) atomicAdd(mism, (unsigned long long)bad);
 }
-void launch_selftest_field(u64 seed, u32 n, u64 *mism_dev, hipStream_t s) {
+void launch_selftest_field(const u64 *in, u32 n, u32 nc, u64 nu_gen, u64 *out, u64 *outc, u64 *mism_dev, hipStream_t s) {
     (void)hipMemsetAsync(mism_dev, 0, 8, s);
-    hipLaunchKernelGGL(k_selftest_field, dim3(cdiv(n, 256)), dim3(256), 0, s, seed, n, (unsigned long long *)mism_dev);
+    if (!n) return;
+    hipLaunchKernelGGL(k_selftest_field, dim3(cdiv(n, 256)), dim3(256), 0, s, in, n, nc, nu_gen, out, outc, (unsigned long long *)mism_dev);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -743,7 +757,7 @@ size_t dot_partial_words(u32 na, u32 nb) { return (size_t)RED_BLOCKS * DOT_NA_MA
 void launch_dot_batch(const DevCrt &t, const u64 *X, size_t ldx, u32 na, const u64 *Y, size_t ldy, u32 nb, size_t n, u64 *partial,
                       u64 *out, hipStream_t s) {
     u32 gb = (u32)((n + 255) / 256);
-    if (gb > 64) gb = 64;   // fatter threads: the 12-value block reduction per block is not free
+    if (gb > LF_DOT_BLOCKS) gb = LF_DOT_BLOCKS;   // fatter threads: the 12-value block reduction per block is not free (the lazy-sum bound of lf_field.cuh counts on this cap)
     if (gb < 1) gb = 1;
 #define LF_DB(N)                                                                                                                           \
     do {                                                                                                                                \
