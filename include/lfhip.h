@@ -14,7 +14,8 @@
  * (arkworks stores Montgomery form internally; the Rust shim converts with into_bigint/from.)
  *
  * Ownership: the caller owns every host buffer; the context owns all device memory.  All
- * pointers below are HOST pointers.  Every function returns 0 on success or a negative
+ * pointers below are HOST pointers, except the array arguments of the `_dev` entry points
+ * ("device-resident callers" below), which are the caller's own device memory.  Every function returns 0 on success or a negative
  * LF_ERR_* code (lf_strerror); nothing aborts.  A context serialises its own calls
  * (internal mutex), so it may be shared between threads (the reference calls `commit` from
  * Rayon workers, nifs/decomposition.rs:185-187); use the batched entry points to collapse
@@ -31,13 +32,15 @@ extern "C" {
 
 #define LF_RING_WORDS 24
 
-/* ABI version: bumped whenever an existing entry point changes meaning (additions alone do not bump it).  lf_abi_version() returns the constant the
+/* ABI version: bumped whenever an existing entry point changes meaning, and with the _dev family (6).  lf_abi_version() returns the constant the
  * library was built with; a binding compares it with the LFHIP_ABI_VERSION it was generated from.
+ *   6  the _dev entry points and lf_ctx_wait_stream ("device-resident callers"): additions only, no existing entry point changes; numbered so that a
+ *      binding can tell a library that has them from one that does not.
  *   5  lf_last_fold_paths: *sv_round_mask is the GEMM-round mask alone on both rings (bits 8..15 used to carry the split-round count of the
  *      linearization on Goldilocks, and BabyBear contexts returned 0): the count moved to lf_last_lin_split_rounds, the table rounds' mask to
  *      lf_last_fold_split_rounds.  lf_debug_i8_prof is declared (it was exported without a prototype).
  *   4  (round 3) first numbered state of this header. */
-#define LFHIP_ABI_VERSION 5
+#define LFHIP_ABI_VERSION 6
 int lf_abi_version(void);
 
 enum {
@@ -332,6 +335,42 @@ int lf_cccs_check(lf_ctx *, const uint64_t *cccs, const lf_witness *wit, uint64_
 /* R_LCCCS, the decider of an accumulator (lcccs [lf_lcccs_len_ring], wit): cm == Com(f), u_j == MLE(M_j z)(r) with z = (x_w, h, w_ccs) for
  * every j, v == f-hat(r) (Witness::get_fhat), and the norm if bound != 0.  LF_OK, or LF_ERR_REJECT with *failed = OR of LF_REL_{CM,U,V,NORM}. */
 int lf_lcccs_check(lf_ctx *, const uint64_t *lcccs, const lf_witness *wit, uint64_t bound, unsigned *failed);
+
+/* ---- device-resident callers: the O(n) arrays as DEVICE memory ----------------------------------------------------------------------------
+ * Every entry point above takes host pointers and stages them over PCIe.  A `_dev` twin has the same signature and the same results, word for word, but
+ * the named array (`in` / `out`, `f`, the input vector, `out` of a getter, `z`) is memory of the CONTEXT'S DEVICE (hipMalloc, a torch tensor, ...) in the
+ * layout of the host ABI: AoS [count][ring words] canonical little-endian u64.  It is read and written in place by the relayout kernels: no staging copy.
+ * Small results stay host pointers: commitments (kappa elements), first_bad, and every handle.
+ *   Checks, before anything is enqueued, after the state and length checks of the host twin (LF_ERR_STATE, LF_ERR_UNSUPPORTED and the length errors are the
+ * host twin's): the array is not NULL, hipPointerGetAttributes reports (unmanaged) device memory of the context's device, the pointer is 8-byte aligned, and
+ * hipMemGetAddressRange shows one allocation covering every byte the call touches.  Anything else -- a host or pinned pointer, another device, a range that
+ * runs off its allocation -- is LF_ERR_INVALID; no kernel is launched on such a pointer.  lf_ntt_{fwd,inv}_dev: in == out is allowed, a partial overlap is
+ * LF_ERR_INVALID.
+ *   Canonical words: the host cannot inspect device data, so the device does.  An input word >= p makes the call return LF_ERR_INVALID: no witness handle is
+ * made and no output is written (only the context's scratch).  What the host-pointer calls do with such words is unchanged.
+ *   Ordering: a _dev call reads its inputs on the context's streams.  The caller guarantees that they are complete -- by synchronising its own stream, or by
+ * lf_ctx_wait_stream(ctx, stream) first: it records an event on `stream` (a hipStream_t; NULL = the default stream) and makes the context's streams wait for
+ * it, without blocking the host and without touching `stream` otherwise.  A _dev call returns after the context's stream is synchronised, like its host twin:
+ * device outputs are complete and the input buffer is free for reuse on return (witness handles own their planes).
+ *   Sharded and small-base contexts accept a _dev call wherever they accept its twin (lf_ccs_check_dev on a sharded context: LF_ERR_UNSUPPORTED, like
+ * lf_ccs_check).  A context with an external basis (lf_set_ext_basis) answers LF_ERR_UNSUPPORTED: that conversion is host code. */
+int lf_ctx_wait_stream(lf_ctx *, void *hip_stream);
+int lf_ntt_fwd_dev(lf_ctx *, const uint64_t *in, uint64_t *out, size_t count);
+int lf_ntt_inv_dev(lf_ctx *, const uint64_t *in, uint64_t *out, size_t count);
+int lf_ajtai_commit_dev(lf_ctx *, const uint64_t *f, size_t n, size_t batch, uint64_t *out /* host */);
+int lf_ajtai_commit_coeff_dev(lf_ctx *, const uint64_t *f_coeff, size_t n, size_t batch, uint64_t *out /* host */);
+int lf_ajtai_decompose_and_commit_coeff_dev(lf_ctx *, const uint64_t *f_coeff, size_t count, uint64_t base, unsigned digits,
+                                            size_t batch, uint64_t *out /* host */);
+int lf_ajtai_decompose_and_commit_ntt_dev(lf_ctx *, const uint64_t *w_ntt, size_t count, uint64_t base, unsigned digits,
+                                          size_t batch, uint64_t *out /* host */);
+int lf_witness_from_w_ccs_dev(lf_ctx *, const uint64_t *w_ccs /* wit_len NTT */, lf_witness **out);
+int lf_witness_from_f_coeff_dev(lf_ctx *, const uint64_t *f_coeff /* N coeff-form */, lf_witness **out);
+int lf_witness_from_f_dev(lf_ctx *, const uint64_t *f_ntt /* N NTT */, lf_witness **out);
+int lf_witness_get_f_coeff_dev(lf_ctx *, const lf_witness *, uint64_t *out /* N */);
+int lf_witness_get_f_dev(lf_ctx *, const lf_witness *, uint64_t *out /* N, NTT */);
+int lf_witness_get_w_ccs_dev(lf_ctx *, const lf_witness *, uint64_t *out /* wit_len, NTT */);
+/* lf_ccs_check on a device z (n NTT elements); *first_bad is a host word.  For general CSR rows z itself is the element-major copy the rows gather from */
+int lf_ccs_check_dev(lf_ctx *, const uint64_t *z, uint64_t *first_bad /* host */);
 
 /* ---- measurement hooks (bench.py): HIP-event time of the last fold step, per phase, in ms ------------ */
 #define LF_N_PHASES 8

@@ -5,6 +5,9 @@ Names follow crates/latticefold: `AjtaiCommitmentScheme` (commitment/commitment_
 (decomposition_parameters.rs:11-20), `NIFSProver.prove` (nifs.rs:48-103), `CCS` (arith.rs:50-74).
 All bulk data are numpy uint64 arrays of canonical residues, shape (..., d) per ring element: d = 24 for
 GoldilocksRingNTT (default), d = 72 for BabyBearRingNTT (`Context(device, ring="babybear")`, `PoseidonTranscript(ring=..)`).
+Where an O(n) array crosses the ABI -- crt / icrt, the commitments, Witness.from_*, the `*_into` getters, check_relation -- a DEVICE array is
+accepted next to numpy: any object with `data_ptr()` and a true `is_cuda` (a torch tensor), contiguous, 8-byte elements, same shape.  It goes to
+the `_dev` entry point as it is, no copy; the context is first ordered behind the current torch stream (lf_ctx_wait_stream).
 
 There is NO CPU fallback: if the HIP library is missing or no GPU is present every call raises.
 """
@@ -173,6 +176,19 @@ def _lib():
         L.lf_last_fold_split_rounds.argtypes = [vp, C.POINTER(C.c_uint)]
         L.lf_last_timeline.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), C.c_int]
         L.lf_last_kernel_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int)]
+        # device-resident callers: the device arrays are plain addresses
+        L.lf_ctx_wait_stream.argtypes = [vp, vp]
+        L.lf_ntt_fwd_dev.argtypes = [vp, vp, vp, C.c_size_t]
+        L.lf_ntt_inv_dev.argtypes = [vp, vp, vp, C.c_size_t]
+        L.lf_ajtai_commit_dev.argtypes = [vp, vp, C.c_size_t, C.c_size_t, u64p]
+        L.lf_ajtai_commit_coeff_dev.argtypes = [vp, vp, C.c_size_t, C.c_size_t, u64p]
+        L.lf_ajtai_decompose_and_commit_coeff_dev.argtypes = [vp, vp, C.c_size_t, C.c_uint64, C.c_uint, C.c_size_t, u64p]
+        L.lf_ajtai_decompose_and_commit_ntt_dev.argtypes = [vp, vp, C.c_size_t, C.c_uint64, C.c_uint, C.c_size_t, u64p]
+        for f in ("lf_witness_from_w_ccs_dev", "lf_witness_from_f_coeff_dev", "lf_witness_from_f_dev"):
+            getattr(L, f).argtypes = [vp, vp, C.POINTER(vp)]
+        for f in ("lf_witness_get_f_coeff_dev", "lf_witness_get_f_dev", "lf_witness_get_w_ccs_dev"):
+            getattr(L, f).argtypes = [vp, vp, vp]
+        L.lf_ccs_check_dev.argtypes = [vp, vp, u64p]
         _LIB = L
     return _LIB
 
@@ -210,6 +226,19 @@ def _a64(x):
 def _chk(rc, where):
     if rc != 0:
         raise LfError(rc, where)
+
+
+def is_device_array(x):
+    """a device-resident array argument: anything with data_ptr() and a true is_cuda (a torch tensor)"""
+    return hasattr(x, "data_ptr") and bool(getattr(x, "is_cuda", False))
+
+
+def _dev(ctx, t):
+    """device array -> its address for a _dev entry point, after ordering the context behind the stream the array was produced on (the current torch stream)"""
+    if not t.is_contiguous() or t.element_size() != 8 or t.dim() < 2 or t.shape[-1] != ctx.RE:
+        raise ValueError(f"device arrays must be contiguous, 8-byte elements, shape (..., {ctx.RE})")
+    ctx.wait_stream()
+    return C.c_void_p(t.data_ptr())
 
 
 class Context:
@@ -332,18 +361,42 @@ class Context:
     def synchronize(self):
         _chk(_lib().lf_device_synchronize(self.h), "lf_device_synchronize")
 
+    def wait_stream(self, stream=None):
+        """lf_ctx_wait_stream: the context's streams wait for what is enqueued so far on `stream` (a hipStream_t address; default: the current torch
+        stream of the context's device); the host does not wait"""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream().cuda_stream
+        _chk(_lib().lf_ctx_wait_stream(self.h, C.c_void_p(stream)), "lf_ctx_wait_stream")
+
     # ---- element-wise ops ----------------------------------------------------------------
-    def crt(self, coeff):  # CRT::elementwise_crt
+    def _ntt_dev(self, fn, name, x, out):
+        import torch
+        o = torch.empty_like(x) if out is None else out
+        if o.shape != x.shape:
+            raise ValueError("out must have the shape of the input")
+        px, po = _dev(self, x), (_dev(self, o) if o is not x else None)
+        _chk(fn(self.h, px, po or px, x.numel() // self.RE), name)
+        return o
+
+    def crt(self, coeff, out=None):  # CRT::elementwise_crt
+        """numpy in, numpy out; a device array in, a device array out (`out`: where to, may be the input itself)"""
+        if is_device_array(coeff):
+            return self._ntt_dev(_lib().lf_ntt_fwd_dev, "lf_ntt_fwd_dev", coeff, out)
         a, p = _a64(coeff)
         o = np.empty_like(a)
         _chk(_lib().lf_ntt_fwd(self.h, p, o.ctypes.data_as(u64p), a.size // self.RE), "lf_ntt_fwd")
         return o
 
-    def icrt(self, ntt):  # ICRT::elementwise_icrt
+    def icrt(self, ntt, out=None):  # ICRT::elementwise_icrt
+        if is_device_array(ntt):
+            return self._ntt_dev(_lib().lf_ntt_inv_dev, "lf_ntt_inv_dev", ntt, out)
         a, p = _a64(ntt)
         o = np.empty_like(a)
         _chk(_lib().lf_ntt_inv(self.h, p, o.ctypes.data_as(u64p), a.size // self.RE), "lf_ntt_inv")
         return o
+
+    ntt_fwd, ntt_inv = crt, icrt
 
     def decompose(self, coeff, base, digits, layout):
         a, p = _a64(coeff)
@@ -416,12 +469,15 @@ class Context:
         """CCS::check_relation (arith.rs:76-110) of the loaded CCS on z (n NTT-form elements): None, or raises NotSatisfied with .row = the first bad row"""
         L = _lib()
         L.lf_ccs_check.argtypes = [C.c_void_p, u64p, u64p]
-        a, p = _a64(z)
         fb = C.c_uint64()
-        rc = L.lf_ccs_check(self.h, p, C.cast(C.byref(fb), u64p))
+        if is_device_array(z):
+            rc, name = L.lf_ccs_check_dev(self.h, _dev(self, z), C.cast(C.byref(fb), u64p)), "lf_ccs_check_dev"
+        else:
+            a, p = _a64(z)
+            rc, name = L.lf_ccs_check(self.h, p, C.cast(C.byref(fb), u64p)), "lf_ccs_check"
         if rc == LF_ERR_REJECT:
-            raise NotSatisfied(fb.value)
-        _chk(rc, "lf_ccs_check")
+            raise NotSatisfied(fb.value, name)
+        _chk(rc, name)
 
     def check_cccs(self, cccs, wit, bound=0):
         """R_CCCS of (cccs, wit): the set of failing components among "cm", "ccs", "norm" (norm: max |centred coefficient| < bound, checked when
@@ -510,21 +566,26 @@ class AjtaiCommitmentScheme:
         return self._n
 
     def commit_ntt(self, f):
-        """commit / commit_ntt: f is (n,d) or (batch,n,d)."""
-        a, p = _a64(f)
+        """commit / commit_ntt: f is (n,d) or (batch,n,d), numpy or a device array; the commitment is numpy either way."""
+        dev = is_device_array(f)
+        a, p = (f, _dev(self.ctx, f)) if dev else _a64(f)
         batch = 1 if a.ndim == 2 else a.shape[0]
         n = a.shape[-2]
         o = np.zeros((batch, self._kappa, self.ctx.RE), dtype=np.uint64)
-        rc = _lib().lf_ajtai_commit(self.ctx.h, p, n, batch, o.ctypes.data_as(u64p))
-        if rc == -1:
+        rc = (_lib().lf_ajtai_commit_dev if dev else _lib().lf_ajtai_commit)(self.ctx.h, p, n, batch, o.ctypes.data_as(u64p))
+        if rc == -1 and (not dev or n != self._n):   # (a device array may also be refused for what it is: LfError)
             raise CommitmentError(rc, f"WrongWitnessLength({n}, {self._n})")
-        _chk(rc, "lf_ajtai_commit")
+        _chk(rc, "lf_ajtai_commit_dev" if dev else "lf_ajtai_commit")
         return o[0] if a.ndim == 2 else o
 
     commit = commit_ntt
 
     def _commit_with(self, fn, name, f, *args, digits=1):
-        a, p = _a64(f)
+        if is_device_array(f):
+            fn, name = getattr(_lib(), name + "_dev"), name + "_dev"
+            a, p = f, _dev(self.ctx, f)
+        else:
+            a, p = _a64(f)
         batch = 1 if a.ndim == 2 else a.shape[0]
         n = a.shape[-2]
         o = np.zeros((batch, self._kappa, self.ctx.RE), dtype=np.uint64)
@@ -592,8 +653,11 @@ class Witness:
 
     @classmethod
     def from_w_ccs(cls, ctx, w_ccs):
-        a, p = _a64(w_ccs)
         h = C.c_void_p()
+        if is_device_array(w_ccs):
+            _chk(_lib().lf_witness_from_w_ccs_dev(ctx.h, _dev(ctx, w_ccs), C.byref(h)), "lf_witness_from_w_ccs_dev")
+            return cls(ctx, h)
+        a, p = _a64(w_ccs)
         _chk(_lib().lf_witness_from_w_ccs(ctx.h, p, C.byref(h)), "lf_witness_from_w_ccs")
         return cls(ctx, h)
 
@@ -604,15 +668,21 @@ class Witness:
 
     @classmethod
     def from_f_coeff(cls, ctx, f_coeff):
-        a, p = _a64(f_coeff)
         h = C.c_void_p()
+        if is_device_array(f_coeff):
+            _chk(_lib().lf_witness_from_f_coeff_dev(ctx.h, _dev(ctx, f_coeff), C.byref(h)), "lf_witness_from_f_coeff_dev")
+            return cls(ctx, h)
+        a, p = _a64(f_coeff)
         _chk(_lib().lf_witness_from_f_coeff(ctx.h, p, C.byref(h)), "lf_witness_from_f_coeff")
         return cls(ctx, h)
 
     @classmethod
     def from_f(cls, ctx, f_ntt):
-        a, p = _a64(f_ntt)
         h = C.c_void_p()
+        if is_device_array(f_ntt):
+            _chk(_lib().lf_witness_from_f_dev(ctx.h, _dev(ctx, f_ntt), C.byref(h)), "lf_witness_from_f_dev")
+            return cls(ctx, h)
+        a, p = _a64(f_ntt)
         _chk(_lib().lf_witness_from_f(ctx.h, p, C.byref(h)), "lf_witness_from_f")
         return cls(ctx, h)
 
@@ -632,6 +702,22 @@ class Witness:
     @property
     def w_ccs(self):
         return self._get(_lib().lf_witness_get_w_ccs, self.ctx.params.wit_len)
+
+    def _get_into(self, fn, name, count, out):
+        if not is_device_array(out) or tuple(out.shape) != (count, self.ctx.RE):
+            raise ValueError(f"out must be a device array of shape ({count}, {self.ctx.RE})")
+        _chk(fn(self.ctx.h, self.h, _dev(self.ctx, out)), name)
+        return out
+
+    def f_coeff_into(self, out):
+        """f_coeff written into a device array (N, d)"""
+        return self._get_into(_lib().lf_witness_get_f_coeff_dev, "lf_witness_get_f_coeff_dev", self.ctx.N, out)
+
+    def f_into(self, out):
+        return self._get_into(_lib().lf_witness_get_f_dev, "lf_witness_get_f_dev", self.ctx.N, out)
+
+    def w_ccs_into(self, out):
+        return self._get_into(_lib().lf_witness_get_w_ccs_dev, "lf_witness_get_w_ccs_dev", self.ctx.params.wit_len, out)
 
     def commit(self, scheme):
         o = np.zeros((scheme.kappa(), self.ctx.RE), dtype=np.uint64)

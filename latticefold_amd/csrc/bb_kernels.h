@@ -29,6 +29,9 @@ E9PreC e9pre_from_h9(const H9 &h, u64 nu);
 // ---- layout / utility ------------------------------------------------------------------------------------------
 void launch_aos_to_soa(const u64 *aos_canon, fe *soa, size_t n, hipStream_t s);     // [n][72] canonical u64 -> [72][n] fe
 void launch_soa_to_aos(const fe *soa, u64 *aos_canon, size_t n, hipStream_t s);
+// the _dev entry points: the source is the caller's device buffer, every word validated against p (bit 0 of *flag: a word >= p); the result goes out unless *flag
+void launch_aos_to_soa_checked(const u64 *aos, fe *soa, size_t n, u32 *flag, hipStream_t s);
+void launch_soa_to_aos_unless(const fe *soa, u64 *aos, size_t n, const u32 *flag, hipStream_t s);
 void launch_fill_ajtai(fe *A, u32 kappa, size_t n, size_t n_total, size_t col0, u64 seed, hipStream_t s, u32 row0 = 0);
 void launch_selftest(const u64 *in_canon /*[n][18]*/, u64 *out_canon /*[n][12]*/, u32 n, fe nu, hipStream_t s);
 // i64 partial sums [nblocks][nv] -> canonical u64 [nv]

@@ -59,12 +59,21 @@ size_t red_partial_words(u32 nv) { return (size_t)RED_BLOCKS * nv; }
 
 // ---------------------------------------------------------------------------------------------------------
 // layout + Montgomery conversion at the ABI
-__global__ void __launch_bounds__(256) k_aos_to_soa(const u64 *aos, fe *soa, size_t n) {
+// CHECKED: the source is a caller's own device buffer (the _dev entry points), read in place, and every word is validated: a wave that saw a word >= p sets
+// *flag -- one vector atomic by its lowest lane after a ballot (every lane of the block runs the same 18 trips, so the ballot sees whole waves)
+template <bool CHECKED>
+__device__ __forceinline__ void aos_to_soa_tile(const u64 *aos, fe *soa, size_t n, u32 *flag) {
     __shared__ fe tile[64][RE + 1];
     size_t base = (size_t)blockIdx.x * 64;
+    bool bad = false;
     for (int idx = threadIdx.x; idx < 64 * RE; idx += 256) {
         size_t e = base + idx / RE;
-        tile[idx / RE][idx % RE] = e < n ? from_canon(aos[e * RE + idx % RE]) : 0;
+        const u64 v = e < n ? aos[e * RE + idx % RE] : 0;
+        if (CHECKED) bad |= v >= BB_P;
+        tile[idx / RE][idx % RE] = from_canon(v);
+    }
+    if (CHECKED) {
+        if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
     }
     __syncthreads();
     for (int idx = threadIdx.x; idx < 64 * RE; idx += 256) {
@@ -72,7 +81,7 @@ __global__ void __launch_bounds__(256) k_aos_to_soa(const u64 *aos, fe *soa, siz
         if (base + j < n) soa[(size_t)w * n + base + j] = tile[j][w];
     }
 }
-__global__ void __launch_bounds__(256) k_soa_to_aos(const fe *soa, u64 *aos, size_t n) {
+__device__ __forceinline__ void soa_to_aos_tile(const fe *soa, u64 *aos, size_t n) {
     __shared__ fe tile[64][RE + 1];
     size_t base = (size_t)blockIdx.x * 64;
     for (int idx = threadIdx.x; idx < 64 * RE; idx += 256) {
@@ -85,11 +94,25 @@ __global__ void __launch_bounds__(256) k_soa_to_aos(const fe *soa, u64 *aos, siz
         if (e < n) aos[e * RE + idx % RE] = to_canon(tile[idx / RE][idx % RE]);
     }
 }
+__global__ void __launch_bounds__(256) k_aos_to_soa(const u64 *aos, fe *soa, size_t n) { aos_to_soa_tile<false>(aos, soa, n, nullptr); }
+__global__ void __launch_bounds__(256) k_aos_to_soa_checked(const u64 *aos, fe *soa, size_t n, u32 *flag) { aos_to_soa_tile<true>(aos, soa, n, flag); }
+__global__ void __launch_bounds__(256) k_soa_to_aos(const fe *soa, u64 *aos, size_t n) { soa_to_aos_tile(soa, aos, n); }
+// the result of a _dev call into the caller's buffer: nothing is written when the checked relayout of the call's input raised *flag
+__global__ void __launch_bounds__(256) k_soa_to_aos_unless(const fe *soa, u64 *aos, size_t n, const u32 *flag) {
+    if (*flag) return;
+    soa_to_aos_tile(soa, aos, n);
+}
 void launch_aos_to_soa(const u64 *aos, fe *soa, size_t n, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_aos_to_soa, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n);
 }
 void launch_soa_to_aos(const fe *soa, u64 *aos, size_t n, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_soa_to_aos, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n);
+}
+void launch_aos_to_soa_checked(const u64 *aos, fe *soa, size_t n, u32 *flag, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_aos_to_soa_checked, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n, flag);
+}
+void launch_soa_to_aos_unless(const fe *soa, u64 *aos, size_t n, const u32 *flag, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_soa_to_aos_unless, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n, flag);
 }
 // workload.py splitmix_fq(ring="babybear"): top 32 bits of SplitMix64 word (index+1), mod p
 __device__ __forceinline__ u64 splitmix_bb(u64 seed, u64 index) {

@@ -466,6 +466,37 @@ int lf_ntt_inv(lf_ctx *c, const uint64_t *in, uint64_t *out, size_t count) {
     if (!c || (!in && count) || (!out && count)) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::ntt_inv(c->bb->p, in, out, count) : ring_ops<GoldRing>::ntt_inv(c, in, out, count);
 }
+// ---- the _dev twins (include/lfhip.h "device-resident callers"): the same bodies with Origin::device.  Here: the null checks of the host twin; a context in an
+// external basis refuses them (the conversion is host code).  The pointer checks proper -- dev_array_check, lf_ring_host.h -- run inside the body, after its
+// state and length checks and before its first launch
+#define LF_DEV_XB(c) do { if (LF_XB(c)) return LF_ERR_UNSUPPORTED; } while (0)
+// in and out of `words` words each: the same array or disjoint ones
+static bool same_or_disjoint(const uint64_t *in, const uint64_t *out, size_t words) { return in == out || in + words <= out || out + words <= in; }
+int lf_ntt_fwd_dev(lf_ctx *c, const uint64_t *in, uint64_t *out, size_t count) {
+    if (!c || (!in && count) || (!out && count) || !same_or_disjoint(in, out, count * lf_ring_words(lf_ctx_ring(c)))) return LF_ERR_INVALID;
+    LF_DEV_XB(c);
+    return c->bb ? ring_ops<BbRing>::ntt_fwd(c->bb->p, in, out, count, Origin::device) : ring_ops<GoldRing>::ntt_fwd(c, in, out, count, Origin::device);
+}
+int lf_ntt_inv_dev(lf_ctx *c, const uint64_t *in, uint64_t *out, size_t count) {
+    if (!c || (!in && count) || (!out && count) || !same_or_disjoint(in, out, count * lf_ring_words(lf_ctx_ring(c)))) return LF_ERR_INVALID;
+    LF_DEV_XB(c);
+    return c->bb ? ring_ops<BbRing>::ntt_inv(c->bb->p, in, out, count, Origin::device) : ring_ops<GoldRing>::ntt_inv(c, in, out, count, Origin::device);
+}
+// Order the context's lanes behind the work enqueued so far on a stream of the caller's: an event recorded there, waited for by every lane.  The host does not
+// wait and the caller's stream is not touched otherwise
+int lf_ctx_wait_stream(lf_ctx *c, void *hip_stream) {
+    if (!c) return LF_ERR_INVALID;
+    CtxCoreBase &k = c->core_any();
+    std::lock_guard<std::mutex> g(k.mu);
+    HIPCHK(hipSetDevice(c->device));
+    hipEvent_t ev;
+    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, (hipStream_t)hip_stream);
+    for (int l = 0; l < LF_NLANES && e == hipSuccess; l++)
+        if (k.st_lane[l]) e = hipStreamWaitEvent(k.st_lane[l], ev, 0);
+    (void)hipEventDestroy(ev);   // (released by the runtime once the waits have passed)
+    return e == hipSuccess ? LF_OK : LF_ERR_HIP;
+}
 int lf_decompose(lf_ctx *c, const uint64_t *in, size_t count, uint64_t base, unsigned digits, int layout, uint64_t *out) {
     if (!c || !in || !out || digits == 0 || digits > 64 || (layout != 0 && layout != 1)) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::decompose(c->bb->p, in, count, base, digits, layout, out) : ring_ops<GoldRing>::decompose(c, in, count, base, digits, layout, out);
@@ -607,9 +638,16 @@ int lf_ajtai_commit(lf_ctx *c, const uint64_t *f, size_t n, size_t batch, uint64
     if (!c || !f || !out || !batch) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::ajtai_commit(c->bb->p, f, n, batch, out) : ring_ops<GoldRing>::ajtai_commit(c, f, n, batch, out);
 }
+int lf_ajtai_commit_dev(lf_ctx *c, const uint64_t *f, size_t n, size_t batch, uint64_t *out) {
+    if (!c || !f || !out || !batch) return LF_ERR_INVALID;
+    LF_DEV_XB(c);
+    return c->bb ? ring_ops<BbRing>::ajtai_commit(c->bb->p, f, n, batch, out, Origin::device) : ring_ops<GoldRing>::ajtai_commit(c, f, n, batch, out, Origin::device);
+}
 // The ABI side of the three (dec false: commit_coeff, no decomposition): arguments are checked before any device work; in an external basis the commitments
 // leave converted and NTT-form input is converted on the way in, coefficient-form input is not (as lf_witness_from_f_coeff).
-static int ajtai_commit_gadget_api(lf_ctx *c, const uint64_t *f, bool ntt_in, size_t count, bool dec, uint64_t base, unsigned digits, size_t batch, uint64_t *out) {
+static int ajtai_commit_gadget_api(lf_ctx *c, const uint64_t *f, bool ntt_in, size_t count, bool dec, uint64_t base, unsigned digits, size_t batch, uint64_t *out,
+                                   Origin org = Origin::host) {
+    if (org == Origin::device) LF_DEV_XB(c);
     if (LF_XB(c) && f && out) {
         XB x(c);
         const u32 kap = c->core_any().kappa;
@@ -623,8 +661,8 @@ static int ajtai_commit_gadget_api(lf_ctx *c, const uint64_t *f, bool ntt_in, si
         if (!pow2(base) || (c->bb && base > (1ull << 32))) return LF_ERR_UNSUPPORTED;
         while ((1ull << lb) < base) lb++;
     }
-    return c->bb ? ring_ops<BbRing>::ajtai_commit_gadget(c->bb->p, f, ntt_in, count, lb, digits, batch, out)
-                 : ring_ops<GoldRing>::ajtai_commit_gadget(c, f, ntt_in, count, lb, digits, batch, out);
+    return c->bb ? ring_ops<BbRing>::ajtai_commit_gadget(c->bb->p, f, ntt_in, count, lb, digits, batch, out, org)
+                 : ring_ops<GoldRing>::ajtai_commit_gadget(c, f, ntt_in, count, lb, digits, batch, out, org);
 }
 int lf_ajtai_commit_coeff(lf_ctx *c, const uint64_t *f_coeff, size_t n, size_t batch, uint64_t *out) {
     return ajtai_commit_gadget_api(c, f_coeff, false, n, false, 0, 1, batch, out);
@@ -634,6 +672,15 @@ int lf_ajtai_decompose_and_commit_coeff(lf_ctx *c, const uint64_t *f_coeff, size
 }
 int lf_ajtai_decompose_and_commit_ntt(lf_ctx *c, const uint64_t *w_ntt, size_t count, uint64_t base, unsigned digits, size_t batch, uint64_t *out) {
     return ajtai_commit_gadget_api(c, w_ntt, true, count, true, base, digits, batch, out);
+}
+int lf_ajtai_commit_coeff_dev(lf_ctx *c, const uint64_t *f_coeff, size_t n, size_t batch, uint64_t *out) {
+    return ajtai_commit_gadget_api(c, f_coeff, false, n, false, 0, 1, batch, out, Origin::device);
+}
+int lf_ajtai_decompose_and_commit_coeff_dev(lf_ctx *c, const uint64_t *f_coeff, size_t count, uint64_t base, unsigned digits, size_t batch, uint64_t *out) {
+    return ajtai_commit_gadget_api(c, f_coeff, false, count, true, base, digits, batch, out, Origin::device);
+}
+int lf_ajtai_decompose_and_commit_ntt_dev(lf_ctx *c, const uint64_t *w_ntt, size_t count, uint64_t base, unsigned digits, size_t batch, uint64_t *out) {
+    return ajtai_commit_gadget_api(c, w_ntt, true, count, true, base, digits, batch, out, Origin::device);
 }
 
 // column-sharded commit: the context holds only columns [col0, col0+n_local) of A (loaded with lf_ajtai_load on
@@ -797,6 +844,36 @@ int lf_witness_get_w_ccs(lf_ctx *c, const lf_witness *w, uint64_t *out) {
     if (LF_XB(c) && w && out && c->have_ccs_any()) { XB x(c); int rc = lf_witness_get_w_ccs(c, w, out); if (rc == LF_OK) x.ring_out(out, c->params_any().wit_len); return rc; }
     if (!c || !w || !out || w->ctx != c) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::witness_get_w_ccs(c->bb->p, w, out) : ring_ops<GoldRing>::witness_get_w_ccs(c, w, out);
+}
+int lf_witness_from_w_ccs_dev(lf_ctx *c, const uint64_t *w_ccs, lf_witness **out) {
+    if (!c || !w_ccs || !out) return LF_ERR_INVALID;
+    LF_DEV_XB(c);
+    return c->bb ? ring_ops<BbRing>::witness_from_w_ccs(c->bb->p, w_ccs, out, Origin::device) : ring_ops<GoldRing>::witness_from_w_ccs(c, w_ccs, out, Origin::device);
+}
+int lf_witness_from_f_coeff_dev(lf_ctx *c, const uint64_t *f_coeff, lf_witness **out) {
+    if (!c || !f_coeff || !out) return LF_ERR_INVALID;
+    LF_DEV_XB(c);
+    return c->bb ? ring_ops<BbRing>::witness_from_f_coeff(c->bb->p, f_coeff, out, Origin::device) : ring_ops<GoldRing>::witness_from_f_coeff(c, f_coeff, out, Origin::device);
+}
+int lf_witness_from_f_dev(lf_ctx *c, const uint64_t *f_ntt, lf_witness **out) {
+    if (!c || !f_ntt || !out) return LF_ERR_INVALID;
+    LF_DEV_XB(c);
+    return c->bb ? ring_ops<BbRing>::witness_from_f(c->bb->p, f_ntt, out, Origin::device) : ring_ops<GoldRing>::witness_from_f(c, f_ntt, out, Origin::device);
+}
+int lf_witness_get_f_coeff_dev(lf_ctx *c, const lf_witness *w, uint64_t *out) {
+    if (!c || !w || !out || w->ctx != c) return LF_ERR_INVALID;
+    LF_DEV_XB(c);
+    return c->bb ? ring_ops<BbRing>::witness_get_f_coeff(c->bb->p, w, out, Origin::device) : ring_ops<GoldRing>::witness_get_f_coeff(c, w, out, Origin::device);
+}
+int lf_witness_get_f_dev(lf_ctx *c, const lf_witness *w, uint64_t *out) {
+    if (!c || !w || !out || w->ctx != c) return LF_ERR_INVALID;
+    LF_DEV_XB(c);
+    return c->bb ? ring_ops<BbRing>::witness_get_f(c->bb->p, w, out, Origin::device) : ring_ops<GoldRing>::witness_get_f(c, w, out, Origin::device);
+}
+int lf_witness_get_w_ccs_dev(lf_ctx *c, const lf_witness *w, uint64_t *out) {
+    if (!c || !w || !out || w->ctx != c) return LF_ERR_INVALID;
+    LF_DEV_XB(c);
+    return c->bb ? ring_ops<BbRing>::witness_get_w_ccs(c->bb->p, w, out, Origin::device) : ring_ops<GoldRing>::witness_get_w_ccs(c, w, out, Origin::device);
 }
 int lf_witness_commit(lf_ctx *c, const lf_witness *w, uint64_t *cm_out) {
     if (LF_XB(c) && w && cm_out) { XB x(c); int rc = lf_witness_commit(c, w, cm_out); if (rc == LF_OK) x.ring_out(cm_out, c->core_any().kappa); return rc; }

@@ -9,9 +9,10 @@
 
 namespace lfring {
 
-// M_j z for every matrix j -> a fresh mz [t][RE][m] (z [RE][n] on the device)
+// M_j z for every matrix j -> a fresh mz [t][RE][m] (z [RE][n] on the device).  z_aos (optional, rings with general CSR rows): an element-major z [n][RE] that
+// exists already -- the device buffer of an lf_ccs_check_dev caller -- so none is rebuilt
 template <class C>
-static int mz_tables(C *c, const typename Ring<C>::W *z, typename Ring<C>::W **mz_out) {
+static int mz_tables(C *c, const typename Ring<C>::W *z, typename Ring<C>::W **mz_out, const u64 *z_aos = nullptr) {
     typedef Ring<C> R;
     const lf_params &P = c->P;
     typename R::W *mz;
@@ -19,9 +20,11 @@ static int mz_tables(C *c, const typename Ring<C>::W *z, typename Ring<C>::W **m
     *mz_out = mz;
     if constexpr (R::general_csr) {   // Goldilocks only: both CSR layouts, as in the linearization
         if (c->ccs_general) {
-            typename R::W *zaos;
-            RET(c->tbuf("spmv_zaos", (size_t)P.t * c->n * R::RE, &zaos));
-            launch_soa_to_aos(z, zaos, c->n, c->stream());
+            typename R::W *zaos = (typename R::W *)z_aos;   // (canonical words are this ring's device form)
+            if (!zaos) {
+                RET(c->tbuf("spmv_zaos", (size_t)P.t * c->n * R::RE, &zaos));
+                launch_soa_to_aos(z, zaos, c->n, c->stream());
+            }
             for (u32 j = 0; j < P.t; j++)
                 launch_spmv_rows(R::tab(c), 1, &c->d_rowptr[j], &c->d_col[j], &c->d_val[j], nullptr, 0, c->n, zaos, mz + (size_t)j * R::RE * c->m, c->m, 0, c->stream());
             return LF_OK;
@@ -41,9 +44,9 @@ static int check_words(C *c, u32 *w) {
 
 // z -> M_j z -> residual: lowers w[0] to the first bad row
 template <class C>
-static int ccs_residual(C *c, const typename Ring<C>::W *z, u32 *w) {
+static int ccs_residual(C *c, const typename Ring<C>::W *z, u32 *w, const u64 *z_aos = nullptr) {
     typename Ring<C>::W *mz;
-    RET(mz_tables(c, z, &mz));
+    RET(mz_tables(c, z, &mz, z_aos));
     launch_ccs_residual(Ring<C>::tab(c), c->desc, mz, c->m, c->m, w, c->stream());
     return LF_OK;
 }
@@ -61,21 +64,26 @@ static int check_state(C *c, const lf_witness *wit, bool need_A) {
 static bool same_words(const u64 *a, const u64 *b, size_t n) { return !memcmp(a, b, n * 8); }
 
 template <class C>
-static int ccs_check(C *c, const u64 *z, u64 *first_bad) {
+static int ccs_check(C *c, const u64 *z, u64 *first_bad, Origin org) {
     typedef Ring<C> R;
     std::lock_guard<std::mutex> g(c->mu);
     RET(check_state(c, nullptr, false));
     HIPCHK(hipSetDevice(c->device));
+    DevIo<C> io(c, org);
+    RET(io.array(z, c->n));
     typename R::W *zd;
     u64 *od;
     RET(c->tbuf("chk_z", (size_t)R::RE * c->n, &zd));
     RET(c->tbuf("chk_od", 8, &od));
     u32 *w = (u32 *)od;
-    RET(up_ring(c, z, c->n, zd));
+    RET(io.begin());
+    RET(up_ring(io, z, c->n, zd));
     RET(check_words(c, w));
-    RET(ccs_residual(c, zd, w));
+    RET(ccs_residual(c, zd, w, io.dev ? z : nullptr));   // a device z is the element-major copy the general CSR rows gather from
     u32 h[2];
+    RET(io.fetch());                                     // (travels with the download of the check words)
     RET(down_small(c, od, 1, (u64 *)h));
+    if (io.bad()) return LF_ERR_INVALID;
     *first_bad = h[0];
     return h[0] < c->m ? LF_ERR_REJECT : LF_OK;
 }
@@ -162,7 +170,12 @@ static int lcccs_check(C *c, const u64 *lcccs, const lf_witness *wit, u64 bound,
 int lf_ccs_check(lf_ctx *c, const uint64_t *z, uint64_t *first_bad) {
     if (LF_XB(c) && z && first_bad && c->have_ccs_any()) { XB x(c); return lf_ccs_check(c, x.ring_in(z, c->n_any()), first_bad); }
     if (!c || !z || !first_bad) return LF_ERR_INVALID;
-    return c->bb ? lfring::ccs_check(c->bb->p, z, first_bad) : lfring::ccs_check(c, z, first_bad);
+    return c->bb ? lfring::ccs_check(c->bb->p, z, first_bad, Origin::host) : lfring::ccs_check(c, z, first_bad, Origin::host);
+}
+int lf_ccs_check_dev(lf_ctx *c, const uint64_t *z, uint64_t *first_bad) {
+    if (!c || !z || !first_bad) return LF_ERR_INVALID;
+    if (LF_XB(c)) return LF_ERR_UNSUPPORTED;   // device words are never converted between bases
+    return c->bb ? lfring::ccs_check(c->bb->p, z, first_bad, Origin::device) : lfring::ccs_check(c, z, first_bad, Origin::device);
 }
 
 int lf_cccs_check(lf_ctx *c, const uint64_t *cccs, const lf_witness *wit, uint64_t bound, unsigned *failed, uint64_t *first_bad) {

@@ -113,6 +113,15 @@ struct CtxCoreBase {
         if (!p && hipHostMalloc((void **)&p, round_out_bytes, hipHostMallocMapped) != hipSuccess) p = nullptr;
         return p;
     }
+    // ---- device-resident callers (the _dev entry points): per lane, the device word the checked relayout raises on an input word >= p and the pinned word it is
+    // copied to.  The copy is enqueued in front of a synchronise the call performs anyway (lf_ring_host.h, DevIo)
+    uint32_t *h_flag_lane[LF_NLANES] = {nullptr, nullptr, nullptr};
+    int dev_flag(uint32_t **dev, uint32_t **host) {
+        uint32_t *&hf = h_flag_lane[lane()];
+        if (!hf && hipHostMalloc((void **)&hf, 64) != hipSuccess) { hf = nullptr; return LF_ERR_HIP; }
+        *host = hf;
+        return tbuf("dev_io_flag", 16, dev);
+    }
     // ---- timed launches: tag 0 = fold round kernels, 1 = ajtai, 10+i = phase i -------------------------------------------------------------------------
     std::vector<EvPair> ev_pool;
     size_t ev_used = 0;
@@ -194,7 +203,9 @@ protected:
         for (int l = 0; l < LF_NLANES; l++) {
             if (h_pin_lane[l]) (void)hipHostFree(h_pin_lane[l]);
             if (h_round[l]) (void)hipHostFree(h_round[l]);
+            if (h_flag_lane[l]) (void)hipHostFree(h_flag_lane[l]);
             h_pin_lane[l] = h_round[l] = nullptr;
+            h_flag_lane[l] = nullptr;
         }
         for (auto &e : ev_pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
         ev_pool.clear();

@@ -28,6 +28,9 @@ struct Fq3Const { u64 c[3]; };
 // ---- layout / utility --------------------------------------------------------------------------------------
 void launch_aos_to_soa(const u64 *aos, u64 *soa, size_t n, hipStream_t s);   // [n][24] -> [24][n]
 void launch_soa_to_aos(const u64 *soa, u64 *aos, size_t n, hipStream_t s);
+// the _dev entry points: the source is the caller's device buffer, every word validated against p (bit 0 of *flag: a word >= p); the result goes out unless *flag
+void launch_aos_to_soa_checked(const u64 *aos, u64 *soa, size_t n, u32 *flag, hipStream_t s);
+void launch_soa_to_aos_unless(const u64 *soa, u64 *aos, size_t n, const u32 *flag, hipStream_t s);
 void launch_fill_uniform(u64 *dst, size_t words, u64 seed, size_t start, hipStream_t s);  // SplitMix64 stream (workload.py)
 // Ajtai matrix generated in place in plane layout, equal to AoS stream splitmix(seed)[((i*n+j)*24+w)]
 // columns [col0, col0+n) of the n_total-column matrix

@@ -66,12 +66,21 @@ void launch_gather_relayout_part(const u64 *all, u32 nranks, size_t planes_tot, 
 
 // ---------------------------------------------------------------------------------------------------------
 // layout
-__global__ void __launch_bounds__(256) k_aos_to_soa(const u64 *aos, u64 *soa, size_t n) {
+// CHECKED: the source is a caller's own device buffer (the _dev entry points), read in place, and every word is validated: a wave that saw a word >= p sets
+// *flag -- one vector atomic by its lowest lane after a ballot (every lane of the block runs the same six trips, so the ballot sees whole waves)
+template <bool CHECKED>
+__device__ __forceinline__ void aos_to_soa_tile(const u64 *aos, u64 *soa, size_t n, u32 *flag) {
     __shared__ u64 tile[64][25];
     size_t base = (size_t)blockIdx.x * 64;
+    bool bad = false;
     for (int idx = threadIdx.x; idx < 64 * 24; idx += 256) {
         size_t e = base + idx / 24;
-        tile[idx / 24][idx % 24] = e < n ? aos[e * 24 + idx % 24] : 0;
+        const u64 v = e < n ? aos[e * 24 + idx % 24] : 0;
+        if (CHECKED) bad |= v >= LF_P;
+        tile[idx / 24][idx % 24] = v;
+    }
+    if (CHECKED) {
+        if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
     }
     __syncthreads();
     for (int idx = threadIdx.x; idx < 64 * 24; idx += 256) {
@@ -79,7 +88,7 @@ __global__ void __launch_bounds__(256) k_aos_to_soa(const u64 *aos, u64 *soa, si
         if (base + j < n) soa[(size_t)w * n + base + j] = tile[j][w];
     }
 }
-__global__ void __launch_bounds__(256) k_soa_to_aos(const u64 *soa, u64 *aos, size_t n) {
+__device__ __forceinline__ void soa_to_aos_tile(const u64 *soa, u64 *aos, size_t n) {
     __shared__ u64 tile[64][25];
     size_t base = (size_t)blockIdx.x * 64;
     for (int idx = threadIdx.x; idx < 64 * 24; idx += 256) {
@@ -92,11 +101,25 @@ __global__ void __launch_bounds__(256) k_soa_to_aos(const u64 *soa, u64 *aos, si
         if (e < n) aos[e * 24 + idx % 24] = tile[idx / 24][idx % 24];
     }
 }
+__global__ void __launch_bounds__(256) k_aos_to_soa(const u64 *aos, u64 *soa, size_t n) { aos_to_soa_tile<false>(aos, soa, n, nullptr); }
+__global__ void __launch_bounds__(256) k_aos_to_soa_checked(const u64 *aos, u64 *soa, size_t n, u32 *flag) { aos_to_soa_tile<true>(aos, soa, n, flag); }
+__global__ void __launch_bounds__(256) k_soa_to_aos(const u64 *soa, u64 *aos, size_t n) { soa_to_aos_tile(soa, aos, n); }
+// the result of a _dev call into the caller's buffer: nothing is written when the checked relayout of the call's input raised *flag
+__global__ void __launch_bounds__(256) k_soa_to_aos_unless(const u64 *soa, u64 *aos, size_t n, const u32 *flag) {
+    if (*flag) return;
+    soa_to_aos_tile(soa, aos, n);
+}
 void launch_aos_to_soa(const u64 *aos, u64 *soa, size_t n, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_aos_to_soa, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n);
 }
 void launch_soa_to_aos(const u64 *soa, u64 *aos, size_t n, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_soa_to_aos, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n);
+}
+void launch_aos_to_soa_checked(const u64 *aos, u64 *soa, size_t n, u32 *flag, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_aos_to_soa_checked, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n, flag);
+}
+void launch_soa_to_aos_unless(const u64 *soa, u64 *aos, size_t n, const u32 *flag, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_soa_to_aos_unless, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n, flag);
 }
 
 __device__ __forceinline__ u64 splitmix_fq(u64 seed, u64 index) {

@@ -176,6 +176,66 @@ int down_ring(C *c, const typename Ring<C>::W *src, size_t n, u64 *host) {
     HIPCHK(hipStreamSynchronize(c->stream()));
     return LF_OK;
 }
+
+// ---- where the O(n) array arguments of an entry point live --------------------------------------------------------------------------------------------
+// Origin::host (every lf_* call without the suffix): pageable host memory, staged through `stage_aos` as above.  Origin::device (the _dev twins): the caller's own
+// memory on the context's device, same AoS layout; the relayout kernels read and write it in place, nothing is staged.  What the host cannot see it lets the
+// device check: the checked relayout raises a flag word on an input word >= p, the flag comes back in front of a synchronise the call performs anyway, results go
+// into the caller's buffer only while the flag is down (launch_soa_to_aos_unless), and the call returns LF_ERR_INVALID.
+enum class Origin { host, device };
+// [p, p + bytes) lies inside the allocation [base, base + size): the whole range arithmetic of the pointer checks
+inline bool range_inside(uintptr_t base, size_t size, uintptr_t p, size_t bytes) { return p >= base && p - base <= size && bytes <= size - (p - base); }
+// THE pointer check of every _dev entry point, before anything is enqueued: device memory of `device`, 8-byte aligned, `bytes` bytes inside one allocation.
+// A host or pinned pointer, managed memory, another device's memory, a range that runs off its allocation: LF_ERR_INVALID, never a launch
+inline int dev_array_check(int device, const void *p, size_t bytes) {
+    if (!p || ((uintptr_t)p & 7)) return LF_ERR_INVALID;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return LF_ERR_INVALID; }   // (older runtimes fail on plain host memory)
+    if (at.type != hipMemoryTypeDevice || at.isManaged || at.device != device) return LF_ERR_INVALID;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return LF_ERR_INVALID; }
+    return range_inside((uintptr_t)base, size, (uintptr_t)p, bytes) ? LF_OK : LF_ERR_INVALID;
+}
+template <class C>
+struct DevIo {
+    C *c;
+    const bool dev;
+    u32 *flag = nullptr, *hflag = nullptr;   // device word / its pinned copy; null: nothing of this call is checked on the device (host origin, or no array input)
+    DevIo(C *c_, Origin o) : c(c_), dev(o == Origin::device) {}
+    // an array argument of n ring elements (after the call's state and length checks, before anything is enqueued)
+    int array(const void *p, size_t n) const { return dev && n ? dev_array_check(c->device, p, n * Ring<C>::RE * 8) : LF_OK; }
+    // the call has device inputs: lower the flag, in stream
+    int begin() {
+        if (!dev) return LF_OK;
+        RET(c->dev_flag(&flag, &hflag));
+        *hflag = 0;
+        HIPCHK(hipMemsetAsync(flag, 0, 4, c->stream()));
+        return LF_OK;
+    }
+    // enqueue the flag's way home; bad() is valid after the next synchronise of the stream
+    int fetch() {
+        if (flag) HIPCHK(hipMemcpyAsync(hflag, flag, 4, hipMemcpyDeviceToHost, c->stream()));
+        return LF_OK;
+    }
+    bool bad() const { return flag && *(volatile u32 *)hflag != 0; }
+};
+template <class C>
+int up_ring(DevIo<C> &io, const u64 *src, size_t n, typename Ring<C>::W *dst) {
+    if (!io.dev) return up_ring(io.c, src, n, dst);
+    launch_aos_to_soa_checked(src, dst, n, io.flag, io.c->stream());
+    return LF_OK;
+}
+// the result of a call, complete on return; from device inputs that were not canonical: LF_ERR_INVALID and `out` untouched
+template <class C>
+int down_ring(DevIo<C> &io, const typename Ring<C>::W *src, size_t n, u64 *out) {
+    if (!io.dev) return down_ring(io.c, src, n, out);
+    if (io.flag) launch_soa_to_aos_unless(src, out, n, io.flag, io.c->stream());
+    else launch_soa_to_aos(src, out, n, io.c->stream());
+    RET(io.fetch());
+    HIPCHK(hipStreamSynchronize(io.c->stream()));
+    return io.bad() ? LF_ERR_INVALID : LF_OK;
+}
 template <class C, class T>
 int upload_consts(C *c, const std::string &name, const std::vector<T> &v, T **out) {
     RET(c->tbuf(name, v.size() + 8, out));
@@ -461,20 +521,25 @@ struct ring_ops<Ring<C>> {
     // ---- a5: general commitments through the ABI ----
     // Both re-read the environment switches, as every prover entry point does (the BabyBear bodies did not before they were merged: nothing in the general
     // commit path of that ring consumes a tunable, so the read changes nothing there until the next linearize / fold step reads them again anyway).
-    static int ajtai_commit(C *c, const u64 *f, size_t n, size_t batch, u64 *out) {
+    static int ajtai_commit(C *c, const u64 *f, size_t n, size_t batch, u64 *out, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         if (!c->A_loaded) return LF_ERR_STATE;
         if (n != c->nA_total) return LF_ERR_INVALID;  // CommitmentError::WrongWitnessLength(n, width)
         HIPCHK(hipSetDevice(c->device));
+        DevIo<C> io(c, org);
+        RET(io.array(f, batch * n));
         W *F;
         u64 *o;
         RET(c->tbuf("io_a", batch * n * RE, &F));
         RET(c->tbuf(R::io_out, batch * c->kappa * RE, &o));
-        for (size_t b = 0; b < batch; b++) RET(up_ring(c, f + b * n * RE, n, F + b * RE * n));
+        RET(io.begin());
+        for (size_t b = 0; b < batch; b++) RET(up_ring(io, f + b * n * RE, n, F + b * RE * n));
         c->tn = Tunables::read(R::lut_min_default);
         c->ev_reset();
         RET(commit_dev_i8g(c, F + c->A_col0, n, (u32)batch, nullptr, 0, o, true));   // timed: lf_last_kernel_stats reports the stand-alone kernel
-        c->ev_collect();
+        RET(io.fetch());
+        c->ev_collect();   // (synchronises the lanes)
+        if (io.bad()) return LF_ERR_INVALID;
         return R::commit_finish(c, o, batch * c->kappa * RE, out);
     }
     // commit_coeff / decompose_and_commit_{coeff,ntt} (commitment_scheme.rs:81-113): element i of f [batch][count] (coefficient form, or NTT form: ntt_in)
@@ -482,17 +547,20 @@ struct ring_ops<Ring<C>> {
     // built: the gadget digit pass (lf_i8g_dec.cuh) writes the commit kernel's operand words from the coefficient table, as few planes as the base needs.
     // NTT-form input is inverse-CRT-ed into one coefficient table first (one pass over count elements; the fused form of k_i8g_cut_ntt would map 32 elements
     // = 32 L columns per block -- DESIGN.md, k_ajtai_i8g row).
-    static int ajtai_commit_gadget(C *c, const u64 *f, bool ntt_in, size_t count, u32 lb, u32 L, size_t batch, u64 *out) {
+    static int ajtai_commit_gadget(C *c, const u64 *f, bool ntt_in, size_t count, u32 lb, u32 L, size_t batch, u64 *out, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         if (!c->A_loaded) return LF_ERR_STATE;
         if (count > c->nA_total || count * L != c->nA_total) return LF_ERR_INVALID;   // CommitmentError::WrongWitnessLength
         HIPCHK(hipSetDevice(c->device));
+        DevIo<C> io(c, org);
+        RET(io.array(f, batch * count));
         W *F, *X = nullptr;
         u64 *o;
         RET(c->tbuf("io_a", batch * count * RE, &F));
         if (ntt_in) RET(c->tbuf("io_c", count * RE, &X));
         RET(c->tbuf(R::io_out, batch * c->kappa * RE, &o));
-        for (size_t b = 0; b < batch; b++) RET(up_ring(c, f + b * count * RE, count, F + b * RE * count));
+        RET(io.begin());
+        for (size_t b = 0; b < batch; b++) RET(up_ring(io, f + b * count * RE, count, F + b * RE * count));
         c->tn = Tunables::read(R::lut_min_default);
         c->ev_reset();
         const u32 NP = lb ? ajtai_i8g_planes_base(R::i8(), 1ull << lb) : ajtai_i8g_planes_general(R::i8());
@@ -501,30 +569,40 @@ struct ring_ops<Ring<C>> {
             if (ntt_in) { launch_icrt_dense(c->d_icrt, src, X, count, c->stream()); src = X; }
             launch_i8g_cut_dec(src, count, c->A_col0, c->nA, L, lb, c->digit_mode, NP, pre, ntiles, c->stream());
         }));
-        c->ev_collect();
+        RET(io.fetch());
+        c->ev_collect();   // (synchronises the lanes)
+        if (io.bad()) return LF_ERR_INVALID;
         return R::commit_finish(c, o, batch * c->kappa * RE, out);
     }
 
     // ---- a1/a2/a3 ----
-    static int ntt_fwd(C *c, const u64 *in, u64 *out, size_t count) {
+    static int ntt_fwd(C *c, const u64 *in, u64 *out, size_t count, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         HIPCHK(hipSetDevice(c->device));
+        DevIo<C> io(c, org);
+        RET(io.array(in, count));
+        RET(io.array(out, count));
         W *a, *b;
         RET(c->tbuf("io_a", count * RE, &a));
         RET(c->tbuf("io_b", count * RE, &b));
-        RET(up_ring(c, in, count, a));
+        RET(io.begin());
+        RET(up_ring(io, in, count, a));
         launch_crt_fwd(R::tab(c), a, b, count, c->stream());
-        return down_ring(c, b, count, out);
+        return down_ring(io, b, count, out);
     }
-    static int ntt_inv(C *c, const u64 *in, u64 *out, size_t count) {
+    static int ntt_inv(C *c, const u64 *in, u64 *out, size_t count, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         HIPCHK(hipSetDevice(c->device));
+        DevIo<C> io(c, org);
+        RET(io.array(in, count));
+        RET(io.array(out, count));
         W *a, *b;
         RET(c->tbuf("io_a", count * RE, &a));
         RET(c->tbuf("io_b", count * RE, &b));
-        RET(up_ring(c, in, count, a));
+        RET(io.begin());
+        RET(up_ring(io, in, count, a));
         launch_icrt_dense(c->d_icrt, a, b, count, c->stream());
-        return down_ring(c, b, count, out);
+        return down_ring(io, b, count, out);
     }
     static int decompose(C *c, const u64 *in, size_t count, u64 base, unsigned digits, int layout, u64 *out) {
         if (!pow2(base)) return LF_ERR_UNSUPPORTED;
@@ -769,7 +847,7 @@ struct ring_ops<Ring<C>> {
     }
 
     // ---- witnesses ----
-    static int witness_from_coef_table(C *c, const W *coef_dev /* [RE][N] */, lf_witness **out) {
+    static int witness_from_coef_table(C *c, const W *coef_dev /* [RE][N] */, lf_witness **out, DevIo<C> *io = nullptr) {
         int32_t *pl;
         HIPCHK(lf_dev_malloc(&pl, c->N * RE * 4));
         int *viol;
@@ -777,10 +855,12 @@ struct ring_ops<Ring<C>> {
         (void)hipMemsetAsync(viol, 0, 4, c->stream());
         launch_coef_to_i32(coef_dev, pl, c->N, (u32)(c->P.B / 2), viol, c->stream());
         int hv = 0;
-        if (hipMemcpyAsync(&hv, viol, 4, hipMemcpyDeviceToHost, c->stream()) != hipSuccess || hipStreamSynchronize(c->stream()) != hipSuccess) {
+        if ((io && io->fetch() != LF_OK) || hipMemcpyAsync(&hv, viol, 4, hipMemcpyDeviceToHost, c->stream()) != hipSuccess ||
+            hipStreamSynchronize(c->stream()) != hipSuccess) {
             (void)hipFree(pl);
             return LF_ERR_HIP;
         }
+        if (io && io->bad()) { (void)hipFree(pl); return LF_ERR_INVALID; }   // device input with a word >= p: no handle
         // bit 0: a coefficient outside the bound; bit 1 (Goldilocks, B = 2^32): +2^31, which an int32 plane cannot hold.  The BabyBear kernel writes bit 0 only
         // (B <= 2^30), so the one expression serves both rings
         if (hv) { (void)hipFree(pl); return (hv & 1) ? LF_ERR_NORM : LF_ERR_UNSUPPORTED; }
@@ -788,70 +868,85 @@ struct ring_ops<Ring<C>> {
         return LF_OK;
     }
     // Witness::from_w_ccs, arith.rs:230-248: ICRT -> gadget_decompose(B, L); on the calling thread's lane (its stream, its buffers)
-    static int witness_from_w_ccs_lane(C *c, const u64 *w_ccs, lf_witness **out) {
+    static int witness_from_w_ccs_lane(C *c, const u64 *w_ccs, lf_witness **out, Origin org = Origin::host) {
+        DevIo<C> io(c, org);
+        RET(io.array(w_ccs, c->P.wit_len));
         W *a, *b, *d;
         RET(c->tbuf("io_a", (size_t)c->P.wit_len * RE, &a));
         RET(c->tbuf("io_b", (size_t)c->P.wit_len * RE, &b));
         RET(c->tbuf("io_c", c->N * RE, &d));
-        RET(up_ring(c, w_ccs, c->P.wit_len, a));
+        RET(io.begin());
+        RET(up_ring(io, w_ccs, c->P.wit_len, a));
         launch_icrt_dense(c->d_icrt, a, b, c->P.wit_len, c->stream());
         launch_decompose(b, c->P.wit_len, c->P.B, c->P.L, 0, d, c->stream(), c->digit_mode);
-        return witness_from_coef_table(c, d, out);
+        return witness_from_coef_table(c, d, out, &io);
     }
-    static int witness_from_w_ccs(C *c, const u64 *w_ccs, lf_witness **out) {
+    static int witness_from_w_ccs(C *c, const u64 *w_ccs, lf_witness **out, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         if (!c->have_ccs) return LF_ERR_STATE;
         HIPCHK(hipSetDevice(c->device));
-        return witness_from_w_ccs_lane(c, w_ccs, out);
+        return witness_from_w_ccs_lane(c, w_ccs, out, org);
     }
-    static int witness_from_f_coeff(C *c, const u64 *f_coeff, lf_witness **out) {
+    static int witness_from_f_coeff(C *c, const u64 *f_coeff, lf_witness **out, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         if (!c->have_ccs) return LF_ERR_STATE;
         HIPCHK(hipSetDevice(c->device));
+        DevIo<C> io(c, org);
+        RET(io.array(f_coeff, c->N));
         W *d;
         RET(c->tbuf("io_c", c->N * RE, &d));
-        RET(up_ring(c, f_coeff, c->N, d));
-        return witness_from_coef_table(c, d, out);
+        RET(io.begin());
+        RET(up_ring(io, f_coeff, c->N, d));
+        return witness_from_coef_table(c, d, out, &io);
     }
-    static int witness_from_f(C *c, const u64 *f_ntt, lf_witness **out) {
+    static int witness_from_f(C *c, const u64 *f_ntt, lf_witness **out, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         if (!c->have_ccs) return LF_ERR_STATE;
         HIPCHK(hipSetDevice(c->device));
+        DevIo<C> io(c, org);
+        RET(io.array(f_ntt, c->N));
         W *a, *d;
         RET(c->tbuf("io_a", c->N * RE, &a));
         RET(c->tbuf("io_c", c->N * RE, &d));
-        RET(up_ring(c, f_ntt, c->N, a));
+        RET(io.begin());
+        RET(up_ring(io, f_ntt, c->N, a));
         launch_icrt_dense(c->d_icrt, a, d, c->N, c->stream());
-        return witness_from_coef_table(c, d, out);
+        return witness_from_coef_table(c, d, out, &io);
     }
-    static int witness_get_f_coeff(C *c, const lf_witness *w, u64 *out) {
+    static int witness_get_f_coeff(C *c, const lf_witness *w, u64 *out, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         HIPCHK(hipSetDevice(c->device));
+        DevIo<C> io(c, org);
+        RET(io.array(out, w->N));
         W *d;
         RET(c->tbuf("io_c", w->N * RE, &d));
         launch_i32_to_coef(w->planes, d, w->N, c->stream());
-        return down_ring(c, d, w->N, out);
+        return down_ring(io, d, w->N, out);
     }
-    static int witness_get_f(C *c, const lf_witness *w, u64 *out) {
+    static int witness_get_f(C *c, const lf_witness *w, u64 *out, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         HIPCHK(hipSetDevice(c->device));
-        if (w->f_ntt) return down_ring(c, (const W *)w->f_ntt, w->N, out);      // built inside the fold step that produced this witness
+        DevIo<C> io(c, org);
+        RET(io.array(out, w->N));
+        if (w->f_ntt) return down_ring(io, (const W *)w->f_ntt, w->N, out);      // built inside the fold step that produced this witness
         W *d, *e;
         RET(c->tbuf("io_c", w->N * RE, &d));
         RET(c->tbuf("io_b", w->N * RE, &e));
         launch_i32_to_coef(w->planes, d, w->N, c->stream());
         launch_crt_fwd(R::tab(c), d, e, w->N, c->stream());
-        return down_ring(c, e, w->N, out);
+        return down_ring(io, e, w->N, out);
     }
-    static int witness_get_w_ccs(C *c, const lf_witness *w, u64 *out) {
+    static int witness_get_w_ccs(C *c, const lf_witness *w, u64 *out, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         if (!c->have_ccs) return LF_ERR_STATE;
         HIPCHK(hipSetDevice(c->device));
-        if (w->w_ccs && w->w_bytes == (size_t)c->P.wit_len * RE * sizeof(W)) return down_ring(c, (const W *)w->w_ccs, c->P.wit_len, out);
+        DevIo<C> io(c, org);
+        RET(io.array(out, c->P.wit_len));
+        if (w->w_ccs && w->w_bytes == (size_t)c->P.wit_len * RE * sizeof(W)) return down_ring(io, (const W *)w->w_ccs, c->P.wit_len, out);
         W *e;
         RET(c->tbuf("io_b", (size_t)c->P.wit_len * RE, &e));
         launch_recompose_crt(R::tab(c), w->planes, w->N, c->P.wit_len, c->P.L, c->P.B, 1, 0, e, c->P.wit_len, 0, c->stream());
-        return down_ring(c, e, c->P.wit_len, out);
+        return down_ring(io, e, c->P.wit_len, out);
     }
     static int witness_commit(C *c, const lf_witness *w, u64 *cm_out) {
         std::lock_guard<std::mutex> g(c->mu);
@@ -912,7 +1007,9 @@ using lfring::ring_ops;
 using lfring::commit_dev_i8g;
 using lfring::commit_dev_pre;
 using lfring::commit_planes_i8;
+using lfring::DevIo;
 using lfring::down_ring;
+using lfring::Origin;
 using lfring::pow2;
 using lfring::up_ring;
 using lfring::upload_consts;

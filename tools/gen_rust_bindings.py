@@ -107,7 +107,8 @@ def defines(path):
 
 def generate():
     L = ["// GENERATED by tools/gen_rust_bindings.py from include/lfhip.h and include/lfplus.h -- do not edit.",
-         "// latticefold-hip-sys: raw binding of liblfhip.so (MI355X / gfx950).  Every pointer is a HOST pointer; every `c_int` result is 0 or a",
+         "// latticefold-hip-sys: raw binding of liblfhip.so (MI355X / gfx950).  Every pointer is a HOST pointer, except the array arguments of",
+         "// the lf_*_dev entry points (the caller's device memory: lfhip.h, \"device-resident callers\"); every `c_int` result is 0 or a",
          "// negative LF_ERR_* / LFPLUS_E_* code.  The comments of the headers are the documentation.",
          "#![allow(non_camel_case_types, non_upper_case_globals, non_snake_case)]",
          "use core::ffi::{c_char, c_int, c_uint, c_void};", ""]
