@@ -89,8 +89,13 @@ int lf_get_ring_tables(lf_ctx *, uint64_t *nonres, uint64_t *y);
  * F_{p^tau} challenge crossing this ABI is in EXTERNAL coordinates -- inputs are converted on entry, outputs on exit -- and the
  * Fiat-Shamir transcript absorbs / squeezes external coordinates, so proofs are those of a prover computing natively in that basis.
  * The multiplication (structure) tensor the caller's field has is then T applied to the binomial one; tools/probe_stark_rings.rs prints
- * it.  Identity T switches the feature off (default; no cost).  LF_ERR_BAD_TABLES if T is singular or does not fix 1.  lf_verify_host
- * keeps the default basis. */
+ * it.  Identity T switches the feature off (default; no cost).  LF_ERR_BAD_TABLES if T is singular or does not fix 1 (the basis in
+ * force stays).  Where the conversion runs: the O(n) arrays in NTT form (lf_ntt_fwd out / lf_ntt_inv in, lf_linf_check, the matrix of
+ * lf_ajtai_load, the input of the NTT-form commits, the tables of lf_mle_eval_batch / lf_sumcheck_*_begin / lf_lincomb / lf_horner_combine,
+ * z and out of lf_spmv, z of lf_ccs_check, lf_witness_from_{w_ccs,f} and lf_witness_get_{f,w_ccs}) change basis on the DEVICE, in the
+ * relayout kernel that reads or writes them, for host pointers and for the _dev twins alike; T and T^-1 are kept in the device word
+ * form and refreshed by every call of this function.  Small data (instances, proofs, commitments, challenges, sumcheck messages, the
+ * CSR values of lf_ccs_load) is converted on the host.  Coefficient-form arrays have no basis.  lf_verify_host keeps the default basis. */
 int lf_set_ext_basis(lf_ctx *, const uint64_t *T);
 /* The balanced-digit rule of stark_rings::balanced_decomposition, the third unpinned convention, as data: mode 0 (default) = truncate
  * toward zero and move |rem| > base/2 to the other side (ties +-base/2 keep the sign of the value); mode 1 = floor rule, digits in
@@ -353,7 +358,9 @@ int lf_lcccs_check(lf_ctx *, const uint64_t *lcccs, const lf_witness *wit, uint6
  * it, without blocking the host and without touching `stream` otherwise.  A _dev call returns after the context's stream is synchronised, like its host twin:
  * device outputs are complete and the input buffer is free for reuse on return (witness handles own their planes).
  *   Sharded and small-base contexts accept a _dev call wherever they accept its twin (lf_ccs_check_dev on a sharded context: LF_ERR_UNSUPPORTED, like
- * lf_ccs_check).  A context with an external basis (lf_set_ext_basis) answers LF_ERR_UNSUPPORTED: that conversion is host code. */
+ * lf_ccs_check).  A context with an external basis (lf_set_ext_basis) accepts them too: the caller's array is read and written in EXTERNAL coordinates, in
+ * place, converted by the relayout kernel that reads or writes it -- the same pointer checks, the canonical test on the caller's own (external) words before
+ * any arithmetic, and an output that stays untouched on LF_ERR_INVALID.  Coefficient-form arrays (f_coeff, the input of commit_coeff) have no basis. */
 int lf_ctx_wait_stream(lf_ctx *, void *hip_stream);
 int lf_ntt_fwd_dev(lf_ctx *, const uint64_t *in, uint64_t *out, size_t count);
 int lf_ntt_inv_dev(lf_ctx *, const uint64_t *in, uint64_t *out, size_t count);

@@ -61,8 +61,30 @@ size_t red_partial_words(u32 nv) { return (size_t)RED_BLOCKS * nv; }
 // layout + Montgomery conversion at the ABI
 // CHECKED: the source is a caller's own device buffer (the _dev entry points), read in place, and every word is validated: a wave that saw a word >= p sets
 // *flag -- one vector atomic by its lowest lane after a ballot (every lane of the block runs the same 18 trips, so the ballot sees whole waves)
-template <bool CHECKED>
-__device__ __forceinline__ void aos_to_soa_tile(const u64 *aos, fe *soa, size_t n, u32 *flag) {
+// XBASIS: the context is in an external basis of F_{p^9} (lf_set_ext_basis).  Between the two passes over the tile every (element, slot) -- 64 x 8 jobs, two per
+// thread -- is multiplied by the 9 x 9 matrix M (wave-uniform: a kernel argument of centred Montgomery words), in place in the tile: M = T^-1 on the way in,
+// after the canonical test has seen the caller's own words, M = T on the way out, before the AoS write.  Lane <-> element, as in the plane pass: the odd row
+// length keeps the 32 lanes of a half on distinct banks; wave w takes slots w and w + 4.  Column 0 of M is e_0 (ExtBasis::set): a row is eight centred products,
+// 8 H^2 < 2^63, summed in one signed 64-bit register and Montgomery-reduced once -- (M v)~ from M~ and v~.  The row loop stays rolled and serves both jobs of
+// the thread: eight matrix words are live in SGPRs at a time, not all 72 (which spill)
+__device__ __forceinline__ void xb_slot_pass(fe (*tile)[RE + 1], const XbMat9 &M) {
+    fe *p0 = &tile[threadIdx.x % 64][TAU * (threadIdx.x / 64)], *p1 = p0 + TAU * 4;
+    fe a[TAU], b[TAU];
+#pragma unroll
+    for (int j = 0; j < TAU; j++) { a[j] = p0[j]; b[j] = p1[j]; }
+#pragma unroll 1
+    for (int i = 0; i < TAU; i++) {
+        const fe *row = M.m + TAU * i;
+        i64 s0 = 0, s1 = 0;
+#pragma unroll
+        for (int j = 1; j < TAU; j++) { s0 += (i64)row[j] * (i64)a[j]; s1 += (i64)row[j] * (i64)b[j]; }
+        const fe r0 = mred(s0), r1 = mred(s1);
+        p0[i] = i ? r0 : fadd(r0, a[0]);
+        p1[i] = i ? r1 : fadd(r1, b[0]);
+    }
+}
+template <bool CHECKED, bool XBASIS = false>
+__device__ __forceinline__ void aos_to_soa_tile(const u64 *aos, fe *soa, size_t n, u32 *flag, const XbMat9 *M = nullptr) {
     __shared__ fe tile[64][RE + 1];
     size_t base = (size_t)blockIdx.x * 64;
     bool bad = false;
@@ -76,12 +98,17 @@ __device__ __forceinline__ void aos_to_soa_tile(const u64 *aos, fe *soa, size_t 
         if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
     }
     __syncthreads();
+    if (XBASIS) {
+        xb_slot_pass(tile, *M);
+        __syncthreads();
+    }
     for (int idx = threadIdx.x; idx < 64 * RE; idx += 256) {
         int w = idx / 64, j = idx % 64;
         if (base + j < n) soa[(size_t)w * n + base + j] = tile[j][w];
     }
 }
-__device__ __forceinline__ void soa_to_aos_tile(const fe *soa, u64 *aos, size_t n) {
+template <bool XBASIS = false>
+__device__ __forceinline__ void soa_to_aos_tile(const fe *soa, u64 *aos, size_t n, const XbMat9 *M = nullptr) {
     __shared__ fe tile[64][RE + 1];
     size_t base = (size_t)blockIdx.x * 64;
     for (int idx = threadIdx.x; idx < 64 * RE; idx += 256) {
@@ -89,6 +116,10 @@ __device__ __forceinline__ void soa_to_aos_tile(const fe *soa, u64 *aos, size_t 
         tile[j][w] = base + j < n ? soa[(size_t)w * n + base + j] : 0;
     }
     __syncthreads();
+    if (XBASIS) {
+        xb_slot_pass(tile, *M);
+        __syncthreads();
+    }
     for (int idx = threadIdx.x; idx < 64 * RE; idx += 256) {
         size_t e = base + idx / RE;
         if (e < n) aos[e * RE + idx % RE] = to_canon(tile[idx / RE][idx % RE]);
@@ -102,6 +133,16 @@ __global__ void __launch_bounds__(256) k_soa_to_aos_unless(const fe *soa, u64 *a
     if (*flag) return;
     soa_to_aos_tile(soa, aos, n);
 }
+// the same four for a context in an external basis: Ti = T^-1 inbound, T outbound
+__global__ void __launch_bounds__(256) k_aos_to_soa_xb(const u64 *aos, fe *soa, size_t n, XbMat9 Ti) { aos_to_soa_tile<false, true>(aos, soa, n, nullptr, &Ti); }
+__global__ void __launch_bounds__(256) k_aos_to_soa_checked_xb(const u64 *aos, fe *soa, size_t n, u32 *flag, XbMat9 Ti) {
+    aos_to_soa_tile<true, true>(aos, soa, n, flag, &Ti);
+}
+__global__ void __launch_bounds__(256) k_soa_to_aos_xb(const fe *soa, u64 *aos, size_t n, XbMat9 T) { soa_to_aos_tile<true>(soa, aos, n, &T); }
+__global__ void __launch_bounds__(256) k_soa_to_aos_unless_xb(const fe *soa, u64 *aos, size_t n, const u32 *flag, XbMat9 T) {
+    if (*flag) return;
+    soa_to_aos_tile<true>(soa, aos, n, &T);
+}
 void launch_aos_to_soa(const u64 *aos, fe *soa, size_t n, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_aos_to_soa, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n);
 }
@@ -113,6 +154,18 @@ void launch_aos_to_soa_checked(const u64 *aos, fe *soa, size_t n, u32 *flag, hip
 }
 void launch_soa_to_aos_unless(const fe *soa, u64 *aos, size_t n, const u32 *flag, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_soa_to_aos_unless, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n, flag);
+}
+void launch_aos_to_soa_xb(const u64 *aos, fe *soa, size_t n, const XbMat9 &Ti, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_aos_to_soa_xb, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n, Ti);
+}
+void launch_soa_to_aos_xb(const fe *soa, u64 *aos, size_t n, const XbMat9 &T, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_soa_to_aos_xb, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n, T);
+}
+void launch_aos_to_soa_checked_xb(const u64 *aos, fe *soa, size_t n, u32 *flag, const XbMat9 &Ti, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_aos_to_soa_checked_xb, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n, flag, Ti);
+}
+void launch_soa_to_aos_unless_xb(const fe *soa, u64 *aos, size_t n, const u32 *flag, const XbMat9 &T, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_soa_to_aos_unless_xb, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n, flag, T);
 }
 // workload.py splitmix_fq(ring="babybear"): top 32 bits of SplitMix64 word (index+1), mod p
 __device__ __forceinline__ u64 splitmix_bb(u64 seed, u64 index) {

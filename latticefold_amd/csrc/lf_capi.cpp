@@ -121,7 +121,21 @@ int lf_set_ext_basis(lf_ctx *c, const uint64_t *T) {
     if (!c || !T) return LF_ERR_INVALID;
     std::lock_guard<std::mutex> g(c->mu);
     const int ring = lf_ctx_ring(c);
-    return c->xb.set(T, lf_ring_tau(ring), lf_ring_modulus(ring));
+    ExtBasis nb = c->xb;
+    RET(nb.set(T, lf_ring_tau(ring), lf_ring_modulus(ring)));   // (a refused matrix leaves the basis in force, on the host and on the device, as it was)
+    c->xb = nb;
+    // the copies the relayout kernels take, in the ring's device word form
+    const int tt = nb.tau * nb.tau;
+    if (c->bb) {
+        lfbb::BbCtxImpl *b = c->bb->p;
+        std::lock_guard<std::mutex> gb(b->mu);
+        b->xb_on = nb.on;
+        for (int i = 0; i < tt; i++) { b->xb_T[i] = lfbb::from_canon(nb.T[i]); b->xb_Ti[i] = lfbb::from_canon(nb.Ti[i]); }
+    } else {
+        c->xb_on = nb.on;
+        for (int i = 0; i < tt; i++) { c->xb_T[i] = nb.T[i]; c->xb_Ti[i] = nb.Ti[i]; }
+    }
+    return LF_OK;
 }
 int lf_set_sharding(lf_ctx *c, int rank, int world, lf_exchange_fn cb, void *user) {
     if (!c || world < 1 || rank < 0 || rank >= world || (world & (world - 1)) != 0 || (world > 1 && !cb)) return LF_ERR_INVALID;
@@ -457,29 +471,28 @@ int lf_selftest_field(lf_ctx *c, uint64_t seed, uint32_t n, uint64_t *mismatches
 
 // ---- a1/a2 --------------------------------------------------------------------------------------------------------
 int lf_ntt_fwd(lf_ctx *c, const uint64_t *in, uint64_t *out, size_t count) {
-    if (LF_XB(c)) { XB x(c); int rc = lf_ntt_fwd(c, in, out, count); if (rc == LF_OK) x.ring_out(out, count); return rc; }
+    XbArrays xa(c);
     if (!c || (!in && count) || (!out && count)) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::ntt_fwd(c->bb->p, in, out, count) : ring_ops<GoldRing>::ntt_fwd(c, in, out, count);
 }
 int lf_ntt_inv(lf_ctx *c, const uint64_t *in, uint64_t *out, size_t count) {
-    if (LF_XB(c) && in) { XB x(c); return lf_ntt_inv(c, x.ring_in(in, count), out, count); }
+    XbArrays xa(c);
     if (!c || (!in && count) || (!out && count)) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::ntt_inv(c->bb->p, in, out, count) : ring_ops<GoldRing>::ntt_inv(c, in, out, count);
 }
-// ---- the _dev twins (include/lfhip.h "device-resident callers"): the same bodies with Origin::device.  Here: the null checks of the host twin; a context in an
-// external basis refuses them (the conversion is host code).  The pointer checks proper -- dev_array_check, lf_ring_host.h -- run inside the body, after its
-// state and length checks and before its first launch
-#define LF_DEV_XB(c) do { if (LF_XB(c)) return LF_ERR_UNSUPPORTED; } while (0)
+// ---- the _dev twins (include/lfhip.h "device-resident callers"): the same bodies with Origin::device.  Here: the null checks of the host twin; on a context in
+// an external basis the caller's array is read and written in external coordinates, like the host twin's (XbArrays: the relayout kernels convert).  The pointer
+// checks proper -- dev_array_check, lf_ring_host.h -- run inside the body, after its state and length checks and before its first launch
 // in and out of `words` words each: the same array or disjoint ones
 static bool same_or_disjoint(const uint64_t *in, const uint64_t *out, size_t words) { return in == out || in + words <= out || out + words <= in; }
 int lf_ntt_fwd_dev(lf_ctx *c, const uint64_t *in, uint64_t *out, size_t count) {
     if (!c || (!in && count) || (!out && count) || !same_or_disjoint(in, out, count * lf_ring_words(lf_ctx_ring(c)))) return LF_ERR_INVALID;
-    LF_DEV_XB(c);
+    XbArrays xa(c);
     return c->bb ? ring_ops<BbRing>::ntt_fwd(c->bb->p, in, out, count, Origin::device) : ring_ops<GoldRing>::ntt_fwd(c, in, out, count, Origin::device);
 }
 int lf_ntt_inv_dev(lf_ctx *c, const uint64_t *in, uint64_t *out, size_t count) {
     if (!c || (!in && count) || (!out && count) || !same_or_disjoint(in, out, count * lf_ring_words(lf_ctx_ring(c)))) return LF_ERR_INVALID;
-    LF_DEV_XB(c);
+    XbArrays xa(c);
     return c->bb ? ring_ops<BbRing>::ntt_inv(c->bb->p, in, out, count, Origin::device) : ring_ops<GoldRing>::ntt_inv(c, in, out, count, Origin::device);
 }
 // Order the context's lanes behind the work enqueued so far on a stream of the caller's: an event recorded there, waited for by every lane.  The host does not
@@ -506,14 +519,14 @@ int lf_recompose(lf_ctx *c, const uint64_t *in, size_t count_out, uint64_t base,
     return c->bb ? ring_ops<BbRing>::recompose(c->bb->p, in, count_out, base, digits, out) : ring_ops<GoldRing>::recompose(c, in, count_out, base, digits, out);
 }
 int lf_linf_check(lf_ctx *c, const uint64_t *f_ntt, size_t count, uint64_t bound, int unsigned_variant, int *ok, uint64_t *max_out) {
-    if (LF_XB(c) && f_ntt) { XB x(c); return lf_linf_check(c, x.ring_in(f_ntt, count), count, bound, unsigned_variant, ok, max_out); }
+    XbArrays xa(c);
     if (!c || !f_ntt || !ok) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::linf_check(c->bb->p, f_ntt, count, bound, unsigned_variant, ok, max_out) : ring_ops<GoldRing>::linf_check(c, f_ntt, count, bound, unsigned_variant, ok, max_out);
 }
 
 // ---- a5 -----------------------------------------------------------------------------------------------------------
 int lf_ajtai_load(lf_ctx *c, const uint64_t *A, size_t kappa, size_t n) {
-    if (LF_XB(c) && A && kappa <= 128) { XB x(c); return lf_ajtai_load(c, x.ring_in(A, kappa * n), kappa, n); }
+    XbArrays xa(c);
     if (!c || !A || !kappa || !n || kappa > 128) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::ajtai_install(c->bb->p, kappa, n, A, 0) : ring_ops<GoldRing>::ajtai_install(c, kappa, n, A, 0);
 }
@@ -630,8 +643,8 @@ int gather_parts(lf_ctx *c, const GatherPart *parts, int np, size_t lcl) {
 }
 int lf_ajtai_commit(lf_ctx *c, const uint64_t *f, size_t n, size_t batch, uint64_t *out) {
     if (LF_XB(c) && f && out) {
-        XB x(c);
-        int rc = lf_ajtai_commit(c, x.ring_in(f, n * batch), n, batch, out);
+        XB x(c, true);   // f changes basis on the device; the commitments are small: on the host
+        int rc = lf_ajtai_commit(c, f, n, batch, out);
         if (rc == LF_OK) x.ring_out(out, batch * c->core_any().kappa);
         return rc;
     }
@@ -640,18 +653,22 @@ int lf_ajtai_commit(lf_ctx *c, const uint64_t *f, size_t n, size_t batch, uint64
 }
 int lf_ajtai_commit_dev(lf_ctx *c, const uint64_t *f, size_t n, size_t batch, uint64_t *out) {
     if (!c || !f || !out || !batch) return LF_ERR_INVALID;
-    LF_DEV_XB(c);
+    if (LF_XB(c)) {
+        XB x(c, true);
+        int rc = lf_ajtai_commit_dev(c, f, n, batch, out);
+        if (rc == LF_OK) x.ring_out(out, batch * c->core_any().kappa);
+        return rc;
+    }
     return c->bb ? ring_ops<BbRing>::ajtai_commit(c->bb->p, f, n, batch, out, Origin::device) : ring_ops<GoldRing>::ajtai_commit(c, f, n, batch, out, Origin::device);
 }
 // The ABI side of the three (dec false: commit_coeff, no decomposition): arguments are checked before any device work; in an external basis the commitments
 // leave converted and NTT-form input is converted on the way in, coefficient-form input is not (as lf_witness_from_f_coeff).
 static int ajtai_commit_gadget_api(lf_ctx *c, const uint64_t *f, bool ntt_in, size_t count, bool dec, uint64_t base, unsigned digits, size_t batch, uint64_t *out,
                                    Origin org = Origin::host) {
-    if (org == Origin::device) LF_DEV_XB(c);
     if (LF_XB(c) && f && out) {
-        XB x(c);
+        XB x(c, true);   // (the body stages NTT-form input as Form::ntt, coefficient-form input as Form::coeff)
         const u32 kap = c->core_any().kappa;
-        int rc = ajtai_commit_gadget_api(c, ntt_in ? x.ring_in(f, count * batch) : f, ntt_in, count, dec, base, digits, batch, out);
+        int rc = ajtai_commit_gadget_api(c, f, ntt_in, count, dec, base, digits, batch, out, org);
         if (rc == LF_OK) x.ring_out(out, batch * kap);
         return rc;
     }
@@ -735,8 +752,8 @@ int lf_build_eq(lf_ctx *c, const uint64_t *point, unsigned nv, uint64_t *out) {
 }
 int lf_mle_eval_batch(lf_ctx *c, const uint64_t *tables, size_t ntables, size_t len, const uint64_t *point, unsigned nv, uint64_t *out) {
     if (LF_XB(c) && tables && point && out) {
-        XB x(c);
-        int rc = lf_mle_eval_batch(c, x.ring_in(tables, ntables * len), ntables, len, x.ext_in(point, nv), nv, out);
+        XB x(c, true);
+        int rc = lf_mle_eval_batch(c, tables, ntables, len, x.ext_in(point, nv), nv, out);
         if (rc == LF_OK) x.ring_out(out, ntables);
         return rc;
     }
@@ -780,7 +797,7 @@ int lf_ccs_load(lf_ctx *c, const lf_params *p, const uint32_t *const *rowptr, co
     return ring_ops<GoldRing>::ccs_load(c, p, rowptr, col, val, S_off, S_idx, cc);
 }
 int lf_spmv(lf_ctx *c, unsigned j, const uint64_t *z, uint64_t *out) {
-    if (LF_XB(c) && z && out && c->have_ccs_any()) { XB x(c); int rc = lf_spmv(c, j, x.ring_in(z, c->n_any()), out); if (rc == LF_OK) x.ring_out(out, c->m_any()); return rc; }
+    XbArrays xa(c);
     if (!c || !z || !out) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::spmv(c->bb->p, j, z, out) : ring_ops<GoldRing>::spmv(c, j, z, out);
 }
@@ -818,7 +835,7 @@ int lf_witness_job_finish(lf_witness_job *job, lf_witness **out) {
     return rc;
 }
 int lf_witness_from_w_ccs(lf_ctx *c, const uint64_t *w_ccs, lf_witness **out) {
-    if (LF_XB(c) && w_ccs && c->have_ccs_any()) { XB x(c); return lf_witness_from_w_ccs(c, x.ring_in(w_ccs, c->params_any().wit_len), out); }
+    XbArrays xa(c);
     if (!c || !w_ccs || !out) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::witness_from_w_ccs(c->bb->p, w_ccs, out) : ring_ops<GoldRing>::witness_from_w_ccs(c, w_ccs, out);
 }
@@ -827,7 +844,7 @@ int lf_witness_from_f_coeff(lf_ctx *c, const uint64_t *f_coeff, lf_witness **out
     return c->bb ? ring_ops<BbRing>::witness_from_f_coeff(c->bb->p, f_coeff, out) : ring_ops<GoldRing>::witness_from_f_coeff(c, f_coeff, out);
 }
 int lf_witness_from_f(lf_ctx *c, const uint64_t *f_ntt, lf_witness **out) {
-    if (LF_XB(c) && f_ntt && c->have_ccs_any()) { XB x(c); return lf_witness_from_f(c, x.ring_in(f_ntt, c->N_any()), out); }
+    XbArrays xa(c);
     if (!c || !f_ntt || !out) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::witness_from_f(c->bb->p, f_ntt, out) : ring_ops<GoldRing>::witness_from_f(c, f_ntt, out);
 }
@@ -836,43 +853,43 @@ int lf_witness_get_f_coeff(lf_ctx *c, const lf_witness *w, uint64_t *out) {
     return c->bb ? ring_ops<BbRing>::witness_get_f_coeff(c->bb->p, w, out) : ring_ops<GoldRing>::witness_get_f_coeff(c, w, out);
 }
 int lf_witness_get_f(lf_ctx *c, const lf_witness *w, uint64_t *out) {
-    if (LF_XB(c) && w && out) { XB x(c); int rc = lf_witness_get_f(c, w, out); if (rc == LF_OK) x.ring_out(out, w->N); return rc; }
+    XbArrays xa(c);
     if (!c || !w || !out || w->ctx != c) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::witness_get_f(c->bb->p, w, out) : ring_ops<GoldRing>::witness_get_f(c, w, out);
 }
 int lf_witness_get_w_ccs(lf_ctx *c, const lf_witness *w, uint64_t *out) {
-    if (LF_XB(c) && w && out && c->have_ccs_any()) { XB x(c); int rc = lf_witness_get_w_ccs(c, w, out); if (rc == LF_OK) x.ring_out(out, c->params_any().wit_len); return rc; }
+    XbArrays xa(c);
     if (!c || !w || !out || w->ctx != c) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::witness_get_w_ccs(c->bb->p, w, out) : ring_ops<GoldRing>::witness_get_w_ccs(c, w, out);
 }
 int lf_witness_from_w_ccs_dev(lf_ctx *c, const uint64_t *w_ccs, lf_witness **out) {
     if (!c || !w_ccs || !out) return LF_ERR_INVALID;
-    LF_DEV_XB(c);
+    XbArrays xa(c);
     return c->bb ? ring_ops<BbRing>::witness_from_w_ccs(c->bb->p, w_ccs, out, Origin::device) : ring_ops<GoldRing>::witness_from_w_ccs(c, w_ccs, out, Origin::device);
 }
 int lf_witness_from_f_coeff_dev(lf_ctx *c, const uint64_t *f_coeff, lf_witness **out) {
     if (!c || !f_coeff || !out) return LF_ERR_INVALID;
-    LF_DEV_XB(c);
+    XbArrays xa(c);
     return c->bb ? ring_ops<BbRing>::witness_from_f_coeff(c->bb->p, f_coeff, out, Origin::device) : ring_ops<GoldRing>::witness_from_f_coeff(c, f_coeff, out, Origin::device);
 }
 int lf_witness_from_f_dev(lf_ctx *c, const uint64_t *f_ntt, lf_witness **out) {
     if (!c || !f_ntt || !out) return LF_ERR_INVALID;
-    LF_DEV_XB(c);
+    XbArrays xa(c);
     return c->bb ? ring_ops<BbRing>::witness_from_f(c->bb->p, f_ntt, out, Origin::device) : ring_ops<GoldRing>::witness_from_f(c, f_ntt, out, Origin::device);
 }
 int lf_witness_get_f_coeff_dev(lf_ctx *c, const lf_witness *w, uint64_t *out) {
     if (!c || !w || !out || w->ctx != c) return LF_ERR_INVALID;
-    LF_DEV_XB(c);
+    XbArrays xa(c);
     return c->bb ? ring_ops<BbRing>::witness_get_f_coeff(c->bb->p, w, out, Origin::device) : ring_ops<GoldRing>::witness_get_f_coeff(c, w, out, Origin::device);
 }
 int lf_witness_get_f_dev(lf_ctx *c, const lf_witness *w, uint64_t *out) {
     if (!c || !w || !out || w->ctx != c) return LF_ERR_INVALID;
-    LF_DEV_XB(c);
+    XbArrays xa(c);
     return c->bb ? ring_ops<BbRing>::witness_get_f(c->bb->p, w, out, Origin::device) : ring_ops<GoldRing>::witness_get_f(c, w, out, Origin::device);
 }
 int lf_witness_get_w_ccs_dev(lf_ctx *c, const lf_witness *w, uint64_t *out) {
     if (!c || !w || !out || w->ctx != c) return LF_ERR_INVALID;
-    LF_DEV_XB(c);
+    XbArrays xa(c);
     return c->bb ? ring_ops<BbRing>::witness_get_w_ccs(c->bb->p, w, out, Origin::device) : ring_ops<GoldRing>::witness_get_w_ccs(c, w, out, Origin::device);
 }
 int lf_witness_commit(lf_ctx *c, const lf_witness *w, uint64_t *cm_out) {

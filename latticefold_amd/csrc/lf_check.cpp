@@ -77,9 +77,10 @@ static int ccs_check(C *c, const u64 *z, u64 *first_bad, Origin org) {
     RET(c->tbuf("chk_od", 8, &od));
     u32 *w = (u32 *)od;
     RET(io.begin());
-    RET(up_ring(io, z, c->n, zd));
+    RET(up_ring(io, z, c->n, zd, Form::ntt));
     RET(check_words(c, w));
-    RET(ccs_residual(c, zd, w, io.dev ? z : nullptr));   // a device z is the element-major copy the general CSR rows gather from
+    // a device z is the element-major copy the general CSR rows gather from -- unless it is in an external basis: then the copy is rebuilt from the converted planes
+    RET(ccs_residual(c, zd, w, io.dev && !xb_converts(c, Form::ntt) ? z : nullptr));
     u32 h[2];
     RET(io.fetch());                                     // (travels with the download of the check words)
     RET(down_small(c, od, 1, (u64 *)h));
@@ -168,13 +169,13 @@ static int lcccs_check(C *c, const u64 *lcccs, const lf_witness *wit, u64 bound,
 }  // namespace lfring
 
 int lf_ccs_check(lf_ctx *c, const uint64_t *z, uint64_t *first_bad) {
-    if (LF_XB(c) && z && first_bad && c->have_ccs_any()) { XB x(c); return lf_ccs_check(c, x.ring_in(z, c->n_any()), first_bad); }
+    XbArrays xa(c);
     if (!c || !z || !first_bad) return LF_ERR_INVALID;
     return c->bb ? lfring::ccs_check(c->bb->p, z, first_bad, Origin::host) : lfring::ccs_check(c, z, first_bad, Origin::host);
 }
 int lf_ccs_check_dev(lf_ctx *c, const uint64_t *z, uint64_t *first_bad) {
     if (!c || !z || !first_bad) return LF_ERR_INVALID;
-    if (LF_XB(c)) return LF_ERR_UNSUPPORTED;   // device words are never converted between bases
+    XbArrays xa(c);
     return c->bb ? lfring::ccs_check(c->bb->p, z, first_bad, Origin::device) : lfring::ccs_check(c, z, first_bad, Origin::device);
 }
 

@@ -274,18 +274,29 @@ struct SideState {
     ~SideState() { if (z_ev) (void)hipEventDestroy(z_ev); }
 };
 int gather_parts(lf_ctx *c, const GatherPart *parts, int np, size_t lcl);
+// External basis at the ABI.  What is SMALL is converted here, on the host, by the wrapper at the head of an entry point (XB below): instances, proofs,
+// commitments, challenges and points, sumcheck messages, the CSR values of lf_ccs_load, and the transcript through its basis hook.  The O(n) ARRAYS in NTT form
+// are converted on the device, by the relayout kernels that move them between the caller's AoS words and the planes (up_ring / down_ring, lf_ring_host.h): the
+// wrapper of such an entry point -- host-pointer call or _dev twin -- opens XB with arrays = true, and the staging helpers convert an array of Form::ntt while
+// t_xb_arrays is up.  Everything a wrapper calls runs with t_xb_active up, so no inner entry point converts again; lf_fold_step and the sub-provers open XB
+// without arrays, so nothing they stage is converted either.
 inline thread_local bool t_xb_active = false;   // external-basis conversion in progress on this thread
+inline thread_local bool t_xb_arrays = false;   // ... and the NTT-form arrays of the running entry point change basis in its relayout kernels
 struct XB {
     lf_ctx *c;
     size_t RE, TAU;
     std::vector<std::unique_ptr<std::vector<u64>>> keep;
     lf_transcript *tr = nullptr;
-    explicit XB(lf_ctx *cc) : c(cc), RE((size_t)lf_ring_words(lf_ctx_ring(cc))), TAU((size_t)lf_ring_tau(lf_ctx_ring(cc))) { t_xb_active = true; }
+    explicit XB(lf_ctx *cc, bool arrays = false) : c(cc), RE((size_t)lf_ring_words(lf_ctx_ring(cc))), TAU((size_t)lf_ring_tau(lf_ctx_ring(cc))) {
+        t_xb_active = true;
+        t_xb_arrays = arrays;
+    }
     ~XB() {
         t_xb_active = false;
+        t_xb_arrays = false;
         if (tr) { tr->t.set_basis(nullptr, nullptr); if (tr->bb) tr->bb->set_basis(nullptr, nullptr); }
     }
-    const u64 *ring_in(const u64 *p, size_t elems) {   // NTT-form ring elements, external -> internal (copy)
+    const u64 *ring_in(const u64 *p, size_t elems) {   // a few NTT-form ring elements, external -> internal (copy)
         if (!p) return p;
         keep.emplace_back(new std::vector<u64>(p, p + elems * RE));
         c->xb.to_int(keep.back()->data(), elems * 8);
@@ -306,6 +317,13 @@ struct XB {
     }
 };
 #define LF_XB(c) ((c) && (c)->xb.on && !t_xb_active)
+// the whole wrapper of an entry point whose only basis-dependent arguments are O(n) arrays (host-pointer call or _dev twin): nothing is copied or converted on
+// the host, the relayout kernels of the body change the basis
+struct XbArrays {
+    const bool set;
+    explicit XbArrays(lf_ctx *c) : set(LF_XB(c)) { if (set) t_xb_active = t_xb_arrays = true; }
+    ~XbArrays() { if (set) t_xb_active = t_xb_arrays = false; }
+};
 int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out, lf_witness **w_out, u64 *proof);
 int commit_download(lf_ctx *c, const u64 *dev, size_t words, u64 *host);
 // small-base path: the NP part commitments y_k = A f_k of the digit planes D [NP][24][ldn] (lf_sb.h) in ONE pass over A -> out_dev [NP][kappa][24] NTT form

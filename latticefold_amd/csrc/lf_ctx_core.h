@@ -224,6 +224,10 @@ struct CtxCore : CtxCoreBase {
     uint32_t *d_icrt_sp_col = nullptr;
     std::vector<W *> d_val, d_valT;
     const W *vs_eq = nullptr;
+    // the external basis of the extension field (lf_set_ext_basis) as the basis-changing relayout kernels take it: T and T^-1, row-major tau x tau, in the ring's
+    // device word form, refreshed by every lf_set_ext_basis.  xb_on false (the identity, the default): the plain relayout kernels run
+    bool xb_on = false;
+    W xb_T[81] = {}, xb_Ti[81] = {};
     void free_ccs() {
         for (auto q : d_rowptr) (void)hipFree(q);
         for (auto q : d_col) (void)hipFree(q);

@@ -692,7 +692,7 @@ int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out,
 
 // ---- generic linearization-shaped sumcheck through the ABI (tests / SURVEY 8b) -------------------------------------------------
 int lf_sumcheck_lin_begin(lf_ctx *c, const uint64_t *tables, const uint64_t *eq_point) {
-    if (LF_XB(c) && tables && eq_point && c->have_ccs_any()) { XB x(c); const lf_params &P = c->params_any(); return lf_sumcheck_lin_begin(c, x.ring_in(tables, (size_t)P.t * c->m_any()), x.ext_in(eq_point, P.s)); }
+    if (LF_XB(c) && tables && eq_point && c->have_ccs_any()) { XB x(c, true); const lf_params &P = c->params_any(); return lf_sumcheck_lin_begin(c, tables, x.ext_in(eq_point, P.s)); }
     if (!c || !tables || !eq_point) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::sumcheck_lin_begin(c->bb->p, tables, eq_point) : ring_ops<GoldRing>::sumcheck_lin_begin(c, tables, eq_point);
 }
@@ -742,7 +742,7 @@ int lf_device_sponge(lf_ctx *c, const uint32_t *ops, size_t nops, const uint64_t
 
 // ---- the folding sumcheck through the ABI: the bodies and the layout of `tables` are in lf_ring_host.h (ring_ops::sumcheck_fold_*)
 int lf_sumcheck_fold_begin(lf_ctx *c, const uint64_t *tables, const uint64_t *mu) {
-    if (LF_XB(c) && tables && mu && c->have_ccs_any()) { XB x(c); const lf_params &P = c->params_any(); return lf_sumcheck_fold_begin(c, x.ring_in(tables, (size_t)(5 + 2 * P.K * x.TAU) * c->m_any()), x.ext_in(mu, 2 * P.K)); }
+    if (LF_XB(c) && tables && mu && c->have_ccs_any()) { XB x(c, true); const lf_params &P = c->params_any(); return lf_sumcheck_fold_begin(c, tables, x.ext_in(mu, 2 * P.K)); }
     if (!c || !tables || !mu) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::sumcheck_fold_begin(c->bb->p, tables, mu) : ring_ops<GoldRing>::sumcheck_fold_begin(c, tables, mu);
 }
@@ -758,14 +758,14 @@ int lf_sumcheck_fold_end(lf_ctx *c) {
 
 // compute_f_0 (nifs/folding.rs:258-268): out[j] = sum_i coef_i (.) tables_i[j] with ring-element coefficients (8 distinct slots)
 int lf_lincomb(lf_ctx *c, const uint64_t *coef, const uint64_t *tables, size_t n_terms, size_t len, uint64_t *out) {
-    if (LF_XB(c) && coef && tables && out) { XB x(c); int rc = lf_lincomb(c, x.ring_in(coef, n_terms), x.ring_in(tables, n_terms * len), n_terms, len, out); if (rc == LF_OK) x.ring_out(out, len); return rc; }
+    if (LF_XB(c) && coef && tables && out) { XB x(c, true); return lf_lincomb(c, x.ring_in(coef, n_terms), tables, n_terms, len, out); }
     if (!c || !coef || !tables || !out || !n_terms || !len) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::lincomb(c->bb->p, coef, tables, n_terms, len, out) : ring_ops<GoldRing>::lincomb(c, coef, tables, n_terms, len, out);
 }
 // calculate_challenged_mz_mle (nifs/folding.rs:208-226) and the f-hat half of prepare_g1_and_3_k_mles_list (folding/utils.rs:524-546):
 // out[x] = sum_{i<groups} sum_{j<per_group} c_i^{j+1} T_{i,j}[x] (the reference's Horner loop `mle += M; mle *= c_i` over j reversed)
 int lf_horner_combine(lf_ctx *c, const uint64_t *tables, size_t groups, size_t per_group, size_t len, const uint64_t *challenges, uint64_t *out) {
-    if (LF_XB(c) && tables && challenges && out) { XB x(c); int rc = lf_horner_combine(c, x.ring_in(tables, groups * per_group * len), groups, per_group, len, x.ext_in(challenges, groups), out); if (rc == LF_OK) x.ring_out(out, len); return rc; }
+    if (LF_XB(c) && tables && challenges && out) { XB x(c, true); return lf_horner_combine(c, tables, groups, per_group, len, x.ext_in(challenges, groups), out); }
     if (!c || !tables || !challenges || !out || !groups || !per_group || !len) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::horner_combine(c->bb->p, tables, groups, per_group, len, challenges, out)
                  : ring_ops<GoldRing>::horner_combine(c, tables, groups, per_group, len, challenges, out);

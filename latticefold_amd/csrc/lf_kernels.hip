@@ -68,8 +68,27 @@ void launch_gather_relayout_part(const u64 *all, u32 nranks, size_t planes_tot, 
 // layout
 // CHECKED: the source is a caller's own device buffer (the _dev entry points), read in place, and every word is validated: a wave that saw a word >= p sets
 // *flag -- one vector atomic by its lowest lane after a ballot (every lane of the block runs the same six trips, so the ballot sees whole waves)
-template <bool CHECKED>
-__device__ __forceinline__ void aos_to_soa_tile(const u64 *aos, u64 *soa, size_t n, u32 *flag) {
+// XBASIS: the context is in an external basis of F_{p^3} (lf_set_ext_basis).  Between the two passes over the tile every (element, slot) -- 64 x 8 jobs, two per
+// thread -- is multiplied by the 3 x 3 matrix M (wave-uniform: a kernel argument, held in SGPRs), in place in the tile: M = T^-1 on the way in, after the
+// canonical test has seen the caller's own words, M = T on the way out, before the AoS write.  Lane <-> element, as in the plane pass: the odd row length
+// keeps the 64-bit LDS accesses of a 32-lane half on distinct banks.  Column 0 of M is e_0 (ExtBasis::set), so a slot costs six products; two products of
+// words < 2^64 and their carry fit the 128-bit + carry accumulator, whatever the words are
+__device__ __forceinline__ void xb_slot_pass(u64 (*tile)[25], const XbMat3 &M) {
+    for (int idx = threadIdx.x; idx < 64 * 8; idx += 256) {
+        u64 *v = &tile[idx % 64][3 * (idx / 64)];
+        const u64 v0 = fq_canon(v[0]), v1 = v[1], v2 = v[2];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            Acc s;
+            acc_set(s, M.m[3 * i + 1], v1);
+            acc_mad(s, M.m[3 * i + 2], v2);
+            const u64 r = acc_reduce(s);
+            v[i] = i ? r : fq_add(r, v0);
+        }
+    }
+}
+template <bool CHECKED, bool XBASIS = false>
+__device__ __forceinline__ void aos_to_soa_tile(const u64 *aos, u64 *soa, size_t n, u32 *flag, const XbMat3 *M = nullptr) {
     __shared__ u64 tile[64][25];
     size_t base = (size_t)blockIdx.x * 64;
     bool bad = false;
@@ -83,12 +102,17 @@ __device__ __forceinline__ void aos_to_soa_tile(const u64 *aos, u64 *soa, size_t
         if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
     }
     __syncthreads();
+    if (XBASIS) {
+        xb_slot_pass(tile, *M);
+        __syncthreads();
+    }
     for (int idx = threadIdx.x; idx < 64 * 24; idx += 256) {
         int w = idx / 64, j = idx % 64;
         if (base + j < n) soa[(size_t)w * n + base + j] = tile[j][w];
     }
 }
-__device__ __forceinline__ void soa_to_aos_tile(const u64 *soa, u64 *aos, size_t n) {
+template <bool XBASIS = false>
+__device__ __forceinline__ void soa_to_aos_tile(const u64 *soa, u64 *aos, size_t n, const XbMat3 *M = nullptr) {
     __shared__ u64 tile[64][25];
     size_t base = (size_t)blockIdx.x * 64;
     for (int idx = threadIdx.x; idx < 64 * 24; idx += 256) {
@@ -96,6 +120,10 @@ __device__ __forceinline__ void soa_to_aos_tile(const u64 *soa, u64 *aos, size_t
         tile[j][w] = base + j < n ? soa[(size_t)w * n + base + j] : 0;
     }
     __syncthreads();
+    if (XBASIS) {
+        xb_slot_pass(tile, *M);
+        __syncthreads();
+    }
     for (int idx = threadIdx.x; idx < 64 * 24; idx += 256) {
         size_t e = base + idx / 24;
         if (e < n) aos[e * 24 + idx % 24] = tile[idx / 24][idx % 24];
@@ -109,6 +137,16 @@ __global__ void __launch_bounds__(256) k_soa_to_aos_unless(const u64 *soa, u64 *
     if (*flag) return;
     soa_to_aos_tile(soa, aos, n);
 }
+// the same four for a context in an external basis: Ti = T^-1 inbound, T outbound
+__global__ void __launch_bounds__(256) k_aos_to_soa_xb(const u64 *aos, u64 *soa, size_t n, XbMat3 Ti) { aos_to_soa_tile<false, true>(aos, soa, n, nullptr, &Ti); }
+__global__ void __launch_bounds__(256) k_aos_to_soa_checked_xb(const u64 *aos, u64 *soa, size_t n, u32 *flag, XbMat3 Ti) {
+    aos_to_soa_tile<true, true>(aos, soa, n, flag, &Ti);
+}
+__global__ void __launch_bounds__(256) k_soa_to_aos_xb(const u64 *soa, u64 *aos, size_t n, XbMat3 T) { soa_to_aos_tile<true>(soa, aos, n, &T); }
+__global__ void __launch_bounds__(256) k_soa_to_aos_unless_xb(const u64 *soa, u64 *aos, size_t n, const u32 *flag, XbMat3 T) {
+    if (*flag) return;
+    soa_to_aos_tile<true>(soa, aos, n, &T);
+}
 void launch_aos_to_soa(const u64 *aos, u64 *soa, size_t n, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_aos_to_soa, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n);
 }
@@ -120,6 +158,18 @@ void launch_aos_to_soa_checked(const u64 *aos, u64 *soa, size_t n, u32 *flag, hi
 }
 void launch_soa_to_aos_unless(const u64 *soa, u64 *aos, size_t n, const u32 *flag, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_soa_to_aos_unless, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n, flag);
+}
+void launch_aos_to_soa_xb(const u64 *aos, u64 *soa, size_t n, const XbMat3 &Ti, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_aos_to_soa_xb, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n, Ti);
+}
+void launch_soa_to_aos_xb(const u64 *soa, u64 *aos, size_t n, const XbMat3 &T, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_soa_to_aos_xb, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n, T);
+}
+void launch_aos_to_soa_checked_xb(const u64 *aos, u64 *soa, size_t n, u32 *flag, const XbMat3 &Ti, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_aos_to_soa_checked_xb, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n, flag, Ti);
+}
+void launch_soa_to_aos_unless_xb(const u64 *soa, u64 *aos, size_t n, const u32 *flag, const XbMat3 &T, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_soa_to_aos_unless_xb, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n, flag, T);
 }
 
 __device__ __forceinline__ u64 splitmix_fq(u64 seed, u64 index) {

@@ -57,6 +57,7 @@ template <> struct Ring<lf_ctx> {
     static constexpr const char *io_out = "io_b", *i8g_co = "i8g_coef";
     static const DevCrt &tab(const lf_ctx *c) { return c->dcrt; }
     static W from_canon(u64 w) { return w; }
+    static XbMat3 xb_mat(const W *m) { XbMat3 r; memcpy(r.m, m, sizeof(r.m)); return r; }   // lf_set_ext_basis: T or T^-1 as a kernel argument
     static void ring_from_u64(u64 v, u64 *o) { HostRing::from_u64(v, o); }
     // the bit-plane form of the witness `planes` belong to, if the running fold step built it for its GEMM rounds (lf_sv_rounds.h): the digit-plane commit
     // kernel then cuts the digits from it.  Null otherwise
@@ -112,6 +113,7 @@ template <> struct Ring<BbCtxImpl> {
     static constexpr const char *io_out = "io_o", *i8g_co = "i8g_co";
     static const DevBb &tab(const BbCtxImpl *c) { return c->dev; }
     static W from_canon(u64 w) { return lfbb::from_canon(w); }
+    static XbMat9 xb_mat(const W *m) { XbMat9 r; memcpy(r.m, m, sizeof(r.m)); return r; }
     static void ring_from_u64(u64 v, u64 *o) { BbHostRing::from_u64(v, o); }
     static int bit_planes(BbCtxImpl *, const int32_t *, const lf_witness *, const u32 **bits) { *bits = nullptr; return LF_OK; }   // no bit-plane form on this ring
     typedef FoldArgs FoldA;
@@ -156,22 +158,31 @@ typedef Ring<lf_ctx> GoldRing;
 typedef Ring<BbCtxImpl> BbRing;
 
 // ---- host<->device staging of AoS ring-element arrays (canonical u64 at the ABI) ---------------------------------------------------------------------
+// What the words of an array at the ABI are: Form::ntt -- NTT-form ring elements, eight slots of F_{p^tau}, presented in the context's external basis
+// (lf_set_ext_basis) -- or Form::coeff -- coefficients (lf_decompose / lf_recompose, f_coeff, the input of commit_coeff), which no basis touches.  On a context
+// in an external basis an NTT-form array of an entry point that converts (t_xb_arrays, lf_ctx.h) goes through the basis-changing relayout kernels; every other
+// array, and every array of a context in the default basis, goes through the plain ones.
+enum class Form { ntt, coeff };
+template <class C>
+inline bool xb_converts(const C *c, Form f) { return f == Form::ntt && c->xb_on && t_xb_arrays; }
 // upload n ring elements (AoS) into a plane table dst [RE][n]
 template <class C>
-int up_ring(C *c, const u64 *host, size_t n, typename Ring<C>::W *dst) {
+int up_ring(C *c, const u64 *host, size_t n, typename Ring<C>::W *dst, Form f) {
     if (!n) return LF_OK;
     u64 *tmp;
     RET(c->tbuf("stage_aos", n * Ring<C>::RE, &tmp));
     HIPCHK(hipMemcpyAsync(tmp, host, n * Ring<C>::RE * 8, hipMemcpyHostToDevice, c->stream()));
-    launch_aos_to_soa(tmp, dst, n, c->stream());
+    if (xb_converts(c, f)) launch_aos_to_soa_xb(tmp, dst, n, Ring<C>::xb_mat(c->xb_Ti), c->stream());
+    else launch_aos_to_soa(tmp, dst, n, c->stream());
     return LF_OK;
 }
 template <class C>
-int down_ring(C *c, const typename Ring<C>::W *src, size_t n, u64 *host) {
+int down_ring(C *c, const typename Ring<C>::W *src, size_t n, u64 *host, Form f) {
     if (!n) return LF_OK;
     u64 *tmp;
     RET(c->tbuf("stage_aos", n * Ring<C>::RE, &tmp));
-    launch_soa_to_aos(src, tmp, n, c->stream());
+    if (xb_converts(c, f)) launch_soa_to_aos_xb(src, tmp, n, Ring<C>::xb_mat(c->xb_T), c->stream());
+    else launch_soa_to_aos(src, tmp, n, c->stream());
     HIPCHK(hipMemcpyAsync(host, tmp, n * Ring<C>::RE * 8, hipMemcpyDeviceToHost, c->stream()));
     HIPCHK(hipStreamSynchronize(c->stream()));
     return LF_OK;
@@ -221,16 +232,21 @@ struct DevIo {
     bool bad() const { return flag && *(volatile u32 *)hflag != 0; }
 };
 template <class C>
-int up_ring(DevIo<C> &io, const u64 *src, size_t n, typename Ring<C>::W *dst) {
-    if (!io.dev) return up_ring(io.c, src, n, dst);
-    launch_aos_to_soa_checked(src, dst, n, io.flag, io.c->stream());
+int up_ring(DevIo<C> &io, const u64 *src, size_t n, typename Ring<C>::W *dst, Form f) {
+    if (!io.dev) return up_ring(io.c, src, n, dst, f);
+    if (xb_converts(io.c, f)) launch_aos_to_soa_checked_xb(src, dst, n, io.flag, Ring<C>::xb_mat(io.c->xb_Ti), io.c->stream());   // (the caller's words are tested, then converted)
+    else launch_aos_to_soa_checked(src, dst, n, io.flag, io.c->stream());
     return LF_OK;
 }
 // the result of a call, complete on return; from device inputs that were not canonical: LF_ERR_INVALID and `out` untouched
 template <class C>
-int down_ring(DevIo<C> &io, const typename Ring<C>::W *src, size_t n, u64 *out) {
-    if (!io.dev) return down_ring(io.c, src, n, out);
-    if (io.flag) launch_soa_to_aos_unless(src, out, n, io.flag, io.c->stream());
+int down_ring(DevIo<C> &io, const typename Ring<C>::W *src, size_t n, u64 *out, Form f) {
+    if (!io.dev) return down_ring(io.c, src, n, out, f);
+    const bool xb = xb_converts(io.c, f);
+    if (io.flag) {
+        if (xb) launch_soa_to_aos_unless_xb(src, out, n, io.flag, Ring<C>::xb_mat(io.c->xb_T), io.c->stream());
+        else launch_soa_to_aos_unless(src, out, n, io.flag, io.c->stream());
+    } else if (xb) launch_soa_to_aos_xb(src, out, n, Ring<C>::xb_mat(io.c->xb_T), io.c->stream());
     else launch_soa_to_aos(src, out, n, io.c->stream());
     RET(io.fetch());
     HIPCHK(hipStreamSynchronize(io.c->stream()));
@@ -418,7 +434,7 @@ struct ring_ops<Ring<C>> {
             W *row;
             RET(c->tbuf("i8_prep_row", RE * cnt, &row));
             for (size_t i = 0; i < kappa; i++) {
-                if (A_host) RET(up_ring(c, A_host + (i * n + col0) * RE, cnt, row));
+                if (A_host) RET(up_ring(c, A_host + (i * n + col0) * RE, cnt, row, Form::ntt));
                 else launch_fill_ajtai(row, 1, cnt, n, col0, seed, c->stream(), (u32)i);
                 RET(R::pack_row(c, row, cnt, (u32)i % kc, MT, Ab + (i / kc) * chunk_bytes));
             }
@@ -533,7 +549,7 @@ struct ring_ops<Ring<C>> {
         RET(c->tbuf("io_a", batch * n * RE, &F));
         RET(c->tbuf(R::io_out, batch * c->kappa * RE, &o));
         RET(io.begin());
-        for (size_t b = 0; b < batch; b++) RET(up_ring(io, f + b * n * RE, n, F + b * RE * n));
+        for (size_t b = 0; b < batch; b++) RET(up_ring(io, f + b * n * RE, n, F + b * RE * n, Form::ntt));
         c->tn = Tunables::read(R::lut_min_default);
         c->ev_reset();
         RET(commit_dev_i8g(c, F + c->A_col0, n, (u32)batch, nullptr, 0, o, true));   // timed: lf_last_kernel_stats reports the stand-alone kernel
@@ -560,7 +576,7 @@ struct ring_ops<Ring<C>> {
         if (ntt_in) RET(c->tbuf("io_c", count * RE, &X));
         RET(c->tbuf(R::io_out, batch * c->kappa * RE, &o));
         RET(io.begin());
-        for (size_t b = 0; b < batch; b++) RET(up_ring(io, f + b * count * RE, count, F + b * RE * count));
+        for (size_t b = 0; b < batch; b++) RET(up_ring(io, f + b * count * RE, count, F + b * RE * count, ntt_in ? Form::ntt : Form::coeff));
         c->tn = Tunables::read(R::lut_min_default);
         c->ev_reset();
         const u32 NP = lb ? ajtai_i8g_planes_base(R::i8(), 1ull << lb) : ajtai_i8g_planes_general(R::i8());
@@ -586,9 +602,9 @@ struct ring_ops<Ring<C>> {
         RET(c->tbuf("io_a", count * RE, &a));
         RET(c->tbuf("io_b", count * RE, &b));
         RET(io.begin());
-        RET(up_ring(io, in, count, a));
+        RET(up_ring(io, in, count, a, Form::coeff));
         launch_crt_fwd(R::tab(c), a, b, count, c->stream());
-        return down_ring(io, b, count, out);
+        return down_ring(io, b, count, out, Form::ntt);
     }
     static int ntt_inv(C *c, const u64 *in, u64 *out, size_t count, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
@@ -600,9 +616,9 @@ struct ring_ops<Ring<C>> {
         RET(c->tbuf("io_a", count * RE, &a));
         RET(c->tbuf("io_b", count * RE, &b));
         RET(io.begin());
-        RET(up_ring(io, in, count, a));
+        RET(up_ring(io, in, count, a, Form::ntt));
         launch_icrt_dense(c->d_icrt, a, b, count, c->stream());
-        return down_ring(io, b, count, out);
+        return down_ring(io, b, count, out, Form::coeff);
     }
     static int decompose(C *c, const u64 *in, size_t count, u64 base, unsigned digits, int layout, u64 *out) {
         if (!pow2(base)) return LF_ERR_UNSUPPORTED;
@@ -611,10 +627,10 @@ struct ring_ops<Ring<C>> {
         W *a, *b;
         RET(c->tbuf("io_a", count * RE, &a));
         RET(c->tbuf("io_b", count * digits * RE, &b));
-        RET(up_ring(c, in, count, a));
+        RET(up_ring(c, in, count, a, Form::coeff));
         launch_decompose(a, count, base, digits, layout, b, c->stream(), c->digit_mode);
-        if (layout == 0) return down_ring(c, b, count * digits, out);
-        for (unsigned k = 0; k < digits; k++) RET(down_ring(c, b + (size_t)k * RE * count, count, out + (size_t)k * count * RE));
+        if (layout == 0) return down_ring(c, b, count * digits, out, Form::coeff);
+        for (unsigned k = 0; k < digits; k++) RET(down_ring(c, b + (size_t)k * RE * count, count, out + (size_t)k * count * RE, Form::coeff));
         return LF_OK;
     }
     static int recompose(C *c, const u64 *in, size_t count_out, u64 base, unsigned digits, u64 *out) {
@@ -623,9 +639,9 @@ struct ring_ops<Ring<C>> {
         W *a, *b;
         RET(c->tbuf("io_a", count_out * digits * RE, &a));
         RET(c->tbuf("io_b", count_out * RE, &b));
-        RET(up_ring(c, in, count_out * digits, a));
+        RET(up_ring(c, in, count_out * digits, a, Form::coeff));
         launch_recompose(a, count_out, base, digits, b, c->stream());
-        return down_ring(c, b, count_out, out);
+        return down_ring(c, b, count_out, out, Form::coeff);
     }
     static int linf_check(C *c, const u64 *f_ntt, size_t count, u64 bound, int unsigned_variant, int *ok, u64 *max_out) {
         std::lock_guard<std::mutex> g(c->mu);
@@ -635,14 +651,14 @@ struct ring_ops<Ring<C>> {
         RET(c->tbuf("io_a", count * RE, &a));
         RET(c->tbuf("io_b", count * RE, &b));
         RET(c->tbuf("small_dev", 4096, &mx));
-        RET(up_ring(c, f_ntt, count, a));
+        RET(up_ring(c, f_ntt, count, a, Form::ntt));
         launch_icrt_dense(c->d_icrt, a, b, count, c->stream());
         u64 m = 0;
         if (unsigned_variant) {
             // literal Witness::within_bound (arith.rs:372-386): canonical coefficient < bound.  The maximum is taken over CANONICAL words, so the table comes
             // down through down_ring (BabyBear planes hold Montgomery words); a maximum does not depend on the layout
             std::vector<u64> h(count * RE);
-            RET(down_ring(c, b, count, h.data()));
+            RET(down_ring(c, b, count, h.data(), Form::coeff));
             for (u64 v : h) m = v > m ? v : m;
         } else {
             launch_linf(b, count, mx, c->stream());
@@ -686,7 +702,7 @@ struct ring_ops<Ring<C>> {
         RET(c->tbuf("red_partial", R::red_partial(ntables * RE), &partial));
         RET(c->tbuf(R::io_out, ntables * RE, &o));   // (the rings name this buffer differently; kept: buffer names are part of a context's memory footprint)
         RET(build_eq_dev(c, load_point(point, nv).data(), nv, eq));
-        for (size_t a = 0; a < ntables; a++) RET(up_ring(c, tables + a * len * RE, len, X + a * RE * len));
+        for (size_t a = 0; a < ntables; a++) RET(up_ring(c, tables + a * len * RE, len, X + a * RE * len, Form::ntt));
         launch_dot_eq(R::tab(c), X, len, (u32)ntables, eq, n, len, partial, o, c->stream());
         return down_small(c, o, ntables * RE, out);
     }
@@ -698,17 +714,17 @@ struct ring_ops<Ring<C>> {
         W *zd, *od;
         RET(c->tbuf("io_a", c->n * RE, &zd));
         RET(c->tbuf("io_b", c->m * RE, &od));
-        RET(up_ring(c, z, c->n, zd));
+        RET(up_ring(c, z, c->n, zd, Form::ntt));
         if constexpr (R::general_csr) {   // Goldilocks only: dense rows gather whole elements from an element-major z
             if (c->ccs_general) {
                 W *zaos;
                 RET(c->tbuf("spmv_zaos", c->n * RE, &zaos));
                 launch_spmv_rows(R::tab(c), 1, &c->d_rowptr[j], &c->d_col[j], &c->d_val[j], zd, 0, c->n, zaos, od, c->m, 0, c->stream());
-                return down_ring(c, od, c->m, out);
+                return down_ring(c, od, c->m, out, Form::ntt);
             }
         }
         launch_spmv(R::tab(c), c->d_rowptr[j], c->d_col[j], c->d_val[j], zd, c->n, od, c->m, 0, c->stream());
-        return down_ring(c, od, c->m, out);
+        return down_ring(c, od, c->m, out, Form::ntt);
     }
 
     // ---- the sumchecks through the ABI (tests / SURVEY 8b): MLSumcheck::prove_as_subprotocol (utils/sumcheck.rs:53-80) split at the transcript ----
@@ -723,7 +739,7 @@ struct ring_ops<Ring<C>> {
         W *mz, *eqb;
         RET(c->tbuf("sc_tab0", (size_t)P.t * RE * m, &mz));
         RET(c->tbuf("sc_eq0", TAU * m, &eqb));
-        for (u32 j = 0; j < P.t; j++) RET(up_ring(c, tables + (size_t)j * m * RE, m, mz + (size_t)j * RE * m));
+        for (u32 j = 0; j < P.t; j++) RET(up_ring(c, tables + (size_t)j * m * RE, m, mz + (size_t)j * RE * m, Form::ntt));
         RET(build_eq_dev(c, load_point(eq_point, P.s).data(), P.s, eqb));
         c->sc_round = 0; c->sc_n = m; c->sc_cur = 0;
         return LF_OK;
@@ -785,12 +801,12 @@ struct ring_ops<Ring<C>> {
         RET(c->tbuf("sf_F0", (size_t)K2 * TAU * RE * m, &F));
         RET(c->tbuf("sf_tmp", RE * m, &tmp));
         for (int e = 0; e < 3; e++) {   // eqL, eqR, eqB -> extension-field tables (slot 0 of the ring table); one stream orders tmp's reuse
-            RET(up_ring(c, tables + (size_t)eq_idx[e] * m * RE, m, tmp));
+            RET(up_ring(c, tables + (size_t)eq_idx[e] * m * RE, m, tmp, Form::ntt));
             HIPCHK(hipMemcpyAsync(T + TAU * e * m, tmp, TAU * m * sizeof(W), hipMemcpyDeviceToDevice, c->stream()));
         }
-        RET(up_ring(c, tables + (size_t)1 * m * RE, m, T + 3 * TAU * m));
-        RET(up_ring(c, tables + (size_t)3 * m * RE, m, T + (3 * TAU + RE) * m));
-        for (u32 i = 0; i < K2 * TAU; i++) RET(up_ring(c, tables + (size_t)(5 + i) * m * RE, m, F + (size_t)i * RE * m));
+        RET(up_ring(c, tables + (size_t)1 * m * RE, m, T + 3 * TAU * m, Form::ntt));
+        RET(up_ring(c, tables + (size_t)3 * m * RE, m, T + (3 * TAU + RE) * m, Form::ntt));
+        for (u32 i = 0; i < K2 * TAU; i++) RET(up_ring(c, tables + (size_t)(5 + i) * m * RE, m, F + (size_t)i * RE * m, Form::ntt));
         std::vector<ExtC> mu_pow((size_t)K2 * TAU);   // mu_i^1 .. mu_i^tau in the kernels' constant form
         for (u32 i = 0; i < K2; i++) {
             const Ext mi = R::ext_load(mu + TAU * i);
@@ -876,7 +892,7 @@ struct ring_ops<Ring<C>> {
         RET(c->tbuf("io_b", (size_t)c->P.wit_len * RE, &b));
         RET(c->tbuf("io_c", c->N * RE, &d));
         RET(io.begin());
-        RET(up_ring(io, w_ccs, c->P.wit_len, a));
+        RET(up_ring(io, w_ccs, c->P.wit_len, a, Form::ntt));
         launch_icrt_dense(c->d_icrt, a, b, c->P.wit_len, c->stream());
         launch_decompose(b, c->P.wit_len, c->P.B, c->P.L, 0, d, c->stream(), c->digit_mode);
         return witness_from_coef_table(c, d, out, &io);
@@ -896,7 +912,7 @@ struct ring_ops<Ring<C>> {
         W *d;
         RET(c->tbuf("io_c", c->N * RE, &d));
         RET(io.begin());
-        RET(up_ring(io, f_coeff, c->N, d));
+        RET(up_ring(io, f_coeff, c->N, d, Form::coeff));
         return witness_from_coef_table(c, d, out, &io);
     }
     static int witness_from_f(C *c, const u64 *f_ntt, lf_witness **out, Origin org = Origin::host) {
@@ -909,7 +925,7 @@ struct ring_ops<Ring<C>> {
         RET(c->tbuf("io_a", c->N * RE, &a));
         RET(c->tbuf("io_c", c->N * RE, &d));
         RET(io.begin());
-        RET(up_ring(io, f_ntt, c->N, a));
+        RET(up_ring(io, f_ntt, c->N, a, Form::ntt));
         launch_icrt_dense(c->d_icrt, a, d, c->N, c->stream());
         return witness_from_coef_table(c, d, out, &io);
     }
@@ -921,20 +937,20 @@ struct ring_ops<Ring<C>> {
         W *d;
         RET(c->tbuf("io_c", w->N * RE, &d));
         launch_i32_to_coef(w->planes, d, w->N, c->stream());
-        return down_ring(io, d, w->N, out);
+        return down_ring(io, d, w->N, out, Form::coeff);
     }
     static int witness_get_f(C *c, const lf_witness *w, u64 *out, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         HIPCHK(hipSetDevice(c->device));
         DevIo<C> io(c, org);
         RET(io.array(out, w->N));
-        if (w->f_ntt) return down_ring(io, (const W *)w->f_ntt, w->N, out);      // built inside the fold step that produced this witness
+        if (w->f_ntt) return down_ring(io, (const W *)w->f_ntt, w->N, out, Form::ntt);      // built inside the fold step that produced this witness
         W *d, *e;
         RET(c->tbuf("io_c", w->N * RE, &d));
         RET(c->tbuf("io_b", w->N * RE, &e));
         launch_i32_to_coef(w->planes, d, w->N, c->stream());
         launch_crt_fwd(R::tab(c), d, e, w->N, c->stream());
-        return down_ring(io, e, w->N, out);
+        return down_ring(io, e, w->N, out, Form::ntt);
     }
     static int witness_get_w_ccs(C *c, const lf_witness *w, u64 *out, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
@@ -942,11 +958,11 @@ struct ring_ops<Ring<C>> {
         HIPCHK(hipSetDevice(c->device));
         DevIo<C> io(c, org);
         RET(io.array(out, c->P.wit_len));
-        if (w->w_ccs && w->w_bytes == (size_t)c->P.wit_len * RE * sizeof(W)) return down_ring(io, (const W *)w->w_ccs, c->P.wit_len, out);
+        if (w->w_ccs && w->w_bytes == (size_t)c->P.wit_len * RE * sizeof(W)) return down_ring(io, (const W *)w->w_ccs, c->P.wit_len, out, Form::ntt);
         W *e;
         RET(c->tbuf("io_b", (size_t)c->P.wit_len * RE, &e));
         launch_recompose_crt(R::tab(c), w->planes, w->N, c->P.wit_len, c->P.L, c->P.B, 1, 0, e, c->P.wit_len, 0, c->stream());
-        return down_ring(io, e, c->P.wit_len, out);
+        return down_ring(io, e, c->P.wit_len, out, Form::ntt);
     }
     static int witness_commit(C *c, const lf_witness *w, u64 *cm_out) {
         std::lock_guard<std::mutex> g(c->mu);
@@ -969,14 +985,14 @@ struct ring_ops<Ring<C>> {
         W *X, *o;
         RET(c->tbuf("io_a", n_terms * len * RE, &X));
         RET(c->tbuf("io_b", len * RE, &o));
-        for (size_t i = 0; i < n_terms; i++) RET(up_ring(c, tables + i * len * RE, len, X + i * RE * len));
+        for (size_t i = 0; i < n_terms; i++) RET(up_ring(c, tables + i * len * RE, len, X + i * RE * len, Form::ntt));
         std::vector<ExtC> cf(n_terms * 8);
         for (size_t i = 0; i < n_terms; i++)
             for (size_t sl = 0; sl < 8; sl++) cf[i * 8 + sl] = R::ext_const(c, R::ext_load(coef + i * RE + TAU * sl));
         ExtC *d_cf;
         RET(upload_consts(c, "lc_coef", cf, &d_cf));
         launch_lincomb_z(R::tab(c), X, len, (u32)n_terms, d_cf, 1, len, o, c->stream(), 1);
-        return down_ring(c, o, len, out);
+        return down_ring(c, o, len, out, Form::ntt);
     }
     // calculate_challenged_mz_mle (nifs/folding.rs:208-226) and the f-hat half of prepare_g1_and_3_k_mles_list (folding/utils.rs:524-546):
     // out[x] = sum_{i<groups} sum_{j<per_group} c_i^{j+1} T_{i,j}[x] (the reference's Horner loop `mle += M; mle *= c_i` over j reversed)
@@ -987,7 +1003,7 @@ struct ring_ops<Ring<C>> {
         W *X, *o;
         RET(c->tbuf("io_a", nt * len * RE, &X));
         RET(c->tbuf("io_b", len * RE, &o));
-        for (size_t i = 0; i < nt; i++) RET(up_ring(c, tables + i * len * RE, len, X + i * RE * len));
+        for (size_t i = 0; i < nt; i++) RET(up_ring(c, tables + i * len * RE, len, X + i * RE * len, Form::ntt));
         std::vector<ExtC> cf(nt);
         for (size_t i = 0; i < groups; i++) {
             Ext ci = R::ext_load(challenges + TAU * i), pw = ci;
@@ -996,7 +1012,7 @@ struct ring_ops<Ring<C>> {
         ExtC *d_cf;
         RET(upload_consts(c, "lc_coef", cf, &d_cf));
         launch_lincomb_z(R::tab(c), X, len, (u32)nt, d_cf, 1, len, o, c->stream(), 0);
-        return down_ring(c, o, len, out);
+        return down_ring(c, o, len, out, Form::ntt);
     }
 };
 }  // namespace lfring
@@ -1009,6 +1025,7 @@ using lfring::commit_dev_pre;
 using lfring::commit_planes_i8;
 using lfring::DevIo;
 using lfring::down_ring;
+using lfring::Form;
 using lfring::Origin;
 using lfring::pow2;
 using lfring::up_ring;
