@@ -27,18 +27,14 @@ E9C e9c_from_h9(const H9 &h);
 E9PreC e9pre_from_h9(const H9 &h, u64 nu);
 
 // ---- layout / utility ------------------------------------------------------------------------------------------
-void launch_aos_to_soa(const u64 *aos_canon, fe *soa, size_t n, hipStream_t s);     // [n][72] canonical u64 -> [72][n] fe
-void launch_soa_to_aos(const fe *soa, u64 *aos_canon, size_t n, hipStream_t s);
-// the _dev entry points: the source is the caller's device buffer, every word validated against p (bit 0 of *flag: a word >= p); the result goes out unless *flag
-void launch_aos_to_soa_checked(const u64 *aos, fe *soa, size_t n, u32 *flag, hipStream_t s);
-void launch_soa_to_aos_unless(const fe *soa, u64 *aos, size_t n, const u32 *flag, hipStream_t s);
-// the same relayouts for a context in an external basis of F_{p^9} (lf_set_ext_basis): every slot is multiplied by a 9 x 9 matrix (row-major, centred Montgomery
+// the relayouts for a context in an external basis of F_{p^9} (lf_set_ext_basis) multiply every slot by a 9 x 9 matrix (row-major, centred Montgomery
 // words like the planes, column 0 = e_0) while the tile is in LDS -- T^-1 on the way in (after the canonical test of the checked form), T on the way out
 struct XbMat9 { fe m[81]; };
-void launch_aos_to_soa_xb(const u64 *aos, fe *soa, size_t n, const XbMat9 &Ti, hipStream_t s);
-void launch_soa_to_aos_xb(const fe *soa, u64 *aos, size_t n, const XbMat9 &T, hipStream_t s);
-void launch_aos_to_soa_checked_xb(const u64 *aos, fe *soa, size_t n, u32 *flag, const XbMat9 &Ti, hipStream_t s);
-void launch_soa_to_aos_unless_xb(const fe *soa, u64 *aos, size_t n, const u32 *flag, const XbMat9 &T, hipStream_t s);
+// [n][72] canonical u64 -> [72][n] fe.  flag (the _dev entry points): the source is the caller's device buffer, every word validated against p (bit 0 of
+// *flag: a word >= p).  Ti: T^-1 of a context in an external basis
+void launch_aos_to_soa(const u64 *aos_canon, fe *soa, size_t n, hipStream_t s, u32 *flag = nullptr, const XbMat9 *Ti = nullptr);
+// unless_flag: the result goes out unless *unless_flag.  T: of a context in an external basis
+void launch_soa_to_aos(const fe *soa, u64 *aos_canon, size_t n, hipStream_t s, const u32 *unless_flag = nullptr, const XbMat9 *T = nullptr);
 void launch_fill_ajtai(fe *A, u32 kappa, size_t n, size_t n_total, size_t col0, u64 seed, hipStream_t s, u32 row0 = 0);
 void launch_selftest(const u64 *in_canon /*[n][18]*/, u64 *out_canon /*[n][12]*/, u32 n, fe nu, hipStream_t s);
 // i64 partial sums [nblocks][nv] -> canonical u64 [nv]

@@ -3,6 +3,8 @@
 // tables, lane <-> consecutive element index, cross-lane reductions by wave64 shuffles + one LDS hop, the Ajtai mat-vec
 // staged through LDS.  Arithmetic: centred Montgomery int32 words; an F_{p^9} product is 81 v_mad_i64_i32 into nine
 // signed 64-bit column sums (9 * H^2 < 2^63) + nine Montgomery reductions (bb_field.cuh).  No MFMA.
+// The kernels that differ from the Goldilocks ones in the word type only -- layouts, decomposition, witness plumbing, the CRT butterflies, compute_f_0 -- are
+// the templates of lf_ring_kernels.cuh, instantiated here under the word policy BbF (bb_kernels_dev.cuh); their launchers below forward to them.
 #include "bb_kernels.h"
 
 #include <stdlib.h>
@@ -58,134 +60,13 @@ void launch_reduce_rows(const i64 *partial, u32 nblocks, u32 nv, u64 *out, hipSt
 size_t red_partial_words(u32 nv) { return (size_t)RED_BLOCKS * nv; }
 
 // ---------------------------------------------------------------------------------------------------------
-// layout + Montgomery conversion at the ABI
-// CHECKED: the source is a caller's own device buffer (the _dev entry points), read in place, and every word is validated: a wave that saw a word >= p sets
-// *flag -- one vector atomic by its lowest lane after a ballot (every lane of the block runs the same 18 trips, so the ballot sees whole waves)
-// XBASIS: the context is in an external basis of F_{p^9} (lf_set_ext_basis).  Between the two passes over the tile every (element, slot) -- 64 x 8 jobs, two per
-// thread -- is multiplied by the 9 x 9 matrix M (wave-uniform: a kernel argument of centred Montgomery words), in place in the tile: M = T^-1 on the way in,
-// after the canonical test has seen the caller's own words, M = T on the way out, before the AoS write.  Lane <-> element, as in the plane pass: the odd row
-// length keeps the 32 lanes of a half on distinct banks; wave w takes slots w and w + 4.  Column 0 of M is e_0 (ExtBasis::set): a row is eight centred products,
-// 8 H^2 < 2^63, summed in one signed 64-bit register and Montgomery-reduced once -- (M v)~ from M~ and v~.  The row loop stays rolled and serves both jobs of
-// the thread: eight matrix words are live in SGPRs at a time, not all 72 (which spill)
-__device__ __forceinline__ void xb_slot_pass(fe (*tile)[RE + 1], const XbMat9 &M) {
-    fe *p0 = &tile[threadIdx.x % 64][TAU * (threadIdx.x / 64)], *p1 = p0 + TAU * 4;
-    fe a[TAU], b[TAU];
-#pragma unroll
-    for (int j = 0; j < TAU; j++) { a[j] = p0[j]; b[j] = p1[j]; }
-#pragma unroll 1
-    for (int i = 0; i < TAU; i++) {
-        const fe *row = M.m + TAU * i;
-        i64 s0 = 0, s1 = 0;
-#pragma unroll
-        for (int j = 1; j < TAU; j++) { s0 += (i64)row[j] * (i64)a[j]; s1 += (i64)row[j] * (i64)b[j]; }
-        const fe r0 = mred(s0), r1 = mred(s1);
-        p0[i] = i ? r0 : fadd(r0, a[0]);
-        p1[i] = i ? r1 : fadd(r1, b[0]);
-    }
+// layout + Montgomery conversion at the ABI, Ajtai matrix fill: lf_ring_kernels.cuh
+void launch_aos_to_soa(const u64 *aos, fe *soa, size_t n, hipStream_t s, u32 *flag, const XbMat9 *Ti) { lfk::launch_aos_to_soa<BbF>(aos, soa, n, s, flag, Ti); }
+void launch_soa_to_aos(const fe *soa, u64 *aos, size_t n, hipStream_t s, const u32 *unless_flag, const XbMat9 *T) {
+    lfk::launch_soa_to_aos<BbF>(soa, aos, n, s, unless_flag, T);
 }
-template <bool CHECKED, bool XBASIS = false>
-__device__ __forceinline__ void aos_to_soa_tile(const u64 *aos, fe *soa, size_t n, u32 *flag, const XbMat9 *M = nullptr) {
-    __shared__ fe tile[64][RE + 1];
-    size_t base = (size_t)blockIdx.x * 64;
-    bool bad = false;
-    for (int idx = threadIdx.x; idx < 64 * RE; idx += 256) {
-        size_t e = base + idx / RE;
-        const u64 v = e < n ? aos[e * RE + idx % RE] : 0;
-        if (CHECKED) bad |= v >= BB_P;
-        tile[idx / RE][idx % RE] = from_canon(v);
-    }
-    if (CHECKED) {
-        if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
-    }
-    __syncthreads();
-    if (XBASIS) {
-        xb_slot_pass(tile, *M);
-        __syncthreads();
-    }
-    for (int idx = threadIdx.x; idx < 64 * RE; idx += 256) {
-        int w = idx / 64, j = idx % 64;
-        if (base + j < n) soa[(size_t)w * n + base + j] = tile[j][w];
-    }
-}
-template <bool XBASIS = false>
-__device__ __forceinline__ void soa_to_aos_tile(const fe *soa, u64 *aos, size_t n, const XbMat9 *M = nullptr) {
-    __shared__ fe tile[64][RE + 1];
-    size_t base = (size_t)blockIdx.x * 64;
-    for (int idx = threadIdx.x; idx < 64 * RE; idx += 256) {
-        int w = idx / 64, j = idx % 64;
-        tile[j][w] = base + j < n ? soa[(size_t)w * n + base + j] : 0;
-    }
-    __syncthreads();
-    if (XBASIS) {
-        xb_slot_pass(tile, *M);
-        __syncthreads();
-    }
-    for (int idx = threadIdx.x; idx < 64 * RE; idx += 256) {
-        size_t e = base + idx / RE;
-        if (e < n) aos[e * RE + idx % RE] = to_canon(tile[idx / RE][idx % RE]);
-    }
-}
-__global__ void __launch_bounds__(256) k_aos_to_soa(const u64 *aos, fe *soa, size_t n) { aos_to_soa_tile<false>(aos, soa, n, nullptr); }
-__global__ void __launch_bounds__(256) k_aos_to_soa_checked(const u64 *aos, fe *soa, size_t n, u32 *flag) { aos_to_soa_tile<true>(aos, soa, n, flag); }
-__global__ void __launch_bounds__(256) k_soa_to_aos(const fe *soa, u64 *aos, size_t n) { soa_to_aos_tile(soa, aos, n); }
-// the result of a _dev call into the caller's buffer: nothing is written when the checked relayout of the call's input raised *flag
-__global__ void __launch_bounds__(256) k_soa_to_aos_unless(const fe *soa, u64 *aos, size_t n, const u32 *flag) {
-    if (*flag) return;
-    soa_to_aos_tile(soa, aos, n);
-}
-// the same four for a context in an external basis: Ti = T^-1 inbound, T outbound
-__global__ void __launch_bounds__(256) k_aos_to_soa_xb(const u64 *aos, fe *soa, size_t n, XbMat9 Ti) { aos_to_soa_tile<false, true>(aos, soa, n, nullptr, &Ti); }
-__global__ void __launch_bounds__(256) k_aos_to_soa_checked_xb(const u64 *aos, fe *soa, size_t n, u32 *flag, XbMat9 Ti) {
-    aos_to_soa_tile<true, true>(aos, soa, n, flag, &Ti);
-}
-__global__ void __launch_bounds__(256) k_soa_to_aos_xb(const fe *soa, u64 *aos, size_t n, XbMat9 T) { soa_to_aos_tile<true>(soa, aos, n, &T); }
-__global__ void __launch_bounds__(256) k_soa_to_aos_unless_xb(const fe *soa, u64 *aos, size_t n, const u32 *flag, XbMat9 T) {
-    if (*flag) return;
-    soa_to_aos_tile<true>(soa, aos, n, &T);
-}
-void launch_aos_to_soa(const u64 *aos, fe *soa, size_t n, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_aos_to_soa, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n);
-}
-void launch_soa_to_aos(const fe *soa, u64 *aos, size_t n, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_soa_to_aos, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n);
-}
-void launch_aos_to_soa_checked(const u64 *aos, fe *soa, size_t n, u32 *flag, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_aos_to_soa_checked, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n, flag);
-}
-void launch_soa_to_aos_unless(const fe *soa, u64 *aos, size_t n, const u32 *flag, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_soa_to_aos_unless, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n, flag);
-}
-void launch_aos_to_soa_xb(const u64 *aos, fe *soa, size_t n, const XbMat9 &Ti, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_aos_to_soa_xb, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n, Ti);
-}
-void launch_soa_to_aos_xb(const fe *soa, u64 *aos, size_t n, const XbMat9 &T, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_soa_to_aos_xb, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n, T);
-}
-void launch_aos_to_soa_checked_xb(const u64 *aos, fe *soa, size_t n, u32 *flag, const XbMat9 &Ti, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_aos_to_soa_checked_xb, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n, flag, Ti);
-}
-void launch_soa_to_aos_unless_xb(const fe *soa, u64 *aos, size_t n, const u32 *flag, const XbMat9 &T, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_soa_to_aos_unless_xb, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n, flag, T);
-}
-// workload.py splitmix_fq(ring="babybear"): top 32 bits of SplitMix64 word (index+1), mod p
-__device__ __forceinline__ u64 splitmix_bb(u64 seed, u64 index) {
-    u64 z = seed + (index + 1) * 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    z = z ^ (z >> 31);
-    return (z >> 32) % BB_P;
-}
-__global__ void __launch_bounds__(256) k_fill_ajtai(fe *A, u32 kappa, size_t n, size_t n_total, size_t col0, u64 seed, u32 row0) {
-    size_t total = (size_t)kappa * RE * n;
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, st = (size_t)gridDim.x * 256;
-    for (; i < total; i += st) {
-        size_t j = i % n, w = (i / n) % RE, row = row0 + i / (RE * n);
-        A[i] = from_canon(splitmix_bb(seed, (row * n_total + col0 + j) * RE + w));
-    }
-}
-// rows [row0, row0 + kappa) of the synthetic matrix into A [kappa][72][n]
 void launch_fill_ajtai(fe *A, u32 kappa, size_t n, size_t n_total, size_t col0, u64 seed, hipStream_t s, u32 row0) {
-    hipLaunchKernelGGL(k_fill_ajtai, dim3(4096), dim3(256), 0, s, A, kappa, n, n_total, col0, seed, row0);
+    lfk::launch_fill_ajtai<BbF>(A, kappa, n, n_total, col0, seed, s, row0);
 }
 // arithmetic self-test: in[i] = (a[9], b[9]) canonical; out[i] = (a*b [9], a0+b0, a0-b0, a0*b0) canonical.
 // The host recomputes with plain % arithmetic (bb_host.cpp) and compares.
@@ -208,27 +89,7 @@ void launch_selftest(const u64 *in, u64 *out, u32 n, fe nu, hipStream_t s) {
 // CRT: a(X) = sum_{r<9} X^r A_r(X^9); A_r is evaluated at the 8 primitive 24th roots by three radix-2 layers over
 // U^8 - U^4 + 1 = (U^4 - w^4)(U^4 - w^20); the per-slot monomial twist X^r -> tw[r] Y^pos[r] maps F_p[X]/(X^9 - zeta_k)
 // onto F_p[Y]/(Y^9 - nu).  (stark-rings CRT; call sites arith.rs:238,327.)
-__device__ __forceinline__ void crt8(const fe x[8], fe o[8], const DevBb &t) {
-    fe lo[4], hi[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        fe tt = fmul(t.w4, x[i + 4]);
-        lo[i] = fadd(x[i], tt);
-        hi[i] = fsub(fadd(x[i], x[i + 4]), tt);
-    }
-    fe l0[2], l1[2], h0[2], h1[2];
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-        fe tt = fmul(t.w2, lo[i + 2]);
-        l0[i] = fadd(lo[i], tt); l1[i] = fsub(lo[i], tt);
-        fe uu = fmul(t.w10, hi[i + 2]);
-        h0[i] = fadd(hi[i], uu); h1[i] = fsub(hi[i], uu);
-    }
-    fe a = fmul(t.w1, l0[1]);  o[0] = fadd(l0[0], a); o[1] = fsub(l0[0], a);
-    fe b = fmul(t.w7, l1[1]);  o[2] = fadd(l1[0], b); o[3] = fsub(l1[0], b);
-    fe c = fmul(t.w5, h0[1]);  o[4] = fadd(h0[0], c); o[5] = fsub(h0[0], c);
-    fe d = fmul(t.w11, h1[1]); o[6] = fadd(h1[0], d); o[7] = fsub(h1[0], d);
-}
+// (the butterflies themselves: lfk::crt8)
 // coefficients a[72] (Montgomery) -> the 72 NTT words of element j of plane table `out`
 __device__ __forceinline__ void crt_store(const fe a[RE], fe *out, size_t ld, size_t j, const DevBb &t) {
 #pragma unroll
@@ -236,7 +97,7 @@ __device__ __forceinline__ void crt_store(const fe a[RE], fe *out, size_t ld, si
         fe x[8], A[8];
 #pragma unroll
         for (int v = 0; v < 8; v++) x[v] = a[r + TAU * v];
-        crt8(x, A, t);
+        lfk::crt8<BbF>(x, A, t);
 #pragma unroll
         for (int p = 0; p < 8; p++) {
             int plane = TAU * t.slot_of_pos[p] + t.pos[r][p];
@@ -244,17 +105,7 @@ __device__ __forceinline__ void crt_store(const fe a[RE], fe *out, size_t ld, si
         }
     }
 }
-__global__ void __launch_bounds__(256) k_crt_fwd(DevBb t, const fe *coef, fe *ntt, size_t n) {
-    size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
-    fe a[RE];
-#pragma unroll
-    for (int c = 0; c < RE; c++) a[c] = coef[(size_t)c * n + j];
-    crt_store(a, ntt, n, j, t);
-}
-void launch_crt_fwd(const DevBb &t, const fe *coef, fe *ntt, size_t n, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_crt_fwd, dim3(cdiv(n, 256)), dim3(256), 0, s, t, coef, ntt, n);
-}
+void launch_crt_fwd(const DevBb &t, const fe *coef, fe *ntt, size_t n, hipStream_t s) { lfk::launch_crt_fwd<BbF>(t, coef, ntt, n, s); }
 // ICRT as the dense 72x72 F_p matrix (rare: ingest / export only)
 __global__ void __launch_bounds__(256) k_icrt_dense(const fe *mat, const fe *ntt, fe *coef, size_t n) {
     __shared__ fe M[RE * RE];
@@ -361,98 +212,16 @@ void launch_i8g_cut_dec(const fe *coef, size_t ldc, size_t col0, size_t n, u32 L
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// balanced decomposition on coefficient tables, power-of-two base (stark_rings::balanced_decomposition; call sites
-// arith.rs:235, decomposition/utils.rs:23-31,48).  Sign-magnitude, |digit| <= base/2, ties kept.
-__global__ void __launch_bounds__(256) k_decompose(const fe *coef, size_t n, u32 log_base, u32 digits, int layout, fe *out, int mode) {
-    size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n * RE) return;
-    size_t c = idx / n, i = idx % n;
-    u32 v = to_canon(coef[idx]);
-    bool neg = v > (BB_P - 1) / 2;
-    u64 mag = neg ? BB_P - v : v;
-    u64 half = 1ULL << (log_base - 1), mask = (1ULL << log_base) - 1;
-    size_t n_out = layout == 0 ? n * digits : n;
-    int64_t cur = neg ? -(int64_t)mag : (int64_t)mag;
-    for (u32 k = 0; k < digits; k++) {
-        int64_t dg;
-        if (mode == 1 && log_base > 1) {   // floor rule (lf_set_digit_mode 1): digits in [-base/2, base/2)
-            int64_t rem = (int64_t)((u64)cur & mask);
-            if ((u64)rem >= half) rem -= (int64_t)(mask + 1);
-            cur = (cur - rem) >> log_base;
-            dg = rem;
-        } else {
-            u64 rem = mag & mask;
-            mag >>= log_base;
-            if (rem > half) { dg = (int64_t)rem - (int64_t)(mask + 1); mag += 1; }
-            else dg = (int64_t)rem;
-            if (neg) dg = -dg;
-        }
-        size_t o = layout == 0 ? (c * n_out + i * digits + k) : ((size_t)k * RE * n + c * n + i);
-        out[o] = from_small((int32_t)dg);
-    }
-}
+// decomposition, int32 planes, l-infinity norm: lf_ring_kernels.cuh
 void launch_decompose(const fe *coef, size_t n, u64 base, u32 digits, int layout, fe *out, hipStream_t s, int mode) {
-    u32 lb = 0;
-    while ((1ULL << lb) < base) lb++;
-    if (n) hipLaunchKernelGGL(k_decompose, dim3(cdiv(n * RE, 256)), dim3(256), 0, s, coef, n, lb, digits, layout, out, mode);
+    lfk::launch_decompose<BbF>(coef, n, base, digits, layout, out, s, mode);
 }
-__global__ void __launch_bounds__(256) k_recompose(const fe *in, size_t n_out, fe base, u32 digits, fe *out) {
-    size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n_out * RE) return;
-    size_t w = idx / n_out, i = idx % n_out;
-    size_t n_in = n_out * digits;
-    fe acc = 0, pw = BB_ONE;
-    for (u32 j = 0; j < digits; j++) {
-        acc = fadd(acc, fmul(in[w * n_in + i * digits + j], pw));
-        pw = fmul(pw, base);
-    }
-    out[idx] = acc;
-}
-void launch_recompose(const fe *in, size_t n_out, u64 base, u32 digits, fe *out, hipStream_t s) {
-    if (n_out) hipLaunchKernelGGL(k_recompose, dim3(cdiv(n_out * RE, 256)), dim3(256), 0, s, in, n_out, from_canon(base % BB_P), digits, out);
-}
-__global__ void __launch_bounds__(256) k_coef_to_i32(const fe *coef, int32_t *planes, size_t total, u32 bound, int *viol) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, st = (size_t)gridDim.x * 256;
-    int bad = 0;
-    for (; i < total; i += st) {
-        u32 v = to_canon(coef[i]);
-        bool neg = v > (BB_P - 1) / 2;
-        u32 mag = neg ? BB_P - v : v;
-        if (mag > bound) { bad = 1; mag = 0; }
-        planes[i] = neg ? -(int32_t)mag : (int32_t)mag;
-    }
-    if (bad) atomicOr(viol, 1);
-}
+void launch_recompose(const fe *in, size_t n_out, u64 base, u32 digits, fe *out, hipStream_t s) { lfk::launch_recompose<BbF>(in, n_out, base, digits, out, s); }
 void launch_coef_to_i32(const fe *coef, int32_t *planes, size_t n, u32 bound, int *viol, hipStream_t s) {
-    hipLaunchKernelGGL(k_coef_to_i32, dim3(grid_for(n * RE, 4096)), dim3(256), 0, s, coef, planes, n * RE, bound, viol);
+    lfk::launch_coef_to_i32<BbF>(coef, planes, n, bound, viol, s);
 }
-__global__ void __launch_bounds__(256) k_i32_to_coef(const int32_t *planes, fe *coef, size_t total) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, st = (size_t)gridDim.x * 256;
-    for (; i < total; i += st) coef[i] = from_small(planes[i]);
-}
-void launch_i32_to_coef(const int32_t *planes, fe *coef, size_t n, hipStream_t s) {
-    hipLaunchKernelGGL(k_i32_to_coef, dim3(grid_for(n * RE, 4096)), dim3(256), 0, s, planes, coef, n * RE);
-}
-__global__ void __launch_bounds__(256) k_linf(const fe *coef, size_t total, unsigned long long *out_max) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, st = (size_t)gridDim.x * 256;
-    u64 mx = 0;
-    for (; i < total; i += st) {
-        u32 v = to_canon(coef[i]);
-        u64 mag = v > (BB_P - 1) / 2 ? BB_P - v : v;
-        mx = mag > mx ? mag : mx;
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        u64 o = __shfl_down((unsigned long long)mx, off, 64);
-        mx = o > mx ? o : mx;
-    }
-    if ((threadIdx.x & 63) == 0) atomicMax(out_max, (unsigned long long)mx);
-}
-void launch_linf(const fe *coef, size_t n, u64 *out_max, hipStream_t s) {
-    (void)hipMemsetAsync(out_max, 0, 8, s);
-    hipLaunchKernelGGL(k_linf, dim3(grid_for(n * RE, 4096)), dim3(256), 0, s, coef, n * RE, (unsigned long long *)out_max);
-}
-
-
+void launch_i32_to_coef(const int32_t *planes, fe *coef, size_t n, hipStream_t s) { lfk::launch_i32_to_coef<BbF>(planes, coef, n, s); }
+void launch_linf(const fe *coef, size_t n, u64 *out_max, hipStream_t s) { lfk::launch_linf<BbF>(coef, n, out_max, s); }
 
 struct BPow { fe v[8]; };
 // thread = (element i, residue class r of the coefficient index); in bit-plane mode the 8 x L plane entries are loaded once and all
@@ -487,7 +256,7 @@ __global__ void __launch_bounds__(256) k_recompose_crt_bits(DevBb t, const int32
             }
             x[q] = acc;
         }
-        crt8(x, A, t);
+        lfk::crt8<BbF>(x, A, t);
         fe *o = out + (size_t)k * RE * ldz;
 #pragma unroll
         for (int p = 0; p < 8; p++) o[(size_t)plane[p] * ldz + jj] = r == 0 ? A[p] : fmul(t.tw[r][p], A[p]);
@@ -515,7 +284,7 @@ __global__ void __launch_bounds__(256) k_recompose_crt(DevBb t, const int32_t *p
         }
         x[q] = acc;
     }
-    crt8(x, A, t);
+    lfk::crt8<BbF>(x, A, t);
     fe *o = out + (size_t)k * RE * ldz;
     const size_t jj = off + i;
 #pragma unroll
@@ -878,69 +647,19 @@ void launch_fix_final(const DevBb &t, const fe *in, size_t ld_in, u32 rows9, con
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// compute_f_0 (folding.rs:258-268) in the coefficient domain: f_0[j] = sum_i rho_i * f_i[j] with rho_i a short challenge
-// (24 coefficients in [-32,32), rings/babybear.rs:36-68) and f_i the i-th bit-plane; X^72 = X^36 - 1.
-// Nibble tables (as in the Goldilocks kernel): for one side, sum_k rho_k[a] * digit_k(v_c) = sign(v_c) * sum_q R[q][nibble_q(|v_c|)][a] with
-// R[q][val][a] = sum_{b<4} bit_b(val) rho_{4q+b}[a] -- four look-ups of a 24-vector per coefficient c instead of 16 x 24 multiply-adds.
-// Tables for both signs and sides (2*2*4*16*24 int32 = 24 KB) are built in LDS per block; one thread per element.  The coefficient loop
-// runs in groups of 8 with a scheduling barrier between groups, so only 8 plane loads are in flight next to the 95 accumulators.
-// Sliding window: coefficient c only touches output positions c..c+23, so with both sides handled per group of 8 coefficients the
-// positions C0..C0+7 are final after the group -- they are stored (before the X^72 wrap) and leave the registers; 31 live accumulators
-// instead of 95.  The wrap X^72 = X^36 - 1 of positions 72..94 is applied to the stored values at the end.
-template <int C0>
-__device__ __forceinline__ void fw_group8(int32_t (&win)[31], const int32_t *pL, const int32_t *pR, size_t n, size_t j,
-                                          const int32_t (*R)[2][4][16][28], int32_t *out) {
-#pragma unroll
-    for (int side = 0; side < 2; side++) {
-        const int32_t *pl = side ? pR : pL;
-        int32_t vv[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) vv[i] = pl[(size_t)(C0 + i) * n + j];
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            int32_t v = vv[i];
-            u32 mg = (u32)(v < 0 ? -v : v), sg = v < 0;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int4 *t = (const int4 *)R[side][sg][q][(mg >> (4 * q)) & 15];
-#pragma unroll
-                for (int w = 0; w < 6; w++) {
-                    int4 x = t[w];
-                    win[i + 4 * w] += x.x; win[i + 4 * w + 1] += x.y; win[i + 4 * w + 2] += x.z; win[i + 4 * w + 3] += x.w;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; i++) out[(size_t)(C0 + i) * n + j] = win[i];
-#pragma unroll
-    for (int i = 0; i < 23; i++) win[i] = win[i + 8];
-#pragma unroll
-    for (int i = 23; i < 31; i++) win[i] = 0;
-}
+// compute_f_0 (folding.rs:258-268) in the coefficient domain, mod Phi_216(X) = X^72 - X^36 + 1 (rho_i: 24 coefficients in [-32,32), rings/babybear.rs:36-68;
+// K <= 16 bit-planes): the tables and the sliding window are lfk::fw_tables / fw_groups
 __global__ void __launch_bounds__(256) k_fold_witness(const int32_t *planesL, const int32_t *planesR, size_t n, u32 K, const int8_t *rho, int32_t *out) {
-    __shared__ __align__(16) int32_t R[2][2][4][16][28];   // [side][sign][nibble][value][a]; rows padded to 28 words (bank spread)
-    for (u32 idx = threadIdx.x; idx < 2 * 4 * 16 * 24; idx += 256) {
-        u32 a = idx % 24, val = (idx / 24) % 16, q = (idx / (24 * 16)) % 4, side = idx / (24 * 16 * 4);
-        int sum = 0;
-#pragma unroll
-        for (u32 b = 0; b < 4; b++)
-            if (4 * q + b < K && ((val >> b) & 1)) sum += rho[(size_t)(side * K + 4 * q + b) * 24 + a];
-        R[side][0][q][val][a] = sum;
-        R[side][1][q][val][a] = -sum;
-    }
+    __shared__ __align__(16) int32_t R[2][2][4][16][28];
+    lfk::fw_tables<4>(R, K, rho);
     __syncthreads();
     size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
     int32_t win[31];
 #pragma unroll
     for (int i = 0; i < 31; i++) win[i] = 0;
-    fw_group8<0>(win, planesL, planesR, n, j, R, out);  fw_group8<8>(win, planesL, planesR, n, j, R, out);
-    fw_group8<16>(win, planesL, planesR, n, j, R, out); fw_group8<24>(win, planesL, planesR, n, j, R, out);
-    fw_group8<32>(win, planesL, planesR, n, j, R, out); fw_group8<40>(win, planesL, planesR, n, j, R, out);
-    fw_group8<48>(win, planesL, planesR, n, j, R, out); fw_group8<56>(win, planesL, planesR, n, j, R, out);
-    fw_group8<64>(win, planesL, planesR, n, j, R, out);
-    // win[i] = position 72 + i;  X^72 = X^36 - 1
+    lfk::fw_groups<0, RE, 4>(win, planesL, planesR, n, j, R, out);
+    // win[i] = position 72 + i;  X^72 = X^36 - 1, applied to the stored values
 #pragma unroll
     for (int i = 0; i < 23; i++) {
         out[(size_t)(36 + i) * n + j] += win[i];

@@ -1,16 +1,58 @@
 // bb_kernels_dev.cuh -- device-side helpers shared by the kernel translation units of the BabyBear backend (bb_kernels.hip, bb_rounds.hip): plane-major
-// F_{p^9} element access, lazy 96-bit sums of product columns, wave / block reductions, grid helpers, base-2 digits.
+// F_{p^9} element access, lazy 96-bit sums of product columns, wave / block reductions, grid helpers, base-2 digits, and BbF, the word policy under which
+// bb_kernels.hip instantiates the ring-generic kernels of lf_ring_kernels.cuh.
 #pragma once
 #include "bb_kernels.h"
+#include "lf_ring_kernels.cuh"
 
 namespace lfbb {
 
-static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
-static inline unsigned grid_for(size_t n, unsigned cap = 2048) {
-    size_t g = (n + 255) / 256;
-    if (g < 1) g = 1;
-    return (unsigned)(g > cap ? cap : g);
-}
+using lfk::cdiv;
+using lfk::grid_for;
+
+// the device word of this ring for lf_ring_kernels.cuh: centred Montgomery int32, converted at the ABI
+struct BbF {
+    typedef fe word;
+    typedef XbMat9 XbMat;
+    static constexpr int RE = lfbb::RE, TAU = lfbb::TAU;
+    static constexpr u32 P = BB_P;
+    static BB_HD word from_canon(u64 v) { return lfbb::from_canon(v); }
+    static BB_HD u32 to_canon(word w) { return lfbb::to_canon(w); }
+    static BB_HD word add(word a, word b) { return fadd(a, b); }
+    static BB_HD word sub(word a, word b) { return fsub(a, b); }
+    static BB_HD word mul(word a, word b) { return fmul(a, b); }
+    static BB_HD word one() { return BB_ONE; }
+    static BB_HD word from_i64(int64_t v) { return from_small((int32_t)v); }   // |v| < 2^31
+    // workload.py splitmix_fq(ring="babybear"): top 32 bits of SplitMix64 word (index+1), mod p
+    static __device__ __forceinline__ u64 splitmix(u64 seed, u64 index) {
+        u64 z = seed + (index + 1) * 0x9E3779B97F4A7C15ULL;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+        z = z ^ (z >> 31);
+        return (z >> 32) % BB_P;
+    }
+    // the 64 x 8 (element, slot) jobs of a relayout tile, two per thread, times the 9 x 9 matrix M (wave-uniform: a kernel argument of centred Montgomery
+    // words).  Lane <-> element, as in the plane pass: the odd row length keeps the 32 lanes of a half on distinct banks; wave w takes slots w and w + 4.
+    // Column 0 of M is e_0 (ExtBasis::set): a row is eight centred products, 8 H^2 < 2^63, summed in one signed 64-bit register and Montgomery-reduced
+    // once -- (M v)~ from M~ and v~.  The row loop stays rolled and serves both jobs of the thread: eight matrix words are live in SGPRs at a time, not
+    // all 72 (which spill)
+    static __device__ __forceinline__ void xb_slot_pass(fe (*tile)[RE + 1], const XbMat9 &M) {
+        fe *p0 = &tile[threadIdx.x % 64][TAU * (threadIdx.x / 64)], *p1 = p0 + TAU * 4;
+        fe a[TAU], b[TAU];
+#pragma unroll
+        for (int j = 0; j < TAU; j++) { a[j] = p0[j]; b[j] = p1[j]; }
+#pragma unroll 1
+        for (int i = 0; i < TAU; i++) {
+            const fe *row = M.m + TAU * i;
+            i64 s0 = 0, s1 = 0;
+#pragma unroll
+            for (int j = 1; j < TAU; j++) { s0 += (i64)row[j] * (i64)a[j]; s1 += (i64)row[j] * (i64)b[j]; }
+            const fe r0 = mred(s0), r1 = mred(s1);
+            p0[i] = i ? r0 : fadd(r0, a[0]);
+            p1[i] = i ? r1 : fadd(r1, b[0]);
+        }
+    }
+};
 
 
 __device__ __forceinline__ E9 ld9(const fe *tab, size_t ld, u32 slot, size_t i) {

@@ -26,18 +26,14 @@ DevCrt make_dev_crt(const CrtTables &T);
 struct Fq3Const { u64 c[3]; };
 
 // ---- layout / utility --------------------------------------------------------------------------------------
-void launch_aos_to_soa(const u64 *aos, u64 *soa, size_t n, hipStream_t s);   // [n][24] -> [24][n]
-void launch_soa_to_aos(const u64 *soa, u64 *aos, size_t n, hipStream_t s);
-// the _dev entry points: the source is the caller's device buffer, every word validated against p (bit 0 of *flag: a word >= p); the result goes out unless *flag
-void launch_aos_to_soa_checked(const u64 *aos, u64 *soa, size_t n, u32 *flag, hipStream_t s);
-void launch_soa_to_aos_unless(const u64 *soa, u64 *aos, size_t n, const u32 *flag, hipStream_t s);
-// the same relayouts for a context in an external basis of F_{p^3} (lf_set_ext_basis): every slot is multiplied by a 3 x 3 matrix (row-major, canonical words,
+// the relayouts for a context in an external basis of F_{p^3} (lf_set_ext_basis) multiply every slot by a 3 x 3 matrix (row-major, canonical words,
 // column 0 = e_0) while the tile is in LDS -- T^-1 on the way in (after the canonical test of the checked form), T on the way out
 struct XbMat3 { u64 m[9]; };
-void launch_aos_to_soa_xb(const u64 *aos, u64 *soa, size_t n, const XbMat3 &Ti, hipStream_t s);
-void launch_soa_to_aos_xb(const u64 *soa, u64 *aos, size_t n, const XbMat3 &T, hipStream_t s);
-void launch_aos_to_soa_checked_xb(const u64 *aos, u64 *soa, size_t n, u32 *flag, const XbMat3 &Ti, hipStream_t s);
-void launch_soa_to_aos_unless_xb(const u64 *soa, u64 *aos, size_t n, const u32 *flag, const XbMat3 &T, hipStream_t s);
+// [n][24] -> [24][n].  flag (the _dev entry points): the source is the caller's device buffer, every word validated against p (bit 0 of *flag: a word >= p).
+// Ti: T^-1 of a context in an external basis
+void launch_aos_to_soa(const u64 *aos, u64 *soa, size_t n, hipStream_t s, u32 *flag = nullptr, const XbMat3 *Ti = nullptr);
+// unless_flag: the result goes out unless *unless_flag.  T: of a context in an external basis
+void launch_soa_to_aos(const u64 *soa, u64 *aos, size_t n, hipStream_t s, const u32 *unless_flag = nullptr, const XbMat3 *T = nullptr);
 void launch_fill_uniform(u64 *dst, size_t words, u64 seed, size_t start, hipStream_t s);  // SplitMix64 stream (workload.py)
 // Ajtai matrix generated in place in plane layout, equal to AoS stream splitmix(seed)[((i*n+j)*24+w)]
 // columns [col0, col0+n) of the n_total-column matrix

@@ -1,5 +1,7 @@
-// lf_kernels.hip -- hand-written gfx950 (CDNA4, wave64) kernels of the LatticeFold prover hot path: layouts, CRT / ICRT, decomposition, witness plumbing, eq
-// tables, SpMV, batched inner products, fix_variables, compute_f_0.  The sumcheck round kernels live in lf_rounds.hip; both include lf_kernels_dev.cuh.
+// lf_kernels.hip -- hand-written gfx950 (CDNA4, wave64) kernels of the LatticeFold prover hot path: CRT / ICRT, recomposition into NTT form, eq
+// tables, SpMV, batched inner products, fix_variables.  The sumcheck round kernels live in lf_rounds.hip; both include lf_kernels_dev.cuh.
+// The kernels that differ between the rings in the word type only -- layouts, decomposition, witness plumbing, the CRT butterflies, compute_f_0 -- are the
+// templates of lf_ring_kernels.cuh, instantiated here under the word policy GoldF (lf_kernels_dev.cuh); their launchers below forward to them.
 //
 // Every kernel works on plane-major (SoA) tables so that lane <-> consecutive element index gives coalesced
 // 8/16-byte accesses; cross-lane reductions use wave64 shuffles + one LDS hop per 256-thread block; the Ajtai
@@ -25,9 +27,6 @@ DevCrt make_dev_crt(const CrtTables &T) {
     }
     return d;
 }
-
-
-__device__ __forceinline__ u64 splitmix_fq(u64 seed, u64 index);
 
 
 // sharded exchanges: out[w] = sum_g parts[g*words + w] mod p after the all-gather of the ranks' partial vectors
@@ -65,138 +64,20 @@ void launch_gather_relayout_part(const u64 *all, u32 nranks, size_t planes_tot, 
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// layout
-// CHECKED: the source is a caller's own device buffer (the _dev entry points), read in place, and every word is validated: a wave that saw a word >= p sets
-// *flag -- one vector atomic by its lowest lane after a ballot (every lane of the block runs the same six trips, so the ballot sees whole waves)
-// XBASIS: the context is in an external basis of F_{p^3} (lf_set_ext_basis).  Between the two passes over the tile every (element, slot) -- 64 x 8 jobs, two per
-// thread -- is multiplied by the 3 x 3 matrix M (wave-uniform: a kernel argument, held in SGPRs), in place in the tile: M = T^-1 on the way in, after the
-// canonical test has seen the caller's own words, M = T on the way out, before the AoS write.  Lane <-> element, as in the plane pass: the odd row length
-// keeps the 64-bit LDS accesses of a 32-lane half on distinct banks.  Column 0 of M is e_0 (ExtBasis::set), so a slot costs six products; two products of
-// words < 2^64 and their carry fit the 128-bit + carry accumulator, whatever the words are
-__device__ __forceinline__ void xb_slot_pass(u64 (*tile)[25], const XbMat3 &M) {
-    for (int idx = threadIdx.x; idx < 64 * 8; idx += 256) {
-        u64 *v = &tile[idx % 64][3 * (idx / 64)];
-        const u64 v0 = fq_canon(v[0]), v1 = v[1], v2 = v[2];
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            Acc s;
-            acc_set(s, M.m[3 * i + 1], v1);
-            acc_mad(s, M.m[3 * i + 2], v2);
-            const u64 r = acc_reduce(s);
-            v[i] = i ? r : fq_add(r, v0);
-        }
-    }
+// layout, Ajtai matrix fill: lf_ring_kernels.cuh
+void launch_aos_to_soa(const u64 *aos, u64 *soa, size_t n, hipStream_t s, u32 *flag, const XbMat3 *Ti) { lfk::launch_aos_to_soa<GoldF>(aos, soa, n, s, flag, Ti); }
+void launch_soa_to_aos(const u64 *soa, u64 *aos, size_t n, hipStream_t s, const u32 *unless_flag, const XbMat3 *T) {
+    lfk::launch_soa_to_aos<GoldF>(soa, aos, n, s, unless_flag, T);
 }
-template <bool CHECKED, bool XBASIS = false>
-__device__ __forceinline__ void aos_to_soa_tile(const u64 *aos, u64 *soa, size_t n, u32 *flag, const XbMat3 *M = nullptr) {
-    __shared__ u64 tile[64][25];
-    size_t base = (size_t)blockIdx.x * 64;
-    bool bad = false;
-    for (int idx = threadIdx.x; idx < 64 * 24; idx += 256) {
-        size_t e = base + idx / 24;
-        const u64 v = e < n ? aos[e * 24 + idx % 24] : 0;
-        if (CHECKED) bad |= v >= LF_P;
-        tile[idx / 24][idx % 24] = v;
-    }
-    if (CHECKED) {
-        if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
-    }
-    __syncthreads();
-    if (XBASIS) {
-        xb_slot_pass(tile, *M);
-        __syncthreads();
-    }
-    for (int idx = threadIdx.x; idx < 64 * 24; idx += 256) {
-        int w = idx / 64, j = idx % 64;
-        if (base + j < n) soa[(size_t)w * n + base + j] = tile[j][w];
-    }
-}
-template <bool XBASIS = false>
-__device__ __forceinline__ void soa_to_aos_tile(const u64 *soa, u64 *aos, size_t n, const XbMat3 *M = nullptr) {
-    __shared__ u64 tile[64][25];
-    size_t base = (size_t)blockIdx.x * 64;
-    for (int idx = threadIdx.x; idx < 64 * 24; idx += 256) {
-        int w = idx / 64, j = idx % 64;
-        tile[j][w] = base + j < n ? soa[(size_t)w * n + base + j] : 0;
-    }
-    __syncthreads();
-    if (XBASIS) {
-        xb_slot_pass(tile, *M);
-        __syncthreads();
-    }
-    for (int idx = threadIdx.x; idx < 64 * 24; idx += 256) {
-        size_t e = base + idx / 24;
-        if (e < n) aos[e * 24 + idx % 24] = tile[idx / 24][idx % 24];
-    }
-}
-__global__ void __launch_bounds__(256) k_aos_to_soa(const u64 *aos, u64 *soa, size_t n) { aos_to_soa_tile<false>(aos, soa, n, nullptr); }
-__global__ void __launch_bounds__(256) k_aos_to_soa_checked(const u64 *aos, u64 *soa, size_t n, u32 *flag) { aos_to_soa_tile<true>(aos, soa, n, flag); }
-__global__ void __launch_bounds__(256) k_soa_to_aos(const u64 *soa, u64 *aos, size_t n) { soa_to_aos_tile(soa, aos, n); }
-// the result of a _dev call into the caller's buffer: nothing is written when the checked relayout of the call's input raised *flag
-__global__ void __launch_bounds__(256) k_soa_to_aos_unless(const u64 *soa, u64 *aos, size_t n, const u32 *flag) {
-    if (*flag) return;
-    soa_to_aos_tile(soa, aos, n);
-}
-// the same four for a context in an external basis: Ti = T^-1 inbound, T outbound
-__global__ void __launch_bounds__(256) k_aos_to_soa_xb(const u64 *aos, u64 *soa, size_t n, XbMat3 Ti) { aos_to_soa_tile<false, true>(aos, soa, n, nullptr, &Ti); }
-__global__ void __launch_bounds__(256) k_aos_to_soa_checked_xb(const u64 *aos, u64 *soa, size_t n, u32 *flag, XbMat3 Ti) {
-    aos_to_soa_tile<true, true>(aos, soa, n, flag, &Ti);
-}
-__global__ void __launch_bounds__(256) k_soa_to_aos_xb(const u64 *soa, u64 *aos, size_t n, XbMat3 T) { soa_to_aos_tile<true>(soa, aos, n, &T); }
-__global__ void __launch_bounds__(256) k_soa_to_aos_unless_xb(const u64 *soa, u64 *aos, size_t n, const u32 *flag, XbMat3 T) {
-    if (*flag) return;
-    soa_to_aos_tile<true>(soa, aos, n, &T);
-}
-void launch_aos_to_soa(const u64 *aos, u64 *soa, size_t n, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_aos_to_soa, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n);
-}
-void launch_soa_to_aos(const u64 *soa, u64 *aos, size_t n, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_soa_to_aos, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n);
-}
-void launch_aos_to_soa_checked(const u64 *aos, u64 *soa, size_t n, u32 *flag, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_aos_to_soa_checked, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n, flag);
-}
-void launch_soa_to_aos_unless(const u64 *soa, u64 *aos, size_t n, const u32 *flag, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_soa_to_aos_unless, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n, flag);
-}
-void launch_aos_to_soa_xb(const u64 *aos, u64 *soa, size_t n, const XbMat3 &Ti, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_aos_to_soa_xb, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n, Ti);
-}
-void launch_soa_to_aos_xb(const u64 *soa, u64 *aos, size_t n, const XbMat3 &T, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_soa_to_aos_xb, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n, T);
-}
-void launch_aos_to_soa_checked_xb(const u64 *aos, u64 *soa, size_t n, u32 *flag, const XbMat3 &Ti, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_aos_to_soa_checked_xb, dim3(cdiv(n, 64)), dim3(256), 0, s, aos, soa, n, flag, Ti);
-}
-void launch_soa_to_aos_unless_xb(const u64 *soa, u64 *aos, size_t n, const u32 *flag, const XbMat3 &T, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_soa_to_aos_unless_xb, dim3(cdiv(n, 64)), dim3(256), 0, s, soa, aos, n, flag, T);
-}
-
-__device__ __forceinline__ u64 splitmix_fq(u64 seed, u64 index) {
-    u64 z = seed + (index + 1) * 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    z = z ^ (z >> 31);
-    return z >= LF_P ? z - LF_P : z;
+void launch_fill_ajtai(u64 *A, u32 kappa, size_t n, size_t n_total, size_t col0, u64 seed, hipStream_t s, u32 row0) {
+    lfk::launch_fill_ajtai<GoldF>(A, kappa, n, n_total, col0, seed, s, row0);
 }
 __global__ void __launch_bounds__(256) k_fill_uniform(u64 *dst, size_t words, u64 seed, size_t start) {
     size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, st = (size_t)gridDim.x * 256;
-    for (; i < words; i += st) dst[i] = splitmix_fq(seed, start + i);
+    for (; i < words; i += st) dst[i] = GoldF::splitmix(seed, start + i);
 }
 void launch_fill_uniform(u64 *dst, size_t words, u64 seed, size_t start, hipStream_t s) {
     hipLaunchKernelGGL(k_fill_uniform, dim3(grid_for(words, 4096)), dim3(256), 0, s, dst, words, seed, start);
-}
-__global__ void __launch_bounds__(256) k_fill_ajtai(u64 *A, u32 kappa, size_t n, size_t n_total, size_t col0, u64 seed, u32 row0) {
-    size_t total = (size_t)kappa * 24 * n;
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, st = (size_t)gridDim.x * 256;
-    for (; i < total; i += st) {
-        size_t j = i % n, w = (i / n) % 24, row = row0 + i / (24 * n);
-        A[i] = splitmix_fq(seed, (row * n_total + col0 + j) * 24 + w);
-    }
-}
-// rows [row0, row0 + kappa) of the synthetic matrix into A [kappa][24][n]
-void launch_fill_ajtai(u64 *A, u32 kappa, size_t n, size_t n_total, size_t col0, u64 seed, hipStream_t s, u32 row0) {
-    hipLaunchKernelGGL(k_fill_ajtai, dim3(4096), dim3(256), 0, s, A, kappa, n, n_total, col0, seed, row0);
 }
 
 
@@ -204,27 +85,7 @@ void launch_fill_ajtai(u64 *A, u32 kappa, size_t n, size_t n_total, size_t col0,
 // CRT: structured forward transform.  a(X) = sum_u X^u A_u(X^3); A_u is evaluated at the 8 primitive 24th
 // roots by three radix-2 layers over Y^8 - Y^4 + 1 = (Y^4 - w^4)(Y^4 - w^20), then the per-slot monomial
 // twist maps F_p[X]/(X^3 - zeta_k) onto F_p[Y]/(Y^3 - nu).  (stark-rings CRT; call sites arith.rs:238,327.)
-__device__ __forceinline__ void crt8(const u64 x[8], u64 o[8], const DevCrt &t) {
-    u64 lo[4], hi[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        u64 tt = fq_mul(t.w4, x[i + 4]);
-        lo[i] = fq_add(x[i], tt);
-        hi[i] = fq_sub(fq_add(x[i], x[i + 4]), tt);
-    }
-    u64 l0[2], l1[2], h0[2], h1[2];
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-        u64 tt = fq_mul(t.w2, lo[i + 2]);
-        l0[i] = fq_add(lo[i], tt); l1[i] = fq_sub(lo[i], tt);
-        u64 uu = fq_mul(t.w10, hi[i + 2]);
-        h0[i] = fq_add(hi[i], uu); h1[i] = fq_sub(hi[i], uu);
-    }
-    u64 a = fq_mul(t.w1, l0[1]);  o[0] = fq_add(l0[0], a); o[1] = fq_sub(l0[0], a);
-    u64 b = fq_mul(t.w7, l1[1]);  o[2] = fq_add(l1[0], b); o[3] = fq_sub(l1[0], b);
-    u64 c = fq_mul(t.w5, h0[1]);  o[4] = fq_add(h0[0], c); o[5] = fq_sub(h0[0], c);
-    u64 d = fq_mul(t.w11, h1[1]); o[6] = fq_add(h1[0], d); o[7] = fq_sub(h1[0], d);
-}
+// (the butterflies themselves: lfk::crt8)
 // same butterflies for a TERNARY input (digits in {-1,0,1}): the first layer needs no multiplication (+-w4 or 0)
 __device__ __forceinline__ void crt8_ternary(const int x[8], u64 o[8], const DevCrt &t) {
     u64 lo[4], hi[4];
@@ -274,13 +135,13 @@ __device__ __forceinline__ void crt_store(const u64 a[24], u64 *out, size_t ld, 
     u64 x[8], A0[8], A1[8], A2[8];
 #pragma unroll
     for (int v = 0; v < 8; v++) x[v] = a[3 * v];
-    crt8(x, A0, t);
+    lfk::crt8<GoldF>(x, A0, t);
 #pragma unroll
     for (int v = 0; v < 8; v++) x[v] = a[3 * v + 1];
-    crt8(x, A1, t);
+    lfk::crt8<GoldF>(x, A1, t);
 #pragma unroll
     for (int v = 0; v < 8; v++) x[v] = a[3 * v + 2];
-    crt8(x, A2, t);
+    lfk::crt8<GoldF>(x, A2, t);
 #pragma unroll
     for (int p = 0; p < 8; p++) {
         int s3 = 3 * t.slot_of_pos[p];
@@ -289,17 +150,7 @@ __device__ __forceinline__ void crt_store(const u64 a[24], u64 *out, size_t ld, 
         out[(size_t)(s3 + t.pos2[p]) * ld + j] = fq_mul(t.tw2[p], A2[p]);
     }
 }
-__global__ void __launch_bounds__(256) k_crt_fwd(DevCrt t, const u64 *coef, u64 *ntt, size_t n) {
-    size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
-    u64 a[24];
-#pragma unroll
-    for (int c = 0; c < 24; c++) a[c] = coef[(size_t)c * n + j];
-    crt_store(a, ntt, n, j, t);
-}
-void launch_crt_fwd(const DevCrt &t, const u64 *coef, u64 *ntt, size_t n, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_crt_fwd, dim3(cdiv(n, 256)), dim3(256), 0, s, t, coef, ntt, n);
-}
+void launch_crt_fwd(const DevCrt &t, const u64 *coef, u64 *ntt, size_t n, hipStream_t s) { lfk::launch_crt_fwd<GoldF>(t, coef, ntt, n, s); }
 // ICRT as the dense 24x24 F_p matrix (rare: ingest / export only)
 __global__ void __launch_bounds__(256) k_icrt_dense(const u64 *mat, const u64 *ntt, u64 *coef, size_t n) {
     __shared__ u64 M[24 * 24];
@@ -323,99 +174,16 @@ void launch_icrt_dense(const u64 *mat, const u64 *ntt, u64 *coef, size_t n, hipS
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// balanced decomposition on canonical coefficients, power-of-two base (stark_rings::balanced_decomposition;
-// call sites arith.rs:235, decomposition/utils.rs:23-31,48).  Sign-magnitude, |digit| <= base/2, ties kept.
-__global__ void __launch_bounds__(256) k_decompose(const u64 *coef, size_t n, u32 log_base, u32 digits, int layout, u64 *out, int mode) {
-    size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n * 24) return;
-    size_t c = idx / n, i = idx % n;
-    u64 v = coef[idx];
-    bool neg = v > (LF_P - 1) / 2;
-    u64 mag = neg ? LF_P - v : v;
-    u64 half = 1ULL << (log_base - 1), mask = (1ULL << log_base) - 1;
-    size_t n_out = layout == 0 ? n * digits : n;
-    int64_t cur = neg ? -(int64_t)mag : (int64_t)mag;   // |centred lift| <= (p-1)/2 < 2^63
-    for (u32 k = 0; k < digits; k++) {
-        int64_t dg;
-        if (mode == 1 && log_base > 1) {
-            // digit mode 1 (data, lf_set_digit_mode): floor / Euclidean rule, digits in [-base/2, base/2): rem = cur mod base, minus base if >= base/2
-            int64_t rem = (int64_t)((u64)cur & mask);
-            if ((u64)rem >= half) rem -= (int64_t)(mask + 1);
-            cur = (cur - rem) >> log_base;
-            dg = rem;
-        } else {
-            u64 rem = mag & mask;
-            mag >>= log_base;
-            if (rem > half) { dg = (int64_t)rem - (int64_t)(mask + 1); mag += 1; }
-            else dg = (int64_t)rem;
-            if (neg) dg = -dg;
-        }
-        size_t o = layout == 0 ? (c * n_out + i * digits + k) : ((size_t)k * 24 * n + c * n + i);
-        out[o] = fq_from_i64(dg);
-    }
-}
+// decomposition, int32 planes, l-infinity norm: lf_ring_kernels.cuh
 void launch_decompose(const u64 *coef, size_t n, u64 base, u32 digits, int layout, u64 *out, hipStream_t s, int mode) {
-    u32 lb = 0;
-    while ((1ULL << lb) < base) lb++;
-    if (n) hipLaunchKernelGGL(k_decompose, dim3(cdiv(n * 24, 256)), dim3(256), 0, s, coef, n, lb, digits, layout, out, mode);
+    lfk::launch_decompose<GoldF>(coef, n, base, digits, layout, out, s, mode);
 }
-// out[i] = sum_j base^j in[i*digits + j] on any table (linear, either form)
-__global__ void __launch_bounds__(256) k_recompose(const u64 *in, size_t n_out, u64 base, u32 digits, u64 *out) {
-    size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n_out * 24) return;
-    size_t w = idx / n_out, i = idx % n_out;
-    size_t n_in = n_out * digits;
-    u64 acc = 0, pw = 1;
-    for (u32 j = 0; j < digits; j++) {
-        acc = fq_add(acc, fq_mul(in[w * n_in + i * digits + j], pw));
-        pw = fq_mul(pw, base);
-    }
-    out[idx] = acc;
-}
-void launch_recompose(const u64 *in, size_t n_out, u64 base, u32 digits, u64 *out, hipStream_t s) {
-    if (n_out) hipLaunchKernelGGL(k_recompose, dim3(cdiv(n_out * 24, 256)), dim3(256), 0, s, in, n_out, base % LF_P, digits, out);
-}
-__global__ void __launch_bounds__(256) k_coef_to_i32(const u64 *coef, int32_t *planes, size_t total, u32 bound, int *viol) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, st = (size_t)gridDim.x * 256;
-    int bad = 0;
-    for (; i < total; i += st) {
-        u64 v = coef[i];
-        bool neg = v > (LF_P - 1) / 2;
-        u64 mag = neg ? LF_P - v : v;
-        if (mag > bound) { bad |= 1; mag = 0; }
-        if (!neg && mag > 0x7fffffffull) { bad |= 2; mag = 0; }   // +2^31 (possible only with B = 2^32) has no int32 representation
-        planes[i] = neg ? (int32_t)(0u - (u32)mag) : (int32_t)mag;
-    }
-    if (bad) atomicOr(viol, bad);
-}
+void launch_recompose(const u64 *in, size_t n_out, u64 base, u32 digits, u64 *out, hipStream_t s) { lfk::launch_recompose<GoldF>(in, n_out, base, digits, out, s); }
 void launch_coef_to_i32(const u64 *coef, int32_t *planes, size_t n, u32 bound, int *viol, hipStream_t s) {
-    hipLaunchKernelGGL(k_coef_to_i32, dim3(grid_for(n * 24, 4096)), dim3(256), 0, s, coef, planes, n * 24, bound, viol);
+    lfk::launch_coef_to_i32<GoldF>(coef, planes, n, bound, viol, s);
 }
-__global__ void __launch_bounds__(256) k_i32_to_coef(const int32_t *planes, u64 *coef, size_t total) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, st = (size_t)gridDim.x * 256;
-    for (; i < total; i += st) coef[i] = fq_from_i64(planes[i]);
-}
-void launch_i32_to_coef(const int32_t *planes, u64 *coef, size_t n, hipStream_t s) {
-    hipLaunchKernelGGL(k_i32_to_coef, dim3(grid_for(n * 24, 4096)), dim3(256), 0, s, planes, coef, n * 24);
-}
-__global__ void __launch_bounds__(256) k_linf(const u64 *coef, size_t total, unsigned long long *out_max) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, st = (size_t)gridDim.x * 256;
-    u64 mx = 0;
-    for (; i < total; i += st) {
-        u64 v = coef[i];
-        u64 mag = v > (LF_P - 1) / 2 ? LF_P - v : v;
-        mx = mag > mx ? mag : mx;
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        u64 o = __shfl_down((unsigned long long)mx, off, 64);
-        mx = o > mx ? o : mx;
-    }
-    if ((threadIdx.x & 63) == 0) atomicMax(out_max, (unsigned long long)mx);
-}
-void launch_linf(const u64 *coef, size_t n, u64 *out_max, hipStream_t s) {
-    (void)hipMemsetAsync(out_max, 0, 8, s);
-    hipLaunchKernelGGL(k_linf, dim3(grid_for(n * 24, 4096)), dim3(256), 0, s, coef, n * 24, (unsigned long long *)out_max);
-}
+void launch_i32_to_coef(const int32_t *planes, u64 *coef, size_t n, hipStream_t s) { lfk::launch_i32_to_coef<GoldF>(planes, coef, n, s); }
+void launch_linf(const u64 *coef, size_t n, u64 *out_max, hipStream_t s) { lfk::launch_linf<GoldF>(coef, n, out_max, s); }
 
 
 struct BPow { u64 v[8]; };
@@ -480,7 +248,7 @@ __global__ void __launch_bounds__(256) k_recompose_crt_b4(DevCrt t, const int32_
             }
             x[v8] = sacc < 0 ? LF_P - (u64)(-sacc) : (u64)sacc;
         }
-        crt8(x, A, t);
+        lfk::crt8<GoldF>(x, A, t);
         u64 *o = out + (size_t)k * 24 * ldz;
 #pragma unroll
         for (int p = 0; p < 8; p++) o[(size_t)plane[p] * ldz + jj] = u == 0 ? A[p] : fq_mul(tw[p], A[p]);
@@ -1117,66 +885,19 @@ void launch_fix_final(const DevCrt &t, const u64 *in, u32 rows3, Fq3Const r, u64
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// compute_f_0 (folding.rs:258-268) in the coefficient domain: ICRT(sum_i rho_i (.) f_i) = sum_i rho_i * f_i mod
-// Phi_72 exactly, with rho_i in [-32,32)^24 and f_i the bit-planes -> plain int32 convolutions.
-// Nibble tables.  For one side, sum_k rho_k[a] * digit_k(v_c) = sign(v_c) * sum_nibbles R[nibble][value][a] with
-// R[q][val][a] = sum_{b<4} bit_b(val) rho_{4q+b}[a]: four look-ups of a 24-vector and 24 additions per coefficient c replace the
-// 16 x 24 multiply-adds over the bit-planes.  The tables (both signs, both sides: 2*2*4*16*24 int32 = 24 KB) are built in LDS per block.
-// Sliding window: coefficient c only touches positions c..c+23, so with both sides handled per group of 8 coefficients the positions
-// C0..C0+7 are final after the group; they are stored (before the X^24 wrap) and leave the registers -- 31 live accumulators, not 47.
-template <int C0, int NQ>
-__device__ __forceinline__ void fw_group8(int32_t (&win)[31], const int32_t *pL, const int32_t *pR, size_t n, size_t j,
-                                          const int32_t (*R)[2][NQ][16][28], int32_t *out) {
-#pragma unroll
-    for (int side = 0; side < 2; side++) {
-        const int32_t *pl = side ? pR : pL;
-        int32_t vv[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) vv[i] = pl[(size_t)(C0 + i) * n + j];
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            int32_t v = vv[i];
-            u32 mg = (u32)(v < 0 ? -v : v), sg = v < 0;
-#pragma unroll
-            for (int q = 0; q < NQ; q++) {
-                const int4 *t = (const int4 *)R[side][sg][q][(mg >> (4 * q)) & 15];
-#pragma unroll
-                for (int w = 0; w < 6; w++) {
-                    int4 x = t[w];
-                    win[i + 4 * w] += x.x; win[i + 4 * w + 1] += x.y; win[i + 4 * w + 2] += x.z; win[i + 4 * w + 3] += x.w;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; i++) out[(size_t)(C0 + i) * n + j] = win[i];
-#pragma unroll
-    for (int i = 0; i < 23; i++) win[i] = win[i + 8];
-#pragma unroll
-    for (int i = 23; i < 31; i++) win[i] = 0;
-}
+// compute_f_0 (folding.rs:258-268) in the coefficient domain, mod Phi_72(X) = X^24 - X^12 + 1: the tables and the sliding window are lfk::fw_tables / fw_groups
 template <int NQ>   // nibbles of |v|: 4 for K <= 16 bit-planes, 8 for K <= 32
 __global__ void __launch_bounds__(256) k_fold_witness(const int32_t *planesL, const int32_t *planesR, size_t n, u32 K, const int8_t *rho,
                                                       int32_t *out) {
-    __shared__ __align__(16) int32_t R[2][2][NQ][16][28];   // [side][sign][nibble][value][a]; rows padded to 28 words (bank spread)
-    for (u32 idx = threadIdx.x; idx < 2 * NQ * 16 * 24; idx += 256) {
-        u32 a = idx % 24, val = (idx / 24) % 16, q = (idx / (24 * 16)) % NQ, side = idx / (24 * 16 * NQ);
-        int sum = 0;
-#pragma unroll
-        for (u32 b = 0; b < 4; b++)
-            if (4 * q + b < K && ((val >> b) & 1)) sum += rho[(size_t)(side * K + 4 * q + b) * 24 + a];
-        R[side][0][q][val][a] = sum;
-        R[side][1][q][val][a] = -sum;
-    }
+    __shared__ __align__(16) int32_t R[2][2][NQ][16][28];
+    lfk::fw_tables<NQ>(R, K, rho);
     __syncthreads();
     size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
     int32_t win[31];
 #pragma unroll
     for (int i = 0; i < 31; i++) win[i] = 0;
-    fw_group8<0, NQ>(win, planesL, planesR, n, j, R, out);
-    fw_group8<8, NQ>(win, planesL, planesR, n, j, R, out);
-    fw_group8<16, NQ>(win, planesL, planesR, n, j, R, out);
+    lfk::fw_groups<0, 24, NQ>(win, planesL, planesR, n, j, R, out);
     // win[i] = position 24 + i;  X^24 = X^12 - 1, applied top down (positions >= 36 land on positions >= 24 first)
     int32_t delta[24];
 #pragma unroll

@@ -1,9 +1,11 @@
 // lf_kernels_dev.cuh -- device-side helpers shared by the kernel translation units of the Goldilocks backend (lf_kernels.hip, lf_rounds.hip): the F_{p^3}
-// product wrappers, the nu-specialised launch macro, grid helpers, wave / block reductions, plane-major element access, base-2 digits.
+// product wrappers, the nu-specialised launch macro, grid helpers, wave / block reductions, plane-major element access, base-2 digits, and GoldF, the word
+// policy under which lf_kernels.hip instantiates the ring-generic kernels of lf_ring_kernels.cuh.
 #pragma once
 #include <stddef.h>
 
 #include "lf_kernels.h"
+#include "lf_ring_kernels.cuh"
 
 namespace lf {
 
@@ -17,12 +19,48 @@ template <bool NU> __device__ __forceinline__ Fq3 S3(Fq3 a, u64 nu) { return fq3
         else hipLaunchKernelGGL((KERNEL<false>), grid, block, 0, stream, __VA_ARGS__);        \
     } while (0)
 
-static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
-static inline unsigned grid_for(size_t n, unsigned cap = 2048) {
-    size_t g = (n + 255) / 256;
-    if (g < 1) g = 1;
-    return (unsigned)(g > cap ? cap : g);
-}
+using lfk::cdiv;
+using lfk::grid_for;
+
+// the device word of this ring for lf_ring_kernels.cuh: canonical u64, so both conversions are the identity
+struct GoldF {
+    typedef u64 word;
+    typedef XbMat3 XbMat;
+    static constexpr int RE = 24, TAU = 3;
+    static constexpr u64 P = LF_P;
+    static LF_HD word from_canon(u64 v) { return v; }
+    static LF_HD u64 to_canon(word w) { return w; }
+    static LF_HD word add(word a, word b) { return fq_add(a, b); }
+    static LF_HD word sub(word a, word b) { return fq_sub(a, b); }
+    static LF_HD word mul(word a, word b) { return fq_mul(a, b); }
+    static LF_HD word one() { return 1; }
+    static LF_HD word from_i64(int64_t v) { return fq_from_i64(v); }
+    // workload.py splitmix_fq: SplitMix64 word (index + 1), minus p if not below it
+    static __device__ __forceinline__ u64 splitmix(u64 seed, u64 index) {
+        u64 z = seed + (index + 1) * 0x9E3779B97F4A7C15ULL;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+        z = z ^ (z >> 31);
+        return z >= LF_P ? z - LF_P : z;
+    }
+    // the 64 x 8 (element, slot) jobs of a relayout tile, two per thread, times the 3 x 3 matrix M (wave-uniform: a kernel argument, held in SGPRs).  Lane <->
+    // element, as in the plane pass: the odd row length keeps the 64-bit LDS accesses of a 32-lane half on distinct banks.  Column 0 of M is e_0 (ExtBasis::set),
+    // so a slot costs six products; two products of words < 2^64 and their carry fit the 128-bit + carry accumulator, whatever the words are
+    static __device__ __forceinline__ void xb_slot_pass(u64 (*tile)[RE + 1], const XbMat3 &M) {
+        for (int idx = threadIdx.x; idx < 64 * 8; idx += 256) {
+            u64 *v = &tile[idx % 64][3 * (idx / 64)];
+            const u64 v0 = fq_canon(v[0]), v1 = v[1], v2 = v[2];
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                Acc s;
+                acc_set(s, M.m[3 * i + 1], v1);
+                acc_mad(s, M.m[3 * i + 2], v2);
+                const u64 r = acc_reduce(s);
+                v[i] = i ? r : fq_add(r, v0);
+            }
+        }
+    }
+};
 
 // ---------------------------------------------------------------------------------------------------------
 // reductions

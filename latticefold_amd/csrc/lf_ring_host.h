@@ -172,8 +172,8 @@ int up_ring(C *c, const u64 *host, size_t n, typename Ring<C>::W *dst, Form f) {
     u64 *tmp;
     RET(c->tbuf("stage_aos", n * Ring<C>::RE, &tmp));
     HIPCHK(hipMemcpyAsync(tmp, host, n * Ring<C>::RE * 8, hipMemcpyHostToDevice, c->stream()));
-    if (xb_converts(c, f)) launch_aos_to_soa_xb(tmp, dst, n, Ring<C>::xb_mat(c->xb_Ti), c->stream());
-    else launch_aos_to_soa(tmp, dst, n, c->stream());
+    const auto Ti = Ring<C>::xb_mat(c->xb_Ti);
+    launch_aos_to_soa(tmp, dst, n, c->stream(), nullptr, xb_converts(c, f) ? &Ti : nullptr);
     return LF_OK;
 }
 template <class C>
@@ -181,8 +181,8 @@ int down_ring(C *c, const typename Ring<C>::W *src, size_t n, u64 *host, Form f)
     if (!n) return LF_OK;
     u64 *tmp;
     RET(c->tbuf("stage_aos", n * Ring<C>::RE, &tmp));
-    if (xb_converts(c, f)) launch_soa_to_aos_xb(src, tmp, n, Ring<C>::xb_mat(c->xb_T), c->stream());
-    else launch_soa_to_aos(src, tmp, n, c->stream());
+    const auto T = Ring<C>::xb_mat(c->xb_T);
+    launch_soa_to_aos(src, tmp, n, c->stream(), nullptr, xb_converts(c, f) ? &T : nullptr);
     HIPCHK(hipMemcpyAsync(host, tmp, n * Ring<C>::RE * 8, hipMemcpyDeviceToHost, c->stream()));
     HIPCHK(hipStreamSynchronize(c->stream()));
     return LF_OK;
@@ -192,7 +192,7 @@ int down_ring(C *c, const typename Ring<C>::W *src, size_t n, u64 *host, Form f)
 // Origin::host (every lf_* call without the suffix): pageable host memory, staged through `stage_aos` as above.  Origin::device (the _dev twins): the caller's own
 // memory on the context's device, same AoS layout; the relayout kernels read and write it in place, nothing is staged.  What the host cannot see it lets the
 // device check: the checked relayout raises a flag word on an input word >= p, the flag comes back in front of a synchronise the call performs anyway, results go
-// into the caller's buffer only while the flag is down (launch_soa_to_aos_unless), and the call returns LF_ERR_INVALID.
+// into the caller's buffer only while the flag is down (launch_soa_to_aos's unless_flag), and the call returns LF_ERR_INVALID.
 enum class Origin { host, device };
 // [p, p + bytes) lies inside the allocation [base, base + size): the whole range arithmetic of the pointer checks
 inline bool range_inside(uintptr_t base, size_t size, uintptr_t p, size_t bytes) { return p >= base && p - base <= size && bytes <= size - (p - base); }
@@ -234,20 +234,16 @@ struct DevIo {
 template <class C>
 int up_ring(DevIo<C> &io, const u64 *src, size_t n, typename Ring<C>::W *dst, Form f) {
     if (!io.dev) return up_ring(io.c, src, n, dst, f);
-    if (xb_converts(io.c, f)) launch_aos_to_soa_checked_xb(src, dst, n, io.flag, Ring<C>::xb_mat(io.c->xb_Ti), io.c->stream());   // (the caller's words are tested, then converted)
-    else launch_aos_to_soa_checked(src, dst, n, io.flag, io.c->stream());
+    const auto Ti = Ring<C>::xb_mat(io.c->xb_Ti);
+    launch_aos_to_soa(src, dst, n, io.c->stream(), io.flag, xb_converts(io.c, f) ? &Ti : nullptr);   // (the caller's words are tested, then converted)
     return LF_OK;
 }
 // the result of a call, complete on return; from device inputs that were not canonical: LF_ERR_INVALID and `out` untouched
 template <class C>
 int down_ring(DevIo<C> &io, const typename Ring<C>::W *src, size_t n, u64 *out, Form f) {
     if (!io.dev) return down_ring(io.c, src, n, out, f);
-    const bool xb = xb_converts(io.c, f);
-    if (io.flag) {
-        if (xb) launch_soa_to_aos_unless_xb(src, out, n, io.flag, Ring<C>::xb_mat(io.c->xb_T), io.c->stream());
-        else launch_soa_to_aos_unless(src, out, n, io.flag, io.c->stream());
-    } else if (xb) launch_soa_to_aos_xb(src, out, n, Ring<C>::xb_mat(io.c->xb_T), io.c->stream());
-    else launch_soa_to_aos(src, out, n, io.c->stream());
+    const auto T = Ring<C>::xb_mat(io.c->xb_T);
+    launch_soa_to_aos(src, out, n, io.c->stream(), io.flag, xb_converts(io.c, f) ? &T : nullptr);
     RET(io.fetch());
     HIPCHK(hipStreamSynchronize(io.c->stream()));
     return io.bad() ? LF_ERR_INVALID : LF_OK;

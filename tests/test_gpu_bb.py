@@ -84,7 +84,7 @@ def test_crt_with_other_ring_tables(ctx):
         ctx.set_ring_tables(nr, bad)
 
 
-@pytest.mark.parametrize("count", [1, 7, 256, 1000])
+@pytest.mark.parametrize("count", [1, 7, 63, 64, 65, 256, 1000])   # 63, 64, 65: a partial relayout tile, the tile edge, one element past it
 def test_crt_icrt(ctx, count):
     x = rnd(11 + count, count, RE)
     assert (ctx.crt(x) == lfo.crt(x)).all()

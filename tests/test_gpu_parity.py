@@ -38,7 +38,7 @@ def test_device_arithmetic_selftest(ctx):
 
 
 # ---- element-wise kernels ------------------------------------------------------------------------------
-@pytest.mark.parametrize("count", [1, 7, 256, 1000])
+@pytest.mark.parametrize("count", [1, 7, 63, 64, 65, 256, 1000])   # 63, 64, 65: a partial relayout tile, the tile edge, one element past it
 def test_crt_icrt(ctx, count):
     x = rnd(11 + count, count, RE)
     assert (ctx.crt(x) == lfo.crt(x)).all()
