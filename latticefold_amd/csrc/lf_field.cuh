@@ -327,6 +327,76 @@ LF_HD Fq3 lh5_finish(const LH5 &a) {
     return r;
 }
 
+// ---- three-column lazy sums for NU = 2^40 -------------------------------------------------------------------
+// With bn1 = NU b1 and bn2 = NU b2 formed beforehand, columns 3 and 4 of a product need not exist:
+//   c0 = a0 b0 + a1 bn2 + a2 bn1,   c1 = a0 b1 + a1 b0 + a2 bn2,   c2 = a0 b2 + a1 b1 + a2 b0
+// -- nine accp_mad into three AccP column sums that stay unfolded across the whole sum (27 registers against 20 for LH5, and no accp_lh per product: the fold was
+// the larger half of lh5_mac's instructions); one accp_reduce per column at the very end.  The two multiples cost one 104-bit reduction each and are shared by
+// every product that reuses b (a loop constant, a square used in two products).
+// Range: a counter grows by at most 2 per accp_mad (c01 takes two partial products, c00 and c11 one each), so by at most 6 per product and column; the most
+// products one thread adds into one accumulator anywhere is 3 LF_LAZY_N_MAX = 196 608, which puts every counter below 2^21 against the 2^32 that accp_reduce
+// accepts (c00 (2^32 - 1) < p and c11 2^32 < p for any 32-bit count).  The 64-bit sums wrap by design -- the counters hold the wraps.  LH5's own limit (|sum H| <
+// 2^55 in lh5_finish, 2^21 products) does not exist here.
+struct A3P {
+    AccP c[3];
+};
+LF_HD void a3p_zero(A3P &a) { accp_zero(a.c[0]); accp_zero(a.c[1]); accp_zero(a.c[2]); }
+// some 64-bit representative of 2^40 b for ANY 64-bit b (loose in, loose out): accp_mad takes arbitrary operands, so no canonicalisation
+LF_HD u64 fq_mul_2p40_loose(u64 b) { return fq_reduce128_loose(b << 40, b >> 24); }
+// the pre-multiplied words of an operand b: n1 = NU b1, n2 = NU b2
+struct Fq3Nu {
+    u64 n1, n2;
+};
+LF_HD Fq3Nu fq3_premul_2p40(Fq3 b) { Fq3Nu r; r.n1 = fq_mul_2p40_loose(b.c[1]); r.n2 = fq_mul_2p40_loose(b.c[2]); return r; }
+// acc += a b, bn = fq3_premul_2p40(b) (not computed here)
+LF_HD void a3p_mac(A3P &acc, Fq3 a, Fq3 b, Fq3Nu bn) {
+    accp_mad(acc.c[0], a.c[0], b.c[0]); accp_mad(acc.c[0], a.c[1], bn.n2); accp_mad(acc.c[0], a.c[2], bn.n1);
+    accp_mad(acc.c[1], a.c[0], b.c[1]); accp_mad(acc.c[1], a.c[1], b.c[0]); accp_mad(acc.c[1], a.c[2], bn.n2);
+    accp_mad(acc.c[2], a.c[0], b.c[2]); accp_mad(acc.c[2], a.c[1], b.c[1]); accp_mad(acc.c[2], a.c[2], b.c[0]);
+}
+// canonical: the same words lh5_finish gives for the same products
+LF_HD Fq3 a3p_finish(const A3P &a) { return fq3_make(accp_reduce(a.c[0]), accp_reduce(a.c[1]), accp_reduce(a.c[2])); }
+// reduced product a b with bn = fq3_premul_2p40(b): three columns of three products, three folds (|L| < 2^33.6, |H| < 2^34 as for any column of up to three
+// products: the bound counts 32-bit pieces and holds for loose operands too), no 2^40 term left in the finish.  Canonical, equal to fq3_mul_2p40(a, b).
+LF_HD Fq3 fq3_mul_2p40_pre(Fq3 a, Fq3 b, Fq3Nu bn) {
+    AccP s[3];
+    accp_set(s[0], a.c[0], b.c[0]); accp_mad(s[0], a.c[1], bn.n2); accp_mad(s[0], a.c[2], bn.n1);
+    accp_set(s[1], a.c[0], b.c[1]); accp_mad(s[1], a.c[1], b.c[0]); accp_mad(s[1], a.c[2], bn.n2);
+    accp_set(s[2], a.c[0], b.c[2]); accp_mad(s[2], a.c[1], b.c[1]); accp_mad(s[2], a.c[2], b.c[0]);
+    Fq3 r;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        LH c = accp_lh(s[i]);
+        r.c[i] = fq_from_lin(c.l, c.h, 0);
+    }
+    return r;
+}
+// The register-lean form of the same idea: the three nu-folded columns of each product are folded to (L, H) and added as in LH5 -- three folds per product instead
+// of five, 12 registers per accumulator instead of 20 (A3P: none and 27).  Per product and column |L| < 2^33.6, |H| < 2^34 (three partial-product sums, as above);
+// nothing is scaled in the finish, so fq_from_lin_wide's 2^62 allows 2^28 products.
+struct LH3 {
+    LH c[3];
+};
+LF_HD void lh3_zero(LH3 &a) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) { a.c[i].l = 0; a.c[i].h = 0; }
+}
+LF_HD void lh3_mac(LH3 &acc, Fq3 a, Fq3 b, Fq3Nu bn) {
+    AccP s[3];
+    accp_set(s[0], a.c[0], b.c[0]); accp_mad(s[0], a.c[1], bn.n2); accp_mad(s[0], a.c[2], bn.n1);
+    accp_set(s[1], a.c[0], b.c[1]); accp_mad(s[1], a.c[1], b.c[0]); accp_mad(s[1], a.c[2], bn.n2);
+    accp_set(s[2], a.c[0], b.c[2]); accp_mad(s[2], a.c[1], b.c[1]); accp_mad(s[2], a.c[2], b.c[0]);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        LH t = accp_lh(s[i]);
+        acc.c[i].l += t.l;
+        acc.c[i].h += t.h;
+    }
+}
+LF_HD Fq3 lh3_finish(const LH3 &a) {
+    return fq3_make(fq_from_lin_wide(a.c[0].l, a.c[0].h, 0), fq_from_lin_wide(a.c[1].l, a.c[1].h, 0), fq_from_lin_wide(a.c[2].l, a.c[2].h, 0));
+}
+
 // generic-NU product: schoolbook, 9 base multiplications, lazy 128-bit column sums, 5 reductions
 template <bool NU2P40>
 LF_HD Fq3 fq3_mul(Fq3 a, Fq3 b, u64 nu) {

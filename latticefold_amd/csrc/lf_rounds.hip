@@ -727,10 +727,22 @@ __device__ __forceinline__ u32 digit_code4(const int32_t *v, u32 k) {
 // T(X) = sum_p E_i[p] (Q0 + Q1 X + Q2 X^2 + Q3 X^3)(p).  The kernel leaves  sum_p E_i[p] Q_e(p), e = 0..2  (three values per slot instead of five evaluations; the G part
 // comes from k_fold_round_g); the host takes sum E Q3 from g(0) + g(1) = the previous message at its challenge.  Q3 is the only coefficient that needs the
 // fourth lazy product of a table (P3): three products per table instead of four.
-template <bool NU, int MODE, bool SPLIT = false>
+// FORM (2^40 non-residue, modes 1, 6, 7): how the lazy sums and the reduced products of a table are formed -- same values in every form.
+//   0  LH5: five columns per product, folded to (L, H) per product (mode 6: per two products), reduced products through fq3_mul_2p40
+//   1  A3P: three nu-folded AccP columns that stay unfolded across the tables, the squares pre-multiplied once for their two products; mode 7's X Y against a
+//      pre-multiplied operand (fq3_mul_2p40_pre).  27 registers per accumulator: the split kernels (three accumulators) keep two waves per SIMD with it, the plain
+//      ones (four) do not, so those stay on form 0
+//   2  LH3 (mode 1): three nu-folded columns folded per product, 12 registers per accumulator, and every reduced product of the table against a pre-multiplied
+//      operand (the fix challenge once per kernel, mu_kd once per table, a square's own words).  Form 1 costs this mode its second wave and measured slower
+// The defaults are the forms that measured faster at 2^20 rows.
+constexpr int fold_form(bool nu, int mode, bool split) { return !nu ? 0 : ((mode == 6 || mode == 7) && split) ? 1 : mode == 1 ? 2 : 0; }
+template <bool NU, int MODE, bool SPLIT = false, int FORM = fold_form(NU, MODE, SPLIT)>
 __global__ void __launch_bounds__(256) k_fold_round(DevCrt t, FoldRoundArgs a, const u64 *F, size_t ldF, u32 K, const Fq3Const *mu_pow,
                                                     FoldSrc src, u64 *partial) {
     static_assert(!SPLIT || (NU && (MODE == 1 || MODE == 6 || MODE == 7)), "split form: the large-round modes of the 2^40 non-residue path");
+    static_assert(FORM == 0 || (NU && (MODE == 1 || MODE == 6 || MODE == 7)), "three-column sums: modes 1, 6, 7 of the 2^40 non-residue path");
+    static_assert(FORM != 2 || MODE == 1, "folded three-column sums: mode 1");
+    constexpr bool COL3 = FORM == 1, PRE = FORM != 0;
     constexpr int NA = SPLIT ? 3 : 5;   // SPLIT: the G part comes from its own small kernel (k_fold_round_g) -- three live accumulators instead of five
     u32 slot = blockIdx.y;
     const size_t pend = a.p0 + a.pcnt;
@@ -741,6 +753,7 @@ __global__ void __launch_bounds__(256) k_fold_round(DevCrt t, FoldRoundArgs a, c
     if (MODE == 1) { F -= 4 * a.pF0; src.out -= 2 * a.pF0; }   // fused fix: previous tables from entry 4 pF0, the fixed ones from entry 2 pF0
     if ((MODE == 4 || MODE == 6 || MODE == 7) && src.out) src.out -= 2 * a.pF0;   // first materialised tables of a rank's slice
     const Fq3 rfix = fq3_make(src.r.c[0], src.r.c[1], src.r.c[2]);
+    const Fq3Nu rfixn = fq3_premul_2p40(rfix);      // (forms 1, 2 of mode 1: the fix challenge is the pre-multiplied operand of both fix products)
     __shared__ u64 slut[MODE == 7 ? 4 * 81 * 3 : (MODE >= 3 ? 3 * 81 * 3 : 1)];   // (mode 5 uses the values only)   // the 81 values, their squares, (mode 4) r times the values
     if (MODE == 7) {   // the four tables A', B', C', D'
         for (u32 i = threadIdx.x; i < 4 * 81; i += 256) {
@@ -779,8 +792,14 @@ __global__ void __launch_bounds__(256) k_fold_round(DevCrt t, FoldRoundArgs a, c
                 ulonglong2 a0 = *(const ulonglong2 *)(fp), a1 = *(const ulonglong2 *)(fp + ldF), a2 = *(const ulonglong2 *)(fp + 2 * ldF);
                 ulonglong2 b0 = *(const ulonglong2 *)(fp + 2), b1 = *(const ulonglong2 *)(fp + ldF + 2), b2 = *(const ulonglong2 *)(fp + 2 * ldF + 2);
                 Fq3 lo = fq3_make(a0.x, a1.x, a2.x), hi = fq3_make(b0.x, b1.x, b2.x);
-                f0 = fq3_add(lo, M3<NU>(fq3_sub(fq3_make(a0.y, a1.y, a2.y), lo), rfix, nu));
-                Fq3 f1 = fq3_add(hi, M3<NU>(fq3_sub(fq3_make(b0.y, b1.y, b2.y), hi), rfix, nu));
+                Fq3 f1;
+                if constexpr (PRE) {
+                    f0 = fq3_add(lo, fq3_mul_2p40_pre(fq3_sub(fq3_make(a0.y, a1.y, a2.y), lo), rfix, rfixn));
+                    f1 = fq3_add(hi, fq3_mul_2p40_pre(fq3_sub(fq3_make(b0.y, b1.y, b2.y), hi), rfix, rfixn));
+                } else {
+                    f0 = fq3_add(lo, M3<NU>(fq3_sub(fq3_make(a0.y, a1.y, a2.y), lo), rfix, nu));
+                    f1 = fq3_add(hi, M3<NU>(fq3_sub(fq3_make(b0.y, b1.y, b2.y), hi), rfix, nu));
+                }
                 u64 *op = src.out + ((size_t)kd * 24 + 3 * slot) * src.ldo + 2 * p;
                 *(ulonglong2 *)(op) = make_ulonglong2(f0.c[0], f1.c[0]);
                 *(ulonglong2 *)(op + src.ldo) = make_ulonglong2(f0.c[1], f1.c[1]);
@@ -868,7 +887,9 @@ __global__ void __launch_bounds__(256) k_fold_round(DevCrt t, FoldRoundArgs a, c
             Q[3] = a3;
         } else if (NU && MODE == 7) {
             LH5 A0, A1, A2, A3;
-            lh5_zero(A0); lh5_zero(A1); lh5_zero(A2); lh5_zero(A3);
+            A3P B0, B1, B2, B3;
+            if constexpr (COL3) { a3p_zero(B0); a3p_zero(B1); a3p_zero(B2); a3p_zero(B3); }
+            else { lh5_zero(A0); lh5_zero(A1); lh5_zero(A2); lh5_zero(A3); }
             Fq3 sp = fq3_zero(), su = fq3_zero();
             for (u32 kd = kd0; kd < kd1; kd++) {     // (pairing the tables as in mode 6 needs 408 registers here)
                 const u32 side = kd / (3 * K), k = (kd / 3) % K, d = kd % 3;
@@ -896,7 +917,9 @@ __global__ void __launch_bounds__(256) k_fold_round(DevCrt t, FoldRoundArgs a, c
                     const ulonglong2 m2 = *(const ulonglong2 *)(mt + 4 * (162 + c2)), m3 = *(const ulonglong2 *)(mt + 4 * (243 + c3));
                     const u64 m0c = mt[4 * c0 + 2], m1c = mt[4 * (81 + c1) + 2], m2c = mt[4 * (162 + c2) + 2], m3c = mt[4 * (243 + c3) + 2];
                     const Fq3 X = fq3_add(lut3(c0), lut3(81 + c1)), Y = fq3_add(lut3(162 + c2), lut3(243 + c3));
-                    const Fq3 xy = fq3_mul_2p40(X, Y);
+                    Fq3 xy;
+                    if constexpr (COL3) xy = fq3_mul_2p40_pre(X, Y, fq3_premul_2p40(Y));
+                    else xy = fq3_mul_2p40(X, Y);
                     fv[e] = fq3_add(X, Y);
                     sq[e] = fq3_add(fq3_add(fq3_make(xa.x, xa.y, xc), fq3_make(ya.x, ya.y, yc)), fq3_add(xy, xy));
                     mf[e] = fq3_add(fq3_add(fq3_make(m0.x, m0.y, m0c), fq3_make(m1.x, m1.y, m1c)), fq3_add(fq3_make(m2.x, m2.y, m2c), fq3_make(m3.x, m3.y, m3c)));
@@ -905,23 +928,31 @@ __global__ void __launch_bounds__(256) k_fold_round(DevCrt t, FoldRoundArgs a, c
                 *(ulonglong2 *)(op) = make_ulonglong2(fv[0].c[0], fv[1].c[0]);
                 *(ulonglong2 *)(op + src.ldo) = make_ulonglong2(fv[0].c[1], fv[1].c[1]);
                 *(ulonglong2 *)(op + 2 * src.ldo) = make_ulonglong2(fv[0].c[2], fv[1].c[2]);
-                lh5_mac(A0, mf[0], sq[0]); lh5_mac(A1, mf[1], sq[0]); lh5_mac(A2, mf[0], sq[1]);
-                if constexpr (!SPLIT) lh5_mac(A3, mf[1], sq[1]);
+                if constexpr (COL3) {     // each square is pre-multiplied once and used in both of its products
+                    const Fq3Nu n0 = fq3_premul_2p40(sq[0]), n1 = fq3_premul_2p40(sq[1]);
+                    a3p_mac(B0, mf[0], sq[0], n0); a3p_mac(B1, mf[1], sq[0], n0); a3p_mac(B2, mf[0], sq[1], n1);
+                    if constexpr (!SPLIT) a3p_mac(B3, mf[1], sq[1], n1);
+                } else {
+                    lh5_mac(A0, mf[0], sq[0]); lh5_mac(A1, mf[1], sq[0]); lh5_mac(A2, mf[0], sq[1]);
+                    if constexpr (!SPLIT) lh5_mac(A3, mf[1], sq[1]);
+                }
                 sp = fq3_add(sp, mf[0]); su = fq3_add(su, mf[1]);
             }
-            Fq3 P0 = lh5_finish(A0), P1 = lh5_finish(A1), P2 = lh5_finish(A2);
+            Fq3 P0 = COL3 ? a3p_finish(B0) : lh5_finish(A0), P1 = COL3 ? a3p_finish(B1) : lh5_finish(A1), P2 = COL3 ? a3p_finish(B2) : lh5_finish(A2);
             Fq3 a1 = fq3_sub(P1, P0);
             Fq3 a2 = fq3_add(fq3_sub(P2, fq3_add(P1, P1)), P0);
             Q[0] = fq3_sub(P0, sp);
             Q[1] = fq3_sub(fq3_add(fq3_add(a1, a1), a1), fq3_sub(su, sp));
             Q[2] = fq3_add(fq3_add(a2, a2), a2);
             if constexpr (!SPLIT) {
-                Fq3 P3 = lh5_finish(A3), p12 = fq3_sub(P1, P2);
+                Fq3 P3 = COL3 ? a3p_finish(B3) : lh5_finish(A3), p12 = fq3_sub(P1, P2);
                 Q[3] = fq3_add(fq3_sub(P3, P0), fq3_add(fq3_add(p12, p12), p12));
             } else Q[3] = fq3_zero();
         } else if (NU && MODE == 6) {
             LH5 A0, A1, A2, A3;
-            lh5_zero(A0); lh5_zero(A1); lh5_zero(A2); lh5_zero(A3);
+            A3P B0, B1, B2, B3;
+            if constexpr (COL3) { a3p_zero(B0); a3p_zero(B1); a3p_zero(B2); a3p_zero(B3); }
+            else { lh5_zero(A0); lh5_zero(A1); lh5_zero(A2); lh5_zero(A3); }
             Fq3 sp = fq3_zero(), su = fq3_zero();
             // operands of table kd's four lazy products: gathers, no multiplication (and the fixed pair stored for round 5)
             auto gen = [&](u32 kd, Fq3 &tt, Fq3 &uu, Fq3 &s0, Fq3 &s1) {
@@ -961,27 +992,37 @@ __global__ void __launch_bounds__(256) k_fold_round(DevCrt t, FoldRoundArgs a, c
                 sp = fq3_add(sp, tt); su = fq3_add(su, uu);
             };
             u32 kd = kd0;
-            for (; kd + 1 < kd1; kd += 2) {     // two tables per iteration: their partial products share the column sums (lh5_mac2)
-                Fq3 tA, uA, xA, yA, tB, uB, xB, yB;
-                gen(kd, tA, uA, xA, yA);
-                gen(kd + 1, tB, uB, xB, yB);
-                lh5_mac2(A0, tA, xA, tB, xB); lh5_mac2(A1, uA, xA, uB, xB); lh5_mac2(A2, tA, yA, tB, yB);
-                if constexpr (!SPLIT) lh5_mac2(A3, uA, yA, uB, yB);
+            if constexpr (COL3) {     // unfolded column sums: nothing to share between tables, one table per iteration
+                for (; kd < kd1; kd++) {
+                    Fq3 tA, uA, xA, yA;
+                    gen(kd, tA, uA, xA, yA);
+                    const Fq3Nu xn = fq3_premul_2p40(xA), yn = fq3_premul_2p40(yA);
+                    a3p_mac(B0, tA, xA, xn); a3p_mac(B1, uA, xA, xn); a3p_mac(B2, tA, yA, yn);
+                    if constexpr (!SPLIT) a3p_mac(B3, uA, yA, yn);
+                }
+            } else {
+                for (; kd + 1 < kd1; kd += 2) {     // two tables per iteration: their partial products share the column sums (lh5_mac2)
+                    Fq3 tA, uA, xA, yA, tB, uB, xB, yB;
+                    gen(kd, tA, uA, xA, yA);
+                    gen(kd + 1, tB, uB, xB, yB);
+                    lh5_mac2(A0, tA, xA, tB, xB); lh5_mac2(A1, uA, xA, uB, xB); lh5_mac2(A2, tA, yA, tB, yB);
+                    if constexpr (!SPLIT) lh5_mac2(A3, uA, yA, uB, yB);
+                }
+                if (kd < kd1) {
+                    Fq3 tA, uA, xA, yA;
+                    gen(kd, tA, uA, xA, yA);
+                    lh5_mac(A0, tA, xA); lh5_mac(A1, uA, xA); lh5_mac(A2, tA, yA);
+                    if constexpr (!SPLIT) lh5_mac(A3, uA, yA);
+                }
             }
-            if (kd < kd1) {
-                Fq3 tA, uA, xA, yA;
-                gen(kd, tA, uA, xA, yA);
-                lh5_mac(A0, tA, xA); lh5_mac(A1, uA, xA); lh5_mac(A2, tA, yA);
-                if constexpr (!SPLIT) lh5_mac(A3, uA, yA);
-            }
-            Fq3 P0 = lh5_finish(A0), P1 = lh5_finish(A1), P2 = lh5_finish(A2);
+            Fq3 P0 = COL3 ? a3p_finish(B0) : lh5_finish(A0), P1 = COL3 ? a3p_finish(B1) : lh5_finish(A1), P2 = COL3 ? a3p_finish(B2) : lh5_finish(A2);
             Fq3 a1 = fq3_sub(P1, P0);                                           // sum mu f0^2 df
             Fq3 a2 = fq3_add(fq3_sub(P2, fq3_add(P1, P1)), P0);                 // sum mu f0 df^2
             Q[0] = fq3_sub(P0, sp);
             Q[1] = fq3_sub(fq3_add(fq3_add(a1, a1), a1), fq3_sub(su, sp));
             Q[2] = fq3_add(fq3_add(a2, a2), a2);
             if constexpr (!SPLIT) {
-                Fq3 P3 = lh5_finish(A3), p12 = fq3_sub(P1, P2);
+                Fq3 P3 = COL3 ? a3p_finish(B3) : lh5_finish(A3), p12 = fq3_sub(P1, P2);
                 Q[3] = fq3_add(fq3_sub(P3, P0), fq3_add(fq3_add(p12, p12), p12)); // sum mu df^3
             } else Q[3] = fq3_zero();
         } else if (NU && MODE == 3) {
@@ -1023,7 +1064,16 @@ __global__ void __launch_bounds__(256) k_fold_round(DevCrt t, FoldRoundArgs a, c
             // sum_kd mu (f0 + X df)^3 - mu (f0 + X df):  with p = mu f0, q = mu df the cubic coefficients are
             //   sum p f0^2,  3 sum q f0^2,  3 sum p df^2,  sum q df^2   -- four LAZY sums, 4 reduced products per table
             LH5 A0, A1, A2, A3;
-            lh5_zero(A0); lh5_zero(A1); lh5_zero(A2); lh5_zero(A3);
+            A3P B0, B1, B2, B3;
+            LH3 C0, C1, C2, C3;
+            if constexpr (FORM == 1) { a3p_zero(B0); a3p_zero(B1); a3p_zero(B2); a3p_zero(B3); }
+            else if constexpr (FORM == 2) { lh3_zero(C0); lh3_zero(C1); lh3_zero(C2); lh3_zero(C3); }
+            else { lh5_zero(A0); lh5_zero(A1); lh5_zero(A2); lh5_zero(A3); }
+            auto fin = [&](const LH5 &x, const A3P &y, const LH3 &z) {
+                if constexpr (FORM == 1) return a3p_finish(y);
+                else if constexpr (FORM == 2) return lh3_finish(z);
+                else return lh5_finish(x);
+            };
             Fq3 sp = fq3_zero(), sq = fq3_zero();
             // (pairing the tables of a step as in mode 6 -- lh5_mac2 -- costs this branch its second wave per SIMD: 268 registers with the fused fix)
             for (u32 kd = kd0; kd < kd1; kd++) {
@@ -1031,17 +1081,32 @@ __global__ void __launch_bounds__(256) k_fold_round(DevCrt t, FoldRoundArgs a, c
                 load_pair(kd, f0, df);
                 Fq3Const mc = mu_pow[kd];
                 Fq3 mu = fq3_make(mc.c[0], mc.c[1], mc.c[2]);
-                Fq3 f0s = fq3_mul_2p40(f0, f0), dfs = fq3_mul_2p40(df, df);
-                Fq3 pp = fq3_mul_2p40(mu, f0), qq = fq3_mul_2p40(mu, df);
-                lh5_mac(A0, pp, f0s); lh5_mac(A1, qq, f0s); lh5_mac(A2, pp, dfs);
-                if constexpr (!SPLIT) lh5_mac(A3, qq, dfs);
-                sp = fq3_add(sp, pp); sq = fq3_add(sq, qq);
+                if constexpr (PRE) {     // mu_kd pre-multiplied once per table, each square once for its two lazy products
+                    const Fq3Nu mun = fq3_premul_2p40(mu);
+                    const Fq3 f0s = fq3_mul_2p40_pre(f0, f0, fq3_premul_2p40(f0)), dfs = fq3_mul_2p40_pre(df, df, fq3_premul_2p40(df));
+                    const Fq3 pp = fq3_mul_2p40_pre(f0, mu, mun), qq = fq3_mul_2p40_pre(df, mu, mun);
+                    const Fq3Nu f0n = fq3_premul_2p40(f0s), dfn = fq3_premul_2p40(dfs);
+                    if constexpr (FORM == 1) {
+                        a3p_mac(B0, pp, f0s, f0n); a3p_mac(B1, qq, f0s, f0n); a3p_mac(B2, pp, dfs, dfn);
+                        if constexpr (!SPLIT) a3p_mac(B3, qq, dfs, dfn);
+                    } else {
+                        lh3_mac(C0, pp, f0s, f0n); lh3_mac(C1, qq, f0s, f0n); lh3_mac(C2, pp, dfs, dfn);
+                        if constexpr (!SPLIT) lh3_mac(C3, qq, dfs, dfn);
+                    }
+                    sp = fq3_add(sp, pp); sq = fq3_add(sq, qq);
+                } else {
+                    Fq3 f0s = fq3_mul_2p40(f0, f0), dfs = fq3_mul_2p40(df, df);
+                    Fq3 pp = fq3_mul_2p40(mu, f0), qq = fq3_mul_2p40(mu, df);
+                    lh5_mac(A0, pp, f0s); lh5_mac(A1, qq, f0s); lh5_mac(A2, pp, dfs);
+                    if constexpr (!SPLIT) lh5_mac(A3, qq, dfs);
+                    sp = fq3_add(sp, pp); sq = fq3_add(sq, qq);
+                }
             }
-            Fq3 t1 = lh5_finish(A1), t2 = lh5_finish(A2);
-            Q[0] = fq3_sub(lh5_finish(A0), sp);
+            Fq3 t1 = fin(A1, B1, C1), t2 = fin(A2, B2, C2);
+            Q[0] = fq3_sub(fin(A0, B0, C0), sp);
             Q[1] = fq3_sub(fq3_add(fq3_add(t1, t1), t1), sq);
             Q[2] = fq3_add(fq3_add(t2, t2), t2);
-            if constexpr (!SPLIT) Q[3] = lh5_finish(A3);
+            if constexpr (!SPLIT) Q[3] = fin(A3, B3, C3);
             else Q[3] = fq3_zero();
         } else {
             Q[0] = Q[1] = Q[2] = Q[3] = fq3_zero();
