@@ -262,6 +262,94 @@ impl HipContext {
     }
 }
 
+/// Device-resident callers (`include/lfhip.h`, "device-resident callers"): the component calls on arrays that already live on the context's device (a
+/// `hipMalloc` of the caller's, another library's buffer), read and written in place in the layout of the host ABI -- AoS canonical little-endian `u64`, a ring
+/// element = `lf_ring_words` words.  The crate has no device-memory type of its own, so the arrays are raw device addresses; points, challenges, coefficients
+/// and small results stay host slices.  The library checks every address before it launches anything (memory of this device, 8-byte aligned, the whole range
+/// inside one allocation: `HipError` from `LF_ERR_INVALID` otherwise) and has the device test the input words (a word >= p: the same error, outputs
+/// untouched, no sumcheck begun).  Order the context behind the stream that produced an input with [`HipContext::wait_stream`], or synchronise that stream.
+///
+/// The HOST slices are checked here against the counts, as the host methods above check theirs (`assert`: a short slice would be an out-of-bounds read that
+/// the library cannot see).
+///
+/// # Safety
+/// Every method: the device ranges named in its comment must stay allocated, and must not be written by anyone else, until the call returns.
+impl HipContext {
+    /// (words of a ring element, words of an F_{p^tau} challenge) on this context's ring
+    fn word_counts(&self) -> (usize, usize) {
+        // SAFETY: raw is a live context; the two size queries take the ring id by value
+        unsafe {
+            let ring = sys::lf_ctx_ring(self.raw);
+            (sys::lf_ring_words(ring) as usize, sys::lf_ring_tau(ring) as usize)
+        }
+    }
+    /// `lf_ctx_wait_stream`: the context's streams wait for what is enqueued so far on `hip_stream` (a `hipStream_t`; null = the default stream)
+    pub unsafe fn wait_stream(&self, hip_stream: *mut core::ffi::c_void) -> Result<(), HipError> {
+        // SAFETY: the caller vouches for the device ranges (see the impl); host slices were checked above
+        chk(unsafe { sys::lf_ctx_wait_stream(self.raw, hip_stream) }, "lf_ctx_wait_stream")
+    }
+    /// `coeff_in`: count elements, `out`: count * digits elements (layout 0: element-major digits, 1: `digits` tables); the ranges may not overlap
+    pub unsafe fn decompose_dev(&self, coeff_in: *const u64, count: usize, base: u64, digits: u32, layout: i32, out: *mut u64) -> Result<(), HipError> {
+        // SAFETY: the caller vouches for the device ranges (see the impl); host slices were checked above
+        chk(unsafe { sys::lf_decompose_dev(self.raw, coeff_in, count, base, digits, layout, out) }, "lf_decompose_dev")
+    }
+    /// `inp`: count_out * digits elements, `out`: count_out elements; the ranges may not overlap
+    pub unsafe fn recompose_dev(&self, inp: *const u64, count_out: usize, base: u64, digits: u32, out: *mut u64) -> Result<(), HipError> {
+        // SAFETY: the caller vouches for the device ranges (see the impl); host slices were checked above
+        chk(unsafe { sys::lf_recompose_dev(self.raw, inp, count_out, base, digits, out) }, "lf_recompose_dev")
+    }
+    /// `f_ntt`: count elements (NTT form); returns (max < bound, max) -- `unsigned_variant`: the literal `Witness::within_bound`
+    pub unsafe fn linf_check_dev(&self, f_ntt: *const u64, count: usize, bound: u64, unsigned_variant: bool) -> Result<(bool, u64), HipError> {
+        let (mut ok, mut max) = (0i32, 0u64);
+        // SAFETY: the caller vouches for the device ranges (see the impl); host slices were checked above
+        chk(unsafe { sys::lf_linf_check_dev(self.raw, f_ntt, count, bound, unsigned_variant as i32, &mut ok, &mut max) }, "lf_linf_check_dev")?;
+        Ok((ok != 0, max))
+    }
+    /// `point`: nv challenges of tau words (host); `out`: (1 << nv) * tau words on the device
+    pub unsafe fn build_eq_dev(&self, point: &[u64], nv: u32, out: *mut u64) -> Result<(), HipError> {
+        assert_eq!(point.len(), nv as usize * self.word_counts().1);
+        // SAFETY: the caller vouches for the device ranges (see the impl); host slices were checked above
+        chk(unsafe { sys::lf_build_eq_dev(self.raw, point.as_ptr(), nv, out) }, "lf_build_eq_dev")
+    }
+    /// `tables`: ntables x len elements on the device; `out`: ntables elements (host)
+    pub unsafe fn mle_eval_batch_dev(&self, tables: *const u64, ntables: usize, len: usize, point: &[u64], nv: u32, out: &mut [u64]) -> Result<(), HipError> {
+        let (re, tau) = self.word_counts();
+        assert_eq!(point.len(), nv as usize * tau);
+        assert_eq!(out.len(), ntables * re);
+        // SAFETY: the caller vouches for the device ranges (see the impl); host slices were checked above
+        chk(unsafe { sys::lf_mle_eval_batch_dev(self.raw, tables, ntables, len, point.as_ptr(), nv, out.as_mut_ptr()) }, "lf_mle_eval_batch_dev")
+    }
+    /// `mat_vec_mul` with matrix j of the loaded CCS: `z`: n elements, `out`: m elements; the ranges may not overlap
+    pub unsafe fn spmv_dev(&self, j: u32, z: *const u64, out: *mut u64) -> Result<(), HipError> {
+        // SAFETY: the caller vouches for the device ranges (see the impl); host slices were checked above
+        chk(unsafe { sys::lf_spmv_dev(self.raw, j, z, out) }, "lf_spmv_dev")
+    }
+    /// `tables`: t x m elements on the device; the rounds are `lf_sumcheck_lin_round` / `_end` as after a host begin
+    pub unsafe fn sumcheck_lin_begin_dev(&self, tables: *const u64, eq_point: &[u64]) -> Result<(), HipError> {
+        assert_eq!(eq_point.len(), self.params()?.s as usize * self.word_counts().1);
+        // SAFETY: the caller vouches for the device ranges (see the impl); host slices were checked above
+        chk(unsafe { sys::lf_sumcheck_lin_begin_dev(self.raw, tables, eq_point.as_ptr()) }, "lf_sumcheck_lin_begin_dev")
+    }
+    /// `tables`: (5 + 2 K tau) x m elements on the device; `mu`: 2 K challenges of tau words (host)
+    pub unsafe fn sumcheck_fold_begin_dev(&self, tables: *const u64, mu: &[u64]) -> Result<(), HipError> {
+        assert_eq!(mu.len(), 2 * self.params()?.K as usize * self.word_counts().1);
+        // SAFETY: the caller vouches for the device ranges (see the impl); host slices were checked above
+        chk(unsafe { sys::lf_sumcheck_fold_begin_dev(self.raw, tables, mu.as_ptr()) }, "lf_sumcheck_fold_begin_dev")
+    }
+    /// `compute_f_0`: `coef`: n_terms elements (host), `tables`: n_terms x len elements, `out`: len elements; the device ranges may not overlap
+    pub unsafe fn lincomb_dev(&self, coef: &[u64], tables: *const u64, n_terms: usize, len: usize, out: *mut u64) -> Result<(), HipError> {
+        assert_eq!(coef.len(), n_terms * self.word_counts().0);
+        // SAFETY: the caller vouches for the device ranges (see the impl); host slices were checked above
+        chk(unsafe { sys::lf_lincomb_dev(self.raw, coef.as_ptr(), tables, n_terms, len, out) }, "lf_lincomb_dev")
+    }
+    /// `calculate_challenged_mz_mle`: `tables`: groups x per_group x len elements, `challenges`: groups x tau words (host), `out`: len elements
+    pub unsafe fn horner_combine_dev(&self, tables: *const u64, groups: usize, per_group: usize, len: usize, challenges: &[u64], out: *mut u64) -> Result<(), HipError> {
+        assert_eq!(challenges.len(), groups * self.word_counts().1);
+        // SAFETY: the caller vouches for the device ranges (see the impl); host slices were checked above
+        chk(unsafe { sys::lf_horner_combine_dev(self.raw, tables, groups, per_group, len, challenges.as_ptr(), out) }, "lf_horner_combine_dev")
+    }
+}
+
 impl Drop for HipContext {
     fn drop(&mut self) {
         // SAFETY: raw came from lf_ctx_create_ring and is destroyed exactly once

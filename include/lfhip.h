@@ -378,6 +378,32 @@ int lf_witness_get_f_dev(lf_ctx *, const lf_witness *, uint64_t *out /* N, NTT *
 int lf_witness_get_w_ccs_dev(lf_ctx *, const lf_witness *, uint64_t *out /* wit_len, NTT */);
 /* lf_ccs_check on a device z (n NTT elements); *first_bad is a host word.  For general CSR rows z itself is the element-major copy the rows gather from */
 int lf_ccs_check_dev(lf_ctx *, const uint64_t *z, uint64_t *first_bad /* host */);
+/* The component calls (balanced_decomposition, mat_vec_mul, DenseMultilinearExtension evaluation, MLSumcheck::prove_as_subprotocol, compute_f_0,
+ * calculate_challenged_mz_mle) on device tables.  Device memory: the arrays marked `dev` below; every other pointer stays a host pointer (points, challenges,
+ * coefficients, mu, ok / max_out, the ntables evaluations of lf_mle_eval_batch_dev).
+ *   Overlap: lf_decompose_dev, lf_recompose_dev, lf_spmv_dev, lf_lincomb_dev and lf_horner_combine_dev refuse ANY overlap of an input range with `out`
+ * (LF_ERR_INVALID, nothing launched): input and output sizes differ, an in-place form has no meaning.
+ *   Non-canonical input: as above, and host results (ok, max_out, the evaluations) stay unwritten too.  A begin whose tables hold a word >= p begins nothing:
+ * the next _round is LF_ERR_STATE, exactly as before any begin (a sumcheck that was in progress on the context is over: its tables were overwritten).  The
+ * slot-constant test of the three eq tables of lf_sumcheck_fold_begin_dev runs on the device (LF_ERR_UNSUPPORTED, as the host twin).
+ *   lf_decompose_dev, layout 1: none of the `digits` tables is written unless all are.  lf_build_eq_dev has no device input, so nothing of it can be refused
+ * after the pointer check; in an external basis its entries are converted by the kernel that stores them.  lf_spmv_dev on general CSR rows (Goldilocks)
+ * gathers from the caller's z, which is the element-major copy, unless the context is in an external basis.
+ *   The _round and _end calls of the two sumchecks have no twin: their arguments are O(1). */
+int lf_decompose_dev(lf_ctx *, const uint64_t *coeff_in, /* dev: count */ size_t count, uint64_t base, unsigned digits, int layout,
+                     uint64_t *out /* dev: count*digits, layout 0 or 1 */);
+int lf_recompose_dev(lf_ctx *, const uint64_t *in, /* dev: count_out*digits */ size_t count_out, uint64_t base, unsigned digits, uint64_t *out /* dev: count_out */);
+int lf_linf_check_dev(lf_ctx *, const uint64_t *f_ntt, /* dev: count */ size_t count, uint64_t bound, int unsigned_variant, int *ok,
+                      uint64_t *max_out);
+int lf_build_eq_dev(lf_ctx *, const uint64_t *point, unsigned nv, uint64_t *out /* dev: (1<<nv)*tau words */);
+int lf_mle_eval_batch_dev(lf_ctx *, const uint64_t *tables /* dev: ntables x len ring elems (NTT) */, size_t ntables, size_t len,
+                          const uint64_t *point, unsigned nv, uint64_t *out /* host: ntables ring elems */);
+int lf_spmv_dev(lf_ctx *, unsigned j, const uint64_t *z, /* dev: n */ uint64_t *out /* dev: m */);
+int lf_sumcheck_lin_begin_dev(lf_ctx *, const uint64_t *tables /* dev: t x m ring elems */, const uint64_t *eq_point /* s*tau */);
+int lf_sumcheck_fold_begin_dev(lf_ctx *, const uint64_t *tables, /* dev: (5 + 2K*tau) x m ring elems */ const uint64_t *mu);
+int lf_lincomb_dev(lf_ctx *, const uint64_t *coef, const uint64_t *tables, /* dev: n_terms x len */ size_t n_terms, size_t len, uint64_t *out /* dev: len */);
+int lf_horner_combine_dev(lf_ctx *, const uint64_t *tables, /* dev: groups x per_group x len */ size_t groups, size_t per_group, size_t len,
+                          const uint64_t *challenges, uint64_t *out /* dev: len */);
 
 /* ---- measurement hooks (bench.py): HIP-event time of the last fold step, per phase, in ms ------------ */
 #define LF_N_PHASES 8

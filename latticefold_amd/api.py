@@ -189,6 +189,16 @@ def _lib():
         for f in ("lf_witness_get_f_coeff_dev", "lf_witness_get_f_dev", "lf_witness_get_w_ccs_dev"):
             getattr(L, f).argtypes = [vp, vp, vp]
         L.lf_ccs_check_dev.argtypes = [vp, vp, u64p]
+        L.lf_decompose_dev.argtypes = [vp, vp, C.c_size_t, C.c_uint64, C.c_uint, C.c_int, vp]
+        L.lf_recompose_dev.argtypes = [vp, vp, C.c_size_t, C.c_uint64, C.c_uint, vp]
+        L.lf_linf_check_dev.argtypes = [vp, vp, C.c_size_t, C.c_uint64, C.c_int, C.POINTER(C.c_int), u64p]
+        L.lf_build_eq_dev.argtypes = [vp, u64p, C.c_uint, vp]
+        L.lf_mle_eval_batch_dev.argtypes = [vp, vp, C.c_size_t, C.c_size_t, u64p, C.c_uint, u64p]
+        L.lf_spmv_dev.argtypes = [vp, C.c_uint, vp, vp]
+        L.lf_sumcheck_lin_begin_dev.argtypes = [vp, vp, u64p]
+        L.lf_sumcheck_fold_begin_dev.argtypes = [vp, vp, u64p]
+        L.lf_lincomb_dev.argtypes = [vp, u64p, vp, C.c_size_t, C.c_size_t, vp]
+        L.lf_horner_combine_dev.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, u64p, vp]
         _LIB = L
     return _LIB
 
@@ -233,12 +243,24 @@ def is_device_array(x):
     return hasattr(x, "data_ptr") and bool(getattr(x, "is_cuda", False))
 
 
-def _dev(ctx, t):
-    """device array -> its address for a _dev entry point, after ordering the context behind the stream the array was produced on (the current torch stream)"""
-    if not t.is_contiguous() or t.element_size() != 8 or t.dim() < 2 or t.shape[-1] != ctx.RE:
-        raise ValueError(f"device arrays must be contiguous, 8-byte elements, shape (..., {ctx.RE})")
+def _dev(ctx, t, words=None):
+    """device array -> its address for a _dev entry point, after ordering the context behind the stream the array was produced on (the current torch stream).
+    words: the last dimension (default: a ring element; an eq table has TAU)"""
+    words = ctx.RE if words is None else words
+    if not t.is_contiguous() or t.element_size() != 8 or t.dim() < 2 or t.shape[-1] != words:
+        raise ValueError(f"device arrays must be contiguous, 8-byte elements, shape (..., {words})")
     ctx.wait_stream()
     return C.c_void_p(t.data_ptr())
+
+
+def _dev_out(like, shape, out):
+    """where a _dev call writes: `out`, which must be a device array of that shape, or a fresh tensor next to `like`"""
+    if out is None:
+        import torch
+        return torch.empty(shape, dtype=like.dtype, device=like.device)
+    if not is_device_array(out) or tuple(out.shape) != tuple(shape):
+        raise ValueError(f"out must be a device array of shape {tuple(shape)}")
+    return out
 
 
 class Context:
@@ -398,14 +420,25 @@ class Context:
 
     ntt_fwd, ntt_inv = crt, icrt
 
-    def decompose(self, coeff, base, digits, layout):
+    def decompose(self, coeff, base, digits, layout, out=None):
+        """numpy in, numpy out; a device array in, a device array out (`out`: where to; it may not overlap the input)"""
+        if is_device_array(coeff):
+            cnt = coeff.numel() // self.RE
+            o = _dev_out(coeff, (cnt * digits, self.RE), out)
+            _chk(_lib().lf_decompose_dev(self.h, _dev(self, coeff), cnt, base, digits, layout, _dev(self, o)), "lf_decompose_dev")
+            return o
         a, p = _a64(coeff)
         cnt = a.size // self.RE
         o = np.zeros((cnt * digits, self.RE), dtype=np.uint64)
         _chk(_lib().lf_decompose(self.h, p, cnt, base, digits, layout, o.ctypes.data_as(u64p)), "lf_decompose")
         return o
 
-    def recompose(self, x, base, digits):
+    def recompose(self, x, base, digits, out=None):
+        if is_device_array(x):
+            cnt = x.numel() // self.RE // digits
+            o = _dev_out(x, (cnt, self.RE), out)
+            _chk(_lib().lf_recompose_dev(self.h, _dev(self, x), cnt, base, digits, _dev(self, o)), "lf_recompose_dev")
+            return o
         a, p = _a64(x)
         cnt = a.size // self.RE // digits
         o = np.zeros((cnt, self.RE), dtype=np.uint64)
@@ -413,26 +446,43 @@ class Context:
         return o
 
     def linf_check(self, f_ntt, bound, unsigned_variant=False):
-        a, p = _a64(f_ntt)
         ok = C.c_int()
         mx = C.c_uint64()
+        if is_device_array(f_ntt):
+            _chk(_lib().lf_linf_check_dev(self.h, _dev(self, f_ntt), f_ntt.numel() // self.RE, bound, int(unsigned_variant), C.byref(ok),
+                                          C.cast(C.byref(mx), u64p)), "lf_linf_check_dev")
+            return bool(ok.value), mx.value
+        a, p = _a64(f_ntt)
         _chk(_lib().lf_linf_check(self.h, p, a.size // self.RE, bound, int(unsigned_variant), C.byref(ok), C.cast(C.byref(mx), u64p)), "lf_linf_check")
         return bool(ok.value), mx.value
 
-    def build_eq(self, point):
+    def build_eq(self, point, out=None):
+        """the eq table of `point` (host), (1 << nv, TAU): a numpy array, or written into the device array `out` (lf_build_eq_dev)"""
         a, p = _a64(point)
         nv = a.size // self.TAU
+        if out is not None:
+            o = _dev_out(None, (1 << nv, self.TAU), out)
+            _chk(_lib().lf_build_eq_dev(self.h, p, nv, _dev(self, o, self.TAU)), "lf_build_eq_dev")
+            return o
         o = np.zeros(((1 << nv), self.TAU), dtype=np.uint64)
         _chk(_lib().lf_build_eq(self.h, p, nv, o.ctypes.data_as(u64p)), "lf_build_eq")
         return o
 
     def evaluate_mles(self, tables, point):  # utils/mle_helpers.rs:65-88
+        """tables (ntables, len, RE), numpy or a device array; the evaluations come back as numpy either way"""
+        b, q = _a64(point)
+        if is_device_array(tables):
+            nt, ln = tables.shape[0], tables.shape[1]
+            o = np.zeros((nt, self.RE), dtype=np.uint64)
+            _chk(_lib().lf_mle_eval_batch_dev(self.h, _dev(self, tables), nt, ln, q, b.size // self.TAU, o.ctypes.data_as(u64p)), "lf_mle_eval_batch_dev")
+            return o
         a, p = _a64(tables)
         nt, ln = a.shape[0], a.shape[1]
-        b, q = _a64(point)
         o = np.zeros((nt, self.RE), dtype=np.uint64)
         _chk(_lib().lf_mle_eval_batch(self.h, p, nt, ln, q, b.size // self.TAU, o.ctypes.data_as(u64p)), "lf_mle_eval_batch")
         return o
+
+    mle_eval_batch = evaluate_mles
 
     # ---- CCS -------------------------------------------------------------------------------
     def load_ccs(self, wl):
@@ -458,7 +508,11 @@ class Context:
         self.m = wl.m
         self.n = wl.n
 
-    def mat_vec_mul(self, j, z):  # arith/utils.rs:52-65
+    def mat_vec_mul(self, j, z, out=None):  # arith/utils.rs:52-65
+        if is_device_array(z):
+            o = _dev_out(z, (self.m, self.RE), out)
+            _chk(_lib().lf_spmv_dev(self.h, j, _dev(self, z), _dev(self, o)), "lf_spmv_dev")
+            return o
         a, p = _a64(z)
         o = np.zeros((self.m, self.RE), dtype=np.uint64)
         _chk(_lib().lf_spmv(self.h, j, p, o.ctypes.data_as(u64p)), "lf_spmv")
@@ -898,8 +952,11 @@ class MLSumcheckLin:
 
     def __init__(self, ctx, tables, eq_point):
         self.ctx = ctx
-        a, p = _a64(tables)
         b, q = _a64(eq_point)
+        if is_device_array(tables):   # (t, m, RE) on the device: read in place
+            _chk(_lib().lf_sumcheck_lin_begin_dev(ctx.h, _dev(ctx, tables), q), "lf_sumcheck_lin_begin_dev")
+            return
+        a, p = _a64(tables)
         _chk(_lib().lf_sumcheck_lin_begin(ctx.h, p, q), "lf_sumcheck_lin_begin")
 
     def prove_round(self, r_prev=None):
@@ -923,8 +980,11 @@ class MLSumcheckFold:
 
     def __init__(self, ctx, tables, mu):
         self.ctx = ctx
-        a, p = _a64(tables)
         b, q = _a64(mu)
+        if is_device_array(tables):
+            _chk(_lib().lf_sumcheck_fold_begin_dev(ctx.h, _dev(ctx, tables), q), "lf_sumcheck_fold_begin_dev")
+            return
+        a, p = _a64(tables)
         _chk(_lib().lf_sumcheck_fold_begin(ctx.h, p, q), "lf_sumcheck_fold_begin")
 
     def prove_round(self, r_prev=None):
@@ -942,21 +1002,31 @@ class MLSumcheckFold:
         _chk(_lib().lf_sumcheck_fold_end(self.ctx.h), "lf_sumcheck_fold_end")
 
 
-def lincomb(ctx, coef, tables):
-    """compute_f_0 (nifs/folding.rs:258-268): sum_i coef_i (.) tables_i; coef (n, RE), tables (n, len, RE)"""
+def lincomb(ctx, coef, tables, out=None):
+    """compute_f_0 (nifs/folding.rs:258-268): sum_i coef_i (.) tables_i; coef (n, RE), tables (n, len, RE).  Device tables: a device result (`out`: where to)"""
+    a, p = _a64(coef)
+    if is_device_array(tables):
+        n, ln = tables.shape[0], tables.shape[1]
+        o = _dev_out(tables, (ln, ctx.RE), out)
+        _chk(_lib().lf_lincomb_dev(ctx.h, p, _dev(ctx, tables), n, ln, _dev(ctx, o)), "lf_lincomb_dev")
+        return o
     t = np.ascontiguousarray(tables, dtype=np.uint64)
     n, ln = t.shape[0], t.shape[1]
-    a, p = _a64(coef)
     o = np.zeros((ln, ctx.RE), dtype=np.uint64)
     _chk(_lib().lf_lincomb(ctx.h, p, t.ctypes.data_as(u64p), n, ln, o.ctypes.data_as(u64p)), "lf_lincomb")
     return o
 
 
-def horner_combine(ctx, tables, challenges):
-    """calculate_challenged_mz_mle (nifs/folding.rs:208-226): tables (groups, per_group, len, RE), challenges (groups, TAU)"""
+def horner_combine(ctx, tables, challenges, out=None):
+    """calculate_challenged_mz_mle (nifs/folding.rs:208-226): tables (groups, per_group, len, RE), challenges (groups, TAU).  Device tables: a device result"""
+    a, p = _a64(challenges)
+    if is_device_array(tables):
+        g, pg, ln = tables.shape[0], tables.shape[1], tables.shape[2]
+        o = _dev_out(tables, (ln, ctx.RE), out)
+        _chk(_lib().lf_horner_combine_dev(ctx.h, _dev(ctx, tables), g, pg, ln, p, _dev(ctx, o)), "lf_horner_combine_dev")
+        return o
     t = np.ascontiguousarray(tables, dtype=np.uint64)
     g, pg, ln = t.shape[0], t.shape[1], t.shape[2]
-    a, p = _a64(challenges)
     o = np.zeros((ln, ctx.RE), dtype=np.uint64)
     _chk(_lib().lf_horner_combine(ctx.h, t.ctypes.data_as(u64p), g, pg, ln, p, o.ctypes.data_as(u64p)), "lf_horner_combine")
     return o

@@ -35,6 +35,10 @@ struct XbMat9 { fe m[81]; };
 void launch_aos_to_soa(const u64 *aos_canon, fe *soa, size_t n, hipStream_t s, u32 *flag = nullptr, const XbMat9 *Ti = nullptr);
 // unless_flag: the result goes out unless *unless_flag.  T: of a context in an external basis
 void launch_soa_to_aos(const fe *soa, u64 *aos_canon, size_t n, hipStream_t s, const u32 *unless_flag = nullptr, const XbMat9 *T = nullptr);
+// an F_{p^9} table [9][n] (an eq table) -> [n][9] canonical in the caller's device buffer (lf_build_eq_dev); T: of a context in an external basis (each entry)
+void launch_ext_to_aos(const fe *soa, u64 *aos_canon, size_t n, hipStream_t s, const XbMat9 *T = nullptr);
+// bit 1 of *flag goes up unless the ring table tab [72][n] is slot-constant (the eq tables of lf_sumcheck_fold_begin_dev)
+void launch_slot_const_check(const fe *tab, size_t n, u32 *flag, hipStream_t s);
 void launch_fill_ajtai(fe *A, u32 kappa, size_t n, size_t n_total, size_t col0, u64 seed, hipStream_t s, u32 row0 = 0);
 void launch_selftest(const u64 *in_canon /*[n][18]*/, u64 *out_canon /*[n][12]*/, u32 n, fe nu, hipStream_t s);
 // i64 partial sums [nblocks][nv] -> canonical u64 [nv]

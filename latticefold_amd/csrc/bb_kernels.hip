@@ -65,6 +65,8 @@ void launch_aos_to_soa(const u64 *aos, fe *soa, size_t n, hipStream_t s, u32 *fl
 void launch_soa_to_aos(const fe *soa, u64 *aos, size_t n, hipStream_t s, const u32 *unless_flag, const XbMat9 *T) {
     lfk::launch_soa_to_aos<BbF>(soa, aos, n, s, unless_flag, T);
 }
+void launch_ext_to_aos(const fe *soa, u64 *aos, size_t n, hipStream_t s, const XbMat9 *T) { lfk::launch_ext_to_aos<BbF>(soa, aos, n, s, T); }
+void launch_slot_const_check(const fe *tab, size_t n, u32 *flag, hipStream_t s) { lfk::launch_slot_const_check<BbF>(tab, n, flag, s); }
 void launch_fill_ajtai(fe *A, u32 kappa, size_t n, size_t n_total, size_t col0, u64 seed, hipStream_t s, u32 row0) {
     lfk::launch_fill_ajtai<BbF>(A, kappa, n, n_total, col0, seed, s, row0);
 }

@@ -523,6 +523,23 @@ int lf_linf_check(lf_ctx *c, const uint64_t *f_ntt, size_t count, uint64_t bound
     if (!c || !f_ntt || !ok) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::linf_check(c->bb->p, f_ntt, count, bound, unsigned_variant, ok, max_out) : ring_ops<GoldRing>::linf_check(c, f_ntt, count, bound, unsigned_variant, ok, max_out);
 }
+// (coefficient-form arrays: no basis, so no XbArrays; the overlap of `in` and `out` is refused in the body, behind its state checks)
+int lf_decompose_dev(lf_ctx *c, const uint64_t *in, size_t count, uint64_t base, unsigned digits, int layout, uint64_t *out) {
+    if (!c || !in || !out || digits == 0 || digits > 64 || (layout != 0 && layout != 1)) return LF_ERR_INVALID;
+    return c->bb ? ring_ops<BbRing>::decompose(c->bb->p, in, count, base, digits, layout, out, Origin::device)
+                 : ring_ops<GoldRing>::decompose(c, in, count, base, digits, layout, out, Origin::device);
+}
+int lf_recompose_dev(lf_ctx *c, const uint64_t *in, size_t count_out, uint64_t base, unsigned digits, uint64_t *out) {
+    if (!c || !in || !out || digits == 0) return LF_ERR_INVALID;
+    return c->bb ? ring_ops<BbRing>::recompose(c->bb->p, in, count_out, base, digits, out, Origin::device)
+                 : ring_ops<GoldRing>::recompose(c, in, count_out, base, digits, out, Origin::device);
+}
+int lf_linf_check_dev(lf_ctx *c, const uint64_t *f_ntt, size_t count, uint64_t bound, int unsigned_variant, int *ok, uint64_t *max_out) {
+    if (!c || !f_ntt || !ok) return LF_ERR_INVALID;
+    XbArrays xa(c);
+    return c->bb ? ring_ops<BbRing>::linf_check(c->bb->p, f_ntt, count, bound, unsigned_variant, ok, max_out, Origin::device)
+                 : ring_ops<GoldRing>::linf_check(c, f_ntt, count, bound, unsigned_variant, ok, max_out, Origin::device);
+}
 
 // ---- a5 -----------------------------------------------------------------------------------------------------------
 int lf_ajtai_load(lf_ctx *c, const uint64_t *A, size_t kappa, size_t n) {
@@ -745,20 +762,35 @@ int build_eq_dev(lf_ctx *c, const Fq3 *pt, u32 nv, u64 *eq_dev) {
     } else launch_build_eq(c->dcrt, rd, nv, eq_dev, c->stream());
     return LF_OK;
 }
-int lf_build_eq(lf_ctx *c, const uint64_t *point, unsigned nv, uint64_t *out) {
-    if (LF_XB(c) && point && out && nv && nv <= 40) { XB x(c); int rc = lf_build_eq(c, x.ext_in(point, nv), nv, out); if (rc == LF_OK) x.ext_out(out, (size_t)1 << nv); return rc; }
+// (a host table leaves the external-basis wrapper converted on the host; a device table changes basis in the kernel that stores it: XB with arrays)
+static int build_eq_api(lf_ctx *c, const uint64_t *point, unsigned nv, uint64_t *out, Origin org) {
+    if (LF_XB(c) && point && out && nv && nv <= 40) {
+        XB x(c, org == Origin::device);
+        int rc = build_eq_api(c, x.ext_in(point, nv), nv, out, org);
+        if (rc == LF_OK && org == Origin::host) x.ext_out(out, (size_t)1 << nv);
+        return rc;
+    }
     if (!c || !point || !out || nv == 0 || nv > 40) return LF_ERR_INVALID;
-    return c->bb ? ring_ops<BbRing>::build_eq(c->bb->p, point, nv, out) : ring_ops<GoldRing>::build_eq(c, point, nv, out);
+    return c->bb ? ring_ops<BbRing>::build_eq(c->bb->p, point, nv, out, org) : ring_ops<GoldRing>::build_eq(c, point, nv, out, org);
 }
-int lf_mle_eval_batch(lf_ctx *c, const uint64_t *tables, size_t ntables, size_t len, const uint64_t *point, unsigned nv, uint64_t *out) {
+int lf_build_eq(lf_ctx *c, const uint64_t *point, unsigned nv, uint64_t *out) { return build_eq_api(c, point, nv, out, Origin::host); }
+int lf_build_eq_dev(lf_ctx *c, const uint64_t *point, unsigned nv, uint64_t *out) { return build_eq_api(c, point, nv, out, Origin::device); }
+static int mle_eval_batch_api(lf_ctx *c, const uint64_t *tables, size_t ntables, size_t len, const uint64_t *point, unsigned nv, uint64_t *out, Origin org) {
     if (LF_XB(c) && tables && point && out) {
         XB x(c, true);
-        int rc = lf_mle_eval_batch(c, tables, ntables, len, x.ext_in(point, nv), nv, out);
+        int rc = mle_eval_batch_api(c, tables, ntables, len, x.ext_in(point, nv), nv, out, org);
         if (rc == LF_OK) x.ring_out(out, ntables);
         return rc;
     }
     if (!c || !tables || !point || !out || !ntables || nv == 0 || nv > 40) return LF_ERR_INVALID;
-    return c->bb ? ring_ops<BbRing>::mle_eval_batch(c->bb->p, tables, ntables, len, point, nv, out) : ring_ops<GoldRing>::mle_eval_batch(c, tables, ntables, len, point, nv, out);
+    return c->bb ? ring_ops<BbRing>::mle_eval_batch(c->bb->p, tables, ntables, len, point, nv, out, org)
+                 : ring_ops<GoldRing>::mle_eval_batch(c, tables, ntables, len, point, nv, out, org);
+}
+int lf_mle_eval_batch(lf_ctx *c, const uint64_t *tables, size_t ntables, size_t len, const uint64_t *point, unsigned nv, uint64_t *out) {
+    return mle_eval_batch_api(c, tables, ntables, len, point, nv, out, Origin::host);
+}
+int lf_mle_eval_batch_dev(lf_ctx *c, const uint64_t *tables, size_t ntables, size_t len, const uint64_t *point, unsigned nv, uint64_t *out) {
+    return mle_eval_batch_api(c, tables, ntables, len, point, nv, out, Origin::device);
 }
 
 // ---- CCS -------------------------------------------------------------------------------------------------------------
@@ -800,6 +832,11 @@ int lf_spmv(lf_ctx *c, unsigned j, const uint64_t *z, uint64_t *out) {
     XbArrays xa(c);
     if (!c || !z || !out) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::spmv(c->bb->p, j, z, out) : ring_ops<GoldRing>::spmv(c, j, z, out);
+}
+int lf_spmv_dev(lf_ctx *c, unsigned j, const uint64_t *z, uint64_t *out) {
+    if (!c || !z || !out) return LF_ERR_INVALID;
+    XbArrays xa(c);
+    return c->bb ? ring_ops<BbRing>::spmv(c->bb->p, j, z, out, Origin::device) : ring_ops<GoldRing>::spmv(c, j, z, out, Origin::device);
 }
 
 // ---- witnesses ---------------------------------------------------------------------------------------------------------

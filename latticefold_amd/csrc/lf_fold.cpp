@@ -691,11 +691,13 @@ int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out,
 }
 
 // ---- generic linearization-shaped sumcheck through the ABI (tests / SURVEY 8b) -------------------------------------------------
-int lf_sumcheck_lin_begin(lf_ctx *c, const uint64_t *tables, const uint64_t *eq_point) {
-    if (LF_XB(c) && tables && eq_point && c->have_ccs_any()) { XB x(c, true); const lf_params &P = c->params_any(); return lf_sumcheck_lin_begin(c, tables, x.ext_in(eq_point, P.s)); }
+static int sumcheck_lin_begin_api(lf_ctx *c, const uint64_t *tables, const uint64_t *eq_point, Origin org) {
+    if (LF_XB(c) && tables && eq_point && c->have_ccs_any()) { XB x(c, true); const lf_params &P = c->params_any(); return sumcheck_lin_begin_api(c, tables, x.ext_in(eq_point, P.s), org); }
     if (!c || !tables || !eq_point) return LF_ERR_INVALID;
-    return c->bb ? ring_ops<BbRing>::sumcheck_lin_begin(c->bb->p, tables, eq_point) : ring_ops<GoldRing>::sumcheck_lin_begin(c, tables, eq_point);
+    return c->bb ? ring_ops<BbRing>::sumcheck_lin_begin(c->bb->p, tables, eq_point, org) : ring_ops<GoldRing>::sumcheck_lin_begin(c, tables, eq_point, org);
 }
+int lf_sumcheck_lin_begin(lf_ctx *c, const uint64_t *tables, const uint64_t *eq_point) { return sumcheck_lin_begin_api(c, tables, eq_point, Origin::host); }
+int lf_sumcheck_lin_begin_dev(lf_ctx *c, const uint64_t *tables, const uint64_t *eq_point) { return sumcheck_lin_begin_api(c, tables, eq_point, Origin::device); }
 int lf_sumcheck_lin_round(lf_ctx *c, const uint64_t *r_prev, uint64_t *evals_out) {
     if (LF_XB(c) && evals_out) { XB x(c); int rc = lf_sumcheck_lin_round(c, x.ext_in(r_prev, 1), evals_out); if (rc == LF_OK) x.ring_out(evals_out, c->params_any().d + 2); return rc; }
     if (!c || !evals_out) return LF_ERR_INVALID;
@@ -741,11 +743,13 @@ int lf_device_sponge(lf_ctx *c, const uint32_t *ops, size_t nops, const uint64_t
 }
 
 // ---- the folding sumcheck through the ABI: the bodies and the layout of `tables` are in lf_ring_host.h (ring_ops::sumcheck_fold_*)
-int lf_sumcheck_fold_begin(lf_ctx *c, const uint64_t *tables, const uint64_t *mu) {
-    if (LF_XB(c) && tables && mu && c->have_ccs_any()) { XB x(c, true); const lf_params &P = c->params_any(); return lf_sumcheck_fold_begin(c, tables, x.ext_in(mu, 2 * P.K)); }
+static int sumcheck_fold_begin_api(lf_ctx *c, const uint64_t *tables, const uint64_t *mu, Origin org) {
+    if (LF_XB(c) && tables && mu && c->have_ccs_any()) { XB x(c, true); const lf_params &P = c->params_any(); return sumcheck_fold_begin_api(c, tables, x.ext_in(mu, 2 * P.K), org); }
     if (!c || !tables || !mu) return LF_ERR_INVALID;
-    return c->bb ? ring_ops<BbRing>::sumcheck_fold_begin(c->bb->p, tables, mu) : ring_ops<GoldRing>::sumcheck_fold_begin(c, tables, mu);
+    return c->bb ? ring_ops<BbRing>::sumcheck_fold_begin(c->bb->p, tables, mu, org) : ring_ops<GoldRing>::sumcheck_fold_begin(c, tables, mu, org);
 }
+int lf_sumcheck_fold_begin(lf_ctx *c, const uint64_t *tables, const uint64_t *mu) { return sumcheck_fold_begin_api(c, tables, mu, Origin::host); }
+int lf_sumcheck_fold_begin_dev(lf_ctx *c, const uint64_t *tables, const uint64_t *mu) { return sumcheck_fold_begin_api(c, tables, mu, Origin::device); }
 int lf_sumcheck_fold_round(lf_ctx *c, const uint64_t *r_prev, uint64_t *evals_out) {
     if (LF_XB(c) && evals_out) { XB x(c); int rc = lf_sumcheck_fold_round(c, x.ext_in(r_prev, 1), evals_out); if (rc == LF_OK) x.ring_out(evals_out, 2 * c->params_any().b + 1); return rc; }
     if (!c || !evals_out) return LF_ERR_INVALID;
@@ -757,17 +761,29 @@ int lf_sumcheck_fold_end(lf_ctx *c) {
 }
 
 // compute_f_0 (nifs/folding.rs:258-268): out[j] = sum_i coef_i (.) tables_i[j] with ring-element coefficients (8 distinct slots)
-int lf_lincomb(lf_ctx *c, const uint64_t *coef, const uint64_t *tables, size_t n_terms, size_t len, uint64_t *out) {
-    if (LF_XB(c) && coef && tables && out) { XB x(c, true); return lf_lincomb(c, x.ring_in(coef, n_terms), tables, n_terms, len, out); }
+static int lincomb_api(lf_ctx *c, const uint64_t *coef, const uint64_t *tables, size_t n_terms, size_t len, uint64_t *out, Origin org) {
+    if (LF_XB(c) && coef && tables && out) { XB x(c, true); return lincomb_api(c, x.ring_in(coef, n_terms), tables, n_terms, len, out, org); }
     if (!c || !coef || !tables || !out || !n_terms || !len) return LF_ERR_INVALID;
-    return c->bb ? ring_ops<BbRing>::lincomb(c->bb->p, coef, tables, n_terms, len, out) : ring_ops<GoldRing>::lincomb(c, coef, tables, n_terms, len, out);
+    return c->bb ? ring_ops<BbRing>::lincomb(c->bb->p, coef, tables, n_terms, len, out, org) : ring_ops<GoldRing>::lincomb(c, coef, tables, n_terms, len, out, org);
+}
+int lf_lincomb(lf_ctx *c, const uint64_t *coef, const uint64_t *tables, size_t n_terms, size_t len, uint64_t *out) {
+    return lincomb_api(c, coef, tables, n_terms, len, out, Origin::host);
+}
+int lf_lincomb_dev(lf_ctx *c, const uint64_t *coef, const uint64_t *tables, size_t n_terms, size_t len, uint64_t *out) {
+    return lincomb_api(c, coef, tables, n_terms, len, out, Origin::device);
 }
 // calculate_challenged_mz_mle (nifs/folding.rs:208-226) and the f-hat half of prepare_g1_and_3_k_mles_list (folding/utils.rs:524-546):
 // out[x] = sum_{i<groups} sum_{j<per_group} c_i^{j+1} T_{i,j}[x] (the reference's Horner loop `mle += M; mle *= c_i` over j reversed)
-int lf_horner_combine(lf_ctx *c, const uint64_t *tables, size_t groups, size_t per_group, size_t len, const uint64_t *challenges, uint64_t *out) {
-    if (LF_XB(c) && tables && challenges && out) { XB x(c, true); return lf_horner_combine(c, tables, groups, per_group, len, x.ext_in(challenges, groups), out); }
+static int horner_combine_api(lf_ctx *c, const uint64_t *tables, size_t groups, size_t per_group, size_t len, const uint64_t *challenges, uint64_t *out, Origin org) {
+    if (LF_XB(c) && tables && challenges && out) { XB x(c, true); return horner_combine_api(c, tables, groups, per_group, len, x.ext_in(challenges, groups), out, org); }
     if (!c || !tables || !challenges || !out || !groups || !per_group || !len) return LF_ERR_INVALID;
-    return c->bb ? ring_ops<BbRing>::horner_combine(c->bb->p, tables, groups, per_group, len, challenges, out)
-                 : ring_ops<GoldRing>::horner_combine(c, tables, groups, per_group, len, challenges, out);
+    return c->bb ? ring_ops<BbRing>::horner_combine(c->bb->p, tables, groups, per_group, len, challenges, out, org)
+                 : ring_ops<GoldRing>::horner_combine(c, tables, groups, per_group, len, challenges, out, org);
+}
+int lf_horner_combine(lf_ctx *c, const uint64_t *tables, size_t groups, size_t per_group, size_t len, const uint64_t *challenges, uint64_t *out) {
+    return horner_combine_api(c, tables, groups, per_group, len, challenges, out, Origin::host);
+}
+int lf_horner_combine_dev(lf_ctx *c, const uint64_t *tables, size_t groups, size_t per_group, size_t len, const uint64_t *challenges, uint64_t *out) {
+    return horner_combine_api(c, tables, groups, per_group, len, challenges, out, Origin::device);
 }
 

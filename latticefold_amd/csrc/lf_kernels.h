@@ -34,6 +34,10 @@ struct XbMat3 { u64 m[9]; };
 void launch_aos_to_soa(const u64 *aos, u64 *soa, size_t n, hipStream_t s, u32 *flag = nullptr, const XbMat3 *Ti = nullptr);
 // unless_flag: the result goes out unless *unless_flag.  T: of a context in an external basis
 void launch_soa_to_aos(const u64 *soa, u64 *aos, size_t n, hipStream_t s, const u32 *unless_flag = nullptr, const XbMat3 *T = nullptr);
+// an F_{p^3} table [3][n] (an eq table) -> [n][3] in the caller's device buffer (lf_build_eq_dev); T: of a context in an external basis (each entry, not each slot)
+void launch_ext_to_aos(const u64 *soa, u64 *aos, size_t n, hipStream_t s, const XbMat3 *T = nullptr);
+// bit 1 of *flag goes up unless the ring table tab [24][n] is slot-constant (the eq tables of lf_sumcheck_fold_begin_dev)
+void launch_slot_const_check(const u64 *tab, size_t n, u32 *flag, hipStream_t s);
 void launch_fill_uniform(u64 *dst, size_t words, u64 seed, size_t start, hipStream_t s);  // SplitMix64 stream (workload.py)
 // Ajtai matrix generated in place in plane layout, equal to AoS stream splitmix(seed)[((i*n+j)*24+w)]
 // columns [col0, col0+n) of the n_total-column matrix

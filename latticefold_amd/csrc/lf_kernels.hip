@@ -69,6 +69,8 @@ void launch_aos_to_soa(const u64 *aos, u64 *soa, size_t n, hipStream_t s, u32 *f
 void launch_soa_to_aos(const u64 *soa, u64 *aos, size_t n, hipStream_t s, const u32 *unless_flag, const XbMat3 *T) {
     lfk::launch_soa_to_aos<GoldF>(soa, aos, n, s, unless_flag, T);
 }
+void launch_ext_to_aos(const u64 *soa, u64 *aos, size_t n, hipStream_t s, const XbMat3 *T) { lfk::launch_ext_to_aos<GoldF>(soa, aos, n, s, T); }
+void launch_slot_const_check(const u64 *tab, size_t n, u32 *flag, hipStream_t s) { lfk::launch_slot_const_check<GoldF>(tab, n, flag, s); }
 void launch_fill_ajtai(u64 *A, u32 kappa, size_t n, size_t n_total, size_t col0, u64 seed, hipStream_t s, u32 row0) {
     lfk::launch_fill_ajtai<GoldF>(A, kappa, n, n_total, col0, seed, s, row0);
 }

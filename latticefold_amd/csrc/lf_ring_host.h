@@ -192,7 +192,9 @@ int down_ring(C *c, const typename Ring<C>::W *src, size_t n, u64 *host, Form f)
 // Origin::host (every lf_* call without the suffix): pageable host memory, staged through `stage_aos` as above.  Origin::device (the _dev twins): the caller's own
 // memory on the context's device, same AoS layout; the relayout kernels read and write it in place, nothing is staged.  What the host cannot see it lets the
 // device check: the checked relayout raises a flag word on an input word >= p, the flag comes back in front of a synchronise the call performs anyway, results go
-// into the caller's buffer only while the flag is down (launch_soa_to_aos's unless_flag), and the call returns LF_ERR_INVALID.
+// into the caller's buffer only while the flag is down (launch_soa_to_aos's unless_flag), and the call returns LF_ERR_INVALID.  A body with several input
+// tables (mle_eval_batch, lincomb, horner_combine, the sumcheck begins) relayouts each into the scratch of the host path and acts on the flag once, at the end;
+// one with several result tables (decompose, layout 1) stores each behind the flag (store_ring) and ends in DevIo::finish.
 enum class Origin { host, device };
 // [p, p + bytes) lies inside the allocation [base, base + size): the whole range arithmetic of the pointer checks
 inline bool range_inside(uintptr_t base, size_t size, uintptr_t p, size_t bytes) { return p >= base && p - base <= size && bytes <= size - (p - base); }
@@ -230,6 +232,21 @@ struct DevIo {
         return LF_OK;
     }
     bool bad() const { return flag && *(volatile u32 *)hflag != 0; }
+    // an input array and `out` of a call whose sizes differ (na, nb ring elements): any overlap is refused, an in-place form has no meaning
+    int disjoint(const void *a, size_t na, const void *b, size_t nb) const {
+        const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+        return !dev || pa + na * Ring<C>::RE * 8 <= pb || pb + nb * Ring<C>::RE * 8 <= pa ? LF_OK : LF_ERR_INVALID;
+    }
+    // the same for an array that is not made of ring elements (the eq table of lf_build_eq_dev)
+    int words(const void *p, size_t n) const { return dev && n ? dev_array_check(c->device, p, n * 8) : LF_OK; }
+    // the flag word itself: bit 0 a word >= p, bit 1 an eq table that is not slot-constant (launch_slot_const_check)
+    u32 raised() const { return flag ? *(volatile u32 *)hflag : 0; }
+    // the end of a device-origin call whose results are stored already, or that has none: the flag comes home, the stream is synchronised
+    int finish() {
+        RET(fetch());
+        HIPCHK(hipStreamSynchronize(c->stream()));
+        return bad() ? LF_ERR_INVALID : LF_OK;
+    }
 };
 template <class C>
 int up_ring(DevIo<C> &io, const u64 *src, size_t n, typename Ring<C>::W *dst, Form f) {
@@ -244,9 +261,13 @@ int down_ring(DevIo<C> &io, const typename Ring<C>::W *src, size_t n, u64 *out, 
     if (!io.dev) return down_ring(io.c, src, n, out, f);
     const auto T = Ring<C>::xb_mat(io.c->xb_T);
     launch_soa_to_aos(src, out, n, io.c->stream(), io.flag, xb_converts(io.c, f) ? &T : nullptr);
-    RET(io.fetch());
-    HIPCHK(hipStreamSynchronize(io.c->stream()));
-    return io.bad() ? LF_ERR_INVALID : LF_OK;
+    return io.finish();
+}
+// one of several result tables of a device-origin call: stored while the flag is down, no synchronise -- io.finish() ends the call
+template <class C>
+void store_ring(DevIo<C> &io, const typename Ring<C>::W *src, size_t n, u64 *out, Form f) {
+    const auto T = Ring<C>::xb_mat(io.c->xb_T);
+    launch_soa_to_aos(src, out, n, io.c->stream(), io.flag, xb_converts(io.c, f) ? &T : nullptr);
 }
 template <class C, class T>
 int upload_consts(C *c, const std::string &name, const std::vector<T> &v, T **out) {
@@ -616,40 +637,58 @@ struct ring_ops<Ring<C>> {
         launch_icrt_dense(c->d_icrt, a, b, count, c->stream());
         return down_ring(io, b, count, out, Form::coeff);
     }
-    static int decompose(C *c, const u64 *in, size_t count, u64 base, unsigned digits, int layout, u64 *out) {
+    static int decompose(C *c, const u64 *in, size_t count, u64 base, unsigned digits, int layout, u64 *out, Origin org = Origin::host) {
         if (!pow2(base)) return LF_ERR_UNSUPPORTED;
         std::lock_guard<std::mutex> g(c->mu);
         HIPCHK(hipSetDevice(c->device));
+        DevIo<C> io(c, org);
+        RET(io.array(in, count));
+        RET(io.array(out, count * digits));
+        RET(io.disjoint(in, count, out, count * digits));
         W *a, *b;
         RET(c->tbuf("io_a", count * RE, &a));
         RET(c->tbuf("io_b", count * digits * RE, &b));
-        RET(up_ring(c, in, count, a, Form::coeff));
+        RET(io.begin());
+        RET(up_ring(io, in, count, a, Form::coeff));
         launch_decompose(a, count, base, digits, layout, b, c->stream(), c->digit_mode);
-        if (layout == 0) return down_ring(c, b, count * digits, out, Form::coeff);
+        if (layout == 0) return down_ring(io, b, count * digits, out, Form::coeff);
+        if (io.dev) {   // every digit table is stored behind the flag: input that was not canonical leaves none of them written
+            for (unsigned k = 0; k < digits; k++) store_ring(io, b + (size_t)k * RE * count, count, out + (size_t)k * count * RE, Form::coeff);
+            return io.finish();
+        }
         for (unsigned k = 0; k < digits; k++) RET(down_ring(c, b + (size_t)k * RE * count, count, out + (size_t)k * count * RE, Form::coeff));
         return LF_OK;
     }
-    static int recompose(C *c, const u64 *in, size_t count_out, u64 base, unsigned digits, u64 *out) {
+    static int recompose(C *c, const u64 *in, size_t count_out, u64 base, unsigned digits, u64 *out, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         HIPCHK(hipSetDevice(c->device));
+        DevIo<C> io(c, org);
+        RET(io.array(in, count_out * digits));
+        RET(io.array(out, count_out));
+        RET(io.disjoint(in, count_out * digits, out, count_out));
         W *a, *b;
         RET(c->tbuf("io_a", count_out * digits * RE, &a));
         RET(c->tbuf("io_b", count_out * RE, &b));
-        RET(up_ring(c, in, count_out * digits, a, Form::coeff));
+        RET(io.begin());
+        RET(up_ring(io, in, count_out * digits, a, Form::coeff));
         launch_recompose(a, count_out, base, digits, b, c->stream());
-        return down_ring(c, b, count_out, out, Form::coeff);
+        return down_ring(io, b, count_out, out, Form::coeff);
     }
-    static int linf_check(C *c, const u64 *f_ntt, size_t count, u64 bound, int unsigned_variant, int *ok, u64 *max_out) {
+    static int linf_check(C *c, const u64 *f_ntt, size_t count, u64 bound, int unsigned_variant, int *ok, u64 *max_out, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         HIPCHK(hipSetDevice(c->device));
+        DevIo<C> io(c, org);
+        RET(io.array(f_ntt, count));
         W *a, *b;
         u64 *mx;
         RET(c->tbuf("io_a", count * RE, &a));
         RET(c->tbuf("io_b", count * RE, &b));
         RET(c->tbuf("small_dev", 4096, &mx));
-        RET(up_ring(c, f_ntt, count, a, Form::ntt));
+        RET(io.begin());
+        RET(up_ring(io, f_ntt, count, a, Form::ntt));
         launch_icrt_dense(c->d_icrt, a, b, count, c->stream());
         u64 m = 0;
+        RET(io.fetch());   // (in front of the synchronise of either download)
         if (unsigned_variant) {
             // literal Witness::within_bound (arith.rs:372-386): canonical coefficient < bound.  The maximum is taken over CANONICAL words, so the table comes
             // down through down_ring (BabyBear planes hold Montgomery words); a maximum does not depend on the layout
@@ -660,6 +699,7 @@ struct ring_ops<Ring<C>> {
             launch_linf(b, count, mx, c->stream());
             RET(down_small(c, mx, 1, &m));
         }
+        if (io.bad()) return LF_ERR_INVALID;
         if (max_out) *max_out = m;
         *ok = m < bound;
         return LF_OK;
@@ -671,13 +711,20 @@ struct ring_ops<Ring<C>> {
         for (unsigned i = 0; i < nv; i++) pt[i] = R::ext_load(point + TAU * i);
         return pt;
     }
-    static int build_eq(C *c, const u64 *point, unsigned nv, u64 *out) {
+    static int build_eq(C *c, const u64 *point, unsigned nv, u64 *out, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         HIPCHK(hipSetDevice(c->device));
         const size_t n = (size_t)1 << nv;
+        DevIo<C> io(c, org);
+        RET(io.words(out, TAU * n));
         W *eq;
         RET(c->tbuf("io_a", TAU * n, &eq));
         RET(build_eq_dev(c, load_point(point, nv).data(), nv, eq));
+        if (io.dev) {   // the transposition below as a kernel into the caller's buffer; in an external basis the entries leave converted, as the host twin's do
+            const auto T = R::xb_mat(c->xb_T);
+            launch_ext_to_aos(eq, out, n, c->stream(), xb_converts(c, Form::ntt) ? &T : nullptr);
+            return io.finish();
+        }
         std::vector<W> h(TAU * n);
         HIPCHK(hipMemcpyAsync(h.data(), eq, h.size() * sizeof(W), hipMemcpyDeviceToHost, c->stream()));
         HIPCHK(hipStreamSynchronize(c->stream()));
@@ -685,11 +732,13 @@ struct ring_ops<Ring<C>> {
             for (size_t q = 0; q < TAU; q++) out[TAU * i + q] = R::canon(h[q * n + i]);
         return LF_OK;
     }
-    static int mle_eval_batch(C *c, const u64 *tables, size_t ntables, size_t len, const u64 *point, unsigned nv, u64 *out) {
+    static int mle_eval_batch(C *c, const u64 *tables, size_t ntables, size_t len, const u64 *point, unsigned nv, u64 *out, Origin org = Origin::host) {
         const size_t n = (size_t)1 << nv;
         if (len > n || len == 0) return LF_ERR_INVALID;   // MleEvaluationError::IncorrectLength
         std::lock_guard<std::mutex> g(c->mu);
         HIPCHK(hipSetDevice(c->device));
+        DevIo<C> io(c, org);
+        RET(io.array(tables, ntables * len));
         W *eq, *X;
         Part *partial;
         u64 *o;
@@ -697,46 +746,66 @@ struct ring_ops<Ring<C>> {
         RET(c->tbuf("io_a", ntables * len * RE, &X));
         RET(c->tbuf("red_partial", R::red_partial(ntables * RE), &partial));
         RET(c->tbuf(R::io_out, ntables * RE, &o));   // (the rings name this buffer differently; kept: buffer names are part of a context's memory footprint)
+        RET(io.begin());
         RET(build_eq_dev(c, load_point(point, nv).data(), nv, eq));
-        for (size_t a = 0; a < ntables; a++) RET(up_ring(c, tables + a * len * RE, len, X + a * RE * len, Form::ntt));
+        for (size_t a = 0; a < ntables; a++) RET(up_ring(io, tables + a * len * RE, len, X + a * RE * len, Form::ntt));
         launch_dot_eq(R::tab(c), X, len, (u32)ntables, eq, n, len, partial, o, c->stream());
-        return down_small(c, o, ntables * RE, out);
+        if (!io.dev) return down_small(c, o, ntables * RE, out);
+        std::vector<u64> h(ntables * RE);   // the caller's `out` is written only once the flag has come home clean
+        RET(io.fetch());
+        RET(down_small(c, o, ntables * RE, h.data()));
+        if (io.bad()) return LF_ERR_INVALID;
+        memcpy(out, h.data(), h.size() * 8);
+        return LF_OK;
     }
-    static int spmv(C *c, unsigned j, const u64 *z, u64 *out) {
+    static int spmv(C *c, unsigned j, const u64 *z, u64 *out, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         if (!c->have_ccs) return LF_ERR_STATE;
         if (j >= c->P.t) return LF_ERR_INVALID;
         HIPCHK(hipSetDevice(c->device));
+        DevIo<C> io(c, org);
+        RET(io.array(z, c->n));
+        RET(io.array(out, c->m));
+        RET(io.disjoint(z, c->n, out, c->m));
         W *zd, *od;
         RET(c->tbuf("io_a", c->n * RE, &zd));
         RET(c->tbuf("io_b", c->m * RE, &od));
-        RET(up_ring(c, z, c->n, zd, Form::ntt));
+        RET(io.begin());
+        RET(up_ring(io, z, c->n, zd, Form::ntt));
         if constexpr (R::general_csr) {   // Goldilocks only: dense rows gather whole elements from an element-major z
             if (c->ccs_general) {
-                W *zaos;
-                RET(c->tbuf("spmv_zaos", c->n * RE, &zaos));
-                launch_spmv_rows(R::tab(c), 1, &c->d_rowptr[j], &c->d_col[j], &c->d_val[j], zd, 0, c->n, zaos, od, c->m, 0, c->stream());
-                return down_ring(c, od, c->m, out, Form::ntt);
+                // a device z is that element-major copy already (as in lf_ccs_check_dev) -- unless it is in an external basis: then it is rebuilt from the converted planes
+                // (the checked relayout into zd above still runs then: it is the canonical-word test of z; its planes are not read)
+                const bool own = io.dev && !xb_converts(c, Form::ntt);
+                W *zaos = (W *)z;   // (canonical words are this ring's device form; read only)
+                if (!own) RET(c->tbuf("spmv_zaos", c->n * RE, &zaos));
+                launch_spmv_rows(R::tab(c), 1, &c->d_rowptr[j], &c->d_col[j], &c->d_val[j], own ? nullptr : zd, 0, c->n, zaos, od, c->m, 0, c->stream());
+                return down_ring(io, od, c->m, out, Form::ntt);
             }
         }
         launch_spmv(R::tab(c), c->d_rowptr[j], c->d_col[j], c->d_val[j], zd, c->n, od, c->m, 0, c->stream());
-        return down_ring(c, od, c->m, out, Form::ntt);
+        return down_ring(io, od, c->m, out, Form::ntt);
     }
 
     // ---- the sumchecks through the ABI (tests / SURVEY 8b): MLSumcheck::prove_as_subprotocol (utils/sumcheck.rs:53-80) split at the transcript ----
     // tables of the current round: the caller's [..][m] in round 1, halved into the other buffer (leading dimension R::halved_ld) by every later round
     static size_t sc_ld(const C *c, size_t n) { return n == c->m ? c->m : R::halved_ld(n); }
-    static int sumcheck_lin_begin(C *c, const u64 *tables, const u64 *eq_point) {
+    static int sumcheck_lin_begin(C *c, const u64 *tables, const u64 *eq_point, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         if (!c->have_ccs) return LF_ERR_STATE;
         HIPCHK(hipSetDevice(c->device));
         const lf_params &P = c->P;
         const size_t m = c->m;
+        DevIo<C> io(c, org);
+        RET(io.array(tables, (size_t)P.t * m));
         W *mz, *eqb;
         RET(c->tbuf("sc_tab0", (size_t)P.t * RE * m, &mz));
         RET(c->tbuf("sc_eq0", TAU * m, &eqb));
-        for (u32 j = 0; j < P.t; j++) RET(up_ring(c, tables + (size_t)j * m * RE, m, mz + (size_t)j * RE * m, Form::ntt));
+        RET(io.begin());
+        if (io.dev) c->sc_round = -1;   // the tables of a sumcheck in progress go now; a new one is active only once the flag has come home clean
+        for (u32 j = 0; j < P.t; j++) RET(up_ring(io, tables + (size_t)j * m * RE, m, mz + (size_t)j * RE * m, Form::ntt));
         RET(build_eq_dev(c, load_point(eq_point, P.s).data(), P.s, eqb));
+        if (io.dev) RET(io.finish());
         c->sc_round = 0; c->sc_n = m; c->sc_cur = 0;
         return LF_OK;
     }
@@ -778,7 +847,7 @@ struct ring_ops<Ring<C>> {
     // (folding/utils.rs:200-259): [eq(r_L), G_L, eq(r_R), G_R, eq(beta), f-hat_{0,0} .. f-hat_{2K-1,tau-1}], 5 + 2K*tau tables of m ring elements; the three eq
     // tables must be slot-constant (they are diagonal embeddings in the reference).  On the device: T = [eqL, eqR, eqB (tau planes each), G_L, G_R (RE planes each)]
     static constexpr size_t T5P = 3 * TAU + 2 * RE;
-    static int sumcheck_fold_begin(C *c, const u64 *tables, const u64 *mu) {
+    static int sumcheck_fold_begin(C *c, const u64 *tables, const u64 *mu, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         if (!c->have_ccs) return LF_ERR_STATE;
         HIPCHK(hipSetDevice(c->device));
@@ -786,23 +855,29 @@ struct ring_ops<Ring<C>> {
         const size_t m = c->m;
         const u32 K2 = 2 * P.K;
         static const int eq_idx[3] = {0, 2, 4};
-        for (int e = 0; e < 3; e++) {   // slot-constant check of the eq tables
-            const u64 *tb = tables + (size_t)eq_idx[e] * m * RE;
-            for (size_t i = 0; i < m; i++)
-                for (size_t sl = 1; sl < 8; sl++)
-                    if (memcmp(tb + i * RE, tb + i * RE + TAU * sl, TAU * 8) != 0) return LF_ERR_UNSUPPORTED;
-        }
+        DevIo<C> io(c, org);
+        RET(io.array(tables, (5 + (size_t)K2 * TAU) * m));
+        if (!io.dev)   // (device tables: the same test on the device, launch_slot_const_check below)
+            for (int e = 0; e < 3; e++) {   // slot-constant check of the eq tables
+                const u64 *tb = tables + (size_t)eq_idx[e] * m * RE;
+                for (size_t i = 0; i < m; i++)
+                    for (size_t sl = 1; sl < 8; sl++)
+                        if (memcmp(tb + i * RE, tb + i * RE + TAU * sl, TAU * 8) != 0) return LF_ERR_UNSUPPORTED;
+            }
         W *T, *F, *tmp;
         RET(c->tbuf("sf_T0", T5P * m, &T));
         RET(c->tbuf("sf_F0", (size_t)K2 * TAU * RE * m, &F));
         RET(c->tbuf("sf_tmp", RE * m, &tmp));
+        RET(io.begin());
+        if (io.dev) c->sf_round = -1;   // as in sumcheck_lin_begin
         for (int e = 0; e < 3; e++) {   // eqL, eqR, eqB -> extension-field tables (slot 0 of the ring table); one stream orders tmp's reuse
-            RET(up_ring(c, tables + (size_t)eq_idx[e] * m * RE, m, tmp, Form::ntt));
+            RET(up_ring(io, tables + (size_t)eq_idx[e] * m * RE, m, tmp, Form::ntt));
+            if (io.dev) launch_slot_const_check(tmp, m, io.flag, c->stream());
             HIPCHK(hipMemcpyAsync(T + TAU * e * m, tmp, TAU * m * sizeof(W), hipMemcpyDeviceToDevice, c->stream()));
         }
-        RET(up_ring(c, tables + (size_t)1 * m * RE, m, T + 3 * TAU * m, Form::ntt));
-        RET(up_ring(c, tables + (size_t)3 * m * RE, m, T + (3 * TAU + RE) * m, Form::ntt));
-        for (u32 i = 0; i < K2 * TAU; i++) RET(up_ring(c, tables + (size_t)(5 + i) * m * RE, m, F + (size_t)i * RE * m, Form::ntt));
+        RET(up_ring(io, tables + (size_t)1 * m * RE, m, T + 3 * TAU * m, Form::ntt));
+        RET(up_ring(io, tables + (size_t)3 * m * RE, m, T + (3 * TAU + RE) * m, Form::ntt));
+        for (u32 i = 0; i < K2 * TAU; i++) RET(up_ring(io, tables + (size_t)(5 + i) * m * RE, m, F + (size_t)i * RE * m, Form::ntt));
         std::vector<ExtC> mu_pow((size_t)K2 * TAU);   // mu_i^1 .. mu_i^tau in the kernels' constant form
         for (u32 i = 0; i < K2; i++) {
             const Ext mi = R::ext_load(mu + TAU * i);
@@ -811,6 +886,10 @@ struct ring_ops<Ring<C>> {
         }
         ExtC *d_mu;
         RET(upload_consts(c, R::sf_mu, mu_pow, &d_mu));
+        if (io.dev) {   // a word >= p: LF_ERR_INVALID; canonical tables whose eq tables are not slot-constant: the host twin's LF_ERR_UNSUPPORTED
+            const int rc = io.finish();
+            if (rc != LF_OK) return (io.raised() & 1) || rc != LF_ERR_INVALID ? rc : LF_ERR_UNSUPPORTED;
+        }
         c->sf_round = 0; c->sf_n = m; c->sf_cur = 0;
         return LF_OK;
     }
@@ -975,31 +1054,41 @@ struct ring_ops<Ring<C>> {
 
     // ---- folding helpers ----
     // compute_f_0 (nifs/folding.rs:258-268): out[j] = sum_i coef_i (.) tables_i[j] with ring-element coefficients (8 distinct slots)
-    static int lincomb(C *c, const u64 *coef, const u64 *tables, size_t n_terms, size_t len, u64 *out) {
+    static int lincomb(C *c, const u64 *coef, const u64 *tables, size_t n_terms, size_t len, u64 *out, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         HIPCHK(hipSetDevice(c->device));
+        DevIo<C> io(c, org);
+        RET(io.array(tables, n_terms * len));
+        RET(io.array(out, len));
+        RET(io.disjoint(tables, n_terms * len, out, len));
         W *X, *o;
         RET(c->tbuf("io_a", n_terms * len * RE, &X));
         RET(c->tbuf("io_b", len * RE, &o));
-        for (size_t i = 0; i < n_terms; i++) RET(up_ring(c, tables + i * len * RE, len, X + i * RE * len, Form::ntt));
+        RET(io.begin());
+        for (size_t i = 0; i < n_terms; i++) RET(up_ring(io, tables + i * len * RE, len, X + i * RE * len, Form::ntt));
         std::vector<ExtC> cf(n_terms * 8);
         for (size_t i = 0; i < n_terms; i++)
             for (size_t sl = 0; sl < 8; sl++) cf[i * 8 + sl] = R::ext_const(c, R::ext_load(coef + i * RE + TAU * sl));
         ExtC *d_cf;
         RET(upload_consts(c, "lc_coef", cf, &d_cf));
         launch_lincomb_z(R::tab(c), X, len, (u32)n_terms, d_cf, 1, len, o, c->stream(), 1);
-        return down_ring(c, o, len, out, Form::ntt);
+        return down_ring(io, o, len, out, Form::ntt);
     }
     // calculate_challenged_mz_mle (nifs/folding.rs:208-226) and the f-hat half of prepare_g1_and_3_k_mles_list (folding/utils.rs:524-546):
     // out[x] = sum_{i<groups} sum_{j<per_group} c_i^{j+1} T_{i,j}[x] (the reference's Horner loop `mle += M; mle *= c_i` over j reversed)
-    static int horner_combine(C *c, const u64 *tables, size_t groups, size_t per_group, size_t len, const u64 *challenges, u64 *out) {
+    static int horner_combine(C *c, const u64 *tables, size_t groups, size_t per_group, size_t len, const u64 *challenges, u64 *out, Origin org = Origin::host) {
         std::lock_guard<std::mutex> g(c->mu);
         HIPCHK(hipSetDevice(c->device));
         const size_t nt = groups * per_group;
+        DevIo<C> io(c, org);
+        RET(io.array(tables, nt * len));
+        RET(io.array(out, len));
+        RET(io.disjoint(tables, nt * len, out, len));
         W *X, *o;
         RET(c->tbuf("io_a", nt * len * RE, &X));
         RET(c->tbuf("io_b", len * RE, &o));
-        for (size_t i = 0; i < nt; i++) RET(up_ring(c, tables + i * len * RE, len, X + i * RE * len, Form::ntt));
+        RET(io.begin());
+        for (size_t i = 0; i < nt; i++) RET(up_ring(io, tables + i * len * RE, len, X + i * RE * len, Form::ntt));
         std::vector<ExtC> cf(nt);
         for (size_t i = 0; i < groups; i++) {
             Ext ci = R::ext_load(challenges + TAU * i), pw = ci;
@@ -1008,7 +1097,7 @@ struct ring_ops<Ring<C>> {
         ExtC *d_cf;
         RET(upload_consts(c, "lc_coef", cf, &d_cf));
         launch_lincomb_z(R::tab(c), X, len, (u32)nt, d_cf, 1, len, o, c->stream(), 0);
-        return down_ring(c, o, len, out, Form::ntt);
+        return down_ring(io, o, len, out, Form::ntt);
     }
 };
 }  // namespace lfring

@@ -133,6 +133,57 @@ void launch_soa_to_aos(const typename F::word *soa, u64 *aos, size_t n, hipStrea
     else hipLaunchKernelGGL((k_soa_to_aos<F, false, false>), g, b, 0, s, soa, aos, n);
 }
 
+// An extension-field table [TAU][n] (an eq table) -> the caller's own device buffer [n][TAU] canonical u64: the store of lf_build_eq_dev, the shape of the host
+// transposition of lf_build_eq.  One thread per entry: the TAU plane reads of a wave are TAU full runs, its writes one run of 64 * TAU words.  XBASIS and
+// Opt as above: entry -> M * entry (M = T, internal -> external coordinates) before the write.  (No UNLESS form: the call has no device input to test.)
+template <class F, bool XBASIS, class... Opt>
+__global__ void __launch_bounds__(256) k_ext_to_aos(const typename F::word *soa, u64 *aos, size_t n, Opt... opt) {
+    static_assert(sizeof...(Opt) == (XBASIS ? 1 : 0), "matrix if XBASIS");
+    constexpr int TAU = F::TAU;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    typename F::word v[TAU];
+#pragma unroll
+    for (int q = 0; q < TAU; q++) v[q] = soa[(size_t)q * n + i];
+    if constexpr (XBASIS) {
+        const typename F::XbMat &M = opt_arg<typename F::XbMat>(opt...);
+#pragma unroll 1
+        for (int r = 0; r < TAU; r++) {
+            typename F::word s = F::mul(M.m[TAU * r], v[0]);
+#pragma unroll
+            for (int q = 1; q < TAU; q++) s = F::add(s, F::mul(M.m[TAU * r + q], v[q]));
+            aos[i * TAU + r] = F::to_canon(s);
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < TAU; q++) aos[i * TAU + q] = F::to_canon(v[q]);
+    }
+}
+template <class F>
+void launch_ext_to_aos(const typename F::word *soa, u64 *aos, size_t n, hipStream_t s, const typename F::XbMat *T) {
+    if (!n) return;
+    const dim3 g(cdiv(n, 256)), b(256);
+    if (T) hipLaunchKernelGGL((k_ext_to_aos<F, true>), g, b, 0, s, soa, aos, n, *T);
+    else hipLaunchKernelGGL((k_ext_to_aos<F, false>), g, b, 0, s, soa, aos, n);
+}
+// A ring table [RE][n] that must be slot-constant (the eq tables of lf_sumcheck_fold_begin_dev, which the host cannot inspect): bit 1 of *flag goes up where
+// slot k > 0 of an entry differs from slot 0.  (Equal field elements are equal device words on both rings.)
+template <class F>
+__global__ void __launch_bounds__(256) k_slot_const_check(const typename F::word *tab, size_t n, u32 *flag) {
+    constexpr int RE = F::RE, TAU = F::TAU;
+    size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x, st = (size_t)gridDim.x * 256;
+    bool bad = false;
+    for (; idx < (size_t)(RE - TAU) * n; idx += st) {
+        const size_t w = TAU + idx / n, i = idx % n;
+        bad |= tab[w * n + i] != tab[(w % TAU) * n + i];
+    }
+    if (bad) atomicOr(flag, 2u);
+}
+template <class F>
+void launch_slot_const_check(const typename F::word *tab, size_t n, u32 *flag, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_slot_const_check<F>, dim3(grid_for((size_t)(F::RE - F::TAU) * n)), dim3(256), 0, s, tab, n, flag);
+}
+
 // rows [row0, row0 + kappa) of the synthetic Ajtai matrix into A [kappa][RE][n]: columns [col0, col0 + n) of the n_total-column matrix
 template <class F>
 __global__ void __launch_bounds__(256) k_fill_ajtai(typename F::word *A, u32 kappa, size_t n, size_t n_total, size_t col0, u64 seed, u32 row0) {

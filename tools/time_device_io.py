@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Host-pointer call against its `_dev` twin at the shapes a user runs, in one process: wall-clock time of calls that end in the library's own synchronise.
 
-    python tools/time_device_io.py [--reps 9] [--out profiles/device_io_times.jsonl] [--only NAME ...]
+    python tools/time_device_io.py [--reps 9] [--out profiles/device_io_times.jsonl] [--only NAME ...] [--append]
 
 Per shape: both variants are warmed up, then `reps` (>= 9) repetitions with the two variants ALTERNATING, host clock around each call.  The host-pointer
 variant reads a pageable numpy array (what a ctypes or Rust caller has) and is the behaviour before the `_dev` entry points existed; the device variant reads a
 torch tensor that is already resident.  One JSON line per shape: min and median of both variants in ms, the array's size, the ratio of the medians.
 
 Shapes: commit_ntt at the reference's CommitNTT rows (Goldilocks kappa 20, BabyBear kappa 15, n = 2^20), Witness::from_w_ccs, lf_ccs_check and
-lf_witness_get_f at C4."""
+lf_witness_get_f at C4; the component calls (`--only components`, or one of their names): at C4 decompose / recompose of w_ccs (B, L), linf_check of f (N
+elements), build_eq at nv = s and spmv of matrix 0; at C2 (m = 2^16 rows) t = 3 tables for mle_eval_batch, sumcheck_lin_begin, lincomb and horner_combine, and
+the 5 + 2 K tau tables of sumcheck_fold_begin."""
 import argparse
 import ctypes as C
 import json
@@ -105,13 +107,137 @@ def c4_shapes(reps, only):
     return out
 
 
+COMPONENTS = ("decompose", "recompose", "linf_check", "build_eq", "mle_eval_batch", "spmv", "sumcheck_lin_begin", "sumcheck_fold_begin", "lincomb",
+              "horner_combine")
+
+
+def component_shapes(reps, only):
+    """the ten component calls, element-wise ones at C4 and table calls at C2; each pair is checked for equal results before it is timed.  The host-pointer side
+    is timed as the get_f row above: the C entry point itself, on host buffers that exist and have been written before the first timed call (no allocation and
+    no first-touch page faults inside a timed call); the device side writes into a tensor that exists"""
+    ring = "goldilocks"
+    out = []
+    tag = "C4"
+    L = api._lib()
+    rnd = lambda seed, *shape: np.ascontiguousarray(splitmix_fq(seed, 0, int(np.prod(shape)), ring).reshape(shape))
+    host = lambda t: t.cpu().numpy().view(np.uint64)
+    u = lambda a: a.ctypes.data_as(api.u64p)
+    hbuf = lambda *shape: np.ones(shape, dtype=np.uint64)                                   # (written: every page is there)
+    dbuf = lambda *shape: torch.zeros(shape, dtype=torch.int64, device="cuda")
+
+    def ok(rc):
+        assert rc == 0, rc
+
+    def pair(name, arr, host_call, dev_call, same):
+        torch.cuda.synchronize()
+        host_call()
+        dev_call()
+        assert same(), name
+        th, td = measure(host_call, dev_call, reps)
+        out.append(row(f"{name} {tag}", ring, arr.nbytes / 1e6, th, td))
+
+    wl = make_workload("C4")
+    ctx = api.Context(0)
+    try:
+        ctx.load_ccs(wl)
+        h, RE, m, s = ctx.h, ctx.RE, wl.m, wl.s
+        if "decompose" in only or "recompose" in only:
+            x = np.ascontiguousarray(ctx.icrt(wl.w_ccs))
+            cnt = wl.wit_len
+            xd, ho, do = dev(x), hbuf(cnt * wl.L, RE), dbuf(cnt * wl.L, RE)
+            if "decompose" in only:
+                pair("lf_decompose", x, lambda: ok(L.lf_decompose(h, u(x), cnt, wl.B, wl.L, 0, u(ho))), lambda: ctx.decompose(xd, wl.B, wl.L, 0, out=do),
+                     lambda: (ho == host(do)).all())
+            if "recompose" in only:
+                d = np.ascontiguousarray(ctx.decompose(x, wl.B, wl.L, 0))
+                dd, ho1, do1 = dev(d), hbuf(cnt, RE), dbuf(cnt, RE)
+                pair("lf_recompose", d, lambda: ok(L.lf_recompose(h, u(d), cnt, wl.B, wl.L, u(ho1))), lambda: ctx.recompose(dd, wl.B, wl.L, out=do1),
+                     lambda: (ho1 == host(do1)).all() and (ho1 == x).all())
+        if "linf_check" in only:
+            f = np.ascontiguousarray(ctx.crt(ctx.decompose(ctx.icrt(wl.w_ccs), wl.B, wl.L, 0)))
+            fd = dev(f)
+            got = {}
+            okw, mx = C.c_int(), C.c_uint64()
+
+            def host_linf():
+                ok(L.lf_linf_check(h, u(f), wl.N, wl.B, 0, C.byref(okw), C.cast(C.byref(mx), api.u64p)))
+                got["h"] = (bool(okw.value), mx.value)
+
+            def dev_linf():
+                got["d"] = ctx.linf_check(fd, wl.B)
+
+            pair("lf_linf_check", f, host_linf, dev_linf, lambda: got["h"] == got["d"])
+        if "build_eq" in only:
+            pt = rnd(21, s, ctx.TAU)
+            ho, do = hbuf(1 << s, ctx.TAU), dbuf(1 << s, ctx.TAU)
+            pair(f"lf_build_eq nv={s}", ho, lambda: ok(L.lf_build_eq(h, u(pt), s, u(ho))), lambda: ctx.build_eq(pt, out=do), lambda: (ho == host(do)).all())
+        if "spmv" in only:
+            z = np.ascontiguousarray(wl.z())
+            zd, ho, do = dev(z), hbuf(m, RE), dbuf(m, RE)
+            pair("lf_spmv", z, lambda: ok(L.lf_spmv(h, 0, u(z), u(ho))), lambda: ctx.mat_vec_mul(0, zd, out=do), lambda: (ho == host(do)).all())
+    finally:
+        ctx.close()
+    if not {"mle_eval_batch", "sumcheck_lin_begin", "lincomb", "horner_combine", "sumcheck_fold_begin"} & set(only):
+        return out
+    wl = make_workload("C2")
+    tag = "C2"
+    ctx = api.Context(0)
+    try:
+        ctx.load_ccs(wl)
+        h, RE, m, s = ctx.h, ctx.RE, wl.m, wl.s
+        if {"mle_eval_batch", "sumcheck_lin_begin", "lincomb", "horner_combine"} & set(only):
+            assert wl.t == 3 and m == 1 << 16
+            tabs = rnd(22, 3, m, RE)
+            td3 = dev(tabs)
+            pt = rnd(23, s, ctx.TAU)
+            ho, do = hbuf(m, RE), dbuf(m, RE)
+            if "mle_eval_batch" in only:
+                ev, got = hbuf(3, RE), {}
+
+                def dev_mle():
+                    got["d"] = ctx.evaluate_mles(td3, pt)
+
+                pair("lf_mle_eval_batch t=3", tabs, lambda: ok(L.lf_mle_eval_batch(h, u(tabs), 3, m, u(pt), s, u(ev))), dev_mle, lambda: (ev == got["d"]).all())
+            if "sumcheck_lin_begin" in only:
+                first = lambda t: api.MLSumcheckLin(ctx, t, pt).prove_round()       # (begin alone has no result to compare: the first message stands for it)
+                assert (first(tabs) == first(td3)).all()
+                pair("lf_sumcheck_lin_begin t=3", tabs, lambda: ok(L.lf_sumcheck_lin_begin(h, u(tabs), u(pt))), lambda: api.MLSumcheckLin(ctx, td3, pt),
+                     lambda: True)
+            if "lincomb" in only:
+                coef = rnd(24, 3, RE)
+                pair("lf_lincomb t=3", tabs, lambda: ok(L.lf_lincomb(h, u(coef), u(tabs), 3, m, u(ho))), lambda: api.lincomb(ctx, coef, td3, out=do),
+                     lambda: (ho == host(do)).all())
+            if "horner_combine" in only:
+                ch = rnd(25, 3, ctx.TAU)
+                t4d = td3.reshape(3, 1, m, RE)
+                pair("lf_horner_combine t=3", tabs, lambda: ok(L.lf_horner_combine(h, u(tabs), 3, 1, m, u(ch), u(ho))),
+                     lambda: api.horner_combine(ctx, t4d, ch, out=do), lambda: (ho == host(do)).all())
+        if "sumcheck_fold_begin" in only:
+            nt = 5 + 2 * wl.K * ctx.TAU
+            ftab = rnd(26, nt, m, RE)
+            for k, idx in enumerate((0, 2, 4)):       # the eq tables are slot-constant
+                ftab[idx] = np.tile(ctx.build_eq(rnd(27 + k, s, ctx.TAU)), (1, 8))
+            mu = rnd(30, 2 * wl.K, ctx.TAU)
+            fd = dev(ftab)
+            first = lambda t: api.MLSumcheckFold(ctx, t, mu).prove_round()
+            assert (first(ftab) == first(fd)).all()
+            pair(f"lf_sumcheck_fold_begin {nt} tables", ftab, lambda: ok(L.lf_sumcheck_fold_begin(h, u(ftab), u(mu))), lambda: api.MLSumcheckFold(ctx, fd, mu),
+                 lambda: True)
+    finally:
+        ctx.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "device_io_times.jsonl"))
-    ap.add_argument("--only", nargs="*", default=["commit_gold", "commit_bb", "from_w_ccs", "ccs_check", "get_f"])
+    ap.add_argument("--only", nargs="*", default=["commit_gold", "commit_bb", "from_w_ccs", "ccs_check", "get_f", "components"])
+    ap.add_argument("--append", action="store_true", help="add the rows to --out, keeping what it holds")
     a = ap.parse_args()
     assert a.reps >= 9
+    if "components" in a.only:
+        a.only = [x for x in a.only if x != "components"] + list(COMPONENTS)
     rows = []
     if "commit_gold" in a.only:
         rows.append(commit_ntt("goldilocks", 20, a.reps))
@@ -123,8 +249,12 @@ def main():
         for r in c4_shapes(a.reps, a.only):
             rows.append(r)
             print(json.dumps(r), flush=True)
+    if set(COMPONENTS) & set(a.only):
+        for r in component_shapes(a.reps, a.only):
+            rows.append(r)
+            print(json.dumps(r), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
+    with open(a.out, "a" if a.append else "w") as f:
         for r in rows:
             f.write(json.dumps(r) + "\n")
 
