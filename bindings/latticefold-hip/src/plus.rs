@@ -191,6 +191,142 @@ impl<R: RingWords + Clone> HipPlusProver<R> {
         self.nacc = 2;
         Ok(PlusProof(proof))
     }
+
+    // ---- device-resident callers (`lfplus.h` "device-resident callers"): raw device pointers, as `HipContext::*_dev` of lib.rs.  NOT COMPILED, like the rest.
+
+    /// `lfplus_prover_wait_stream`: every context of the prover waits for what `hip_stream` holds now (null: the default stream)
+    /// # Safety
+    /// `hip_stream` is a live `hipStream_t` of the prover's device, or null
+    pub unsafe fn wait_stream(&mut self, hip_stream: *mut core::ffi::c_void) -> Result<(), HipPlusError> {
+        // SAFETY: the caller's contract
+        let rc = unsafe { sys::lfplus_prover_wait_stream(self.raw, hip_stream) };
+        if rc != sys::LFPLUS_OK { Err(self.err(rc, "lfplus_prover_wait_stream")) } else { Ok(()) }
+    }
+
+    /// `lfplus_prover_ingest_dev`: the fresh instances of the next prove from short witnesses `z[i]` (m ring elements each) in DEVICE memory, read in
+    /// place -> their commitments (count x kappa x 16 words)
+    /// # Safety
+    /// every `z[i]` is 16-byte aligned device memory of the prover's device holding m x 16 canonical words, complete on the stream last passed to `wait_stream`
+    pub unsafe fn ingest_dev(&mut self, z: &[*const u64], m: usize, l_in: usize) -> Result<Vec<u64>, HipPlusError> {
+        let mut cm = vec![0u64; z.len() * self.params.kappa as usize * 16];
+        // SAFETY: the caller's contract; cm holds count x kappa ring elements
+        let rc = unsafe { sys::lfplus_prover_ingest_dev(self.raw, z.as_ptr(), z.len() as u32, m as u64, l_in as u32, cm.as_mut_ptr()) };
+        if rc != sys::LFPLUS_OK { Err(self.err(rc, "lfplus_prover_ingest_dev")) } else { Ok(cm) }
+    }
+
+    /// `lfplus_prover_set_instances_dev`: the same from witnesses `f[i]` (n ring elements each) in DEVICE memory; copied and checked before the call returns
+    /// (no upload thread, nothing is borrowed afterwards).  `cm_f[i]`: host words (kappa x 16) or null
+    /// # Safety
+    /// every `f[i]` is 16-byte aligned device memory of the prover's device holding n x 16 words; every non-null `cm_f[i]` is kappa x 16 host words
+    pub unsafe fn set_instances_dev(&mut self, f: &[*const u64], cm_f: &[*const u64]) -> Result<(), HipPlusError> {
+        assert_eq!(f.len(), cm_f.len());
+        // SAFETY: the caller's contract
+        let rc = unsafe { sys::lfplus_prover_set_instances_dev(self.raw, f.as_ptr(), cm_f.as_ptr(), f.len() as u32) };
+        if rc != sys::LFPLUS_OK { Err(self.err(rc, "lfplus_prover_set_instances_dev")) } else { Ok(()) }
+    }
+
+    /// `lfplus_prover_accumulator_dev`: the accumulator halves copied, device to device, into `F0` / `F1` (n x 16 words each; either may be null)
+    /// # Safety
+    /// non-null pointers are 16-byte aligned device memory of the prover's device with room for n x 16 words, and do not overlap
+    pub unsafe fn accumulator_dev(&mut self, F0: *mut u64, F1: *mut u64) -> Result<(), HipPlusError> {
+        // SAFETY: the caller's contract
+        let rc = unsafe { sys::lfplus_prover_accumulator_dev(self.raw, F0, F1) };
+        if rc != sys::LFPLUS_OK { Err(self.err(rc, "lfplus_prover_accumulator_dev")) } else { Ok(()) }
+    }
+}
+
+/// One `lfplus_ctx` for the component calls on DEVICE memory (`lfplus_*_dev`): the commitment matrix generated on the device, witnesses and vectors as raw
+/// device pointers.  NOT COMPILED, like the rest of the crate.
+pub struct HipPlusContext {
+    raw: *mut sys::lfplus_ctx,
+    kappa: usize,
+}
+// SAFETY: no thread affinity (every entry point selects its device); `&mut self` serialises the users
+unsafe impl Send for HipPlusContext {}
+
+impl HipPlusContext {
+    /// `lfplus_ctx_create` + `lfplus_matrix_generate(seed, kappa, n)`
+    pub fn generate(device: i32, seed: u64, kappa: usize, n: usize) -> Result<Self, HipPlusError> {
+        let mut raw = core::ptr::null_mut();
+        // SAFETY: raw receives an owned handle
+        let rc = unsafe { sys::lfplus_ctx_create(device, &mut raw) };
+        if rc != sys::LFPLUS_OK {
+            return Err(HipPlusError::new(rc, "lfplus_ctx_create", "no usable device"));
+        }
+        let ctx = HipPlusContext { raw, kappa };
+        // SAFETY: live handle
+        ctx.chk(unsafe { sys::lfplus_matrix_generate(raw, seed, kappa as u32, n as u64) }, "lfplus_matrix_generate")?;
+        Ok(ctx)
+    }
+    fn chk(&self, rc: i32, what: &'static str) -> Result<(), HipPlusError> {
+        if rc == sys::LFPLUS_OK {
+            return Ok(());
+        }
+        // SAFETY: a NUL-terminated string owned by the context, valid until its next call
+        let msg = unsafe { std::ffi::CStr::from_ptr(sys::lfplus_last_error(self.raw)) }.to_string_lossy().into_owned();
+        Err(HipPlusError::new(rc, what, msg))
+    }
+    /// `lfplus_ctx_wait_stream`
+    /// # Safety
+    /// `hip_stream` is a live `hipStream_t` of the context's device, or null
+    pub unsafe fn wait_stream(&mut self, hip_stream: *mut core::ffi::c_void) -> Result<(), HipPlusError> {
+        // SAFETY: the caller's contract
+        self.chk(unsafe { sys::lfplus_ctx_wait_stream(self.raw, hip_stream) }, "lfplus_ctx_wait_stream")
+    }
+    /// `lfplus_set_witness_dev`
+    /// # Safety
+    /// `f`: n x 16 words of 16-byte aligned device memory of the context's device
+    pub unsafe fn set_witness_dev(&mut self, f: *const u64, n: usize) -> Result<(), HipPlusError> {
+        // SAFETY: the caller's contract
+        self.chk(unsafe { sys::lfplus_set_witness_dev(self.raw, f, n as u64) }, "lfplus_set_witness_dev")
+    }
+    /// `lfplus_witness_from_z_dev` -> cm_f
+    /// # Safety
+    /// `z`: m x 16 words of 16-byte aligned device memory of the context's device
+    pub unsafe fn witness_from_z_dev(&mut self, z: *const u64, m: usize, b: u64, k: u32) -> Result<Vec<u64>, HipPlusError> {
+        let mut cm = vec![0u64; self.kappa * 16];
+        // SAFETY: the caller's contract; cm holds kappa ring elements
+        self.chk(unsafe { sys::lfplus_witness_from_z_dev(self.raw, z, m as u64, b, k, cm.as_mut_ptr()) }, "lfplus_witness_from_z_dev")?;
+        Ok(cm)
+    }
+    /// `lfplus_commit_dev` -> A v
+    /// # Safety
+    /// `v`: n x 16 words of 16-byte aligned device memory of the context's device
+    pub unsafe fn commit_dev(&mut self, v: *const u64, n: usize) -> Result<Vec<u64>, HipPlusError> {
+        let mut out = vec![0u64; self.kappa * 16];
+        // SAFETY: the caller's contract; out holds kappa ring elements
+        self.chk(unsafe { sys::lfplus_commit_dev(self.raw, v, n as u64, out.as_mut_ptr()) }, "lfplus_commit_dev")?;
+        Ok(out)
+    }
+    /// `lfplus_get_witness_dev`
+    /// # Safety
+    /// `f_out`: room for n x 16 words of 16-byte aligned device memory of the context's device
+    pub unsafe fn get_witness_dev(&mut self, f_out: *mut u64, n: usize) -> Result<(), HipPlusError> {
+        // SAFETY: the caller's contract
+        self.chk(unsafe { sys::lfplus_get_witness_dev(self.raw, f_out, n as u64) }, "lfplus_get_witness_dev")
+    }
+    /// `lfplus_decompose_dev` on the resident constraint matrices (`nm` of them; 0: none) -> (C0, C1, v0, v1); `F0` / `F1` (either may be null) receive the halves
+    /// # Safety
+    /// non-null `F0` / `F1`: room for n x 16 words of 16-byte aligned device memory of the context's device each, not overlapping; `r_a` / `r_b`: log2(n) ring elements
+    pub unsafe fn decompose_dev(&mut self, B: u64, r_a: &[u64], r_b: &[u64], nm: usize, F0: *mut u64, F1: *mut u64) -> Result<[Vec<u64>; 4], HipPlusError> {
+        let (mut c0, mut c1) = (vec![0u64; self.kappa * 16], vec![0u64; self.kappa * 16]);
+        let (mut v0, mut v1) = (vec![0u64; (1 + nm) * 32], vec![0u64; (1 + nm) * 32]);
+        // SAFETY: the caller's contract; the host outputs have the sizes lfplus.h documents; null CSR pointers select the resident matrices
+        self.chk(
+            unsafe {
+                sys::lfplus_decompose_dev(self.raw, B, r_a.as_ptr(), r_b.as_ptr(), nm as u32, core::ptr::null(), core::ptr::null(), core::ptr::null(), F0, F1, c0.as_mut_ptr(),
+                                          c1.as_mut_ptr(), v0.as_mut_ptr(), v1.as_mut_ptr())
+            },
+            "lfplus_decompose_dev",
+        )?;
+        Ok([c0, c1, v0, v1])
+    }
+}
+impl Drop for HipPlusContext {
+    fn drop(&mut self) {
+        // SAFETY: owned handle, destroyed once
+        unsafe { sys::lfplus_ctx_destroy(self.raw) }
+    }
 }
 
 impl<R> Drop for HipPlusProver<R> {

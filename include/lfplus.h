@@ -325,6 +325,50 @@ int lfplus_prover_decide(lfplus_prover *prover, const uint64_t *proof, uint64_t 
 int lfplus_verify(const lfplus_params *params, uint64_t n, uint32_t nM, uint32_t L, uint32_t nfresh, lfplus_transcript *transcript, const uint64_t *proof,
                   uint64_t proof_words, int *which, int *stage);
 
+/* ---- device-resident callers: the O(n) arrays as DEVICE memory ------------------------------------------------------------------------------------------
+ * Every entry point above takes host pointers.  A `_dev` twin has the parameter list of its call and its results, word for word, but the O(n) arrays -- the
+ * witness f, the short witness z, the vector v of lfplus_commit, f_out, the halves F0 / F1 -- are memory of the CONTEXT'S DEVICE (hipMalloc, a torch tensor,
+ * ...).  Everything small stays a host pointer: cm_f, out, C0 / C1, v0 / v1, r_a / r_b, the CSR arrays, the arrays OF pointers (z, f of the prover calls: host
+ * arrays of device pointers; cm_f of lfplus_prover_set_instances_dev: host arrays throughout).  No twin exists for the commitment matrix (set once;
+ * lfplus_matrix_generate avoids the upload), for lfplus_rg_read, the digit arrays of the set check / range check or the relation checks.
+ *   Layout: that of the host ABI -- coefficient form, 16 canonical little-endian u64 words per ring element, AoS.  It is also the library's resident layout:
+ * lfplus_witness_from_z_dev, lfplus_commit_dev and lfplus_decompose_dev read and write the caller's array in place (no staging copy; lfplus_decompose_dev
+ * allocates no scratch for a half the caller receives), lfplus_set_witness_dev and lfplus_prover_set_instances_dev copy it once with the kernel that tests its
+ * words, lfplus_get_witness_dev and lfplus_prover_accumulator_dev are one device-to-device copy.
+ *   Pointer checks, after the twin's own argument and state checks and before anything is touched or enqueued: the array is not NULL (F0 / F1 may be, as in the
+ * host calls), hipPointerGetAttributes reports unmanaged device memory of the context's device, hipMemGetAddressRange shows ONE allocation covering every byte
+ * the call touches, and the pointer is 16-BYTE aligned (lfhip.h asks for 8: the kernels of this slice use 16-byte vector accesses; a view of whole ring elements
+ * into any allocation satisfies it).  Anything else -- a host or pinned pointer, another device, a misaligned pointer, a range that runs off its allocation -- is
+ * LFPLUS_E_ARG with a message in lfplus_last_error / lfplus_prover_last_error: no kernel is launched on such a pointer, no output is written, the context keeps
+ * the resident witness and the lfplus_rg_from_f results it had, the prover is not FAILED and stays usable.  (lfplus_witness_from_z_dev keeps the witness on
+ * EVERY refusal of its checks; its host twin drops it.)  A sharded context (a transport or lfplus_set_sharding_model) refuses every _dev call the same way.
+ *   Canonical words: the host cannot inspect device data, so the device does.  lfplus_set_witness_dev and lfplus_witness_from_z_dev behave as their twins: a
+ * word >= p is LFPLUS_E_ARG and the context is left WITHOUT a resident witness.  lfplus_commit_dev: LFPLUS_E_ARG, `out` is not written, the resident witness is
+ * untouched.
+ *   Overlap: F0 and F1 of lfplus_decompose_dev / lfplus_prover_accumulator_dev must not overlap each other (LFPLUS_E_ARG); read-only inputs may alias each other.
+ *   Ordering: a _dev call reads its inputs on the context's stream.  The caller guarantees that they are complete -- by synchronising its own stream, or by
+ * lfplus_ctx_wait_stream(ctx, stream) first: it records an event on `stream` (a hipStream_t; NULL = the default stream) and makes both streams of the context
+ * wait for it, without blocking the host and without touching `stream` otherwise; lfplus_prover_wait_stream does so for every context of the prover (and joins
+ * an upload thread that still writes into them).  A _dev call returns after the context's stream is synchronised: device outputs are complete and the inputs
+ * are free for reuse on return.
+ *   After a failure other than the refusals above (LFPLUS_E_HIP, a non-canonical word) the device outputs of the call are undefined; the context or prover is
+ * in the state its host twin leaves (no resident witness; an error INSIDE lfplus_prover_ingest_dev / lfplus_prover_set_instances_dev makes the prover FAILED).
+ *   No upload thread: lfplus_prover_set_instances_dev copies and checks on the calling thread and returns when the instances are resident -- f[i] is NOT
+ * borrowed after it returns, a non-canonical word is reported by THIS call (LFPLUS_E_ARG, prover FAILED), and the following prove finds every instance arrived.
+ *   Pending work: a pending lfplus_rg_from_f_async pass is joined before the witness it reads is overwritten, exactly as in the twins. */
+int lfplus_ctx_wait_stream(lfplus_ctx *ctx, void *hip_stream);
+int lfplus_set_witness_dev(lfplus_ctx *ctx, const uint64_t *f, uint64_t n);
+int lfplus_witness_from_z_dev(lfplus_ctx *ctx, const uint64_t *z, uint64_t m, uint64_t b, uint32_t k, uint64_t *cm_f);
+int lfplus_commit_dev(lfplus_ctx *ctx, const uint64_t *v, uint64_t n, uint64_t *out);
+int lfplus_get_witness_dev(lfplus_ctx *ctx, uint64_t *f_out /* n * 16 words */, uint64_t n);
+int lfplus_decompose_dev(lfplus_ctx *ctx, uint64_t B, const uint64_t *r_a, const uint64_t *r_b, uint32_t nm, const uint32_t *const *rowptr,
+                         const uint32_t *const *col, const uint64_t *const *val, uint64_t *F0, uint64_t *F1, uint64_t *C0, uint64_t *C1, uint64_t *v0,
+                         uint64_t *v1);
+int lfplus_prover_wait_stream(lfplus_prover *prover, void *hip_stream);
+int lfplus_prover_ingest_dev(lfplus_prover *prover, const uint64_t *const *z, uint32_t count, uint64_t m, uint32_t l_in, uint64_t *cm_f_out);
+int lfplus_prover_set_instances_dev(lfplus_prover *prover, const uint64_t *const *f, const uint64_t *const *cm_f, uint32_t count);
+int lfplus_prover_accumulator_dev(lfplus_prover *prover, uint64_t *F0, uint64_t *F1);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,7 @@
 #include "bb_ctx.h"
 #include "lf_check.h"
 #include "lf_ctx.h"
+#include "lf_dev_ptr.h"
 
 #pragma GCC visibility push(hidden)
 // ---- lengths in ring elements (tau = extension degree: the v part of an LCCCS and of the proofs is tau elements) ------------------------------------
@@ -195,21 +196,13 @@ int down_ring(C *c, const typename Ring<C>::W *src, size_t n, u64 *host, Form f)
 // into the caller's buffer only while the flag is down (launch_soa_to_aos's unless_flag), and the call returns LF_ERR_INVALID.  A body with several input
 // tables (mle_eval_batch, lincomb, horner_combine, the sumcheck begins) relayouts each into the scratch of the host path and acts on the flag once, at the end;
 // one with several result tables (decompose, layout 1) stores each behind the flag (store_ring) and ends in DevIo::finish.
-enum class Origin { host, device };
-// [p, p + bytes) lies inside the allocation [base, base + size): the whole range arithmetic of the pointer checks
-inline bool range_inside(uintptr_t base, size_t size, uintptr_t p, size_t bytes) { return p >= base && p - base <= size && bytes <= size - (p - base); }
+// (Origin and the check itself: lf_dev_ptr.h, which the LatticeFold+ slice includes as well)
+using lfdev::Origin;
+using lfdev::range_inside;
 // THE pointer check of every _dev entry point, before anything is enqueued: device memory of `device`, 8-byte aligned, `bytes` bytes inside one allocation.
 // A host or pinned pointer, managed memory, another device's memory, a range that runs off its allocation: LF_ERR_INVALID, never a launch
-inline int dev_array_check(int device, const void *p, size_t bytes) {
-    if (!p || ((uintptr_t)p & 7)) return LF_ERR_INVALID;
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return LF_ERR_INVALID; }   // (older runtimes fail on plain host memory)
-    if (at.type != hipMemoryTypeDevice || at.isManaged || at.device != device) return LF_ERR_INVALID;
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return LF_ERR_INVALID; }
-    return range_inside((uintptr_t)base, size, (uintptr_t)p, bytes) ? LF_OK : LF_ERR_INVALID;
-}
+using lfdev::dev_array_check;
+static_assert(LF_OK == 0 && LF_ERR_INVALID == -1, "dev_array_check returns 0 / -1");
 template <class C>
 struct DevIo {
     C *c;

@@ -8,7 +8,32 @@
 #include "../../include/lfplus.h"
 #include "lfp_kernels.h"
 #include "lfp_ctx.h"
+#include "lfp_guard.h"
+#include "lf_dev_ptr.h"
 
+using lfdev::Origin;
+static_assert(LFPLUS_OK == 0 && LFPLUS_E_ARG == -1, "dev_array_check returns 0 / -1");
+// ---- the _dev twins (lfplus.h "device-resident callers"): every body below that takes an O(n) array takes its Origin as well ----------------------------------
+// a sharded context has no device spelling: the witness is whole on every rank as the HOST hands it over
+static int dev_unsharded(lfplus_ctx *c, Origin o, const char *who) {
+    return o == Origin::device && c->sharded() ? fail(c, LFPLUS_E_ARG, std::string(who) + ": sharded contexts take host pointers only") : LFPLUS_OK;
+}
+// THE pointer check of a device-origin array of `elems` ring elements (dev_array_check, lf_dev_ptr.h; 16-byte aligned here: the kernels of this slice read and
+// write their operands with 16-byte vector accesses), after the call's argument and state checks and before anything is touched or enqueued
+int lfp_dev_ptr_check(lfplus_ctx *c, const void *p, uint64_t elems, const char *who) {
+    if (elems <= (1ull << 32) && lfdev::dev_array_check(c->device, p, (size_t)elems * 16 * 8, 16) == 0) return LFPLUS_OK;
+    return fail(c, LFPLUS_E_ARG, std::string(who) + ": not " + std::to_string(elems) + " ring elements of unmanaged, 16-byte aligned device memory of this context's device inside one allocation");
+}
+static int dev_array(lfplus_ctx *c, Origin o, const void *p, uint64_t elems, const char *who) { return o == Origin::device ? lfp_dev_ptr_check(c, p, elems, who) : LFPLUS_OK; }
+static bool overlap(const void *a, const void *b, uint64_t elems) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b, bytes = (uintptr_t)elems * 16 * 8;
+    return a && b && pa < pb + bytes && pb < pa + bytes;
+}
+// the guard's answer when memory itself ran out: the message is a literal, nothing is formatted
+static int oom(lfplus_ctx *c, const char *m) {
+    try { c->err = m; } catch (...) {}
+    return LFPLUS_E_HIP;
+}
 
 extern "C" int lfplus_ctx_create(int device, lfplus_ctx **out) {
     if (!out) return LFPLUS_E_ARG;
@@ -205,8 +230,12 @@ extern "C" int lfplus_share_matrix(lfplus_ctx *c, lfplus_ctx *from) {
 }
 // The words are checked on the DEVICE, behind the upload (a host scan of a 2^20-row witness costs 5 ms, twice its upload): a non-canonical word fails the call
 // and leaves the context WITHOUT a resident witness.
-extern "C" int lfplus_set_witness(lfplus_ctx *c, const uint64_t *f, uint64_t n) {
+// Device origin: the caller's array is read once, by the kernel that tests its words and writes the resident copy (k_copy_checked).
+static int set_witness(lfplus_ctx *c, const uint64_t *f, uint64_t n, Origin o) {
     if (!c || !f || !n) return fail(c, LFPLUS_E_ARG, "lfplus_set_witness: bad arguments");
+    int rc = dev_unsharded(c, o, "lfplus_set_witness_dev");
+    if (!rc) rc = dev_array(c, o, f, n, "lfplus_set_witness_dev");
+    if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     ff_join(c);     // (an asynchronous from_f may still read the witness that is being replaced)
     c->have = false;
@@ -218,8 +247,13 @@ extern "C" int lfplus_set_witness(lfplus_ctx *c, const uint64_t *f, uint64_t n) 
     c->nf = 0;
     u32 flag = 0;
     HIPCHK(c, hipMemsetAsync(c->err_d, 0, 4, c->st));
-    HIPCHK(c, hipMemcpyAsync(c->f, f, (size_t)n * 16 * 8, hipMemcpyHostToDevice, c->st));
-    lfp::launch_check_canonical(c->f, (size_t)n * 16, c->err_d, 4u, c->st);
+    if (o == Origin::device) {
+        lfp::launch_copy_checked(f, c->f, (size_t)n * 16, c->err_d, 4u, c->st);
+        HIPCHK(c, hipGetLastError());
+    } else {
+        HIPCHK(c, hipMemcpyAsync(c->f, f, (size_t)n * 16 * 8, hipMemcpyHostToDevice, c->st));
+        lfp::launch_check_canonical(c->f, (size_t)n * 16, c->err_d, 4u, c->st);
+    }
     HIPCHK(c, hipMemcpyAsync(&flag, c->err_d, 4, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     if (flag & 4u) {
@@ -229,6 +263,27 @@ extern "C" int lfplus_set_witness(lfplus_ctx *c, const uint64_t *f, uint64_t n) 
     }
     c->nf = n;
     return LFPLUS_OK;
+}
+extern "C" int lfplus_set_witness(lfplus_ctx *c, const uint64_t *f, uint64_t n) { return set_witness(c, f, n, Origin::host); }
+extern "C" int lfplus_set_witness_dev(lfplus_ctx *c, const uint64_t *f, uint64_t n) {
+    if (!c) return LFPLUS_E_ARG;
+    LFP_GUARD(set_witness(c, f, n, Origin::device), oom(c, "lfplus_set_witness_dev: out of host memory"))
+}
+// lfplus_ctx_wait_stream: both streams of the context wait for what `hip_stream` (NULL: the default stream) holds now; the host does not wait
+static int ctx_wait_stream(lfplus_ctx *c, void *hip_stream) {
+    HIPCHK(c, hipSetDevice(c->device));
+    hipEvent_t ev;
+    HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, (hipStream_t)hip_stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->st, ev, 0);
+    if (e == hipSuccess && c->st2) e = hipStreamWaitEvent(c->st2, ev, 0);
+    (void)hipEventDestroy(ev);   // (released by the runtime once the waits have passed)
+    HIPCHK(c, e);
+    return LFPLUS_OK;
+}
+extern "C" int lfplus_ctx_wait_stream(lfplus_ctx *c, void *hip_stream) {
+    if (!c) return LFPLUS_E_ARG;
+    LFP_GUARD(ctx_wait_stream(c, hip_stream), oom(c, "lfplus_ctx_wait_stream: out of host memory"))
 }
 
 static int log2_exact(u64 b) { return (b && !(b & (b - 1))) ? __builtin_ctzll(b) : -1; }
@@ -462,19 +517,40 @@ extern "C" int lfplus_rg_read(lfplus_ctx *c, int8_t *Df, uint64_t *comMf, uint64
     HIPCHK(c, hipStreamSynchronize(c->st));
     return LFPLUS_OK;
 }
-extern "C" int lfplus_commit(lfplus_ctx *c, const uint64_t *v, uint64_t n, uint64_t *out) {
+// Device origin: the words are tested where they are (k_check_canonical) and phase 1 reads the caller's array in place -- no allocation, no copy; `out` is written
+// only once the flag has come back down.
+static int commit(lfplus_ctx *c, const uint64_t *v, uint64_t n, uint64_t *out, Origin o) {
     if (!c || !v || !out) return fail(c, LFPLUS_E_ARG, "lfplus_commit: null argument");
     if (!c->A || n != c->n) return fail(c, LFPLUS_E_ARG, "lfplus_commit: matrix not set / length mismatch");
-    if (!canonical(v, (size_t)n * 16)) return fail(c, LFPLUS_E_ARG, "lfplus_commit: non-canonical word");
+    const bool dev = o == Origin::device;
+    int rc = dev_unsharded(c, o, "lfplus_commit_dev");
+    if (!rc) rc = dev_array(c, o, v, n, "lfplus_commit_dev");
+    if (rc) return rc;
+    if (!dev && !canonical(v, (size_t)n * 16)) return fail(c, LFPLUS_E_ARG, "lfplus_commit: non-canonical word");
     HIPCHK(c, hipSetDevice(c->device));
     ff_join(c);
     Plan p = plan_for(c->nloc, c->kappa, 0);
-    int rc = ensure_part(c, (size_t)p.nblk * p.nout_f + p.nout_f);
+    rc = ensure_part(c, (size_t)p.nblk * p.nout_f + p.nout_f);
     if (rc) return rc;
+    u64 *res = c->part + (size_t)p.nblk * p.nout_f;
+    if (dev) {
+        u32 flag = 0;
+        u64 got[64 * 16];      // (kappa <= 64)
+        HIPCHK(c, hipMemsetAsync(c->err_d, 0, 4, c->st));
+        lfp::launch_check_canonical(v, (size_t)n * 16, c->err_d, 4u, c->st);
+        enqueue_phase1(c, v, 2, 0, p, c->part);
+        lfp::launch_reduce(c->part, p.nblk, (u32)p.nout_f, res, 0, c->kappa, 0, 2, 0, nullptr, c->st);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(got, res, p.nout_f * 8, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(c, hipMemcpyAsync(&flag, c->err_d, 4, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        if (flag & 4u) return fail(c, LFPLUS_E_ARG, "lfplus_commit_dev: non-canonical word");
+        memcpy(out, got, p.nout_f * 8);
+        return LFPLUS_OK;
+    }
     u64 *dv = nullptr;      // the rank's rows of v (all of them unsharded): partial commitment, summed over the ranks below
     HIPCHK(c, lfp_dev_malloc(&dv, (size_t)c->nloc * 16 * 8));
     (void)hipMemcpyAsync(dv, v + c->row0 * 16, (size_t)c->nloc * 16 * 8, hipMemcpyHostToDevice, c->st);
-    u64 *res = c->part + (size_t)p.nblk * p.nout_f;
     enqueue_phase1(c, dv, 2, 0, p, c->part);
     lfp::launch_reduce(c->part, p.nblk, (u32)p.nout_f, res, 0, c->kappa, 0, 2, 0, nullptr, c->st);
     (void)hipMemcpyAsync(out, res, p.nout_f * 8, hipMemcpyDeviceToHost, c->st);
@@ -484,12 +560,17 @@ extern "C" int lfplus_commit(lfplus_ctx *c, const uint64_t *v, uint64_t n, uint6
     HIPCHK(c, hipGetLastError());
     return lfp_xsum(c, out, p.nout_f);
 }
+extern "C" int lfplus_commit(lfplus_ctx *c, const uint64_t *v, uint64_t n, uint64_t *out) { return commit(c, v, n, out, Origin::host); }
+extern "C" int lfplus_commit_dev(lfplus_ctx *c, const uint64_t *v, uint64_t n, uint64_t *out) {
+    if (!c) return LFPLUS_E_ARG;
+    LFP_GUARD(commit(c, v, n, out, Origin::device), oom(c, "lfplus_commit_dev: out of host memory"))
+}
 // r 2^64 mod p (Montgomery form) on the host
 static u64 to_mont(u64 a) { return (u64)((((unsigned __int128)a) << 64) % lfp::P); }
 // dst0 / dst1 (optional): contexts that receive F0 / F1 as their resident witnesses (device-to-device; `c` itself is allowed: its witness is consumed first)
 static int decompose_impl(lfplus_ctx *c, uint64_t B, const uint64_t *r_a, const uint64_t *r_b, uint32_t nm, const uint32_t *const *rowptr,
                           const uint32_t *const *col, const uint64_t *const *val, uint64_t *F0, uint64_t *F1, uint64_t *C0, uint64_t *C1, uint64_t *v0,
-                          uint64_t *v1, lfplus_ctx *dst0, lfplus_ctx *dst1) {
+                          uint64_t *v1, lfplus_ctx *dst0, lfplus_ctx *dst1, Origin o) {
     if (!c || !r_a || !r_b || (nm && rowptr && (!col || !val))) return fail(c, LFPLUS_E_ARG, "lfplus_decompose: null argument");
     for (lfplus_ctx *d : {dst0, dst1})
         if (d && (d->device != c->device || d->n != c->n)) return fail(c, LFPLUS_E_ARG, "lfplus_decompose_resident: the receiving context is on another device or has another width");
@@ -513,6 +594,13 @@ static int decompose_impl(lfplus_ctx *c, uint64_t B, const uint64_t *r_a, const 
             if (col[j][k] >= n) return fail(c, LFPLUS_E_ARG, "lfplus_decompose: column index out of range");
         if (!canonical(val[j], (size_t)nnz * 16)) return fail(c, LFPLUS_E_ARG, "lfplus_decompose: non-canonical coefficient");
     }
+    // Device origin: F0 / F1 (where given) are the caller's arrays; launch_decompose2 writes them there and every later pass reads them there
+    const bool dev = o == Origin::device;
+    int rc = dev_unsharded(c, o, "lfplus_decompose_dev");
+    if (!rc && F0) rc = dev_array(c, o, F0, n, "lfplus_decompose_dev (F0)");
+    if (!rc && F1) rc = dev_array(c, o, F1, n, "lfplus_decompose_dev (F1)");
+    if (rc) return rc;
+    if (dev && overlap(F0, F1, n)) return fail(c, LFPLUS_E_ARG, "lfplus_decompose_dev: F0 and F1 overlap");
     HIPCHK(c, hipSetDevice(c->device));
     // Sharded: the witness is whole on every rank (after lfplus_mlin: all-gathered), F0 / F1 are cut whole (element-wise, cheap) because the M_j F_i rows
     // read arbitrary columns; the tables -- the rank's rows of F_i and of M_j F_i -- are fixed locally for the first log2(n / world) variables, gathered (one
@@ -520,12 +608,12 @@ static int decompose_impl(lfplus_ctx *c, uint64_t B, const uint64_t *r_a, const 
     const u32 E = 2 * (1 + nm), T = 2 * E;        // vectors (F0, M_j F0 .., F1, M_j F1 ..), tables = one per vector and point
     const size_t vw = (size_t)n * 16, nl = c->nloc, lw = nl * 16, r0w = c->row0 * 16;
     u64 *buf = nullptr;
-    // F0 | F1 | tables T*nloc | ping T*nloc/2 | rM nvars*32 | gathered tables T*world
-    const size_t words = 2 * vw + (size_t)T * lw + (size_t)T * lw / 2 + (size_t)nvars * 32 + 64 + (size_t)T * c->world * 16;
+    // F0 | F1 (each unless it is the caller's device array) | tables T*nloc | ping T*nloc/2 | rM nvars*32 | gathered tables T*world
+    u64 *const uF0 = dev ? F0 : nullptr, *const uF1 = dev ? F1 : nullptr;
+    const size_t words = (uF0 ? 0 : vw) + (uF1 ? 0 : vw) + (size_t)T * lw + (size_t)T * lw / 2 + (size_t)nvars * 32 + 64 + (size_t)T * c->world * 16;
     buf = (u64 *)c->pool.get(words * 8);
     if (!buf) return fail(c, LFPLUS_E_HIP, "hipMalloc (decompose tables)");
-    u64 *dF0 = buf, *dF1 = dF0 + vw, *tab = dF1 + vw, *ping = tab + (size_t)T * lw, *drM = ping + (size_t)T * lw / 2, *gath = drM + (size_t)nvars * 32 + 64;
-    int rc = LFPLUS_OK;
+    u64 *dF0 = uF0 ? uF0 : buf, *dF1 = uF1 ? uF1 : buf + (uF0 ? 0 : vw), *tab = buf + (uF0 ? 0 : vw) + (uF1 ? 0 : vw), *ping = tab + (size_t)T * lw, *drM = ping + (size_t)T * lw / 2, *gath = drM + (size_t)nvars * 32 + 64;
     std::vector<void *> tofree;
     auto cleanup = [&]() { for (void *q : tofree) c->pool.put(q); c->pool.put(buf); };
 #define HIPCHK2(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { c->err = std::string(#x) + ": " + hipGetErrorString(e_); cleanup(); return LFPLUS_E_HIP; } } while (0)
@@ -614,8 +702,8 @@ static int decompose_impl(lfplus_ctx *c, uint64_t B, const uint64_t *r_a, const 
         if (C0) HIPCHK2(hipMemcpyAsync(C0, res, p.nout_f * 8, hipMemcpyDeviceToHost, c->st));
         if (C1) HIPCHK2(hipMemcpyAsync(C1, res + p.nout_f, p.nout_f * 8, hipMemcpyDeviceToHost, c->st));
     }
-    if (F0) HIPCHK2(hipMemcpyAsync(F0, dF0, vw * 8, hipMemcpyDeviceToHost, c->st));
-    if (F1) HIPCHK2(hipMemcpyAsync(F1, dF1, vw * 8, hipMemcpyDeviceToHost, c->st));
+    if (F0 && !dev) HIPCHK2(hipMemcpyAsync(F0, dF0, vw * 8, hipMemcpyDeviceToHost, c->st));
+    if (F1 && !dev) HIPCHK2(hipMemcpyAsync(F1, dF1, vw * 8, hipMemcpyDeviceToHost, c->st));
     lfplus_ctx *publish[2] = {nullptr, nullptr};
     for (int s2 = 0; s2 < 2; s2++) {     // the parts as resident witnesses of the receiving contexts (all on c's stream: the source of F0 / F1 -- c->f -- was read above)
         lfplus_ctx *d = s2 ? dst1 : dst0;
@@ -641,21 +729,36 @@ static int decompose_impl(lfplus_ctx *c, uint64_t B, const uint64_t *r_a, const 
 extern "C" int lfplus_decompose(lfplus_ctx *c, uint64_t B, const uint64_t *r_a, const uint64_t *r_b, uint32_t nm, const uint32_t *const *rowptr,
                                 const uint32_t *const *col, const uint64_t *const *val, uint64_t *F0, uint64_t *F1, uint64_t *C0, uint64_t *C1, uint64_t *v0,
                                 uint64_t *v1) {
-    return decompose_impl(c, B, r_a, r_b, nm, rowptr, col, val, F0, F1, C0, C1, v0, v1, nullptr, nullptr);
+    return decompose_impl(c, B, r_a, r_b, nm, rowptr, col, val, F0, F1, C0, C1, v0, v1, nullptr, nullptr, Origin::host);
+}
+extern "C" int lfplus_decompose_dev(lfplus_ctx *c, uint64_t B, const uint64_t *r_a, const uint64_t *r_b, uint32_t nm, const uint32_t *const *rowptr,
+                                    const uint32_t *const *col, const uint64_t *const *val, uint64_t *F0, uint64_t *F1, uint64_t *C0, uint64_t *C1, uint64_t *v0,
+                                    uint64_t *v1) {
+    if (!c) return LFPLUS_E_ARG;
+    LFP_GUARD(decompose_impl(c, B, r_a, r_b, nm, rowptr, col, val, F0, F1, C0, C1, v0, v1, nullptr, nullptr, Origin::device),
+              oom(c, "lfplus_decompose_dev: out of host memory"))
 }
 extern "C" int lfplus_decompose_resident(lfplus_ctx *c, uint64_t B, const uint64_t *r_a, const uint64_t *r_b, uint32_t nm, const uint32_t *const *rowptr,
                                          const uint32_t *const *col, const uint64_t *const *val, lfplus_ctx *dst0, lfplus_ctx *dst1, uint64_t *C0, uint64_t *C1,
                                          uint64_t *v0, uint64_t *v1) {
     if (!dst0 || !dst1) return fail(c, LFPLUS_E_ARG, "lfplus_decompose_resident: null receiving context");
-    return decompose_impl(c, B, r_a, r_b, nm, rowptr, col, val, nullptr, nullptr, C0, C1, v0, v1, dst0, dst1);
+    return decompose_impl(c, B, r_a, r_b, nm, rowptr, col, val, nullptr, nullptr, C0, C1, v0, v1, dst0, dst1, Origin::host);
 }
-extern "C" int lfplus_get_witness(lfplus_ctx *c, uint64_t *f_out, uint64_t n) {
+static int get_witness(lfplus_ctx *c, uint64_t *f_out, uint64_t n, Origin o) {
     if (!c || !f_out) return fail(c, LFPLUS_E_ARG, "lfplus_get_witness: null argument");
     if (!c->f || c->nf != n) return fail(c, LFPLUS_E_ARG, "lfplus_get_witness: no resident witness of this length");
+    int rc = dev_unsharded(c, o, "lfplus_get_witness_dev");
+    if (!rc) rc = dev_array(c, o, f_out, n, "lfplus_get_witness_dev");
+    if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(f_out, c->f, (size_t)n * 16 * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(f_out, c->f, (size_t)n * 16 * 8, o == Origin::device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     return LFPLUS_OK;
+}
+extern "C" int lfplus_get_witness(lfplus_ctx *c, uint64_t *f_out, uint64_t n) { return get_witness(c, f_out, n, Origin::host); }
+extern "C" int lfplus_get_witness_dev(lfplus_ctx *c, uint64_t *f_out, uint64_t n) {
+    if (!c) return LFPLUS_E_ARG;
+    LFP_GUARD(get_witness(c, f_out, n, Origin::device), oom(c, "lfplus_get_witness_dev: out of host memory"))
 }
 // ---- ComR1CS::new on the device (r1cs.rs:48-60; kernel: lfp_ingest.hip) ----------------------------------------------------------------------------
 static void drop_witness(lfplus_ctx *c) {
@@ -665,7 +768,10 @@ static void drop_witness(lfplus_ctx *c) {
     c->nf = 0;
     c->have = false;
 }
-static int witness_from_z_impl(lfplus_ctx *c, const uint64_t *z, uint64_t m, uint64_t b, uint32_t k, uint64_t *cm_f, u64 **dz, u32 iters, double *ms_avg) {
+static int witness_from_z_impl(lfplus_ctx *c, const uint64_t *z, uint64_t m, uint64_t b, uint32_t k, uint64_t *cm_f, u64 **dz, u32 iters, double *ms_avg, Origin o,
+                               bool *untouched) {
+    const bool dev = o == Origin::device;
+    *untouched = dev;      // a _dev call refused by the checks below leaves the resident witness and the from_f results as they were (the host twin drops them)
     if (!z || !m) return fail(c, LFPLUS_E_ARG, "lfplus_witness_from_z: null / empty z");
     if (!c->A) return fail(c, LFPLUS_E_ARG, "lfplus_witness_from_z: matrix not set");
     if (c->sharded()) return fail(c, LFPLUS_E_ARG, "lfplus_witness_from_z: sharded contexts are not supported (upload f with lfplus_set_witness)");
@@ -673,6 +779,9 @@ static int witness_from_z_impl(lfplus_ctx *c, const uint64_t *z, uint64_t m, uin
     if (m > c->n || m * k != c->n) return fail(c, LFPLUS_E_ARG, "lfplus_witness_from_z: m * k differs from the matrix width");
     if (c->n > (1ull << 28)) return fail(c, LFPLUS_E_ARG, "lfplus_witness_from_z: more than 2^28 rows (the lazy 128-bit sums would no longer be exact)");
     const u64 n = c->n;
+    if (dev && lfp_dev_ptr_check(c, z, m, "lfplus_witness_from_z_dev")) return LFPLUS_E_ARG;
+    *untouched = false;
+    c->have = false;
     if (!(c->f && c->nf == n)) {
         c->own_free(c->f);
         c->f = nullptr; c->nf = 0;
@@ -685,16 +794,19 @@ static int witness_from_z_impl(lfplus_ctx *c, const uint64_t *z, uint64_t m, uin
     const size_t nout = (size_t)c->kappa * 16;
     int rc = ensure_part(c, (size_t)nblk * nout + nout);
     if (rc) return rc;
-    *dz = (u64 *)c->pool.get((size_t)m * 16 * 8);
-    if (!*dz) return fail(c, LFPLUS_E_HIP, "lfplus_witness_from_z: out of device memory");
+    if (!dev) {                                 // (device origin: the kernel reads the caller's z in place; its bit-4 test covers those words as it covers the upload's)
+        *dz = (u64 *)c->pool.get((size_t)m * 16 * 8);
+        if (!*dz) return fail(c, LFPLUS_E_HIP, "lfplus_witness_from_z: out of device memory");
+    }
+    const u64 *zsrc = dev ? z : *dz;
     u32 flag = 0;
     HIPCHK(c, hipMemsetAsync(c->err_d, 0, 4, c->st));
-    HIPCHK(c, hipMemcpyAsync(*dz, z, (size_t)m * 16 * 8, hipMemcpyHostToDevice, c->st));
+    if (!dev) HIPCHK(c, hipMemcpyAsync(*dz, z, (size_t)m * 16 * 8, hipMemcpyHostToDevice, c->st));
     u64 *res = c->part + (size_t)nblk * nout;
     auto enqueue = [&]() -> hipError_t {
         for (u32 i0 = 0; i0 < c->kappa;) {
             lfp::IngestArgs a;
-            a.z = *dz; a.A = c->A; a.f = c->f; a.m = m; a.n = n;
+            a.z = zsrc; a.A = c->A; a.f = c->f; a.m = m; a.n = n;
             a.kappa = c->kappa; a.i0 = i0; a.icnt = lfp::group_size(c->kappa - i0);
             a.k = k; a.b = b; a.sh = log2_exact(b); a.JZ = (u32)JZ;
             a.part = c->part; a.err = c->err_d; a.first = i0 == 0;
@@ -729,14 +841,14 @@ static int witness_from_z_impl(lfplus_ctx *c, const uint64_t *z, uint64_t m, uin
     c->nf = n;
     return LFPLUS_OK;
 }
-static int witness_from_z(lfplus_ctx *c, const uint64_t *z, uint64_t m, uint64_t b, uint32_t k, uint64_t *cm_f, u32 iters, double *ms_avg) {
+static int witness_from_z(lfplus_ctx *c, const uint64_t *z, uint64_t m, uint64_t b, uint32_t k, uint64_t *cm_f, u32 iters, double *ms_avg, Origin o = Origin::host) {
     if (!c) return LFPLUS_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     ff_join(c);      // (an asynchronous from_f may still read the witness that is being replaced)
-    c->have = false;
     u64 *dz = nullptr;
-    const int rc = witness_from_z_impl(c, z, m, b, k, cm_f, &dz, iters, ms_avg);
-    if (rc) {        // whatever failed: the context is left without a resident witness, never with a half-written one
+    bool untouched = false;
+    const int rc = witness_from_z_impl(c, z, m, b, k, cm_f, &dz, iters, ms_avg, o, &untouched);
+    if (rc && !untouched) {        // whatever failed: the context is left without a resident witness, never with a half-written one
         const std::string keep = c->err;
         drop_witness(c);
         c->err = keep;
@@ -746,6 +858,10 @@ static int witness_from_z(lfplus_ctx *c, const uint64_t *z, uint64_t m, uint64_t
 }
 extern "C" int lfplus_witness_from_z(lfplus_ctx *c, const uint64_t *z, uint64_t m, uint64_t b, uint32_t k, uint64_t *cm_f) {
     return witness_from_z(c, z, m, b, k, cm_f, 0, nullptr);
+}
+extern "C" int lfplus_witness_from_z_dev(lfplus_ctx *c, const uint64_t *z, uint64_t m, uint64_t b, uint32_t k, uint64_t *cm_f) {
+    if (!c) return LFPLUS_E_ARG;
+    LFP_GUARD(witness_from_z(c, z, m, b, k, cm_f, 0, nullptr, Origin::device), oom(c, "lfplus_witness_from_z_dev: out of host memory"))
 }
 // the same, then the pass alone `iters` times back to back, timed with HIP events on the library's stream (z resident): average ms
 extern "C" int lfplus_witness_from_z_timed(lfplus_ctx *c, const uint64_t *z, uint64_t m, uint64_t b, uint32_t k, uint32_t iters, double *ms_avg) {

@@ -134,6 +134,8 @@ void launch_linb_dots(const u64 *f, size_t n, const u64 *w, size_t ldw, u32 nw, 
 void launch_absmax(const u64 *x, size_t words, u64 *absmax, hipStream_t s);
 void launch_vec_add(u64 *acc, const u64 *x, size_t n, hipStream_t s);
 void launch_check_canonical(const u64 *x /* 16-byte aligned */, size_t n, u32 *flag, u32 bit, hipStream_t s);
+// dst = src (`words` words, a multiple of 16; both 16-byte aligned, not overlapping) and *flag |= bit if a word is not canonical: one pass (k_copy_checked)
+void launch_copy_checked(const u64 *src, u64 *dst, size_t words, u32 *flag, u32 bit, hipStream_t s);
 void launch_tensor_level(const u64 *cur, u64 len, u64 r, u64 *nxt, hipStream_t s);
 void launch_tensor_product(const u64 *a, u64 m, const u64 *b, u64 n, u64 *out, hipStream_t s);
 }  // namespace lfp

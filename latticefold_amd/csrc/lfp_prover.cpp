@@ -6,7 +6,9 @@
 //   * RgInstance::from_f needs no challenge: it is enqueued on every context's second stream as soon as the witness is resident and runs next to the
 //     linearizations' latency-bound rounds (lfplus_mlin collects the results);
 //   * host witnesses cross PCIe on a worker thread, one after the other, while this thread linearizes the instances that have arrived;
-//   * a prove that fails half way has advanced the Fiat-Shamir transcript: the object refuses to continue.
+//   * a prove that fails half way has advanced the Fiat-Shamir transcript: the object refuses to continue;
+//   * the _dev twins (device-origin z, f, F0 / F1) go through the contexts' own _dev entry points: the bodies below take the origin, and a device witness is
+//     copied and checked at once, on this thread (a device-to-device pass is tens of microseconds: there is nothing for a worker to hide).
 #include <condition_variable>
 #include <cstring>
 #include <mutex>
@@ -14,11 +16,13 @@
 #include <thread>
 #include <vector>
 #include "../../include/lfplus.h"
+#include "lfp_guard.h"
 
-// no C++ exception crosses the C boundary: an allocation that fails inside an entry point ends it with LFPLUS_E_HIP (the code for "a resource could not be had")
-#define LFP_GUARD(expr, on_throw) try { return (expr); } catch (...) { return (on_throw); }
+// THE pointer check of a device-origin array (lfp_capi.cpp; dev_array_check behind it): LFPLUS_OK, or LFPLUS_E_ARG with the context's message set
+int lfp_dev_ptr_check(lfplus_ctx *c, const void *p, uint64_t elems, const char *who);
 
 namespace {
+enum class Origin { host, device };      // where the O(n) arrays of a call live (include/lfplus.h "device-resident callers")
 typedef uint64_t u64;
 typedef uint32_t u32;
 constexpr u64 D = LFPLUS_D;
@@ -194,7 +198,13 @@ static int fresh_ok(lfplus_prover *pr, const void *ptrs, u32 count, const char *
     if ((size_t)pr->nacc + count > pr->ctxs.size()) return pfail(pr, LFPLUS_E_ARG, std::string(who) + ": more instances than contexts (ncomp)");
     return LFPLUS_OK;
 }
-static int prover_ingest_impl(lfplus_prover *pr, const uint64_t *const *z, uint32_t count, uint64_t m, uint32_t l_in, uint64_t *cm_f_out) {
+// every device-origin array of a call against THE pointer check, before any context is touched: a refusal is a shape error, the prover stays usable
+static int dev_arrays_ok(lfplus_prover *pr, Origin o, const uint64_t *const *ptrs, u32 count, u64 elems, const char *who) {
+    for (u32 i = 0; i < count && o == Origin::device; i++)
+        if (ptrs[i] && lfp_dev_ptr_check(pr->ctxs[0], ptrs[i], elems, who)) return pfail(pr, LFPLUS_E_ARG, lfplus_last_error(pr->ctxs[0]));
+    return LFPLUS_OK;
+}
+static int prover_ingest_impl(lfplus_prover *pr, const uint64_t *const *z, uint32_t count, uint64_t m, uint32_t l_in, uint64_t *cm_f_out, Origin o) {
     if (!pr) return LFPLUS_E_ARG;
     (void)l_in;
     int rc = fresh_ok(pr, z, count, "lfplus_prover_ingest");
@@ -202,9 +212,11 @@ static int prover_ingest_impl(lfplus_prover *pr, const uint64_t *const *z, uint3
     for (u32 i = 0; i < count; i++)
         if (!z[i]) return pfail(pr, LFPLUS_E_ARG, "lfplus_prover_ingest: null z");
     if (!m || m > pr->n || m * pr->p.k != pr->n) return pfail(pr, LFPLUS_E_ARG, "lfplus_prover_ingest: m * k differs from n");      // (a shape error: nothing is touched)
+    if ((rc = dev_arrays_ok(pr, o, z, count, m, "lfplus_prover_ingest_dev"))) return rc;
     for (u32 i = 0; i < count; i++) {
         lfplus_ctx *c = pr->ctxs[pr->nacc + i];
-        rc = lfplus_witness_from_z(c, z[i], m, pr->p.B, pr->p.k, cm_f_out ? cm_f_out + (size_t)i * pr->p.kappa * D : nullptr);
+        u64 *cm = cm_f_out ? cm_f_out + (size_t)i * pr->p.kappa * D : nullptr;
+        rc = o == Origin::device ? lfplus_witness_from_z_dev(c, z[i], m, pr->p.B, pr->p.k, cm) : lfplus_witness_from_z(c, z[i], m, pr->p.B, pr->p.k, cm);
         if (rc) return pbreak(pr, rc, ctx_err(c, "lfplus_prover_ingest"));      // (a context may be left without its witness)
     }
     pr->cm_f.clear();
@@ -212,18 +224,28 @@ static int prover_ingest_impl(lfplus_prover *pr, const uint64_t *const *z, uint3
     { std::lock_guard<std::mutex> g(pr->mu); pr->arrived = count; pr->up_rc = 0; }
     return LFPLUS_OK;
 }
-static int prover_set_instances_impl(lfplus_prover *pr, const uint64_t *const *f, const uint64_t *const *cm_f, uint32_t count) {
+static int prover_set_instances_impl(lfplus_prover *pr, const uint64_t *const *f, const uint64_t *const *cm_f, uint32_t count, Origin o) {
     if (!pr) return LFPLUS_E_ARG;
     int rc = fresh_ok(pr, f, count, "lfplus_prover_set_instances");
     if (rc) return rc;
     for (u32 i = 0; i < count; i++)
         if (!f[i]) return pfail(pr, LFPLUS_E_ARG, "lfplus_prover_set_instances: null f");
+    if ((rc = dev_arrays_ok(pr, o, f, count, pr->n, "lfplus_prover_set_instances_dev"))) return rc;
     pr->join();
     pr->cm_f.assign(count, std::vector<u64>());
     for (u32 i = 0; i < count && cm_f; i++)
         if (cm_f[i]) pr->cm_f[i].assign(cm_f[i], cm_f[i] + (size_t)pr->p.kappa * D);
     pr->nfresh = count;
     { std::lock_guard<std::mutex> g(pr->mu); pr->arrived = 0; pr->up_rc = 0; pr->up_err.clear(); }
+    if (o == Origin::device) {      // no worker: copied and checked here, f[i] is free again on return and the prove finds every instance arrived
+        for (u32 i = 0; i < count; i++) {
+            lfplus_ctx *c = pr->ctxs[pr->nacc + i];
+            if ((rc = lfplus_set_witness_dev(c, f[i], pr->n))) return pbreak(pr, rc, ctx_err(c, "lfplus_prover_set_instances_dev"));
+        }
+        std::lock_guard<std::mutex> g(pr->mu);
+        pr->arrived = count;
+        return LFPLUS_OK;
+    }
     // the uploads, one after the other (an upload is 2.4 ms per 2^20-row witness, a linearization 2.3 ms: only the first is exposed)
     std::vector<const u64 *> src(f, f + count);
     try {
@@ -297,15 +319,32 @@ static int prover_prove_impl(lfplus_prover *pr, uint64_t *proof, uint64_t proof_
     pr->last_L = L; pr->last_nfresh = nfresh;
     return LFPLUS_OK;
 }
-static int prover_accumulator_impl(lfplus_prover *pr, uint64_t *F0, uint64_t *F1) {
+static int prover_accumulator_impl(lfplus_prover *pr, uint64_t *F0, uint64_t *F1, Origin o) {
     if (!pr) return LFPLUS_E_ARG;
     if (pr->failed) return pdead(pr, "lfplus_prover_accumulator");
     if (pr->nacc != 2) return pfail(pr, LFPLUS_E_ARG, "lfplus_prover_accumulator: no accumulator (call it after a successful prove)");
+    if (o == Origin::device) {
+        const u64 *const both[2] = {F0, F1};
+        const int rc = dev_arrays_ok(pr, o, both, 2, pr->n, "lfplus_prover_accumulator_dev");
+        if (rc) return rc;
+        const uintptr_t a = (uintptr_t)F0, b = (uintptr_t)F1, bytes = (uintptr_t)pr->n * D * 8;
+        if (F0 && F1 && a < b + bytes && b < a + bytes) return pfail(pr, LFPLUS_E_ARG, "lfplus_prover_accumulator_dev: F0 and F1 overlap");
+    }
     for (int i = 0; i < 2; i++) {
         u64 *dst = i ? F1 : F0;
         if (!dst) continue;
-        const int rc = lfplus_get_witness(pr->ctxs[i], dst, pr->n);
+        const int rc = o == Origin::device ? lfplus_get_witness_dev(pr->ctxs[i], dst, pr->n) : lfplus_get_witness(pr->ctxs[i], dst, pr->n);
         if (rc) return pfail(pr, rc, ctx_err(pr->ctxs[i], "lfplus_prover_accumulator"));
+    }
+    return LFPLUS_OK;
+}
+// every context's streams wait for what `hip_stream` holds now (lfplus_ctx_wait_stream); a worker still uploading into them is joined first: one thread per context
+static int prover_wait_stream_impl(lfplus_prover *pr, void *hip_stream) {
+    if (pr->failed) return pdead(pr, "lfplus_prover_wait_stream");
+    pr->join();
+    for (lfplus_ctx *c : pr->ctxs) {
+        const int rc = lfplus_ctx_wait_stream(c, hip_stream);
+        if (rc) return pfail(pr, rc, ctx_err(c, "lfplus_prover_wait_stream"));
     }
     return LFPLUS_OK;
 }
@@ -349,11 +388,23 @@ extern "C" int lfplus_prover_create(int device, const lfplus_params *params, con
 }
 extern "C" int lfplus_prover_ingest(lfplus_prover *pr, const uint64_t *const *z, uint32_t count, uint64_t m, uint32_t l_in, uint64_t *cm_f_out) {
     if (!pr) return LFPLUS_E_ARG;
-    LFP_GUARD(prover_ingest_impl(pr, z, count, m, l_in, cm_f_out), pbreak_nothrow(pr, "lfplus_prover_ingest: out of host memory"))
+    LFP_GUARD(prover_ingest_impl(pr, z, count, m, l_in, cm_f_out, Origin::host), pbreak_nothrow(pr, "lfplus_prover_ingest: out of host memory"))
+}
+extern "C" int lfplus_prover_ingest_dev(lfplus_prover *pr, const uint64_t *const *z, uint32_t count, uint64_t m, uint32_t l_in, uint64_t *cm_f_out) {
+    if (!pr) return LFPLUS_E_ARG;
+    LFP_GUARD(prover_ingest_impl(pr, z, count, m, l_in, cm_f_out, Origin::device), pbreak_nothrow(pr, "lfplus_prover_ingest_dev: out of host memory"))
 }
 extern "C" int lfplus_prover_set_instances(lfplus_prover *pr, const uint64_t *const *f, const uint64_t *const *cm_f, uint32_t count) {
     if (!pr) return LFPLUS_E_ARG;
-    LFP_GUARD(prover_set_instances_impl(pr, f, cm_f, count), pbreak_nothrow(pr, "lfplus_prover_set_instances: out of host memory"))
+    LFP_GUARD(prover_set_instances_impl(pr, f, cm_f, count, Origin::host), pbreak_nothrow(pr, "lfplus_prover_set_instances: out of host memory"))
+}
+extern "C" int lfplus_prover_set_instances_dev(lfplus_prover *pr, const uint64_t *const *f, const uint64_t *const *cm_f, uint32_t count) {
+    if (!pr) return LFPLUS_E_ARG;
+    LFP_GUARD(prover_set_instances_impl(pr, f, cm_f, count, Origin::device), pbreak_nothrow(pr, "lfplus_prover_set_instances_dev: out of host memory"))
+}
+extern "C" int lfplus_prover_wait_stream(lfplus_prover *pr, void *hip_stream) {
+    if (!pr) return LFPLUS_E_ARG;
+    LFP_GUARD(prover_wait_stream_impl(pr, hip_stream), pfail(pr, LFPLUS_E_HIP, "lfplus_prover_wait_stream: out of host memory"))
 }
 extern "C" int lfplus_prover_prove(lfplus_prover *pr, uint64_t *proof, uint64_t proof_words) {
     if (!pr) return LFPLUS_E_ARG;
@@ -361,7 +412,11 @@ extern "C" int lfplus_prover_prove(lfplus_prover *pr, uint64_t *proof, uint64_t 
 }
 extern "C" int lfplus_prover_accumulator(lfplus_prover *pr, uint64_t *F0, uint64_t *F1) {
     if (!pr) return LFPLUS_E_ARG;
-    LFP_GUARD(prover_accumulator_impl(pr, F0, F1), pfail(pr, LFPLUS_E_HIP, "lfplus_prover_accumulator: out of host memory"))
+    LFP_GUARD(prover_accumulator_impl(pr, F0, F1, Origin::host), pfail(pr, LFPLUS_E_HIP, "lfplus_prover_accumulator: out of host memory"))
+}
+extern "C" int lfplus_prover_accumulator_dev(lfplus_prover *pr, uint64_t *F0, uint64_t *F1) {
+    if (!pr) return LFPLUS_E_ARG;
+    LFP_GUARD(prover_accumulator_impl(pr, F0, F1, Origin::device), pfail(pr, LFPLUS_E_HIP, "lfplus_prover_accumulator_dev: out of host memory"))
 }
 extern "C" int lfplus_prover_decide(lfplus_prover *pr, const uint64_t *proof, uint64_t proof_words, uint64_t bound, int *ok, unsigned *failed, uint64_t *absmax) {
     if (!pr) return LFPLUS_E_ARG;

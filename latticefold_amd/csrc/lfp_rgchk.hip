@@ -1037,4 +1037,26 @@ void launch_check_canonical(const u64 *x, size_t n, u32 *flag, u32 bit, hipStrea
     if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(k_check_canonical, dim3((unsigned)nb), dim3(256), 0, s, x, n, flag, bit);
 }
+// dst[i] = src[i] for `pairs` pairs of words, and *flag |= bit if any of them is not a canonical residue: a caller's DEVICE array becomes the resident copy and is
+// tested on the way (lfplus_set_witness_dev; a copy followed by k_check_canonical would read the words twice).  One 16-byte load and one 16-byte store per lane and
+// step, consecutive lanes on consecutive pairs (a wave moves 1 KB per access), the grid strides over the pairs with a 64-bit index; the bad words of a wave are
+// folded with a vote and reported by its first lane alone (one atomic per wave that saw one, none otherwise).  src and dst are 16-byte aligned and do not overlap.
+__global__ void __launch_bounds__(256) k_copy_checked(const ulonglong2 *__restrict__ src, ulonglong2 *__restrict__ dst, u64 pairs, u32 *flag, u32 bit) {
+    const u64 stride = (u64)gridDim.x * 256;
+    bool bad = false;
+#pragma unroll 4
+    for (u64 q = (u64)blockIdx.x * 256 + threadIdx.x; q < pairs; q += stride) {
+        const ulonglong2 v = src[q];
+        bad |= v.x >= P || v.y >= P;
+        dst[q] = v;
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, bit);      // (every lane of the wave is here again: the vote spans the 64 of them)
+}
+void launch_copy_checked(const u64 *src, u64 *dst, size_t words, u32 *flag, u32 bit, hipStream_t s) {
+    const u64 pairs = words / 2;      // (words is a multiple of 16: whole ring elements)
+    if (!pairs) return;
+    u64 nb = cdiv(pairs, 256 * 4);    // four steps per lane where the array is long enough, up to 8 blocks per CU
+    if (nb > 2048) nb = 2048;
+    hipLaunchKernelGGL(k_copy_checked, dim3((unsigned)nb), dim3(256), 0, s, (const ulonglong2 *)src, (ulonglong2 *)dst, pairs, flag, bit);
+}
 }  // namespace lfp

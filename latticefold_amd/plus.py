@@ -102,6 +102,13 @@ def _lib():
         L.lfplus_dist_unique_id.argtypes = [u8p]
         L.lfplus_dist_init.argtypes = [vp, C.c_int, C.c_int, u8p]
         L.lfplus_dist_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]
+        # the _dev twins (lfplus.h "device-resident callers"): the O(n) arrays are device addresses
+        L.lfplus_ctx_wait_stream.argtypes = [vp, vp]
+        L.lfplus_set_witness_dev.argtypes = [vp, vp, C.c_uint64]
+        L.lfplus_witness_from_z_dev.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, u64p]
+        L.lfplus_commit_dev.argtypes = [vp, vp, C.c_uint64, u64p]
+        L.lfplus_get_witness_dev.argtypes = [vp, vp, C.c_uint64]
+        L.lfplus_decompose_dev.argtypes = [vp, C.c_uint64, u64p, u64p, C.c_uint32, u32pp, u32pp, u64pp, vp, vp, u64p, u64p, u64p, u64p]
         _READY = True
     return L
 
@@ -109,6 +116,13 @@ def _lib():
 def _w(a):
     a = np.ascontiguousarray(a, dtype=np.uint64)
     return a, a.ctypes.data_as(u64p)
+
+
+def _dev(t, shape=None):
+    """device array (api.is_device_array: a torch tensor) -> its address for a _dev entry point: contiguous, 8-byte elements, (rows, 16) -- `shape` when given"""
+    if not t.is_contiguous() or t.element_size() != 8 or t.dim() != 2 or t.shape[1] != D or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise LfPlusError(E_ARG, f"device arrays must be contiguous, 8-byte elements, shape {tuple(shape) if shape is not None else '(rows, 16)'}")
+    return C.c_void_p(t.data_ptr())
 
 
 @dataclass
@@ -236,16 +250,37 @@ class PlusContext:
     def share_matrices(self, other):
         self._chk(_lib().lfplus_share_matrices(self.h, other.h))
 
+    def wait_stream(self, stream=None):
+        """lfplus_ctx_wait_stream: both streams of the context wait for what is enqueued so far on `stream` (a hipStream_t address; default: the current torch
+        stream); the host does not wait"""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream().cuda_stream
+        self._chk(_lib().lfplus_ctx_wait_stream(self.h, C.c_void_p(stream)))
+
+    def _dev_in(self, t, shape=None):
+        """a device input: its address, after ordering the context behind the stream it was produced on (the current torch stream)"""
+        p = _dev(t, shape)
+        self.wait_stream()
+        return p
+
     def set_witness(self, f):
+        """f: (n, 16) host array, or a device array (lfplus_set_witness_dev: copied and checked on the device, nothing crosses PCIe)"""
+        if api.is_device_array(f):
+            return self._chk(_lib().lfplus_set_witness_dev(self.h, self._dev_in(f), f.shape[0]))
         f, p = _w(f)
         assert f.ndim == 2 and f.shape[1] == D
         self._chk(_lib().lfplus_set_witness(self.h, p, f.shape[0]))
 
     def witness_from_z(self, z, b, k):
-        """ComR1CS::new on the device (lfplus_witness_from_z): f = z.gadget_decompose(b, k) becomes the resident witness, only z is uploaded -> cm_f = A f"""
+        """ComR1CS::new on the device (lfplus_witness_from_z): f = z.gadget_decompose(b, k) becomes the resident witness, only z is uploaded -> cm_f = A f.
+        A device array z is read in place (lfplus_witness_from_z_dev)"""
+        out = np.zeros((self.kappa, D), dtype=np.uint64)
+        if api.is_device_array(z):
+            self._chk(_lib().lfplus_witness_from_z_dev(self.h, self._dev_in(z), z.shape[0], int(b), int(k), out.ctypes.data_as(u64p)))
+            return out
         z, p = _w(z)
         assert z.ndim == 2 and z.shape[1] == D
-        out = np.zeros((self.kappa, D), dtype=np.uint64)
         self._chk(_lib().lfplus_witness_from_z(self.h, p, z.shape[0], int(b), int(k), out.ctypes.data_as(u64p)))
         return out
 
@@ -263,9 +298,12 @@ class PlusContext:
         return out
 
     def commit(self, v):
-        """Matrix::try_mul_vec"""
-        v, p = _w(v)
+        """Matrix::try_mul_vec; a device array v is read in place (lfplus_commit_dev)"""
         out = np.zeros((self.kappa, D), dtype=np.uint64)
+        if api.is_device_array(v):
+            self._chk(_lib().lfplus_commit_dev(self.h, self._dev_in(v), v.shape[0], out.ctypes.data_as(u64p)))
+            return out
+        v, p = _w(v)
         self._chk(_lib().lfplus_commit(self.h, p, v.shape[0], out.ctypes.data_as(u64p)))
         return out
 
@@ -282,8 +320,14 @@ class PlusContext:
         self._chk(_lib().lfplus_tensor_product(self.h, pa, a.size, pb, b.size, out.ctypes.data_as(u64p)))
         return out
 
-    def get_witness(self):
-        """the context's resident witness (n, 16), read back from the device"""
+    def get_witness(self, out=None):
+        """the context's resident witness (n, 16), read back from the device; out = a device array (n, 16): copied there instead (lfplus_get_witness_dev) and
+        returned"""
+        if out is not None:
+            if not api.is_device_array(out):
+                raise LfPlusError(E_ARG, "get_witness: out must be a device array")
+            self._chk(_lib().lfplus_get_witness_dev(self.h, self._dev_in(out, (self.n, D)), self.n))
+            return out
         out = np.zeros((self.n, D), dtype=np.uint64)
         self._chk(_lib().lfplus_get_witness(self.h, out.ctypes.data_as(u64p), self.n))
         return out
@@ -328,11 +372,14 @@ class PlusContext:
             self._chk(rc)
         return rc == 0, failed.value, am.value
 
-    def decompose(self, f, A, B, r, M=(), into=None, out_bufs=None):
+    def decompose(self, f, A, B, r, M=(), into=None, out_bufs=None, out=None):
         """Decomp{f, r, M}.decompose(&A, B) (decomp.rs:32-99).  r: (nvars, 2, 16) pairs of ring elements; M: CSR matrices (rowptr, col, val[nnz][16]).
         -> dict(F0, F1 (n,16); C0, C1 (kappa,16); v0, v1 (1+len(M), 2, 16)): ((LinB0, LinB1), DecompProof) of the reference, flat.
         into = (ctx0, ctx1): F0 / F1 stay on the device as the resident witnesses of those contexts (lfplus_decompose_resident) and are not returned;
-        out_bufs = (F0, F1): host arrays to receive them (already touched: a download into fresh pages is page-fault-bound, 10 ms instead of 2.4 per 2^20 rows)"""
+        out_bufs = (F0, F1): host arrays to receive them (already touched: a download into fresh pages is page-fault-bound, 10 ms instead of 2.4 per 2^20 rows);
+        out = (F0, F1): DEVICE arrays (n, 16), either may be None -- the halves are written there by the kernel that cuts them (lfplus_decompose_dev) and
+        returned under "F0" / "F1" (None for a half not asked for)"""
+        dev_out = out
         if A is not None:
             self.set_matrix(A)
         if f is not None:              # None: the resident witness (e.g. the folded g Mlin.mlin left there)
@@ -347,6 +394,15 @@ class PlusContext:
         if into is not None:
             self._chk(_lib().lfplus_decompose_resident(self.h, B, r_a.ctypes.data_as(u64p), r_b.ctypes.data_as(u64p), nm, rp, cp, vp_, into[0].h, into[1].h,
                                                        *[out[k].ctypes.data_as(u64p) for k in ("C0", "C1", "v0", "v1")]))
+            return out
+        if dev_out is not None:
+            F = tuple(dev_out)
+            if len(F) != 2 or any(x is not None and not api.is_device_array(x) for x in F):
+                raise LfPlusError(E_ARG, "decompose: out must be two device arrays (or None)")
+            ptrs = [None if x is None else self._dev_in(x, (n, D)) for x in F]
+            self._chk(_lib().lfplus_decompose_dev(self.h, B, r_a.ctypes.data_as(u64p), r_b.ctypes.data_as(u64p), nm, rp, cp, vp_, *ptrs,
+                                                  *[out[k].ctypes.data_as(u64p) for k in ("C0", "C1", "v0", "v1")]))
+            out["F0"], out["F1"] = F
             return out
         if out_bufs is not None and all(isinstance(b, np.ndarray) and b.shape == (n, D) and b.dtype == np.uint64 and b.flags.c_contiguous for b in out_bufs):
             out["F0"], out["F1"] = out_bufs
@@ -745,7 +801,8 @@ class ComR1CS:
     def new_resident(ctx, r1cs, z, l_in, b, k):
         """ComR1CS::new with f cut and committed on the device (PlusContext.witness_from_z): only z crosses PCIe, f stays in `ctx` and is not downloaded
         (fetch_f reads it back)"""
-        z = np.ascontiguousarray(z, dtype=np.uint64)
+        if not api.is_device_array(z):      # (a device z goes through as it is: lfplus_witness_from_z_dev reads it in place)
+            z = np.ascontiguousarray(z, dtype=np.uint64)
         return ComR1CS(tuple(r1cs), z, None, ctx.witness_from_z(z, b, k), l_in, ctx)
 
     def fetch_f(self):
@@ -1203,6 +1260,11 @@ def _nlib():
         L.lfplus_prover_accumulator.argtypes = [vp, u64p, u64p]
         L.lfplus_prover_decide.argtypes = [vp, u64p, C.c_uint64, C.c_uint64, ip, C.POINTER(C.c_uint), u64p]
         L.lfplus_verify.argtypes = [pp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, u64p, C.c_uint64, ip, ip]
+        vpp = C.POINTER(vp)              # host arrays of device addresses
+        L.lfplus_prover_wait_stream.argtypes = [vp, vp]
+        L.lfplus_prover_ingest_dev.argtypes = [vp, vpp, C.c_uint32, C.c_uint64, C.c_uint32, u64p]
+        L.lfplus_prover_set_instances_dev.argtypes = [vp, vpp, u64pp, C.c_uint32]
+        L.lfplus_prover_accumulator_dev.argtypes = [vp, vp, vp]
         _NATIVE_READY = True
     return L
 
@@ -1320,8 +1382,31 @@ class NativePlusProver:
             self.h = C.c_void_p()
         self._keep = None
 
+    def wait_stream(self, stream=None):
+        """lfplus_prover_wait_stream: the streams of every context of the prover wait for what is enqueued so far on `stream` (a hipStream_t address; default:
+        the current torch stream); the host does not wait for the device"""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream().cuda_stream
+        self._chk(_nlib().lfplus_prover_wait_stream(self.h, C.c_void_p(stream)))
+
+    def _dev_ptrs(self, ts, shape, who):
+        if not all(api.is_device_array(t) for t in ts):
+            raise LfPlusError(E_ARG, f"NativePlusProver.{who}: device and host arrays cannot be mixed")
+        ptrs = (C.c_void_p * len(ts))(*[_dev(t, shape) for t in ts])
+        self.wait_stream()
+        return ptrs
+
     def ingest(self, zs, r1cs=None, l_in=1):
-        """lfplus_prover_ingest: the fresh instances of the next prove from their short witnesses -> cm_f (count, kappa, 16)"""
+        """lfplus_prover_ingest: the fresh instances of the next prove from their short witnesses -> cm_f (count, kappa, 16).  Device arrays z are read in place
+        (lfplus_prover_ingest_dev)"""
+        zs = list(zs)
+        if zs and any(api.is_device_array(z) for z in zs):
+            ptrs = self._dev_ptrs(zs, tuple(zs[0].shape), "ingest")
+            out = np.zeros((len(zs), self.kappa, D), dtype=np.uint64)
+            self._chk(_nlib().lfplus_prover_ingest_dev(self.h, ptrs, len(zs), zs[0].shape[0], int(l_in), out.ctypes.data_as(u64p)))
+            self.nfresh = len(zs)
+            return out
         zs = [np.ascontiguousarray(z, dtype=np.uint64) for z in zs]
         if not zs or any(z.ndim != 2 or z.shape != zs[0].shape or z.shape[1] != D for z in zs):
             raise LfPlusError(E_ARG, "NativePlusProver.ingest: z must be equal (m, 16) arrays")
@@ -1332,13 +1417,23 @@ class NativePlusProver:
         return out
 
     def set_instances(self, fs, cm_fs=None):
-        """lfplus_prover_set_instances: the fresh instances of the next prove from host witnesses (n, 16); they go up on the library's worker thread"""
-        fs = [np.ascontiguousarray(f, dtype=np.uint64) for f in fs]
-        if not fs or any(f.shape != (self.n, D) for f in fs):
+        """lfplus_prover_set_instances: the fresh instances of the next prove from host witnesses (n, 16); they go up on the library's worker thread.  Device
+        arrays f (cm_f stays host) are copied and checked at once, without a worker, and are free again on return (lfplus_prover_set_instances_dev)"""
+        fs = list(fs)
+        dev = bool(fs) and any(api.is_device_array(f) for f in fs)
+        if not dev:
+            fs = [np.ascontiguousarray(f, dtype=np.uint64) for f in fs]
+        if not fs or any(tuple(f.shape) != (self.n, D) for f in fs):
             raise LfPlusError(E_ARG, "NativePlusProver.set_instances: f must be (n, 16) arrays")
         cms = None if cm_fs is None else [np.ascontiguousarray(c, dtype=np.uint64) for c in cm_fs]
         if cms is not None and (len(cms) != len(fs) or any(c.shape != (self.kappa, D) for c in cms)):
             raise LfPlusError(E_ARG, "NativePlusProver.set_instances: cm_f must be (kappa, 16) arrays, one per instance")
+        if dev:
+            fp = self._dev_ptrs(fs, (self.n, D), "set_instances")
+            cp = None if cms is None else (u64p * len(fs))(*[c.ctypes.data_as(u64p) for c in cms])
+            self._chk(_nlib().lfplus_prover_set_instances_dev(self.h, fp, cp, len(fs)))
+            self.nfresh = len(fs)
+            return
         fp = (u64p * len(fs))(*[f.ctypes.data_as(u64p) for f in fs])
         cp = None if cms is None else (u64p * len(fs))(*[c.ctypes.data_as(u64p) for c in cms])
         self._keep = fs          # borrowed by the worker until the prove returns
@@ -1360,8 +1455,17 @@ class NativePlusProver:
         self.nacc, self.nfresh, self.last = 2, 0, (L, nfresh)
         return out
 
-    def accumulator(self):
-        """(F0, F1) of the last prove, read back from the device"""
+    def accumulator(self, out=None):
+        """(F0, F1) of the last prove, read back from the device; out = (F0, F1) device arrays (n, 16), either may be None: copied there, device to device
+        (lfplus_prover_accumulator_dev), and returned"""
+        if out is not None:
+            F = tuple(out)
+            if len(F) != 2 or any(x is not None and not api.is_device_array(x) for x in F):
+                raise LfPlusError(E_ARG, "NativePlusProver.accumulator: out must be two device arrays (or None)")
+            ptrs = [None if x is None else _dev(x, (self.n, D)) for x in F]
+            self.wait_stream()
+            self._chk(_nlib().lfplus_prover_accumulator_dev(self.h, *ptrs))
+            return F
         F = [np.zeros((self.n, D), dtype=np.uint64) for _ in range(2)]
         self._chk(_nlib().lfplus_prover_accumulator(self.h, F[0].ctypes.data_as(u64p), F[1].ctypes.data_as(u64p)))
         return tuple(F)

@@ -74,7 +74,7 @@ def split_params(s):
             ctype, name = p, None
         if name is None:
             base = re.findall(r"[A-Za-z_][A-Za-z_0-9]*", ctype)[-1]
-            name = {"lf_ctx": "ctx", "lf_transcript": "t", "lf_witness": "w", "lf_params": "p", "lfplus_ctx": "ctx"}.get(base, f"a{i}")
+            name = {"lf_ctx": "ctx", "lf_transcript": "t", "lf_witness": "w", "lf_params": "p", "lfplus_ctx": "ctx", "lfplus_prover": "prover"}.get(base, f"a{i}")
         out.append((KEYWORDS.get(name, name), rust_type(ctype)))
     return out
 
@@ -108,7 +108,7 @@ def defines(path):
 def generate():
     L = ["// GENERATED by tools/gen_rust_bindings.py from include/lfhip.h and include/lfplus.h -- do not edit.",
          "// latticefold-hip-sys: raw binding of liblfhip.so (MI355X / gfx950).  Every pointer is a HOST pointer, except the array arguments of",
-         "// the lf_*_dev entry points (the caller's device memory: lfhip.h, \"device-resident callers\"); every `c_int` result is 0 or a",
+         "// the lf_*_dev / lfplus_*_dev entry points (the caller's device memory: \"device-resident callers\" in both headers); every `c_int` result is 0 or a",
          "// negative LF_ERR_* / LFPLUS_E_* code.  The comments of the headers are the documentation.",
          "#![allow(non_camel_case_types, non_upper_case_globals, non_snake_case)]",
          "use core::ffi::{c_char, c_int, c_uint, c_void};", ""]

@@ -10,7 +10,8 @@ torch tensor that is already resident.  One JSON line per shape: min and median 
 Shapes: commit_ntt at the reference's CommitNTT rows (Goldilocks kappa 20, BabyBear kappa 15, n = 2^20), Witness::from_w_ccs, lf_ccs_check and
 lf_witness_get_f at C4; the component calls (`--only components`, or one of their names): at C4 decompose / recompose of w_ccs (B, L), linf_check of f (N
 elements), build_eq at nv = s and spmv of matrix 0; at C2 (m = 2^16 rows) t = 3 tables for mle_eval_batch, sumcheck_lin_begin, lincomb and horner_combine, and
-the 5 + 2 K tau tables of sumcheck_fold_begin."""
+the 5 + 2 K tau tables of sumcheck_fold_begin; the LatticeFold+ twins (`--only lfplus`, or one of their names) at P20 (2^20 rows): lfplus_set_witness,
+lfplus_witness_from_z, lfplus_commit, lfplus_get_witness, and one chained prover step (ingest of the fresh short witnesses + prove) of NativePlusProver."""
 import argparse
 import ctypes as C
 import json
@@ -228,6 +229,88 @@ def component_shapes(reps, only):
     return out
 
 
+LFPLUS = ("lfplus_set_witness", "lfplus_witness_from_z", "lfplus_commit", "lfplus_get_witness", "lfplus_chain_step")
+
+
+def lfplus_shapes(reps, only):
+    """the LatticeFold+ twins at P20; each pair is checked for equal results before it is timed, host buffers exist and have been written before the first timed
+    call.  The chain step runs two NativePlusProvers side by side -- one ingests host z, the other device z -- and times ingest + prove of a chained step (step 0,
+    which pays the allocations, is outside)"""
+    from latticefold_amd import plus
+    wl = plus.make_plus_workload("P20")
+    n, k, B, kappa, D = wl.n, wl.k, wl.B, wl.kappa, plus.D
+    ring, out = "frog", []
+    host = lambda t: t.cpu().numpy().view(np.uint64)
+    u = lambda a: a.ctypes.data_as(plus.u64p)
+
+    def ok(rc):
+        assert rc == 0, rc
+
+    def pair(name, arr, host_call, dev_call, same):
+        torch.cuda.synchronize()
+        host_call()
+        dev_call()
+        assert same(), name
+        th, td = measure(host_call, dev_call, reps)
+        out.append(row(f"{name} P20", ring, arr.nbytes / 1e6, th, td))
+
+    z = wl.z(0)
+    if set(LFPLUS[:4]) & set(only):
+        ctx = plus.PlusContext(0)
+        try:
+            L = plus._lib()
+            ctx.generate_matrix(wl.ajtai_seed, kappa, n)
+            f = plus.gadget_decompose(z, B, k)
+            fd, zd = dev(f), dev(z)
+            got = {}
+
+            def keep(key, fn):
+                def call():
+                    got[key] = fn()
+                return call
+            if "lfplus_set_witness" in only:
+                pair("lfplus_set_witness", f, lambda: ctx.set_witness(f), lambda: ctx.set_witness(fd), lambda: True)
+            if "lfplus_witness_from_z" in only:
+                pair("lfplus_witness_from_z", z, keep("h", lambda: ctx.witness_from_z(z, B, k)), keep("d", lambda: ctx.witness_from_z(zd, B, k)),
+                     lambda: (got["h"] == got["d"]).all())
+            if "lfplus_commit" in only:
+                pair("lfplus_commit", f, keep("h", lambda: ctx.commit(f)), keep("d", lambda: ctx.commit(fd)), lambda: (got["h"] == got["d"]).all())
+            if "lfplus_get_witness" in only:
+                ctx.set_witness(fd)
+                ho, do = np.ones((n, D), dtype=np.uint64), torch.zeros((n, D), dtype=torch.int64, device="cuda")
+                pair("lfplus_get_witness", ho, lambda: ok(L.lfplus_get_witness(ctx.h, u(ho), n)), lambda: ctx.get_witness(out=do), lambda: (ho == host(do)).all())
+        finally:
+            ctx.close()
+            plus.scratch_trim(0)
+    if "lfplus_chain_step" in only:
+        r1cs, params, ncomp = wl.r1cs(), wl.params(), max(1, wl.L - 2)
+        provers = [plus.NativePlusProver.init(None, list(r1cs), ncomp, params, plus.PoseidonTranscript(), 0, seed=wl.ajtai_seed) for _ in range(2)]
+        try:
+            zs0 = [wl.z(i) for i in range(wl.L)]
+            zs = [wl.z(wl.L + i) for i in range(ncomp)]
+            zds = [dev(x) for x in zs]
+            torch.cuda.synchronize()
+            flats = []
+            for pr, first in zip(provers, (zs0, [dev(x) for x in zs0])):
+                pr.ingest(first, r1cs)
+                flats.append(pr.prove())
+            assert (flats[0] == flats[1]).all(), "step 0: the device-z prover differs from the host-z prover"
+
+            def step(pr, fresh):
+                def call():
+                    pr.ingest(fresh, r1cs)
+                    pr.prove()
+                return call
+            th, td = measure(step(provers[0], zs), step(provers[1], zds), reps)
+            assert provers[0].transcript.get_challenge() == provers[1].transcript.get_challenge(), "the two chains end in different states"
+            out.append(row(f"NativePlusProver chained step ({ncomp} fresh z) P20", ring, sum(x.nbytes for x in zs) / 1e6, th, td))
+        finally:
+            for pr in provers:
+                pr.close()
+            plus.scratch_trim(0)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
@@ -238,6 +321,8 @@ def main():
     assert a.reps >= 9
     if "components" in a.only:
         a.only = [x for x in a.only if x != "components"] + list(COMPONENTS)
+    if "lfplus" in a.only:
+        a.only = [x for x in a.only if x != "lfplus"] + list(LFPLUS)
     rows = []
     if "commit_gold" in a.only:
         rows.append(commit_ntt("goldilocks", 20, a.reps))
@@ -251,6 +336,10 @@ def main():
             print(json.dumps(r), flush=True)
     if set(COMPONENTS) & set(a.only):
         for r in component_shapes(a.reps, a.only):
+            rows.append(r)
+            print(json.dumps(r), flush=True)
+    if set(LFPLUS) & set(a.only):
+        for r in lfplus_shapes(a.reps, a.only):
             rows.append(r)
             print(json.dumps(r), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
