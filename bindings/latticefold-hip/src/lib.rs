@@ -348,6 +348,22 @@ impl HipContext {
         // SAFETY: the caller vouches for the device ranges (see the impl); host slices were checked above
         chk(unsafe { sys::lf_horner_combine_dev(self.raw, tables, groups, per_group, len, challenges.as_ptr(), out) }, "lf_horner_combine_dev")
     }
+    /// `lf_ring_mul_device`: out[x] = sum_i a_i[x] * b_i[x]; `a`, `b`: n_terms x count elements, `out`: count elements, all in `form` (`LF_FORM_NTT` /
+    /// `LF_FORM_COEFF`).  With one term `out` may be `a` or `b` itself; any other overlap of `out` with an input is refused
+    pub unsafe fn ring_mul_device(&self, a: *const u64, b: *const u64, n_terms: usize, count: usize, form: i32, out: *mut u64) -> Result<(), HipError> {
+        // SAFETY: the caller vouches for the device ranges (see the impl); host slices were checked above
+        chk(unsafe { sys::lf_ring_mul_device(self.raw, a, b, n_terms, count, form, out) }, "lf_ring_mul_device")
+    }
+    /// `lf_ring_mul` on canonical words in host memory: `a`, `b`: n_terms x count elements, returns count elements in the same `form`
+    pub fn ring_mul(&self, a: &[u64], b: &[u64], n_terms: usize, count: usize, form: i32) -> Result<Vec<u64>, HipError> {
+        let re = self.word_counts().0;
+        assert_eq!(a.len(), n_terms * count * re);
+        assert_eq!(b.len(), n_terms * count * re);
+        let mut out = vec![0u64; count * re];
+        // SAFETY: the three slices hold what the counts say (checked above)
+        chk(unsafe { sys::lf_ring_mul(self.raw, a.as_ptr(), b.as_ptr(), n_terms, count, form, out.as_mut_ptr()) }, "lf_ring_mul")?;
+        Ok(out)
+    }
 }
 
 impl Drop for HipContext {

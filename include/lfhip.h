@@ -35,7 +35,8 @@ extern "C" {
 /* ABI version: bumped whenever an existing entry point changes meaning, and with the _dev family (6).  lf_abi_version() returns the constant the
  * library was built with; a binding compares it with the LFHIP_ABI_VERSION it was generated from.
  *   6  the _dev entry points and lf_ctx_wait_stream ("device-resident callers"): additions only, no existing entry point changes; numbered so that a
- *      binding can tell a library that has them from one that does not.
+ *      binding can tell a library that has them from one that does not.  The later twins and lf_ring_mul / lf_ring_mul_device are additions of the same kind
+ *      and keep the number: a binding asks for a symbol it needs.
  *   5  lf_last_fold_paths: *sv_round_mask is the GEMM-round mask alone on both rings (bits 8..15 used to carry the split-round count of the
  *      linearization on Goldilocks, and BabyBear contexts returned 0): the count moved to lf_last_lin_split_rounds, the table rounds' mask to
  *      lf_last_fold_split_rounds.  lf_debug_i8_prof is declared (it was exported without a prototype).
@@ -113,6 +114,15 @@ int lf_selftest_field(lf_ctx *, uint64_t seed, uint32_t n, uint64_t *mismatches)
 /* ---- a1/a2: CRT::elementwise_crt / ICRT::elementwise_icrt (arith.rs:232,238,300,327) -------- */
 int lf_ntt_fwd(lf_ctx *, const uint64_t *in, uint64_t *out, size_t count); /* in/out may alias */
 int lf_ntt_inv(lf_ctx *, const uint64_t *in, uint64_t *out, size_t count);
+/* The ring as a ring: sums of products of arrays of ring elements, what the transforms exist for.  Works on a bare context, on both rings; a sharded
+ * context computes the same (the product is local).  NULL pointers, n_terms == 0 and any other `form` are LF_ERR_INVALID.  `out` may be `a` or `b` itself
+ * when n_terms == 1. */
+#define LF_FORM_NTT   0   /* eight slots of F_{p^tau}, in the context's external basis if one is set */
+#define LF_FORM_COEFF 1   /* coefficients of Z_p[X]/Phi (X^24-X^12+1 / X^72-X^36+1); no basis touches them */
+/* out[x] = sum_{i<n_terms} a_i[x] * b_i[x] in the context's ring.  a, b: n_terms x count ring elements
+ * (table i at a + i*count*RE); out: count ring elements, same form as the inputs.  LF_FORM_COEFF is word for word
+ * lf_ntt_inv(lf_ring_mul(lf_ntt_fwd a, lf_ntt_fwd b, LF_FORM_NTT)), in one kernel: one inverse transform per output element. */
+int lf_ring_mul(lf_ctx *, const uint64_t *a, const uint64_t *b, size_t n_terms, size_t count, int form, uint64_t *out);
 
 /* ---- a3: balanced decomposition (stark_rings::balanced_decomposition) ------------------------
  * layout 0 = gadget_decompose (element i -> out[i*digits + j], arith.rs:235);
@@ -364,6 +374,10 @@ int lf_lcccs_check(lf_ctx *, const uint64_t *lcccs, const lf_witness *wit, uint6
 int lf_ctx_wait_stream(lf_ctx *, void *hip_stream);
 int lf_ntt_fwd_dev(lf_ctx *, const uint64_t *in, uint64_t *out, size_t count);
 int lf_ntt_inv_dev(lf_ctx *, const uint64_t *in, uint64_t *out, size_t count);
+/* lf_ring_mul on device memory, under every rule of the _dev calls above (pointer checks, canonical words, ordering, external basis).  Spelled _device: the
+ * _dev names are the 23 twins of ABI 6, a set the ABI tests count.  a, b (n_terms x count) and out (count) in device memory.  With n_terms == 1, out == a or out == b is the in-place form of lf_ntt_fwd_dev; any other overlap
+ * of `out` with an input range is LF_ERR_INVALID, nothing launched.  a and b may overlap each other (a square) */
+int lf_ring_mul_device(lf_ctx *, const uint64_t *a, const uint64_t *b, size_t n_terms, size_t count, int form, uint64_t *out /* dev */);
 int lf_ajtai_commit_dev(lf_ctx *, const uint64_t *f, size_t n, size_t batch, uint64_t *out /* host */);
 int lf_ajtai_commit_coeff_dev(lf_ctx *, const uint64_t *f_coeff, size_t n, size_t batch, uint64_t *out /* host */);
 int lf_ajtai_decompose_and_commit_coeff_dev(lf_ctx *, const uint64_t *f_coeff, size_t count, uint64_t base, unsigned digits,

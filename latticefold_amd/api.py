@@ -21,6 +21,7 @@ P = 2**64 - 2**32 + 1
 RING_IDS = {"goldilocks": 0, "babybear": 1}   # LF_RING_* of include/lfhip.h
 RING_WORDS = {"goldilocks": 24, "babybear": 72}
 RING_TAU = {"goldilocks": 3, "babybear": 9}
+FORMS = {"ntt": 0, "coeff": 1}                # LF_FORM_* of include/lfhip.h
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "liblfhip.so")
 
@@ -104,6 +105,7 @@ def _lib():
         L.lf_selftest_field.argtypes = [vp, C.c_uint64, C.c_uint32, u64p]
         L.lf_ntt_fwd.argtypes = [vp, u64p, u64p, C.c_size_t]
         L.lf_ntt_inv.argtypes = [vp, u64p, u64p, C.c_size_t]
+        L.lf_ring_mul.argtypes = [vp, u64p, u64p, C.c_size_t, C.c_size_t, C.c_int, u64p]
         L.lf_decompose.argtypes = [vp, u64p, C.c_size_t, C.c_uint64, C.c_uint, C.c_int, u64p]
         L.lf_recompose.argtypes = [vp, u64p, C.c_size_t, C.c_uint64, C.c_uint, u64p]
         L.lf_linf_check.argtypes = [vp, u64p, C.c_size_t, C.c_uint64, C.c_int, C.POINTER(C.c_int), u64p]
@@ -180,6 +182,7 @@ def _lib():
         L.lf_ctx_wait_stream.argtypes = [vp, vp]
         L.lf_ntt_fwd_dev.argtypes = [vp, vp, vp, C.c_size_t]
         L.lf_ntt_inv_dev.argtypes = [vp, vp, vp, C.c_size_t]
+        L.lf_ring_mul_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp]
         L.lf_ajtai_commit_dev.argtypes = [vp, vp, C.c_size_t, C.c_size_t, u64p]
         L.lf_ajtai_commit_coeff_dev.argtypes = [vp, vp, C.c_size_t, C.c_size_t, u64p]
         L.lf_ajtai_decompose_and_commit_coeff_dev.argtypes = [vp, vp, C.c_size_t, C.c_uint64, C.c_uint, C.c_size_t, u64p]
@@ -419,6 +422,23 @@ class Context:
         return o
 
     ntt_fwd, ntt_inv = crt, icrt
+
+    def ring_mul(self, a, b, form="ntt", out=None):
+        """lf_ring_mul: out[x] = sum_i a_i[x] * b_i[x] in the context's ring.  a, b: (count, RE) or (n_terms, count, RE), both in `form` ("ntt": slot-wise
+        products, in the external basis if one is set; "coeff": products mod the cyclotomic polynomial, transforms fused); the result has that form too.
+        numpy in, numpy out; device arrays in, a device array out (`out`: where to; with one term it may be `a` or `b` itself)"""
+        fid = FORMS[form]
+        if is_device_array(a) != is_device_array(b) or tuple(a.shape) != tuple(b.shape) or len(a.shape) not in (2, 3) or a.shape[-1] != self.RE:
+            raise ValueError(f"a and b: two numpy arrays or two device arrays of one shape, (count, {self.RE}) or (n_terms, count, {self.RE})")
+        nt, cnt = (1, a.shape[0]) if len(a.shape) == 2 else (a.shape[0], a.shape[1])
+        if is_device_array(a):
+            o = _dev_out(a, (cnt, self.RE), out)
+            _chk(_lib().lf_ring_mul_device(self.h, _dev(self, a), _dev(self, b), nt, cnt, fid, _dev(self, o)), "lf_ring_mul_device")
+            return o
+        (x, px), (y, py) = _a64(a), _a64(b)
+        o = np.empty((cnt, self.RE), dtype=np.uint64)
+        _chk(_lib().lf_ring_mul(self.h, px, py, nt, cnt, fid, o.ctypes.data_as(u64p)), "lf_ring_mul")
+        return o
 
     def decompose(self, coeff, base, digits, layout, out=None):
         """numpy in, numpy out; a device array in, a device array out (`out`: where to; it may not overlap the input)"""

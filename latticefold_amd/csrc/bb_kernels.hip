@@ -92,21 +92,7 @@ void launch_selftest(const u64 *in, u64 *out, u32 n, fe nu, hipStream_t s) {
 // U^8 - U^4 + 1 = (U^4 - w^4)(U^4 - w^20); the per-slot monomial twist X^r -> tw[r] Y^pos[r] maps F_p[X]/(X^9 - zeta_k)
 // onto F_p[Y]/(Y^9 - nu).  (stark-rings CRT; call sites arith.rs:238,327.)
 // (the butterflies themselves: lfk::crt8)
-// coefficients a[72] (Montgomery) -> the 72 NTT words of element j of plane table `out`
-__device__ __forceinline__ void crt_store(const fe a[RE], fe *out, size_t ld, size_t j, const DevBb &t) {
-#pragma unroll
-    for (int r = 0; r < TAU; r++) {
-        fe x[8], A[8];
-#pragma unroll
-        for (int v = 0; v < 8; v++) x[v] = a[r + TAU * v];
-        lfk::crt8<BbF>(x, A, t);
-#pragma unroll
-        for (int p = 0; p < 8; p++) {
-            int plane = TAU * t.slot_of_pos[p] + t.pos[r][p];
-            out[(size_t)plane * ld + j] = r == 0 ? A[p] : fmul(t.tw[r][p], A[p]);
-        }
-    }
-}
+// (crt_store, the monomial twists behind the butterflies: bb_kernels_dev.cuh, shared with bb_ring_mul.hip)
 void launch_crt_fwd(const DevBb &t, const fe *coef, fe *ntt, size_t n, hipStream_t s) { lfk::launch_crt_fwd<BbF>(t, coef, ntt, n, s); }
 // ICRT as the dense 72x72 F_p matrix (rare: ingest / export only)
 __global__ void __launch_bounds__(256) k_icrt_dense(const fe *mat, const fe *ntt, fe *coef, size_t n) {
@@ -118,17 +104,7 @@ __global__ void __launch_bounds__(256) k_icrt_dense(const fe *mat, const fe *ntt
     fe x[RE];
 #pragma unroll
     for (int c = 0; c < RE; c++) x[c] = ntt[(size_t)c * n + j];
-    for (int i = 0; i < RE; i++) {
-        i64 tot = 0;
-#pragma unroll
-        for (int g = 0; g < 8; g++) {   // 9 products per exact 64-bit group
-            i64 acc = 0;
-#pragma unroll
-            for (int c = 0; c < 9; c++) acc += (i64)M[i * RE + 9 * g + c] * (i64)x[9 * g + c];
-            tot += mred(acc);
-        }
-        coef[(size_t)i * n + j] = fred(tot);
-    }
+    icrt_dense_elem(M, x, coef, n, j);
 }
 void launch_icrt_dense(const fe *mat, const fe *ntt, fe *coef, size_t n, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_icrt_dense, dim3(cdiv(n, 256)), dim3(256), 0, s, mat, ntt, coef, n);

@@ -91,6 +91,39 @@ __device__ __forceinline__ fe hl_finish(const HL &a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// the per-element halves of the two transforms, shared by k_crt_fwd / k_icrt_dense (bb_kernels.hip) and the fused product of bb_ring_mul.hip
+// coefficients a[72] (Montgomery) -> the 72 NTT words of element j of plane table `out`
+__device__ __forceinline__ void crt_store(const fe a[RE], fe *out, size_t ld, size_t j, const DevBb &t) {
+#pragma unroll
+    for (int r = 0; r < TAU; r++) {
+        fe x[8], A[8];
+#pragma unroll
+        for (int v = 0; v < 8; v++) x[v] = a[r + TAU * v];
+        lfk::crt8<BbF>(x, A, t);
+#pragma unroll
+        for (int p = 0; p < 8; p++) {
+            int plane = TAU * t.slot_of_pos[p] + t.pos[r][p];
+            out[(size_t)plane * ld + j] = r == 0 ? A[p] : fmul(t.tw[r][p], A[p]);
+        }
+    }
+}
+// the dense inverse map of one element: x its 72 NTT words (registers), M the 72 x 72 matrix (LDS in k_icrt_dense, the kernel argument itself -- scalar loads --
+// in the fused product) -> the 72 coefficients of element j of plane table `coef`
+__device__ __forceinline__ void icrt_dense_elem(const fe *M, const fe (&x)[RE], fe *coef, size_t ld, size_t j) {
+    for (int i = 0; i < RE; i++) {
+        i64 tot = 0;
+#pragma unroll
+        for (int g = 0; g < 8; g++) {   // 9 products per exact 64-bit group
+            i64 acc = 0;
+#pragma unroll
+            for (int c = 0; c < 9; c++) acc += (i64)M[i * RE + 9 * g + c] * (i64)x[9 * g + c];
+            tot += mred(acc);
+        }
+        coef[(size_t)i * ld + j] = fred(tot);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // reductions: every thread holds NV signed 64-bit partial sums (of centred words)
 __device__ __forceinline__ i64 wave_sum(i64 v) {
 #pragma unroll

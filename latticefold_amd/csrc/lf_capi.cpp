@@ -495,6 +495,18 @@ int lf_ntt_inv_dev(lf_ctx *c, const uint64_t *in, uint64_t *out, size_t count) {
     XbArrays xa(c);
     return c->bb ? ring_ops<BbRing>::ntt_inv(c->bb->p, in, out, count, Origin::device) : ring_ops<GoldRing>::ntt_inv(c, in, out, count, Origin::device);
 }
+// the ring as a ring: sum of n_terms products of arrays, NTT form (slot-wise) or coefficient form (transforms fused); one body for both spellings and both rings
+static int ring_mul_api(lf_ctx *c, const uint64_t *a, const uint64_t *b, size_t n_terms, size_t count, int form, uint64_t *out, Origin org) {
+    if (!c || !a || !b || !out || !n_terms || (form != LF_FORM_NTT && form != LF_FORM_COEFF)) return LF_ERR_INVALID;
+    XbArrays xa(c);
+    return c->bb ? ring_ops<BbRing>::ring_mul(c->bb->p, a, b, n_terms, count, form, out, org) : ring_ops<GoldRing>::ring_mul(c, a, b, n_terms, count, form, out, org);
+}
+int lf_ring_mul(lf_ctx *c, const uint64_t *a, const uint64_t *b, size_t n_terms, size_t count, int form, uint64_t *out) {
+    return ring_mul_api(c, a, b, n_terms, count, form, out, Origin::host);
+}
+int lf_ring_mul_device(lf_ctx *c, const uint64_t *a, const uint64_t *b, size_t n_terms, size_t count, int form, uint64_t *out) {
+    return ring_mul_api(c, a, b, n_terms, count, form, out, Origin::device);
+}
 // Order the context's lanes behind the work enqueued so far on a stream of the caller's: an event recorded there, waited for by every lane.  The host does not
 // wait and the caller's stream is not touched otherwise
 int lf_ctx_wait_stream(lf_ctx *c, void *hip_stream) {

@@ -54,6 +54,10 @@ void launch_selftest_field(const u64 *in, u32 n, u32 nc, u64 nu_gen, u64 *out, u
 // ---- CRT / ICRT (a1, a2) ---------------------------------------------------------------------------------------
 void launch_crt_fwd(const DevCrt &t, const u64 *coef, u64 *ntt, size_t n, hipStream_t s);
 void launch_icrt_dense(const u64 *icrt_mat /*24*24 dev*/, const u64 *ntt, u64 *coef, size_t n, hipStream_t s);
+// out[x] = sum_{i < n_terms} a_i[x] * b_i[x] (lf_ring_mul.hip).  NTT form, slot-wise: a, b AoS [n_terms][n][24] canonical words (flag, Ti as for
+// launch_aos_to_soa), out the plane table [24][n].  Coefficient form, transforms and product fused: plane tables [24][n] in (table i at a + i * 24 * n) and out
+void launch_ring_mul_ntt(const DevCrt &t, const u64 *a, const u64 *b, size_t n_terms, size_t n, u64 *out, hipStream_t s, u32 *flag = nullptr, const XbMat3 *Ti = nullptr);
+void launch_ring_mul_coeff(const DevCrt &t, const u64 *icrt_mat /*24*24 dev*/, const u64 *a, const u64 *b, size_t n_terms, size_t n, u64 *out, hipStream_t s);
 
 // ---- digit-plane commitments on the int8 matrix cores: lf_ajtai_i8.h
 

@@ -132,26 +132,7 @@ __device__ __forceinline__ void crt_store_ternary(const int dg[24], u64 *out, si
         out[(size_t)(s3 + t.pos2[p]) * ld + j] = fq_mul(t.tw2[p], A2[p]);
     }
 }
-// coefficients a[24] (canonical) -> stores the 24 NTT words of element j into plane table `out` (ld = n)
-__device__ __forceinline__ void crt_store(const u64 a[24], u64 *out, size_t ld, size_t j, const DevCrt &t) {
-    u64 x[8], A0[8], A1[8], A2[8];
-#pragma unroll
-    for (int v = 0; v < 8; v++) x[v] = a[3 * v];
-    lfk::crt8<GoldF>(x, A0, t);
-#pragma unroll
-    for (int v = 0; v < 8; v++) x[v] = a[3 * v + 1];
-    lfk::crt8<GoldF>(x, A1, t);
-#pragma unroll
-    for (int v = 0; v < 8; v++) x[v] = a[3 * v + 2];
-    lfk::crt8<GoldF>(x, A2, t);
-#pragma unroll
-    for (int p = 0; p < 8; p++) {
-        int s3 = 3 * t.slot_of_pos[p];
-        out[(size_t)s3 * ld + j] = A0[p];
-        out[(size_t)(s3 + t.pos1[p]) * ld + j] = fq_mul(t.tw1[p], A1[p]);
-        out[(size_t)(s3 + t.pos2[p]) * ld + j] = fq_mul(t.tw2[p], A2[p]);
-    }
-}
+// (crt_store, the monomial twists behind the butterflies: lf_kernels_dev.cuh, shared with lf_ring_mul.hip)
 void launch_crt_fwd(const DevCrt &t, const u64 *coef, u64 *ntt, size_t n, hipStream_t s) { lfk::launch_crt_fwd<GoldF>(t, coef, ntt, n, s); }
 // ICRT as the dense 24x24 F_p matrix (rare: ingest / export only)
 __global__ void __launch_bounds__(256) k_icrt_dense(const u64 *mat, const u64 *ntt, u64 *coef, size_t n) {
@@ -163,13 +144,7 @@ __global__ void __launch_bounds__(256) k_icrt_dense(const u64 *mat, const u64 *n
     u64 x[24];
 #pragma unroll
     for (int c = 0; c < 24; c++) x[c] = ntt[(size_t)c * n + j];
-    for (int i = 0; i < 24; i++) {
-        Acc a;
-        acc_set(a, M[i * 24], x[0]);
-#pragma unroll
-        for (int c = 1; c < 24; c++) acc_mad(a, M[i * 24 + c], x[c]);
-        coef[(size_t)i * n + j] = acc_reduce(a);
-    }
+    icrt_dense_elem(M, x, coef, n, j);
 }
 void launch_icrt_dense(const u64 *mat, const u64 *ntt, u64 *coef, size_t n, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_icrt_dense, dim3(cdiv(n, 256)), dim3(256), 0, s, mat, ntt, coef, n);

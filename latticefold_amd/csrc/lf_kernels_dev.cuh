@@ -102,6 +102,40 @@ __device__ __forceinline__ void st3(u64 *tab, size_t ld, u32 slot, size_t i, Fq3
     tab[(size_t)(3 * slot) * ld + i] = v.c[0]; tab[(size_t)(3 * slot + 1) * ld + i] = v.c[1]; tab[(size_t)(3 * slot + 2) * ld + i] = v.c[2];
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// the per-element halves of the two transforms, shared by k_crt_fwd / k_icrt_dense (lf_kernels.hip) and the fused product of lf_ring_mul.hip
+// coefficients a[24] (canonical) -> stores the 24 NTT words of element j into plane table `out` (ld = n)
+__device__ __forceinline__ void crt_store(const u64 a[24], u64 *out, size_t ld, size_t j, const DevCrt &t) {
+    u64 x[8], A0[8], A1[8], A2[8];
+#pragma unroll
+    for (int v = 0; v < 8; v++) x[v] = a[3 * v];
+    lfk::crt8<GoldF>(x, A0, t);
+#pragma unroll
+    for (int v = 0; v < 8; v++) x[v] = a[3 * v + 1];
+    lfk::crt8<GoldF>(x, A1, t);
+#pragma unroll
+    for (int v = 0; v < 8; v++) x[v] = a[3 * v + 2];
+    lfk::crt8<GoldF>(x, A2, t);
+#pragma unroll
+    for (int p = 0; p < 8; p++) {
+        int s3 = 3 * t.slot_of_pos[p];
+        out[(size_t)s3 * ld + j] = A0[p];
+        out[(size_t)(s3 + t.pos1[p]) * ld + j] = fq_mul(t.tw1[p], A1[p]);
+        out[(size_t)(s3 + t.pos2[p]) * ld + j] = fq_mul(t.tw2[p], A2[p]);
+    }
+}
+// the dense inverse map of one element: x its 24 NTT words (registers), M the 24 x 24 matrix (LDS in k_icrt_dense, the kernel argument itself -- scalar loads --
+// in the fused product) -> the 24 coefficients of element j of plane table `coef`
+__device__ __forceinline__ void icrt_dense_elem(const u64 *M, const u64 (&x)[24], u64 *coef, size_t ld, size_t j) {
+    for (int i = 0; i < 24; i++) {
+        Acc a;
+        acc_set(a, M[i * 24], x[0]);
+#pragma unroll
+        for (int c = 1; c < 24; c++) acc_mad(a, M[i * 24 + c], x[c]);
+        coef[(size_t)i * ld + j] = acc_reduce(a);
+    }
+}
+
 constexpr u32 RED_BLOCKS = 256;   // partial rows of every two-stage reduction
 
 // fused fix_variables of the linearization round kernels (k_lin_round, k_lin_round_wide): the challenge and where the fixed tables go

@@ -630,6 +630,48 @@ struct ring_ops<Ring<C>> {
         launch_icrt_dense(c->d_icrt, a, b, count, c->stream());
         return down_ring(io, b, count, out, Form::coeff);
     }
+    // lf_ring_mul: out[x] = sum_{i < n_terms} a_i[x] * b_i[x], all three arrays in the same form.  NTT form: the slot-wise product, in an external basis between
+    // the basis-changing relayouts like every NTT-form array; coefficient form: transforms and product in one kernel, nothing converted.  `out` may BE table 0
+    // of a or of b when there is one term (the result is complete in a scratch table before `out` is written); any other overlap of a device `out` is refused
+    static int ring_mul(C *c, const u64 *a, const u64 *b, size_t n_terms, size_t count, int form, u64 *out, Origin org = Origin::host) {
+        std::lock_guard<std::mutex> g(c->mu);
+        HIPCHK(hipSetDevice(c->device));
+        const Form f = form == LF_FORM_COEFF ? Form::coeff : Form::ntt;
+        DevIo<C> io(c, org);
+        RET(io.array(a, n_terms * count));
+        RET(io.array(b, n_terms * count));
+        RET(io.array(out, count));
+        for (const u64 *in : {a, b})
+            if (n_terms != 1 || in != out) RET(io.disjoint(in, n_terms * count, out, count));
+        W *o;
+        RET(c->tbuf("io_b", count * RE, &o));
+        RET(io.begin());
+        if (f == Form::ntt) {   // the kernel reads the AoS operands themselves (the caller's device arrays, or their staged copies) and relayouts them in LDS
+            const u64 *da = a, *db = b;
+            if (!io.dev) {
+                u64 *sa, *sb;
+                RET(c->tbuf("io_a", n_terms * count * RE, &sa));
+                RET(c->tbuf("io_c", n_terms * count * RE, &sb));
+                if (count) {
+                    HIPCHK(hipMemcpyAsync(sa, a, n_terms * count * RE * 8, hipMemcpyHostToDevice, c->stream()));
+                    HIPCHK(hipMemcpyAsync(sb, b, n_terms * count * RE * 8, hipMemcpyHostToDevice, c->stream()));
+                }
+                da = sa; db = sb;
+            }
+            const auto Ti = R::xb_mat(c->xb_Ti);
+            launch_ring_mul_ntt(R::tab(c), da, db, n_terms, count, o, c->stream(), io.flag, xb_converts(c, f) ? &Ti : nullptr);
+        } else {
+            W *A, *B;
+            RET(c->tbuf("io_a", n_terms * count * RE, &A));
+            RET(c->tbuf("io_c", n_terms * count * RE, &B));
+            for (size_t i = 0; i < n_terms; i++) {
+                RET(up_ring(io, a + i * count * RE, count, A + i * RE * count, f));
+                RET(up_ring(io, b + i * count * RE, count, B + i * RE * count, f));
+            }
+            launch_ring_mul_coeff(R::tab(c), c->d_icrt, A, B, n_terms, count, o, c->stream());
+        }
+        return down_ring(io, o, count, out, f);
+    }
     static int decompose(C *c, const u64 *in, size_t count, u64 base, unsigned digits, int layout, u64 *out, Origin org = Origin::host) {
         if (!pow2(base)) return LF_ERR_UNSUPPORTED;
         std::lock_guard<std::mutex> g(c->mu);
