@@ -7,6 +7,7 @@
 //! |-------------------------------------------------------------------------------|----------------------------------------|
 //! | `AjtaiCommitmentScheme::{new, rand, commit, commit_ntt, commit_coeff, decompose_and_commit_coeff, decompose_and_commit_ntt, kappa, width}` `commitment/commitment_scheme.rs:17-113` | [`HipAjtai`] |
 //! | `Witness::{from_w_ccs, from_f, from_f_coeff, commit}` `arith.rs:230-362`        | [`HipWitness`] (device resident)       |
+//! | `decompose_witness` `nifs/decomposition.rs:162-167`, the `w_s` of `LFFoldingProver::prove` | [`HipWitness::decompose`], [`HipWitness::recompose`], `prove_resident_parts` of the two provers (on the device) |
 //! | `Arith::check_relation` of `CCS` / `CCCS` / `LCCCS` `arith.rs:76-110,193-206`      | [`HipContext::check_relation`], `check_cccs`, `check_lcccs` (on the device) |
 //! | `PoseidonTranscript` (`Transcript`, `TranscriptWithShortChallenges`) `transcript/poseidon.rs:17-75` | [`HipTranscript`] -- same traits, same challenges |
 //! | `LinearizationProver::prove` `nifs/linearization.rs:26-52`                      | `impl LinearizationProver for HipLinearizationProver` |
@@ -52,11 +53,7 @@ use latticefold::{
     utils::sumcheck::Proof as SumcheckProof,
 };
 use latticefold_hip_sys as sys;
-use stark_rings::{
-    balanced_decomposition::{recompose, DecomposeToVec},
-    PolyRing,
-};
-use stark_rings_linalg::ops::Transpose;
+use stark_rings::PolyRing;
 use stark_rings_poly::mle::DenseMultilinearExtension;
 
 // ------------------------------------------------------------------------------------------------------------------------------------
@@ -554,6 +551,26 @@ impl<NTT: SuitableRing> HipWitness<NTT> {
         Self::make(ctx, &flatten(f_coeff), sys::lf_witness_from_f_coeff, "lf_witness_from_f_coeff")
     }
 
+    /// `decompose_witness` (nifs/decomposition.rs:162-167) on the device: the K base-b parts of this witness under the context's digit rule, each a witness
+    /// of its own (`lf_witness_decompose`)
+    pub fn decompose(&self) -> Result<Vec<Self>, HipError> {
+        let k = self.ctx.params()?.K as usize;
+        let mut raws: Vec<*mut sys::lf_witness> = vec![core::ptr::null_mut(); k];
+        // SAFETY: raws holds K handles; after an error every one of them is null
+        chk(unsafe { sys::parts::lf_witness_decompose(self.ctx.raw, self.raw, raws.as_mut_ptr()) }, "lf_witness_decompose")?;
+        Ok(raws.into_iter().map(|raw| Self { ctx: self.ctx.clone(), raw, _r: PhantomData }).collect())
+    }
+
+    /// the witness whose base-b parts are `parts` (K of them), summed on the device (`lf_witness_recompose`).  An error unless the parts are exactly the
+    /// decomposition of their sum: a digit outside the rule's range, a tie on the wrong side or a sum over the bound never becomes a witness
+    pub fn recompose(ctx: &Arc<HipContext>, parts: &[Self]) -> Result<Self, HipError> {
+        let raws: Vec<*const sys::lf_witness> = parts.iter().map(|w| w.raw as *const sys::lf_witness).collect();
+        let mut raw = core::ptr::null_mut();
+        // SAFETY: raws holds parts.len() live handles; the count is checked against K by the entry point
+        chk(unsafe { sys::parts::lf_witness_recompose(ctx.raw, raws.as_ptr(), raws.len() as u32, &mut raw) }, "lf_witness_recompose")?;
+        Ok(Self { ctx: ctx.clone(), raw, _r: PhantomData })
+    }
+
     /// upload of a reference `Witness` (its `f_coeff`; `f`, `w_ccs`, `f_hat` are functions of it)
     pub fn from_reference(ctx: &Arc<HipContext>, w: &Witness<NTT>) -> Result<Self, HipError> {
         Self::from_f_coeff(ctx, &w.f_coeff)
@@ -856,12 +873,29 @@ impl<NTT: SuitableRing, T: Transcript<NTT>> HipDecompositionProver<NTT, T> {
         let lcs = outs.chunks(ll * NTT::WORDS).map(|w| lcccs_from(w, &p)).collect();
         Ok((lcs, dec_proof_from(&unflatten::<NTT>(&pr), &p)))
     }
+
+    /// resident form with the reference's `wit_s`: the K decomposed LCCCS, the proof and the K decomposed witnesses as device handles
+    /// (`lf_decomposition_prove_parts`)
+    pub fn prove_resident_parts(ctx: &Arc<HipContext>, cm_i: &LCCCS<NTT>, wit: &HipWitness<NTT>, transcript: &mut impl Transcript<NTT>) -> Result<(Vec<LCCCS<NTT>>, Vec<HipWitness<NTT>>, DecompositionProof<NTT>), HipError> {
+        let p = ctx.params()?;
+        let tr = as_hip::<NTT, _>(transcript)?;
+        let (_, dec, _) = section_lens::<NTT>(&p);
+        // SAFETY: as above
+        let ll = unsafe { sys::lf_lcccs_len_ring(&p, ring_id::<NTT>()?) };
+        let lc = lcccs_words(cm_i);
+        let (mut outs, mut pr) = (vec![0u64; p.K as usize * ll * NTT::WORDS], vec![0u64; dec * NTT::WORDS]);
+        let mut raws: Vec<*mut sys::lf_witness> = vec![core::ptr::null_mut(); p.K as usize];
+        // SAFETY: K LCCCS, K (t + tau + l + 1 + kappa) proof elements and K handles out; after an error every handle is null
+        chk(unsafe { sys::parts::lf_decomposition_prove_parts(ctx.raw, tr, lc.as_ptr(), wit.raw, outs.as_mut_ptr(), pr.as_mut_ptr(), raws.as_mut_ptr()) }, "lf_decomposition_prove_parts")?;
+        let lcs = outs.chunks(ll * NTT::WORDS).map(|w| lcccs_from(w, &p)).collect();
+        let parts = raws.into_iter().map(|raw| HipWitness { ctx: ctx.clone(), raw, _r: PhantomData }).collect();
+        Ok((lcs, parts, dec_proof_from(&unflatten::<NTT>(&pr), &p)))
+    }
 }
 
 impl<NTT: SuitableRing, T: Transcript<NTT>> DecompositionProver<NTT, T> for HipDecompositionProver<NTT, T> {
-    /// The trait hands back host objects the GPU path never materialises: `mz_mles` comes back EMPTY (only `LFFoldingProver` consumes it, and
-    /// [`HipFoldingProver`] rebuilds M z on the device), and the K decomposed witnesses are rebuilt on the host from `wit.f_coeff` with the reference's own
-    /// `decompose_to_vec(b, K).transpose()` + `Witness::from_f_coeff` -- O(K N) host work: use `prove_resident` in a loop.
+    /// The trait hands back host objects: `mz_mles` comes back EMPTY (only `LFFoldingProver` consumes it, and [`HipFoldingProver`] rebuilds M z on the
+    /// device); the K decomposed witnesses are cut on the device (`prove_resident_parts`) and downloaded, one `f_coeff` each.
     fn prove<P: DecompositionParams>(
         cm_i: &LCCCS<NTT>,
         wit: &Witness<NTT>,
@@ -873,12 +907,11 @@ impl<NTT: SuitableRing, T: Transcript<NTT>> DecompositionProver<NTT, T> for HipD
             let s = HipSession::current()?;
             s.check(ccs)?;
             let w = HipWitness::from_reference(&s.ctx, wit)?;
-            Self::prove_resident(&s.ctx, cm_i, &w, transcript)
+            let (lcs, parts, proof) = Self::prove_resident_parts(&s.ctx, cm_i, &w, transcript)?;
+            let wits = parts.iter().map(|part| part.to_reference::<P>()).collect::<Result<Vec<_>, _>>()?;
+            Ok((lcs, wits, proof))
         };
-        let (lcs, proof) = run().map_err(|e| { eprintln!("latticefold-hip: {e}"); DecompositionError::IncorrectLength })?;
-        // decompose_B_vec_into_k_vec (nifs/decomposition/utils.rs:45-49; pub(super) there)
-        let parts: Vec<Vec<NTT::CoefficientRepresentation>> = wit.f_coeff.decompose_to_vec(P::B_SMALL as u128, P::K).transpose();
-        let wits = parts.into_iter().map(|f| Witness::from_f_coeff::<P>(f)).collect();
+        let (lcs, wits, proof) = run().map_err(|e| { eprintln!("latticefold-hip: {e}"); DecompositionError::IncorrectLength })?;
         Ok((Vec::new(), lcs, wits, proof))
     }
 }
@@ -905,11 +938,32 @@ impl<NTT: SuitableRing, T: TranscriptWithShortChallenges<NTT>> HipFoldingProver<
         chk(unsafe { sys::lf_folding_prove(ctx.raw, tr, ins.as_ptr(), w_left.raw, w_right.raw, lc.as_mut_ptr(), &mut w_out, pr.as_mut_ptr()) }, "lf_folding_prove")?;
         Ok((lcccs_from(&lc, &p), HipWitness { ctx: ctx.clone(), raw: w_out, _r: PhantomData }, fold_proof_from(&unflatten::<NTT>(&pr), &p)))
     }
+
+    /// resident form with the reference's `w_s`: the 2K decomposed witnesses (K of the accumulator, then K of the fresh instance) as device handles,
+    /// recomposed on the device (`lf_folding_prove_parts`).  DEVIATION from the reference, which accepts any 2K witnesses: each half must be the decomposition
+    /// of its own sum -- all `LFDecompositionProver` ever produces; anything else is an error, never a proof about other witnesses
+    pub fn prove_resident_parts(ctx: &Arc<HipContext>, cm_i_s: &[LCCCS<NTT>], w_s: &[HipWitness<NTT>], transcript: &mut impl TranscriptWithShortChallenges<NTT>) -> Result<(LCCCS<NTT>, HipWitness<NTT>, FoldingProof<NTT>), HipError> {
+        let p = ctx.params()?;
+        let tr = as_hip::<NTT, _>(transcript)?;
+        let (_, _, fold) = section_lens::<NTT>(&p);
+        // SAFETY: as above
+        let ll = unsafe { sys::lf_lcccs_len_ring(&p, ring_id::<NTT>()?) };
+        let mut ins = Vec::with_capacity(cm_i_s.len() * ll * NTT::WORDS);
+        for x in cm_i_s {
+            ins.extend(lcccs_words(x));
+        }
+        let raws: Vec<*const sys::lf_witness> = w_s.iter().map(|w| w.raw as *const sys::lf_witness).collect();
+        let (mut lc, mut pr, mut w_out) = (vec![0u64; ll * NTT::WORDS], vec![0u64; fold * NTT::WORDS], core::ptr::null_mut());
+        // SAFETY: 2K LCCCS and w_s.len() live handles in (the count is checked against 2K by the entry point), one LCCCS and the proof out; w_out receives a fresh handle
+        chk(unsafe { sys::parts::lf_folding_prove_parts(ctx.raw, tr, ins.as_ptr(), raws.as_ptr(), raws.len() as u32, lc.as_mut_ptr(), &mut w_out, pr.as_mut_ptr()) }, "lf_folding_prove_parts")?;
+        Ok((lcccs_from(&lc, &p), HipWitness { ctx: ctx.clone(), raw: w_out, _r: PhantomData }, fold_proof_from(&unflatten::<NTT>(&pr), &p)))
+    }
 }
 
 impl<NTT: SuitableRing, T: TranscriptWithShortChallenges<NTT>> FoldingProver<NTT, T> for HipFoldingProver<NTT, T> {
-    /// `w_s` = 2K decomposed witnesses (K of the accumulator, K of the fresh instance): recomposed on the host (sum_k b^k f_k) and uploaded as the two
-    /// witnesses whose virtual base-b parts they are; `mz_mles` is ignored (M z is rebuilt on the device).
+    /// `w_s` = 2K decomposed witnesses (K of the accumulator, K of the fresh instance): uploaded one by one and recomposed on the device
+    /// (`prove_resident_parts`, with its deviation: parts that are not the decomposition of their sum are an error); `mz_mles` is ignored (M z is rebuilt
+    /// on the device).
     fn prove<P: DecompositionParams>(
         cm_i_s: &[LCCCS<NTT>],
         w_s: Vec<Witness<NTT>>,
@@ -920,15 +974,8 @@ impl<NTT: SuitableRing, T: TranscriptWithShortChallenges<NTT>> FoldingProver<NTT
         let run = || -> Result<_, HipError> {
             let s = HipSession::current()?;
             s.check(ccs)?;
-            let k = P::K;
-            let recompose = |ws: &[Witness<NTT>]| -> Vec<NTT::CoefficientRepresentation> {
-                (0..ws[0].f_coeff.len())
-                    .map(|i| recompose(&ws.iter().map(|w| w.f_coeff[i]).collect::<Vec<_>>(), P::B_SMALL as u128))     // sum_k b^k f_k[i]
-                    .collect()
-            };
-            let wl = HipWitness::from_f_coeff(&s.ctx, &recompose(&w_s[..k]))?;
-            let wr = HipWitness::from_f_coeff(&s.ctx, &recompose(&w_s[k..]))?;
-            let (lc, w0, proof) = Self::prove_resident(&s.ctx, cm_i_s, &wl, &wr, transcript)?;
+            let parts = w_s.iter().map(|w| HipWitness::from_reference(&s.ctx, w)).collect::<Result<Vec<_>, _>>()?;
+            let (lc, w0, proof) = Self::prove_resident_parts(&s.ctx, cm_i_s, &parts, transcript)?;
             Ok((lc, w0.to_reference::<P>()?, proof))
         };
         run().map_err(|e| { eprintln!("latticefold-hip: {e}"); FoldingError::IncorrectLength })

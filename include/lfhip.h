@@ -327,7 +327,7 @@ int lf_fold_step(lf_ctx *, lf_transcript *, const uint64_t *acc_lcccs, const lf_
 /* The two other sub-provers of the reference as entry points of their own (the reference exposes all three as public traits).
  * LFDecompositionProver::prove (nifs/decomposition.rs:33-88): dec_proof_out = u_s[K][t] | v_s[K][tau] | x_s[K][l+1] | y_s[K][kappa]
  * ring elements; lcccs_s_out (optional) = the K decomposed LCCCS, flat; the K decomposed witnesses stay virtual (base-b parts of
- * `wit`).  Needs the CCS and the Ajtai matrix. */
+ * `wit`; lf_decomposition_prove_parts below hands them out as handles).  Needs the CCS and the Ajtai matrix. */
 int lf_decomposition_prove(lf_ctx *, lf_transcript *, const uint64_t *lcccs, const lf_witness *wit, uint64_t *lcccs_s_out,
                            uint64_t *dec_proof_out);
 /* LFFoldingProver::prove (nifs/folding.rs:42-130): lcccs_s = 2K LCCCS (K parts of the accumulator's decomposition, then K of the
@@ -464,6 +464,10 @@ int lf_verify_host(int ring, const lf_params *, const uint32_t *S_off, const uin
 size_t lf_proof_wire_size(const lf_params *, int ring);
 int lf_proof_serialize(const lf_params *, int ring, const uint64_t *proof, uint8_t *out, size_t cap);
 int lf_proof_deserialize(const lf_params *, int ring, const uint8_t *in, size_t len, uint64_t *proof);
+
+/* ---- decomposed witnesses (decompose_witness, nifs/decomposition.rs:162-167; the w_s of LFFoldingProver::prove): four more entry points of this ABI, declared
+ * in a file of their own that this header includes -- the prototypes written in THIS file are a set the ABI tests count, as the _dev twins are ------------ */
+#include "lfhip_parts.h"
 
 #ifdef __cplusplus
 }

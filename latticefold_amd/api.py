@@ -169,6 +169,11 @@ def _lib():
         L.lf_horner_combine.argtypes = [vp, u64p, C.c_size_t, C.c_size_t, C.c_size_t, u64p, u64p]
         L.lf_decomposition_prove.argtypes = [vp, vp, u64p, vp, u64p, u64p]
         L.lf_folding_prove.argtypes = [vp, vp, u64p, vp, vp, u64p, C.POINTER(vp), u64p]
+        # decomposed witnesses: arrays of handles
+        L.lf_witness_decompose.argtypes = [vp, vp, C.POINTER(vp)]
+        L.lf_witness_recompose.argtypes = [vp, C.POINTER(vp), C.c_uint, C.POINTER(vp)]
+        L.lf_decomposition_prove_parts.argtypes = [vp, vp, u64p, vp, u64p, u64p, C.POINTER(vp)]
+        L.lf_folding_prove_parts.argtypes = [vp, vp, u64p, C.POINTER(vp), C.c_uint, u64p, C.POINTER(vp), u64p]
         L.lf_last_phase_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.lf_phase_name.restype = C.c_char_p
         L.lf_phase_name.argtypes = [C.c_int]
@@ -223,10 +228,10 @@ def abi_version():
     return int(L.lf_abi_version())
 
 
-def exported_symbols():
-    """Every symbol include/lfhip.h declares (used by the CPU-side ABI test)."""
+def exported_symbols(header="lfhip.h"):
+    """Every symbol include/lfhip.h declares (used by the CPU-side ABI test); header="lfhip_parts.h": the ones of the file it includes."""
     import re
-    hdr = open(os.path.join(_HERE, "..", "include", "lfhip.h")).read()
+    hdr = open(os.path.join(_HERE, "..", "include", header)).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     return sorted(set(re.findall(r"\b(lf_[a-z0-9_]+)\s*\(", hdr)))
 
@@ -798,6 +803,19 @@ class Witness:
         _chk(_lib().lf_witness_commit(self.ctx.h, self.h, o.ctypes.data_as(u64p)), "lf_witness_commit")
         return o
 
+    def decompose(self, ctx):
+        """decompose_witness (nifs/decomposition.rs:162-167): the K base-b parts of this witness under the context's digit rule, each a Witness of its own"""
+        hs = (C.c_void_p * max(ctx.params.K if ctx.params else 0, 1))()
+        _chk(_lib().lf_witness_decompose(ctx.h, self.h, hs), "lf_witness_decompose")
+        return [Witness(ctx, C.c_void_p(h)) for h in hs[:ctx.params.K]]
+
+    @classmethod
+    def recompose(cls, ctx, parts):
+        """the witness whose base-b parts are `parts` (K of them); LfError unless they are exactly the decomposition of their sum"""
+        h = C.c_void_p()
+        _chk(_lib().lf_witness_recompose(ctx.h, _handles(parts), len(parts), C.byref(h)), "lf_witness_recompose")
+        return cls(ctx, h)
+
     def free(self):
         if self.h:
             _lib().lf_witness_free(self.h)
@@ -808,6 +826,11 @@ class Witness:
             self.free()
         except Exception:
             pass
+
+
+def _handles(wits):
+    """witnesses -> the array of handles an entry point with a `const lf_witness *const *` argument takes"""
+    return (C.c_void_p * max(len(wits), 1))(*[w.h.value if isinstance(w.h, C.c_void_p) else w.h for w in wits])
 
 
 class PoseidonTranscript:
@@ -888,6 +911,18 @@ class LFDecompositionProver:
              "lf_decomposition_prove")
         return lcs, pr
 
+    @staticmethod
+    def prove_parts(ctx, lcccs, wit, transcript):
+        """LFDecompositionProver::prove with its wit_s -> (K decomposed LCCCS flat, decomposition proof flat, the K decomposed witnesses)"""
+        a, p = _a64(lcccs)
+        prm = ctx.params
+        lcs = np.zeros((prm.K * ctx.lcccs_len, ctx.RE), dtype=np.uint64)
+        pr = np.zeros((prm.K * (prm.t + ctx.TAU + prm.l + 1 + prm.kappa), ctx.RE), dtype=np.uint64)
+        hs = (C.c_void_p * prm.K)()
+        _chk(_lib().lf_decomposition_prove_parts(ctx.h, transcript.h, p, wit.h, lcs.ctypes.data_as(u64p), pr.ctypes.data_as(u64p), hs),
+             "lf_decomposition_prove_parts")
+        return lcs, pr, [Witness(ctx, C.c_void_p(h)) for h in hs]
+
 
 class LFFoldingProver:
     @staticmethod
@@ -901,6 +936,19 @@ class LFFoldingProver:
         h = C.c_void_p()
         _chk(_lib().lf_folding_prove(ctx.h, transcript.h, p, w_left.h, w_right.h, lc.ctypes.data_as(u64p), C.byref(h),
                                      pr.ctypes.data_as(u64p)), "lf_folding_prove")
+        return lc, Witness(ctx, h), pr
+
+    @staticmethod
+    def prove_parts(ctx, lcccs_s, w_s, transcript):
+        """LFFoldingProver::prove with the reference's w_s: the 2K decomposed witnesses (K of the accumulator, then K of the fresh instance), which must be
+        the decompositions of their sums -> (folded LCCCS flat, folded Witness, folding proof flat), those of `prove` on the two sums."""
+        a, p = _a64(lcccs_s)
+        prm = ctx.params
+        lc = np.zeros((ctx.lcccs_len, ctx.RE), dtype=np.uint64)
+        pr = np.zeros((prm.s * (2 * prm.b + 1) + 2 * prm.K * (ctx.TAU + prm.t), ctx.RE), dtype=np.uint64)
+        h = C.c_void_p()
+        _chk(_lib().lf_folding_prove_parts(ctx.h, transcript.h, p, _handles(w_s), len(w_s), lc.ctypes.data_as(u64p), C.byref(h),
+                                           pr.ctypes.data_as(u64p)), "lf_folding_prove_parts")
         return lc, Witness(ctx, h), pr
 
 

@@ -946,6 +946,50 @@ int lf_witness_commit(lf_ctx *c, const lf_witness *w, uint64_t *cm_out) {
     if (!c || !w || !cm_out || w->ctx != c) return LF_ERR_INVALID;
     return c->bb ? ring_ops<BbRing>::witness_commit(c->bb->p, w, cm_out) : ring_ops<GoldRing>::witness_commit(c, w, cm_out);
 }
+// ---- decomposed witnesses: the wit_s of LFDecompositionProver::prove and the w_s of LFFoldingProver::prove as handles (lf_ring_host.h: witness_decompose /
+// witness_recompose; one body for both rings).  The two provers with parts are the calls above and below composed: every refusal of the parts comes before the
+// prover sees its transcript.
+// every output handle is NULL after an error: cleared before the first check that can refuse (a context without a CCS has no K: nothing to clear)
+static void parts_clear(lf_ctx *c, lf_witness **parts_out) {
+    if (c && parts_out && c->have_ccs_any())
+        for (u32 k = 0, K = c->params_any().K; k < K; k++) parts_out[k] = nullptr;
+}
+int lf_witness_decompose(lf_ctx *c, const lf_witness *wit, lf_witness **parts_out) {
+    parts_clear(c, parts_out);
+    if (!c || !wit || !parts_out || wit->ctx != c) return LF_ERR_INVALID;
+    return c->bb ? ring_ops<BbRing>::witness_decompose(c->bb->p, wit, parts_out) : ring_ops<GoldRing>::witness_decompose(c, wit, parts_out);
+}
+int lf_witness_recompose(lf_ctx *c, const lf_witness *const *parts, unsigned count, lf_witness **out) {
+    if (out) *out = nullptr;
+    if (!c || !parts || !out) return LF_ERR_INVALID;
+    return c->bb ? ring_ops<BbRing>::witness_recompose(c->bb->p, parts, count, out) : ring_ops<GoldRing>::witness_recompose(c, parts, count, out);
+}
+int lf_decomposition_prove_parts(lf_ctx *c, lf_transcript *t, const uint64_t *lcccs, const lf_witness *wit, uint64_t *lcccs_s_out, uint64_t *dec_proof_out,
+                                 lf_witness **parts_out) {
+    parts_clear(c, parts_out);
+    if (!c || !t || !lcccs || !wit || !dec_proof_out || !parts_out || wit->ctx != c || (c->bb != nullptr) != (t->bb != nullptr)) return LF_ERR_INVALID;
+    RET(lf_witness_decompose(c, wit, parts_out));   // the parts first: whatever refuses them refuses the call before the first absorb
+    const int rc = lf_decomposition_prove(c, t, lcccs, wit, lcccs_s_out, dec_proof_out);
+    if (rc != LF_OK)
+        for (u32 k = 0, K = c->params_any().K; k < K; k++) { lf_witness_free(parts_out[k]); parts_out[k] = nullptr; }
+    return rc;
+}
+int lf_folding_prove_parts(lf_ctx *c, lf_transcript *t, const uint64_t *lcccs_s, const lf_witness *const *w_s, unsigned count, uint64_t *lcccs_out,
+                           lf_witness **w_out, uint64_t *fold_proof_out) {
+    if (w_out) *w_out = nullptr;
+    if (!c || !t || !lcccs_s || !w_s || !lcccs_out || !w_out || !fold_proof_out || (c->bb != nullptr) != (t->bb != nullptr)) return LF_ERR_INVALID;
+    if (!c->have_ccs_any()) return LF_ERR_STATE;
+    const u32 K = c->params_any().K;
+    if (count != 2 * K) return LF_ERR_INVALID;
+    lf_witness *side[2] = {nullptr, nullptr};   // the two sums: the accumulator's, then the fresh instance's
+    int rc = lf_witness_recompose(c, w_s, K, &side[0]);
+    if (rc == LF_OK) rc = lf_witness_recompose(c, w_s + K, K, &side[1]);
+    if (rc == LF_OK) rc = lf_folding_prove(c, t, lcccs_s, side[0], side[1], lcccs_out, w_out, fold_proof_out);
+    lf_witness_free(side[0]);
+    lf_witness_free(side[1]);
+    if (rc != LF_OK && *w_out) { lf_witness_free(*w_out); *w_out = nullptr; }
+    return rc;
+}
 // pool of recycled witness-plane buffers: process-wide (a witness may be freed after its context), keyed by device and size
 namespace {
 struct PoolEnt { int device; size_t bytes; int32_t *p; };

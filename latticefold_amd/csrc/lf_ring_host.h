@@ -28,6 +28,7 @@
 #include "lf_check.h"
 #include "lf_ctx.h"
 #include "lf_dev_ptr.h"
+#include "lf_witness_parts.h"
 
 #pragma GCC visibility push(hidden)
 // ---- lengths in ring elements (tau = extension degree: the v part of an LCCCS and of the proofs is tau elements) ------------------------------------
@@ -1085,6 +1086,75 @@ struct ring_ops<Ring<C>> {
         RET(commit_dev_i8g(c, nullptr, 0, 1, w->planes + c->A_col0, w->N, o, true));   // timed: lf_last_kernel_stats reports the stand-alone kernel
         c->ev_collect();
         return R::commit_finish(c, o, (size_t)c->kappa * RE, cm_out);   // the sharded gather: per ring
+    }
+
+    // ---- decomposed witnesses: decompose_witness (nifs/decomposition.rs:162-167) and its inverse on handles (lf_witness_parts.hip) ----
+    // what both directions need of the context, under its lock: a constraint system, and K base-b digits that cover B/2 under the digit rule in force -- the
+    // test a decomposition step performs where it starts (the rule may have changed since the load)
+    static int parts_ready(const C *c, u32 *lb) {
+        if (!c->have_ccs) return LF_ERR_STATE;
+        const lf_params &P = c->P;
+        if (P.K > lfparts::MAX_PARTS || !sb_digits_cover(P.b, P.K, P.B, c->digit_mode)) return LF_ERR_UNSUPPORTED;
+        *lb = sb_log2(P.b);
+        return LF_OK;
+    }
+    // parts_out[k] = Witness::from_f_coeff(part k of decompose_B_vec_into_k_vec(wit.f_coeff)): K handles with planes of their own, so that each is freed alone
+    static int witness_decompose(C *c, const lf_witness *wit, lf_witness **parts_out) {
+        std::lock_guard<std::mutex> g(c->mu);
+        u32 lb;
+        const int ready = parts_ready(c, &lb);
+        if (ready == LF_ERR_STATE) return ready;
+        const u32 K = c->P.K;
+        if (wit->N != c->N) return LF_ERR_INVALID;
+        RET(ready);
+        HIPCHK(hipSetDevice(c->device));
+        const size_t bytes = c->N * RE * 4;
+        int32_t *pl[lfparts::MAX_PARTS] = {};
+        int rc = LF_OK;
+        for (u32 k = 0; k < K && rc == LF_OK; k++) rc = lf_planes_alloc(R::owner(c), bytes, &pl[k]);
+        if (rc == LF_OK && lfparts::launch_witness_cut(wit->planes, c->N * RE, K, lb, c->digit_mode, pl, c->stream()) != 0) rc = LF_ERR_HIP;
+        if (hipStreamSynchronize(c->stream()) != hipSuccess) rc = LF_ERR_HIP;   // (before any of the planes goes back to the pool)
+        if (rc != LF_OK) {
+            for (u32 k = 0; k < K; k++)
+                if (pl[k]) lf_planes_release(R::owner(c), bytes, pl[k]);
+            return rc;
+        }
+        for (u32 k = 0; k < K; k++) parts_out[k] = new lf_witness{R::owner(c), pl[k], c->N, c->device, bytes};
+        return LF_OK;
+    }
+    // *out = the witness whose base-b parts are parts[0..count): digits in the rule's range that are the decomposition of their own sum, a sum the ingest of
+    // lf_witness_from_f_coeff accepts.  Anything else is refused with the flag the kernel raised (it rides home in front of the call's only synchronise)
+    static int witness_recompose(C *c, const lf_witness *const *parts, unsigned count, lf_witness **out) {
+        std::lock_guard<std::mutex> g(c->mu);
+        *out = nullptr;
+        u32 lb;
+        const int ready = parts_ready(c, &lb);
+        if (ready == LF_ERR_STATE) return ready;
+        if (count != c->P.K) return LF_ERR_INVALID;
+        const int32_t *pl[lfparts::MAX_PARTS] = {};
+        for (u32 k = 0; k < count; k++) {
+            if (!parts[k] || parts[k]->ctx != R::owner(c) || parts[k]->N != c->N) return LF_ERR_INVALID;
+            if (k < lfparts::MAX_PARTS) pl[k] = parts[k]->planes;
+        }
+        RET(ready);
+        HIPCHK(hipSetDevice(c->device));
+        u32 *flag;
+        RET(c->tbuf("small_dev", 4096, (u64 **)&flag));
+        const size_t bytes = c->N * RE * 4;
+        int32_t *sum;
+        RET(lf_planes_alloc(R::owner(c), bytes, &sum));
+        u32 hv = 0;
+        int rc = LF_OK;
+        if (hipMemsetAsync(flag, 0, 4, c->stream()) != hipSuccess ||
+            lfparts::launch_witness_join(pl, c->N * RE, count, lb, c->digit_mode, c->P.B / 2, sum, flag, c->stream()) != 0 ||
+            hipMemcpyAsync(&hv, flag, 4, hipMemcpyDeviceToHost, c->stream()) != hipSuccess)
+            rc = LF_ERR_HIP;
+        if (hipStreamSynchronize(c->stream()) != hipSuccess) rc = LF_ERR_HIP;
+        if (rc == LF_OK && hv)
+            rc = (hv & (lfparts::FLAG_DIGIT | lfparts::FLAG_NOT_CANONICAL)) ? LF_ERR_INVALID : ((hv & lfparts::FLAG_NORM) ? LF_ERR_NORM : LF_ERR_UNSUPPORTED);
+        if (rc != LF_OK) { lf_planes_release(R::owner(c), bytes, sum); return rc; }
+        *out = new lf_witness{R::owner(c), sum, c->N, c->device, bytes};
+        return LF_OK;
     }
 
     // ---- folding helpers ----

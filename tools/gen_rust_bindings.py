@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Generates the raw Rust binding of the C ABI (`latticefold-hip-sys/src/lib.rs`) from include/lfhip.h and include/lfplus.h.
+"""Generates the raw Rust binding of the C ABI (`latticefold-hip-sys/src/lib.rs`) from include/lfhip.h and include/lfplus.h, and its module `parts`
+(`src/parts.rs`) from include/lfhip_parts.h, the file lfhip.h includes for the entry points of the decomposed witnesses.
 
     python tools/gen_rust_bindings.py            print the binding
     python tools/gen_rust_bindings.py --write    rewrite bindings/latticefold-hip-sys/src/lib.rs and the block between the
-                                                 GENERATED markers of INTEGRATION.md
+                                                 GENERATED markers of INTEGRATION.md; the same for src/parts.rs and its markers
 
 The reference is safe Rust with `#![forbid(unsafe_code)]` (crates/latticefold/src/lib.rs:4): the `extern "C"` block lives in a new
 `-sys` crate.  No Rust toolchain exists in the build image, so the text is derived mechanically from the headers (every prototype, the
@@ -18,6 +19,9 @@ HEADERS = ("include/lfhip.h", "include/lfplus.h")
 OUT = os.path.join(ROOT, "bindings", "latticefold-hip-sys", "src", "lib.rs")
 DOC = os.path.join(ROOT, "INTEGRATION.md")
 BEGIN, END = "<!-- BEGIN GENERATED BINDING (tools/gen_rust_bindings.py) -->", "<!-- END GENERATED BINDING -->"
+PARTS_HEADER = "include/lfhip_parts.h"
+PARTS_OUT = os.path.join(ROOT, "bindings", "latticefold-hip-sys", "src", "parts.rs")
+PARTS_BEGIN, PARTS_END = "<!-- BEGIN GENERATED BINDING: parts (tools/gen_rust_bindings.py) -->", "<!-- END GENERATED BINDING: parts -->"
 
 SCALARS = {
     "int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "char": "c_char", "float": "f32", "double": "f64", "void": "c_void",
@@ -139,7 +143,23 @@ def generate():
             L.append(f"    pub fn {name}({ps})" + (f" -> {ret}" if ret else "") + ";")
             allfns.append(name)
         L += ["}", ""]
+    L += ["/// include/lfhip_parts.h (included by lfhip.h): the decomposed witnesses as handles -- `parts::lf_witness_decompose`, ...", "pub mod parts;", ""]
     return "\n".join(L), allfns
+
+
+def generate_parts():
+    """src/parts.rs: the entry points of include/lfhip_parts.h, over the types of the crate root"""
+    _, fns = parse(PARTS_HEADER)
+    L = [f"// GENERATED by tools/gen_rust_bindings.py from {PARTS_HEADER} -- do not edit.",
+         "// Module `parts` of latticefold-hip-sys: the decomposed witnesses of LFDecompositionProver / LFFoldingProver as device handles.",
+         "use core::ffi::{c_int, c_uint};", "",
+         "use super::{lf_ctx, lf_transcript, lf_witness};", "",
+         '#[link(name = "lfhip")]', 'extern "C" {']
+    for name, params, ret in fns:
+        ps = ", ".join(f"{n}: {t}" for n, t in params)
+        L.append(f"    pub fn {name}({ps})" + (f" -> {ret}" if ret else "") + ";")
+    L += ["}", ""]
+    return "\n".join(L), [f[0] for f in fns]
 
 
 def main():
@@ -152,9 +172,17 @@ def main():
             a, b = doc.index(BEGIN) + len(BEGIN), doc.index(END)
             doc = doc[:a] + "\n```rust\n" + text + "```\n" + doc[b:]
             open(DOC, "w").write(doc)
+        ptext, pfns = generate_parts()
+        open(PARTS_OUT, "w").write(ptext)
+        doc = open(DOC).read()
+        if PARTS_BEGIN in doc and PARTS_END in doc:
+            a, b = doc.index(PARTS_BEGIN) + len(PARTS_BEGIN), doc.index(PARTS_END)
+            open(DOC, "w").write(doc[:a] + "\n```rust\n" + ptext + "```\n" + doc[b:])
+        print(f"{len(pfns)} functions -> {os.path.relpath(PARTS_OUT, ROOT)}")
         print(f"{len(fns)} functions -> {os.path.relpath(OUT, ROOT)}" + (", INTEGRATION.md" if BEGIN in doc else ""))
     else:
         sys.stdout.write(text)
+        sys.stdout.write(generate_parts()[0])
 
 
 if __name__ == "__main__":
