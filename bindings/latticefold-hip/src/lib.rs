@@ -10,6 +10,7 @@
 //! | `decompose_witness` `nifs/decomposition.rs:162-167`, the `w_s` of `LFFoldingProver::prove` | [`HipWitness::decompose`], [`HipWitness::recompose`], `prove_resident_parts` of the two provers (on the device) |
 //! | `Arith::check_relation` of `CCS` / `CCCS` / `LCCCS` `arith.rs:76-110,193-206`      | [`HipContext::check_relation`], `check_cccs`, `check_lcccs` (on the device) |
 //! | `PoseidonTranscript` (`Transcript`, `TranscriptWithShortChallenges`) `transcript/poseidon.rs:17-75` | [`HipTranscript`] -- same traits, same challenges |
+//! | `MLSumcheck::{prove_as_subprotocol, verify_as_subprotocol}` `utils/sumcheck.rs:53-104` over a `(coefficient, indices)` product list `utils/sumcheck/utils.rs:24-75` | [`HipMLSumcheck`] (prover on the device, verifier on the host) |
 //! | `LinearizationProver::prove` `nifs/linearization.rs:26-52`                      | `impl LinearizationProver for HipLinearizationProver` |
 //! | `DecompositionProver::prove` `nifs/decomposition/structs.rs:48-64`              | `impl DecompositionProver for HipDecompositionProver` |
 //! | `FoldingProver::prove` `nifs/folding/structs.rs:43-70`                          | `impl FoldingProver for HipFoldingProver` |
@@ -810,6 +811,83 @@ fn section_lens<NTT: SuitableRing>(p: &sys::lf_params) -> (usize, usize, usize) 
     let dec = p.K as usize * (p.t as usize + tau + p.l as usize + 1 + p.kappa as usize);
     let fold = p.s as usize * (2 * p.b as usize + 1) + 2 * p.K as usize * (tau + p.t as usize);
     (lin, dec, fold)
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// MLSumcheck over any sum of products of MLE tables (include/lfhip_sumcheck.h; `sys::sumcheck`)
+// ------------------------------------------------------------------------------------------------------------------------------------
+/// `MLSumcheck::prove_as_subprotocol` / `verify_as_subprotocol` (utils/sumcheck.rs:53-104) for a polynomial given as the product list of a
+/// `VirtualPolynomial` (utils/sumcheck/utils.rs:24-75): `products[i] = (coefficient, indices into mles)`,
+/// g = sum_i coefficient_i * prod_{j in indices_i} mles[j].  The reference takes the comb function as a closure; the device takes its description.
+/// Every error of the library comes back as `HipError::Lib(_, code)` with the library's own code (`LF_ERR_INVALID`, `LF_ERR_UNSUPPORTED`, `LF_ERR_STATE`,
+/// `LF_ERR_HIP`, `LF_ERR_REJECT`): nothing is collapsed.
+pub struct HipMLSumcheck<NTT, T> {
+    _r: PhantomData<(NTT, T)>,
+}
+
+fn ext_from_words<NTT: SuitableRing>(w: &[u64]) -> NTT::BaseRing {
+    let fs: Vec<_> = w.iter().map(|&x| <<NTT::BaseRing as Field>::BasePrimeField as From<u64>>::from(x)).collect();
+    <NTT::BaseRing as Field>::from_base_prime_field_elems(&fs).expect("tau coordinates")
+}
+
+impl<NTT: SuitableRing, T: Transcript<NTT>> HipMLSumcheck<NTT, T> {
+    /// -> (the proof, the point, every MLE's value at the point).  The last is what each caller of the reference computes next from the returned
+    /// `ProverState` (its MLEs fixed nvars - 1 times): `lf_mlsumcheck_final` does it where the tables already are.
+    pub fn prove_as_subprotocol(
+        ctx: &Arc<HipContext>,
+        transcript: &mut impl Transcript<NTT>,
+        mles: &[DenseMultilinearExtension<NTT>],
+        nvars: usize,
+        degree: usize,
+        products: &[(NTT, Vec<usize>)],
+    ) -> Result<(SumcheckProof<NTT>, Vec<NTT::BaseRing>, Vec<NTT>), HipError> {
+        let tau = <NTT::BaseRing as Field>::extension_degree() as usize;
+        let tr = as_hip::<NTT, _>(transcript)?;
+        let mut tables = Vec::with_capacity(mles.len() * (1usize << nvars) * NTT::WORDS);
+        for m in mles {
+            assert_eq!(m.evaluations.len(), 1usize << nvars, "every MLE has 2^nvars evaluations");
+            tables.extend(flatten(&m.evaluations));
+        }
+        let (mut off, mut idx, mut coef) = (vec![0u32], Vec::new(), Vec::new());
+        for (c, ix) in products {
+            idx.extend(ix.iter().map(|&j| j as u32));
+            off.push(idx.len() as u32);
+            c.to_words(&mut coef);
+        }
+        let poly = sys::sumcheck::lf_vpoly {
+            nvars: nvars as u32, ntables: mles.len() as u32, nterms: products.len() as u32, degree: degree as u32,
+            term_off: off.as_ptr(), term_idx: idx.as_ptr(), coef: coef.as_ptr(),
+        };
+        let (mut msgs, mut point, mut fin) = (vec![0u64; nvars * (degree + 1) * NTT::WORDS], vec![0u64; nvars * tau], vec![0u64; mles.len() * NTT::WORDS]);
+        // SAFETY: the descriptor's arrays and the tables hold what its counts say (built above) and outlive the call; the outputs are sized as the header states
+        chk(unsafe { sys::sumcheck::lf_mlsumcheck_prove(ctx.raw, tr, &poly, tables.as_ptr(), msgs.as_mut_ptr(), point.as_mut_ptr(), fin.as_mut_ptr()) }, "lf_mlsumcheck_prove")?;
+        Ok((sumcheck_proof(&unflatten::<NTT>(&msgs), nvars, degree + 1), point.chunks(tau).map(ext_from_words::<NTT>).collect(), unflatten(&fin)))
+    }
+
+    /// -> the subclaim: (point, expected evaluation).  A failed round check is `Err(HipError::Lib(_, LF_ERR_REJECT))`; the transcript has advanced over every
+    /// round, as the reference's has.  Host only: no context
+    pub fn verify_as_subprotocol(
+        transcript: &mut impl Transcript<NTT>,
+        nvars: usize,
+        degree: usize,
+        claimed_sum: NTT,
+        proof: &SumcheckProof<NTT>,
+    ) -> Result<(Vec<NTT::BaseRing>, NTT), HipError> {
+        let tau = <NTT::BaseRing as Field>::extension_degree() as usize;
+        let tr = as_hip::<NTT, _>(transcript)?;
+        // (the inverse of `sumcheck_proof`: the derived encoding of Proof is that of Vec<Vec<NTT>>)
+        let mut buf = Vec::new();
+        proof.serialize_uncompressed(&mut buf).expect("in-memory serialisation");
+        let rounds: Vec<Vec<NTT>> = CanonicalDeserialize::deserialize_uncompressed(&buf[..]).expect("Vec<ProverMsg<R>> and Vec<Vec<R>> share one encoding");
+        assert!(rounds.len() == nvars && rounds.iter().all(|m| m.len() == degree + 1), "nvars messages of degree + 1 evaluations");
+        let msgs: Vec<u64> = rounds.iter().flat_map(|m| flatten(m)).collect();
+        let mut claim = Vec::new();
+        claimed_sum.to_words(&mut claim);
+        let (mut point, mut expected) = (vec![0u64; nvars * tau], vec![0u64; NTT::WORDS]);
+        // SAFETY: claim is one element, msgs nvars x (degree + 1) elements (checked above); the outputs are sized as the header states
+        chk(unsafe { sys::sumcheck::lf_mlsumcheck_verify(ring_id::<NTT>()?, tr, nvars as u32, degree as u32, claim.as_ptr(), msgs.as_ptr(), point.as_mut_ptr(), expected.as_mut_ptr()) }, "lf_mlsumcheck_verify")?;
+        Ok((point.chunks(tau).map(ext_from_words::<NTT>).collect(), NTT::from_words(&expected)))
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------

@@ -469,6 +469,10 @@ int lf_proof_deserialize(const lf_params *, int ring, const uint8_t *in, size_t 
  * in a file of their own that this header includes -- the prototypes written in THIS file are a set the ABI tests count, as the _dev twins are ------------ */
 #include "lfhip_parts.h"
 
+/* ---- MLSumcheck::prove_as_subprotocol / verify_as_subprotocol over any sum of products of MLE tables (utils/sumcheck.rs:53-104): eight more entry points,
+ * lf_mlsumcheck_*, in a file of their own for the same reason ------------ */
+#include "lfhip_sumcheck.h"
+
 #ifdef __cplusplus
 }
 #endif

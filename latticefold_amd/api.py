@@ -63,6 +63,12 @@ class Params(C.Structure):
                 ("t", C.c_uint32), ("q", C.c_uint32), ("d", C.c_uint32)]
 
 
+class VPolyDesc(C.Structure):
+    """lf_vpoly (include/lfhip_sumcheck.h)"""
+    _fields_ = [("nvars", C.c_uint32), ("ntables", C.c_uint32), ("nterms", C.c_uint32), ("degree", C.c_uint32),
+                ("term_off", u32p), ("term_idx", u32p), ("coef", u64p)]
+
+
 _LIB = None
 
 
@@ -207,6 +213,16 @@ def _lib():
         L.lf_sumcheck_fold_begin_dev.argtypes = [vp, vp, u64p]
         L.lf_lincomb_dev.argtypes = [vp, u64p, vp, C.c_size_t, C.c_size_t, vp]
         L.lf_horner_combine_dev.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, u64p, vp]
+        # the generic sumcheck (include/lfhip_sumcheck.h)
+        vpp = C.POINTER(VPolyDesc)
+        L.lf_mlsumcheck_begin.argtypes = [vp, vpp, u64p]
+        L.lf_mlsumcheck_begin_device.argtypes = [vp, vpp, vp]
+        L.lf_mlsumcheck_round.argtypes = [vp, u64p, u64p]
+        L.lf_mlsumcheck_final.argtypes = [vp, u64p, u64p]
+        L.lf_mlsumcheck_end.argtypes = [vp]
+        L.lf_mlsumcheck_prove.argtypes = [vp, vp, vpp, u64p, u64p, u64p, u64p]
+        L.lf_mlsumcheck_prove_device.argtypes = [vp, vp, vpp, vp, u64p, u64p, u64p]
+        L.lf_mlsumcheck_verify.argtypes = [C.c_int, vp, C.c_uint32, C.c_uint32, u64p, u64p, u64p, u64p]
         _LIB = L
     return _LIB
 
@@ -229,7 +245,7 @@ def abi_version():
 
 
 def exported_symbols(header="lfhip.h"):
-    """Every symbol include/lfhip.h declares (used by the CPU-side ABI test); header="lfhip_parts.h": the ones of the file it includes."""
+    """Every symbol include/lfhip.h declares (used by the CPU-side ABI test); header="lfhip_parts.h" / "lfhip_sumcheck.h": the ones of a file it includes."""
     import re
     hdr = open(os.path.join(_HERE, "..", "include", header)).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
@@ -1040,6 +1056,119 @@ class MLSumcheckLin:
 
     def end(self):
         _chk(_lib().lf_sumcheck_lin_end(self.ctx.h), "lf_sumcheck_lin_end")
+
+
+class VPoly:
+    """VirtualPolynomial (utils/sumcheck/utils.rs:24-75) over a flat list of MLE tables: g = sum_i coef_i * prod_{j in indices_i} T_j.
+    terms: [(coef, [indices])], coef a ring element in NTT form (RE words) or a Python integer (the constant, the same in every slot); an index may repeat
+    inside a term and across terms.  degree: what the prover sends degree + 1 evaluations for (default: the widest term)."""
+
+    def __init__(self, terms, degree=None):
+        self.terms = [(c, [int(j) for j in idx]) for c, idx in terms]
+        self.degree = max((len(idx) for _, idx in self.terms), default=0) if degree is None else int(degree)
+
+    def desc(self, ring, nvars, ntables):
+        """the lf_vpoly of this polynomial on `ring` (the arrays it points to stay alive with the returned object)"""
+        RE_, tau, p = RING_WORDS[ring], RING_TAU[ring], int(_lib().lf_ring_modulus(RING_IDS[ring]))
+        off = np.zeros(len(self.terms) + 1, dtype=np.uint32)
+        coef = np.zeros((max(len(self.terms), 1), RE_), dtype=np.uint64)
+        idx = []
+        for i, (c, ix) in enumerate(self.terms):
+            idx += ix
+            off[i + 1] = len(idx)
+            if isinstance(c, (int, np.integer)):
+                coef[i, ::tau] = int(c) % p
+            else:
+                coef[i] = np.asarray(c, dtype=np.uint64).reshape(RE_)
+        idx = np.asarray(idx + [0], dtype=np.uint32)
+        d = VPolyDesc(nvars, ntables, len(self.terms), self.degree, off.ctypes.data_as(u32p), idx.ctypes.data_as(u32p), coef.ctypes.data_as(u64p))
+        d._keep = (off, idx, coef)
+        return d
+
+
+class MLSumcheck:
+    """MLSumcheck::prove_as_subprotocol / verify_as_subprotocol (utils/sumcheck.rs:53-104) over any VPoly (lf_mlsumcheck_*, include/lfhip_sumcheck.h), on a
+    bare context.  tables: (T, 2^nvars, RE) ring elements in NTT form, a numpy array or a device array (read in place).  The object is the split form:
+    prove_round / final / end with the caller's transcript in between; prove is the whole subprotocol in one call."""
+
+    @staticmethod
+    def _shape(ctx, tables):
+        sh = tuple(tables.shape)
+        if len(sh) != 3 or sh[2] != ctx.RE or sh[1] < 2 or sh[1] & (sh[1] - 1):
+            raise ValueError(f"tables: (T, 2^nvars, {ctx.RE})")
+        return sh[0], sh[1].bit_length() - 1
+
+    def __init__(self, ctx, tables, vpoly):
+        self.ctx = ctx
+        self.ntables, self.nvars = self._shape(ctx, tables)
+        self.degree = vpoly.degree
+        d = vpoly.desc(ctx.ring, self.nvars, self.ntables)
+        if is_device_array(tables):
+            _chk(_lib().lf_mlsumcheck_begin_device(ctx.h, C.byref(d), _dev(ctx, tables)), "lf_mlsumcheck_begin_device")
+            return
+        a, p = _a64(tables)
+        _chk(_lib().lf_mlsumcheck_begin(ctx.h, C.byref(d), p), "lf_mlsumcheck_begin")
+
+    def prove_round(self, r_prev=None):
+        o = np.zeros((self.degree + 1, self.ctx.RE), dtype=np.uint64)
+        if r_prev is None:
+            rc = _lib().lf_mlsumcheck_round(self.ctx.h, None, o.ctypes.data_as(u64p))
+        else:
+            a, p = _a64(r_prev)
+            rc = _lib().lf_mlsumcheck_round(self.ctx.h, p, o.ctypes.data_as(u64p))
+        _chk(rc, "lf_mlsumcheck_round")
+        return o
+
+    def final(self, r_last):
+        """after the last round: every table's value at the whole point, (T, RE)"""
+        o = np.zeros((self.ntables, self.ctx.RE), dtype=np.uint64)
+        a, p = _a64(r_last)
+        _chk(_lib().lf_mlsumcheck_final(self.ctx.h, p, o.ctypes.data_as(u64p)), "lf_mlsumcheck_final")
+        return o
+
+    def end(self):
+        _chk(_lib().lf_mlsumcheck_end(self.ctx.h), "lf_mlsumcheck_end")
+
+    @staticmethod
+    def prove(ctx, transcript, tables, vpoly):
+        """prove_as_subprotocol -> (msgs (nvars, degree + 1, RE), point (nvars, TAU), final (T, RE): the tables' values at the point)"""
+        T, nv = MLSumcheck._shape(ctx, tables)
+        d = vpoly.desc(ctx.ring, nv, T)
+        msgs = np.zeros((nv, vpoly.degree + 1, ctx.RE), dtype=np.uint64)
+        point = np.zeros((nv, ctx.TAU), dtype=np.uint64)
+        fin = np.zeros((T, ctx.RE), dtype=np.uint64)
+        outs = (msgs.ctypes.data_as(u64p), point.ctypes.data_as(u64p), fin.ctypes.data_as(u64p))
+        if is_device_array(tables):
+            _chk(_lib().lf_mlsumcheck_prove_device(ctx.h, transcript.h, C.byref(d), _dev(ctx, tables), *outs), "lf_mlsumcheck_prove_device")
+        else:
+            a, p = _a64(tables)
+            _chk(_lib().lf_mlsumcheck_prove(ctx.h, transcript.h, C.byref(d), p, *outs), "lf_mlsumcheck_prove")
+        return msgs, point, fin
+
+    @staticmethod
+    def verify(transcript, nvars, degree, claimed_sum, msgs, ring="goldilocks"):
+        """verify_as_subprotocol on the host (no GPU, no context) -> (ok, point (nvars, TAU), expected): expected is the subclaim's ring element, or the index of
+        the failing round when ok is False"""
+        RE_, tau = RING_WORDS[ring], RING_TAU[ring]
+        cs, pc = _a64(claimed_sum)
+        m, pm = _a64(msgs)
+        if cs.size != RE_ or m.size != nvars * (degree + 1) * RE_:
+            raise ValueError("claimed_sum: one ring element; msgs: nvars x (degree + 1) ring elements")
+        point = np.zeros((nvars, tau), dtype=np.uint64)
+        exp = np.zeros(RE_, dtype=np.uint64)
+        rc = _lib().lf_mlsumcheck_verify(RING_IDS[ring], transcript.h, nvars, degree, pc, pm, point.ctypes.data_as(u64p), exp.ctypes.data_as(u64p))
+        if rc not in (0, LF_ERR_REJECT):
+            raise LfError(rc, "lf_mlsumcheck_verify")
+        return rc == 0, point, (exp if rc == 0 else int(exp[0]))
+
+    @staticmethod
+    def extract_sum(msgs):
+        """MLSumcheck::extract_sum (utils/sumcheck.rs:46-48): the claimed sum a proof is about, p_1(0) + p_1(1)"""
+        m = np.asarray(msgs, dtype=np.uint64)
+        ring = {v: k for k, v in RING_WORDS.items()}[m.shape[-1]]
+        p = int(_lib().lf_ring_modulus(RING_IDS[ring]))
+        m = m.reshape(-1, m.shape[-1])
+        return ((m[0].astype(object) + m[1].astype(object)) % p).astype(np.uint64)
 
 
 class MLSumcheckFold:

@@ -188,8 +188,8 @@ int ccs_envelope(const lf_params *P) {
 }
 
 // ---- host-side verifier ------------------------------------------------------------------------------------------------------------
-int bb_verify_host(const lf_params *p, const uint32_t *S_off, const uint32_t *S_idx, const uint64_t *c, BbTranscript &tr, const uint64_t *acc,
-                   const uint64_t *cm_i, const uint64_t *proof, uint64_t *lcccs_out, int *failed_stage) {
+// the host ring with the default tables: what the context-free verifiers compute in
+static const BbHostRing &default_host_ring() {
     static const BbHostRing *ring = [] {
         BbHostRing *g = new BbHostRing();
         u64 nr, y[8 * TAU];
@@ -197,7 +197,15 @@ int bb_verify_host(const lf_params *p, const uint32_t *S_off, const uint32_t *S_
         bb_build_tables(nr, y, g->T);
         return g;
     }();
-    const BbV bv{*ring};
+    return *ring;
+}
+int bb_mlsumcheck_verify(BbTranscript &tr, uint32_t nvars, uint32_t degree, const uint64_t *claimed_sum, const uint64_t *msgs, uint64_t *point_out,
+                         uint64_t *expected_out) {
+    return lfv::mlsumcheck_verify(BbV{default_host_ring()}, tr, nvars, degree, claimed_sum, msgs, point_out, expected_out);
+}
+int bb_verify_host(const lf_params *p, const uint32_t *S_off, const uint32_t *S_idx, const uint64_t *c, BbTranscript &tr, const uint64_t *acc,
+                   const uint64_t *cm_i, const uint64_t *proof, uint64_t *lcccs_out, int *failed_stage) {
+    const BbV bv{default_host_ring()};
     lfv::Verifier<BbV> V(bv, *p, S_off, S_idx, c);
     int rc = V.verify(tr, acc, cm_i, proof, lcccs_out);
     if (failed_stage) *failed_stage = V.stage;

@@ -36,6 +36,9 @@ struct BbCtx {
 };
 
 int ccs_envelope(const lf_params *p);   // the limits of lf_ccs_load on this ring: LF_OK or LF_ERR_UNSUPPORTED
+// lf_mlsumcheck_verify on this ring (lf_capi.cpp checked the arguments)
+int bb_mlsumcheck_verify(BbTranscript &tr, uint32_t nvars, uint32_t degree, const uint64_t *claimed_sum, const uint64_t *msgs, uint64_t *point_out,
+                         uint64_t *expected_out);
 int bb_verify_host(const lf_params *p, const uint32_t *S_off, const uint32_t *S_idx, const uint64_t *c, BbTranscript &tr, const uint64_t *acc,
                    const uint64_t *cm_i, const uint64_t *proof, uint64_t *lcccs_out, int *failed_stage);
 

@@ -1159,6 +1159,17 @@ int lf_last_kernel_stats(lf_ctx *c, float *fold_ms, int *fold_n, float *aj_ms, i
 }
 
 // ---- host-side verifier ---------------------------------------------------------------------------------------
+// the host ring with the default tables: what the context-free verifiers compute in
+static const HostRing &default_host_ring() {
+    static const HostRing *hr = [] {
+        HostRing *g = new HostRing();
+        u64 nr, y[24];
+        default_ring(&nr, y);
+        build_crt_tables(nr, y, g->T);
+        return g;
+    }();
+    return *hr;
+}
 int lf_verify_host(int ring, const lf_params *p, const uint32_t *S_off, const uint32_t *S_idx, const uint64_t *c, lf_transcript *t,
                    const uint64_t *acc, const uint64_t *cm_i, const uint64_t *proof, uint64_t *lcccs_out, int *failed_stage) {
     if (!p || !S_off || !S_idx || !c || !t || !acc || !cm_i || !proof || !lcccs_out) return LF_ERR_INVALID;
@@ -1167,17 +1178,20 @@ int lf_verify_host(int ring, const lf_params *p, const uint32_t *S_off, const ui
     if (failed_stage) *failed_stage = 0;
     if (ring == LF_RING_BABYBEAR) return t->bb ? lfbb::bb_verify_host(p, S_off, S_idx, c, *t->bb, acc, cm_i, proof, lcccs_out, failed_stage) : LF_ERR_INVALID;
     if (ring != LF_RING_GOLDILOCKS || t->bb) return LF_ERR_INVALID;
-    static const HostRing *hr = [] {
-        HostRing *g = new HostRing();
-        u64 nr, y[24];
-        default_ring(&nr, y);
-        build_crt_tables(nr, y, g->T);
-        return g;
-    }();
-    const GoldV gv{*hr};
+    const GoldV gv{default_host_ring()};
     lfv::Verifier<GoldV> V(gv, *p, S_off, S_idx, c);
     int rc = V.verify(t->t, acc, cm_i, proof, lcccs_out);
     if (failed_stage) *failed_stage = V.stage;
     return rc;
 }
 
+// MLSumcheck::verify_as_subprotocol (utils/sumcheck.rs:84-104) on the host: lfv::sumcheck_verify, the body the NIFS verifier runs its two sumchecks through
+int lf_mlsumcheck_verify(int ring, lf_transcript *t, uint32_t nvars, uint32_t degree, const uint64_t *claimed_sum, const uint64_t *msgs, uint64_t *point_out,
+                         uint64_t *expected_out) {
+    if (!t || !claimed_sum || !msgs || !point_out || !expected_out) return LF_ERR_INVALID;
+    if (ring != LF_RING_GOLDILOCKS && ring != LF_RING_BABYBEAR) return LF_ERR_INVALID;
+    if ((ring == LF_RING_BABYBEAR) != (t->bb != nullptr)) return LF_ERR_INVALID;
+    if (nvars < 1 || nvars > lfml::MAX_NVARS || degree < 1 || degree > lfml::MAX_DEGREE) return LF_ERR_UNSUPPORTED;
+    if (ring == LF_RING_BABYBEAR) return lfbb::bb_mlsumcheck_verify(*t->bb, nvars, degree, claimed_sum, msgs, point_out, expected_out);
+    return lfv::mlsumcheck_verify(GoldV{default_host_ring()}, t->t, nvars, degree, claimed_sum, msgs, point_out, expected_out);
+}

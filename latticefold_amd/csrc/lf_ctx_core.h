@@ -13,6 +13,7 @@
 
 #include "../../include/lfhip.h"
 #include "lf_common.h"
+#include "lf_mlsumcheck.h"
 
 struct lf_witness;
 
@@ -47,6 +48,12 @@ struct CtxCoreBase {
     size_t sc_n = 0;
     int sf_round = -1, sf_cur = 0;
     size_t sf_n = 0;
+    // the generic sumcheck (lf_mlsumcheck_*), a state of its own with buffers of its own (ml_*): rounds done (-1: none active), the buffer the current tables
+    // are in, their length, and the copied descriptor as the round kernel takes it
+    int ml_round = -1, ml_cur = 0;
+    size_t ml_n = 0;
+    uint32_t ml_nvars = 0, ml_T = 0;
+    lfml::Desc ml_desc{};
     // v_s of the linearized instance computed inside the linearization (v = sum_k 2^k v_s[k]); reused by the right decomposition of the same fold step
     const lf_witness *vs_wit = nullptr;
     bool vs_keep = false;            // set by the fold step around its linearization: only there the decomposition that follows uses the same point

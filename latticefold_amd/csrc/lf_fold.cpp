@@ -708,6 +708,41 @@ int lf_sumcheck_lin_end(lf_ctx *c) {
     return c->bb ? ring_ops<BbRing>::sumcheck_lin_end(c->bb->p) : ring_ops<GoldRing>::sumcheck_lin_end(c);
 }
 
+// ---- the generic sumcheck (include/lfhip_sumcheck.h): argument checks and ring dispatch; bodies in lf_ring_host.h (mlsumcheck_*), kernel lf_mlsumcheck.hip ----
+static int mlsumcheck_begin_api(lf_ctx *c, const lf_vpoly *vp, const uint64_t *tables, Origin org) {
+    if (!c || !vp || !tables || !vp->term_off || !vp->term_idx || !vp->coef) return LF_ERR_INVALID;
+    return c->bb ? ring_ops<BbRing>::mlsumcheck_begin(c->bb->p, vp, tables, org) : ring_ops<GoldRing>::mlsumcheck_begin(c, vp, tables, org);
+}
+int lf_mlsumcheck_begin(lf_ctx *c, const lf_vpoly *vp, const uint64_t *tables) { return mlsumcheck_begin_api(c, vp, tables, Origin::host); }
+int lf_mlsumcheck_begin_device(lf_ctx *c, const lf_vpoly *vp, const uint64_t *tables) { return mlsumcheck_begin_api(c, vp, tables, Origin::device); }
+int lf_mlsumcheck_round(lf_ctx *c, const uint64_t *r_prev, uint64_t *evals_out) {
+    if (!c || !evals_out) return LF_ERR_INVALID;
+    return c->bb ? ring_ops<BbRing>::mlsumcheck_round(c->bb->p, r_prev, evals_out) : ring_ops<GoldRing>::mlsumcheck_round(c, r_prev, evals_out);
+}
+int lf_mlsumcheck_final(lf_ctx *c, const uint64_t *r_last, uint64_t *evals_out) {
+    if (!c || !r_last || !evals_out) return LF_ERR_INVALID;
+    return c->bb ? ring_ops<BbRing>::mlsumcheck_final(c->bb->p, r_last, evals_out) : ring_ops<GoldRing>::mlsumcheck_final(c, r_last, evals_out);
+}
+int lf_mlsumcheck_end(lf_ctx *c) {
+    if (!c) return LF_ERR_INVALID;
+    return c->bb ? ring_ops<BbRing>::mlsumcheck_end(c->bb->p) : ring_ops<GoldRing>::mlsumcheck_end(c);
+}
+// MLSumcheck::prove_as_subprotocol: the round loop with the transcript is ring_ops::mlsumcheck_prove, one body over the split form for both origins
+static int mlsumcheck_prove_api(lf_ctx *c, lf_transcript *t, const lf_vpoly *vp, const uint64_t *tables, uint64_t *msgs_out, uint64_t *point_out, uint64_t *final_out,
+                                Origin org) {
+    if (!c || !t || !vp || !tables || !msgs_out || !point_out || !vp->term_off || !vp->term_idx || !vp->coef || (c->bb != nullptr) != (t->bb != nullptr))
+        return LF_ERR_INVALID;
+    return c->bb ? ring_ops<BbRing>::mlsumcheck_prove(c->bb->p, *t->bb, vp, tables, msgs_out, point_out, final_out, org)
+                 : ring_ops<GoldRing>::mlsumcheck_prove(c, t->t, vp, tables, msgs_out, point_out, final_out, org);
+}
+int lf_mlsumcheck_prove(lf_ctx *c, lf_transcript *t, const lf_vpoly *vp, const uint64_t *tables, uint64_t *msgs_out, uint64_t *point_out, uint64_t *final_out) {
+    return mlsumcheck_prove_api(c, t, vp, tables, msgs_out, point_out, final_out, Origin::host);
+}
+int lf_mlsumcheck_prove_device(lf_ctx *c, lf_transcript *t, const lf_vpoly *vp, const uint64_t *tables, uint64_t *msgs_out, uint64_t *point_out,
+                               uint64_t *final_out) {
+    return mlsumcheck_prove_api(c, t, vp, tables, msgs_out, point_out, final_out, Origin::device);
+}
+
 // PoseidonSponge on the device: a script of absorb / squeeze operations on a fresh sponge, one wave.  ops[i] =
 // (kind << 24) | count: kind 0 absorbs the next `count` words of absorb_words, kind 1 squeezes `count` words into squeezed_out.
 // state_out (optional, 26 words): the 24 state words, the rate index and the mode (1 = squeezing) afterwards.

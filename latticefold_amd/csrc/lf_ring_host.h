@@ -28,6 +28,7 @@
 #include "lf_check.h"
 #include "lf_ctx.h"
 #include "lf_dev_ptr.h"
+#include "lf_mlsumcheck.h"
 #include "lf_witness_parts.h"
 
 #pragma GCC visibility push(hidden)
@@ -85,6 +86,10 @@ template <> struct Ring<lf_ctx> {
     static void fix(lf_ctx *c, const u64 *in, size_t ld_in, u64 *out, size_t ld_out, size_t n_in, u32 rows, const ExtC &r) {
         launch_fix_many(c->dcrt, in, ld_in, out, ld_out, n_in, rows, r, c->stream());
     }
+    // the generic sumcheck (lf_mlsumcheck.h): points a block of its round kernel evaluates; the last fix of `rows` extension-field rows of two entries
+    // (leading dimension 2) -> canonical words [rows][TAU]
+    static constexpr u32 ml_pts = lfml::PTS_GOLD;
+    static void fix_final(lf_ctx *c, const u64 *in, size_t, u32 rows, const ExtC &r, u64 *out) { launch_fix_final(c->dcrt, in, rows, r, out, c->stream()); }
     // one row of A (NTT form [RE][cnt]) -> row i of a row chunk of the byte planes: inverse CRT and packing fused
     static int pack_row(lf_ctx *c, const u64 *row, size_t cnt, u32 i, u32 MT, unsigned char *Ab) {
         launch_ajtai_icrt_pack_i8(c->d_icrt, row, cnt, i, MT, Ab, c->stream());
@@ -128,6 +133,8 @@ template <> struct Ring<BbCtxImpl> {
     static void fix(BbCtxImpl *c, const fe *in, size_t ld_in, fe *out, size_t ld_out, size_t n_in, u32 rows, const ExtC &r) {
         launch_fix(c->dev, in, ld_in, out, ld_out, n_in, rows, r, c->stream());
     }
+    static constexpr u32 ml_pts = lfml::PTS_BB;
+    static void fix_final(BbCtxImpl *c, const fe *in, size_t ld_in, u32 rows, const ExtC &r, u64 *out) { launch_fix_final(c->dev, in, ld_in, rows, r, out, c->stream()); }
     static int pack_row(BbCtxImpl *c, const fe *row, size_t cnt, u32 i, u32 MT, unsigned char *Ab) {   // inverse CRT -> canonical element-major words -> bytes
         const AjtaiI8Ring I = i8();
         fe *coef;
@@ -879,6 +886,139 @@ struct ring_ops<Ring<C>> {
         c->sc_round = -1;
         return LF_OK;
     }
+    // ---- the generic sumcheck (lf_mlsumcheck_*, lfhip_sumcheck.h): MLSumcheck::prove_as_subprotocol over any sum of products of MLE tables, split at the
+    // transcript like the two above but with a state (ml_*) and buffers (ml_*) of its own; the round kernel is lf_mlsumcheck.hip, the fix between rounds R::fix
+    // on the T tables, ping-pong between ml_tab0 and ml_tab1 ----
+    // The descriptor's own checks, before the context is looked at: LF_ERR_INVALID first (on what the envelope lets us walk), then the envelope.  *d: the copy
+    // the kernel takes, offsets relative to term_off[0], the class of every coefficient per slot
+    static int ml_describe(const lf_vpoly *vp, lfml::Desc *d) {
+        const u32 q = vp->nterms, T = vp->ntables;
+        const bool q_ok = q >= 1 && q <= lfml::MAX_TERMS;
+        bool walk = q_ok;   // term_idx can be walked: the offsets increase and span at most MAX_IDX factors
+        if (q_ok) {
+            for (u32 i = 0; i < q; i++)
+                if (vp->term_off[i + 1] <= vp->term_off[i]) return LF_ERR_INVALID;
+            walk = vp->term_off[q] <= lfml::MAX_IDX;
+            if (walk)
+                for (u32 k = vp->term_off[0]; k < vp->term_off[q]; k++)
+                    if (vp->term_idx[k] >= T) return LF_ERR_INVALID;
+            for (size_t w = 0; w < (size_t)q * RE; w++)
+                if (vp->coef[w] >= R::modulus) return LF_ERR_INVALID;
+        }
+        if (vp->nvars < 1 || vp->nvars > lfml::MAX_NVARS || T < 1 || T > lfml::MAX_TABLES || !walk || vp->degree > lfml::MAX_DEGREE) return LF_ERR_UNSUPPORTED;
+        u32 widest = 0;
+        for (u32 i = 0; i < q; i++) widest = std::max(widest, vp->term_off[i + 1] - vp->term_off[i]);
+        if (widest > lfml::MAX_FACTORS || vp->degree < widest) return LF_ERR_UNSUPPORTED;
+        *d = lfml::Desc{};
+        d->q = q; d->npts = vp->degree + 1;
+        const u32 k0 = vp->term_off[0];
+        for (u32 i = 0; i <= q; i++) d->off[i] = vp->term_off[i] - k0;
+        for (u32 k = k0; k < vp->term_off[q]; k++) d->set_idx(k - k0, vp->term_idx[k]);
+        for (u32 i = 0; i < q; i++)
+            for (u32 s = 0; s < 8; s++) {
+                const u64 *w = vp->coef + (size_t)i * RE + s * TAU;
+                bool tail0 = true;
+                for (size_t x = 1; x < TAU; x++) tail0 = tail0 && w[x] == 0;
+                const u32 cls = !tail0 ? lfml::COEF_GENERAL : w[0] == 0 ? lfml::COEF_ZERO : w[0] == 1 ? lfml::COEF_ONE : w[0] == R::modulus - 1 ? lfml::COEF_MINUS_ONE : lfml::COEF_GENERAL;
+                d->cls[i] |= cls << (2 * s);
+            }
+        return LF_OK;
+    }
+    static size_t ml_ld(const C *c, size_t n) { return n == ((size_t)1 << c->ml_nvars) ? n : R::halved_ld(n); }
+    // the buffers of a generic sumcheck over T tables of m entries; allocation failure: LF_ERR_HIP
+    struct MlBufs { W *tab[2], *coef; Part *partial; u64 *out; };
+    static int ml_bufs(C *c, u32 T, size_t m, MlBufs *b) {
+        RET(c->tbuf("ml_tab0", (size_t)T * RE * m, &b->tab[0]));
+        RET(c->tbuf("ml_tab1", (size_t)T * RE * R::halved_ld(m / 2), &b->tab[1]));
+        RET(c->tbuf("ml_coef", (size_t)lfml::MAX_TERMS * RE, &b->coef));
+        RET(c->tbuf("ml_partial", lfml::partial_words(R::ml_pts, RE), &b->partial));
+        return c->tbuf("ml_out", (size_t)lfml::MAX_TABLES * RE, &b->out);   // (a message is at most 9 elements, the final values at most 16)
+    }
+    static int mlsumcheck_begin(C *c, const lf_vpoly *vp, const u64 *tables, Origin org = Origin::host) {
+        lfml::Desc d;
+        RET(ml_describe(vp, &d));
+        const u32 T = vp->ntables;
+        const size_t m = (size_t)1 << vp->nvars;
+        std::lock_guard<std::mutex> g(c->mu);
+        if (c->sh_world > 1 || c->xb_on) return LF_ERR_UNSUPPORTED;   // out of scope: one GPU, the default basis
+        if (org == Origin::host)
+            for (size_t w = 0, nw = (size_t)T * m * RE; w < nw; w++)
+                if (tables[w] >= R::modulus) return LF_ERR_INVALID;
+        HIPCHK(hipSetDevice(c->device));
+        DevIo<C> io(c, org);
+        RET(io.array(tables, (size_t)T * m));
+        c->ml_round = -1;   // from here on the buffers of a sumcheck in progress are rewritten: a new one is active only once everything below went through
+        MlBufs b;
+        RET(ml_bufs(c, T, m, &b));
+        RET(io.begin());
+        for (u32 j = 0; j < T; j++) RET(up_ring(io, tables + (size_t)j * m * RE, m, b.tab[0] + (size_t)j * RE * m, Form::ntt));
+        std::vector<W> hc((size_t)lfml::MAX_TERMS * RE, W(0));
+        for (size_t w = 0; w < (size_t)vp->nterms * RE; w++) hc[w] = R::from_canon(vp->coef[w]);
+        RET(R::h2d_consts(c, b.coef, hc.data(), hc.size() * sizeof(W)));
+        if (io.dev) RET(io.finish());
+        else HIPCHK(hipStreamSynchronize(c->stream()));   // the caller's arrays are free again on return
+        c->ml_desc = d;
+        c->ml_nvars = vp->nvars; c->ml_T = T;
+        c->ml_round = 0; c->ml_n = m; c->ml_cur = 0;
+        return LF_OK;
+    }
+    static int mlsumcheck_round(C *c, const u64 *r_prev, u64 *evals_out) {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (c->ml_round < 0 || c->ml_round >= (int)c->ml_nvars) return LF_ERR_STATE;   // "Prover is not active"
+        if ((c->ml_round == 0) != (r_prev == nullptr)) return LF_ERR_STATE;           // "first round should be prover first" / "verifier message is empty"
+        HIPCHK(hipSetDevice(c->device));
+        const u32 T = c->ml_T;
+        MlBufs b;
+        RET(ml_bufs(c, T, (size_t)1 << c->ml_nvars, &b));
+        if (r_prev) {
+            const ExtC r = R::ext_const(c, R::ext_load(r_prev));
+            const int src = c->ml_cur, dst = src ^ 1;
+            R::fix(c, b.tab[src], ml_ld(c, c->ml_n), b.tab[dst], R::halved_ld(c->ml_n / 2), c->ml_n, T * 8, r);
+            c->ml_cur = dst; c->ml_n /= 2;
+        }
+        if (lfml::launch_mls_round(R::tab(c), c->ml_desc, b.tab[c->ml_cur], ml_ld(c, c->ml_n), c->ml_n / 2, b.coef, b.partial, b.out, c->stream()) != 0) return LF_ERR_HIP;
+        c->ml_round++;
+        return down_small(c, b.out, (size_t)c->ml_desc.npts * RE, evals_out);
+    }
+    // after the last round: the last fix, every table's value at the whole point (canonical words, T ring elements)
+    static int mlsumcheck_final(C *c, const u64 *r_last, u64 *evals_out) {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (c->ml_round < 0 || c->ml_round != (int)c->ml_nvars) return LF_ERR_STATE;
+        HIPCHK(hipSetDevice(c->device));
+        const u32 T = c->ml_T;
+        MlBufs b;
+        RET(ml_bufs(c, T, (size_t)1 << c->ml_nvars, &b));
+        const ExtC r = R::ext_const(c, R::ext_load(r_last));
+        R::fix_final(c, b.tab[c->ml_cur], ml_ld(c, c->ml_n), T * 8, r, b.out);   // (two entries are left: the leading dimension is 2 on both rings)
+        return down_small(c, b.out, (size_t)T * RE, evals_out);
+    }
+    static int mlsumcheck_end(C *c) {
+        std::lock_guard<std::mutex> g(c->mu);
+        c->ml_round = -1;
+        return LF_OK;
+    }
+    // prove_as_subprotocol (utils/sumcheck.rs:53-80): the loop over the split form with the transcript steps of lf_step_host.h.  Everything begin refuses is
+    // refused before the first absorb
+    static int mlsumcheck_prove(C *c, typename R::Host::Tr &tr, const lf_vpoly *vp, const u64 *tables, u64 *msgs_out, u64 *point_out, u64 *final_out, Origin org) {
+        typedef typename R::Host V;
+        RET(mlsumcheck_begin(c, vp, tables, org));
+        lfs::sumcheck_prologue<V>(tr, vp->nvars, vp->degree);
+        const u32 npts = vp->degree + 1;
+        const u64 *r_prev = nullptr;
+        int rc = LF_OK;
+        for (u32 i = 0; i < vp->nvars && rc == LF_OK; i++) {
+            u64 *ev = msgs_out + (size_t)i * npts * RE, rw[RE];
+            rc = mlsumcheck_round(c, r_prev, ev);
+            if (rc != LF_OK) break;
+            V::from_ext(lfs::sumcheck_round<V>(tr, ev, npts), rw);   // the challenge as a ring element: every slot carries its tau words
+            memcpy(point_out + (size_t)i * TAU, rw, TAU * 8);
+            r_prev = point_out + (size_t)i * TAU;
+        }
+        if (rc == LF_OK && final_out) rc = mlsumcheck_final(c, r_prev, final_out);
+        mlsumcheck_end(c);
+        return rc;
+    }
+
     // The folding sumcheck with the comb function of nifs/folding/utils.rs:273-325.  `tables` is the reference's mle list of create_sumcheck_polynomial
     // (folding/utils.rs:200-259): [eq(r_L), G_L, eq(r_R), G_R, eq(beta), f-hat_{0,0} .. f-hat_{2K-1,tau-1}], 5 + 2K*tau tables of m ring elements; the three eq
     // tables must be slot-constant (they are diagonal embeddings in the reference).  On the device: T = [eqL, eqR, eqB (tau planes each), G_L, G_R (RE planes each)]

@@ -16,6 +16,72 @@ namespace lfv {
 typedef uint64_t u64;
 typedef uint32_t u32;
 
+// ---- MLSumcheck::verify_as_subprotocol (utils/sumcheck.rs:84-104) on its own: what the NIFS verifier below and lf_mlsumcheck_verify (lfhip_sumcheck.h) share ----
+// Lagrange interpolation through (0, p_0), .., (len-1, p_{len-1}) evaluated at `at` (ring elements, slot-constant weights): interpolate_uni_poly
+// (utils/sumcheck/verifier.rs:139-257)
+template <class V>
+void interpolate_uni_poly(const V &v, const u64 *p_i, u32 len, typename V::Ext at, u64 *out) {
+    typedef typename V::Ext Ext;
+    constexpr int RE = V::RE;
+    u64 res[RE] = {0}, t[RE];
+    for (u32 i = 0; i < len; i++) {
+        Ext num = v.ext_from_u64(1), den = num;
+        for (u32 j = 0; j < len; j++) {
+            if (j == i) continue;
+            num = v.ext_mul(num, v.ext_sub(at, v.ext_from_u64(j)));
+            den = v.ext_mul(den, v.ext_sub(v.ext_from_u64(i), v.ext_from_u64(j)));
+        }
+        Ext w = v.ext_mul(num, v.ext_inv(den));
+        v.mul_ext(p_i + (size_t)i * RE, w, t);
+        v.add(res, t, res);
+    }
+    memcpy(out, res, sizeof(res));
+}
+// The transcript runs over ALL rounds first (the reference's verifier absorbs and samples per round and checks at the end, verifier.rs:56-121); then the
+// round checks p(0) + p(1) == expected.  false on a failed check: *failed_round (optional) = its index, expected_out untouched
+template <class V>
+bool sumcheck_verify(const V &v, typename V::Tr &tr, u32 nv, u32 degree, const u64 *claimed, const u64 *msgs, std::vector<typename V::Ext> &point,
+                     u64 *expected_out, u32 *failed_round = nullptr) {
+    constexpr int RE = V::RE;
+    lfs::sumcheck_prologue<V>(tr, nv, degree);
+    point.resize(nv);
+    for (u32 i = 0; i < nv; i++) point[i] = lfs::sumcheck_round<V>(tr, msgs + (size_t)i * (degree + 1) * RE, degree + 1);
+    u64 expected[RE], s[RE];
+    memcpy(expected, claimed, sizeof(expected));
+    for (u32 i = 0; i < nv; i++) {
+        const u64 *ev = msgs + (size_t)i * (degree + 1) * RE;
+        v.add(ev, ev + RE, s);
+        if (memcmp(s, expected, sizeof(s))) {
+            if (failed_round) *failed_round = i;
+            return false;
+        }
+        interpolate_uni_poly(v, ev, degree + 1, point[i], expected);
+    }
+    memcpy(expected_out, expected, sizeof(expected));
+    return true;
+}
+
+// lf_mlsumcheck_verify after its argument checks, for either ring: a word >= p in the claim or the messages -> LF_ERR_INVALID (before the transcript is
+// touched); LF_OK with the point (tau words per challenge) and the expected evaluation, or LF_ERR_REJECT with expected_out[0] = the failing round
+template <class V>
+int mlsumcheck_verify(const V &v, typename V::Tr &tr, u32 nv, u32 degree, const u64 *claimed, const u64 *msgs, u64 *point_out, u64 *expected_out) {
+    constexpr int RE = V::RE, TAU = V::TAU;
+    for (int w = 0; w < RE; w++)
+        if (claimed[w] >= V::modulus()) return LF_ERR_INVALID;
+    for (size_t w = 0, nw = (size_t)nv * (degree + 1) * RE; w < nw; w++)
+        if (msgs[w] >= V::modulus()) return LF_ERR_INVALID;
+    std::vector<typename V::Ext> pt;
+    u32 bad = 0;
+    const bool ok = sumcheck_verify(v, tr, nv, degree, claimed, msgs, pt, expected_out, &bad);
+    for (u32 i = 0; i < nv; i++) {
+        u64 rw[RE];
+        V::from_ext(pt[i], rw);
+        memcpy(point_out + (size_t)i * TAU, rw, TAU * sizeof(u64));
+    }
+    if (!ok) { memset(expected_out, 0, RE * sizeof(u64)); expected_out[0] = bad; return LF_ERR_REJECT; }
+    return LF_OK;
+}
+
 template <class V>
 struct Verifier {
     typedef typename V::Ext Ext;
@@ -44,37 +110,9 @@ struct Verifier {
         }
         return res;
     }
-    // Lagrange interpolation through (0, p_0), .., (len-1, p_{len-1}) evaluated at `at` (ring elements, slot-constant weights)
-    void interpolate(const u64 *p_i, u32 len, Ext at, u64 *out) const {
-        u64 res[RE] = {0}, t[RE];
-        for (u32 i = 0; i < len; i++) {
-            Ext num = v.ext_from_u64(1), den = num;
-            for (u32 j = 0; j < len; j++) {
-                if (j == i) continue;
-                num = v.ext_mul(num, v.ext_sub(at, v.ext_from_u64(j)));
-                den = v.ext_mul(den, v.ext_sub(v.ext_from_u64(i), v.ext_from_u64(j)));
-            }
-            Ext w = v.ext_mul(num, v.ext_inv(den));
-            v.mul_ext(p_i + (size_t)i * RE, w, t);
-            v.add(res, t, res);
-        }
-        memcpy(out, res, sizeof(res));
-    }
     // verify_as_subprotocol: returns false on a failed round check
     bool sumcheck(Tr &tr, u32 nv, u32 degree, const u64 *claimed, const u64 *msgs, std::vector<Ext> &point, u64 *expected_out) const {
-        lfs::sumcheck_prologue<V>(tr, nv, degree);
-        point.resize(nv);
-        for (u32 i = 0; i < nv; i++) point[i] = lfs::sumcheck_round<V>(tr, msgs + (size_t)i * (degree + 1) * RE, degree + 1);
-        u64 expected[RE], s[RE];
-        memcpy(expected, claimed, sizeof(expected));
-        for (u32 i = 0; i < nv; i++) {
-            const u64 *ev = msgs + (size_t)i * (degree + 1) * RE;
-            v.add(ev, ev + RE, s);
-            if (memcmp(s, expected, sizeof(s))) return false;
-            interpolate(ev, degree + 1, point[i], expected);
-        }
-        memcpy(expected_out, expected, sizeof(expected));
-        return true;
+        return sumcheck_verify(v, tr, nv, degree, claimed, msgs, point, expected_out);
     }
     void write_point(const std::vector<Ext> &pt, u64 *o) const {
         for (size_t i = 0; i < pt.size(); i++) v.from_ext(pt[i], o + i * RE);

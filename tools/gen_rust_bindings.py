@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Generates the raw Rust binding of the C ABI (`latticefold-hip-sys/src/lib.rs`) from include/lfhip.h and include/lfplus.h, and its module `parts`
-(`src/parts.rs`) from include/lfhip_parts.h, the file lfhip.h includes for the entry points of the decomposed witnesses.
+"""Generates the raw Rust binding of the C ABI (`latticefold-hip-sys/src/lib.rs`) from include/lfhip.h and include/lfplus.h, and its modules `parts`
+(`src/parts.rs`) from include/lfhip_parts.h, the file lfhip.h includes for the entry points of the decomposed witnesses, and `sumcheck` (`src/sumcheck.rs`)
+from include/lfhip_sumcheck.h, the one for the generic sumcheck.
 
     python tools/gen_rust_bindings.py            print the binding
     python tools/gen_rust_bindings.py --write    rewrite bindings/latticefold-hip-sys/src/lib.rs and the block between the
-                                                 GENERATED markers of INTEGRATION.md; the same for src/parts.rs and its markers
+                                                 GENERATED markers of INTEGRATION.md; the same for src/parts.rs, src/sumcheck.rs and their markers
 
 The reference is safe Rust with `#![forbid(unsafe_code)]` (crates/latticefold/src/lib.rs:4): the `extern "C"` block lives in a new
 `-sys` crate.  No Rust toolchain exists in the build image, so the text is derived mechanically from the headers (every prototype, the
@@ -22,6 +23,9 @@ BEGIN, END = "<!-- BEGIN GENERATED BINDING (tools/gen_rust_bindings.py) -->", "<
 PARTS_HEADER = "include/lfhip_parts.h"
 PARTS_OUT = os.path.join(ROOT, "bindings", "latticefold-hip-sys", "src", "parts.rs")
 PARTS_BEGIN, PARTS_END = "<!-- BEGIN GENERATED BINDING: parts (tools/gen_rust_bindings.py) -->", "<!-- END GENERATED BINDING: parts -->"
+SUMCHECK_HEADER = "include/lfhip_sumcheck.h"
+SUMCHECK_OUT = os.path.join(ROOT, "bindings", "latticefold-hip-sys", "src", "sumcheck.rs")
+SUMCHECK_BEGIN, SUMCHECK_END = "<!-- BEGIN GENERATED BINDING: sumcheck (tools/gen_rust_bindings.py) -->", "<!-- END GENERATED BINDING: sumcheck -->"
 
 SCALARS = {
     "int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "char": "c_char", "float": "f32", "double": "f64", "void": "c_void",
@@ -53,7 +57,7 @@ def rust_type(ctype):
     name = " ".join(base)
     if name in SCALARS:
         r = SCALARS[name]
-    elif name in OPAQUE or name in ("lf_params", "lfplus_params"):
+    elif name in OPAQUE or name in ("lf_params", "lfplus_params", "lf_vpoly"):
         r = name
     elif name in ("lf_exchange_fn", "lfplus_exchange_fn"):
         r = "lf_exchange_fn"
@@ -74,11 +78,11 @@ def split_params(s):
     for i, p in enumerate(x.strip() for x in s.split(",")):
         m = re.match(r"^(.*?)([A-Za-z_][A-Za-z_0-9]*)?$", p)
         ctype, name = m.group(1).strip(), m.group(2)
-        if name in SCALARS or name in OPAQUE or name in ("lf_params", "lfplus_params", "lf_exchange_fn", "lfplus_exchange_fn", "unsigned", "const") or not ctype:   # unnamed parameter
+        if name in SCALARS or name in OPAQUE or name in ("lf_params", "lfplus_params", "lf_vpoly", "lf_exchange_fn", "lfplus_exchange_fn", "unsigned", "const") or not ctype:   # unnamed parameter
             ctype, name = p, None
         if name is None:
             base = re.findall(r"[A-Za-z_][A-Za-z_0-9]*", ctype)[-1]
-            name = {"lf_ctx": "ctx", "lf_transcript": "t", "lf_witness": "w", "lf_params": "p", "lfplus_ctx": "ctx", "lfplus_prover": "prover"}.get(base, f"a{i}")
+            name = {"lf_ctx": "ctx", "lf_transcript": "t", "lf_witness": "w", "lf_params": "p", "lf_vpoly": "poly", "lfplus_ctx": "ctx", "lfplus_prover": "prover"}.get(base, f"a{i}")
         out.append((KEYWORDS.get(name, name), rust_type(ctype)))
     return out
 
@@ -143,7 +147,9 @@ def generate():
             L.append(f"    pub fn {name}({ps})" + (f" -> {ret}" if ret else "") + ";")
             allfns.append(name)
         L += ["}", ""]
-    L += ["/// include/lfhip_parts.h (included by lfhip.h): the decomposed witnesses as handles -- `parts::lf_witness_decompose`, ...", "pub mod parts;", ""]
+    L += ["/// include/lfhip_parts.h (included by lfhip.h): the decomposed witnesses as handles -- `parts::lf_witness_decompose`, ...", "pub mod parts;",
+          "/// include/lfhip_sumcheck.h (included by lfhip.h): MLSumcheck over any sum of products of MLE tables -- `sumcheck::lf_mlsumcheck_prove`, ...",
+          "pub mod sumcheck;", ""]
     return "\n".join(L), allfns
 
 
@@ -154,6 +160,24 @@ def generate_parts():
          "// Module `parts` of latticefold-hip-sys: the decomposed witnesses of LFDecompositionProver / LFFoldingProver as device handles.",
          "use core::ffi::{c_int, c_uint};", "",
          "use super::{lf_ctx, lf_transcript, lf_witness};", "",
+         '#[link(name = "lfhip")]', 'extern "C" {']
+    for name, params, ret in fns:
+        ps = ", ".join(f"{n}: {t}" for n, t in params)
+        L.append(f"    pub fn {name}({ps})" + (f" -> {ret}" if ret else "") + ";")
+    L += ["}", ""]
+    return "\n".join(L), [f[0] for f in fns]
+
+
+def generate_sumcheck():
+    """src/sumcheck.rs: the descriptor and the entry points of include/lfhip_sumcheck.h, over the types of the crate root"""
+    _, fns = parse(SUMCHECK_HEADER)
+    L = [f"// GENERATED by tools/gen_rust_bindings.py from {SUMCHECK_HEADER} -- do not edit.",
+         "// Module `sumcheck` of latticefold-hip-sys: MLSumcheck::prove_as_subprotocol / verify_as_subprotocol over any sum of products of MLE tables.",
+         "use core::ffi::c_int;", "",
+         "use super::{lf_ctx, lf_transcript};", "",
+         "/// VirtualPolynomial as a flat product list (utils/sumcheck/utils.rs:24-75): g = sum_i coef_i prod_{k in [term_off[i], term_off[i+1])} T_{term_idx[k]}",
+         "#[repr(C)] #[derive(Clone, Copy, Debug)]",
+         "pub struct lf_vpoly { pub nvars: u32, pub ntables: u32, pub nterms: u32, pub degree: u32, pub term_off: *const u32, pub term_idx: *const u32, pub coef: *const u64 }", "",
          '#[link(name = "lfhip")]', 'extern "C" {']
     for name, params, ret in fns:
         ps = ", ".join(f"{n}: {t}" for n, t in params)
@@ -179,10 +203,18 @@ def main():
             a, b = doc.index(PARTS_BEGIN) + len(PARTS_BEGIN), doc.index(PARTS_END)
             open(DOC, "w").write(doc[:a] + "\n```rust\n" + ptext + "```\n" + doc[b:])
         print(f"{len(pfns)} functions -> {os.path.relpath(PARTS_OUT, ROOT)}")
+        stext, sfns = generate_sumcheck()
+        open(SUMCHECK_OUT, "w").write(stext)
+        doc = open(DOC).read()
+        if SUMCHECK_BEGIN in doc and SUMCHECK_END in doc:
+            a, b = doc.index(SUMCHECK_BEGIN) + len(SUMCHECK_BEGIN), doc.index(SUMCHECK_END)
+            open(DOC, "w").write(doc[:a] + "\n```rust\n" + stext + "```\n" + doc[b:])
+        print(f"{len(sfns)} functions -> {os.path.relpath(SUMCHECK_OUT, ROOT)}")
         print(f"{len(fns)} functions -> {os.path.relpath(OUT, ROOT)}" + (", INTEGRATION.md" if BEGIN in doc else ""))
     else:
         sys.stdout.write(text)
         sys.stdout.write(generate_parts()[0])
+        sys.stdout.write(generate_sumcheck()[0])
 
 
 if __name__ == "__main__":
