@@ -37,6 +37,8 @@ u64 hpow(u64 a, u64 e);
 inline u64 hinv(u64 a) { return hpow(a, BB_P - 2); }
 inline u64 hfrom_i64(int64_t v) { int64_t r = v % (int64_t)BB_P; return (u64)(r < 0 ? r + (int64_t)BB_P : r); }
 
+// inverse in F_p[Y]/(Y^9 - nu): solve (multiplication by a) x = 1 by Gaussian elimination on the 9 x 9 matrix M[i][j] = [Y^i](a Y^j); false if a = 0
+bool h9_inv(const H9 &a, u64 nu, H9 *out);
 struct BbHostRing {
     BbTables T;
     H9 mul9(const H9 &a, const H9 &b) const;
@@ -90,8 +92,6 @@ inline H9 h9_one() { H9 r = h9_zero(); r.c[0] = 1; return r; }
 inline H9 h9_sub(const H9 &a, const H9 &b) { H9 r; for (int i = 0; i < TAU; i++) r.c[i] = hsub(a.c[i], b.c[i]); return r; }
 inline H9 h9_add(const H9 &a, const H9 &b) { H9 r; for (int i = 0; i < TAU; i++) r.c[i] = hadd(a.c[i], b.c[i]); return r; }
 inline H9 h9_scale(const H9 &a, u64 k) { H9 r; for (int i = 0; i < TAU; i++) r.c[i] = hmul(a.c[i], k % BB_P); return r; }
-// inverse in F_p[Y]/(Y^9 - nu): solve (multiplication by a) x = 1 by Gaussian elimination on the 9 x 9 matrix M[i][j] = [Y^i](a Y^j); false if a = 0
-bool h9_inv(const H9 &a, u64 nu, H9 *out);
 
 // ---- host policy of lf_step_host.h / lf_verify.h on this ring: small inline functions over a host ring it REFERS to (a context's, or the default one) ------
 struct BbV {
@@ -117,6 +117,8 @@ struct BbV {
     static Ext ext_add(const Ext &a, const Ext &b) { return h9_add(a, b); }
     static Ext ext_sub(const Ext &a, const Ext &b) { return h9_sub(a, b); }
     Ext ext_inv(const Ext &a) const { Ext r; return h9_inv(a, ring.T.nu, &r) ? r : h9_zero(); }
+    static Ext ext_scale(const Ext &a, u64 k) { return h9_scale(a, k); }   // times a base-field word
+    static u64 finv(u64 a) { return hinv(a); }
     static void absorb_ext(Tr &tr, const Ext &e) { tr.absorb_h9_as_ring(e); }
     void crt(const u64 *c, u64 *o) const { ring.crt(c, o); }
     void icrt(const u64 *x, u64 *o) const { ring.icrt(x, o); }

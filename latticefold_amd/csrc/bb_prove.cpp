@@ -313,18 +313,66 @@ static int dec_finish(C *c, BbTranscript &tr, const u64 *lcccs, SideState &S, u6
     return LF_OK;
 }
 
-// LFFoldingProver::prove (nifs/folding.rs:42-130)
-static E9 e9_from_h9(const H9 &h) { E9 r; for (int i = 0; i < TAU; i++) r.c[i] = from_canon(h.c[i]); return r; }
-static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_witness **w_out, u64 *proof) {
+// ---- LFFoldingProver::prove (nifs/folding.rs:42-130) as stages over one state, the scheme of the Goldilocks driver (lf_fold.cpp) with this ring's launch
+// signatures and scratch shapes.  Stages: prepare (challenges; per side combine z, SpMV, f-hat combination; eq tables) -- per round: fix of the special tables
+// (with the hand-over of a sharded step), choice of the f-hat producer, split decision, kernel dispatch, collection of the message, completion, transcript --
+// evaluations (theta, eta) -- finish (rho, fold_witness, from_f, the folded instance).  The numeric host work is lf_step_host.h's, shared with that driver.
+struct BbFold {
+    C *c;
+    BbTranscript &tr;
+    SideState *S;   // [2]
+    u64 *proof;     // the s round messages, theta, eta
     const lf_params &P = c->P;
-    size_t m = c->m, n = c->n, N = c->N;
-    u32 K = P.K, K2 = 2 * K, deg = 2 * P.b;
-    size_t ll = lcccs_len(&P, TAU);
+    const size_t m = c->m, n = c->n, N = c->N;
+    const u32 K = P.K, K2 = 2 * K, deg = 2 * P.b;
     const u64 nu = c->ring.T.nu;
     const BbV hv{c->ring};
-    std::vector<H9> alpha, zeta, mu, beta;
-    // the bit-plane form of the two witnesses (GEMM rounds below) needs no challenge: built while the host squeezes alpha and zeta
-    u32 *svbits[2] = {nullptr, nullptr};
+    const size_t Gw = (size_t)c->sh_world, gr = (size_t)c->sh_rank;
+    std::vector<H9> alpha, zeta, mu, beta, pt = std::vector<H9>(P.s);
+    E9C *d_mu = nullptr, *d_ap = nullptr;
+    E9PreC *d_mup = nullptr, *d_zp = nullptr;
+    fe *G[2] = {nullptr, nullptr}, *eqb = nullptr, *zz = nullptr;
+    i64 *partial = nullptr;
+    u64 *od = nullptr;
+    u32 *svbits[2] = {nullptr, nullptr};   // bit-plane form of the two witnesses (GEMM rounds)
+    // switches of this step (rounds_begin)
+    bool fused = false, use_lut = false, use_r5 = false, use_sv = false, fr_split = false;
+    size_t sv_min = 0;
+    // what the round loop mutates
+    FoldArgs a;
+    fe *F[2] = {nullptr, nullptr}, *T5[2] = {nullptr, nullptr};   // ping-pong: the 2K*9 materialised f-hat tables, the 5 special tables (eqL eqR eqB G1 G2 = 171 planes)
+    const fe *curF = nullptr, *prevF = nullptr, *Er = nullptr;   // f-hat tables (null while virtual); the tables a fused fix reads; (split round) E_round
+    size_t ldF = 0, prevld = 0, ldEr = 0;
+    bool sharded = false, fix_fused = false, sv_done = false, split_now = false;
+    int flip = 0, lut_mode = 0;    // lut_mode: producer of this round's pairs: 3 / 4 digit look-up table (rounds 3 / 4), 7 round 5 from the planes; 0 with fix_fused: fused fix; else tables
+    fe *svE[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *d_lut = nullptr;   // E_i = eq((beta_{i+1}..beta_s), .): one value per pair of round i
+    u32 svE_level = 0;
+    lfs::SplitCoef<BbV> sp{};      // c_i = prod_{k<i} eq(beta_k, r_k), beta_i and their inverses of a split round
+    u64 *msg(u32 round) const { return proof + (size_t)(round - 1) * (deg + 1) * RE; }
+    u64 *theta() const { return proof + (size_t)P.s * (deg + 1) * RE; }
+    u64 *eta() const { return theta() + (size_t)K2 * TAU * RE; }
+    int svE_ensure(u32 level) {   // E_1 built, E_2.. pair sums (GEMM rounds and the split table rounds)
+        static const char *const names[5] = {"sv_E1", "sv_E2", "sv_E3", "sv_E4", "sv_E5"};
+        for (; svE_level < level && svE_level < 5; svE_level++) {
+            const size_t ne = m >> (svE_level + 1);
+            RET(c->tbuf(names[svE_level], (size_t)TAU * atl(ne), &svE[svE_level]));
+            if (svE_level == 0) RET(build_eq_dev(c, beta.data() + 1, P.s - 1, svE[0]));
+            else launch_bb_eq_pairsum(svE[svE_level - 1], atl(m >> svE_level), ne, svE[svE_level], atl(ne), c->stream());
+        }
+        return LF_OK;
+    }
+    void set_tables(fe *dst, size_t nn) {
+        const size_t ldn = atl(nn);
+        a.eqL = dst; a.eqR = dst + (size_t)TAU * ldn; a.eqB = dst + (size_t)2 * TAU * ldn;
+        a.G1 = dst + (size_t)3 * TAU * ldn; a.G2 = dst + (size_t)(3 * TAU + RE) * ldn;
+        a.ld = ldn; a.n = nn;
+    }
+    int prepare(), rounds_begin(), fix_tables(u32 round, fe *dst, bool *gathered), choose_producer(u32 round), gemm_round(u32 round), decide_split(u32 round);
+    int dispatch(u32 round), rounds(), evaluations(), finish(u64 *lcccs_out, lf_witness **w_out);
+};
+
+int BbFold::prepare() {
+    // the bit-plane form of the two witnesses (GEMM rounds) needs no challenge: built while the host squeezes alpha and zeta
     {
         const size_t sv_min0 = c->tn.sv_min >= 65536 ? 16384 : c->tn.sv_min;
         if (c->sh_world == 1 && !c->tn.fold_no_sv && N <= m && (N & 3) == 0 && P.s >= 4 && c->tn.sv_rounds >= 1 && m / 2 >= sv_min0 && bbsv_shape_ok(1, m / 2, K))
@@ -344,13 +392,8 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
         lfs::powers(hv, alpha[i], TAU, [&](u32 d, const H9 &pw) { a_pow[(size_t)i * TAU + d] = e9c_from_h9(pw); });
         lfs::powers(hv, zeta[i], P.t, [&](u32 j, const H9 &pw) { z_pow[(size_t)i * P.t + j] = e9pre_from_h9(pw, nu); });
     }
-    E9C *d_mu, *d_ap;
-    E9PreC *d_mup, *d_zp;
     RET(upload_consts(c, "c_ap", a_pow, &d_ap));
     RET(upload_consts(c, "c_zp", z_pow, &d_zp));
-    fe *G[2], *eqb, *zz;
-    i64 *partial;
-    u64 *od;
     RET(c->tbuf("fold_G1", RE * m, &G[0]));
     RET(c->tbuf("fold_G2", RE * m, &G[1]));
     RET(c->tbuf("fold_eqb", TAU * m, &eqb));
@@ -360,16 +403,11 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
     if (!od) return LF_ERR_HIP;
     {
         // G = sum_j M_j (sum_k zeta_k^{j+1} z_k)  +  sum_k sum_d alpha_k^{d+1} fhat_{k,d}   (folding.rs:208-226, utils.rs:524-546): the two sides are
-        // independent chains -- the right one runs on the other (idle) stream, as in the Goldilocks driver
+        // independent chains -- the right one runs on the other (idle) stream
         hipStream_t s0 = c->stream(), s1 = (c->cur_lane == 0 && c->sh_world == 1) ? c->st_lane[1] : s0;
         fe *zz1 = zz;
-        if (s1 != s0) {
-            RET(c->tbuf("fold_zz1", (size_t)P.t * RE * n, &zz1));
-            for (int e = 0; e < 2; e++)
-                if (!c->ev_prep[e]) HIPCHK(hipEventCreateWithFlags(&c->ev_prep[e], hipEventDisableTiming));
-            HIPCHK(hipEventRecord(c->ev_prep[0], s0));           // the challenge powers were uploaded on s0
-            HIPCHK(hipStreamWaitEvent(s1, c->ev_prep[0], 0));
-        }
+        if (s1 != s0) RET(c->tbuf("fold_zz1", (size_t)P.t * RE * n, &zz1));
+        RET(c->fork(s0, s1));           // the challenge powers were uploaded on s0
         for (int sd = 0; sd < 2; sd++) {
             hipStream_t st = sd ? s1 : s0;
             fe *zb = sd ? zz1 : zz;
@@ -377,10 +415,7 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
             launch_spmv_sum(c->dev, P.t, c->d_rowptr.data(), c->d_col.data(), c->d_val.data(), zb, (size_t)RE * n, n, G[sd], m, st);
             launch_add_fhat_comb(c->dev, S[sd].planes, N, K, d_ap + (size_t)sd * K * TAU, G[sd], m, st);
         }
-        if (s1 != s0) {
-            HIPCHK(hipEventRecord(c->ev_prep[1], s1));
-            HIPCHK(hipStreamWaitEvent(s0, c->ev_prep[1], 0));
-        }
+        RET(c->join(s1, s0));
     }
     { HostTimer ht(c); lfs::draw_mu_beta<BbV>(tr, K2, P.s, mu, beta); }
     for (u32 i = 0; i < K2; i++)
@@ -394,288 +429,225 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
     RET(build_eq_dev(c, beta.data(), P.s, eqb));
     c->ev_end(ph);
     if (g_marks.on) { (void)hipStreamSynchronize(c->stream()); BB_MARK(" fold prepare (synced)"); }
-
-    ph = c->ev_begin(14);
-    u64 *msgs = proof;
-    std::vector<H9> pt(P.s);
-    { HostTimer ht(c); lfs::sumcheck_prologue<BbV>(tr, P.s, deg); }
-    // working tables (ping-pong): 5 special tables (eqL eqR eqB G1 G2 = 171 planes) + the 2K*9 materialised f-hat tables
-    const size_t T5P = 3 * TAU + 2 * RE;
-    fe *F[2], *T5[2];
-    RET(c->tbuf("fold_T0", T5P * atl(m / 2), &T5[0]));
-    RET(c->tbuf("fold_T1", T5P * atl(m / 4), &T5[1]));
-    FoldArgs a;
+    return LF_OK;
+}
+// the switches of the round loop and its working tables
+int BbFold::rounds_begin() {
+    RET(c->tbuf("fold_T0", (3 * TAU + 2 * RE) * atl(m / 2), &T5[0]));
+    RET(c->tbuf("fold_T1", (3 * TAU + 2 * RE) * atl(m / 4), &T5[1]));
     a.eqL = S[0].eq_r; a.eqR = S[1].eq_r; a.eqB = eqb; a.G1 = G[0]; a.G2 = G[1]; a.ld = m; a.n = m;
     a.p0 = 0; a.pcnt = m / 2; a.pF0 = 0;
-    const fe *curF = nullptr;
-    size_t ldF = 0;
-    int flip = 0;
-    // Sharded rounds (same scheme as the Goldilocks driver): rank g evaluates the pairs of its index slice (high bits:
-    // pairs (2j,2j+1) stay local, the f-hat tables exist only for that slice), the 5-element partial messages are all-gathered and
-    // added mod p, every rank runs the same transcript.  Below 64 pairs per rank the f-hat slices are gathered and the tail is replicated.
-    const size_t Gw = (size_t)c->sh_world, gr = (size_t)c->sh_rank;
-    bool sharded = Gw > 1;
-    // unsharded, rounds >= 4 with many entries: fix_variables of the f-hat tables is fused into the (ALU-bound) round kernel
-    const bool fused = Gw == 1 && !c->tn.fold_unfused;
-    const size_t fuse_min = c->tn.fuse_min;   // entries; tests lower it
-    const fe *prevF = nullptr;
-    size_t prevld = 0;
-    // rounds 3 and 4 of large unsharded instances never materialise the m/4-entry tables (k_fold_round modes 3 and 4)
-    const size_t lut_min = c->tn.lut_min;   // default 2^15
-    const bool use_lut = fused && P.s >= 4 && m / 4 >= lut_min && m / 4 >= 4 && !c->tn.fold_no_lut;
-    // round 5 on the planes as well (mode 7): round 4 then stores no tables.  From 2^18 rows on, like the Goldilocks driver
-    const bool use_r5 = use_lut && !c->tn.fold_no_r4tab && !c->tn.fold_no_r5tab && P.s >= 5 && (N & 3) == 0 && m / 32 >= c->tn.r5_min;
+    // Sharded rounds: rank g evaluates the pairs of its index slice (high bits: pairs (2j,2j+1) stay local, the f-hat tables exist only for that
+    // slice), the 5-element partial messages are all-gathered and added mod p, every rank runs the same transcript.  Below 64 pairs per rank the f-hat slices
+    // are gathered and the tail is replicated.
+    sharded = Gw > 1;
+    // unsharded, rounds >= 4 with many entries (fuse_min; tests lower it): fix_variables of the f-hat tables is fused into the (ALU-bound) round kernel
+    fused = Gw == 1 && !c->tn.fold_unfused;
+    // rounds 3 and 4 of large unsharded instances never materialise the m/4-entry tables (k_fold_round modes 3 and 4; lut_min: default 2^15)
+    use_lut = fused && P.s >= 4 && m / 4 >= c->tn.lut_min && m / 4 >= 4 && !c->tn.fold_no_lut;
+    // round 5 on the planes as well (mode 7): round 4 then stores no tables.  From 2^18 rows on
+    use_r5 = use_lut && !c->tn.fold_no_r4tab && !c->tn.fold_no_r5tab && P.s >= 5 && (N & 3) == 0 && m / 32 >= c->tn.r5_min;
     // f-hat is materialised after two rounds (m/4 entries, F[0]; round r > 3 writes its m/2^(r-1) entries to F[r odd ? 0 : 1]) -- or later: the
     // look-up-table rounds store their first tables in round 4 (m/8, F[1]), with round 5 on the planes too in round 5 (m/16, F[0])
     RET(c->tbuf("fold_F0", (size_t)K2 * TAU * RE * atl(use_lut ? m / 16 : m / 4), &F[0]));
     RET(c->tbuf("fold_F1", (size_t)K2 * TAU * RE * atl(use_r5 ? m / 32 : m / 8), &F[1]));
-    fe *d_lut = nullptr;
-    int lut_mode = 0;
     // Rounds 1..3 as exact int8 GEMMs on the matrix cores (bb_sv_rounds.hip: the norm part of the message from the bit-plane form of the witnesses, in the split
     // eq form; the G part from the round kernel run without tables).  Unsharded steps whose witness fills whole super-steps.
-    const bool use_sv = Gw == 1 && !c->tn.fold_no_sv && N <= m && (N & 3) == 0 && P.s >= 4;
-    const size_t sv_min = c->tn.sv_min >= 65536 ? 16384 : c->tn.sv_min;   // (the default threshold is the Goldilocks driver's; a BabyBear pair carries three times the rows)
-    // E_i = eq((beta_{i+1}..beta_s), .): one value per pair of round i; E_1 built, E_2.. pair sums (GEMM rounds and the split table rounds)
-    fe *svE[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    u32 svE_level = 0;
-    auto svE_ensure = [&](u32 level) -> int {
-        static const char *const names[5] = {"sv_E1", "sv_E2", "sv_E3", "sv_E4", "sv_E5"};
-        for (; svE_level < level && svE_level < 5; svE_level++) {
-            const size_t ne = m >> (svE_level + 1);
-            RET(c->tbuf(names[svE_level], (size_t)TAU * atl(ne), &svE[svE_level]));
-            if (svE_level == 0) RET(build_eq_dev(c, beta.data() + 1, P.s - 1, svE[0]));
-            else launch_bb_eq_pairsum(svE[svE_level - 1], atl(m >> svE_level), ne, svE[svE_level], atl(ne), c->stream());
-        }
-        return LF_OK;
-    };
+    use_sv = Gw == 1 && !c->tn.fold_no_sv && N <= m && (N & 3) == 0 && P.s >= 4;
+    sv_min = c->tn.sv_min >= 65536 ? 16384 : c->tn.sv_min;   // (the default threshold is the Goldilocks driver's; a BabyBear pair carries three times the rows)
     // rounds 4 / 5 in the split form (k_fold_round SPLIT): three lazy products per table, the host completes the message
-    const bool fr_split = Gw == 1 && !c->tn.fold_rounds_no_split && P.s >= 5;
+    fr_split = Gw == 1 && !c->tn.fold_rounds_no_split && P.s >= 5;
     c->sv_round_mask = 0;
     c->fold_split_mask = 0;
+    return LF_OK;
+}
+// the special tables of round-1, fixed at r_{round-1} into dst; the hand-over of a sharded step to the replicated tail gathers the fixed f-hat slices along
+// (if they exist yet: *gathered)
+int BbFold::fix_tables(u32 round, fe *dst, bool *gathered) {
+    const E9PreC r = e9pre_from_h9(pt[round - 2], nu);
+    const size_t nn = a.n / 2, ldn = atl(nn);
+    if (round == 2) {   // sources are the five separate full-size tables
+        launch_fix(c->dev, a.eqL, a.ld, dst, ldn, a.n, 1, r, c->stream());
+        launch_fix(c->dev, a.eqR, a.ld, dst + (size_t)TAU * ldn, ldn, a.n, 1, r, c->stream());
+        launch_fix(c->dev, a.eqB, a.ld, dst + (size_t)2 * TAU * ldn, ldn, a.n, 1, r, c->stream());
+        launch_fix(c->dev, a.G1, a.ld, dst + (size_t)3 * TAU * ldn, ldn, a.n, 8, r, c->stream());
+        launch_fix(c->dev, a.G2, a.ld, dst + (size_t)(3 * TAU + RE) * ldn, ldn, a.n, 8, r, c->stream());
+    } else {            // source is the previous 171-plane buffer (same layout): one launch over its 19 F_{p^9} rows
+        launch_fix(c->dev, a.eqL, a.ld, dst, ldn, a.n, 19, r, c->stream());
+    }
+    if (!(sharded && nn / 2 < Gw * 64)) return LF_OK;
+    sharded = false;
+    if (round <= 3) return LF_OK;
+    fe *fd = F[(round & 1) ? 0 : 1];
+    const size_t lcl = ldF / 2;   // local entries after this fix
+    launch_fix(c->dev, curF, ldF, fd, lcl, ldF, K2 * TAU * 8, r, c->stream());
+    const size_t planes = (size_t)K2 * TAU * RE, cnt = planes * lcl, words = (cnt + 1) / 2;   // two 32-bit words per u64
+    std::vector<u64> mine(words, 0), all(words * Gw);
+    std::vector<fe> full(planes * nn);
+    HIPCHK(hipMemcpyAsync(mine.data(), fd, cnt * sizeof(fe), hipMemcpyDeviceToHost, c->stream()));
+    HIPCHK(hipStreamSynchronize(c->stream()));
+    RET(c->comm.allgather_host(mine.data(), all.data(), words, c->stream()));
+    for (size_t rk = 0; rk < Gw; rk++) {
+        const fe *src = (const fe *)&all[rk * words];
+        for (size_t w = 0; w < planes; w++) memcpy(&full[w * nn + rk * lcl], src + w * lcl, lcl * sizeof(fe));
+    }
+    HIPCHK(hipMemcpyAsync(fd, full.data(), full.size() * sizeof(fe), hipMemcpyHostToDevice, c->stream()));
+    HIPCHK(hipStreamSynchronize(c->stream()));
+    curF = fd; ldF = nn;
+    *gathered = true;
+    return LF_OK;
+}
+// where this round's f-hat pairs come from (lut_mode, fix_fused), and the tables it leaves behind (curF, ldF)
+int BbFold::choose_producer(u32 round) {
+    const size_t nn = a.n / 2;
+    if (round == 3) {
+        const size_t q = sharded ? nn / Gw : nn, j0 = sharded ? gr * q : 0;   // this rank's slice of the m/4 entries
+        if (use_lut) {
+            H9 lh[162];
+            lfs::fold_lut81(hv, pt[0], pt[1], lh);
+            std::vector<fe> lut(2 * 81 * TAU);   // the 81 values, then their squares, as Montgomery words
+            for (int i = 0; i < 162; i++)
+                for (int q2 = 0; q2 < TAU; q2++) lut[(size_t)i * TAU + q2] = from_canon(lh[i].c[q2]);
+            RET(c->tbuf("fold_lut", 2 * 81 * TAU + 8, &d_lut));
+            HIPCHK(hipMemcpyAsync(d_lut, lut.data(), lut.size() * sizeof(fe), hipMemcpyHostToDevice, c->stream()));
+            HIPCHK(hipStreamSynchronize(c->stream()));   // lut is a stack-lifetime buffer
+            lut_mode = 3;
+            curF = nullptr; ldF = atl(q);
+        } else {
+            launch_fold_materialize2(c->dev, S[0].planes, S[1].planes, N, j0, q, K, pt[0], pt[1], c->ring, F[0], c->stream());
+            curF = F[0]; ldF = atl(q);
+        }
+    } else if (round > 3) {
+        fe *fd = F[(round & 1) ? 0 : 1];   // round 4 -> F[1], round 5 -> F[0], ...
+        if (use_lut && round == 4) lut_mode = 4;
+        else if (use_r5 && round == 5) lut_mode = 7;
+        else if (fused && ldF >= c->tn.fuse_min && ldF >= 4 && nn * 2 == ldF) { prevF = curF; prevld = ldF; fix_fused = true; }
+        else launch_fix(c->dev, curF, ldF, fd, atl(ldF / 2), ldF, K2 * TAU * 8, e9pre_from_h9(pt[round - 2], nu), c->stream());
+        curF = fd; ldF = atl(ldF / 2);
+    }
+    return LF_OK;
+}
+// rounds 1..3 as GEMMs: weights W_b = eq((r_1..r_{i-1}), b), their digit-monomial coefficients, c_i = prod_{k<i} eq(beta_k, r_k), w_h = c_i eq(beta_i, h)
+int BbFold::gemm_round(u32 round) {
+    const int svV = 1 << (round - 1);
+    std::vector<H9> W((size_t)svV), Cf;
+    lfs::eq_weights(hv, pt.data(), round - 1, W.data());
+    lfs::sv_coef(hv, svV, W.data(), lf::sv_num_pairs(svV), [&](int i) { return lf::sv_pair(svV, i); }, Cf);
+    std::vector<fe> coef(Cf.size() * TAU);   // C_pi(X) -> [pairs][4][9] Montgomery words
+    for (size_t i = 0; i < Cf.size(); i++)
+        for (int q = 0; q < TAU; q++) coef[i * TAU + q] = from_canon(Cf[i].c[q]);
+    const H9 ci = lfs::eq_prefix(hv, beta.data(), pt.data(), round), bi = beta[round - 1];
+    const E9C w0 = e9c_from_h9(hv.ext_mul(ci, h9_sub(h9_one(), bi))), w1 = e9c_from_h9(hv.ext_mul(ci, bi));
+    fe *d_coef, *svtp;
+    u64 *gtmp;
+    unsigned char *sveb;
+    int32_t *svpart, *svtot;
+    RET(c->tbuf("sv_coef", coef.size() + 8, &d_coef));
+    RET(c->tbuf("sv_gtmp", (size_t)5 * RE + 8, &gtmp));
+    RET(c->tbuf("sv_tp", bbsv_tp_words(K), &svtp));
+    RET(c->tbuf("sv_eb", bbsv_eb_bytes(a.pcnt), &sveb));
+    RET(c->tbuf("sv_part", bbsv_part_words(svV, K), &svpart));
+    RET(c->tbuf("sv_tot", bbsv_tot_words(svV, K), &svtot));
+    HIPCHK(hipMemcpyAsync(d_coef, coef.data(), coef.size() * sizeof(fe), hipMemcpyHostToDevice, c->stream()));
+    HIPCHK(hipStreamSynchronize(c->stream()));   // coef is a stack-lifetime buffer
+    if (!svbits[0])
+        for (int sd = 0; sd < 2; sd++) {
+            RET(c->tbuf(sd ? "sv_bits_R" : "sv_bits_L", bbsv_bits_words(N, K), &svbits[sd]));
+            launch_bbsv_bits(S[sd].planes, N, N, K, svbits[sd], c->stream());
+        }
+    RET(svE_ensure(round));
+    i64 *gpartial;
+    RET(c->tbuf("sv_gpartial", red_partial_words(5 * RE), &gpartial));
+    // the G part (eqL G1 + eqR G2: the round kernel without tables) on the other, idle stream next to the GEMM chain
+    hipStream_t sg = (c->cur_lane == 0 && c->st_lane[1]) ? c->st_lane[1] : c->stream();
+    RET(c->fork(c->stream(), sg));      // the special tables of this round were fixed on this stream
+    launch_fold_round_g(c->dev, a, gpartial, gtmp, sg);
+    hipEvent_t g_ready = nullptr;       // the GEMM chain's last kernel waits for the G part
+    if (sg != c->stream() && !(g_ready = c->join_mark(sg))) return LF_ERR_HIP;
+    if (launch_bbsv_round(c->dev, svV, svbits[0], svbits[1], N, svE[round - 1], atl(m >> round), a.pcnt, K, d_mu, d_coef, w0, w1, sveb, svpart, svtot, svtp, gtmp, od,
+                          c->stream(), g_ready) == 0) {
+        sv_done = true;
+        c->sv_round_mask |= 1u << (round - 1);
+    }
+    return LF_OK;
+}
+// split form of this round's table kernel?  (modes 6 / 7; c_i and beta_i must be invertible for the host's completion.  Round 5 from the planes runs on two
+// lanes per pair -- k_fold_round5_2l: all four products, unsplit -- unless LF_FOLD_R5_ONE_LANE=1)
+int BbFold::decide_split(u32 round) {
+    Er = nullptr; ldEr = 0; split_now = false;
+    if (!(fr_split && !sv_done && round >= 2 && round <= 5 && !sharded && (lut_mode == 4 && !c->tn.fold_no_r4tab) && a.pcnt >= c->tn.fold_split_min)) return LF_OK;
+    sp = lfs::split_coef(hv, lfs::eq_prefix(hv, beta.data(), pt.data(), round), beta[round - 1]);
+    if (!sp.ok) return LF_OK;
+    RET(svE_ensure(round));
+    Er = svE[round - 1]; ldEr = atl(m >> round);
+    split_now = true;
+    c->fold_split_mask |= 1u << (round - 1);
+    return LF_OK;
+}
+// the table kernel of this round (unless its GEMMs ran): its message (or, split, its three sums and the G part) goes to od
+int BbFold::dispatch(u32 round) {
+    const int32_t *pL = S[0].planes, *pR = S[1].planes;
+    hipStream_t st = c->stream();
+    if (sv_done) {}
+    else if (round == 1) launch_fold_round1(c->dev, a, pL, pR, N, K, d_mu, partial, od, st);
+    else if (round == 2) launch_fold_round2(c->dev, a, pL, pR, N, K, d_mu, pt[0], c->ring, partial, od, st);
+    else if (lut_mode == 3) {
+        fe *mutab;
+        RET(c->tbuf("fold_mutab", (size_t)3 * K2 * TAU * 81 * 12, &mutab));
+        launch_fold_round_lut_mu(c->dev, a, pL, pR, N, d_lut, mutab, K, d_mup, partial, od, st);
+    } else if (lut_mode == 4 && !c->tn.fold_no_r4tab) {
+        fe *r4sq, *r4mt;
+        RET(c->tbuf("fold_r4sq", (size_t)6561 * 12, &r4sq));
+        RET(c->tbuf("fold_r4mt", (size_t)K2 * TAU * 162 * 12, &r4mt));
+        launch_fold_round_lut_fix_tab(c->dev, a, pL, pR, N, d_lut, pt[round - 2], c->ring, r4sq, r4mt, use_r5 ? nullptr : (fe *)curF, ldF, K, d_mup, partial, od, st, Er, ldEr);
+    } else if (lut_mode == 7) {
+        fe *r5xx, *r5yy, *r5mt;
+        RET(c->tbuf("fold_r5xx", (size_t)6561 * 12, &r5xx));
+        RET(c->tbuf("fold_r5yy", (size_t)6561 * 12, &r5yy));
+        RET(c->tbuf("fold_r5mt", (size_t)K2 * TAU * 324 * 12, &r5mt));
+        launch_fold_round_lut_fix5(c->dev, a, pL, pR, N, d_lut, pt[round - 3], pt[round - 2], c->ring, r5xx, r5yy, r5mt, (fe *)curF, ldF, K, d_mup, partial, od, st, Er, ldEr);
+    } else if (lut_mode == 4) launch_fold_round_lut_fix(c->dev, a, pL, pR, N, d_lut, pt[round - 2], c->ring, (fe *)curF, ldF, K, d_mup, partial, od, st);
+    else if (fix_fused) launch_fold_round_fix(c->dev, a, prevF, prevld, pt[round - 2], c->ring, (fe *)curF, ldF, K, d_mup, partial, od, st);
+    else launch_fold_round(c->dev, a, curF, ldF, K, d_mup, partial, od, st);
+    if (split_now) {   // the G part of the message (eqL G1 + eqR G2 at X = 0..4) from the round kernel run without tables, behind the three sums of the table kernel
+        i64 *gpartial;
+        RET(c->tbuf("sv_gpartial", red_partial_words(5 * RE), &gpartial));
+        launch_fold_round_g(c->dev, a, gpartial, od + 5 * RE, st);
+    }
+    return LF_OK;
+}
+int BbFold::rounds() {
+    size_t ph = c->ev_begin(14);
+    { HostTimer ht(c); lfs::sumcheck_prologue<BbV>(tr, P.s, deg); }
+    RET(rounds_begin());
     for (u32 round = 1; round <= P.s; round++) {
-        bool fix_fused = false;
+        fix_fused = false;
         lut_mode = 0;
         if (round > 1) {
-            H9 rh = pt[round - 2];
-            E9PreC r = e9pre_from_h9(rh, nu);
-            size_t nn = a.n / 2, ldn = atl(nn);
+            const size_t nn = a.n / 2;
             fe *dst = T5[flip];
-            if (round == 2) {   // sources are the five separate full-size tables
-                launch_fix(c->dev, a.eqL, a.ld, dst, ldn, a.n, 1, r, c->stream());
-                launch_fix(c->dev, a.eqR, a.ld, dst + (size_t)TAU * ldn, ldn, a.n, 1, r, c->stream());
-                launch_fix(c->dev, a.eqB, a.ld, dst + (size_t)2 * TAU * ldn, ldn, a.n, 1, r, c->stream());
-                launch_fix(c->dev, a.G1, a.ld, dst + (size_t)3 * TAU * ldn, ldn, a.n, 8, r, c->stream());
-                launch_fix(c->dev, a.G2, a.ld, dst + (size_t)(3 * TAU + RE) * ldn, ldn, a.n, 8, r, c->stream());
-            } else {            // source is the previous 171-plane buffer (same layout): one launch over its 19 F_{p^9} rows
-                launch_fix(c->dev, a.eqL, a.ld, dst, ldn, a.n, 19, r, c->stream());
-            }
             bool gathered = false;
-            if (sharded && nn / 2 < Gw * 64) {
-                // transition to the replicated tail: gather the fixed f-hat slices (if they exist yet)
-                if (round > 3) {
-                    fe *fd = F[(round & 1) ? 0 : 1];
-                    size_t lcl = ldF / 2;   // local entries after this fix
-                    launch_fix(c->dev, curF, ldF, fd, lcl, ldF, K2 * TAU * 8, r, c->stream());
-                    size_t planes = (size_t)K2 * TAU * RE, cnt = planes * lcl, words = (cnt + 1) / 2;   // two 32-bit words per u64
-                    std::vector<u64> mine(words, 0), all(words * Gw);
-                    std::vector<fe> full(planes * nn);
-                    HIPCHK(hipMemcpyAsync(mine.data(), fd, cnt * sizeof(fe), hipMemcpyDeviceToHost, c->stream()));
-                    HIPCHK(hipStreamSynchronize(c->stream()));
-                    RET(c->comm.allgather_host(mine.data(), all.data(), words, c->stream()));
-                    for (size_t rk = 0; rk < Gw; rk++) {
-                        const fe *src = (const fe *)&all[rk * words];
-                        for (size_t w = 0; w < planes; w++) memcpy(&full[w * nn + rk * lcl], src + w * lcl, lcl * sizeof(fe));
-                    }
-                    HIPCHK(hipMemcpyAsync(fd, full.data(), full.size() * sizeof(fe), hipMemcpyHostToDevice, c->stream()));
-                    HIPCHK(hipStreamSynchronize(c->stream()));
-                    curF = fd; ldF = nn;
-                    gathered = true;
-                }
-                sharded = false;
-            }
-            if (!gathered) {
-                if (round == 3) {
-                    size_t q = sharded ? nn / Gw : nn, j0 = sharded ? gr * q : 0;   // this rank's slice of the m/4 entries
-                    if (use_lut) {
-                        std::vector<fe> lut(2 * 81 * TAU);
-                        build_fold_lut(pt[0], pt[1], c->ring, lut.data());
-                        RET(c->tbuf("fold_lut", 2 * 81 * TAU + 8, &d_lut));
-                        HIPCHK(hipMemcpyAsync(d_lut, lut.data(), lut.size() * sizeof(fe), hipMemcpyHostToDevice, c->stream()));
-                        HIPCHK(hipStreamSynchronize(c->stream()));   // lut is a stack-lifetime buffer
-                        lut_mode = 3;
-                        curF = nullptr; ldF = atl(q);
-                    } else {
-                        launch_fold_materialize2(c->dev, S[0].planes, S[1].planes, N, j0, q, K, pt[0], pt[1], c->ring, F[0], c->stream());
-                        curF = F[0]; ldF = atl(q);
-                    }
-                } else if (round > 3) {
-                    fe *fd = F[(round & 1) ? 0 : 1];   // round 4 -> F[1], round 5 -> F[0], ...
-                    if (use_lut && round == 4) lut_mode = 4;
-                    else if (use_r5 && round == 5) lut_mode = 7;
-                    else if (fused && ldF >= fuse_min && ldF >= 4 && nn * 2 == ldF) { prevF = curF; prevld = ldF; fix_fused = true; }
-                    else launch_fix(c->dev, curF, ldF, fd, atl(ldF / 2), ldF, K2 * TAU * 8, r, c->stream());
-                    curF = fd; ldF = atl(ldF / 2);
-                }
-            }
-            a.eqL = dst; a.eqR = dst + (size_t)TAU * ldn; a.eqB = dst + (size_t)2 * TAU * ldn;
-            a.G1 = dst + (size_t)3 * TAU * ldn; a.G2 = dst + (size_t)(3 * TAU + RE) * ldn;
-            a.ld = ldn; a.n = nn;
+            RET(fix_tables(round, dst, &gathered));
+            if (!gathered) RET(choose_producer(round));
+            set_tables(dst, nn);
             flip ^= 1;
         }
         if (sharded && a.n / 2 < Gw * 64) sharded = false;   // (round 1 of a tiny instance)
         if (sharded) { a.pcnt = a.n / 2 / Gw; a.p0 = gr * a.pcnt; a.pF0 = a.p0; }
         else { a.p0 = 0; a.pcnt = a.n / 2; a.pF0 = 0; }
         size_t ev = c->ev_begin(0);
-        const int svV = 1 << (round - 1);
-        bool sv_done = false;
-        if (use_sv && (int)round <= c->tn.sv_rounds && round <= 3 && a.pcnt >= sv_min && bbsv_shape_ok(svV, a.pcnt, K)) {
-            // weights W_b = eq((r_1..r_{i-1}), b), their digit-monomial coefficients, c_i = prod_{k<i} eq(beta_k, r_k), w_h = c_i eq(beta_i, h)
-            const fe nuM = from_canon(nu);
-            std::vector<H9> W((size_t)svV, h9_one()), Cf;
-            for (int b = 0; b < svV; b++)
-                for (u32 j = 0; j + 1 < round; j++) W[b] = c->ring.mul9(W[b], ((b >> j) & 1) ? pt[j] : h9_sub(h9_one(), pt[j]));
-            lfs::sv_coef(hv, svV, W.data(), lf::sv_num_pairs(svV), [&](int i) { return lf::sv_pair(svV, i); }, Cf);
-            std::vector<fe> coef(Cf.size() * TAU);   // C_pi(X) -> [pairs][4][9] Montgomery words
-            for (size_t i = 0; i < Cf.size(); i++)
-                for (int q = 0; q < TAU; q++) coef[i * TAU + q] = from_canon(Cf[i].c[q]);
-            E9 cc = e9_from_h9(h9_one());
-            for (u32 k2 = 1; k2 < round; k2++) {
-                const E9 b = e9_from_h9(beta[k2 - 1]), r = e9_from_h9(pt[k2 - 1]), one = e9_from_h9(h9_one());
-                cc = e9_mul(cc, e9_add(e9_mul(e9_sub(one, b), e9_sub(one, r), nuM), e9_mul(b, r, nuM)), nuM);
-            }
-            const E9 bi = e9_from_h9(beta[round - 1]);
-            const E9 w0e = e9_mul(cc, e9_sub(e9_from_h9(h9_one()), bi), nuM), w1e = e9_mul(cc, bi, nuM);
-            E9C w0, w1;
-            for (int q = 0; q < TAU; q++) { w0.c[q] = w0e.c[q]; w1.c[q] = w1e.c[q]; }
-            fe *d_coef, *svtp;
-            u64 *gtmp;
-            unsigned char *sveb;
-            int32_t *svpart, *svtot;
-            RET(c->tbuf("sv_coef", coef.size() + 8, &d_coef));
-            RET(c->tbuf("sv_gtmp", (size_t)5 * RE + 8, &gtmp));
-            RET(c->tbuf("sv_tp", bbsv_tp_words(K), &svtp));
-            RET(c->tbuf("sv_eb", bbsv_eb_bytes(a.pcnt), &sveb));
-            RET(c->tbuf("sv_part", bbsv_part_words(svV, K), &svpart));
-            RET(c->tbuf("sv_tot", bbsv_tot_words(svV, K), &svtot));
-            HIPCHK(hipMemcpyAsync(d_coef, coef.data(), coef.size() * sizeof(fe), hipMemcpyHostToDevice, c->stream()));
-            HIPCHK(hipStreamSynchronize(c->stream()));   // coef is a stack-lifetime buffer
-            if (!svbits[0])
-                for (int sd = 0; sd < 2; sd++) {
-                    RET(c->tbuf(sd ? "sv_bits_R" : "sv_bits_L", bbsv_bits_words(N, K), &svbits[sd]));
-                    launch_bbsv_bits(S[sd].planes, N, N, K, svbits[sd], c->stream());
-                }
-            RET(svE_ensure(round));
-            i64 *gpartial;
-            RET(c->tbuf("sv_gpartial", red_partial_words(5 * RE), &gpartial));
-            // the G part (eqL G1 + eqR G2: the round kernel without tables) on the other, idle stream next to the GEMM chain
-            hipStream_t sg = (c->cur_lane == 0 && c->st_lane[1]) ? c->st_lane[1] : c->stream();
-            hipEvent_t g_ready = nullptr;
-            if (sg != c->stream()) {
-                for (int e = 0; e < 2; e++)
-                    if (!c->ev_prep[e]) HIPCHK(hipEventCreateWithFlags(&c->ev_prep[e], hipEventDisableTiming));
-                HIPCHK(hipEventRecord(c->ev_prep[0], c->stream()));      // the special tables of this round were fixed on this stream
-                HIPCHK(hipStreamWaitEvent(sg, c->ev_prep[0], 0));
-            }
-            launch_fold_round_g(c->dev, a, gpartial, gtmp, sg);
-            if (sg != c->stream()) { HIPCHK(hipEventRecord(c->ev_prep[1], sg)); g_ready = c->ev_prep[1]; }
-            if (launch_bbsv_round(c->dev, svV, svbits[0], svbits[1], N, svE[round - 1], atl(m >> round), a.pcnt, K, d_mu, d_coef, w0, w1, sveb, svpart, svtot, svtp, gtmp, od,
-                                  c->stream(), g_ready) == 0) {
-                sv_done = true;
-                c->sv_round_mask |= 1u << (round - 1);
-            }
-        }
-        // split form of this round's table kernel?  (modes 6 / 7; c_i and beta_i must be invertible for the host's completion)
-        bool split_now = false;
-        H9 sp_c = h9_one(), sp_cinv = h9_one(), sp_binv = h9_one();
-        const fe *Er = nullptr;
-        size_t ldEr = 0;
-        // (round 5 from the planes runs on two lanes per pair -- k_fold_round5_2l: all four products, unsplit -- unless LF_FOLD_R5_ONE_LANE=1)
-        if (fr_split && !sv_done && round >= 2 && round <= 5 && !sharded && (lut_mode == 4 && !c->tn.fold_no_r4tab) &&
-            a.pcnt >= c->tn.fold_split_min) {
-            for (u32 k2 = 1; k2 < round; k2++) {
-                const H9 b = beta[k2 - 1], r = pt[k2 - 1];
-                sp_c = c->ring.mul9(sp_c, h9_add(c->ring.mul9(h9_sub(h9_one(), b), h9_sub(h9_one(), r)), c->ring.mul9(b, r)));
-            }
-            if (h9_inv(sp_c, nu, &sp_cinv) && h9_inv(beta[round - 1], nu, &sp_binv)) {
-                RET(svE_ensure(round));
-                Er = svE[round - 1]; ldEr = atl(m >> round);
-                split_now = true;
-                c->fold_split_mask |= 1u << (round - 1);
-            }
-        }
-        if (sv_done) {}
-        else if (round == 1) launch_fold_round1(c->dev, a, S[0].planes, S[1].planes, N, K, d_mu, partial, od, c->stream());
-        else if (round == 2) launch_fold_round2(c->dev, a, S[0].planes, S[1].planes, N, K, d_mu, pt[0], c->ring, partial, od, c->stream());
-        else if (lut_mode == 3) {
-            fe *mutab;
-            RET(c->tbuf("fold_mutab", (size_t)3 * K2 * TAU * 81 * 12, &mutab));
-            launch_fold_round_lut_mu(c->dev, a, S[0].planes, S[1].planes, N, d_lut, mutab, K, d_mup, partial, od, c->stream());
-        }
-        else if (lut_mode == 4 && !c->tn.fold_no_r4tab) {
-            fe *r4sq, *r4mt;
-            RET(c->tbuf("fold_r4sq", (size_t)6561 * 12, &r4sq));
-            RET(c->tbuf("fold_r4mt", (size_t)K2 * TAU * 162 * 12, &r4mt));
-            launch_fold_round_lut_fix_tab(c->dev, a, S[0].planes, S[1].planes, N, d_lut, pt[round - 2], c->ring, r4sq, r4mt, use_r5 ? nullptr : (fe *)curF, ldF, K, d_mup, partial, od,
-                                          c->stream(), Er, ldEr);
-        } else if (lut_mode == 7) {
-            fe *r5xx, *r5yy, *r5mt;
-            RET(c->tbuf("fold_r5xx", (size_t)6561 * 12, &r5xx));
-            RET(c->tbuf("fold_r5yy", (size_t)6561 * 12, &r5yy));
-            RET(c->tbuf("fold_r5mt", (size_t)K2 * TAU * 324 * 12, &r5mt));
-            launch_fold_round_lut_fix5(c->dev, a, S[0].planes, S[1].planes, N, d_lut, pt[round - 3], pt[round - 2], c->ring, r5xx, r5yy, r5mt, (fe *)curF, ldF, K, d_mup, partial, od,
-                                       c->stream(), Er, ldEr);
-        } else if (lut_mode == 4) launch_fold_round_lut_fix(c->dev, a, S[0].planes, S[1].planes, N, d_lut, pt[round - 2], c->ring, (fe *)curF, ldF, K, d_mup, partial, od, c->stream());
-        else if (fix_fused) launch_fold_round_fix(c->dev, a, prevF, prevld, pt[round - 2], c->ring, (fe *)curF, ldF, K, d_mup, partial, od, c->stream());
-        else launch_fold_round(c->dev, a, curF, ldF, K, d_mup, partial, od, c->stream());
-        if (split_now) {   // the G part of the message (eqL G1 + eqR G2 at X = 0..4) from the round kernel run without tables, behind the three sums of the table kernel
-            i64 *gpartial;
-            RET(c->tbuf("sv_gpartial", red_partial_words(5 * RE), &gpartial));
-            launch_fold_round_g(c->dev, a, gpartial, od + 5 * RE, c->stream());
-        }
+        sv_done = false;
+        if (use_sv && (int)round <= c->tn.sv_rounds && round <= 3 && a.pcnt >= sv_min && bbsv_shape_ok(1 << (round - 1), a.pcnt, K)) RET(gemm_round(round));
+        RET(decide_split(round));
+        RET(dispatch(round));
         c->ev_end(ev);
-        u64 *evs = msgs + (size_t)(round - 1) * (deg + 1) * RE;
+        u64 *evs = msg(round);
         HIPCHK(hipStreamSynchronize(c->stream()));            // message is in mapped host memory
-        if (split_now) {
-            // od[e][slot] (e = 0..2): A_e = sum_p E[p] C_e(p); od[5 + X][slot]: the G part.  g(X) = c l(X) (A0 + A1 X + A2 X^2 + A3 X^3) + G(X), l(X) = eq(beta_i, X);
-            // A3 from g(0) + g(1) = the previous message at its challenge (interpolated: no assumption on the claimed sum)
+        if (split_now) {   // od[e][slot] (e = 0..2): A_e = sum_p E[p] C_e(p); od[5 + X][slot]: the G part at X = 0..4
             HostTimer ht2(c);
-            const H9 bi = beta[round - 1], obi = h9_sub(h9_one(), bi), x = pt[round - 2];
-            H9 wS[5];
-            for (u32 j2 = 0; j2 <= deg; j2++) {
-                H9 num = h9_one();
-                u64 den = 1;
-                for (u32 k2 = 0; k2 <= deg; k2++) {
-                    if (k2 == j2) continue;
-                    H9 xk = x; xk.c[0] = hsub(xk.c[0], k2);
-                    num = c->ring.mul9(num, xk);
-                    den = hmul(den, j2 > k2 ? (u64)(j2 - k2) : BB_P - (u64)(k2 - j2));
-                }
-                wS[j2] = h9_scale(num, hinv(den));
-            }
-            H9 cl[5];   // c l(X)
-            {
-                H9 l = obi;
-                const H9 dl = h9_sub(bi, obi);
-                for (u32 X = 0; X <= deg; X++) { cl[X] = c->ring.mul9(sp_c, l); l = h9_add(l, dl); }
-            }
-            const u64 *pe = msgs + (size_t)(round - 2) * (deg + 1) * RE, *gev = od + 5 * RE;
-            auto ld = [&](const u64 *b, u32 e, u32 slot) { return h9_load(b + (size_t)e * RE + TAU * slot); };
-            for (u32 slot = 0; slot < 8; slot++) {
-                H9 Sv = ld(pe, 0, slot);
-                Sv = c->ring.mul9(wS[0], Sv);
-                for (u32 j2 = 1; j2 <= deg; j2++) Sv = h9_add(Sv, c->ring.mul9(wS[j2], ld(pe, j2, slot)));
-                const H9 A0 = ld(od, 0, slot), A1 = ld(od, 1, slot), A2 = ld(od, 2, slot);
-                const H9 Gsum = h9_add(ld(gev, 0, slot), ld(gev, 1, slot));
-                const H9 T1 = c->ring.mul9(h9_sub(c->ring.mul9(h9_sub(Sv, Gsum), sp_cinv), c->ring.mul9(obi, A0)), sp_binv);
-                const H9 A3 = h9_sub(h9_sub(h9_sub(T1, A0), A1), A2);
-                for (u32 X = 0; X <= deg; X++) {
-                    const H9 T = h9_add(A0, h9_scale(h9_add(A1, h9_scale(h9_add(A2, h9_scale(A3, X)), X)), X));
-                    const H9 g = h9_add(c->ring.mul9(cl[X], T), ld(gev, X, slot));
-                    memcpy(evs + (size_t)X * RE + TAU * slot, g.c, sizeof(g.c));
-                }
-            }
+            lfs::complete_fold_split(hv, sp, od, od + 5 * RE, msg(round - 1), pt[round - 2], evs);
         } else
-        memcpy(evs, od, (size_t)(deg + 1) * RE * 8);
+            memcpy(evs, od, (size_t)(deg + 1) * RE * 8);
         if (sharded) RET(exchange_modsum(c, evs, (size_t)(deg + 1) * RE));
         HostTimer ht(c);
         pt[round - 1] = lfs::sumcheck_round<BbV>(tr, evs, deg + 1);
@@ -683,44 +655,33 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
     }
     c->ev_end(ph);
     BB_MARK(" fold sumcheck");
-
-    ph = c->ev_begin(15);
-    // theta, eta at r_0 (folding.rs:236-256)
-    u64 *theta = proof + (size_t)P.s * (deg + 1) * RE, *eta = theta + (size_t)K2 * TAU * RE;
+    return LF_OK;
+}
+// theta, eta at r_0 (folding.rs:236-256)
+int BbFold::evaluations() {
     fe *eq0, *q;
     i64 *red;
-    u64 *sm;
     RET(c->tbuf("fold_eq0", TAU * m, &eq0));
     RET(c->tbuf("dec_q", (size_t)P.t * RE * n, &q));
     RET(c->tbuf("red_partial", red_partial_words(16 * RE * TAU), &red));
-    RET(c->tbuf("dec_small", 16 * RE * TAU + 16 * 4 * RE, &sm));
     RET(build_eq_dev(c, pt.data(), P.s, eq0));
-    // the other stream is idle here: every second q_j = M_j^T eq(r_o) is gathered there, and the eta products of the right side run there (as in the Goldilocks driver)
+    // the other stream is idle here: every second q_j = M_j^T eq(r_o) is gathered there, and the eta products of the right side run there
     hipStream_t s1f = (c->cur_lane == 0 && c->sh_world == 1 && c->st_lane[1]) ? c->st_lane[1] : c->stream();
-    if (s1f != c->stream()) {
-        for (int e = 0; e < 2; e++)
-            if (!c->ev_prep[e]) HIPCHK(hipEventCreateWithFlags(&c->ev_prep[e], hipEventDisableTiming));
-        HIPCHK(hipEventRecord(c->ev_prep[0], c->stream()));           // eq(r_o) is built
-        HIPCHK(hipStreamWaitEvent(s1f, c->ev_prep[0], 0));
-    }
+    RET(c->fork(c->stream(), s1f));           // eq(r_o) is built
     for (u32 j = 0; j < P.t; j++)
         launch_spmv_t_eq(c->dev, c->d_colptr[j], c->d_rowidx[j], c->d_valT[j], eq0, m, q + (size_t)j * RE * n, n, (j & 1) ? s1f : c->stream());
-    if (s1f != c->stream()) {
-        HIPCHK(hipEventRecord(c->ev_prep[1], s1f));
-        HIPCHK(hipStreamWaitEvent(c->stream(), c->ev_prep[1], 0));
-    }
+    RET(c->join(s1f, c->stream()));
     // theta for both sides first, then eta; the host absorbs theta while the GPU still computes the eta dot products
     u64 *fsm;
-    size_t nth = (size_t)K2 * TAU * RE, net = (size_t)K2 * P.t * RE;
+    const size_t nth = (size_t)K2 * TAU * RE, net = (size_t)K2 * P.t * RE;
     RET(c->tbuf("fold_small", nth + net + 64, &fsm));
     u64 *hp = c->arena_alloc(nth + net);
     if (!hp) return LF_ERR_HIP;
     u64 *d_theta = fsm, *d_eta = fsm + nth;
-    (void)sm;
     // theta = f-hat_{k,d}(r_o): the sumcheck's f-hat tables, fixed at r_1..r_{s-1}, have two entries left -- one more fix gives the
     // evaluations (exact arithmetic: the same words as evaluate_mles on the witness).  LF_THETA_EVAL=1 / fewer than 4 variables:
     // stand-alone evaluation.
-    if (P.s >= 4 && curF && ldF == 2 && !c->tn.theta_eval) launch_fix_final(c->dev, curF, ldF, K2 * TAU * 8, e9pre_from_h9(pt[P.s - 1], c->ring.T.nu), d_theta, c->stream());
+    if (P.s >= 4 && curF && ldF == 2 && !c->tn.theta_eval) launch_fix_final(c->dev, curF, ldF, K2 * TAU * 8, e9pre_from_h9(pt[P.s - 1], nu), d_theta, c->stream());
     else
         for (int sd = 0; sd < 2; sd++) RET(coef_eval_bits_dev(c, S[sd].planes, N, eq0, m, K, red, d_theta + (size_t)sd * K * TAU * RE));
     HIPCHK(hipMemcpyAsync(hp, d_theta, nth * 8, hipMemcpyDeviceToHost, c->stream()));
@@ -731,33 +692,35 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
             RET(c->tbuf("dot_yb", bbdot_i8_yb_bytes(n + 1), &ybq));
             if (launch_dot_pack_y(S[0].z, q, n, P.t, n, ybq, c->stream()) != 0) ybq = nullptr;
         }
-        HIPCHK(hipEventRecord(c->ev_prep[0], c->stream()));           // q (and its digits) are ready
-        HIPCHK(hipStreamWaitEvent(s1f, c->ev_prep[0], 0));
+        RET(c->fork(c->stream(), s1f));           // q (and its digits) are ready
         i64 *red1;
         RET(c->tbuf("red_partial1", red_partial_words(16 * RE * TAU), &red1));
         RET(dot_batch_dev(c, S[1].z, n, K, q, n, P.t, n, red1, d_eta + (size_t)K * P.t * RE, s1f, "_1", ybq));
-        HIPCHK(hipEventRecord(c->ev_prep[1], s1f));
+        if (!c->join_mark(s1f)) return LF_ERR_HIP;
         RET(dot_batch_dev(c, S[0].z, n, K, q, n, P.t, n, red, d_eta, nullptr, "", ybq));
-        HIPCHK(hipStreamWaitEvent(c->stream(), c->ev_prep[1], 0));
+        RET(c->join_wait(c->stream()));
     } else
         for (int sd = 0; sd < 2; sd++) RET(dot_batch_dev(c, S[sd].z, n, K, q, n, P.t, n, red, d_eta + (size_t)sd * K * P.t * RE));
     HIPCHK(hipMemcpyAsync(hp + nth, d_eta, net * 8, hipMemcpyDeviceToHost, c->stream()));
     HIPCHK(hipEventSynchronize(c->ev_side[0]));
     BB_MARK("  theta down");
-    memcpy(theta, hp, nth * 8);
+    memcpy(theta(), hp, nth * 8);
     {
         HostTimer ht(c);
-        tr.absorb_ring(theta, (size_t)K2 * TAU);
+        tr.absorb_ring(theta(), (size_t)K2 * TAU);
     }
     BB_MARK("  theta absorbed");
     HIPCHK(hipStreamSynchronize(c->stream()));
     BB_MARK("  eta down");
-    memcpy(eta, hp + nth, net * 8);
+    memcpy(eta(), hp + nth, net * 8);
+    return LF_OK;
+}
+int BbFold::finish(u64 *lcccs_out, lf_witness **w_out) {
     std::vector<u64> rho_c, rho;
     std::vector<int8_t> rho8;
     {   // get_rhos (folding/utils.rs:116-131)
         HostTimer ht(c);
-        tr.absorb_ring(eta, (size_t)K2 * P.t);
+        tr.absorb_ring(eta(), (size_t)K2 * P.t);
         lfs::draw_rho(hv, tr, K2, rho_c, rho, &rho8);
     }
     // f_0 in the coefficient domain -> new witness
@@ -775,16 +738,25 @@ static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_wi
     launch_recompose_crt(c->dev, npl, N, (u32)N, 1, P.B, 1, 0, nf, N, 0, c->stream());
     launch_recompose_crt(c->dev, npl, N, P.wit_len, P.L, P.B, 1, 0, nw, P.wit_len, 0, c->stream());
     BB_MARK("  eta absorbed, rho drawn, fold_witness enqueued");
-
     // the folded instance (folding/utils.rs:460-521) on the host while the GPU folds the witness
     {
         HostTimer ht(c);
-        lfs::fold_instance(hv, P, pt, theta, eta, rho_c.data(), rho.data(), [&](u32 i) { return &S[i / K].lcccs[(size_t)(i % K) * ll * RE]; }, lcccs_out);
+        const size_t ll = lcccs_len(&P, TAU);
+        lfs::fold_instance(hv, P, pt, theta(), eta(), rho_c.data(), rho.data(), [&](u32 i) { return &S[i / K].lcccs[(size_t)(i % K) * ll * RE]; }, lcccs_out);
     }
     BB_MARK("  folded instance on the host");
     HIPCHK(hipStreamSynchronize(c->stream()));
     *w_out = new lf_witness{c->owner, npl, N, lf_ctx_device(c->owner), N * RE * 4};
-    if (nf) { (*w_out)->f_ntt = (uint64_t *)nf; (*w_out)->f_bytes = nf_bytes; (*w_out)->w_ccs = (uint64_t *)nw; (*w_out)->w_bytes = nw_bytes; }
+    (*w_out)->f_ntt = (uint64_t *)nf; (*w_out)->f_bytes = nf_bytes; (*w_out)->w_ccs = (uint64_t *)nw; (*w_out)->w_bytes = nw_bytes;
+    return LF_OK;
+}
+static int fold_impl(C *c, BbTranscript &tr, SideState *S, u64 *lcccs_out, lf_witness **w_out, u64 *proof) {
+    BbFold f{c, tr, S, proof};
+    RET(f.prepare());
+    RET(f.rounds());
+    size_t ph = c->ev_begin(15);
+    RET(f.evaluations());
+    RET(f.finish(lcccs_out, w_out));
     c->ev_end(ph);
     return LF_OK;
 }

@@ -14,6 +14,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -77,6 +78,16 @@ struct Timeline {
 };
 inline thread_local Timeline *t_tl = nullptr;
 #define TL_MARK(x) do { if (t_tl) t_tl->mark(x); } while (0)
+// "<what> <round>" as a mark: the marks keep pointers, so the formatted names are interned for the life of the library
+inline const char *tl_round_name(const char *what, unsigned round) {
+    static std::mutex mu;
+    static std::set<std::string> names;
+    char nm[32];
+    snprintf(nm, sizeof nm, "%s %u", what, round);
+    std::lock_guard<std::mutex> g(mu);
+    return names.insert(nm).first->c_str();
+}
+#define TL_MARK_ROUND(what, round) do { if (t_tl) t_tl->mark(tl_round_name(what, round)); } while (0)
 
 static const char *PHASE_NAMES[LF_N_PHASES] = {"linearization", "decomp_crt_commit", "decomp_evals", "fold_prepare",
                                                 "fold_sumcheck", "fold_finish", "host_transcript", "total"};
@@ -331,6 +342,43 @@ int commit_parts_i8g(lf_ctx *c, const unsigned char *D, size_t ldn, u32 NP, u64 
 // the digit planes of a witness, cut on the calling lane's stream into the buffer `name`
 int sb_cut_parts(lf_ctx *c, const lf_witness *wit, const char *name, const unsigned char **D);
 int fold_impl_sb(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out, lf_witness **w_out, u64 *proof);
+// One run of the folding prover: the state its stages share, and the stages that are the same code for b = 2 (lf_fold.cpp, which defines them) and for the
+// small bases (lf_fold_sb.cpp).  A stage queues on the stream it is given: the streams a path uses are that path's schedule.
+struct FoldStep {
+    lf_ctx *c;
+    Transcript &tr;
+    SideState *S;   // [2]
+    u64 *proof;     // the s round messages, theta, eta
+    const lf_params &P;
+    const size_t m, n, N;
+    const u32 K, K2, deg;
+    const GoldV hv;
+    std::vector<Fq3> alpha, zeta, mu, beta, pt;
+    Fq3Const *d_mu = nullptr, *d_ap = nullptr, *d_zp = nullptr;   // challenge powers x^{j+1}
+    u64 *G[2] = {nullptr, nullptr}, *eqb = nullptr, *zz = nullptr;
+    FoldRoundArgs a;                       // the five special tables of the current round
+    u64 *T5[2] = {nullptr, nullptr};       // ... fixed ping-pong, 57 planes per buffer
+    const u64 *curF = nullptr;             // the materialised f-hat tables (null while they are virtual)
+    size_t ldF = 0;
+    u64 *eq0 = nullptr, *q = nullptr, *dpart = nullptr, *d_theta = nullptr, *d_eta = nullptr;
+    FoldStep(lf_ctx *c, Transcript &tr, SideState *S, u64 *proof);
+    u64 *msg(u32 round) const { return proof + (size_t)(round - 1) * (deg + 1) * 24; }
+    u64 *theta() const { return proof + (size_t)P.s * (deg + 1) * 24; }
+    u64 *eta() const { return theta() + (size_t)K2 * 72; }
+    // prepare
+    int powers_alpha_zeta();
+    int powers_mu();
+    int prepare_buffers();
+    int side_mz(int sd, hipStream_t st, u64 *zb, const char *zaos_name, size_t zc_lo, size_t zc_hi, size_t g_r0 = 0, size_t g_rcnt = (size_t)-1);
+    // rounds
+    void first_tables();
+    void fix_special(u32 round, Fq3Const r, u64 *dst, hipStream_t sg);
+    void set_tables(u64 *dst, size_t nn);
+    // evaluations, finish
+    int eval_buffers();
+    int gather_q(hipStream_t s1f);
+    int finish(u64 *lcccs_out, lf_witness **w_out, const std::function<int(const std::vector<int8_t> &rho8, int8_t *d_rho, int32_t *npl)> &fold_witness);
+};
 int sb_fold_round_abi(lf_ctx *c, const u64 *t5, const u64 *F, size_t n, const Fq3Const *d_mu, u64 *evals_out);
 int dot_batch_dev(lf_ctx *c, const u64 *X, size_t ldx, u32 na, const u64 *Y, size_t ldy, u32 nb, size_t n, u64 *dpart, u64 *od, hipStream_t st = nullptr,
                          const char *tag = "", unsigned char *yb_pre = nullptr);

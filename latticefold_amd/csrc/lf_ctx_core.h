@@ -58,7 +58,20 @@ struct CtxCoreBase {
     const lf_witness *vs_wit = nullptr;
     bool vs_keep = false;            // set by the fold step around its linearization: only there the decomposition that follows uses the same point
     uint64_t *vs_dev = nullptr;
-    hipEvent_t ev_prep[2] = {nullptr, nullptr};   // fold prepare: fork / join of the right side's chain on the other lane's stream
+    // Second-stream hand-off of the fold step (the helper lane's idle stream next to the caller's): fork(from, to) lets `to` continue behind what `from` has queued,
+    // guarded by ev_prep[0]; join(from, to) is the way back, guarded by ev_prep[1] (join_mark + join_wait where the wait comes later or inside a launcher).
+    // One stream on both ends: nothing to do.  The events are created once.
+    hipEvent_t ev_prep[2] = {nullptr, nullptr};
+    hipEvent_t prep_mark(int e, hipStream_t from) {   // nullptr: HIP error
+        for (int i = 0; i < 2; i++)
+            if (!ev_prep[i] && hipEventCreateWithFlags(&ev_prep[i], hipEventDisableTiming) != hipSuccess) return nullptr;
+        return hipEventRecord(ev_prep[e], from) == hipSuccess ? ev_prep[e] : nullptr;
+    }
+    int prep_wait(int e, hipStream_t to) { return hipStreamWaitEvent(to, ev_prep[e], 0) == hipSuccess ? LF_OK : LF_ERR_HIP; }
+    int fork(hipStream_t from, hipStream_t to) { return from == to ? LF_OK : (prep_mark(0, from) ? prep_wait(0, to) : LF_ERR_HIP); }
+    int join(hipStream_t from, hipStream_t to) { return from == to ? LF_OK : (prep_mark(1, from) ? prep_wait(1, to) : LF_ERR_HIP); }
+    hipEvent_t join_mark(hipStream_t from) { return prep_mark(1, from); }
+    int join_wait(hipStream_t to) { return prep_wait(1, to); }
     unsigned sv_round_mask = 0;      // rounds of the last folding sumcheck that ran as int8 GEMMs (bit i-1 = round i; lf_last_fold_paths)
     unsigned fold_split_mask = 0;    // table rounds of the last folding sumcheck that ran in the split eq form (lf_last_fold_split_rounds)
     // measurement

@@ -119,6 +119,8 @@ struct GoldV {
     static Ext ext_add(Ext a, Ext b) { return fq3_add(a, b); }
     static Ext ext_sub(Ext a, Ext b) { return fq3_sub(a, b); }
     Ext ext_inv(Ext a) const { return ring.inv3(a); }
+    static Ext ext_scale(Ext a, u64 k) { return fq3_make(fq_mul(a.c[0], k), fq_mul(a.c[1], k), fq_mul(a.c[2], k)); }   // times a base-field word
+    static u64 finv(u64 a) { return fq_inv(a); }
     static void absorb_ext(Tr &tr, Ext e) { tr.absorb_fq3_as_ring(e); }
     void crt(const u64 *c, u64 *o) const { ring.crt(c, o); }
     void icrt(const u64 *x, u64 *o) const { ring.icrt(x, o); }

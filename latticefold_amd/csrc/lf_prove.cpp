@@ -40,31 +40,28 @@ static int run_lin_sumcheck(lf_ctx *c, Transcript &tr, const u64 *mz, const u64 
     bool sharded = shard_keep(c, 0, m);
     u64 *od_dev = nullptr;
     if (Gw > 1) RET(c->tbuf("lin_round_out", (size_t)(deg + 1) * 24 + 8, &od_dev));   // (up to d + 2 = 9 points in the wide envelope)
-    // split form: while `split` is set, cure is the per-pair table E_i of the round i that ran last (in fe[(i - 1) & 1]) and c_lvl = c_i = prod_{k<i} eq(beta_k, r_k)
+    // split form: while `split` is set, cure is the per-pair table E_i of the round i that ran last (in fe[(i - 1) & 1]) and sp.c = c_i = prod_{k<i} eq(beta_k, r_k)
     const u32 dT = P.d;                                          // degree of T_i; the message has degree dT + 1 = deg
     const bool wide = P.t > 4 || P.d > 3;                        // k_lin_round_wide (lf_lin_wide.hip): per-round launches only, no persistent tail
     bool split = beta && Gw == 1 && !c->tn.lin_no_split && P.s >= 2 && m >= c->tn.lin_split_min && m >= 16 && dT >= 1 && deg <= 8;
-    Fq3 c_lvl = fq3_one();
-    auto f3zero = [](const Fq3 &x) { return !(x.c[0] | x.c[1] | x.c[2]); };
-    auto eq1 = [&](const Fq3 &b, const Fq3 &r) {   // eq(beta, r) = (1 - beta)(1 - r) + beta r
-        return fq3_add(c->ring.mul3(fq3_sub(fq3_one(), b), fq3_sub(fq3_one(), r)), c->ring.mul3(b, r));
-    };
+    const GoldV hv{c->ring};
+    lfs::SplitCoef<GoldV> sp = lfs::split_coef(hv, fq3_one(), beta ? beta[0] : fq3_one());   // c_i, beta_i and their inverses (round 1 divides by neither)
     if (split) RET(build_eq_dev(c, beta + 1, P.s - 1, fe[0]));   // E_1 = eq((beta_2..beta_s), .), m / 2 entries
     c->lin_split_rounds = 0;
     for (u32 round = 1; round <= P.s; round++) {
         if (split && round >= 2) {
             // stay in the split form?  Not into the persistent tail, not below the size where it pays, not when c_i or beta_i cannot be divided by
             const bool tail_next = !wide && !c->tn.no_tail && n <= c->tn.tail_n && n >= 4 && P.s - round + 1 <= TAIL_MAX_ROUNDS;
-            const Fq3 c_next = c->ring.mul3(c_lvl, eq1(beta[round - 2], point[round - 2]));
-            if (tail_next || n < 8 || n / 2 < c->tn.lin_split_min || f3zero(c_next) || f3zero(beta[round - 1])) {
+            const lfs::SplitCoef<GoldV> sp_next = lfs::split_coef(hv, c->ring.mul3(sp.c, lfs::eq1(hv, beta[round - 2], point[round - 2])), beta[round - 1]);
+            if (tail_next || n < 8 || n / 2 < c->tn.lin_split_min || !sp_next.ok) {
                 // back to the ordinary table of the previous round's n entries: eq(beta, (r_1..r_{i-1}, b, p)) = c_i eq(beta_i, b) E_i[p] at entry 2p + b
                 u64 *ex;
                 RET(c->tbuf("lin_eexp", 3 * n, &ex));
                 const Fq3 bi = beta[round - 2];
-                launch_eq_expand(c->dcrt, cure, n / 2, n / 2, f3c(c->ring.mul3(c_lvl, fq3_sub(fq3_one(), bi))), f3c(c->ring.mul3(c_lvl, bi)), ex, n, c->stream());
+                launch_eq_expand(c->dcrt, cure, n / 2, n / 2, f3c(c->ring.mul3(sp.c, fq3_sub(fq3_one(), bi))), f3c(c->ring.mul3(sp.c, bi)), ex, n, c->stream());
                 cure = ex;
                 split = false;
-            } else c_lvl = c_next;
+            } else sp = sp_next;
         }
         // persistent tail (k_lin_tail): all remaining rounds in one launch once the tables are small, as in the folding sumcheck
         if (!wide && !sharded && !c->tn.no_tail && round >= 2 && n <= c->tn.tail_n && n >= 4 && P.s - round + 1 <= TAIL_MAX_ROUNDS) {
@@ -118,64 +115,13 @@ static int run_lin_sumcheck(lf_ctx *c, Transcript &tr, const u64 *mz, const u64 
             // od[X][slot] = T(X) = sum_p E[p] h(X, p) at the evaluated X: complete the message g(X) = c_i eq(beta_i, X) T(X), X = 0..deg
             HostTimer ht2(c);
             c->lin_split_rounds++;
-            const Fq3 bi = beta[round - 1], obi = fq3_sub(fq3_one(), bi);
-            Fq3 wS[9];   // Lagrange weights of the previous message at r_{i-1} (nodes 0..deg <= 8)
-            Fq3 cinv = fq3_one(), binv = fq3_one();
-            if (round >= 2) {
-                const Fq3 x = point[round - 2];
-                for (u32 j = 0; j <= deg; j++) {
-                    Fq3 num = fq3_one();
-                    u64 den = 1;
-                    for (u32 k = 0; k <= deg; k++) {
-                        if (k == j) continue;
-                        num = c->ring.mul3(num, fq3_sub(x, fq3_make(k, 0, 0)));
-                        den = fq_mul(den, j > k ? (u64)(j - k) : LF_P - (u64)(k - j));
-                    }
-                    const u64 di = fq_inv(den);
-                    wS[j] = fq3_make(fq_mul(num.c[0], di), fq_mul(num.c[1], di), fq_mul(num.c[2], di));
-                }
-                cinv = c->ring.inv3(c_lvl);
-                binv = c->ring.inv3(bi);
-            }
-            const u64 *prev_ev = round >= 2 ? msgs + (size_t)(round - 2) * (deg + 1) * 24 : nullptr;
-            static const int binom[9][9] = {{1}, {1, 1}, {1, 2, 1}, {1, 3, 3, 1}, {1, 4, 6, 4, 1}, {1, 5, 10, 10, 5, 1}, {1, 6, 15, 20, 15, 6, 1}, {1, 7, 21, 35, 35, 21, 7, 1},
-                                            {1, 8, 28, 56, 70, 56, 28, 8, 1}};
-            for (u32 slot = 0; slot < 8; slot++) {
-                Fq3 T[9];
-                for (u32 X = 0; X <= dT; X++) T[X] = fq3_make(od[X * 24 + 3 * slot], od[X * 24 + 3 * slot + 1], od[X * 24 + 3 * slot + 2]);
-                if (round >= 2) {
-                    Fq3 S = fq3_zero();
-                    for (u32 j = 0; j <= deg; j++)
-                        S = fq3_add(S, c->ring.mul3(wS[j], fq3_make(prev_ev[j * 24 + 3 * slot], prev_ev[j * 24 + 3 * slot + 1], prev_ev[j * 24 + 3 * slot + 2])));
-                    // c (l(0) T(0) + l(1) T(1)) = S,  l(0) = 1 - beta_i, l(1) = beta_i
-                    T[1] = c->ring.mul3(fq3_sub(c->ring.mul3(S, cinv), c->ring.mul3(obi, T[0])), binv);
-                }
-                // T has degree dT: its value at dT + 1 from the dT + 1 below (the (dT+1)-th finite difference vanishes)
-                Fq3 top = fq3_zero();
-                for (u32 j = 0; j <= dT; j++) {
-                    Fq3 term = T[j];
-                    Fq3 acc = fq3_zero();
-                    for (int q = 0; q < binom[dT + 1][j]; q++) acc = fq3_add(acc, term);
-                    top = ((dT - j) & 1) ? fq3_sub(top, acc) : fq3_add(top, acc);
-                }
-                T[dT + 1] = top;
-                Fq3 l = obi;   // eq(beta_i, X) = (1 - beta_i) + X (2 beta_i - 1)
-                const Fq3 dl = fq3_sub(bi, obi);
-                for (u32 X = 0; X <= deg; X++) {
-                    const Fq3 g = c->ring.mul3(c->ring.mul3(c_lvl, l), T[X]);
-                    ev[X * 24 + 3 * slot] = g.c[0]; ev[X * 24 + 3 * slot + 1] = g.c[1]; ev[X * 24 + 3 * slot + 2] = g.c[2];
-                    l = fq3_add(l, dl);
-                }
-            }
+            lfs::complete_lin_split(hv, sp, dT, od, round >= 2 ? msgs + (size_t)(round - 2) * (deg + 1) * 24 : nullptr, point[round >= 2 ? round - 2 : 0], ev);
         } else
         memcpy(ev, od, (size_t)(deg + 1) * 24 * 8);
         HostTimer ht(c);
         point[round - 1] = lfs::sumcheck_round<GoldV>(tr, ev, deg + 1);
         if (after_round) (*after_round)(round);
-        if (round == 1) TL_MARK("  lin round 1");
-        if (round == 2) TL_MARK("  lin round 2");
-        if (round == 4) TL_MARK("  lin round 4");
-        if (round == 8) TL_MARK("  lin round 8");
+        if (round <= 2 || round == 4 || round == 8) TL_MARK_ROUND("  lin round", round);
     }
     TL_MARK("  lin rounds done");
     if (u_dev) launch_fix_final(c->dcrt, cur, P.t * 8, f3c(point[P.s - 1]), u_dev, c->stream());   // n == 2 here (ld 2)
@@ -228,10 +174,6 @@ int build_z(lf_ctx *c, const int32_t *planes, u32 K, int mode_bits, const u64 *h
     HIPCHK(hipMemcpy2DAsync(z, c->n * 8, stage, hl * 8, hl * 8, (size_t)K * 24, hipMemcpyDeviceToDevice, c->stream()));
     return LF_OK;
 }
-
-struct LinOut {
-    std::vector<Fq3> r;  // point
-};
 
 static int linearize_impl(lf_ctx *c, Transcript &tr, const u64 *cccs, const lf_witness *wit, u64 *lcccs_out, u64 *proof, u64 **eq_r_keep) {
     const lf_params &P = c->P;

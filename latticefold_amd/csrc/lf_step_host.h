@@ -4,7 +4,8 @@
 //
 // `V` is the ring's host policy (GoldV in lf_host.h, BbV in bb_host.h): a plain struct of small inline functions that REFERS to a host ring -- the context's in
 // the provers (a context may carry other tables than the default ring), the default one in lf_verify_host.  Functions that need the tables take `v`; the
-// others name the policy (`lfs::sumcheck_round<GoldV>(tr, ..)`).
+// others name the policy (`lfs::sumcheck_round<GoldV>(tr, ..)`).  The numeric host work inside the sumcheck rounds of the provers is here too: eq weights, the
+// digit look-up table, the completion of a split round message and its invertibility test.
 //
 // What belongs to a prover's schedule stays at its call sites: the HostTimer scopes and the host_tr_ms accounting, the timeline marks, the waits and
 // downloads in front of a call.
@@ -212,6 +213,149 @@ void fold_instance(const V &v, const lf_params &P, const std::vector<typename V:
     for (u32 c = 0; c < P.l + 1; c++, o += RE) {
         memset(o, 0, RE * 8);
         for (u32 i = 0; i < K2; i++) { v.mul(rho + (size_t)i * RE, part(i) + (x + c) * RE, tmp); V::add(o, tmp, o); }
+    }
+}
+
+// ---- the numeric host work inside the sumcheck rounds: eq weights, the digit look-up table, the completion of a split message -------------------------
+// An Ext of either ring is TAU canonical words `c`; a message is [X][RE] words with slot k at word TAU k.
+template <class V>
+bool ext_is_zero(const typename V::Ext &x) { return std::all_of(x.c, x.c + V::TAU, [](u64 w) { return w == 0; }); }
+template <class V>
+typename V::Ext ext_load(const u64 *w) {
+    typename V::Ext r;
+    for (int i = 0; i < V::TAU; i++) r.c[i] = w[i] % V::modulus();
+    return r;
+}
+template <class V>
+typename V::Ext eq1(const V &v, const typename V::Ext &b, const typename V::Ext &r) {   // eq(b, r) = (1 - b)(1 - r) + b r
+    const typename V::Ext one = V::ext_from_u64(1);
+    return V::ext_add(v.ext_mul(V::ext_sub(one, b), V::ext_sub(one, r)), v.ext_mul(b, r));
+}
+// W_b = eq((r_1..r_nbits), b) for the 2^nbits indices b, LSB-first (bit j of b goes with r_{j+1} = pt[j])
+template <class V>
+void eq_weights(const V &v, const typename V::Ext *pt, u32 nbits, typename V::Ext *W) {
+    const typename V::Ext one = V::ext_from_u64(1);
+    for (u32 b = 0; b < (1u << nbits); b++) {
+        W[b] = one;
+        for (u32 j = 0; j < nbits; j++) W[b] = v.ext_mul(W[b], ((b >> j) & 1) ? pt[j] : V::ext_sub(one, pt[j]));
+    }
+}
+// c_round = prod_{k < round} eq(beta_k, r_k) (rounds count from 1: beta_k = beta[k - 1], r_k = pt[k - 1])
+template <class V>
+typename V::Ext eq_prefix(const V &v, const typename V::Ext *beta, const typename V::Ext *pt, u32 round) {
+    typename V::Ext c = V::ext_from_u64(1);
+    for (u32 k = 1; k < round; k++) c = v.ext_mul(c, eq1(v, beta[k - 1], pt[k - 1]));
+    return c;
+}
+// Lagrange weights of the nodes 0..deg at x: p(x) = sum_j w[j] p(j) for a polynomial of degree <= deg
+template <class V>
+void lagrange_weights(const V &v, u32 deg, const typename V::Ext &x, typename V::Ext *w) {
+    for (u32 j = 0; j <= deg; j++) {
+        typename V::Ext num = V::ext_from_u64(1);
+        u64 den = 1;
+        for (u32 k = 0; k <= deg; k++) {
+            if (k == j) continue;
+            num = v.ext_mul(num, V::ext_sub(x, V::ext_from_u64(k)));
+            den = V::fmul(den, V::from_i64((int64_t)j - (int64_t)k));
+        }
+        w[j] = V::ext_scale(num, V::finv(den));
+    }
+}
+// lut[code] = sum_b (t_b - 1) W_b for the 81 codes sum_b t_b 3^b of four ternary digits, W_b = eq((r1, r2), b); out[81 + code] = its square
+template <class V>
+void fold_lut81(const V &v, const typename V::Ext &r1, const typename V::Ext &r2, typename V::Ext *out /* [162] */) {
+    const typename V::Ext pt[2] = {r1, r2};
+    typename V::Ext W[4];
+    eq_weights(v, pt, 2, W);
+    for (int code = 0; code < 81; code++) {
+        typename V::Ext x = V::ext_from_u64(0);
+        int cc = code;
+        for (int b = 0; b < 4; b++, cc /= 3) {
+            if (cc % 3 == 2) x = V::ext_add(x, W[b]);
+            else if (cc % 3 == 0) x = V::ext_sub(x, W[b]);
+        }
+        out[code] = x;
+        out[81 + code] = v.ext_mul(x, x);
+    }
+}
+// The split form of a round: the kernel sums against E_i[p] only, and the host completes g_i(X) = c_i eq(beta_i, X) T_i(X) (+ G(X)).  The value the kernel
+// leaves out follows from g_i(0) + g_i(1) = g_{i-1}(r_{i-1}) -- which divides by c_i and beta_i: `ok` is the one test of both completions (a driver that
+// finds it false runs the round unsplit).
+template <class V>
+struct SplitCoef {
+    typename V::Ext c, bi, cinv, binv;
+    bool ok;
+};
+template <class V>
+SplitCoef<V> split_coef(const V &v, const typename V::Ext &c, const typename V::Ext &bi) {
+    SplitCoef<V> s{c, bi, V::ext_from_u64(0), V::ext_from_u64(0), false};
+    if (ext_is_zero<V>(c) || ext_is_zero<V>(bi)) return s;
+    s.cinv = v.ext_inv(c);
+    s.binv = v.ext_inv(bi);
+    s.ok = !ext_is_zero<V>(s.cinv) && !ext_is_zero<V>(s.binv);
+    return s;
+}
+// shared tail of both completions: T(1) (slot-wise) from the previous message `prev` ([deg + 1][RE]) at its challenge x, less gsum = G(0) + G(1) if any
+template <class V>
+typename V::Ext split_T1(const V &v, const SplitCoef<V> &s, const typename V::Ext *wS, u32 deg, const u64 *prev, u32 slot, const typename V::Ext &T0,
+                         const typename V::Ext *gsum) {
+    typename V::Ext S = V::ext_from_u64(0);
+    for (u32 j = 0; j <= deg; j++) S = V::ext_add(S, v.ext_mul(wS[j], ext_load<V>(prev + (size_t)j * V::RE + V::TAU * slot)));
+    if (gsum) S = V::ext_sub(S, *gsum);
+    // c (l(0) T(0) + l(1) T(1)) = S,  l(0) = 1 - beta_i, l(1) = beta_i
+    return v.ext_mul(V::ext_sub(v.ext_mul(S, s.cinv), v.ext_mul(V::ext_sub(V::ext_from_u64(1), s.bi), T0)), s.binv);
+}
+template <class V>
+void split_store(const V &v, const SplitCoef<V> &s, u32 deg, const typename V::Ext *T, const u64 *G, u32 slot, u64 *out) {
+    const typename V::Ext obi = V::ext_sub(V::ext_from_u64(1), s.bi), dl = V::ext_sub(s.bi, obi);
+    typename V::Ext l = obi;   // eq(beta_i, X) = (1 - beta_i) + X (2 beta_i - 1)
+    for (u32 X = 0; X <= deg; X++) {
+        typename V::Ext g = v.ext_mul(v.ext_mul(s.c, l), T[X]);
+        if (G) g = V::ext_add(g, ext_load<V>(G + (size_t)X * V::RE + V::TAU * slot));
+        memcpy(out + (size_t)X * V::RE + V::TAU * slot, g.c, sizeof(g.c));
+        l = V::ext_add(l, dl);
+    }
+}
+// Folding sumcheck (degree 4): A [3][RE] = the sums A_e = sum_p E[p] Q_e(p), G [5][RE] = the G part eqL G1 + eqR G2 at X = 0..4, prev = the previous
+// message, x its challenge.  g(X) = c l(X) (A0 + A1 X + A2 X^2 + A3 X^3) + G(X), A3 from g(0) + g(1) = prev(x).  out [5][RE].
+template <class V>
+void complete_fold_split(const V &v, const SplitCoef<V> &s, const u64 *A, const u64 *G, const u64 *prev, const typename V::Ext &x, u64 *out) {
+    typedef typename V::Ext Ext;
+    constexpr u32 deg = 4;
+    Ext wS[deg + 1];
+    lagrange_weights(v, deg, x, wS);
+    for (u32 slot = 0; slot < 8; slot++) {
+        auto ld = [&](const u64 *b, u32 e) { return ext_load<V>(b + (size_t)e * V::RE + V::TAU * slot); };
+        const Ext A0 = ld(A, 0), A1 = ld(A, 1), A2 = ld(A, 2), gsum = V::ext_add(ld(G, 0), ld(G, 1));
+        const Ext T1 = split_T1(v, s, wS, deg, prev, slot, A0, &gsum);   // T(1) = A0 + A1 + A2 + A3
+        const Ext A3 = V::ext_sub(V::ext_sub(V::ext_sub(T1, A0), A1), A2);
+        Ext T[deg + 1];
+        for (u32 X = 0; X <= deg; X++) T[X] = V::ext_add(A0, V::ext_scale(V::ext_add(A1, V::ext_scale(V::ext_add(A2, V::ext_scale(A3, X)), X)), X));
+        split_store(v, s, deg, T, G, slot, out);
+    }
+}
+// Linearization sumcheck: Tv [dT + 1][RE] = T(X) = sum_p E[p] h(X, p) at X = 0..dT -- all of them in round 1 (prev = nullptr), X = 1 missing afterwards (from
+// prev, the previous message of degree dT + 1, at its challenge x).  T has degree dT <= 7: its value at dT + 1 from the vanishing (dT+1)-th finite
+// difference.  out [dT + 2][RE] = g(X) = c eq(beta_i, X) T(X).
+template <class V>
+void complete_lin_split(const V &v, const SplitCoef<V> &s, u32 dT, const u64 *Tv, const u64 *prev, const typename V::Ext &x, u64 *out) {
+    typedef typename V::Ext Ext;
+    static const int binom[9][9] = {{1}, {1, 1}, {1, 2, 1}, {1, 3, 3, 1}, {1, 4, 6, 4, 1}, {1, 5, 10, 10, 5, 1}, {1, 6, 15, 20, 15, 6, 1}, {1, 7, 21, 35, 35, 21, 7, 1},
+                                    {1, 8, 28, 56, 70, 56, 28, 8, 1}};
+    const u32 deg = dT + 1;
+    Ext wS[9];
+    if (prev) lagrange_weights(v, deg, x, wS);
+    for (u32 slot = 0; slot < 8; slot++) {
+        Ext T[9];
+        for (u32 X = 0; X <= dT; X++) T[X] = ext_load<V>(Tv + (size_t)X * V::RE + V::TAU * slot);
+        if (prev) T[1] = split_T1(v, s, wS, deg, prev, slot, T[0], nullptr);
+        Ext top = V::ext_from_u64(0);
+        for (u32 j = 0; j <= dT; j++) {
+            const Ext term = V::ext_scale(T[j], (u64)binom[dT + 1][j]);
+            top = ((dT - j) & 1) ? V::ext_sub(top, term) : V::ext_add(top, term);
+        }
+        T[dT + 1] = top;
+        split_store(v, s, deg, T, nullptr, slot, out);
     }
 }
 
