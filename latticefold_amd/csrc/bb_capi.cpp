@@ -107,18 +107,48 @@ int exchange_modsum(C *c, u64 *inout, size_t words) {
     return LF_OK;
 }
 
+// ---- arithmetic self-test: operands ----------------------------------------------------------------------------------
+// The kernels' bounds are bounds on the DEVICE word, the centred Montgomery word in [-H, H] (bb_field.cuh): canonical corners such as p - 1 or (p +- 1) / 2
+// are words at 27 % and 13 % of H and reach neither the top of a 64-bit column nor the pre-centring of mred.  The first operand pairs therefore put every pair
+// of the device-word grid below (tests/field_corners.py: EDGE_BW) into every pair of coordinate positions, followed by the saturating pairs -- a_i = +-H,
+// b_j = H for j <= k and nu b_j = H for j > k, so that column k is nine terms of +-H^2 -- of nu = 2 and of the context's nu; the rest are pseudo-random.
+namespace selftest_bb {
+constexpr int32_t H = BB_H, R32 = (int32_t)BB_R;
+constexpr int NG = 30;
+const int32_t GRID[NG] = {0, 1, -1, 2, -2, H, -H, H - 1, -(H - 1), H / 2, -(H / 2), H / 2 + 1, -(H / 2 + 1), R32, -R32, 1 << 29, -(1 << 29),
+                          0x3B7F7F7F, -0x3B7F7F7F, 0x3B808080, -0x3B808080, 0x007F7F7F, -0x00808080, 0x7F, -0x80, 0x80, -0x81, 0x7FFF, 0x8000, -0x8000};
+inline u64 pw(u64 a, u64 e) { u64 r = 1; a %= BB_P; while (e) { if (e & 1) r = r * a % BB_P; a = a * a % BB_P; e >>= 1; } return r; }
+inline u64 canon_of(int32_t w) { return (u64)((i64)w + (i64)BB_P) % BB_P * pw(BB_R, BB_P - 2) % BB_P; }   // device word -> canonical residue
+void operands(u64 seed, u32 n, u64 nu, std::vector<u64> &in) {
+    in.resize((size_t)n * 18);
+    u64 cg[NG];
+    for (int i = 0; i < NG; i++) cg[i] = canon_of(GRID[i]);
+    u32 i = 0;
+    for (int sh = 0; sh < TAU && i < n; sh++)
+        for (int x = 0; x < NG && i < n; x++)
+            for (int y = 0; y < NG && i < n; y++, i++)
+                for (int q = 0; q < TAU; q++) { in[(size_t)i * 18 + q] = cg[(x + q * sh) % NG]; in[(size_t)i * 18 + 9 + q] = cg[(y + 5 * q * sh) % NG]; }
+    const u64 nus[2] = {2, nu % BB_P};
+    for (int v = 0; v < 2; v++) {
+        const u64 hi = canon_of(H), half = nus[v] == 2 ? canon_of(H / 2) : hi * pw(nus[v], BB_P - 2) % BB_P;
+        for (int sg = 0; sg < 2; sg++)
+            for (int k = 0; k < TAU && i < n; k++, i++)
+                for (int q = 0; q < TAU; q++) { in[(size_t)i * 18 + q] = canon_of(sg ? -H : H); in[(size_t)i * 18 + 9 + q] = q <= k ? hi : half; }
+    }
+    u64 s = seed * 0x9E3779B97F4A7C15ULL + 1;
+    for (size_t k = (size_t)i * 18; k < in.size(); k++) {
+        s ^= s << 13; s ^= s >> 7; s ^= s << 17;
+        in[k] = s % BB_P;
+    }
+}
+}  // namespace selftest_bb
+
 int BbCtx::selftest_field(uint64_t seed, uint32_t n, uint64_t *mismatches) {
     C *c = p;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(hipSetDevice(c->device));
-    std::vector<u64> in((size_t)n * 18), out((size_t)n * 12);
-    u64 s = seed * 0x9E3779B97F4A7C15ULL + 1;
-    for (size_t i = 0; i < in.size(); i++) {
-        s ^= s << 13; s ^= s >> 7; s ^= s << 17;
-        in[i] = s % BB_P;
-    }
-    // edge operands in the first elements
-    for (int q = 0; q < 18 && n > 2; q++) { in[q] = (BB_P - 1) / 2; in[18 + q] = q < 9 ? (BB_P - 1) / 2 : (BB_P + 1) / 2; in[36 + q] = BB_P - 1; }
+    std::vector<u64> in, out((size_t)n * 12);
+    selftest_bb::operands(seed, n, c->ring.T.nu, in);
     u64 *di, *dout;
     RET(c->tbuf("io_a", in.size() * 2, (fe **)&di));
     RET(c->tbuf("io_b", out.size() * 2, (fe **)&dout));
