@@ -8,6 +8,7 @@
 //! | `PlusProof` `plus.rs:34-40`                             | [`PlusProof`]: the flat words of `lfplus.h`    |
 //! | `PlusParameters` `plus.rs:42-47`                        | [`PlusParameters`] (`sys::lfplus_params`)      |
 //! | `PoseidonTranscript<RqPoly>` `transcript.rs:20-78`      | [`HipPlusTranscript`]                          |
+//! | `MLSumcheck::{prove, verify}_as_subprotocol` `latticefold/src/utils/sumcheck.rs:53-104` | [`HipPlusMLSumcheck`] over a [`HipPlusVPoly`] |
 //!
 //! The ring is the one the reference runs latticefold-plus on (FrogRing `RqPoly`, coefficient form, 16 canonical words per element); `R: RingWords` with
 //! `WORDS == 16` marshals it.  The schedule of a prove -- which context holds which accumulator half, the upload thread, the refusal to continue after a
@@ -320,6 +321,72 @@ impl HipPlusContext {
             "lfplus_decompose_dev",
         )?;
         Ok([c0, c1, v0, v1])
+    }
+    /// `lfplus_ctx_create` alone: a BARE context (no matrix, no witness) -- all the generic sumcheck needs
+    pub fn bare(device: i32) -> Result<Self, HipPlusError> {
+        let mut raw = core::ptr::null_mut();
+        // SAFETY: raw receives an owned handle
+        let rc = unsafe { sys::lfplus_ctx_create(device, &mut raw) };
+        if rc != sys::LFPLUS_OK {
+            return Err(HipPlusError::new(rc, "lfplus_ctx_create", "no usable device"));
+        }
+        Ok(HipPlusContext { raw, kappa: 0 })
+    }
+}
+
+/// `VirtualPolynomial<RqPoly>` as the flat product list of `lfplus_vpoly` (`latticefold/src/utils/sumcheck/utils.rs:24-75`):
+/// g = sum_i coef_i prod_{k in terms[i]} T_k; `coef[i]` is one ring element (16 canonical words)
+#[derive(Debug, Clone)]
+pub struct HipPlusVPoly {
+    pub nvars: usize,
+    pub ntables: usize,
+    pub degree: usize,
+    pub terms: Vec<([u64; 16], Vec<u32>)>,
+}
+
+/// `MLSumcheck<RqPoly, _>` over any product list on the GPU (`lfplus_mlsumcheck_*`), under the reference's names (`latticefold/src/utils/sumcheck.rs:53-104`)
+pub struct HipPlusMLSumcheck;
+
+impl HipPlusMLSumcheck {
+    /// `MLSumcheck::prove_as_subprotocol`: `tables` = T x 2^nvars x 16 canonical words (table j first entry at `j * 2^nvars * 16`; variable 1 in bit 0 of the
+    /// entry index) -> (msgs: nvars x (degree + 1) x 16 words, point: nvars challenges, the T table values at the point)
+    pub fn prove_as_subprotocol(ctx: &mut HipPlusContext, transcript: &mut HipPlusTranscript, poly: &HipPlusVPoly, tables: &[u64])
+                                -> Result<(Vec<u64>, Vec<u64>, Vec<u64>), HipPlusError> {
+        if poly.nvars == 0 || poly.nvars > 28 || tables.len() != (poly.ntables << poly.nvars) * 16 {
+            return Err(HipPlusError::new(sys::LFPLUS_E_ARG, "prove_as_subprotocol", "tables: ntables x 2^nvars x 16 words, 1 <= nvars <= 28"));
+        }
+        let (mut off, mut idx, mut coef) = (vec![0u32], Vec::new(), Vec::new());
+        for (c, ix) in &poly.terms {
+            idx.extend_from_slice(ix);
+            off.push(idx.len() as u32);
+            coef.extend_from_slice(c);
+        }
+        idx.push(0);
+        let d = sys::lfplus_vpoly { nvars: poly.nvars as u32, ntables: poly.ntables as u32, nterms: poly.terms.len() as u32, degree: poly.degree as u32,
+                                    term_off: off.as_ptr(), term_idx: idx.as_ptr(), coef: coef.as_ptr() };
+        let mut msgs = vec![0u64; poly.nvars * (poly.degree + 1) * 16];
+        let (mut point, mut fin) = (vec![0u64; poly.nvars], vec![0u64; poly.ntables * 16]);
+        // SAFETY: live handles; d points into off / idx / coef, which outlive the call; tables and the outputs have the sizes lfplus.h documents (the library
+        // refuses a descriptor outside its envelope before it reads a table)
+        ctx.chk(unsafe { sys::lfplus_mlsumcheck_prove(ctx.raw, transcript.raw, &d, tables.as_ptr(), msgs.as_mut_ptr(), point.as_mut_ptr(), fin.as_mut_ptr()) },
+                "lfplus_mlsumcheck_prove")?;
+        Ok((msgs, point, fin))
+    }
+    /// `MLSumcheck::verify_as_subprotocol`, host only -> the subclaim (point, expected evaluation); `Err` with `is_reject()` and the failing round in `msg`
+    pub fn verify_as_subprotocol(transcript: &mut HipPlusTranscript, nvars: usize, degree: usize, claimed_sum: &[u64; 16], msgs: &[u64])
+                                 -> Result<(Vec<u64>, [u64; 16]), HipPlusError> {
+        if nvars == 0 || nvars > 28 || degree == 0 || degree > 8 || msgs.len() != nvars * (degree + 1) * 16 {
+            return Err(HipPlusError::new(sys::LFPLUS_E_ARG, "verify_as_subprotocol", "msgs: nvars x (degree + 1) x 16 words, 1 <= nvars <= 28, 1 <= degree <= 8"));
+        }
+        let (mut point, mut expected, mut round) = (vec![0u64; nvars], [0u64; 16], -1i32);
+        // SAFETY: live handle; the arrays have the sizes checked above
+        let rc = unsafe {
+            sys::lfplus_mlsumcheck_verify(transcript.raw, nvars as u32, degree as u32, claimed_sum.as_ptr(), msgs.as_ptr(), point.as_mut_ptr(), expected.as_mut_ptr(), &mut round)
+        };
+        if rc != sys::LFPLUS_OK {
+            return Err(HipPlusError::new(rc, "lfplus_mlsumcheck_verify", if rc == sys::LFPLUS_E_REJECT { format!("round {round}") } else { "bad arguments".into() }));
+        }
+        Ok((point, expected))
     }
 }
 impl Drop for HipPlusContext {

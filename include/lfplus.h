@@ -15,7 +15,8 @@
  *   PoseidonTranscript<RqPoly>, utils::short_challenge       src/transcript.rs:20-78, src/utils.rs:87-101
  *   In::set_check / Out::verify                      src/setchk.rs:65-262 / 266-340
  *   Rg::range_check / Dcom::verify                   src/rgchk.rs:81-186 / 193-258
- *   PlusProver::{init, prove} / PlusVerifier::{init, verify}   src/plus.rs:15-146   (lfplus_prover_*, lfplus_verify: the objects, at the end of this file)
+ *   PlusProver::{init, prove} / PlusVerifier::{init, verify}   src/plus.rs:15-146   (lfplus_prover_*, lfplus_verify: the objects, below)
+ *   MLSumcheck::{prove, verify}_as_subprotocol over any product list   latticefold/src/utils/sumcheck.rs:53-104   (lfplus_mlsumcheck_*, at the end of this file)
  *
  * M_f and m_tau are matrices / vectors of unit monomials; they cross this boundary as their EXPONENT digits (int8 in (-d/2, d/2)):
  * exp(a) = X^a for a >= 0 and X^(d + a) for a < 0.  The Rust binding rebuilds Matrix<R> from them if a caller needs the dense form
@@ -368,6 +369,68 @@ int lfplus_prover_wait_stream(lfplus_prover *prover, void *hip_stream);
 int lfplus_prover_ingest_dev(lfplus_prover *prover, const uint64_t *const *z, uint32_t count, uint64_t m, uint32_t l_in, uint64_t *cm_f_out);
 int lfplus_prover_set_instances_dev(lfplus_prover *prover, const uint64_t *const *f, const uint64_t *const *cm_f, uint32_t count);
 int lfplus_prover_accumulator_dev(lfplus_prover *prover, uint64_t *F0, uint64_t *F1);
+
+/* ---- MLSumcheck::prove_as_subprotocol / verify_as_subprotocol over ANY sum of products of MLE tables (latticefold utils/sumcheck.rs:53-104,
+ * sumcheck/prover.rs:56-162, sumcheck/verifier.rs:92-257; the VirtualPolynomial of sumcheck/utils.rs:24-75) on the Frog ring: the counterpart of
+ * lf_mlsumcheck_* (lfhip_sumcheck.h), field for field.  Every sumcheck of latticefold-plus is this one MLSumcheck with another comb function (r1cs.rs:90-95,
+ * cm.rs, setchk.rs); the three the slice runs keep their specialised kernels and digests, this is the call for every OTHER constraint shape over RqPoly.
+ *      g(x) = sum_{i < nterms} coef_i * prod_{k in [term_off[i], term_off[i+1])} T_{term_idx[k]}(x),      x in {0,1}^nvars,
+ * with negacyclic products in Z_p[X]/(X^16 + 1).  Tables are ntables x 2^nvars GENERAL ring elements in the layout of this header (coefficient form, 16 canonical
+ * words per element, AoS; table j at tables + j * 2^nvars * 16); entry x of a table has variable 1 in bit 0 of x (DenseMultilinearExtension: the first round
+ * fixes the lowest bit).  A constant-polynomial table (eq(r, .)) costs a full ring table and full products.  A challenge is ONE F_p word (RqPoly's base ring has
+ * extension degree 1): fix_variables is lo + r (hi - lo), coefficient by coefficient.
+ *   Independence.  The state and the buffers of this sumcheck are the context's own and nothing else's: it runs on a BARE context (no matrix, no witness), and on
+ * a loaded one it neither reads nor writes the resident witness, the lfplus_rg_from_f results, a pending lfplus_rg_from_f_async pass or the resident matrices.
+ * The caller's tables are never written, in either memory space.  lfplus_mlsumcheck_begin while a generic sumcheck is active replaces it; so does
+ * lfplus_mlsumcheck_prove, which leaves none behind.
+ *   Refusals of begin / prove, every one LFPLUS_E_ARG with a message in lfplus_last_error, in this order: a NULL argument; a table index >= ntables; term_off that
+ * does not start at 0 or is not strictly increasing (every term has at least one factor); a coefficient word >= p; anything outside the envelope stated on the
+ * fields below; a sharded context (a transport or lfplus_set_sharding_model); [_device: the pointer checks of the _dev section above;] a table word >= p (host tables
+ * are tested on the host before anything is enqueued, device tables by the first kernel that reads them: the flag it raises comes home before begin returns).
+ * Without a device: LFPLUS_E_NO_DEVICE (also for the NULL context such a caller holds).  Of the split form, LFPLUS_E_ARG as well: lfplus_mlsumcheck_round before
+ * a begin, with r_prev NULL in a later round or non-NULL in round 1, or after nvars rounds; lfplus_mlsumcheck_final before the last round; a challenge >= p.
+ *   After any refusal the context is usable.  A begin refused by the checks above leaves a sumcheck in progress as it was -- except one refused after the tables
+ * were touched (a device word >= p, an allocation failure: LFPLUS_E_HIP): that leaves none, and the next round is refused.  lfplus_mlsumcheck_prove refuses
+ * everything above before its first absorb: the transcript is untouched then. */
+typedef struct {
+    uint32_t nvars;            /* m = 2^nvars entries per table, 1 <= nvars <= 28 (the slice's n limit) */
+    uint32_t ntables;          /* T, 1..16 */
+    uint32_t nterms;           /* q, 1..16 */
+    uint32_t degree;           /* the degree the prover absorbs and sends degree+1 evaluations for; max_i |S_i| <= degree <= 8 */
+    const uint32_t *term_off;  /* q+1 offsets into term_idx; every term has 1..8 factors; term_off[q] <= 64 */
+    const uint32_t *term_idx;  /* table indices < T; an index may repeat inside a term (a square) and across terms */
+    const uint64_t *coef;      /* q ring elements, 16 canonical words each, any value including 0 */
+} lfplus_vpoly;
+/* The split form (the caller's transcript stays in charge between the rounds).  begin copies the descriptor, the coefficients and the tables into buffers of
+ * the context: the caller's arrays are free again when the call returns. */
+int lfplus_mlsumcheck_begin(lfplus_ctx *ctx, const lfplus_vpoly *poly, const uint64_t *tables /* T x m x 16 words */);
+/* the same with `tables` in memory of the context's device (spelled _device, as lf_mlsumcheck_begin_device is), under every rule of the _dev section above (unmanaged memory of the context's device, ONE allocation
+ * covering T * m * 128 bytes, 16-byte alignment, ordering by lfplus_ctx_wait_stream, return after the context's stream is synchronised).  The device layout is
+ * the resident layout: the array is copied once, by the kernel that tests its words, and is free again on return */
+int lfplus_mlsumcheck_begin_device(lfplus_ctx *ctx, const lfplus_vpoly *poly, const uint64_t *tables /* device */);
+/* round i = 1 .. nvars: fixes the previous variable at r_prev, then evaluates the round polynomial at 0 .. degree */
+int lfplus_mlsumcheck_round(lfplus_ctx *ctx, const uint64_t *r_prev /* ONE word; NULL in round 1 */, uint64_t *evals_out /* (degree+1) x 16 words */);
+/* valid after nvars rounds: fixes the last variable at r_last and returns every table's value at the whole point.  DEVIATION from ProverState
+ * (sumcheck/prover.rs), as lf_mlsumcheck_final: the reference leaves the MLEs fixed nvars - 1 times and each caller evaluates them next */
+int lfplus_mlsumcheck_final(lfplus_ctx *ctx, const uint64_t *r_last /* one word */, uint64_t *evals_out /* T x 16 words */);
+/* drops the state; always LFPLUS_OK (LFPLUS_E_ARG for a NULL context) */
+int lfplus_mlsumcheck_end(lfplus_ctx *ctx);
+/* prove_as_subprotocol in one call: absorb(nvars), absorb(degree) as constant polynomials, then per round absorb_slice(the degree+1 evaluations), get_challenge,
+ * absorb(the challenge as a constant polynomial) -- the schedule of every sumcheck of the slice.  msgs_out: nvars x (degree+1) x 16 words (the Proof);
+ * point_out: the nvars challenges; final_out (may be NULL): the T table values at the point, as lfplus_mlsumcheck_final.  The _device form reads the caller's
+ * device array IN PLACE (rounds 1 and 2; the fixed tables of round 2 onwards go to scratch of the context): no staging copy */
+int lfplus_mlsumcheck_prove(lfplus_ctx *ctx, lfplus_transcript *t, const lfplus_vpoly *poly, const uint64_t *tables, uint64_t *msgs_out, uint64_t *point_out,
+                            uint64_t *final_out);
+int lfplus_mlsumcheck_prove_device(lfplus_ctx *ctx, lfplus_transcript *t, const lfplus_vpoly *poly, const uint64_t *tables /* device */, uint64_t *msgs_out,
+                                uint64_t *point_out, uint64_t *final_out);
+/* verify_as_subprotocol on the host: no context, no GPU.  claimed_sum: one ring element; msgs: nvars x (degree+1) ring elements; point_out: nvars words;
+ * expected_out: one ring element, the subclaim's expected evaluation g(point) (written on LFPLUS_OK only).  The transcript runs over ALL rounds first, the checks
+ * follow (verifier.rs:92-139); interpolation is the coefficient-wise Lagrange form on the nodes 0 .. degree -- the one host body lfplus_r1cs_verify and
+ * lfplus_cm_verify run their sumcheck rounds through.  LFPLUS_OK with *round = -1, or LFPLUS_E_REJECT with *round = the index (from 0) of the first round whose
+ * p(0) + p(1) is not the running claim (round may be NULL).  A NULL argument, nvars == 0 or > 28, degree == 0 or > 8, a word >= p in claimed_sum or msgs ->
+ * LFPLUS_E_ARG, the transcript untouched */
+int lfplus_mlsumcheck_verify(lfplus_transcript *t, uint32_t nvars, uint32_t degree, const uint64_t *claimed_sum, const uint64_t *msgs, uint64_t *point_out,
+                             uint64_t *expected_out, int *round);
 
 #ifdef __cplusplus
 }

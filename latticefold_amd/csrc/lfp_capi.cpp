@@ -70,6 +70,7 @@ extern "C" void lfplus_ctx_destroy(lfplus_ctx *c) {
     c->A = nullptr;
     c->A_ref.reset();      // frees the matrix unless another context still shares it
     c->drop_mats();
+    lfp_mls_drop(c);
     for (void *p : {(void *)c->f, (void *)c->Df, (void *)c->mtau, (void *)c->comMf, (void *)c->tau, (void *)c->coms, (void *)c->part, (void *)c->g}) c->own_free(p);
     c->pool.clear();       // (every block is idle now: they go to the process-wide cache)
     if (c->err_d) (void)hipFree(c->err_d);

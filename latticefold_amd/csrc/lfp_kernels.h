@@ -124,6 +124,20 @@ void launch_cm_evals_c(const u64 *R, size_t ldr, size_t n, const u64 *eq, u32 nt
 // ---- ComR1CS::linearize (r1cs.rs:76-139): degree-3 round of eq (ga gb - gc); part: cm_round_blocks(half) * 64
 void launch_r1cs_round_fused(const u64 *E, const u64 *G, size_t ld, size_t half, u64 rM, u64 *Eo, u64 *Go, size_t ld_o, u64 *part, hipStream_t s);   // + fix_variables of the previous round (E / G: previous tables)
 void launch_r1cs_round(const u64 *E, const u64 *G, size_t ld, size_t half, u64 *part, hipStream_t s);
+// ---- the generic sumcheck (lfp_mlsumcheck.hip; lfplus_mlsumcheck_*): g = sum_i coef_i prod_{k in [off[i], off[i + 1])} T_{idx[k]} over nt ring tables [table][ld][16]
+struct MlsDesc {
+    u32 nt, nterms, degree;
+    uint8_t off[17], idx[64];
+    uint8_t cls[16];          // the coefficient of term i: MLS_ZERO (the term is skipped), MLS_ONE / MLS_MINUS_ONE (the constants: no coefficient product), MLS_GENERAL
+};
+enum { MLS_ZERO = 0, MLS_ONE = 1, MLS_MINUS_ONE = 2, MLS_GENERAL = 3 };
+u32 mls_round_blocks(size_t half, u32 cap);      // workgroups of a round over `half` pairs: 16 pairs each and pass, at most cap
+// one round: part[block][degree + 1][16] canonical block partials of the evaluations at 0 .. degree.  coef: nterms x 16 canonical words (device).  The fused form
+// reads the PREVIOUS tables (4 entries per new pair), fixes them at rM (Montgomery) on the way in and stores the fixed tables to out (ld_out entries per table)
+void launch_mls_round(const u64 *in, size_t ld_in, size_t half, const MlsDesc &d, const u64 *coef, u32 blocks, u64 *part, hipStream_t s);
+void launch_mls_round_fused(const u64 *in, size_t ld_in, size_t half, const MlsDesc &d, const u64 *coef, u64 rM, u64 *out, size_t ld_out, u32 blocks, u64 *part, hipStream_t s);
+// out[t][16] = in[t][0] + r (in[t][1] - in[t][0]) for t < nt: the last variable of every table
+void launch_mls_final(const u64 *in, size_t ld_in, u32 nt, u64 rM, u64 *out, hipStream_t s);
 // ---- relation checks (lfp_check.hip): R_ComR1CS (r1cs.rs:21-60), R_LinB (lin.rs:29-40)
 // *first_bad = min(*first_bad, smallest row r < nrows with ((M_0 f) (M_1 f) - M_2 f)[r] != 0); vals[q]: LfpMatrix::spmv_vals() of matrix q (const_coef[q] as there)
 void launch_r1cs_residual(const u32 *const *rowptr, const u32 *const *col, const u64 *const *vals, const int *const_coef, const u64 *f, size_t nrows, u64 *first_bad,

@@ -706,7 +706,65 @@ int sumcheck_verify(lfplus_transcript *tr, u32 nv, u32 deg, const u64 *msgs, u64
     *expected = cur;
     return 0;
 }
+// verify_as_subprotocol with RING-valued messages, coefficient by coefficient: THE host body of the sumcheck rounds of lfplus_cm_verify, lfplus_r1cs_verify and
+// lfplus_mlsumcheck_verify.  Transcript: absorb(nv), absorb(deg), per round absorb_slice(the deg + 1 evaluations), get_challenge, absorb(challenge); a round
+// holds when p(0) + p(1) is the running claim `cur` (in: the claimed sum), which then becomes p(challenge) by the Lagrange form on the nodes 0 .. deg (oracle
+// lfp_protocol.c ring_sumcheck_verify).  Returns -1 with cur = the expected evaluation, or the first failing round.  stop: return right behind the transcript
+// schedule of that round (the two protocol verifiers: their transcript stops where the oracle's does); otherwise the transcript runs over ALL rounds, as the
+// reference's does (the verifier absorbs every message before it checks, sumcheck/verifier.rs:92-139)
+int ring_sumcheck_rounds(lfplus_transcript *tr, u32 nv, u32 deg, const u64 *msgs, u64 *cur, u64 *point, bool stop) {
+    tr->absorb_const(nv);
+    tr->absorb_const(deg);
+    int bad = -1;
+    std::vector<u64> inv(deg + 1);
+    for (u32 i = 0; i <= deg; i++) {      // 1 / prod_{j != i} (i - j)
+        u64 den = 1;
+        for (u32 j = 0; j <= deg; j++) if (j != i) den = fmul(den, fsub((u64)i, (u64)j));
+        inv[i] = fpow(den, P - 2);
+    }
+    for (u32 rnd = 0; rnd < nv; rnd++) {
+        const u64 *m = msgs + (size_t)rnd * (deg + 1) * D;
+        tr->absorb_ring(m, deg + 1);
+        const u64 x = tr->challenge();
+        tr->absorb_const(x);
+        point[rnd] = x;
+        if (bad < 0) {
+            for (int ci = 0; ci < D; ci++) if (fadd(m[ci] % P, m[D + ci] % P) != cur[ci]) bad = (int)rnd;
+        }
+        if (bad >= 0) {
+            if (stop) return bad;
+            continue;
+        }
+        u64 wgt[9];
+        for (u32 i = 0; i <= deg; i++) {
+            u64 num = 1;
+            for (u32 j = 0; j <= deg; j++) if (j != i) num = fmul(num, fsub(x, (u64)j));
+            wgt[i] = fmul(num, inv[i]);
+        }
+        for (int ci = 0; ci < D; ci++) {
+            u64 v = 0;
+            for (u32 i = 0; i <= deg; i++) v = fadd(v, fmul(m[i * D + ci] % P, wgt[i]));
+            cur[ci] = v;
+        }
+    }
+    return bad;
+}
 }  // namespace
+
+// MLSumcheck::verify_as_subprotocol (latticefold utils/sumcheck.rs:84-104) for lfplus_mlsumcheck_prove's proofs, host only: no context, no GPU
+extern "C" int lfplus_mlsumcheck_verify(lfplus_transcript *tr, uint32_t nvars, uint32_t degree, const uint64_t *claimed_sum, const uint64_t *msgs, uint64_t *point_out,
+                                        uint64_t *expected_out, int *round) {
+    if (!tr || !claimed_sum || !msgs || !point_out || !expected_out) return LFPLUS_E_ARG;
+    if (nvars < 1 || nvars > 28 || degree < 1 || degree > 8) return LFPLUS_E_ARG;
+    if (!canonical(claimed_sum, D) || !canonical(msgs, (size_t)nvars * (degree + 1) * D)) return LFPLUS_E_ARG;
+    u64 cur[D];
+    memcpy(cur, claimed_sum, sizeof(cur));
+    const int bad = ring_sumcheck_rounds(tr, nvars, degree, msgs, cur, point_out, false);
+    if (round) *round = bad;
+    if (bad >= 0) return LFPLUS_E_REJECT;
+    memcpy(expected_out, cur, sizeof(cur));
+    return LFPLUS_OK;
+}
 
 // Out::verify (setchk.rs:266-340).  LFPLUS_OK = accepted, LFPLUS_E_REJECT with *stage = 1 / 2 (sumcheck), 3 (final evaluation)
 extern "C" int lfplus_set_check_verify(lfplus_transcript *tr, uint32_t nvars, uint32_t nmat, uint32_t ncols, uint32_t nvec, uint32_t nM, const uint64_t *msgs,
@@ -1260,23 +1318,7 @@ extern "C" int lfplus_cm_verify(lfplus_transcript *tr, uint32_t nvars, uint32_t 
             const u64 *proof = pass ? pb : pa, *evs = pass ? eb : ea;
             u64 *rop = ro + (size_t)pass * nvars;
             // verify_as_subprotocol with ring-valued messages: coefficient-wise, degree 2
-            tr->absorb_const(nvars);
-            tr->absorb_const(2);
-            for (u32 rnd = 0; rnd < nvars && !st; rnd++) {
-                const u64 *m = proof + (size_t)rnd * 3 * D;
-                tr->absorb_ring(m, 3);
-                const u64 x = tr->challenge();
-                tr->absorb_const(x);
-                rop[rnd] = x;
-                // Lagrange weights on the nodes 0, 1, 2
-                const u64 inv2 = fpow(2, P - 2), x1 = fsub(x, 1), x2 = fsub(x, 2);
-                const u64 w0 = fmul(fmul(x1, x2), inv2), w1 = fsub(0, fmul(x, x2)), w2 = fmul(fmul(x, x1), inv2);
-                for (int ci = 0; ci < D; ci++) {
-                    const u64 y0 = m[ci] % P, y1 = m[D + ci] % P, y2 = m[2 * D + ci] % P;
-                    if (fadd(y0, y1) != cur[ci]) { st = 6; break; }
-                    cur[ci] = fadd(fadd(fmul(y0, w0), fmul(y1, w1)), fmul(y2, w2));
-                }
-            }
+            if (ring_sumcheck_rounds(tr, nvars, 2, proof, cur, rop, true) >= 0) st = 6;
             if (st) break;
             // t0, t1 at ro: fold the tables along the point, variable 0 first
             u64 tz[2][D];
@@ -1461,27 +1503,7 @@ extern "C" int lfplus_r1cs_verify(lfplus_transcript *tr, uint32_t nvars, const u
     for (u32 j = 0; j < nvars; j++) r[j] = tr->challenge();
     int st = 0;
     u64 cur[D] = {0};
-    tr->absorb_const(nvars);
-    tr->absorb_const(3);
-    for (u32 rnd = 0; rnd < nvars && !st; rnd++) {
-        const u64 *m = msgs + (size_t)rnd * 4 * D;
-        tr->absorb_ring(m, 4);
-        const u64 x = tr->challenge();
-        tr->absorb_const(x);
-        ro[rnd] = x;
-        u64 wgt[4];   // Lagrange weights on the nodes 0..3
-        for (u32 i = 0; i < 4; i++) {
-            u64 num = 1, den = 1;
-            for (u32 j = 0; j < 4; j++) if (j != i) { num = fmul(num, fsub(x, (u64)j)); den = fmul(den, fsub((u64)i, (u64)j)); }
-            wgt[i] = fmul(num, fpow(den, P - 2));
-        }
-        for (int ci = 0; ci < D; ci++) {
-            if (fadd(m[ci] % P, m[D + ci] % P) != cur[ci]) { st = 1; break; }
-            u64 v = 0;
-            for (int i = 0; i < 4; i++) v = fadd(v, fmul(m[i * D + ci] % P, wgt[i]));
-            cur[ci] = v;
-        }
-    }
+    if (ring_sumcheck_rounds(tr, nvars, 3, msgs, cur, ro, true) >= 0) st = 1;
     if (!st) {
         tr->absorb_ring(evals, 4);
         const u64 e = eq_eval(r.data(), ro, nvars);

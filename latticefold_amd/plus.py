@@ -31,6 +31,12 @@ REL_CM, REL_R1CS, REL_V, REL_NORM = 1, 2, 4, 8      # lfplus.h LFPLUS_REL_*: the
 ABSENT = -128     # exponent digit of a zero entry of a monomial set (lfplus.h LFPLUS_ABSENT)
 
 
+class VPolyDesc(C.Structure):
+    """lfplus.h lfplus_vpoly"""
+    _fields_ = [("nvars", C.c_uint32), ("ntables", C.c_uint32), ("nterms", C.c_uint32), ("degree", C.c_uint32), ("term_off", C.POINTER(C.c_uint32)),
+                ("term_idx", C.POINTER(C.c_uint32)), ("coef", u64p)]
+
+
 def exported_symbols():
     """every symbol include/lfplus.h declares"""
     hdr = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "lfplus.h")).read()
@@ -109,6 +115,16 @@ def _lib():
         L.lfplus_commit_dev.argtypes = [vp, vp, C.c_uint64, u64p]
         L.lfplus_get_witness_dev.argtypes = [vp, vp, C.c_uint64]
         L.lfplus_decompose_dev.argtypes = [vp, C.c_uint64, u64p, u64p, C.c_uint32, u32pp, u32pp, u64pp, vp, vp, u64p, u64p, u64p, u64p]
+        # the generic sumcheck (lfplus_mlsumcheck_*)
+        dp = C.POINTER(VPolyDesc)
+        L.lfplus_mlsumcheck_begin.argtypes = [vp, dp, u64p]
+        L.lfplus_mlsumcheck_begin_device.argtypes = [vp, dp, vp]
+        L.lfplus_mlsumcheck_round.argtypes = [vp, u64p, u64p]
+        L.lfplus_mlsumcheck_final.argtypes = [vp, u64p, u64p]
+        L.lfplus_mlsumcheck_end.argtypes = [vp]
+        L.lfplus_mlsumcheck_prove.argtypes = [vp, vp, dp, u64p, u64p, u64p, u64p]
+        L.lfplus_mlsumcheck_prove_device.argtypes = [vp, vp, dp, vp, u64p, u64p, u64p]
+        L.lfplus_mlsumcheck_verify.argtypes = [vp, C.c_uint32, C.c_uint32, u64p, u64p, u64p, u64p, ip]
         _READY = True
     return L
 
@@ -872,6 +888,111 @@ def decomp_verify(dproof, cm_f, v, B, kappa=None, nM=None):
     if rc not in (0, E_REJECT):
         raise LfPlusError(rc, "lfplus_decomp_verify")
     return rc == 0, st.value
+
+
+# ---- MLSumcheck over any sum of products of MLE tables (latticefold utils/sumcheck.rs:53-104; lfplus_mlsumcheck_*) --------------------------------------
+class VPoly:
+    """VirtualPolynomial (utils/sumcheck/utils.rs:24-75) over a flat list of MLE tables: g = sum_i coef_i * prod_{j in indices_i} T_j.
+    terms: [(coef, [indices])], coef a ring element (16 canonical words) or a Python integer (the constant polynomial); an index may repeat inside a term and
+    across terms.  degree: what the prover sends degree + 1 evaluations for (default: the widest term)."""
+
+    def __init__(self, terms, degree=None):
+        self.terms = [(c, [int(j) for j in idx]) for c, idx in terms]
+        self.degree = max((len(idx) for _, idx in self.terms), default=0) if degree is None else int(degree)
+
+    def desc(self, nvars, ntables):
+        """the lfplus_vpoly of this polynomial (the arrays it points to stay alive with the returned object)"""
+        off = np.zeros(len(self.terms) + 1, dtype=np.uint32)
+        coef = np.zeros((max(len(self.terms), 1), D), dtype=np.uint64)
+        idx = []
+        for i, (c, ix) in enumerate(self.terms):
+            idx += ix
+            off[i + 1] = len(idx)
+            if isinstance(c, (int, np.integer)):
+                coef[i, 0] = int(c) % P
+            else:
+                coef[i] = np.asarray(c, dtype=np.uint64).reshape(D)
+        idx = np.asarray(idx + [0], dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        d = VPolyDesc(int(nvars), int(ntables), len(self.terms), self.degree, off.ctypes.data_as(u32p), idx.ctypes.data_as(u32p), coef.ctypes.data_as(u64p))
+        d._keep = (off, idx, coef)
+        return d
+
+
+def _mls_tables(ctx, tables):
+    """tables (T, 2^nvars, 16): a host array, or a device array on the context's device (read by the _dev calls) -> (T, nvars, pointer, is_device, keep-alive)"""
+    sh = tuple(tables.shape)
+    if len(sh) != 3 or sh[2] != D or sh[1] < 2 or sh[1] & (sh[1] - 1):
+        raise LfPlusError(E_ARG, "tables: (T, 2^nvars, 16)")
+    if api.is_device_array(tables):
+        if not tables.is_contiguous() or tables.element_size() != 8:
+            raise LfPlusError(E_ARG, "device tables must be contiguous with 8-byte elements")
+        ctx.wait_stream()
+        return sh[0], sh[1].bit_length() - 1, C.c_void_p(tables.data_ptr()), True, tables
+    a, p = _w(tables)
+    return sh[0], sh[1].bit_length() - 1, p, False, a
+
+
+class MLSumcheck:
+    """The split form of MLSumcheck::prove_as_subprotocol over any VPoly (lfplus_mlsumcheck_begin / _round / _final / _end), on a bare context or a loaded one:
+    prove_round / final / end with the caller's transcript in between.  tables: (T, 2^nvars, 16) canonical words, a numpy array or a device array"""
+
+    def __init__(self, ctx, tables, vpoly):
+        self.ctx, self.degree = ctx, vpoly.degree
+        self.ntables, self.nvars, p, dev, keep = _mls_tables(ctx, tables)
+        d = vpoly.desc(self.nvars, self.ntables)
+        ctx._chk((_lib().lfplus_mlsumcheck_begin_device if dev else _lib().lfplus_mlsumcheck_begin)(ctx.h, C.byref(d), p))
+
+    def prove_round(self, r_prev=None):
+        """round messages in order: r_prev = None in round 1, the previous challenge (one word) afterwards -> (degree + 1, 16)"""
+        o = np.zeros((self.degree + 1, D), dtype=np.uint64)
+        r = None if r_prev is None else C.byref(C.c_uint64(int(r_prev)))
+        self.ctx._chk(_lib().lfplus_mlsumcheck_round(self.ctx.h, r, o.ctypes.data_as(u64p)))
+        return o
+
+    def final(self, r_last):
+        """after the last round: every table's value at the whole point, (T, 16)"""
+        o = np.zeros((self.ntables, D), dtype=np.uint64)
+        r = C.c_uint64(int(r_last))
+        self.ctx._chk(_lib().lfplus_mlsumcheck_final(self.ctx.h, C.byref(r), o.ctypes.data_as(u64p)))
+        return o
+
+    def end(self):
+        self.ctx._chk(_lib().lfplus_mlsumcheck_end(self.ctx.h))
+
+
+def mlsumcheck_prove(ctx, transcript, tables, vpoly):
+    """prove_as_subprotocol in one call (lfplus_mlsumcheck_prove; a device array is read in place by lfplus_mlsumcheck_prove_device) ->
+    (msgs (nvars, degree + 1, 16), point (nvars,), final (T, 16): the tables' values at the point)"""
+    T, nv, p, dev, keep = _mls_tables(ctx, tables)
+    d = vpoly.desc(nv, T)
+    msgs, point, fin = np.zeros((nv, vpoly.degree + 1, D), dtype=np.uint64), np.zeros(nv, dtype=np.uint64), np.zeros((T, D), dtype=np.uint64)
+    f = _lib().lfplus_mlsumcheck_prove_device if dev else _lib().lfplus_mlsumcheck_prove
+    ctx._chk(f(ctx.h, transcript.h, C.byref(d), p, msgs.ctypes.data_as(u64p), point.ctypes.data_as(u64p), fin.ctypes.data_as(u64p)))
+    return msgs, point, fin
+
+
+def mlsumcheck_verify(transcript, nvars, degree, claimed_sum, msgs):
+    """verify_as_subprotocol on the host (lfplus_mlsumcheck_verify: no GPU, no context) -> (ok, point (nvars,), expected): expected is the subclaim's ring
+    element g(point), or the index of the first failing round when ok is False"""
+    if not isinstance(nvars, (int, np.integer)) or not isinstance(degree, (int, np.integer)) or not 1 <= int(nvars) <= 28 or not 1 <= int(degree) <= 8:
+        raise LfPlusError(E_ARG, "mlsumcheck_verify: nvars outside [1, 28] or degree outside [1, 8]")
+    cs, pc = _w(claimed_sum)
+    m = _shaped({"msgs": msgs}, "msgs", (int(nvars), int(degree) + 1, D))
+    if cs.shape != (D,):
+        raise LfPlusError(E_ARG, "mlsumcheck_verify: claimed_sum is one ring element")
+    point, exp, rnd = np.zeros(int(nvars), dtype=np.uint64), np.zeros(D, dtype=np.uint64), C.c_int(-1)
+    rc = _lib().lfplus_mlsumcheck_verify(transcript.h, int(nvars), int(degree), pc, m.ctypes.data_as(u64p), point.ctypes.data_as(u64p), exp.ctypes.data_as(u64p),
+                                         C.byref(rnd))
+    if rc not in (0, E_REJECT):
+        raise LfPlusError(rc, "lfplus_mlsumcheck_verify")
+    return rc == 0, point, (exp if rc == 0 else rnd.value)
+
+
+def mlsumcheck_extract_sum(msgs):
+    """MLSumcheck::extract_sum (utils/sumcheck.rs:46-48): the claimed sum a proof is about, p_1(0) + p_1(1)"""
+    m = np.asarray(msgs, dtype=np.uint64).reshape(-1, D)
+    return ((m[0].astype(object) + m[1].astype(object)) % P).astype(np.uint64)
 
 
 def mlin(ctxs, transcript, params, M=()):

@@ -57,7 +57,7 @@ def rust_type(ctype):
     name = " ".join(base)
     if name in SCALARS:
         r = SCALARS[name]
-    elif name in OPAQUE or name in ("lf_params", "lfplus_params", "lf_vpoly"):
+    elif name in OPAQUE or name in ("lf_params", "lfplus_params", "lf_vpoly", "lfplus_vpoly"):
         r = name
     elif name in ("lf_exchange_fn", "lfplus_exchange_fn"):
         r = "lf_exchange_fn"
@@ -78,7 +78,7 @@ def split_params(s):
     for i, p in enumerate(x.strip() for x in s.split(",")):
         m = re.match(r"^(.*?)([A-Za-z_][A-Za-z_0-9]*)?$", p)
         ctype, name = m.group(1).strip(), m.group(2)
-        if name in SCALARS or name in OPAQUE or name in ("lf_params", "lfplus_params", "lf_vpoly", "lf_exchange_fn", "lfplus_exchange_fn", "unsigned", "const") or not ctype:   # unnamed parameter
+        if name in SCALARS or name in OPAQUE or name in ("lf_params", "lfplus_params", "lf_vpoly", "lfplus_vpoly", "lf_exchange_fn", "lfplus_exchange_fn", "unsigned", "const") or not ctype:   # unnamed parameter
             ctype, name = p, None
         if name is None:
             base = re.findall(r"[A-Za-z_][A-Za-z_0-9]*", ctype)[-1]
@@ -129,6 +129,9 @@ def generate():
           "/// PlusParameters with LinParameters / DecompParameters flattened (latticefold-plus plus.rs:43-47, lin.rs:24-28, rgchk.rs:20-24)",
           "#[repr(C)] #[derive(Clone, Copy, Debug)]",
           "pub struct lfplus_params { pub kappa: u32, pub k: u32, pub l: u32, pub b: u64, pub B: u64 }",
+          "/// VirtualPolynomial over RqPoly as a flat product list (latticefold utils/sumcheck/utils.rs:24-75; lfplus_mlsumcheck_*): 16 words per coefficient",
+          "#[repr(C)] #[derive(Clone, Copy, Debug)]",
+          "pub struct lfplus_vpoly { pub nvars: u32, pub ntables: u32, pub nterms: u32, pub degree: u32, pub term_off: *const u32, pub term_idx: *const u32, pub coef: *const u64 }",
           "/// all-gather `words` u64 from every rank into recv_all[world * words] in rank order; 0 on success (lf_set_sharding)",
           "pub type lf_exchange_fn = Option<unsafe extern \"C\" fn(user: *mut c_void, send: *const u64, recv_all: *mut u64, words: usize) -> c_int>;", ""]
     allfns = []
