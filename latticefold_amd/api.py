@@ -614,6 +614,18 @@ class Context:
         _chk(_lib().lf_last_lin_split_rounds(self.h, C.byref(m)), "lf_last_lin_split_rounds")
         return m.value
 
+    def live_rows(self):
+        """1 + the last row with an entry in any matrix of the loaded CCS (the rows behind it are skipped) -- test hook, not part of the ABI"""
+        f = _lib().lfdbg_live_rows
+        f.argtypes, f.restype = [C.c_void_p], C.c_longlong
+        return f(self.h)
+
+    def lin_live_rounds(self):
+        """rounds of the last linearization sumcheck that ran over a live prefix of their tables only -- test hook, not part of the ABI"""
+        f = _lib().lfdbg_last_lin_live_rounds
+        f.argtypes, f.restype = [C.c_void_p], C.c_int
+        return f(self.h)
+
     def fold_split_rounds(self):
         """mask (bit i-1 = round i) of the table rounds of the last folding sumcheck that ran in the split eq form -- test hook"""
         m = C.c_uint()

@@ -1133,6 +1133,16 @@ int lf_debug_i8_prof(uint64_t *out64) {   // (LF_I8G_PROF set: the table of the 
 extern "C" int lfdbg_i8g_wg(unsigned int *out512) { return out512 ? ajtai_i8g_read_wg(out512) : -1; }
 // (not part of the ABI: tests) digit planes the gadget commitments use for a power-of-two base (ring: LF_RING_*)
 extern "C" unsigned lfdbg_i8g_planes_base(int ring, uint64_t base) { return ajtai_i8g_planes_base(ring == LF_RING_BABYBEAR ? ajtai_i8_babybear() : ajtai_i8_goldilocks(), base); }
+// (not part of the ABI: tests) the trailing-empty-row schedule of lf_live_rows.h: live_rows of the loaded CCS (-1: none / BabyBear), of host row pointers, and the
+// live entries of the linearization tables of rounds 1 .. rounds for m rows (low != 0: the LF_LIVE_ROWS_LOW threshold and granule); the rounds of the last
+// linearization that ran on a live prefix
+extern "C" long long lfdbg_live_rows(lf_ctx *c) { return c && !c->bb && c->have_ccs ? (long long)c->live_rows : -1; }
+extern "C" size_t lfdbg_live_rows_csr(unsigned t, size_t m, const uint32_t *const *rowptr) { return lflive::live_rows(t, m, rowptr); }
+extern "C" void lfdbg_live_schedule(size_t m, size_t live, int low, unsigned rounds, size_t *out) {
+    const lflive::Plan p = low ? lflive::plan(m, live, lflive::GRANULE_LOW, lflive::MIN_M_LOW) : lflive::plan(m, live, lflive::GRANULE, lflive::MIN_M);
+    for (unsigned i = 1; i <= rounds; i++) out[i - 1] = lflive::entries(p, i);
+}
+extern "C" int lfdbg_last_lin_live_rounds(lf_ctx *c) { return c && !c->bb ? (int)c->lin_live_rounds : -1; }
 int lf_last_fold_paths(lf_ctx *c, unsigned *sv_round_mask) {
     if (!c || !sv_round_mask) return LF_ERR_INVALID;
     *sv_round_mask = c->core_any().sv_round_mask;

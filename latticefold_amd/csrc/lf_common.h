@@ -94,6 +94,8 @@ struct Tunables {
     bool fold_sv_no_split = false;    // LF_FOLD_SV_NO_SPLIT: GEMM rounds against the digits of eqB(2p), eqB(2p+1) (three column tiles) instead of the per-pair E_i[p] (two)
     bool lin_no_split = false;        // LF_LIN_NO_SPLIT: linearization rounds on the full eq table (k_lin_round evaluates every point) instead of the split form
     size_t lin_split_min = (size_t)1 << 17;   // LF_LIN_SPLIT_MIN: entries of a round's tables from which the split form is used (at 2^16 rows the host's completion costs what the kernel saves)
+    bool no_live_rows = false;        // LF_NO_LIVE_ROWS: M z, the linearization rounds and G over all m rows, G in two launches (no skipping of the trailing empty rows of the constraint matrices)
+    bool live_rows_low = false;       // LF_LIVE_ROWS_LOW: skip the trailing empty rows from m = 16 on with a granule of 8 rows (default: from m = 2^14, granule 4096) -- tiny shapes run the truncated rounds
     size_t fold_split_min = 8192;     // LF_FOLD_SPLIT_MIN: pairs of a table round (modes 6 / 7) from which it runs in the split form
     bool force_exchange = false;     // LF_DIST_FORCE_EXCHANGE: run the sharded exchanges even with a 1-rank RCCL communicator (test hook)
     bool device_transcript = false;  // LF_DEVICE_TRANSCRIPT: Poseidon sponge of the tail rounds on the device (opt-in: slower than the host's)
@@ -127,6 +129,8 @@ struct Tunables {
         t.fold_no_r5tab = getenv("LF_FOLD_NO_R5TAB") != nullptr;
         t.lin_no_split = getenv("LF_LIN_NO_SPLIT") != nullptr;
         t.fold_sv_no_split = getenv("LF_FOLD_SV_NO_SPLIT") != nullptr;
+        t.no_live_rows = getenv("LF_NO_LIVE_ROWS") != nullptr;
+        t.live_rows_low = getenv("LF_LIVE_ROWS_LOW") != nullptr;
         t.fold_rounds_no_split = getenv("LF_FOLD_ROUNDS_NO_SPLIT") != nullptr;
         if (const char *e = getenv("LF_LIN_SPLIT_MIN")) t.lin_split_min = (size_t)atoll(e);
         if (const char *e = getenv("LF_FOLD_SPLIT_MIN")) t.fold_split_min = (size_t)atoll(e);

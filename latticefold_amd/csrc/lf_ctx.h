@@ -24,6 +24,7 @@
 #include "lf_common.h"
 #include "lf_dist.h"
 #include "lf_kernels.h"
+#include "lf_live_rows.h"
 #include "lf_sb.h"
 #include "lf_verify.h"
 
@@ -166,6 +167,12 @@ struct lf_ctx : CtxCore<u64> {
     lfdist::Comm comm[2];
     lfdist::Comm &cm() { assert(t_lane < 2); return comm[t_lane]; }
     bool ccs_general = false;   // some constraint matrix has more than ~1.5 entries per (non-empty) row: M z runs on k_spmv_rows (whole-element gathers from an element-major z)
+    size_t live_rows = 0;       // 1 + the last row with an entry in any constraint matrix (lf_live_rows.h; fixed at lf_ccs_load): the rows behind it are zeros of every M_j z
+    // the padded live prefix the linearization and the G tables of this call work on (the switches are read per call); sharded contexts keep whole tables
+    lflive::Plan live_plan() const {
+        if (tn.no_live_rows || sh_world > 1) return lflive::plan(m, m, 0, 0);
+        return tn.live_rows_low ? lflive::plan(m, live_rows, lflive::GRANULE_LOW, lflive::MIN_M_LOW) : lflive::plan(m, live_rows, lflive::GRANULE, lflive::MIN_M);
+    }
     // sharded step: the columns of z this rank's row slice of the constraint matrices refers to (shard_col_range; (size_t)-1 = not computed)
     size_t shc_r0 = (size_t)-1, shc_rcnt = 0, shc_lo = 0, shc_hi = 0;
     LinCombDesc desc{};
@@ -190,6 +197,7 @@ struct lf_ctx : CtxCore<u64> {
     hipEvent_t ev_aux = nullptr;
     u64 *h_aux = nullptr;   // pinned, 1 KB: the known part of the point
     unsigned lin_split_rounds = 0;   // rounds of the last linearization sumcheck that ran in the split eq form (run_lin_sumcheck)
+    unsigned lin_live_rounds = 0;    // ... and those that ran over a live prefix of their tables only (lf_live_rows.h)
 
     // Small host-to-device uploads inside a step (challenge powers, look-up tables, evaluation points) go through a pinned ring per lane:
     // the copy is truly asynchronous and the caller's stack / vector buffer is free at once -- no stream synchronisation per upload.

@@ -314,8 +314,18 @@ int FoldB2::prepare() {
         u64 *zz1 = zz;
         if (s1 != s0) RET(c->tbuf("fold_zz1", (size_t)P.t * 24 * n, &zz1));
         RET(c->fork(s0, s1));           // the challenge powers were uploaded on s0
+        // one-entry-per-row matrices, t <= 4, whole tables: both sums in ONE pass that writes each row of G once (k_g_rows) and does not look up the trailing
+        // empty rows of the matrices; otherwise G = M zb (k_spmv_rows / k_spmv_sum), then read back and completed by k_add_fhat_comb
+        const bool one_pass = !c->tn.no_live_rows && !c->ccs_general && P.t <= 4 && !shard_tabs && c->sh_world == 1 && N <= m;
         for (int sd = 0; sd < 2; sd++) {
             hipStream_t st = sd ? s1 : s0;
+            if (one_pass) {
+                u64 *zb = sd ? zz1 : zz;
+                launch_lincomb_z(c->dcrt, S[sd].z, n, K, d_zp + (size_t)sd * K * P.t, P.t, n, zb, st);
+                launch_g_rows(c->dcrt, P.t, c->d_rowptr.data(), c->d_col.data(), c->d_val.data(), zb, (size_t)24 * n, n, c->live_rows, S[sd].planes, N, K,
+                              d_ap + (size_t)sd * K * 3, G[sd], m, st);
+                continue;
+            }
             RET(side_mz(sd, st, sd ? zz1 : zz, sd ? "spmv_zaos_R" : "spmv_zaos_L", zc_lo, zc_hi, g_r0, g_rcnt));
             launch_add_fhat_comb(c->dcrt, S[sd].planes, N, K, d_ap + (size_t)sd * K * 3, G[sd], m, st, g_r0, g_rcnt);
         }

@@ -119,6 +119,9 @@ void launch_lincomb_z(const DevCrt &t, const u64 *z, size_t ldz, u32 K, const Fq
 // G[row][slot] += sum_{k<K} sum_{d<3} apow[k][d] * digit_k(planes[8d+slot][row])   (rows < n_planes)
 void launch_add_fhat_comb(const DevCrt &t, const int32_t *planes, size_t n_planes, u32 K, const Fq3Const *apow_dev /*K*3*/,
                           u64 *G, size_t m, hipStream_t s, size_t r0 = 0, size_t rcnt = (size_t)-1 /* all positions */);
+// both in one pass over the m rows of G (nm <= 4, n_planes <= m):  G[row] = (row < live ? sum_j M_j z_j : 0) + the f-hat combination; G is only written
+void launch_g_rows(const DevCrt &t, u32 nm, const u32 *const *rowptr, const u32 *const *col, const u64 *const *val, const u64 *z, size_t z_stride, size_t ldz, size_t live,
+                   const int32_t *planes, size_t n_planes, u32 K, const Fq3Const *apow_dev /*K*3*/, u64 *G, size_t m, hipStream_t s);
 
 // ---- sumcheck (a10) ---------------------------------------------------------------------------------------------
 // generic in-place-free fix: ring tables and fq3 tables, new[j] = old[2j] + r*(old[2j+1]-old[2j])

@@ -800,6 +800,69 @@ void launch_add_fhat_comb(const DevCrt &t, const int32_t *planes, size_t n_plane
     if (K <= 16) hipLaunchKernelGGL(k_add_fhat_comb<4>, dim3(cdiv(r1 - r0, 256), 8), dim3(256), 0, s, planes, n_planes, K, apow_dev, G, m, r0, r1);
     else hipLaunchKernelGGL(k_add_fhat_comb<8>, dim3(cdiv(r1 - r0, 256), 8), dim3(256), 0, s, planes, n_planes, K, apow_dev, G, m, r0, r1);
 }
+// The whole row of G in one pass (fold prepare, t <= 4, one-entry-per-row matrices):  G[row] = (row < live ? sum_j M_j z_j : 0) + sum_k sum_d alpha_k^{d+1} fhat_{k,d}[row]
+// -- k_spmv_sum's gather and k_add_fhat_comb's nibble tables in one thread, the same additions in the same order.  G is written once and not read back; the rows
+// from `live` on are empty in every M_j (lf_live_rows.h) and are not looked up.  Rows [0, m), witness positions [0, n_planes), n_planes <= m.
+template <bool NU, int NQ>
+__global__ void __launch_bounds__(256) k_g_rows(DevCrt t, SpmvSet ms, size_t ldz, size_t live, const int32_t *planes, size_t n_planes, u32 K, const Fq3Const *apow, u64 *G,
+                                                size_t m) {
+    __shared__ u64 T[3 * NQ * 16][4];
+    for (u32 e = threadIdx.x; e < 3 * NQ * 16; e += 256) {
+        u32 val = e % 16, q = (e / 16) % NQ, d = e / (16 * NQ);
+        Fq3 sum = fq3_zero();
+        for (u32 b = 0; b < 4; b++)
+            if (4 * q + b < K && ((val >> b) & 1)) {
+                Fq3Const a = apow[(4 * q + b) * 3 + d];
+                sum = fq3_add(sum, fq3_make(a.c[0], a.c[1], a.c[2]));
+            }
+        T[e][0] = sum.c[0]; T[e][1] = sum.c[1]; T[e][2] = sum.c[2]; T[e][3] = 0;
+    }
+    __syncthreads();
+    const size_t row = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const u32 slot = blockIdx.y;
+    if (row >= m) return;
+    Fq3 acc = fq3_zero();
+    if (row < live) {
+#pragma unroll
+        for (u32 j = 0; j < 4; j++) {
+            if (j < ms.nm) {
+                const u32 *rp = ms.rowptr[j], *cl = ms.col[j];
+                for (u32 k = rp[row]; k < rp[row + 1]; k++) {
+                    const u64 *v = ms.val[j] + (size_t)k * 24 + 3 * slot;
+                    acc = fq3_add(acc, M3<NU>(fq3_make(v[0], v[1], v[2]), ld3(ms.z[j], ldz, slot, cl[k]), t.nu));
+                }
+            }
+        }
+    }
+    if (row < n_planes) {
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            int32_t v = planes[(size_t)(8 * d + slot) * n_planes + row];
+            u32 mg = (u32)(v < 0 ? -v : v);
+            Fq3 part = fq3_zero();
+#pragma unroll
+            for (int q = 0; q < NQ; q++) {
+                const u64 *e = T[(d * NQ + q) * 16 + ((mg >> (4 * q)) & 15)];
+                part = fq3_add(part, fq3_make(e[0], e[1], e[2]));
+            }
+            acc = v < 0 ? fq3_sub(acc, part) : fq3_add(acc, part);
+        }
+    }
+    st3(G, m, slot, row, acc);
+}
+void launch_g_rows(const DevCrt &t, u32 nm, const u32 *const *rowptr, const u32 *const *col, const u64 *const *val, const u64 *z, size_t z_stride, size_t ldz, size_t live,
+                   const int32_t *planes, size_t n_planes, u32 K, const Fq3Const *apow_dev, u64 *G, size_t m, hipStream_t s) {
+    if (!m || nm > 4 || n_planes > m) return;   // (callers keep the two-launch form for more than four matrices)
+    SpmvSet ms = {};
+    ms.nm = nm;
+    for (u32 j = 0; j < nm; j++) { ms.rowptr[j] = rowptr[j]; ms.col[j] = col[j]; ms.val[j] = val[j]; ms.z[j] = z + (size_t)j * z_stride; }
+    if (live > m) live = m;
+    const dim3 grid(cdiv(m, 256), 8);
+#define LF_GR(NUV, NQ) hipLaunchKernelGGL((k_g_rows<NUV, NQ>), grid, dim3(256), 0, s, t, ms, ldz, live, planes, n_planes, K, apow_dev, G, m)
+    if (K <= 16) { if (t.nu2p40) LF_GR(true, 4); else LF_GR(false, 4); }
+    else { if (t.nu2p40) LF_GR(true, 8); else LF_GR(false, 8); }
+#undef LF_GR
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // fix_variables (DenseMultilinearExtension, sumcheck/prover.rs:70-72): new[j] = old[2j] + r*(old[2j+1]-old[2j])

@@ -16,8 +16,14 @@
 // beta (optional): the point of eqb.  With it the large rounds of an unsharded run use the split form of the eq factor (k_lin_round SPLIT): the kernel sums
 // E_i[p] h(X, p) at d of the d + 2 points and the host completes the message -- g_i(X) = c_i eq(beta_i, X) T_i(X), T_i(1) from g_i(0) + g_i(1) = g_{i-1}(r_{i-1}),
 // the top point by extrapolation of the degree-d T_i -- in exact field arithmetic: the words of the reference's message.
+// live (optional, < m; lf_live_rows.h): only the first `live` entries of the mz tables are written, the rest is taken as zero -- the rounds then run over the live
+// pairs alone and the fused rounds write the live prefix of the fixed tables, halved exactly from round to round.  The invariant: every table word a later kernel
+// reads was either written by the previous pass or is explicitly zero.  Whatever takes whole tables (the persistent tail, the non-fused small rounds, k_fix_final;
+// a prefix that no longer halves into whole pairs) is preceded by ONE zero-fill of the rest of the current tables -- mz's own rest when that is round 2, so a
+// caller that passes `live` owns mz.  The eq tables (the fixed table, or the per-pair E_i of the split form) are dense and stay WHOLE: the entry past the prefix
+// pairs with a live one as soon as the tables are whole again, so a round on a prefix is followed by one small pass that fixes / pair-sums the rest of eq.
 static int run_lin_sumcheck(lf_ctx *c, Transcript &tr, const u64 *mz, const u64 *eqb, u64 *msgs /* s*(d+2) ring */, Fq3 *point, u64 *u_dev = nullptr,
-                            const std::function<void(u32)> *after_round = nullptr, const Fq3 *beta = nullptr) {
+                            const std::function<void(u32)> *after_round = nullptr, const Fq3 *beta = nullptr, size_t live = 0) {
     const lf_params &P = c->P;
     u32 deg = P.d + 1;
     size_t m = c->m;
@@ -33,6 +39,8 @@ static int run_lin_sumcheck(lf_ctx *c, Transcript &tr, const u64 *mz, const u64 
     const u64 *cur = mz, *cure = eqb;
     size_t n = m;
     int flip = 0;
+    // nl: live entries of the n-entry tables at `cur`
+    size_t nl = live && live < m && c->sh_world == 1 ? live : m;
     // Sharded rounds: rank g owns the entries [g*n/G, (g+1)*n/G) of every table (high index bits: pairs stay local), fixes
     // and evaluates only those; the (deg+1)-element partial messages are all-gathered and added mod p on the device.  Below 64 pairs per
     // rank the slices are gathered and the tail rounds are replicated.
@@ -48,6 +56,7 @@ static int run_lin_sumcheck(lf_ctx *c, Transcript &tr, const u64 *mz, const u64 
     lfs::SplitCoef<GoldV> sp = lfs::split_coef(hv, fq3_one(), beta ? beta[0] : fq3_one());   // c_i, beta_i and their inverses (round 1 divides by neither)
     if (split) RET(build_eq_dev(c, beta + 1, P.s - 1, fe[0]));   // E_1 = eq((beta_2..beta_s), .), m / 2 entries
     c->lin_split_rounds = 0;
+    c->lin_live_rounds = 0;
     for (u32 round = 1; round <= P.s; round++) {
         if (split && round >= 2) {
             // stay in the split form?  Not into the persistent tail, not below the size where it pays, not when c_i or beta_i cannot be divided by
@@ -63,8 +72,14 @@ static int run_lin_sumcheck(lf_ctx *c, Transcript &tr, const u64 *mz, const u64 
                 split = false;
             } else sp = sp_next;
         }
+        const bool tail_now = !wide && !sharded && !c->tn.no_tail && round >= 2 && n <= c->tn.tail_n && n >= 4 && P.s - round + 1 <= TAIL_MAX_ROUNDS;
+        if (round >= 2 && nl < n && !(lflive::halves(n, nl) && !tail_now && !sharded && (split || (Gw == 1 && n >= 8)))) {
+            // the live prefix ends here (see above): the rest of the tables of round - 1 is zero from now on and every later pass is a whole one
+            HIPCHK(hipMemset2DAsync((u64 *)cur + nl, n * 8, 0, (n - nl) * 8, (size_t)P.t * 24, c->stream()));
+            nl = n;
+        }
         // persistent tail (k_lin_tail): all remaining rounds in one launch once the tables are small, as in the folding sumcheck
-        if (!wide && !sharded && !c->tn.no_tail && round >= 2 && n <= c->tn.tail_n && n >= 4 && P.s - round + 1 <= TAIL_MAX_ROUNDS) {
+        if (tail_now) {
             int trc = lin_tail_rounds(c, tr, cur, cure, n, fx[flip], partial, round, point, msgs, deg, after_round);
             if (trc == LF_OK) { cur = fx[flip]; n = 2; break; }
             if (trc != LF_ERR_UNSUPPORTED) return trc;
@@ -87,6 +102,7 @@ static int run_lin_sumcheck(lf_ctx *c, Transcript &tr, const u64 *mz, const u64 
             cur = fx[flip]; cure = split ? fe[(round - 1) & 1] : fe[flip];   // (split: E_round, one entry per pair of the new tables)
             flip ^= 1;
             n /= 2;
+            nl /= 2;
             if (sharded && !shard_keep(c, 0, n)) {   // hand-over to the replicated rounds: the Mz tables and eq in one exchange
                 const size_t lcl = n / Gw;
                 const GatherPart gp[2] = {{cur + gr * lcl, n, (u64 *)cur, (size_t)P.t * 24}, {cure + gr * lcl, n, (u64 *)cure, 3}};
@@ -95,6 +111,7 @@ static int run_lin_sumcheck(lf_ctx *c, Transcript &tr, const u64 *mz, const u64 
             }
         }
         u64 *ev = msgs + (size_t)(round - 1) * (deg + 1) * 24;
+        if (nl < n) c->lin_live_rounds++;
         if (sharded) {
             const size_t p0 = gr * (n / 2 / Gw), pcnt = n / 2 / Gw;
             launch_lin_round(c->dcrt, c->desc, cur + 2 * p0, n, cure + 2 * p0, n, 2 * pcnt, deg, partial, od_dev, c->stream(), c->lin_blocks);
@@ -103,13 +120,16 @@ static int run_lin_sumcheck(lf_ctx *c, Transcript &tr, const u64 *mz, const u64 
         } else if (split) {
             // the points the kernel evaluates: all of 0..dT in round 1 (no previous message to take T(1) from), 0 and 2..dT afterwards
             const u32 xmask = round == 1 ? (1u << (dT + 1)) - 1 : (((1u << (dT + 1)) - 1) & ~2u);
-            if (round == 1) launch_lin_round(c->dcrt, c->desc, cur, n, fe[0], n / 2, n, deg, partial, od, c->stream(), c->lin_blocks, xmask);
-            else launch_lin_round_fused(c->dcrt, c->desc, prev, prevn, preve, prevn / 2, f3c(point[round - 2]), (u64 *)cur, n, (u64 *)cure, n / 2, n, deg, partial, od, c->stream(),
+            if (round == 1) launch_lin_round(c->dcrt, c->desc, cur, n, fe[0], n / 2, nl, deg, partial, od, c->stream(), c->lin_blocks, xmask);
+            else launch_lin_round_fused(c->dcrt, c->desc, prev, prevn, preve, prevn / 2, f3c(point[round - 2]), (u64 *)cur, n, (u64 *)cure, n / 2, nl, deg, partial, od, c->stream(),
                                         c->lin_blocks, xmask);
             if (round == 1) cure = fe[0];
-        } else if (fused_now)
-            launch_lin_round_fused(c->dcrt, c->desc, prev, prevn, preve, prevn, f3c(point[round - 2]), (u64 *)cur, n, (u64 *)cure, n, n, deg, partial, od, c->stream(), c->lin_blocks);
-        else launch_lin_round(c->dcrt, c->desc, cur, n, cure, n, n, deg, partial, od, c->stream(), c->lin_blocks);
+            else if (nl < n) launch_eq_pairsum(preve + nl, prevn / 2, (n - nl) / 2, (u64 *)cure + nl / 2, n / 2, c->stream());   // the rest of E_round
+        } else if (fused_now) {
+            launch_lin_round_fused(c->dcrt, c->desc, prev, prevn, preve, prevn, f3c(point[round - 2]), (u64 *)cur, n, (u64 *)cure, n, nl, deg, partial, od, c->stream(), c->lin_blocks);
+            if (nl < n) launch_fix_many(c->dcrt, preve + 2 * nl, prevn, (u64 *)cure + nl, n, prevn - 2 * nl, 1, f3c(point[round - 2]), c->stream());   // the rest of eq
+        }
+        else launch_lin_round(c->dcrt, c->desc, cur, n, cure, n, nl, deg, partial, od, c->stream(), c->lin_blocks);   // (nl < n in round 1 only)
         RET(c->lane_sync());                                  // the message is in mapped host memory
         if (split) {
             // od[X][slot] = T(X) = sum_p E[p] h(X, p) at the evaluated X: complete the message g(X) = c_i eq(beta_i, X) T(X), X = 0..deg
@@ -199,12 +219,14 @@ static int linearize_impl(lf_ctx *c, Transcript &tr, const u64 *cccs, const lf_w
         for (u32 i = 0; i < P.s; i++) beta[i] = tr.get_challenge();
     }
     RET(build_eq_dev(c, beta.data(), P.s, eqb));
+    const size_t live = c->tn.lin_u_eval ? m : c->live_plan().pad;   // (LF_LIN_U_EVAL evaluates the whole M z tables afterwards)
     {
         // a sharded rank evaluates and fixes the entries [rank m/G, (rank+1) m/G) of the Mz tables until the fixed slices are gathered (run_lin_sumcheck):
         // it computes only those rows (z itself stays whole: a row refers to arbitrary columns)
         const size_t Gw = (size_t)c->sh_world;
         const bool rows_sliced = shard_keep(c, 0, m) && !c->tn.lin_u_eval;
-        const size_t r0 = rows_sliced ? (size_t)c->sh_rank * (m / Gw) : 0, rcnt = rows_sliced ? m / Gw : m;
+        // unsharded: only the padded live prefix of the tables is written (rows live_rows .. live - 1 are empty: zeros); run_lin_sumcheck takes the rest as zero
+        const size_t r0 = rows_sliced ? (size_t)c->sh_rank * (m / Gw) : 0, rcnt = rows_sliced ? m / Gw : live;
         if (c->ccs_general) {      // general matrices: whole-element gathers from one element-major copy of z
             u64 *zaos;
             RET(c->tbuf("spmv_zaos", (size_t)P.t * n * 24, &zaos));
@@ -265,7 +287,7 @@ static int linearize_impl(lf_ctx *c, Transcript &tr, const u64 *cccs, const lf_w
         vsp.launched = ok;
         vsp.failed = !ok;
     };
-    RET(run_lin_sumcheck(c, tr, mz, eqb, proof, pt.data(), u_eval ? nullptr : od + 72, vsp.armed ? &vs_hook : nullptr, beta.data()));
+    RET(run_lin_sumcheck(c, tr, mz, eqb, proof, pt.data(), u_eval ? nullptr : od + 72, vsp.armed ? &vs_hook : nullptr, beta.data(), live));
     if (vsp.failed) { (void)hipStreamSynchronize(c->st_aux); return LF_ERR_HIP; }
     if (!vsp.launched) RET(build_eq_dev(c, pt.data(), P.s, eqr));
     u64 *v = proof + (size_t)P.s * (P.d + 2) * 24, *u = v + 3 * 24;   // contiguous: v[3 ring] u[t ring]

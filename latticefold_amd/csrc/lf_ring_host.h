@@ -547,6 +547,7 @@ struct ring_ops<Ring<C>> {
             for (u32 jj = 0; jj < P->t; jj++)
                 if ((size_t)rowptr[jj][m] * 2 > rows_used * 3) c->ccs_general = true;
             c->shc_r0 = (size_t)-1;
+            c->live_rows = lflive::live_rows(P->t, m, rowptr);   // the trailing empty rows are skipped by M z, the linearization rounds and G (lf_live_rows.h)
         }
         c->have_ccs = true;
         return LF_OK;
