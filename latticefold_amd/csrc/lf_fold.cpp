@@ -678,8 +678,14 @@ int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out,
     RET(f.finish(lcccs_out, w_out, [&](const std::vector<int8_t> &rho8, int8_t *d_rho, int32_t *npl) -> int {
         HIPCHK(hipMemcpyAsync(d_rho, rho8.data(), rho8.size(), hipMemcpyHostToDevice, c->stream()));
         LF_TRACE(c, "theta/eta");
-        launch_fold_witness(S[0].planes, S[1].planes, f.N, f.K, d_rho, npl, c->stream());
-        return LF_OK;
+        int rc = 1;
+        if (!c->tn.fold_witness_valu) {
+            int rho_max = 0;
+            for (int8_t r : rho8) rho_max = std::max(rho_max, std::abs((int)r));
+            rc = launch_fold_witness_i8(S[0].planes, S[1].planes, f.N, f.K, d_rho, rho_max, npl, c->stream());
+        }
+        if (rc > 0) launch_fold_witness(S[0].planes, S[1].planes, f.N, f.K, d_rho, npl, c->stream());   // (the shapes the int8 form declines, or the switch)
+        return rc < 0 ? LF_ERR_HIP : LF_OK;
     }));
     c->ev_end(ph);
     return LF_OK;

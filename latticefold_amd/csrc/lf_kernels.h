@@ -279,5 +279,9 @@ u32 launch_fold_tail(const DevCrt &t, const FoldTailArgs &A, int num_cus, hipStr
 // out[c][j] = sum_{i<2K} (rho_i * bitplane_i)(c)  with rho_i small-coefficient polynomials (i8 [2K][24])
 void launch_fold_witness(const int32_t *planesL, const int32_t *planesR, size_t n, u32 K, const int8_t *rho_dev, int32_t *out,
                          hipStream_t s);
+// the same on the int8 matrix cores (lf_fold_i8.hip): K <= 16, n a multiple of 4, 16-byte aligned tables, rho_max = max |rho coefficient| <= 63 (the wrap
+// X^24 = X^12 - 1 is inside the int8 matrix).  Returns 0, 1 if the shape is not handled (nothing launched), -1 if the launch failed.
+int launch_fold_witness_i8(const int32_t *planesL, const int32_t *planesR, size_t n, u32 K, const int8_t *rho_dev, int rho_max, int32_t *out,
+                           hipStream_t s);
 
 }  // namespace lf
