@@ -27,6 +27,7 @@ static int install_tables(lf_ctx *c, u64 nonres, const u64 *y) {
     if (build_crt_tables(nonres, y, T) != 0) return LF_ERR_BAD_TABLES;
     c->ring.T = T;
     c->dcrt = make_dev_crt(T);
+    c->zk_i8.state = 0;   // (the int8 matrix of the z_k build belongs to the tables: built again at its next use)
     return ring_ops<GoldRing>::install_icrt(c, &T.icrt[0][0]);
 }
 
@@ -82,6 +83,7 @@ void lf_ctx_destroy(lf_ctx *c) {
     if (c->tail_mail) (void)hipHostFree(c->tail_mail);
     if (c->tail_counters) (void)hipFree(c->tail_counters);
     if (c->d_poseidon) (void)hipFree(c->d_poseidon);
+    if (c->zk_i8.dev) (void)hipFree(c->zk_i8.dev);
     if (c->ev_theta) (void)hipEventDestroy(c->ev_theta);
     if (c->ev_aux) (void)hipEventDestroy(c->ev_aux);
     if (c->st_aux) (void)hipStreamDestroy(c->st_aux);

@@ -111,6 +111,7 @@ struct Tunables {
     size_t dot_min = 4096;           // LF_DOT_MIN: columns from which the int8 form of the inner products is used
     bool dot_valu = false;           // LF_DOT_VALU: u_s / eta inner products on the 64-bit VALU kernel (k_dot_batch) instead of the int8 matrix cores
     bool fold_witness_valu = false;  // LF_FOLD_WITNESS_VALU: compute_f_0 on the nibble-table kernel (k_fold_witness) instead of the int8 matrix cores (lf_fold_i8.hip)
+    bool zk_valu = false;            // LF_ZK_VALU: the z_k build on the butterfly kernel (k_recompose_crt_b4) instead of the int8 matrix cores (lf_zk_i8.hip)
     bool fold_no_sv = false;         // LF_FOLD_NO_SV: rounds 1-3 of the folding sumcheck on the VALU kernels instead of the int8 matrix-core GEMMs (lf_sv_rounds.hip)
     size_t sv_min = 65536;           // LF_FOLD_SV_MIN: pairs of a round from which the GEMM form is used
     int sv_rounds = 3;               // LF_FOLD_SV_ROUNDS: last round in GEMM form (1..3)
@@ -140,6 +141,7 @@ struct Tunables {
         t.fold_no_sv = getenv("LF_FOLD_NO_SV") != nullptr;
         t.dot_valu = getenv("LF_DOT_VALU") != nullptr;
         t.fold_witness_valu = getenv("LF_FOLD_WITNESS_VALU") != nullptr;
+        t.zk_valu = getenv("LF_ZK_VALU") != nullptr;
         if ((e = getenv("LF_DOT_MIN"))) t.dot_min = (size_t)atoll(e);
         t.lin_no_small = getenv("LF_LIN_NO_SMALL") != nullptr;
         t.lin_no_r1cs = getenv("LF_LIN_NO_R1CS") != nullptr;

@@ -158,6 +158,17 @@ struct lf_ctx : CtxCore<u64> {
     size_t N_any() { return core_any().N; }
     HostRing ring;
     DevCrt dcrt;
+    // the z_k build's int8 matrix (lf_zk_i8.hip) of dcrt for the base of the loaded parameters: built at the first z_k build that can use it, on the calling
+    // lane's stream (set-up: one synchronisation), and again after install_tables or a change of B
+    ZkI8 zk_i8;
+    std::mutex zk_mu;    // (either lane may be the first to ask)
+    int zk_i8_get(u64 B, const ZkI8 **out) {
+        std::lock_guard<std::mutex> g(zk_mu);
+        if (zk_i8.state == 0 || zk_i8.B != B)
+            if (zk_i8_prepare(dcrt, B, &zk_i8, stream()) != 0) return LF_ERR_HIP;
+        *out = zk_i8.state == 1 ? &zk_i8 : nullptr;
+        return LF_OK;
+    }
     LaneWorker lane1;
     int agreed_two_lanes = -1;       // lf_dist_init's handshake: the schedule ALL ranks agreed on (1 threaded / 0 one thread); -1 = no handshake ran (host transports, model)
     bool two_lanes_ok = false;       // the transport's two channels have been seen working concurrently (lf_dist_init's handshake; two host callbacks): a sharded

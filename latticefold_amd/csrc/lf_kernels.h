@@ -73,8 +73,21 @@ void launch_i32_to_coef(const int32_t *planes, u64 *coef, size_t n, hipStream_t 
 // NTT of bit-plane k (k0 <= k < k1) of every element: out[(k-k0)][24][n]
 // z-vector tails: out_k[off + i] = CRT( sum_l B^l * digit_k(planes[i*L + l]) ) for k < K (mode_bits = 1), or the
 // full value (mode_bits = 0, K = 1).  out_k = out + k*24*ldz.
+// zk (optional): the int8 matrix of these tables for this base (below); the bit-plane launches with L = 4 then run on the matrix cores
+struct ZkI8;
 void launch_recompose_crt(const DevCrt &t, const int32_t *planes, size_t n_planes, u32 wit_len, u32 L, u64 B, u32 K,
-                          int mode_bits, u64 *out, size_t ldz, size_t off, hipStream_t s);
+                          int mode_bits, u64 *out, size_t ldz, size_t off, hipStream_t s, const ZkI8 *zk = nullptr);
+// the same tails as an exact int8 GEMM (lf_zk_i8.hip): mode_bits, L = 4, B < 2^20, K <= 32, n_planes a multiple of 4, 16-byte aligned planes.  The matrix
+// (CRT coefficients of the installed tables times B^l, cut into balanced bytes, in operand order) is set-up: zk_i8_prepare derives it from the generic
+// kernel's answers to the 96 unit inputs and synchronises s; state 1 = ready, -1 = tables the kernel does not handle.  It is rebuilt when the tables or B change.
+struct ZkI8 {
+    u64 B = 0;
+    int state = 0;
+    int *dev = nullptr;   // A operands [3 classes][2 tiles][64 lanes] x 16 bytes, then the output planes [3][8]
+};
+int zk_i8_prepare(const DevCrt &t, u64 B, ZkI8 *zk, hipStream_t s);   // 0, or -1 for a HIP error
+// 0: launched; 1: shape not handled (the caller launches k_recompose_crt_b4); -1: the launch failed
+int launch_recompose_crt_i8(const ZkI8 &zk, const int32_t *planes, size_t n_planes, u32 wit_len, u32 K, u64 *out, size_t ldz, size_t off, hipStream_t s);
 // l-infinity norm (a15): max |centred coefficient| of canonical coefficient table -> *out_max (u64)
 void launch_linf(const u64 *coef, size_t n, u64 *out_max, hipStream_t s);
 

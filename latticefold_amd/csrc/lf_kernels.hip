@@ -232,8 +232,10 @@ __global__ void __launch_bounds__(256) k_recompose_crt_b4(DevCrt t, const int32_
     }
 }
 void launch_recompose_crt(const DevCrt &t, const int32_t *planes, size_t n_planes, u32 wit_len, u32 L, u64 B, u32 K, int mode_bits,
-                          u64 *out, size_t ldz, size_t off, hipStream_t s) {
+                          u64 *out, size_t ldz, size_t off, hipStream_t s, const ZkI8 *zk) {
     if (mode_bits && L == 4 && B < ((u64)1 << 20) && (n_planes & 3) == 0 && ((uintptr_t)planes & 15) == 0) {
+        // on the int8 matrix cores where the context holds the matrix of these tables for this base (a failed launch shows again at the next one)
+        if (zk && zk->state == 1 && zk->B == B && launch_recompose_crt_i8(*zk, planes, n_planes, wit_len, K, out, ldz, off, s) != 1) return;
         BInt4 bi;
         bi.v[0] = 1;
         for (int l = 1; l < 4; l++) bi.v[l] = bi.v[l - 1] * (long long)B;

@@ -182,7 +182,11 @@ int build_z(lf_ctx *c, const int32_t *planes, u32 K, int mode_bits, const u64 *h
         if (w0 != 0 || wcnt != P.wit_len || !mode_bits) return LF_ERR_UNSUPPORTED;
         if (launch_sb_recompose_crt(c->dcrt, D, sb_ld(c->N), P.wit_len, P.L, P.B, K, z, c->n, hl, c->stream()) != 0) return LF_ERR_HIP;
     } else
-    if (wcnt) launch_recompose_crt(c->dcrt, planes + w0 * P.L, c->N, (u32)wcnt, P.L, P.B, K, mode_bits, z, c->n, hl + w0, c->stream());
+    if (wcnt) {
+        const ZkI8 *zk = nullptr;   // the K bit-plane tails on the int8 matrix cores (lf_zk_i8.hip) unless LF_ZK_VALU is set, the step is sharded or the shape is not handled there
+        if (mode_bits && !c->tn.zk_valu && c->sh_world == 1 && P.L == 4 && P.B < ((u64)1 << 20)) RET(c->zk_i8_get(P.B, &zk));
+        launch_recompose_crt(c->dcrt, planes + w0 * P.L, c->N, (u32)wcnt, P.L, P.B, K, mode_bits, z, c->n, hl + w0, c->stream(), zk);
+    }
     // heads: write plane entries 0..l of each table
     std::vector<u64> h((size_t)K * 24 * hl);
     for (u32 k = 0; k < K; k++)
