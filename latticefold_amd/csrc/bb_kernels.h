@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bb_host.h"
+#include "lf_i8_launch.h"
 
 namespace lfbb {
 
@@ -82,9 +83,9 @@ void launch_spmv_t_eq(const DevBb &t, const u32 *colptr, const u32 *rowidx, cons
                       hipStream_t s);
 size_t red_partial_words(u32 nv);
 // the same on the int8 matrix cores (bb_dot_i8.hip), na <= 16, nb <= 3; scratch: YB bbdot_i8_yb_bytes(n), part bbdot_i8_part_words(n) int32,
-// tot bbdot_i8_tot_words() int64.  Returns 0, or -1 if the shape is not handled.
+// tot bbdot_i8_tot_words() int64.  Result: lf_i8_launch.h.
 // T[k][c] = sum_i eq[i] digit_k(planes[c][i]) of the K <= 16 binary digit planes on the matrix cores (bb_dot_i8.hip); scratch: EB coef_eval_i8_eb_bytes(n) (16-byte
-// aligned), part coef_eval_i8_part_words(nwg) int32, tot coef_eval_i8_tot_words() int64.  out as launch_coef_eval (mode_bits).  0, or -1 if the shape is not handled.
+// aligned), part coef_eval_i8_part_words(nwg) int32, tot coef_eval_i8_tot_words() int64.  out as launch_coef_eval (mode_bits).  Result: lf_i8_launch.h.
 size_t coef_eval_i8_eb_bytes(size_t n);
 size_t coef_eval_i8_part_words(u32 nwg);
 size_t coef_eval_i8_tot_words();
@@ -186,8 +187,8 @@ size_t bbsv_part_words(int V, u32 K);
 size_t bbsv_tot_words(int V, u32 K);
 size_t bbsv_tp_words(u32 K);
 size_t bbsv_bits_words(size_t n, u32 K);
-void launch_bbsv_bits(const int32_t *planes, size_t ldp, size_t n, u32 K, u32 *bits, hipStream_t s);
-void launch_bb_eq_pairsum(const fe *in, size_t ldi, size_t nout, fe *out, size_t ldo, hipStream_t s);
+int launch_bbsv_bits(const int32_t *planes, size_t ldp, size_t n, u32 K, u32 *bits, hipStream_t s);
+int launch_bb_eq_pairsum(const fe *in, size_t ldi, size_t nout, fe *out, size_t ldo, hipStream_t s);
 int launch_bbsv_round(const DevBb &t, int V, const u32 *bitsL, const u32 *bitsR, size_t nplanes, const fe *E, size_t ldE, size_t npairs, u32 K, const E9C *mu_c,
                       const fe *coef, const E9C &w0, const E9C &w1, unsigned char *EB, int32_t *part, int32_t *tot, fe *tp, const u64 *gpart, u64 *out, hipStream_t s, hipEvent_t gpart_ready = nullptr);
 }  // namespace lfbb

@@ -120,7 +120,8 @@ static int coef_eval_bits_dev(BbCtxImpl *c, const int32_t *planes, size_t n, con
         RET(c->tbuf("ce_eb", coef_eval_i8_eb_bytes(n), &EB));
         RET(c->tbuf("ce_part", coef_eval_i8_part_words(nwg), &part));
         RET(c->tbuf("ce_tot", coef_eval_i8_tot_words(), &tot));
-        if (launch_coef_eval_i8(planes, n, n, eq, ldeq, K, EB, nwg, part, tot, out, c->stream()) == 0) return LF_OK;
+        const int rc = launch_coef_eval_i8(planes, n, n, eq, ldeq, K, EB, nwg, part, tot, out, c->stream());
+        if (rc != i8mma::I8_ERR_SHAPE) return rc == 0 ? LF_OK : LF_ERR_HIP;
     }
     launch_coef_eval(c->dev, planes, n, eq, ldeq, K, 1, partial, out, c->stream());
     return LF_OK;
@@ -243,11 +244,11 @@ static int dot_batch_dev(BbCtxImpl *c, const fe *X, size_t ldx, u32 na, const fe
         else RET(c->tbuf(std::string("dot_yb") + tag, bbdot_i8_yb_bytes(n + 1), &yb));
         RET(c->tbuf(std::string("dot_i8_part") + tag, bbdot_i8_part_words(n + 1), &part));
         RET(c->tbuf(std::string("dot_i8_tot") + tag, bbdot_i8_tot_words(), &tot));
-        bool ok = true;
-        for (u32 a0 = 0; a0 < na && ok; a0 += 16)
-            ok = launch_dot_batch_i8(c->dev, X + (size_t)a0 * RE * ldx, ldx, na - a0 < 16 ? na - a0 : 16, Y, ldy, nb, n, yb, part, tot, od + (size_t)a0 * nb * RE, st,
-                                     yb_pre != nullptr) == 0;
-        if (ok) return LF_OK;
+        int rc = 0;
+        for (u32 a0 = 0; a0 < na && rc == 0; a0 += 16)
+            rc = launch_dot_batch_i8(c->dev, X + (size_t)a0 * RE * ldx, ldx, na - a0 < 16 ? na - a0 : 16, Y, ldy, nb, n, yb, part, tot, od + (size_t)a0 * nb * RE, st,
+                                     yb_pre != nullptr);
+        if (rc != i8mma::I8_ERR_SHAPE) return rc == 0 ? LF_OK : LF_ERR_HIP;
     }
     launch_dot_batch(c->dev, X, ldx, na, Y, ldy, nb, n, partial, od, st);
     return LF_OK;
@@ -357,7 +358,7 @@ struct BbFold {
             const size_t ne = m >> (svE_level + 1);
             RET(c->tbuf(names[svE_level], (size_t)TAU * atl(ne), &svE[svE_level]));
             if (svE_level == 0) RET(build_eq_dev(c, beta.data() + 1, P.s - 1, svE[0]));
-            else launch_bb_eq_pairsum(svE[svE_level - 1], atl(m >> svE_level), ne, svE[svE_level], atl(ne), c->stream());
+            else if (launch_bb_eq_pairsum(svE[svE_level - 1], atl(m >> svE_level), ne, svE[svE_level], atl(ne), c->stream()) < 0) return LF_ERR_HIP;
         }
         return LF_OK;
     }
@@ -378,7 +379,7 @@ int BbFold::prepare() {
         if (c->sh_world == 1 && !c->tn.fold_no_sv && N <= m && (N & 3) == 0 && P.s >= 4 && c->tn.sv_rounds >= 1 && m / 2 >= sv_min0 && bbsv_shape_ok(1, m / 2, K))
             for (int sd = 0; sd < 2; sd++) {
                 RET(c->tbuf(sd ? "sv_bits_R" : "sv_bits_L", bbsv_bits_words(N, K), &svbits[sd]));
-                launch_bbsv_bits(S[sd].planes, N, N, K, svbits[sd], c->stream());
+                if (launch_bbsv_bits(S[sd].planes, N, N, K, svbits[sd], c->stream()) < 0) return LF_ERR_HIP;
             }
     }
     { HostTimer ht(c); lfs::draw_alpha_zeta<BbV>(tr, K2, alpha, zeta); }
@@ -553,7 +554,7 @@ int BbFold::gemm_round(u32 round) {
     if (!svbits[0])
         for (int sd = 0; sd < 2; sd++) {
             RET(c->tbuf(sd ? "sv_bits_R" : "sv_bits_L", bbsv_bits_words(N, K), &svbits[sd]));
-            launch_bbsv_bits(S[sd].planes, N, N, K, svbits[sd], c->stream());
+            if (launch_bbsv_bits(S[sd].planes, N, N, K, svbits[sd], c->stream()) < 0) return LF_ERR_HIP;
         }
     RET(svE_ensure(round));
     i64 *gpartial;
@@ -564,8 +565,10 @@ int BbFold::gemm_round(u32 round) {
     launch_fold_round_g(c->dev, a, gpartial, gtmp, sg);
     hipEvent_t g_ready = nullptr;       // the GEMM chain's last kernel waits for the G part
     if (sg != c->stream() && !(g_ready = c->join_mark(sg))) return LF_ERR_HIP;
-    if (launch_bbsv_round(c->dev, svV, svbits[0], svbits[1], N, svE[round - 1], atl(m >> round), a.pcnt, K, d_mu, d_coef, w0, w1, sveb, svpart, svtot, svtp, gtmp, od,
-                          c->stream(), g_ready) == 0) {
+    const int rc = launch_bbsv_round(c->dev, svV, svbits[0], svbits[1], N, svE[round - 1], atl(m >> round), a.pcnt, K, d_mu, d_coef, w0, w1, sveb, svpart, svtot, svtp, gtmp,
+                                     od, c->stream(), g_ready);
+    if (rc == i8mma::I8_ERR_HIP) return LF_ERR_HIP;
+    if (rc == 0) {
         sv_done = true;
         c->sv_round_mask |= 1u << (round - 1);
     }
@@ -690,7 +693,9 @@ int BbFold::evaluations() {
         unsigned char *ybq = nullptr;   // the digits of q are the same for both sides: packed once, before the streams part
         if (!c->tn.dot_valu && n >= c->tn.dot_min && P.t <= 3 && K <= 16 && ((((size_t)S[0].z) ^ ((size_t)S[1].z)) & 7) == 0) {
             RET(c->tbuf("dot_yb", bbdot_i8_yb_bytes(n + 1), &ybq));
-            if (launch_dot_pack_y(S[0].z, q, n, P.t, n, ybq, c->stream()) != 0) ybq = nullptr;
+            const int rc = launch_dot_pack_y(S[0].z, q, n, P.t, n, ybq, c->stream());
+            if (rc == i8mma::I8_ERR_HIP) return LF_ERR_HIP;
+            if (rc < 0) ybq = nullptr;
         }
         RET(c->fork(c->stream(), s1f));           // q (and its digits) are ready
         i64 *red1;

@@ -15,11 +15,12 @@
 #include "bb_field.cuh"
 #include "bb_kernels.h"
 #include "lf_sv_rounds.h"
+#include "lf_i8_mma.cuh"
 
 namespace lfbb {
-static inline size_t cdiv(size_t a, size_t b) { return (a + b - 1) / b; }
+using namespace i8mma;
 
-// EB[(4 q + u)][slot] = balanced base-256 digit u of the centred Montgomery word E[q][pair(slot)]: the bytes of (x + 0x80808080) ^ 0x80808080 (|x| < 2^30)
+// EB[(4 q + u)][slot] = balanced base-256 digit u of the centred Montgomery word E[q][pair(slot)]
 __global__ void __launch_bounds__(256) k_bbsv_pack(const fe *E, size_t ld, size_t npairs, size_t ldeb, int V, unsigned char *EB) {
     const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, groups = ldeb / 16;
     if (gid >= groups * TAU) return;
@@ -30,7 +31,7 @@ __global__ void __launch_bounds__(256) k_bbsv_pack(const fe *E, size_t ld, size_
     for (int t = 0; t < 16; t++) {
         const size_t pr = p0 + (size_t)lf::sv_slot_pair_pub(V, t >> 2, t & 3);
         const fe x = pr < npairs ? E[(size_t)q * ld + pr] : 0;
-        w[t] = ((u32)x + 0x80808080u) ^ 0x80808080u;
+        w[t] = balanced_bytes((u32)x);
     }
 #pragma unroll
     for (int u = 0; u < 4; u++) {
@@ -127,8 +128,9 @@ __global__ void __launch_bounds__(256) k_bb_eq_pairsum(const fe *in, size_t ldi,
     const int2 v = *(const int2 *)(in + q * ldi + 2 * p);
     out[q * ldo + p] = fadd(v.x, v.y);
 }
-void launch_bb_eq_pairsum(const fe *in, size_t ldi, size_t nout, fe *out, size_t ldo, hipStream_t s) {
+int launch_bb_eq_pairsum(const fe *in, size_t ldi, size_t nout, fe *out, size_t ldo, hipStream_t s) {
     hipLaunchKernelGGL(k_bb_eq_pairsum, dim3((unsigned)cdiv(nout * TAU, 256)), dim3(256), 0, s, in, ldi, nout, out, ldo);
+    return i8_launched();
 }
 
 bool bbsv_shape_ok(int V, size_t npairs, u32 K) { return lf::sv_shape_ok(V, npairs, K); }
@@ -137,23 +139,23 @@ size_t bbsv_part_words(int V, u32 K) { return lf::sv_part_words_rd(RE, V, K); }
 size_t bbsv_tot_words(int V, u32 K) { return lf::sv_tot_words_rd(RE, V, K); }
 size_t bbsv_tp_words(u32 K) { return (size_t)2 * K * RE * 5 * TAU; }
 size_t bbsv_bits_words(size_t n, u32 K) { return lf::sv_bits_words(n, K, RE); }
-void launch_bbsv_bits(const int32_t *planes, size_t ldp, size_t n, u32 K, u32 *bits, hipStream_t s) { lf::launch_sv_bits(planes, ldp, n, K, bits, s, RE); }
+int launch_bbsv_bits(const int32_t *planes, size_t ldp, size_t n, u32 K, u32 *bits, hipStream_t s) { return lf::launch_sv_bits(planes, ldp, n, K, bits, s, RE); }
 
 // norm part of round log2(V) + 1 in the split eq form, added to the G part `gpart` (5 x 72 canonical words, device) -> out (5 x 72 canonical words).
 // E: E_i[9][ldE] (one value per pair), npairs pairs; coef: [sv_num_pairs(V)][4][9] Montgomery words (device); mu_c: [2K][9] constants mu_k^(d+1);
-// w0 / w1 = c_i eq(beta_i, 0 / 1).  Returns 0, or -1 when the shape is not handled (the caller keeps its VALU kernels).
+// w0 / w1 = c_i eq(beta_i, 0 / 1).  Result: lf_i8_launch.h (shape not handled: the caller keeps its VALU kernels).
 int launch_bbsv_round(const DevBb &t, int V, const u32 *bitsL, const u32 *bitsR, size_t nplanes, const fe *E, size_t ldE, size_t npairs, u32 K, const E9C *mu_c,
                       const fe *coef, const E9C &w0, const E9C &w1, unsigned char *EB, int32_t *part, int32_t *tot, fe *tp, const u64 *gpart, u64 *out, hipStream_t s, hipEvent_t gpart_ready) {
-    if (!bbsv_shape_ok(V, npairs, K)) return -1;
+    if (!bbsv_shape_ok(V, npairs, K)) return I8_ERR_SHAPE;
     const size_t ldeb = lf::sv_ldeb_pub(npairs);
-    (void)hipMemsetAsync(EB + 36 * ldeb, 0, 12 * ldeb, s);     // digit columns 36..47: none
+    I8_HIPCHK(hipMemsetAsync(EB + 36 * ldeb, 0, 12 * ldeb, s));     // digit columns 36..47: none
     hipLaunchKernelGGL(k_bbsv_pack, dim3((unsigned)cdiv(ldeb / 16 * TAU, 256)), dim3(256), 0, s, E, ldE, npairs, ldeb, V, EB);
-    if (lf::launch_sv_gemm_tiles(RE, V, bitsL, bitsR, nplanes, EB, ldeb, npairs, K, part, tot, s) != 0) return -1;
+    if (const int rc = lf::launch_sv_gemm_tiles(RE, V, bitsL, bitsR, nplanes, EB, ldeb, npairs, K, part, tot, s)) return rc;
     const u32 npr = (u32)lf::sv_num_pairs(V), ktiles = (K + 15) / 16;
     if (t.nu == BB_TWO) hipLaunchKernelGGL((k_bbsv_finish1<true>), dim3(2 * K * RE), dim3(128), 0, s, t.nu, tot, npr, K, ktiles, coef, mu_c, tp, w0, w1);
     else hipLaunchKernelGGL((k_bbsv_finish1<false>), dim3(2 * K * RE), dim3(128), 0, s, t.nu, tot, npr, K, ktiles, coef, mu_c, tp, w0, w1);
-    if (gpart_ready) (void)hipStreamWaitEvent(s, gpart_ready, 0);   // the G part was computed on another stream
+    if (gpart_ready) I8_HIPCHK(hipStreamWaitEvent(s, gpart_ready, 0));   // the G part was computed on another stream
     hipLaunchKernelGGL(k_bbsv_finish2, dim3(8 * TAU), dim3(320), 0, s, tp, K, gpart, out);
-    return 0;
+    return i8_launched();
 }
 }  // namespace lfbb

@@ -19,15 +19,14 @@
 //     L[d] = f[d] - f[d + 24] - f[d + 36]   (outputs c_out <  12)        (terms outside 0..23 dropped)
 // are built with SWAR byte arithmetic, and the B operand of a lane is the two adjacent entries d = c_out - c_in, c_out - c_in - 1.
 #include <hip/hip_runtime.h>
-#include <cstdlib>
 #include <type_traits>
 #include "lf_field.cuh"
 #include "lf_kernels.h"
 #include "lf_ajtai_i8.h"
+#include "lf_i8_mma.cuh"
 
 namespace lf {
-static inline size_t cdiv(size_t a, size_t b) { return (a + b - 1) / b; }
-typedef int v4i __attribute__((ext_vector_type(4)));
+using namespace i8mma;
 typedef unsigned long long ull;
 
 constexpr int I8_WAVES = 8;          // 2 row groups x 4 column groups
@@ -74,10 +73,11 @@ __global__ void __launch_bounds__(256) k_ajtai_pack_i8(const u64 *coef, size_t c
     w.w = b[12] | (b[13] << 8) | (b[14] << 16) | ((u32)b[15] << 24);
     *(uint4 *)(Ab + ((T * KS + s) * MT + mt) * 1024 + lane * 16) = w;
 }
-void launch_ajtai_pack_i8(const u64 *coef, size_t cs, size_t js, size_t n, u32 i, u32 MT, u32 RD, u32 NL, unsigned char *Ab, hipStream_t s) {
+int launch_ajtai_pack_i8(const u64 *coef, size_t cs, size_t js, size_t n, u32 i, u32 MT, u32 RD, u32 NL, unsigned char *Ab, hipStream_t s) {
     size_t ntiles = (n + 7) / 8;
     const u32 KS = RD / 8;
     hipLaunchKernelGGL(k_ajtai_pack_i8, dim3((unsigned)cdiv(ntiles * KS * 4 * NL, 256)), dim3(256), 0, s, coef, cs, js, n, i, MT, KS, NL, ntiles, Ab);
+    return i8_launched();
 }
 
 // The Goldilocks set-up in one pass over a row: NTT form [24][n] -> coefficients (dense 24 x 24 inverse map, as k_icrt_dense) -> operand
@@ -115,9 +115,10 @@ __global__ void __launch_bounds__(256) k_ajtai_icrt_pack_i8(const u64 *mat, cons
         *(uint4 *)(Ab + ((T * KS + s) * MT + mt) * 1024 + lane * 16) = make_uint4(o[0], o[1], o[2], o[3]);
     }
 }
-void launch_ajtai_icrt_pack_i8(const u64 *icrt_mat, const u64 *ntt, size_t n, u32 i, u32 MT, unsigned char *Ab, hipStream_t s) {
+int launch_ajtai_icrt_pack_i8(const u64 *icrt_mat, const u64 *ntt, size_t n, u32 i, u32 MT, unsigned char *Ab, hipStream_t s) {
     const size_t ntiles = (n + 7) / 8;
     hipLaunchKernelGGL(k_ajtai_icrt_pack_i8, dim3((unsigned)cdiv(ntiles, 4)), dim3(256), 0, s, icrt_mat, ntt, n, i, MT, ntiles, Ab);
+    return i8_launched();
 }
 struct AjtaiI8Args {
     const unsigned char *Ab;
@@ -1259,8 +1260,10 @@ u32 ajtai_i8_max_rows(const AjtaiI8Ring &R) { return R.RD == 24 ? 26 : 16; }    
 size_t ajtai_i8_part_words(u32 nwg, u32 MT, u32 NT) { return (size_t)nwg * MT * NT * 256; }
 size_t ajtai_i8_sum_words(const AjtaiI8Ring &R, u32 MT, u32 NT, u32 NP) { return 2 * ((size_t)MT * NT * 256 + (size_t)NP * R.RD); }   // (two sides)
 
+// couple_w: window of the pair coupling in tiles (0 switches the coupling off); prof: the profiled instantiations (Tunables::i8_couple_w / i8_prof)
 int launch_ajtai_i8(const AjtaiI8Ring &R, const unsigned char *Ab, u32 MT, const int32_t *planes, size_t ld, size_t n, u32 kappa, u32 row0, u32 kappa_total,
-                    u32 k0, u32 NP, u32 nwg, int32_t *part, int32_t *dsum, long long *sum, u64 *coef_out, hipStream_t s, const u32 *bits, size_t bits_nw, u32 bits_rows) {
+                    u32 k0, u32 NP, u32 nwg, int32_t *part, int32_t *dsum, long long *sum, u64 *coef_out, hipStream_t s, int couple_w, bool prof, const u32 *bits, size_t bits_nw,
+                    u32 bits_rows) {
     AjtaiI8Args a;
     a.bits = nullptr; a.bits_nw = 0; a.bits_rows = 0;
     a.Ab = Ab; a.planes = planes; a.ld = ld; a.n = n;
@@ -1268,10 +1271,9 @@ int launch_ajtai_i8(const AjtaiI8Ring &R, const unsigned char *Ab, u32 MT, const
     a.ntiles = (u32)((n + 7) / 8);
     a.part = part; a.dsum = dsum; a.sync = nullptr; a.couple_w = 0; a.couple_e = 1;
     a.sides = 1;
-    if ((size_t)R.RD * ld * 4 >= ((size_t)1 << 32)) return -1;   // 32-bit plane offsets in the kernel
-    if ((R.RD != 24 && R.RD != 72) || kappa > ajtai_i8_max_rows(R) || R.NL * kappa > 16 * MT || MT > 13 || NP > ajtai_i8_max_planes_mt(R, MT) || NP == 0 || nwg == 0) return -1;
-    static const bool prof = getenv("LF_I8_PROF") != nullptr;
-    static const int cw = getenv("LF_I8_COUPLE_W") ? atoi(getenv("LF_I8_COUPLE_W")) : 4;      // window of the pair coupling in tiles (0 switches the coupling off)
+    if ((size_t)R.RD * ld * 4 >= ((size_t)1 << 32)) return I8_ERR_SHAPE;   // 32-bit plane offsets in the kernel
+    if ((R.RD != 24 && R.RD != 72) || kappa > ajtai_i8_max_rows(R) || R.NL * kappa > 16 * MT || MT > 13 || NP > ajtai_i8_max_planes_mt(R, MT) || NP == 0 || nwg == 0)
+        return I8_ERR_SHAPE;
     const u32 ce = 4;      // the handshake runs every 4 tiles (measured: every tile costs 0.1 ms per launch, every 8 lets the pair drift out of the L2)
     // The specialised-wave kernels: the 13-row-tile shape of the 24-ring (k_ajtai_i8s) and the 4-row-tile shape of the 72-ring (k_ajtai_i8x).  Plane groups of 8;
     // two groups = paired workgroups on one XCD, coupled through an L2 counter (i8s_build).  Every workgroup of the grid must be resident for the coupling to make
@@ -1291,61 +1293,48 @@ int launch_ajtai_i8(const AjtaiI8Ring &R, const unsigned char *Ab, u32 MT, const
             u32 nch = (a.ntiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
             if (groups == 2) nch = (nch + 7) & ~7u;
             a.sides = groups; a.nchunks = nch; a.NT = NTg;
-            static bool attr_set = false;
-            if (!attr_set) {
-                (void)hipFuncSetAttribute((const void *)k_ajtai_i8x<72, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                (void)hipFuncSetAttribute((const void *)k_ajtai_i8x<72, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                (void)hipFuncSetAttribute((const void *)k_ajtai_i8s<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                (void)hipFuncSetAttribute((const void *)k_ajtai_i8s<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                (void)hipFuncSetAttribute((const void *)k_ajtai_i8s<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                (void)hipFuncSetAttribute((const void *)k_ajtai_i8s<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr_set = true;
-            }
             const dim3 g(groups * nch), b(512);
             // the coupling counters live behind the digit sums this path uses (ndi words per workgroup; the caller sizes dsum for the largest plane count)
-            if (groups == 2 && cw > 0 && g.x <= nwg && (size_t)nwg * ndi + g.x <= (size_t)nwg * ajtai_i8_max_planes_mt(R, MT) * R.RD && g.x <= 256) {
+            if (groups == 2 && couple_w > 0 && g.x <= nwg && (size_t)nwg * ndi + g.x <= (size_t)nwg * ajtai_i8_max_planes_mt(R, MT) * R.RD && g.x <= 256) {
                 a.sync = (u32 *)(dsum + (size_t)nwg * ndi);
-                a.couple_w = (u32)cw;
+                a.couple_w = (u32)couple_w;
                 a.couple_e = ce;
-                (void)hipMemsetAsync(a.sync, 0, (size_t)nch * 4, s);      // one signed counter per column chunk (pair of workgroups)
+                I8_HIPCHK(hipMemsetAsync(a.sync, 0, (size_t)nch * 4, s));      // one signed counter per column chunk (pair of workgroups)
             }
             if (prof) {
                 static const unsigned long long zeros[64] = {0};
-                (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_i8_prof), zeros, sizeof(zeros), 0, hipMemcpyHostToDevice, s);
+                I8_HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_i8_prof), zeros, sizeof(zeros), 0, hipMemcpyHostToDevice, s));
             }
+            int rc;
             if (spec_x) {
-                if (prof) hipLaunchKernelGGL((k_ajtai_i8x<72, 4, true>), g, b, G::lds_bytes(), s, a);
-                else hipLaunchKernelGGL((k_ajtai_i8x<72, 4, false>), g, b, G::lds_bytes(), s, a);
+                rc = prof ? i8_launch_lds<k_ajtai_i8x<72, 4, true>>(g, b, G::lds_bytes(), s, a) : i8_launch_lds<k_ajtai_i8x<72, 4, false>>(g, b, G::lds_bytes(), s, a);
             } else {
                 // digits from the bit-plane form when the caller has it and digit plane k0 + NP - 1 is one of its magnitude rows
                 a.bits = bits; a.bits_nw = bits_nw; a.bits_rows = bits_rows;
                 const bool ub = bits != nullptr && k0 + NP <= bits_rows - 1;
                 const size_t lds_s = ajtai_i8s_lds_bytes();
-                if (prof && ub) hipLaunchKernelGGL((k_ajtai_i8s<true, true>), g, b, lds_s, s, a);
-                else if (prof) hipLaunchKernelGGL((k_ajtai_i8s<true, false>), g, b, lds_s, s, a);
-                else if (ub) hipLaunchKernelGGL((k_ajtai_i8s<false, true>), g, b, lds_s, s, a);
-                else hipLaunchKernelGGL((k_ajtai_i8s<false, false>), g, b, lds_s, s, a);
+                if (prof && ub) rc = i8_launch_lds<k_ajtai_i8s<true, true>>(g, b, lds_s, s, a);
+                else if (prof) rc = i8_launch_lds<k_ajtai_i8s<true, false>>(g, b, lds_s, s, a);
+                else if (ub) rc = i8_launch_lds<k_ajtai_i8s<false, true>>(g, b, lds_s, s, a);
+                else rc = i8_launch_lds<k_ajtai_i8s<false, false>>(g, b, lds_s, s, a);
             }
+            if (rc < 0) return rc;
             const size_t per_wg = (size_t)MT * NTg * 256;
             hipLaunchKernelGGL(k_ajtai_i8_sum, dim3((unsigned)cdiv(per_wg + ndi, 256), groups), dim3(256), 0, s, part, per_wg, dsum, ndi, nch, sum);
             hipLaunchKernelGGL(k_ajtai_i8_finish, dim3((unsigned)cdiv((size_t)NPG * kappa * R.RD, 256), groups), dim3(256), 0, s, sum, per_wg, MT, NTg, NPG, kappa, row0,
                                kappa_total, R.RD, R.NL, R.p_small, R.soa_out, coef_out, NP, NPG);
-            return (int)(groups * nch);
+            return i8_launched() < 0 ? I8_ERR_HIP : (int)(groups * nch);
         }
     }
     // every other shape: the generic kernel (all eight waves build and multiply), guarded instantiations by row-tile count
-    if (NP > ajtai_i8_max_planes(R)) return -1;
+    if (NP > ajtai_i8_max_planes(R)) return I8_ERR_SHAPE;
     a.tiles_per_wg = (a.ntiles + nwg - 1) / nwg;
     const u32 nchunks = (a.ntiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
     a.nchunks = nchunks;
     const u32 grid = nchunks;
     const size_t lds = ajtai_i8_lds_bytes(R, MT, NP);
-#define LF_I8_LAUNCH(RD, RG, MTWA, MTWB, NTW, ACH)                                                                                  \
-    do {                                                                                                                           \
-        static bool attr_set = false;                                                                                              \
-        if (!attr_set) { (void)hipFuncSetAttribute((const void *)k_ajtai_i8<RD, RG, MTWA, MTWB, NTW, ACH, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; } \
-        hipLaunchKernelGGL((k_ajtai_i8<RD, RG, MTWA, MTWB, NTW, ACH, false>), dim3(grid), dim3(64 * I8_WAVES), lds, s, a);         \
-    } while (0)
+    int rc;
+#define LF_I8_LAUNCH(RD, RG, MTWA, MTWB, NTW, ACH) rc = i8_launch_lds<k_ajtai_i8<RD, RG, MTWA, MTWB, NTW, ACH, false>>(dim3(grid), dim3(64 * I8_WAVES), lds, s, a)
     if (R.RD == 24) {   // 2 row groups x 4 column groups of 6 tiles (24 x 16 planes = 24 tiles)
         const u32 mh = (MT + 1) / 2;
         if (mh <= 2) LF_I8_LAUNCH(24, 2, 2, 2, 6, 2);
@@ -1355,14 +1344,15 @@ int launch_ajtai_i8(const AjtaiI8Ring &R, const unsigned char *Ab, u32 MT, const
         if (MT <= 1) LF_I8_LAUNCH(72, 1, 1, 1, 5, 2);
         else if (MT <= 2) LF_I8_LAUNCH(72, 1, 2, 2, 5, 3);
         else if (MT <= 4) LF_I8_LAUNCH(72, 1, 4, 4, 5, 5);
-        else return -1;
+        else return I8_ERR_SHAPE;
     }
 #undef LF_I8_LAUNCH
+    if (rc < 0) return rc;
     const size_t per_wg = (size_t)MT * a.NT * 256;
     hipLaunchKernelGGL(k_ajtai_i8_sum, dim3((unsigned)cdiv(per_wg + NP * R.RD, 256), 1), dim3(256), 0, s, part, per_wg, dsum, NP * R.RD, nchunks, sum);
     hipLaunchKernelGGL(k_ajtai_i8_finish, dim3((unsigned)cdiv((size_t)NP * kappa * R.RD, 256), 1), dim3(256), 0, s, sum, per_wg, MT, a.NT, NP, kappa, row0,
                        kappa_total, R.RD, R.NL, R.p_small, R.soa_out, coef_out, NP, 0u);
-    return (int)grid;
+    return i8_launched() < 0 ? I8_ERR_HIP : (int)grid;
 }
 
 // =====================================================================================================================================
@@ -1514,17 +1504,17 @@ __global__ void __launch_bounds__(256) k_coef_eval_i8_finish(const long long *su
 size_t coef_eval_i8_eb_bytes(size_t n) { return 24 * ((n + 15) / 16 * 16) + 64; }
 size_t coef_eval_i8_part_words(u32 nwg) { return (size_t)nwg * 24 * 2 * 256; }
 // planes [24][ldp] (n columns from the pointer), eq [3][ldeq] (same columns), K planes (mode_bits) or the coefficients themselves (mode 0, bound =
-// max |coefficient|).  EB / part / sum: scratch (coef_eval_i8_eb_bytes, coef_eval_i8_part_words(nwg), 24*2*256 words).  Returns 0, or -1 if the
-// shape is not handled (caller falls back to k_coef_eval).
+// max |coefficient|).  EB / part / sum: scratch (coef_eval_i8_eb_bytes, coef_eval_i8_part_words(nwg), 24*2*256 words).  Result: lf_i8_launch.h (shape
+// not handled: the caller falls back to k_coef_eval).
 int launch_coef_eval_i8(const int32_t *planes, size_t ldp, size_t n, const u64 *eq, size_t ldeq, u32 K, int mode_bits, u64 bound, unsigned char *EB, u32 nwg,
                         int32_t *part, long long *sum, u64 *out, hipStream_t s) {
-    if (!n || (mode_bits && K == 0)) return -1;
+    if (!n || (mode_bits && K == 0)) return I8_ERR_SHAPE;
     u32 nbytes = 0;
     if (!mode_bits) {   // balanced base-256 digits needed for |v| <= bound
         u64 cap = 127;
         nbytes = 1;
         while (cap < bound && nbytes < 4) { cap = cap * 256 + 127; nbytes++; }
-        if (cap < bound) return -1;
+        if (cap < bound) return I8_ERR_SHAPE;
     }
     const size_t ldb = (n + 15) / 16 * 16;
     hipLaunchKernelGGL(k_eq_pack_i8, dim3((unsigned)cdiv(3 * cdiv(cdiv(ldb, 64), 8), 4)), dim3(256), 0, s, eq, ldeq, n, ldb, EB);
@@ -1545,6 +1535,6 @@ int launch_coef_eval_i8(const int32_t *planes, size_t ldp, size_t n, const u64 *
         hipLaunchKernelGGL(k_ajtai_i8_sum, dim3((unsigned)cdiv(per_wg, 256)), dim3(256), 0, s, part, per_wg, part, 0u, grid, sum);
         hipLaunchKernelGGL(k_coef_eval_i8_finish, dim3((unsigned)cdiv(mode_bits ? a.rows * 72 : 72, 256)), dim3(256), 0, s, sum, k0, a.rows, mode_bits, nbytes, out);
     }
-    return 0;
+    return i8_launched();
 }
 }  // namespace lf

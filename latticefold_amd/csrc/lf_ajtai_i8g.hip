@@ -19,15 +19,14 @@
 // -- unlike the plane groups of k_ajtai_i8s -- nothing is fetched twice and no pair of workgroups has to be kept in step.  int32
 // accumulators are flushed to a fresh partial slot every `ft` tiles: |a b| <= 2^14 per MAC, 8 RD MACs per tile and output.
 #include <hip/hip_runtime.h>
-#include <cstdlib>
 #include "lf_field.cuh"
 #include "lf_ajtai_i8.h"
 #include "lf_i8g_dec.cuh"
+#include "lf_i8_mma.cuh"
 
 namespace lf {
+using namespace i8mma;
 namespace {
-inline size_t cdiv(size_t a, size_t b) { return (a + b - 1) / b; }
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef unsigned long long ull;
 // workgroup barrier that waits for LDS traffic only (see lf_ajtai_i8.hip)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -665,9 +664,9 @@ int ajtai_i8g_scratch(const AjtaiI8Ring &R, u32 MT, size_t n, u32 NP, u32 nwg, s
     return 0;
 }
 int launch_ajtai_i8g(const AjtaiI8Ring &R, const unsigned char *Ab, u32 MT, const unsigned long long *pre, size_t ldw, size_t n, u32 kappa, u32 row0, u32 kappa_total,
-                     u32 NP, u32 nwg, int32_t *part, int32_t *dsum, long long *sum, u64 *coef_out, hipStream_t s, int per_plane) {
+                     u32 NP, u32 nwg, int32_t *part, int32_t *dsum, long long *sum, u64 *coef_out, hipStream_t s, int per_plane, bool prof) {
     GPlan g;
-    if (!g_plan(R, MT, n, NP, nwg, &g) || R.NL * kappa > 16 * MT) return -1;
+    if (!g_plan(R, MT, n, NP, nwg, &g) || R.NL * kappa > 16 * MT) return I8_ERR_SHAPE;
     AjtaiI8GArgs a;
     a.Ab = Ab; a.MT = MT; a.pre = pre; a.ldw = ldw; a.NP = NP; a.ntiles = (u32)((n + 7) / 8); a.ft = g.ft;
     for (int h = 0; h < 2; h++) { a.m_lo[h] = g.m_lo[h]; a.mth[h] = g.mth[h]; a.nch[h] = g.nch[h]; a.tpw[h] = g.tpw[h]; a.nsub[h] = g.nsub[h]; }
@@ -675,31 +674,18 @@ int launch_ajtai_i8g(const AjtaiI8Ring &R, const unsigned char *Ab, u32 MT, cons
     a.part[1] = part + (size_t)g.nch[0] * g.nsub[0] * g.per[0];
     a.dsum = dsum;
     const dim3 grid(g.nch[0] + g.nch[1]), block(512);
-#define LF_G_LAUNCH(RD_, MTW_, NTW_)                                                                                                                 \
-    do {                                                                                                                                             \
-        static bool attr_ = false;                                                                                                                   \
-        if (!attr_) { (void)hipFuncSetAttribute((const void *)k_ajtai_i8g<RD_, MTW_, NTW_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_ = true; } \
-        typedef GX<RD_, MTW_, NTW_> GL_;                                                                                                             \
-        hipLaunchKernelGGL((k_ajtai_i8g<RD_, MTW_, NTW_>), grid, block, GL_::lds_bytes(), s, a);                                                     \
-    } while (0)
-    static const bool gprof = getenv("LF_I8G_PROF") != nullptr;
-    if (gprof && R.RD == 24) {
-        static bool attr_p = false;
-        if (!attr_p) {
-            (void)hipFuncSetAttribute((const void *)k_ajtai_i8g<24, 7, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_ajtai_i8g<24, 7, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_p = true;
-        }
-        typedef GX<24, 7, 4> G4_;
-        typedef GX<24, 7, 2> G2_;
+    int rc;
+#define LF_G_LAUNCH(PROF_, RD_, MTW_, NTW_) rc = i8_launch_lds<k_ajtai_i8g<RD_, MTW_, NTW_, PROF_>>(grid, block, GX<RD_, MTW_, NTW_>::lds_bytes(), s, a)
+    if (prof && R.RD == 24) {
         static const unsigned long long zeros[64] = {0};
-        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_i8g_prof), zeros, sizeof(zeros), 0, hipMemcpyHostToDevice, s);
-        if (g.NT == 16) hipLaunchKernelGGL((k_ajtai_i8g<24, 7, 4, true>), grid, block, G4_::lds_bytes(), s, a);
-        else hipLaunchKernelGGL((k_ajtai_i8g<24, 7, 2, true>), grid, block, G2_::lds_bytes(), s, a);
-    } else if (R.RD == 24 && g.NT == 16) LF_G_LAUNCH(24, 7, 4);
-    else if (R.RD == 24) LF_G_LAUNCH(24, 7, 2);
-    else LF_G_LAUNCH(72, 4, 6);
+        I8_HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_i8g_prof), zeros, sizeof(zeros), 0, hipMemcpyHostToDevice, s));
+        if (g.NT == 16) LF_G_LAUNCH(true, 24, 7, 4);
+        else LF_G_LAUNCH(true, 24, 7, 2);
+    } else if (R.RD == 24 && g.NT == 16) LF_G_LAUNCH(false, 24, 7, 4);
+    else if (R.RD == 24) LF_G_LAUNCH(false, 24, 7, 2);
+    else LF_G_LAUNCH(false, 72, 4, 6);
 #undef LF_G_LAUNCH
+    if (rc < 0) return rc;
     hipLaunchKernelGGL(k_ajtai_i8g_sum, dim3((unsigned)cdiv(g.sum_words, 256)), dim3(256), 0, s, a.part[0], g.per[0], g.nch[0] * g.nsub[0], a.part[1], g.per[1],
                        g.nch[1] * g.nsub[1], dsum, g.ndi, g.nch[0], sum);
     if (per_plane)
@@ -708,7 +694,6 @@ int launch_ajtai_i8g(const AjtaiI8Ring &R, const unsigned char *Ab, u32 MT, cons
     else
     hipLaunchKernelGGL(k_ajtai_i8g_finish<false>, dim3((unsigned)cdiv((size_t)kappa * R.RD, 256)), dim3(256), 0, s, sum, g.mth[0], g.mth[1], g.NT, g.ndi, NP, kappa, row0,
                        kappa_total, R.RD, R.NL, R.p_small, R.soa_out, coef_out);
-    if (per_plane && hipGetLastError() != hipSuccess) return -1;
-    return (int)grid.x;
+    return i8_launched() < 0 ? I8_ERR_HIP : (int)grid.x;
 }
 }  // namespace lf

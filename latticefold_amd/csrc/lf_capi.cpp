@@ -593,9 +593,9 @@ int commit_parts_i8g(lf_ctx *c, const unsigned char *D, size_t ldn, u32 NP, u64 
     const size_t ev = c->ev_begin(1);
     for (u32 ch = 0; ch < nch; ch++) {
         const u32 row0 = ch * kc, kn = c->kappa - row0 < kc ? c->kappa - row0 : kc;
-        if (launch_ajtai_i8g(R, c->dAb + (size_t)ch * chunk_bytes, MT, (const unsigned long long *)D, ldn / 8, c->nA, kn, row0, c->kappa, NP, nwg, part, dsum, sum, coef,
-                             c->stream(), 1) < 0)
-            return hipGetLastError() == hipSuccess ? LF_ERR_UNSUPPORTED : LF_ERR_HIP;
+        const int g = launch_ajtai_i8g(R, c->dAb + (size_t)ch * chunk_bytes, MT, (const unsigned long long *)D, ldn / 8, c->nA, kn, row0, c->kappa, NP, nwg, part, dsum, sum,
+                                       coef, c->stream(), 1, c->tn.i8g_prof);
+        if (g < 0) return i8_rc(g);
     }
     c->ev_end(ev);
     launch_crt_fwd(c->dcrt, coef, ntt, ne, c->stream());

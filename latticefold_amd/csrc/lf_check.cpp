@@ -95,6 +95,7 @@ static int cccs_check(C *c, const u64 *cccs, const lf_witness *wit, u64 bound, u
     constexpr size_t RE = R::RE;
     std::lock_guard<std::mutex> g(c->mu);
     RET(check_state(c, wit, true));
+    c->tn = Tunables::read(R::lut_min_default);   // (the commitment's switches, as every entry point that reaches the commit kernels)
     HIPCHK(hipSetDevice(c->device));
     const lf_params &P = c->P;
     const size_t cmw = (size_t)P.kappa * RE;
@@ -130,6 +131,7 @@ static int lcccs_check(C *c, const u64 *lcccs, const lf_witness *wit, u64 bound,
     constexpr size_t RE = R::RE, TAU = R::TAU;
     std::lock_guard<std::mutex> g(c->mu);
     RET(check_state(c, wit, true));
+    c->tn = Tunables::read(R::lut_min_default);   // (the commitment's switches, as every entry point that reaches the commit kernels)
     const lf_params &P = c->P;
     std::vector<typename R::Ext> pt;
     if (!lfs::lcccs_point<typename R::Host>(P, lcccs, pt)) return LF_ERR_UNSUPPORTED;   // the reference's points are diagonal challenges (as lf_fold_step)

@@ -86,8 +86,8 @@ void lf_planes_release(lf_ctx *ctx, size_t bytes, int32_t *p);
 int lf_ctx_device(const lf_ctx *ctx);
 
 
-// Test/diagnostic switches of the fold-step driver (environment variables): read ONCE at the start of every
-// lf_linearize / lf_fold_step call -- never inside the round loops.
+// Test/diagnostic switches of the fold-step driver and the commit kernels (environment variables): read ONCE at the start of every
+// lf_linearize / lf_fold_step / commit call -- never inside the round loops, never in a launcher.
 struct Tunables {
     bool lin_u_eval = false, fold_unfused = false, fold_no_lut = false, fold_tab_r1 = false, theta_eval = false, fold_no_r4tab = false, fold_no_r5tab = false;
     bool fold_rounds_no_split = false;   // LF_FOLD_ROUNDS_NO_SPLIT: the large table rounds (k_fold_round modes 1, 6, 7) evaluate all five points themselves (four lazy products per table)
@@ -106,6 +106,10 @@ struct Tunables {
                                      // (a round there is a ~30 us launch: an exchange costs as much as it saves); never above m / 16
     size_t shard_fold_min = 2048;    // LF_SHARD_FOLD_MIN: the same for the folding sumcheck (96 tables per entry: rounds stay worth sharding down to the persistent tail's size)
     long i8_wgs = 0;                 // LF_I8_WGS: workgroups of the int8 commit kernel (0: one per CU)
+    int i8_couple_w = 4;             // LF_I8_COUPLE_W: window, in tiles, of the pair coupling of the specialised commit kernels (k_ajtai_i8s / k_ajtai_i8x); 0 switches the coupling off
+    long i8g_wgs = 0;                // LF_I8G_WGS: workgroups of the general commit kernel (test hook; 0: one per CU)
+    bool i8_prof = false;            // LF_I8_PROF: the profiled instantiations of k_ajtai_i8s / k_ajtai_i8x (per-phase shader-clock totals, tools/i8_prof.py)
+    bool i8g_prof = false;           // LF_I8G_PROF: the profiled instantiation of k_ajtai_i8g (tools/i8g_prof.py)
     bool lin_no_r1cs = false;        // LF_LIN_NO_R1CS: (BabyBear) the R1CS shape through the generic linearization round kernel
     bool lin_no_small = false;       // LF_LIN_NO_SMALL: (BabyBear) small linearization rounds as separate fix / round / reduce launches
     size_t dot_min = 4096;           // LF_DOT_MIN: columns from which the int8 form of the inner products is used
@@ -148,6 +152,10 @@ struct Tunables {
         if ((e = getenv("LF_FOLD_SV_MIN"))) t.sv_min = (size_t)atoll(e);
         if ((e = getenv("LF_FOLD_SV_ROUNDS"))) t.sv_rounds = atoi(e);
         if ((e = getenv("LF_I8_WGS"))) t.i8_wgs = atol(e);
+        if ((e = getenv("LF_I8_COUPLE_W"))) t.i8_couple_w = atoi(e);
+        if ((e = getenv("LF_I8G_WGS"))) t.i8g_wgs = atol(e);
+        t.i8_prof = getenv("LF_I8_PROF") != nullptr;
+        t.i8g_prof = getenv("LF_I8G_PROF") != nullptr;
         if ((e = getenv("LF_SHARD_TWO_LANES"))) t.shard_two_lanes = atoi(e) != 0;
         if ((e = getenv("LF_SHARD_LIN_MIN"))) t.shard_lin_min = (size_t)atoll(e);
         if ((e = getenv("LF_SHARD_FOLD_MIN"))) t.shard_fold_min = (size_t)atoll(e);

@@ -493,7 +493,7 @@ int FoldB2::gemm_round(u32 round) {
         for (int sd = 0; sd < 2; sd++) {
             if (S[sd].sv_bits) { sv_bits[sd] = S[sd].sv_bits; continue; }
             RET(c->tbuf(sd ? "sv_bits_R" : "sv_bits_L", sv_bits_words(N, K), &sv_bits[sd]));
-            launch_sv_bits(S[sd].planes, N, N, K, sv_bits[sd], c->stream());
+            if (launch_sv_bits(S[sd].planes, N, N, K, sv_bits[sd], c->stream()) < 0) return LF_ERR_HIP;
         }
     hipStream_t sg = round == 1 ? (sv_two_streams && !sharded ? c->st_lane[1] : c->stream()) : sv_g_stream;
     // the tables of round 1 come from fold prepare, whose left chain ran on this lane's stream: the other stream has not seen it (later rounds: fixed on sg itself)
@@ -512,9 +512,9 @@ int FoldB2::gemm_round(u32 round) {
         svE_ensure(round);
         Ei = svE[round - 1]; ldE = m >> round;   // entries of E_round
     }
-    if (launch_sv_round(c->dcrt, svV, sv_bits[0], sv_bits[1], N, a.eqB, a.ld, a.p0, a.pcnt, K, d_mu, d_coef, sveb, svpart, svtot, svtp, gtmp, od, c->stream(), g_ready,
-                        Ei, ldE, w01) != 0)
-        return LF_ERR_UNSUPPORTED;
+    const int rc = launch_sv_round(c->dcrt, svV, sv_bits[0], sv_bits[1], N, a.eqB, a.ld, a.p0, a.pcnt, K, d_mu, d_coef, sveb, svpart, svtot, svtp, gtmp, od, c->stream(),
+                                   g_ready, Ei, ldE, w01);
+    if (rc < 0) return i8_rc(rc);
     c->sv_round_mask |= 1u << (round - 1);
     return LF_OK;
 }
@@ -643,7 +643,9 @@ int FoldB2::evaluations() {
             unsigned char *ybq = nullptr;
             if (!c->tn.dot_valu && cnt >= c->tn.dot_min && P.t <= 3 && K <= 16 && ((((size_t)(S[0].z + c0)) ^ ((size_t)(S[1].z + c0))) & 15) == 0) {
                 RET(c->tbuf("dot_yb", dot_i8_yb_bytes(n + 1), &ybq));
-                if (launch_dot_pack_y(S[0].z + c0, q + c0, n, P.t, cnt, ybq, c->stream()) != 0) ybq = nullptr;
+                const int rc = launch_dot_pack_y(S[0].z + c0, q + c0, n, P.t, cnt, ybq, c->stream());
+                if (rc == i8mma::I8_ERR_HIP) return LF_ERR_HIP;
+                if (rc < 0) ybq = nullptr;
             }
             RET(c->fork(c->stream(), s1));           // q = M_j^T eq(r_o) is ready (and packed)
             u64 *dpart1;
@@ -678,14 +680,14 @@ int fold_impl(lf_ctx *c, Transcript &tr, SideState *S /* [2] */, u64 *lcccs_out,
     RET(f.finish(lcccs_out, w_out, [&](const std::vector<int8_t> &rho8, int8_t *d_rho, int32_t *npl) -> int {
         HIPCHK(hipMemcpyAsync(d_rho, rho8.data(), rho8.size(), hipMemcpyHostToDevice, c->stream()));
         LF_TRACE(c, "theta/eta");
-        int rc = 1;
+        int rc = i8mma::I8_ERR_SHAPE;
         if (!c->tn.fold_witness_valu) {
             int rho_max = 0;
             for (int8_t r : rho8) rho_max = std::max(rho_max, std::abs((int)r));
             rc = launch_fold_witness_i8(S[0].planes, S[1].planes, f.N, f.K, d_rho, rho_max, npl, c->stream());
         }
-        if (rc > 0) launch_fold_witness(S[0].planes, S[1].planes, f.N, f.K, d_rho, npl, c->stream());   // (the shapes the int8 form declines, or the switch)
-        return rc < 0 ? LF_ERR_HIP : LF_OK;
+        if (rc == i8mma::I8_ERR_SHAPE) launch_fold_witness(S[0].planes, S[1].planes, f.N, f.K, d_rho, npl, c->stream());   // (the shapes the int8 form declines, or the switch)
+        return rc == i8mma::I8_ERR_HIP ? LF_ERR_HIP : LF_OK;
     }));
     c->ev_end(ph);
     return LF_OK;

@@ -18,9 +18,10 @@
 #include <hip/hip_runtime.h>
 #include "lf_field.cuh"
 #include "lf_kernels.h"
+#include "lf_i8_mma.cuh"
 
 namespace lf {
-typedef int v4i __attribute__((ext_vector_type(4)));
+using namespace i8mma;
 
 // four bits of x (bit b -> byte b) times mul (1, or 0xFF for a negative entry: bytes 0x01 -> 0xFF = -1).  x * 0x00204081 copies bit b to the positions
 // b + 7 j, all distinct for b < 4, j < 4 (no carries); the mask keeps b + 7 b = 8 b.
@@ -101,12 +102,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     }
 }
 
-// 0: launched; 1: shape not handled (the caller launches k_fold_witness); -1: the launch failed
+// Result: lf_i8_launch.h (shape not handled: the caller launches k_fold_witness)
 int launch_fold_witness_i8(const int32_t *planesL, const int32_t *planesR, size_t n, u32 K, const int8_t *rho_dev, int rho_max, int32_t *out, hipStream_t s) {
-    if (K < 1 || K > 16 || n == 0 || (n & 3) || rho_max > 63) return 1;
-    if ((((uintptr_t)planesL) | ((uintptr_t)planesR) | ((uintptr_t)out)) & 15) return 1;
+    if (K < 1 || K > 16 || n == 0 || (n & 3) || rho_max > 63) return I8_ERR_SHAPE;
+    if ((((uintptr_t)planesL) | ((uintptr_t)planesR) | ((uintptr_t)out)) & 15) return I8_ERR_SHAPE;
     const size_t blocks = (n + 255) / 256;       // four chunks of 64 columns per block and trip
     hipLaunchKernelGGL(k_fold_witness_i8, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, s, planesL, planesR, n, K, rho_dev, out);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return i8_launched();
 }
 }  // namespace lf

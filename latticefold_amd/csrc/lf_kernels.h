@@ -86,7 +86,7 @@ struct ZkI8 {
     int *dev = nullptr;   // A operands [3 classes][2 tiles][64 lanes] x 16 bytes, then the output planes [3][8]
 };
 int zk_i8_prepare(const DevCrt &t, u64 B, ZkI8 *zk, hipStream_t s);   // 0, or -1 for a HIP error
-// 0: launched; 1: shape not handled (the caller launches k_recompose_crt_b4); -1: the launch failed
+// result: lf_i8_launch.h (shape not handled: the caller launches k_recompose_crt_b4)
 int launch_recompose_crt_i8(const ZkI8 &zk, const int32_t *planes, size_t n_planes, u32 wit_len, u32 K, u64 *out, size_t ldz, size_t off, hipStream_t s);
 // l-infinity norm (a15): max |centred coefficient| of canonical coefficient table -> *out_max (u64)
 void launch_linf(const u64 *coef, size_t n, u64 *out_max, hipStream_t s);
@@ -141,7 +141,7 @@ void launch_g_rows(const DevCrt &t, u32 nm, const u32 *const *rowptr, const u32 
 void launch_fix_ring(const DevCrt &t, const u64 *in, u64 *out, size_t n_in, Fq3Const r, hipStream_t s);
 void launch_fix_fq3(const DevCrt &t, const u64 *in, u64 *out, size_t n_in, Fq3Const r, hipStream_t s);
 // batched inner products on the int8 matrix cores (lf_dot_i8.hip): out[(a*nb + b)*24 + 3*slot + q] = sum_i X_a[slot][i] * Y_b[slot][i], na <= 16, nb <= 3.
-// YB / part / tot: scratch (dot_i8_yb_bytes(n), dot_i8_part_words(n) int32, dot_i8_tot_words() int64).  Returns 0, or -1 if the shape is not handled.
+// YB / part / tot: scratch (dot_i8_yb_bytes(n), dot_i8_part_words(n) int32, dot_i8_tot_words() int64).  Result: lf_i8_launch.h.
 size_t dot_i8_yb_bytes(size_t n);
 size_t dot_i8_part_words(size_t n);
 size_t dot_i8_tot_words();
@@ -293,7 +293,7 @@ u32 launch_fold_tail(const DevCrt &t, const FoldTailArgs &A, int num_cus, hipStr
 void launch_fold_witness(const int32_t *planesL, const int32_t *planesR, size_t n, u32 K, const int8_t *rho_dev, int32_t *out,
                          hipStream_t s);
 // the same on the int8 matrix cores (lf_fold_i8.hip): K <= 16, n a multiple of 4, 16-byte aligned tables, rho_max = max |rho coefficient| <= 63 (the wrap
-// X^24 = X^12 - 1 is inside the int8 matrix).  Returns 0, 1 if the shape is not handled (nothing launched), -1 if the launch failed.
+// X^24 = X^12 - 1 is inside the int8 matrix).  Result: lf_i8_launch.h.
 int launch_fold_witness_i8(const int32_t *planesL, const int32_t *planesR, size_t n, u32 K, const int8_t *rho_dev, int rho_max, int32_t *out,
                            hipStream_t s);
 

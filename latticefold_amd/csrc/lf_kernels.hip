@@ -235,7 +235,7 @@ void launch_recompose_crt(const DevCrt &t, const int32_t *planes, size_t n_plane
                           u64 *out, size_t ldz, size_t off, hipStream_t s, const ZkI8 *zk) {
     if (mode_bits && L == 4 && B < ((u64)1 << 20) && (n_planes & 3) == 0 && ((uintptr_t)planes & 15) == 0) {
         // on the int8 matrix cores where the context holds the matrix of these tables for this base (a failed launch shows again at the next one)
-        if (zk && zk->state == 1 && zk->B == B && launch_recompose_crt_i8(*zk, planes, n_planes, wit_len, K, out, ldz, off, s) != 1) return;
+        if (zk && zk->state == 1 && zk->B == B && launch_recompose_crt_i8(*zk, planes, n_planes, wit_len, K, out, ldz, off, s) != i8mma::I8_ERR_SHAPE) return;
         BInt4 bi;
         bi.v[0] = 1;
         for (int l = 1; l < 4; l++) bi.v[l] = bi.v[l - 1] * (long long)B;

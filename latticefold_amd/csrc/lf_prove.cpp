@@ -314,7 +314,7 @@ static int linearize_impl(lf_ctx *c, Transcript &tr, const u64 *cccs, const lf_w
                 }
                 RET(c->h2d_small(vsp.wts, w.data(), w.size() * 8));
                 HIPCHK(hipStreamWaitEvent(c->stream(), c->ev_aux, 0));
-                launch_sv_vs_combine(c->dcrt, vsp.part, vsp.nblocks, vsp.wts, P.K, vs, c->stream());
+                if (launch_sv_vs_combine(c->dcrt, vsp.part, vsp.nblocks, vsp.wts, P.K, vs, c->stream()) < 0) return LF_ERR_HIP;
             } else
                 RET(coef_eval_dev(c, wit->planes, c->N, eqr, m, P.K, 1, partial, vs, c->N, wit));
             launch_vs_combine(vs, P.K, od, c->stream());
@@ -401,7 +401,8 @@ int coef_eval_dev(lf_ctx *c, const int32_t *planes, size_t n, const u64 *eq, siz
                 RET(c->tbuf("vs_part", sv_vs_part_words(n, K), &part));
                 RET(c->tbuf("vs_tot", sv_vs_tot_words(K), &tot));
                 if (c->stream() != c->st_lane[1]) HIPCHK(hipStreamWaitEvent(c->stream(), c->bits_ev[sd], 0));
-                if (launch_sv_vs(c->bits_ptr[sd], n, eq, ldeq, K, EB, part, tot, od, c->stream()) == 0) return LF_OK;
+                const int rc = launch_sv_vs(c->bits_ptr[sd], n, eq, ldeq, K, EB, part, tot, od, c->stream());
+                if (rc != i8mma::I8_ERR_SHAPE) return rc == 0 ? LF_OK : LF_ERR_HIP;
                 break;
             }
     if (n >= 64) {
@@ -412,7 +413,8 @@ int coef_eval_dev(lf_ctx *c, const int32_t *planes, size_t n, const u64 *eq, siz
         RET(c->tbuf("ce_eb", coef_eval_i8_eb_bytes(n), &EB));
         RET(c->tbuf("ce_part", coef_eval_i8_part_words(nwg), &part));
         RET(c->tbuf("ce_sum", (size_t)24 * 2 * 256, &sum));
-        if (launch_coef_eval_i8(planes, ldp ? ldp : n, n, eq, ldeq, K, mode_bits, c->P.B / 2, EB, nwg, part, sum, od, c->stream()) == 0) return LF_OK;
+        const int rc = launch_coef_eval_i8(planes, ldp ? ldp : n, n, eq, ldeq, K, mode_bits, c->P.B / 2, EB, nwg, part, sum, od, c->stream());
+        if (rc != i8mma::I8_ERR_SHAPE) return rc == 0 ? LF_OK : LF_ERR_HIP;
     }
     launch_coef_eval(c->dcrt, planes, n, eq, ldeq, K, mode_bits, partial, od, c->stream(), ldp);
     return LF_OK;
@@ -434,15 +436,15 @@ int dot_batch_dev(lf_ctx *c, const u64 *X, size_t ldx, u32 na, const u64 *Y, siz
         RET(c->tbuf(std::string("dot_yb") + tag, dot_i8_yb_bytes(n + 1), &yb));            // (+1: an odd column slice starts one column early)
         RET(c->tbuf(std::string("dot_i8_part") + tag, dot_i8_part_words(n + 1), &part));
         RET(c->tbuf(std::string("dot_i8_tot") + tag, dot_i8_tot_words(), &tot));
-        bool ok = true;
+        int rc = 0;
         // a launch takes at most three vectors Y (their 72 digit rows fill its column tiles): the four matrices of a degree-three CCS (arith/ccs.rs:14-43) go in two
         // groups of two (the 64-bit VALU kernel this shape used to fall back to took 4 x 1.03 ms of a 19.3 ms C4 step)
         const u32 gsz = nb <= 3 ? nb : 2;
-        for (u32 b0 = 0; b0 < nb && ok; b0 += gsz)
-            for (u32 a0 = 0; a0 < na && ok; a0 += 16)
-                ok = launch_dot_batch_i8(c->dcrt, X + (size_t)a0 * 24 * ldx, ldx, na - a0 < 16 ? na - a0 : 16, Y + (size_t)b0 * 24 * ldy, ldy, nb - b0 < gsz ? nb - b0 : gsz, n, yb, part, tot,
-                                         od + (size_t)a0 * nb * 24, st, yb_pre != nullptr && nb <= 3, nb, b0) == 0;
-        if (ok) return LF_OK;
+        for (u32 b0 = 0; b0 < nb && rc == 0; b0 += gsz)
+            for (u32 a0 = 0; a0 < na && rc == 0; a0 += 16)
+                rc = launch_dot_batch_i8(c->dcrt, X + (size_t)a0 * 24 * ldx, ldx, na - a0 < 16 ? na - a0 : 16, Y + (size_t)b0 * 24 * ldy, ldy, nb - b0 < gsz ? nb - b0 : gsz, n, yb, part, tot,
+                                         od + (size_t)a0 * nb * 24, st, yb_pre != nullptr && nb <= 3, nb, b0);
+        if (rc != i8mma::I8_ERR_SHAPE) return rc == 0 ? LF_OK : LF_ERR_HIP;
     }
     if (nb > 4) {   // wide CCS envelope on the 64-bit VALU kernel (four tables Y per launch): groups of four into a scratch, copied to their place in [na][nb][24]
         u64 *tmp;
@@ -701,7 +703,7 @@ int lf_fold_step(lf_ctx *c, lf_transcript *t, const uint64_t *acc, const lf_witn
             u32 *bits;
             if (c->tbuf(sd ? "sv_bits_R" : "sv_bits_L", sv_bits_words(c->N, P.K), &bits) != LF_OK) break;
             if (!c->bits_ev[sd] && hipEventCreateWithFlags(&c->bits_ev[sd], hipEventDisableTiming) != hipSuccess) break;
-            launch_sv_bits(ws[sd]->planes, c->N, c->N, P.K, bits, c->st_lane[1]);
+            if (launch_sv_bits(ws[sd]->planes, c->N, c->N, P.K, bits, c->st_lane[1]) < 0) break;
             if (hipEventRecord(c->bits_ev[sd], c->st_lane[1]) != hipSuccess) break;
             c->bits_wit[sd] = ws[sd]; c->bits_ptr[sd] = bits;
             S[sd].sv_bits = bits;

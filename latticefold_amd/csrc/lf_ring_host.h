@@ -92,8 +92,7 @@ template <> struct Ring<lf_ctx> {
     static void fix_final(lf_ctx *c, const u64 *in, size_t, u32 rows, const ExtC &r, u64 *out) { launch_fix_final(c->dcrt, in, rows, r, out, c->stream()); }
     // one row of A (NTT form [RE][cnt]) -> row i of a row chunk of the byte planes: inverse CRT and packing fused
     static int pack_row(lf_ctx *c, const u64 *row, size_t cnt, u32 i, u32 MT, unsigned char *Ab) {
-        launch_ajtai_icrt_pack_i8(c->d_icrt, row, cnt, i, MT, Ab, c->stream());
-        return LF_OK;
+        return launch_ajtai_icrt_pack_i8(c->d_icrt, row, cnt, i, MT, Ab, c->stream()) < 0 ? LF_ERR_HIP : LF_OK;
     }
     static lf_ctx *owner(lf_ctx *c) { return c; }
     static AjtaiI8Ring i8() { return ajtai_i8_goldilocks(); }
@@ -143,8 +142,7 @@ template <> struct Ring<BbCtxImpl> {
         RET(c->tbuf("i8_prep_canon", (size_t)RE * cnt, &canon));
         launch_icrt_dense(c->d_icrt, row, coef, cnt, c->stream());
         launch_soa_to_aos(coef, canon, cnt, c->stream());
-        launch_ajtai_pack_i8(canon, 1, RE, cnt, i, MT, I.RD, I.NL, Ab, c->stream());
-        return LF_OK;
+        return launch_ajtai_pack_i8(canon, 1, RE, cnt, i, MT, I.RD, I.NL, Ab, c->stream()) < 0 ? LF_ERR_HIP : LF_OK;
     }
     static lf_ctx *owner(BbCtxImpl *c) { return c->owner; }
     static AjtaiI8Ring i8() { return ajtai_i8_babybear(); }
@@ -276,6 +274,9 @@ int upload_consts(C *c, const std::string &name, const std::vector<T> &v, T **ou
     return Ring<C>::h2d_consts(c, *out, v.data(), v.size() * sizeof(T));
 }
 
+// a launcher's negative result (lf_i8_launch.h) as an ABI code: a shape nothing handles / a failed HIP call
+inline int i8_rc(int r) { return r == i8mma::I8_ERR_HIP ? LF_ERR_HIP : LF_ERR_UNSUPPORTED; }
+
 // ---- general commit, host side -----------------------------------------------------------------------------------------------------------------------
 // The contraction of `batch` operands whose digit words [NP][RE][ntiles] of this rank's columns the caller's pass cut(b, pre, ntiles) writes: NP = 10 (5 on
 // BabyBear) for an arbitrary element, 5 for the int32 planes of a witness handle, fewer for the digits of a gadget decomposition (ajtai_i8g_planes_base).
@@ -288,8 +289,7 @@ int commit_dev_pre(C *c, u32 NP, u32 batch, u64 *out_dev, bool timed, Cut &&cut)
     const AjtaiI8Ring I = R::i8();
     const u32 nch = c->i8_nch, kc = c->i8_kc, MT = ajtai_i8_row_tiles(I, kc);
     const size_t ntiles = (c->nA + 7) / 8, chunk_bytes = ntiles * (I.RD / 8) * MT * 1024;
-    const char *e_wgs = getenv("LF_I8G_WGS");           // (test hook: workgroups of the general commit kernel; default one per CU)
-    const u32 nwg = e_wgs && atoi(e_wgs) > 0 ? (u32)atoi(e_wgs) : 256;
+    const u32 nwg = c->tn.i8g_wgs > 0 ? (u32)c->tn.i8g_wgs : 256;   // (default: one per CU)
     size_t pw, dw, sw;
     if (ajtai_i8g_scratch(I, MT, c->nA, NP, nwg, &pw, &dw, &sw) != 0) return LF_ERR_UNSUPPORTED;
     unsigned long long *pre;
@@ -310,8 +310,9 @@ int commit_dev_pre(C *c, u32 NP, u32 batch, u64 *out_dev, bool timed, Cut &&cut)
         cut(b, pre, ntiles);
         for (u32 ch = 0; ch < nch; ch++) {
             const u32 row0 = ch * kc, kn = c->kappa - row0 < kc ? c->kappa - row0 : kc;
-            const int g = launch_ajtai_i8g(I, c->dAb + (size_t)ch * chunk_bytes, MT, pre, ntiles, c->nA, kn, row0, c->kappa, NP, nwg, part, dsum, sum, co, c->stream());
-            if (g < 0) return LF_ERR_UNSUPPORTED;
+            const int g = launch_ajtai_i8g(I, c->dAb + (size_t)ch * chunk_bytes, MT, pre, ntiles, c->nA, kn, row0, c->kappa, NP, nwg, part, dsum, sum, co, c->stream(), 0,
+                                           c->tn.i8g_prof);
+            if (g < 0) return i8_rc(g);
         }
         if constexpr (R::montgomery) launch_aos_to_soa(co, cf, c->kappa, c->stream());   // BabyBear only: the kernel's element-major canonical words -> Montgomery planes
         launch_crt_fwd(R::tab(c), cf, ntt, c->kappa, c->stream());
@@ -375,9 +376,9 @@ int commit_planes_i8(C *c, const int32_t *planes, size_t ld, u32 k0, u32 NP, u64
             const u32 row0 = ch * kc, kn = c->kappa - row0 < kc ? c->kappa - row0 : kc;
             size_t ev = c->ev_begin(1);
             int g = launch_ajtai_i8(I, c->dAb + (size_t)ch * chunk_bytes, MT, planes, ld, c->nA, kn, row0, c->kappa, k0 + p0, np, nwg, part, dsum, sum, co, c->stream(),
-                                    bits, bits_nw, bits_rows);
+                                    c->tn.i8_couple_w, c->tn.i8_prof, bits, bits_nw, bits_rows);
             c->ev_end(ev);
-            if (g < 0) return LF_ERR_UNSUPPORTED;
+            if (g < 0) return i8_rc(g);
         }
         const size_t ne = (size_t)np * c->kappa;
         const W *src;
@@ -1223,6 +1224,7 @@ struct ring_ops<Ring<C>> {
         HIPCHK(hipSetDevice(c->device));
         u64 *o;
         RET(c->tbuf("io_o", (size_t)c->kappa * RE, &o));
+        c->tn = Tunables::read(R::lut_min_default);
         c->ev_reset();
         RET(commit_dev_i8g(c, nullptr, 0, 1, w->planes + c->A_col0, w->N, o, true));   // timed: lf_last_kernel_stats reports the stand-alone kernel
         c->ev_collect();
@@ -1352,6 +1354,7 @@ using lfring::GoldRing;
 using lfring::ring_ops;
 // the staging and commit helpers the provers of both backends call (unqualified, from the global namespace and from lfbb)
 using lfring::commit_dev_i8g;
+using lfring::i8_rc;
 using lfring::commit_dev_pre;
 using lfring::commit_planes_i8;
 using lfring::DevIo;

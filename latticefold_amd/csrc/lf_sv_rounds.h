@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include "lf_i8_launch.h"
 namespace lf {
 struct SvPair {
     unsigned char s, b;   // subset of the 2V signed bits whose signs are multiplied / whose magnitude bits are ANDed
@@ -53,9 +55,9 @@ size_t sv_tot_words(int V, uint32_t K);               // int32 words of their su
 size_t sv_tp_words(uint32_t K);                       // u64 words of the per-table polynomials
 // bit-plane form of a witness ([24][ldp] int32 planes, n positions, |v| < 2^K): rows of magnitude bits + one row of signs per coefficient
 size_t sv_bits_words(size_t n, uint32_t K, uint32_t rd = 24);   // rd: coefficients per ring element (24 / 72)
-void launch_sv_bits(const int32_t *planes, size_t ldp, size_t n, uint32_t K, uint32_t *bits, hipStream_t s, uint32_t rd = 24);
+int launch_sv_bits(const int32_t *planes, size_t ldp, size_t n, uint32_t K, uint32_t *bits, hipStream_t s, uint32_t rd = 24);
 // The GEMM stage alone, for the BabyBear backend (bb_sv_rounds.hip): rd coefficient groups per side, three column tiles of digit bytes EB[48][ldeb] in slot
-// order, all sv_num_pairs(V) digit monomials; the summed int32 tiles are left in tot (layout: lf_sv_rounds.hip).  0, or -1 (shape).
+// order, all sv_num_pairs(V) digit monomials; the summed int32 tiles are left in tot (layout: lf_sv_rounds.hip).  Results of every launch_* here: lf_i8_launch.h.
 size_t sv_tot_words_rd(uint32_t rd, int V, uint32_t K);
 size_t sv_part_words_rd(uint32_t rd, int V, uint32_t K);
 size_t sv_ldeb_pub(size_t npairs);
@@ -65,7 +67,7 @@ int launch_sv_gemm_tiles(uint32_t rd, int V, const uint32_t *bitsL, const uint32
 // norm part of round log2(V)+1:  out[X*24 + 3*slot + q] = gpart[...] + sum_tables mu_T sum_p eqB(p)(X) (h_T^3 - h_T)(p)(X),  X = 0..4.
 // bitsL / bitsR: launch_sv_bits forms of the two witnesses (nplanes positions); eqB: [3][ldeq]; the launch covers the pairs [pair0, pair0 + npairs)
 // (a rank's slice of a sharded step: the partial messages of the ranks add up; gpart = the same slice's G part);
-// coef: [sv_num_pairs(V)][4][3] words C_pi (device); mu_pow: [2K*3].  Returns 0, or -1 if the shape is not handled.
+// coef: [sv_num_pairs(V)][4][3] words C_pi (device); mu_pow: [2K*3].
 struct DevCrt;
 struct Fq3Const;
 int launch_sv_round(const DevCrt &t, int V, const uint32_t *bitsL, const uint32_t *bitsR, size_t nplanes, const uint64_t *eqB, size_t ldeq, size_t pair0, size_t npairs, uint32_t K,
@@ -75,7 +77,7 @@ int launch_sv_round(const DevCrt &t, int V, const uint32_t *bitsL, const uint32_
                     // against the 24 digit columns of E (two column tiles instead of three) and the finish multiplies by w01[0], w01[1] (host pointers)
                     const uint64_t *E = nullptr, size_t ldE = 0, const Fq3Const *w01 = nullptr);
 // v_s[k][c][q] = sum_i eq[q][i] * digit_k(planes[c][i]) of ONE witness from its bit-plane form (the two single pairs of the round-1 GEMM);
-// out[(k*24 + c)*3 + q] canonical.  Scratch: EB sv_eb_bytes(n / 2), part sv_vs_part_words(n, K), tot sv_vs_tot_words(K).  0, or -1 (shape).
+// out[(k*24 + c)*3 + q] canonical.  Scratch: EB sv_eb_bytes(n / 2), part sv_vs_part_words(n, K), tot sv_vs_tot_words(K).
 size_t sv_vs_part_words(size_t n, uint32_t K);
 size_t sv_vs_tot_words(uint32_t K);
 int launch_sv_vs(const uint32_t *bits, size_t n, const uint64_t *eq, size_t ldeq, uint32_t K, unsigned char *EB, int32_t *part, int32_t *tot, uint64_t *out, hipStream_t s);
@@ -83,5 +85,5 @@ int launch_sv_vs(const uint32_t *bits, size_t n, const uint64_t *eq, size_t ldeq
 size_t sv_vs_max_blocks(uint32_t K);
 size_t sv_vs_blocks_part_words(uint32_t nblocks, uint32_t K);
 int launch_sv_vs_blocks(const uint32_t *bits, size_t n, const uint64_t *eq_lo, size_t ldeq, uint32_t J, uint32_t K, unsigned char *EB, int32_t *part, hipStream_t s);
-void launch_sv_vs_combine(const DevCrt &t, const int32_t *part, uint32_t nblocks, const uint64_t *wts, uint32_t K, uint64_t *out, hipStream_t s);
+int launch_sv_vs_combine(const DevCrt &t, const int32_t *part, uint32_t nblocks, const uint64_t *wts, uint32_t K, uint64_t *out, hipStream_t s);
 }  // namespace lf

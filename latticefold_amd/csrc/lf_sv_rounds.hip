@@ -13,15 +13,14 @@
 //                  sum_pi C_pi(X) (M0 + X (M1 - M0)), times mu_T;
 //   k_sv_finish2   sum over the tables of a slot, evaluation at X = 0..4, plus the G part of the message.
 #include <hip/hip_runtime.h>
-#include <cstdlib>
 #include <utility>
 #include "lf_field.cuh"
 #include "lf_kernels.h"
 #include "lf_sv_rounds.h"
+#include "lf_i8_mma.cuh"
 
 namespace lf {
-static inline size_t cdiv(size_t a, size_t b) { return (a + b - 1) / b; }
-typedef int v4i __attribute__((ext_vector_type(4)));
+using namespace i8mma;
 constexpr u32 ONES4 = 0x01010101u;
 constexpr int ctz8(unsigned m) { int i = 0; while (i < 8 && !((m >> i) & 1)) i++; return i; }
 constexpr int pop8(unsigned m) { int n = 0; for (int i = 0; i < 8; i++) n += (m >> i) & 1; return n; }
@@ -83,12 +82,8 @@ __global__ void __launch_bounds__(256) k_sv_pack_eq(const u64 *eq, size_t ld, si
 #pragma unroll
     for (int t = 0; t < 16; t++) {
         const size_t pr = p0 + (size_t)sv_slot_pair(V, t >> 2, t & 3);
-        // balanced base-256 digits d_u in [-128, 127] of a representative of the word mod p: sum_u d_u 256^u = E or E - p.  With
-        // s = E' + 0x80..80 in [0, 2^64) the digits are (byte_u(s) - 128), i.e. byte_u(s) ^ 0x80 as int8 -- no bias column in the GEMM
         const u64 e = pr < npairs ? (single ? eq[(size_t)q * ld + pr] : eq[(size_t)q * ld + 2 * pr + h]) : 0;
-        u64 sb = e + 0x8080808080808080ull;
-        if (sb < e) sb += 0xFFFFFFFFull;          // wrapped past 2^64: take E - p instead (2^64 - p = 2^32 - 1)
-        w[t] = sb ^ 0x8080808080808080ull;
+        w[t] = balanced_bytes(e);
     }
 #pragma unroll
     for (int u = 0; u < 8; u++) {
@@ -346,9 +341,10 @@ static size_t sv_ldeb(size_t npairs) { return (npairs + 255) / 256 * 256; }
 size_t sv_eb_bytes(size_t npairs) { return 48 * sv_ldeb(npairs) + 64; }
 static size_t sv_npad(size_t n) { return (n + 511) / 512 * 512; }
 size_t sv_bits_words(size_t n, uint32_t K, uint32_t rd) { return (size_t)rd * (16 * ((K + 15) / 16) + 1) * (sv_npad(n) / 32); }
-void launch_sv_bits(const int32_t *planes, size_t ldp, size_t n, uint32_t K, uint32_t *bits, hipStream_t s, uint32_t rd) {
+int launch_sv_bits(const int32_t *planes, size_t ldp, size_t n, uint32_t K, uint32_t *bits, hipStream_t s, uint32_t rd) {
     const size_t npad = sv_npad(n);
     hipLaunchKernelGGL(k_sv_bits, dim3((unsigned)cdiv(rd * (npad / 512), 4)), dim3(256), 0, s, planes, ldp, n, npad, 16 * ((K + 15) / 16) + 1, bits, rd);
+    return i8_launched();
 }
 // chunks of super-steps (512 positions): the launches of the pair groups run one after the other, a block fills a CU (registers), so one launch
 // is one batch of at most 256 blocks
@@ -380,7 +376,7 @@ size_t sv_part_words_rd(uint32_t rd, int V, uint32_t K) { return sv_tot_words_rd
 size_t sv_ldeb_pub(size_t npairs) { return (npairs + 255) / 256 * 256; }
 int launch_sv_gemm_tiles(uint32_t rd, int V, const uint32_t *bitsL, const uint32_t *bitsR, size_t nplanes, const unsigned char *EB, size_t ldeb, size_t npairs, uint32_t K,
                          int32_t *part, int32_t *tot, hipStream_t s) {
-    if (!sv_shape_ok(V, npairs, K) || (2 * rd * ((K + 15) / 16)) % (u32)sv_waves(V)) return -1;
+    if (!sv_shape_ok(V, npairs, K) || (2 * rd * ((K + 15) / 16)) % (u32)sv_waves(V)) return I8_ERR_SHAPE;
     const size_t wall = cdiv(nplanes, 2 * (size_t)V), wpairs = wall < npairs ? wall : npairs;
     SvGemmArgs a;
     a.bits[0] = bitsL; a.bits[1] = bitsR;
@@ -402,7 +398,7 @@ int launch_sv_gemm_tiles(uint32_t rd, int V, const uint32_t *bitsL, const uint32
     else launch_gemm_pg<4, 0>(a, grid, s);
     const size_t words = sv_tot_words_rd(rd, V, K);
     hipLaunchKernelGGL(k_sv_sum, dim3((unsigned)cdiv(words / 4, 256)), dim3(256), 0, s, part, words, chunks, tot);
-    return 0;
+    return i8_launched();
 }
 
 int launch_sv_round(const DevCrt &t, int V, const uint32_t *bitsL, const uint32_t *bitsR, size_t nplanes, const uint64_t *eqB, size_t ldeq, size_t pair0, size_t npairs, uint32_t K,
@@ -411,12 +407,12 @@ int launch_sv_round(const DevCrt &t, int V, const uint32_t *bitsL, const uint32_
     // pairs of the slice behind which witness positions exist (positions >= nplanes are zero digits: nothing to add)
     const size_t wall = cdiv(nplanes, 2 * (size_t)V);
     const size_t wpairs = pair0 >= wall ? 0 : (wall - pair0 < npairs ? wall - pair0 : npairs);
-    if (!sv_shape_ok(V, npairs, K) || (pair0 * V) % 256) return -1;
+    if (!sv_shape_ok(V, npairs, K) || (pair0 * V) % 256) return I8_ERR_SHAPE;
     const size_t ldeb = sv_ldeb(npairs);
     const bool split = E != nullptr;
     const u32 NT = split ? 2u : 3u;
     if (split) {   // one value per pair: 24 digit rows + 8 zero rows = two column tiles instead of three
-        (void)hipMemsetAsync(EB + 24 * ldeb, 0, 8 * ldeb, s);
+        I8_HIPCHK(hipMemsetAsync(EB + 24 * ldeb, 0, 8 * ldeb, s));
         hipLaunchKernelGGL(k_sv_pack_eq, dim3((unsigned)cdiv(ldeb / 16 * 3, 256)), dim3(256), 0, s, E + pair0, ldE, npairs, ldeb, V, EB, 1);
     } else
     hipLaunchKernelGGL(k_sv_pack_eq, dim3((unsigned)cdiv(ldeb / 16 * 6, 256)), dim3(256), 0, s, eqB + 2 * pair0, ldeq, npairs, ldeb, V, EB, 0);
@@ -449,9 +445,9 @@ int launch_sv_round(const DevCrt &t, int V, const uint32_t *bitsL, const uint32_
     const Fq3Const wz = {{0, 0, 0}}, w0 = split ? w01[0] : wz, w1 = split ? w01[1] : wz;
     if (t.nu2p40) hipLaunchKernelGGL((k_sv_finish1<true>), dim3(2 * K * 24), dim3(128), 0, s, t, tot, npr, K, a.ktiles, coef, mu_pow, tp, NT, w0, w1);
     else hipLaunchKernelGGL((k_sv_finish1<false>), dim3(2 * K * 24), dim3(128), 0, s, t, tot, npr, K, a.ktiles, coef, mu_pow, tp, NT, w0, w1);
-    if (gpart_ready) (void)hipStreamWaitEvent(s, gpart_ready, 0);   // the G part was computed on another stream
+    if (gpart_ready) I8_HIPCHK(hipStreamWaitEvent(s, gpart_ready, 0));   // the G part was computed on another stream
     hipLaunchKernelGGL(k_sv_finish2, dim3(1), dim3(1024), 0, s, tp, K, gpart, out);
-    return 0;
+    return i8_launched();
 }
 
 // v_s[k][c][q] = sum_i eq[q][i] * digit_k(planes[c][i]) (decomposition.rs:204-211) from the bit-plane form of ONE witness with the round-1
@@ -476,11 +472,11 @@ __global__ void __launch_bounds__(256) k_sv_vs_finish(const int32_t *tot, u32 K,
 size_t sv_vs_part_words(size_t, uint32_t K) { return sv_tot_words(1, K) / 2 * sv_max_chunks(1, K, 1); }
 size_t sv_vs_tot_words(uint32_t K) { return sv_tot_words(1, K) / 2; }
 // bits: launch_sv_bits form of the witness (n positions, n even); eq [3][ldeq]; EB / part / tot: scratch (sv_eb_bytes(n / 2), sv_vs_part_words, sv_vs_tot_words).
-// Returns 0, or -1 if the shape is not handled.
+// Result: lf_i8_launch.h.
 int launch_sv_vs(const uint32_t *bits, size_t n, const uint64_t *eq, size_t ldeq, uint32_t K, unsigned char *EB, int32_t *part, int32_t *tot, uint64_t *out, hipStream_t s) {
     static_assert(sv_pair(1, 0).s == 1 && sv_pair(1, 0).b == 1 && sv_pair(1, 2).s == 2 && sv_pair(1, 2).b == 2, "single pairs of V = 1");
     const size_t npairs = n / 2;
-    if ((n & 1) || !sv_shape_ok(1, npairs, K)) return -1;
+    if ((n & 1) || !sv_shape_ok(1, npairs, K)) return I8_ERR_SHAPE;
     const size_t ldeb = sv_ldeb(npairs);
     hipLaunchKernelGGL(k_sv_pack_eq, dim3((unsigned)cdiv(ldeb / 16 * 6, 256)), dim3(256), 0, s, eq, ldeq, npairs, ldeb, 1, EB, 0);
     SvGemmArgs a;
@@ -501,19 +497,19 @@ int launch_sv_vs(const uint32_t *bits, size_t n, const uint64_t *eq, size_t ldeq
     const size_t words = sv_vs_tot_words(K);
     hipLaunchKernelGGL(k_sv_sum, dim3((unsigned)cdiv(words / 4, 256)), dim3(256), 0, s, part, words, chunks, tot);
     hipLaunchKernelGGL(k_sv_vs_finish, dim3((unsigned)cdiv((size_t)K * 72, 256)), dim3(256), 0, s, tot, K, a.ktiles, out);
-    return 0;
+    return i8_launched();
 }
 // The same evaluation in two steps, so that its pass over the witness can start BEFORE the evaluation point is complete: with the first J coordinates
 // r_1..r_J (low index bits) known, launch_sv_vs_blocks leaves per block b of 2^J positions the partial tiles of  T_b = sum_{i_lo} eq_lo[i_lo] digit_k(f[b 2^J + i_lo])
 // (eq_lo = eq((r_1..r_J), .), [3][ldeq], 2^J entries; one chunk of the GEMM per block, the eqB bytes repeat from block to block); once the other
 // coordinates are known, launch_sv_vs_combine adds  v_s[k][c] = sum_b w_b T_b  with w_b = eq((r_{J+1}..), b) (F_{p^3} weights, [nblocks][3] device words).
-// part: sv_vs_blocks_part_words(nblocks, K) int32 words, nblocks <= sv_vs_max_blocks(K); EB: sv_eb_bytes(2^(J-1)).  Returns 0, or -1 if the shape is not handled.
+// part: sv_vs_blocks_part_words(nblocks, K) int32 words, nblocks <= sv_vs_max_blocks(K); EB: sv_eb_bytes(2^(J-1)).  Result: lf_i8_launch.h.
 size_t sv_vs_max_blocks(uint32_t) { return 256; }
 size_t sv_vs_blocks_part_words(uint32_t nblocks, uint32_t K) { return sv_vs_tot_words(K) * nblocks; }
 int launch_sv_vs_blocks(const uint32_t *bits, size_t n, const uint64_t *eq_lo, size_t ldeq, uint32_t J, uint32_t K, unsigned char *EB, int32_t *part, hipStream_t s) {
-    if (J < 10 || J > 24 || (n & (((size_t)1 << J) - 1)) || n == 0) return -1;
+    if (J < 10 || J > 24 || (n & (((size_t)1 << J) - 1)) || n == 0) return I8_ERR_SHAPE;
     const size_t bs = (size_t)1 << J, nblocks = n / bs, lo_pairs = bs / 2;
-    if (nblocks > sv_vs_max_blocks(K) || !sv_shape_ok(1, n / 2, K)) return -1;
+    if (nblocks > sv_vs_max_blocks(K) || !sv_shape_ok(1, n / 2, K)) return I8_ERR_SHAPE;
     const size_t ldeb = sv_ldeb(lo_pairs);
     hipLaunchKernelGGL(k_sv_pack_eq, dim3((unsigned)cdiv(ldeb / 16 * 6, 256)), dim3(256), 0, s, eq_lo, ldeq, lo_pairs, ldeb, 1, EB, 0);
     SvGemmArgs a;
@@ -530,7 +526,7 @@ int launch_sv_vs_blocks(const uint32_t *bits, size_t n, const uint64_t *eq_lo, s
     a.super_per_chunk = a.eb_mod;
     a.part = part;
     hipLaunchKernelGGL((k_sv_gemm<1, 0, 3, true>), dim3(24 * a.ktiles / (u32)sv_waves(1) * (u32)nblocks), dim3(64 * sv_waves(1)), 0, s, a);
-    return 0;
+    return i8_launched();
 }
 // one wave per output (k, c), lane = block b (the blocks are independent until the weighted sum): out[(k*24 + c)*3 + q]
 template <bool NU>
@@ -564,10 +560,11 @@ __global__ void __launch_bounds__(64) k_sv_vs_combine(DevCrt t, const int32_t *p
         for (int q = 0; q < 3; q++) acc.c[q] = fq_add(acc.c[q], __shfl_down(acc.c[q], off, 64));
     if (lane == 0) { out[(size_t)o * 3] = acc.c[0]; out[(size_t)o * 3 + 1] = acc.c[1]; out[(size_t)o * 3 + 2] = acc.c[2]; }
 }
-void launch_sv_vs_combine(const DevCrt &t, const int32_t *part, uint32_t nblocks, const uint64_t *wts, uint32_t K, uint64_t *out, hipStream_t s) {
+int launch_sv_vs_combine(const DevCrt &t, const int32_t *part, uint32_t nblocks, const uint64_t *wts, uint32_t K, uint64_t *out, hipStream_t s) {
     const u32 ktiles = (K + 15) / 16;
     const size_t words = sv_vs_tot_words(K);
     if (t.nu2p40) hipLaunchKernelGGL((k_sv_vs_combine<true>), dim3(K * 24), dim3(64), 0, s, t, part, nblocks, words, wts, K, ktiles, out);
     else hipLaunchKernelGGL((k_sv_vs_combine<false>), dim3(K * 24), dim3(64), 0, s, t, part, nblocks, words, wts, K, ktiles, out);
+    return i8_launched();
 }
 }  // namespace lf

@@ -23,9 +23,10 @@
 #include "lf_common.h"
 #include "lf_field.cuh"
 #include "lf_kernels.h"
+#include "lf_i8_mma.cuh"
 
 namespace lf {
-typedef int v4i __attribute__((ext_vector_type(4)));
+using namespace i8mma;
 typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr size_t ZK_A_WORDS = 3 * 2 * 64 * 4;   // the A operands [class][tile][lane] x 16 bytes, then the 24 output planes [class][p], then the three biases
@@ -168,10 +169,10 @@ int zk_i8_prepare(const DevCrt &t, u64 B, ZkI8 *zk, hipStream_t s) {
     return 0;
 }
 
-// 0: launched; 1: shape not handled (the caller launches k_recompose_crt_b4); -1: the launch failed
+// Result: lf_i8_launch.h (shape not handled: the caller launches k_recompose_crt_b4)
 int launch_recompose_crt_i8(const ZkI8 &zk, const int32_t *planes, size_t n_planes, u32 wit_len, u32 K, u64 *out, size_t ldz, size_t off, hipStream_t s) {
-    if (zk.state != 1 || !zk.dev || wit_len == 0 || K < 1 || K > 32 || (n_planes & 3) || ((uintptr_t)planes & 15) || ((uintptr_t)out & 7)) return 1;
+    if (zk.state != 1 || !zk.dev || wit_len == 0 || K < 1 || K > 32 || (n_planes & 3) || ((uintptr_t)planes & 15) || ((uintptr_t)out & 7)) return I8_ERR_SHAPE;
     hipLaunchKernelGGL(k_recompose_crt_i8, dim3((wit_len + 127) / 128, 3), dim3(256), 0, s, (const int *)zk.dev, planes, n_planes, wit_len, K, out, ldz, off);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return i8_launched();
 }
 }  // namespace lf

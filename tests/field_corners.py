@@ -803,7 +803,7 @@ def count_classes_hl(sums, nu=2):
 
 
 def digits_bb(w):
-    """the four balanced base-256 digits of a device word (bb_dot_i8.hip: bbd_digits) and, per digit, whether balancing it carried into the next"""
+    """the four balanced base-256 digits of a device word (lf_i8_mma.cuh: balanced_bytes) and, per digit, whether balancing it carried into the next"""
     d, carry = [], []
     for _ in range(4):
         byte = w % 256
@@ -826,7 +826,7 @@ def count_classes_dig(values):
 
 
 def bbdot_guard(n):
-    """the exactness guard of launch_dot_batch_i8 restated (bb_dot_i8.hip: bbdot_chunks and `steps_per_chunk >= 2048 -> -1`): a wave adds steps_per_chunk * 64
+    """the exactness guard of launch_dot_batch_i8 restated (lf_dot_i8.cuh: DotPlan::make with the 12 chunks of bb_dot_i8.hip refuses `steps_per_chunk >= 2048`): a wave adds steps_per_chunk * 64
     digit products of at most 2^14 into one int32"""
     cd = lambda a, b: (a + b - 1) // b
     nsteps = cd(n, 64)
@@ -1023,7 +1023,7 @@ def dot_y_words(n):
 
 def dot_case_bb(name, l):
     """a workload whose matrices have row DOT_I0 dense over all n columns with dot_y_words, and the 0 / 1 point r of that row: eq(r) is the row's indicator, so
-    M_j^T eq(r) -- the Y operand of k_bbdot_pack_y / k_bbdot_i8 -- is that row"""
+    M_j^T eq(r) -- the Y operand of k_dot_pack_y / k_bbdot_i8 -- is that row"""
     wl = make_workload(name, l=l)
     for j in range(wl.t):
         rp, col, val = (np.asarray(a) for a in (wl.rowptr[j], wl.col[j], wl.val[j]))

@@ -259,7 +259,7 @@ def test_crt_reference_and_coverage():
 # ---- the int8 paths ------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,l", fc.DOT_SHAPES_BB)
 def test_int8_inner_product_operands(name, l):
-    """the Y operand of k_bbdot_pack_y / k_bbdot_i8 in the decomposition of fc.dot_case_bb is row DOT_I0 of each matrix: with eq(r) the indicator of that row the
+    """the Y operand of k_dot_pack_y / k_bbdot_i8 in the decomposition of fc.dot_case_bb is row DOT_I0 of each matrix: with eq(r) the indicator of that row the
     oracle's u_s equal the big-integer inner products <z_k, row>, and the row's words carry a -128 and a 127 at every digit position, with carries"""
     from latticefold_amd.workload import make_workload
     wl, r = fc.dot_case_bb(name, l)
@@ -296,13 +296,17 @@ def _lcccs(wl, inst, cm, f, r):
 
 def test_int8_accumulator_guard_arithmetic():
     """launch_dot_batch_i8 refuses a shape whose waves would add 2048 or more steps of 64 digit products (each at most 2^14) into one int32: 2047 * 64 * 2^14 <
-    2^31 <= 2048 * 64 * 2^14.  The guard's formula, restated from bbdot_chunks, flips between 12 * 2047 and 12 * 2047 + 1 steps"""
+    2^31 <= 2048 * 64 * 2^14.  The guard's formula, restated from DotPlan::make (lf_dot_i8.cuh) with BabyBear's 12 chunks, flips between 12 * 2047 and
+    12 * 2047 + 1 steps"""
     assert 2047 * 64 * 2**14 < 2**31 <= 2048 * 64 * 2**14
     edge = 12 * 2047 * 64
     assert fc.bbdot_guard(edge) == 0 and fc.bbdot_guard(edge - 63) == 0 and fc.bbdot_guard(edge + 1) == -1 and fc.bbdot_guard(64) == 0 and fc.bbdot_guard(4096) == 0
     with open(os.path.join(CSRC, "bb_dot_i8.hip")) as fh:
         src = fh.read()
-    assert "bbdot_chunks(ldq / 64)) >= 2048) return -1;" in src and "size_t want = 12;" in src
+    with open(os.path.join(CSRC, "lf_dot_i8.cuh")) as fh:
+        plan = fh.read()
+    assert "return steps_per_chunk < 2048;" in plan and "constexpr u32 BBDOT_CHUNKS = 12;" in src
+    assert src.count("!p.make(X, n, BBDOT_CHUNKS)) return I8_ERR_SHAPE;") == 2     # both launchers refuse through the plan
 
 
 def test_coef_eval_eq_words():

@@ -174,7 +174,7 @@ def _decomposition(wl, r, monkeypatch, envs):
 
 @pytest.mark.parametrize("name,l", fc.DOT_SHAPES_BB)
 def test_int8_inner_products_on_digit_boundary_words(name, l, monkeypatch):
-    """k_bbdot_pack_y / k_bbdot_i8: r is a 0 / 1 point, so M_j^T eq(r) -- the Y operand -- is the dense row of fc.dot_case_bb: words with -128 and 127 at every
+    """k_dot_pack_y / k_bbdot_i8: r is a 0 / 1 point, so M_j^T eq(r) -- the Y operand -- is the dense row of fc.dot_case_bb: words with -128 and 127 at every
     digit position, +-H, runs of -0x3B808080; 192 columns (three steps of 64) and 130 (a partial last step).  Once on the matrix cores (LF_DOT_MIN lowers the
     driver's threshold of 4096 columns, as in test_fold_step_int8_inner_products_match_oracle) and once on the VALU kernel"""
     wl, r = fc.dot_case_bb(name, l)
