@@ -9,6 +9,7 @@
 //! | `PlusParameters` `plus.rs:42-47`                        | [`PlusParameters`] (`sys::lfplus_params`)      |
 //! | `PoseidonTranscript<RqPoly>` `transcript.rs:20-78`      | [`HipPlusTranscript`]                          |
 //! | `MLSumcheck::{prove, verify}_as_subprotocol` `latticefold/src/utils/sumcheck.rs:53-104` | [`HipPlusMLSumcheck`] over a [`HipPlusVPoly`] |
+//! | `RqPoly` products and `SparseMatrix` x vector on arrays (the `g_q = M_q f`, `g_A o g_B - g_C` of `r1cs.rs:76-95`) | [`HipPlusContext::ring_mul`], [`HipPlusContext::spmv`] and their `_device` forms |
 //!
 //! The ring is the one the reference runs latticefold-plus on (FrogRing `RqPoly`, coefficient form, 16 canonical words per element); `R: RingWords` with
 //! `WORDS == 16` marshals it.  The schedule of a prove -- which context holds which accumulator half, the upload thread, the refusal to continue after a
@@ -321,6 +322,44 @@ impl HipPlusContext {
             "lfplus_decompose_dev",
         )?;
         Ok([c0, c1, v0, v1])
+    }
+    /// `lfplus_ring_mul`: out[x] = sum_i a_i[x] * b_i[x] over `n_terms` tables of `count` ring elements (16 canonical words each; table i of `a` at
+    /// `i * count * 16`).  `broadcast`: `b` holds one ring element per term instead of a table
+    pub fn ring_mul(&mut self, a: &[u64], b: &[u64], n_terms: usize, count: usize, broadcast: bool) -> Result<Vec<u64>, HipPlusError> {
+        if n_terms == 0 || count == 0 || a.len() != n_terms * count * 16 || b.len() != if broadcast { n_terms * 16 } else { a.len() } {
+            return Err(HipPlusError::new(sys::LFPLUS_E_ARG, "ring_mul", "a: n_terms x count x 16 words; b: the same, or n_terms x 16 words with broadcast"));
+        }
+        let mode = if broadcast { sys::LFPLUS_MUL_BROADCAST } else { sys::LFPLUS_MUL_ELEMENTWISE };
+        let mut out = vec![0u64; count * 16];
+        // SAFETY: live handle; the arrays have the sizes checked above
+        self.chk(unsafe { sys::lfplus_ring_mul(self.raw, a.as_ptr(), b.as_ptr(), n_terms as u64, count as u64, mode as i32, out.as_mut_ptr()) }, "lfplus_ring_mul")?;
+        Ok(out)
+    }
+    /// `lfplus_ring_mul_device`: the same on the caller's device arrays, in place; `b` is a HOST pointer with `broadcast`
+    /// # Safety
+    /// `a` (and `b` without `broadcast`): n_terms x count x 16 words, `out`: count x 16 words of 16-byte aligned device memory of the context's device; `b` with
+    /// `broadcast`: n_terms x 16 words of host memory; `out` overlaps an input only as lfplus.h allows
+    pub unsafe fn ring_mul_device(&mut self, a: *const u64, b: *const u64, n_terms: usize, count: usize, broadcast: bool, out: *mut u64) -> Result<(), HipPlusError> {
+        let mode = if broadcast { sys::LFPLUS_MUL_BROADCAST } else { sys::LFPLUS_MUL_ELEMENTWISE };
+        // SAFETY: the caller's contract
+        self.chk(unsafe { sys::lfplus_ring_mul_device(self.raw, a, b, n_terms as u64, count as u64, mode as i32, out) }, "lfplus_ring_mul_device")
+    }
+    /// `lfplus_spmv`: M_j x for the j-th resident constraint matrix; `x` = n ring elements
+    pub fn spmv(&mut self, j: usize, x: &[u64]) -> Result<Vec<u64>, HipPlusError> {
+        if x.is_empty() || x.len() % 16 != 0 {
+            return Err(HipPlusError::new(sys::LFPLUS_E_ARG, "spmv", "x: n x 16 words"));
+        }
+        let mut y = vec![0u64; x.len()];
+        // SAFETY: live handle; y has the size of x
+        self.chk(unsafe { sys::lfplus_spmv(self.raw, j as u32, x.as_ptr(), (x.len() / 16) as u64, y.as_mut_ptr()) }, "lfplus_spmv")?;
+        Ok(y)
+    }
+    /// `lfplus_spmv_device`
+    /// # Safety
+    /// `x`, `y`: n x 16 words of 16-byte aligned device memory of the context's device each, not overlapping
+    pub unsafe fn spmv_device(&mut self, j: usize, x: *const u64, n: usize, y: *mut u64) -> Result<(), HipPlusError> {
+        // SAFETY: the caller's contract
+        self.chk(unsafe { sys::lfplus_spmv_device(self.raw, j as u32, x, n as u64, y) }, "lfplus_spmv_device")
     }
     /// `lfplus_ctx_create` alone: a BARE context (no matrix, no witness) -- all the generic sumcheck needs
     pub fn bare(device: i32) -> Result<Self, HipPlusError> {

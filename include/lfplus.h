@@ -16,7 +16,8 @@
  *   In::set_check / Out::verify                      src/setchk.rs:65-262 / 266-340
  *   Rg::range_check / Dcom::verify                   src/rgchk.rs:81-186 / 193-258
  *   PlusProver::{init, prove} / PlusVerifier::{init, verify}   src/plus.rs:15-146   (lfplus_prover_*, lfplus_verify: the objects, below)
- *   MLSumcheck::{prove, verify}_as_subprotocol over any product list   latticefold/src/utils/sumcheck.rs:53-104   (lfplus_mlsumcheck_*, at the end of this file)
+ *   MLSumcheck::{prove, verify}_as_subprotocol over any product list   latticefold/src/utils/sumcheck.rs:53-104   (lfplus_mlsumcheck_*, near the end of this file)
+ *   RqPoly products and SparseMatrix x vector on arrays (the g_q = M_q f and g_A o g_B - g_C of r1cs.rs:76-95 as calls of their own)   (lfplus_ring_mul, lfplus_spmv, at the end of this file)
  *
  * M_f and m_tau are matrices / vectors of unit monomials; they cross this boundary as their EXPONENT digits (int8 in (-d/2, d/2)):
  * exp(a) = X^a for a >= 0 and X^(d + a) for a < 0.  The Rust binding rebuilds Matrix<R> from them if a caller needs the dense form
@@ -431,6 +432,35 @@ int lfplus_mlsumcheck_prove_device(lfplus_ctx *ctx, lfplus_transcript *t, const 
  * LFPLUS_E_ARG, the transcript untouched */
 int lfplus_mlsumcheck_verify(lfplus_transcript *t, uint32_t nvars, uint32_t degree, const uint64_t *claimed_sum, const uint64_t *msgs, uint64_t *point_out,
                              uint64_t *expected_out, int *round);
+
+/* ---- ring arithmetic on arrays: the negacyclic product and the resident matrices as calls of their own (the counterparts of lf_ring_mul / lf_spmv on the Frog
+ * ring; the oracle's lfp_ring_mul).  With lfplus_tensor and lfplus_mlsumcheck_prove_device they take a constraint shape the slice does not hard-wire from the
+ * witness to the proof on the device: g_q = lfplus_spmv_device(q, f), products and residuals of those tables with lfplus_ring_mul_device, linear combinations
+ * sum_l s_l f_l with ring (short-challenge) coefficients in the broadcast mode.
+ *   Layout as everywhere in this header: coefficient form, 16 canonical little-endian words per element, AoS.  Envelope: 1 <= n_terms <= 64, 1 <= count <= 2^28,
+ * mode 0 or 1.  The device forms (spelled _device, as lfplus_mlsumcheck_begin_device is) take a, out, x, y -- and b in mode 0 -- as memory of the context's device
+ * under every rule of the "device-resident callers" section above (unmanaged memory of the context's device, ONE allocation covering every byte, 16-byte
+ * alignment, ordering by lfplus_ctx_wait_stream, return after the context's stream is synchronised); b of mode 1 is small and stays a HOST pointer.
+ *   Independence, as lfplus_mlsumcheck_*: the calls run on a bare context (lfplus_ring_mul needs no matrix and no witness) and on a loaded one neither read nor
+ * write the resident witness, the lfplus_rg_from_f results, a pending lfplus_rg_from_f_async pass or an active generic sumcheck.  Inputs are never written.
+ *   Aliasing: a and b may alias each other (a square).  out may be EXACTLY a (or exactly b in mode 0) when n_terms == 1; any other overlap of out with an input
+ * range is refused with nothing launched, in both memory spaces.  y overlapping x in any way is refused: the product gathers.
+ *   Refusals, every one LFPLUS_E_ARG with a message in lfplus_last_error, in this order: a NULL context (tested before any device is touched: the answer on a
+ * machine without a GPU as well); a NULL array; n_terms, count or mode outside the envelope; [lfplus_spmv: no resident matrices, j >= their number, n != the
+ * resident n;] a sharded context (a transport or lfplus_set_sharding_model); the overlap rules; [_device: the pointer checks;] in mode 1 a word >= p in b (tested
+ * on the host); a word >= p in an O(n) input.  The O(n) words are tested on the device by the kernel that reads them and the flag comes home before the call
+ * returns: a host out / y is downloaded only when it is down and stays untouched otherwise, a device out / y is undefined then (as that section says for a
+ * non-canonical word).  After any refusal the context is usable and nothing resident has changed.
+ *   Not built: sharded contexts; an NTT form of the Frog ring (its slot conventions are unpinned and it has no oracle); an int8 matrix-core form of the product. */
+#define LFPLUS_MUL_ELEMENTWISE 0   /* b: n_terms x count ring elements */
+#define LFPLUS_MUL_BROADCAST   1   /* b: n_terms ring elements, one per term */
+/* mode 0: out[x] = sum_{i<n_terms} a_i[x] * b_i[x]; mode 1: out[x] = sum_i a_i[x] * b_i; x < count,
+ * negacyclic products in Z_p[X]/(X^16+1); table i of a at a + i*count*16 words */
+int lfplus_ring_mul(lfplus_ctx *ctx, const uint64_t *a, const uint64_t *b, uint64_t n_terms, uint64_t count, int mode, uint64_t *out);
+int lfplus_ring_mul_device(lfplus_ctx *ctx, const uint64_t *a, const uint64_t *b, uint64_t n_terms, uint64_t count, int mode, uint64_t *out);
+/* y = M_j x, M_j the j-th matrix of lfplus_set_matrices / lfplus_share_matrices (n x n), x and y n ring elements */
+int lfplus_spmv(lfplus_ctx *ctx, uint32_t j, const uint64_t *x, uint64_t n, uint64_t *y);
+int lfplus_spmv_device(lfplus_ctx *ctx, uint32_t j, const uint64_t *x, uint64_t n, uint64_t *y);
 
 #ifdef __cplusplus
 }

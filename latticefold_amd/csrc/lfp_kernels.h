@@ -138,6 +138,12 @@ void launch_mls_round(const u64 *in, size_t ld_in, size_t half, const MlsDesc &d
 void launch_mls_round_fused(const u64 *in, size_t ld_in, size_t half, const MlsDesc &d, const u64 *coef, u64 rM, u64 *out, size_t ld_out, u32 blocks, u64 *part, hipStream_t s);
 // out[t][16] = in[t][0] + r (in[t][1] - in[t][0]) for t < nt: the last variable of every table
 void launch_mls_final(const u64 *in, size_t ld_in, u32 nt, u64 rM, u64 *out, hipStream_t s);
+// ---- ring arithmetic on arrays (lfp_ring_ops.hip; lfplus_ring_mul): out[x] = sum_{i < n_terms} a_i[x] * b_i[x] for x < count, table i of a at a + i count 16.
+// mode 0: b is n_terms x count canonical ring elements; mode 1: b is n_terms x 16 MONTGOMERY words (device), one coefficient per term.  n_terms <= 64.  a, out
+// (and b in mode 0) are 16-byte aligned; out may be exactly a (or b in mode 0) when n_terms == 1 and overlaps nothing otherwise.  *flag |= 1 if a word of a
+// (of b in mode 0) is not canonical.  blocks = ring_mul_blocks(count, cap): one workgroup per 16 elements, at most cap
+u32 ring_mul_blocks(u64 count, u32 cap);
+void launch_ring_mul(const u64 *a, const u64 *b, u32 n_terms, u64 count, int mode, u64 *out, u32 *flag, u32 blocks, hipStream_t s);
 // ---- relation checks (lfp_check.hip): R_ComR1CS (r1cs.rs:21-60), R_LinB (lin.rs:29-40)
 // *first_bad = min(*first_bad, smallest row r < nrows with ((M_0 f) (M_1 f) - M_2 f)[r] != 0); vals[q]: LfpMatrix::spmv_vals() of matrix q (const_coef[q] as there)
 void launch_r1cs_residual(const u32 *const *rowptr, const u32 *const *col, const u64 *const *vals, const int *const_coef, const u64 *f, size_t nrows, u64 *first_bad,

@@ -29,6 +29,7 @@ class LfPlusError(RuntimeError):
 E_ARG, E_NO_DEVICE, E_HIP, E_EXP_DOMAIN, E_SMALL_N, E_REJECT = -1, -2, -3, -4, -5, -6
 REL_CM, REL_R1CS, REL_V, REL_NORM = 1, 2, 4, 8      # lfplus.h LFPLUS_REL_*: the components of a relation check (lfplus_r1cs_check / lfplus_linb_check)
 ABSENT = -128     # exponent digit of a zero entry of a monomial set (lfplus.h LFPLUS_ABSENT)
+MUL_ELEMENTWISE, MUL_BROADCAST = 0, 1      # lfplus.h LFPLUS_MUL_*: the modes of lfplus_ring_mul
 
 
 class VPolyDesc(C.Structure):
@@ -125,6 +126,12 @@ def _lib():
         L.lfplus_mlsumcheck_prove.argtypes = [vp, vp, dp, u64p, u64p, u64p, u64p]
         L.lfplus_mlsumcheck_prove_device.argtypes = [vp, vp, dp, vp, u64p, u64p, u64p]
         L.lfplus_mlsumcheck_verify.argtypes = [vp, C.c_uint32, C.c_uint32, u64p, u64p, u64p, u64p, ip]
+        # ring arithmetic on arrays (the _device forms: a, out, x, y -- and b of mode 0 -- are device addresses; b of mode 1 stays a host pointer, so it is
+        # passed as an address in both modes)
+        L.lfplus_ring_mul.argtypes = [vp, u64p, u64p, C.c_uint64, C.c_uint64, C.c_int, u64p]
+        L.lfplus_ring_mul_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp]
+        L.lfplus_spmv.argtypes = [vp, C.c_uint32, u64p, C.c_uint64, u64p]
+        L.lfplus_spmv_device.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp]
         _READY = True
     return L
 
@@ -346,6 +353,70 @@ class PlusContext:
             return out
         out = np.zeros((self.n, D), dtype=np.uint64)
         self._chk(_lib().lfplus_get_witness(self.h, out.ctypes.data_as(u64p), self.n))
+        return out
+
+    def ring_mul(self, a, b, broadcast=False, out=None):
+        """lfplus_ring_mul: out[x] = sum_i a_i[x] * b_i[x] (negacyclic products).  a: (count, 16) or (n_terms, count, 16); b: the shape of a, or with
+        broadcast=True one coefficient per term, (16,) or (n_terms, 16), always a host array.  a, b and out are numpy arrays, or device arrays
+        (lfplus_ring_mul_device: read and written in place).  out (count, 16): default a new array; it may be a (or b, element-wise) when n_terms == 1"""
+        dev = api.is_device_array(a)
+        sh = tuple(a.shape)
+        if len(sh) not in (2, 3) or sh[-1] != D:
+            raise LfPlusError(E_ARG, "ring_mul: a is (count, 16) or (n_terms, count, 16)")
+        n_terms, count = (1, sh[0]) if len(sh) == 2 else (sh[0], sh[1])
+        if broadcast:
+            if api.is_device_array(b):
+                raise LfPlusError(E_ARG, "ring_mul: the coefficients of a broadcast are a host array")
+            bk = np.ascontiguousarray(b, dtype=np.uint64)
+            if bk.size != n_terms * D:
+                raise LfPlusError(E_ARG, "ring_mul: b is one ring element per term")
+        elif api.is_device_array(b) != dev or tuple(b.shape) != sh:
+            raise LfPlusError(E_ARG, "ring_mul: b has the shape and the memory space of a")
+        if out is not None and (api.is_device_array(out) != dev or tuple(out.shape) != (count, D)):
+            raise LfPlusError(E_ARG, "ring_mul: out is (count, 16) in the memory space of a")
+        mode = MUL_BROADCAST if broadcast else MUL_ELEMENTWISE
+        if dev:
+            if out is None:
+                out = a.new_empty((count, D))
+            for t in (a, out) if broadcast else (a, b, out):
+                if not t.is_contiguous() or t.element_size() != 8:
+                    raise LfPlusError(E_ARG, "device arrays must be contiguous with 8-byte elements")
+            self.wait_stream()
+            pb = C.c_void_p(bk.ctypes.data) if broadcast else C.c_void_p(b.data_ptr())
+            self._chk(_lib().lfplus_ring_mul_device(self.h, C.c_void_p(a.data_ptr()), pb, n_terms, count, mode, C.c_void_p(out.data_ptr())))
+            return out
+        square = b is a
+        a, pa = _w(a)
+        bk, pb = (bk, bk.ctypes.data_as(u64p)) if broadcast else ((a, pa) if square else _w(b))
+        if out is None:
+            out = np.zeros((count, D), dtype=np.uint64)
+        elif out.dtype != np.uint64 or not out.flags["C_CONTIGUOUS"]:
+            raise LfPlusError(E_ARG, "ring_mul: out is a contiguous uint64 array")
+        self._chk(_lib().lfplus_ring_mul(self.h, pa, pb, n_terms, count, mode, out.ctypes.data_as(u64p)))
+        return out
+
+    def spmv(self, j, x, out=None):
+        """lfplus_spmv: M_j x for the j-th resident matrix (set_matrices / share_matrices); x (n, 16), a numpy array or a device array
+        (lfplus_spmv_device) -> out (n, 16) in the memory space of x"""
+        if len(tuple(x.shape)) != 2 or x.shape[1] != D:
+            raise LfPlusError(E_ARG, "spmv: x is (n, 16)")
+        n = x.shape[0]
+        dev = api.is_device_array(x)
+        if out is not None and (api.is_device_array(out) != dev or tuple(out.shape) != (n, D)):
+            raise LfPlusError(E_ARG, "spmv: out is (n, 16) in the memory space of x")
+        if dev:
+            if out is None:
+                out = x.new_empty((n, D))
+            px, po = _dev(x), _dev(out)
+            self.wait_stream()
+            self._chk(_lib().lfplus_spmv_device(self.h, int(j), px, n, po))
+            return out
+        x, px = _w(x)
+        if out is None:
+            out = np.zeros((n, D), dtype=np.uint64)
+        elif out.dtype != np.uint64 or not out.flags["C_CONTIGUOUS"]:
+            raise LfPlusError(E_ARG, "spmv: out is a contiguous uint64 array")
+        self._chk(_lib().lfplus_spmv(self.h, int(j), px, n, out.ctypes.data_as(u64p)))
         return out
 
     def _cm_arg(self, cm_f):
