@@ -94,12 +94,13 @@ __global__ void __launch_bounds__(256) k_sv_pack_eq(const u64 *eq, size_t ld, si
     }
 }
 
-// x * 255 for x with one bit per byte, as shift + subtract (the compiler would turn (x << 8) - x into a quarter-rate 32-bit multiply)
-__device__ __forceinline__ u32 sv_full(u32 x) {
-    u32 t, r;
-    asm("v_lshlrev_b32 %0, 8, %1" : "=v"(t) : "v"(x));
-    asm("v_sub_u32 %0, %1, %2" : "=v"(r) : "v"(t), "v"(x));
-    return r;
+// bit -> byte expansion of a word with one bit per byte, one packed 16-bit instruction each (full rate; a 32-bit multiply is quarter rate, and
+// shift + subtract are two instructions):  sv_full  0x01 -> 0xFF (x * 255: a half word is at most 0x0101 * 255 = 0xFFFF),
+// sv_sign  0x00 -> 0x01, 0x01 -> 0xFF (x * 254 + 0x0101): the sign byte with its low bit set, +1 / -1 as int8
+typedef unsigned short sv_us2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ u32 sv_full(u32 x) { return __builtin_bit_cast(u32, (sv_us2)(__builtin_bit_cast(sv_us2, x) * (sv_us2){255, 255})); }
+__device__ __forceinline__ u32 sv_sign(u32 x) {
+    return __builtin_bit_cast(u32, (sv_us2)(__builtin_bit_cast(sv_us2, x) * (sv_us2){254, 254} + (sv_us2){0x0101, 0x0101}));
 }
 struct SvGemmArgs {
     const u32 *bits[2];         // k_sv_bits form of the two witnesses
@@ -116,7 +117,8 @@ struct SvGemmArgs {
     int32_t *part;              // [chunk][group][pair][3][64][4]
 };
 
-// operand register j of pair IDX:  +-1 where every bit of beta is set, sign = product of the signs of sigma
+// operand register j of pair IDX:  +-1 where every bit of beta is set, sign = product of the signs of sigma.
+// S holds the sign bytes WITH their low bit (sv_sign: 0x01 / 0xFF), formed once per digit; the XOR of three of them keeps that bit
 template <int V, int IDX>
 __device__ __forceinline__ u32 sv_operand(const u32 (&Xf)[2 * V][4], const u32 (&S)[2 * V][4], const u32 (&D)[2 * V][4], int j) {
     constexpr SvPair pr = sv_pair(V, IDX);
@@ -128,7 +130,7 @@ __device__ __forceinline__ u32 sv_operand(const u32 (&Xf)[2 * V][4], const u32 (
         return Xf[q][j] & D[z][j];
     } else {
         constexpr int x = ctz8(pr.b), y = ctz8(pr.b & ~(1u << x)), z = ctz8(pr.b & ~(1u << x) & ~(1u << y));
-        return (Xf[x][j] & Xf[y][j] & Xf[z][j]) & ((S[x][j] ^ S[y][j] ^ S[z][j]) | ONES4);
+        return (Xf[x][j] & Xf[y][j] & Xf[z][j]) & (S[x][j] ^ S[y][j] ^ S[z][j]);
     }
 }
 // VS (launch_sv_vs*: V = 1, NT = 3): only the two single pairs are read afterwards, pair 0 against the digits of eq(2p) (columns 0..23: tiles 0, 1) and pair 2
@@ -193,36 +195,45 @@ __global__ void __launch_bounds__(64 * sv_waves(V)) __attribute__((amdgpu_waves_
         }
     };
     if (u0 < u1) { stage_load(u0); stage_store(0); }
-    uint4 wm4 = make_uint4(0, 0, 0, 0), ws4 = wm4;
     mrow += (size_t)a.super0 * 16; srow += (size_t)a.super0 * 16;
-    if (u0 < u1) { wm4 = *(const uint4 *)(mrow + ((size_t)u0 * 4 + g) * 4); ws4 = *(const uint4 *)(srow + ((size_t)u0 * 4 + g) * 4); }
+    // the signed bits of sub-step ss of a super-step (words wm: magnitude bits, ws: sign bits), one register per bit x and operand register j:
+    // Xf 0x00 / 0xFF (bit set), S 0x01 / 0xFF (sign, low bit kept), D = Xf & S the digit itself as int8
+    auto expand = [&](const uint4 &wm4, const uint4 &ws4, int ss, u32 (&Xf)[NX][4], u32 (&S)[NX][4], u32 (&D)[NX][4]) {
+        const u32 wm[4] = {wm4.x, wm4.y, wm4.z, wm4.w}, wsg[4] = {ws4.x, ws4.y, ws4.z, ws4.w};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const u32 wmj = wm[ss * V + j / RPW], wsj = wsg[ss * V + j / RPW];
+#pragma unroll
+            for (int x = 0; x < NX; x++) {
+                const int sh = NX * (j % RPW) + x;
+                Xf[x][j] = sv_full((wmj >> sh) & ONES4);
+                S[x][j] = sv_sign((wsj >> sh) & ONES4);
+                D[x][j] = Xf[x][j] & S[x][j];
+            }
+        }
+    };
+    auto load_b = [&](u32 buf, int ss, v4i (&b)[NT]) {
+        const unsigned char *lb = &lds[buf][row][g * (64 / V) + 16 * ss];
+#pragma unroll
+        for (int nt = 0; nt < NT; nt++) b[nt] = *(const v4i *)(lb + 16 * nt * LROW);
+    };
+    auto words = [&](const u32 *r, u32 u) { return *(const uint4 *)(r + ((size_t)u * 4 + g) * 4); };
+    uint4 wm4 = make_uint4(0, 0, 0, 0), ws4 = wm4;
+    if (u0 < u1) { wm4 = words(mrow, u0); ws4 = words(srow, u0); }
     __syncthreads();
     for (u32 u = u0; u < u1; u++) {
         const u32 buf = (u - u0) & 1;
-        const u32 wm[4] = {wm4.x, wm4.y, wm4.z, wm4.w}, wsg[4] = {ws4.x, ws4.y, ws4.z, ws4.w};
+        const uint4 wmc = wm4, wsc = ws4;
         const u32 un = u + 1 < u1 ? u + 1 : u;
         stage_load(un);                                  // in flight while this super-step is computed
-        wm4 = *(const uint4 *)(mrow + ((size_t)un * 4 + g) * 4);
-        ws4 = *(const uint4 *)(srow + ((size_t)un * 4 + g) * 4);
+        wm4 = words(mrow, un);
+        ws4 = words(srow, un);
 #pragma unroll
         for (int ss = 0; ss < SS; ss++) {
             v4i b[NT];
-            const unsigned char *lb = &lds[buf][row][g * (64 / V) + 16 * ss];
-#pragma unroll
-            for (int nt = 0; nt < NT; nt++) b[nt] = *(const v4i *)(lb + 16 * nt * LROW);
+            load_b(buf, ss, b);
             u32 Xf[NX][4], S[NX][4], D[NX][4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const u32 wmj = wm[ss * V + j / RPW], wsj = wsg[ss * V + j / RPW];
-#pragma unroll
-                for (int x = 0; x < NX; x++) {
-                    const int sh = NX * (j % RPW) + x;
-                    const u32 x1 = (wmj >> sh) & ONES4, s1 = (wsj >> sh) & ONES4;
-                    Xf[x][j] = sv_full(x1);   // 0x01 -> 0xFF per byte
-                    S[x][j] = sv_full(s1);
-                    D[x][j] = Xf[x][j] & (S[x][j] | ONES4);
-                }
-            }
+            expand(wmc, wsc, ss, Xf, S, D);
             sv_mfma_all<V, PG * PW, NT, VS>(acc, b, Xf, S, D, std::make_integer_sequence<int, PW>{});
         }
         stage_store(buf ^ 1);
