@@ -9,6 +9,7 @@
 //! | `PlusParameters` `plus.rs:42-47`                        | [`PlusParameters`] (`sys::lfplus_params`)      |
 //! | `PoseidonTranscript<RqPoly>` `transcript.rs:20-78`      | [`HipPlusTranscript`]                          |
 //! | `MLSumcheck::{prove, verify}_as_subprotocol` `latticefold/src/utils/sumcheck.rs:53-104` | [`HipPlusMLSumcheck`] over a [`HipPlusVPoly`] |
+//! | (none: "Support CCS" is the reference README's next step) committed CCS instances, `ComR1CS::linearize` / `ComR1CSProof::verify` `r1cs.rs:72-163` generalised | [`HipComCCS`] over a [`HipPlusCCS`]: `linearize`, `verify`, `check_relation` |
 //! | `RqPoly` products and `SparseMatrix` x vector on arrays (the `g_q = M_q f`, `g_A o g_B - g_C` of `r1cs.rs:76-95`) | [`HipPlusContext::ring_mul`], [`HipPlusContext::spmv`] and their `_device` forms |
 //!
 //! The ring is the one the reference runs latticefold-plus on (FrogRing `RqPoly`, coefficient form, 16 canonical words per element); `R: RingWords` with
@@ -426,6 +427,99 @@ impl HipPlusMLSumcheck {
             return Err(HipPlusError::new(rc, "lfplus_mlsumcheck_verify", if rc == sys::LFPLUS_E_REJECT { format!("round {round}") } else { "bad arguments".into() }));
         }
         Ok((point, expected))
+    }
+}
+/// A CCS shape over `t` resident constraint matrices (`lfplus_ccs`): sum_i coef_i prod_{j in multisets[i]} (M_j f) = 0 row by row; `coef` is one ring element
+/// (16 canonical words) per multiset.  Envelope (refused by the library with `LFPLUS_E_ARG`): 1 <= t, q <= 8, 1 <= |S_i| <= 7, at most 16 indices in all.
+#[derive(Debug, Clone)]
+pub struct HipPlusCCS {
+    pub t: usize,
+    pub terms: Vec<([u64; 16], Vec<u32>)>,
+}
+
+impl HipPlusCCS {
+    /// (M_0 f) o (M_1 f) - M_2 f: the shape `lfplus_r1cs_linearize` hard-wires (word-identical proofs)
+    pub fn r1cs() -> Self {
+        let (mut one, mut minus) = ([0u64; 16], [0u64; 16]);
+        one[0] = 1;
+        minus[0] = sys::LFPLUS_P - 1;
+        HipPlusCCS { t: 3, terms: vec![(one, vec![0, 1]), (minus, vec![2])] }
+    }
+    /// d = max |S_i|: the sumcheck runs at degree d + 1
+    pub fn degree(&self) -> usize {
+        self.terms.iter().map(|(_, s)| s.len()).max().unwrap_or(0)
+    }
+    fn flat(&self) -> (Vec<u32>, Vec<u32>, Vec<u64>) {
+        let (mut off, mut idx, mut coef) = (vec![0u32], Vec::new(), Vec::new());
+        for (c, s) in &self.terms {
+            idx.extend_from_slice(s);
+            off.push(idx.len() as u32);
+            coef.extend_from_slice(c);
+        }
+        idx.push(0);
+        (off, idx, coef)
+    }
+}
+
+/// The linearization of a committed CCS instance (`lfplus_ccs_*`; self-consistent, pinned to the reference at the R1CS shape), on a context whose resident
+/// witness is the instance's `f` and whose resident matrices (`lfplus_set_matrices`) are the shape's `t`
+pub struct HipComCCS;
+
+impl HipComCCS {
+    /// `lfplus_ccs_linearize` -> (msgs: nvars x (d + 2) x 16 words, ro: nvars words, evals: (1 + t) x 16 words); `nvars` = log2 of the resident witness's length
+    pub fn linearize(ctx: &mut HipPlusContext, transcript: &mut HipPlusTranscript, shape: &HipPlusCCS, nvars: usize) -> Result<(Vec<u64>, Vec<u64>, Vec<u64>), HipPlusError> {
+        let (off, idx, coef) = shape.flat();
+        let d = sys::lfplus_ccs { t: shape.t as u32, q: shape.terms.len() as u32, S_off: off.as_ptr(), S_idx: idx.as_ptr(), c: coef.as_ptr() };
+        let mut msgs = vec![0u64; nvars * (shape.degree() + 2) * 16];
+        let (mut ro, mut evals) = (vec![0u64; nvars.max(1)], vec![0u64; (1 + shape.t) * 16]);
+        // SAFETY: live handles; d points into off / idx / coef, which outlive the call; the outputs have the sizes lfplus.h documents for a witness of 2^nvars
+        // elements (the library refuses a shape outside its envelope before it writes); null CSR pointers select the resident matrices
+        ctx.chk(
+            unsafe {
+                sys::lfplus_ccs_linearize(ctx.raw, transcript.raw, &d, core::ptr::null(), core::ptr::null(), core::ptr::null(), msgs.as_mut_ptr(), ro.as_mut_ptr(),
+                                          evals.as_mut_ptr())
+            },
+            "lfplus_ccs_linearize",
+        )?;
+        ro.truncate(nvars);
+        Ok((msgs, ro, evals))
+    }
+    /// `lfplus_ccs_verify`, host only -> ro; `Err` with `is_reject()` and the stage (1 = a sumcheck round, 2 = the final identity) in `msg`
+    pub fn verify(transcript: &mut HipPlusTranscript, nvars: usize, shape: &HipPlusCCS, msgs: &[u64], evals: &[u64]) -> Result<Vec<u64>, HipPlusError> {
+        let dg = shape.degree();
+        if nvars == 0 || nvars > 32 || dg == 0 || dg > 7 || shape.t == 0 || shape.t > 8 || msgs.len() != nvars * (dg + 2) * 16 || evals.len() != (1 + shape.t) * 16 {
+            return Err(HipPlusError::new(sys::LFPLUS_E_ARG, "ccs_verify", "msgs: nvars x (d + 2) x 16 words, evals: (1 + t) x 16 words, 1 <= nvars <= 32, 1 <= d <= 7, 1 <= t <= 8"));
+        }
+        let (off, idx, coef) = shape.flat();
+        let d = sys::lfplus_ccs { t: shape.t as u32, q: shape.terms.len() as u32, S_off: off.as_ptr(), S_idx: idx.as_ptr(), c: coef.as_ptr() };
+        let (mut ro, mut stage) = (vec![0u64; nvars], 0i32);
+        // SAFETY: live handle; d points into off / idx / coef; the arrays have the sizes checked above
+        let rc = unsafe { sys::lfplus_ccs_verify(transcript.raw, nvars as u32, &d, msgs.as_ptr(), evals.as_ptr(), ro.as_mut_ptr(), &mut stage) };
+        if rc != sys::LFPLUS_OK {
+            return Err(HipPlusError::new(rc, "lfplus_ccs_verify", if rc == sys::LFPLUS_E_REJECT { format!("stage {stage}") } else { "bad arguments".into() }));
+        }
+        Ok(ro)
+    }
+    /// `lfplus_ccs_check` on the resident (A, f) and the resident matrices -> (failed: the `LFPLUS_REL_*` bits, first_bad, absmax); `Ok` also when the instance
+    /// is not satisfied (`failed != 0`).  `cm_f`: kappa x 16 words, or `None` (not checked); `bound` 0: the norm is not checked
+    pub fn check_relation(ctx: &mut HipPlusContext, shape: &HipPlusCCS, cm_f: Option<&[u64]>, bound: u64) -> Result<(u32, u64, u64), HipPlusError> {
+        if let Some(cm) = cm_f {
+            if cm.len() != ctx.kappa * 16 {
+                return Err(HipPlusError::new(sys::LFPLUS_E_ARG, "ccs_check", "cm_f: kappa x 16 words"));
+            }
+        }
+        let (off, idx, coef) = shape.flat();
+        let d = sys::lfplus_ccs { t: shape.t as u32, q: shape.terms.len() as u32, S_off: off.as_ptr(), S_idx: idx.as_ptr(), c: coef.as_ptr() };
+        let (mut failed, mut first_bad, mut absmax) = (0u32, 0u64, 0u64);
+        // SAFETY: live handle; d points into off / idx / coef; cm_f has the size checked above; null CSR pointers select the resident matrices
+        let rc = unsafe {
+            sys::lfplus_ccs_check(ctx.raw, cm_f.map_or(core::ptr::null(), |c| c.as_ptr()), &d, core::ptr::null(), core::ptr::null(), core::ptr::null(), bound, &mut failed,
+                                  &mut first_bad, &mut absmax)
+        };
+        if rc != sys::LFPLUS_OK && rc != sys::LFPLUS_E_REJECT {
+            ctx.chk(rc, "lfplus_ccs_check")?;
+        }
+        Ok((failed, first_bad, absmax))
     }
 }
 impl Drop for HipPlusContext {

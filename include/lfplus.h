@@ -152,7 +152,7 @@ int lfplus_get_witness(lfplus_ctx *ctx, uint64_t *f_out /* n * 16 words */, uint
  * (bound 0: not checked).  Read-only: neither the witness, the from_f buffers nor a transcript is touched; a pending lfplus_rg_from_f_async pass is waited for.
  * Arguments are validated as by lfplus_decompose (CSR shape, canonical words, n a power of two): LFPLUS_E_ARG, as for a context without matrix or witness, a
  * NULL `failed`, and a sharded context (a rank holds only its columns of A; as lfplus_witness_from_z).  The context stays usable after every return. */
-enum { LFPLUS_REL_CM = 1, LFPLUS_REL_R1CS = 2, LFPLUS_REL_V = 4, LFPLUS_REL_NORM = 8 };
+enum { LFPLUS_REL_CM = 1, LFPLUS_REL_R1CS = 2, LFPLUS_REL_CCS = 2 /* the row-wise residual of lfplus_ccs_check: the same bit */, LFPLUS_REL_V = 4, LFPLUS_REL_NORM = 8 };
 /* R_ComR1CS (src/r1cs.rs:21-60): cm_f = A f (cm_f NULL: not checked) and (M_A f) o (M_B f) = M_C f row by row in Z_p[X]/(X^16 + 1), for the three n x n
  * matrices that act on f (r1cs_decomposed_square; rowptr NULL: the resident ones, which must number 3).  *first_bad (may be NULL) = the smallest row with a
  * non-zero residual in any of its 16 coefficients, n when every row holds.  The residual is fused: the three product tables are never written. */
@@ -461,6 +461,37 @@ int lfplus_ring_mul_device(lfplus_ctx *ctx, const uint64_t *a, const uint64_t *b
 /* y = M_j x, M_j the j-th matrix of lfplus_set_matrices / lfplus_share_matrices (n x n), x and y n ring elements */
 int lfplus_spmv(lfplus_ctx *ctx, uint32_t j, const uint64_t *x, uint64_t n, uint64_t *y);
 int lfplus_spmv_device(lfplus_ctx *ctx, uint32_t j, const uint64_t *x, uint64_t n, uint64_t *y);
+
+/* ---- committed CCS instances: the linearization of ANY constraint shape sum_i c_i prod_{j in S_i} (M_j f) = 0 as a protocol step of its own, with its own round
+ * kernel (lfp_ccs.hip).  The reference has none (its README lists "Support CCS" as the next step of latticefold-plus): this is ComR1CS::linearize /
+ * ComR1CSProof::verify (src/r1cs.rs:72-163) generalised in the only way that leaves the R1CS case untouched -- SELF-CONSISTENT, PINNED TO THE REFERENCE AT THE
+ * R1CS SHAPE: with t = 3, S = ({0,1},{2}), c = (1, -1) every word of msgs, ro, evals and the transcript state afterwards is that of lfplus_r1cs_linearize.
+ *   Shape: t matrices M_0 .. M_{t-1} (n x n, CSR, ring coefficients, as lfplus_set_matrices), q multisets S_i of matrix indices (S_idx[S_off[i] .. S_off[i+1])) and
+ * q ring coefficients c_i (16 canonical words each); d = max |S_i|.  An index may repeat inside a multiset (a power) and across multisets (a Plonk-style gate).
+ *   Prover, on the resident witness f (n = 2^nvars ring elements): g_j = M_j f; nvars challenges r from the transcript; MLSumcheck::prove_as_subprotocol of
+ * eq(r, .) * sum_i c_i prod_{j in S_i} g_j at degree d + 1 (absorbs nvars, d + 1, each round's d + 2 evaluations; draws and re-absorbs the challenge);
+ * v = mle(f)(ro), v_j = mle(g_j)(ro); absorbs [v, v_0 .. v_{t-1}] as one slice.  Outputs: msgs (nvars x (d + 2) ring elements), ro (nvars words), evals
+ * ((1 + t) ring elements).  The LinB of the instance is (f, cm_f, r = ro at both points, v = evals at both points): what lfplus_mlin -> lfplus_decompose take with nM = t.
+ *   Verifier, host only (no context): draws r, verify_as_subprotocol(nvars, d + 1, claimed sum 0), absorbs the evals, accepts iff
+ * eq(r, ro) * sum_i c_i prod_{j in S_i} v_j is the expected evaluation.  LFPLUS_E_REJECT with *stage = 1 (a sumcheck round) or 2 (the final identity).
+ *   Neither side checks that the instance is satisfied (the reference's prover does not either): the verifier's round 0 and lfplus_ccs_check do.
+ *   Refusals, every one LFPLUS_E_ARG (with a message in lfplus_last_error where there is a context) before the transcript or the context is touched, in this
+ * order: a NULL argument; t or q outside 1 .. 8; S_off that does not start at 0 or is not strictly increasing (every |S_i| >= 1); a multiset of more than 7
+ * indices (d <= 7); S_off[q] > 16; an index >= t; a word of c >= p; [lfplus_ccs_verify: nvars outside 1 .. 32;] [lfplus_ccs_linearize:] a sharded context (a
+ * transport or lfplus_set_sharding_model; a rank-sharded form is not built, as for lfplus_witness_from_z); no resident witness of 2^nvars ring elements,
+ * nvars >= 1; rowptr NULL and resident matrices that do not number t (or of another n); a CSR array as lfplus_decompose refuses it.  [lfplus_ccs_check: after
+ * the shape, the refusals of lfplus_r1cs_check.]  A NULL context is LFPLUS_E_ARG (without a device none can exist).
+ *   lfplus_ccs_check is lfplus_r1cs_check for this shape: cm_f = A f (NULL: not checked), the norm rule absmax < bound, and the row-wise residual
+ * sum_i c_i prod_{j in S_i} (M_j f)[row] = 0 in the ring, fused (the t product tables are never written; *first_bad = the smallest failing row, n when none fails),
+ * reported as LFPLUS_REL_CCS.  Read-only; the context stays usable after every return.
+ *   No _dev twins: the only O(n) input is the resident witness, which has lfplus_set_witness_dev / lfplus_witness_from_z_dev; everything these calls take or return is small.
+ *   Not built: the prover object and the flat PlusProof for CCS instances (lfplus_prover_* keep nM == 3 / ComR1CS); sharded contexts. */
+typedef struct { uint32_t t, q; const uint32_t *S_off /* q + 1 */, *S_idx /* S_off[q] */; const uint64_t *c /* q x 16 canonical words */; } lfplus_ccs;
+int lfplus_ccs_linearize(lfplus_ctx *ctx, lfplus_transcript *t, const lfplus_ccs *shape, const uint32_t *const *rowptr, const uint32_t *const *col,
+                         const uint64_t *const *val /* t matrices; rowptr NULL: the resident ones, which must number t */, uint64_t *msgs, uint64_t *ro, uint64_t *evals);
+int lfplus_ccs_verify(lfplus_transcript *t, uint32_t nvars, const lfplus_ccs *shape, const uint64_t *msgs, const uint64_t *evals, uint64_t *ro, int *stage);
+int lfplus_ccs_check(lfplus_ctx *ctx, const uint64_t *cm_f, const lfplus_ccs *shape, const uint32_t *const *rowptr, const uint32_t *const *col,
+                     const uint64_t *const *val, uint64_t bound, unsigned *failed, uint64_t *first_bad, uint64_t *absmax);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 // lfp_check.cpp -- on-device relation checks of the LatticeFold+ slice (include/lfplus.h): lfplus_r1cs_check (R_ComR1CS, r1cs.rs:21-60) and lfplus_linb_check
-// (R_LinB, lin.rs:29-40) on the resident (A, f).  The reference has no check_relation for these; the relations are the ones its structs define and its tests
-// assert piecewise (decomp.rs:157-215, r1cs.rs:211-233).  Kernels: lfp_check.hip.  Both calls are read-only: they touch neither the witness, the from_f buffers
+// (R_LinB, lin.rs:29-40) on the resident (A, f), and lfplus_ccs_check, lfplus_r1cs_check for a CCS shape (lfp_ccs.h).  The reference has no check_relation for these; the relations are the ones its structs define and its tests
+// assert piecewise (decomp.rs:157-215, r1cs.rs:211-233).  Kernels: lfp_check.hip.  The calls are read-only: they touch neither the witness, the from_f buffers
 // nor a transcript; every component is evaluated and *failed is the OR of the failing ones; the result words come back in ONE download.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -10,6 +10,7 @@
 #include "../../include/lfplus.h"
 #include "lfp_kernels.h"
 #include "lfp_ctx.h"
+#include "lfp_ccs.h"
 
 namespace {
 constexpr int D = lfp::D;
@@ -111,6 +112,44 @@ extern "C" int lfplus_r1cs_check(lfplus_ctx *c, const uint64_t *cm_f, const uint
     if (first_bad) *first_bad = h[0];
     if (absmax) *absmax = h[1];
     return bad ? fail(c, LFPLUS_E_REJECT, "lfplus_r1cs_check: the instance does not satisfy R_ComR1CS") : LFPLUS_OK;
+}
+
+// lfplus_r1cs_check for a CCS shape: cm_f = A f, the norm rule, and sum_i c_i prod_{j in S_i} (M_j f)[row] = 0 row by row (fused: launch_ccs_residual)
+extern "C" int lfplus_ccs_check(lfplus_ctx *c, const uint64_t *cm_f, const lfplus_ccs *shape, const uint32_t *const *rowptr, const uint32_t *const *col,
+                                const uint64_t *const *val, uint64_t bound, unsigned *failed, uint64_t *first_bad, uint64_t *absmax) {
+    if (!c) return LFPLUS_E_ARG;
+    lfp::CcsDesc d;
+    int rc = lfp_ccs_shape(c, "lfplus_ccs_check", shape, d, nullptr);
+    if (rc) return rc;
+    if ((rc = check_ctx(c, "lfplus_ccs_check", failed, cm_f))) return rc;
+    Mats M;
+    if ((rc = M.get(c, "lfplus_ccs_check", d.t, rowptr, col, val))) return rc;
+    const u64 n = c->n;
+    const size_t cw = (size_t)c->kappa * D;
+    Scratch sc(c);
+    u64 *res = sc.words(RES_HEAD + cw), *coefM = sc.words((size_t)d.q * D);
+    if (!res || !coefM) return fail(c, LFPLUS_E_HIP, "lfplus_ccs_check: out of device memory");
+    const u64 init2[RES_HEAD] = {n, 0};
+    if ((rc = start_result(c, res, init2, cm_f))) return rc;
+    std::vector<u64> hM((size_t)d.q * D);
+    for (size_t i = 0; i < hM.size(); i++) hM[i] = to_mont(shape->c[i]);
+    HIPCHK(c, hipMemcpyAsync(coefM, hM.data(), hM.size() * 8, hipMemcpyHostToDevice, c->st));
+    const u32 *rp[8], *ci[8];
+    const u64 *vv[8];
+    int cc[8];
+    for (u32 q = 0; q < d.t; q++) { rp[q] = M.m[q].rowptr; ci[q] = M.m[q].col; vv[q] = M.m[q].spmv_vals(); cc[q] = M.m[q].const_coef; }
+    lfp::launch_ccs_residual(rp, ci, vv, cc, d, coefM, c->f, (size_t)n, res, c->st);
+    if (absmax || bound) lfp::launch_absmax(c->f, (size_t)n * D, res + 1, c->st);
+    std::vector<u64> h(RES_HEAD + cw);
+    if ((rc = finish_result(c, res, h))) return rc;      // (synchronises: hM is free)
+    unsigned bad = 0;
+    if (cm_f && memcmp(cm_f, h.data() + RES_HEAD, cw * 8)) bad |= LFPLUS_REL_CM;
+    if (h[0] != n) bad |= LFPLUS_REL_CCS;
+    if (bound && !(h[1] < bound)) bad |= LFPLUS_REL_NORM;
+    *failed = bad;
+    if (first_bad) *first_bad = h[0];
+    if (absmax) *absmax = h[1];
+    return bad ? fail(c, LFPLUS_E_REJECT, "lfplus_ccs_check: the instance does not satisfy the committed CCS relation") : LFPLUS_OK;
 }
 
 extern "C" int lfplus_linb_check(lfplus_ctx *c, const uint64_t *cm_f, const uint64_t *r_a, const uint64_t *r_b, uint32_t nM, const uint32_t *const *rowptr,

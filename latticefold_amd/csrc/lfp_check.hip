@@ -2,6 +2,7 @@
 // lfplus_linb_check): R_ComR1CS (r1cs.rs:21-60) and R_LinB (lin.rs:29-40) on the Frog ring Z_p[X]/(X^16 + 1), coefficient form.
 //   k_r1cs_residual  (M_A f) o (M_B f) - M_C f row by row, FUSED: the three n x 16 product tables are never written; the only output is the smallest row with a
 //                    non-zero residual (one atomicMin per wave that holds one; a satisfied system issues none)
+//   k_ccs_residual   the same for a CCS shape (lfplus_ccs_check): sum_i c_i prod_{j in S_i} (M_j f) row by row, fused, the t gathered elements in registers
 //   k_linb_dots      one pass over f: up to 8 ring-valued inner products <f, w_t> against SCALAR weight vectors (eq(r_pt), M_j^T eq(r_pt)) and the centred absmax
 //   k_absmax         the centred absmax alone (the R1CS check, and the LinB check when it runs on tables)
 // HBM-bound integer work; no MFMA.  Results cross to the host in one download of the result words (lfp_check.cpp).
@@ -74,6 +75,64 @@ void launch_r1cs_residual(const u32 *const *rowptr, const u32 *const *col, const
     R1csMats m;
     for (int q = 0; q < 3; q++) { m.rowptr[q] = rowptr[q]; m.col[q] = col[q]; m.vals[q] = vals[q]; m.const_coef[q] = const_coef[q]; }
     hipLaunchKernelGGL(k_r1cs_residual, dim3((unsigned)cdiv(nrows, 16)), dim3(256), 0, s, m, f, nrows, first_bad);
+}
+
+// The same for a CCS shape (lfplus_ccs_check): sum_i c_i prod_{j in S_i} (M_j f)[row], FUSED -- the t product tables are never written.  The row's t gathered
+// elements stay in registers (selected by unrolled compares: a run-time index would send the array to scratch); a chain's products go through the shuffles of the
+// row group as above, a general coefficient (coefM: Montgomery words, read by every lane alike) is the last product of its chain.
+struct CcsMats {
+    const u32 *rowptr[8], *col[8];
+    const u64 *vals[8];
+    int const_coef[8];
+};
+__device__ __forceinline__ u64 ccs_pick(const u64 (&g)[8], u32 j) {
+    u64 r = g[0];
+#pragma unroll
+    for (u32 k = 1; k < 8; k++) r = j == k ? g[k] : r;
+    return r;
+}
+__global__ void __launch_bounds__(256) k_ccs_residual(CcsMats m, CcsDesc d, const u64 *coefM, const u64 *f, size_t nrows, u64 *first_bad) {
+    const size_t row = (size_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+    const int t = threadIdx.x & 15;
+    bool bad = false;
+    if (row < nrows) {      // (the 16 lanes of a row group take this branch together)
+        u64 g[8];
+#pragma unroll
+        for (u32 j = 0; j < 8; j++) g[j] = j < d.t ? row_gather(m.rowptr[j], m.col[j], m.vals[j], m.const_coef[j], f, row, t) : 0;
+        u64 tot = 0;
+        for (u32 i = 0; i < d.q; i++) {
+            const u32 lev = d.lev[i];
+            if (!lev) continue;
+            u64 cur = ccs_pick(g, d.op[i][0]);
+            for (u32 l = 1; l < lev; l++) {
+                Acc160 acc;
+                acc160_bias16(acc);
+                if (l < d.len[i]) {
+                    const u64 a = to_mont(cur), b = ccs_pick(g, d.op[i][l]);
+#pragma unroll
+                    for (int s = 0; s < D; s++) acc160_mad_signed(acc, __shfl(a, s, 16), __shfl(b, (t - s) & 15, 16), s > t);
+                } else {
+#pragma unroll
+                    for (int s = 0; s < D; s++) acc160_mad_signed(acc, coefM[i * 16 + s], __shfl(cur, (t - s) & 15, 16), s > t);
+                }
+                cur = acc160_red(acc);
+            }
+            const u32 cls = d.cls[i];
+            tot = cls == CCS_MINUS_ONE ? sub_p(tot, cur) : cls == CCS_CONST ? add_p(tot, mont_mul(d.cst[i], cur)) : add_p(tot, cur);
+        }
+        bad = tot != 0;
+    }
+    const unsigned long long mask = __ballot(bad);
+    if (mask && (int)(threadIdx.x & 63) == __ffsll((long long)mask) - 1) atomicMin((unsigned long long *)first_bad, (unsigned long long)row);
+}
+void launch_ccs_residual(const u32 *const *rowptr, const u32 *const *col, const u64 *const *vals, const int *const_coef, const CcsDesc &d, const u64 *coefM, const u64 *f,
+                         size_t nrows, u64 *first_bad, hipStream_t s) {
+    CcsMats m;
+    for (u32 q = 0; q < 8; q++) {
+        const u32 k = q < d.t ? q : 0;      // (unused slots repeat matrix 0: never dereferenced)
+        m.rowptr[q] = rowptr[k]; m.col[q] = col[k]; m.vals[q] = vals[k]; m.const_coef[q] = const_coef[k];
+    }
+    hipLaunchKernelGGL(k_ccs_residual, dim3((unsigned)cdiv(nrows, 16)), dim3(256), 0, s, m, d, coefM, f, nrows, first_bad);
 }
 
 // part[chunk][q][16] = sum over the chunk's rows of w[q ldw + row] f[row] for q < NW (w: scalar weights in Montgomery form, f canonical: canonical sums), and the

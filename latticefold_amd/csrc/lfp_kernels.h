@@ -124,6 +124,29 @@ void launch_cm_evals_c(const u64 *R, size_t ldr, size_t n, const u64 *eq, u32 nt
 // ---- ComR1CS::linearize (r1cs.rs:76-139): degree-3 round of eq (ga gb - gc); part: cm_round_blocks(half) * 64
 void launch_r1cs_round_fused(const u64 *E, const u64 *G, size_t ld, size_t half, u64 rM, u64 *Eo, u64 *Go, size_t ld_o, u64 *part, hipStream_t s);   // + fix_variables of the previous round (E / G: previous tables)
 void launch_r1cs_round(const u64 *E, const u64 *G, size_t ld, size_t half, u64 *part, hipStream_t s);
+// ---- linearization of a committed CCS instance (lfp_ccs.hip; lfplus_ccs_linearize): one round of eq * sum_i c_i prod_{j in S_i} g_j at the points 0 .. d + 1.
+// The shape, as the host classified it once (lfp_ccs.h): chain i multiplies the tables op[i][0 .. len[i]); its coefficient is CCS_ZERO (lev[i] = 0: the chain is
+// skipped), CCS_ONE / CCS_MINUS_ONE, CCS_CONST (a base-field constant, cst[i] in Montgomery form: a word-wise multiply) or CCS_GENERAL (one more negacyclic product,
+// against coefficient i of `coef`).  lev[i] = len[i] + (general ? 1 : 0) operands enter chain i, so it costs lev[i] - 1 negacyclic products; maxlev = max_i lev[i];
+// slot[i]: the LDS slot of the running product of a chain with lev[i] >= 2 (nslots of them)
+enum { CCS_ZERO = 0, CCS_ONE = 1, CCS_MINUS_ONE = 2, CCS_CONST = 3, CCS_GENERAL = 4 };
+struct CcsDesc {
+    u32 t, q, maxlev, nslots;
+    uint8_t len[8], lev[8], cls[8], slot[8];
+    uint8_t op[8][8];
+    u64 cst[8];
+};
+u32 ccs_round_blocks(size_t half, u32 cap);      // workgroups of a round over `half` pairs: 16 pairs each and pass, at most cap
+// E: eq(r, .) as Montgomery scalars, ONE word per row; G: the t tables g_j, canonical, [table][ld][16]; coef: q x 16 canonical words (device); np = d + 2 points
+// (3 .. 9).  part[block][np][16] canonical block partials.  The fused form reads the PREVIOUS tables (4 entries per new pair), fixes them at rM (Montgomery) on
+// the way in and stores the fixed tables to Eo / Go (ld_o entries per table)
+void launch_ccs_round(const u64 *E, const u64 *G, size_t ld, size_t half, const CcsDesc &d, u32 np, const u64 *coef, u32 blocks, u64 *part, hipStream_t s);
+void launch_ccs_round_fused(const u64 *E, const u64 *G, size_t ld, size_t half, const CcsDesc &d, u32 np, const u64 *coef, u64 rM, u64 *Eo, u64 *Go, size_t ld_o, u32 blocks,
+                            u64 *part, hipStream_t s);
+// *first_bad = min(*first_bad, smallest row r < nrows with sum_i c_i prod_{j in S_i} (M_j f)[r] != 0) (lfp_check.hip); vals / const_coef as launch_r1cs_residual,
+// coefM: q x 16 MONTGOMERY words (device)
+void launch_ccs_residual(const u32 *const *rowptr, const u32 *const *col, const u64 *const *vals, const int *const_coef, const CcsDesc &d, const u64 *coefM, const u64 *f,
+                         size_t nrows, u64 *first_bad, hipStream_t s);
 // ---- the generic sumcheck (lfp_mlsumcheck.hip; lfplus_mlsumcheck_*): g = sum_i coef_i prod_{k in [off[i], off[i + 1])} T_{idx[k]} over nt ring tables [table][ld][16]
 struct MlsDesc {
     u32 nt, nterms, degree;

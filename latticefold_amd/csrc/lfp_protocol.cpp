@@ -11,6 +11,7 @@
 #include <functional>
 #include <memory>
 #include "lfp_ctx.h"
+#include "lfp_ccs.h"
 #include "lfp_poseidon_simd.h"
 #include "poseidon_host.h"
 static constexpr uint32_t LFP_HOST_SUM_BLOCKS = 256;   // block partials the host adds per round; rounds with more workgroups add theirs on the device (launch_reduce)
@@ -1510,6 +1511,135 @@ extern "C" int lfplus_r1cs_verify(lfplus_transcript *tr, uint32_t nvars, const u
         u64 t[D] = {0};
         rmul_acc(t, evals + D, evals + 2 * D);
         for (int i = 0; i < D; i++) if (fmul(e, fsub(t[i], evals[3 * D + i] % P)) != cur[i]) st = 2;
+    }
+    if (stage) *stage = st;
+    return st ? LFPLUS_E_REJECT : LFPLUS_OK;
+}
+// ---- the linearization of a committed CCS instance (include/lfplus.h lfplus_ccs_*; the reference has none: ComR1CS::linearize with the comb function
+// eq * sum_i c_i prod_{j in S_i} g_j at degree d + 1; self-consistent, pinned to the reference at the R1CS shape).  Kernel: lfp_ccs.hip.
+namespace {
+u32 ccs_block_cap() {
+    const char *e = getenv("LFPLUS_CCS_BLOCKS");   // workgroups of a CCS linearization round at most (default 2048, as cm_round_blocks); a test switch, read once per call: the grid-stride loop at tiny n
+    const long v = e ? atol(e) : 0;
+    return v >= 1 && v <= 65535 ? (u32)v : 2048u;
+}
+}  // namespace
+extern "C" int lfplus_ccs_linearize(lfplus_ctx *c, lfplus_transcript *tr, const lfplus_ccs *shape, const uint32_t *const *rowptr, const uint32_t *const *col,
+                                    const uint64_t *const *val, uint64_t *msgs, uint64_t *ro, uint64_t *evals) {
+    if (!c) return LFPLUS_E_ARG;
+    if (!tr || !msgs || !ro || !evals) return fail(c, LFPLUS_E_ARG, "lfplus_ccs_linearize: null argument");
+    lfp::CcsDesc d;
+    u32 deg = 0;
+    int rc = lfp_ccs_shape(c, "lfplus_ccs_linearize", shape, d, &deg);
+    if (rc) return rc;
+    if (c->sharded()) return fail(c, LFPLUS_E_ARG, "lfplus_ccs_linearize: sharded contexts are not supported (a rank-sharded form is not built)");
+    const size_t n = c->nf;
+    if (!c->f || n < 2 || (n & (n - 1))) return fail(c, LFPLUS_E_ARG, "lfplus_ccs_linearize: needs a resident witness of 2^nvars ring elements, nvars >= 1");
+    if (!rowptr && (c->mats.size() != d.t || c->mats_n != n)) return fail(c, LFPLUS_E_ARG, "lfplus_ccs_linearize: the resident matrices do not number t, or have another shape (lfplus_set_matrices)");
+    u32 nvars = 0;
+    while (((size_t)1 << nvars) < n) nvars++;
+    const u32 T = d.t, np = deg + 2, cap = ccs_block_cap();
+    HIPCHK(c, hipSetDevice(c->device));
+    PoolScope pool_scope(c);
+    MatHold M;      // (the caller's CSR arrays are validated here: still before the transcript is touched)
+    if ((rc = M.get(c, n, T, rowptr, col, val))) return rc;
+    DevBuf E[2], G[2], part, small, coef;
+    const u32 nb0 = lfp::ccs_round_blocks(n / 2, cap);
+    if (E[0].alloc(n * 8) || E[1].alloc(n / 2 * 8) || G[0].alloc((size_t)T * n * D * 8) || G[1].alloc((size_t)T * (n / 2) * D * 8) ||
+        part.alloc(std::max<size_t>((size_t)nb0 * np * D, (size_t)lfp::eval_chunks(n) * D) * 8) || small.alloc((size_t)(1 + T) * D * 8) || coef.alloc((size_t)d.q * D * 8))
+        return fail(c, LFPLUS_E_HIP, "hipMalloc (CCS linearize tables)");
+    u64 *hpart = c->pin((size_t)LFP_HOST_SUM_BLOCKS * np * D);
+    if (!hpart) return fail(c, LFPLUS_E_HIP, "hipHostMalloc (round partials)");
+    HIPCHK(c, hipMemcpyAsync(coef.p, shape->c, (size_t)d.q * D * 8, hipMemcpyHostToDevice, c->st));
+    for (u32 q = 0; q < T; q++) lfp::launch_spmv_ring(M[q].rowptr, M[q].col, M[q].spmv_vals(), c->f, n, G[0].as<u64>() + (size_t)q * n * D, c->st, M[q].const_coef);
+    std::vector<u64> r(nvars);
+    for (u32 j = 0; j < nvars; j++) r[j] = tr->challenge();
+    eq_build_local(c, r.data(), nvars, E[0].as<u64>());
+    tr->absorb_const(nvars);
+    tr->absorb_const(deg + 1);
+    // round 0 reads the full tables (stride n), later rounds ping-pong between the first halves of the two buffers; fix_variables is deferred into the next
+    // round's kernel (k_ccs_round<NP, true>) unless LFPLUS_CM_UNFUSED asks for the separate launches
+    const u64 *Ec = E[0].as<u64>(), *Gc = G[0].as<u64>();
+    size_t ld = n, len = n;
+    int w = 1;
+    const bool fuse = getenv("LFPLUS_CM_UNFUSED") == nullptr;   // (read per call, like the other switches)
+    bool pending = false;
+    u64 xpend = 0;
+    for (u32 rnd = 0; rnd < nvars; rnd++) {
+        const size_t half = pending ? len / 4 : len / 2;
+        const u32 nb = lfp::ccs_round_blocks(half, cap);
+        const bool dev_sum = nb > LFP_HOST_SUM_BLOCKS;     // (as the R1CS rounds: small rounds write their block partials into mapped host memory, large ones add them on the device)
+        u64 *pdst = dev_sum ? part.as<u64>() : c->hpin_dev;
+        if (pending) {
+            const size_t ldo = n / 2;
+            u64 *Eo = w ? E[1].as<u64>() : E[0].as<u64>(), *Go = w ? G[1].as<u64>() : G[0].as<u64>();
+            lfp::launch_ccs_round_fused(Ec, Gc, ld, half, d, np, coef.as<u64>(), to_mont(xpend), Eo, Go, ldo, nb, pdst, c->st);
+            Ec = Eo; Gc = Go; ld = ldo; w ^= 1;
+            len /= 2;
+            pending = false;
+        } else
+            lfp::launch_ccs_round(Ec, Gc, ld, half, d, np, coef.as<u64>(), nb, pdst, c->st);
+        if (dev_sum) lfp::launch_sum_parts(part.as<u64>(), nb, (size_t)np * D, np * D, c->hpin_dev, c->st);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        u64 *m = msgs + (size_t)rnd * np * D;
+        const u32 nbh = dev_sum ? 1u : nb;
+        for (u32 x = 0; x < np * D; x++) {
+            u64 s = 0;
+            for (u32 b = 0; b < nbh; b++) s = fadd(s, hpart[(size_t)b * np * D + x]);
+            m[x] = s;
+        }
+        tr->absorb_ring(m, np);
+        const u64 x = tr->challenge();
+        tr->absorb_const(x);
+        ro[rnd] = x;
+        if (fuse && rnd + 1 < nvars) { pending = true; xpend = x; }
+        else {
+            const size_t ldo = n / 2;
+            u64 *Eo = w ? E[1].as<u64>() : E[0].as<u64>(), *Go = w ? G[1].as<u64>() : G[0].as<u64>();
+            lfp::launch_cm_fix(Ec, ld, Eo, ldo, 1, 1, half, to_mont(x), c->st);
+            lfp::launch_cm_fix(Gc, ld, Go, ldo, D, T, half, to_mont(x), c->st);
+            Ec = Eo; Gc = Go; ld = ldo; w ^= 1;
+            len = half;
+        }
+    }
+    // v = f at ro; v_j = the fully fixed tables
+    HIPCHK(c, hipMemcpy2DAsync(small.as<u64>() + D, D * 8, Gc, ld * D * 8, D * 8, T, hipMemcpyDeviceToDevice, c->st));    // before E[0] / G are reused
+    eq_build_local(c, ro, nvars, E[0].as<u64>());
+    lfp::launch_wring(c->f, n, E[0].as<u64>(), 1, part.as<u64>(), small.as<u64>(), c->st);
+    HIPCHK(c, hipMemcpyAsync(evals, small.p, (size_t)(1 + T) * D * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    tr->absorb_ring(evals, 1 + T);
+    return LFPLUS_OK;
+}
+// the verifier of lfplus_ccs_linearize's proofs, host only: stage 1 = a sumcheck round, 2 = eq(r, ro) sum_i c_i prod_{j in S_i} v_j != the expected evaluation
+extern "C" int lfplus_ccs_verify(lfplus_transcript *tr, uint32_t nvars, const lfplus_ccs *shape, const uint64_t *msgs, const uint64_t *evals, uint64_t *ro, int *stage) {
+    if (!tr || !msgs || !evals || !ro) return LFPLUS_E_ARG;
+    lfp::CcsDesc d;
+    u32 deg = 0;
+    const int rc = lfp_ccs_shape(nullptr, "lfplus_ccs_verify", shape, d, &deg);
+    if (rc) return rc;
+    if (nvars < 1 || nvars > 32) return LFPLUS_E_ARG;
+    std::vector<u64> r(nvars);
+    for (u32 j = 0; j < nvars; j++) r[j] = tr->challenge();
+    int st = 0;
+    u64 cur[D] = {0};
+    if (ring_sumcheck_rounds(tr, nvars, deg + 1, msgs, cur, ro, true) >= 0) st = 1;
+    if (!st) {
+        tr->absorb_ring(evals, 1 + d.t);
+        const u64 e = eq_eval(r.data(), ro, nvars);
+        u64 tot[D] = {0};
+        for (u32 i = 0; i < d.q; i++) {
+            u64 pr[D];
+            for (int x = 0; x < D; x++) pr[x] = evals[(size_t)(1 + d.op[i][0]) * D + x] % P;
+            for (u32 k = 1; k < d.len[i]; k++) {
+                u64 nx[D] = {0};
+                rmul_acc(nx, pr, evals + (size_t)(1 + d.op[i][k]) * D);
+                memcpy(pr, nx, sizeof(pr));
+            }
+            rmul_acc(tot, shape->c + (size_t)i * D, pr);
+        }
+        for (int x = 0; x < D; x++) if (fmul(e, tot[x]) != cur[x]) st = 2;
     }
     if (stage) *stage = st;
     return st ? LFPLUS_E_REJECT : LFPLUS_OK;

@@ -28,6 +28,7 @@ class LfPlusError(RuntimeError):
 
 E_ARG, E_NO_DEVICE, E_HIP, E_EXP_DOMAIN, E_SMALL_N, E_REJECT = -1, -2, -3, -4, -5, -6
 REL_CM, REL_R1CS, REL_V, REL_NORM = 1, 2, 4, 8      # lfplus.h LFPLUS_REL_*: the components of a relation check (lfplus_r1cs_check / lfplus_linb_check)
+REL_CCS = 2                                         # the row-wise residual of lfplus_ccs_check: the bit of REL_R1CS
 ABSENT = -128     # exponent digit of a zero entry of a monomial set (lfplus.h LFPLUS_ABSENT)
 MUL_ELEMENTWISE, MUL_BROADCAST = 0, 1      # lfplus.h LFPLUS_MUL_*: the modes of lfplus_ring_mul
 
@@ -36,6 +37,11 @@ class VPolyDesc(C.Structure):
     """lfplus.h lfplus_vpoly"""
     _fields_ = [("nvars", C.c_uint32), ("ntables", C.c_uint32), ("nterms", C.c_uint32), ("degree", C.c_uint32), ("term_off", C.POINTER(C.c_uint32)),
                 ("term_idx", C.POINTER(C.c_uint32)), ("coef", u64p)]
+
+
+class CCSDesc(C.Structure):
+    """lfplus.h lfplus_ccs"""
+    _fields_ = [("t", C.c_uint32), ("q", C.c_uint32), ("S_off", C.POINTER(C.c_uint32)), ("S_idx", C.POINTER(C.c_uint32)), ("c", u64p)]
 
 
 def exported_symbols():
@@ -132,6 +138,11 @@ def _lib():
         L.lfplus_ring_mul_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp]
         L.lfplus_spmv.argtypes = [vp, C.c_uint32, u64p, C.c_uint64, u64p]
         L.lfplus_spmv_device.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp]
+        # committed CCS instances (lfplus_ccs_*)
+        cp = C.POINTER(CCSDesc)
+        L.lfplus_ccs_linearize.argtypes = [vp, vp, cp, u32pp, u32pp, u64pp, u64p, u64p, u64p]
+        L.lfplus_ccs_verify.argtypes = [vp, C.c_uint32, cp, u64p, u64p, u64p, ip]
+        L.lfplus_ccs_check.argtypes = [vp, u64p, cp, u32pp, u32pp, u64pp, C.c_uint64, uip, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         _READY = True
     return L
 
@@ -437,6 +448,22 @@ class PlusContext:
         cm, cmp_ = self._cm_arg(cm_f)
         failed, fb, am = C.c_uint(), C.c_uint64(), C.c_uint64()
         rc = _lib().lfplus_r1cs_check(self.h, cmp_, rp, cp, vp, int(bound), C.byref(failed), C.byref(fb), C.byref(am))
+        if rc not in (0, E_REJECT):
+            self._chk(rc)
+        return rc == 0, failed.value, fb.value, am.value
+
+    def ccs_check(self, cm_f, shape, M=None, bound=0):
+        """The committed CCS relation on the resident (A, f) (lfplus_ccs_check): cm_f = A f (None: not checked), sum_i c_i prod_{j in S_i} (M_j f)[row] = 0 row
+        by row, ||f||_inf < bound (0: not checked) -> (ok, failed, first_bad, absmax) as r1cs_check; the residual's bit is REL_CCS.  M: the shape's t matrices
+        (None: the resident ones)"""
+        M = RESIDENT(shape.t) if M is None else M
+        if len(M) != shape.t:
+            raise LfPlusError(E_ARG, f"ccs_check: the shape has {shape.t} matrices")
+        keep, rp, cp, vp = _csr_args(M)
+        cm, cmp_ = self._cm_arg(cm_f)
+        d = shape.desc()
+        failed, fb, am = C.c_uint(), C.c_uint64(), C.c_uint64()
+        rc = _lib().lfplus_ccs_check(self.h, cmp_, C.byref(d), rp, cp, vp, int(bound), C.byref(failed), C.byref(fb), C.byref(am))
         if rc not in (0, E_REJECT):
             self._chk(rc)
         return rc == 0, failed.value, fb.value, am.value
@@ -942,6 +969,123 @@ def r1cs_verify(transcript, proof, nvars=None):
     rc = _lib().lfplus_r1cs_verify(transcript.h, nvars, msgs.ctypes.data_as(u64p), ev.ctypes.data_as(u64p), ro.ctypes.data_as(u64p), C.byref(st))
     if rc not in (0, E_REJECT):
         raise LfPlusError(rc, "lfplus_r1cs_verify")
+    return rc == 0, st.value, ro
+
+
+# ---- committed CCS instances (lfplus_ccs_*; the reference has none: self-consistent, pinned to the reference at the R1CS shape) ---------------------------
+class CCSShape:
+    """A CCS shape over t matrices: sum_i c_i * prod_{j in S_i} (M_j f) = 0 row by row.  multisets: q sequences of matrix indices (an index may repeat inside
+    one and across them); coeffs: q ring elements (16 canonical words) or Python integers (constant polynomials, reduced mod p).  The envelope (1 <= t, q <= 8,
+    1 <= |S_i| <= 7, at most 16 indices in all, indices < t) is the library's to refuse: desc() passes anything that can be written down."""
+
+    def __init__(self, t, multisets, coeffs):
+        self.t = int(t)
+        self.multisets = [[int(j) for j in S] for S in multisets]
+        if len(coeffs) != len(self.multisets):
+            raise LfPlusError(E_ARG, "CCSShape: one coefficient per multiset")
+        self.coeffs = np.zeros((max(len(self.multisets), 1), D), dtype=np.uint64)
+        for i, c in enumerate(coeffs):
+            if isinstance(c, (int, np.integer)):
+                self.coeffs[i, 0] = int(c) % P
+            else:
+                self.coeffs[i] = np.asarray(c, dtype=np.uint64).reshape(D)
+
+    @staticmethod
+    def r1cs():
+        """(M_0 f) o (M_1 f) - M_2 f: the shape lfplus_r1cs_linearize hard-wires"""
+        return CCSShape(3, [[0, 1], [2]], [1, -1])
+
+    @property
+    def q(self):
+        return len(self.multisets)
+
+    @property
+    def degree(self):
+        """d = max |S_i| (the sumcheck runs at degree d + 1 and sends d + 2 evaluations per round)"""
+        return max((len(S) for S in self.multisets), default=0)
+
+    def desc(self):
+        """the lfplus_ccs of this shape (the arrays it points to stay alive with the returned object)"""
+        off = np.zeros(self.q + 1, dtype=np.uint32)
+        idx = []
+        for i, S in enumerate(self.multisets):
+            idx += S
+            off[i + 1] = len(idx)
+        idx = np.asarray(idx + [0], dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        d = CCSDesc(self.t, self.q, off.ctypes.data_as(u32p), idx.ctypes.data_as(u32p), self.coeffs.ctypes.data_as(u64p))
+        d._keep = (off, idx, self.coeffs)
+        return d
+
+
+@dataclass
+class ComCCS:
+    """A committed CCS instance, mirroring ComR1CS: shape, its t CSR matrices (n x n), the witness f (n ring elements; None: resident in `ctx`) and cm_f = A f"""
+    shape: CCSShape
+    mats: tuple
+    f: np.ndarray
+    cm_f: np.ndarray
+    ctx: object = None
+
+    @staticmethod
+    def new(ctx, shape, mats, f, A=None):
+        if A is not None:
+            ctx.set_matrix(A)
+        if len(mats) != shape.t:
+            raise LfPlusError(E_ARG, f"ComCCS: the shape has {shape.t} matrices")
+        f = np.ascontiguousarray(f, dtype=np.uint64)
+        return ComCCS(shape, tuple(mats), f, ctx.commit(f))
+
+    def matrices(self):
+        return list(self.mats)
+
+    def check_relation(self, ctx, bound=0, resident=False):
+        """Is the instance satisfied?  PlusContext.ccs_check on `ctx` -> (ok, failed, first_bad, absmax).  A host instance uploads its f into `ctx`; a resident
+        one is checked in the context that holds its witness.  resident: the matrices are the ones ctx.set_matrices / share_matrices left on the device"""
+        if self.f is None:
+            if ctx is not self.ctx:
+                raise LfPlusError(E_ARG, "ComCCS.check_relation: a resident instance is checked in the context that holds its witness")
+        else:
+            ctx.set_witness(self.f)
+        return ctx.ccs_check(self.cm_f, self.shape, None if resident else self.mats, bound)
+
+    def linearize(self, ctx, transcript, resident=False, preloaded=False):
+        """lfplus_ccs_linearize on `ctx` (the witness becomes resident there) -> (LinB fields, proof fields): msgs (nvars, d + 2, 16), r = ro (nvars), evals
+        (1 + t, 16).  The LinB goes into mlin / decompose with the shape's t matrices.  resident / preloaded as ComR1CS.linearize"""
+        if self.f is None:
+            if ctx is not self.ctx:
+                raise LfPlusError(E_ARG, "ComCCS.linearize: a resident instance is linearized in the context that holds its witness")
+        elif not preloaded:
+            ctx.set_witness(self.f)
+        n = ctx.n if self.f is None else self.f.shape[0]
+        nvars = max(int(n).bit_length() - 1, 0)
+        t, d = self.shape.t, self.shape.degree
+        keep, rp, cp, vp = _csr_args(RESIDENT(t) if resident else self.mats)
+        if not resident and len(self.mats) != t:
+            raise LfPlusError(E_ARG, f"ComCCS.linearize: the shape has {t} matrices")
+        msgs, ro, ev = np.zeros((nvars, d + 2, D), dtype=np.uint64), np.zeros(max(nvars, 1), dtype=np.uint64), np.zeros((1 + max(t, 0), D), dtype=np.uint64)
+        desc = self.shape.desc()
+        ctx._chk(_lib().lfplus_ccs_linearize(ctx.h, transcript.h, C.byref(desc), rp, cp, vp, *[x.ctypes.data_as(u64p) for x in (msgs, ro, ev)]))
+        ro = ro[:nvars]
+        proof = {"msgs": msgs, "nvars": nvars, "r": ro, "evals": ev}
+        linb = {"f": self.f, "cm_f": self.cm_f, "r": ro, "v": ev}
+        return linb, proof
+
+
+def ccs_verify(transcript, shape, proof, nvars=None):
+    """The verifier of ComCCS.linearize's proofs (lfplus_ccs_verify), host -> (accepted, stage, ro): stage 1 = a sumcheck round, 2 = the final identity.  nvars:
+    the VERIFIER's log2 n (None: the proof's own field); the arrays are checked against it and against the shape either way"""
+    if not isinstance(shape, CCSShape):
+        raise LfPlusError(E_ARG, "ccs_verify: shape must be a CCSShape")
+    nvars = _nvars_ok(proof["nvars"] if nvars is None else nvars)
+    if not 1 <= shape.t <= 8 or not 1 <= shape.q <= 8 or not 1 <= shape.degree <= 7:      # (the arrays' shapes follow from these: nothing to check them against)
+        raise LfPlusError(E_ARG, "ccs_verify: shape outside the envelope (1 <= t, q <= 8, 1 <= |S_i| <= 7)")
+    msgs, ev = _shaped(proof, "msgs", (nvars, shape.degree + 2, D)), _shaped(proof, "evals", (1 + shape.t, D))
+    ro, st = np.zeros(nvars, dtype=np.uint64), C.c_int()
+    d = shape.desc()
+    rc = _lib().lfplus_ccs_verify(transcript.h, nvars, C.byref(d), msgs.ctypes.data_as(u64p), ev.ctypes.data_as(u64p), ro.ctypes.data_as(u64p), C.byref(st))
+    if rc not in (0, E_REJECT):
+        raise LfPlusError(rc, "lfplus_ccs_verify")
     return rc == 0, st.value, ro
 
 

@@ -57,7 +57,7 @@ def rust_type(ctype):
     name = " ".join(base)
     if name in SCALARS:
         r = SCALARS[name]
-    elif name in OPAQUE or name in ("lf_params", "lfplus_params", "lf_vpoly", "lfplus_vpoly"):
+    elif name in OPAQUE or name in ("lf_params", "lfplus_params", "lf_vpoly", "lfplus_vpoly", "lfplus_ccs"):
         r = name
     elif name in ("lf_exchange_fn", "lfplus_exchange_fn"):
         r = "lf_exchange_fn"
@@ -78,7 +78,7 @@ def split_params(s):
     for i, p in enumerate(x.strip() for x in s.split(",")):
         m = re.match(r"^(.*?)([A-Za-z_][A-Za-z_0-9]*)?$", p)
         ctype, name = m.group(1).strip(), m.group(2)
-        if name in SCALARS or name in OPAQUE or name in ("lf_params", "lfplus_params", "lf_vpoly", "lfplus_vpoly", "lf_exchange_fn", "lfplus_exchange_fn", "unsigned", "const") or not ctype:   # unnamed parameter
+        if name in SCALARS or name in OPAQUE or name in ("lf_params", "lfplus_params", "lf_vpoly", "lfplus_vpoly", "lfplus_ccs", "lf_exchange_fn", "lfplus_exchange_fn", "unsigned", "const") or not ctype:   # unnamed parameter
             ctype, name = p, None
         if name is None:
             base = re.findall(r"[A-Za-z_][A-Za-z_0-9]*", ctype)[-1]
@@ -132,6 +132,9 @@ def generate():
           "/// VirtualPolynomial over RqPoly as a flat product list (latticefold utils/sumcheck/utils.rs:24-75; lfplus_mlsumcheck_*): 16 words per coefficient",
           "#[repr(C)] #[derive(Clone, Copy, Debug)]",
           "pub struct lfplus_vpoly { pub nvars: u32, pub ntables: u32, pub nterms: u32, pub degree: u32, pub term_off: *const u32, pub term_idx: *const u32, pub coef: *const u64 }",
+          "/// A CCS shape over t matrices (lfplus_ccs_*): sum_i c_i prod_{j in S_idx[S_off[i] .. S_off[i+1])} (M_j f), 16 words per coefficient",
+          "#[repr(C)] #[derive(Clone, Copy, Debug)]",
+          "pub struct lfplus_ccs { pub t: u32, pub q: u32, pub S_off: *const u32, pub S_idx: *const u32, pub c: *const u64 }",
           "/// all-gather `words` u64 from every rank into recv_all[world * words] in rank order; 0 on success (lf_set_sharding)",
           "pub type lf_exchange_fn = Option<unsafe extern \"C\" fn(user: *mut c_void, send: *const u64, recv_all: *mut u64, words: usize) -> c_int>;", ""]
     allfns = []
