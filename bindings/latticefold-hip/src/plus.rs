@@ -61,6 +61,27 @@ impl PlusProof {
         // SAFETY: params is a valid reference; the call reads nothing else
         unsafe { sys::lfplus_proof_len(params, n as u64, nM as u32, L as u32, nfresh as u32) as usize }
     }
+    /// `lfplus_proof_len_ccs`: the same for a prover of committed CCS instances (0: a shape or parameters the library refuses)
+    pub fn len_for_ccs(params: &PlusParameters, n: usize, shape: &HipPlusCCS, L: usize, nfresh: usize) -> usize {
+        let (off, idx, coef) = shape.flat();
+        let d = sys::lfplus_ccs { t: shape.t as u32, q: shape.terms.len() as u32, S_off: off.as_ptr(), S_idx: idx.as_ptr(), c: coef.as_ptr() };
+        // SAFETY: params is a valid reference; d points into off / idx / coef, which outlive the call
+        unsafe { sys::lfplus_proof_len_ccs(params, n as u64, &d, L as u32, nfresh as u32) as usize }
+    }
+    /// `lfplus_proof_layout_ccs`: (offset, length) in words of every field of such a proof, in the order `lfplus.h` documents; `None` where `len_for_ccs` is 0
+    pub fn layout_for_ccs(params: &PlusParameters, n: usize, shape: &HipPlusCCS, L: usize, nfresh: usize) -> Option<Vec<(usize, usize)>> {
+        let (off, idx, coef) = shape.flat();
+        let d = sys::lfplus_ccs { t: shape.t as u32, q: shape.terms.len() as u32, S_off: off.as_ptr(), S_idx: idx.as_ptr(), c: coef.as_ptr() };
+        // SAFETY: no pointer is passed
+        let nf = unsafe { sys::lfplus_proof_fields(nfresh as u32) } as usize;
+        let (mut o, mut l) = (vec![0u64; nf], vec![0u64; nf]);
+        // SAFETY: d points into off / idx / coef; o and l hold the nf entries the call is told of
+        let rc = unsafe { sys::lfplus_proof_layout_ccs(params, n as u64, &d, L as u32, nfresh as u32, o.as_mut_ptr(), l.as_mut_ptr(), nf as u32) };
+        if rc != sys::LFPLUS_OK {
+            return None;
+        }
+        Some(o.iter().zip(&l).map(|(a, b)| (*a as usize, *b as usize)).collect())
+    }
 }
 
 /// `PoseidonTranscript::<RqPoly>::empty::<FrogPoseidonConfig>()`: the host sponge the library advances
@@ -137,6 +158,9 @@ pub struct HipPlusProver<R> {
     n: usize,
     nM: usize,
     nacc: usize,
+    nfresh: usize,
+    // Some: a prover of committed CCS instances (`init_ccs`); its proofs have the CCS layout
+    shape: Option<HipPlusCCS>,
     _r: PhantomData<R>,
 }
 // SAFETY: the object has no thread affinity (every entry point selects its device); `&mut self` gives the one-thread-at-a-time the header asks for
@@ -160,7 +184,83 @@ impl<R: RingWords + Clone> HipPlusProver<R> {
         if rc != sys::LFPLUS_OK {
             return Err(HipPlusError::new(rc, "lfplus_prover_create", "no usable device, or parameters outside the envelope"));
         }
-        Ok(HipPlusProver { raw, transcript, params, n, nM: M.len(), nacc: 0, _r: PhantomData })
+        Ok(HipPlusProver { raw, transcript, params, n, nM: M.len(), nacc: 0, nfresh: 0, shape: None, _r: PhantomData })
+    }
+
+    /// The same for committed CCS instances over the `shape.t` matrices `M` (`lfplus_prover_create_ccs`): `prove` linearizes with `lfplus_ccs_linearize` and
+    /// writes the CCS layout; the instances are `HipComR1CS` values (a witness and its commitment: nothing in them is R1CS-specific)
+    pub fn init_ccs(A: Matrix<R>, M: Vec<SparseMatrix<R>>, shape: HipPlusCCS, ncomp: usize, params: PlusParameters, transcript: HipPlusTranscript) -> Result<Self, HipPlusError> {
+        assert_eq!(R::WORDS, 16, "the LatticeFold+ ABI is the Frog ring: 16 words per element");
+        if M.len() != shape.t {
+            return Err(HipPlusError::new(sys::LFPLUS_E_ARG, "lfplus_prover_create_ccs", "the shape names t matrices"));
+        }
+        let n = A.ncols;
+        let a_words: Vec<u64> = A.vals.iter().flat_map(|row| flatten(row)).collect();
+        let mats: Vec<_> = M.iter().map(|m| csr(m, n)).collect();
+        let rp: Vec<*const u32> = mats.iter().map(|m| m.0.as_ptr()).collect();
+        let cp: Vec<*const u32> = mats.iter().map(|m| m.1.as_ptr()).collect();
+        let vp: Vec<*const u64> = mats.iter().map(|m| m.2.as_ptr()).collect();
+        let (off, idx, coef) = shape.flat();
+        let d = sys::lfplus_ccs { t: shape.t as u32, q: shape.terms.len() as u32, S_off: off.as_ptr(), S_idx: idx.as_ptr(), c: coef.as_ptr() };
+        let mut raw = core::ptr::null_mut();
+        // SAFETY: every pointer outlives the call (the library copies A, M and the shape); the transcript handle outlives the prover, which owns it
+        let rc = unsafe {
+            sys::lfplus_prover_create_ccs(0, &params, a_words.as_ptr(), 0, n as u64, &d, rp.as_ptr(), cp.as_ptr(), vp.as_ptr(), ncomp as u32, transcript.raw, &mut raw)
+        };
+        if rc != sys::LFPLUS_OK {
+            return Err(HipPlusError::new(rc, "lfplus_prover_create_ccs", "no usable device, a refused shape, or parameters outside the envelope"));
+        }
+        Ok(HipPlusProver { raw, transcript, params, n, nM: M.len(), nacc: 0, nfresh: 0, shape: Some(shape), _r: PhantomData })
+    }
+
+    /// `lfplus_prover_set_instances`: names the fresh instances of the next prove (their upload starts on the library's worker thread).  With
+    /// [`HipPlusProver::check_fresh`] and [`HipPlusProver::prove_named`] this is `prove` in steps.
+    /// # Safety
+    /// every `comp[i].f` stays alive and unmoved until `prove_named` (or the drop of the prover) returns: the library borrows it
+    pub unsafe fn set_instances(&mut self, comp: &[HipComR1CS]) -> Result<(), HipPlusError> {
+        let fp: Vec<*const u64> = comp.iter().map(|c| c.f.as_ptr()).collect();
+        let cp: Vec<*const u64> = comp.iter().map(|c| c.cm_f.as_ptr()).collect();
+        // SAFETY: the caller's contract
+        let rc = unsafe { sys::lfplus_prover_set_instances(self.raw, fp.as_ptr(), cp.as_ptr(), comp.len() as u32) };
+        if rc != sys::LFPLUS_OK {
+            return Err(self.err(rc, "lfplus_prover_set_instances"));
+        }
+        self.nfresh = comp.len();
+        Ok(())
+    }
+
+    /// `lfplus_prover_check_fresh`: is every instance named for the next prove in its relation (`lfplus_ccs_check` for a CCS prover, `lfplus_r1cs_check`
+    /// otherwise), where it lives -> per instance (failed: the `LFPLUS_REL_*` bits, first_bad, absmax); `Ok` also when one is not satisfied.  Read-only
+    pub fn check_fresh(&mut self, bound: u64) -> Result<Vec<(u32, u64, u64)>, HipPlusError> {
+        let cnt = self.nfresh.max(1);
+        let (mut ok, mut failed, mut first_bad, mut absmax) = (vec![0i32; cnt], vec![0u32; cnt], vec![0u64; cnt], vec![0u64; cnt]);
+        // SAFETY: the four arrays hold at least nfresh entries, the number of instances the library has been given
+        let rc = unsafe { sys::lfplus_prover_check_fresh(self.raw, bound, ok.as_mut_ptr(), failed.as_mut_ptr(), first_bad.as_mut_ptr(), absmax.as_mut_ptr()) };
+        if rc != sys::LFPLUS_OK && rc != sys::LFPLUS_E_REJECT {
+            return Err(self.err(rc, "lfplus_prover_check_fresh"));
+        }
+        Ok((0..self.nfresh).map(|i| (failed[i], first_bad[i], absmax[i])).collect())
+    }
+
+    fn proof_words(&self, L: usize, nfresh: usize) -> usize {
+        match &self.shape {
+            Some(shape) => PlusProof::len_for_ccs(&self.params, self.n, shape, L, nfresh),
+            None => PlusProof::len_for(&self.params, self.n, self.nM, L, nfresh),
+        }
+    }
+
+    /// `lfplus_prover_prove` on the instances named by `set_instances` / `ingest_dev` / `set_instances_dev`
+    pub fn prove_named(&mut self) -> Result<PlusProof, HipPlusError> {
+        let words = self.proof_words(self.nacc + self.nfresh, self.nfresh);
+        let mut proof = vec![0u64; words];
+        // SAFETY: proof holds exactly the words the library checks the length against
+        let rc = unsafe { sys::lfplus_prover_prove(self.raw, proof.as_mut_ptr(), words as u64) };
+        if rc != sys::LFPLUS_OK {
+            return Err(self.err(rc, "lfplus_prover_prove"));
+        }
+        self.nacc = 2;
+        self.nfresh = 0;
+        Ok(PlusProof(proof))
     }
 
     /// The transcript the prover advances (`PlusProver::transcript` of the reference, read-only here: the library borrows the handle until the prover is
@@ -184,7 +284,7 @@ impl<R: RingWords + Clone> HipPlusProver<R> {
         if rc != sys::LFPLUS_OK {
             return Err(self.err(rc, "lfplus_prover_set_instances"));
         }
-        let words = PlusProof::len_for(&self.params, self.n, self.nM, self.nacc + comp.len(), comp.len());
+        let words = self.proof_words(self.nacc + comp.len(), comp.len());
         let mut proof = vec![0u64; words];
         // SAFETY: proof holds exactly the words the library checks the length against
         let rc = unsafe { sys::lfplus_prover_prove(self.raw, proof.as_mut_ptr(), words as u64) };
@@ -214,7 +314,11 @@ impl<R: RingWords + Clone> HipPlusProver<R> {
         let mut cm = vec![0u64; z.len() * self.params.kappa as usize * 16];
         // SAFETY: the caller's contract; cm holds count x kappa ring elements
         let rc = unsafe { sys::lfplus_prover_ingest_dev(self.raw, z.as_ptr(), z.len() as u32, m as u64, l_in as u32, cm.as_mut_ptr()) };
-        if rc != sys::LFPLUS_OK { Err(self.err(rc, "lfplus_prover_ingest_dev")) } else { Ok(cm) }
+        if rc != sys::LFPLUS_OK {
+            return Err(self.err(rc, "lfplus_prover_ingest_dev"));
+        }
+        self.nfresh = z.len();
+        Ok(cm)
     }
 
     /// `lfplus_prover_set_instances_dev`: the same from witnesses `f[i]` (n ring elements each) in DEVICE memory; copied and checked before the call returns
@@ -225,7 +329,11 @@ impl<R: RingWords + Clone> HipPlusProver<R> {
         assert_eq!(f.len(), cm_f.len());
         // SAFETY: the caller's contract
         let rc = unsafe { sys::lfplus_prover_set_instances_dev(self.raw, f.as_ptr(), cm_f.as_ptr(), f.len() as u32) };
-        if rc != sys::LFPLUS_OK { Err(self.err(rc, "lfplus_prover_set_instances_dev")) } else { Ok(()) }
+        if rc != sys::LFPLUS_OK {
+            return Err(self.err(rc, "lfplus_prover_set_instances_dev"));
+        }
+        self.nfresh = f.len();
+        Ok(())
     }
 
     /// `lfplus_prover_accumulator_dev`: the accumulator halves copied, device to device, into `F0` / `F1` (n x 16 words each; either may be null)
@@ -543,13 +651,19 @@ pub struct HipPlusVerifier<R> {
     n: usize,
     nM: usize,
     nacc: usize,
+    // Some: the statement is about committed CCS instances (`init_ccs`); proofs have the CCS layout
+    shape: Option<HipPlusCCS>,
     _r: PhantomData<R>,
 }
 
 impl<R: RingWords> HipPlusVerifier<R> {
     /// Initialize (plus.rs:118-130): only the shapes of A and M enter the verification
     pub fn init(A: Matrix<R>, M: Vec<SparseMatrix<R>>, params: PlusParameters, transcript: HipPlusTranscript) -> Self {
-        HipPlusVerifier { transcript, params, n: A.ncols, nM: M.len(), nacc: 0, _r: PhantomData }
+        HipPlusVerifier { transcript, params, n: A.ncols, nM: M.len(), nacc: 0, shape: None, _r: PhantomData }
+    }
+    /// The verifier of a [`HipPlusProver::init_ccs`] prover (`lfplus_verify_ccs`; host only)
+    pub fn init_ccs(A: Matrix<R>, M: Vec<SparseMatrix<R>>, shape: HipPlusCCS, params: PlusParameters, transcript: HipPlusTranscript) -> Self {
+        HipPlusVerifier { transcript, params, n: A.ncols, nM: M.len(), nacc: 0, shape: Some(shape), _r: PhantomData }
     }
 
     /// Verify (plus.rs:133-143) a proof that folds `nfresh` fresh instances into this verifier's accumulator.  `Err` with `LFPLUS_E_REJECT` and the
@@ -557,12 +671,22 @@ impl<R: RingWords> HipPlusVerifier<R> {
     pub fn verify_fresh(&mut self, proof: &PlusProof, nfresh: usize) -> Result<bool, HipPlusError> {
         let (mut which, mut stage) = (0i32, 0i32);
         let L = self.nacc + nfresh;
-        // SAFETY: the library checks proof.0.len() against its own layout before it reads a field
-        let rc = unsafe {
-            sys::lfplus_verify(&self.params, self.n as u64, self.nM as u32, L as u32, nfresh as u32, self.transcript.raw, proof.0.as_ptr(), proof.0.len() as u64, &mut which, &mut stage)
+        let rc = match &self.shape {
+            Some(shape) => {
+                let (off, idx, coef) = shape.flat();
+                let d = sys::lfplus_ccs { t: shape.t as u32, q: shape.terms.len() as u32, S_off: off.as_ptr(), S_idx: idx.as_ptr(), c: coef.as_ptr() };
+                // SAFETY: d points into off / idx / coef; the library checks proof.0.len() against its own layout before it reads a field
+                unsafe {
+                    sys::lfplus_verify_ccs(&self.params, self.n as u64, &d, L as u32, nfresh as u32, self.transcript.raw, proof.0.as_ptr(), proof.0.len() as u64, &mut which, &mut stage)
+                }
+            }
+            // SAFETY: the library checks proof.0.len() against its own layout before it reads a field
+            None => unsafe {
+                sys::lfplus_verify(&self.params, self.n as u64, self.nM as u32, L as u32, nfresh as u32, self.transcript.raw, proof.0.as_ptr(), proof.0.len() as u64, &mut which, &mut stage)
+            },
         };
         if rc != sys::LFPLUS_OK {
-            return Err(HipPlusError::new(rc, "lfplus_verify", format!("which = {which}, stage = {stage}")));
+            return Err(HipPlusError::new(rc, if self.shape.is_some() { "lfplus_verify_ccs" } else { "lfplus_verify" }, format!("which = {which}, stage = {stage}")));
         }
         self.nacc = 2;
         Ok(true)

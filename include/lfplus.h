@@ -485,13 +485,52 @@ int lfplus_spmv_device(lfplus_ctx *ctx, uint32_t j, const uint64_t *x, uint64_t 
  * sum_i c_i prod_{j in S_i} (M_j f)[row] = 0 in the ring, fused (the t product tables are never written; *first_bad = the smallest failing row, n when none fails),
  * reported as LFPLUS_REL_CCS.  Read-only; the context stays usable after every return.
  *   No _dev twins: the only O(n) input is the resident witness, which has lfplus_set_witness_dev / lfplus_witness_from_z_dev; everything these calls take or return is small.
- *   Not built: the prover object and the flat PlusProof for CCS instances (lfplus_prover_* keep nM == 3 / ComR1CS); sharded contexts. */
+ *   The prover object and the flat proof for these instances: lfplus_prover_create_ccs / lfplus_verify_ccs below.
+ *   Not built: sharded contexts (and so a sharded CCS prover). */
 typedef struct { uint32_t t, q; const uint32_t *S_off /* q + 1 */, *S_idx /* S_off[q] */; const uint64_t *c /* q x 16 canonical words */; } lfplus_ccs;
 int lfplus_ccs_linearize(lfplus_ctx *ctx, lfplus_transcript *t, const lfplus_ccs *shape, const uint32_t *const *rowptr, const uint32_t *const *col,
                          const uint64_t *const *val /* t matrices; rowptr NULL: the resident ones, which must number t */, uint64_t *msgs, uint64_t *ro, uint64_t *evals);
 int lfplus_ccs_verify(lfplus_transcript *t, uint32_t nvars, const lfplus_ccs *shape, const uint64_t *msgs, const uint64_t *evals, uint64_t *ro, int *stage);
 int lfplus_ccs_check(lfplus_ctx *ctx, const uint64_t *cm_f, const lfplus_ccs *shape, const uint32_t *const *rowptr, const uint32_t *const *col,
                      const uint64_t *const *val, uint64_t bound, unsigned *failed, uint64_t *first_bad, uint64_t *absmax);
+
+/* ---- PlusProver / PlusVerifier for committed CCS instances: the objects above with "the linearization of this prover" a CCS shape in place of ComR1CS.  One
+ * body serves both (lfp_prover.cpp): lfplus_ccs_linearize per fresh instance as it arrives (from_f on the second stream, as for R1CS), lfplus_mlin and
+ * lfplus_decompose_resident with nM = t.  SELF-CONSISTENT, PINNED AT THE R1CS SHAPE: with t = 3, S = ({0,1},{2}), c = (1, -1) every field word after the header,
+ * the accumulator and the transcript state are those of the lfplus_prover_create prover on the same inputs (through the general round kernel: the object has one
+ * linearization path per kind, no dispatch on the shape).
+ *   lfplus_prover_create_ccs is lfplus_prover_create with the shape in place of nM (rowptr / col / val name shape->t matrices).  The shape is COPIED (S_off, S_idx,
+ * c are free again on return); its refusals are those of lfplus_ccs_linearize, in that order, LFPLUS_E_ARG with *out = NULL before any context is created.  The
+ * result is an ordinary lfplus_prover: ingest, set_instances, their _dev twins, prove, accumulator(_dev), decide, wait_stream, destroy and last_error work on it
+ * unchanged, with the same state machine and failed-state rules; prove and decide expect the CCS layout below.  Unsharded only.
+ *   The flat proof: the layout above with another header and per fresh instance i < nfresh (d = max |S_i|)
+ *     msgs        nvars * (d + 2) * 16     r        nvars          evals    (1 + t) * 16
+ *   then the CmProof, LinB2X and DecompProof fields with nM = t; lfplus_proof_fields(nfresh) fields as before.
+ *   header        LFPLUS_PROOF_MAGIC_CCS, L, nfresh, nvars, k, l, kappa, t, q, d, S_off[q], 0      (LFPLUS_PROOF_HEADER_CCS words; CHECKED, never used for sizing)
+ * lfplus_proof_len_ccs / lfplus_proof_layout_ccs: as their namesakes; a shape lfplus_ccs_linearize refuses, or parameters outside the envelope above, give
+ * 0 / LFPLUS_E_ARG.
+ *   lfplus_verify_ccs is lfplus_verify for this layout, host only (no context, no GPU): a refused shape, a length or header that differs from the verifier's own
+ * statement, or a NULL proof is LFPLUS_E_ARG before any word of a field is read and with the transcript untouched; then lfplus_ccs_verify per fresh instance,
+ * lfplus_cm_verify (nM = t), lfplus_decomp_verify (1 + t).  *which / *stage are numbered exactly as in lfplus_verify (stage of a fresh instance: 1 = a sumcheck
+ * round, 2 = the final identity -- evaluations of the LAST round that were changed show there, the sums of the earlier rounds having held). */
+#define LFPLUS_PROOF_HEADER_CCS 12
+#define LFPLUS_PROOF_MAGIC_CCS 0x4C46504C55533032ULL   /* the bytes "LFPLUS02", most significant first */
+int lfplus_prover_create_ccs(int device, const lfplus_params *params, const uint64_t *A, uint64_t seed, uint64_t n, const lfplus_ccs *shape,
+                             const uint32_t *const *rowptr, const uint32_t *const *col, const uint64_t *const *val, uint32_t ncomp, lfplus_transcript *transcript,
+                             lfplus_prover **out);
+uint64_t lfplus_proof_len_ccs(const lfplus_params *params, uint64_t n, const lfplus_ccs *shape, uint32_t L, uint32_t nfresh);
+int lfplus_proof_layout_ccs(const lfplus_params *params, uint64_t n, const lfplus_ccs *shape, uint32_t L, uint32_t nfresh, uint64_t *offsets, uint64_t *lengths,
+                            uint32_t nfields);
+int lfplus_verify_ccs(const lfplus_params *params, uint64_t n, const lfplus_ccs *shape, uint32_t L, uint32_t nfresh, lfplus_transcript *transcript,
+                      const uint64_t *proof, uint64_t proof_words, int *which, int *stage);
+/* Is every fresh instance named by the last ingest / set_instances in its relation?  Asked where the instance lives, on the resident matrices: lfplus_ccs_check
+ * for a prover of lfplus_prover_create_ccs, lfplus_r1cs_check for one of lfplus_prover_create (neither the linearization nor the prove checks satisfaction, as
+ * the reference's do not).  Outputs are arrays of nfresh entries: ok[i] = 1 / 0, failed[i] = the LFPLUS_REL_* bits, first_bad[i] = the smallest failing row (n:
+ * none), absmax[i]; cm_f is compared when set_instances supplied it, ||f||_inf < bound when bound != 0.  Valid between naming the instances and the prove
+ * (LFPLUS_E_ARG otherwise, and on a FAILED prover).  Waits for the upload worker; an upload that failed fails the prover exactly as it would in the prove.
+ * LFPLUS_OK when all hold, LFPLUS_E_REJECT when one does not (all outputs written in both cases).  Read-only: the transcript is untouched and the following
+ * prove writes the proof it would have written without the call. */
+int lfplus_prover_check_fresh(lfplus_prover *prover, uint64_t bound, int *ok, unsigned *failed, uint64_t *first_bad, uint64_t *absmax);
 
 #ifdef __cplusplus
 }

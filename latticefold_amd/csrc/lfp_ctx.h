@@ -253,7 +253,8 @@ static inline bool canonical(const u64 *w, size_t n) {
 int lfp_commit_resident_enqueue(lfplus_ctx *c, u64 **res_dev);                                                                       // lfp_capi.cpp
 int lfp_dev_ptr_check(lfplus_ctx *c, const void *p, uint64_t elems, const char *who);                                                // lfp_capi.cpp (lfp_prover.cpp declares it itself)
 int lfp_upload_matrix(lfplus_ctx *c, size_t n, const u32 *rowptr, const u32 *col, const u64 *val, LfpMatrix &m);   // lfp_protocol.cpp
-void lfp_mls_drop(lfplus_ctx *c);                                                                                   // lfp_mlsumcheck.cpp: ends the generic sumcheck in progress, if any
+int lfp_ccs_shape_check(const lfplus_ccs *shape, uint32_t *deg);                                                    // lfp_protocol.cpp: the refusals of lfp_ccs.h without a context (lfp_prover.cpp declares it itself)
+void lfp_mls_drop(lfplus_ctx *c);                                                                                  // lfp_mlsumcheck.cpp: ends the generic sumcheck in progress, if any
 // ---- exchanges of a sharded prover (no-ops when world == 1).  Every small exchange is "all-gather `words` u64 per rank, add the world vectors mod p" on host
 // buffers (the round messages and evaluations are summed on the host anyway); the two large ones (h and the folded g, n ring elements) are device all-gathers.
 static inline u64 lfp_addp(u64 a, u64 b) { unsigned __int128 s = (unsigned __int128)a + b; return (u64)(s >= lfp::P ? s - lfp::P : s); }

@@ -1612,6 +1612,12 @@ extern "C" int lfplus_ccs_linearize(lfplus_ctx *c, lfplus_transcript *tr, const 
     tr->absorb_ring(evals, 1 + T);
     return LFPLUS_OK;
 }
+// THE shape refusals (lfp_ccs.h) for the prover object, which has no context yet when it must refuse and is compiled without HIP (lfp_prover.cpp declares it
+// itself, as lfp_dev_ptr_check): LFPLUS_OK with *deg = max |S_i|, or LFPLUS_E_ARG
+int lfp_ccs_shape_check(const lfplus_ccs *shape, uint32_t *deg) {
+    lfp::CcsDesc d;
+    return lfp_ccs_shape(nullptr, "lfplus_ccs", shape, d, deg);
+}
 // the verifier of lfplus_ccs_linearize's proofs, host only: stage 1 = a sumcheck round, 2 = eq(r, ro) sum_i c_i prod_{j in S_i} v_j != the expected evaluation
 extern "C" int lfplus_ccs_verify(lfplus_transcript *tr, uint32_t nvars, const lfplus_ccs *shape, const uint64_t *msgs, const uint64_t *evals, uint64_t *ro, int *stage) {
     if (!tr || !msgs || !evals || !ro) return LFPLUS_E_ARG;

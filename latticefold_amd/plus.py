@@ -1036,6 +1036,19 @@ class ComCCS:
         f = np.ascontiguousarray(f, dtype=np.uint64)
         return ComCCS(shape, tuple(mats), f, ctx.commit(f))
 
+    @staticmethod
+    def new_resident(ctx, shape, mats, z, b, k):
+        """ComCCS.new with f = z.gadget_decompose(b, k) cut and committed on the device (PlusContext.witness_from_z), as ComR1CS.new_resident: f stays in `ctx`"""
+        if len(mats) != shape.t:
+            raise LfPlusError(E_ARG, f"ComCCS: the shape has {shape.t} matrices")
+        if not api.is_device_array(z):
+            z = np.ascontiguousarray(z, dtype=np.uint64)
+        return ComCCS(shape, tuple(mats), None, ctx.witness_from_z(z, b, k), ctx)
+
+    def fetch_f(self):
+        """f as a host array: of a resident instance, read back from its context (which must still hold it)"""
+        return self.f if self.f is not None else self.ctx.get_witness()
+
     def matrices(self):
         return list(self.mats)
 
@@ -1049,14 +1062,16 @@ class ComCCS:
             ctx.set_witness(self.f)
         return ctx.ccs_check(self.cm_f, self.shape, None if resident else self.mats, bound)
 
-    def linearize(self, ctx, transcript, resident=False, preloaded=False):
+    def linearize(self, ctx, transcript, resident=False, preloaded=False, from_f_hint=None):
         """lfplus_ccs_linearize on `ctx` (the witness becomes resident there) -> (LinB fields, proof fields): msgs (nvars, d + 2, 16), r = ro (nvars), evals
-        (1 + t, 16).  The LinB goes into mlin / decompose with the shape's t matrices.  resident / preloaded as ComR1CS.linearize"""
+        (1 + t, 16).  The LinB goes into mlin / decompose with the shape's t matrices.  resident / preloaded / from_f_hint as ComR1CS.linearize"""
         if self.f is None:
             if ctx is not self.ctx:
                 raise LfPlusError(E_ARG, "ComCCS.linearize: a resident instance is linearized in the context that holds its witness")
         elif not preloaded:
             ctx.set_witness(self.f)
+        if from_f_hint is not None:
+            ctx.rg_from_f_async(from_f_hint)
         n = ctx.n if self.f is None else self.f.shape[0]
         nvars = max(int(n).bit_length() - 1, 0)
         t, d = self.shape.t, self.shape.degree
@@ -1244,11 +1259,17 @@ def _ro_pairs(ro):
 class PlusProver:
     """plus.rs:15-108.  One context per instance (2 accumulated + ncomp fresh); all share the Ajtai matrix of the first."""
 
-    def __init__(self, A, M, ncomp, params, transcript, device=0, shard=None):
-        """shard = (rank, world, transport): a prover column-sharded over `world` ranks, one GPU each -- A is then the rank's column slice (kappa, n / world,
+    def __init__(self, A, M, ncomp, params, transcript, device=0, shard=None, shape=None):
+        """shape: a CCSShape over the t = len(M) matrices -- the prover folds ComCCS instances (lfplus_ccs_linearize in place of lfplus_r1cs_linearize; unsharded
+        only).  shard = (rank, world, transport): a prover column-sharded over `world` ranks, one GPU each -- A is then the rank's column slice (kappa, n / world,
         16); transport is an allgather callable (host transport: PlusContext.set_sharding) or the bytes of an ncclUniqueId (RCCL: PlusContext.dist_init).
         Every rank makes the same calls with the same (whole) witnesses and gets the same proof."""
-        self.M, self.params, self.transcript = list(M), params, transcript
+        self.M, self.params, self.transcript, self.shape = list(M), params, transcript, shape
+        if shape is not None:      # (before a context exists)
+            if not isinstance(shape, CCSShape) or shape.t != len(self.M):
+                raise LfPlusError(E_ARG, "PlusProver: shape must be a CCSShape over len(M) matrices")
+            if shard is not None:
+                raise LfPlusError(E_ARG, "PlusProver: a CCS prover is unsharded only (lfplus_ccs_linearize refuses sharded contexts)")
         self.device = device
         self.ctxs = [PlusContext(device) for _ in range(2 + ncomp)]
         if shard is not None:
@@ -1271,8 +1292,8 @@ class PlusProver:
         self.failed = None     # set when a prove() raised half way: the Fiat-Shamir transcript has advanced and the contexts hold a half-folded state
 
     @staticmethod
-    def init(A, M, ncomp, params, transcript, device=0, shard=None):
-        return PlusProver(A, M, ncomp, params, transcript, device, shard)
+    def init(A, M, ncomp, params, transcript, device=0, shard=None, shape=None):
+        return PlusProver(A, M, ncomp, params, transcript, device, shard, shape)
 
     def close(self):
         for c in reversed(self.ctxs):
@@ -1289,17 +1310,20 @@ class PlusProver:
             self.ctxs[nacc + i].set_witness(ci.f)
         self._preloaded = [ci.f for ci in comp]
 
-    def ingest(self, zs, r1cs, l_in=1):
+    def ingest(self, zs, r1cs=None, l_in=1):
         """The fresh instances of the next prove, built in the contexts that prove will use (ComR1CS.new_resident in ctxs[nacc + i]: z is uploaded, cut into
         f = z.gadget_decompose(B, k) and committed on the device) -> the ComR1CS list; prove(comps) then neither uploads nor reads a host f.  Not for a sharded
-        prover.  A prover whose ingest raised is failed, as one whose prove raised (a context may be left without its witness)."""
+        prover.  A CCS prover (shape=) builds resident ComCCS over its own matrices (r1cs: not used).  A prover whose ingest raised is failed, as one whose prove raised (a context may be left without its witness)."""
         if self.failed is not None:
             raise LfPlusError(E_ARG, f"PlusProver.ingest: this prover failed earlier ({self.failed}) -- build a new prover")
         nacc = len(self.acc)
         if nacc + len(zs) > len(self.ctxs):
             raise LfPlusError(E_ARG, "PlusProver.ingest: more instances than contexts (ncomp)")
         try:
-            comps = [ComR1CS.new_resident(self.ctxs[nacc + i], r1cs, z, l_in, self.params.B, self.params.lin.decomp.k) for i, z in enumerate(zs)]
+            if self.shape is not None:
+                comps = [ComCCS.new_resident(self.ctxs[nacc + i], self.shape, self.M, z, self.params.B, self.params.lin.decomp.k) for i, z in enumerate(zs)]
+            else:
+                comps = [ComR1CS.new_resident(self.ctxs[nacc + i], r1cs, z, l_in, self.params.B, self.params.lin.decomp.k) for i, z in enumerate(zs)]
         except Exception as ex:
             self.failed = repr(ex)
             raise
@@ -1342,6 +1366,8 @@ class PlusProver:
         nacc = len(self.acc)
         if nacc + len(comp) > len(self.ctxs):
             raise LfPlusError(E_ARG, "PlusProver.prove: more instances than contexts (ncomp)")
+        if any((self.shape is not None) != isinstance(ci, ComCCS) for ci in comp):      # (a shape error: nothing is touched)
+            raise LfPlusError(E_ARG, "PlusProver.prove: a CCS prover (shape=) folds ComCCS instances, any other prover ComR1CS")
         try:
             return self._prove(comp, nacc)
         except Exception as ex:      # the reference's prove() panics on these paths; here the object survives, so it must refuse to continue from this state
@@ -1406,7 +1432,8 @@ class PlusProver:
                 _wait(ctxs[i])
                 ctxs[i].rg_from_f_async(dp)
             for i, ci in enumerate(comp):
-                same = len(self.M) == 3 and all(a is b for x, y in zip(ci.r1cs, self.M) for a, b in zip(x, y))   # (M = cr1cs.x.matrices() in every reference use)
+                mats = ci.mats if self.shape is not None else ci.r1cs
+                same = len(self.M) == (3 if self.shape is None else self.shape.t) and all(a is b for x, y in zip(mats, self.M) for a, b in zip(x, y))   # (M = cr1cs.x.matrices() in every reference use)
                 _wait(ctxs[nacc + i])
                 _, lp = ci.linearize(ctxs[nacc + i], self.transcript, resident=same, preloaded=True, from_f_hint=dp)
                 lproof.append(lp)
@@ -1432,8 +1459,10 @@ class PlusProver:
 class PlusVerifier:
     """plus.rs:25-33, 110-146 (host only).  verify returns True, or False with .stage = (which proof, stage) -- the reference panics there"""
 
-    def __init__(self, A, M, params, transcript):
-        self.M, self.params, self.transcript = list(M), params, transcript
+    def __init__(self, A, M, params, transcript, shape=None):
+        self.M, self.params, self.transcript, self.shape = list(M), params, transcript, shape
+        if shape is not None and (not isinstance(shape, CCSShape) or shape.t != len(self.M)):
+            raise LfPlusError(E_ARG, "PlusVerifier: shape must be a CCSShape over len(M) matrices")
         self.stage = None
         # the verifier's OWN shape parameters (plus.rs:110-146 passes &self.A, &self.M down; CmProof::verify sizes everything from them, cm.rs:349-365):
         # nothing below is taken from the proof
@@ -1444,8 +1473,8 @@ class PlusVerifier:
         self.nvars = self.n.bit_length() - 1
 
     @staticmethod
-    def init(A, M, params, transcript):
-        return PlusVerifier(A, M, params, transcript)
+    def init(A, M, params, transcript, shape=None):
+        return PlusVerifier(A, M, params, transcript, shape)
 
     def verify(self, proof):
         """False with .stage = (which proof, stage); a proof whose arrays do not have the shapes this verifier's parameters imply is rejected as
@@ -1453,7 +1482,10 @@ class PlusVerifier:
         dp, nM = self.params.lin.decomp, len(self.M)
         try:
             for i, lp in enumerate(proof["lproof"]):
-                ok, st, _ = r1cs_verify(self.transcript, lp, nvars=self.nvars)
+                if self.shape is not None:
+                    ok, st, _ = ccs_verify(self.transcript, self.shape, lp, nvars=self.nvars)
+                else:
+                    ok, st, _ = r1cs_verify(self.transcript, lp, nvars=self.nvars)
                 if not ok:
                     self.stage = (f"lproof[{i}]", st)
                     return False
@@ -1559,6 +1591,8 @@ def make_plus_workload(name):
 # ---- PlusProver / PlusVerifier behind the C ABI (lfplus_prover_*, lfplus_verify: csrc/lfp_prover.cpp) and the flat PlusProof ------------------------------
 PROOF_HEADER = 8                                  # lfplus.h LFPLUS_PROOF_HEADER
 PROOF_MAGIC = 0x4C46504C55533031                  # lfplus.h LFPLUS_PROOF_MAGIC
+PROOF_HEADER_CCS = 12                             # lfplus.h LFPLUS_PROOF_HEADER_CCS
+PROOF_MAGIC_CCS = 0x4C46504C55533032              # lfplus.h LFPLUS_PROOF_MAGIC_CCS
 PROOF_CM_KEYS = ("r", "msgs", "e", "b", "v", "a", "bb", "c", "comh", "pa", "pb", "ea", "eb", "cm_g", "ro", "vo", "fcoms")    # the order lfplus_mlin takes them
 _NATIVE_READY = False
 
@@ -1601,21 +1635,47 @@ def _nlib():
         L.lfplus_prover_ingest_dev.argtypes = [vp, vpp, C.c_uint32, C.c_uint64, C.c_uint32, u64p]
         L.lfplus_prover_set_instances_dev.argtypes = [vp, vpp, u64pp, C.c_uint32]
         L.lfplus_prover_accumulator_dev.argtypes = [vp, vp, vp]
+        # the same objects for committed CCS instances (the shape in place of nM) and the relation check of the fresh instances
+        cp = C.POINTER(CCSDesc)
+        L.lfplus_prover_create_ccs.argtypes = [C.c_int, pp, u64p, C.c_uint64, C.c_uint64, cp, u32pp, u32pp, u64pp, C.c_uint32, vp, C.POINTER(vp)]
+        L.lfplus_proof_len_ccs.argtypes = [pp, C.c_uint64, cp, C.c_uint32, C.c_uint32]
+        L.lfplus_proof_len_ccs.restype = C.c_uint64
+        L.lfplus_proof_layout_ccs.argtypes = [pp, C.c_uint64, cp, C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32]
+        L.lfplus_verify_ccs.argtypes = [pp, C.c_uint64, cp, C.c_uint32, C.c_uint32, vp, u64p, C.c_uint64, ip, ip]
+        L.lfplus_prover_check_fresh.argtypes = [vp, C.c_uint64, ip, C.POINTER(C.c_uint), u64p, u64p]
         _NATIVE_READY = True
     return L
 
 
-def proof_len(params, n, nM, L, nfresh):
-    """lfplus_proof_len: words of the flat PlusProof of a prove that folds L instances, nfresh of them fresh (0: outside the envelope)"""
+def _shape_nM(shape, nM, who):
+    """the number of matrices of a flat proof: the shape's t when a CCSShape is given in place of nM (nM is then None, or agrees)"""
+    if shape is None:
+        return int(nM)
+    if not isinstance(shape, CCSShape):
+        raise LfPlusError(E_ARG, f"{who}: shape must be a CCSShape")
+    if nM is not None and int(nM) != shape.t:
+        raise LfPlusError(E_ARG, f"{who}: nM differs from the shape's t")
+    return shape.t
+
+
+def proof_len(params, n, nM, L, nfresh, shape=None):
+    """lfplus_proof_len: words of the flat PlusProof of a prove that folds L instances, nfresh of them fresh (0: outside the envelope).  shape: a CCSShape in
+    place of nM -- the flat proof of a CCS prover (lfplus_proof_len_ccs)"""
+    if shape is not None:
+        _shape_nM(shape, nM, "proof_len")
+        return int(_nlib().lfplus_proof_len_ccs(C.byref(_cparams(params)), int(n), C.byref(shape.desc()), int(L), int(nfresh)))
     return int(_nlib().lfplus_proof_len(C.byref(_cparams(params)), int(n), int(nM), int(L), int(nfresh)))
 
 
-def proof_fields(params, n, nM, L, nfresh):
-    """The fields of the flat PlusProof in their fixed order (lfplus.h): [(path, shape)], path = ("lproof", i, key) or (part, key)"""
+def proof_fields(params, n, nM, L, nfresh, shape=None):
+    """The fields of the flat PlusProof in their fixed order (lfplus.h): [(path, shape)], path = ("lproof", i, key) or (part, key).  shape: a CCSShape in place
+    of nM (msgs (nvars, d + 2, 16) and evals (1 + t, 16) per fresh instance, the tail with nM = t)"""
+    nM = _shape_nM(shape, nM, "proof_fields")
+    np_, nev = (4, 4) if shape is None else (shape.degree + 2, 1 + shape.t)
     nvars, kappa, k, q, per = int(n).bit_length() - 1, params.lin.kappa, params.lin.decomp.k, 1 + nM, 4 + 4 * nM
     out = []
     for i in range(nfresh):
-        out += [(("lproof", i, "msgs"), (nvars, 4, D)), (("lproof", i, "r"), (nvars,)), (("lproof", i, "evals"), (4, D))]
+        out += [(("lproof", i, "msgs"), (nvars, np_, D)), (("lproof", i, "r"), (nvars,)), (("lproof", i, "evals"), (nev, D))]
     cm = {"r": (nvars,), "msgs": (nvars, 4, D), "e": (q, L * k, D, D), "b": (L, D), "v": (L, D), "a": (L, q), "bb": (L, q, D), "c": (L, q, D), "comh": (L, kappa, D),
           "pa": (nvars, 3, D), "pb": (nvars, 3, D), "ea": (L, per, D), "eb": (L, per, D), "cm_g": (L, kappa, D), "ro": (2, nvars), "vo": (L, q, 2, D),
           "fcoms": (L, 3, kappa, D)}
@@ -1625,63 +1685,78 @@ def proof_fields(params, n, nM, L, nfresh):
     return out
 
 
-def proof_layout(params, n, nM, L, nfresh):
-    """lfplus_proof_layout -> (offsets, lengths) in words, one entry per field of proof_fields; LfPlusError(E_ARG) outside the envelope"""
+def proof_layout(params, n, nM, L, nfresh, shape=None):
+    """lfplus_proof_layout -> (offsets, lengths) in words, one entry per field of proof_fields; LfPlusError(E_ARG) outside the envelope.  shape: a CCSShape in
+    place of nM (lfplus_proof_layout_ccs)"""
     lib = _nlib()
     nf = int(lib.lfplus_proof_fields(int(nfresh)))
     off, ln = np.zeros(nf, dtype=np.uint64), np.zeros(nf, dtype=np.uint64)
-    rc = lib.lfplus_proof_layout(C.byref(_cparams(params)), int(n), int(nM), int(L), int(nfresh), off.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), nf)
+    if shape is not None:
+        _shape_nM(shape, nM, "proof_layout")
+        rc = lib.lfplus_proof_layout_ccs(C.byref(_cparams(params)), int(n), C.byref(shape.desc()), int(L), int(nfresh), off.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), nf)
+    else:
+        rc = lib.lfplus_proof_layout(C.byref(_cparams(params)), int(n), int(nM), int(L), int(nfresh), off.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), nf)
     if rc:
         raise LfPlusError(rc, "lfplus_proof_layout: parameters outside the envelope")
     return [int(x) for x in off], [int(x) for x in ln]
 
 
-def _proof_header(params, n, nM, L, nfresh):
+def _proof_header(params, n, nM, L, nfresh, shape=None):
     dp = params.lin.decomp
-    return np.array([PROOF_MAGIC, L, nfresh, int(n).bit_length() - 1, dp.k, dp.l, params.lin.kappa, nM], dtype=np.uint64)
+    h = [PROOF_MAGIC, L, nfresh, int(n).bit_length() - 1, dp.k, dp.l, params.lin.kappa, nM]
+    if shape is not None:
+        h = [PROOF_MAGIC_CCS] + h[1:7] + [shape.t, shape.q, shape.degree, sum(len(S) for S in shape.multisets), 0]
+    return np.array(h, dtype=np.uint64)
 
 
-def proof_to_flat(proof, params, n, nM):
+def proof_to_flat(proof, params, n, nM, shape=None):
     """A PlusProof dict (PlusProver.prove, the oracle's) as the flat words of lfplus.h; L = the instances the Cm proof folds, nfresh = len(lproof).  A field
-    whose shape is not the one (params, n, nM, L) imply raises LfPlusError(E_ARG)"""
+    whose shape is not the one (params, n, nM, L) imply raises LfPlusError(E_ARG).  shape: a CCSShape in place of nM (the CCS layout and header)"""
+    nM = _shape_nM(shape, nM, "proof_to_flat")
     try:
         L, nfresh = int(np.asarray(proof["cmproof"]["b"]).shape[0]), len(proof["lproof"])
     except (KeyError, TypeError, IndexError) as ex:
         raise LfPlusError(E_ARG, f"malformed proof: {ex!r}")
-    off, ln = proof_layout(params, n, nM, L, nfresh)
+    off, ln = proof_layout(params, n, nM, L, nfresh, shape=shape)
+    hdr = _proof_header(params, n, nM, L, nfresh, shape)
     out = np.zeros(off[-1] + ln[-1], dtype=np.uint64)
-    out[:PROOF_HEADER] = _proof_header(params, n, nM, L, nfresh)
-    for (path, shape), o, w in zip(proof_fields(params, n, nM, L, nfresh), off, ln):
+    out[:hdr.size] = hdr
+    for (path, shp), o, w in zip(proof_fields(params, n, nM, L, nfresh, shape=shape), off, ln):
         try:
             src = proof["lproof"][path[1]] if path[0] == "lproof" else proof[path[0]]
         except (KeyError, TypeError, IndexError) as ex:
             raise LfPlusError(E_ARG, f"malformed proof: {ex!r}")
-        out[o:o + w] = _shaped(src, path[-1], shape).reshape(-1)
+        out[o:o + w] = _shaped(src, path[-1], shp).reshape(-1)
     return out
 
 
-def proof_from_flat(words, params, n, nM, L, nfresh):
+def proof_from_flat(words, params, n, nM, L, nfresh, shape=None):
     """The flat words as a PlusProof dict of the shapes PlusProver.prove returns (copies; the metadata k / ell / kappa / nvars is the CALLER's).  A buffer whose
-    length or header disagrees with (params, n, nM, L, nfresh) raises LfPlusError(E_ARG)"""
+    length or header disagrees with (params, n, nM, L, nfresh) raises LfPlusError(E_ARG).  shape: a CCSShape in place of nM"""
+    nM = _shape_nM(shape, nM, "proof_from_flat")
     words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
-    off, ln = proof_layout(params, n, nM, L, nfresh)
-    if words.size != off[-1] + ln[-1] or (words[:PROOF_HEADER] != _proof_header(params, n, nM, L, nfresh)).any():
+    off, ln = proof_layout(params, n, nM, L, nfresh, shape=shape)
+    hdr = _proof_header(params, n, nM, L, nfresh, shape)
+    if words.size != off[-1] + ln[-1] or (words[:hdr.size] != hdr).any():
         raise LfPlusError(E_ARG, "malformed proof: length or header differs from the parameters")
     nvars, dp = int(n).bit_length() - 1, params.lin.decomp
     proof = {"lproof": [{"nvars": nvars} for _ in range(nfresh)], "cmproof": {"k": dp.k, "ell": dp.l, "kappa": params.lin.kappa, "nvars": nvars}, "linb2x": {}, "dproof": {}}
-    for (path, shape), o, w in zip(proof_fields(params, n, nM, L, nfresh), off, ln):
+    for (path, shp), o, w in zip(proof_fields(params, n, nM, L, nfresh, shape=shape), off, ln):
         dst = proof["lproof"][path[1]] if path[0] == "lproof" else proof[path[0]]
-        dst[path[-1]] = words[o:o + w].reshape(shape).copy()
+        dst[path[-1]] = words[o:o + w].reshape(shp).copy()
     return proof
 
 
 class NativePlusProver:
     """PlusProver (plus.rs:15-108) as the C object lfplus_prover: the schedule PlusProver runs in Python (contexts, upload thread, from_f hints, device-resident
     accumulator, failed state) lives below the ABI; this class only marshals.  Unsharded, the accumulator always stays on the device (PlusProver.device_acc).
-    A = None: the commitment matrix is generated on the device from `seed` (PlusContext.generate_matrix).  prove() returns the FLAT proof (proof_from_flat)."""
+    A = None: the commitment matrix is generated on the device from `seed` (PlusContext.generate_matrix).  prove() returns the FLAT proof (proof_from_flat).
+    shape: a CCSShape -- the prover folds committed CCS instances over the shape's t matrices M (lfplus_prover_create_ccs) and its proofs have the CCS layout."""
 
-    def __init__(self, A, M, ncomp, params, transcript, device=0, seed=0):
-        self.params, self.transcript, self.nM, self.ncomp = params, transcript, len(M), int(ncomp)
+    def __init__(self, A, M, ncomp, params, transcript, device=0, seed=0, shape=None):
+        if shape is not None and not isinstance(shape, CCSShape):
+            raise LfPlusError(E_ARG, "NativePlusProver: shape must be a CCSShape")
+        self.params, self.transcript, self.nM, self.ncomp, self.shape = params, transcript, len(M), int(ncomp), shape
         self.h = C.c_void_p()
         self.nacc = self.nfresh = 0
         self.last = None         # (L, nfresh) of the last proof
@@ -1695,15 +1770,22 @@ class NativePlusProver:
         else:
             ap, self.n = None, int(keep[0][0].size - 1) if keep else 0
         self.kappa = int(params.lin.kappa)
-        rc = _nlib().lfplus_prover_create(int(device), C.byref(_cparams(params)), ap, int(seed) & (2**64 - 1), self.n, self.nM, rp, cp, vp, self.ncomp, transcript.h,
-                                          C.byref(self.h))
+        if shape is not None:
+            if self.nM != shape.t:
+                raise LfPlusError(E_ARG, f"NativePlusProver: the shape has {shape.t} matrices")
+            rc = _nlib().lfplus_prover_create_ccs(int(device), C.byref(_cparams(params)), ap, int(seed) & (2**64 - 1), self.n, C.byref(shape.desc()), rp, cp, vp, self.ncomp,
+                                                  transcript.h, C.byref(self.h))
+        else:
+            rc = _nlib().lfplus_prover_create(int(device), C.byref(_cparams(params)), ap, int(seed) & (2**64 - 1), self.n, self.nM, rp, cp, vp, self.ncomp, transcript.h,
+                                              C.byref(self.h))
         if rc:
             self.h = C.c_void_p()
-            raise LfPlusError(rc, "lfplus_prover_create: no usable HIP device, parameters outside the envelope (three R1CS matrices, n = 2^nvars), or the upload failed")
+            raise LfPlusError(rc, "lfplus_prover_create: no usable HIP device, parameters outside the envelope (three R1CS matrices or a CCS shape, n = 2^nvars), or the "
+                                  "upload failed")
 
     @staticmethod
-    def init(A, M, ncomp, params, transcript, device=0, seed=0):
-        return NativePlusProver(A, M, ncomp, params, transcript, device, seed)
+    def init(A, M, ncomp, params, transcript, device=0, seed=0, shape=None):
+        return NativePlusProver(A, M, ncomp, params, transcript, device, seed, shape)
 
     def last_error(self):
         return _nlib().lfplus_prover_last_error(self.h).decode() if self.h else ""
@@ -1782,7 +1864,7 @@ class NativePlusProver:
         if comp is not None:
             self.set_instances([ci.f for ci in comp], [ci.cm_f for ci in comp])
         L, nfresh = self.nacc + self.nfresh, self.nfresh
-        words = proof_len(self.params, self.n, self.nM, L, nfresh) if L else 0
+        words = proof_len(self.params, self.n, self.nM, L, nfresh, shape=self.shape) if L else 0
         out = np.zeros(max(words, 1), dtype=np.uint64)
         try:
             self._chk(_nlib().lfplus_prover_prove(self.h, out.ctypes.data_as(u64p), words))
@@ -1790,6 +1872,17 @@ class NativePlusProver:
             self._keep = None
         self.nacc, self.nfresh, self.last = 2, 0, (L, nfresh)
         return out
+
+    def check_fresh(self, bound=0):
+        """lfplus_prover_check_fresh: is every instance named by the last ingest / set_instances in its relation (ccs_check for a CCS prover, r1cs_check otherwise,
+        where the instance lives; cm_f when set_instances gave it; ||f||_inf < bound, 0: not checked) -> [(ok, failed, first_bad, absmax)] per instance.  Valid
+        between naming the instances and prove(); read-only"""
+        cnt = max(self.nfresh, 1)
+        ok, failed, fb, am = (C.c_int * cnt)(), (C.c_uint * cnt)(), (C.c_uint64 * cnt)(), (C.c_uint64 * cnt)()
+        rc = _nlib().lfplus_prover_check_fresh(self.h, int(bound), ok, failed, fb, am)
+        if rc not in (0, E_REJECT):
+            self._chk(rc)
+        return [(bool(ok[i]), int(failed[i]), int(fb[i]), int(am[i])) for i in range(self.nfresh)]
 
     def accumulator(self, out=None):
         """(F0, F1) of the last prove, read back from the device; out = (F0, F1) device arrays (n, 16), either may be None: copied there, device to device
@@ -1819,10 +1912,13 @@ class NativePlusProver:
 class NativePlusVerifier:
     """PlusVerifier (plus.rs:25-33, 110-146) through lfplus_verify: host only, on the flat proof.  The statement -- params, n, nM and per proof (L, nfresh) --
     is the verifier's own.  verify returns True, or False with .stage = (which proof, stage) named as PlusVerifier names them, ("malformed", message) for a
-    buffer that does not fit the statement; .which is the C index (i < nfresh, nfresh: cmproof, nfresh + 1: dproof, -1: malformed)"""
+    buffer that does not fit the statement; .which is the C index (i < nfresh, nfresh: cmproof, nfresh + 1: dproof, -1: malformed).  shape: a CCSShape -- the
+    statement is about committed CCS instances over the shape's t matrices and the proofs have the CCS layout (lfplus_verify_ccs)"""
 
-    def __init__(self, A, M, params, transcript):
-        self.params, self.transcript, self.nM = params, transcript, len(M)
+    def __init__(self, A, M, params, transcript, shape=None):
+        if shape is not None and (not isinstance(shape, CCSShape) or shape.t != len(M)):
+            raise LfPlusError(E_ARG, "NativePlusVerifier: shape must be a CCSShape over len(M) matrices")
+        self.params, self.transcript, self.nM, self.shape = params, transcript, len(M), shape
         shape = tuple(A) if isinstance(A, tuple) else np.asarray(A).shape          # (kappa, n, 16): the matrix or just its shape
         if len(shape) != 3 or shape[2] != D or shape[0] != params.lin.kappa or shape[1] < 2 or shape[1] & (shape[1] - 1):
             raise LfPlusError(E_ARG, "NativePlusVerifier: A must be (kappa, n = 2^nvars, 16) with kappa = params.lin.kappa")
@@ -1830,14 +1926,18 @@ class NativePlusVerifier:
         self.stage, self.which, self.code = None, None, 0
 
     @staticmethod
-    def init(A, M, params, transcript):
-        return NativePlusVerifier(A, M, params, transcript)
+    def init(A, M, params, transcript, shape=None):
+        return NativePlusVerifier(A, M, params, transcript, shape)
 
     def verify(self, proof, L, nfresh):
         w, p = (None, None) if proof is None else _w(np.asarray(proof).reshape(-1))
         which, st = C.c_int(), C.c_int()
-        rc = _nlib().lfplus_verify(C.byref(_cparams(self.params)), self.n, self.nM, int(L), int(nfresh), self.transcript.h, p, 0 if w is None else w.size,
-                                   C.byref(which), C.byref(st))
+        if self.shape is not None:
+            rc = _nlib().lfplus_verify_ccs(C.byref(_cparams(self.params)), self.n, C.byref(self.shape.desc()), int(L), int(nfresh), self.transcript.h, p,
+                                           0 if w is None else w.size, C.byref(which), C.byref(st))
+        else:
+            rc = _nlib().lfplus_verify(C.byref(_cparams(self.params)), self.n, self.nM, int(L), int(nfresh), self.transcript.h, p, 0 if w is None else w.size,
+                                       C.byref(which), C.byref(st))
         self.code, self.which = rc, which.value
         if rc == 0:
             self.stage = None
