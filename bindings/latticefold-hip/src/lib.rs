@@ -15,6 +15,7 @@
 //! | `DecompositionProver::prove` `nifs/decomposition/structs.rs:48-64`              | `impl DecompositionProver for HipDecompositionProver` |
 //! | `FoldingProver::prove` `nifs/folding/structs.rs:43-70`                          | `impl FoldingProver for HipFoldingProver` |
 //! | `NIFSProver::prove` `nifs.rs:48-103`                                            | [`HipNIFSProver::prove`] (same signature) and [`HipNIFSProver::prove_resident`] |
+//! | `NIFSProver::prove` in a loop `nifs/tests.rs:58-117`, `examples/e2e.rs`        | [`HipChainProver`] (the accumulator stays on the device; borrows `&HipContext`) |
 //!
 //! Two ways in.  (1) The trait methods take the reference's host types (`&Witness<NTT>`, `&CCS<NTT>`, `&AjtaiCommitmentScheme<NTT>`); every call marshals them
 //! (Montgomery -> canonical words: `into_bigint`, O(N), outside the kernels) into the session installed with [`HipSession::install`] -- the CCS and the Ajtai
@@ -32,6 +33,9 @@
 
 /// LatticeFold+ (`crates/latticefold-plus`): `HipPlusProver` / `HipPlusVerifier` over the prover and verifier objects of include/lfplus.h
 pub mod plus;
+/// The chained NIFS prover object of include/lfhip_prover.h: `HipChainProver`, a safe owner with `Drop` that borrows its context
+pub mod chain;
+pub use chain::HipChainProver;
 
 use core::marker::PhantomData;
 use std::sync::{Arc, Mutex, OnceLock};

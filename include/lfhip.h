@@ -473,6 +473,10 @@ int lf_proof_deserialize(const lf_params *, int ring, const uint8_t *in, size_t 
  * lf_mlsumcheck_*, in a file of their own for the same reason ------------ */
 #include "lfhip_sumcheck.h"
 
+/* ---- NIFSProver::prove chained (nifs/tests.rs:58-117, examples/e2e.rs): the prover object lf_prover_*, fourteen more entry points, in a file of their own for
+ * the same reason ------------ */
+#include "lfhip_prover.h"
+
 #ifdef __cplusplus
 }
 #endif

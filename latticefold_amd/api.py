@@ -223,6 +223,25 @@ def _lib():
         L.lf_mlsumcheck_prove.argtypes = [vp, vp, vpp, u64p, u64p, u64p, u64p]
         L.lf_mlsumcheck_prove_device.argtypes = [vp, vp, vpp, vp, u64p, u64p, u64p]
         L.lf_mlsumcheck_verify.argtypes = [C.c_int, vp, C.c_uint32, C.c_uint32, u64p, u64p, u64p, u64p]
+        # the chained prover object (include/lfhip_prover.h); the _dev arrays are plain addresses
+        uip = C.POINTER(C.c_uint)
+        L.lf_prover_create.argtypes = [vp, C.c_uint, C.POINTER(vp)]
+        L.lf_prover_destroy.argtypes = [vp]
+        L.lf_prover_destroy.restype = None
+        L.lf_prover_last_error.argtypes = [vp]
+        L.lf_prover_last_error.restype = C.c_char_p
+        L.lf_prover_init.argtypes = [vp, vp, u64p, u64p, u64p, u64p]
+        L.lf_prover_resume.argtypes = [vp, u64p, u64p]
+        L.lf_prover_resume_dev.argtypes = [vp, u64p, vp]
+        L.lf_prover_ingest.argtypes = [vp, u64p, u64p]
+        L.lf_prover_ingest_dev.argtypes = [vp, vp, u64p]
+        L.lf_prover_check_fresh.argtypes = [vp, C.c_uint64, uip, u64p]
+        L.lf_prover_prove.argtypes = [vp, vp, u64p, u64p, u64p]
+        L.lf_prover_accumulator.argtypes = [vp, u64p, u64p]
+        L.lf_prover_accumulator_dev.argtypes = [vp, u64p, vp]
+        L.lf_prover_decide.argtypes = [vp, C.c_uint64, uip]
+        L.lf_prover_steps.argtypes = [vp]
+        L.lf_prover_steps.restype = C.c_uint64
         _LIB = L
     return _LIB
 
@@ -245,7 +264,8 @@ def abi_version():
 
 
 def exported_symbols(header="lfhip.h"):
-    """Every symbol include/lfhip.h declares (used by the CPU-side ABI test); header="lfhip_parts.h" / "lfhip_sumcheck.h": the ones of a file it includes."""
+    """Every symbol include/lfhip.h declares (used by the CPU-side ABI test); header="lfhip_parts.h" / "lfhip_sumcheck.h" / "lfhip_prover.h": the ones of a
+    file it includes."""
     import re
     hdr = open(os.path.join(_HERE, "..", "include", header)).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
@@ -993,6 +1013,140 @@ class NIFSProver:
         _chk(_lib().lf_fold_step(ctx.h, transcript.h, pa, w_acc.h, pb, w_i.h, lc.ctypes.data_as(u64p), C.byref(h),
                                  pr.ctypes.data_as(u64p)), "lf_fold_step")
         return lc, Witness(ctx, h), pr
+
+
+class ChainProverError(LfError):
+    """an lf_prover_* call failed: .code is the LF_ERR_* code, .detail the text of lf_prover_last_error"""
+
+    def __init__(self, code, where, detail=""):
+        super().__init__(code, where)
+        self.detail = detail
+        if detail:
+            self.args = (f"{self.args[0]} -- {detail}",)
+
+
+class NIFSChainProver:
+    """The chained NIFS prover object (lf_prover_*, include/lfhip_prover.h): NIFSProver::prove made a chain that owns its accumulator on the device.
+    create -> init | resume -> (ingest -> [check_fresh] -> prove)* ; accumulator / decide / steps at any point with an accumulator; close.
+    w_ccs, f_ntt: numpy, or a device array (a torch tensor) for the `_dev` entry points.  The context is borrowed: close the prover before it."""
+    COMMIT_INLINE = 1   # LF_PROVER_COMMIT_INLINE
+
+    def __init__(self, ctx, flags=0):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        self._keep = None
+        self.last_first_bad = None
+        rc = _lib().lf_prover_create(ctx.h, int(flags), C.byref(self.h))
+        if rc != 0:
+            self.h = None
+            raise ChainProverError(rc, "lf_prover_create")
+
+    create = classmethod(lambda cls, ctx, flags=0: cls(ctx, flags))
+
+    def last_error(self):
+        return _lib().lf_prover_last_error(self.h).decode()
+
+    def _chk(self, rc, where, ok=()):
+        if rc != 0 and rc not in ok:
+            raise ChainProverError(rc, where, self.last_error())
+        return rc
+
+    def init(self, transcript, w_ccs, x_ccs):
+        """first accumulator = the linearization of (x_ccs, w_ccs) on `transcript` -> (LCCCS flat, linearization proof flat)"""
+        ctx, prm = self.ctx, self.ctx.params
+        (a, pw), (b, px) = _a64(w_ccs), _a64(x_ccs)
+        assert a.size == prm.wit_len * ctx.RE and b.size == prm.l * ctx.RE
+        lc = np.zeros((ctx.lcccs_len, ctx.RE), dtype=np.uint64)
+        pr = np.zeros((prm.s * (prm.d + 2) + ctx.TAU + prm.t, ctx.RE), dtype=np.uint64)
+        self._chk(_lib().lf_prover_init(self.h, transcript.h, pw, px, lc.ctypes.data_as(u64p), pr.ctypes.data_as(u64p)), "lf_prover_init")
+        return lc, pr
+
+    def resume(self, lcccs, f_ntt):
+        """take up a chain again from (LCCCS, folded witness f in NTT form: numpy or a device array)"""
+        a, pl = _a64(lcccs)
+        assert a.size == self.ctx.lcccs_len * self.ctx.RE
+        if is_device_array(f_ntt):
+            assert f_ntt.numel() == self.ctx.N * self.ctx.RE
+            self._chk(_lib().lf_prover_resume_dev(self.h, pl, _dev(self.ctx, f_ntt)), "lf_prover_resume_dev")
+            return
+        f, pf = _a64(f_ntt)
+        assert f.size == self.ctx.N * self.ctx.RE
+        self._chk(_lib().lf_prover_resume(self.h, pl, pf), "lf_prover_resume")
+
+    def ingest(self, w_ccs, x_ccs):
+        """names the fresh instance of the next prove and returns at once (a device w_ccs: blocking).  The host words are kept alive until that prove"""
+        b, px = _a64(x_ccs)
+        assert b.size == self.ctx.params.l * self.ctx.RE
+        if is_device_array(w_ccs):
+            assert w_ccs.numel() == self.ctx.params.wit_len * self.ctx.RE
+            self._chk(_lib().lf_prover_ingest_dev(self.h, _dev(self.ctx, w_ccs), px), "lf_prover_ingest_dev")
+            return
+        a, pw = _a64(w_ccs)
+        assert a.size == self.ctx.params.wit_len * self.ctx.RE
+        keep, self._keep = self._keep, a     # (a refused ingest drops the instance that was pending: its words may go once the call is back)
+        try:
+            self._chk(_lib().lf_prover_ingest(self.h, pw, px), "lf_prover_ingest")
+        except ChainProverError:
+            self._keep = None
+            raise
+        finally:
+            del keep
+
+    def check_fresh(self, bound=0):
+        """R_CCCS of the pending instance: the set of failing components among "ccs", "norm" (the commitment is the prover's own); the first bad row of the CCS
+        (m when it holds) is left in .last_first_bad"""
+        f, fb = C.c_uint(), C.c_uint64()
+        rc = _lib().lf_prover_check_fresh(self.h, int(bound), C.byref(f), C.cast(C.byref(fb), u64p))
+        if rc not in (0, LF_ERR_REJECT):
+            self._keep = None
+        self._chk(rc, "lf_prover_check_fresh", ok=(LF_ERR_REJECT,))
+        self.last_first_bad = fb.value
+        return {name for name, bit in REL_BITS.items() if f.value & bit}
+
+    def prove(self, transcript):
+        """NIFSProver::prove of (accumulator, pending instance) -> (fresh CCCS cm || x_ccs, folded LCCCS flat, LFProof flat); the folded pair is the accumulator"""
+        ctx = self.ctx
+        cc = np.zeros((ctx.cccs_len, ctx.RE), dtype=np.uint64)
+        lc = np.zeros((ctx.lcccs_len, ctx.RE), dtype=np.uint64)
+        pr = np.zeros((ctx.proof_len, ctx.RE), dtype=np.uint64)
+        rc = _lib().lf_prover_prove(self.h, transcript.h, cc.ctypes.data_as(u64p), lc.ctypes.data_as(u64p), pr.ctypes.data_as(u64p))
+        self._keep = None
+        self._chk(rc, "lf_prover_prove")
+        return cc, lc, pr
+
+    def accumulator(self, out=None):
+        """(LCCCS flat, f in NTT form); out: a device array (N, d) to write f into (lf_prover_accumulator_dev)"""
+        ctx = self.ctx
+        lc = np.zeros((ctx.lcccs_len, ctx.RE), dtype=np.uint64)
+        if out is not None:
+            if not is_device_array(out) or tuple(out.shape) != (ctx.N, ctx.RE):
+                raise ValueError(f"out must be a device array of shape ({ctx.N}, {ctx.RE})")
+            self._chk(_lib().lf_prover_accumulator_dev(self.h, lc.ctypes.data_as(u64p), _dev(ctx, out)), "lf_prover_accumulator_dev")
+            return lc, out
+        f = np.zeros((ctx.N, ctx.RE), dtype=np.uint64)
+        self._chk(_lib().lf_prover_accumulator(self.h, lc.ctypes.data_as(u64p), f.ctypes.data_as(u64p)), "lf_prover_accumulator")
+        return lc, f
+
+    def decide(self, bound=0):
+        """R_LCCCS of the accumulator: the set of failing components among "cm", "u", "v", "norm"; empty when it holds"""
+        f = C.c_uint()
+        self._chk(_lib().lf_prover_decide(self.h, int(bound), C.byref(f)), "lf_prover_decide", ok=(LF_ERR_REJECT,))
+        return {name for name, bit in REL_BITS.items() if f.value & bit}
+
+    def steps(self):
+        return int(_lib().lf_prover_steps(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            _lib().lf_prover_destroy(self.h)
+            self.h = None
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class NIFSVerifier:

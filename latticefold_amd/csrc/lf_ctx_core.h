@@ -43,6 +43,7 @@ struct CtxCoreBase {
     lf_params P{};
     size_t N = 0, m = 0, n = 0;
     std::vector<uint32_t *> d_rowptr, d_col, d_colptr, d_rowidx;
+    uint64_t setup_gen = 0;   // counts the times the matrix or the constraint system was dropped (a reload drops first): how an lf_prover sees a reload of equal shape
     // sumcheck ABI state: linearization (lf_sumcheck_lin_*) and folding (lf_sumcheck_fold_*)
     int sc_round = -1, sc_cur = 0;
     size_t sc_n = 0;
@@ -206,6 +207,7 @@ struct CtxCoreBase {
     }
     void drop_matrix() {   // the context holds no matrix afterwards
         if (dAb) (void)hipFree(dAb);
+        setup_gen++;
         dAb = nullptr;
         A_loaded = false;
         kappa = i8_nch = i8_kc = 0;
@@ -257,6 +259,7 @@ struct CtxCore : CtxCoreBase {
         for (auto q : d_valT) (void)hipFree(q);
         d_rowptr.clear(); d_col.clear(); d_val.clear(); d_colptr.clear(); d_rowidx.clear(); d_valT.clear();
         have_ccs = false;
+        setup_gen++;
     }
     // release everything the core owns (both lanes' streams are idle)
     void release_core() {

@@ -1118,22 +1118,24 @@ struct ring_ops<Ring<C>> {
     // ---- witnesses ----
     static int witness_from_coef_table(C *c, const W *coef_dev /* [RE][N] */, lf_witness **out, DevIo<C> *io = nullptr) {
         int32_t *pl;
-        HIPCHK(lf_dev_malloc(&pl, c->N * RE * 4));
+        const size_t pl_bytes = c->N * RE * 4;
+        RET(lf_planes_alloc(R::owner(c), pl_bytes, &pl));   // the recycle pool: a chain in steady state takes the planes its last step gave back
+        auto drop = [&] { lf_planes_release(R::owner(c), pl_bytes, pl); };
         int *viol;
-        if (c->tbuf("small_dev", 4096, (u64 **)&viol) != LF_OK) { (void)hipFree(pl); return LF_ERR_HIP; }
+        if (c->tbuf("small_dev", 4096, (u64 **)&viol) != LF_OK) { drop(); return LF_ERR_HIP; }
         (void)hipMemsetAsync(viol, 0, 4, c->stream());
         launch_coef_to_i32(coef_dev, pl, c->N, (u32)(c->P.B / 2), viol, c->stream());
         int hv = 0;
         if ((io && io->fetch() != LF_OK) || hipMemcpyAsync(&hv, viol, 4, hipMemcpyDeviceToHost, c->stream()) != hipSuccess ||
             hipStreamSynchronize(c->stream()) != hipSuccess) {
-            (void)hipFree(pl);
+            drop();
             return LF_ERR_HIP;
         }
-        if (io && io->bad()) { (void)hipFree(pl); return LF_ERR_INVALID; }   // device input with a word >= p: no handle
+        if (io && io->bad()) { drop(); return LF_ERR_INVALID; }   // device input with a word >= p: no handle
         // bit 0: a coefficient outside the bound; bit 1 (Goldilocks, B = 2^32): +2^31, which an int32 plane cannot hold.  The BabyBear kernel writes bit 0 only
         // (B <= 2^30), so the one expression serves both rings
-        if (hv) { (void)hipFree(pl); return (hv & 1) ? LF_ERR_NORM : LF_ERR_UNSUPPORTED; }
-        *out = new lf_witness{R::owner(c), pl, c->N, c->device, c->N * RE * 4};
+        if (hv) { drop(); return (hv & 1) ? LF_ERR_NORM : LF_ERR_UNSUPPORTED; }
+        *out = new lf_witness{R::owner(c), pl, c->N, c->device, pl_bytes};
         return LF_OK;
     }
     // Witness::from_w_ccs, arith.rs:230-248: ICRT -> gadget_decompose(B, L); on the calling thread's lane (its stream, its buffers)

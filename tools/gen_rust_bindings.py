@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """Generates the raw Rust binding of the C ABI (`latticefold-hip-sys/src/lib.rs`) from include/lfhip.h and include/lfplus.h, and its modules `parts`
 (`src/parts.rs`) from include/lfhip_parts.h, the file lfhip.h includes for the entry points of the decomposed witnesses, and `sumcheck` (`src/sumcheck.rs`)
-from include/lfhip_sumcheck.h, the one for the generic sumcheck.
+from include/lfhip_sumcheck.h, the one for the generic sumcheck, and `prover` (`src/prover.rs`) from include/lfhip_prover.h, the one for the chained prover object.
 
     python tools/gen_rust_bindings.py            print the binding
     python tools/gen_rust_bindings.py --write    rewrite bindings/latticefold-hip-sys/src/lib.rs and the block between the
-                                                 GENERATED markers of INTEGRATION.md; the same for src/parts.rs, src/sumcheck.rs and their markers
+                                                 GENERATED markers of INTEGRATION.md; the same for src/parts.rs, src/sumcheck.rs, src/prover.rs and their markers
 
 The reference is safe Rust with `#![forbid(unsafe_code)]` (crates/latticefold/src/lib.rs:4): the `extern "C"` block lives in a new
 `-sys` crate.  No Rust toolchain exists in the build image, so the text is derived mechanically from the headers (every prototype, the
@@ -26,12 +26,16 @@ PARTS_BEGIN, PARTS_END = "<!-- BEGIN GENERATED BINDING: parts (tools/gen_rust_bi
 SUMCHECK_HEADER = "include/lfhip_sumcheck.h"
 SUMCHECK_OUT = os.path.join(ROOT, "bindings", "latticefold-hip-sys", "src", "sumcheck.rs")
 SUMCHECK_BEGIN, SUMCHECK_END = "<!-- BEGIN GENERATED BINDING: sumcheck (tools/gen_rust_bindings.py) -->", "<!-- END GENERATED BINDING: sumcheck -->"
+PROVER_HEADER = "include/lfhip_prover.h"
+PROVER_OUT = os.path.join(ROOT, "bindings", "latticefold-hip-sys", "src", "prover.rs")
+PROVER_BEGIN, PROVER_END = "<!-- BEGIN GENERATED BINDING: prover (tools/gen_rust_bindings.py) -->", "<!-- END GENERATED BINDING: prover -->"
 
 SCALARS = {
     "int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "char": "c_char", "float": "f32", "double": "f64", "void": "c_void",
     "size_t": "usize", "uint64_t": "u64", "uint32_t": "u32", "uint8_t": "u8", "int8_t": "i8", "int32_t": "i32", "int64_t": "i64",
 }
 OPAQUE = ["lf_ctx", "lf_witness", "lf_witness_job", "lf_transcript", "lfplus_ctx", "lfplus_transcript", "lfplus_prover"]
+PROVER_OPAQUE = ["lf_prover"]     # declared by module `prover`, not by the crate root
 KEYWORDS = {"in": "inp", "type": "ty", "ref": "r", "fn": "f", "mod": "m", "box": "b", "use": "u", "loop": "lp", "match": "mt", "move": "mv", "self": "this"}
 
 
@@ -57,7 +61,7 @@ def rust_type(ctype):
     name = " ".join(base)
     if name in SCALARS:
         r = SCALARS[name]
-    elif name in OPAQUE or name in ("lf_params", "lfplus_params", "lf_vpoly", "lfplus_vpoly", "lfplus_ccs"):
+    elif name in OPAQUE or name in PROVER_OPAQUE or name in ("lf_params", "lfplus_params", "lf_vpoly", "lfplus_vpoly", "lfplus_ccs"):
         r = name
     elif name in ("lf_exchange_fn", "lfplus_exchange_fn"):
         r = "lf_exchange_fn"
@@ -78,11 +82,11 @@ def split_params(s):
     for i, p in enumerate(x.strip() for x in s.split(",")):
         m = re.match(r"^(.*?)([A-Za-z_][A-Za-z_0-9]*)?$", p)
         ctype, name = m.group(1).strip(), m.group(2)
-        if name in SCALARS or name in OPAQUE or name in ("lf_params", "lfplus_params", "lf_vpoly", "lfplus_vpoly", "lfplus_ccs", "lf_exchange_fn", "lfplus_exchange_fn", "unsigned", "const") or not ctype:   # unnamed parameter
+        if name in SCALARS or name in OPAQUE or name in PROVER_OPAQUE or name in ("lf_params", "lfplus_params", "lf_vpoly", "lfplus_vpoly", "lfplus_ccs", "lf_exchange_fn", "lfplus_exchange_fn", "unsigned", "const") or not ctype:   # unnamed parameter
             ctype, name = p, None
         if name is None:
             base = re.findall(r"[A-Za-z_][A-Za-z_0-9]*", ctype)[-1]
-            name = {"lf_ctx": "ctx", "lf_transcript": "t", "lf_witness": "w", "lf_params": "p", "lf_vpoly": "poly", "lfplus_ctx": "ctx", "lfplus_prover": "prover"}.get(base, f"a{i}")
+            name = {"lf_ctx": "ctx", "lf_transcript": "t", "lf_witness": "w", "lf_params": "p", "lf_vpoly": "poly", "lfplus_ctx": "ctx", "lfplus_prover": "prover", "lf_prover": "prover"}.get(base, f"a{i}")
         out.append((KEYWORDS.get(name, name), rust_type(ctype)))
     return out
 
@@ -155,7 +159,9 @@ def generate():
         L += ["}", ""]
     L += ["/// include/lfhip_parts.h (included by lfhip.h): the decomposed witnesses as handles -- `parts::lf_witness_decompose`, ...", "pub mod parts;",
           "/// include/lfhip_sumcheck.h (included by lfhip.h): MLSumcheck over any sum of products of MLE tables -- `sumcheck::lf_mlsumcheck_prove`, ...",
-          "pub mod sumcheck;", ""]
+          "pub mod sumcheck;",
+          "/// include/lfhip_prover.h (included by lfhip.h): the chained NIFS prover object -- `prover::lf_prover_create`, `prover::lf_prover_prove`, ...",
+          "pub mod prover;", ""]
     return "\n".join(L), allfns
 
 
@@ -192,6 +198,25 @@ def generate_sumcheck():
     return "\n".join(L), [f[0] for f in fns]
 
 
+def generate_prover():
+    """src/prover.rs: the handle, the flag and the entry points of include/lfhip_prover.h, over the types of the crate root"""
+    enums, fns = parse(PROVER_HEADER)
+    L = [f"// GENERATED by tools/gen_rust_bindings.py from {PROVER_HEADER} -- do not edit.",
+         "// Module `prover` of latticefold-hip-sys: NIFSProver::prove chained -- an object that owns the accumulator on the device (lf_prover_*).",
+         "use core::ffi::{c_char, c_int, c_uint};", "",
+         "use super::{lf_ctx, lf_transcript};", ""]
+    for o in PROVER_OPAQUE:
+        L.append(f"#[repr(C)] pub struct {o} {{ _p: [u8; 0] }}")
+    for name, val in enums:
+        L.append(f"pub const {name}: c_uint = {val};")
+    L += ["", '#[link(name = "lfhip")]', 'extern "C" {']
+    for name, params, ret in fns:
+        ps = ", ".join(f"{n}: {t}" for n, t in params)
+        L.append(f"    pub fn {name}({ps})" + (f" -> {ret}" if ret else "") + ";")
+    L += ["}", ""]
+    return "\n".join(L), [f[0] for f in fns]
+
+
 def main():
     text, fns = generate()
     if "--write" in sys.argv:
@@ -216,11 +241,19 @@ def main():
             a, b = doc.index(SUMCHECK_BEGIN) + len(SUMCHECK_BEGIN), doc.index(SUMCHECK_END)
             open(DOC, "w").write(doc[:a] + "\n```rust\n" + stext + "```\n" + doc[b:])
         print(f"{len(sfns)} functions -> {os.path.relpath(SUMCHECK_OUT, ROOT)}")
+        rtext, rfns = generate_prover()
+        open(PROVER_OUT, "w").write(rtext)
+        doc = open(DOC).read()
+        if PROVER_BEGIN in doc and PROVER_END in doc:
+            a, b = doc.index(PROVER_BEGIN) + len(PROVER_BEGIN), doc.index(PROVER_END)
+            open(DOC, "w").write(doc[:a] + "\n```rust\n" + rtext + "```\n" + doc[b:])
+        print(f"{len(rfns)} functions -> {os.path.relpath(PROVER_OUT, ROOT)}")
         print(f"{len(fns)} functions -> {os.path.relpath(OUT, ROOT)}" + (", INTEGRATION.md" if BEGIN in doc else ""))
     else:
         sys.stdout.write(text)
         sys.stdout.write(generate_parts()[0])
         sys.stdout.write(generate_sumcheck()[0])
+        sys.stdout.write(generate_prover()[0])
 
 
 if __name__ == "__main__":
