@@ -114,6 +114,7 @@ struct Tunables {
     bool lin_no_small = false;       // LF_LIN_NO_SMALL: (BabyBear) small linearization rounds as separate fix / round / reduce launches
     size_t dot_min = 4096;           // LF_DOT_MIN: columns from which the int8 form of the inner products is used
     bool dot_valu = false;           // LF_DOT_VALU: u_s / eta inner products on the 64-bit VALU kernel (k_dot_batch) instead of the int8 matrix cores
+    bool q_two_pass = false;         // LF_Q_TWO_PASS: q_j = M_j^T eq as 64-bit words (k_spmv_t_eq per matrix) and k_dot_pack_y behind them, instead of the one fused pass k_q_pack_i8
     bool fold_witness_valu = false;  // LF_FOLD_WITNESS_VALU: compute_f_0 on the nibble-table kernel (k_fold_witness) instead of the int8 matrix cores (lf_fold_i8.hip)
     bool zk_valu = false;            // LF_ZK_VALU: the z_k build on the butterfly kernel (k_recompose_crt_b4) instead of the int8 matrix cores (lf_zk_i8.hip)
     bool fold_no_sv = false;         // LF_FOLD_NO_SV: rounds 1-3 of the folding sumcheck on the VALU kernels instead of the int8 matrix-core GEMMs (lf_sv_rounds.hip)
@@ -144,6 +145,7 @@ struct Tunables {
         t.no_tail = getenv("LF_NO_TAIL") != nullptr;
         t.fold_no_sv = getenv("LF_FOLD_NO_SV") != nullptr;
         t.dot_valu = getenv("LF_DOT_VALU") != nullptr;
+        t.q_two_pass = getenv("LF_Q_TWO_PASS") != nullptr;
         t.fold_witness_valu = getenv("LF_FOLD_WITNESS_VALU") != nullptr;
         t.zk_valu = getenv("LF_ZK_VALU") != nullptr;
         if ((e = getenv("LF_DOT_MIN"))) t.dot_min = (size_t)atoll(e);

@@ -394,13 +394,15 @@ struct FoldStep {
     void fix_special(u32 round, Fq3Const r, u64 *dst, hipStream_t sg);
     void set_tables(u64 *dst, size_t nn);
     // evaluations, finish
-    int eval_buffers();
+    int eval_buffers(bool q_words = true);
     int gather_q(hipStream_t s1f);
     int finish(u64 *lcccs_out, lf_witness **w_out, const std::function<int(const std::vector<int8_t> &rho8, int8_t *d_rho, int32_t *npl)> &fold_witness);
 };
 int sb_fold_round_abi(lf_ctx *c, const u64 *t5, const u64 *F, size_t n, const Fq3Const *d_mu, u64 *evals_out);
 int dot_batch_dev(lf_ctx *c, const u64 *X, size_t ldx, u32 na, const u64 *Y, size_t ldy, u32 nb, size_t n, u64 *dpart, u64 *od, hipStream_t st = nullptr,
                          const char *tag = "", unsigned char *yb_pre = nullptr);
+bool q_pack_takes(lf_ctx *c, const u64 *X, size_t ldx, u32 na);
+int q_pack_dev(lf_ctx *c, const u64 *X, const u64 *eq, unsigned char **yb);
 int coef_eval_dev(lf_ctx *c, const int32_t *planes, size_t n, const u64 *eq, size_t ldeq, u32 K, int mode_bits, u64 *partial, u64 *od, size_t ldp,
                          const lf_witness *wit = nullptr);
 int lin_tail_rounds(lf_ctx *c, Transcript &tr, const u64 *cur, const u64 *cure, size_t n, u64 *tout, u64 *partial, u32 round, Fq3 *point,

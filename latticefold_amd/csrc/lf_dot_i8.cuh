@@ -8,6 +8,7 @@
 #include "lf_i8_mma.cuh"
 
 namespace i8mma {
+#if defined(__HIPCC__)   // (the kernels: not for the stand-alone host program that includes this file for DotPlan, lf_q_pack_selftest.cpp)
 // W = word of the ring (D = sizeof(W) balanced digits), COMP = words per slot (3 / 9): 8 COMP word planes per vector, 3 COMP D digit rows per slot.
 // YB[slot][(b*COMP + cq)*D + v][.] = digit v of Y_b[COMP slot + cq][i] in the operand order of a K-step (kstep_col) per block of 64 columns, zero beyond n and
 // below `lead` (those columns belong to the neighbour slice); ldq columns per row; wave = (word plane, 8 blocks of 64 columns)
@@ -91,6 +92,7 @@ __global__ void __launch_bounds__(256) k_dot_sum(const int32_t *part, uint32_t c
     for (uint32_t ch = 0; ch < chunks; ch++) s += part[((size_t)unit * chunks + ch) * PER + e];
     tot[(size_t)unit * PER + e] = s;
 }
+#endif
 // The column plan of one call.  A slice whose first word is not aligned for the GEMM kernel's two-word loads (a rank's slice of a sharded step) starts `lead` = 1
 // column early, and that column gets zero digits on the Y side.  `want` chunks of K-steps fill the chip in one batch (one wave per SIMD); the chunk count is not
 // monotone in the step count (80 steps -> 40 chunks, 81 -> 27), so the scratch is sized for `want`.

@@ -13,6 +13,7 @@
 #include "lf_field.cuh"
 #include "lf_kernels.h"
 #include "lf_dot_i8.cuh"
+#include "lf_dot_plan.h"
 
 namespace lf {
 using namespace i8mma;
@@ -118,15 +119,77 @@ __global__ void __launch_bounds__(32) k_dot_i8_finish(const long long *tot, u32 
 }
 
 size_t dot_i8_yb_bytes(size_t n) { return (size_t)8 * 72 * (cdiv(n, 64) * 64) + 64; }
-constexpr u32 DOT_CHUNKS = 40;   // 24 units x 40 chunks = 240 blocks of 4 waves: ONE batch on 256 CUs at one wave per SIMD (44 chunks = 264 blocks ran as two batches: 2x the time)
 size_t dot_i8_part_words(size_t) { return (size_t)24 * DOT_CHUNKS * 10240; }   // (the largest chunk count: see DotPlan)
 size_t dot_i8_tot_words() { return (size_t)24 * 10240; }
 // the Y digits alone (k_dot_pack_y), for a following launch_dot_batch_i8(.., y_packed = true) on vectors X with the same alignment: two X sets against the
 // same Y (the eta inner products of the two sides of a fold step) pack it once.  Result: lf_i8_launch.h.
 int launch_dot_pack_y(const u64 *X, const u64 *Y, size_t ldy, u32 nb, size_t n, unsigned char *YB, hipStream_t s) {
     DotPlan p;
-    if (nb < 1 || nb > 3 || !p.make(X, n, DOT_CHUNKS)) return I8_ERR_SHAPE;
+    if (!dot_i8_shape(X, 2, 1, nb, n, &p)) return I8_ERR_SHAPE;   // (the Y side alone: na and ldx are the following launch's)
     hipLaunchKernelGGL((k_dot_pack_y<u64, 3>), dim3(p.pack_blocks(nb, 24)), dim3(256), 0, s, Y - p.lead, ldy, nb, p.n, p.lead, p.ldq, YB);
+    return i8_launched();
+}
+// q_j = M_j^T eq(r) for the nm <= 3 matrices of a step, written ONLY as the packed digits YB that k_dot_i8 reads: the gather of k_spmv_t_eq (lf_kernels.hip: the
+// same CSC walk, the same product and the same order of the sums, so the words are the ones that kernel stores) and the digit cut of k_dot_pack_y in one pass --
+// the words, 151 MB at 2^18 columns x 3 matrices, are never stored and never read back.
+// block = (one K-step block of 64 columns, one matrix: blockIdx.y).  Gather: thread = (column cl of 32, slot) as in k_spmv_t_eq, the two halves of the block in
+// turn.  The balanced words cross LDS as sm[word plane][column] (rows of 66 words: the eight slots of a column -- planes 3 apart -- land on eight different
+// bank quads, ds_write_b64 conflict-free).  Cut: thread = (word plane, four operand positions 4 q .. 4 q + 3), which hold columns c, c + 1, c + 8, c + 9 with
+// c = kstep_col(4 q): two 16-byte LDS reads, and per digit v one 32-bit word (gather_bytes) into digit row v -- 16 lanes store one 64-byte row segment.
+// Columns >= n and empty columns give zero digits.
+// (All nm matrices in one block -- 38 KB of LDS, 125 to 188 registers, two to four blocks per CU -- took 650 to 720 us next to the commit, on the 32 CUs it leaves,
+// where the three k_spmv_t_eq and k_dot_pack_y take 470; with the first non-zero of the six columns of a thread loaded side by side it was no faster.)
+struct QPackArgs {
+    const u32 *colptr[3], *rowidx[3];
+    const u64 *val[3], *eq;
+    size_t m, n, ldq;      // ldq: n padded to blocks of 64, the row length of YB
+    unsigned char *YB;     // [8][72][ldq]
+};
+template <bool NU>
+__global__ void __launch_bounds__(256) k_q_pack_i8(DevCrt t, QPackArgs a) {
+    const u32 cl = threadIdx.x >> 3, slot = threadIdx.x & 7, j = blockIdx.y;
+    const size_t cb = (size_t)blockIdx.x * 64;
+    __shared__ __attribute__((aligned(16))) u64 sm[24][66];
+    const u32 *colptr = a.colptr[j], *rowidx = a.rowidx[j];
+    const u64 *val = a.val[j];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const size_t c = cb + 32 * h + cl;
+        Fq3 acc = fq3_zero();
+        if (c < a.n)
+            for (u32 k = colptr[c]; k < colptr[c + 1]; k++) {
+                const u64 *v = val + (size_t)k * 24 + 3 * slot;
+                const size_t r = rowidx[k];
+                acc = fq3_add(acc, fq3_mul<NU>(fq3_make(v[0], v[1], v[2]), fq3_make(a.eq[r], a.eq[a.m + r], a.eq[2 * a.m + r]), t.nu));
+            }
+#pragma unroll
+        for (int cq = 0; cq < 3; cq++) sm[3 * slot + cq][32 * h + cl] = balanced_bytes(acc.c[cq]);
+    }
+    __syncthreads();
+    for (u32 task = threadIdx.x; task < 24 * 16; task += 256) {
+        const u32 pos0 = 4 * (task & 15), plane = task >> 4;
+        const u32 c = kstep_col(pos0);   // even; positions pos0 + 2, pos0 + 3 hold columns c + 8, c + 9
+        const ulonglong2 lo = *(const ulonglong2 *)&sm[plane][c], hi = *(const ulonglong2 *)&sm[plane][c + 8];
+        unsigned char *dst = a.YB + ((size_t)(plane / 3) * 72 + (j * 3 + plane % 3) * 8) * a.ldq + cb + pos0;
+#pragma unroll
+        for (int v = 0; v < 8; v++) {
+            const int sh = v < 4 ? 0 : 32;
+            *(u32 *)(dst + (size_t)v * a.ldq) = gather_bytes((u32)(lo.x >> sh), (u32)(lo.y >> sh), (u32)(hi.x >> sh), (u32)(hi.y >> sh), v & 3);
+        }
+    }
+}
+// The Y digits of q_j = M_j^T eq, j < nm <= 3, for following launch_dot_batch_i8(.., y_packed = true) calls on vectors X of this alignment -- what
+// nm x launch_spmv_t_eq + launch_dot_pack_y leave in YB, without the words.  Declines (I8_ERR_SHAPE, nothing launched) where the dot launch would, and where the
+// slice needs a lead column (its digits sit one position to the right: the two-pass form handles that).  Result: lf_i8_launch.h.
+int launch_q_pack_i8(const DevCrt &t, u32 nm, const u32 *const *colptr, const u32 *const *rowidx, const u64 *const *val, const u64 *eq, size_t m, const u64 *X,
+                     size_t n, unsigned char *YB, hipStream_t s) {
+    DotPlan p;
+    if (!dot_i8_shape(X, 2, 1, nm, n, &p) || p.lead) return I8_ERR_SHAPE;
+    QPackArgs a = {};
+    for (u32 j = 0; j < nm; j++) { a.colptr[j] = colptr[j]; a.rowidx[j] = rowidx[j]; a.val[j] = val[j]; }
+    a.eq = eq; a.m = m; a.n = n; a.ldq = p.ldq; a.YB = YB;
+    if (t.nu2p40) hipLaunchKernelGGL(k_q_pack_i8<true>, dim3(p.nsteps, nm), dim3(256), 0, s, t, a);
+    else hipLaunchKernelGGL(k_q_pack_i8<false>, dim3(p.nsteps, nm), dim3(256), 0, s, t, a);
     return i8_launched();
 }
 // X [na][24][ldx], Y [nb][24][ldy], n columns; out[(a*nb + b)*24 + 3*slot + comp] canonical.  Result: lf_i8_launch.h.
@@ -134,7 +197,7 @@ int launch_dot_batch_i8(const DevCrt &t, const u64 *X, size_t ldx, u32 na, const
                         long long *tot, u64 *out, hipStream_t s, bool y_packed, u32 nb_out, u32 b0) {
     if (!nb_out) nb_out = nb;
     DotPlan p;
-    if (na < 1 || na > 16 || nb < 1 || nb > 3 || (ldx & 1) || !p.make(X, n, DOT_CHUNKS)) return I8_ERR_SHAPE;
+    if (!dot_i8_shape(X, ldx, na, nb, n, &p)) return I8_ERR_SHAPE;
     if (!y_packed) hipLaunchKernelGGL((k_dot_pack_y<u64, 3>), dim3(p.pack_blocks(nb, 24)), dim3(256), 0, s, Y - p.lead, ldy, nb, p.n, p.lead, p.ldq, YB);
     const DotI8Args a = p.args<DotI8Args>(X, ldx, na, YB, 24 * nb, part);
     hipLaunchKernelGGL(k_dot_i8, dim3((unsigned)cdiv(a.chunks, 4) * 24), dim3(256), 0, s, a);

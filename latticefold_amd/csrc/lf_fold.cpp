@@ -172,10 +172,11 @@ void FoldStep::fix_special(u32 round, Fq3Const r, u64 *dst, hipStream_t sg) {
     }
 }
 // theta, eta at r_0 (folding.rs:236-256): their buffers and eq(r_o)
-int FoldStep::eval_buffers() {
+// (q_words = false: the caller gathers q_j straight into the packed digits -- q_pack_dev -- and the words get no buffer)
+int FoldStep::eval_buffers(bool q_words) {
     u64 *fsm;
     RET(c->tbuf("fold_eq0", 3 * m, &eq0));
-    RET(c->tbuf("dec_q", (size_t)P.t * 24 * n, &q));
+    if (q_words) RET(c->tbuf("dec_q", (size_t)P.t * 24 * n, &q));
     RET(c->tbuf("dot_partial", dot_partial_words(K, P.t), &dpart));
     RET(c->tbuf("fold_small", (size_t)K2 * 72 + (size_t)K2 * P.t * 24 + 64, &fsm));
     d_theta = fsm; d_eta = fsm + (size_t)K2 * 72;   // contiguous, as theta and eta are in the proof
@@ -614,10 +615,15 @@ int FoldB2::rounds() {
 int FoldB2::evaluations() {
     u64 *red;
     RET(c->tbuf("red_partial", 256 * 4096, &red));
-    RET(eval_buffers());
     // the helper lane's stream is idle here: every second q_j is gathered there, and the eta products of the right side run there
     hipStream_t s1 = (t_lane == 0 && c->sh_world == 1 && c->st_lane[1]) ? c->st_lane[1] : c->stream();
-    RET(gather_q(s1));
+    // q_j = M_j^T eq(r_o): one launch that leaves the packed digits both sides read (no words, no dec_q) where both sides' inner products take them; otherwise
+    // the gathers into words, every second one on s1
+    const bool fused_q = q_pack_takes(c, S[0].z, n, K) && q_pack_takes(c, S[1].z, n, K);
+    unsigned char *ybq = nullptr;
+    RET(eval_buffers(!fused_q));
+    if (fused_q) RET(q_pack_dev(c, S[0].z, eq0, &ybq));
+    else RET(gather_q(s1));
     // theta for both sides first, then eta; the host absorbs theta while the GPU still computes the eta dot products
     RET(c->pin((size_t)K2 * 72 + (size_t)K2 * P.t * 24));
     u64 *hp = c->h_pin_ref();
@@ -640,8 +646,7 @@ int FoldB2::evaluations() {
         // the two sides stream their own 0.8 GB of z_k: side by side on the two streams
         if (s1 != c->stream()) {
             // the digits of q are the same for both sides: packed once, before the streams part
-            unsigned char *ybq = nullptr;
-            if (!c->tn.dot_valu && cnt >= c->tn.dot_min && P.t <= 3 && K <= 16 && ((((size_t)(S[0].z + c0)) ^ ((size_t)(S[1].z + c0))) & 15) == 0) {
+            if (!fused_q && !c->tn.dot_valu && cnt >= c->tn.dot_min && P.t <= 3 && K <= 16 && ((((size_t)(S[0].z + c0)) ^ ((size_t)(S[1].z + c0))) & 15) == 0) {
                 RET(c->tbuf("dot_yb", dot_i8_yb_bytes(n + 1), &ybq));
                 const int rc = launch_dot_pack_y(S[0].z + c0, q + c0, n, P.t, cnt, ybq, c->stream());
                 if (rc == i8mma::I8_ERR_HIP) return LF_ERR_HIP;
@@ -655,7 +660,7 @@ int FoldB2::evaluations() {
             RET(dot_batch_dev(c, S[0].z + c0, n, K, q + c0, n, P.t, cnt, dpart, d_eta, nullptr, "", ybq));
             RET(c->join_wait(c->stream()));
         } else
-            for (int sd = 0; sd < 2; sd++) RET(dot_batch_dev(c, S[sd].z + c0, n, K, q + c0, n, P.t, cnt, dpart, d_eta + (size_t)sd * K * P.t * 24));
+            for (int sd = 0; sd < 2; sd++) RET(dot_batch_dev(c, S[sd].z + c0, n, K, q + c0, n, P.t, cnt, dpart, d_eta + (size_t)sd * K * P.t * 24, nullptr, "", ybq));
         RET(exchange_modsum_dev(c, d_eta, (size_t)K2 * P.t * 24));
     }
     HIPCHK(hipMemcpyAsync(hp + (size_t)K2 * 72, d_eta, (size_t)K2 * P.t * 24 * 8, hipMemcpyDeviceToHost, c->stream()));

@@ -151,6 +151,10 @@ int launch_dot_batch_i8(const DevCrt &t, const u64 *X, size_t ldx, u32 na, const
 // run in groups; 0 = nb)
 // the Y digits alone, for launch_dot_batch_i8(.., y_packed = true) calls on X vectors of the same alignment
 int launch_dot_pack_y(const u64 *X, const u64 *Y, size_t ldy, u32 nb, size_t n, unsigned char *YB, hipStream_t s);
+// ... and for q_j = M_j^T eq, j < nm <= 3, gathered straight into those digits (k_q_pack_i8: the words of q are not stored); CSC as launch_spmv_t_eq, all n columns.
+// I8_ERR_SHAPE where launch_dot_batch_i8 on X would decline or would start a column early (lf_dot_plan.h)
+int launch_q_pack_i8(const DevCrt &t, u32 nm, const u32 *const *colptr, const u32 *const *rowidx, const u64 *const *val, const u64 *eq, size_t m, const u64 *X,
+                     size_t n, unsigned char *YB, hipStream_t s);
 void launch_vs_combine(const u64 *vs /* [K][72] */, u32 K, u64 *v /* [72] */, hipStream_t s);   // v = sum_k 2^k v_s[k]
 void launch_fix_final(const DevCrt &t, const u64 *in /* [rows3][3][2] */, u32 rows3, Fq3Const r, u64 *out /* [rows3][3] canonical */, hipStream_t s);
 

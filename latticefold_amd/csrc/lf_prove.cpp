@@ -4,6 +4,7 @@
 //
 // Host <-> device traffic inside a fold step is O(proof size): per sumcheck round (D+1) ring elements come back
 // and one F_{p^3} challenge goes down; everything of size N stays in HBM.
+#include "lf_dot_plan.h"
 #include "lf_ring_host.h"
 
 // =================================================================================================================================
@@ -446,6 +447,7 @@ int dot_batch_dev(lf_ctx *c, const u64 *X, size_t ldx, u32 na, const u64 *Y, siz
                                          od + (size_t)a0 * nb * 24, st, yb_pre != nullptr && nb <= 3, nb, b0);
         if (rc != i8mma::I8_ERR_SHAPE) return rc == 0 ? LF_OK : LF_ERR_HIP;
     }
+    if (!Y) return LF_ERR_STATE;   // (q_pack_dev left digits and no words: its test is the launcher's, so this is not reached)
     if (nb > 4) {   // wide CCS envelope on the 64-bit VALU kernel (four tables Y per launch): groups of four into a scratch, copied to their place in [na][nb][24]
         u64 *tmp;
         RET(c->tbuf(std::string("dot_wide_tmp") + tag, (size_t)na * 4 * 24, &tmp));
@@ -458,6 +460,21 @@ int dot_batch_dev(lf_ctx *c, const u64 *X, size_t ldx, u32 na, const u64 *Y, siz
     }
     launch_dot_batch(c->dcrt, X, ldx, na, Y, ldy, nb, n, dpart, od, st);
     return LF_OK;
+}
+// q_j = M_j^T eq for the t matrices of a step, gathered straight into the packed digits that the int8 inner products read (k_q_pack_i8: one launch, the words
+// of q are never stored).  q_pack_takes: the inner products against the na vectors X [24][ldx] will be ONE int8 launch over all n columns from their first word
+// -- the test of lf_dot_plan.h, made before anything is enqueued -- on an unsharded b = 2 step with t <= 3, and LF_Q_TWO_PASS is not set.  Where it is false the
+// caller gathers into words (launch_spmv_t_eq) and the dot call packs them, as before.  q_pack_dev (only where it is true): *yb = the digits, for
+// dot_batch_dev(.., Y = nullptr, .., yb_pre = *yb).
+bool q_pack_takes(lf_ctx *c, const u64 *X, size_t ldx, u32 na) {
+    const lf_params &P = c->P;
+    i8mma::DotPlan p;
+    return !c->tn.q_two_pass && c->sh_world == 1 && P.b == 2 && P.t <= 3 && dot_i8_takes(c->tn.dot_valu, c->tn.dot_min, X, ldx, na, P.t, c->n, &p) && !p.lead;
+}
+int q_pack_dev(lf_ctx *c, const u64 *X, const u64 *eq, unsigned char **yb) {
+    RET(c->tbuf("dot_yb", dot_i8_yb_bytes(c->n + 1), yb));
+    const int rc = launch_q_pack_i8(c->dcrt, c->P.t, c->d_colptr.data(), c->d_rowidx.data(), c->d_valT.data(), eq, c->m, X, c->n, *yb, c->stream());
+    return rc == 0 ? LF_OK : rc == i8mma::I8_ERR_HIP ? LF_ERR_HIP : LF_ERR_STATE;   // (declined: q_pack_takes was false -- there is no kernel to fall back to from here)
 }
 // the point-dependent half of LFDecompositionProver::prove (decomposition.rs:33-88): x_s, v_s, z_k, u_s
 // The part of a decomposition's evaluations that does not depend on the evaluation point: x_s (host, into the proof) and the K vectors
@@ -506,7 +523,6 @@ static int decompose_evals(lf_ctx *c, const u64 *lcccs, const std::vector<Fq3> &
     RET(c->tbuf("red_partial", 256 * 4096, &partial));
     if (K > 32 || P.t > 8) return LF_ERR_UNSUPPORTED;       // the fixed layout of dec_small below (v_s: 32 x 72 words, u_s: 32 x 8 elements); lf_ccs_load enforces the same envelope
     RET(c->tbuf("dec_small", 32 * 72 + 32 * 8 * 24 + 64, &od));
-    RET(c->tbuf("dec_q", (size_t)P.t * 24 * n, &q));
     u64 *od_v = od, *od_u = od + 32 * 72;
     if (!eq_r) {
         RET(c->tbuf("eq_r_" + sd, 3 * m, &eq_r));
@@ -543,9 +559,16 @@ static int decompose_evals(lf_ctx *c, const u64 *lcccs, const std::vector<Fq3> &
     {
         size_t c0, cnt;
         shard_slice(c, n, &c0, &cnt);   // sharded: dot products over this rank's column slice of z_k and q_j -- and only that slice of q_j is computed
-        for (u32 j = 0; j < P.t; j++)
-            launch_spmv_t_eq(c->dcrt, c->d_colptr[j], c->d_rowidx[j], c->d_valT[j], eq_r, m, q + (size_t)j * 24 * n, n, c->stream(), c0, cnt);
-        RET(dot_batch_dev(c, z + c0, n, K, q + c0, n, P.t, cnt, dpart, od_u));
+        if (q_pack_takes(c, z + c0, n, K)) {
+            unsigned char *ybq;
+            RET(q_pack_dev(c, z + c0, eq_r, &ybq));
+            RET(dot_batch_dev(c, z + c0, n, K, nullptr, n, P.t, cnt, dpart, od_u, nullptr, "", ybq));
+        } else {
+            RET(c->tbuf("dec_q", (size_t)P.t * 24 * n, &q));
+            for (u32 j = 0; j < P.t; j++)
+                launch_spmv_t_eq(c->dcrt, c->d_colptr[j], c->d_rowidx[j], c->d_valT[j], eq_r, m, q + (size_t)j * 24 * n, n, c->stream(), c0, cnt);
+            RET(dot_batch_dev(c, z + c0, n, K, q + c0, n, P.t, cnt, dpart, od_u));
+        }
         RET(exchange_modsum_dev(c, od, (size_t)32 * 72 + (size_t)K * P.t * 24));   // sharded: the partial v_s and u_s of this rank's slices, ONE all-gather + modular sum
     }
     // one download (one stream synchronisation) for both result sets
