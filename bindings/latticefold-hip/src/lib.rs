@@ -232,6 +232,17 @@ impl HipContext {
         chk(rc, "lf_ccs_check").map(Ok)
     }
 
+    /// the transposed product `M_j^T v` with matrix j of the loaded CCS (what `SparseMatrix::mul_vec` is to `M_j z`): `v`: m general elements, n back
+    pub fn mul_vec_transposed<NTT: SuitableRing>(&self, j: usize, v: &[NTT]) -> Result<Vec<NTT>, HipError> {
+        let p = self.params()?;
+        assert_eq!(v.len(), 1usize << p.s);
+        let w = flatten(v);
+        let mut out = vec![0u64; (p.l + 1 + p.wit_len) as usize * NTT::WORDS];
+        // SAFETY: w holds m elements, out n
+        chk(unsafe { sys::tables::lf_spmv_t(self.raw, j as u32, w.as_ptr(), out.as_mut_ptr()) }, "lf_spmv_t")?;
+        Ok(unflatten(&out))
+    }
+
     /// R_CCCS of (`cccs`, `wit`): the `LF_REL_*` bits of the failing components (cm, CCS on z = (x_ccs, 1, w_ccs), norm when `bound` != 0); 0 = holds
     pub fn check_cccs<NTT: SuitableRing>(&self, cccs: &CCCS<NTT>, wit: &HipWitness<NTT>, bound: u64) -> Result<u32, HipError> {
         let mut w = flatten(cccs.cm.as_ref());
@@ -325,6 +336,18 @@ impl HipContext {
     pub unsafe fn spmv_dev(&self, j: u32, z: *const u64, out: *mut u64) -> Result<(), HipError> {
         // SAFETY: the caller vouches for the device ranges (see the impl); host slices were checked above
         chk(unsafe { sys::lf_spmv_dev(self.raw, j, z, out) }, "lf_spmv_dev")
+    }
+    /// the transposed product with matrix j of the loaded CCS (`SparseMatrix`-side `mul_vec_transposed`): `v`: m general elements, `out`: n elements; the
+    /// ranges may not overlap
+    pub unsafe fn spmv_t_device(&self, j: u32, v: *const u64, out: *mut u64) -> Result<(), HipError> {
+        // SAFETY: the caller vouches for the device ranges (see the impl); host slices were checked above
+        chk(unsafe { sys::tables::lf_spmv_t_device(self.raw, j, v, out) }, "lf_spmv_t_device")
+    }
+    /// `fix_variables` on tables: `tables`: ntables x len elements on the device, `point`: nfix challenges of tau words (host), `out`: ntables x (len >> nfix)
+    pub unsafe fn mle_fix_variables_device(&self, tables: *const u64, ntables: usize, len: usize, point: &[u64], nfix: u32, out: *mut u64) -> Result<(), HipError> {
+        assert_eq!(point.len(), nfix as usize * self.word_counts().1);
+        // SAFETY: the caller vouches for the device ranges (see the impl); host slices were checked above
+        chk(unsafe { sys::tables::lf_mle_fix_variables_device(self.raw, tables, ntables, len, point.as_ptr(), nfix, out) }, "lf_mle_fix_variables_device")
     }
     /// `tables`: t x m elements on the device; the rounds are `lf_sumcheck_lin_round` / `_end` as after a host begin
     pub unsafe fn sumcheck_lin_begin_dev(&self, tables: *const u64, eq_point: &[u64]) -> Result<(), HipError> {
@@ -600,6 +623,40 @@ impl<NTT: SuitableRing> HipWitness<NTT> {
         // SAFETY: w holds N coefficient-form elements
         chk(unsafe { sys::lf_witness_get_f_coeff(self.ctx.raw, self.raw, w.as_mut_ptr()) }, "lf_witness_get_f_coeff")?;
         Ok(Witness::from_f_coeff::<P>(unflatten(&w)))
+    }
+
+    /// `Witness::get_fhat` (arith.rs:273-297): the tau tables of m = 2^s entries, built on the device
+    pub fn f_hat(&self) -> Result<Vec<Vec<NTT>>, HipError> {
+        let p = self.ctx.params()?;
+        let (m, tau) = (1usize << p.s, self.ctx.word_counts().1);
+        let mut out = vec![0u64; tau * m * NTT::WORDS];
+        let h = [self.raw as *const sys::lf_witness];
+        // SAFETY: out holds tau tables of m elements; h holds one handle of this context
+        chk(unsafe { sys::tables::lf_witness_get_fhat(self.ctx.raw, h.as_ptr(), 1, out.as_mut_ptr()) }, "lf_witness_get_fhat")?;
+        Ok(out.chunks(m * NTT::WORDS).map(unflatten).collect())
+    }
+
+    /// `z = x || 1 || w_ccs` (`get_z_vector`, arith.rs:399-409) for the public input `x_ccs` (l elements)
+    pub fn z(&self, x_ccs: &[NTT]) -> Result<Vec<NTT>, HipError> {
+        let p = self.ctx.params()?;
+        assert_eq!(x_ccs.len(), p.l as usize);
+        let x = flatten(x_ccs);
+        let mut out = vec![0u64; (p.l as usize + 1 + p.wit_len as usize) * NTT::WORDS];
+        // SAFETY: x holds l elements, out n = l + 1 + wit_len
+        chk(unsafe { sys::tables::lf_witness_get_z(self.ctx.raw, self.raw, x.as_ptr(), out.as_mut_ptr()) }, "lf_witness_get_z")?;
+        Ok(unflatten(&out))
+    }
+
+    /// `calculate_Mz_mles` (utils/mle_helpers.rs:137-146): the t tables `M_j z` of m entries
+    pub fn mz(&self, x_ccs: &[NTT]) -> Result<Vec<Vec<NTT>>, HipError> {
+        let p = self.ctx.params()?;
+        assert_eq!(x_ccs.len(), p.l as usize);
+        let x = flatten(x_ccs);
+        let m = 1usize << p.s;
+        let mut out = vec![0u64; p.t as usize * m * NTT::WORDS];
+        // SAFETY: x holds l elements, out t tables of m
+        chk(unsafe { sys::tables::lf_witness_mz(self.ctx.raw, self.raw, x.as_ptr(), out.as_mut_ptr()) }, "lf_witness_mz")?;
+        Ok(out.chunks(m * NTT::WORDS).map(unflatten).collect())
     }
 
     /// `Witness::within_bound` (arith.rs:372-386) with centred representatives: max |coefficient| < bound

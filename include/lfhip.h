@@ -403,7 +403,10 @@ int lf_ccs_check_dev(lf_ctx *, const uint64_t *z, uint64_t *first_bad /* host */
  *   lf_decompose_dev, layout 1: none of the `digits` tables is written unless all are.  lf_build_eq_dev has no device input, so nothing of it can be refused
  * after the pointer check; in an external basis its entries are converted by the kernel that stores them.  lf_spmv_dev on general CSR rows (Goldilocks)
  * gathers from the caller's z, which is the element-major copy, unless the context is in an external basis.
- *   The _round and _end calls of the two sumchecks have no twin: their arguments are O(1). */
+ *   The _round and _end calls of the two sumchecks have no twin: their arguments are O(1).
+ *   Where the tables come from on the device: the 2K*tau f-hat tables of lf_sumcheck_fold_begin_dev are what lf_witness_get_fhat_device writes for the 2K part
+ * handles of lf_witness_decompose, in one call, straight into slots 5.. of the array; the t tables of lf_sumcheck_lin_begin_dev are lf_witness_mz_device's
+ * (lfhip_tables.h). */
 int lf_decompose_dev(lf_ctx *, const uint64_t *coeff_in, /* dev: count */ size_t count, uint64_t base, unsigned digits, int layout,
                      uint64_t *out /* dev: count*digits, layout 0 or 1 */);
 int lf_recompose_dev(lf_ctx *, const uint64_t *in, /* dev: count_out*digits */ size_t count_out, uint64_t base, unsigned digits, uint64_t *out /* dev: count_out */);
@@ -468,6 +471,10 @@ int lf_proof_deserialize(const lf_params *, int ring, const uint8_t *in, size_t 
 /* ---- decomposed witnesses (decompose_witness, nifs/decomposition.rs:162-167; the w_s of LFFoldingProver::prove): four more entry points of this ABI, declared
  * in a file of their own that this header includes -- the prototypes written in THIS file are a set the ABI tests count, as the _dev twins are ------------ */
 #include "lfhip_parts.h"
+
+/* ---- the protocol's own tables from a witness handle, on the device (Witness::get_fhat, z = x || 1 || w_ccs, calculate_Mz_mles, M_j^T v, fix_variables on
+ * tables): ten more entry points, in a file of their own for the same reason.  Their device-memory twins end in _device, as lf_ring_mul_device does ------------ */
+#include "lfhip_tables.h"
 
 /* ---- MLSumcheck::prove_as_subprotocol / verify_as_subprotocol over any sum of products of MLE tables (utils/sumcheck.rs:53-104): eight more entry points,
  * lf_mlsumcheck_*, in a file of their own for the same reason ------------ */

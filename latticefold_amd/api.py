@@ -223,6 +223,18 @@ def _lib():
         L.lf_mlsumcheck_prove.argtypes = [vp, vp, vpp, u64p, u64p, u64p, u64p]
         L.lf_mlsumcheck_prove_device.argtypes = [vp, vp, vpp, vp, u64p, u64p, u64p]
         L.lf_mlsumcheck_verify.argtypes = [C.c_int, vp, C.c_uint32, C.c_uint32, u64p, u64p, u64p, u64p]
+        # witness tables (include/lfhip_tables.h); the _device arrays are plain addresses
+        hp = C.POINTER(vp)
+        L.lf_witness_get_fhat.argtypes = [vp, hp, C.c_uint, u64p]
+        L.lf_witness_get_fhat_device.argtypes = [vp, hp, C.c_uint, vp]
+        L.lf_witness_get_z.argtypes = L.lf_witness_mz.argtypes = [vp, vp, u64p, u64p]
+        L.lf_witness_get_z_device.argtypes = L.lf_witness_mz_device.argtypes = [vp, vp, u64p, vp]
+        L.lf_spmv_t.argtypes = [vp, C.c_uint, u64p, u64p]
+        L.lf_spmv_t_device.argtypes = [vp, C.c_uint, vp, vp]
+        L.lf_mle_fix_variables.argtypes = [vp, u64p, C.c_size_t, C.c_size_t, u64p, C.c_uint, u64p]
+        L.lf_mle_fix_variables_device.argtypes = [vp, vp, C.c_size_t, C.c_size_t, u64p, C.c_uint, vp]
+        L.lfdbg_spmv_t_heavy_min.argtypes = [vp, C.c_uint]
+        L.lfdbg_spmv_t_heavy_min.restype = C.c_uint
         # the chained prover object (include/lfhip_prover.h); the _dev arrays are plain addresses
         uip = C.POINTER(C.c_uint)
         L.lf_prover_create.argtypes = [vp, C.c_uint, C.POINTER(vp)]
@@ -265,7 +277,7 @@ def abi_version():
 
 def exported_symbols(header="lfhip.h"):
     """Every symbol include/lfhip.h declares (used by the CPU-side ABI test); header="lfhip_parts.h" / "lfhip_sumcheck.h" / "lfhip_prover.h": the ones of a
-    file it includes."""
+    file it includes ("lfhip_tables.h": the witness tables)."""
     import re
     hdr = open(os.path.join(_HERE, "..", "include", header)).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
@@ -312,6 +324,7 @@ class Context:
 
     def __init__(self, device=0, ring="goldilocks"):
         self.h = C.c_void_p()
+        self.device = device
         self.ring = ring
         self.ring_id = RING_IDS[ring]
         self.RE = RING_WORDS[ring]
@@ -578,6 +591,26 @@ class Context:
         o = np.zeros((self.m, self.RE), dtype=np.uint64)
         _chk(_lib().lf_spmv(self.h, j, p, o.ctypes.data_as(u64p)), "lf_spmv")
         return o
+
+    def mat_vec_mul_t(self, j, v, out=None, device=None):
+        """lf_spmv_t: M_j^T v for v of m general ring elements (NTT form), (n, RE).  v a device array: lf_spmv_t_device, the result a device array (`out` or a
+        fresh one); device=True with a numpy v uploads it first"""
+        if device and not is_device_array(v):
+            import torch
+            v = torch.from_numpy(np.ascontiguousarray(v, dtype=np.uint64).view(np.int64)).to(torch.device("cuda", self.device))
+        if is_device_array(v):
+            o = _dev_out(v, (self.n, self.RE), out)
+            _chk(_lib().lf_spmv_t_device(self.h, j, _dev(self, v), _dev(self, o)), "lf_spmv_t_device")
+            return o
+        a, p = _a64(v)
+        o = np.zeros((self.n, self.RE), dtype=np.uint64)
+        _chk(_lib().lf_spmv_t(self.h, j, p, o.ctypes.data_as(u64p)), "lf_spmv_t")
+        return o
+
+    def spmv_t_heavy_min(self, next=0):
+        """(tests, measurements; not part of the ABI) the heavy-column threshold of lf_spmv_t in force for the loaded system; next != 0: the one the next
+        load_ccs builds its work lists with"""
+        return int(_lib().lfdbg_spmv_t_heavy_min(self.h, next))
 
     # ---- relation checks (arith.rs:76-110, 193-206) ------------------------------------------------------------
     def check_relation(self, z):
@@ -846,6 +879,32 @@ class Witness:
     def w_ccs_into(self, out):
         return self._get_into(_lib().lf_witness_get_w_ccs_dev, "lf_witness_get_w_ccs_dev", self.ctx.params.wit_len, out)
 
+    def get_fhat(self, device=None):
+        """Witness::get_fhat (arith.rs:273-297): the tau f-hat tables, (tau, m, RE); device: a device array to write into, or True for a fresh one"""
+        return get_fhat(self.ctx, [self], device=device)
+
+    def _xz(self, x, host_fn, dev_fn, name, shape, device):
+        a, p = _a64(x)
+        if a.size != self.ctx.params.l * self.ctx.RE:
+            raise ValueError("x must hold l ring elements")
+        if device is not None and device is not False:
+            o = _new_dev(self.ctx, shape) if device is True else _dev_out(None, shape, device)
+            _chk(dev_fn(self.ctx.h, self.h, p, _dev(self.ctx, o)), name + "_device")
+            return o
+        o = np.zeros(shape, dtype=np.uint64)
+        _chk(host_fn(self.ctx.h, self.h, p, o.ctypes.data_as(u64p)), name)
+        return o
+
+    def get_z(self, x, device=None):
+        """z = x || 1 || w_ccs (arith.rs:399-409), (n, RE); x: (l, RE) on the host"""
+        L = _lib()
+        return self._xz(x, L.lf_witness_get_z, L.lf_witness_get_z_device, "lf_witness_get_z", (self.ctx.n, self.ctx.RE), device)
+
+    def mz(self, x, device=None):
+        """calculate_Mz_mles (utils/mle_helpers.rs:137-146): the t tables M_j z, (t, m, RE)"""
+        L = _lib()
+        return self._xz(x, L.lf_witness_mz, L.lf_witness_mz_device, "lf_witness_mz", (self.ctx.params.t, self.ctx.m, self.ctx.RE), device)
+
     def commit(self, scheme):
         o = np.zeros((scheme.kappa(), self.ctx.RE), dtype=np.uint64)
         _chk(_lib().lf_witness_commit(self.ctx.h, self.h, o.ctypes.data_as(u64p)), "lf_witness_commit")
@@ -879,6 +938,42 @@ class Witness:
 def _handles(wits):
     """witnesses -> the array of handles an entry point with a `const lf_witness *const *` argument takes"""
     return (C.c_void_p * max(len(wits), 1))(*[w.h.value if isinstance(w.h, C.c_void_p) else w.h for w in wits])
+
+
+def _new_dev(ctx, shape):
+    """a fresh device array of canonical words on the context's device"""
+    import torch
+    return torch.empty(shape, dtype=torch.int64, device=torch.device("cuda", ctx.device))
+
+
+def get_fhat(ctx, wits, device=None):
+    """lf_witness_get_fhat for a batch: (len(wits) * tau, m, RE), table w * tau + j = f-hat_j of wits[w] -- the order MLSumcheckFold takes them from slot 5
+    on.  device: a device array to write into (e.g. a view of the fold sumcheck's table array), or True for a fresh one: lf_witness_get_fhat_device"""
+    shape = (len(wits) * ctx.TAU, ctx.m, ctx.RE)
+    if device is not None and device is not False:
+        o = _new_dev(ctx, shape) if device is True else _dev_out(None, shape, device)
+        _chk(_lib().lf_witness_get_fhat_device(ctx.h, _handles(wits), len(wits), _dev(ctx, o)), "lf_witness_get_fhat_device")
+        return o
+    o = np.zeros(shape, dtype=np.uint64)
+    _chk(_lib().lf_witness_get_fhat(ctx.h, _handles(wits), len(wits), o.ctypes.data_as(u64p)), "lf_witness_get_fhat")
+    return o
+
+
+def mle_fix_variables(ctx, tables, point, out=None):
+    """DenseMultilinearExtension::fix_variables on tables (ntables, len, RE): the lowest nfix = len(point) / tau variables fixed at `point` (host) ->
+    (ntables, len >> nfix, RE).  tables a device array: lf_mle_fix_variables_device, the result a device array (`out` or a fresh one)"""
+    b, q = _a64(point)
+    nfix = b.size // ctx.TAU
+    nt, ln = int(tables.shape[0]), int(tables.shape[1])
+    shape = (nt, ln >> nfix, ctx.RE)
+    if is_device_array(tables):
+        o = _dev_out(tables, shape, out)
+        _chk(_lib().lf_mle_fix_variables_device(ctx.h, _dev(ctx, tables), nt, ln, q, nfix, _dev(ctx, o)), "lf_mle_fix_variables_device")
+        return o
+    a, p = _a64(tables)
+    o = np.zeros(shape, dtype=np.uint64)
+    _chk(_lib().lf_mle_fix_variables(ctx.h, p, nt, ln, q, nfix, o.ctypes.data_as(u64p)), "lf_mle_fix_variables")
+    return o
 
 
 class PoseidonTranscript:

@@ -81,6 +81,17 @@ void launch_spmv_sum(const DevBb &t, u32 nm, const u32 *const *rowptr, const u32
                      size_t ldz, fe *out, size_t m, hipStream_t s);
 void launch_spmv_t_eq(const DevBb &t, const u32 *colptr, const u32 *rowidx, const fe *val, const fe *eq, size_t m, fe *q, size_t n,
                       hipStream_t s);
+// ---- witness tables (lfhip_tables.h; kernels in lf_ring_kernels.cuh, lf_spmv_t.cuh) ----
+// Witness::get_fhat: planes [RE][N] centred int32 -> out [TAU][m][RE] canonical AoS words, each word written once (t: picks the ring's overload only)
+void launch_fhat(const DevBb &t, const int32_t *planes, size_t N, size_t m, u64 *out, hipStream_t s);
+// the head x || 1 of z = x || 1 || w_ccs into the plane table z [RE][n]: x = l staged elements of canonical AoS words
+void launch_z_head(const u64 *x, size_t l, fe *z, size_t n, hipStream_t s);
+// [n][RE] canonical u64 -> [n][RE] device words, element-major (flag, Ti as for launch_aos_to_soa)
+void launch_aos_words(const u64 *aos, fe *dst, size_t n, hipStream_t s, u32 *flag = nullptr, const XbMat9 *Ti = nullptr);
+// out [RE][n] = M^T v for general v: CSC as launch_spmv_t_eq, vw = v element-major [m][RE] (launch_aos_words); heavy_min, plan, nitems, ncols: the heavy
+// columns of the matrix as lf_ccs_load listed them (lf_spmv_t_plan.h), part: scratch of nitems * RE words
+void launch_spmv_t(const DevBb &t, const u32 *colptr, const u32 *rowidx, const fe *val, const fe *vw, fe *out, size_t n, u32 heavy_min, const u32 *plan,
+                   u32 nitems, u32 ncols, fe *part, hipStream_t s);
 size_t red_partial_words(u32 nv);
 // the same on the int8 matrix cores (bb_dot_i8.hip), na <= 16, nb <= 3; scratch: YB bbdot_i8_yb_bytes(n), part bbdot_i8_part_words(n) int32,
 // tot bbdot_i8_tot_words() int64.  Result: lf_i8_launch.h.

@@ -200,6 +200,9 @@ void launch_coef_to_i32(const fe *coef, int32_t *planes, size_t n, u32 bound, in
 }
 void launch_i32_to_coef(const int32_t *planes, fe *coef, size_t n, hipStream_t s) { lfk::launch_i32_to_coef<BbF>(planes, coef, n, s); }
 void launch_linf(const fe *coef, size_t n, u64 *out_max, hipStream_t s) { lfk::launch_linf<BbF>(coef, n, out_max, s); }
+void launch_fhat(const DevBb &, const int32_t *planes, size_t N, size_t m, u64 *out, hipStream_t s) { lfk::launch_fhat<BbF>(planes, N, m, out, s); }
+void launch_z_head(const u64 *x, size_t l, fe *z, size_t n, hipStream_t s) { lfk::launch_z_head<BbF>(x, l, z, n, s); }
+void launch_aos_words(const u64 *aos, fe *dst, size_t n, hipStream_t s, u32 *flag, const XbMat9 *Ti) { lfk::launch_aos_words<BbF>(aos, dst, n, s, flag, Ti); }
 
 struct BPow { fe v[8]; };
 // thread = (element i, residue class r of the coefficient index); in bit-plane mode the 8 x L plane entries are loaded once and all

@@ -13,6 +13,7 @@
 
 #include "bb_kernels_dev.cuh"
 #include "lf_ring_mul.cuh"
+#include "lf_spmv_t.cuh"
 
 namespace lfbb {
 
@@ -55,6 +56,11 @@ void launch_ring_mul_ntt(const DevBb &t, const u64 *a, const u64 *b, size_t n_te
 }
 void launch_ring_mul_coeff(const DevBb &t, const fe *icrt_mat, const fe *a, const fe *b, size_t n_terms, size_t n, fe *out, hipStream_t s) {
     lfk::launch_ring_mul_coeff<BbMul>(t, icrt_mat, a, b, n_terms, n, out, s);
+}
+// M^T v for general v (lf_spmv_t.cuh): instantiated here because the lazy sum of slot products is this file's field policy
+void launch_spmv_t(const DevBb &t, const u32 *colptr, const u32 *rowidx, const fe *val, const fe *vw, fe *out, size_t n, u32 heavy_min, const u32 *plan,
+                   u32 nitems, u32 ncols, fe *part, hipStream_t s) {
+    lfk::launch_spmv_t<BbF, BbMul>(t, colptr, rowidx, val, vw, out, n, heavy_min, plan, nitems, ncols, part, s);
 }
 
 }  // namespace lfbb

@@ -992,6 +992,70 @@ int lf_folding_prove_parts(lf_ctx *c, lf_transcript *t, const uint64_t *lcccs_s,
     if (rc != LF_OK && *w_out) { lf_witness_free(*w_out); *w_out = nullptr; }
     return rc;
 }
+// ---- witness tables (lfhip_tables.h; lf_ring_host.h: one body per call for both spellings and both rings).  In an external basis the arrays change basis in
+// the relayout kernels (f-hat needs none: a constant slot is c e_0 in any basis), x and the points on the host
+static int witness_get_fhat_api(lf_ctx *c, const lf_witness *const *wits, unsigned count, uint64_t *out, Origin org) {
+    if (!c || !wits || !out) return LF_ERR_INVALID;
+    for (unsigned w = 0; w < count; w++)
+        if (!wits[w] || wits[w]->ctx != c) return LF_ERR_INVALID;
+    return c->bb ? ring_ops<BbRing>::witness_get_fhat(c->bb->p, wits, count, out, org) : ring_ops<GoldRing>::witness_get_fhat(c, wits, count, out, org);
+}
+int lf_witness_get_fhat(lf_ctx *c, const lf_witness *const *wits, unsigned count, uint64_t *out) { return witness_get_fhat_api(c, wits, count, out, Origin::host); }
+int lf_witness_get_fhat_device(lf_ctx *c, const lf_witness *const *wits, unsigned count, uint64_t *out) {
+    return witness_get_fhat_api(c, wits, count, out, Origin::device);
+}
+// z and M z: x is small -- validated, then converted by the wrapper
+static int witness_z_api(lf_ctx *c, const lf_witness *w, const uint64_t *x, uint64_t *out, bool mz, Origin org) {
+    if (!c || !w || !x || !out || w->ctx != c) return LF_ERR_INVALID;
+    if (LF_XB(c) && c->have_ccs_any()) {   // (x is read only once the handle is known to belong to the loaded system: it holds l elements of THAT system)
+        if (w->N != c->N_any()) return LF_ERR_INVALID;
+        const size_t l = c->params_any().l, words = l * (size_t)lf_ring_words(lf_ctx_ring(c));
+        for (size_t i = 0; i < words; i++)
+            if (x[i] >= lf_ring_modulus(lf_ctx_ring(c))) return LF_ERR_INVALID;
+        XB xb(c, true);
+        return witness_z_api(c, w, xb.ring_in(x, l), out, mz, org);
+    }
+    if (mz) return c->bb ? ring_ops<BbRing>::witness_mz(c->bb->p, w, x, out, org) : ring_ops<GoldRing>::witness_mz(c, w, x, out, org);
+    return c->bb ? ring_ops<BbRing>::witness_get_z(c->bb->p, w, x, out, org) : ring_ops<GoldRing>::witness_get_z(c, w, x, out, org);
+}
+int lf_witness_get_z(lf_ctx *c, const lf_witness *w, const uint64_t *x, uint64_t *out) { return witness_z_api(c, w, x, out, false, Origin::host); }
+int lf_witness_get_z_device(lf_ctx *c, const lf_witness *w, const uint64_t *x, uint64_t *out) { return witness_z_api(c, w, x, out, false, Origin::device); }
+int lf_witness_mz(lf_ctx *c, const lf_witness *w, const uint64_t *x, uint64_t *out) { return witness_z_api(c, w, x, out, true, Origin::host); }
+int lf_witness_mz_device(lf_ctx *c, const lf_witness *w, const uint64_t *x, uint64_t *out) { return witness_z_api(c, w, x, out, true, Origin::device); }
+static int spmv_t_api(lf_ctx *c, unsigned j, const uint64_t *v, uint64_t *out, Origin org) {
+    if (!c || !v || !out) return LF_ERR_INVALID;
+    XbArrays xa(c);
+    return c->bb ? ring_ops<BbRing>::spmv_t(c->bb->p, j, v, out, org) : ring_ops<GoldRing>::spmv_t(c, j, v, out, org);
+}
+int lf_spmv_t(lf_ctx *c, unsigned j, const uint64_t *v, uint64_t *out) { return spmv_t_api(c, j, v, out, Origin::host); }
+int lf_spmv_t_device(lf_ctx *c, unsigned j, const uint64_t *v, uint64_t *out) { return spmv_t_api(c, j, v, out, Origin::device); }
+static int mle_fix_variables_api(lf_ctx *c, const uint64_t *tables, size_t ntables, size_t len, const uint64_t *point, unsigned nfix, uint64_t *out, Origin org) {
+    if (!c || !tables || !point || !out) return LF_ERR_INVALID;
+    if (LF_XB(c)) {   // (the shape first: the point holds nfix challenges only if nfix is one the body accepts)
+        if (len < 2 || (len & (len - 1)) || !nfix || nfix >= 64 || ((size_t)1 << nfix) > len) return LF_ERR_INVALID;
+        for (size_t i = 0, words = (size_t)nfix * lf_ring_tau(lf_ctx_ring(c)); i < words; i++)
+            if (point[i] >= lf_ring_modulus(lf_ctx_ring(c))) return LF_ERR_INVALID;
+        XB xb(c, true);
+        return mle_fix_variables_api(c, tables, ntables, len, xb.ext_in(point, nfix), nfix, out, org);
+    }
+    return c->bb ? ring_ops<BbRing>::mle_fix_variables(c->bb->p, tables, ntables, len, point, nfix, out, org)
+                 : ring_ops<GoldRing>::mle_fix_variables(c, tables, ntables, len, point, nfix, out, org);
+}
+int lf_mle_fix_variables(lf_ctx *c, const uint64_t *tables, size_t ntables, size_t len, const uint64_t *point, unsigned nfix, uint64_t *out) {
+    return mle_fix_variables_api(c, tables, ntables, len, point, nfix, out, Origin::host);
+}
+int lf_mle_fix_variables_device(lf_ctx *c, const uint64_t *tables, size_t ntables, size_t len, const uint64_t *point, unsigned nfix, uint64_t *out) {
+    return mle_fix_variables_api(c, tables, ntables, len, point, nfix, out, Origin::device);
+}
+// (not part of the ABI: tests and measurements) the heavy-column threshold of lf_spmv_t the NEXT lf_ccs_load builds its work lists with (0: the shipped one);
+// returns the one in force for the loaded system
+extern "C" unsigned lfdbg_spmv_t_heavy_min(lf_ctx *c, unsigned next) {
+    if (!c) return 0;
+    CtxCoreBase &k = c->core_any();
+    std::lock_guard<std::mutex> g(k.mu);
+    k.spmvt_min_next = next ? next : lfk::SPMV_T_HEAVY;
+    return k.spmvt_min;
+}
 // pool of recycled witness-plane buffers: process-wide (a witness may be freed after its context), keyed by device and size
 namespace {
 struct PoolEnt { int device; size_t bytes; int32_t *p; };

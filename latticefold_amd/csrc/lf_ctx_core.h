@@ -14,6 +14,7 @@
 #include "../../include/lfhip.h"
 #include "lf_common.h"
 #include "lf_mlsumcheck.h"
+#include "lf_spmv_t_plan.h"
 
 struct lf_witness;
 
@@ -43,6 +44,11 @@ struct CtxCoreBase {
     lf_params P{};
     size_t N = 0, m = 0, n = 0;
     std::vector<uint32_t *> d_rowptr, d_col, d_colptr, d_rowidx;
+    // lf_spmv_t: per matrix, the work list of its heavy columns on the device (lf_spmv_t_plan.h; null without heavy columns) and its two lengths; the threshold
+    // the lists of the loaded system were built with, and the one the next lf_ccs_load takes (a test hook moves it: lfdbg_spmv_t_heavy_min)
+    std::vector<uint32_t *> d_spmvt_plan;
+    std::vector<uint32_t> spmvt_items, spmvt_cols;
+    uint32_t spmvt_min = lfk::SPMV_T_HEAVY, spmvt_min_next = lfk::SPMV_T_HEAVY;
     uint64_t setup_gen = 0;   // counts the times the matrix or the constraint system was dropped (a reload drops first): how an lf_prover sees a reload of equal shape
     // sumcheck ABI state: linearization (lf_sumcheck_lin_*) and folding (lf_sumcheck_fold_*)
     int sc_round = -1, sc_cur = 0;
@@ -257,7 +263,10 @@ struct CtxCore : CtxCoreBase {
         for (auto q : d_colptr) (void)hipFree(q);
         for (auto q : d_rowidx) (void)hipFree(q);
         for (auto q : d_valT) (void)hipFree(q);
+        for (auto q : d_spmvt_plan)
+            if (q) (void)hipFree(q);
         d_rowptr.clear(); d_col.clear(); d_val.clear(); d_colptr.clear(); d_rowidx.clear(); d_valT.clear();
+        d_spmvt_plan.clear(); spmvt_items.clear(); spmvt_cols.clear();
         have_ccs = false;
         setup_gen++;
     }

@@ -113,6 +113,17 @@ void launch_spmv_rows(const DevCrt &t, u32 nm, const u32 *const *rowptr, const u
                       u64 *zaos, u64 *out, size_t m, int accumulate, hipStream_t s, size_t r0 = 0, size_t rcnt = (size_t)-1);
 void launch_spmv_t_eq(const DevCrt &t, const u32 *colptr, const u32 *rowidx, const u64 *val, const u64 *eq, size_t m,
                       u64 *q, size_t n, hipStream_t s, size_t c0 = 0, size_t ccnt = (size_t)-1 /* all columns */);
+// ---- witness tables (lfhip_tables.h; kernels in lf_ring_kernels.cuh, lf_spmv_t.cuh) ----
+// Witness::get_fhat: planes [RE][N] centred int32 -> out [TAU][m][RE] canonical AoS words, each word written once (t: picks the ring's overload only)
+void launch_fhat(const DevCrt &t, const int32_t *planes, size_t N, size_t m, u64 *out, hipStream_t s);
+// the head x || 1 of z = x || 1 || w_ccs into the plane table z [RE][n]: x = l staged elements of canonical AoS words
+void launch_z_head(const u64 *x, size_t l, u64 *z, size_t n, hipStream_t s);
+// [n][RE] canonical u64 -> [n][RE] device words, element-major (flag, Ti as for launch_aos_to_soa)
+void launch_aos_words(const u64 *aos, u64 *dst, size_t n, hipStream_t s, u32 *flag = nullptr, const XbMat3 *Ti = nullptr);
+// out [RE][n] = M^T v for general v: CSC as launch_spmv_t_eq, vw = v element-major [m][RE] (launch_aos_words); heavy_min, plan, nitems, ncols: the heavy
+// columns of the matrix as lf_ccs_load listed them (lf_spmv_t_plan.h), part: scratch of nitems * RE words
+void launch_spmv_t(const DevCrt &t, const u32 *colptr, const u32 *rowidx, const u64 *val, const u64 *vw, u64 *out, size_t n, u32 heavy_min, const u32 *plan,
+                   u32 nitems, u32 ncols, u64 *part, hipStream_t s);
 // dots: out[a][b] = sum_i X_a[i] (.) Y_b[i] (ring tables, slot-wise), a < na, b < nb -> out AoS [na][nb][24]
 void launch_dot_batch(const DevCrt &t, const u64 *X, size_t ldx, u32 na, const u64 *Y, size_t ldy, u32 nb, size_t n,
                       u64 *partial, u64 *out, hipStream_t s);

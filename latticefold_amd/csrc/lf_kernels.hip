@@ -161,6 +161,9 @@ void launch_coef_to_i32(const u64 *coef, int32_t *planes, size_t n, u32 bound, i
 }
 void launch_i32_to_coef(const int32_t *planes, u64 *coef, size_t n, hipStream_t s) { lfk::launch_i32_to_coef<GoldF>(planes, coef, n, s); }
 void launch_linf(const u64 *coef, size_t n, u64 *out_max, hipStream_t s) { lfk::launch_linf<GoldF>(coef, n, out_max, s); }
+void launch_fhat(const DevCrt &, const int32_t *planes, size_t N, size_t m, u64 *out, hipStream_t s) { lfk::launch_fhat<GoldF>(planes, N, m, out, s); }
+void launch_z_head(const u64 *x, size_t l, u64 *z, size_t n, hipStream_t s) { lfk::launch_z_head<GoldF>(x, l, z, n, s); }
+void launch_aos_words(const u64 *aos, u64 *dst, size_t n, hipStream_t s, u32 *flag, const XbMat3 *Ti) { lfk::launch_aos_words<GoldF>(aos, dst, n, s, flag, Ti); }
 
 
 struct BPow { u64 v[8]; };

@@ -541,6 +541,16 @@ struct ring_ops<Ring<C>> {
             HIPCHK(hipMemcpy(dcp, cp.data(), (n + 1) * 4, hipMemcpyHostToDevice));
             HIPCHK(hipMemcpy(dri, ri.data(), nnz * 4, hipMemcpyHostToDevice));
             HIPCHK(hipMemcpy(dvT, vT.data(), nnz * RE * sizeof(W), hipMemcpyHostToDevice));
+            std::vector<u32> plan;   // lf_spmv_t: the heavy columns of M_j as work items (lf_spmv_t_plan.h)
+            u32 nitems, ncols;
+            c->spmvt_min = c->spmvt_min_next;
+            lfk::spmv_t_plan(n, cp.data(), c->spmvt_min, &plan, &nitems, &ncols);
+            c->d_spmvt_plan.push_back(nullptr);
+            c->spmvt_items.push_back(nitems); c->spmvt_cols.push_back(ncols);
+            if (nitems) {
+                HIPCHK(lf_dev_malloc(&c->d_spmvt_plan.back(), plan.size() * 4));
+                HIPCHK(hipMemcpy(c->d_spmvt_plan.back(), plan.data(), plan.size() * 4, hipMemcpyHostToDevice));
+            }
         }
         if constexpr (R::general_csr) {
             const size_t rows_used = n < m ? n : m;
@@ -1299,6 +1309,180 @@ struct ring_ops<Ring<C>> {
             rc = (hv & (lfparts::FLAG_DIGIT | lfparts::FLAG_NOT_CANONICAL)) ? LF_ERR_INVALID : ((hv & lfparts::FLAG_NORM) ? LF_ERR_NORM : LF_ERR_UNSUPPORTED);
         if (rc != LF_OK) { lf_planes_release(R::owner(c), bytes, sum); return rc; }
         *out = new lf_witness{R::owner(c), sum, c->N, c->device, bytes};
+        return LF_OK;
+    }
+
+    // ---- witness tables (lfhip_tables.h): f-hat, z, M z, M^T v and fix_variables on tables, each ONE body for both spellings ----
+    // Order of the refusals, the same for all five: the ABI function's null / foreign-handle checks; here under the lock: a handle with another N ->
+    // LF_ERR_INVALID, no constraint system -> LF_ERR_STATE (not for fix_variables), index / count / length / a word >= p -> LF_ERR_INVALID, a sharded context -> LF_ERR_UNSUPPORTED, the pointer and overlap checks of a
+    // device array -> LF_ERR_INVALID; only then is anything allocated or enqueued.  None of the calls has a device input but spmv_t and fix_variables, whose
+    // results go into the caller's buffer behind the canonical-word flag like every other _dev result
+    static bool words_canonical(const u64 *w, size_t n) {
+        for (size_t i = 0; i < n; i++)
+            if (w[i] >= R::modulus) return false;
+        return true;
+    }
+    // Witness::get_fhat for `count` witnesses: table (w tau + j) of out = f-hat_j of wits[w]; one launch per witness, every word of out written once by it
+    static int witness_get_fhat(C *c, const lf_witness *const *wits, unsigned count, u64 *out, Origin org = Origin::host) {
+        std::lock_guard<std::mutex> g(c->mu);
+        for (unsigned w = 0; w < count && c->have_ccs; w++)   // (without a constraint system there is no N to compare with)
+            if (wits[w]->N != c->N) return LF_ERR_INVALID;
+        if (!c->have_ccs) return LF_ERR_STATE;
+        if (!count) return LF_ERR_INVALID;
+        if (c->sh_world > 1) return LF_ERR_UNSUPPORTED;
+        HIPCHK(hipSetDevice(c->device));
+        const size_t per = TAU * c->m;   // ring elements per witness
+        DevIo<C> io(c, org);
+        RET(io.array(out, count * per));
+        if (io.dev) {
+            for (unsigned w = 0; w < count; w++) launch_fhat(R::tab(c), wits[w]->planes, c->N, c->m, out + w * per * RE, c->stream());
+            HIPCHK(hipStreamSynchronize(c->stream()));
+            return LF_OK;
+        }
+        u64 *tmp;
+        RET(c->tbuf("stage_aos", per * RE, &tmp));
+        for (unsigned w = 0; w < count; w++) {   // (one stream: the next launch overwrites the stage only after the copy before it)
+            launch_fhat(R::tab(c), wits[w]->planes, c->N, c->m, tmp, c->stream());
+            HIPCHK(hipMemcpyAsync(out + w * per * RE, tmp, per * RE * 8, hipMemcpyDeviceToHost, c->stream()));
+        }
+        HIPCHK(hipStreamSynchronize(c->stream()));
+        return LF_OK;
+    }
+    // z = x || 1 || w_ccs of a witness as the plane table [RE][n] the SpMV launchers read (buffer "tab_z"); x: l elements, host, internal basis, canonical
+    static int z_planes(C *c, const lf_witness *w, const u64 *x, W **z_out) {
+        const size_t l = c->P.l, wl = c->P.wit_len, n = c->n;
+        W *z;
+        u64 *xs;
+        RET(c->tbuf("tab_z", n * RE, &z));
+        RET(c->tbuf("tab_x", (l + 1) * RE, &xs));
+        if (l) HIPCHK(hipMemcpyAsync(xs, x, l * RE * 8, hipMemcpyHostToDevice, c->stream()));
+        launch_z_head(xs, l, z, n, c->stream());
+        if (w->w_ccs && w->w_bytes == wl * RE * sizeof(W))   // materialised by the fold step that made this witness: planes [RE][wit_len]
+            HIPCHK(hipMemcpy2DAsync(z + l + 1, n * sizeof(W), w->w_ccs, wl * sizeof(W), wl * sizeof(W), RE, hipMemcpyDeviceToDevice, c->stream()));
+        else launch_recompose_crt(R::tab(c), w->planes, w->N, (u32)wl, c->P.L, c->P.B, 1, 0, z, n, l + 1, c->stream());
+        *z_out = z;
+        return LF_OK;
+    }
+    static int witness_tables_ready(C *c, const lf_witness *w, const u64 *x) {
+        if (c->have_ccs && w->N != c->N) return LF_ERR_INVALID;
+        if (!c->have_ccs) return LF_ERR_STATE;
+        if (!words_canonical(x, (size_t)c->P.l * RE)) return LF_ERR_INVALID;
+        return c->sh_world > 1 ? LF_ERR_UNSUPPORTED : LF_OK;
+    }
+    static int witness_get_z(C *c, const lf_witness *w, const u64 *x, u64 *out, Origin org = Origin::host) {
+        std::lock_guard<std::mutex> g(c->mu);
+        RET(witness_tables_ready(c, w, x));
+        HIPCHK(hipSetDevice(c->device));
+        DevIo<C> io(c, org);
+        RET(io.array(out, c->n));
+        W *z;
+        RET(z_planes(c, w, x, &z));
+        return down_ring(io, z, c->n, out, Form::ntt);
+    }
+    // calculate_Mz_mles (utils/mle_helpers.rs:137-146): table j of out = M_j z, one SpMV launch per matrix as lf_spmv runs it; on Goldilocks over the live rows
+    // only (lf_live_rows.h: the rows behind them are zeros of every M_j z -- one memset)
+    static int witness_mz(C *c, const lf_witness *w, const u64 *x, u64 *out, Origin org = Origin::host) {
+        std::lock_guard<std::mutex> g(c->mu);
+        RET(witness_tables_ready(c, w, x));
+        HIPCHK(hipSetDevice(c->device));
+        const size_t m = c->m, n = c->n;
+        const u32 t = c->P.t;
+        DevIo<C> io(c, org);
+        RET(io.array(out, t * m));
+        W *z, *od;
+        RET(c->tbuf("tab_mz", (size_t)t * RE * m, &od));
+        RET(z_planes(c, w, x, &z));
+        if constexpr (R::general_csr) {
+            const size_t live = c->live_rows < m ? c->live_rows : m;
+            W *zaos = nullptr;
+            if (c->ccs_general) RET(c->tbuf("spmv_zaos", n * RE, &zaos));
+            if (live < m) HIPCHK(hipMemsetAsync(od, 0, (size_t)t * RE * m * sizeof(W), c->stream()));
+            for (u32 j = 0; j < t; j++) {
+                W *oj = od + (size_t)j * RE * m;
+                if (c->ccs_general)   // (the element-major copy of z is made by the first launch and read by the others)
+                    launch_spmv_rows(R::tab(c), 1, &c->d_rowptr[j], &c->d_col[j], &c->d_val[j], j ? nullptr : z, 0, n, zaos, oj, m, 0, c->stream(), 0, live);
+                else launch_spmv(R::tab(c), c->d_rowptr[j], c->d_col[j], c->d_val[j], z, n, oj, m, 0, c->stream(), 0, live);
+            }
+        } else {
+            for (u32 j = 0; j < t; j++) launch_spmv(R::tab(c), c->d_rowptr[j], c->d_col[j], c->d_val[j], z, n, od + (size_t)j * RE * m, m, 0, c->stream());
+        }
+        if (io.dev) {
+            for (u32 j = 0; j < t; j++) store_ring(io, od + (size_t)j * RE * m, m, out + (size_t)j * m * RE, Form::ntt);
+            return io.finish();
+        }
+        for (u32 j = 0; j < t; j++) RET(down_ring(c, od + (size_t)j * RE * m, m, out + (size_t)j * m * RE, Form::ntt));
+        return LF_OK;
+    }
+    // out (n elements) = M_j^T v, v = m general ring elements (lf_spmv_t.cuh)
+    static int spmv_t(C *c, unsigned j, const u64 *v, u64 *out, Origin org = Origin::host) {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (!c->have_ccs) return LF_ERR_STATE;
+        if (j >= c->P.t) return LF_ERR_INVALID;
+        if (c->sh_world > 1) return LF_ERR_UNSUPPORTED;
+        if (org == Origin::host && !words_canonical(v, c->m * RE)) return LF_ERR_INVALID;
+        HIPCHK(hipSetDevice(c->device));
+        DevIo<C> io(c, org);
+        RET(io.array(v, c->m));
+        RET(io.array(out, c->n));
+        RET(io.disjoint(v, c->m, out, c->n));
+        W *vw, *od, *part;
+        RET(c->tbuf("io_a", c->m * RE, &vw));
+        RET(c->tbuf("io_b", c->n * RE, &od));
+        RET(c->tbuf("spmvt_part", (size_t)c->spmvt_items[j] * RE + 8, &part));
+        RET(io.begin());
+        const u64 *src = v;
+        if (!io.dev) {
+            u64 *tmp;
+            RET(c->tbuf("stage_aos", c->m * RE, &tmp));
+            HIPCHK(hipMemcpyAsync(tmp, v, c->m * RE * 8, hipMemcpyHostToDevice, c->stream()));
+            src = tmp;
+        }
+        const auto Ti = R::xb_mat(c->xb_Ti);
+        launch_aos_words(src, vw, c->m, c->stream(), io.flag, xb_converts(c, Form::ntt) ? &Ti : nullptr);
+        launch_spmv_t(R::tab(c), c->d_colptr[j], c->d_rowidx[j], c->d_valT[j], vw, od, c->n, c->spmvt_min, c->d_spmvt_plan[j], c->spmvt_items[j], c->spmvt_cols[j],
+                      part, c->stream());
+        return down_ring(io, od, c->n, out, Form::ntt);
+    }
+    // DenseMultilinearExtension::fix_variables on `ntables` tables of len = 2^nv entries: the lowest nfix variables, one R::fix per variable, ping-pong between two
+    // scratch tables (leading dimensions as in the generic sumcheck); works on a bare context
+    static int mle_fix_variables(C *c, const u64 *tables, size_t ntables, size_t len, const u64 *point, unsigned nfix, u64 *out, Origin org = Origin::host) {
+        if (!ntables || len < 2 || (len & (len - 1)) || !nfix || nfix >= 64 || ((size_t)1 << nfix) > len) return LF_ERR_INVALID;
+        if (!words_canonical(point, (size_t)nfix * TAU)) return LF_ERR_INVALID;
+        std::lock_guard<std::mutex> g(c->mu);
+        if (c->sh_world > 1) return LF_ERR_UNSUPPORTED;
+        if (org == Origin::host && !words_canonical(tables, ntables * len * RE)) return LF_ERR_INVALID;
+        HIPCHK(hipSetDevice(c->device));
+        const size_t len_out = len >> nfix;
+        DevIo<C> io(c, org);
+        RET(io.array(tables, ntables * len));
+        RET(io.array(out, ntables * len_out));
+        RET(io.disjoint(tables, ntables * len, out, ntables * len_out));
+        W *tab[2];
+        RET(c->tbuf("fx_tab0", ntables * RE * len, &tab[0]));
+        RET(c->tbuf("fx_tab1", ntables * RE * R::halved_ld(len / 2), &tab[1]));
+        RET(io.begin());
+        for (size_t a = 0; a < ntables; a++) RET(up_ring(io, tables + a * len * RE, len, tab[0] + a * RE * len, Form::ntt));
+        size_t n = len, ld = len;
+        int cur = 0;
+        for (unsigned i = 0; i < nfix; i++) {
+            const ExtC r = R::ext_const(c, R::ext_load(point + TAU * i));
+            const size_t ldo = R::halved_ld(n / 2);
+            for (size_t a0 = 0; a0 < ntables; a0 += 4096) {   // (a launch takes rows in its grid's y: at most 65535 / 8 tables at a time)
+                const size_t na = ntables - a0 < 4096 ? ntables - a0 : 4096;
+                R::fix(c, tab[cur] + a0 * RE * ld, ld, tab[cur ^ 1] + a0 * RE * ldo, ldo, n, (u32)(na * 8), r);
+            }
+            cur ^= 1; n /= 2; ld = ldo;
+        }
+        const W *res = tab[cur];
+        if (ld != n) {   // (a leading dimension padded beyond the length: the planes move together for the relayout, which takes ld == n)
+            HIPCHK(hipMemcpy2DAsync(tab[cur ^ 1], n * sizeof(W), tab[cur], ld * sizeof(W), n * sizeof(W), ntables * RE, hipMemcpyDeviceToDevice, c->stream()));
+            res = tab[cur ^ 1];
+        }
+        if (io.dev) {
+            for (size_t a = 0; a < ntables; a++) store_ring(io, res + a * RE * n, n, out + a * n * RE, Form::ntt);
+            return io.finish();
+        }
+        for (size_t a = 0; a < ntables; a++) RET(down_ring(c, res + a * RE * n, n, out + a * n * RE, Form::ntt));
         return LF_OK;
     }
 

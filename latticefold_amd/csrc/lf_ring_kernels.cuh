@@ -43,6 +43,8 @@ static inline unsigned grid_for(size_t n, unsigned cap = 2048) {
 // XBASIS: the context is in an external basis of F_{p^TAU} (lf_set_ext_basis).  Between the two passes over the tile every (element, slot) is multiplied by the
 // matrix M (F::xb_slot_pass), in place in the tile: M = T^-1 on the way in, after the canonical test has seen the caller's own words, M = T on the way out,
 // before the AoS write.
+// ELEM (aos_to_soa only): the destination is element-major device words [n][RE] (launch_aos_words: the operand k_spmv_t gathers whole elements from) instead of
+// the plane table -- the same tile, canonical test and basis pass, only the store differs.
 // Opt: the kernel arguments behind (src, dst, n) -- the flag word if CHECKED / UNLESS, then the matrix (by value: wave-uniform) if XBASIS.  Only what an
 // instantiation reads is passed; opt_arg picks by type.
 template <class T, class U, class... Rest>
@@ -50,7 +52,7 @@ __device__ __forceinline__ const T &opt_arg(const U &u, const Rest &...rest) {
     if constexpr (std::is_same<T, U>::value) return u;
     else return opt_arg<T>(rest...);
 }
-template <class F, bool CHECKED, bool XBASIS>
+template <class F, bool CHECKED, bool XBASIS, bool ELEM = false>
 __device__ __forceinline__ void aos_to_soa_tile(const u64 *aos, typename F::word *soa, size_t n, u32 *flag, const typename F::XbMat *M) {
     constexpr int RE = F::RE;
     __shared__ typename F::word tile[64][RE + 1];
@@ -69,6 +71,13 @@ __device__ __forceinline__ void aos_to_soa_tile(const u64 *aos, typename F::word
     if (XBASIS) {
         F::xb_slot_pass(tile, *M);
         __syncthreads();
+    }
+    if constexpr (ELEM) {
+        for (int idx = threadIdx.x; idx < 64 * RE; idx += 256) {
+            const size_t e = base + idx / RE;
+            if (e < n) soa[e * RE + idx % RE] = tile[idx / RE][idx % RE];
+        }
+        return;
     }
     for (int idx = threadIdx.x; idx < 64 * RE; idx += 256) {
         int w = idx / 64, j = idx % 64;
@@ -94,14 +103,14 @@ __device__ __forceinline__ void soa_to_aos_tile(const typename F::word *soa, u64
         if (e < n) aos[e * RE + idx % RE] = F::to_canon(tile[idx / RE][idx % RE]);   // (Goldilocks: the tile word as it is)
     }
 }
-template <class F, bool CHECKED, bool XBASIS, class... Opt>
+template <class F, bool CHECKED, bool XBASIS, bool ELEM = false, class... Opt>
 __global__ void __launch_bounds__(256) k_aos_to_soa(const u64 *aos, typename F::word *soa, size_t n, Opt... opt) {
     static_assert(sizeof...(Opt) == (CHECKED ? 1 : 0) + (XBASIS ? 1 : 0), "flag if CHECKED, matrix if XBASIS");
     u32 *flag = nullptr;
     const typename F::XbMat *M = nullptr;
     if constexpr (CHECKED) flag = opt_arg<u32 *>(opt...);
     if constexpr (XBASIS) M = &opt_arg<typename F::XbMat>(opt...);
-    aos_to_soa_tile<F, CHECKED, XBASIS>(aos, soa, n, flag, M);
+    aos_to_soa_tile<F, CHECKED, XBASIS, ELEM>(aos, soa, n, flag, M);
 }
 template <class F, bool UNLESS, bool XBASIS, class... Opt>
 __global__ void __launch_bounds__(256) k_soa_to_aos(const typename F::word *soa, u64 *aos, size_t n, Opt... opt) {
@@ -416,5 +425,74 @@ __device__ __forceinline__ void fw_tables(int32_t (*R)[2][NQ][16][28], u32 K, co
 }
 // The kernel itself stays with the ring: its last step, the wrap of positions >= D, differs (in registers on X^24 = X^12 - 1, on the stored values on
 // X^72 = X^36 - 1), and as a call from a shared shell it changes the schedule of the whole kernel (Goldilocks, NQ = 4: 332 VGPRs instead of 120).
+
+// ---------------------------------------------------------------------------------------------------------
+// witness tables (lfhip_tables.h)
+// Witness::get_fhat (arith.rs:273-297): the TAU tables f-hat_j of one witness from its centred int32 planes [RE][N], straight into the caller's layout --
+// out [TAU][m][RE] canonical AoS words, entry i of table j = the ring element whose slot k is the base-field constant f_coeff[i][8 j + k] (word TAU k holds
+// it, the other words of the slot are 0), entries N <= i < m zero.  A pure write stream: block = (64 entries, one table): the 8 x 64 coefficients come in
+// as eight 256-byte runs into LDS, the 64 RE words leave as one run of consecutive u64, every word written once -- two words (16 bytes) per lane and store
+// where `out` is 16-byte aligned (V2; RE is even, so a pair never straddles two entries), one word otherwise.  A negative coefficient c leaves as p - |c|
+// (the u64 sum below wraps to it).  An external basis changes nothing here: its matrix keeps e_0 (column 0 = e_0, ExtBasis::set), and a constant slot is
+// c e_0.
+constexpr int FHAT_TILE = 64;
+template <class F>
+__device__ __forceinline__ u64 fhat_word(const int32_t (*cf)[FHAT_TILE + 1], int e, int w) {
+    const int32_t c = cf[w / F::TAU][e];
+    return w % F::TAU ? 0 : (u64)(int64_t)c + (c < 0 ? (u64)F::P : 0);
+}
+template <class F, bool V2>
+__global__ void __launch_bounds__(256) k_fhat(const int32_t *planes, size_t N, size_t m, u64 *out) {
+    constexpr int RE = F::RE, TAU = F::TAU;
+    static_assert(RE == 8 * TAU && RE % 2 == 0 && 8 * FHAT_TILE == 2 * 256, "eight slots; pairs of words; two loads per thread");
+    __shared__ int32_t cf[8][FHAT_TILE + 1];
+    const size_t i0 = (size_t)blockIdx.x * FHAT_TILE, j = blockIdx.y;
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const int k = threadIdx.x / FHAT_TILE + 4 * h, i = threadIdx.x % FHAT_TILE;   // 256 threads = 4 planes x 64 entries, twice
+        cf[k][i] = i0 + i < N ? planes[(8 * j + k) * N + i0 + i] : 0;
+    }
+    __syncthreads();
+    u64 *dst = out + (j * m + i0) * RE;
+    const size_t left = m - i0 < (size_t)FHAT_TILE ? m - i0 : (size_t)FHAT_TILE;   // entries of this tile
+    if constexpr (V2) {
+        for (int idx = 2 * threadIdx.x; idx < (int)left * RE; idx += 512) {
+            const int e = idx / RE, w = idx % RE;
+            *(ulonglong2 *)(dst + idx) = make_ulonglong2(fhat_word<F>(cf, e, w), fhat_word<F>(cf, e, w + 1));
+        }
+    } else {
+        for (int idx = threadIdx.x; idx < (int)left * RE; idx += 256) dst[idx] = fhat_word<F>(cf, idx / RE, idx % RE);
+    }
+}
+template <class F>
+void launch_fhat(const int32_t *planes, size_t N, size_t m, u64 *out, hipStream_t s) {
+    const dim3 g(cdiv(m, FHAT_TILE), F::TAU), b(256);
+    if (((uintptr_t)out & 15) == 0) hipLaunchKernelGGL((k_fhat<F, true>), g, b, 0, s, planes, N, m, out);
+    else hipLaunchKernelGGL((k_fhat<F, false>), g, b, 0, s, planes, N, m, out);
+}
+// z = x || 1 || w_ccs (arith.rs:399-409) as the plane table [RE][n] the SpMV launchers read: the head, entries [0, l] -- x from l staged elements of canonical
+// AoS words, then the ring's one; the tail is written in place by launch_recompose_crt (or copied from the witness's own w_ccs planes)
+template <class F>
+__global__ void __launch_bounds__(256) k_z_head(const u64 *x, size_t l, typename F::word *z, size_t n) {
+    constexpr int RE = F::RE, TAU = F::TAU;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (l + 1) * RE) return;
+    const size_t w = idx / (l + 1), i = idx % (l + 1);
+    z[w * n + i] = i < l ? F::from_canon(x[i * RE + w]) : (w % TAU ? typename F::word(0) : F::one());
+}
+template <class F>
+void launch_z_head(const u64 *x, size_t l, typename F::word *z, size_t n, hipStream_t s) {
+    hipLaunchKernelGGL(k_z_head<F>, dim3(cdiv((l + 1) * F::RE, 256)), dim3(256), 0, s, x, l, z, n);
+}
+// [n][RE] canonical u64 -> [n][RE] device words, element-major: k_aos_to_soa with the ELEM store (flag, Ti as for launch_aos_to_soa)
+template <class F>
+void launch_aos_words(const u64 *aos, typename F::word *dst, size_t n, hipStream_t s, u32 *flag, const typename F::XbMat *Ti) {
+    if (!n) return;
+    const dim3 g(cdiv(n, 64)), b(256);
+    if (flag && Ti) hipLaunchKernelGGL((k_aos_to_soa<F, true, true, true>), g, b, 0, s, aos, dst, n, flag, *Ti);
+    else if (flag) hipLaunchKernelGGL((k_aos_to_soa<F, true, false, true>), g, b, 0, s, aos, dst, n, flag);
+    else if (Ti) hipLaunchKernelGGL((k_aos_to_soa<F, false, true, true>), g, b, 0, s, aos, dst, n, *Ti);
+    else hipLaunchKernelGGL((k_aos_to_soa<F, false, false, true>), g, b, 0, s, aos, dst, n);
+}
 
 }  // namespace lfk

@@ -13,6 +13,7 @@
 
 #include "lf_kernels_dev.cuh"
 #include "lf_ring_mul.cuh"
+#include "lf_spmv_t.cuh"
 
 namespace lf {
 
@@ -57,6 +58,12 @@ void launch_ring_mul_ntt(const DevCrt &t, const u64 *a, const u64 *b, size_t n_t
 void launch_ring_mul_coeff(const DevCrt &t, const u64 *icrt_mat, const u64 *a, const u64 *b, size_t n_terms, size_t n, u64 *out, hipStream_t s) {
     if (t.nu2p40) lfk::launch_ring_mul_coeff<GoldMul<true>>(t, icrt_mat, a, b, n_terms, n, out, s);
     else lfk::launch_ring_mul_coeff<GoldMul<false>>(t, icrt_mat, a, b, n_terms, n, out, s);
+}
+// M^T v for general v (lf_spmv_t.cuh): instantiated here because the lazy sum of slot products is this file's field policy
+void launch_spmv_t(const DevCrt &t, const u32 *colptr, const u32 *rowidx, const u64 *val, const u64 *vw, u64 *out, size_t n, u32 heavy_min, const u32 *plan,
+                   u32 nitems, u32 ncols, u64 *part, hipStream_t s) {
+    if (t.nu2p40) lfk::launch_spmv_t<GoldF, GoldMul<true>>(t, colptr, rowidx, val, vw, out, n, heavy_min, plan, nitems, ncols, part, s);
+    else lfk::launch_spmv_t<GoldF, GoldMul<false>>(t, colptr, rowidx, val, vw, out, n, heavy_min, plan, nitems, ncols, part, s);
 }
 
 }  // namespace lf

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Generates the raw Rust binding of the C ABI (`latticefold-hip-sys/src/lib.rs`) from include/lfhip.h and include/lfplus.h, and its modules `parts`
 (`src/parts.rs`) from include/lfhip_parts.h, the file lfhip.h includes for the entry points of the decomposed witnesses, and `sumcheck` (`src/sumcheck.rs`)
-from include/lfhip_sumcheck.h, the one for the generic sumcheck, and `prover` (`src/prover.rs`) from include/lfhip_prover.h, the one for the chained prover object.
+from include/lfhip_sumcheck.h, the one for the generic sumcheck, `prover` (`src/prover.rs`) from include/lfhip_prover.h, the one for the chained prover object,
+and `tables` (`src/tables.rs`) from include/lfhip_tables.h, the one for the witness tables.
 
     python tools/gen_rust_bindings.py            print the binding
     python tools/gen_rust_bindings.py --write    rewrite bindings/latticefold-hip-sys/src/lib.rs and the block between the
-                                                 GENERATED markers of INTEGRATION.md; the same for src/parts.rs, src/sumcheck.rs, src/prover.rs and their markers
+                                                 GENERATED markers of INTEGRATION.md; the same for src/parts.rs, src/sumcheck.rs, src/prover.rs, src/tables.rs and their markers
 
 The reference is safe Rust with `#![forbid(unsafe_code)]` (crates/latticefold/src/lib.rs:4): the `extern "C"` block lives in a new
 `-sys` crate.  No Rust toolchain exists in the build image, so the text is derived mechanically from the headers (every prototype, the
@@ -29,6 +30,9 @@ SUMCHECK_BEGIN, SUMCHECK_END = "<!-- BEGIN GENERATED BINDING: sumcheck (tools/ge
 PROVER_HEADER = "include/lfhip_prover.h"
 PROVER_OUT = os.path.join(ROOT, "bindings", "latticefold-hip-sys", "src", "prover.rs")
 PROVER_BEGIN, PROVER_END = "<!-- BEGIN GENERATED BINDING: prover (tools/gen_rust_bindings.py) -->", "<!-- END GENERATED BINDING: prover -->"
+TABLES_HEADER = "include/lfhip_tables.h"
+TABLES_OUT = os.path.join(ROOT, "bindings", "latticefold-hip-sys", "src", "tables.rs")
+TABLES_BEGIN, TABLES_END = "<!-- BEGIN GENERATED BINDING: tables (tools/gen_rust_bindings.py) -->", "<!-- END GENERATED BINDING: tables -->"
 
 SCALARS = {
     "int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "char": "c_char", "float": "f32", "double": "f64", "void": "c_void",
@@ -161,7 +165,9 @@ def generate():
           "/// include/lfhip_sumcheck.h (included by lfhip.h): MLSumcheck over any sum of products of MLE tables -- `sumcheck::lf_mlsumcheck_prove`, ...",
           "pub mod sumcheck;",
           "/// include/lfhip_prover.h (included by lfhip.h): the chained NIFS prover object -- `prover::lf_prover_create`, `prover::lf_prover_prove`, ...",
-          "pub mod prover;", ""]
+          "pub mod prover;",
+          "/// include/lfhip_tables.h (included by lfhip.h): f-hat, z, M z, M^T v and fix_variables from a witness handle -- `tables::lf_witness_get_fhat`, ...",
+          "pub mod tables;", ""]
     return "\n".join(L), allfns
 
 
@@ -217,6 +223,22 @@ def generate_prover():
     return "\n".join(L), [f[0] for f in fns]
 
 
+def generate_tables():
+    """src/tables.rs: the entry points of include/lfhip_tables.h, over the types of the crate root"""
+    _, fns = parse(TABLES_HEADER)
+    L = [f"// GENERATED by tools/gen_rust_bindings.py from {TABLES_HEADER} -- do not edit.",
+         "// Module `tables` of latticefold-hip-sys: the protocol's own tables from a witness handle (f-hat, z, M z), M^T v and fix_variables on tables; the",
+         "// array arguments of the *_device functions are the caller's device memory.",
+         "use core::ffi::{c_int, c_uint};", "",
+         "use super::{lf_ctx, lf_witness};", "",
+         '#[link(name = "lfhip")]', 'extern "C" {']
+    for name, params, ret in fns:
+        ps = ", ".join(f"{n}: {t}" for n, t in params)
+        L.append(f"    pub fn {name}({ps})" + (f" -> {ret}" if ret else "") + ";")
+    L += ["}", ""]
+    return "\n".join(L), [f[0] for f in fns]
+
+
 def main():
     text, fns = generate()
     if "--write" in sys.argv:
@@ -248,12 +270,20 @@ def main():
             a, b = doc.index(PROVER_BEGIN) + len(PROVER_BEGIN), doc.index(PROVER_END)
             open(DOC, "w").write(doc[:a] + "\n```rust\n" + rtext + "```\n" + doc[b:])
         print(f"{len(rfns)} functions -> {os.path.relpath(PROVER_OUT, ROOT)}")
+        ttext, tfns = generate_tables()
+        open(TABLES_OUT, "w").write(ttext)
+        doc = open(DOC).read()
+        if TABLES_BEGIN in doc and TABLES_END in doc:
+            a, b = doc.index(TABLES_BEGIN) + len(TABLES_BEGIN), doc.index(TABLES_END)
+            open(DOC, "w").write(doc[:a] + "\n```rust\n" + ttext + "```\n" + doc[b:])
+        print(f"{len(tfns)} functions -> {os.path.relpath(TABLES_OUT, ROOT)}")
         print(f"{len(fns)} functions -> {os.path.relpath(OUT, ROOT)}" + (", INTEGRATION.md" if BEGIN in doc else ""))
     else:
         sys.stdout.write(text)
         sys.stdout.write(generate_parts()[0])
         sys.stdout.write(generate_sumcheck()[0])
         sys.stdout.write(generate_prover()[0])
+        sys.stdout.write(generate_tables()[0])
 
 
 if __name__ == "__main__":
