@@ -4,6 +4,7 @@ same seeded inputs.  Run on the MI355X box with `pytest -m gpu`."""
 import numpy as np
 import pytest
 
+import fold_paths
 import lfo_bb as lfo
 from latticefold_amd import api
 from latticefold_amd.workload import chain_w_ccs, diag, make_workload, splitmix_fq
@@ -295,26 +296,25 @@ def test_fold_step_fused_fix_rounds_match_oracle(ctx, name, monkeypatch):
     separate k_fix pass: identical proofs, equal to the oracle's"""
     wl, inst, A, f_coeff, wit, cccs, acc_g, _, acc_o, _ = run_both(ctx, name, 2)
     lc_o, f0_o, proof_o = inst.fold_step(lfo.Transcript(), A, acc_o, f_coeff, cccs, f_coeff)
-    monkeypatch.setenv("LF_FOLD_FUSE_MIN", "4")
-    monkeypatch.setenv("LF_FOLD_NO_LUT", "1")
-    lc_f, w_f, proof_f = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, tr_new())
+    with fold_paths.applied(monkeypatch, fold_paths.BB_FUSED_FIX):
+        lc_f, w_f, proof_f = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, tr_new())
     # rounds 3 and 4 from the 81-entry digit look-up table instead of materialised m/4-entry tables (large instances by default)
-    monkeypatch.delenv("LF_FOLD_NO_LUT")
-    monkeypatch.setenv("LF_FOLD_LUT_MIN", "1")
+    for key, val in fold_paths.BB_FUSED_LUT.items():
+        monkeypatch.setenv(key, val)
     lc_l, w_l, proof_l = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, tr_new())
     # rounds 4 / 5 from the product-free tables over the digit codes (modes 6 / 7), round 5 on the stored round-4 tables, and the older modes 4 / 1
-    for extra in ({"LF_FOLD_R5_MIN": "1"}, {"LF_FOLD_NO_R5TAB": "1"}, {"LF_FOLD_NO_R4TAB": "1"}):
+    for extra in fold_paths.BB_FUSED_LUT_EXTRAS:
         for key, val in extra.items():
             monkeypatch.setenv(key, val)
         lc_x, w_x, proof_x = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, tr_new())
         for key in extra:
             monkeypatch.delenv(key)
         assert (proof_x == proof_o).all() and (lc_x == lc_o).all() and (w_x.f == f0_o).all(), extra
-    monkeypatch.delenv("LF_FOLD_LUT_MIN")
-    monkeypatch.delenv("LF_FOLD_FUSE_MIN")
-    monkeypatch.setenv("LF_FOLD_UNFUSED", "1")
-    monkeypatch.setenv("LF_THETA_EVAL", "1")       # theta from evaluate_mles-style sums instead of the last fix of the sumcheck tables
-    monkeypatch.setenv("LF_LIN_U_EVAL", "1")       # likewise u of the linearization
+    for key in fold_paths.BB_FUSED_LUT:
+        monkeypatch.delenv(key)
+    # the separate k_fix pass; theta from evaluate_mles-style sums instead of the last fix of the sumcheck tables, likewise u of the linearization
+    for key, val in fold_paths.UNFUSED_EVAL.items():
+        monkeypatch.setenv(key, val)
     lc_u, w_u, proof_u = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, tr_new())
     assert (proof_f == proof_o).all() and (lc_f == lc_o).all() and (w_f.f == f0_o).all()
     assert (proof_l == proof_o).all() and (lc_l == lc_o).all() and (w_l.f == f0_o).all()
@@ -328,10 +328,10 @@ def test_fold_step_gemm_rounds_match_oracle(ctx, name, monkeypatch):
     equal to the oracle's (nifs/folding/utils.rs:273-325, utils/sumcheck/prover.rs:56-162)"""
     wl, inst, A, f_coeff, wit, cccs, acc_g, _, acc_o, _ = run_both(ctx, name, 2)
     lc_o, f0_o, proof_o = inst.fold_step(lfo.Transcript(), A, acc_o, f_coeff, cccs, f_coeff)
-    monkeypatch.setenv("LF_FOLD_SV_MIN", "64")
+    for k, v in fold_paths.BB_GEMM_BASE.items():
+        monkeypatch.setenv(k, v)
     m = 1 << wl.s
-    for rounds, extra in ((1, {}), (2, {}), (3, {}), (3, {"LF_FOLD_LUT_MIN": "1", "LF_FOLD_FUSE_MIN": "4"}), (2, {"LF_FOLD_LUT_MIN": "1", "LF_FOLD_FUSE_MIN": "4", "LF_FOLD_R5_MIN": "1"}),
-                          (3, {"LF_FOLD_UNFUSED": "1"}), (3, {"LF_FOLD_LUT_MIN": "1", "LF_FOLD_FUSE_MIN": "4", "LF_FOLD_NO_R4TAB": "1"})):
+    for rounds, extra in fold_paths.BB_GEMM_CASES:
         monkeypatch.setenv("LF_FOLD_SV_ROUNDS", str(rounds))
         for k, v in extra.items():
             monkeypatch.setenv(k, v)
@@ -342,7 +342,8 @@ def test_fold_step_gemm_rounds_match_oracle(ctx, name, monkeypatch):
         assert ctx.fold_paths() == want, (rounds, extra, ctx.fold_paths(), want)
         bad = np.nonzero((proof != proof_o).any(axis=1))[0]
         assert bad.size == 0 and (lc == lc_o).all() and (w.f == f0_o).all(), (rounds, extra, bad[:6])
-    monkeypatch.setenv("LF_FOLD_NO_SV", "1")
+    for k, v in fold_paths.GEMM_OFF.items():
+        monkeypatch.setenv(k, v)
     lc, w, proof = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, tr_new())
     assert ctx.fold_paths() == 0 and (proof == proof_o).all()
 
@@ -355,10 +356,9 @@ def test_fold_step_split_table_rounds_match_oracle(ctx, name, monkeypatch):
     wl, inst, A, f_coeff, wit, cccs, acc_g, _, acc_o, _ = run_both(ctx, name, 4)
     lc_o, f0_o, proof_o = inst.fold_step(lfo.Transcript(), A, acc_o, f_coeff, cccs, f_coeff)
     m = 1 << wl.s
-    base = {"LF_FOLD_LUT_MIN": "1", "LF_FOLD_FUSE_MIN": "4", "LF_FOLD_SPLIT_MIN": "1"}
+    base = fold_paths.BB_SPLIT_BASE
     # (round 5 from the planes: two lanes per pair, unsplit -- k_fold_round5_2l)
-    cases = [({}, 0b01000), ({"LF_FOLD_R5_MIN": "1"}, 0b01000), ({"LF_FOLD_R5_MIN": "1", "LF_FOLD_SV_MIN": "64"}, 0b01000),
-             ({"LF_FOLD_R5_MIN": "1", "LF_FOLD_ROUNDS_NO_SPLIT": "1"}, 0), ({"LF_FOLD_NO_R4TAB": "1"}, 0)]
+    cases = fold_paths.BB_SPLIT_CASES
     for extra, want in cases:
         env = dict(base, **extra)
         for k, v in env.items():
@@ -379,9 +379,11 @@ def test_fold_step_int8_inner_products_match_oracle(ctx, name, monkeypatch):
     threshold) and on the VALU kernel: identical proofs, equal to the oracle's"""
     wl, inst, A, f_coeff, wit, cccs, acc_g, _, acc_o, _ = run_both(ctx, name, 3)
     lc_o, f0_o, proof_o = inst.fold_step(lfo.Transcript(), A, acc_o, f_coeff, cccs, f_coeff)
-    monkeypatch.setenv("LF_DOT_MIN", "64")
+    for k, v in fold_paths.BB_DOT_I8.items():
+        monkeypatch.setenv(k, v)
     lc_i, w_i, proof_i = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, tr_new())
-    monkeypatch.setenv("LF_DOT_VALU", "1")
+    for k, v in fold_paths.BB_DOT_VALU.items():
+        monkeypatch.setenv(k, v)
     lc_v, w_v, proof_v = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, tr_new())
     assert (proof_i == proof_o).all() and (lc_i == lc_o).all() and (w_i.f == f0_o).all()
     assert (proof_v == proof_o).all() and (lc_v == lc_o).all()
@@ -518,11 +520,12 @@ def test_fold_step_with_another_nonresidue(ctx, monkeypatch):
         rc, _ = inst.verify(lfo.Transcript(), acc_g, cccs, proof_g)
         assert rc == 0
         # the look-up-table / fused forms of rounds 3-6 in their generic-nu instantiations
-        monkeypatch.setenv("LF_FOLD_LUT_MIN", "1")
-        monkeypatch.setenv("LF_FOLD_FUSE_MIN", "4")
+        for k, v in fold_paths.BB_NU_LUT.items():
+            monkeypatch.setenv(k, v)
         lc_l, w_l, proof_l = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, tr_new())
         assert (proof_l == proof_o).all() and (lc_l == lc_o).all() and (w_l.f == f0_o).all()
-        monkeypatch.setenv("LF_FOLD_R5_MIN", "1")      # ... and round 5 from the planes (mode 7)
+        for k, v in fold_paths.BB_NU_LUT_R5.items():   # ... and round 5 from the planes (mode 7)
+            monkeypatch.setenv(k, v)
         lc_l, w_l, proof_l = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, tr_new())
         assert (proof_l == proof_o).all() and (lc_l == lc_o).all() and (w_l.f == f0_o).all()
     finally:

@@ -5,22 +5,11 @@ import numpy as np
 import pytest
 
 import lfo
+from fold_paths import A3P_BASE as BASE, A3P_PATHS as PATHS     # the switch sets: rounds 1..3 as GEMMs, then modes 6 / 7 / 1, split and plain
 from latticefold_amd import api
 from latticefold_amd.workload import make_workload
 
 pytestmark = pytest.mark.gpu
-
-# rounds 1..3 as GEMMs (the split form of the table rounds hangs on their eq tables), rounds 4.. per launch from the digit look-up tables / with the fused fix
-BASE = {"LF_FOLD_SV_MIN": "64", "LF_DOT_MIN": "64", "LF_FOLD_SV_ROUNDS": "3", "LF_FOLD_LUT_MIN": "1", "LF_FOLD_FUSE_MIN": "4", "LF_NO_TAIL": "1"}
-# name -> (switches, round 5 on the planes?, split form asked for?)
-#   round 4 is mode 6 in every case (storing its tables only when round 5 does not run on the planes); round 5 is mode 7 or the fused fix (mode 1); rounds 6.. mode 1,
-#   which the driver never runs in the split form
-PATHS = {
-    "m6+m7+m1 split": ({"LF_FOLD_R5_MIN": "1", "LF_FOLD_SPLIT_MIN": "1"}, True, True),
-    "m6+m7+m1 plain": ({"LF_FOLD_R5_MIN": "1", "LF_FOLD_ROUNDS_NO_SPLIT": "1"}, True, False),
-    "m6(stored)+m1 split": ({"LF_FOLD_NO_R5TAB": "1", "LF_FOLD_SPLIT_MIN": "1"}, False, True),
-    "m6(stored)+m1 plain": ({"LF_FOLD_NO_R5TAB": "1", "LF_FOLD_ROUNDS_NO_SPLIT": "1"}, False, False),
-}
 
 
 @pytest.fixture(scope="module")

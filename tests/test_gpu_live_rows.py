@@ -11,14 +11,12 @@ import numpy as np
 import pytest
 
 import lfo
+from fold_paths import LIVE_LOW as LOW, LIVE_OFF, LIVE_SPLIT as SPLIT, LIVE_TAIL_N as TAIL_N     # LF_LIVE_ROWS_LOW + LF_TAIL_N = 64; ... + LF_LIN_SPLIT_MIN = 16
 from latticefold_amd import api
 from latticefold_amd.workload import make_workload
 
 pytestmark = pytest.mark.gpu
 
-TAIL_N = 64
-LOW = {"LF_LIVE_ROWS_LOW": "1", "LF_TAIL_N": str(TAIL_N)}
-SPLIT = dict(LOW, LF_LIN_SPLIT_MIN="16")
 G = 8   # granule under LF_LIVE_ROWS_LOW
 
 
@@ -139,7 +137,7 @@ def test_live_rows_match_the_oracle_and_the_whole_tables(name, ccs, kind, env, m
     ref = _reference(name, ccs, kind)
     wl = ref[0]
     on = _run(wl, env, monkeypatch)
-    off = _run(wl, dict(env, LF_NO_LIVE_ROWS="1"), monkeypatch)
+    off = _run(wl, dict(env, **LIVE_OFF), monkeypatch)
     want = _oracle(ref, on["cccs"], on["A"])
     # the count lf_ccs_load keeps, and the rounds that really ran on a prefix
     live = _numpy_live_rows(wl)

@@ -3,6 +3,7 @@
 import numpy as np
 import pytest
 
+import fold_paths
 import lfo
 from latticefold_amd import api
 from latticefold_amd.workload import P, RE, diag, make_workload, splitmix_fq
@@ -312,34 +313,30 @@ def test_fold_step_fused_fix_rounds_match_oracle(ctx, name, monkeypatch):
     separate k_fix pass: identical proofs, both equal to the oracle's."""
     wl, inst, A, f_coeff, wit, cccs, acc_g, _, acc_o, _ = run_both(ctx, name, 2)
     lc_o, f0_o, proof_o = inst.fold_step(lfo.Transcript(), A, acc_o, f_coeff, cccs, f_coeff)
-    monkeypatch.setenv("LF_NO_TAIL", "1")          # per-round launches for every round (the persistent tail has its own test below)
-    monkeypatch.setenv("LF_FOLD_FUSE_MIN", "4")
-    monkeypatch.setenv("LF_FOLD_NO_LUT", "1")
-    lc_f, w_f, proof_f = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, api.PoseidonTranscript())
+    for key, val in fold_paths.FUSED_TAIL_OFF.items():     # per-round launches for every round (the persistent tail has its own test below)
+        monkeypatch.setenv(key, val)
+    with fold_paths.applied(monkeypatch, fold_paths.FUSED_FIX):
+        lc_f, w_f, proof_f = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, api.PoseidonTranscript())
     # rounds 3 and 4 from the 81-entry digit look-up table instead of materialised m/4-entry tables (large instances by default)
-    monkeypatch.delenv("LF_FOLD_NO_LUT")
-    monkeypatch.setenv("LF_FOLD_LUT_MIN", "1")
-    monkeypatch.setenv("LF_FOLD_TAB_MIN", "1")     # ... and rounds 1-2 as gathers from the per-table coefficient tables
-    monkeypatch.setenv("LF_FOLD_TAB_R1", "1")
+    # ... and rounds 1-2 as gathers from the per-table coefficient tables
+    for key, val in fold_paths.FUSED_LUT_TAB.items():
+        monkeypatch.setenv(key, val)
     lc_l, w_l, proof_l = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, api.PoseidonTranscript())
     # the product-free forms of rounds 4 and 5 (modes 6 and 7: squares and mu products of the fixed look-up values from tables over the digit codes),
     # with round 5 still on the planes / on the stored round-4 tables / both through the older modes 4 and 1
     # (LF_FOLD_SPLIT_MIN=1: rounds 4 / 5 in the split form -- three sums per slot, the host completes the message -- at this size too)
-    for extra in ({"LF_FOLD_R5_MIN": "1"}, {"LF_FOLD_R5_MIN": "1", "LF_FOLD_SPLIT_MIN": "1"}, {"LF_FOLD_NO_R5TAB": "1"}, {"LF_FOLD_NO_R5TAB": "1", "LF_FOLD_SPLIT_MIN": "1"},
-                  {"LF_FOLD_NO_R4TAB": "1"}):
+    for extra in fold_paths.FUSED_LUT_EXTRAS:
         for key, val in extra.items():
             monkeypatch.setenv(key, val)
         lc_x, w_x, proof_x = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, api.PoseidonTranscript())
         for key in extra:
             monkeypatch.delenv(key)
         assert (proof_x == proof_o).all() and (lc_x == lc_o).all() and (w_x.f == f0_o).all(), extra
-    monkeypatch.delenv("LF_FOLD_LUT_MIN")
-    monkeypatch.delenv("LF_FOLD_TAB_MIN")
-    monkeypatch.delenv("LF_FOLD_TAB_R1")
-    monkeypatch.delenv("LF_FOLD_FUSE_MIN")
-    monkeypatch.setenv("LF_FOLD_UNFUSED", "1")
-    monkeypatch.setenv("LF_THETA_EVAL", "1")       # theta from evaluate_mles-style sums instead of the last fix of the sumcheck tables
-    monkeypatch.setenv("LF_LIN_U_EVAL", "1")       # likewise u of the linearization
+    for key in fold_paths.FUSED_LUT_TAB:
+        monkeypatch.delenv(key)
+    # the separate k_fix pass; theta from evaluate_mles-style sums instead of the last fix of the sumcheck tables, likewise u of the linearization
+    for key, val in fold_paths.UNFUSED_EVAL.items():
+        monkeypatch.setenv(key, val)
     lc_u, w_u, proof_u = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, api.PoseidonTranscript())
     assert (proof_f == proof_o).all() and (lc_f == lc_o).all() and (w_f.f == f0_o).all()
     assert (proof_l == proof_o).all() and (lc_l == lc_o).all() and (w_l.f == f0_o).all()
@@ -353,16 +350,12 @@ def test_fold_step_gemm_rounds_match_oracle(ctx, name, monkeypatch):
     fused-fix rounds or plain tables -- identical proofs, all equal to the oracle's"""
     wl, inst, A, f_coeff, wit, cccs, acc_g, _, acc_o, _ = run_both(ctx, name, 2)
     lc_o, f0_o, proof_o = inst.fold_step(lfo.Transcript(), A, acc_o, f_coeff, cccs, f_coeff)
-    monkeypatch.setenv("LF_FOLD_SV_MIN", "64")
-    monkeypatch.setenv("LF_DOT_MIN", "64")          # ... and the u_s / eta inner products as int8 GEMMs at this size too
+    for k, v in fold_paths.GEMM_BASE.items():       # LF_FOLD_SV_MIN ... and the u_s / eta inner products as int8 GEMMs at this size too
+        monkeypatch.setenv(k, v)
     m = 1 << wl.s
     # (the GEMMs run against one eq value per pair -- two column tiles -- unless LF_FOLD_SV_NO_SPLIT=1; rounds 4 and 5 from the tables over the digit codes leave three
     # sums per slot and the host completes the message unless LF_FOLD_ROUNDS_NO_SPLIT=1: both forms, same words)
-    for rounds, extra in ((1, {}), (2, {}), (3, {}), (2, {"LF_FOLD_LUT_MIN": "1", "LF_FOLD_FUSE_MIN": "4"}), (3, {"LF_FOLD_LUT_MIN": "1", "LF_FOLD_FUSE_MIN": "4"}),
-                          (3, {"LF_NO_TAIL": "1", "LF_FOLD_UNFUSED": "1"}), (3, {"LF_FOLD_SV_NO_SPLIT": "1"}),
-                          (3, {"LF_FOLD_LUT_MIN": "1", "LF_FOLD_FUSE_MIN": "4", "LF_FOLD_R5_MIN": "1", "LF_NO_TAIL": "1", "LF_FOLD_SPLIT_MIN": "1"}),
-                          (3, {"LF_FOLD_LUT_MIN": "1", "LF_FOLD_FUSE_MIN": "4", "LF_FOLD_R5_MIN": "1", "LF_NO_TAIL": "1", "LF_FOLD_ROUNDS_NO_SPLIT": "1"}),
-                          (2, {"LF_FOLD_LUT_MIN": "1", "LF_FOLD_FUSE_MIN": "4", "LF_FOLD_NO_R5TAB": "1", "LF_FOLD_ROUNDS_NO_SPLIT": "1"})):
+    for rounds, extra in fold_paths.GEMM_CASES:
         monkeypatch.setenv("LF_FOLD_SV_ROUNDS", str(rounds))
         for k, v in extra.items():
             monkeypatch.setenv(k, v)
@@ -376,7 +369,8 @@ def test_fold_step_gemm_rounds_match_oracle(ctx, name, monkeypatch):
         elif wl.s >= 5 and wl.N % 4 == 0:                                               # rounds 4 and 5 took the split form (lf_last_fold_split_rounds)
             assert ctx.fold_split_rounds() == 0b11000, (extra, bin(ctx.fold_split_rounds()))
         assert (proof == proof_o).all() and (lc == lc_o).all() and (w.f == f0_o).all(), (rounds, extra)
-    monkeypatch.setenv("LF_FOLD_NO_SV", "1")
+    for k, v in fold_paths.GEMM_OFF.items():
+        monkeypatch.setenv(k, v)
     lc, w, proof = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, api.PoseidonTranscript())
     assert ctx.fold_paths() == 0 and (proof == proof_o).all()
 
@@ -390,22 +384,16 @@ def test_fold_step_persistent_tail_matches_oracle(ctx, name, monkeypatch):
     lc_o, f0_o, proof_o = inst.fold_step(lfo.Transcript(), A, acc_o, f_coeff, cccs, f_coeff)
     # lut: rounds 3-4 from the digit look-up tables (k_fold_round modes 3/5 and 4/6) and, when the tail starts later than round 5, round 5 from the
     # planes as well (mode 7; LF_FOLD_R5_MIN=1 lifts its size threshold) -- a tail that starts AT round 5 needs the round-4 tables mode 6 then must store
-    for tail_n, lut in (("16384", False), ("16", False), ("4", False), ("64", True), ("16", True), ("0", False)):
+    for tail_n, lut in fold_paths.TAIL_CASES:
         monkeypatch.setenv("LF_TAIL_N", tail_n)
-        if lut:
-            monkeypatch.setenv("LF_FOLD_LUT_MIN", "1")
-            monkeypatch.setenv("LF_FOLD_FUSE_MIN", "4")
-            monkeypatch.setenv("LF_FOLD_R5_MIN", "1")
-        lc, w, proof = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, api.PoseidonTranscript())
-        if lut:
-            monkeypatch.delenv("LF_FOLD_LUT_MIN")
-            monkeypatch.delenv("LF_FOLD_FUSE_MIN")
-            monkeypatch.delenv("LF_FOLD_R5_MIN")
+        with fold_paths.applied(monkeypatch, fold_paths.TAIL_LUT if lut else {}):
+            lc, w, proof = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, api.PoseidonTranscript())
         assert (proof == proof_o).all() and (lc == lc_o).all() and (w.f == f0_o).all(), (tail_n, lut)
     # the tail rounds' Fiat-Shamir transcript on the DEVICE sponge (no host round trip at all); the host transcript
     # takes the sponge back afterwards (theta / eta absorbs, rho challenges), so any divergence shows in the proof and the folded instance
-    monkeypatch.setenv("LF_DEVICE_TRANSCRIPT", "1")
-    for tail_n in ("16384", "16"):
+    for k, v in fold_paths.TAIL_DEVICE_TRANSCRIPT.items():
+        monkeypatch.setenv(k, v)
+    for tail_n in fold_paths.TAIL_DEVICE_TRANSCRIPT_N:
         monkeypatch.setenv("LF_TAIL_N", tail_n)
         lc, w, proof = api.NIFSProver.prove(ctx, acc_g, wit, cccs, wit, api.PoseidonTranscript())
         assert (proof == proof_o).all() and (lc == lc_o).all() and (w.f == f0_o).all(), ("device transcript", tail_n)

@@ -15,6 +15,7 @@ import pytest
 import lfo
 from latticefold_amd import api
 from latticefold_amd.workload import P, RE, diag, make_workload, splitmix_fq
+from two_sided import sections as _sections
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "small_base_digests.json")
@@ -50,17 +51,6 @@ def _tr():
 
 def _sha(a):
     return hashlib.sha256(np.ascontiguousarray(a, dtype=np.uint64).tobytes()).hexdigest()
-
-
-def _sections(wl, proof):
-    tau = wl.tau
-    lin = wl.s * (wl.d + 2) + tau + wl.t
-    dec = wl.K * (wl.t + tau + wl.l + 1 + wl.kappa)
-    fm = wl.s * (2 * wl.b + 1)
-    p = np.asarray(proof).reshape(-1, wl.RE)
-    o = lin + 2 * dec
-    return {"proof_lin": p[:lin], "proof_dec_left": p[lin:lin + dec], "proof_dec_right": p[lin + dec:o], "proof_fold_msgs": p[o:o + fm],
-            "proof_theta": p[o + fm:o + fm + 2 * wl.K * tau], "proof_eta": p[o + fm + 2 * wl.K * tau:], "proof": p}
 
 
 def _digests(wl, acc, lc, f0, proof):

@@ -5,6 +5,7 @@ six pair groups instead of four).  Proof, folded LCCCS and f_0 must equal the or
 import numpy as np
 import pytest
 
+import fold_paths
 import lfo
 import test_gpu_bb as bb
 from latticefold_amd import api, workload
@@ -57,13 +58,12 @@ def sv_chunks(V, nsuper, K, rd=24):
     return -(-nsuper // spc), spc
 
 
-def gemm_rounds(ctx, monkeypatch, wl, acc_g, wit, cccs, ref, forms=({}, {"LF_FOLD_SV_NO_SPLIT": "1"}), transcript=api.PoseidonTranscript, dot_min=True):
+def gemm_rounds(ctx, monkeypatch, wl, acc_g, wit, cccs, ref, forms=fold_paths.SV_FORMS, transcript=api.PoseidonTranscript, dot_min=True):
     lc_o, f0_o, proof_o = ref
-    monkeypatch.setenv("LF_FOLD_SV_MIN", "64")
-    if dot_min:
-        monkeypatch.setenv("LF_DOT_MIN", "64")
+    for k, v in dict(fold_paths.SV_MIN, **(fold_paths.SV_DOT_MIN if dot_min else {})).items():
+        monkeypatch.setenv(k, v)
     m = 1 << wl.s
-    for rounds in (1, 2, 3):
+    for rounds in fold_paths.SV_ROUNDS:
         monkeypatch.setenv("LF_FOLD_SV_ROUNDS", str(rounds))
         for extra in forms:
             for k, v in extra.items():
