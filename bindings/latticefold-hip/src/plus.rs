@@ -470,6 +470,88 @@ impl HipPlusContext {
         // SAFETY: the caller's contract
         self.chk(unsafe { sys::lfplus_spmv_device(self.raw, j as u32, x, n as u64, y) }, "lfplus_spmv_device")
     }
+    /// `lfplus_build_eq`: the table eq(point, .) as 2^nv constant polynomials (nv = `point.len()` words, 1..=28) -- the eq factor of a generic sumcheck
+    pub fn build_eq(&mut self, point: &[u64]) -> Result<Vec<u64>, HipPlusError> {
+        if point.is_empty() || point.len() > 28 {
+            return Err(HipPlusError::new(sys::LFPLUS_E_ARG, "build_eq", "point: 1 ..= 28 words"));
+        }
+        let mut out = vec![0u64; 16usize << point.len()];
+        // SAFETY: live handle; out holds 2^nv ring elements
+        self.chk(unsafe { sys::lfplus_build_eq(self.raw, point.as_ptr(), point.len() as u32, out.as_mut_ptr()) }, "lfplus_build_eq")?;
+        Ok(out)
+    }
+    /// `lfplus_build_eq_device`
+    /// # Safety
+    /// `out`: room for 2^nv x 16 words of 16-byte aligned device memory of the context's device
+    pub unsafe fn build_eq_device(&mut self, point: &[u64], out: *mut u64) -> Result<(), HipPlusError> {
+        // SAFETY: the caller's contract
+        self.chk(unsafe { sys::lfplus_build_eq_device(self.raw, point.as_ptr(), point.len() as u32, out) }, "lfplus_build_eq_device")
+    }
+    /// `lfplus_mle_eval_batch`: out[j] = sum_{x < len} eq(point, x) T_j[x] for `ntables` tables of `len` <= 2^nv general ring elements -> ntables x 16 words
+    pub fn mle_eval_batch(&mut self, tables: &[u64], ntables: usize, len: usize, point: &[u64]) -> Result<Vec<u64>, HipPlusError> {
+        if ntables == 0 || len == 0 || tables.len() != ntables * len * 16 || point.is_empty() {
+            return Err(HipPlusError::new(sys::LFPLUS_E_ARG, "mle_eval_batch", "tables: ntables x len x 16 words; point: nv words"));
+        }
+        let mut out = vec![0u64; ntables * 16];
+        // SAFETY: live handle; the arrays have the sizes checked above
+        self.chk(
+            unsafe { sys::lfplus_mle_eval_batch(self.raw, tables.as_ptr(), ntables as u32, len as u64, point.as_ptr(), point.len() as u32, out.as_mut_ptr()) },
+            "lfplus_mle_eval_batch",
+        )?;
+        Ok(out)
+    }
+    /// `lfplus_mle_eval_batch_device`: the tables are read in place; the point and the result stay on the host
+    /// # Safety
+    /// `tables`: ntables x len x 16 words of 16-byte aligned device memory of the context's device
+    pub unsafe fn mle_eval_batch_device(&mut self, tables: *const u64, ntables: usize, len: usize, point: &[u64]) -> Result<Vec<u64>, HipPlusError> {
+        let mut out = vec![0u64; ntables * 16];
+        // SAFETY: the caller's contract; out holds ntables ring elements
+        self.chk(
+            unsafe { sys::lfplus_mle_eval_batch_device(self.raw, tables, ntables as u32, len as u64, point.as_ptr(), point.len() as u32, out.as_mut_ptr()) },
+            "lfplus_mle_eval_batch_device",
+        )?;
+        Ok(out)
+    }
+    /// `lfplus_mle_fix_variables`: the lowest `point.len()` variables of `ntables` tables of `len` = 2^nv ring elements fixed at `point` -> ntables x (len >> nfix) x 16 words
+    pub fn mle_fix_variables(&mut self, tables: &[u64], ntables: usize, len: usize, point: &[u64]) -> Result<Vec<u64>, HipPlusError> {
+        if ntables == 0 || !len.is_power_of_two() || tables.len() != ntables * len * 16 || point.is_empty() || point.len() > 28 || len >> point.len() == 0 {
+            return Err(HipPlusError::new(sys::LFPLUS_E_ARG, "mle_fix_variables", "tables: ntables x 2^nv x 16 words; point: 1 ..= nv words"));
+        }
+        let mut out = vec![0u64; ntables * (len >> point.len()) * 16];
+        // SAFETY: live handle; the arrays have the sizes checked above
+        self.chk(
+            unsafe { sys::lfplus_mle_fix_variables(self.raw, tables.as_ptr(), ntables as u32, len as u64, point.as_ptr(), point.len() as u32, out.as_mut_ptr()) },
+            "lfplus_mle_fix_variables",
+        )?;
+        Ok(out)
+    }
+    /// `lfplus_mle_fix_variables_device`
+    /// # Safety
+    /// `tables`: ntables x len x 16 words, `out`: room for ntables x (len >> nfix) x 16 words of 16-byte aligned device memory of the context's device, not overlapping
+    pub unsafe fn mle_fix_variables_device(&mut self, tables: *const u64, ntables: usize, len: usize, point: &[u64], out: *mut u64) -> Result<(), HipPlusError> {
+        // SAFETY: the caller's contract
+        self.chk(
+            unsafe { sys::lfplus_mle_fix_variables_device(self.raw, tables, ntables as u32, len as u64, point.as_ptr(), point.len() as u32, out) },
+            "lfplus_mle_fix_variables_device",
+        )
+    }
+    /// `lfplus_spmv_t`: M_j^T v for the j-th resident constraint matrix; `v` = n general ring elements
+    pub fn spmv_t(&mut self, j: usize, v: &[u64]) -> Result<Vec<u64>, HipPlusError> {
+        if v.is_empty() || v.len() % 16 != 0 {
+            return Err(HipPlusError::new(sys::LFPLUS_E_ARG, "spmv_t", "v: n x 16 words"));
+        }
+        let mut out = vec![0u64; v.len()];
+        // SAFETY: live handle; out has the size of v
+        self.chk(unsafe { sys::lfplus_spmv_t(self.raw, j as u32, v.as_ptr(), (v.len() / 16) as u64, out.as_mut_ptr()) }, "lfplus_spmv_t")?;
+        Ok(out)
+    }
+    /// `lfplus_spmv_t_device`
+    /// # Safety
+    /// `v`, `out`: n x 16 words of 16-byte aligned device memory of the context's device each, not overlapping
+    pub unsafe fn spmv_t_device(&mut self, j: usize, v: *const u64, n: usize, out: *mut u64) -> Result<(), HipPlusError> {
+        // SAFETY: the caller's contract
+        self.chk(unsafe { sys::lfplus_spmv_t_device(self.raw, j as u32, v, n as u64, out) }, "lfplus_spmv_t_device")
+    }
     /// `lfplus_ctx_create` alone: a BARE context (no matrix, no witness) -- all the generic sumcheck needs
     pub fn bare(device: i32) -> Result<Self, HipPlusError> {
         let mut raw = core::ptr::null_mut();

@@ -18,6 +18,7 @@
  *   PlusProver::{init, prove} / PlusVerifier::{init, verify}   src/plus.rs:15-146   (lfplus_prover_*, lfplus_verify: the objects, below)
  *   MLSumcheck::{prove, verify}_as_subprotocol over any product list   latticefold/src/utils/sumcheck.rs:53-104   (lfplus_mlsumcheck_*, near the end of this file)
  *   RqPoly products and SparseMatrix x vector on arrays (the g_q = M_q f and g_A o g_B - g_C of r1cs.rs:76-95 as calls of their own)   (lfplus_ring_mul, lfplus_spmv, at the end of this file)
+ *   DenseMultilinearExtension::{evaluate, fix_variables}, the eq(r, .) table and the transposed matrix product on arrays   (lfplus_build_eq, lfplus_mle_eval_batch, lfplus_mle_fix_variables, lfplus_spmv_t, behind them)
  *
  * M_f and m_tau are matrices / vectors of unit monomials; they cross this boundary as their EXPONENT digits (int8 in (-d/2, d/2)):
  * exp(a) = X^a for a >= 0 and X^(d + a) for a < 0.  The Rust binding rebuilds Matrix<R> from them if a caller needs the dense form
@@ -378,7 +379,7 @@ int lfplus_prover_accumulator_dev(lfplus_prover *prover, uint64_t *F0, uint64_t 
  *      g(x) = sum_{i < nterms} coef_i * prod_{k in [term_off[i], term_off[i+1])} T_{term_idx[k]}(x),      x in {0,1}^nvars,
  * with negacyclic products in Z_p[X]/(X^16 + 1).  Tables are ntables x 2^nvars GENERAL ring elements in the layout of this header (coefficient form, 16 canonical
  * words per element, AoS; table j at tables + j * 2^nvars * 16); entry x of a table has variable 1 in bit 0 of x (DenseMultilinearExtension: the first round
- * fixes the lowest bit).  A constant-polynomial table (eq(r, .)) costs a full ring table and full products.  A challenge is ONE F_p word (RqPoly's base ring has
+ * fixes the lowest bit).  A constant-polynomial table (eq(r, .); lfplus_build_eq_device makes it) costs a full ring table and full products.  A challenge is ONE F_p word (RqPoly's base ring has
  * extension degree 1): fix_variables is lo + r (hi - lo), coefficient by coefficient.
  *   Independence.  The state and the buffers of this sumcheck are the context's own and nothing else's: it runs on a BARE context (no matrix, no witness), and on
  * a loaded one it neither reads nor writes the resident witness, the lfplus_rg_from_f results, a pending lfplus_rg_from_f_async pass or the resident matrices.
@@ -461,6 +462,52 @@ int lfplus_ring_mul_device(lfplus_ctx *ctx, const uint64_t *a, const uint64_t *b
 /* y = M_j x, M_j the j-th matrix of lfplus_set_matrices / lfplus_share_matrices (n x n), x and y n ring elements */
 int lfplus_spmv(lfplus_ctx *ctx, uint32_t j, const uint64_t *x, uint64_t n, uint64_t *y);
 int lfplus_spmv_device(lfplus_ctx *ctx, uint32_t j, const uint64_t *x, uint64_t n, uint64_t *y);
+
+/* ---- MLE tables on arrays: the eq(r, .) table, evaluations and partial evaluations of tables at a point, and M_j^T v (the counterparts of lf_build_eq,
+ * lf_mle_eval_batch, lf_mle_fix_variables and lf_spmv_t on the Frog ring; DenseMultilinearExtension::{evaluate, fix_variables}, utils::mle_helpers build_eq_x_r).
+ * With the section above they close the loop of a generic sumcheck on the device: lfplus_build_eq_device makes the eq factor lfplus_mlsumcheck_begin(_device)
+ * takes, lfplus_mle_eval_batch_device evaluates tables outside a sumcheck, and w = lfplus_spmv_t_device(j, eq(r, .)) turns u_j = MLE(M_j f)(r) into the one inner
+ * product sum_c f[c] * w[c].
+ *   Layout as everywhere in this header: coefficient form, 16 canonical little-endian words per element, AoS; table j of `tables` at tables + j * len * 16.  A
+ * challenge is ONE F_p word, so a point is nv (nfix) words; entry x of a table has variable 1 in bit 0 of x.  Points are small and stay HOST pointers in both
+ * spellings, as does `out` of lfplus_mle_eval_batch.  The device forms (spelled _device, as lfplus_mlsumcheck_begin_device is) take every other array as memory of
+ * the context's device under every rule of the "device-resident callers" section above (unmanaged memory of the context's device, ONE allocation covering every
+ * byte, 16-byte alignment, ordering by lfplus_ctx_wait_stream, return after the context's stream is synchronised).
+ *   Envelope: 1 <= nv <= 28; 1 <= ntables <= 64; lfplus_mle_eval_batch: 1 <= len <= 2^nv, entries from len on count as zero (the ragged form lf_mle_eval_batch
+ * has); lfplus_mle_fix_variables: len = 2^nv, 1 <= nfix <= nv.
+ *   Exactness: every output word is the canonical value of an exact sum mod p.  Fixing nfix variables in one call gives the words of nfix calls that fix one
+ * each (lo + r (hi - lo), coefficient by coefficient); nfix == nv leaves what lfplus_mle_eval_batch returns; a column of lfplus_spmv_t does not depend on the
+ * order or the number of its entries.  The eq weights of an evaluation are never materialised as a ring table.
+ *   Independence, as lfplus_mlsumcheck_*: lfplus_build_eq, lfplus_mle_eval_batch and lfplus_mle_fix_variables run on a bare context (no matrix and no witness),
+ * and on a loaded one none of the eight reads or writes the resident witness, the lfplus_rg_from_f results, a pending lfplus_rg_from_f_async pass or an active
+ * generic sumcheck.  Inputs are never written.  lfplus_spmv_t reads the transposed structure the resident matrices carry: it is owned and reference-counted
+ * with them (a context that got them through lfplus_share_matrices shares it) and goes when they are replaced.
+ *   Refusals, every one LFPLUS_E_ARG with a message in lfplus_last_error, in this order: a NULL context (tested before any device is touched: the answer on a
+ * machine without a GPU as well); a NULL array; ntables, len, nv or nfix outside the envelope; [lfplus_spmv_t: no resident matrices, j >= their number, n != the
+ * resident n;] a sharded context (a transport or lfplus_set_sharding_model); out overlapping an input range (arrays of one memory space; out of lfplus_spmv_t
+ * overlapping v in any way: the product gathers); [_device: the pointer checks;] a word >= p in the point (tested on the host); a word >= p in an O(n) input.
+ * The O(n) words are tested on the device by the kernel that reads them and the flag comes home before the call returns: a host out is written only when it is
+ * down and stays untouched otherwise, a device out is undefined then (as that section says for a non-canonical word).  After any refusal the context is usable
+ * and nothing resident has changed.
+ *   Not built: sharded contexts; an NTT form of the Frog ring; a compact (one word per entry) eq output. */
+/* out[x] = the constant polynomial eq(point, x) = prod_i (r_i x_i + (1 - r_i)(1 - x_i)) for x < 2^nv: word 0 holds the value, words 1..15 are 0 -- the table
+ * lfplus_mlsumcheck_begin(_device) takes as the eq factor */
+int lfplus_build_eq(lfplus_ctx *ctx, const uint64_t *point /* nv words */, uint32_t nv, uint64_t *out /* 2^nv x 16 words */);
+int lfplus_build_eq_device(lfplus_ctx *ctx, const uint64_t *point /* nv words */, uint32_t nv, uint64_t *out /* 2^nv x 16 words */);
+/* out[j] = sum_{x < len} eq(point, x) * T_j[x], coefficient by coefficient: DenseMultilinearExtension::evaluate of ntables tables of GENERAL ring elements */
+int lfplus_mle_eval_batch(lfplus_ctx *ctx, const uint64_t *tables, uint32_t ntables, uint64_t len, const uint64_t *point /* nv words */, uint32_t nv,
+                          uint64_t *out /* ntables x 16 words, host */);
+int lfplus_mle_eval_batch_device(lfplus_ctx *ctx, const uint64_t *tables, uint32_t ntables, uint64_t len, const uint64_t *point /* nv words */, uint32_t nv,
+                          uint64_t *out /* ntables x 16 words, host */);
+/* DenseMultilinearExtension::fix_variables on whole tables: the LOWEST nfix variables at point[0 .. nfix); table j of out at out + j * (len >> nfix) * 16 */
+int lfplus_mle_fix_variables(lfplus_ctx *ctx, const uint64_t *tables, uint32_t ntables, uint64_t len, const uint64_t *point /* nfix words */, uint32_t nfix,
+                             uint64_t *out /* ntables x (len >> nfix) x 16 words */);
+int lfplus_mle_fix_variables_device(lfplus_ctx *ctx, const uint64_t *tables, uint32_t ntables, uint64_t len, const uint64_t *point /* nfix words */, uint32_t nfix,
+                             uint64_t *out /* ntables x (len >> nfix) x 16 words */);
+/* out[c] = sum over the entries (r, c) of M_j of M_j[r][c] * v[r] (negacyclic products), M_j the j-th matrix of lfplus_set_matrices / lfplus_share_matrices
+ * (n x n); v and out n GENERAL ring elements */
+int lfplus_spmv_t(lfplus_ctx *ctx, uint32_t j, const uint64_t *v, uint64_t n, uint64_t *out);
+int lfplus_spmv_t_device(lfplus_ctx *ctx, uint32_t j, const uint64_t *v, uint64_t n, uint64_t *out);
 
 /* ---- committed CCS instances: the linearization of ANY constraint shape sum_i c_i prod_{j in S_i} (M_j f) = 0 as a protocol step of its own, with its own round
  * kernel (lfp_ccs.hip).  The reference has none (its README lists "Support CCS" as the next step of latticefold-plus): this is ComR1CS::linearize /

@@ -167,6 +167,22 @@ void launch_mls_final(const u64 *in, size_t ld_in, u32 nt, u64 rM, u64 *out, hip
 // (of b in mode 0) is not canonical.  blocks = ring_mul_blocks(count, cap): one workgroup per 16 elements, at most cap
 u32 ring_mul_blocks(u64 count, u32 cap);
 void launch_ring_mul(const u64 *a, const u64 *b, u32 n_terms, u64 count, int mode, u64 *out, u32 *flag, u32 blocks, hipStream_t s);
+// ---- MLE tables on arrays (lfp_tables.hip; lfplus_build_eq, lfplus_mle_eval_batch, lfplus_mle_fix_variables, lfplus_spmv_t).  Tables are [table][len][16]
+// canonical words, 16-byte aligned; a point is its coordinates in Montgomery form (host-converted) and travels as a kernel argument
+struct TabPoint { u64 rM[28]; u64 oneM; };      // r_i 2^64 mod p for i < nv, and 2^64 mod p
+constexpr u32 TAB_LO = 10;         // k_tab_eval: the eq weights of the low min(nv, 10) variables live in LDS; a workgroup takes 2^TAB_LO entries (a chunk) per pass
+constexpr u32 TAB_FIX = 6;         // k_tab_fix: variables one launch fixes at most (each thread sums 2^6 entries)
+constexpr u32 SPT_HEAVY = 64;      // k_spmv_t: a column of MORE entries is summed by the whole workgroup, 16 entries abreast
+constexpr u32 SPT_FLUSH = 64;      // k_spmv_t: products of one 16-lane group before its lazy sum is reduced (the heavy path: a column of more than 16 * 64 entries)
+// out[x] = (eq(point, x), 0, .., 0) for x < 2^nv
+void launch_tab_eq(const TabPoint &pt, u32 nv, u64 *out, u32 cap, hipStream_t s);
+u32 tab_eval_blocks(u64 len, u32 nv, u32 ntables, u32 cap);      // workgroups per table: one per chunk, at most max(1, cap / ntables)
+// part[table][block][16] = the block's share of sum_{x < len} eq(point, x) T[x]; then out[table][16] = the sum over the blocks.  *flag |= 1: a word >= p
+void launch_tab_eval(const u64 *tables, u32 ntables, u64 len, const TabPoint &pt, u32 nv, u32 blocks, u64 *part, u64 *out, u32 *flag, hipStream_t s);
+// out[table][y] = sum_{t < 2^nf} eq(point[0 .. nf), t) in[table][y 2^nf + t] for y < nout, nf <= TAB_FIX; tables of `in` are ld_in entries apart, of out nout
+void launch_tab_fix(const u64 *in, u64 ld_in, u32 ntables, u64 nout, const TabPoint &pt, u32 nf, u64 *out, u32 *flag, hipStream_t s);
+// out[c] = sum over the entries k in [colptr[c], colptr[c + 1]) of val[k] * v[rowidx[k]] (negacyclic; val and v canonical) for c < n
+void launch_spmv_t(const u32 *colptr, const u32 *rowidx, const u64 *val, const u64 *v, u64 n, u64 *out, hipStream_t s);
 // ---- relation checks (lfp_check.hip): R_ComR1CS (r1cs.rs:21-60), R_LinB (lin.rs:29-40)
 // *first_bad = min(*first_bad, smallest row r < nrows with ((M_0 f) (M_1 f) - M_2 f)[r] != 0); vals[q]: LfpMatrix::spmv_vals() of matrix q (const_coef[q] as there)
 void launch_r1cs_residual(const u32 *const *rowptr, const u32 *const *col, const u64 *const *vals, const int *const_coef, const u64 *f, size_t nrows, u64 *first_bad,

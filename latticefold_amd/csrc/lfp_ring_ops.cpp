@@ -8,41 +8,19 @@
 #include <cstring>
 #include <string>
 #include <vector>
+#include "lfp_array_call.h"
 #include "lfp_ctx.h"
 #include "lfp_guard.h"
 #include "lf_dev_ptr.h"
 
 using lfdev::Origin;
+using namespace lfp_arr;
 
 namespace {
-constexpr u64 P = lfp::P;
-u64 to_mont(u64 a) { return (u64)((((unsigned __int128)a) << 64) % P); }
-bool ranges_overlap(const void *a, u64 abytes, const void *b, u64 bbytes) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + bbytes && pb < pa + abytes;
-}
 u32 block_cap() {
     const char *e = getenv("LFPLUS_RING_BLOCKS");   // workgroups of lfplus_ring_mul at most (default 2048: 8 per CU); read once per call
     const long v = e ? atol(e) : 0;
     return v >= 1 && v <= 65535 ? (u32)v : 2048u;
-}
-// the call's own scratch: blocks of the context's pool (which releases the process-wide cache and retries before it gives up), given back on every way out
-struct Scratch {
-    lfplus_ctx *c;
-    std::vector<void *> held;
-    explicit Scratch(lfplus_ctx *ctx) : c(ctx) {}
-    ~Scratch() { for (void *p : held) c->own_free(p); }
-    template <class T> bool get(T **p, size_t bytes) {
-        if (c->own_alloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
-        held.push_back((void *)*p);
-        return true;
-    }
-};
-// after a failure inside the enqueued part: the stream is drained before the scratch goes back to the pool
-int hip_fail(lfplus_ctx *c, const std::string &who, hipError_t e) {
-    (void)hipStreamSynchronize(c->st);
-    (void)hipGetLastError();
-    return fail(c, LFPLUS_E_HIP, who + ": " + hipGetErrorString(e));
 }
 
 int ring_mul_impl(lfplus_ctx *c, const uint64_t *a, const uint64_t *b, uint64_t n_terms, uint64_t count, int mode, uint64_t *out, Origin o, const char *who) {
@@ -147,10 +125,6 @@ int spmv_impl(lfplus_ctx *c, uint32_t j, const uint64_t *x, uint64_t n, uint64_t
         if (e != hipSuccess) return hip_fail(c, w, e);
     }
     return LFPLUS_OK;
-}
-int oom(lfplus_ctx *c, const char *m) {
-    try { c->err = m; } catch (...) {}
-    return LFPLUS_E_HIP;
 }
 }  // namespace
 

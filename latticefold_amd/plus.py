@@ -138,6 +138,15 @@ def _lib():
         L.lfplus_ring_mul_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp]
         L.lfplus_spmv.argtypes = [vp, C.c_uint32, u64p, C.c_uint64, u64p]
         L.lfplus_spmv_device.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp]
+        # MLE tables on arrays (the _device forms: tables, v and the O(n) outputs are device addresses; points and the results of an evaluation stay host pointers)
+        L.lfplus_build_eq.argtypes = [vp, u64p, C.c_uint32, u64p]
+        L.lfplus_build_eq_device.argtypes = [vp, u64p, C.c_uint32, vp]
+        L.lfplus_mle_eval_batch.argtypes = [vp, u64p, C.c_uint32, C.c_uint64, u64p, C.c_uint32, u64p]
+        L.lfplus_mle_eval_batch_device.argtypes = [vp, vp, C.c_uint32, C.c_uint64, u64p, C.c_uint32, u64p]
+        L.lfplus_mle_fix_variables.argtypes = [vp, u64p, C.c_uint32, C.c_uint64, u64p, C.c_uint32, u64p]
+        L.lfplus_mle_fix_variables_device.argtypes = [vp, vp, C.c_uint32, C.c_uint64, u64p, C.c_uint32, vp]
+        L.lfplus_spmv_t.argtypes = [vp, C.c_uint32, u64p, C.c_uint64, u64p]
+        L.lfplus_spmv_t_device.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp]
         # committed CCS instances (lfplus_ccs_*)
         cp = C.POINTER(CCSDesc)
         L.lfplus_ccs_linearize.argtypes = [vp, vp, cp, u32pp, u32pp, u64pp, u64p, u64p, u64p]
@@ -428,6 +437,104 @@ class PlusContext:
         elif out.dtype != np.uint64 or not out.flags["C_CONTIGUOUS"]:
             raise LfPlusError(E_ARG, "spmv: out is a contiguous uint64 array")
         self._chk(_lib().lfplus_spmv(self.h, int(j), px, n, out.ctypes.data_as(u64p)))
+        return out
+
+    @staticmethod
+    def _point(point, who):
+        pt = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1)
+        if pt.size < 1:
+            raise LfPlusError(E_ARG, f"{who}: the point has at least one word")
+        return pt
+
+    @staticmethod
+    def _tables(tables, who):
+        """tables (len, 16) or (ntables, len, 16), numpy or device -> (is_device, ntables, len)"""
+        sh = tuple(tables.shape)
+        if len(sh) not in (2, 3) or sh[-1] != D:
+            raise LfPlusError(E_ARG, f"{who}: tables are (len, 16) or (ntables, len, 16)")
+        dev = api.is_device_array(tables)
+        if dev and (not tables.is_contiguous() or tables.element_size() != 8):
+            raise LfPlusError(E_ARG, "device arrays must be contiguous with 8-byte elements")
+        return (dev, 1, sh[0]) if len(sh) == 2 else (dev, sh[0], sh[1])
+
+    def build_eq(self, point, out=None):
+        """lfplus_build_eq: the table eq(point, .) as constant polynomials, (2^nv, 16) -- the eq factor MLSumcheck takes.  Answers a numpy array, or writes the
+        device array `out` (2^nv, 16) (lfplus_build_eq_device: nothing crosses PCIe) and returns it"""
+        pt = self._point(point, "build_eq")
+        nv = pt.size
+        if out is not None and api.is_device_array(out):
+            self._chk(_lib().lfplus_build_eq_device(self.h, pt.ctypes.data_as(u64p), nv, self._dev_in(out, (1 << nv, D))))
+            return out
+        if out is None:
+            out = np.zeros((1 << nv, D), dtype=np.uint64)
+        elif out.dtype != np.uint64 or not out.flags["C_CONTIGUOUS"] or out.shape != (1 << nv, D):
+            raise LfPlusError(E_ARG, "build_eq: out is a contiguous uint64 array of (2^nv, 16)")
+        self._chk(_lib().lfplus_build_eq(self.h, pt.ctypes.data_as(u64p), nv, out.ctypes.data_as(u64p)))
+        return out
+
+    def mle_eval_batch(self, tables, point):
+        """lfplus_mle_eval_batch: out[j] = sum_{x < len} eq(point, x) T_j[x] for tables (len, 16) or (ntables, len, 16) of general ring elements, len <= 2^nv
+        (entries from len on count as zero); a device array is read in place (lfplus_mle_eval_batch_device) -> a numpy array (16,) or (ntables, 16)"""
+        pt = self._point(point, "mle_eval_batch")
+        dev, nt, ln = self._tables(tables, "mle_eval_batch")
+        out = np.zeros((nt, D), dtype=np.uint64)
+        if dev:
+            self.wait_stream()
+            self._chk(_lib().lfplus_mle_eval_batch_device(self.h, C.c_void_p(tables.data_ptr()), nt, ln, pt.ctypes.data_as(u64p), pt.size, out.ctypes.data_as(u64p)))
+        else:
+            t, p = _w(tables)
+            self._chk(_lib().lfplus_mle_eval_batch(self.h, p, nt, ln, pt.ctypes.data_as(u64p), pt.size, out.ctypes.data_as(u64p)))
+        return out[0] if len(tuple(tables.shape)) == 2 else out
+
+    def mle_fix_variables(self, tables, point, out=None):
+        """lfplus_mle_fix_variables: the LOWEST len(point) variables of tables (len, 16) or (ntables, len, 16), len a power of two, fixed at the point ->
+        (len >> nfix, 16) or (ntables, len >> nfix, 16) in the memory space of the tables (lfplus_mle_fix_variables_device reads and writes in place)"""
+        pt = self._point(point, "mle_fix_variables")
+        dev, nt, ln = self._tables(tables, "mle_fix_variables")
+        if ln >> pt.size < 1 or ln & (ln - 1):
+            raise LfPlusError(E_ARG, "mle_fix_variables: len is a power of two of at least 2^nfix entries")
+        osh = (ln >> pt.size, D) if len(tuple(tables.shape)) == 2 else (nt, ln >> pt.size, D)
+        if out is not None and (api.is_device_array(out) != dev or tuple(out.shape) != osh):
+            raise LfPlusError(E_ARG, f"mle_fix_variables: out is {osh} in the memory space of the tables")
+        if dev:
+            if out is None:
+                out = tables.new_empty(osh)
+            if not out.is_contiguous() or out.element_size() != 8:
+                raise LfPlusError(E_ARG, "device arrays must be contiguous with 8-byte elements")
+            self.wait_stream()
+            self._chk(_lib().lfplus_mle_fix_variables_device(self.h, C.c_void_p(tables.data_ptr()), nt, ln, pt.ctypes.data_as(u64p), pt.size,
+                                                             C.c_void_p(out.data_ptr())))
+            return out
+        t, p = _w(tables)
+        if out is None:
+            out = np.zeros(osh, dtype=np.uint64)
+        elif out.dtype != np.uint64 or not out.flags["C_CONTIGUOUS"]:
+            raise LfPlusError(E_ARG, "mle_fix_variables: out is a contiguous uint64 array")
+        self._chk(_lib().lfplus_mle_fix_variables(self.h, p, nt, ln, pt.ctypes.data_as(u64p), pt.size, out.ctypes.data_as(u64p)))
+        return out
+
+    def spmv_t(self, j, v, out=None):
+        """lfplus_spmv_t: M_j^T v for the j-th resident matrix (set_matrices / share_matrices); v (n, 16) general ring elements, a numpy array or a device
+        array (lfplus_spmv_t_device) -> out (n, 16) in the memory space of v"""
+        if len(tuple(v.shape)) != 2 or v.shape[1] != D:
+            raise LfPlusError(E_ARG, "spmv_t: v is (n, 16)")
+        n = v.shape[0]
+        dev = api.is_device_array(v)
+        if out is not None and (api.is_device_array(out) != dev or tuple(out.shape) != (n, D)):
+            raise LfPlusError(E_ARG, "spmv_t: out is (n, 16) in the memory space of v")
+        if dev:
+            if out is None:
+                out = v.new_empty((n, D))
+            pv, po = _dev(v), _dev(out)
+            self.wait_stream()
+            self._chk(_lib().lfplus_spmv_t_device(self.h, int(j), pv, n, po))
+            return out
+        v, pv = _w(v)
+        if out is None:
+            out = np.zeros((n, D), dtype=np.uint64)
+        elif out.dtype != np.uint64 or not out.flags["C_CONTIGUOUS"]:
+            raise LfPlusError(E_ARG, "spmv_t: out is a contiguous uint64 array")
+        self._chk(_lib().lfplus_spmv_t(self.h, int(j), pv, n, out.ctypes.data_as(u64p)))
         return out
 
     def _cm_arg(self, cm_f):
