@@ -552,6 +552,78 @@ impl HipPlusContext {
         // SAFETY: the caller's contract
         self.chk(unsafe { sys::lfplus_spmv_t_device(self.raw, j as u32, v, n as u64, out) }, "lfplus_spmv_t_device")
     }
+    /// `lfplus_balanced_decompose`: the `k` balanced base-`b` digits of every coefficient of `x` (count x 16 words), as canonical residues.  `planes`: digit i of
+    /// element j at `i * count + j` (`decompose_to_vec(b, k).transpose()`); otherwise at `j * k + i` (`Vec<R>::gadget_decompose(b, k)`)
+    pub fn balanced_decompose(&mut self, x: &[u64], b: u64, k: usize, planes: bool) -> Result<Vec<u64>, HipPlusError> {
+        if x.is_empty() || x.len() % 16 != 0 || k == 0 || k > 64 {
+            return Err(HipPlusError::new(sys::LFPLUS_E_ARG, "balanced_decompose", "x: count x 16 words; 1 <= k <= 64"));
+        }
+        let layout = if planes { sys::LFPLUS_DIGITS_PLANES } else { sys::LFPLUS_DIGITS_GADGET };
+        let mut out = vec![0u64; x.len() * k];
+        // SAFETY: live handle; out has k times the size of x
+        self.chk(unsafe { sys::lfplus_balanced_decompose(self.raw, x.as_ptr(), (x.len() / 16) as u64, b, k as u32, layout as i32, out.as_mut_ptr()) }, "lfplus_balanced_decompose")?;
+        Ok(out)
+    }
+    /// `lfplus_balanced_decompose_device`
+    /// # Safety
+    /// `x`: count x 16 words, `out`: count x k x 16 words of 16-byte aligned device memory of the context's device, not overlapping
+    pub unsafe fn balanced_decompose_device(&mut self, x: *const u64, count: usize, b: u64, k: usize, planes: bool, out: *mut u64) -> Result<(), HipPlusError> {
+        let layout = if planes { sys::LFPLUS_DIGITS_PLANES } else { sys::LFPLUS_DIGITS_GADGET };
+        // SAFETY: the caller's contract
+        self.chk(unsafe { sys::lfplus_balanced_decompose_device(self.raw, x, count as u64, b, k as u32, layout as i32, out) }, "lfplus_balanced_decompose_device")
+    }
+    /// `lfplus_balanced_recompose`: out[j] = sum_i b^i x[digit i of j], coefficient by coefficient mod p; `x` = count x k GENERAL ring elements in the layout
+    /// `balanced_decompose` writes
+    pub fn balanced_recompose(&mut self, x: &[u64], b: u64, k: usize, planes: bool) -> Result<Vec<u64>, HipPlusError> {
+        if x.is_empty() || k == 0 || k > 64 || x.len() % (16 * k) != 0 {
+            return Err(HipPlusError::new(sys::LFPLUS_E_ARG, "balanced_recompose", "x: count x k x 16 words; 1 <= k <= 64"));
+        }
+        let layout = if planes { sys::LFPLUS_DIGITS_PLANES } else { sys::LFPLUS_DIGITS_GADGET };
+        let mut out = vec![0u64; x.len() / k];
+        // SAFETY: live handle; out has a k-th of the size of x
+        self.chk(unsafe { sys::lfplus_balanced_recompose(self.raw, x.as_ptr(), (x.len() / (16 * k)) as u64, b, k as u32, layout as i32, out.as_mut_ptr()) }, "lfplus_balanced_recompose")?;
+        Ok(out)
+    }
+    /// `lfplus_balanced_recompose_device`
+    /// # Safety
+    /// `x`: count x k x 16 words, `out`: count x 16 words of 16-byte aligned device memory of the context's device, not overlapping
+    pub unsafe fn balanced_recompose_device(&mut self, x: *const u64, count: usize, b: u64, k: usize, planes: bool, out: *mut u64) -> Result<(), HipPlusError> {
+        let layout = if planes { sys::LFPLUS_DIGITS_PLANES } else { sys::LFPLUS_DIGITS_GADGET };
+        // SAFETY: the caller's contract
+        self.chk(unsafe { sys::lfplus_balanced_recompose_device(self.raw, x, count as u64, b, k as u32, layout as i32, out) }, "lfplus_balanced_recompose_device")
+    }
+    /// `lfplus_linf_norm`: the largest |centred coefficient| of `v` (count x 16 words)
+    pub fn linf_norm(&mut self, v: &[u64]) -> Result<u64, HipPlusError> {
+        if v.is_empty() || v.len() % 16 != 0 {
+            return Err(HipPlusError::new(sys::LFPLUS_E_ARG, "linf_norm", "v: count x 16 words"));
+        }
+        let mut absmax = 0u64;
+        // SAFETY: live handle; absmax is one word
+        self.chk(unsafe { sys::lfplus_linf_norm(self.raw, v.as_ptr(), (v.len() / 16) as u64, &mut absmax) }, "lfplus_linf_norm")?;
+        Ok(absmax)
+    }
+    /// `lfplus_linf_norm_device`
+    /// # Safety
+    /// `v`: count x 16 words of 16-byte aligned device memory of the context's device
+    pub unsafe fn linf_norm_device(&mut self, v: *const u64, count: usize) -> Result<u64, HipPlusError> {
+        let mut absmax = 0u64;
+        // SAFETY: the caller's contract; absmax is one word of host memory
+        self.chk(unsafe { sys::lfplus_linf_norm_device(self.raw, v, count as u64, &mut absmax) }, "lfplus_linf_norm_device")?;
+        Ok(absmax)
+    }
+    /// `lfplus_set_matrices_gadget`: the system as stated over z (`M`: matrices of `rows` x `m`) made resident in its gadget form over
+    /// f = z.gadget_decompose(b, k), n = m k -- what `r1cs_decomposed_square` builds on the host, expanded on the device from the short arrays
+    pub fn set_matrices_gadget<R: RingWords + Clone>(&mut self, M: &[SparseMatrix<R>], rows: usize, m: usize, b: u64, k: usize) -> Result<(), HipPlusError> {
+        let flat: Vec<(Vec<u32>, Vec<u32>, Vec<u64>)> = M.iter().map(|x| csr(x, rows)).collect();
+        let rp: Vec<*const u32> = flat.iter().map(|x| x.0.as_ptr()).collect();
+        let cp: Vec<*const u32> = flat.iter().map(|x| x.1.as_ptr()).collect();
+        let vp: Vec<*const u64> = flat.iter().map(|x| x.2.as_ptr()).collect();
+        // SAFETY: live handle; the pointer arrays name M.len() CSR triples of rows + 1 / nnz / nnz x 16 entries that outlive the call
+        self.chk(
+            unsafe { sys::lfplus_set_matrices_gadget(self.raw, rows as u64, m as u64, b, k as u32, (m * k) as u64, M.len() as u32, rp.as_ptr(), cp.as_ptr(), vp.as_ptr()) },
+            "lfplus_set_matrices_gadget",
+        )
+    }
     /// `lfplus_ctx_create` alone: a BARE context (no matrix, no witness) -- all the generic sumcheck needs
     pub fn bare(device: i32) -> Result<Self, HipPlusError> {
         let mut raw = core::ptr::null_mut();

@@ -509,6 +509,54 @@ int lfplus_mle_fix_variables_device(lfplus_ctx *ctx, const uint64_t *tables, uin
 int lfplus_spmv_t(lfplus_ctx *ctx, uint32_t j, const uint64_t *v, uint64_t n, uint64_t *out);
 int lfplus_spmv_t_device(lfplus_ctx *ctx, uint32_t j, const uint64_t *v, uint64_t n, uint64_t *out);
 
+/* ---- gadget maps on arrays: the digit and gadget maps every LatticeFold+ object is built with, as calls of their own (the counterparts of lf_decompose,
+ * lf_recompose and lf_linf_check on the Frog ring): Vec<R>::gadget_decompose(b, k) (r1cs.rs:50), decompose_to_vec(b, k) with or without .transpose()
+ * (decomp.rs:34, rgchk.rs:271), gadget_recompose / recompose (z = G f: the check DecompProof::verify performs, on arrays), the infinity norm of an array, and
+ * SparseMatrix::gadget_decompose(b, k) + pad_rows(n) = r1cs_decomposed_square (r1cs.rs:172-185) from the system as stated over z.  With the three sections above a
+ * caller that builds its own relation cuts a table into digits, puts digits back together, bounds a norm and loads a system stated over z without the host.
+ *   Layout as everywhere in this header: coefficient form, 16 canonical little-endian words per element, AoS.  The device forms (spelled _device, as
+ * lfplus_mlsumcheck_begin_device is) take in / out / v as memory of the context's device under every rule of the "device-resident callers" section above (unmanaged
+ * memory of the context's device, ONE allocation covering every byte, 16-byte alignment, ordering by lfplus_ctx_wait_stream, return after the context's stream is
+ * synchronised); absmax stays a HOST pointer, as do the CSR arrays of lfplus_set_matrices_gadget.
+ *   Envelope: 1 <= count and count * k <= 2^28; 1 <= k <= 64; 2 <= b <= 2^62 (every intermediate of the digit rule then fits an int64; the centred value is below
+ * 2^63); layout 0 or 1; lfplus_linf_norm: 1 <= count <= 2^28; lfplus_set_matrices_gadget: n <= 2^32, nnz * k < 2^32 per matrix, nM <= 64, rows <= n, m * k == n.
+ *   Decompose: each of the 16 coefficients is centred to (-p/2, p/2), then k steps of the ONE digit rule of this slice are taken (lfp::digit_step on the device,
+ * lfp_balanced_digits in the oracle: the division truncates, a remainder with |rem| <= b/2 is kept, a tie keeps the sign of the value; powers of two take the shift
+ * path, every other b the division path) and each digit is written as its canonical residue.  A value that does not fit k digits loses what is left, as in the
+ * reference and in lfplus_witness_from_z: not an error.  Recompose: out[j] = sum_{i<k} b^i in[digit i of j], coefficient by coefficient mod p, for GENERAL ring
+ * elements in every slot (the k powers are computed once on the host); every output word is the canonical value of the exact sum.  It inverts decompose exactly
+ * when the value fitted.  lfplus_linf_norm: *absmax = the largest |centred coefficient| over count * 16 words (centred as for the relation checks, which run the
+ * same kernel).
+ *   lfplus_set_matrices_gadget: nM matrices of rows x m (CSR, ring coefficients, 16 words per non-zero: the system as stated over z) become the context's resident
+ * matrices exactly as after lfplus_set_matrices(ctx, n, nM, pad_rows(gadget_decompose(M_q, b, k), n)): the coefficient c at (r, j) becomes c b^i mod p at
+ * (r, j k + i), rows from `rows` on are empty.  Only the short CSR arrays and the short column counts cross PCIe (a k-th of the data; no host product); the device
+ * expands them into the complete resident matrix, the transposed structure lfplus_spmv_t reads and the constant-coefficient copies included, and every later call
+ * takes the result unchanged: lfplus_spmv, lfplus_spmv_t, lfplus_r1cs_linearize, lfplus_ccs_*, the checks, and the provers through lfplus_share_matrices (the
+ * set is reference-counted like any other).  nM == 0 drops the matrices, as lfplus_set_matrices does.  The CSR arrays are validated as lfplus_set_matrices
+ * validates them; on ANY failure the matrices that were resident before stay resident.
+ *   Independence, as lfplus_mlsumcheck_*: the six array calls run on a bare context (no matrix and no witness), and on a loaded one they neither read nor write the
+ * resident witness, the lfplus_rg_from_f results, a pending lfplus_rg_from_f_async pass, the resident matrices or an active generic sumcheck.  Inputs are never written.
+ *   Refusals, every one LFPLUS_E_ARG with a message in lfplus_last_error, in this order: a NULL context (tested before any device is touched: the answer on a
+ * machine without a GPU as well); a NULL array; anything outside the envelope; a sharded context (a transport or lfplus_set_sharding_model); out overlapping in in
+ * any way, with nothing launched (both maps permute); [_device: the pointer checks;] a word >= p in an O(n) input.  The O(n) words are tested on the device by the
+ * kernel that reads them and the flag comes home before the call returns: a host out (or *absmax) is written only when it is down and stays untouched otherwise,
+ * a device out is undefined then.  After any refusal the context is usable and nothing resident has changed.
+ *   Not built: sharded contexts; an int8 output form of the digits (lfplus_rg_read returns the exponent digits of the range check); exp() of digits to dense
+ * monomials; a prover constructor that takes the short system (lfplus_prover_create after lfplus_set_matrices_gadget and lfplus_share_matrices already serves it:
+ * the prover's contexts share what the first one holds). */
+#define LFPLUS_DIGITS_GADGET 0  /* digit i of element j at out[j k + i]: Vec<R>::gadget_decompose(b, k) = what lfplus_witness_from_z makes resident */
+#define LFPLUS_DIGITS_PLANES 1  /* digit i of element j at out[i count + j]: decompose_to_vec(b, k).transpose() = F_0, F_1 of lfplus_decompose; D_f order of lfplus_rg_read */
+int lfplus_balanced_decompose(lfplus_ctx *ctx, const uint64_t *in /* count */, uint64_t count, uint64_t b, uint32_t k, int layout, uint64_t *out /* count k */);
+int lfplus_balanced_decompose_device(lfplus_ctx *ctx, const uint64_t *in /* count */, uint64_t count, uint64_t b, uint32_t k, int layout, uint64_t *out /* count k */);
+int lfplus_balanced_recompose(lfplus_ctx *ctx, const uint64_t *in /* count k GENERAL ring elements */, uint64_t count, uint64_t b, uint32_t k, int layout,
+                              uint64_t *out /* count */);
+int lfplus_balanced_recompose_device(lfplus_ctx *ctx, const uint64_t *in /* count k GENERAL ring elements */, uint64_t count, uint64_t b, uint32_t k, int layout,
+                                     uint64_t *out /* count */);
+int lfplus_linf_norm(lfplus_ctx *ctx, const uint64_t *v, uint64_t count, uint64_t *absmax /* host */);
+int lfplus_linf_norm_device(lfplus_ctx *ctx, const uint64_t *v /* device */, uint64_t count, uint64_t *absmax /* host */);
+int lfplus_set_matrices_gadget(lfplus_ctx *ctx, uint64_t rows, uint64_t m, uint64_t b, uint32_t k, uint64_t n, uint32_t nM, const uint32_t *const *rowptr,
+                               const uint32_t *const *col, const uint64_t *const *val);
+
 /* ---- committed CCS instances: the linearization of ANY constraint shape sum_i c_i prod_{j in S_i} (M_j f) = 0 as a protocol step of its own, with its own round
  * kernel (lfp_ccs.hip).  The reference has none (its README lists "Support CCS" as the next step of latticefold-plus): this is ComR1CS::linearize /
  * ComR1CSProof::verify (src/r1cs.rs:72-163) generalised in the only way that leaves the R1CS case untouched -- SELF-CONSISTENT, PINNED TO THE REFERENCE AT THE

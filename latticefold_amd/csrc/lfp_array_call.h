@@ -1,5 +1,5 @@
 // lfp_array_call.h -- what the host bodies of the calls on caller-owned arrays share (lfp_ring_ops.cpp: lfplus_ring_mul / lfplus_spmv; lfp_tables.cpp: lfplus_build_eq,
-// lfplus_mle_eval_batch, lfplus_mle_fix_variables, lfplus_spmv_t): the overlap test, the call's scratch, the way out after a failure inside the enqueued part
+// lfplus_mle_eval_batch, lfplus_mle_fix_variables, lfplus_spmv_t; lfp_digits.cpp: lfplus_balanced_decompose / _recompose, lfplus_linf_norm): the overlap test, the call's scratch, the way out after a failure inside the enqueued part
 #pragma once
 #include <string>
 #include <vector>

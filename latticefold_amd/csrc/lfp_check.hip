@@ -4,24 +4,13 @@
 //                    non-zero residual (one atomicMin per wave that holds one; a satisfied system issues none)
 //   k_ccs_residual   the same for a CCS shape (lfplus_ccs_check): sum_i c_i prod_{j in S_i} (M_j f) row by row, fused, the t gathered elements in registers
 //   k_linb_dots      one pass over f: up to 8 ring-valued inner products <f, w_t> against SCALAR weight vectors (eq(r_pt), M_j^T eq(r_pt)) and the centred absmax
-//   k_absmax         the centred absmax alone (the R1CS check, and the LinB check when it runs on tables)
+//   (the centred absmax alone -- the R1CS check, and the LinB check when it runs on tables -- is k_absmax of lfp_digits.hip, which lfplus_linf_norm shares)
 // HBM-bound integer work; no MFMA.  Results cross to the host in one download of the result words (lfp_check.cpp).
 #include "lfp_kernels.h"
 #include "lfp_dev.cuh"
 
 namespace lfp {
 static inline size_t cdiv(size_t a, size_t b) { return (a + b - 1) / b; }
-
-// |centred w| for a canonical word: w if w <= (p - 1) / 2, else p - w
-__device__ __forceinline__ u64 abs_centred(u64 w) { return w <= (P - 1) / 2 ? w : P - w; }
-// the wave's maximum -> one vector atomicMax on a 64-bit word (skipped when it cannot raise a zero-initialised word)
-__device__ __forceinline__ void wave_atomic_max(u64 v, u64 *dst) {
-    for (int o = 32; o; o >>= 1) {
-        const u64 x = __shfl_xor(v, o);
-        v = x > v ? x : v;
-    }
-    if ((threadIdx.x & 63) == 0 && v) atomicMax((unsigned long long *)dst, (unsigned long long)v);
-}
 
 // coefficient t of (M f)[row] for the 16 lanes of a row group (lane t), canonical.  Constant-coefficient matrices (vals: ONE Montgomery word per non-zero,
 // LfpMatrix::valMc): the scalar x element path of k_spmv_ring_const, the whole row as one lazy sum; ring coefficients (16 Montgomery words per non-zero): the
@@ -173,17 +162,4 @@ void launch_linb_dots(const u64 *f, size_t n, const u64 *w, size_t ldw, u32 nw, 
     launch_sum_parts(part, ch, (size_t)nw * 16, nw * 16, out, s);
 }
 
-__global__ void __launch_bounds__(256) k_absmax(const u64 *x, size_t words, u64 *absmax) {
-    u64 mx = 0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) {
-        const u64 a = abs_centred(x[i]);
-        mx = a > mx ? a : mx;
-    }
-    wave_atomic_max(mx, absmax);
-}
-void launch_absmax(const u64 *x, size_t words, u64 *absmax, hipStream_t s) {
-    size_t b = cdiv(words, 256 * 8);
-    b = b < 1 ? 1 : (b > 2048 ? 2048 : b);
-    hipLaunchKernelGGL(k_absmax, dim3((unsigned)b), dim3(256), 0, s, x, words, absmax);
-}
 }  // namespace lfp

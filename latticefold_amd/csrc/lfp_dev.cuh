@@ -1,5 +1,5 @@
-// lfp_dev.cuh -- device helpers shared by the kernel files of the LatticeFold+ slice (lfp_kernels.hip, lfp_ingest.hip): the balanced digit rule,
-// centred representatives, the word-wise reduction mod p and the block-level sum over the 16 row lanes
+// lfp_dev.cuh -- device helpers shared by the kernel files of the LatticeFold+ slice (lfp_kernels.hip, lfp_ingest.hip, lfp_check.hip, lfp_digits.hip): the balanced
+// digit rule, centred representatives and their wave-wide maximum, the word-wise reduction mod p and the block-level sum over the 16 row lanes
 #pragma once
 #include "lfp_field.cuh"
 namespace lfp {
@@ -25,6 +25,16 @@ __device__ __forceinline__ int64_t digit_step(int64_t &cur, u64 b, int sh) {
     return rem;
 }
 __device__ __forceinline__ int64_t centre(u64 v) { return v <= (P - 1) / 2 ? (int64_t)v : -(int64_t)(P - v); }
+// |centred w| for a canonical word: w if w <= (p - 1) / 2, else p - w
+__device__ __forceinline__ u64 abs_centred(u64 w) { return w <= (P - 1) / 2 ? w : P - w; }
+// the wave's maximum -> one vector atomicMax on a 64-bit word (skipped when it cannot raise a zero-initialised word)
+__device__ __forceinline__ void wave_atomic_max(u64 v, u64 *dst) {
+    for (int o = 32; o; o >>= 1) {
+        const u64 x = __shfl_xor(v, o);
+        v = x > v ? x : v;
+    }
+    if ((threadIdx.x & 63) == 0 && v) atomicMax((unsigned long long *)dst, (unsigned long long)v);
+}
 
 // sum over the 16 row lanes (tid >> 4) of a value mod p held by thread (jl, t): two 16-lane shuffles inside each wave, LDS across waves;
 // valid in threads tid < 16

@@ -190,7 +190,25 @@ void launch_r1cs_residual(const u32 *const *rowptr, const u32 *const *col, const
 // out[q][16] = sum_row w[q ldw + row] f[row] for q < nw, nw in {2, 4, 8} (w: SCALAR weights, Montgomery; out canonical) in one pass over f; absmax (may be null):
 // *absmax = max(*absmax, largest |centred word| of f).  part: eval_chunks(n) * nw * 16 words
 void launch_linb_dots(const u64 *f, size_t n, const u64 *w, size_t ldw, u32 nw, u64 *part, u64 *out, u64 *absmax, hipStream_t s);
-void launch_absmax(const u64 *x, size_t words, u64 *absmax, hipStream_t s);
+// *absmax = max(*absmax, largest |centred word| of x); flag (may be null): *flag |= 1 if a word is not canonical (lfp_digits.hip: the relation checks and lfplus_linf_norm)
+void launch_absmax(const u64 *x, size_t words, u64 *absmax, hipStream_t s, u32 *flag = nullptr);
+// ---- gadget maps on arrays (lfp_digits.hip; lfplus_balanced_decompose / _recompose, lfplus_set_matrices_gadget).  Arrays are [element][16] canonical words; digit i
+// of element j sits at element j k + i (layout 0: gadget order) or i count + j (layout 1: planes).  blocks = digit_blocks(words, cap): 256 words each and pass
+struct DigitPows { u64 pM[64]; };      // b^i 2^64 mod p for i < k
+u32 digit_blocks(u64 words, u32 cap);
+// out: the k balanced base-b digits (digit_step) of every centred word of in; *flag |= 1: a word >= p
+void launch_digits_decompose(const u64 *in, u64 count, u64 b, u32 k, int layout, u64 *out, u32 *flag, u32 blocks, hipStream_t s);
+// out[j] = sum_{i < k} b^i in[digit i of j], word by word mod p (in: general canonical words); *flag |= 1: a word >= p
+void launch_digits_recompose(const u64 *in, u64 count, u32 k, int layout, const DigitPows &pw, u64 *out, u32 *flag, u32 blocks, hipStream_t s);
+// The gadget form of a short CSR matrix (rows x m, nnz entries e with ring coefficients val[e][16], canonical) as a complete n x n LfpMatrix, n = m k: entry e at
+// (r, j) becomes the k entries e k + i at (r, j k + i) with val b^i.  rowptr_s has rows + 1 entries, colptr_s (the short column pointers) m + 1.
+// perm[pos] = the CSR index of the entry at position pos of the short CSC order (column-major, rows ascending): launch_gadget_perm, a stable sort of the entries by
+// column (tmp: gadget_perm_bytes(nnz, m) bytes)
+size_t gadget_perm_bytes(u64 nnz, u64 m);
+hipError_t launch_gadget_perm(const u32 *col_s, u64 nnz, u64 m, u32 *perm, void *tmp, size_t tmp_bytes, hipStream_t s);
+struct GadgetOut { u32 *rowptr, *col, *colptr, *rowidx; u64 *valM, *valT, *valMc, *valTc; };      // valMc / valTc null: not a constant-coefficient matrix
+void launch_gadget_expand(const u32 *rowptr_s, const u32 *col_s, const u64 *val_s, const u32 *colptr_s, const u32 *perm, u64 rows, u64 m, u64 n, u64 nnz, u32 k,
+                          const DigitPows &pw, const GadgetOut &o, hipStream_t s);
 void launch_vec_add(u64 *acc, const u64 *x, size_t n, hipStream_t s);
 void launch_check_canonical(const u64 *x /* 16-byte aligned */, size_t n, u32 *flag, u32 bit, hipStream_t s);
 // dst = src (`words` words, a multiple of 16; both 16-byte aligned, not overlapping) and *flag |= bit if a word is not canonical: one pass (k_copy_checked)

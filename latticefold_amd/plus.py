@@ -31,6 +31,7 @@ REL_CM, REL_R1CS, REL_V, REL_NORM = 1, 2, 4, 8      # lfplus.h LFPLUS_REL_*: the
 REL_CCS = 2                                         # the row-wise residual of lfplus_ccs_check: the bit of REL_R1CS
 ABSENT = -128     # exponent digit of a zero entry of a monomial set (lfplus.h LFPLUS_ABSENT)
 MUL_ELEMENTWISE, MUL_BROADCAST = 0, 1      # lfplus.h LFPLUS_MUL_*: the modes of lfplus_ring_mul
+DIGITS_GADGET, DIGITS_PLANES = 0, 1        # lfplus.h LFPLUS_DIGITS_*: the layouts of lfplus_balanced_decompose / lfplus_balanced_recompose
 
 
 class VPolyDesc(C.Structure):
@@ -147,6 +148,14 @@ def _lib():
         L.lfplus_mle_fix_variables_device.argtypes = [vp, vp, C.c_uint32, C.c_uint64, u64p, C.c_uint32, vp]
         L.lfplus_spmv_t.argtypes = [vp, C.c_uint32, u64p, C.c_uint64, u64p]
         L.lfplus_spmv_t_device.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp]
+        # gadget maps on arrays (the _device forms: in, out and v are device addresses; absmax and the CSR arrays stay host pointers)
+        L.lfplus_balanced_decompose.argtypes = [vp, u64p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, u64p]
+        L.lfplus_balanced_decompose_device.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, vp]
+        L.lfplus_balanced_recompose.argtypes = [vp, u64p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, u64p]
+        L.lfplus_balanced_recompose_device.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, vp]
+        L.lfplus_linf_norm.argtypes = [vp, u64p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.lfplus_linf_norm_device.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.lfplus_set_matrices_gadget.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, u32pp, u32pp, u64pp]
         # committed CCS instances (lfplus_ccs_*)
         cp = C.POINTER(CCSDesc)
         L.lfplus_ccs_linearize.argtypes = [vp, vp, cp, u32pp, u32pp, u64pp, u64p, u64p, u64p]
@@ -536,6 +545,65 @@ class PlusContext:
             raise LfPlusError(E_ARG, "spmv_t: out is a contiguous uint64 array")
         self._chk(_lib().lfplus_spmv_t(self.h, int(j), pv, n, out.ctypes.data_as(u64p)))
         return out
+
+    def _digits(self, name, x, nin, nout, b, k, layout, out):
+        """the body of balanced_decompose / balanced_recompose: x (nin, 16) -> out (nout, 16) in the memory space of x"""
+        if len(tuple(x.shape)) != 2 or x.shape[1] != D or x.shape[0] != nin:
+            raise LfPlusError(E_ARG, f"{name}: the input is ({nin}, 16)")
+        dev = api.is_device_array(x)
+        if out is not None and (api.is_device_array(out) != dev or tuple(out.shape) != (nout, D)):
+            raise LfPlusError(E_ARG, f"{name}: out is ({nout}, 16) in the memory space of the input")
+        count = min(nin, nout)
+        if dev:
+            if out is None:
+                out = x.new_empty((nout, D))
+            pi, po = _dev(x), _dev(out)
+            self.wait_stream()
+            self._chk(getattr(_lib(), f"lfplus_{name}_device")(self.h, pi, count, int(b), int(k), int(layout), po))
+            return out
+        x, pi = _w(x)
+        if out is None:
+            out = np.zeros((nout, D), dtype=np.uint64)
+        elif out.dtype != np.uint64 or not out.flags["C_CONTIGUOUS"]:
+            raise LfPlusError(E_ARG, f"{name}: out is a contiguous uint64 array")
+        self._chk(getattr(_lib(), f"lfplus_{name}")(self.h, pi, count, int(b), int(k), int(layout), out.ctypes.data_as(u64p)))
+        return out
+
+    def balanced_decompose(self, x, b, k, layout=DIGITS_GADGET, out=None):
+        """lfplus_balanced_decompose: the k balanced base-b digits of every coefficient of x (count, 16), as canonical residues -> (count k, 16): digit i of element
+        j at row j k + i (DIGITS_GADGET: Vec<R>::gadget_decompose) or i count + j (DIGITS_PLANES: decompose_to_vec(b, k).transpose()); a numpy array or a device
+        array (lfplus_balanced_decompose_device), out in the memory space of x"""
+        return self._digits("balanced_decompose", x, x.shape[0], x.shape[0] * int(k), b, k, layout, out)
+
+    def balanced_recompose(self, x, b, k, layout=DIGITS_GADGET, out=None):
+        """lfplus_balanced_recompose: out[j] = sum_i b^i x[digit i of j] coefficient by coefficient mod p, x (count k, 16) GENERAL ring elements -> (count, 16)"""
+        if int(k) < 1 or x.shape[0] % int(k):
+            raise LfPlusError(E_ARG, "balanced_recompose: the input is (count k, 16)")
+        return self._digits("balanced_recompose", x, x.shape[0], x.shape[0] // int(k), b, k, layout, out)
+
+    def linf_norm(self, v):
+        """lfplus_linf_norm: the largest |centred coefficient| of v (count, 16), a numpy array or a device array (lfplus_linf_norm_device) -> int"""
+        if len(tuple(v.shape)) != 2 or v.shape[1] != D:
+            raise LfPlusError(E_ARG, "linf_norm: v is (count, 16)")
+        am = C.c_uint64()
+        if api.is_device_array(v):
+            pv = _dev(v)
+            self.wait_stream()
+            self._chk(_lib().lfplus_linf_norm_device(self.h, pv, v.shape[0], C.byref(am)))
+        else:
+            v, pv = _w(v)
+            self._chk(_lib().lfplus_linf_norm(self.h, pv, v.shape[0], C.byref(am)))
+        return am.value
+
+    def set_matrices_gadget(self, M, m, b, k, n=None):
+        """lfplus_set_matrices_gadget: the system as stated over z -- CSR triples of rows x m with ring coefficients -- made resident in its gadget form over
+        f = gadget_decompose(z, b, k), n = m k: what set_matrices(r1cs_decomposed_square(M, n, b, k)) leaves, expanded on the device from the short arrays"""
+        keep, rp, cp, vp = _csr_args(M)
+        rows = keep[0][0].size - 1 if keep else 0
+        if any(r.size - 1 != rows for r, _, _ in keep):
+            raise LfPlusError(E_ARG, "set_matrices_gadget: the matrices have the same number of rows")
+        self._chk(_lib().lfplus_set_matrices_gadget(self.h, rows, int(m), int(b), int(k), int(n) if n is not None else int(m) * int(k), len(M), rp, cp, vp))
+        self._nres = len(M)
 
     def _cm_arg(self, cm_f):
         if cm_f is None:
